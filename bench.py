@@ -7,7 +7,7 @@ channelizer (configs[1]); roofline = algorithmic HBM bytes (B_al
 
 A "step" is one pass of the hot path (overlap-save gather -> forward FFT -> fused per-channel
 slice/window/IFFT/discard) over one batch of device-resident synthetic multicarrier input.
-  python bench.py [--gpus N --steps K --warmup W] [--config 2|3|4|5]
+  python bench.py [--gpus N --steps K --warmup W] [--config 2|3|4|5] [--dump-outputs DIR]
 
 --config picks the BASELINE.json workload (numbered as SURVEY.md §8d does, cfgK = configs[K-1]):
   1            configs[0]: the example flowgraph's plan (4096-pt FFT, 4 channels of l = 256/512/1024/512), a mixed plan on
@@ -107,7 +107,15 @@ def parse():
     ap.add_argument("--sparse", type=int, default=0, metavar="K", help="diagnostics (config 2): K channels (widths 256 ... 2048 in turn) spread "
                                                                        "over the band instead of a plan that tiles it (spectrum path)")
     ap.add_argument("--sparse-widths", default="256,512,1024,2048", help="--sparse: the channel widths in turn (bins, powers of two)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most "
+                         "64 MB: a fixed, seeded sample of the blocks of a larger output); same arguments, same inputs, so two builds "
+                         "can be compared output for output (rank 0)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.warmup < 0:
+        ap.error("--warmup must not be negative")
     if a.sparse and a.config != 2:
         ap.error("--sparse applies to --config 2 only")
     if a.offset and a.config not in (2, 4):
@@ -393,6 +401,76 @@ def verify_last_launch(torch, np, a, pipe, ring, out, plan, params, N, R, nb, fi
     err = max(worst_l2, worst_mx)
     return {"blocks": len(blocks), "block_indices": blocks, "channels": len(chans), "max_rel_err": err, "tolerance": 1e-5,
             "what": "output of the last timed launch vs the oracle on the ring it read (max over rel. L2 and max-abs/max per block and channel)"}
+
+
+DUMP_BYTES = 60_000_000        # --dump-outputs: everything written, at most (under 64 MB however MB is counted)
+PDU_FIELDS = ("kind", "source", "chan_id", "finalized", "part", "has_part", "rel_bw", "rel_cfreq", "blockstart", "blockend",
+              "vectorstart", "vectorend", "nsamples", "payload_len")
+
+
+def dump_pipeline_outputs(torch, np, path, pipe, out, params, nb):
+    """--dump-outputs, configs 1/2/4: the channel outputs the last timed launch wrote (what fdc_pipeline_process_device hands its caller).
+    blocks.npy: the step's block indices kept (all of them, or block 0, block nb-1 and a seeded random set, as many as fit in the budget);
+    channels.npy: float32 [block, sample, re/im], every channel's lout samples of that block one behind the other in plan order;
+    channel_columns.npy: float64 [channel, (first column, lout)] into the sample axis."""
+    louts = [int(p_[2]) for p_ in params]
+    row = sum(louts)
+    k = max(1, min(nb, (DUMP_BYTES - 1_000_000) // (8 * row + 8)))
+    if k == nb:
+        blocks = np.arange(nb)
+    else:
+        rng = np.random.default_rng(20251015)
+        blocks = np.sort(np.concatenate([[0, nb - 1], rng.choice(np.arange(1, nb - 1), size=k - 2, replace=False)])) if k > 2 else np.array([0, nb - 1][:k])
+    assert all(0 <= pipe.channel_offset(c, nb) and pipe.channel_offset(c, nb) + nb * lo <= out.numel() for c, lo in enumerate(louts))
+    dev = out.device
+    idx = torch.cat([pipe.channel_offset(c, nb) + torch.arange(lo, device=dev, dtype=torch.int64)[None, :] +
+                     torch.as_tensor(blocks, device=dev, dtype=torch.int64)[:, None] * lo for c, lo in enumerate(louts)], dim=1)
+    vals = torch.view_as_real(out[idx.reshape(-1)]).reshape(len(blocks), row, 2).cpu().numpy().astype(np.float32)
+    cols = np.array([[sum(louts[:c]), lo] for c, lo in enumerate(louts)], dtype=np.float64)
+    np.save(os.path.join(path, "blocks.npy"), blocks.astype(np.float64))
+    np.save(os.path.join(path, "channels.npy"), vals)
+    np.save(os.path.join(path, "channel_columns.npy"), cols)
+
+
+def dump_sink_outputs(np, path, sinks, batch_first):
+    """--dump-outputs, configs 3/5: the PDUs of the last timed step's batch (what the bank hands its caller after the region's flush).
+    pdus.npy: float64 [pdu, field] with the fields PDU_FIELDS; the bank's counters do not show the running-in, whose length is timed:
+    block numbers are relative to the first block of that batch, chan_id (an activation / detection counter) to the smallest chan_id of
+    the same kind and source among these PDUs; payload.npy: float32 [sample, re/im], the PDUs' payloads one behind the other
+    in the order of pdus.npy (if they exceed the budget: a seeded random set of whole PDUs, the others with payload_len 0)."""
+    import ctypes as ct
+    got = sinks.pdus()
+    if sinks.device_payload and sinks.engine() == 1:       # payloads in device memory: (address, samples); the region's fence has run
+        hip = ct.CDLL("libamdhip64.so")
+        hip.hipMemcpy.argtypes = [ct.c_void_p, ct.c_void_p, ct.c_size_t, ct.c_int]
+        host = []
+        for meta, (addr, n) in got:
+            buf = np.zeros(n, np.complex64)
+            if n > 0 and hip.hipMemcpy(buf.ctypes.data, addr, 8 * n, 2) != 0:        # 2 = hipMemcpyDeviceToHost
+                raise RuntimeError("--dump-outputs: hipMemcpy of a PDU payload failed")
+            host.append((meta, buf))
+        got = host
+    key = lambda m: (m["kind"], m["source"], m["chan_id"], m["blockstart"], m["blockend"], m["vectorstart"], m["vectorend"], m["part"])
+    got.sort(key=lambda md: key(md[0]))
+    id0 = {}
+    for m, _d in got:
+        id0[(m["kind"], m["source"])] = min(id0.get((m["kind"], m["source"]), m["chan_id"]), m["chan_id"])
+    keep = np.ones(len(got), bool)
+    total = sum(d.size for _m, d in got)
+    if 8 * total > DUMP_BYTES - 1_000_000:
+        keep[:] = False
+        budget = (DUMP_BYTES - 1_000_000) // 8
+        for i in np.random.default_rng(20251015).permutation(len(got)):
+            if got[i][1].size <= budget:
+                keep[i] = True
+                budget -= got[i][1].size
+    rows = [[m["kind"], m["source"], m["chan_id"] - id0[(m["kind"], m["source"])], int(m["finalized"]), m["part"], int(m["has_part"]), m["rel_bw"], m["rel_cfreq"],
+             m["blockstart"] - batch_first, m["blockend"] - batch_first, m["vectorstart"], m["vectorend"], d.size,
+             d.size if k else 0] for (m, d), k in zip(got, keep)]
+    np.save(os.path.join(path, "pdus.npy"), np.array(rows, dtype=np.float64).reshape(len(rows), len(PDU_FIELDS)))
+    pay = [d for (_m, d), k in zip(got, keep) if k]
+    np.save(os.path.join(path, "payload.npy"),
+            np.concatenate(pay).view(np.float32).reshape(-1, 2) if pay else np.zeros((0, 2), np.float32))
 
 
 def host_entry_leg(G, np, N, R, plan, sum_lout, devices, blocks_per_member):
@@ -742,6 +820,9 @@ def main():
             step()
         torch.cuda.synchronize()
         nsettle += 8
+    # the ring rotation starts over here: how many running-in steps fit into settle_ms varies, the ring the last timed step reads must not
+    if sinks is None:
+        turn[0] = 0
     for _ in range(a.warmup):
         step()
     if sinks is not None:
@@ -772,6 +853,14 @@ def main():
         t = mine.clone()
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+
+    # --dump-outputs: what the last timed step computed, read back before anything below reuses the buffers (not timed)
+    if a.dump_outputs and rank == 0:
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        if sinks is None:
+            dump_pipeline_outputs(torch, np, a.dump_outputs, pipe, out, params, nb)
+        else:
+            dump_sink_outputs(np, a.dump_outputs, sinks, (nsettle + a.warmup + a.steps - 1) * nb)
 
     # The line certifies itself: blocks of the LAST timed launch's output (first, last and random ones; every 16th channel) and the
     # matching piece of the input ring it read go to the host and through the oracle (the checker; nothing of it is timed).

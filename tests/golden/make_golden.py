@@ -5,6 +5,7 @@ by oracle/Makefile) for the window tables.
 Fixtures are DATA (inputs + expected outputs):
   windows_ref.npz      tables produced by the reference's own cr_win (lib/windows.h:41-78), unmodified,
                        through oracle/ref_windows_driver.cpp.
+  windows_ref_seeded.npz  the same, on 60 seeded random parameter sets (SEEDED_WINDOW_CASES).
   channel_params.json  NOT made here: tests/golden/make_params_from_reference.py produces it by running the
                        reference's own get_opt_channelparams / frequency-mode lambdas.
   chain_numpy.npz      the throughput chain evaluated with numpy.fft in
@@ -39,6 +40,25 @@ def make_windows():
         d["case%02d" % i] = O.ref_window(t, l, np.float32(p), np.float32(s), R)
     d["params"] = np.array(WINDOW_CASES, dtype=np.float64)
     np.savez_compressed(os.path.join(HERE, "windows_ref.npz"), **d)
+
+
+def SEEDED_WINDOW_CASES():
+    """60 random (wintype, l, passbw, stopbw, R), seed 7; passbw/stopbw are float32."""
+    rng = np.random.default_rng(7)
+    cases = []
+    for _ in range(60):
+        t = int(rng.integers(0, 3)); l = int(2 ** rng.integers(1, 12)); R = int(2 ** rng.integers(1, 4))
+        p = np.float32(rng.uniform(0.05, 1.1)); s = np.float32(p + rng.uniform(0, 0.5))
+        cases.append((t, l, p, s, R))
+    return cases
+
+
+def make_windows_seeded():
+    assert O.have_ref(), "oracle/_ref missing: run `make -C oracle` with /root/reference present"
+    cases = SEEDED_WINDOW_CASES()
+    d = {"case%02d" % i: O.ref_window(t, l, p, s, R) for i, (t, l, p, s, R) in enumerate(cases)}
+    d["params"] = np.array(cases, dtype=np.float64)      # float32 passbw/stopbw are exact in float64
+    np.savez_compressed(os.path.join(HERE, "windows_ref_seeded.npz"), **d)
 
 
 def multicarrier(N, chans, nsamp, seed, noise=0.1):
@@ -122,6 +142,7 @@ def make_sink_known_answers():
 
 if __name__ == "__main__":
     make_windows()
-        make_chain()
+    make_windows_seeded()
+    make_chain()
     make_sink_known_answers()
     print("fixtures written to", HERE)

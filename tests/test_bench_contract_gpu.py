@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -93,3 +94,28 @@ def test_bench_two_ranks_rehearsal_on_one_gpu():
     d = _line(["--gpus", "2", "--steps", "3", "--warmup", "1", "--blocks", "256", "--no-cpu-baseline"],
               env={"FDC_BENCH_REHEARSE": "1"})
     assert d["n_gpus"] == 2 and d["config"]["parallelism"].startswith("block-span sharding x2") and d["value"] > 1e3
+
+
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs: the last timed step's outputs as .npy (float32 / float64, at most 64 MB), the same arrays from two runs with the
+    same arguments (the inputs are seeded; the ring the last step reads does not depend on the running-in), for a pipeline and a sink config."""
+    args = ["--blocks", "128", "--steps", "7", "--warmup", "2", "--no-cpu-baseline", "--no-end-to-end"]
+    runs = []
+    for k in range(2):
+        d = _line(args + ["--dump-outputs", str(tmp_path / ("p%d" % k))])
+        assert d["steps"] == 7 and d["ms_per_step"] > 0 and d["verified"]["max_rel_err"] <= 1e-5
+        runs.append({f: np.load(tmp_path / ("p%d" % k) / f) for f in sorted(os.listdir(tmp_path / ("p%d" % k)))})
+    a, b = runs
+    assert sorted(a) == ["blocks.npy", "channel_columns.npy", "channels.npy"]
+    assert sum(v.nbytes for v in a.values()) <= 64_000_000 and all(v.dtype in (np.float32, np.float64) for v in a.values())
+    ch, cols = a["channels.npy"], a["channel_columns.npy"]
+    assert ch.shape == (128, 256 * 128, 2) and (a["blocks.npy"] == np.arange(128)).all()
+    assert cols.shape == (256, 2) and (cols[:, 1] == 128).all() and np.abs(ch).max() > 0
+    for f in a:
+        assert a[f].shape == b[f].shape and (a[f].view(np.uint32 if a[f].dtype == np.float32 else np.uint64) ==
+                                             b[f].view(np.uint32 if b[f].dtype == np.float32 else np.uint64)).all(), f
+    d = _line(["--config", "3", "--blocks", "256", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-end-to-end",
+               "--dump-outputs", str(tmp_path / "s")])
+    pdus, pay = np.load(tmp_path / "s" / "pdus.npy"), np.load(tmp_path / "s" / "payload.npy")
+    assert pdus.dtype == np.float64 and pdus.shape[1] == 14 and pdus.shape[0] > 0
+    assert pay.dtype == np.float32 and pay.shape == (int(pdus[:, 13].sum()), 2) and (pdus[:, 12] == pdus[:, 13]).all()

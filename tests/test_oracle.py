@@ -21,15 +21,20 @@ def test_window_tables_bit_exact_vs_reference_fixture(oracle, golden_dir):
         assert (w.view(np.uint32) == ref.view(np.uint32)).all(), "case %d" % i
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/lib/windows.h"), reason="reference not mounted")
-def test_window_tables_vs_live_reference_build(oracle):
-    """When /root/reference is present: compare with oracle/_ref built from it, more parameter sets."""
+def test_window_tables_vs_live_reference_build(oracle, golden_dir):
+    """60 seeded parameter sets: fdco_window == the reference's cr_win tables stored in windows_ref_seeded.npz
+    (tests/golden/make_golden.py), bit for bit; and == oracle/_ref as well when the build made it."""
+    z = np.load(os.path.join(golden_dir, "windows_ref_seeded.npz"))
     rng = np.random.default_rng(7)
-    for _ in range(60):
+    for i in range(60):
         t = int(rng.integers(0, 3)); l = int(2 ** rng.integers(1, 12)); R = int(2 ** rng.integers(1, 4))
         p = np.float32(rng.uniform(0.05, 1.1)); s = np.float32(p + rng.uniform(0, 0.5))
-        a = oracle.window(t, l, p, s, R); b = oracle.ref_window(t, l, p, s, R)
-        assert (a.view(np.uint32) == b.view(np.uint32)).all(), (t, l, p, s, R)
+        assert tuple(z["params"][i]) == (t, l, p, s, R), i
+        a = oracle.window(t, l, p, s, R); b = z["case%02d" % i]
+        assert a.shape == b.shape and (a.view(np.uint32) == b.view(np.uint32)).all(), (t, l, p, s, R)
+        if oracle.have_ref():
+            b = oracle.ref_window(t, l, p, s, R)
+            assert (a.view(np.uint32) == b.view(np.uint32)).all(), (t, l, p, s, R)
 
 
 def test_channel_params_vs_reference_fixture(oracle, golden_dir):
