@@ -67,6 +67,11 @@ class fdc_pdu(C.Structure):
                 ("vectorend", C.c_int64), ("nsamples", C.c_int64), ("samples", C.c_void_p), ("id", C.c_char * 72)]
 
 
+class fdc_waterfall_cfg(C.Structure):
+    _fields_ = [("blocklen", C.c_int32), ("blockdecimation", C.c_int32), ("loginput", C.c_int32),
+                ("minvaldb", C.c_double), ("maxvaldb", C.c_double), ("colorscheme", C.c_int32)]
+
+
 # every symbol include/fdc_amd.h declares: (restype, argtypes)
 _vp = C.c_void_p
 SYMBOLS = {
@@ -162,6 +167,18 @@ SYMBOLS = {
     "fdc_phase_window_destroy": (None, [_vp]),
     "fdc_window_table": (C.c_int, [C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int, _vp]),
     "fdc_fft_vcc": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp]),
+    "fdc_waterfall_check": (C.c_int, [C.POINTER(fdc_waterfall_cfg), C.POINTER(fdc_waterfall_cfg)]),
+    "fdc_waterfall_create": (C.c_int, [C.c_int, C.POINTER(fdc_waterfall_cfg), C.c_int32, C.POINTER(_vp)]),
+    "fdc_waterfall_destroy": (None, [_vp]),
+    "fdc_waterfall_reset": (None, [_vp]),
+    "fdc_waterfall_set_levels": (C.c_int, [_vp, C.c_double, C.c_double]),
+    "fdc_waterfall_set_colorscheme": (C.c_int, [_vp, C.c_int32]),
+    "fdc_waterfall_rows_done": (C.c_int64, [_vp]),
+    "fdc_waterfall_color_table": (C.c_int, [C.c_int32, _vp, _vp]),
+    "fdc_waterfall_edges": (C.c_int, [C.c_int32, C.c_double, C.c_double, _vp]),
+    "fdc_waterfall_work": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, _vp, C.c_int, C.POINTER(C.c_int32)]),
+    "fdc_pipeline_work_waterfall": (C.c_int, [_vp, _vp, _vp, C.c_int, C.POINTER(_vp), _vp, _vp, _vp, C.c_int,
+                                              C.POINTER(C.c_int32)]),
 }
 
 _lib = None

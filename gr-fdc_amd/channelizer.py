@@ -199,6 +199,23 @@ class Pipeline:
                                                    spec.ctypes.data if spec is not None else None))
         return (outs, spec) if want_spectrum else outs
 
+    def work_waterfall(self, x, waterfall):
+        """fdc_pipeline_work_waterfall: the channel outputs as work(), and the gr_fdc_amd.Waterfall rows this call finished (Rows of
+        mean power, colour index and RGB per pixel).  N = 4096 in one launch stays in one launch (path 5)."""
+        from .waterfall import Rows, WIDTH
+        x = np.ascontiguousarray(x, dtype=np.complex64)
+        if x.size % self.H:
+            raise ValueError("input must be a whole number of (N - N/R)-sample items")
+        nb = x.size // self.H
+        outs = [np.empty(nb * lo, dtype=np.complex64) for lo in self.lout]
+        ptrs = (C.c_void_p * max(1, len(outs)))(*[o.ctypes.data for o in outs])
+        cap = waterfall.rows_for(nb)
+        rows, idx, rgb = np.empty((cap, WIDTH), np.float32), np.empty((cap, WIDTH), np.uint16), np.empty((cap, WIDTH, 3), np.uint8)
+        n = C.c_int32(0)
+        _lib.check(_lib.lib().fdc_pipeline_work_waterfall(self._h, waterfall._h, x.ctypes.data, nb, ptrs, rows.ctypes.data, idx.ctypes.data,
+                                                          rgb.ctypes.data, cap, C.byref(n)))
+        return outs, Rows(rows[:n.value], idx[:n.value], rgb[:n.value])
+
     def flush_sinks(self, sinks):
         """fdc_pipeline_flush_sinks: the pipelined form (a bank made with lookahead=True) hands out the oldest batch still inside;
         returns its block count, 0 when nothing is left.  The PDUs are then the bank's current ones (sinks.pdus())."""
@@ -411,7 +428,7 @@ class FrequencyDomainChannelizer:
                  act_det_deactivation_delay, minchanflankpuffer, verbose,
                  pow_act_deactivation_delay,
                  pow_act_maxblocks, act_det_maxblocks,
-                 debug, device_id=0, max_blocks=64, devices=None, pipelined=False):
+                 debug, device_id=0, max_blocks=64, devices=None, pipelined=False, waterfall=None):
         # pipelined (not an argument of the reference): the sink blocks run beside the front end of the FOLLOWING work() calls, as the
         # thread-per-block scheduler runs them beside the FFT in the reference (fdc_pipeline_work_sinks on a look-ahead bank,
         # include/fdc_amd.h): same PDUs, handed out one or two work() calls later; flush() at the end of the stream
@@ -496,6 +513,15 @@ class FrequencyDomainChannelizer:
                                      device_id=devices[0] if devices else device_id,
                                      keep_spectrum=self.debug or self.sinks is not None)
         self.N_throughput_channelizers = len(self.channel_params)
+        # waterfall (not an argument of the reference, whose example flowgraph wires the spectrum to complex_to_mag_squared and
+        # FDC.WaterfallMsgTagging outside the hier block): a gr_fdc_amd.Waterfall fed from the spectrum on the device; work() then
+        # returns (ports, rows)
+        self.waterfall = waterfall
+        if waterfall is not None:
+            if not isinstance(self.pipeline, Pipeline) or self.sinks is not None or self.inpveclen != 1 or self.itemsize != 8 or self.debug:
+                raise ValueError("a waterfall needs a complex sample stream on one device, without sink blocks and without the debug port")
+            if waterfall.blocklen != self.blocksize or waterfall.max_items < int(max_blocks):
+                raise ValueError("the waterfall needs blocklen = blocksize and max_items >= max_blocks")
         self.messages = []          # PDUs published on "msgout" by the last work() call
 
     @staticmethod
@@ -544,6 +570,8 @@ class FrequencyDomainChannelizer:
             if self.sinks is not None:
                 raise ValueError("real input with sink blocks is not supported")
             res = self.pipeline.work_real(samples, want_spectrum=self.debug)
+        elif self.waterfall is not None:
+            return self.pipeline.work_waterfall(samples, self.waterfall)
         elif self.inpveclen == 1 and self.sinks is None:
             res = self.pipeline.work(samples, want_spectrum=self.debug)
         elif self.inpveclen == 1:

@@ -5,6 +5,7 @@
 #include "fdc_window.hpp"
 #include "fdc_guard.hpp"
 #include "fdc_plan_cost.hpp"
+#include "fdc_waterfall.hpp"
 
 #include <algorithm>
 #include <array>
@@ -229,6 +230,12 @@ struct fdc_pipeline {
     // the block whose spectrum starts at gpow_spec + k N go to gpow_base + k N / 16.  Set for the duration of one call.
     float *gpow_base = nullptr;
     const float2 *gpow_spec = nullptr;
+    // fdc_pipeline_work_waterfall: the row sums of the call's blocks go to wf_rows + (block - wf_first) * 1024 (path 5: the fused kernel's epilogue);
+    // wf_spec: the call writes the internal spectrum the rows are summed from (other paths), without keep_spectrum.  Set for the duration of one call.
+    float *wf_rows = nullptr;
+    int64_t wf_first = 0;
+    bool wf_spec = false;
+    std::string wf_route;        // the route of the last waterfall call (fdc_pipeline_describe)
     bool cfg_generic = false;    // FDC_FORCE_GENERIC=1: bypass the size-specialised kernels (A/B testing)
     // timing
     bool timing = false;
@@ -1118,6 +1125,7 @@ int32_t fdc_pipeline_describe(const fdc_pipeline *p, char *buf, int32_t n)
     } else {
         add("%s", "forward transform to a spectrum in memory + channel kernels");
     }
+    if (!p->wf_route.empty()) add("; waterfall rows: %s", p->wf_route.c_str());
     std::snprintf(buf, (size_t)n, "%s", t);
     return k;
 }
@@ -1271,7 +1279,7 @@ int fdc_pipeline_process_device(fdc_pipeline *p, const void *d_ring, int64_t fir
     if (nblocks < 0 || first_block < 0) return fail(FDC_ERR_INVALID_ARGUMENT, "negative block count/index");
     if (nblocks == 0) return FDC_OK;
     if (!d_ring || (p->C > 0 && !d_out)) return fail(FDC_ERR_INVALID_ARGUMENT, "null device buffer");
-    if (d_spectrum && !p->cfg.keep_spectrum) return fail(FDC_ERR_INVALID_ARGUMENT, "spectrum output needs keep_spectrum");
+    if (d_spectrum && !p->cfg.keep_spectrum && !p->wf_spec) return fail(FDC_ERR_INVALID_ARGUMENT, "spectrum output needs keep_spectrum");
     // one call produces less than 4 GiB (32-bit output offsets; checked for max_blocks at create): a longer call is refused, not sent down
     // a path whose internal spectrum may be partial (a split plan's remainder-only spectrum under the channel kernels of ALL channels)
     if ((int64_t)nblocks * p->sum_lout * 8 > 0xFFFFF000ll)
@@ -1303,7 +1311,8 @@ int fdc_pipeline_process_device(fdc_pipeline *p, const void *d_ring, int64_t fir
         if (p->fused && !d_spectrum) {
             // N = 4096: one launch, nothing but the input samples and the output samples crosses the memory interface
             if (tg) HIPCHK(hipEventRecord(p->events[span[0]], s));
-            HIPCHK(fdc::launch_fused4096(in0, (size_t)p->H, o, nb, p->R, m0, nblocks, first_block, p->d_tw, p->ntab, p->d_wins, p->d_f4rows, p->f4_cls, p->f4_teams, s));
+            float *wf = p->wf_rows ? p->wf_rows + (size_t)(first_block - p->wf_first + m0) * fdc::kWfWidth : nullptr;
+            HIPCHK(fdc::launch_fused4096(in0, (size_t)p->H, o, nb, p->R, m0, nblocks, first_block, p->d_tw, p->ntab, p->d_wins, p->d_f4rows, p->f4_cls, p->f4_teams, s, wf));
             if (tg) { HIPCHK(hipEventRecord(p->events[span[1]], s)); span[2] = span[3] = span[1]; span[4] = kSpanBanks; p->ev_spans.push_back(span); }
             continue;
         }
@@ -1486,7 +1495,7 @@ static int pipeline_work_impl(fdc_pipeline *p, const void *in, int nblocks, void
     if (nblocks == 0) return 0;
     if (nblocks > p->cfg.max_blocks) return fail(FDC_ERR_INVALID_ARGUMENT, "nblocks %d above max_blocks %d", nblocks, p->cfg.max_blocks);
     if (!in || (p->C > 0 && !outs)) return fail(FDC_ERR_INVALID_ARGUMENT, "null host buffer");
-    if ((spectrum || d_spec_dst) && !p->cfg.keep_spectrum) return fail(FDC_ERR_INVALID_ARGUMENT, "spectrum output needs keep_spectrum");
+    if ((spectrum || (d_spec_dst && !p->wf_spec)) && !p->cfg.keep_spectrum) return fail(FDC_ERR_INVALID_ARGUMENT, "spectrum output needs keep_spectrum");
     HIPCHK(hipSetDevice(p->cfg.device_id));
     int rc = work_io_setup(p);
     if (rc != FDC_OK) return rc;
@@ -1615,6 +1624,48 @@ int fdc_pipeline_work(fdc_pipeline *p, const void *in, int nblocks, void *const 
 {
     FDC_ENTRY("fdc_pipeline_work")
     return pipeline_work_impl(p, in, nblocks, outs, spectrum, nullptr);
+    FDC_ENTRY_END
+}
+
+// The hier block with the waterfall on its spectrum (include/fdc_amd.h).  Path 5: the one-launch kernel's ROWS form sums the pixels from the spectrum in
+// LDS, no spectrum reaches memory.  Other paths: the call writes the handle's whole-call spectrum (the spectrum path of every plan, as a debug-port call)
+// and the rows are summed from its 16-bin group powers (N a multiple of 16384: the block kernel's epilogue or a pass over the spectrum) or from its bins.
+int fdc_pipeline_work_waterfall(fdc_pipeline *p, fdc_waterfall *w, const void *in, int nblocks, void *const *outs, float *rows, uint16_t *index,
+                                uint8_t *rgb, int cap_rows, int32_t *nrows)
+{
+    FDC_ENTRY("fdc_pipeline_work_waterfall")
+    if (!p) return fail(FDC_ERR_INVALID_ARGUMENT, "null handle");
+    if (nblocks < 0) return fail(FDC_ERR_INVALID_ARGUMENT, "negative item count");
+    if (nblocks > p->cfg.max_blocks) return fail(FDC_ERR_INVALID_ARGUMENT, "nblocks %d above max_blocks %d", nblocks, p->cfg.max_blocks);
+    int rc = fdc::wf_check_call(w, p->cfg.device_id, p->N, nblocks, cap_rows);
+    if (rc != FDC_OK) return rc;
+    if (nblocks == 0) { if (nrows) *nrows = 0; return 0; }
+    HIPCHK(hipSetDevice(p->cfg.device_id));
+    const bool fused = p->fused, groups = !fused && p->N % (16 * fdc::kWfWidth) == 0;
+    float2 *spec = nullptr;
+    float *gpow = nullptr;
+    if (!fused && (rc = spec_staging(p, &spec)) != FDC_OK) return rc;
+    if (groups && (rc = fdc::wf_group_buffer(w, nblocks, &gpow)) != FDC_OK) return rc;
+    {
+        // the per-call fields are cleared however the call leaves (an exception included): a later fdc_pipeline_work must not see them
+        struct Clear {
+            fdc_pipeline *p;
+            ~Clear() { p->wf_rows = nullptr; p->wf_spec = false; p->gpow_base = nullptr; p->gpow_spec = nullptr; }
+        } clear{p};
+        p->wf_rows = fused ? fdc::wf_block_rows(w) : nullptr;
+        p->wf_first = p->blockcount;
+        p->wf_spec = !fused;
+        p->gpow_base = gpow; p->gpow_spec = gpow ? spec : nullptr;
+        rc = pipeline_work_impl(p, in, nblocks, outs, nullptr, spec);
+    }
+    if (rc < 0) return rc;
+    p->wf_route = fused ? "k_f4096 epilogue (pixels from the spectrum in LDS)"
+                : groups ? "k_wf_from_groups (pixels from the 16-bin group powers of the internal spectrum)"
+                         : "k_wf_from_spectrum (pixels from the bins of the internal spectrum)";
+    if (groups) HIPCHK(fdc::wf_rows_from_groups(w, gpow, nblocks, p->stream));
+    else if (!fused) HIPCHK(fdc::wf_rows_from_spectrum(w, spec, nblocks, p->stream));
+    rc = fdc::wf_finish(w, nblocks, p->stream, rows, index, rgb, nrows);
+    return rc < 0 ? rc : nblocks;
     FDC_ENTRY_END
 }
 

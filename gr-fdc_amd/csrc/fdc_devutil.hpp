@@ -162,6 +162,12 @@ __device__ __forceinline__ float swap_pair(float x)
 {
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0xB1, 0xF, 0xF, true));
 }
+// the sum over the lane's quad (lanes 4 q .. 4 q + 3), the same bits in all four: (x0 + x1) + (x2 + x3) by DPP quad_perm [1, 0, 3, 2], [2, 3, 0, 1]
+__device__ __forceinline__ float quad_sum(float x)
+{
+    x += swap_pair(x);
+    return x + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x4E, 0xF, 0xF, true));
+}
 
 
 }  // namespace fdc

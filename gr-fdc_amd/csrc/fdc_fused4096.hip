@@ -89,11 +89,13 @@ __device__ __forceinline__ RowAt row_at(const F4Row &ri, int L, int m0, int nb, 
 // rows of two blocks); TEAMS = 1 — four independent workgroups per unit instead of two of twice the size — where the schedule of one block fits four waves.
 // wcls: four bits per wave: 0 = no rows, 1 = l = 256 (slots 0..3), 2 = l = 256 two sets (slots 0..7), 3 = l = 512 (slots 0..3), 4 = l = 1024 (slots 0..1),
 // 5 = l = 128, 6 = l = 64, 7 = l = 32, 8 = l = 16 (slots 0..7 each)
-template <bool WIDE, int TEAMS>
+// ROWS: the waterfall epilogue (fdc_waterfall.hip): wf[m][p] = sum of |X|^2 over shifted bins 4 p .. 4 p + 3 of the 1/N-scaled spectrum, taken from the
+// registers the spectrum store leaves; ROWS = false is the kernel without it, instruction for instruction
+template <bool WIDE, int TEAMS, bool ROWS>
 __global__ __launch_bounds__(256 * TEAMS, 4 /* waves per SIMD */) void k_f4096(const float2 *__restrict__ in, size_t in_stride, float2 *__restrict__ out, int nb, int R,
                                                   int mbase, int nb_call, int fbm /* (first block of the call + mbase) mod R */, const float2 *__restrict__ tw,
                                                   int twstride /* ntab / 4096 */, const float2 *__restrict__ wins,
-                                                  const F4Row *__restrict__ rows, unsigned wcls)
+                                                  const F4Row *__restrict__ rows, unsigned wcls, float *__restrict__ wf)
 {
     float2 *tiles = reinterpret_cast<float2 *>(fdc_smem_f4);
     float2 *t256 = reinterpret_cast<float2 *>(fdc_smem_f4 + f4_off_t256(TEAMS));
@@ -165,6 +167,19 @@ __global__ __launch_bounds__(256 * TEAMS, 4 /* waves per SIMD */) void k_f4096(c
         // the shifted spectrum (fftshift: bin k at k + N/2; python/FrequencyDomainChannelizer.py:206 fft_vcc(..., shift = True)), times 1/N
 #pragma unroll
         for (int k2 = 0; k2 < 16; k2++) st2(&tile[tid + 256 * (k2 ^ 8)], u[rev16(k2)] * (1.0f / 4096.0f));
+        if constexpr (ROWS) {
+            // shifted bin tid + 256 (k2 ^ 8) is pixel (tid >> 2) + 64 (k2 ^ 8): the four bins of a pixel are in four adjacent lanes (one DPP quad);
+            // m is uniform over the team, so every lane of the quad takes part
+            if (m < nb) {
+                float *dst = wf + (size_t)m * 1024 + (tid >> 2);
+#pragma unroll
+                for (int k2 = 0; k2 < 16; k2++) {
+                    const cf x = u[rev16(k2)] * (1.0f / 4096.0f);
+                    const float pw = quad_sum(x.x * x.x + x.y * x.y);
+                    if ((tid & 3) == 0) dst[64 * (k2 ^ 8)] = pw;
+                }
+            }
+        }
     }
     __syncthreads();
     // ---- the rows of this wave ---------------------------------------------------------------------------------------------------------
@@ -388,22 +403,44 @@ __global__ __launch_bounds__(256 * TEAMS, 4 /* waves per SIMD */) void k_f4096(c
     }
 }
 
+template <bool ROWS>
+static hipError_t init_fused4096_forms()
+{
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_f4096<false, 2, ROWS>), hipFuncAttributeMaxDynamicSharedMemorySize, f4_lds(2));
+    if (e != hipSuccess) return e;
+    e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_f4096<false, 1, ROWS>), hipFuncAttributeMaxDynamicSharedMemorySize, f4_lds(1));
+    if (e != hipSuccess) return e;
+    e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_f4096<true, 1, ROWS>), hipFuncAttributeMaxDynamicSharedMemorySize, f4_lds_wide(1));
+    if (e != hipSuccess) return e;
+    return hipFuncSetAttribute(reinterpret_cast<const void *>(k_f4096<true, 2, ROWS>), hipFuncAttributeMaxDynamicSharedMemorySize, f4_lds_wide(2));
+}
+
 hipError_t init_fused4096_kernels()
 {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_f4096<false, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, f4_lds(2));
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_f4096<false, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, f4_lds(1));
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_f4096<true, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, f4_lds_wide(1));
-    if (e != hipSuccess) return e;
-    return hipFuncSetAttribute(reinterpret_cast<const void *>(k_f4096<true, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, f4_lds_wide(2));
+    const hipError_t e = init_fused4096_forms<false>();
+    return e != hipSuccess ? e : init_fused4096_forms<true>();
 }
 
 int fused4096_tile_points() { return kF4TilePts; }
 
+template <bool ROWS>
+static void launch_fused4096_form(dim3 grid, bool wide, int teams, hipStream_t s, const float2 *in, size_t in_stride, float2 *out, int nb_chunk, int R,
+                                  int mbase, int nb_call, int fbm, const float2 *tw, int ntab, const float2 *wins, const F4Row *rows, unsigned wcls, float *wf)
+{
+    if (wide && teams == 1)
+        hipLaunchKernelGGL((k_f4096<true, 1, ROWS>), grid, dim3(256), f4_lds_wide(1), s, in, in_stride, out, nb_chunk, R, mbase, nb_call, fbm, tw, ntab / 4096, wins, rows, wcls, wf);
+    else if (wide)
+        hipLaunchKernelGGL((k_f4096<true, 2, ROWS>), grid, dim3(512), f4_lds_wide(2), s, in, in_stride, out, nb_chunk, R, mbase, nb_call, fbm, tw, ntab / 4096, wins, rows, wcls, wf);
+    else if (teams == 2)
+        hipLaunchKernelGGL((k_f4096<false, 2, ROWS>), grid, dim3(512), f4_lds(2), s, in, in_stride, out, nb_chunk, R, mbase, nb_call, fbm, tw, ntab / 4096, wins, rows, wcls, wf);
+    else
+        hipLaunchKernelGGL((k_f4096<false, 1, ROWS>), grid, dim3(256), f4_lds(1), s, in, in_stride, out, nb_chunk, R, mbase, nb_call, fbm, tw, ntab / 4096, wins, rows, wcls, wf);
+}
+
 // teams: blocks per workgroup the schedule was made for (1: rows[4 waves][8]; 2: rows[8 waves][8])
+// wf: NULL, or nb_chunk x 1024 floats: the waterfall row sums of the chunk's blocks (the ROWS form of the kernel)
 hipError_t launch_fused4096(const float2 *in, size_t in_stride, float2 *out, int nb_chunk, int R, int mbase, int nb_call, int64_t first_block,
-                            const float2 *tw, int ntab, const float2 *wins, const F4Row *rows, unsigned wcls, int teams, hipStream_t s)
+                            const float2 *tw, int ntab, const float2 *wins, const F4Row *rows, unsigned wcls, int teams, hipStream_t s, float *wf)
 {
     if (nb_chunk <= 0) return hipSuccess;
     bool wide = false;
@@ -412,14 +449,8 @@ hipError_t launch_fused4096(const float2 *in, size_t in_stride, float2 *out, int
     const int ngroups = (nb_chunk + teams - 1) / teams;
     const dim3 grid((unsigned)(8 * ((ngroups + 7) / 8)));
     const int fbm = (int)((first_block + mbase) % R);
-    if (wide && teams == 1)
-        hipLaunchKernelGGL((k_f4096<true, 1>), grid, dim3(256), f4_lds_wide(1), s, in, in_stride, out, nb_chunk, R, mbase, nb_call, fbm, tw, ntab / 4096, wins, rows, wcls);
-    else if (wide)
-        hipLaunchKernelGGL((k_f4096<true, 2>), grid, dim3(512), f4_lds_wide(2), s, in, in_stride, out, nb_chunk, R, mbase, nb_call, fbm, tw, ntab / 4096, wins, rows, wcls);
-    else if (teams == 2)
-        hipLaunchKernelGGL((k_f4096<false, 2>), grid, dim3(512), f4_lds(2), s, in, in_stride, out, nb_chunk, R, mbase, nb_call, fbm, tw, ntab / 4096, wins, rows, wcls);
-    else
-        hipLaunchKernelGGL((k_f4096<false, 1>), grid, dim3(256), f4_lds(1), s, in, in_stride, out, nb_chunk, R, mbase, nb_call, fbm, tw, ntab / 4096, wins, rows, wcls);
+    if (wf) launch_fused4096_form<true>(grid, wide, teams, s, in, in_stride, out, nb_chunk, R, mbase, nb_call, fbm, tw, ntab, wins, rows, wcls, wf);
+    else launch_fused4096_form<false>(grid, wide, teams, s, in, in_stride, out, nb_chunk, R, mbase, nb_call, fbm, tw, ntab, wins, rows, wcls, nullptr);
     return hipGetLastError();
 }
 

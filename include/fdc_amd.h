@@ -529,6 +529,57 @@ int fdc_window_table(int windowtype, int blocklen, float passbw, float stopbw, i
  * (python/FrequencyDomainChannelizer.py:206,228) on host buffers: nitems transforms of length n. */
 int fdc_fft_vcc(int device_id, int n, int forward, int shift, const void *in, int nitems, void *out);
 
+/* ---------------------------------------------------------------------------------------------
+ * Waterfall rows: the data path of FDC.WaterfallMsgTagging (python/WaterfallMsgTagging.py), the sink the reference's example
+ * flowgraph ends in (examples/FDC_example.grc: complex_to_mag_squared(blocklen) -> WaterfallMsgTagging).  Per block the N-bin power
+ * vector becomes 1024 pixels (:251-254: the mean of N/1024 consecutive bins for N >= 1024, each bin repeated 1024/N times below),
+ * blockdecimation consecutive rows are averaged, aligned to the first block of the stream, the unfinished group carried to the next
+ * call (:153-164 pxupdate, puffer_blocks), and every pixel gets a colour index = numpy.digitize(x, edges, right=False) against 1023
+ * edges linspace(minvaldb, maxvaldb, 1023), 10**(edge/10) when loginput = 0 (:261-262, :284-287), compared in FP64, and optionally
+ * the RGB888 colour of one of four schemes (:276-312).  The Qt widget and the PDU rectangles are not here (host code, the Python
+ * WaterfallImage draws them).  Row values are deterministic: the same input gives the same bytes, however the calls split it.
+ *   rows   NULL or cap_rows x 1024 float32: mean power per pixel of every row finished in the call
+ *   index  NULL or cap_rows x 1024 uint16: colour index 0 .. 1023
+ *   rgb    NULL or cap_rows x 1024 x 3 bytes
+ *   nrows  receives the number of rows finished; more than cap_rows is FDC_ERR_INVALID_ARGUMENT before anything is consumed.
+ * Row r covers blocks [r D, (r + 1) D) of the handle's stream (D = blockdecimation); fdc_waterfall_reset starts a new stream
+ * (fdc_pipeline_reset does NOT reset a waterfall used with the pipeline: call both).
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct fdc_waterfall fdc_waterfall;
+typedef struct {
+    int32_t blocklen;         /* N: a multiple of 1024 or a divisor of 1024 (the reference's reshape fails elsewhere) */
+    int32_t blockdecimation;  /* D; <= 0 is 1 (:37) */
+    int32_t loginput;         /* != 0: the input is already in dB, the edges are linspace itself */
+    double minvaldb, maxvaldb;  /* the reference's levels are Python floats: the edges are made from these doubles */
+    int32_t colorscheme;      /* 0 black-blue-cyan-white, 1 black-rainbow, 2 black-red-yellow, 3 black-white; others are 0 (:306) */
+} fdc_waterfall_cfg;
+/* Host only: the configuration create would use (D <= 0 -> 1) or FDC_ERR_INVALID_ARGUMENT. */
+int fdc_waterfall_check(const fdc_waterfall_cfg *cfg, fdc_waterfall_cfg *normalized);
+/* max_items: the most blocks one fdc_pipeline_work_waterfall call carries, and the blocks per internal pass of fdc_waterfall_work */
+int fdc_waterfall_create(int device_id, const fdc_waterfall_cfg *cfg, int32_t max_items, fdc_waterfall **out);
+void fdc_waterfall_destroy(fdc_waterfall *w);
+void fdc_waterfall_reset(fdc_waterfall *w);                                   /* carried rows and row counter <- 0 */
+int fdc_waterfall_set_levels(fdc_waterfall *w, double minvaldb, double maxvaldb);   /* set_minvaldb / set_maxvaldb (:264-270) */
+int fdc_waterfall_set_colorscheme(fdc_waterfall *w, int32_t scheme);            /* set_colorscheme (:272-274) */
+int64_t fdc_waterfall_rows_done(const fdc_waterfall *w);                      /* rows finished since create / reset */
+/* Host only: the 1024 x 3 colour table and the frame colour of a scheme (cr_colorscheme, numpy.linspace(..., dtype = uint8) truncation) */
+int fdc_waterfall_color_table(int32_t scheme, uint8_t *rgb, uint8_t *frame);
+/* Host only: the 1023 FP64 edges the colour index is counted against */
+int fdc_waterfall_edges(int32_t loginput, double minvaldb, double maxvaldb, double *edges);
+/* The reference block: nitems float32 power vectors of blocklen (host buffers, as fdc_pipeline_work) */
+int fdc_waterfall_work(fdc_waterfall *w, const float *power, int nitems, float *rows, uint16_t *index, uint8_t *rgb, int cap_rows,
+                       int32_t *nrows);
+/* The hier block with the waterfall on its spectrum: the channels of fdc_pipeline_work and the rows of this call as above (no spectrum to the host,
+ * no keep_spectrum needed).  Needs the same device and blocklen, nblocks <= the waterfall's max_items.  Routes:
+ *  - path 5 (N = 4096 in one launch) stays path 5: its kernel sums the rows' pixels from the spectrum in LDS, and the channel outputs are
+ *    bit-identical to fdc_pipeline_work's;
+ *  - every other plan runs the spectrum path, as a call that asks for the spectrum does (the channel outputs are those of fdc_pipeline_work
+ *    with a debug spectrum, equal to fdc_pipeline_work's to rounding): the rows are summed from the spectrum's 16-bin group powers (N a multiple
+ *    of 16384) or from its bins.
+ * fdc_pipeline_describe names the route of the last such call. */
+int fdc_pipeline_work_waterfall(fdc_pipeline *p, fdc_waterfall *w, const void *in, int nblocks, void *const *outs, float *rows,
+                                uint16_t *index, uint8_t *rgb, int cap_rows, int32_t *nrows);
+
 #ifdef __cplusplus
 }
 #endif
