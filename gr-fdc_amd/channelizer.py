@@ -139,6 +139,43 @@ def plan_preview(blocklen, relinvovl, channels, windowtype=WINDOWTYPES.HANN, max
     return rc, buf.value.decode(), [int(asg[i]) for i in range(len(chans))]
 
 
+IQ_SC16, IQ_SC8 = 1, 2          # FDC_IQ_SC16 / FDC_IQ_SC8 (include/fdc_amd.h)
+IQ_FORMATS = {"sc16": IQ_SC16, "sc8": IQ_SC8}
+
+
+def iq_format(x):
+    """The C-ABI format of a complex integer array: int16 -> FDC_IQ_SC16, int8 -> FDC_IQ_SC8; other dtypes raise TypeError."""
+    dt = np.asarray(x).dtype if not isinstance(x, np.dtype) else x
+    if dt == np.int16:
+        return IQ_SC16
+    if dt == np.int8:
+        return IQ_SC8
+    raise TypeError("complex integer input is int16 (sc16) or int8 (sc8) interleaved I/Q, not %s" % dt)
+
+
+def _iq_input(x, scale, H):
+    """Checks of the _iq entries made before any library call: dtype (TypeError), shape (flat interleaved I/Q or (n, 2)), a whole number
+    of (N - N/R)-sample items, a finite non-zero scale.  Returns (contiguous array, format, complex sample count, scale as float32)."""
+    if not isinstance(x, np.ndarray):
+        raise TypeError("complex integer input must be a numpy int16 or int8 array")
+    fmt = iq_format(x)
+    if x.ndim == 2:
+        if x.shape[1] != 2:
+            raise ValueError("complex integer input of shape (n, 2) holds I and Q in its columns; got shape %s" % (x.shape,))
+    elif x.ndim != 1:
+        raise ValueError("complex integer input is a flat interleaved array or one of shape (n, 2); got shape %s" % (x.shape,))
+    elif x.size % 2:
+        raise ValueError("a flat interleaved I/Q array has an even number of values")
+    n = x.size // 2
+    if H and n % H:
+        raise ValueError("input must be a whole number of (N - N/R)-sample items")
+    with np.errstate(over="ignore"):
+        sc = np.float32(scale)
+    if not np.isfinite(sc) or sc == 0:
+        raise ValueError("scale must be finite and not zero (float32), got %r" % (scale,))
+    return np.ascontiguousarray(x), fmt, n, sc
+
+
 class Pipeline:
     """fdc_pipeline handle: channels = [(f, l, passbw, stopbw), ...]."""
 
@@ -242,6 +279,44 @@ class Pipeline:
                                                     spec.ctypes.data if spec is not None else None))
         return (outs, spec) if want_spectrum else outs
 
+    def work_iq(self, x, scale=1.0, want_spectrum=False, outs=None):
+        """Complex integer input (fdc_pipeline_work_iq): x is int16 (sc16) or int8 (sc8), a flat interleaved I/Q array or one of shape (n, 2).
+        Sample k is (I_k * scale, Q_k * scale) in float32; the outputs are bit-identical to work() on that complex64 input.  scale defaults to
+        1.0 as GNU Radio's interleaved_short_to_complex; UHD's sc16 -> fc32 is scale = 1/32768.  The first work call after create / reset
+        latches the handle's input form (float, or this format and scale): a call in another form raises FdcError.  outs: as work()."""
+        x, fmt, n, sc = _iq_input(x, scale, self.H)
+        nb = n // self.H
+        if outs is None:
+            outs = [np.empty(nb * lo, dtype=np.complex64) for lo in self.lout]
+        else:
+            if len(outs) != len(self.lout):
+                raise ValueError("outs needs one array per channel")
+            for o, lo in zip(outs, self.lout):
+                if o.dtype != np.complex64 or not o.flags.c_contiguous or o.size != nb * lo:
+                    raise ValueError("outs[c] must be contiguous complex64 with nblocks*lout_c samples")
+        ptrs = (C.c_void_p * max(1, len(outs)))(*[o.ctypes.data for o in outs])
+        spec = np.empty(nb * self.N, dtype=np.complex64) if want_spectrum else None
+        _lib.check(_lib.lib().fdc_pipeline_work_iq(self._h, fmt, float(sc), x.ctypes.data, nb, ptrs,
+                                                  spec.ctypes.data if spec is not None else None))
+        return (outs, spec) if want_spectrum else outs
+
+    def work_span_iq(self, halo, x, first_block, scale=1.0, want_spectrum=False):
+        """fdc_pipeline_work_span_iq: one span of a longer integer stream; halo = the N/R integer samples in front of it (None = zeros)."""
+        x, fmt, n, sc = _iq_input(x, scale, self.H)
+        hp = None
+        if halo is not None:
+            halo, hfmt, hn, _ = _iq_input(halo, scale, 0)
+            if hfmt != fmt or hn != self.ovl:
+                raise ValueError("halo: N/R samples of the input's format")
+            hp = halo.ctypes.data
+        nb = n // self.H
+        outs = [np.empty(nb * lo, dtype=np.complex64) for lo in self.lout]
+        ptrs = (C.c_void_p * max(1, len(outs)))(*[o.ctypes.data for o in outs])
+        spec = np.empty(nb * self.N, dtype=np.complex64) if want_spectrum else None
+        _lib.check(_lib.lib().fdc_pipeline_work_span_iq(self._h, fmt, float(sc), hp, x.ctypes.data, int(first_block), nb, ptrs,
+                                                       spec.ctypes.data if spec is not None else None))
+        return (outs, spec) if want_spectrum else outs
+
     def work_raw(self, in_ptr, nblocks, out_ptrs):
         """fdc_pipeline_work on raw addresses (out_ptrs: ctypes array of c_void_p, one per channel) — for callers that
         keep their buffers and want no per-call Python work, e.g. timing the C entry itself."""
@@ -274,6 +349,15 @@ class Pipeline:
         else:
             _lib.check(_lib.lib().fdc_pipeline_process_device(self._h, d_ring, int(first_block), int(nblocks), d_out,
                                                              d_spectrum, stream))
+
+    def process_device_iq(self, fmt, scale, d_ring, first_block, nblocks, d_out, d_spectrum=None, stream=None):
+        """fdc_pipeline_process_device_iq: a device ring of complex integers (fmt: "sc16" / "sc8" or IQ_SC16 / IQ_SC8; d_ring 4-byte aligned).
+        Stateless, as process_device."""
+        fmt = IQ_FORMATS.get(fmt, fmt) if isinstance(fmt, str) else int(fmt)
+        if fmt not in (IQ_SC16, IQ_SC8):
+            raise ValueError("fmt is 'sc16' or 'sc8'")
+        _lib.check(_lib.lib().fdc_pipeline_process_device_iq(self._h, fmt, float(np.float32(scale)), d_ring, int(first_block), int(nblocks),
+                                                            d_out, d_spectrum, stream))
 
     def synchronize(self):
         _lib.check(_lib.lib().fdc_pipeline_synchronize(self._h))
@@ -371,6 +455,13 @@ class PipelineGroup:
             raise ValueError("input must be a whole number of (N - N/R)-sample items")
         return self._run(_lib.lib().fdc_pipeline_group_work_real, x, x.size // self.H, want_spectrum, None)
 
+    def work_iq(self, x, scale=1.0, want_spectrum=False, outs=None):
+        """Complex integer input (fdc_pipeline_group_work_iq): the arguments and the bytes of Pipeline.work_iq."""
+        x, fmt, n, sc = _iq_input(x, scale, self.H)
+        lib = _lib.lib()
+        return self._run(lambda h, xp, nb, ptrs, sp: lib.fdc_pipeline_group_work_iq(h, fmt, float(sc), xp, nb, ptrs, sp), x, n // self.H,
+                         want_spectrum, outs)
+
     def work_raw(self, in_ptr, nblocks, out_ptrs):
         return _lib.check(_lib.lib().fdc_pipeline_group_work(self._h, in_ptr, int(nblocks), out_ptrs, None))
 
@@ -428,7 +519,7 @@ class FrequencyDomainChannelizer:
                  act_det_deactivation_delay, minchanflankpuffer, verbose,
                  pow_act_deactivation_delay,
                  pow_act_maxblocks, act_det_maxblocks,
-                 debug, device_id=0, max_blocks=64, devices=None, pipelined=False, waterfall=None):
+                 debug, device_id=0, max_blocks=64, devices=None, pipelined=False, waterfall=None, iq_input=None, iq_scale=1.0):
         # pipelined (not an argument of the reference): the sink blocks run beside the front end of the FOLLOWING work() calls, as the
         # thread-per-block scheduler runs them beside the FFT in the reference (fdc_pipeline_work_sinks on a look-ahead bank,
         # include/fdc_amd.h): same PDUs, handed out one or two work() calls later; flush() at the end of the stream
@@ -464,6 +555,25 @@ class FrequencyDomainChannelizer:
                 raise ValueError("Float input (itemsize 4) needs inpveclen 1: pre-transformed items are complex spectra")
             if self.activity_controlled_channels or self.activity_detection_segments:
                 raise ValueError("Float input (itemsize 4) cannot feed activity-controlled channels or detection segments")
+        # iq_input (not an argument of the reference): "sc16" / "sc8" — work() takes interleaved int16 / int8 I/Q as a radio source delivers it
+        # (UHD sc16 with iq_scale = 1/32768; the default 1.0 is GNU Radio's interleaved_short_to_complex) and converts it inside the device's
+        # loads (Pipeline.work_iq).  The restrictions of the Float input: a sample stream, no sink blocks, no waterfall.
+        if iq_input is not None and iq_input not in IQ_FORMATS:
+            raise ValueError("iq_input is None, 'sc16' or 'sc8'")
+        self.iq_input, self.iq_scale = iq_input, float(iq_scale)
+        if iq_input is not None:
+            if self.itemsize != 8:
+                raise ValueError("iq_input replaces the complex input type (itemsize 8)")
+            if self.inpveclen != 1:
+                raise ValueError("iq_input needs inpveclen 1: pre-transformed items are complex spectra")
+            if activity_controlled_channels or activity_detection_segments:
+                raise ValueError("iq_input cannot feed activity-controlled channels or detection segments")
+            if waterfall is not None:
+                raise ValueError("iq_input cannot feed a waterfall")
+            with np.errstate(over="ignore"):
+                sc = np.float32(iq_scale)
+            if not np.isfinite(sc) or sc == 0:
+                raise ValueError("iq_scale must be finite and not zero")
 
         if self.verbose:                                        # runtime information, :176-193
             bar = '\n' + '#' * 32 + '\n'
@@ -566,7 +676,11 @@ class FrequencyDomainChannelizer:
         """Returns the hier block's stream ports; PDUs of the sink blocks ("msgout", :166-168) are left in
         self.messages as (dict, complex64 array) pairs.  Detection segments run as SegmentDetection instances, like in
         the reference hier block (:261-278)."""
-        if self.inpveclen == 1 and self.itemsize == 4:
+        if self.iq_input is not None:
+            if iq_format(samples) != IQ_FORMATS[self.iq_input]:
+                raise TypeError("this block takes %s input (%s)" % (self.iq_input, "int16" if self.iq_input == "sc16" else "int8"))
+            res = self.pipeline.work_iq(samples, scale=self.iq_scale, want_spectrum=self.debug)
+        elif self.inpveclen == 1 and self.itemsize == 4:
             if self.sinks is not None:
                 raise ValueError("real input with sink blocks is not supported")
             res = self.pipeline.work_real(samples, want_spectrum=self.debug)

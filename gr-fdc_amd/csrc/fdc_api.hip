@@ -6,9 +6,11 @@
 #include "fdc_guard.hpp"
 #include "fdc_plan_cost.hpp"
 #include "fdc_waterfall.hpp"
+#include "fdc_iq.hpp"
 
 #include <algorithm>
 #include <array>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -210,6 +212,14 @@ struct fdc_pipeline {
     float2 *d_ring = nullptr;    // work(): ovl + max_blocks*H
     float2 *d_specfull = nullptr; // work() with a host spectrum (debug port) and no bank to put it in: max_blocks*N, allocated at the first such call
     float *d_real = nullptr;     // work_real(): max_blocks*H real samples
+    // complex integer input (fdc_pipeline_work_iq and friends).  The input form of the work calls is latched by the first one after create / reset:
+    // in_form -1 = none yet, 0 = float (work, work_real, ...), FDC_IQ_SC16 / FDC_IQ_SC8 with in_scale
+    int in_form = -1;
+    float in_scale = 0.f;
+    void *d_iq = nullptr;        // work_iq(): the integer ring, ovl + max_blocks*H samples of fdc::kIqRingBytes (the widest format; its first ovl samples
+                                 // of the latched format: the history)
+    float2 *d_iqw = nullptr;     // process_device_iq(): one launch group widened, chunk*H + ovl samples (paths without integer loads)
+    std::string iq_route;        // how the last integer-input call was served (fdc_pipeline_describe)
     float2 *d_out = nullptr;     // work(): max_blocks*sum_lout
     int64_t blockcount = 0;      // work(): blocks consumed so far
     // work(): transfers and kernels of consecutive sub-batches overlap (H2D on s_in, kernels on stream, D2H on s_out)
@@ -411,7 +421,7 @@ void fdc_pipeline_destroy(fdc_pipeline *p)
     (void)hipFree(p->d_tw); (void)hipFree(p->d_wins); (void)hipFree(p->d_chans); (void)hipFree(p->d_groups); (void)hipFree(p->d_rgroups); (void)hipFree(p->d_keep); (void)hipFree(p->d_f4rows);
     (void)hipFree(p->d_tw512); (void)hipFree(p->d_twq512); (void)hipFree(p->d_t2g);
     (void)hipFree(p->d_tw1k); (void)hipFree(p->d_twq1k);
-    (void)hipFree(p->d_big); (void)hipFree(p->d_wtasks); (void)hipFree(p->d_tmp); (void)hipFree(p->d_spec); (void)hipFree(p->d_ring); (void)hipFree(p->d_out); (void)hipFree(p->d_real);
+    (void)hipFree(p->d_big); (void)hipFree(p->d_wtasks); (void)hipFree(p->d_tmp); (void)hipFree(p->d_spec); (void)hipFree(p->d_ring); (void)hipFree(p->d_out); (void)hipFree(p->d_real); (void)hipFree(p->d_iq); (void)hipFree(p->d_iqw);
     if (p->stream) (void)hipStreamDestroy(p->stream);
     delete p;
 }
@@ -1126,6 +1136,7 @@ int32_t fdc_pipeline_describe(const fdc_pipeline *p, char *buf, int32_t n)
         add("%s", "forward transform to a spectrum in memory + channel kernels");
     }
     if (!p->wf_route.empty()) add("; waterfall rows: %s", p->wf_route.c_str());
+    if (!p->iq_route.empty()) add("; input %s", p->iq_route.c_str());
     std::snprintf(buf, (size_t)n, "%s", t);
     return k;
 }
@@ -1223,17 +1234,17 @@ static int run_channel_groups(fdc_pipeline *p, bool rem, const float2 *spec, flo
 
 // The remainder of a split plan for one launch group: forward transform into the handle's internal (partial) spectrum, channel kernels
 // over the remainder's groups.  ev2 / ev3 (timing): recorded behind the forward transform and behind the channel kernels.
-static int run_remainder(fdc_pipeline *p, const float2 *ring, int m0, int nb, int nblocks, int64_t first_block, float2 *d_out, bool few,
+static int run_remainder(fdc_pipeline *p, const float2 *in0, int m0, int nb, int nblocks, int64_t first_block, float2 *d_out, bool few,
                          hipStream_t s, hipEvent_t ev2, hipEvent_t ev3)
 {
     if (p->fwd_block && !few)
-        HIPCHK(fdc::launch_block_fft(p->N, ring + (size_t)m0 * p->H, (size_t)p->H, p->d_spec, nb, p->d_tw256, p->d_ftwq, p->d_fcbt, p->d_fshn,
+        HIPCHK(fdc::launch_block_fft(p->N, in0, (size_t)p->H, p->d_spec, nb, p->d_tw256, p->d_ftwq, p->d_fcbt, p->d_fshn,
                                           p->d_fslot, p->d_fscr, p->ncu - p->reserved_cu, p->block_hints, s, nullptr, p->d_keep));
     else if (p->N == 65536)
-        HIPCHK(fdc::launch_fft65536(ring + (size_t)m0 * p->H, (size_t)p->H, p->d_spec, p->d_tmp, nb, p->N / 2, 1.0f / (float)p->N, p->d_tw256,
+        HIPCHK(fdc::launch_fft65536(in0, (size_t)p->H, p->d_spec, p->d_tmp, nb, p->N / 2, 1.0f / (float)p->N, p->d_tw256,
                                     p->d_twf, s, nullptr));
     else
-        HIPCHK(fdc::launch_fft(ring + (size_t)m0 * p->H, (size_t)p->H, p->d_spec, p->d_tmp, p->N, nb, false, 0, p->N / 2, 1.0f / (float)p->N, p->d_tw, p->ntab,
+        HIPCHK(fdc::launch_fft(in0, (size_t)p->H, p->d_spec, p->d_tmp, p->N, nb, false, 0, p->N / 2, 1.0f / (float)p->N, p->d_tw, p->ntab,
                                s, nullptr, p->d_twf, p->cfg_generic));
     if (ev2) HIPCHK(hipEventRecord(ev2, s));
     const int rc = run_channel_groups(p, true, p->d_spec, d_out, nb, m0, nblocks, first_block, s);
@@ -1247,10 +1258,17 @@ enum { kSpanBanks = 0 /* banks | remainder forward | remainder channels */, kSpa
        kSpanSpectrumLds = 2 /* forward transform = a + b | channels */, kSpanSpectrum = 3 /* pass A / block forward | pass B | channels */ };
 
 // one launch of the bank's block kernel over the launch group (ev0 / ev1: stamped by the dispatch itself, may be null)
+// fmt != 0: in0 is complex integer input (raw: the launch group's first sample), read by the 256-bin kernel itself
 static int launch_bank(fdc_pipeline *p, const fdc_pipeline::Bank &bk, const float2 *in0, float2 *o, int nb, int m0, int nblocks, int64_t first_block,
-                       unsigned out_bytes, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1)
+                       unsigned out_bytes, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1, int fmt = 0, float scale = 1.0f, const void *raw = nullptr)
 {
     const bool half = bk.r == bk.L / 2;
+    if (fmt) {
+        if (bk.L != 256) return fail(FDC_ERR_UNSUPPORTED, "integer loads in a %d-bin bank", bk.L);
+        HIPCHK(fdc::launch_poly_block_iq(fmt, scale, raw, (size_t)p->H, o, nb, m0, nblocks, p->d_tw256, p->d_twq, bk.d_cbt, bk.d_shn, bk.d_slot_off, out_bytes,
+                                         p->ncu - p->reserved_cu, p->block_hints, s, bk.r, first_block + m0, ev0, ev1, p->R, p->d_fscr, p->N));
+        return FDC_OK;
+    }
     switch (bk.L) {
     case 256:
         HIPCHK(fdc::launch_poly_block(in0, (size_t)p->H, o, nb, m0, nblocks, p->d_tw256, p->d_twq, bk.d_cbt, bk.d_shn, bk.d_slot_off, out_bytes, p->ncu - p->reserved_cu,
@@ -1271,10 +1289,22 @@ static int launch_bank(fdc_pipeline *p, const fdc_pipeline::Bank &bk, const floa
     return FDC_OK;
 }
 
-int fdc_pipeline_process_device(fdc_pipeline *p, const void *d_ring, int64_t first_block, int nblocks,
-                                void *d_out, void *d_spectrum, void *stream)
+// whether a launch group of the plan reads integer input in its own loads: path 5 (k_f4096) and the banks of 256-bin channels (k_blk256) without
+// a remainder; every other form reads a float ring the group is widened into first (k_iq_to_complex)
+static bool iq_fused(const fdc_pipeline *p, bool spectrum, bool few)
 {
-    FDC_ENTRY("fdc_pipeline_process_device")
+    if (spectrum || p->wf_rows || p->cfg_generic) return false;
+    if (p->fused) return true;
+    if (!p->poly_ok || !p->poly_block || p->split || (few && two_launch_possible(p))) return false;
+    for (const auto &b : p->banks) if (b.L != 256) return false;
+    return true;
+}
+
+// fmt: 0 = float2 ring; FDC_IQ_SC16 / FDC_IQ_SC8: a ring of complex integers (scale: their factor), and `wide` the float2 buffer of chunk*H + ovl
+// samples a launch group is widened into where the kernels take float input
+static int process_device_impl(fdc_pipeline *p, int fmt, float scale, const void *d_ring, int64_t first_block, int nblocks,
+                               void *d_out, void *d_spectrum, void *stream, float2 *wide, bool *all_fused)
+{
     if (!p) return fail(FDC_ERR_INVALID_ARGUMENT, "null handle");
     if (nblocks < 0 || first_block < 0) return fail(FDC_ERR_INVALID_ARGUMENT, "negative block count/index");
     if (nblocks == 0) return FDC_OK;
@@ -1287,6 +1317,8 @@ int fdc_pipeline_process_device(fdc_pipeline *p, const void *d_ring, int64_t fir
     HIPCHK(hipSetDevice(p->cfg.device_id));
     hipStream_t s = stream ? (hipStream_t)stream : p->stream;
     const float2 *ring = static_cast<const float2 *>(d_ring);
+    const unsigned char *iring = static_cast<const unsigned char *>(d_ring);
+    const size_t esz = fdc::iq_bytes(fmt);
     float2 *o = static_cast<float2 *>(d_out);
     const bool use_poly = p->poly_ok && !d_spectrum;
     const unsigned out_bytes = (unsigned)((int64_t)nblocks * p->sum_lout * 8);
@@ -1303,16 +1335,28 @@ int fdc_pipeline_process_device(fdc_pipeline *p, const void *d_ring, int64_t fir
             evp = ev;
         }
         const float2 *in0 = ring + (size_t)m0 * p->H;
+        const void *raw0 = iring + (size_t)m0 * p->H * esz;
+        const bool few = nb < p->block_min;
+        const bool ifused = fmt && iq_fused(p, d_spectrum != nullptr, few);
+        if (fmt && !ifused) {
+            // this launch group's samples (nb blocks and the history in front of the last one) widened into the float ring the kernels read
+            HIPCHK(fdc::launch_iq_to_complex(fmt, scale, raw0, wide, (size_t)nb * p->H + (size_t)p->ovl, s));
+            in0 = wide;
+            if (all_fused) *all_fused = false;
+        }
         // overlap-save gather fused into the load (item m at ring + m*H), fftshift + 1/N into the store.
         // A block kernel gives a whole block to one compute unit: a launch group of fewer blocks than the device has compute
         // units leaves the rest idle (one block takes ~42 us there, however few there are).  Short calls — a scheduler handing
         // over a few items — take the two-launch form where the plan has one (ONE bank on its grid), which spreads every block over the device.
-        const bool few = nb < p->block_min;
         if (p->fused && !d_spectrum) {
             // N = 4096: one launch, nothing but the input samples and the output samples crosses the memory interface
             if (tg) HIPCHK(hipEventRecord(p->events[span[0]], s));
             float *wf = p->wf_rows ? p->wf_rows + (size_t)(first_block - p->wf_first + m0) * fdc::kWfWidth : nullptr;
-            HIPCHK(fdc::launch_fused4096(in0, (size_t)p->H, o, nb, p->R, m0, nblocks, first_block, p->d_tw, p->ntab, p->d_wins, p->d_f4rows, p->f4_cls, p->f4_teams, s, wf));
+            if (ifused)
+                HIPCHK(fdc::launch_fused4096_iq(fmt, scale, raw0, (size_t)p->H, o, nb, p->R, m0, nblocks, first_block, p->d_tw, p->ntab, p->d_wins, p->d_f4rows,
+                                                p->f4_cls, p->f4_teams, s));
+            else
+                HIPCHK(fdc::launch_fused4096(in0, (size_t)p->H, o, nb, p->R, m0, nblocks, first_block, p->d_tw, p->ntab, p->d_wins, p->d_f4rows, p->f4_cls, p->f4_teams, s, wf));
             if (tg) { HIPCHK(hipEventRecord(p->events[span[1]], s)); span[2] = span[3] = span[1]; span[4] = kSpanBanks; p->ev_spans.push_back(span); }
             continue;
         }
@@ -1321,7 +1365,8 @@ int fdc_pipeline_process_device(fdc_pipeline *p, const void *d_ring, int64_t fir
             // timing: the first launch's begin and the last one's end are the dispatches' own stamps, no packets around the kernels
             for (size_t k = 0; k < p->banks.size(); k++) {
                 const int rcb = launch_bank(p, p->banks[k], in0, o, nb, m0, nblocks, first_block, out_bytes, s,
-                                            tg && k == 0 ? p->events[span[0]] : nullptr, tg && k + 1 == p->banks.size() ? p->events[span[1]] : nullptr);
+                                            tg && k == 0 ? p->events[span[0]] : nullptr, tg && k + 1 == p->banks.size() ? p->events[span[1]] : nullptr,
+                                            ifused ? fmt : 0, scale, raw0);
                 if (rcb != FDC_OK) return rcb;
             }
             for (const auto &al : p->bank_alias) {
@@ -1330,7 +1375,7 @@ int fdc_pipeline_process_device(fdc_pipeline *p, const void *d_ring, int64_t fir
                                       sizeof(float2) * (size_t)nb * dc.lout, hipMemcpyDeviceToDevice, s));
             }
             if (p->split) {
-                const int rcr = run_remainder(p, ring, m0, nb, nblocks, first_block, o, few, s, tg ? p->events[span[2]] : nullptr, tg ? p->events[span[3]] : nullptr);
+                const int rcr = run_remainder(p, in0, m0, nb, nblocks, first_block, o, few, s, tg ? p->events[span[2]] : nullptr, tg ? p->events[span[3]] : nullptr);
                 if (rcr != FDC_OK) return rcr;
             } else if (tg) span[2] = span[3] = span[1];
             if (tg) { span[4] = kSpanBanks; p->ev_spans.push_back(span); }
@@ -1352,7 +1397,7 @@ int fdc_pipeline_process_device(fdc_pipeline *p, const void *d_ring, int64_t fir
             else
                 HIPCHK(fdc::launch_poly_stage2(p->d_g, o, p->N / 256, p->R, nb, m0, nblocks, p->d_tw256, p->d_tw1024, bk.d_slot_off, out_bytes, p->ncu - p->reserved_cu, s));
             if (p->split) {                                     // (timing: the remainder is counted with stage 2)
-                const int rcr = run_remainder(p, ring, m0, nb, nblocks, first_block, o, few, s, nullptr, nullptr);
+                const int rcr = run_remainder(p, in0, m0, nb, nblocks, first_block, o, few, s, nullptr, nullptr);
                 if (rcr != FDC_OK) return rcr;
             }
             if (tg) {
@@ -1387,6 +1432,44 @@ int fdc_pipeline_process_device(fdc_pipeline *p, const void *d_ring, int64_t fir
         }
     }
     return FDC_OK;
+}
+
+int fdc_pipeline_process_device(fdc_pipeline *p, const void *d_ring, int64_t first_block, int nblocks,
+                                void *d_out, void *d_spectrum, void *stream)
+{
+    FDC_ENTRY("fdc_pipeline_process_device")
+    return process_device_impl(p, 0, 1.0f, d_ring, first_block, nblocks, d_out, d_spectrum, stream, nullptr, nullptr);
+    FDC_ENTRY_END
+}
+
+static int check_iq_form(int32_t format, float scale)
+{
+    if (format != FDC_IQ_SC16 && format != FDC_IQ_SC8) return fail(FDC_ERR_INVALID_ARGUMENT, "unknown complex integer format %d", (int)format);
+    if (!std::isfinite(scale) || scale == 0.0f) return fail(FDC_ERR_INVALID_ARGUMENT, "the scale must be finite and not zero");
+    return FDC_OK;
+}
+static const char *iq_name(int fmt) { return fmt == FDC_IQ_SC16 ? "sc16" : "sc8"; }
+
+int fdc_pipeline_process_device_iq(fdc_pipeline *p, int32_t format, float scale, const void *d_ring, int64_t first_block, int nblocks,
+                                   void *d_out, void *d_spectrum, void *stream)
+{
+    FDC_ENTRY("fdc_pipeline_process_device_iq")
+    if (!p) return fail(FDC_ERR_INVALID_ARGUMENT, "null handle");
+    int rc = check_iq_form(format, scale);
+    if (rc != FDC_OK) return rc;
+    if (reinterpret_cast<uintptr_t>(d_ring) & 3) return fail(FDC_ERR_INVALID_ARGUMENT, "the integer ring must be 4-byte aligned");
+    if (nblocks > 0 && !p->d_iqw) {
+        bool need = false;      // the widened launch group: allocated at the first call that has a form without integer loads
+        for (int m0 = 0; m0 < nblocks && !need; m0 += p->chunk) need = !iq_fused(p, d_spectrum != nullptr, std::min(p->chunk, nblocks - m0) < p->block_min);
+        if (need) {
+            HIPCHK(hipSetDevice(p->cfg.device_id));
+            HIPCHK(hipMalloc(&p->d_iqw, sizeof(float2) * ((size_t)p->chunk * p->H + (size_t)p->ovl)));
+        }
+    }
+    bool all = true;
+    rc = process_device_impl(p, format, scale, d_ring, first_block, nblocks, d_out, d_spectrum, stream, p->d_iqw, &all);
+    if (rc == FDC_OK && nblocks > 0) p->iq_route = std::string(iq_name(format)) + (all ? ": fused" : ": widened");
+    return rc;
     FDC_ENTRY_END
 }
 
@@ -1439,8 +1522,13 @@ void fdc_pipeline_reset(fdc_pipeline *p)
     if (p->d_ring) {
         (void)hipSetDevice(p->cfg.device_id);
         (void)hipMemsetAsync(p->d_ring, 0, sizeof(float2) * (size_t)p->ovl, p->stream);
+        // the integer ring is sized for the widest format (fdc::kIqRingBytes per sample): its history of any format is zeroed
+        if (p->d_iq) (void)hipMemsetAsync(p->d_iq, 0, fdc::kIqRingBytes * (size_t)p->ovl, p->stream);
         (void)hipStreamSynchronize(p->stream);
     }
+    p->in_form = -1;
+    p->in_scale = 0.f;
+    p->iq_route.clear();
 }
 
 // The whole-call spectrum of a work() that hands it to the host (debug port, python/FrequencyDomainChannelizer.py:152-158, :314-315) when
@@ -1479,6 +1567,27 @@ static int work_io_setup(fdc_pipeline *p)
     return FDC_OK;
 }
 
+// The input form of a work call against the form the handle is latched to (the first work call after create / reset latches it): a call in another
+// form is refused before it touches anything.  fmt 0 = float input (scale unused).  check_form only compares; latch_form records the form of a
+// call that got past its set-up (a first call that fails there leaves the handle unlatched).
+static int check_form(const fdc_pipeline *p, int fmt, float scale)
+{
+    if (p->in_form < 0) return FDC_OK;
+    if (p->in_form == fmt && (fmt == 0 || std::memcmp(&p->in_scale, &scale, sizeof(float)) == 0)) return FDC_OK;
+    auto name = [](int f, float sc) {
+        char b[48];
+        if (f == 0) std::snprintf(b, sizeof(b), "float");
+        else std::snprintf(b, sizeof(b), "%s x %.9g", f == FDC_IQ_SC16 ? "sc16" : "sc8", (double)sc);
+        return std::string(b);
+    };
+    return fail(FDC_ERR_INVALID_ARGUMENT, "the handle takes %s input since its first work call (reset it to change the input form), not %s",
+                name(p->in_form, p->in_scale).c_str(), name(fmt, scale).c_str());
+}
+static void latch_form(fdc_pipeline *p, int fmt, float scale)
+{
+    if (p->in_form < 0) { p->in_form = fmt; p->in_scale = fmt ? scale : 0.f; }
+}
+
 // Host entry.  The call is cut into sub-batches; sub-batch k's H2D copy (stream s_in), its kernels (p->stream) and
 // its D2H leg (s_out) run beside the neighbouring sub-batches' other legs, so a long call moves at the rate of the
 // slower PCIe direction instead of the sum of all legs.  Caller buffers pinned with fdc_host_register() are DMA'd in
@@ -1487,8 +1596,10 @@ static int work_io_setup(fdc_pipeline *p)
 // through two pinned staging slots and a CPU copy on this thread.
 // span: the call is one contiguous span of a longer stream handed over by a dispatcher (fdc_pipeline_work_span): the history comes
 // from `halo` (N/R samples, NULL = zeros) and the block counter from `first_block` instead of from the handle.
+// fmt != 0: `in` and `halo` hold complex integers (FDC_IQ_SC16 / FDC_IQ_SC8, times scale): the ring and its history are kept in that format
+// (d_iq), the integer kernels read it where the plan has them, the handle's float ring takes the widened launch groups otherwise.
 static int pipeline_work_impl(fdc_pipeline *p, const void *in, int nblocks, void *const *outs, void *spectrum,
-                              float2 *d_spec_dst, bool span = false, const void *halo = nullptr, int64_t first_block = 0)
+                              float2 *d_spec_dst, bool span = false, const void *halo = nullptr, int64_t first_block = 0, int fmt = 0, float scale = 1.0f)
 {
     if (!p) return fail(FDC_ERR_INVALID_ARGUMENT, "null handle");
     if (nblocks < 0) return fail(FDC_ERR_INVALID_ARGUMENT, "negative item count");
@@ -1496,16 +1607,31 @@ static int pipeline_work_impl(fdc_pipeline *p, const void *in, int nblocks, void
     if (nblocks > p->cfg.max_blocks) return fail(FDC_ERR_INVALID_ARGUMENT, "nblocks %d above max_blocks %d", nblocks, p->cfg.max_blocks);
     if (!in || (p->C > 0 && !outs)) return fail(FDC_ERR_INVALID_ARGUMENT, "null host buffer");
     if ((spectrum || (d_spec_dst && !p->wf_spec)) && !p->cfg.keep_spectrum) return fail(FDC_ERR_INVALID_ARGUMENT, "spectrum output needs keep_spectrum");
-    HIPCHK(hipSetDevice(p->cfg.device_id));
-    int rc = work_io_setup(p);
+    int rc = check_form(p, fmt, scale);
     if (rc != FDC_OK) return rc;
+    HIPCHK(hipSetDevice(p->cfg.device_id));
+    if ((rc = work_io_setup(p)) != FDC_OK) return rc;
     hipStream_t s = p->stream;
-    const size_t nin = (size_t)nblocks * p->H;
-    const float2 *hin = static_cast<const float2 *>(in);
+    const size_t nin = (size_t)nblocks * p->H, esz = fdc::iq_bytes(fmt);
+    if (fmt && !p->d_iq) {
+        // the integer ring: allocated at the first integer call, for the WIDEST format (a reset may latch the handle to another one); its
+        // history starts at zero, as the float ring's
+        HIPCHK(hipMalloc(&p->d_iq, fdc::kIqRingBytes * ((size_t)p->ovl + (size_t)p->cfg.max_blocks * p->H)));
+        HIPCHK(hipMemsetAsync(p->d_iq, 0, fdc::kIqRingBytes * (size_t)p->ovl, s));
+    }
+    latch_form(p, fmt, scale);
+    // the ring the call's samples go to, as bytes: float2 (d_ring) or the integer format (d_iq)
+    unsigned char *const ringb = fmt ? static_cast<unsigned char *>(p->d_iq) : reinterpret_cast<unsigned char *>(p->d_ring);
+    const unsigned char *hin = static_cast<const unsigned char *>(in);
+    bool all_fused = true;
+    auto process = [&](size_t b0, int nb, int64_t first, float2 *dok, float2 *dspec) {
+        return fmt ? process_device_impl(p, fmt, scale, ringb + b0 * p->H * esz, first, nb, dok, dspec, s, p->d_ring, &all_fused)
+                   : fdc_pipeline_process_device(p, ringb + b0 * p->H * esz, first, nb, dok, dspec, s);
+    };
     if (span) {
         // every kernel of the call is enqueued on s behind this copy; the previous call ended with s drained
-        if (halo) HIPCHK(hipMemcpyAsync(p->d_ring, halo, sizeof(float2) * (size_t)p->ovl, hipMemcpyHostToDevice, s));
-        else HIPCHK(hipMemsetAsync(p->d_ring, 0, sizeof(float2) * (size_t)p->ovl, s));
+        if (halo) HIPCHK(hipMemcpyAsync(ringb, halo, esz * (size_t)p->ovl, hipMemcpyHostToDevice, s));
+        else HIPCHK(hipMemsetAsync(ringb, 0, esz * (size_t)p->ovl, s));
         p->blockcount = first_block;
     }
 
@@ -1513,7 +1639,7 @@ static int pipeline_work_impl(fdc_pipeline *p, const void *in, int nblocks, void
     float2 *d_specfull = d_spec_dst;
     if (spectrum && !d_specfull && (rc = spec_staging(p, &d_specfull)) != FDC_OK) return rc;
 
-    const bool in_reg = host_registered(in, sizeof(float2) * nin);
+    const bool in_reg = host_registered(in, esz * nin);
     bool out_reg = p->C > 0;
     for (int c = 0; c < p->C && out_reg; c++) {
         fdc::ScatterEnt &e = p->pin_tab[c];
@@ -1540,16 +1666,17 @@ static int pipeline_work_impl(fdc_pipeline *p, const void *in, int nblocks, void
     const int K = (nblocks + sub - 1) / sub;
     if (K == 1) {
         // short call (the usual work() of a running flowgraph): nothing to overlap, one stream, one synchronisation
-        HIPCHK(hipMemcpyAsync(p->d_ring + p->ovl, hin, sizeof(float2) * nin, hipMemcpyHostToDevice, s));
-        rc = fdc_pipeline_process_device(p, p->d_ring, p->blockcount, nblocks, p->d_out, d_specfull, s);
+        HIPCHK(hipMemcpyAsync(ringb + esz * p->ovl, hin, esz * nin, hipMemcpyHostToDevice, s));
+        rc = process(0, nblocks, p->blockcount, p->d_out, d_specfull);
         if (rc != FDC_OK) return rc;
         if (p->C > 0) {
             if (out_reg) HIPCHK(fdc::launch_scatter_out(p->d_out, p->d_tab, p->C, nblocks, 0, s));
             else HIPCHK(hipMemcpyAsync(p->pin_out[0], p->d_out, sizeof(float2) * (size_t)nblocks * p->sum_lout, hipMemcpyDeviceToHost, s));
         }
         if (spectrum) HIPCHK(hipMemcpyAsync(spectrum, d_specfull, sizeof(float2) * (size_t)nblocks * p->N, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(p->d_ring, p->d_ring + nin, sizeof(float2) * (size_t)p->ovl, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpyAsync(ringb, ringb + esz * nin, esz * (size_t)p->ovl, hipMemcpyDeviceToDevice, s));
         HIPCHK(hipStreamSynchronize(s));
+        if (fmt) p->iq_route = std::string(iq_name(fmt)) + (all_fused ? ": fused" : ": widened");
         if (p->C > 0 && !out_reg)
             for (int c = 0; c < p->C; c++)
                 if (outs[c])
@@ -1567,14 +1694,14 @@ static int pipeline_work_impl(fdc_pipeline *p, const void *in, int nblocks, void
     } feeder;
     if (!in_reg) {
         const int dev = p->cfg.device_id, Hs = p->H;
-        float2 *ring_in = p->d_ring + p->ovl;
+        unsigned char *ring_in = ringb + esz * p->ovl;
         hipStream_t sin = p->s_in;
-        feeder.th = std::thread([&feeder, dev, Hs, ring_in, sin, hin, K, sub, nblocks] {
+        feeder.th = std::thread([&feeder, dev, Hs, ring_in, sin, hin, K, sub, nblocks, esz] {
             hipError_t e = hipSetDevice(dev);
             for (int k = 0; k < K; k++) {
                 const int b0 = k * sub, nb = std::min(sub, nblocks - b0);
                 if (e == hipSuccess)
-                    e = hipMemcpyAsync(ring_in + (size_t)b0 * Hs, hin + (size_t)b0 * Hs, sizeof(float2) * (size_t)nb * Hs,
+                    e = hipMemcpyAsync(ring_in + (size_t)b0 * Hs * esz, hin + (size_t)b0 * Hs * esz, esz * (size_t)nb * Hs,
                                        hipMemcpyHostToDevice, sin);
                 if (e == hipSuccess) e = hipStreamSynchronize(sin);
                 std::lock_guard<std::mutex> lk(feeder.mu);
@@ -1586,8 +1713,8 @@ static int pipeline_work_impl(fdc_pipeline *p, const void *in, int nblocks, void
     for (int k = 0; k < K; k++) {
         const int slot = k & 1, b0 = k * sub, nb = std::min(sub, nblocks - b0);
         if (in_reg) {
-            HIPCHK(hipMemcpyAsync(p->d_ring + p->ovl + (size_t)b0 * p->H, hin + (size_t)b0 * p->H,
-                                  sizeof(float2) * (size_t)nb * p->H, hipMemcpyHostToDevice, p->s_in));
+            HIPCHK(hipMemcpyAsync(ringb + esz * (p->ovl + (size_t)b0 * p->H), hin + esz * (size_t)b0 * p->H,
+                                  esz * (size_t)nb * p->H, hipMemcpyHostToDevice, p->s_in));
             HIPCHK(hipEventRecord(p->ev_in[slot], p->s_in));
             HIPCHK(hipStreamWaitEvent(s, p->ev_in[slot], 0));
         } else {
@@ -1596,8 +1723,7 @@ static int pipeline_work_impl(fdc_pipeline *p, const void *in, int nblocks, void
             if (feeder.err != hipSuccess) return fail(FDC_ERR_HIP, "input copy failed: %s", hipGetErrorString(feeder.err));
         }
         float2 *dok = p->d_out + (size_t)b0 * p->sum_lout;                    // [channel][nb*lout] of this sub-batch
-        rc = fdc_pipeline_process_device(p, p->d_ring + (size_t)b0 * p->H, p->blockcount + b0, nb, dok,
-                                         d_specfull ? d_specfull + (size_t)b0 * p->N : nullptr, s);
+        rc = process((size_t)b0, nb, p->blockcount + b0, dok, d_specfull ? d_specfull + (size_t)b0 * p->N : nullptr);
         if (rc != FDC_OK) return rc;
         if (p->C == 0) continue;
         HIPCHK(hipEventRecord(p->ev_k[slot], s));
@@ -1613,9 +1739,10 @@ static int pipeline_work_impl(fdc_pipeline *p, const void *in, int nblocks, void
     if (!out_reg && p->C > 0 && (rc = drain(K - 1)) != FDC_OK) return rc;
     if (spectrum) HIPCHK(hipMemcpyAsync(spectrum, d_specfull, sizeof(float2) * (size_t)nblocks * p->N, hipMemcpyDeviceToHost, s));
     // history <- last ovl samples of this call (overlap_save_impl.cc:78); src and dst never overlap (H >= ovl)
-    HIPCHK(hipMemcpyAsync(p->d_ring, p->d_ring + nin, sizeof(float2) * (size_t)p->ovl, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(ringb, ringb + esz * nin, esz * (size_t)p->ovl, hipMemcpyDeviceToDevice, s));
     HIPCHK(hipStreamSynchronize(s));
     HIPCHK(hipStreamSynchronize(p->s_out));
+    if (fmt) p->iq_route = std::string(iq_name(fmt)) + (all_fused ? ": fused" : ": widened");
     p->blockcount += nblocks;
     return nblocks;
 }
@@ -1689,9 +1816,12 @@ static int pipeline_work_real_impl(fdc_pipeline *p, const void *in, int nblocks,
     if (nblocks > p->cfg.max_blocks) return fail(FDC_ERR_INVALID_ARGUMENT, "nblocks %d above max_blocks %d", nblocks, p->cfg.max_blocks);
     if (!in || (p->C > 0 && !outs)) return fail(FDC_ERR_INVALID_ARGUMENT, "null host buffer");
     if (spectrum && !p->cfg.keep_spectrum) return fail(FDC_ERR_INVALID_ARGUMENT, "spectrum output needs keep_spectrum");
-    HIPCHK(hipSetDevice(p->cfg.device_id));
-    int rc = work_io_setup(p);
+    int rc = check_form(p, 0, 0.f);
     if (rc != FDC_OK) return rc;
+    HIPCHK(hipSetDevice(p->cfg.device_id));
+    rc = work_io_setup(p);
+    if (rc != FDC_OK) return rc;
+    latch_form(p, 0, 0.f);
     hipStream_t s = p->stream;
     const size_t nin = (size_t)nblocks * p->H;
     // d_real: [N/R history samples of a span call][max_blocks*H new samples]
@@ -1736,6 +1866,28 @@ int fdc_pipeline_work_span_real(fdc_pipeline *p, const void *halo, const void *i
     FDC_ENTRY_END
 }
 
+int fdc_pipeline_work_iq(fdc_pipeline *p, int32_t format, float scale, const void *in, int nblocks, void *const *outs, void *spectrum)
+{
+    FDC_ENTRY("fdc_pipeline_work_iq")
+    if (!p) return fail(FDC_ERR_INVALID_ARGUMENT, "null handle");
+    const int rc = check_iq_form(format, scale);
+    if (rc != FDC_OK) return rc;
+    return pipeline_work_impl(p, in, nblocks, outs, spectrum, nullptr, false, nullptr, 0, format, scale);
+    FDC_ENTRY_END
+}
+
+int fdc_pipeline_work_span_iq(fdc_pipeline *p, int32_t format, float scale, const void *halo, const void *in, int64_t first_block, int nblocks,
+                              void *const *outs, void *spectrum)
+{
+    FDC_ENTRY("fdc_pipeline_work_span_iq")
+    if (!p) return fail(FDC_ERR_INVALID_ARGUMENT, "null handle");
+    const int rc = check_iq_form(format, scale);
+    if (rc != FDC_OK) return rc;
+    if (first_block < 0) return fail(FDC_ERR_INVALID_ARGUMENT, "negative block index");
+    return pipeline_work_impl(p, in, nblocks, outs, spectrum, nullptr, true, halo, first_block, format, scale);
+    FDC_ENTRY_END
+}
+
 // fdc_pipeline_work_sinks on a bank created with FDC_SINKS_LOOKAHEAD: the pipelined hier block.  What one call does:
 //   - the items' copy to the device (own stream), their forward transform (+ channel kernels) into the bank's NEXT-batch buffer and its
 //     power cells (fdc_sinks_prepare) — all on the bank's fill stream, behind the copy;
@@ -1755,9 +1907,11 @@ static int work_sinks_pipelined(fdc_pipeline *p, const void *in, int nblocks, vo
     if (p->hier_bank && p->hier_bank != sinks && p->hier_filled > 0)
         return fail(FDC_ERR_INVALID_ARGUMENT, "a batch of another bank is still inside this pipeline: fdc_pipeline_flush_sinks() with that bank first");
     if (p->hier_broken) return fail(FDC_ERR_HIP, "an earlier pipelined call failed after it had advanced the stream state: destroy the pipeline and the bank");
-    HIPCHK(hipSetDevice(p->cfg.device_id));
-    int rc = work_io_setup(p);
+    int rc = check_form(p, 0, 0.f);
     if (rc != FDC_OK) return rc;
+    HIPCHK(hipSetDevice(p->cfg.device_id));
+    if ((rc = work_io_setup(p)) != FDC_OK) return rc;
+    latch_form(p, 0, 0.f);
     if (!p->ev_hier) {
         HIPCHK(hipEventCreateWithFlags(&p->ev_hier, hipEventDisableTiming));
         HIPCHK(hipStreamSynchronize(p->stream));                  // work_io_setup zeroes the history on the handle's own stream; this entry runs on others

@@ -34,6 +34,7 @@
 #include "fdc_kernels.h"
 #include "fdc_radix16.hpp"
 #include "fdc_devutil.hpp"
+#include "fdc_iq.hpp"
 
 namespace fdc {
 
@@ -152,17 +153,23 @@ __device__ __forceinline__ void blk_pass_dft(cf (&a)[P])
 #ifndef FDC_FWD_TWO_WG
 #define FDC_FWD_TWO_WG 0
 #endif
-template <int P, bool NT, bool OFF, bool FWD, bool R4 = false, bool STG = false, bool HALF = false>
-__global__ FDC_PLAIN_DS __launch_bounds__(512, (P == 2 && !OFF && !R4 && !FWD) ? 4 : 2) void k_blk256(const float2 *__restrict__ in, size_t in_stride, float2 *__restrict__ out,
+// TI: the input sample, float2 or complex integer (sc16 / sc8: fdc_iq.hpp); integer rows are loaded as they are (4 / 2 bytes a sample) and
+// widened in registers at the top of the pass that transforms them, times iq_scale
+template <int P, bool NT, bool OFF, bool FWD, bool R4 = false, bool STG = false, bool HALF = false, class TI = float2>
+__global__ FDC_PLAIN_DS __launch_bounds__(512, (P == 2 && !OFF && !R4 && !FWD) ? 4 : 2) void k_blk256(const TI *__restrict__ in, size_t in_stride, float2 *__restrict__ out,
                                                 const float2 *__restrict__ tw256, const float2 *__restrict__ twq,
                                                 const float2 *__restrict__ cbt, const float *__restrict__ shn,
                                                 const long long *__restrict__ slot_off, long long out_base,
                                                 long long nb_call, unsigned out_bytes, int nb, int hints,
                                                 unsigned long long *__restrict__ dbg, int roff, long long first_block,
                                                 float2 *__restrict__ fwd_scratch, const unsigned *__restrict__ keep,
-                                                float *__restrict__ gpow)
+                                                typename IqTail<TI>::type gpow /* integer TI: iq_scale */)
 {
     typedef BlkGeom<P> GM;
+    constexpr bool kIq = !std::is_same<TI, float2>::value;
+    static_assert(!kIq || (!STG && !FWD), "integer input: the channelizer forms (the forward transform and the staged loads take widened input)");
+    constexpr unsigned kEs = (unsigned)sizeof(TI);                              // bytes per input sample
+    [[maybe_unused]] const float iq_scale = iq_tail_scale(gpow);
     static_assert(!STG || (P == 8 && !OFF && !R4), "staged loads: the plain channelizer and the forward transform at N = 65536");
     static_assert(!HALF || (!OFF && !FWD && !STG), "the half-slot form is a variant of the on-grid channelizer");
     constexpr int kN1 = GM::kN1, kLd = GM::kLd, kJT = GM::kJT, kJB = GM::kJB;
@@ -209,9 +216,15 @@ __global__ FDC_PLAIN_DS __launch_bounds__(512, (P == 2 && !OFF && !R4 && !FWD) ?
     if ((blockIdx.x >> 3) & 1) for (int i = 0; i < FDC_BLK_STAGGER; i++) __builtin_amdgcn_s_sleep(127);
 #endif
 
-    constexpr unsigned inbytes = (unsigned)GM::kN * 8u;
-    constexpr unsigned kRowGrp = (unsigned)kN1 * 128u;            // 16 rows of kN1 columns, bytes (P = 8: 32 KiB)
-    const unsigned voff = (unsigned)(b * kN1 + c5) * 8u;          // row b, column c5 of pass 0; pass adds 256 B, row group a 16 rows
+    constexpr unsigned inbytes = (unsigned)GM::kN * kEs;
+    constexpr unsigned kRowGrp = (unsigned)kN1 * 16u * kEs;       // 16 rows of kN1 columns, bytes (P = 8, float2: 32 KiB)
+    const unsigned voff = (unsigned)(b * kN1 + c5) * kEs;         // row b, column c5 of pass 0; pass adds 32 samples, row group a 16 rows
+    // one input sample: float2 as before; an integer sample's raw bits in .x (.y a constant the compiler drops), widened by iq_widen_bits
+    [[maybe_unused]] auto ld_in = [&](__amdgpu_buffer_rsrc_t r, unsigned soff, auto aux) __attribute__((always_inline)) -> cf {
+        constexpr int kAux = decltype(aux)::value;                // 0, or 2 = nt (hints bit 1)
+        if constexpr (sizeof(TI) == 4) return mk(__uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, kAux)), 0.f);
+        else return mk(__uint_as_float((unsigned)__builtin_amdgcn_raw_buffer_load_b16(r, voff, soff, kAux)), 0.f);
+    };
     // the first block's rows are requested before the tables are built: their latency hides behind the table set-up
     const __amdgpu_buffer_rsrc_t rcb = make_rsrc(cbt, (unsigned)kN1 * 16u * 8u);      // cbt[n1][b], n1 = 32 pass + c5
     const unsigned voffc = (unsigned)(c5 * 16 + b) * 8u;
@@ -234,7 +247,10 @@ __global__ FDC_PLAIN_DS __launch_bounds__(512, (P == 2 && !OFF && !R4 && !FWD) ?
     } else {
         const __amdgpu_buffer_rsrc_t rin = make_rsrc(in + (size_t)first * in_stride, inbytes);
 #pragma unroll
-        for (int a = 0; a < 16; a++) LA[a] = bld2(rin, voff, (unsigned)a * kRowGrp);
+        for (int a = 0; a < 16; a++) {
+            if constexpr (kIq) LA[a] = ld_in(rin, (unsigned)a * kRowGrp, std::integral_constant<int, 0>{});
+            else LA[a] = bld2(rin, voff, (unsigned)a * kRowGrp);
+        }
         cbA = bld2(rcb, voffc, 0);
     }
     // ---- tables (once per workgroup; the workgroup is persistent)
@@ -348,7 +364,15 @@ __global__ FDC_PLAIN_DS __launch_bounds__(512, (P == 2 && !OFF && !R4 && !FWD) ?
                 // the pass offset (32 columns) sits in the descriptor's base: every pass uses the same per-lane offset and the
                 // same 16 scalar row offsets
                 const __amdgpu_buffer_rsrc_t rin = make_rsrc(in + (size_t)mb * in_stride + 32 * pn, inbytes);
-                if (hints & 2) {
+                if constexpr (kIq) {
+                    if (hints & 2) {
+#pragma unroll
+                        for (int a = 0; a < 16; a++) L[a] = ld_in(rin, (unsigned)a * kRowGrp, std::integral_constant<int, 2>{});
+                    } else {
+#pragma unroll
+                        for (int a = 0; a < 16; a++) L[a] = ld_in(rin, (unsigned)a * kRowGrp, std::integral_constant<int, 0>{});
+                    }
+                } else if (hints & 2) {
 #pragma unroll
 #ifdef FDC_BLK_SC1LOADS
                     for (int a = 0; a < 16; a++) L[a] = bld2_sc1(rin, voff, (unsigned)a * kRowGrp);
@@ -360,6 +384,10 @@ __global__ FDC_PLAIN_DS __launch_bounds__(512, (P == 2 && !OFF && !R4 && !FWD) ?
                     for (int a = 0; a < 16; a++) L[a] = bld2(rin, voff, (unsigned)a * kRowGrp);
                 }
                 cbn = bld2(rcb, voffc, (unsigned)pn * 4096u);
+            }
+            if constexpr (kIq) {
+#pragma unroll
+                for (int a = 0; a < 16; a++) cur[a] = iq_widen_bits(TI{}, __float_as_uint(cur[a].x), iq_scale);
             }
             dft16<false>(cur);                                    // in place, over a: index p in cur[rev16(p)]
             cf tw[16];
@@ -675,9 +703,34 @@ __global__ FDC_PLAIN_DS __launch_bounds__(512, (P == 2 && !OFF && !R4 && !FWD) ?
 #define FDC_FWD_STAGED 0
 #endif
 
-hipError_t init_block_kernels()
+// the channelizer forms of one input type (TI != float2: the integer-input instantiations, fdc_pipeline_work_iq)
+template <class TI>
+static hipError_t init_block_kernels_in()
 {
     hipError_t e;
+#define FDC_SETB(P, A, B, R4) \
+    e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_blk256<P, A, B, false, R4, false, false, TI>), hipFuncAttributeMaxDynamicSharedMemorySize, \
+                            B ? BlkGeom<P>::kLdsOff : BlkGeom<P>::kLds); \
+    if (e != hipSuccess) return e;
+#define FDC_SETH(P, A, R4) \
+    e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_blk256<P, A, false, false, R4, false, true, TI>), hipFuncAttributeMaxDynamicSharedMemorySize, BlkGeom<P>::kLds); \
+    if (e != hipSuccess) return e;
+#define FDC_SETP(P) \
+    FDC_SETB(P, true, false, false) FDC_SETB(P, false, false, false) FDC_SETB(P, true, true, false) FDC_SETB(P, false, true, false) \
+    FDC_SETB(P, true, false, true) FDC_SETB(P, false, false, true) FDC_SETB(P, true, true, true) FDC_SETB(P, false, true, true) \
+    FDC_SETH(P, true, false) FDC_SETH(P, false, false) FDC_SETH(P, true, true) FDC_SETH(P, false, true)
+    FDC_SETP(2) FDC_SETP(4) FDC_SETP(8)
+#undef FDC_SETP
+#undef FDC_SETH
+#undef FDC_SETB
+    return hipSuccess;
+}
+
+hipError_t init_block_kernels()
+{
+    hipError_t e = init_block_kernels_in<sc16>();
+    if (e != hipSuccess) return e;
+    if ((e = init_block_kernels_in<sc8>()) != hipSuccess) return e;
 #define FDC_SETB(P, A, B, F, R4) \
     e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_blk256<P, A, B, F, R4>), hipFuncAttributeMaxDynamicSharedMemorySize, \
                             B ? BlkGeom<P>::kLdsOff : BlkGeom<P>::kLds); \
@@ -715,13 +768,18 @@ hipError_t init_block_kernels()
 
 bool poly_block_supports(int N) { return N == 16384 || N == 32768 || N == 65536; }
 
-hipError_t launch_poly_block(const float2 *in, size_t in_stride, float2 *out, int nb_chunk, int mbase, int nb_call,
-                             const float2 *tw256, const float2 *twq, const float2 *cbt, const float *shn,
-                             const long long *slot_off, unsigned out_bytes, int ncu, int hints, hipStream_t s,
-                             unsigned long long *dbg, int r, long long first_block, hipEvent_t ev_start, hipEvent_t ev_stop, int R,
-                             float2 *scratch, int N)
+template <class TI>
+static hipError_t poly_block_in(const TI *in, size_t in_stride, float2 *out, int nb_chunk, int mbase, int nb_call,
+                                const float2 *tw256, const float2 *twq, const float2 *cbt, const float *shn,
+                                const long long *slot_off, unsigned out_bytes, int ncu, int hints, hipStream_t s,
+                                unsigned long long *dbg, int r, long long first_block, hipEvent_t ev_start, hipEvent_t ev_stop, int R,
+                                float2 *scratch, int N, float iq_scale)
 {
     if (nb_chunk <= 0) return hipSuccess;
+    // the kernel's last argument: float2 input, no group powers (null); integer input, the scale (IqTail)
+    auto iq_tail = [](float sc) -> typename IqTail<TI>::type {
+        if constexpr (std::is_same<TI, float2>::value) return (void)sc, (float *)nullptr; else return sc;
+    };
     const bool halfslot = (r & 255) == 128;                 // half a slot: the on-grid kernel with its tables moved (HALF), R = 2 and 4
     if (!poly_block_supports(N) || (R != 2 && R != 4) || (R == 4 && !scratch)) return hipErrorInvalidValue;
     int grid = ncu > 0 ? ncu : 256;                         // one 512-thread workgroup per CU (LDS: up to 159.5 KiB each)
@@ -734,13 +792,15 @@ hipError_t launch_poly_block(const float2 *in, size_t in_stride, float2 *out, in
     // in front of or behind the kernel, unlike hipEventRecord (measured 7-17 us per bracketed launch)
     // R = 4: three quarters of every inverse transform kept: 192 rows per block, 64 of them via the scratch
 #define FDC_LB(P, A, B, R4) \
-    hipExtLaunchKernelGGL((k_blk256<P, A, B, false, R4>), dim3((unsigned)grid), dim3(512), B ? BlkGeom<P>::kLdsOff : BlkGeom<P>::kLds, s, ev_start, \
-                          ev_stop, 0u, in, in_stride, out, tw256, twq, cbt, shn, slot_off, (long long)mbase * (R4 ? 192 : 128), (long long)nb_call, \
-                          out_bytes, nb_chunk, hints, dbg, r & 255, first_block, R4 ? scratch : (float2 *)nullptr, (const unsigned *)nullptr, (float *)nullptr)
+    hipExtLaunchKernelGGL((k_blk256<P, A, B, false, R4, false, false, TI>), dim3((unsigned)grid), dim3(512), B ? BlkGeom<P>::kLdsOff : BlkGeom<P>::kLds, s, \
+                          ev_start, ev_stop, 0u, in, in_stride, out, tw256, twq, cbt, shn, slot_off, (long long)mbase * (R4 ? 192 : 128), (long long)nb_call, \
+                          out_bytes, nb_chunk, hints, dbg, r & 255, first_block, R4 ? scratch : (float2 *)nullptr, (const unsigned *)nullptr, \
+                          iq_tail(iq_scale))
 #define FDC_LH(P, A, R4) \
-    hipExtLaunchKernelGGL((k_blk256<P, A, false, false, R4, false, true>), dim3((unsigned)grid), dim3(512), BlkGeom<P>::kLds, s, ev_start, \
+    hipExtLaunchKernelGGL((k_blk256<P, A, false, false, R4, false, true, TI>), dim3((unsigned)grid), dim3(512), BlkGeom<P>::kLds, s, ev_start, \
                           ev_stop, 0u, in, in_stride, out, tw256, twq, cbt, shn, slot_off, (long long)mbase * (R4 ? 192 : 128), (long long)nb_call, \
-                          out_bytes, nb_chunk, hints, dbg, 0, first_block, R4 ? scratch : (float2 *)nullptr, (const unsigned *)nullptr, (float *)nullptr)
+                          out_bytes, nb_chunk, hints, dbg, 0, first_block, R4 ? scratch : (float2 *)nullptr, (const unsigned *)nullptr, \
+                          iq_tail(iq_scale))
 #define FDC_LP(P) \
     do { \
         if (halfslot) { \
@@ -752,21 +812,46 @@ hipError_t launch_poly_block(const float2 *in, size_t in_stride, float2 *out, in
         else { if (hints & 1) FDC_LB(P, true, false, false); else FDC_LB(P, false, false, false); } \
     } while (0)
 #if FDC_BLK_STAGED
-    if (N == 65536 && R == 2 && !(r & 255)) {
+    if constexpr (std::is_same<TI, float2>::value) if (N == 65536 && R == 2 && !(r & 255)) {
         // the plain channelizer with its loads staged through LDS
 #define FDC_LS(A) \
         hipExtLaunchKernelGGL((k_blk256<8, A, false, false, false, true>), dim3((unsigned)grid), dim3(512), BlkGeom<8>::kLdsS, s, ev_start, ev_stop, 0u, in, \
                               in_stride, out, tw256, twq, cbt, shn, slot_off, (long long)mbase * 128, (long long)nb_call, out_bytes, nb_chunk, hints, dbg, 0, \
                               first_block, (float2 *)nullptr, (const unsigned *)nullptr, (float *)nullptr)
         if (hints & 1) FDC_LS(true); else FDC_LS(false);
+        return hipGetLastError();
 #undef FDC_LS
-    } else
+    }
 #endif
     if (N == 65536) FDC_LP(8); else if (N == 32768) FDC_LP(4); else FDC_LP(2);
 #undef FDC_LP
 #undef FDC_LH
 #undef FDC_LB
     return hipGetLastError();
+}
+
+hipError_t launch_poly_block(const float2 *in, size_t in_stride, float2 *out, int nb_chunk, int mbase, int nb_call,
+                             const float2 *tw256, const float2 *twq, const float2 *cbt, const float *shn,
+                             const long long *slot_off, unsigned out_bytes, int ncu, int hints, hipStream_t s,
+                             unsigned long long *dbg, int r, long long first_block, hipEvent_t ev_start, hipEvent_t ev_stop, int R,
+                             float2 *scratch, int N)
+{
+    return poly_block_in(in, in_stride, out, nb_chunk, mbase, nb_call, tw256, twq, cbt, shn, slot_off, out_bytes, ncu, hints, s, dbg, r, first_block,
+                         ev_start, ev_stop, R, scratch, N, 1.0f);
+}
+
+hipError_t launch_poly_block_iq(int fmt, float scale, const void *in, size_t in_stride, float2 *out, int nb_chunk, int mbase, int nb_call,
+                                const float2 *tw256, const float2 *twq, const float2 *cbt, const float *shn,
+                                const long long *slot_off, unsigned out_bytes, int ncu, int hints, hipStream_t s,
+                                int r, long long first_block, hipEvent_t ev_start, hipEvent_t ev_stop, int R, float2 *scratch, int N)
+{
+    if (fmt == kIqSc16)
+        return poly_block_in(static_cast<const sc16 *>(in), in_stride, out, nb_chunk, mbase, nb_call, tw256, twq, cbt, shn, slot_off, out_bytes, ncu, hints, s,
+                             nullptr, r, first_block, ev_start, ev_stop, R, scratch, N, scale);
+    if (fmt == kIqSc8)
+        return poly_block_in(static_cast<const sc8 *>(in), in_stride, out, nb_chunk, mbase, nb_call, tw256, twq, cbt, shn, slot_off, out_bytes, ncu, hints, s,
+                             nullptr, r, first_block, ev_start, ev_stop, R, scratch, N, scale);
+    return hipErrorInvalidValue;
 }
 
 // Forward transform of nitems blocks of 65536 samples (item m at in + m*in_stride) into the shifted, 1/N-scaled spectrum

@@ -23,6 +23,8 @@
 #include "fdc_kernels.h"
 #include "fdc_radix16.hpp"
 #include "fdc_devutil.hpp"
+#include <type_traits>
+#include "fdc_iq.hpp"
 
 namespace fdc {
 
@@ -91,12 +93,14 @@ __device__ __forceinline__ RowAt row_at(const F4Row &ri, int L, int m0, int nb, 
 // 5 = l = 128, 6 = l = 64, 7 = l = 32, 8 = l = 16 (slots 0..7 each)
 // ROWS: the waterfall epilogue (fdc_waterfall.hip): wf[m][p] = sum of |X|^2 over shifted bins 4 p .. 4 p + 3 of the 1/N-scaled spectrum, taken from the
 // registers the spectrum store leaves; ROWS = false is the kernel without it, instruction for instruction
-template <bool WIDE, int TEAMS, bool ROWS>
-__global__ __launch_bounds__(256 * TEAMS, 4 /* waves per SIMD */) void k_f4096(const float2 *__restrict__ in, size_t in_stride, float2 *__restrict__ out, int nb, int R,
+// TI: the input sample, float2 or complex integer (sc16 / sc8, fdc_iq.hpp: widened times iq_scale right after its load)
+template <bool WIDE, int TEAMS, bool ROWS, class TI = float2>
+__global__ __launch_bounds__(256 * TEAMS, 4 /* waves per SIMD */) void k_f4096(const TI *__restrict__ in, size_t in_stride, float2 *__restrict__ out, int nb, int R,
                                                   int mbase, int nb_call, int fbm /* (first block of the call + mbase) mod R */, const float2 *__restrict__ tw,
                                                   int twstride /* ntab / 4096 */, const float2 *__restrict__ wins,
-                                                  const F4Row *__restrict__ rows, unsigned wcls, float *__restrict__ wf)
+                                                  const F4Row *__restrict__ rows, unsigned wcls, typename IqTail<TI>::type wf /* integer TI: iq_scale */)
 {
+    [[maybe_unused]] const float iq_scale = iq_tail_scale(wf);
     float2 *tiles = reinterpret_cast<float2 *>(fdc_smem_f4);
     float2 *t256 = reinterpret_cast<float2 *>(fdc_smem_f4 + f4_off_t256(TEAMS));
     float2 *t4k = reinterpret_cast<float2 *>(fdc_smem_f4 + f4_off_t4k(TEAMS));
@@ -125,10 +129,21 @@ __global__ __launch_bounds__(256 * TEAMS, 4 /* waves per SIMD */) void k_f4096(c
     cf v[32];
     {
         cf (&u)[16] = reinterpret_cast<cf (&)[16]>(v[0]);
+        // integer input: the sixteen raw words first, all in flight together; widened behind the barrier (converted one by one as they
+        // arrive, the compiler waited for each load before issuing the next)
+        [[maybe_unused]] unsigned raw[16];
+        if constexpr (!std::is_same<TI, float2>::value) {
+#pragma unroll
+            for (int c = 0; c < 16; c++) raw[c] = m < nb ? iq_bits(in + (size_t)m * in_stride + (tid + 256 * c)) : 0u;
+        } else
 #pragma unroll
         for (int c = 0; c < 16; c++) u[c] = m < nb ? ((F4_NT & 2) ? __builtin_nontemporal_load(reinterpret_cast<const cf *>(in + (size_t)m * in_stride + (tid + 256 * c)))
                                                                    : ld2(in + ((F4_EXP & 1) ? (size_t)(tid & 15) + 16 * c : (size_t)m * in_stride + (tid + 256 * c)))) : mk(0.f, 0.f);
         __syncthreads();
+        if constexpr (!std::is_same<TI, float2>::value) {
+#pragma unroll
+            for (int c = 0; c < 16; c++) u[c] = iq_widen_bits(TI{}, raw[c], iq_scale);
+        }
         dft16<false>(u);                                             // layer 1 over c: k0 in u[rev16(k0)]; thread = (a = lo, b = hi)
         {
             cf w[16];
@@ -403,38 +418,54 @@ __global__ __launch_bounds__(256 * TEAMS, 4 /* waves per SIMD */) void k_f4096(c
     }
 }
 
-template <bool ROWS>
+template <bool ROWS, class TI = float2>
 static hipError_t init_fused4096_forms()
 {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_f4096<false, 2, ROWS>), hipFuncAttributeMaxDynamicSharedMemorySize, f4_lds(2));
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_f4096<false, 2, ROWS, TI>), hipFuncAttributeMaxDynamicSharedMemorySize, f4_lds(2));
     if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_f4096<false, 1, ROWS>), hipFuncAttributeMaxDynamicSharedMemorySize, f4_lds(1));
+    e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_f4096<false, 1, ROWS, TI>), hipFuncAttributeMaxDynamicSharedMemorySize, f4_lds(1));
     if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_f4096<true, 1, ROWS>), hipFuncAttributeMaxDynamicSharedMemorySize, f4_lds_wide(1));
+    e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_f4096<true, 1, ROWS, TI>), hipFuncAttributeMaxDynamicSharedMemorySize, f4_lds_wide(1));
     if (e != hipSuccess) return e;
-    return hipFuncSetAttribute(reinterpret_cast<const void *>(k_f4096<true, 2, ROWS>), hipFuncAttributeMaxDynamicSharedMemorySize, f4_lds_wide(2));
+    return hipFuncSetAttribute(reinterpret_cast<const void *>(k_f4096<true, 2, ROWS, TI>), hipFuncAttributeMaxDynamicSharedMemorySize, f4_lds_wide(2));
 }
 
 hipError_t init_fused4096_kernels()
 {
-    const hipError_t e = init_fused4096_forms<false>();
-    return e != hipSuccess ? e : init_fused4096_forms<true>();
+    hipError_t e = init_fused4096_forms<false>();
+    if (e == hipSuccess) e = init_fused4096_forms<true>();
+    if (e == hipSuccess) e = init_fused4096_forms<false, sc16>();     // integer input: the channel outputs only (no ROWS form)
+    return e != hipSuccess ? e : init_fused4096_forms<false, sc8>();
 }
 
 int fused4096_tile_points() { return kF4TilePts; }
 
-template <bool ROWS>
-static void launch_fused4096_form(dim3 grid, bool wide, int teams, hipStream_t s, const float2 *in, size_t in_stride, float2 *out, int nb_chunk, int R,
-                                  int mbase, int nb_call, int fbm, const float2 *tw, int ntab, const float2 *wins, const F4Row *rows, unsigned wcls, float *wf)
+template <bool ROWS, class TI = float2>
+static void launch_fused4096_form(dim3 grid, bool wide, int teams, hipStream_t s, const TI *in, size_t in_stride, float2 *out, int nb_chunk, int R,
+                                  int mbase, int nb_call, int fbm, const float2 *tw, int ntab, const float2 *wins, const F4Row *rows, unsigned wcls,
+                                  typename IqTail<TI>::type wf /* integer TI: the scale */)
 {
     if (wide && teams == 1)
-        hipLaunchKernelGGL((k_f4096<true, 1, ROWS>), grid, dim3(256), f4_lds_wide(1), s, in, in_stride, out, nb_chunk, R, mbase, nb_call, fbm, tw, ntab / 4096, wins, rows, wcls, wf);
+        hipLaunchKernelGGL((k_f4096<true, 1, ROWS, TI>), grid, dim3(256), f4_lds_wide(1), s, in, in_stride, out, nb_chunk, R, mbase, nb_call, fbm, tw, ntab / 4096, wins, rows, wcls, wf);
     else if (wide)
-        hipLaunchKernelGGL((k_f4096<true, 2, ROWS>), grid, dim3(512), f4_lds_wide(2), s, in, in_stride, out, nb_chunk, R, mbase, nb_call, fbm, tw, ntab / 4096, wins, rows, wcls, wf);
+        hipLaunchKernelGGL((k_f4096<true, 2, ROWS, TI>), grid, dim3(512), f4_lds_wide(2), s, in, in_stride, out, nb_chunk, R, mbase, nb_call, fbm, tw, ntab / 4096, wins, rows, wcls, wf);
     else if (teams == 2)
-        hipLaunchKernelGGL((k_f4096<false, 2, ROWS>), grid, dim3(512), f4_lds(2), s, in, in_stride, out, nb_chunk, R, mbase, nb_call, fbm, tw, ntab / 4096, wins, rows, wcls, wf);
+        hipLaunchKernelGGL((k_f4096<false, 2, ROWS, TI>), grid, dim3(512), f4_lds(2), s, in, in_stride, out, nb_chunk, R, mbase, nb_call, fbm, tw, ntab / 4096, wins, rows, wcls, wf);
     else
-        hipLaunchKernelGGL((k_f4096<false, 1, ROWS>), grid, dim3(256), f4_lds(1), s, in, in_stride, out, nb_chunk, R, mbase, nb_call, fbm, tw, ntab / 4096, wins, rows, wcls, wf);
+        hipLaunchKernelGGL((k_f4096<false, 1, ROWS, TI>), grid, dim3(256), f4_lds(1), s, in, in_stride, out, nb_chunk, R, mbase, nb_call, fbm, tw, ntab / 4096, wins, rows, wcls, wf);
+}
+
+// The launch shape both entries share: whether a wave holds wide rows (l = 512 / 1024: the WIDE form), the grid (one workgroup per `teams`
+// blocks, a multiple of the eight XCDs) and fbm = (first block of the call + first block of the launch) mod R
+struct F4Shape { dim3 grid; bool wide; int fbm; };
+static hipError_t f4_shape(int nb_chunk, int R, int mbase, int64_t first_block, unsigned wcls, int teams, F4Shape *sh)
+{
+    if (teams != 2 && teams != 1) return hipErrorInvalidValue;
+    bool wide = false;
+    for (int w = 0; w < 8; w++) wide = wide || ((wcls >> (4 * w)) & 0xfu) == 3 || ((wcls >> (4 * w)) & 0xfu) == 4;
+    const int ngroups = (nb_chunk + teams - 1) / teams;
+    *sh = F4Shape{dim3((unsigned)(8 * ((ngroups + 7) / 8))), wide, (int)((first_block + mbase) % R)};
+    return hipSuccess;
 }
 
 // teams: blocks per workgroup the schedule was made for (1: rows[4 waves][8]; 2: rows[8 waves][8])
@@ -443,14 +474,28 @@ hipError_t launch_fused4096(const float2 *in, size_t in_stride, float2 *out, int
                             const float2 *tw, int ntab, const float2 *wins, const F4Row *rows, unsigned wcls, int teams, hipStream_t s, float *wf)
 {
     if (nb_chunk <= 0) return hipSuccess;
-    bool wide = false;
-    for (int w = 0; w < 8; w++) wide = wide || ((wcls >> (4 * w)) & 0xfu) == 3 || ((wcls >> (4 * w)) & 0xfu) == 4;
-    if (teams != 2 && teams != 1) return hipErrorInvalidValue;
-    const int ngroups = (nb_chunk + teams - 1) / teams;
-    const dim3 grid((unsigned)(8 * ((ngroups + 7) / 8)));
-    const int fbm = (int)((first_block + mbase) % R);
-    if (wf) launch_fused4096_form<true>(grid, wide, teams, s, in, in_stride, out, nb_chunk, R, mbase, nb_call, fbm, tw, ntab, wins, rows, wcls, wf);
-    else launch_fused4096_form<false>(grid, wide, teams, s, in, in_stride, out, nb_chunk, R, mbase, nb_call, fbm, tw, ntab, wins, rows, wcls, nullptr);
+    F4Shape sh;
+    const hipError_t e = f4_shape(nb_chunk, R, mbase, first_block, wcls, teams, &sh);
+    if (e != hipSuccess) return e;
+    if (wf) launch_fused4096_form<true>(sh.grid, sh.wide, teams, s, in, in_stride, out, nb_chunk, R, mbase, nb_call, sh.fbm, tw, ntab, wins, rows, wcls, wf);
+    else launch_fused4096_form<false>(sh.grid, sh.wide, teams, s, in, in_stride, out, nb_chunk, R, mbase, nb_call, sh.fbm, tw, ntab, wins, rows, wcls, nullptr);
+    return hipGetLastError();
+}
+
+hipError_t launch_fused4096_iq(int fmt, float scale, const void *in, size_t in_stride, float2 *out, int nb_chunk, int R, int mbase, int nb_call,
+                               int64_t first_block, const float2 *tw, int ntab, const float2 *wins, const F4Row *rows, unsigned wcls, int teams, hipStream_t s)
+{
+    if (nb_chunk <= 0) return hipSuccess;
+    if (fmt != kIqSc16 && fmt != kIqSc8) return hipErrorInvalidValue;
+    F4Shape sh;
+    const hipError_t e = f4_shape(nb_chunk, R, mbase, first_block, wcls, teams, &sh);
+    if (e != hipSuccess) return e;
+    if (fmt == kIqSc16)
+        launch_fused4096_form<false>(sh.grid, sh.wide, teams, s, static_cast<const sc16 *>(in), in_stride, out, nb_chunk, R, mbase, nb_call, sh.fbm, tw, ntab,
+                                     wins, rows, wcls, scale);
+    else
+        launch_fused4096_form<false>(sh.grid, sh.wide, teams, s, static_cast<const sc8 *>(in), in_stride, out, nb_chunk, R, mbase, nb_call, sh.fbm, tw, ntab,
+                                     wins, rows, wcls, scale);
     return hipGetLastError();
 }
 

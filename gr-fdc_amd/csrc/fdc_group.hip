@@ -17,10 +17,12 @@
 // arithmetic of the dispatcher is tested bit for bit on a one-GPU box (tests/test_group_gpu.py).
 #include "../../include/fdc_amd.h"
 #include "fdc_guard.hpp"
+#include "fdc_iq.hpp"
 
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <condition_variable>
 #include <cstring>
 #include <functional>
@@ -44,6 +46,8 @@ struct SpanJob {
     void *const *outs = nullptr;
     void *spectrum = nullptr;
     bool real = false;
+    int fmt = 0;                 // complex integer input (FDC_IQ_SC16 / FDC_IQ_SC8, times scale), 0 = float
+    float scale = 1.0f;
 };
 
 // one worker thread per member beyond the first (the first member's share runs on the calling thread)
@@ -61,6 +65,7 @@ struct Worker {
 
 int run_span(fdc_pipeline *p, const SpanJob &j)
 {
+    if (j.fmt) return fdc_pipeline_work_span_iq(p, j.fmt, j.scale, j.halo, j.in, j.first, j.n, j.outs, j.spectrum);
     return j.real ? fdc_pipeline_work_span_real(p, j.halo, j.in, j.first, j.n, j.outs, j.spectrum)
                   : fdc_pipeline_work_span(p, j.halo, j.in, j.first, j.n, j.outs, j.spectrum);
 }
@@ -139,6 +144,8 @@ struct fdc_pipeline_group {
     bool keep_spectrum = false;
     std::vector<int32_t> lout;
     std::vector<unsigned char> hist;                        // the last N/R samples of the stream so far (zeros at start, overlap_save_impl.cc:52)
+    int in_form = -1;                                       // input form latched by the first call after create / reset (fdc_pipeline_work_iq): -1 none,
+    float in_scale = 0.f;                                   // 0 float, FDC_IQ_SC16 / FDC_IQ_SC8 with in_scale
     size_t hist_item = 0;                                   // bytes per history sample: 8 (complex) until a real-input call makes it 4
     int64_t blockcount = 0;
     std::vector<std::vector<void *>> outs;                  // per member: the caller's output pointers moved to its span
@@ -163,7 +170,7 @@ void span_of(int n, int k, int i, int *first, int *cnt)      // balanced contigu
     *first = i * base + std::min(i, extra);
 }
 
-int group_work(fdc_pipeline_group *g, const void *in, int nblocks, void *const *outs, void *spectrum, bool real)
+int group_work(fdc_pipeline_group *g, const void *in, int nblocks, void *const *outs, void *spectrum, bool real, int fmt = 0, float scale = 1.0f)
 {
     if (!g) return fdc::set_error(FDC_ERR_INVALID_ARGUMENT, "null group handle");
     if (g->dead) return fdc::set_error(FDC_ERR_HIP, "the group failed in an earlier call: reset or destroy it");
@@ -176,10 +183,16 @@ int group_work(fdc_pipeline_group *g, const void *in, int nblocks, void *const *
     for (int c = 0; c < g->C; c++)
         if (!outs[c]) return fdc::set_error(FDC_ERR_INVALID_ARGUMENT, "null output buffer of channel %d", c);
     if (spectrum && !g->keep_spectrum) return fdc::set_error(FDC_ERR_INVALID_ARGUMENT, "spectrum output needs keep_spectrum");
-    const size_t item = real ? sizeof(float) : 2 * sizeof(float);
+    if (fmt && (fmt != FDC_IQ_SC16 && fmt != FDC_IQ_SC8)) return fdc::set_error(FDC_ERR_INVALID_ARGUMENT, "unknown complex integer format %d", fmt);
+    if (fmt && (!std::isfinite(scale) || scale == 0.0f)) return fdc::set_error(FDC_ERR_INVALID_ARGUMENT, "the scale must be finite and not zero");
+    if (g->in_form >= 0 && (g->in_form != fmt || (fmt && std::memcmp(&g->in_scale, &scale, sizeof(float)) != 0)))
+        return fdc::set_error(FDC_ERR_INVALID_ARGUMENT, "the group's input form was latched by its first work call (reset it to change the input form)");
+    const size_t item = fmt ? fdc::iq_bytes(fmt) : real ? sizeof(float) : 2 * sizeof(float);
     if (g->blockcount == 0) g->hist_item = item;
     if (item != g->hist_item)
         return fdc::set_error(FDC_ERR_INVALID_ARGUMENT, "complex and real input calls must not be mixed on one group (reset it first)");
+    g->in_form = fmt;                                       // latched: every check of the call is behind
+    g->in_scale = fmt ? scale : 0.f;
     const unsigned char *hin = static_cast<const unsigned char *>(in);
     const int k = members_for(g, nblocks);
     g->last_first.assign(g->mem.size(), 0);
@@ -201,6 +214,8 @@ int group_work(fdc_pipeline_group *g, const void *in, int nblocks, void *const *
         j.outs = g->outs[(size_t)i].data();
         j.spectrum = spectrum ? static_cast<unsigned char *>(spectrum) + (size_t)b0 * (size_t)g->N * 8 : nullptr;
         j.real = real;
+        j.fmt = fmt;
+        j.scale = scale;
         g->last_first[(size_t)i] = j.first; g->last_n[(size_t)i] = nb;
         if (i == 0) { job0 = j; continue; }
         fdc_pipeline *pm = g->mem[(size_t)i];
@@ -304,12 +319,23 @@ int fdc_pipeline_group_work_real(fdc_pipeline_group *g, const void *in, int nblo
     FDC_ENTRY_END
 }
 
+int fdc_pipeline_group_work_iq(fdc_pipeline_group *g, int32_t format, float scale, const void *in, int nblocks, void *const *outs, void *spectrum)
+{
+    FDC_ENTRY("fdc_pipeline_group_work_iq")
+    if (format == 0) return fdc::set_error(FDC_ERR_INVALID_ARGUMENT, "unknown complex integer format 0");
+    return group_work(g, in, nblocks, outs, spectrum, false, format, scale);
+    FDC_ENTRY_END
+}
+
 void fdc_pipeline_group_reset(fdc_pipeline_group *g)
 {
     if (!g) return;
     std::fill(g->hist.begin(), g->hist.end(), 0);
     g->blockcount = 0;
     g->hist_item = 8;
+    g->in_form = -1;
+    g->in_scale = 0.f;
+    for (fdc_pipeline *p : g->mem) fdc_pipeline_reset(p);      // the members' input-form latches (their history comes with every span)
     g->dead = false;
 }
 

@@ -1,0 +1,48 @@
+// Complex integer input (fdc_pipeline_work_iq and friends): interleaved int16 (sc16) or int8 (sc8) I/Q, sample k = (I_k * scale, Q_k * scale).
+// The int -> float conversion is exact; the product is rounded once in f32 and kept out of FMA contraction with whatever consumes it (the first
+// butterfly of a transform), so a kernel that converts in its own loads gives the bytes of the complex path on the numpy-converted input.
+#pragma once
+#include <hip/hip_runtime.h>
+#include "fdc_radix16.hpp"
+
+namespace fdc {
+
+enum IqFormat { kIqFloat = 0, kIqSc16 = 1, kIqSc8 = 2 };   // kIqSc16 / kIqSc8 = FDC_IQ_SC16 / FDC_IQ_SC8 (include/fdc_amd.h)
+
+struct __attribute__((aligned(4))) sc16 { short i, q; };
+struct __attribute__((aligned(2))) sc8 { signed char i, q; };
+
+inline size_t iq_bytes(int fmt) { return fmt == kIqSc16 ? 4 : fmt == kIqSc8 ? 2 : 8; }
+constexpr size_t kIqRingBytes = 4;      // bytes per sample of the widest integer format (sc16): what a handle's integer ring is sized for
+
+__device__ __forceinline__ float iq_mul(float a, float s)
+{
+#pragma clang fp contract(off)
+    return a * s;      // (__fmul_rn is a plain, contractable product in this HIP)
+}
+__device__ __forceinline__ cf iq_widen(sc16 v, float s) { return mk(iq_mul((float)v.i, s), iq_mul((float)v.q, s)); }
+__device__ __forceinline__ cf iq_widen(sc8 v, float s) { return mk(iq_mul((float)v.i, s), iq_mul((float)v.q, s)); }
+__device__ __forceinline__ cf iq_widen(float2 v, float) { return mk(v.x, v.y); }
+
+// The last argument of the kernels with integer forms (k_blk256, k_f4096): the float2 forms' epilogue output pointer, which the integer forms never
+// use; they take the scale in its place, so the argument block of every float2 form stays what it was
+template <class TI> struct IqTail { typedef float type; };
+template <> struct IqTail<float2> { typedef float *__restrict__ type; };
+__device__ __forceinline__ float iq_tail_scale(float s) { return s; }
+__device__ __forceinline__ float iq_tail_scale(const float *) { return 1.0f; }
+
+// one sample's raw bits (a dword / a 16-bit load), widened later by iq_widen_bits
+__device__ __forceinline__ unsigned iq_bits(const sc16 *p) { return *reinterpret_cast<const unsigned *>(p); }
+__device__ __forceinline__ unsigned iq_bits(const sc8 *p) { return *reinterpret_cast<const unsigned short *>(p); }
+
+// raw sample bits in a buffer-load register: sc16 one dword, sc8 the low half of one (a 2-byte load)
+__device__ __forceinline__ cf iq_widen_bits(sc16, unsigned u, float s)
+{
+    return mk(iq_mul((float)(int)(short)(u & 0xFFFFu), s), iq_mul((float)(int)(short)(u >> 16), s));
+}
+__device__ __forceinline__ cf iq_widen_bits(sc8, unsigned u, float s)
+{
+    return mk(iq_mul((float)(int)(signed char)(u & 0xFFu), s), iq_mul((float)(int)(signed char)((u >> 8) & 0xFFu), s));
+}
+
+}  // namespace fdc

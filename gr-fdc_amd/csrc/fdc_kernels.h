@@ -94,6 +94,9 @@ int fused4096_tile_points();
 hipError_t launch_fused4096(const float2 *in, size_t in_stride, float2 *out, int nb_chunk, int R, int mbase, int nb_call, int64_t first_block,
                             const float2 *tw, int ntab, const float2 *wins, const F4Row *rows, unsigned wcls, int teams /* blocks per workgroup: 1 (rows[4][8], no wide rows) or 2 (rows[8][8]) */, hipStream_t s,
                             float *wf = nullptr /* nb_chunk x 1024 waterfall row sums (fdc_waterfall.hip), or NULL */);
+// the same on complex integer input (fmt: kIqSc16 / kIqSc8, fdc_iq.hpp; item m at in + m*in_stride samples), widened in the kernel's loads
+hipError_t launch_fused4096_iq(int fmt, float scale, const void *in, size_t in_stride, float2 *out, int nb_chunk, int R, int mbase, int nb_call,
+                               int64_t first_block, const float2 *tw, int ntab, const float2 *wins, const F4Row *rows, unsigned wcls, int teams, hipStream_t s);
 
 // uniform plan (all channels l = 256, f = 256*slot, N = 256*N1): stage 1 + stage 2, no spectrum in memory.
 //   twq[n1][q] = W_N^(16*n1*q), cbt[n1][b] = (-1)^n1 W_N^(n1*b)  (16 entries per n1 each), shn[k2] = shape[k2]/N;
@@ -135,6 +138,11 @@ hipError_t launch_poly_block(const float2 *in, size_t in_stride, float2 *out, in
                              hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr /* timing: stamped by the dispatch itself */,
                              int R = 2 /* 2 or 4 */, float2 *scratch = nullptr /* R = 4: ncu x 32768 points */,
                              int N = 65536 /* block length: 16384, 32768 or 65536 (poly_block_supports) */);
+// the same on complex integer input (fmt: kIqSc16 / kIqSc8, fdc_iq.hpp; in_stride in samples), widened in the kernel's loads (the channelizer forms)
+hipError_t launch_poly_block_iq(int fmt, float scale, const void *in, size_t in_stride, float2 *out, int nb_chunk, int mbase, int nb_call,
+                                const float2 *tw256, const float2 *twq, const float2 *cbt, const float *shn,
+                                const long long *slot_off, unsigned out_bytes, int ncu, int hints, hipStream_t s,
+                                int r, long long first_block, hipEvent_t ev_start, hipEvent_t ev_stop, int R, float2 *scratch, int N);
 bool poly_block_supports(int N);
 
 // uniform plan of 512-bin channels on the 512-bin grid, N = 65536, R = 2 or 4: one kernel, one block per CU (fdc_block512.hip): the two
@@ -191,6 +199,8 @@ hipError_t launch_group_power(const float2 *spec, int N, int nblocks, float *gpo
 
 // real samples -> complex samples with zero imaginary part (the real-input front end)
 hipError_t launch_real_to_complex(const float *in, float2 *out, size_t n, hipStream_t s);
+// complex integer samples (fmt: kIqSc16 / kIqSc8, fdc_iq.hpp) -> complex float, (I * scale, Q * scale)
+hipError_t launch_iq_to_complex(int fmt, float scale, const void *in, float2 *out, size_t n, hipStream_t s);
 
 hipError_t launch_scale(const float2 *in, float2 *out, size_t n, float k, hipStream_t s);
 

@@ -17,6 +17,7 @@
 #include "fdc_kernels.h"
 #include <cstdlib>
 #include "fdc_radix16.hpp"
+#include "fdc_iq.hpp"
 
 namespace fdc {
 
@@ -976,6 +977,23 @@ hipError_t launch_real_to_complex(const float *in, float2 *out, size_t n, hipStr
     if (!n) return hipSuccess;
     size_t g = (n + 255) / 256; if (g > 8192) g = 8192;
     hipLaunchKernelGGL(k_real_to_complex, dim3((unsigned)g), dim3(256), 0, s, in, out, n);
+    return hipGetLastError();
+}
+
+// complex integer samples -> complex float, times scale (fdc_iq.hpp): the widening front end of the paths without integer loads of their own
+template <class TI>
+__global__ __launch_bounds__(256) void k_iq_to_complex(const TI *__restrict__ in, float2 *__restrict__ out, size_t n, float scale)
+{
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) out[i] = to2(iq_widen(in[i], scale));
+}
+
+hipError_t launch_iq_to_complex(int fmt, float scale, const void *in, float2 *out, size_t n, hipStream_t s)
+{
+    if (!n) return hipSuccess;
+    size_t g = (n + 255) / 256; if (g > 8192) g = 8192;
+    if (fmt == kIqSc16) hipLaunchKernelGGL(k_iq_to_complex<sc16>, dim3((unsigned)g), dim3(256), 0, s, static_cast<const sc16 *>(in), out, n, scale);
+    else if (fmt == kIqSc8) hipLaunchKernelGGL(k_iq_to_complex<sc8>, dim3((unsigned)g), dim3(256), 0, s, static_cast<const sc8 *>(in), out, n, scale);
+    else return hipErrorInvalidValue;
     return hipGetLastError();
 }
 

@@ -145,6 +145,26 @@ int fdc_pipeline_work_span(fdc_pipeline *p, const void *halo, const void *in, in
 int fdc_pipeline_work_span_real(fdc_pipeline *p, const void *halo, const void *in, int64_t first_block, int nblocks, void *const *outs,
                                 void *spectrum);
 
+/* Complex INTEGER input, as radio front ends deliver it (UHD sc16 / sc8, RFSoC and ADC capture cards: interleaved int16 or int8 I/Q).
+ * Sample k is (float(I_k) * scale, float(Q_k) * scale): the conversion is exact, the product rounded once in float32 (numpy's
+ * np.float32(I) * np.float32(scale)), and everything behind it is the complex path, so the outputs are bit-identical to
+ * fdc_pipeline_work / _span / process_device on the converted complex64 input, for any finite scale.  UHD sc16 -> fc32 is scale = 1/32768;
+ * GNU Radio's interleaved_short_to_complex has scale 1.
+ *   format   FDC_IQ_SC16 (4 bytes per sample) or FDC_IQ_SC8 (2 bytes per sample); anything else, or a scale that is zero or not finite:
+ *            FDC_ERR_INVALID_ARGUMENT
+ *   in, halo the same sample counts as the float entries, in the format (halo: N/R samples); a registered `in` is DMA'd in place
+ * Input form: the first work call after create / fdc_pipeline_reset latches the handle to (format, scale), or to float input (fdc_pipeline_work,
+ * _span, _real, ...).  A call in another form returns FDC_ERR_INVALID_ARGUMENT and changes nothing; the next call in the right form continues
+ * the stream.  The overlap history of integer calls is kept in the integer format.  Path 5 (N = 4096 in one launch) and the banks of 256-bin
+ * channels at N = 16384 / 32768 / 65536 read the integers in their own loads; every other plan widens them on the device first
+ * (fdc_pipeline_describe names which: "input sc16: fused" / "input sc16: widened").  The integer ring (and any staging) is allocated at the
+ * first integer call; nothing is allocated in the steady state.  Out of scope: the sink and waterfall entries take float input only. */
+enum { FDC_IQ_SC16 = 1,   /* int16 I, int16 Q interleaved: 4 bytes per sample */
+       FDC_IQ_SC8  = 2 }; /* int8  I, int8  Q interleaved: 2 bytes per sample */
+int fdc_pipeline_work_iq(fdc_pipeline *p, int32_t format, float scale, const void *in, int nblocks, void *const *outs, void *spectrum);
+int fdc_pipeline_work_span_iq(fdc_pipeline *p, int32_t format, float scale, const void *halo, const void *in, int64_t first_block, int nblocks,
+                              void *const *outs, void *spectrum);
+
 /* Optional: pin a host range that will be handed to fdc_pipeline_work() again and again (GNU Radio's circular buffers
  * live as long as the flowgraph: register them in start(), unregister in stop()).  A call whose `in` lies in a
  * registered range is DMA'd from it in place, and when every outs[c] does, the results are stored straight into
@@ -152,7 +172,7 @@ int fdc_pipeline_work_span_real(fdc_pipeline *p, const void *halo, const void *i
  * The range must stay mapped until fdc_host_unregister(ptr) (same ptr as registered). */
 int fdc_host_register(void *ptr, size_t bytes);
 int fdc_host_unregister(void *ptr);
-void fdc_pipeline_reset(fdc_pipeline *p);    /* history <- zeros, block counter <- 0 (fresh ctor state)  */
+void fdc_pipeline_reset(fdc_pipeline *p);    /* history <- zeros, block counter <- 0, input form unlatched (fresh ctor state)  */
 
 /* Device-resident entry (stateless; the form bench.py and a device-side flowgraph use).
  *   d_ring      device pointer: N/R halo samples preceding the span, then nblocks*(N-N/R) new samples
@@ -163,6 +183,10 @@ void fdc_pipeline_reset(fdc_pipeline *p);    /* history <- zeros, block counter 
  *   stream      hipStream_t (NULL = the handle's own stream).  Asynchronous: returns after enqueue. */
 int fdc_pipeline_process_device(fdc_pipeline *p, const void *d_ring, int64_t first_block, int nblocks,
                                 void *d_out, void *d_spectrum, void *stream);
+/* The same on a device ring of complex integers (format / scale as fdc_pipeline_work_iq; d_ring 4-byte aligned, the same sample counts).
+ * Stateless, like fdc_pipeline_process_device: it neither checks nor latches the handle's input form. */
+int fdc_pipeline_process_device_iq(fdc_pipeline *p, int32_t format, float scale, const void *d_ring, int64_t first_block, int nblocks,
+                                   void *d_out, void *d_spectrum, void *stream);
 /* The same, and beside the spectrum the POWER OF ITS 16-BIN GROUPS (round 6): d_group_power receives nblocks x N/16 float32, entry [m][g] = the sum
  * of |S|^2 over bins 16 g .. 16 g + 15 of block m's normalised, shifted spectrum.  At N = 16384 / 32768 / 65536 the forward kernel sums them in its
  * epilogue, while the bins are in its registers; elsewhere (other block lengths, launch groups too short for the block kernel) a pass over the
@@ -246,7 +270,9 @@ void fdc_pipeline_group_destroy(fdc_pipeline_group *g);
 /* work()-shaped, same arguments and state semantics as fdc_pipeline_work() / fdc_pipeline_work_real() */
 int fdc_pipeline_group_work(fdc_pipeline_group *g, const void *in, int nblocks, void *const *outs, void *spectrum);
 int fdc_pipeline_group_work_real(fdc_pipeline_group *g, const void *in, int nblocks, void *const *outs, void *spectrum);
-void fdc_pipeline_group_reset(fdc_pipeline_group *g);           /* history <- zeros, block counter <- 0, error state cleared */
+/* complex integer input: the arguments, the bytes and the input-form latch of fdc_pipeline_work_iq (the group latches, as its members do) */
+int fdc_pipeline_group_work_iq(fdc_pipeline_group *g, int32_t format, float scale, const void *in, int nblocks, void *const *outs, void *spectrum);
+void fdc_pipeline_group_reset(fdc_pipeline_group *g);           /* history <- zeros, block counter <- 0, input form unlatched, error state cleared */
 int32_t fdc_pipeline_group_size(const fdc_pipeline_group *g);
 fdc_pipeline *fdc_pipeline_group_member(fdc_pipeline_group *g, int i);   /* owned by the group (fdc_pipeline_path, sizes, timing) */
 int32_t fdc_pipeline_group_device(const fdc_pipeline_group *g, int i);
