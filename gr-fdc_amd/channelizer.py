@@ -176,7 +176,57 @@ def _iq_input(x, scale, H):
     return np.ascontiguousarray(x), fmt, n, sc
 
 
-class Pipeline:
+OQ_FC32 = 0                     # FDC_OQ_FC32; FDC_OQ_SC16 / FDC_OQ_SC8 are IQ_SC16 / IQ_SC8 (include/fdc_amd.h)
+OQ_FORMATS = {None: OQ_FC32, "fc32": OQ_FC32, "sc16": IQ_SC16, "sc8": IQ_SC8}
+_OQ_DTYPES = {IQ_SC16: np.int16, IQ_SC8: np.int8}
+
+
+def _oq_format(fmt, scale):
+    """Checks of set_output_format made before any library call: fmt in None / "fc32" / "sc16" / "sc8" (ValueError otherwise), a finite non-zero
+    float32 scale.  Returns (format code, scale as float32)."""
+    if not (fmt is None or isinstance(fmt, str)) or fmt not in OQ_FORMATS:
+        raise ValueError("output format is None, 'fc32', 'sc16' or 'sc8', not %r" % (fmt,))
+    try:
+        with np.errstate(over="ignore"):
+            sc = np.float32(scale)
+    except (TypeError, ValueError):
+        raise ValueError("scale must be a finite, non-zero number, got %r" % (scale,))
+    if not np.isfinite(sc) or sc == 0:
+        raise ValueError("scale must be finite and not zero (float32), got %r" % (scale,))
+    return OQ_FORMATS[fmt], sc
+
+
+class _OutputFormat:
+    """The channel outputs in the handle's output format (fdc_pipeline_set_output_format): complex64 arrays of nblocks*lout_c samples, or
+    int16 / int8 arrays of shape (nblocks*lout_c, 2) (interleaved I/Q: sc16 / sc8)."""
+    _oq = OQ_FC32
+    _oq_scale = np.float32(1.0)
+
+    def output_format(self):
+        """(format name, scale): ("fc32", 1.0), ("sc16", s) or ("sc8", s)."""
+        return ({OQ_FC32: "fc32", IQ_SC16: "sc16", IQ_SC8: "sc8"}[self._oq], float(self._oq_scale))
+
+    def _new_outs(self, nb):
+        if self._oq == OQ_FC32:
+            return [np.empty(nb * lo, dtype=np.complex64) for lo in self.lout]
+        return [np.empty((nb * lo, 2), dtype=_OQ_DTYPES[self._oq]) for lo in self.lout]
+
+    def _check_outs(self, outs, nb):
+        if outs is None:
+            return self._new_outs(nb)
+        if len(outs) != len(self.lout):
+            raise ValueError("outs needs one array per channel")
+        dt = np.complex64 if self._oq == OQ_FC32 else _OQ_DTYPES[self._oq]
+        per = 1 if self._oq == OQ_FC32 else 2
+        for o, lo in zip(outs, self.lout):
+            if not isinstance(o, np.ndarray) or o.dtype != dt or not o.flags.c_contiguous or o.size != per * nb * lo:
+                if self._oq == OQ_FC32:
+                    raise ValueError("outs[c] must be contiguous complex64 with nblocks*lout_c samples")
+                raise ValueError("outs[c] must be contiguous %s with nblocks*lout_c interleaved I/Q samples (the output format)" % np.dtype(dt).name)
+        return outs
+
+
+class Pipeline(_OutputFormat):
     """fdc_pipeline handle: channels = [(f, l, passbw, stopbw), ...]."""
 
     def __init__(self, blocklen, relinvovl, channels, windowtype=WINDOWTYPES.HANN, max_blocks=64,
@@ -209,23 +259,25 @@ class Pipeline:
     def channel_offset(self, c, nblocks):
         return int(_lib.lib().fdc_pipeline_channel_offset(self._h, c, nblocks))
 
+    def set_output_format(self, fmt, scale=1.0):
+        """fdc_pipeline_set_output_format: fmt None / "fc32" (complex64, the default), "sc16" or "sc8".  While sc16 / sc8 is set, work*, work_span*
+        and work_iq* return int16 / int8 arrays of shape (n, 2), one per channel: each component saturate(rint(y * scale)) of the complex64 value y
+        the float output would have (NaN -> 0, +-Inf -> the limits); process_device* take device buffers of that format.  A setting, not a latch:
+        it applies from the next call, survives reset(), and does not touch the stream.  UHD's sc16 convention is scale = 32768."""
+        code, sc = _oq_format(fmt, scale)
+        _lib.check(_lib.lib().fdc_pipeline_set_output_format(self._h, code, float(sc)))
+        self._oq, self._oq_scale = code, sc if code else np.float32(1.0)
+
     # -- host path (what sync_block::work() would call)
     def work(self, x, want_spectrum=False, sinks=None, outs=None):
         """sinks: a gr_fdc_amd.Sinks bank fed from the device-resident spectrum of this call (needs keep_spectrum).
-        outs: optional caller-owned complex64 arrays, one per channel with nblocks*lout_c samples (e.g. slices of
-        buffers pinned with register_host); allocated here when None."""
+        outs: optional caller-owned arrays, one per channel with nblocks*lout_c samples of the output format (complex64 unless
+        set_output_format chose sc16 / sc8; e.g. slices of buffers pinned with register_host); allocated here when None."""
         x = np.ascontiguousarray(x, dtype=np.complex64)
         if x.size % self.H:
             raise ValueError("input must be a whole number of (N - N/R)-sample items")
         nb = x.size // self.H
-        if outs is None:
-            outs = [np.empty(nb * lo, dtype=np.complex64) for lo in self.lout]
-        else:
-            if len(outs) != len(self.lout):
-                raise ValueError("outs needs one array per channel")
-            for o, lo in zip(outs, self.lout):
-                if o.dtype != np.complex64 or not o.flags.c_contiguous or o.size != nb * lo:
-                    raise ValueError("outs[c] must be contiguous complex64 with nblocks*lout_c samples")
+        outs = self._check_outs(outs, nb)
         ptrs = (C.c_void_p * max(1, len(outs)))(*[o.ctypes.data for o in outs])
         spec = np.empty(nb * self.N, dtype=np.complex64) if want_spectrum else None
         if sinks is not None:
@@ -272,7 +324,7 @@ class Pipeline:
         if x.size % self.H:
             raise ValueError("input must be a whole number of (N - N/R)-sample items")
         nb = x.size // self.H
-        outs = [np.empty(nb * lo, dtype=np.complex64) for lo in self.lout]
+        outs = self._new_outs(nb)
         ptrs = (C.c_void_p * max(1, len(outs)))(*[o.ctypes.data for o in outs])
         spec = np.empty(nb * self.N, dtype=np.complex64) if want_spectrum else None
         _lib.check(_lib.lib().fdc_pipeline_work_real(self._h, x.ctypes.data, nb, ptrs,
@@ -286,14 +338,7 @@ class Pipeline:
         latches the handle's input form (float, or this format and scale): a call in another form raises FdcError.  outs: as work()."""
         x, fmt, n, sc = _iq_input(x, scale, self.H)
         nb = n // self.H
-        if outs is None:
-            outs = [np.empty(nb * lo, dtype=np.complex64) for lo in self.lout]
-        else:
-            if len(outs) != len(self.lout):
-                raise ValueError("outs needs one array per channel")
-            for o, lo in zip(outs, self.lout):
-                if o.dtype != np.complex64 or not o.flags.c_contiguous or o.size != nb * lo:
-                    raise ValueError("outs[c] must be contiguous complex64 with nblocks*lout_c samples")
+        outs = self._check_outs(outs, nb)
         ptrs = (C.c_void_p * max(1, len(outs)))(*[o.ctypes.data for o in outs])
         spec = np.empty(nb * self.N, dtype=np.complex64) if want_spectrum else None
         _lib.check(_lib.lib().fdc_pipeline_work_iq(self._h, fmt, float(sc), x.ctypes.data, nb, ptrs,
@@ -310,7 +355,7 @@ class Pipeline:
                 raise ValueError("halo: N/R samples of the input's format")
             hp = halo.ctypes.data
         nb = n // self.H
-        outs = [np.empty(nb * lo, dtype=np.complex64) for lo in self.lout]
+        outs = self._new_outs(nb)
         ptrs = (C.c_void_p * max(1, len(outs)))(*[o.ctypes.data for o in outs])
         spec = np.empty(nb * self.N, dtype=np.complex64) if want_spectrum else None
         _lib.check(_lib.lib().fdc_pipeline_work_span_iq(self._h, fmt, float(sc), hp, x.ctypes.data, int(first_block), nb, ptrs,
@@ -404,7 +449,7 @@ class Pipeline:
             pass
 
 
-class PipelineGroup:
+class PipelineGroup(_OutputFormat):
     """fdc_pipeline_group handle: one work() spread over several devices (contiguous spans of the call's blocks, one per
     member, run concurrently).  devices: HIP ordinals, repeats allowed (virtual members on one GPU).  Same work() / work_real()
     as Pipeline; state (overlap history, block counter) is kept once, by the group."""
@@ -435,9 +480,14 @@ class PipelineGroup:
         m0 = _lib.lib().fdc_pipeline_group_member(self._h, 0)
         self.lout = [_lib.lib().fdc_pipeline_channel_lout(m0, c) for c in range(len(self.channels))]
 
+    def set_output_format(self, fmt, scale=1.0):
+        """fdc_pipeline_group_set_output_format: Pipeline.set_output_format for every member."""
+        code, sc = _oq_format(fmt, scale)
+        _lib.check(_lib.lib().fdc_pipeline_group_set_output_format(self._h, code, float(sc)))
+        self._oq, self._oq_scale = code, sc if code else np.float32(1.0)
+
     def _run(self, fn, x, nb, want_spectrum, outs):
-        if outs is None:
-            outs = [np.empty(nb * lo, dtype=np.complex64) for lo in self.lout]
+        outs = self._check_outs(outs, nb)
         ptrs = (C.c_void_p * max(1, len(outs)))(*[o.ctypes.data for o in outs])
         spec = np.empty(nb * self.N, dtype=np.complex64) if want_spectrum else None
         _lib.check(fn(self._h, x.ctypes.data, nb, ptrs, spec.ctypes.data if spec is not None else None))
@@ -519,7 +569,8 @@ class FrequencyDomainChannelizer:
                  act_det_deactivation_delay, minchanflankpuffer, verbose,
                  pow_act_deactivation_delay,
                  pow_act_maxblocks, act_det_maxblocks,
-                 debug, device_id=0, max_blocks=64, devices=None, pipelined=False, waterfall=None, iq_input=None, iq_scale=1.0):
+                 debug, device_id=0, max_blocks=64, devices=None, pipelined=False, waterfall=None, iq_input=None, iq_scale=1.0,
+                 iq_output=None, iq_output_scale=1.0):
         # pipelined (not an argument of the reference): the sink blocks run beside the front end of the FOLLOWING work() calls, as the
         # thread-per-block scheduler runs them beside the FFT in the reference (fdc_pipeline_work_sinks on a look-ahead bank,
         # include/fdc_amd.h): same PDUs, handed out one or two work() calls later; flush() at the end of the stream
@@ -574,6 +625,20 @@ class FrequencyDomainChannelizer:
                 sc = np.float32(iq_scale)
             if not np.isfinite(sc) or sc == 0:
                 raise ValueError("iq_scale must be finite and not zero")
+        # iq_output (not an argument of the reference): "sc16" / "sc8" — the channel ports come back as int16 / int8 arrays of shape (n, 2), narrowed on
+        # the device (Pipeline.set_output_format; UHD's sc16 convention is iq_output_scale = 32768).  The restrictions of iq_input; combines with it
+        # and with the Float input type.
+        if iq_output is not None and iq_output not in ("sc16", "sc8"):
+            raise ValueError("iq_output is None, 'sc16' or 'sc8'")
+        self.iq_output, self.iq_output_scale = iq_output, float(iq_output_scale)
+        if iq_output is not None:
+            if self.inpveclen != 1:
+                raise ValueError("iq_output needs inpveclen 1: the pre-transformed item entry writes complex outputs only")
+            if activity_controlled_channels or activity_detection_segments:
+                raise ValueError("iq_output cannot go with activity-controlled channels or detection segments")
+            if waterfall is not None:
+                raise ValueError("iq_output cannot go with a waterfall")
+            _oq_format(iq_output, iq_output_scale)
 
         if self.verbose:                                        # runtime information, :176-193
             bar = '\n' + '#' * 32 + '\n'
@@ -622,6 +687,8 @@ class FrequencyDomainChannelizer:
                                      windowtype=int(windowtype), max_blocks=max_blocks,
                                      device_id=devices[0] if devices else device_id,
                                      keep_spectrum=self.debug or self.sinks is not None)
+        if iq_output is not None:
+            self.pipeline.set_output_format(iq_output, iq_output_scale)
         self.N_throughput_channelizers = len(self.channel_params)
         # waterfall (not an argument of the reference, whose example flowgraph wires the spectrum to complex_to_mag_squared and
         # FDC.WaterfallMsgTagging outside the hier block): a gr_fdc_amd.Waterfall fed from the spectrum on the device; work() then

@@ -220,6 +220,12 @@ struct fdc_pipeline {
                                  // of the latched format: the history)
     float2 *d_iqw = nullptr;     // process_device_iq(): one launch group widened, chunk*H + ovl samples (paths without integer loads)
     std::string iq_route;        // how the last integer-input call was served (fdc_pipeline_describe)
+    // complex integer output (fdc_pipeline_set_output_format): a setting, not a latch; out_form 0 = complex float, FDC_OQ_SC16 / FDC_OQ_SC8 with out_scale
+    int out_form = 0;
+    float out_scale = 1.f;
+    unsigned char *d_oq = nullptr;   // host entries: the narrow results, max_blocks*sum_lout samples of fdc::kIqRingBytes (the widest format), allocated
+                                     // at the first integer-output call
+    std::string oq_route;        // how the last integer-output call was served (fdc_pipeline_describe)
     float2 *d_out = nullptr;     // work(): max_blocks*sum_lout
     int64_t blockcount = 0;      // work(): blocks consumed so far
     // work(): transfers and kernels of consecutive sub-batches overlap (H2D on s_in, kernels on stream, D2H on s_out)
@@ -255,6 +261,15 @@ struct fdc_pipeline {
     size_t ev_used = 0;
     std::vector<std::array<size_t, 5>> ev_spans;   // events: start, mid, end-of-fft, end-of-channels; [4]: which form the span ran (kSpan*)
 };
+
+namespace fdc {
+// shared with fdc_group.hip: a member's output format (FDC_OQ_*) and scale — the group places its spans by the members' own setting
+int pipeline_output_format(const fdc_pipeline *p, float *scale)
+{
+    if (scale) *scale = p->out_scale;
+    return p->out_form;
+}
+}  // namespace fdc
 
 extern "C" {
 
@@ -407,7 +422,7 @@ void fdc_pipeline_destroy(fdc_pipeline *p)
     if (!p) return;
     if (p->stream) (void)hipStreamSynchronize(p->stream);
     if (p->ev_hier) { (void)hipEventSynchronize(p->ev_hier); (void)hipEventDestroy(p->ev_hier); }   // kernels of the pipelined entry ran on the bank's stream
-    (void)hipFree(p->d_dbg); (void)hipFree(p->d_g); (void)hipFree(p->d_specfull);
+    (void)hipFree(p->d_dbg); (void)hipFree(p->d_g); (void)hipFree(p->d_specfull); (void)hipFree(p->d_oq);
     for (auto e : p->events) (void)hipEventDestroy(e);
     for (auto st : {p->s_in, p->s_out}) if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
     for (int i = 0; i < 2; i++) {
@@ -1137,6 +1152,7 @@ int32_t fdc_pipeline_describe(const fdc_pipeline *p, char *buf, int32_t n)
     }
     if (!p->wf_route.empty()) add("; waterfall rows: %s", p->wf_route.c_str());
     if (!p->iq_route.empty()) add("; input %s", p->iq_route.c_str());
+    if (!p->oq_route.empty()) add("; output %s", p->oq_route.c_str());
     std::snprintf(buf, (size_t)n, "%s", t);
     return k;
 }
@@ -1259,10 +1275,19 @@ enum { kSpanBanks = 0 /* banks | remainder forward | remainder channels */, kSpa
 
 // one launch of the bank's block kernel over the launch group (ev0 / ev1: stamped by the dispatch itself, may be null)
 // fmt != 0: in0 is complex integer input (raw: the launch group's first sample), read by the 256-bin kernel itself
+// ofmt != 0: the 256-bin kernel narrows in its stores into oq (out_bytes: the narrow extent), o is not written
 static int launch_bank(fdc_pipeline *p, const fdc_pipeline::Bank &bk, const float2 *in0, float2 *o, int nb, int m0, int nblocks, int64_t first_block,
-                       unsigned out_bytes, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1, int fmt = 0, float scale = 1.0f, const void *raw = nullptr)
+                       unsigned out_bytes, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1, int fmt = 0, float scale = 1.0f, const void *raw = nullptr,
+                       int ofmt = 0, float oscale = 1.0f, void *oq = nullptr)
 {
     const bool half = bk.r == bk.L / 2;
+    if (ofmt) {
+        if (bk.L != 256) return fail(FDC_ERR_UNSUPPORTED, "integer stores in a %d-bin bank", bk.L);
+        HIPCHK(fdc::launch_poly_block_oq(fmt, scale, fmt ? raw : static_cast<const void *>(in0), (size_t)p->H, ofmt, oscale, oq, nb, m0, nblocks, p->d_tw256,
+                                         p->d_twq, bk.d_cbt, bk.d_shn, bk.d_slot_off, out_bytes, p->ncu - p->reserved_cu, p->block_hints, s, bk.r,
+                                         first_block + m0, ev0, ev1, p->R, p->d_fscr, p->N));
+        return FDC_OK;
+    }
     if (fmt) {
         if (bk.L != 256) return fail(FDC_ERR_UNSUPPORTED, "integer loads in a %d-bin bank", bk.L);
         HIPCHK(fdc::launch_poly_block_iq(fmt, scale, raw, (size_t)p->H, o, nb, m0, nblocks, p->d_tw256, p->d_twq, bk.d_cbt, bk.d_shn, bk.d_slot_off, out_bytes,
@@ -1300,10 +1325,29 @@ static bool iq_fused(const fdc_pipeline *p, bool spectrum, bool few)
     return true;
 }
 
+// integer output: whether EVERY launch group of a call of nblocks narrows in its own kernel's stores — path 5 (k_f4096) and the banks of 256-bin channels
+// (k_blk256, streamed stores; not N = 65536 at R = 4 on float input, whose forms would spill: fdc_block256.hip kOqR4Narrowed) without a remainder;
+// otherwise the call writes complex float and k_complex_to_iq narrows it (whole call: one layout).  fmt: the input form.
+static bool oq_fused(const fdc_pipeline *p, int fmt, bool spectrum, int nblocks)
+{
+    if (spectrum || p->wf_rows || p->cfg_generic) return false;
+    if (p->fused) return true;
+    if (!p->poly_ok || !p->poly_block || p->split || !(p->block_hints & 1)) return false;
+    if (!fmt && p->N == 65536 && p->R == 4) return false;
+    for (const auto &b : p->banks) if (b.L != 256) return false;
+    for (int m0 = 0; m0 < nblocks; m0 += p->chunk)
+        if (std::min(p->chunk, nblocks - m0) < p->block_min && two_launch_possible(p)) return false;
+    return true;
+}
+
 // fmt: 0 = float2 ring; FDC_IQ_SC16 / FDC_IQ_SC8: a ring of complex integers (scale: their factor), and `wide` the float2 buffer of chunk*H + ovl
-// samples a launch group is widened into where the kernels take float input
+// samples a launch group is widened into where the kernels take float input.
+// ofmt: 0 = complex float output into d_out; FDC_OQ_SC16 / FDC_OQ_SC8 (times oscale): d_out receives the narrow samples (same offsets).  Where the call's
+// kernels do not narrow themselves (oq_fused) they write complex float into fout (nblocks*sum_lout samples) and k_complex_to_iq narrows it into d_out —
+// unless narrow is false (the caller narrows fout itself: the scatter into registered host buffers).  *ofused: which of the two it was.
 static int process_device_impl(fdc_pipeline *p, int fmt, float scale, const void *d_ring, int64_t first_block, int nblocks,
-                               void *d_out, void *d_spectrum, void *stream, float2 *wide, bool *all_fused)
+                               void *d_out, void *d_spectrum, void *stream, float2 *wide, bool *all_fused,
+                               int ofmt = 0, float oscale = 1.0f, float2 *fout = nullptr, bool narrow = true, bool *ofused_out = nullptr)
 {
     if (!p) return fail(FDC_ERR_INVALID_ARGUMENT, "null handle");
     if (nblocks < 0 || first_block < 0) return fail(FDC_ERR_INVALID_ARGUMENT, "negative block count/index");
@@ -1319,9 +1363,14 @@ static int process_device_impl(fdc_pipeline *p, int fmt, float scale, const void
     const float2 *ring = static_cast<const float2 *>(d_ring);
     const unsigned char *iring = static_cast<const unsigned char *>(d_ring);
     const size_t esz = fdc::iq_bytes(fmt);
-    float2 *o = static_cast<float2 *>(d_out);
+    const bool ofused = ofmt && oq_fused(p, fmt, d_spectrum != nullptr, nblocks);
+    if (ofused_out) *ofused_out = ofused;
+    if (ofmt && !ofused && !fout) return fail(FDC_ERR_INVALID_ARGUMENT, "integer output: no float staging");
+    float2 *o = ofmt && !ofused ? fout : static_cast<float2 *>(d_out);
+    const size_t osz = ofused ? fdc::iq_bytes(ofmt) : sizeof(float2);       // bytes per sample the kernels store
+    unsigned char *const ob = ofused ? static_cast<unsigned char *>(d_out) : reinterpret_cast<unsigned char *>(o);
     const bool use_poly = p->poly_ok && !d_spectrum;
-    const unsigned out_bytes = (unsigned)((int64_t)nblocks * p->sum_lout * 8);
+    const unsigned out_bytes = (unsigned)((int64_t)nblocks * p->sum_lout * (int64_t)osz);
     for (int m0 = 0; m0 < nblocks; m0 += p->chunk) {
         const int nb = std::min(p->chunk, nblocks - m0);
         float2 *spec = d_spectrum ? static_cast<float2 *>(d_spectrum) + (size_t)m0 * p->N : p->d_spec;
@@ -1352,7 +1401,10 @@ static int process_device_impl(fdc_pipeline *p, int fmt, float scale, const void
             // N = 4096: one launch, nothing but the input samples and the output samples crosses the memory interface
             if (tg) HIPCHK(hipEventRecord(p->events[span[0]], s));
             float *wf = p->wf_rows ? p->wf_rows + (size_t)(first_block - p->wf_first + m0) * fdc::kWfWidth : nullptr;
-            if (ifused)
+            if (ofused)
+                HIPCHK(fdc::launch_fused4096_oq(ifused ? fmt : 0, scale, ifused ? raw0 : static_cast<const void *>(in0), (size_t)p->H, ofmt, oscale, d_out, nb, p->R,
+                                                m0, nblocks, first_block, p->d_tw, p->ntab, p->d_wins, p->d_f4rows, p->f4_cls, p->f4_teams, s));
+            else if (ifused)
                 HIPCHK(fdc::launch_fused4096_iq(fmt, scale, raw0, (size_t)p->H, o, nb, p->R, m0, nblocks, first_block, p->d_tw, p->ntab, p->d_wins, p->d_f4rows,
                                                 p->f4_cls, p->f4_teams, s));
             else
@@ -1366,13 +1418,13 @@ static int process_device_impl(fdc_pipeline *p, int fmt, float scale, const void
             for (size_t k = 0; k < p->banks.size(); k++) {
                 const int rcb = launch_bank(p, p->banks[k], in0, o, nb, m0, nblocks, first_block, out_bytes, s,
                                             tg && k == 0 ? p->events[span[0]] : nullptr, tg && k + 1 == p->banks.size() ? p->events[span[1]] : nullptr,
-                                            ifused ? fmt : 0, scale, raw0);
+                                            ifused ? fmt : 0, scale, raw0, ofused ? ofmt : 0, oscale, d_out);
                 if (rcb != FDC_OK) return rcb;
             }
             for (const auto &al : p->bank_alias) {
                 const fdc::ChanDev &dc = p->chans[(size_t)al.first], &sc = p->chans[(size_t)al.second];
-                HIPCHK(hipMemcpyAsync(o + (size_t)nblocks * dc.out_off + (size_t)m0 * dc.lout, o + (size_t)nblocks * sc.out_off + (size_t)m0 * sc.lout,
-                                      sizeof(float2) * (size_t)nb * dc.lout, hipMemcpyDeviceToDevice, s));
+                HIPCHK(hipMemcpyAsync(ob + osz * ((size_t)nblocks * dc.out_off + (size_t)m0 * dc.lout), ob + osz * ((size_t)nblocks * sc.out_off + (size_t)m0 * sc.lout),
+                                      osz * (size_t)nb * dc.lout, hipMemcpyDeviceToDevice, s));
             }
             if (p->split) {
                 const int rcr = run_remainder(p, in0, m0, nb, nblocks, first_block, o, few, s, tg ? p->events[span[2]] : nullptr, tg ? p->events[span[3]] : nullptr);
@@ -1431,14 +1483,37 @@ static int process_device_impl(fdc_pipeline *p, int fmt, float scale, const void
             p->ev_spans.push_back(span);
         }
     }
+    if (ofmt && !ofused && narrow && p->C > 0) HIPCHK(fdc::launch_complex_to_iq(ofmt, oscale, fout, d_out, (size_t)nblocks * p->sum_lout, s));
     return FDC_OK;
+}
+
+static const char *iq_name(int fmt) { return fmt == FDC_IQ_SC16 ? "sc16" : "sc8"; }
+
+// The device entries with the handle's output format: integer output needs the float staging (p->d_out, max_blocks*sum_lout samples, allocated by
+// fdc_pipeline_set_output_format, never on this enqueue path) where the call's kernels do not narrow themselves
+static int process_device_oq(fdc_pipeline *p, int fmt, float scale, const void *d_ring, int64_t first_block, int nblocks, void *d_out, void *d_spectrum,
+                             void *stream, float2 *wide, bool *all_fused)
+{
+    const int ofmt = p->out_form;
+    if (!ofmt || nblocks <= 0) return process_device_impl(p, fmt, scale, d_ring, first_block, nblocks, d_out, d_spectrum, stream, wide, all_fused);
+    if (!oq_fused(p, fmt, d_spectrum != nullptr, nblocks)) {
+        if (nblocks > p->cfg.max_blocks)
+            return fail(FDC_ERR_INVALID_ARGUMENT, "integer output on this plan: nblocks %d above max_blocks %d", nblocks, p->cfg.max_blocks);
+        if (!p->d_out && p->sum_lout > 0) return fail(FDC_ERR_HIP, "integer output: no float staging");
+    }
+    bool of = false;
+    const int rc = process_device_impl(p, fmt, scale, d_ring, first_block, nblocks, d_out, d_spectrum, stream, wide, all_fused, ofmt, p->out_scale, p->d_out,
+                                       true, &of);
+    if (rc == FDC_OK) p->oq_route = std::string(iq_name(ofmt)) + (of ? ": fused" : ": narrowed");
+    return rc;
 }
 
 int fdc_pipeline_process_device(fdc_pipeline *p, const void *d_ring, int64_t first_block, int nblocks,
                                 void *d_out, void *d_spectrum, void *stream)
 {
     FDC_ENTRY("fdc_pipeline_process_device")
-    return process_device_impl(p, 0, 1.0f, d_ring, first_block, nblocks, d_out, d_spectrum, stream, nullptr, nullptr);
+    if (!p) return fail(FDC_ERR_INVALID_ARGUMENT, "null handle");
+    return process_device_oq(p, 0, 1.0f, d_ring, first_block, nblocks, d_out, d_spectrum, stream, nullptr, nullptr);
     FDC_ENTRY_END
 }
 
@@ -1448,7 +1523,6 @@ static int check_iq_form(int32_t format, float scale)
     if (!std::isfinite(scale) || scale == 0.0f) return fail(FDC_ERR_INVALID_ARGUMENT, "the scale must be finite and not zero");
     return FDC_OK;
 }
-static const char *iq_name(int fmt) { return fmt == FDC_IQ_SC16 ? "sc16" : "sc8"; }
 
 int fdc_pipeline_process_device_iq(fdc_pipeline *p, int32_t format, float scale, const void *d_ring, int64_t first_block, int nblocks,
                                    void *d_out, void *d_spectrum, void *stream)
@@ -1467,7 +1541,7 @@ int fdc_pipeline_process_device_iq(fdc_pipeline *p, int32_t format, float scale,
         }
     }
     bool all = true;
-    rc = process_device_impl(p, format, scale, d_ring, first_block, nblocks, d_out, d_spectrum, stream, p->d_iqw, &all);
+    rc = process_device_oq(p, format, scale, d_ring, first_block, nblocks, d_out, d_spectrum, stream, p->d_iqw, &all);
     if (rc == FDC_OK && nblocks > 0) p->iq_route = std::string(iq_name(format)) + (all ? ": fused" : ": widened");
     return rc;
     FDC_ENTRY_END
@@ -1478,6 +1552,7 @@ int fdc_pipeline_process_device_power(fdc_pipeline *p, const void *d_ring, int64
 {
     FDC_ENTRY("fdc_pipeline_process_device_power")
     if (!p) return fail(FDC_ERR_INVALID_ARGUMENT, "null handle");
+    if (p->out_form) return fail(FDC_ERR_INVALID_ARGUMENT, "fdc_pipeline_process_device_power writes complex float outputs only (the handle's output format is not FC32)");
     if (d_group_power && (!d_spectrum || (p->N & 15))) return fail(FDC_ERR_INVALID_ARGUMENT, "group powers go with a spectrum output of a block length that is a multiple of 16");
     p->gpow_base = static_cast<float *>(d_group_power);
     p->gpow_spec = static_cast<const float2 *>(d_spectrum);
@@ -1529,6 +1604,33 @@ void fdc_pipeline_reset(fdc_pipeline *p)
     p->in_form = -1;
     p->in_scale = 0.f;
     p->iq_route.clear();
+    p->oq_route.clear();         // (the output format itself is a setting: it stays)
+}
+
+// the entries that write complex float only (sinks, spectrum items, group powers, waterfall): refused while the output format is not FC32
+static int check_float_output(const fdc_pipeline *p, const char *entry)
+{
+    if (p && p->out_form) return fail(FDC_ERR_INVALID_ARGUMENT, "%s writes complex float outputs only: set the output format to FDC_OQ_FC32 first", entry);
+    return FDC_OK;
+}
+
+int fdc_pipeline_set_output_format(fdc_pipeline *p, int32_t format, float scale)
+{
+    FDC_ENTRY("fdc_pipeline_set_output_format")
+    if (!p) return fail(FDC_ERR_INVALID_ARGUMENT, "null handle");
+    if (format != FDC_OQ_FC32 && format != FDC_OQ_SC16 && format != FDC_OQ_SC8) return fail(FDC_ERR_INVALID_ARGUMENT, "unknown output format %d", (int)format);
+    if (!std::isfinite(scale) || scale == 0.0f) return fail(FDC_ERR_INVALID_ARGUMENT, "the output scale must be finite and not zero");
+    if (p->hier_filled > 0)
+        return fail(FDC_ERR_INVALID_ARGUMENT, "a pipelined sinks batch is still inside the handle: fdc_pipeline_flush_sinks until it returns 0 first");
+    if (format && !p->d_out && p->sum_lout > 0) {
+        // the float staging of the plans whose kernels do not narrow themselves: allocated here, once, so that no device entry allocates while it enqueues
+        HIPCHK(hipSetDevice(p->cfg.device_id));
+        HIPCHK(hipMalloc(&p->d_out, sizeof(float2) * (size_t)p->cfg.max_blocks * p->sum_lout));
+    }
+    p->out_form = format;
+    p->out_scale = format ? scale : 1.0f;
+    return FDC_OK;
+    FDC_ENTRY_END
 }
 
 // The whole-call spectrum of a work() that hands it to the host (debug port, python/FrequencyDomainChannelizer.py:152-158, :314-315) when
@@ -1545,7 +1647,7 @@ static int work_io_setup(fdc_pipeline *p)
     if (p->d_ring) return FDC_OK;
     HIPCHK(hipMalloc(&p->d_ring, sizeof(float2) * ((size_t)p->ovl + (size_t)p->cfg.max_blocks * p->H)));
     HIPCHK(hipMemsetAsync(p->d_ring, 0, sizeof(float2) * (size_t)p->ovl, p->stream));   // zero history (overlap_save_impl.cc:52)
-    if (p->sum_lout > 0) HIPCHK(hipMalloc(&p->d_out, sizeof(float2) * (size_t)p->cfg.max_blocks * p->sum_lout));
+    if (p->sum_lout > 0 && !p->d_out) HIPCHK(hipMalloc(&p->d_out, sizeof(float2) * (size_t)p->cfg.max_blocks * p->sum_lout));   // (integer-output device calls may have made it)
     HIPCHK(hipStreamCreateWithFlags(&p->s_in, hipStreamNonBlocking));
     HIPCHK(hipStreamCreateWithFlags(&p->s_out, hipStreamNonBlocking));
     for (int i = 0; i < 2; i++) {
@@ -1598,6 +1700,8 @@ static void latch_form(fdc_pipeline *p, int fmt, float scale)
 // from `halo` (N/R samples, NULL = zeros) and the block counter from `first_block` instead of from the handle.
 // fmt != 0: `in` and `halo` hold complex integers (FDC_IQ_SC16 / FDC_IQ_SC8, times scale): the ring and its history are kept in that format
 // (d_iq), the integer kernels read it where the plan has them, the handle's float ring takes the widened launch groups otherwise.
+// Integer output (p->out_form): the kernels narrow into d_oq where the plan lets them (oq_fused), else they write d_out and k_complex_to_iq narrows it
+// into d_oq; registered outputs are scattered from either (k_scatter_oq: narrowing from d_out, copying from d_oq), staged ones copied from d_oq.
 static int pipeline_work_impl(fdc_pipeline *p, const void *in, int nblocks, void *const *outs, void *spectrum,
                               float2 *d_spec_dst, bool span = false, const void *halo = nullptr, int64_t first_block = 0, int fmt = 0, float scale = 1.0f)
 {
@@ -1613,6 +1717,10 @@ static int pipeline_work_impl(fdc_pipeline *p, const void *in, int nblocks, void
     if ((rc = work_io_setup(p)) != FDC_OK) return rc;
     hipStream_t s = p->stream;
     const size_t nin = (size_t)nblocks * p->H, esz = fdc::iq_bytes(fmt);
+    const int ofmt = p->out_form;
+    const float oscale = p->out_scale;
+    const size_t osz = ofmt ? fdc::iq_bytes(ofmt) : sizeof(float2);       // bytes per output sample the caller receives
+    if (ofmt && !p->d_oq && p->sum_lout > 0) HIPCHK(hipMalloc(&p->d_oq, fdc::kIqRingBytes * (size_t)p->cfg.max_blocks * p->sum_lout));
     if (fmt && !p->d_iq) {
         // the integer ring: allocated at the first integer call, for the WIDEST format (a reset may latch the handle to another one); its
         // history starts at zero, as the float ring's
@@ -1623,11 +1731,6 @@ static int pipeline_work_impl(fdc_pipeline *p, const void *in, int nblocks, void
     // the ring the call's samples go to, as bytes: float2 (d_ring) or the integer format (d_iq)
     unsigned char *const ringb = fmt ? static_cast<unsigned char *>(p->d_iq) : reinterpret_cast<unsigned char *>(p->d_ring);
     const unsigned char *hin = static_cast<const unsigned char *>(in);
-    bool all_fused = true;
-    auto process = [&](size_t b0, int nb, int64_t first, float2 *dok, float2 *dspec) {
-        return fmt ? process_device_impl(p, fmt, scale, ringb + b0 * p->H * esz, first, nb, dok, dspec, s, p->d_ring, &all_fused)
-                   : fdc_pipeline_process_device(p, ringb + b0 * p->H * esz, first, nb, dok, dspec, s);
-    };
     if (span) {
         // every kernel of the call is enqueued on s behind this copy; the previous call ended with s drained
         if (halo) HIPCHK(hipMemcpyAsync(ringb, halo, esz * (size_t)p->ovl, hipMemcpyHostToDevice, s));
@@ -1644,9 +1747,31 @@ static int pipeline_work_impl(fdc_pipeline *p, const void *in, int nblocks, void
     for (int c = 0; c < p->C && out_reg; c++) {
         fdc::ScatterEnt &e = p->pin_tab[c];
         e.dst = nullptr; e.out_off = p->chans[c].out_off; e.lout = p->chans[c].lout; e.pad = 0;
-        if (outs[c] && !host_registered(outs[c], sizeof(float2) * (size_t)nblocks * p->chans[c].lout, reinterpret_cast<void **>(&e.dst)))
+        if (outs[c] && !host_registered(outs[c], osz * (size_t)nblocks * p->chans[c].lout, reinterpret_cast<void **>(&e.dst)))
             out_reg = false;
     }
+    bool all_fused = true, oq_all = true, oq_sub = false;
+    // dok: the float results of the sub-batch starting at block b0.  Integer output: its narrow results go to the same sample offset of d_oq (oq_sub: the
+    // kernels wrote them there themselves; otherwise dok holds float and is narrowed into d_oq, unless the outputs are registered: k_scatter_oq narrows)
+    auto process = [&](size_t b0, int nb, int64_t first, float2 *dok, float2 *dspec) {
+        if (ofmt) {
+            const int rc2 = process_device_impl(p, fmt, scale, ringb + b0 * p->H * esz, first, nb, p->d_oq + osz * b0 * (size_t)p->sum_lout, dspec, s,
+                                                fmt ? p->d_ring : nullptr, &all_fused, ofmt, oscale, dok, !out_reg, &oq_sub);
+            oq_all = oq_all && oq_sub;
+            return rc2;
+        }
+        return fmt ? process_device_impl(p, fmt, scale, ringb + b0 * p->H * esz, first, nb, dok, dspec, s, p->d_ring, &all_fused)
+                   : fdc_pipeline_process_device(p, ringb + b0 * p->H * esz, first, nb, dok, dspec, s);
+    };
+    // what the caller's buffers receive for the sub-batch at b0: float from d_out, or narrow from d_oq
+    auto res = [&](size_t b0) -> const void * {
+        return ofmt ? static_cast<const void *>(p->d_oq + osz * b0 * (size_t)p->sum_lout) : static_cast<const void *>(p->d_out + b0 * (size_t)p->sum_lout);
+    };
+    auto scatter = [&](size_t b0, int nb, hipStream_t st) -> hipError_t {
+        if (!ofmt) return fdc::launch_scatter_out(p->d_out + b0 * (size_t)p->sum_lout, p->d_tab, p->C, nb, (long long)b0, st);
+        return oq_sub ? fdc::launch_scatter_oq(ofmt, res(b0), ofmt, oscale, p->d_tab, p->C, nb, (long long)b0, st)
+                      : fdc::launch_scatter_oq(fdc::kIqFloat, p->d_out + b0 * (size_t)p->sum_lout, ofmt, oscale, p->d_tab, p->C, nb, (long long)b0, st);
+    };
     const int sub = p->sub;
     if (!out_reg && p->C > 0 && !p->pin_out[0])
         for (int i = 0; i < 2; i++)
@@ -1655,11 +1780,11 @@ static int pipeline_work_impl(fdc_pipeline *p, const void *in, int nblocks, void
     auto drain = [&](int j) -> int {
         const int b0 = j * sub, nb = std::min(sub, nblocks - b0);
         HIPCHK(hipEventSynchronize(p->ev_out[j & 1]));
-        const float2 *src = p->pin_out[j & 1];
+        const unsigned char *src = reinterpret_cast<const unsigned char *>(p->pin_out[j & 1]);
         for (int c = 0; c < p->C; c++) {
             if (!outs[c]) continue;
             const size_t lo = (size_t)p->chans[c].lout;
-            std::memcpy(static_cast<float2 *>(outs[c]) + (size_t)b0 * lo, src + (size_t)nb * p->chans[c].out_off, sizeof(float2) * nb * lo);
+            std::memcpy(static_cast<unsigned char *>(outs[c]) + osz * (size_t)b0 * lo, src + osz * (size_t)nb * p->chans[c].out_off, osz * nb * lo);
         }
         return FDC_OK;
     };
@@ -1670,18 +1795,19 @@ static int pipeline_work_impl(fdc_pipeline *p, const void *in, int nblocks, void
         rc = process(0, nblocks, p->blockcount, p->d_out, d_specfull);
         if (rc != FDC_OK) return rc;
         if (p->C > 0) {
-            if (out_reg) HIPCHK(fdc::launch_scatter_out(p->d_out, p->d_tab, p->C, nblocks, 0, s));
-            else HIPCHK(hipMemcpyAsync(p->pin_out[0], p->d_out, sizeof(float2) * (size_t)nblocks * p->sum_lout, hipMemcpyDeviceToHost, s));
+            if (out_reg) HIPCHK(scatter(0, nblocks, s));
+            else HIPCHK(hipMemcpyAsync(p->pin_out[0], res(0), osz * (size_t)nblocks * p->sum_lout, hipMemcpyDeviceToHost, s));
         }
         if (spectrum) HIPCHK(hipMemcpyAsync(spectrum, d_specfull, sizeof(float2) * (size_t)nblocks * p->N, hipMemcpyDeviceToHost, s));
         HIPCHK(hipMemcpyAsync(ringb, ringb + esz * nin, esz * (size_t)p->ovl, hipMemcpyDeviceToDevice, s));
         HIPCHK(hipStreamSynchronize(s));
         if (fmt) p->iq_route = std::string(iq_name(fmt)) + (all_fused ? ": fused" : ": widened");
+        if (ofmt) p->oq_route = std::string(iq_name(ofmt)) + (oq_all ? ": fused" : ": narrowed");
         if (p->C > 0 && !out_reg)
             for (int c = 0; c < p->C; c++)
                 if (outs[c])
-                    std::memcpy(outs[c], p->pin_out[0] + (size_t)nblocks * p->chans[c].out_off,
-                                sizeof(float2) * (size_t)nblocks * p->chans[c].lout);
+                    std::memcpy(outs[c], reinterpret_cast<const unsigned char *>(p->pin_out[0]) + osz * (size_t)nblocks * p->chans[c].out_off,
+                                osz * (size_t)nblocks * p->chans[c].lout);
         p->blockcount += nblocks;
         return nblocks;
     }
@@ -1729,9 +1855,9 @@ static int pipeline_work_impl(fdc_pipeline *p, const void *in, int nblocks, void
         HIPCHK(hipEventRecord(p->ev_k[slot], s));
         HIPCHK(hipStreamWaitEvent(p->s_out, p->ev_k[slot], 0));
         if (out_reg) {
-            HIPCHK(fdc::launch_scatter_out(dok, p->d_tab, p->C, nb, b0, p->s_out));
+            HIPCHK(scatter((size_t)b0, nb, p->s_out));
         } else {
-            HIPCHK(hipMemcpyAsync(p->pin_out[slot], dok, sizeof(float2) * (size_t)nb * p->sum_lout, hipMemcpyDeviceToHost, p->s_out));
+            HIPCHK(hipMemcpyAsync(p->pin_out[slot], res((size_t)b0), osz * (size_t)nb * p->sum_lout, hipMemcpyDeviceToHost, p->s_out));
             HIPCHK(hipEventRecord(p->ev_out[slot], p->s_out));
             if (k >= 1 && (rc = drain(k - 1)) != FDC_OK) return rc;
         }
@@ -1743,6 +1869,7 @@ static int pipeline_work_impl(fdc_pipeline *p, const void *in, int nblocks, void
     HIPCHK(hipStreamSynchronize(s));
     HIPCHK(hipStreamSynchronize(p->s_out));
     if (fmt) p->iq_route = std::string(iq_name(fmt)) + (all_fused ? ": fused" : ": widened");
+    if (ofmt) p->oq_route = std::string(iq_name(ofmt)) + (oq_all ? ": fused" : ": narrowed");
     p->blockcount += nblocks;
     return nblocks;
 }
@@ -1762,6 +1889,7 @@ int fdc_pipeline_work_waterfall(fdc_pipeline *p, fdc_waterfall *w, const void *i
 {
     FDC_ENTRY("fdc_pipeline_work_waterfall")
     if (!p) return fail(FDC_ERR_INVALID_ARGUMENT, "null handle");
+    if (int rcf = check_float_output(p, "fdc_pipeline_work_waterfall")) return rcf;
     if (nblocks < 0) return fail(FDC_ERR_INVALID_ARGUMENT, "negative item count");
     if (nblocks > p->cfg.max_blocks) return fail(FDC_ERR_INVALID_ARGUMENT, "nblocks %d above max_blocks %d", nblocks, p->cfg.max_blocks);
     int rc = fdc::wf_check_call(w, p->cfg.device_id, p->N, nblocks, cap_rows);
@@ -1837,15 +1965,24 @@ static int pipeline_work_real_impl(fdc_pipeline *p, const void *in, int nblocks,
     } else {
         HIPCHK(fdc::launch_real_to_complex(p->d_real + p->ovl, p->d_ring + p->ovl, nin, s));
     }
-    rc = fdc_pipeline_process_device(p, p->d_ring, p->blockcount, nblocks, p->d_out, d_specfull, s);
+    // integer output (p->out_form): the narrow results in d_oq (the kernels' own stores, or k_complex_to_iq behind them), copied as they are
+    const int ofmt = p->out_form;
+    const size_t osz = ofmt ? fdc::iq_bytes(ofmt) : sizeof(float2);
+    if (ofmt && !p->d_oq && p->sum_lout > 0) HIPCHK(hipMalloc(&p->d_oq, fdc::kIqRingBytes * (size_t)p->cfg.max_blocks * p->sum_lout));
+    bool of = false;
+    if (ofmt) rc = process_device_impl(p, 0, 1.0f, p->d_ring, p->blockcount, nblocks, p->d_oq, d_specfull, s, nullptr, nullptr, ofmt, p->out_scale, p->d_out,
+                                       true, &of);
+    else rc = fdc_pipeline_process_device(p, p->d_ring, p->blockcount, nblocks, p->d_out, d_specfull, s);
     if (rc != FDC_OK) return rc;
+    const unsigned char *res = ofmt ? p->d_oq : reinterpret_cast<const unsigned char *>(p->d_out);
     for (int c = 0; c < p->C; c++)
         if (outs[c])
-            HIPCHK(hipMemcpyAsync(outs[c], p->d_out + (size_t)nblocks * p->chans[c].out_off,
-                                  sizeof(float2) * (size_t)nblocks * p->chans[c].lout, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(outs[c], res + osz * (size_t)nblocks * p->chans[c].out_off,
+                                  osz * (size_t)nblocks * p->chans[c].lout, hipMemcpyDeviceToHost, s));
     if (spectrum) HIPCHK(hipMemcpyAsync(spectrum, d_specfull, sizeof(float2) * (size_t)nblocks * p->N, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(p->d_ring, p->d_ring + nin, sizeof(float2) * (size_t)p->ovl, hipMemcpyDeviceToDevice, s));
     HIPCHK(hipStreamSynchronize(s));
+    if (ofmt) p->oq_route = std::string(iq_name(ofmt)) + (of ? ": fused" : ": narrowed");
     p->blockcount += nblocks;
     return nblocks;
 }
@@ -1981,6 +2118,7 @@ int fdc_pipeline_work_sinks(fdc_pipeline *p, const void *in, int nblocks, void *
     FDC_ENTRY("fdc_pipeline_work_sinks")
     if (!sinks) return fail(FDC_ERR_INVALID_ARGUMENT, "null sinks handle");
     if (!p) return fail(FDC_ERR_INVALID_ARGUMENT, "null handle");
+    if (int rcf = check_float_output(p, "fdc_pipeline_work_sinks")) return rcf;
     if (fdc_sinks_blocklen(sinks) != p->N || nblocks > fdc_sinks_max_blocks(sinks))
         return fail(FDC_ERR_INVALID_ARGUMENT, "sinks were created for blocklen %d / %d blocks per call, pipeline call has %d / %d",
                     fdc_sinks_blocklen(sinks), fdc_sinks_max_blocks(sinks), p->N, nblocks);
@@ -2002,6 +2140,7 @@ int fdc_pipeline_flush_sinks(fdc_pipeline *p, fdc_sinks *sinks)
 {
     FDC_ENTRY("fdc_pipeline_flush_sinks")
     if (!p || !sinks) return fail(FDC_ERR_INVALID_ARGUMENT, "null handle");
+    if (int rcf = check_float_output(p, "fdc_pipeline_flush_sinks")) return rcf;
     if (p->hier_broken) return fail(FDC_ERR_HIP, "an earlier pipelined call failed after it had advanced the stream state: destroy the pipeline and the bank");
     if (p->hier_bank == sinks && p->hier_filled > 0) {
         const int n = p->hier_filled;
@@ -2027,6 +2166,7 @@ int fdc_pipeline_work_spectrum(fdc_pipeline *p, const void *in, int nblocks, voi
     // hier block with inpveclen > 1 (py:284-290): items are spectra already; only multiply_const(1/N) and the channel /
     // sink branches remain.  The front-end state (overlap history) is untouched; the block counter advances.
     if (!p) return fail(FDC_ERR_INVALID_ARGUMENT, "null handle");
+    if (int rcf = check_float_output(p, "fdc_pipeline_work_spectrum")) return rcf;
     if (nblocks < 0) return fail(FDC_ERR_INVALID_ARGUMENT, "negative item count");
     if (nblocks == 0) return 0;
     if (nblocks > p->cfg.max_blocks) return fail(FDC_ERR_INVALID_ARGUMENT, "nblocks %d above max_blocks %d", nblocks, p->cfg.max_blocks);

@@ -154,22 +154,26 @@ __device__ __forceinline__ void blk_pass_dft(cf (&a)[P])
 #define FDC_FWD_TWO_WG 0
 #endif
 // TI: the input sample, float2 or complex integer (sc16 / sc8: fdc_iq.hpp); integer rows are loaded as they are (4 / 2 bytes a sample) and
-// widened in registers at the top of the pass that transforms them, times iq_scale
-template <int P, bool NT, bool OFF, bool FWD, bool R4 = false, bool STG = false, bool HALF = false, class TI = float2>
-__global__ FDC_PLAIN_DS __launch_bounds__(512, (P == 2 && !OFF && !R4 && !FWD) ? 4 : 2) void k_blk256(const TI *__restrict__ in, size_t in_stride, float2 *__restrict__ out,
+// widened in registers at the top of the pass that transforms them, times iq_scale.  TO: the output sample, float2 or complex integer (sc16 / sc8:
+// narrowed in the store, times oq_scale, oq_bits): one dword / one 16-bit store per sample at the same per-wave offsets, scaled to the narrow element
+template <int P, bool NT, bool OFF, bool FWD, bool R4 = false, bool STG = false, bool HALF = false, class TI = float2, class TO = float2>
+__global__ FDC_PLAIN_DS __launch_bounds__(512, (P == 2 && !OFF && !R4 && !FWD) ? 4 : 2) void k_blk256(const TI *__restrict__ in, size_t in_stride, TO *__restrict__ out,
                                                 const float2 *__restrict__ tw256, const float2 *__restrict__ twq,
                                                 const float2 *__restrict__ cbt, const float *__restrict__ shn,
                                                 const long long *__restrict__ slot_off, long long out_base,
                                                 long long nb_call, unsigned out_bytes, int nb, int hints,
                                                 unsigned long long *__restrict__ dbg, int roff, long long first_block,
                                                 float2 *__restrict__ fwd_scratch, const unsigned *__restrict__ keep,
-                                                typename IqTail<TI>::type gpow /* integer TI: iq_scale */)
+                                                typename IqTail<TI, TO>::type gpow /* integer TI / TO: iq_scale / oq_scale */)
 {
     typedef BlkGeom<P> GM;
-    constexpr bool kIq = !std::is_same<TI, float2>::value;
+    constexpr bool kIq = !std::is_same<TI, float2>::value, kOq = !std::is_same<TO, float2>::value;
     static_assert(!kIq || (!STG && !FWD), "integer input: the channelizer forms (the forward transform and the staged loads take widened input)");
+    static_assert(!kOq || (!STG && !FWD), "integer output: the channelizer forms");
     constexpr unsigned kEs = (unsigned)sizeof(TI);                              // bytes per input sample
+    constexpr unsigned kOs = (unsigned)sizeof(TO);                              // bytes per output sample
     [[maybe_unused]] const float iq_scale = iq_tail_scale(gpow);
+    [[maybe_unused]] const float oq_scale = oq_tail_scale(gpow);
     static_assert(!STG || (P == 8 && !OFF && !R4), "staged loads: the plain channelizer and the forward transform at N = 65536");
     static_assert(!HALF || (!OFF && !FWD && !STG), "the half-slot form is a variant of the on-grid channelizer");
     constexpr int kN1 = GM::kN1, kLd = GM::kLd, kJT = GM::kJT, kJB = GM::kJB;
@@ -267,7 +271,7 @@ __global__ FDC_PLAIN_DS __launch_bounds__(512, (P == 2 && !OFF && !R4 && !FWD) ?
     }
     for (int i = tid; i < kN1; i += 512) {
         const long long o = slot_off[i];                  // slot i = klo + P khi, khi = k0 + 2 k1, is entry [klo][16 k0 + rev16(k1)]
-        soff[(i % P) * 32 + ((i / P) & 1) * 16 + rev16((i / P) >> 1)] = o >= 0 ? (unsigned)((o * nb_call + out_base) * 8) : 0xFFFFFFFFu;
+        soff[(i % P) * 32 + ((i / P) & 1) * 16 + rev16((i / P) >> 1)] = o >= 0 ? (unsigned)((o * nb_call + out_base) * kOs) : 0xFFFFFFFFu;
     }
     for (int i = tid; i < 32 * P; i += 512) ctab[i] = tw256[((i / P) * (i % P) * (8 / P)) & 255];     // [c5][klo] = W_N1^(c5 klo)
     // FWD: entry r < 8 of a row is the one of q = 2 r + h (the rows this workgroup computes); entries 8 .. 15 are not read
@@ -591,7 +595,7 @@ __global__ FDC_PLAIN_DS __launch_bounds__(512, (P == 2 && !OFF && !R4 && !FWD) ?
                     // FWD: [block][N bins]; row t' = b + 16 j of the run is bin k2 = b + 16 (2 j + h): four 16-bin runs per wave store, 32 bins apart
                     const int trow0 = 16 * kJT * tr + 64 * rh2, trow = trow0 + lane2;
                     const unsigned rb = FW2 ? (unsigned)(m * GM::kN + (trow & 15) + 32 * (trow >> 4) + 16 * fhalf) * 8u
-                                            : (unsigned)(m * (FWD ? GM::kN : (R4 ? 192 : 128)) + rowbase + trow) * 8u;
+                                            : (unsigned)(m * (FWD ? GM::kN : (R4 ? 192 : 128)) + rowbase + trow) * kOs;
                     // two workgroups per block: the two 64-bin groups of k2 a wave's store touches (lanes 0-31 / 32-63): kept if some channel reads either
                     unsigned mq = FW2 ? (mqs[(trow0 >> 5) & 3] | mqs[((trow0 >> 5) + 1) & 3])
                                       : FWD ? mqs[((rowbase + trow0) >> 6) & 3] : ~0u;
@@ -604,7 +608,13 @@ __global__ FDC_PLAIN_DS __launch_bounds__(512, (P == 2 && !OFF && !R4 && !FWD) ?
                         for (int e = 0; e < 4; e++) {
                             // FWD: a store nobody reads gets the offset of an unused slot (all ones: a scalar term, one OR per store)
                             const unsigned o = FWD ? (so[e] | (((mq >> (4 * q + e)) & 1u) - 1u)) : so[e];
-                            bst2t<NT>(rout, (o == 0xFFFFFFFFu ? 0xFFFFFFF0u : o + rb), v[4 * q + e]);
+                            // (integer output: the unused-slot offset 0xFFFFFFF0 lies beyond any narrow extent, which is below 4 GiB too)
+                            if constexpr (kOq) {
+                                const unsigned u = oq_bits(TO{}, v[4 * q + e], oq_scale);
+                                if constexpr (kOs == 4) __builtin_amdgcn_raw_buffer_store_b32(u, rout, (o == 0xFFFFFFFFu ? 0xFFFFFFF0u : o + rb), 0, NT ? 2 : 0);
+                                else __builtin_amdgcn_raw_buffer_store_b16((unsigned short)u, rout, (o == 0xFFFFFFFFu ? 0xFFFFFFF0u : o + rb), 0, NT ? 2 : 0);
+                            } else
+                                bst2t<NT>(rout, (o == 0xFFFFFFFFu ? 0xFFFFFFF0u : o + rb), v[4 * q + e]);
                         }
                     }
                     if constexpr (FWD && !FW2) {
@@ -726,11 +736,47 @@ static hipError_t init_block_kernels_in()
     return hipSuccess;
 }
 
+// P = 8, R = 4 (N = 65536, three quarters of every inverse transform kept) on float input with integer output: the narrowing costs the 256-register
+// kernel 2-3 spilled registers, so these plans narrow behind the float form instead (fdc_api.hip oq_fused)
+template <class TI, class TO> struct kOqR4Narrowed {
+    static constexpr bool value = std::is_same<TI, float2>::value && !std::is_same<TO, float2>::value;
+};
+
+// the channelizer forms with integer output (TO = sc16 / sc8, fdc_pipeline_set_output_format) for one input type: streamed (nt) stores only — a
+// handle with FDC_PIPE_PLAIN_STORES narrows behind the float form instead (half the instantiations)
+template <class TI, class TO>
+static hipError_t init_block_kernels_oq()
+{
+    hipError_t e;
+#define FDC_SETB(P, B, R4) \
+    e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_blk256<P, true, B, false, R4, false, false, TI, TO>), hipFuncAttributeMaxDynamicSharedMemorySize, \
+                            B ? BlkGeom<P>::kLdsOff : BlkGeom<P>::kLds); \
+    if (e != hipSuccess) return e;
+#define FDC_SETH(P, R4) \
+    e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_blk256<P, true, false, false, R4, false, true, TI, TO>), hipFuncAttributeMaxDynamicSharedMemorySize, BlkGeom<P>::kLds); \
+    if (e != hipSuccess) return e;
+#define FDC_SETP(P) \
+    FDC_SETB(P, false, false) FDC_SETB(P, true, false) FDC_SETB(P, false, true) FDC_SETB(P, true, true) FDC_SETH(P, false) FDC_SETH(P, true)
+    FDC_SETP(2) FDC_SETP(4)
+    FDC_SETB(8, false, false) FDC_SETB(8, true, false) FDC_SETH(8, false)
+    if constexpr (!kOqR4Narrowed<TI, TO>::value) { FDC_SETB(8, false, true) FDC_SETB(8, true, true) FDC_SETH(8, true) }
+#undef FDC_SETP
+#undef FDC_SETH
+#undef FDC_SETB
+    return hipSuccess;
+}
+
 hipError_t init_block_kernels()
 {
     hipError_t e = init_block_kernels_in<sc16>();
     if (e != hipSuccess) return e;
     if ((e = init_block_kernels_in<sc8>()) != hipSuccess) return e;
+    if ((e = init_block_kernels_oq<float2, sc16>()) != hipSuccess) return e;
+    if ((e = init_block_kernels_oq<float2, sc8>()) != hipSuccess) return e;
+    if ((e = init_block_kernels_oq<sc16, sc16>()) != hipSuccess) return e;
+    if ((e = init_block_kernels_oq<sc16, sc8>()) != hipSuccess) return e;
+    if ((e = init_block_kernels_oq<sc8, sc16>()) != hipSuccess) return e;
+    if ((e = init_block_kernels_oq<sc8, sc8>()) != hipSuccess) return e;
 #define FDC_SETB(P, A, B, F, R4) \
     e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_blk256<P, A, B, F, R4>), hipFuncAttributeMaxDynamicSharedMemorySize, \
                             B ? BlkGeom<P>::kLdsOff : BlkGeom<P>::kLds); \
@@ -768,17 +814,23 @@ hipError_t init_block_kernels()
 
 bool poly_block_supports(int N) { return N == 16384 || N == 32768 || N == 65536; }
 
-template <class TI>
-static hipError_t poly_block_in(const TI *in, size_t in_stride, float2 *out, int nb_chunk, int mbase, int nb_call,
+template <class TI, class TO = float2>
+static hipError_t poly_block_in(const TI *in, size_t in_stride, TO *out, int nb_chunk, int mbase, int nb_call,
                                 const float2 *tw256, const float2 *twq, const float2 *cbt, const float *shn,
                                 const long long *slot_off, unsigned out_bytes, int ncu, int hints, hipStream_t s,
                                 unsigned long long *dbg, int r, long long first_block, hipEvent_t ev_start, hipEvent_t ev_stop, int R,
-                                float2 *scratch, int N, float iq_scale)
+                                float2 *scratch, int N, float iq_scale, float oq_scale = 1.0f)
 {
     if (nb_chunk <= 0) return hipSuccess;
-    // the kernel's last argument: float2 input, no group powers (null); integer input, the scale (IqTail)
-    auto iq_tail = [](float sc) -> typename IqTail<TI>::type {
-        if constexpr (std::is_same<TI, float2>::value) return (void)sc, (float *)nullptr; else return sc;
+    constexpr bool kIq = !std::is_same<TI, float2>::value, kOq = !std::is_same<TO, float2>::value;
+    // integer output: the streamed-store forms only (init_block_kernels_oq); the macros below name NT = true for both hints then
+    if (kOq && !(hints & 1)) return hipErrorInvalidValue;
+    // the kernel's last argument: float2 input and output, no group powers (null); otherwise the scale(s) of the integer side(s) (IqTail)
+    auto iq_tail = [](float si, float so) -> typename IqTail<TI, TO>::type {
+        if constexpr (!kIq && !kOq) return (void)si, (void)so, (float *)nullptr;
+        else if constexpr (kIq && kOq) return make_float2(si, so);
+        else if constexpr (kIq) return (void)so, si;
+        else return (void)si, so;
     };
     const bool halfslot = (r & 255) == 128;                 // half a slot: the on-grid kernel with its tables moved (HALF), R = 2 and 4
     if (!poly_block_supports(N) || (R != 2 && R != 4) || (R == 4 && !scratch)) return hipErrorInvalidValue;
@@ -792,27 +844,29 @@ static hipError_t poly_block_in(const TI *in, size_t in_stride, float2 *out, int
     // in front of or behind the kernel, unlike hipEventRecord (measured 7-17 us per bracketed launch)
     // R = 4: three quarters of every inverse transform kept: 192 rows per block, 64 of them via the scratch
 #define FDC_LB(P, A, B, R4) \
-    hipExtLaunchKernelGGL((k_blk256<P, A, B, false, R4, false, false, TI>), dim3((unsigned)grid), dim3(512), B ? BlkGeom<P>::kLdsOff : BlkGeom<P>::kLds, s, \
+    hipExtLaunchKernelGGL((k_blk256<P, A || kOq, B, false, R4, false, false, TI, TO>), dim3((unsigned)grid), dim3(512), B ? BlkGeom<P>::kLdsOff : BlkGeom<P>::kLds, s, \
                           ev_start, ev_stop, 0u, in, in_stride, out, tw256, twq, cbt, shn, slot_off, (long long)mbase * (R4 ? 192 : 128), (long long)nb_call, \
                           out_bytes, nb_chunk, hints, dbg, r & 255, first_block, R4 ? scratch : (float2 *)nullptr, (const unsigned *)nullptr, \
-                          iq_tail(iq_scale))
+                          iq_tail(iq_scale, oq_scale))
 #define FDC_LH(P, A, R4) \
-    hipExtLaunchKernelGGL((k_blk256<P, A, false, false, R4, false, true, TI>), dim3((unsigned)grid), dim3(512), BlkGeom<P>::kLds, s, ev_start, \
+    hipExtLaunchKernelGGL((k_blk256<P, A || kOq, false, false, R4, false, true, TI, TO>), dim3((unsigned)grid), dim3(512), BlkGeom<P>::kLds, s, ev_start, \
                           ev_stop, 0u, in, in_stride, out, tw256, twq, cbt, shn, slot_off, (long long)mbase * (R4 ? 192 : 128), (long long)nb_call, \
                           out_bytes, nb_chunk, hints, dbg, 0, first_block, R4 ? scratch : (float2 *)nullptr, (const unsigned *)nullptr, \
-                          iq_tail(iq_scale))
+                          iq_tail(iq_scale, oq_scale))
+// (FDC_R4(P): the R = 4 forms exist — not at P = 8 on float input with integer output, kOqR4Narrowed)
+#define FDC_R4(P) if constexpr (P != 8 || !kOqR4Narrowed<TI, TO>::value)
 #define FDC_LP(P) \
     do { \
         if (halfslot) { \
-            if (R == 4) { if (hints & 1) FDC_LH(P, true, true); else FDC_LH(P, false, true); } \
+            if (R == 4) { FDC_R4(P) { if (hints & 1) FDC_LH(P, true, true); else FDC_LH(P, false, true); } else return hipErrorInvalidValue; } \
             else { if (hints & 1) FDC_LH(P, true, false); else FDC_LH(P, false, false); } \
-        } else if (R == 4 && (r & 255)) { if (hints & 1) FDC_LB(P, true, true, true); else FDC_LB(P, false, true, true); } \
-        else if (R == 4) { if (hints & 1) FDC_LB(P, true, false, true); else FDC_LB(P, false, false, true); } \
+        } else if (R == 4 && (r & 255)) { FDC_R4(P) { if (hints & 1) FDC_LB(P, true, true, true); else FDC_LB(P, false, true, true); } else return hipErrorInvalidValue; } \
+        else if (R == 4) { FDC_R4(P) { if (hints & 1) FDC_LB(P, true, false, true); else FDC_LB(P, false, false, true); } else return hipErrorInvalidValue; } \
         else if (r & 255) { if (hints & 1) FDC_LB(P, true, true, false); else FDC_LB(P, false, true, false); } \
         else { if (hints & 1) FDC_LB(P, true, false, false); else FDC_LB(P, false, false, false); } \
     } while (0)
 #if FDC_BLK_STAGED
-    if constexpr (std::is_same<TI, float2>::value) if (N == 65536 && R == 2 && !(r & 255)) {
+    if constexpr (!kIq && !kOq) if (N == 65536 && R == 2 && !(r & 255)) {
         // the plain channelizer with its loads staged through LDS
 #define FDC_LS(A) \
         hipExtLaunchKernelGGL((k_blk256<8, A, false, false, false, true>), dim3((unsigned)grid), dim3(512), BlkGeom<8>::kLdsS, s, ev_start, ev_stop, 0u, in, \
@@ -825,6 +879,7 @@ static hipError_t poly_block_in(const TI *in, size_t in_stride, float2 *out, int
 #endif
     if (N == 65536) FDC_LP(8); else if (N == 32768) FDC_LP(4); else FDC_LP(2);
 #undef FDC_LP
+#undef FDC_R4
 #undef FDC_LH
 #undef FDC_LB
     return hipGetLastError();
@@ -851,6 +906,36 @@ hipError_t launch_poly_block_iq(int fmt, float scale, const void *in, size_t in_
     if (fmt == kIqSc8)
         return poly_block_in(static_cast<const sc8 *>(in), in_stride, out, nb_chunk, mbase, nb_call, tw256, twq, cbt, shn, slot_off, out_bytes, ncu, hints, s,
                              nullptr, r, first_block, ev_start, ev_stop, R, scratch, N, scale);
+    return hipErrorInvalidValue;
+}
+
+template <class TO>
+static hipError_t poly_block_oq_in(int ifmt, float iscale, const void *in, size_t in_stride, TO *out, int nb_chunk, int mbase, int nb_call,
+                                   const float2 *tw256, const float2 *twq, const float2 *cbt, const float *shn, const long long *slot_off,
+                                   unsigned out_bytes, int ncu, int hints, hipStream_t s, int r, long long first_block, hipEvent_t ev_start,
+                                   hipEvent_t ev_stop, int R, float2 *scratch, int N, float oscale)
+{
+#define FDC_OQ(TI, sc) \
+    return poly_block_in<TI, TO>(static_cast<const TI *>(in), in_stride, out, nb_chunk, mbase, nb_call, tw256, twq, cbt, shn, slot_off, out_bytes, ncu, \
+                                 hints, s, nullptr, r, first_block, ev_start, ev_stop, R, scratch, N, sc, oscale)
+    if (ifmt == kIqFloat) FDC_OQ(float2, 1.0f);
+    if (ifmt == kIqSc16) FDC_OQ(sc16, iscale);
+    if (ifmt == kIqSc8) FDC_OQ(sc8, iscale);
+#undef FDC_OQ
+    return hipErrorInvalidValue;
+}
+
+hipError_t launch_poly_block_oq(int ifmt, float iscale, const void *in, size_t in_stride, int ofmt, float oscale, void *out, int nb_chunk, int mbase,
+                                int nb_call, const float2 *tw256, const float2 *twq, const float2 *cbt, const float *shn,
+                                const long long *slot_off, unsigned out_bytes, int ncu, int hints, hipStream_t s,
+                                int r, long long first_block, hipEvent_t ev_start, hipEvent_t ev_stop, int R, float2 *scratch, int N)
+{
+    if (ofmt == kIqSc16)
+        return poly_block_oq_in(ifmt, iscale, in, in_stride, static_cast<sc16 *>(out), nb_chunk, mbase, nb_call, tw256, twq, cbt, shn, slot_off, out_bytes,
+                                ncu, hints, s, r, first_block, ev_start, ev_stop, R, scratch, N, oscale);
+    if (ofmt == kIqSc8)
+        return poly_block_oq_in(ifmt, iscale, in, in_stride, static_cast<sc8 *>(out), nb_chunk, mbase, nb_call, tw256, twq, cbt, shn, slot_off, out_bytes,
+                                ncu, hints, s, r, first_block, ev_start, ev_stop, R, scratch, N, oscale);
     return hipErrorInvalidValue;
 }
 

@@ -64,7 +64,7 @@ __device__ __forceinline__ void wave_sync()
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-__device__ __forceinline__ void out_st(float2 *p, cf v)
+__device__ __forceinline__ void out_st(float2 *p, cf v, float)
 {
 #if F4_NT & 1
     if (!(F4_EXP & 4) || v.x == 1.2345e30f) __builtin_nontemporal_store(v, reinterpret_cast<cf *>(p));
@@ -72,6 +72,19 @@ __device__ __forceinline__ void out_st(float2 *p, cf v)
     if (!(F4_EXP & 4) || v.x == 1.2345e30f) st2(p, v);
 #endif
 }
+// integer output (fdc_pipeline_set_output_format): the sample narrowed times s (oq_bits), one dword (sc16) / one 16-bit store (sc8), nt as above
+template <class TO, class TU>
+__device__ __forceinline__ void out_st_oq(TO *p, cf v, float s)
+{
+    const TU u = (TU)oq_bits(TO{}, v, s);
+#if F4_NT & 1
+    if (!(F4_EXP & 4) || v.x == 1.2345e30f) __builtin_nontemporal_store(u, reinterpret_cast<TU *>(p));
+#else
+    if (!(F4_EXP & 4) || v.x == 1.2345e30f) *reinterpret_cast<TU *>(p) = u;
+#endif
+}
+__device__ __forceinline__ void out_st(sc16 *p, cf v, float s) { out_st_oq<sc16, unsigned>(p, v, s); }
+__device__ __forceinline__ void out_st(sc8 *p, cf v, float s) { out_st_oq<sc8, unsigned short>(p, v, s); }
 
 struct RowAt { const float2 *win; const float2 *spec; long long dst; bool on; };
 // ri.valid: 0 = no row, 1 + k = a row of the workgroup's block k
@@ -94,13 +107,17 @@ __device__ __forceinline__ RowAt row_at(const F4Row &ri, int L, int m0, int nb, 
 // ROWS: the waterfall epilogue (fdc_waterfall.hip): wf[m][p] = sum of |X|^2 over shifted bins 4 p .. 4 p + 3 of the 1/N-scaled spectrum, taken from the
 // registers the spectrum store leaves; ROWS = false is the kernel without it, instruction for instruction
 // TI: the input sample, float2 or complex integer (sc16 / sc8, fdc_iq.hpp: widened times iq_scale right after its load)
-template <bool WIDE, int TEAMS, bool ROWS, class TI = float2>
-__global__ __launch_bounds__(256 * TEAMS, 4 /* waves per SIMD */) void k_f4096(const TI *__restrict__ in, size_t in_stride, float2 *__restrict__ out, int nb, int R,
+// TO: the output sample, float2 or complex integer (sc16 / sc8: narrowed times oq_scale in out_st)
+template <bool WIDE, int TEAMS, bool ROWS, class TI = float2, class TO = float2>
+__global__ __launch_bounds__(256 * TEAMS, 4 /* waves per SIMD */) void k_f4096(const TI *__restrict__ in, size_t in_stride, TO *__restrict__ out, int nb, int R,
                                                   int mbase, int nb_call, int fbm /* (first block of the call + mbase) mod R */, const float2 *__restrict__ tw,
                                                   int twstride /* ntab / 4096 */, const float2 *__restrict__ wins,
-                                                  const F4Row *__restrict__ rows, unsigned wcls, typename IqTail<TI>::type wf /* integer TI: iq_scale */)
+                                                  const F4Row *__restrict__ rows, unsigned wcls,
+                                                  typename IqTail<TI, TO>::type wf /* integer TI / TO: iq_scale / oq_scale */)
 {
+    static_assert(!ROWS || std::is_same<TO, float2>::value, "integer output: not the waterfall form");
     [[maybe_unused]] const float iq_scale = iq_tail_scale(wf);
+    [[maybe_unused]] const float oq_scale = oq_tail_scale(wf);
     float2 *tiles = reinterpret_cast<float2 *>(fdc_smem_f4);
     float2 *t256 = reinterpret_cast<float2 *>(fdc_smem_f4 + f4_off_t256(TEAMS));
     float2 *t4k = reinterpret_cast<float2 *>(fdc_smem_f4 + f4_off_t4k(TEAMS));
@@ -285,11 +302,11 @@ __global__ __launch_bounds__(256 * TEAMS, 4 /* waves per SIMD */) void k_f4096(c
         const int skip = 256 - r0.lout;
         if (a0.on) {
 #pragma unroll
-            for (int q = 0; q < 16; q++) if (b + 16 * q >= skip) out_st(out + a0.dst + b + 16 * q, v[rev16(q)] * 256.f);
+            for (int q = 0; q < 16; q++) if (b + 16 * q >= skip) out_st(out + a0.dst + b + 16 * q, v[rev16(q)] * 256.f, oq_scale);
         }
         if (cls == 2 && a1.on) {
 #pragma unroll
-            for (int q = 0; q < 16; q++) if (b + 16 * q >= skip) out_st(out + a1.dst + b + 16 * q, v[16 + rev16(q)] * 256.f);
+            for (int q = 0; q < 16; q++) if (b + 16 * q >= skip) out_st(out + a1.dst + b + 16 * q, v[16 + rev16(q)] * 256.f, oq_scale);
         }
     }
     if constexpr (WIDE) {
@@ -317,7 +334,7 @@ __global__ __launch_bounds__(256 * TEAMS, 4 /* waves per SIMD */) void k_f4096(c
                 const int skip = 1024 - r0.lout;
                 if (a0.on) {
 #pragma unroll
-                    for (int q = 0; q < 32; q++) if (b + 32 * q >= skip) out_st(out + a0.dst + b + 32 * q, v[pos32(q)] * 1024.f);
+                    for (int q = 0; q < 32; q++) if (b + 32 * q >= skip) out_st(out + a0.dst + b + 32 * q, v[pos32(q)] * 1024.f, oq_scale);
                 }
             } else {
                 // l = 512 = 32 x 16: DFT-16 over b for p = lane and p = lane + 16; y[t = p + 32 q]
@@ -333,8 +350,8 @@ __global__ __launch_bounds__(256 * TEAMS, 4 /* waves per SIMD */) void k_f4096(c
 #pragma unroll
                     for (int q = 0; q < 16; q++) {
                         const int t0 = b + 32 * q, t1 = t0 + 16;
-                        if (t0 >= skip) out_st(out + a0.dst + t0, v[rev16(q)] * 512.f);
-                        if (t1 >= skip) out_st(out + a0.dst + t1, v[16 + rev16(q)] * 512.f);
+                        if (t0 >= skip) out_st(out + a0.dst + t0, v[rev16(q)] * 512.f, oq_scale);
+                        if (t1 >= skip) out_st(out + a0.dst + t1, v[16 + rev16(q)] * 512.f, oq_scale);
                     }
                 }
             }
@@ -370,8 +387,8 @@ __global__ __launch_bounds__(256 * TEAMS, 4 /* waves per SIMD */) void k_f4096(c
 #pragma unroll
                 for (int q = 0; q < 8; q++) {
                     const int t0 = b + 16 * q, t1 = t0 + 8;
-                    if (t0 >= skip) out_st(out + a0.dst + t0, v[4 * (q & 1) + (q >> 1)] * 128.f);
-                    if (t1 >= skip) out_st(out + a0.dst + t1, v[8 + 4 * (q & 1) + (q >> 1)] * 128.f);
+                    if (t0 >= skip) out_st(out + a0.dst + t0, v[4 * (q & 1) + (q >> 1)] * 128.f, oq_scale);
+                    if (t1 >= skip) out_st(out + a0.dst + t1, v[8 + 4 * (q & 1) + (q >> 1)] * 128.f, oq_scale);
                 }
             }
         } else if (cls == 7) {
@@ -386,7 +403,7 @@ __global__ __launch_bounds__(256 * TEAMS, 4 /* waves per SIMD */) void k_f4096(c
 #pragma unroll
                 for (int j = 0; j < 8; j++) {
 #pragma unroll
-                    for (int q = 0; q < 2; q++) if (b + 2 * j + 16 * q >= skip) out_st(out + a0.dst + b + 2 * j + 16 * q, v[2 * j + q] * 32.f);
+                    for (int q = 0; q < 2; q++) if (b + 2 * j + 16 * q >= skip) out_st(out + a0.dst + b + 2 * j + 16 * q, v[2 * j + q] * 32.f, oq_scale);
                 }
             }
         } else if (cls == 8) {
@@ -396,7 +413,7 @@ __global__ __launch_bounds__(256 * TEAMS, 4 /* waves per SIMD */) void k_f4096(c
             const int skip = 16 - r0.lout;
             if (a0.on) {
 #pragma unroll
-                for (int p = 0; p < 16; p++) if (p >= skip) out_st(out + a0.dst + p, v[p] * 16.f);
+                for (int p = 0; p < 16; p++) if (p >= skip) out_st(out + a0.dst + p, v[p] * 16.f, oq_scale);
             }
         } else {
             // p = b + 4 j, j < 4: four DFT-4
@@ -411,23 +428,31 @@ __global__ __launch_bounds__(256 * TEAMS, 4 /* waves per SIMD */) void k_f4096(c
 #pragma unroll
                 for (int j = 0; j < 4; j++) {
 #pragma unroll
-                    for (int q = 0; q < 4; q++) if (b + 4 * j + 16 * q >= skip) out_st(out + a0.dst + b + 4 * j + 16 * q, v[4 * j + q] * 64.f);
+                    for (int q = 0; q < 4; q++) if (b + 4 * j + 16 * q >= skip) out_st(out + a0.dst + b + 4 * j + 16 * q, v[4 * j + q] * 64.f, oq_scale);
                 }
             }
         }
     }
 }
 
-template <bool ROWS, class TI = float2>
+template <bool ROWS, class TI = float2, class TO = float2>
 static hipError_t init_fused4096_forms()
 {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_f4096<false, 2, ROWS, TI>), hipFuncAttributeMaxDynamicSharedMemorySize, f4_lds(2));
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_f4096<false, 2, ROWS, TI, TO>), hipFuncAttributeMaxDynamicSharedMemorySize, f4_lds(2));
     if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_f4096<false, 1, ROWS, TI>), hipFuncAttributeMaxDynamicSharedMemorySize, f4_lds(1));
+    e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_f4096<false, 1, ROWS, TI, TO>), hipFuncAttributeMaxDynamicSharedMemorySize, f4_lds(1));
     if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_f4096<true, 1, ROWS, TI>), hipFuncAttributeMaxDynamicSharedMemorySize, f4_lds_wide(1));
+    e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_f4096<true, 1, ROWS, TI, TO>), hipFuncAttributeMaxDynamicSharedMemorySize, f4_lds_wide(1));
     if (e != hipSuccess) return e;
-    return hipFuncSetAttribute(reinterpret_cast<const void *>(k_f4096<true, 2, ROWS, TI>), hipFuncAttributeMaxDynamicSharedMemorySize, f4_lds_wide(2));
+    return hipFuncSetAttribute(reinterpret_cast<const void *>(k_f4096<true, 2, ROWS, TI, TO>), hipFuncAttributeMaxDynamicSharedMemorySize, f4_lds_wide(2));
+}
+
+template <class TO>
+static hipError_t init_fused4096_oq()
+{
+    hipError_t e = init_fused4096_forms<false, float2, TO>();
+    if (e == hipSuccess) e = init_fused4096_forms<false, sc16, TO>();
+    return e != hipSuccess ? e : init_fused4096_forms<false, sc8, TO>();
 }
 
 hipError_t init_fused4096_kernels()
@@ -435,24 +460,26 @@ hipError_t init_fused4096_kernels()
     hipError_t e = init_fused4096_forms<false>();
     if (e == hipSuccess) e = init_fused4096_forms<true>();
     if (e == hipSuccess) e = init_fused4096_forms<false, sc16>();     // integer input: the channel outputs only (no ROWS form)
-    return e != hipSuccess ? e : init_fused4096_forms<false, sc8>();
+    if (e == hipSuccess) e = init_fused4096_forms<false, sc8>();
+    if (e == hipSuccess) e = init_fused4096_oq<sc16>();               // integer output, every input form (no ROWS form)
+    return e != hipSuccess ? e : init_fused4096_oq<sc8>();
 }
 
 int fused4096_tile_points() { return kF4TilePts; }
 
-template <bool ROWS, class TI = float2>
-static void launch_fused4096_form(dim3 grid, bool wide, int teams, hipStream_t s, const TI *in, size_t in_stride, float2 *out, int nb_chunk, int R,
+template <bool ROWS, class TI = float2, class TO = float2>
+static void launch_fused4096_form(dim3 grid, bool wide, int teams, hipStream_t s, const TI *in, size_t in_stride, TO *out, int nb_chunk, int R,
                                   int mbase, int nb_call, int fbm, const float2 *tw, int ntab, const float2 *wins, const F4Row *rows, unsigned wcls,
-                                  typename IqTail<TI>::type wf /* integer TI: the scale */)
+                                  typename IqTail<TI, TO>::type wf /* integer TI / TO: the scale(s) */)
 {
     if (wide && teams == 1)
-        hipLaunchKernelGGL((k_f4096<true, 1, ROWS, TI>), grid, dim3(256), f4_lds_wide(1), s, in, in_stride, out, nb_chunk, R, mbase, nb_call, fbm, tw, ntab / 4096, wins, rows, wcls, wf);
+        hipLaunchKernelGGL((k_f4096<true, 1, ROWS, TI, TO>), grid, dim3(256), f4_lds_wide(1), s, in, in_stride, out, nb_chunk, R, mbase, nb_call, fbm, tw, ntab / 4096, wins, rows, wcls, wf);
     else if (wide)
-        hipLaunchKernelGGL((k_f4096<true, 2, ROWS, TI>), grid, dim3(512), f4_lds_wide(2), s, in, in_stride, out, nb_chunk, R, mbase, nb_call, fbm, tw, ntab / 4096, wins, rows, wcls, wf);
+        hipLaunchKernelGGL((k_f4096<true, 2, ROWS, TI, TO>), grid, dim3(512), f4_lds_wide(2), s, in, in_stride, out, nb_chunk, R, mbase, nb_call, fbm, tw, ntab / 4096, wins, rows, wcls, wf);
     else if (teams == 2)
-        hipLaunchKernelGGL((k_f4096<false, 2, ROWS, TI>), grid, dim3(512), f4_lds(2), s, in, in_stride, out, nb_chunk, R, mbase, nb_call, fbm, tw, ntab / 4096, wins, rows, wcls, wf);
+        hipLaunchKernelGGL((k_f4096<false, 2, ROWS, TI, TO>), grid, dim3(512), f4_lds(2), s, in, in_stride, out, nb_chunk, R, mbase, nb_call, fbm, tw, ntab / 4096, wins, rows, wcls, wf);
     else
-        hipLaunchKernelGGL((k_f4096<false, 1, ROWS, TI>), grid, dim3(256), f4_lds(1), s, in, in_stride, out, nb_chunk, R, mbase, nb_call, fbm, tw, ntab / 4096, wins, rows, wcls, wf);
+        hipLaunchKernelGGL((k_f4096<false, 1, ROWS, TI, TO>), grid, dim3(256), f4_lds(1), s, in, in_stride, out, nb_chunk, R, mbase, nb_call, fbm, tw, ntab / 4096, wins, rows, wcls, wf);
 }
 
 // The launch shape both entries share: whether a wave holds wide rows (l = 512 / 1024: the WIDE form), the grid (one workgroup per `teams`
@@ -497,6 +524,39 @@ hipError_t launch_fused4096_iq(int fmt, float scale, const void *in, size_t in_s
         launch_fused4096_form<false>(sh.grid, sh.wide, teams, s, static_cast<const sc8 *>(in), in_stride, out, nb_chunk, R, mbase, nb_call, sh.fbm, tw, ntab,
                                      wins, rows, wcls, scale);
     return hipGetLastError();
+}
+
+template <class TO>
+static hipError_t fused4096_oq_in(int ifmt, float iscale, const void *in, size_t in_stride, TO *out, int nb_chunk, int R, int mbase, int nb_call,
+                                  const F4Shape &sh, const float2 *tw, int ntab, const float2 *wins, const F4Row *rows, unsigned wcls, int teams,
+                                  hipStream_t s, float oscale)
+{
+    if (ifmt == kIqFloat)
+        launch_fused4096_form<false>(sh.grid, sh.wide, teams, s, static_cast<const float2 *>(in), in_stride, out, nb_chunk, R, mbase, nb_call, sh.fbm, tw,
+                                     ntab, wins, rows, wcls, oscale);
+    else if (ifmt == kIqSc16)
+        launch_fused4096_form<false>(sh.grid, sh.wide, teams, s, static_cast<const sc16 *>(in), in_stride, out, nb_chunk, R, mbase, nb_call, sh.fbm, tw,
+                                     ntab, wins, rows, wcls, make_float2(iscale, oscale));
+    else if (ifmt == kIqSc8)
+        launch_fused4096_form<false>(sh.grid, sh.wide, teams, s, static_cast<const sc8 *>(in), in_stride, out, nb_chunk, R, mbase, nb_call, sh.fbm, tw,
+                                     ntab, wins, rows, wcls, make_float2(iscale, oscale));
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+hipError_t launch_fused4096_oq(int ifmt, float iscale, const void *in, size_t in_stride, int ofmt, float oscale, void *out, int nb_chunk, int R, int mbase,
+                               int nb_call, int64_t first_block, const float2 *tw, int ntab, const float2 *wins, const F4Row *rows, unsigned wcls, int teams,
+                               hipStream_t s)
+{
+    if (nb_chunk <= 0) return hipSuccess;
+    F4Shape sh;
+    const hipError_t e = f4_shape(nb_chunk, R, mbase, first_block, wcls, teams, &sh);
+    if (e != hipSuccess) return e;
+    if (ofmt == kIqSc16)
+        return fused4096_oq_in(ifmt, iscale, in, in_stride, static_cast<sc16 *>(out), nb_chunk, R, mbase, nb_call, sh, tw, ntab, wins, rows, wcls, teams, s, oscale);
+    if (ofmt == kIqSc8)
+        return fused4096_oq_in(ifmt, iscale, in, in_stride, static_cast<sc8 *>(out), nb_chunk, R, mbase, nb_call, sh, tw, ntab, wins, rows, wcls, teams, s, oscale);
+    return hipErrorInvalidValue;
 }
 
 }  // namespace fdc

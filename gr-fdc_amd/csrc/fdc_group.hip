@@ -34,6 +34,8 @@
 
 #include "fdc_hostplace.hpp"
 
+namespace fdc { int pipeline_output_format(const fdc_pipeline *p, float *scale); }   // fdc_api.hip
+
 namespace {
 
 #define FDC_ENTRY(name) return fdc::guarded(name, [&]() -> int {
@@ -183,6 +185,16 @@ int group_work(fdc_pipeline_group *g, const void *in, int nblocks, void *const *
     for (int c = 0; c < g->C; c++)
         if (!outs[c]) return fdc::set_error(FDC_ERR_INVALID_ARGUMENT, "null output buffer of channel %d", c);
     if (spectrum && !g->keep_spectrum) return fdc::set_error(FDC_ERR_INVALID_ARGUMENT, "spectrum output needs keep_spectrum");
+    // the output format is the members' own setting (fdc_pipeline_group_set_output_format sets them all; a member handle may have been set on its own):
+    // the spans are placed at its bytes per sample, so members that disagree are refused
+    float osc0 = 1.0f;
+    const int ofmt = fdc::pipeline_output_format(g->mem[0], &osc0);
+    for (fdc_pipeline *pm : g->mem) {
+        float osc = 1.0f;
+        if (fdc::pipeline_output_format(pm, &osc) != ofmt || std::memcmp(&osc, &osc0, sizeof(float)) != 0)
+            return fdc::set_error(FDC_ERR_INVALID_ARGUMENT, "the group's members have different output formats (set it with fdc_pipeline_group_set_output_format)");
+    }
+    const size_t osz = ofmt ? fdc::iq_bytes(ofmt) : 2 * sizeof(float);
     if (fmt && (fmt != FDC_IQ_SC16 && fmt != FDC_IQ_SC8)) return fdc::set_error(FDC_ERR_INVALID_ARGUMENT, "unknown complex integer format %d", fmt);
     if (fmt && (!std::isfinite(scale) || scale == 0.0f)) return fdc::set_error(FDC_ERR_INVALID_ARGUMENT, "the scale must be finite and not zero");
     if (g->in_form >= 0 && (g->in_form != fmt || (fmt && std::memcmp(&g->in_scale, &scale, sizeof(float)) != 0)))
@@ -210,7 +222,7 @@ int group_work(fdc_pipeline_group *g, const void *in, int nblocks, void *const *
         j.first = g->blockcount + b0;
         j.n = nb;
         for (int c = 0; c < g->C; c++)
-            g->outs[(size_t)i][(size_t)c] = outs[c] ? static_cast<unsigned char *>(outs[c]) + (size_t)b0 * (size_t)g->lout[(size_t)c] * 8 : nullptr;
+            g->outs[(size_t)i][(size_t)c] = outs[c] ? static_cast<unsigned char *>(outs[c]) + (size_t)b0 * (size_t)g->lout[(size_t)c] * osz : nullptr;
         j.outs = g->outs[(size_t)i].data();
         j.spectrum = spectrum ? static_cast<unsigned char *>(spectrum) + (size_t)b0 * (size_t)g->N * 8 : nullptr;
         j.real = real;
@@ -337,6 +349,19 @@ void fdc_pipeline_group_reset(fdc_pipeline_group *g)
     g->in_scale = 0.f;
     for (fdc_pipeline *p : g->mem) fdc_pipeline_reset(p);      // the members' input-form latches (their history comes with every span)
     g->dead = false;
+}
+
+int fdc_pipeline_group_set_output_format(fdc_pipeline_group *g, int32_t format, float scale)
+{
+    FDC_ENTRY("fdc_pipeline_group_set_output_format")
+    if (!g) return fdc::set_error(FDC_ERR_INVALID_ARGUMENT, "null group handle");
+    // every member takes the same arguments: the first refuses what all would refuse, before any has changed
+    for (fdc_pipeline *p : g->mem) {
+        const int rc = fdc_pipeline_set_output_format(p, format, scale);
+        if (rc != FDC_OK) return rc;
+    }
+    return FDC_OK;
+    FDC_ENTRY_END
 }
 
 int32_t fdc_pipeline_group_size(const fdc_pipeline_group *g) { return g ? (int32_t)g->mem.size() : -1; }

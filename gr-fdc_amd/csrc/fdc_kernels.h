@@ -97,6 +97,11 @@ hipError_t launch_fused4096(const float2 *in, size_t in_stride, float2 *out, int
 // the same on complex integer input (fmt: kIqSc16 / kIqSc8, fdc_iq.hpp; item m at in + m*in_stride samples), widened in the kernel's loads
 hipError_t launch_fused4096_iq(int fmt, float scale, const void *in, size_t in_stride, float2 *out, int nb_chunk, int R, int mbase, int nb_call,
                                int64_t first_block, const float2 *tw, int ntab, const float2 *wins, const F4Row *rows, unsigned wcls, int teams, hipStream_t s);
+// integer OUTPUT (ofmt: kIqSc16 / kIqSc8 with its scale, fdc_iq.hpp oq_bits; out: the same sample offsets, narrow elements), narrowed in the kernel's
+// stores; input ifmt: kIqFloat (in: float2) or kIqSc16 / kIqSc8 with iscale
+hipError_t launch_fused4096_oq(int ifmt, float iscale, const void *in, size_t in_stride, int ofmt, float oscale, void *out, int nb_chunk, int R, int mbase,
+                               int nb_call, int64_t first_block, const float2 *tw, int ntab, const float2 *wins, const F4Row *rows, unsigned wcls, int teams,
+                               hipStream_t s);
 
 // uniform plan (all channels l = 256, f = 256*slot, N = 256*N1): stage 1 + stage 2, no spectrum in memory.
 //   twq[n1][q] = W_N^(16*n1*q), cbt[n1][b] = (-1)^n1 W_N^(n1*b)  (16 entries per n1 each), shn[k2] = shape[k2]/N;
@@ -106,6 +111,9 @@ struct ScatterEnt { float2 *dst; long long out_off; int lout; int pad; };
 // dst[c][row0*lout_c + i] = src[nb*out_off_c + i], i < nb*lout_c: the [channel][nb*lout] result of one sub-batch is
 // stored straight into the caller's per-channel host buffers (PCIe writes, 512 B per wave)
 hipError_t launch_scatter_out(const float2 *src, const ScatterEnt *tab, int nchan, int nb, long long row0, hipStream_t s);
+// the same with integer output (ofmt: kIqSc16 / kIqSc8; dst holds narrow samples): src_fmt kIqFloat = src is float2, narrowed times scale on the way
+// (oq_bits); src_fmt = ofmt = src holds the narrow samples already (a copy)
+hipError_t launch_scatter_oq(int src_fmt, const void *src, int ofmt, float scale, const ScatterEnt *tab, int nchan, int nb, long long row0, hipStream_t s);
 
 hipError_t launch_poly_stage1(const float2 *in, size_t in_stride, float2 *g, int N1, int R, int nb_chunk,
                               const float2 *tw256, const float2 *twq, const float2 *cbt, const float *shn,
@@ -141,6 +149,12 @@ hipError_t launch_poly_block(const float2 *in, size_t in_stride, float2 *out, in
 // the same on complex integer input (fmt: kIqSc16 / kIqSc8, fdc_iq.hpp; in_stride in samples), widened in the kernel's loads (the channelizer forms)
 hipError_t launch_poly_block_iq(int fmt, float scale, const void *in, size_t in_stride, float2 *out, int nb_chunk, int mbase, int nb_call,
                                 const float2 *tw256, const float2 *twq, const float2 *cbt, const float *shn,
+                                const long long *slot_off, unsigned out_bytes, int ncu, int hints, hipStream_t s,
+                                int r, long long first_block, hipEvent_t ev_start, hipEvent_t ev_stop, int R, float2 *scratch, int N);
+// integer OUTPUT (ofmt: kIqSc16 / kIqSc8 with its scale; out_bytes: the narrow extent), narrowed in the kernel's stores, on input ifmt (kIqFloat: float2,
+// or kIqSc16 / kIqSc8 with iscale); streamed stores only (hints bit 0 set)
+hipError_t launch_poly_block_oq(int ifmt, float iscale, const void *in, size_t in_stride, int ofmt, float oscale, void *out, int nb_chunk, int mbase,
+                                int nb_call, const float2 *tw256, const float2 *twq, const float2 *cbt, const float *shn,
                                 const long long *slot_off, unsigned out_bytes, int ncu, int hints, hipStream_t s,
                                 int r, long long first_block, hipEvent_t ev_start, hipEvent_t ev_stop, int R, float2 *scratch, int N);
 bool poly_block_supports(int N);
@@ -201,6 +215,8 @@ hipError_t launch_group_power(const float2 *spec, int N, int nblocks, float *gpo
 hipError_t launch_real_to_complex(const float *in, float2 *out, size_t n, hipStream_t s);
 // complex integer samples (fmt: kIqSc16 / kIqSc8, fdc_iq.hpp) -> complex float, (I * scale, Q * scale)
 hipError_t launch_iq_to_complex(int fmt, float scale, const void *in, float2 *out, size_t n, hipStream_t s);
+// complex float -> complex integer samples (fmt: kIqSc16 / kIqSc8), each component saturate(round_half_even(x * scale)) (fdc_iq.hpp oq_bits)
+hipError_t launch_complex_to_iq(int fmt, float scale, const float2 *in, void *out, size_t n, hipStream_t s);
 
 hipError_t launch_scale(const float2 *in, float2 *out, size_t n, float k, hipStream_t s);
 

@@ -16,6 +16,7 @@
 //   cut + *l                python/FrequencyDomainChannelizer.py:229-231
 #include "fdc_kernels.h"
 #include <cstdlib>
+#include <type_traits>
 #include "fdc_radix16.hpp"
 #include "fdc_iq.hpp"
 
@@ -995,6 +996,61 @@ hipError_t launch_iq_to_complex(int fmt, float scale, const void *in, float2 *ou
     else if (fmt == kIqSc8) hipLaunchKernelGGL(k_iq_to_complex<sc8>, dim3((unsigned)g), dim3(256), 0, s, static_cast<const sc8 *>(in), out, n, scale);
     else return hipErrorInvalidValue;
     return hipGetLastError();
+}
+
+// complex float -> complex integer samples, times scale (fdc_iq.hpp oq_narrow): the narrowing back end of the plans without integer stores of their own
+template <class TO>
+__global__ __launch_bounds__(256) void k_complex_to_iq(const float2 *__restrict__ in, TO *__restrict__ out, size_t n, float scale)
+{
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) out[i] = oq_narrow(TO{}, from2(in[i]), scale);
+}
+
+hipError_t launch_complex_to_iq(int fmt, float scale, const float2 *in, void *out, size_t n, hipStream_t s)
+{
+    if (!n) return hipSuccess;
+    size_t g = (n + 255) / 256; if (g > 8192) g = 8192;
+    if (fmt == kIqSc16) hipLaunchKernelGGL(k_complex_to_iq<sc16>, dim3((unsigned)g), dim3(256), 0, s, in, static_cast<sc16 *>(out), n, scale);
+    else if (fmt == kIqSc8) hipLaunchKernelGGL(k_complex_to_iq<sc8>, dim3((unsigned)g), dim3(256), 0, s, in, static_cast<sc8 *>(out), n, scale);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+// registered outputs with integer output: k_scatter_out's layout; TS = float2 narrows on the way (the caller's mapped buffer receives the narrow bytes
+// only), TS = TO copies samples the kernels narrowed already
+template <class TS, class TO>
+__global__ __launch_bounds__(256) void k_scatter_oq(const TS *__restrict__ src, const ScatterEnt *__restrict__ tab, int nb, long long row0, float scale)
+{
+    const ScatterEnt e = tab[blockIdx.y];
+    if (!e.dst) return;
+    const size_t n = (size_t)nb * e.lout;
+    const TS *sp = src + (size_t)nb * e.out_off;
+    TO *d = reinterpret_cast<TO *>(e.dst) + (size_t)row0 * e.lout;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+        if constexpr (std::is_same<TS, float2>::value) d[i] = oq_narrow(TO{}, from2(sp[i]), scale);
+        else d[i] = sp[i];
+    }
+}
+
+template <class TO>
+static hipError_t scatter_oq_to(int src_fmt, const void *src, float scale, const ScatterEnt *tab, int nchan, int nb, long long row0, hipStream_t s)
+{
+    for (int c0 = 0; c0 < nchan; c0 += 32768) {
+        const int nc = nchan - c0 < 32768 ? nchan - c0 : 32768;
+        if (src_fmt == kIqFloat)
+            hipLaunchKernelGGL((k_scatter_oq<float2, TO>), dim3(4, nc), dim3(256), 0, s, static_cast<const float2 *>(src), tab + c0, nb, row0, scale);
+        else
+            hipLaunchKernelGGL((k_scatter_oq<TO, TO>), dim3(4, nc), dim3(256), 0, s, static_cast<const TO *>(src), tab + c0, nb, row0, scale);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_scatter_oq(int src_fmt, const void *src, int ofmt, float scale, const ScatterEnt *tab, int nchan, int nb, long long row0, hipStream_t s)
+{
+    if (nchan <= 0 || nb <= 0) return hipSuccess;
+    if (src_fmt != kIqFloat && src_fmt != ofmt) return hipErrorInvalidValue;
+    if (ofmt == kIqSc16) return scatter_oq_to<sc16>(src_fmt, src, scale, tab, nchan, nb, row0, s);
+    if (ofmt == kIqSc8) return scatter_oq_to<sc8>(src_fmt, src, scale, tab, nchan, nb, row0, s);
+    return hipErrorInvalidValue;
 }
 
 hipError_t launch_scale(const float2 *in, float2 *out, size_t n, float k, hipStream_t s)

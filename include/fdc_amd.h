@@ -120,7 +120,8 @@ int32_t fdc_pipeline_channel_lout(const fdc_pipeline *p, int channel);
 /* work()-shaped entry: host buffers, stateful like the block chain (overlap history + window counters
  * persist across calls; lib/overlap_save_impl.h:33, lib/phase_shifting_windowing_vcc_impl.h:47).
  *   in          nblocks*(N-N/R) new samples (what stream_to_vector hands overlap_save)
- *   outs[c]     nblocks*lout_c samples for channel c (hier output port c)
+ *   outs[c]     nblocks*lout_c samples for channel c (hier output port c), in the handle's output format (fdc_pipeline_set_output_format below:
+ *               complex float unless it was set to sc16 / sc8; the same for every work, span, real, iq and device entry that names it)
  *   spectrum    NULL, or nblocks*N samples of the normalised spectrum (needs keep_spectrum)
  * Returns nblocks (items consumed, sync 1:1) or a negative fdc_status. */
 int fdc_pipeline_work(fdc_pipeline *p, const void *in, int nblocks, void *const *outs, void *spectrum);
@@ -165,6 +166,27 @@ int fdc_pipeline_work_iq(fdc_pipeline *p, int32_t format, float scale, const voi
 int fdc_pipeline_work_span_iq(fdc_pipeline *p, int32_t format, float scale, const void *halo, const void *in, int64_t first_block, int nblocks,
                               void *const *outs, void *spectrum);
 
+/* Complex INTEGER output (the other half of the integer I/O: recorders, network sinks and fixed-point demodulators behind an SDR front end want the
+ * channel streams back as sc16 / sc8).  A SETTING of the handle, not a latch: it may be changed between any two calls and applies from the next one; it
+ * does not touch the history, the block counter or the input-form latch, and survives fdc_pipeline_reset.
+ *   format   FDC_OQ_FC32 (default: complex float32, 8 bytes per sample), FDC_OQ_SC16 (int16 I, int16 Q interleaved: 4 bytes) or FDC_OQ_SC8 (int8: 2 bytes)
+ *   scale    float32; zero or not finite: FDC_ERR_INVALID_ARGUMENT (negative is allowed).  UHD's sc16 convention is scale = 32768.
+ * Each component of a channel sample y (exactly what the float entries write) becomes saturate(round_half_even(float32(y * scale))), the product rounded
+ * once and kept out of FMA contraction; NaN -> 0, +Inf -> the maximum, -Inf -> the minimum; saturation to [-32768, 32767] / [-128, 127].
+ * While it is set, outs[c] (host) or d_out (device) of fdc_pipeline_work, _work_real, _work_span, _work_span_real, _work_iq, _work_span_iq,
+ * _process_device, _process_device_iq and the group's work entries hold nblocks*lout_c samples OF THAT FORMAT (sample counts, offsets and lout are
+ * unchanged; the max_blocks rule stays computed at 8 bytes).  The debug spectrum stays complex float.  The entries that write complex float only —
+ * fdc_pipeline_work_sinks, _flush_sinks, _work_spectrum, _process_device_power, fdc_pipeline_work_waterfall — return FDC_ERR_INVALID_ARGUMENT and change
+ * nothing while it is not FC32.  Refused (FDC_ERR_INVALID_ARGUMENT) while a pipelined sinks batch is inside the handle (flush it first).
+ * Path 5 and the banks of 256-bin channels at N = 16384 / 32768 / 65536 (streamed stores) narrow in their kernels' own stores; every other plan narrows
+ * the complex float results on the device (fdc_pipeline_describe: "output sc16: fused" / "output sc16: narrowed").  The float staging of the narrowed
+ * route (max_blocks*sum_lout samples) is allocated by the first call that sets sc16 / sc8, the host entries' narrow staging at their first integer-output
+ * call; nothing in the steady state, nothing inside a device entry.  A device call that is narrowed needs nblocks <= max_blocks. */
+enum { FDC_OQ_FC32 = 0,   /* complex float32 (the default) */
+       FDC_OQ_SC16 = 1,   /* = FDC_IQ_SC16 */
+       FDC_OQ_SC8  = 2 }; /* = FDC_IQ_SC8 */
+int fdc_pipeline_set_output_format(fdc_pipeline *p, int32_t format, float scale);
+
 /* Optional: pin a host range that will be handed to fdc_pipeline_work() again and again (GNU Radio's circular buffers
  * live as long as the flowgraph: register them in start(), unregister in stop()).  A call whose `in` lies in a
  * registered range is DMA'd from it in place, and when every outs[c] does, the results are stored straight into
@@ -177,7 +199,7 @@ void fdc_pipeline_reset(fdc_pipeline *p);    /* history <- zeros, block counter 
 /* Device-resident entry (stateless; the form bench.py and a device-side flowgraph use).
  *   d_ring      device pointer: N/R halo samples preceding the span, then nblocks*(N-N/R) new samples
  *   first_block global index of the span's first block (window phase = first_block*shift mod R)
- *   d_out       device pointer, fdc_pipeline_output_samples() samples: channel c's stream of
+ *   d_out       device pointer, fdc_pipeline_output_samples() samples of the handle's output format: channel c's stream of
  *               nblocks*lout_c samples starts at fdc_pipeline_channel_offset(p, c, nblocks)
  *   d_spectrum  NULL or device pointer for nblocks*N samples (needs keep_spectrum)
  *   stream      hipStream_t (NULL = the handle's own stream).  Asynchronous: returns after enqueue. */
@@ -267,12 +289,15 @@ typedef struct fdc_pipeline_group fdc_pipeline_group;
 int fdc_pipeline_group_create(const fdc_pipeline_cfg *cfg, const int32_t *devices, int ndevices, int min_span_blocks,
                               fdc_pipeline_group **out);
 void fdc_pipeline_group_destroy(fdc_pipeline_group *g);
-/* work()-shaped, same arguments and state semantics as fdc_pipeline_work() / fdc_pipeline_work_real() */
+/* work()-shaped, same arguments and state semantics as fdc_pipeline_work() / fdc_pipeline_work_real(); outs[c] in the group's output format */
 int fdc_pipeline_group_work(fdc_pipeline_group *g, const void *in, int nblocks, void *const *outs, void *spectrum);
 int fdc_pipeline_group_work_real(fdc_pipeline_group *g, const void *in, int nblocks, void *const *outs, void *spectrum);
 /* complex integer input: the arguments, the bytes and the input-form latch of fdc_pipeline_work_iq (the group latches, as its members do) */
 int fdc_pipeline_group_work_iq(fdc_pipeline_group *g, int32_t format, float scale, const void *in, int nblocks, void *const *outs, void *spectrum);
 void fdc_pipeline_group_reset(fdc_pipeline_group *g);           /* history <- zeros, block counter <- 0, input form unlatched, error state cleared */
+/* complex integer output for every member (fdc_pipeline_set_output_format: the same arguments, refusals and setting semantics).  A group call takes
+ * the members' own setting and refuses (FDC_ERR_INVALID_ARGUMENT) when members set one by one through fdc_pipeline_group_member disagree. */
+int fdc_pipeline_group_set_output_format(fdc_pipeline_group *g, int32_t format, float scale);
 int32_t fdc_pipeline_group_size(const fdc_pipeline_group *g);
 fdc_pipeline *fdc_pipeline_group_member(fdc_pipeline_group *g, int i);   /* owned by the group (fdc_pipeline_path, sizes, timing) */
 int32_t fdc_pipeline_group_device(const fdc_pipeline_group *g, int i);
