@@ -176,7 +176,6 @@ struct fdc_pipeline {
     std::vector<size_t> rgroup_off;
     std::vector<char> rg_aligned, rg_out_aligned;
     int32_t *d_rgroups = nullptr;
-    unsigned long long *d_dbg = nullptr;   // FDC_BLOCK_DEBUG=1: cycle stamps of the block kernel, printed by synchronize
     int block_hints = 1;         // FDC_BLOCK_HINTS: 1 = nt output stores, 2 = nt input loads
     int block_min = kBlockMinBlocks;   // FDC_BLOCK_MIN_BLOCKS (tests: 1 = the block kernels at any size)
     float2 *d_g = nullptr;                       // uniform path (two launches): stage-1 output G, chunk*lout*N/256 samples
@@ -185,9 +184,9 @@ struct fdc_pipeline {
     float2 *d_twq = nullptr;                     // banks of 256-bin channels: W_N^(16 n1 q)
     // N = 65536 spectrum path: forward transform by the block kernel (fdc_block256.hip, FWD), own r = 0 tables
     bool fwd_block = false;
-    // N = 4096 in one launch (fdc_fused4096.hip; fdc_pipeline_path() = 5): the spectrum of a block stays in LDS.  A workgroup takes two blocks; f4_wave[w]:
-    // the rows wave w of its eight runs (2 channel + block of the pair; one width per wave), f4_cls the kernel's class nibble per wave; the device
-    // schedule is made in build_device_state
+    // N = 4096 in one launch (fdc_fused4096.hip; fdc_pipeline_path() = 5): the spectrum of a block stays in LDS.  A workgroup takes f4_teams blocks (one
+    // or two); f4_wave[w]: the rows wave w runs, up to eight (2 channel + block of the workgroup; one width per wave), f4_cls the kernel's class nibble
+    // per wave; the device schedule is made in build_device_state
     bool fused = false;
     std::vector<int> f4_wave[8];
     unsigned f4_cls = 0;
@@ -422,7 +421,7 @@ void fdc_pipeline_destroy(fdc_pipeline *p)
     if (!p) return;
     if (p->stream) (void)hipStreamSynchronize(p->stream);
     if (p->ev_hier) { (void)hipEventSynchronize(p->ev_hier); (void)hipEventDestroy(p->ev_hier); }   // kernels of the pipelined entry ran on the bank's stream
-    (void)hipFree(p->d_dbg); (void)hipFree(p->d_g); (void)hipFree(p->d_specfull); (void)hipFree(p->d_oq);
+    (void)hipFree(p->d_g); (void)hipFree(p->d_specfull); (void)hipFree(p->d_oq);
     for (auto e : p->events) (void)hipEventDestroy(e);
     for (auto st : {p->s_in, p->s_out}) if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
     for (int i = 0; i < 2; i++) {
@@ -957,12 +956,6 @@ int build_device_state(fdc_pipeline *p, const fdc_pipeline_cfg *cfg, const std::
         const int rc = build_keep_map(p);
         if (rc != FDC_OK) return rc;
     }
-    if (p->poly_block && !p->banks.empty() && p->banks[0].L == 256) {
-        if (const char *dg = fdc::debug_env("FDC_BLOCK_DEBUG")) if (dg[0] == '1') {
-            CHK_DEV(hipMalloc(&p->d_dbg, sizeof(unsigned long long) * 8 * 4 * 32));
-            CHK_DEV(hipMemset(p->d_dbg, 0, sizeof(unsigned long long) * 8 * 4 * 32));
-        }
-    }
     if (two_launch_possible(p)) {
         // G scratch of the two-launch form.  With block kernels only launch groups shorter than block_min take it
         const int L = p->banks[0].L, gblocks = p->poly_block ? std::min(chunk, p->block_min) : chunk;
@@ -1163,19 +1156,6 @@ int fdc_pipeline_synchronize(fdc_pipeline *p)
     if (!p) return fail(FDC_ERR_INVALID_ARGUMENT, "null handle");
     HIPCHK(hipSetDevice(p->cfg.device_id));
     HIPCHK(hipStreamSynchronize(p->stream));
-    if (p->d_dbg) {                                   // diagnostics: stage timeline of workgroup 0 of the last launch, cycles from block start
-        std::vector<unsigned long long> st(8 * 4 * 32);
-        HIPCHK(hipDeviceSynchronize());
-        HIPCHK(hipMemcpy(st.data(), p->d_dbg, sizeof(unsigned long long) * st.size(), hipMemcpyDeviceToHost));
-        for (int k = 0; k < 4; k++)
-            for (int w = 0; w < 8; w++) {
-                const unsigned long long *q = st.data() + (w * 4 + k) * 32;
-                if (!q[0]) continue;
-                std::fprintf(stderr, "[fdc block] round %d wave %d t0=%llu :", k, w, q[0] - st[0]);
-                for (int i = 1; i < 31; i++) std::fprintf(stderr, " %lld", (long long)(q[i] - q[0]));
-                std::fprintf(stderr, "\n");
-            }
-    }
     return FDC_OK;
     FDC_ENTRY_END
 }
@@ -1297,7 +1277,7 @@ static int launch_bank(fdc_pipeline *p, const fdc_pipeline::Bank &bk, const floa
     switch (bk.L) {
     case 256:
         HIPCHK(fdc::launch_poly_block(in0, (size_t)p->H, o, nb, m0, nblocks, p->d_tw256, p->d_twq, bk.d_cbt, bk.d_shn, bk.d_slot_off, out_bytes, p->ncu - p->reserved_cu,
-                                      p->block_hints, s, p->d_dbg, bk.r, first_block + m0, ev0, ev1, p->R, p->d_fscr, p->N));
+                                      p->block_hints, s, bk.r, first_block + m0, ev0, ev1, p->R, p->d_fscr, p->N));
         break;
     case 512:
         HIPCHK(fdc::launch_poly_block512(in0, (size_t)p->H, o, nb, m0, nblocks, p->d_tw256, p->d_tw512, p->d_twq512, bk.d_cbt, bk.d_shn, bk.d_slot_off,

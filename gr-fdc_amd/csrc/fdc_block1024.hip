@@ -11,7 +11,7 @@
 //                                    bit-swapped lane order in, lane rho' holds phase rho' afterwards
 //     kept: t = 4 m + rho' >= 512  <=>  m >= 128: eight values per lane and pass, as before: G is 8 passes x 8 = 128 VGPRs.
 // A wave owns one column per pass, the workgroup 8: 8 passes for the 64 columns.  A wave's own load instruction would be 64 single 8-byte samples, one
-// per row (64 cache lines): the rows are fetched by the workgroup as whole 64-byte row segments and handed over through LDS instead (STAGED, below).
+// per row (64 cache lines): the rows are fetched by the workgroup as whole 64-byte row segments and handed over through LDS instead (below).
 // Stage 2 is the FFT-64 over the columns n1 = 8 pass + c3: DFT-8 over the pass index in registers, W_64^(c3 klo), one trip through LDS
 // ([128 rows][8 klo][8 c3], four trips for the 512 kept rows), DFT-8 over c3 in the lane that owns (row, klo); a wave's store is 64 consecutive
 // samples of one channel.
@@ -58,7 +58,7 @@ constexpr int kKOffX = 8 * kKScrPts * 8;                         // 69376: end o
 // Sh: rows of 18 floats, i stride 304 floats (16 mod 64): the 4 x 8 rows of an 8-byte read's 32 lanes on all 64 banks once.
 constexpr int kKT1kRho = 16 * 18 + 8;
 constexpr int kKShRow = 18, kKShQ = 16 * kKShRow + 16;
-// STAGED loads (below): the next pass's 8 columns x 1024 rows as [column][row] planes, 2 points of padding per plane: a store instruction's sixteen
+// Staged loads (below): the next pass's 8 columns x 1024 rows as [column][row] planes, 2 points of padding per plane: a store instruction's sixteen
 // contiguous lanes are 4 column pairs x 4 rows, and an 8-byte STORE is banked on 32 dwords (MI355X_MICROARCH.md, LDS table): dword 2 (2 cp 1026 +
 // row) = 8 cp + 2 row mod 32 — four windows of 8 dwords, conflict-free (round 5; 1032-point planes put all four pairs on the same banks: 4-way).
 // A wave reads 64 consecutive rows of its one column: conflict-free either way.
@@ -79,11 +79,10 @@ struct B1kGeom {
     static constexpr int kOffB = kOffT1k + 4 * kKT1kRho * 8;      // [N1 n1][18]  W_N^(16 n1 q)
     static constexpr int kOffSh = kOffB + kN1 * 18 * 8;           // [4 i][16 b][18] floats: shape[b + 16 q + 256 i] / N
     static constexpr int kOffSoff = kOffSh + 4 * kKShQ * 4;       // [P klo][8] output offsets (bytes)
-    static constexpr int kLds = kOffSoff + kN1 * 4;               // P = 8: 96000
-    static constexpr int kOffStage = kLds;
-    static constexpr int kLdsStaged = kOffStage + 8 * kKStagePlane * 8;   // P = 8: 162048 <= 163840
+    static constexpr int kOffStage = kOffSoff + kN1 * 4;          // P = 8: 96000
+    static constexpr int kLds = kOffStage + 8 * kKStagePlane * 8; // P = 8: 162048 <= 163840
     static_assert(kOffCt % 16 == 0 && kOffB % 16 == 0 && kOffSh % 16 == 0 && kOffSoff % 16 == 0 && kOffStage % 16 == 0, "aligned table reads");
-    static_assert(kLdsStaged <= 160 * 1024, "LDS budget");
+    static_assert(kLds <= 160 * 1024, "LDS budget");
     static_assert((kLd * 2) % 8 == 4, "trip rows an odd number of 4-dword windows apart");
 };
 template <int P> __device__ __forceinline__ constexpr int b1k_pass_idx(int k) { return P == 8 ? 4 * (k & 1) + (k >> 1) : k; }
@@ -95,14 +94,14 @@ __device__ __forceinline__ void b1k_pass_dft(cf (&a)[P])
     else { const cf s0 = a[0] + a[1], d0 = a[0] - a[1]; a[0] = s0; a[1] = d0; }
 }
 
-// STAGED = true: the rows reach the lanes through LDS.  One column per wave means a wave's own load instruction is 64 single samples from 64 rows
+// The rows reach the lanes through LDS.  One column per wave means a wave's own load instruction would be 64 single samples from 64 rows
 // (64 cache lines); staged, the workgroup's eight waves fetch the pass's 8 columns x 1024 rows in 16-byte pieces of whole 64-byte row segments (wave w:
 // rows 128 w .., 16 rows x 4 column pairs per instruction: 16 lines, half the instructions), park them in registers for a pass as before, write them to
 // [column][row] planes in LDS at the pass boundary and read their own column back: two workgroup barriers per pass for an eighth of the line requests.
 // R4 = true: relinvovl = 4 (the reference's default overlap): 768 of the 1024 samples of every inverse transform are kept.  The rows m >= 128 of all four
 // phases stay in the G registers as for R = 2 (output rows 256 ..); the rows 64 <= m < 128 go to 128 KiB of per-workgroup scratch ([pass][q - 4][thread]:
 // the L2 holds it) and come back for a second, 256-row run of stage 2 (output rows 0 .. 255), as in fdc_block512.hip.
-template <bool NT, bool STAGED, bool R4, int P = 8>
+template <bool NT, bool R4, int P = 8>
 __global__ FDC_PLAIN_DS1K __launch_bounds__(512) void k_blk1024(const float2 *__restrict__ in, size_t in_stride, float2 *__restrict__ out,
                                                       const float2 *__restrict__ tw256, const float2 *__restrict__ tw1024 /* W_1024^k, k < 1024 */,
                                                       const float2 *__restrict__ twq /* [n1][16] W_N^(16 n1 q) */,
@@ -134,14 +133,11 @@ __global__ FDC_PLAIN_DS1K __launch_bounds__(512) void k_blk1024(const float2 *__
     if (first >= nb) return;
 
     constexpr unsigned inbytes = (unsigned)GM::kN * 8u;
-    constexpr unsigned kRow64 = 64u * (unsigned)kN1 * 8u;          // 64 rows further on, bytes (P = 8: 32 KiB)
-    constexpr unsigned kRow16 = 16u * (unsigned)kN1 * 8u;          // 16 rows (staged loads: one instruction further on)
-    // row n2 = 4 (16 a + b) + rho of column 8 pass + w: kN1 columns per row; a adds 64 rows, a pass 8 columns = 64 B
-    const unsigned voff = (unsigned)((4 * b + rho) * kN1 + w) * 8u;
+    constexpr unsigned kRow16 = 16u * (unsigned)kN1 * 8u;          // 16 rows: one load instruction further on
     const __amdgpu_buffer_rsrc_t rcb = make_rsrc(cbt, (unsigned)kN1 * 64u * 8u);
     const unsigned voffc = (unsigned)(w * 64 + b + 16 * iq) * 8u;
     cf LA[16], LB[16], cbA, cbB;
-    // staged: wave w fetches rows 128 w + 16 i + (lane >> 2), columns 2 (lane & 3), + 1 of the pass (16 bytes); instruction i adds 16 rows = 8 KiB
+    // wave w fetches rows 128 w + 16 i + (lane >> 2), columns 2 (lane & 3), + 1 of the pass (16 bytes); instruction i adds 16 rows = 8 KiB
     float2 *stg = reinterpret_cast<float2 *>(fdc_smem_b1k + GM::kOffStage);
     const unsigned voffs = (unsigned)((128 * w + (lane >> 2)) * kN1 + 2 * (lane & 3)) * 8u;
     float2 *const stw = stg + 2 * (lane & 3) * kKStagePlane + 128 * w + (lane >> 2);       // + 16 i rows; second column: + one plane
@@ -159,17 +155,10 @@ __global__ FDC_PLAIN_DS1K __launch_bounds__(512) void k_blk1024(const float2 *__
             st2(&stw[kKStagePlane + 16 * i], mk(__uint_as_float(PF[i].z), __uint_as_float(PF[i].w)));
         }
     };
-    if constexpr (STAGED) {
-        stage_load(first, 0);
-        cbA = bld2(rcb, voffc, 0);
-        stage_write();                                           // pass 0 of the first block: visible after the barrier behind the tables
-        stage_load(first, 1);
-    } else {
-        const __amdgpu_buffer_rsrc_t rin = make_rsrc(in + (size_t)first * in_stride, inbytes);
-#pragma unroll
-        for (int a = 0; a < 16; a++) LA[a] = bld2(rin, voff, (unsigned)a * kRow64);
-        cbA = bld2(rcb, voffc, 0);
-    }
+    stage_load(first, 0);
+    cbA = bld2(rcb, voffc, 0);
+    stage_write();                                               // pass 0 of the first block: visible after the barrier behind the tables
+    stage_load(first, 1);
     // ---- tables
     for (int i = tid; i < 256; i += 512) wrow[(i >> 4) * 18 + (i & 15)] = tw256[((i >> 4) * (i & 15)) & 255];
     for (int i = tid; i < 1024; i += 512) {
@@ -204,30 +193,16 @@ __global__ FDC_PLAIN_DS1K __launch_bounds__(512) void k_blk1024(const float2 *__
         const int mnext = m + grid < nb ? m + grid : m;
         typedef unsigned long long gvec __attribute__((ext_vector_type(P)));
         gvec G[8];
-        auto one_pass = [&](const int ps, cf (&cur)[16], const cf cb, cf (&L)[16], cf &cbn) __attribute__((always_inline)) {
-            if constexpr (STAGED) {
-                // the pass's rows are in the planes (written a pass ago, or by the prologue): take this lane's sixteen, then hand the planes over to
-                // the rows that arrived in the meantime (pass + 1) and request pass + 2
-                __syncthreads();
+        auto one_pass = [&](const int ps, cf (&cur)[16], const cf cb, cf &cbn) __attribute__((always_inline)) {
+            // the pass's rows are in the planes (written a pass ago, or by the prologue): take this lane's sixteen, then hand the planes over to
+            // the rows that arrived in the meantime (pass + 1) and request pass + 2
+            __syncthreads();
 #pragma unroll
-                for (int a = 0; a < 16; a++) cur[a] = ld2(&strd[64 * a]);
-                __syncthreads();
-                stage_write();
-                stage_load(ps < P - 2 ? m : mnext, (ps + 2) & (P - 1));
-                cbn = bld2(rcb, voffc, (unsigned)((ps + 1) & (P - 1)) * 4096u);
-            } else {
-                const int pn = ps < P - 1 ? ps + 1 : 0;
-                const int mb = ps < P - 1 ? m : mnext;
-                const __amdgpu_buffer_rsrc_t rin = make_rsrc(in + (size_t)mb * in_stride + 8 * pn, inbytes);
-                if (hints & 2) {
-#pragma unroll
-                    for (int a = 0; a < 16; a++) L[a] = bld2_nt(rin, voff, (unsigned)a * kRow64);
-                } else {
-#pragma unroll
-                    for (int a = 0; a < 16; a++) L[a] = bld2(rin, voff, (unsigned)a * kRow64);
-                }
-                cbn = bld2(rcb, voffc, (unsigned)pn * 4096u);
-            }
+            for (int a = 0; a < 16; a++) cur[a] = ld2(&strd[64 * a]);
+            __syncthreads();
+            stage_write();
+            stage_load(ps < P - 2 ? m : mnext, (ps + 2) & (P - 1));
+            cbn = bld2(rcb, voffc, (unsigned)((ps + 1) & (P - 1)) * 4096u);
             // ---- the 256-point forward transform of this lane's phase: exactly the old stage 1
             dft16<false>(cur);
             {
@@ -301,8 +276,8 @@ __global__ FDC_PLAIN_DS1K __launch_bounds__(512) void k_blk1024(const float2 *__
         };
 #pragma nounroll
         for (int pp = 0; pp < P; pp += 2) {
-            one_pass(pp, LA, cbA, LB, cbB);
-            one_pass(pp + 1, LB, cbB, LA, cbA);
+            one_pass(pp, LA, cbA, cbB);
+            one_pass(pp + 1, LB, cbB, cbA);
         }
         // ---------------- stage 2: FFT-N1 over n1 = 8 pass + c3 of every row t' = rowbase + 4 (b + 16 j) + rho = rowbase + lane + 64 j ----------------
         // get(j, pass): the value of row group j; rowbase: first output row of the run; njc: its number of 64-row groups (a trip holds kJT of them:
@@ -384,10 +359,6 @@ __global__ FDC_PLAIN_DS1K __launch_bounds__(512) void k_blk1024(const float2 *__
     }
 }
 
-#ifndef FDC_1K_STAGED
-#define FDC_1K_STAGED 1
-#endif
-
 bool poly_block1024_supports(int N, int R)
 {
     return (N == 65536 || N == 32768 || N == 16384) && (R == 2 || R == 4);
@@ -396,12 +367,11 @@ bool poly_block1024_supports(int N, int R)
 hipError_t init_block1024_kernels()
 {
     hipError_t e = hipSuccess;
-#define FDC_SET1K(A, B, C, P) \
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_blk1024<A, B, C, P>), hipFuncAttributeMaxDynamicSharedMemorySize, B ? B1kGeom<P>::kLdsStaged : B1kGeom<P>::kLds);
-    FDC_SET1K(true, false, false, 8) FDC_SET1K(false, false, false, 8) FDC_SET1K(true, true, false, 8) FDC_SET1K(false, true, false, 8)
-    FDC_SET1K(true, false, true, 8) FDC_SET1K(false, false, true, 8) FDC_SET1K(true, true, true, 8) FDC_SET1K(false, true, true, 8)
-    FDC_SET1K(true, true, false, 4) FDC_SET1K(false, true, false, 4) FDC_SET1K(true, true, true, 4) FDC_SET1K(false, true, true, 4)
-    FDC_SET1K(true, true, false, 2) FDC_SET1K(false, true, false, 2) FDC_SET1K(true, true, true, 2) FDC_SET1K(false, true, true, 2)
+#define FDC_SET1K(A, C, P) \
+    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_blk1024<A, C, P>), hipFuncAttributeMaxDynamicSharedMemorySize, B1kGeom<P>::kLds);
+#define FDC_SET1KP(P) FDC_SET1K(true, false, P) FDC_SET1K(false, false, P) FDC_SET1K(true, true, P) FDC_SET1K(false, true, P)
+    FDC_SET1KP(8) FDC_SET1KP(4) FDC_SET1KP(2)
+#undef FDC_SET1KP
 #undef FDC_SET1K
     return e;
 }
@@ -415,22 +385,18 @@ hipError_t launch_poly_block1024(const float2 *in, size_t in_stride, float2 *out
     if (!poly_block1024_supports(N, R) || (R == 4 && !scratch)) return hipErrorInvalidValue;
     int grid = ncu > 0 ? ncu : 256;
     if (grid > nb_chunk) grid = nb_chunk;
-    constexpr bool kStaged = FDC_1K_STAGED != 0;
-#define FDC_L1K(A, S, C, P) \
-    hipExtLaunchKernelGGL((k_blk1024<A, S, C, P>), dim3((unsigned)grid), dim3(512), S ? B1kGeom<P>::kLdsStaged : B1kGeom<P>::kLds, s, ev_start, ev_stop, 0u, in, in_stride, \
+#define FDC_L1K(A, C, P) \
+    hipExtLaunchKernelGGL((k_blk1024<A, C, P>), dim3((unsigned)grid), dim3(512), B1kGeom<P>::kLds, s, ev_start, ev_stop, 0u, in, in_stride, \
                           out, tw256, tw1024, twq, cbt, shn, slot_off, (long long)mbase * (C ? 768 : 512), (long long)nb_call, out_bytes, nb_chunk, hints, \
                           half ? 1 : 0, C ? scratch : (float2 *)nullptr)
     const bool nt = (hints & 1) != 0;
-    if (N == 65536) {
-        if (R == 4) { if (nt) FDC_L1K(true, kStaged, true, 8); else FDC_L1K(false, kStaged, true, 8); }
-        else { if (nt) FDC_L1K(true, kStaged, false, 8); else FDC_L1K(false, kStaged, false, 8); }
-    } else if (N == 32768) {
-        if (R == 4) { if (nt) FDC_L1K(true, true, true, 4); else FDC_L1K(false, true, true, 4); }
-        else { if (nt) FDC_L1K(true, true, false, 4); else FDC_L1K(false, true, false, 4); }
-    } else {
-        if (R == 4) { if (nt) FDC_L1K(true, true, true, 2); else FDC_L1K(false, true, true, 2); }
-        else { if (nt) FDC_L1K(true, true, false, 2); else FDC_L1K(false, true, false, 2); }
-    }
+#define FDC_L1KP(P) \
+    do { \
+        if (R == 4) { if (nt) FDC_L1K(true, true, P); else FDC_L1K(false, true, P); } \
+        else { if (nt) FDC_L1K(true, false, P); else FDC_L1K(false, false, P); } \
+    } while (0)
+    if (N == 65536) FDC_L1KP(8); else if (N == 32768) FDC_L1KP(4); else FDC_L1KP(2);
+#undef FDC_L1KP
 #undef FDC_L1K
     return hipGetLastError();
 }

@@ -84,18 +84,6 @@ struct BlkGeom {
     static constexpr int kOffWrowF = kOffSoffOff + kN1 * 4;
     static constexpr int kLdsOff = kOffWrowF + 16 * 18 * 8;       // P = 8: 163584 <= 163840
     static_assert(kLdsOff <= 160 * 1024 && kLds <= 160 * 1024, "LDS budget");
-    // STG (P = 8): the pass's 32 columns x 256 rows staged in LDS as [row][34] (rows 68 dwords apart: the sixteen lanes of a 16-byte store cover a row's
-    // 64 banks, the sixteen row groups x four columns of an 8-byte read fall on every bank twice — the minimum for 512 bytes), behind the strips;
-    // the tables move up by 2 KiB and the SA rows give up their padding for it
-    static constexpr int kPlLd = 34;
-    static constexpr int kOffPl = kBlkOffX;
-    static constexpr int kPlBytes = 256 * kPlLd * 8;              // 69632
-    static constexpr int kOffWrowS = kOffPl + kPlBytes;           // 139008
-    static constexpr int kOffBS = kOffWrowS + 16 * 18 * 8;
-    static constexpr int kOffSAS = kOffBS + 32 * 18 * 8;
-    static constexpr int kOffSoffS = kOffSAS + 16 * P * 16 * 8;
-    static constexpr int kLdsS = kOffSoffS + kN1 * 4;             // P = 8: 163328
-    static_assert(P != 8 || kLdsS <= 160 * 1024, "LDS budget (staged)");
     static_assert(kOffCt >= kBlkOffX && kOffCt + 32 * P * 8 <= kOffWrow, "stage-2 trip buffer and twiddles below the tables, tables above the strips");
     static_assert((16 * (kJB - 1) * kLd + 32 * (P - 1)) * 8 < 65536, "ds offsets of a base register");
 };
@@ -105,17 +93,13 @@ struct BlkGeom {
 // twice what the G registers hold.  Rounds 2-5 kept the half k2 < 128 in G and sent the other half through 256 KiB of per-workgroup
 // scratch: the counters (profiles/r06/pmc_summary_fwd.txt) say that trip is real traffic — WRITE 807 MB + FETCH 560 MB per 1024 blocks
 // for 805 MB of work, at 5.5 TB/s: the kernel was bound by the memory system on bytes of which 39 % were its own scratch.
-// Round 6 built the alternative (-DFDC_FWD_TWO_WG=1; not shipped, it measured 5 % slower — see the macro below): TWO WORKGROUPS PER BLOCK,
-// no scratch.  A work item is (block, half h): the workgroup computes the columns' forward
-// FFT-256 for the rows k2 = b + 16 q with q = 2 r + h only — bit 4 of k2, so that a half is every other 16-bin run = every other
-// 128-byte line of the spectrum: both halves store whole lines — 128 rows, exactly G.  The split is a decimation in frequency of
-// the SECOND DFT-16 (over the exchanged index bb): q even: DFT-8 of v[bb] + v[bb + 8]; q odd: DFT-8 of (v[bb] - v[bb + 8]) W_16^bb;
-// first DFT-16, twiddle and exchange are done in full by both halves (stage-1 arithmetic per half: 0.7 of the whole).  The two
-// halves of a block are neighbouring slots of ONE XCD in the same round (h = slot & 1 is a constant of the workgroup): the input
-// rows are fetched from memory once and the second reader hits that XCD's L2, as the overlap half of the next block always did.
-// Stage 2 is unchanged and runs once per item; its "slots" are the k1 of the spectrum: bins 256 c + k2 of the SHIFTED spectrum (the
-// (-1)^n1 of cbt moves k1 by 128 = fftshift); a wave store is four 16-bin runs 32 bins apart.  This is what plans that need a
-// spectrum in memory (mixed channel plans, the sinks, the debug port) use instead of two passes through a scratch of the whole batch.
+// Round 6 measured the alternative, two workgroups per block (each the forward FFT-256 of every column for half of the rows k2) and no scratch:
+// it moves 805 MB instead of 1367 and is SLOWER, full band 0.2525 against 0.2405 ms per 1024 blocks, nothing written 0.2017 against 0.188
+// (profiles/r06/fwd_ab.txt): its passes are a third of the channelizer's (no inverse transform), so the rows requested one pass ahead are not
+// there when the pass starts, and it asks for every row twice.
+// Stage 2 runs on G, then on the scratch half; its "slots" are the k1 of the spectrum: bins 256 c + k2 of the SHIFTED spectrum (the (-1)^n1
+// of cbt moves k1 by 128 = fftshift).  This is what plans that need a spectrum in memory (mixed channel plans, the sinks, the debug port) use
+// instead of two passes through a scratch of the whole batch.
 // R4 = true: the channelizer at relinvovl = 4 (the reference's default overlap, grc/FDC_FrequencyDomainChannelizer.xml:61): three
 // quarters of every inverse transform are kept, G is 192 rows x N1 columns.  The rows t >= 128 stay in the G registers
 // as for R = 2; the rows 64 <= t < 128 take the route of the forward-transform variant: per-workgroup scratch (L2),
@@ -135,56 +119,41 @@ __device__ __forceinline__ void blk_pass_dft(cf (&a)[P])
     }
 }
 
-// STG = true (P = 8, the plain channelizer): the input rows reach the lanes through LDS.  A wave's own load instruction is 16 rows x 32 bytes (16 cache
-// lines, each of which four waves ask for); staged, wave w fetches rows 32 w .. of the pass's 32 columns in 16-byte pieces of whole 256-byte row
-// segments (4 rows per instruction: 8 lines, half the instructions: a quarter of the line requests), keeps them in registers for a pass as before, writes
-// them to [row][34] in LDS at the pass boundary and reads its own column's sixteen rows back: two workgroup barriers per pass (profiles/r04/NOTES.md
-// section 11; the same move took k_blk1024 from 0.20 to 0.30; here it costs 1.5 %: a build variant, -DFDC_BLK_STAGED=1).
 // HALF = true: every channel half a slot higher (f = 256 slot + 128: a bank centred on multiples of 256 bins) WITHOUT the offset machinery.  The block
 // modulated by exp(-2 pi i 128 n / N) = W_N^(128 n1) (-1)^n2: the (-1)^n2 moves every column's spectrum by half its length, which together with the
 // ifftshift of the inverse is the identity — the value stays in its register, the tables are read at k2 ^ 128 (q ^ 8), W_N^(128 n1) is in cbt (the host
 // builds it for r = 128 as for any offset).  No second twiddle table, no rotated exchange, both row sets: the on-grid rate, and relinvovl 4 too
 // (128 mod 4 = 0: the window phase stays 0).
-// -DFDC_FWD_TWO_WG=1 builds the forward-transform variant as TWO WORKGROUPS PER BLOCK without scratch (round 6, tools/build_variant.sh); the
-// shipped form is the round-2..5 one (one workgroup per block, the half k2 >= 128 through per-workgroup scratch).  Measured on one box,
-// alternating (profiles/r06/fwd_ab.txt): full band 0.2525 against 0.2405 ms per 1024 blocks, nothing written 0.2017 against 0.188 — the
-// two-workgroup form moves 805 MB instead of 1367 and is SLOWER: its passes are a third of the channelizer's (no inverse transform), so the
-// rows requested one pass ahead are not there when the pass starts, and it asks for every row twice (16 cache lines per load instruction).
-#ifndef FDC_FWD_TWO_WG
-#define FDC_FWD_TWO_WG 0
-#endif
 // TI: the input sample, float2 or complex integer (sc16 / sc8: fdc_iq.hpp); integer rows are loaded as they are (4 / 2 bytes a sample) and
 // widened in registers at the top of the pass that transforms them, times iq_scale.  TO: the output sample, float2 or complex integer (sc16 / sc8:
 // narrowed in the store, times oq_scale, oq_bits): one dword / one 16-bit store per sample at the same per-wave offsets, scaled to the narrow element
-template <int P, bool NT, bool OFF, bool FWD, bool R4 = false, bool STG = false, bool HALF = false, class TI = float2, class TO = float2>
+template <int P, bool NT, bool OFF, bool FWD, bool R4 = false, bool HALF = false, class TI = float2, class TO = float2>
 __global__ FDC_PLAIN_DS __launch_bounds__(512, (P == 2 && !OFF && !R4 && !FWD) ? 4 : 2) void k_blk256(const TI *__restrict__ in, size_t in_stride, TO *__restrict__ out,
                                                 const float2 *__restrict__ tw256, const float2 *__restrict__ twq,
                                                 const float2 *__restrict__ cbt, const float *__restrict__ shn,
                                                 const long long *__restrict__ slot_off, long long out_base,
                                                 long long nb_call, unsigned out_bytes, int nb, int hints,
-                                                unsigned long long *__restrict__ dbg, int roff, long long first_block,
+                                                unsigned long long *__restrict__ dbg /* unused (null): keeps the kernarg layout */, int roff, long long first_block,
                                                 float2 *__restrict__ fwd_scratch, const unsigned *__restrict__ keep,
                                                 typename IqTail<TI, TO>::type gpow /* integer TI / TO: iq_scale / oq_scale */)
 {
     typedef BlkGeom<P> GM;
     constexpr bool kIq = !std::is_same<TI, float2>::value, kOq = !std::is_same<TO, float2>::value;
-    static_assert(!kIq || (!STG && !FWD), "integer input: the channelizer forms (the forward transform and the staged loads take widened input)");
-    static_assert(!kOq || (!STG && !FWD), "integer output: the channelizer forms");
+    static_assert(!kIq || !FWD, "integer input: the channelizer forms (the forward transform takes widened input)");
+    static_assert(!kOq || !FWD, "integer output: the channelizer forms");
     constexpr unsigned kEs = (unsigned)sizeof(TI);                              // bytes per input sample
     constexpr unsigned kOs = (unsigned)sizeof(TO);                              // bytes per output sample
     [[maybe_unused]] const float iq_scale = iq_tail_scale(gpow);
     [[maybe_unused]] const float oq_scale = oq_tail_scale(gpow);
-    static_assert(!STG || (P == 8 && !OFF && !R4), "staged loads: the plain channelizer and the forward transform at N = 65536");
-    static_assert(!HALF || (!OFF && !FWD && !STG), "the half-slot form is a variant of the on-grid channelizer");
+    static_assert(!HALF || (!OFF && !FWD), "the half-slot form is a variant of the on-grid channelizer");
     constexpr int kN1 = GM::kN1, kLd = GM::kLd, kJT = GM::kJT, kJB = GM::kJB;
-    constexpr bool FW2 = FWD && FDC_FWD_TWO_WG;                                  // forward transform, two workgroups per block
     float2 *scr = reinterpret_cast<float2 *>(fdc_smem_blk);                     // stage 1: 8 wave scratches; stage 2: the trip buffer
-    float2 *wrow = reinterpret_cast<float2 *>(fdc_smem_blk + (STG ? GM::kOffWrowS : GM::kOffWrow));     // [b][p] = W256^(b p), rows of 18
-    float2 *Bt = reinterpret_cast<float2 *>(fdc_smem_blk + (STG ? GM::kOffBS : GM::kOffB));             // [c5][q] = W_N^(16 c5 q)
-    float2 *SA = reinterpret_cast<float2 *>(fdc_smem_blk + (STG ? GM::kOffSAS : GM::kOffSA));           // [pass][b][q] = shape[b+16q]/N * W_N^(512 pass q)
-    // offset plans need a second twiddle table, staged loads 2 KiB more for the rows: the SA rows give up their padding (2-way conflicts on 8 reads per pass)
-    constexpr int kSaLd = (OFF || STG) ? 16 : 18;
-    unsigned *soff = reinterpret_cast<unsigned *>(fdc_smem_blk + (STG ? GM::kOffSoffS : OFF ? GM::kOffSoffOff : GM::kOffSoff));
+    float2 *wrow = reinterpret_cast<float2 *>(fdc_smem_blk + GM::kOffWrow);     // [b][p] = W256^(b p), rows of 18
+    float2 *Bt = reinterpret_cast<float2 *>(fdc_smem_blk + GM::kOffB);             // [c5][q] = W_N^(16 c5 q)
+    float2 *SA = reinterpret_cast<float2 *>(fdc_smem_blk + GM::kOffSA);           // [pass][b][q] = shape[b+16q]/N * W_N^(512 pass q)
+    // offset plans need a second twiddle table: the SA rows give up their padding (2-way conflicts on 8 reads per pass)
+    constexpr int kSaLd = OFF ? 16 : 18;
+    unsigned *soff = reinterpret_cast<unsigned *>(fdc_smem_blk + (OFF ? GM::kOffSoffOff : GM::kOffSoff));
     float2 *ctab = reinterpret_cast<float2 *>(fdc_smem_blk + GM::kOffCt);       // [c5][klo] = W_N1^(c5 klo): stage 2, after the DFT-P
     const int tid = threadIdx.x;
     // stage-1 roles
@@ -202,23 +171,9 @@ __global__ FDC_PLAIN_DS __launch_bounds__(512, (P == 2 && !OFF && !R4 && !FWD) ?
     // block order: round rho, XCD x = workgroup mod 8 (round-robin dispatch), slot = workgroup / 8:
     // block = rho*grid + x*(grid/8) + slot, i.e. one XCD works on grid/8 consecutive blocks at a time
     const int grid = gridDim.x, per = grid >> 3;
-    // FWD: the work items are (block, half); neighbouring slots of an XCD share a block (the launcher makes the grid even), so a round is
-    // grid / 2 blocks and an XCD still walks a contiguous run of them
-    const bool xmap = FW2 ? (grid & 15) == 0 : (grid & 7) == 0;
-    const int fhalf = FW2 ? (xmap ? (int)(blockIdx.x >> 3) & 1 : (int)blockIdx.x & 1) : 0;      // which rows this workgroup computes: k2 bit 4
-    const int mstride = FW2 ? grid >> 1 : grid;
-    const int first = FW2 ? (xmap ? (int)(blockIdx.x & 7) * (per >> 1) + (int)(blockIdx.x >> 4) : (int)(blockIdx.x >> 1))
-                          : (xmap ? (int)(blockIdx.x & 7) * per + (int)(blockIdx.x >> 3) : (int)blockIdx.x);
+    const bool xmap = (grid & 7) == 0;
+    const int first = xmap ? (int)(blockIdx.x & 7) * per + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
     if (first >= nb) return;
-#ifdef FDC_BLK_WGTIMES
-    // diagnostics (tools/wg_times.py): when every workgroup starts and ends, 100 MHz clock: [0..255] starts, [256..511] ends
-    if (dbg && tid == 0) dbg[blockIdx.x] = wall_clock64();
-#endif
-#ifdef FDC_BLK_STAGGER
-    // experiment: half of the workgroups (by slot parity inside their XCD) start FDC_BLK_STAGGER x 8128 cycles late, so that the
-    // store bursts of one half meet the load phases of the other
-    if ((blockIdx.x >> 3) & 1) for (int i = 0; i < FDC_BLK_STAGGER; i++) __builtin_amdgcn_s_sleep(127);
-#endif
 
     constexpr unsigned inbytes = (unsigned)GM::kN * kEs;
     constexpr unsigned kRowGrp = (unsigned)kN1 * 16u * kEs;       // 16 rows of kN1 columns, bytes (P = 8, float2: 32 KiB)
@@ -234,21 +189,7 @@ __global__ FDC_PLAIN_DS __launch_bounds__(512, (P == 2 && !OFF && !R4 && !FWD) ?
     const unsigned voffc = (unsigned)(c5 * 16 + b) * 8u;
     // two row sets: a pass computes on one while the rows of the next pass arrive in the other (no register copies between passes)
     cf LA[16], LB[16], cbA, cbB;
-    // staged: wave w fetches rows 32 w + 4 i + (lane >> 4), columns 2 (lane & 15), + 1 of the pass (16 bytes); instruction i adds 4 rows = 8 KiB
-    [[maybe_unused]] float2 *pl = reinterpret_cast<float2 *>(fdc_smem_blk + GM::kOffPl);
-    [[maybe_unused]] const unsigned voffs = (unsigned)((32 * w + (lane >> 4)) * kN1 + 2 * (lane & 15)) * 8u;
-    [[maybe_unused]] float2 *const plw = pl + (32 * w + (lane >> 4)) * GM::kPlLd + 2 * (lane & 15);      // + 4 i rows
-    [[maybe_unused]] const float2 *const plr = pl + b * GM::kPlLd + c5;                                   // this lane's rows 16 a + b of column c5
-    [[maybe_unused]] u32x4 PF[8];
-    [[maybe_unused]] auto stage_load = [&](int mb, int pn) __attribute__((always_inline)) {
-        const __amdgpu_buffer_rsrc_t rin = make_rsrc(in + (size_t)mb * in_stride + 32 * pn, inbytes);
-#pragma unroll
-        for (int i = 0; i < 8; i++) PF[i] = bld4(rin, voffs, (unsigned)i * 4u * (unsigned)kN1 * 8u);
-    };
-    if constexpr (STG) {
-        stage_load(first, 0);
-        cbA = bld2(rcb, voffc, 0);
-    } else {
+    {
         const __amdgpu_buffer_rsrc_t rin = make_rsrc(in + (size_t)first * in_stride, inbytes);
 #pragma unroll
         for (int a = 0; a < 16; a++) {
@@ -274,10 +215,9 @@ __global__ FDC_PLAIN_DS __launch_bounds__(512, (P == 2 && !OFF && !R4 && !FWD) ?
         soff[(i % P) * 32 + ((i / P) & 1) * 16 + rev16((i / P) >> 1)] = o >= 0 ? (unsigned)((o * nb_call + out_base) * kOs) : 0xFFFFFFFFu;
     }
     for (int i = tid; i < 32 * P; i += 512) ctab[i] = tw256[((i / P) * (i % P) * (8 / P)) & 255];     // [c5][klo] = W_N1^(c5 klo)
-    // FWD: entry r < 8 of a row is the one of q = 2 r + h (the rows this workgroup computes); entries 8 .. 15 are not read
-    Bt[(tid >> 4) * 18 + (tid & 15)] = twq[HALF ? tid ^ 8 : FW2 ? (tid & ~15) + ((2 * (tid & 15) + fhalf) & 15) : tid];   // c5 = tid >> 4 < 32, q = tid & 15 (HALF: the entry of q ^ 8)
+    Bt[(tid >> 4) * 18 + (tid & 15)] = twq[HALF ? tid ^ 8 : tid];   // c5 = tid >> 4 < 32, q = tid & 15 (HALF: the entry of q ^ 8)
     for (int i = tid; i < 256 * P; i += 512) {
-        const int ps = i >> 8, bb = (i >> 4) & 15, q = i & 15, qt = HALF ? q ^ 8 : FW2 ? (2 * q + fhalf) & 15 : q;
+        const int ps = i >> 8, bb = (i >> 4) & 15, q = i & 15, qt = HALF ? q ^ 8 : q;
         const float2 t = twq[(size_t)(32 * ps) * 16 + qt];                       // W_N^(16 * 32 ps * q)
         const float s = shn[bb + 16 * qt];
         SA[(ps * 16 + bb) * kSaLd + q] = make_float2(t.x * s, t.y * s);
@@ -291,29 +231,14 @@ __global__ FDC_PLAIN_DS __launch_bounds__(512, (P == 2 && !OFF && !R4 && !FWD) ?
     const float2 *const btr = Bt + c5 * 18;
     const __amdgpu_buffer_rsrc_t rout = make_rsrc(out, out_bytes);
     // FWD / R4: this workgroup's scratch, [pass][j][thread]
-    constexpr bool kScr = (FWD && !FW2) || R4;
+    constexpr bool kScr = FWD || R4;
     const __amdgpu_buffer_rsrc_t rscr = make_rsrc(kScr ? fwd_scratch + (size_t)blockIdx.x * 32768 : fwd_scratch, kScr ? 32768u * 8u : 0u);
 
     // Two waves share a SIMD (waves w and w + 4).  The older one wins the issue arbitration and finishes stage 1 ~10 k cycles
     // earlier; s_setprio (either half favoured, or alternating per pass) changes nothing about that (profiles/r02/NOTES.md).
 
-    // diagnostics (FDC_BLOCK_DEBUG=1): cycle stamps of workgroup 0, per wave: [wave][block round][24]
-    [[maybe_unused]] int dbgk = 0;
-    // (only in the -DFDC_BLK_STAMPS build, tools/block_probe.py: the stamps cost half a dozen registers the kernel does not have)
-#ifdef FDC_BLK_STAMPS
-    // the stamps are taken into scalar registers (s_memtime) and written out once per block: no vector register is held
-#define FDC_STAMP(i) do { st[i] = __builtin_readcyclecounter(); } while (0)
-#else
-#define FDC_STAMP(i) do { } while (0)
-#endif
-#ifdef FDC_BLK_L2PF
-    unsigned pfd = 0;
-#endif
-    for (int m = first; m < nb; m += mstride) {
-        const int mnext = m + mstride < nb ? m + mstride : m;
-#ifdef FDC_BLK_STAMPS
-        unsigned long long st[32] = {};
-#endif
+    for (int m = first; m < nb; m += grid) {
+        const int mnext = m + grid < nb ? m + grid : m;
         const float sgn = (OFF && !R4 && (roff & 1) && ((first_block + m) & 1)) ? -1.0f : 1.0f;
         // R = 4 off the grid: the window phase counter (phase_shifting_windowing_vcc_impl.cc:82) is (block * (f mod 4)) mod 4, and phase p of the window
         // table is the window times exp(2 pi i p / 4) = j^p: one constant per block
@@ -322,7 +247,6 @@ __global__ FDC_PLAIN_DS __launch_bounds__(512, (P == 2 && !OFF && !R4 && !FWD) ?
             const int pc = (int)((((first_block + m) & 3) * (roff & 3)) & 3);
             phs = mk(pc == 0 ? 1.f : pc == 2 ? -1.f : 0.f, pc == 1 ? 1.f : pc == 3 ? -1.f : 0.f);
         }
-        FDC_STAMP(0);
         // G[j][pass]: row t' = b + 16 j, column 32 pass + c5.  One complex value = one 64-bit vector element (two floats packed
         // into an integer): the element index is the pass number at run time, and with 64-bit elements the compiler brackets
         // all sixteen moves of a pass with ONE s_set_gpr_idx_on / off pair (a pair per dword with 32-bit elements).  Integer,
@@ -336,59 +260,28 @@ __global__ FDC_PLAIN_DS __launch_bounds__(512, (P == 2 && !OFF && !R4 && !FWD) ?
         // pass (of this block, or pass 0 of this workgroup's next block; after the last block: the same rows again, unused)
         // are requested first, unconditionally (a conditional request costs a second set of register copies).
         auto one_pass = [&](const int ps, cf (&cur)[16], const cf cbc, cf (&L)[16], cf &cbn) __attribute__((always_inline)) {
-#ifdef FDC_BLK_L2PF
-            // experiment: touch every 128-byte line of the pass after next (this block's, or the next block's) once, two passes ahead
-            {
-                asm volatile("" :: "v"(pfd));
-                const int p2 = (ps + 2) & (P - 1);
-                const int mb2 = ps < P - 2 ? m : mnext;
-                const __amdgpu_buffer_rsrc_t rpf = make_rsrc(in + (size_t)mb2 * in_stride + 32 * p2, inbytes);
-                pfd = __builtin_amdgcn_raw_buffer_load_b32(rpf, (unsigned)((tid >> 1) * (kN1 * 8) + (tid & 1) * 128), 0u, 0);
-            }
-#endif
             const cf cb = (OFF && R4) ? cmul(cbc, phs) : OFF ? cbc * sgn : cbc;
-            if constexpr (STG) {
-                // the rows of this pass arrived in PF during the pass before: into the planes, this lane's sixteen back out, then the next pass's
-                // rows (of this block, or pass 0 of this workgroup's next block, kept in PF across stage 2) are requested
+            const int pn = ps < P - 1 ? ps + 1 : 0;
+            const int mb = ps < P - 1 ? m : mnext;
+            // the pass offset (32 columns) sits in the descriptor's base: every pass uses the same per-lane offset and the
+            // same 16 scalar row offsets
+            const __amdgpu_buffer_rsrc_t rin = make_rsrc(in + (size_t)mb * in_stride + 32 * pn, inbytes);
+            if constexpr (kIq) {
+                if (hints & 2) {
 #pragma unroll
-                for (int i = 0; i < 8; i++) *reinterpret_cast<u32x4 *>(&plw[4 * i * GM::kPlLd]) = PF[i];
-                __syncthreads();
-#pragma unroll
-                for (int a = 0; a < 16; a++) cur[a] = ld2(&plr[16 * a * GM::kPlLd]);
-                __syncthreads();                                  // every lane has its rows: the planes may be rewritten
-                stage_load(ps < P - 1 ? m : mnext, ps < P - 1 ? ps + 1 : 0);
-                cbn = bld2(rcb, voffc, (unsigned)(ps < P - 1 ? ps + 1 : 0) * 4096u);
-                if (ps == P - 1) {
-                    // stage 2's twiddles live where the planes' last rows were: rebuilt for every block (stage 2 reads them behind its first barrier)
-                    for (int i = tid; i < 32 * P; i += 512) ctab[i] = tw256[((i / P) * (i % P) * (8 / P)) & 255];
-                }
-            } else {
-                const int pn = ps < P - 1 ? ps + 1 : 0;
-                const int mb = ps < P - 1 ? m : mnext;
-                // the pass offset (32 columns) sits in the descriptor's base: every pass uses the same per-lane offset and the
-                // same 16 scalar row offsets
-                const __amdgpu_buffer_rsrc_t rin = make_rsrc(in + (size_t)mb * in_stride + 32 * pn, inbytes);
-                if constexpr (kIq) {
-                    if (hints & 2) {
-#pragma unroll
-                        for (int a = 0; a < 16; a++) L[a] = ld_in(rin, (unsigned)a * kRowGrp, std::integral_constant<int, 2>{});
-                    } else {
-#pragma unroll
-                        for (int a = 0; a < 16; a++) L[a] = ld_in(rin, (unsigned)a * kRowGrp, std::integral_constant<int, 0>{});
-                    }
-                } else if (hints & 2) {
-#pragma unroll
-#ifdef FDC_BLK_SC1LOADS
-                    for (int a = 0; a < 16; a++) L[a] = bld2_sc1(rin, voff, (unsigned)a * kRowGrp);
-#else
-                    for (int a = 0; a < 16; a++) L[a] = bld2_nt(rin, voff, (unsigned)a * kRowGrp);
-#endif
+                    for (int a = 0; a < 16; a++) L[a] = ld_in(rin, (unsigned)a * kRowGrp, std::integral_constant<int, 2>{});
                 } else {
 #pragma unroll
-                    for (int a = 0; a < 16; a++) L[a] = bld2(rin, voff, (unsigned)a * kRowGrp);
+                    for (int a = 0; a < 16; a++) L[a] = ld_in(rin, (unsigned)a * kRowGrp, std::integral_constant<int, 0>{});
                 }
-                cbn = bld2(rcb, voffc, (unsigned)pn * 4096u);
+            } else if (hints & 2) {
+#pragma unroll
+                for (int a = 0; a < 16; a++) L[a] = bld2_nt(rin, voff, (unsigned)a * kRowGrp);
+            } else {
+#pragma unroll
+                for (int a = 0; a < 16; a++) L[a] = bld2(rin, voff, (unsigned)a * kRowGrp);
             }
+            cbn = bld2(rcb, voffc, (unsigned)pn * 4096u);
             if constexpr (kIq) {
 #pragma unroll
                 for (int a = 0; a < 16; a++) cur[a] = iq_widen_bits(TI{}, __float_as_uint(cur[a].x), iq_scale);
@@ -412,7 +305,7 @@ __global__ FDC_PLAIN_DS __launch_bounds__(512, (P == 2 && !OFF && !R4 && !FWD) ?
             cf v[16];
 #pragma unroll
             for (int bb = 0; bb < 16; bb++) v[bb] = ld2(&scrr[4 * bb]);
-            if constexpr (FWD && !FW2) {
+            if constexpr (FWD) {
                 // round-2..5 form: T[k2 = b + 16 q][n1] = A[k2] W_N^(n1 k2) / N.  The half q < 8 stays in the G registers, the half q >= 8 goes to this
                 // workgroup's 256 KiB of scratch ([pass][j][thread]: 512-byte wave stores) and comes back for the second run of stage 2
                 dft16<false>(v);
@@ -427,32 +320,6 @@ __global__ FDC_PLAIN_DS __launch_bounds__(512, (P == 2 && !OFF && !R4 && !FWD) ?
                         bst2(rscr, (unsigned)tid * 8u + (unsigned)(2 * i - 8) * 4096u, (unsigned)ps * 32768u, y0);
                         bst2(rscr, (unsigned)tid * 8u + (unsigned)(2 * i - 7) * 4096u, (unsigned)ps * 32768u, y1);
                     }
-                }
-            } else if constexpr (FW2) {
-                // forward only: T[k2 = b + 16 q][n1] = A[k2] W_N^(n1 k2) / N for this workgroup's rows q = 2 r + h: the second DFT-16 decimated
-                // in frequency — a fold of v[bb] with v[bb + 8] and ONE DFT-8 (h is uniform: a scalar branch)
-                cf e[8];
-                if (fhalf) {
-                    e[0] = v[0] - v[8];
-                    e[1] = mul_w16<false, 1>(v[1] - v[9]);
-                    e[2] = mul_w16<false, 2>(v[2] - v[10]);
-                    e[3] = mul_w16<false, 3>(v[3] - v[11]);
-                    e[4] = mul_w16<false, 4>(v[4] - v[12]);
-                    e[5] = mul_w16<false, 5>(v[5] - v[13]);
-                    e[6] = mul_w16<false, 6>(v[6] - v[14]);
-                    e[7] = mul_w16<false, 7>(v[7] - v[15]);
-                } else {
-#pragma unroll
-                    for (int i = 0; i < 8; i++) e[i] = v[i] + v[i + 8];
-                }
-                dft8<false>(e);                                   // A[b + 16 (2 r + h)], r = k0 + 2 k1, in e[4 k0 + k1]
-                const float2 *sar = SA + (ps * 16 + b) * kSaLd;
-#pragma unroll
-                for (int i = 0; i < 4; i++) {
-                    const float4 t0 = ld4(&btr[2 * i]), t1 = ld4(&sar[2 * i]);
-                    constexpr int kRev8[8] = {0, 4, 1, 5, 2, 6, 3, 7};          // r -> 4 (r & 1) + (r >> 1)
-                    FDC_GPUT(2 * i, ps, cmul(cmul(cmul(e[kRev8[2 * i]], mk(t0.x, t0.y)), mk(t1.x, t1.y)), cb));
-                    FDC_GPUT(2 * i + 1, ps, cmul(cmul(cmul(e[kRev8[2 * i + 1]], mk(t0.z, t0.w)), mk(t1.z, t1.w)), cb));
                 }
             } else {
                 dft16<false>(v);                                  // A[k2 = b + 16 q] in v[rev16(q)]
@@ -490,14 +357,10 @@ __global__ FDC_PLAIN_DS __launch_bounds__(512, (P == 2 && !OFF && !R4 && !FWD) ?
                     for (int j = 0; j < 4; j++) bst2(rscr, (unsigned)tid * 8u + (unsigned)j * 4096u, (unsigned)ps * 16384u, u[rev16(4 + j)]);
                 }
             }
-            FDC_STAMP(1 + ps);
         };
         // two passes per trip: the row sets swap roles (the pass count is even for every P).  The offset-plan variant at P = 8 has no
         // registers for the second set's live range (32 bytes of scratch): it copies the rows at the top of a pass as before.
-#ifndef FDC_BLK_COPYFORM
-#define FDC_BLK_COPYFORM 0
-#endif
-        if constexpr ((OFF || (FDC_BLK_COPYFORM && !STG)) && P == 8) {
+        if constexpr (OFF && P == 8) {
 #pragma nounroll
             for (int ps = 0; ps < P; ps++) {
                 cf cur[16];
@@ -525,7 +388,6 @@ __global__ FDC_PLAIN_DS __launch_bounds__(512, (P == 2 && !OFF && !R4 && !FWD) ?
             constexpr int kNJ = decltype(njc)::value;
             constexpr int kNTrip = (kNJ + kJT - 1) / kJT;
             __syncthreads();                                          // every wave is done with its stage-1 scratch
-            FDC_STAMP(9);
             // the stage-2 roles are worked out here, from a thread index the compiler cannot trace back: loop-invariant address
             // registers would otherwise stay live across stage 1, which has none to spare
             int t2 = tid;
@@ -570,10 +432,8 @@ __global__ FDC_PLAIN_DS __launch_bounds__(512, (P == 2 && !OFF && !R4 && !FWD) ?
 #pragma unroll
                     for (int k = 1; k < P; k++) st2(&gw[32 * k], cmul(a[blk_pass_idx<P>(k)], ct[k]));
                 }
-                FDC_STAMP(10 + 5 * tr);
                 __builtin_amdgcn_sched_barrier(0);                    // keep the next phase's arithmetic (and its registers) behind
                 __syncthreads();                                      // the trip is in LDS
-                FDC_STAMP(11 + 5 * tr);
                 const bool reads = P == 8 || 4 * rh2 < ja;            // P < 8: waves whose row half the trip does not have sit the phase out
                 cf v[32];
                 if (reads) {
@@ -585,20 +445,15 @@ __global__ FDC_PLAIN_DS __launch_bounds__(512, (P == 2 && !OFF && !R4 && !FWD) ?
                 }
                 __syncthreads();                                      // every read of the trip is done: the region may be rewritten
                 __builtin_amdgcn_sched_barrier(0);
-                FDC_STAMP(12 + 5 * tr);
                 if (reads) {
                     dft32<false>(v);                                  // khi = k0 + 2 k1 in v[16 k0 + rev16(k1)]
-                    FDC_STAMP(13 + 5 * tr);
                     // Stores: slot klo + P khi of row t' = 16 kJT tr + 64 rh + lane.  The 32 stream offsets are the same for the whole
                     // wave (table laid out [klo][register]).  Unused slots: the byte offset is pushed beyond the buffer's extent and the
                     // store is dropped by the range check of the descriptor (no branch per store).
-                    // FWD: [block][N bins]; row t' = b + 16 j of the run is bin k2 = b + 16 (2 j + h): four 16-bin runs per wave store, 32 bins apart
+                    // FWD: [block][N bins]
                     const int trow0 = 16 * kJT * tr + 64 * rh2, trow = trow0 + lane2;
-                    const unsigned rb = FW2 ? (unsigned)(m * GM::kN + (trow & 15) + 32 * (trow >> 4) + 16 * fhalf) * 8u
-                                            : (unsigned)(m * (FWD ? GM::kN : (R4 ? 192 : 128)) + rowbase + trow) * kOs;
-                    // two workgroups per block: the two 64-bin groups of k2 a wave's store touches (lanes 0-31 / 32-63): kept if some channel reads either
-                    unsigned mq = FW2 ? (mqs[(trow0 >> 5) & 3] | mqs[((trow0 >> 5) + 1) & 3])
-                                      : FWD ? mqs[((rowbase + trow0) >> 6) & 3] : ~0u;
+                    const unsigned rb = (unsigned)(m * (FWD ? GM::kN : (R4 ? 192 : 128)) + rowbase + trow) * kOs;
+                    unsigned mq = FWD ? mqs[((rowbase + trow0) >> 6) & 3] : ~0u;
                     if constexpr (FWD) asm volatile("" : "+s"(mq));   // the 32 scalar terms below are worked out here, not held from block to block
 #pragma unroll
                     for (int q = 0; q < 8; q++) {
@@ -617,7 +472,7 @@ __global__ FDC_PLAIN_DS __launch_bounds__(512, (P == 2 && !OFF && !R4 && !FWD) ?
                                 bst2t<NT>(rout, (o == 0xFFFFFFFFu ? 0xFFFFFFF0u : o + rb), v[4 * q + e]);
                         }
                     }
-                    if constexpr (FWD && !FW2) {
+                    if constexpr (FWD) {
                         // Power of every 16-bin group of the spectrum while it is in the registers (round 6: what the sinks' power cells are summed from —
                         // k_cell_power used to read the whole spectrum back, 444-472 MB per 1024 blocks).  This lane holds bins 256 slot + k2 of 32
                         // slots, its row of 16 lanes is one 16-bin group of each: 32 sums over 16 lanes as ONE transposed reduction — every step
@@ -673,12 +528,11 @@ __global__ FDC_PLAIN_DS __launch_bounds__(512, (P == 2 && !OFF && !R4 && !FWD) ?
                         }
                     }
                 }
-                FDC_STAMP(14 + 5 * tr);
                 __builtin_amdgcn_sched_barrier(0);
             }
         };
         stage2([&](int j, int ps) { return FDC_GGET(j, ps); }, R4 ? 64 : 0, std::integral_constant<int, 8>{});
-        if constexpr (FWD && !FW2) {
+        if constexpr (FWD) {
             // second half of k2: the values stage 1 put aside are this lane's own stores; sc1 loads are served by the L2
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             stage2([&](int j, int ps) { return bld2_sc1(rscr, (unsigned)tid * 8u + (unsigned)(j * 4096 + ps * 32768), 0u); }, 128,
@@ -690,28 +544,9 @@ __global__ FDC_PLAIN_DS __launch_bounds__(512, (P == 2 && !OFF && !R4 && !FWD) ?
             stage2([&](int j, int ps) { return bld2_sc1(rscr, (unsigned)tid * 8u + (unsigned)(j * 4096 + ps * 16384), 0u); }, 0,
                    std::integral_constant<int, 4>{});
         }
-        FDC_STAMP(30);
-#ifdef FDC_BLK_STAMPS
-        if (dbg && blockIdx.x == 0 && lane == 0 && dbgk < 4)
-            for (int i = 0; i < 32; i++) dbg[(w * 4 + dbgk) * 32 + i] = st[i];
-#endif
-        dbgk++;
         // the trip region (= stage-1 scratch) was last read before the barrier above: the next block starts without one
     }
-#ifdef FDC_BLK_WGTIMES
-    if (dbg && tid == 0) dbg[256 + blockIdx.x] = wall_clock64();
-#endif
 }
-
-// -DFDC_BLK_STAGED=1: the plain channelizer at N = 65536 with its loads staged through LDS (the STG variant above): measured 1.5 % SLOWER than the
-// shipped form (profiles/r04/NOTES.md section 11), kept as a build variant
-#ifndef FDC_BLK_STAGED
-#define FDC_BLK_STAGED 0
-#endif
-// -DFDC_FWD_STAGED=1: the forward-transform variant at N = 65536 with its loads staged through LDS (experiment, round 6)
-#ifndef FDC_FWD_STAGED
-#define FDC_FWD_STAGED 0
-#endif
 
 // the channelizer forms of one input type (TI != float2: the integer-input instantiations, fdc_pipeline_work_iq)
 template <class TI>
@@ -719,11 +554,11 @@ static hipError_t init_block_kernels_in()
 {
     hipError_t e;
 #define FDC_SETB(P, A, B, R4) \
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_blk256<P, A, B, false, R4, false, false, TI>), hipFuncAttributeMaxDynamicSharedMemorySize, \
+    e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_blk256<P, A, B, false, R4, false, TI>), hipFuncAttributeMaxDynamicSharedMemorySize, \
                             B ? BlkGeom<P>::kLdsOff : BlkGeom<P>::kLds); \
     if (e != hipSuccess) return e;
 #define FDC_SETH(P, A, R4) \
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_blk256<P, A, false, false, R4, false, true, TI>), hipFuncAttributeMaxDynamicSharedMemorySize, BlkGeom<P>::kLds); \
+    e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_blk256<P, A, false, false, R4, true, TI>), hipFuncAttributeMaxDynamicSharedMemorySize, BlkGeom<P>::kLds); \
     if (e != hipSuccess) return e;
 #define FDC_SETP(P) \
     FDC_SETB(P, true, false, false) FDC_SETB(P, false, false, false) FDC_SETB(P, true, true, false) FDC_SETB(P, false, true, false) \
@@ -749,11 +584,11 @@ static hipError_t init_block_kernels_oq()
 {
     hipError_t e;
 #define FDC_SETB(P, B, R4) \
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_blk256<P, true, B, false, R4, false, false, TI, TO>), hipFuncAttributeMaxDynamicSharedMemorySize, \
+    e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_blk256<P, true, B, false, R4, false, TI, TO>), hipFuncAttributeMaxDynamicSharedMemorySize, \
                             B ? BlkGeom<P>::kLdsOff : BlkGeom<P>::kLds); \
     if (e != hipSuccess) return e;
 #define FDC_SETH(P, R4) \
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_blk256<P, true, false, false, R4, false, true, TI, TO>), hipFuncAttributeMaxDynamicSharedMemorySize, BlkGeom<P>::kLds); \
+    e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_blk256<P, true, false, false, R4, true, TI, TO>), hipFuncAttributeMaxDynamicSharedMemorySize, BlkGeom<P>::kLds); \
     if (e != hipSuccess) return e;
 #define FDC_SETP(P) \
     FDC_SETB(P, false, false) FDC_SETB(P, true, false) FDC_SETB(P, false, true) FDC_SETB(P, true, true) FDC_SETH(P, false) FDC_SETH(P, true)
@@ -791,24 +626,12 @@ hipError_t init_block_kernels()
 #undef FDC_SETP
 #undef FDC_SETB
 #define FDC_SETH(P, A, R4) \
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_blk256<P, A, false, false, R4, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, BlkGeom<P>::kLds); \
+    e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_blk256<P, A, false, false, R4, true>), hipFuncAttributeMaxDynamicSharedMemorySize, BlkGeom<P>::kLds); \
     if (e != hipSuccess) return e;
 #define FDC_SETHP(P) FDC_SETH(P, true, false) FDC_SETH(P, false, false) FDC_SETH(P, true, true) FDC_SETH(P, false, true)
     FDC_SETHP(2) FDC_SETHP(4) FDC_SETHP(8)
 #undef FDC_SETHP
 #undef FDC_SETH
-#if FDC_FWD_STAGED
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_blk256<8, true, false, true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, BlkGeom<8>::kLdsS);
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_blk256<8, false, false, true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, BlkGeom<8>::kLdsS);
-    if (e != hipSuccess) return e;
-#endif
-#if FDC_BLK_STAGED
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_blk256<8, true, false, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, BlkGeom<8>::kLdsS);
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_blk256<8, false, false, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, BlkGeom<8>::kLdsS);
-    if (e != hipSuccess) return e;
-#endif
     return hipSuccess;
 }
 
@@ -818,7 +641,7 @@ template <class TI, class TO = float2>
 static hipError_t poly_block_in(const TI *in, size_t in_stride, TO *out, int nb_chunk, int mbase, int nb_call,
                                 const float2 *tw256, const float2 *twq, const float2 *cbt, const float *shn,
                                 const long long *slot_off, unsigned out_bytes, int ncu, int hints, hipStream_t s,
-                                unsigned long long *dbg, int r, long long first_block, hipEvent_t ev_start, hipEvent_t ev_stop, int R,
+                                int r, long long first_block, hipEvent_t ev_start, hipEvent_t ev_stop, int R,
                                 float2 *scratch, int N, float iq_scale, float oq_scale = 1.0f)
 {
     if (nb_chunk <= 0) return hipSuccess;
@@ -844,14 +667,14 @@ static hipError_t poly_block_in(const TI *in, size_t in_stride, TO *out, int nb_
     // in front of or behind the kernel, unlike hipEventRecord (measured 7-17 us per bracketed launch)
     // R = 4: three quarters of every inverse transform kept: 192 rows per block, 64 of them via the scratch
 #define FDC_LB(P, A, B, R4) \
-    hipExtLaunchKernelGGL((k_blk256<P, A || kOq, B, false, R4, false, false, TI, TO>), dim3((unsigned)grid), dim3(512), B ? BlkGeom<P>::kLdsOff : BlkGeom<P>::kLds, s, \
+    hipExtLaunchKernelGGL((k_blk256<P, A || kOq, B, false, R4, false, TI, TO>), dim3((unsigned)grid), dim3(512), B ? BlkGeom<P>::kLdsOff : BlkGeom<P>::kLds, s, \
                           ev_start, ev_stop, 0u, in, in_stride, out, tw256, twq, cbt, shn, slot_off, (long long)mbase * (R4 ? 192 : 128), (long long)nb_call, \
-                          out_bytes, nb_chunk, hints, dbg, r & 255, first_block, R4 ? scratch : (float2 *)nullptr, (const unsigned *)nullptr, \
+                          out_bytes, nb_chunk, hints, (unsigned long long *)nullptr, r & 255, first_block, R4 ? scratch : (float2 *)nullptr, (const unsigned *)nullptr, \
                           iq_tail(iq_scale, oq_scale))
 #define FDC_LH(P, A, R4) \
-    hipExtLaunchKernelGGL((k_blk256<P, A || kOq, false, false, R4, false, true, TI, TO>), dim3((unsigned)grid), dim3(512), BlkGeom<P>::kLds, s, ev_start, \
+    hipExtLaunchKernelGGL((k_blk256<P, A || kOq, false, false, R4, true, TI, TO>), dim3((unsigned)grid), dim3(512), BlkGeom<P>::kLds, s, ev_start, \
                           ev_stop, 0u, in, in_stride, out, tw256, twq, cbt, shn, slot_off, (long long)mbase * (R4 ? 192 : 128), (long long)nb_call, \
-                          out_bytes, nb_chunk, hints, dbg, 0, first_block, R4 ? scratch : (float2 *)nullptr, (const unsigned *)nullptr, \
+                          out_bytes, nb_chunk, hints, (unsigned long long *)nullptr, 0, first_block, R4 ? scratch : (float2 *)nullptr, (const unsigned *)nullptr, \
                           iq_tail(iq_scale, oq_scale))
 // (FDC_R4(P): the R = 4 forms exist — not at P = 8 on float input with integer output, kOqR4Narrowed)
 #define FDC_R4(P) if constexpr (P != 8 || !kOqR4Narrowed<TI, TO>::value)
@@ -865,18 +688,6 @@ static hipError_t poly_block_in(const TI *in, size_t in_stride, TO *out, int nb_
         else if (r & 255) { if (hints & 1) FDC_LB(P, true, true, false); else FDC_LB(P, false, true, false); } \
         else { if (hints & 1) FDC_LB(P, true, false, false); else FDC_LB(P, false, false, false); } \
     } while (0)
-#if FDC_BLK_STAGED
-    if constexpr (!kIq && !kOq) if (N == 65536 && R == 2 && !(r & 255)) {
-        // the plain channelizer with its loads staged through LDS
-#define FDC_LS(A) \
-        hipExtLaunchKernelGGL((k_blk256<8, A, false, false, false, true>), dim3((unsigned)grid), dim3(512), BlkGeom<8>::kLdsS, s, ev_start, ev_stop, 0u, in, \
-                              in_stride, out, tw256, twq, cbt, shn, slot_off, (long long)mbase * 128, (long long)nb_call, out_bytes, nb_chunk, hints, dbg, 0, \
-                              first_block, (float2 *)nullptr, (const unsigned *)nullptr, (float *)nullptr)
-        if (hints & 1) FDC_LS(true); else FDC_LS(false);
-        return hipGetLastError();
-#undef FDC_LS
-    }
-#endif
     if (N == 65536) FDC_LP(8); else if (N == 32768) FDC_LP(4); else FDC_LP(2);
 #undef FDC_LP
 #undef FDC_R4
@@ -888,10 +699,10 @@ static hipError_t poly_block_in(const TI *in, size_t in_stride, TO *out, int nb_
 hipError_t launch_poly_block(const float2 *in, size_t in_stride, float2 *out, int nb_chunk, int mbase, int nb_call,
                              const float2 *tw256, const float2 *twq, const float2 *cbt, const float *shn,
                              const long long *slot_off, unsigned out_bytes, int ncu, int hints, hipStream_t s,
-                             unsigned long long *dbg, int r, long long first_block, hipEvent_t ev_start, hipEvent_t ev_stop, int R,
+                             int r, long long first_block, hipEvent_t ev_start, hipEvent_t ev_stop, int R,
                              float2 *scratch, int N)
 {
-    return poly_block_in(in, in_stride, out, nb_chunk, mbase, nb_call, tw256, twq, cbt, shn, slot_off, out_bytes, ncu, hints, s, dbg, r, first_block,
+    return poly_block_in(in, in_stride, out, nb_chunk, mbase, nb_call, tw256, twq, cbt, shn, slot_off, out_bytes, ncu, hints, s, r, first_block,
                          ev_start, ev_stop, R, scratch, N, 1.0f);
 }
 
@@ -902,10 +713,10 @@ hipError_t launch_poly_block_iq(int fmt, float scale, const void *in, size_t in_
 {
     if (fmt == kIqSc16)
         return poly_block_in(static_cast<const sc16 *>(in), in_stride, out, nb_chunk, mbase, nb_call, tw256, twq, cbt, shn, slot_off, out_bytes, ncu, hints, s,
-                             nullptr, r, first_block, ev_start, ev_stop, R, scratch, N, scale);
+                             r, first_block, ev_start, ev_stop, R, scratch, N, scale);
     if (fmt == kIqSc8)
         return poly_block_in(static_cast<const sc8 *>(in), in_stride, out, nb_chunk, mbase, nb_call, tw256, twq, cbt, shn, slot_off, out_bytes, ncu, hints, s,
-                             nullptr, r, first_block, ev_start, ev_stop, R, scratch, N, scale);
+                             r, first_block, ev_start, ev_stop, R, scratch, N, scale);
     return hipErrorInvalidValue;
 }
 
@@ -917,7 +728,7 @@ static hipError_t poly_block_oq_in(int ifmt, float iscale, const void *in, size_
 {
 #define FDC_OQ(TI, sc) \
     return poly_block_in<TI, TO>(static_cast<const TI *>(in), in_stride, out, nb_chunk, mbase, nb_call, tw256, twq, cbt, shn, slot_off, out_bytes, ncu, \
-                                 hints, s, nullptr, r, first_block, ev_start, ev_stop, R, scratch, N, sc, oscale)
+                                 hints, s, r, first_block, ev_start, ev_stop, R, scratch, N, sc, oscale)
     if (ifmt == kIqFloat) FDC_OQ(float2, 1.0f);
     if (ifmt == kIqSc16) FDC_OQ(sc16, iscale);
     if (ifmt == kIqSc8) FDC_OQ(sc8, iscale);
@@ -953,12 +764,7 @@ hipError_t launch_block_fft(int N, const float2 *in, size_t in_stride, float2 *o
     for (int m0 = 0; m0 < nitems; m0 += per) {
         const int nb = nitems - m0 < per ? nitems - m0 : per;
         int grid = ncu > 0 ? ncu : 256;
-#if FDC_FWD_TWO_WG
-        grid &= ~1;                                        // two workgroups per block (the halves of k2): an even grid, at most two per block
-        if (grid > 2 * nb) grid = 2 * nb;
-#else
         if (grid > nb) grid = nb;
-#endif
         hipEvent_t e0 = ev && m0 == 0 ? ev[0] : nullptr, e2 = ev && m0 + nb >= nitems ? ev[1] : nullptr;
 #define FDC_LF(P, A) \
         hipExtLaunchKernelGGL((k_blk256<P, A, false, true>), dim3((unsigned)grid), dim3(512), BlkGeom<P>::kLds, s, e0, e2, 0u, in + (size_t)m0 * in_stride, \
@@ -966,24 +772,11 @@ hipError_t launch_block_fft(int N, const float2 *in, size_t in_stride, float2 *o
                               (unsigned)((size_t)nb * (size_t)N * 8), nb, hints, (unsigned long long *)nullptr, 0, 0ll, scratch, keep, \
                               gpow ? gpow + (size_t)m0 * (size_t)(N / 16) : (float *)nullptr)
         const bool nt = (hints & 1) != 0;
-#if FDC_FWD_STAGED
-#define FDC_LFS(A) \
-        hipExtLaunchKernelGGL((k_blk256<8, A, false, true, false, true>), dim3((unsigned)grid), dim3(512), BlkGeom<8>::kLdsS, s, e0, e2, 0u, in + (size_t)m0 * in_stride, \
-                              in_stride, out + (size_t)m0 * (size_t)N, tw256, twq, cbt0, shn1, slot_off, 0ll, 1ll, \
-                              (unsigned)((size_t)nb * (size_t)N * 8), nb, hints, (unsigned long long *)nullptr, 0, 0ll, scratch, keep, \
-                              gpow ? gpow + (size_t)m0 * (size_t)(N / 16) : (float *)nullptr)
-        if (N == 65536) { if (nt) FDC_LFS(true); else FDC_LFS(false); } else
-#undef FDC_LFS
-#endif
         if (N == 65536) { if (nt) FDC_LF(8, true); else FDC_LF(8, false); }
         else if (N == 32768) { if (nt) FDC_LF(4, true); else FDC_LF(4, false); }
         else { if (nt) FDC_LF(2, true); else FDC_LF(2, false); }
 #undef FDC_LF
     }
-#if FDC_FWD_TWO_WG
-    // (variant build: the epilogue reduction exists in the shipped form only)
-    if (gpow) { hipError_t e = launch_group_power(out, N, nitems, gpow, s); if (e != hipSuccess) return e; }
-#endif
     if (ev) { hipError_t e = hipEventRecord(ev[2], s); if (e != hipSuccess) return e; }
     return hipGetLastError();
 }

@@ -56,7 +56,7 @@ constexpr int k5OffX = 8 * k5ScrPts * 8;                         // 69376: end o
 // four b rows on five different 4-dword windows (round 5: two tables [2 par][16][18] put (0, b) and (1, b) on the same banks — 2-way on every read)
 constexpr int k5T512Tab = 46;
 constexpr int k5ShPar = 16 * 16 + 4;                             // floats between the two halves of Sh: the rows (0, b) and (1, b) of a 16-byte read 4 dwords apart
-// STAGED loads: the next pass's 16 columns x 512 rows as [column][row] planes.  Round 5 (the counters said a third of this kernel's LDS
+// Staged loads: the next pass's 16 columns x 512 rows as [column][row] planes.  Round 5 (the counters said a third of this kernel's LDS
 // cycles were bank conflicts, profiles/r05/NOTES.md section 5): planes 528 points apart and the rows of column pair cp turned by 2 cp —
 //   store (16 contiguous lanes = 8 column pairs x 2 rows, 8 bytes each): dword 2 (col 528 + row + 2 cp) = 32 col + 2 row + 4 cp mod 64: the eight pairs
 //         on eight different 4-dword windows, the two columns of a pair (separate instructions) on the two bank halves: conflict-free;
@@ -78,11 +78,10 @@ struct B5Geom {
     static constexpr int kOffB = kOffT512 + (k5T512Tab + 16 * 18) * 8;   // [P pass][16 c4][16]  W_N^(16 n1 q), n1 = 16 pass + c4 (rows unpadded: a wave reads two of them, broadcast)
     static constexpr int kOffSh = kOffB + P * 16 * 16 * 8;        // [2 h][16 b][16] floats: shape[b + 16 q + 256 h] / N
     static constexpr int kOffSoff = kOffSh + (k5ShPar + 16 * 16) * 4;    // [P klo][16] output offsets (bytes)
-    static constexpr int kLds = kOffSoff + kN1 * 4;               // P = 8: 94336
-    static constexpr int kOffStage = kLds;
-    static constexpr int kLdsStaged = kOffStage + 16 * k5StagePlane * 8;   // P = 8: 161920
+    static constexpr int kOffStage = kOffSoff + kN1 * 4;          // P = 8: 94336
+    static constexpr int kLds = kOffStage + 16 * k5StagePlane * 8;   // P = 8: 161920
     static_assert(kOffB % 16 == 0 && kOffSh % 16 == 0 && kOffSoff % 16 == 0 && kOffCt % 16 == 0, "16-byte table reads");
-    static_assert(kLdsStaged <= 160 * 1024, "LDS budget");
+    static_assert(kLds <= 160 * 1024, "LDS budget");
     static_assert((kLd * 2) % 64 == 12, "trip rows 12 dwords apart mod 64: the lane groups of ds_read_b128 on all banks");
 };
 // DFT over the pass index (the register index of G): P points in place; X[k] is read through b5_pass_idx<P>(k)
@@ -98,11 +97,11 @@ __device__ __forceinline__ void b5_pass_dft(cf (&a)[P])
 // R4 = true: relinvovl = 4 (the reference's default overlap): 384 of the 512 samples of every inverse transform are kept.  The rows m >= 128 of
 // both parities stay in the G registers as for R = 2 (output rows 128 ..); the rows 64 <= m < 128 go to 128 KiB of per-workgroup scratch
 // ([pass][q - 4][thread]: the L2 holds it) and come back for a third, 128-row run of stage 2 (output rows 0 .. 127), as in fdc_block256.hip.
-// STAGED = true: the rows reach the lanes through LDS, as in fdc_block1024.hip.  A wave's own load instruction is 32 rows x 16 bytes (32 cache lines);
+// The rows reach the lanes through LDS, as in fdc_block1024.hip.  A wave's own load instruction would be 32 rows x 16 bytes (32 cache lines);
 // staged, wave w fetches rows 64 w .. of the pass's 16 columns in 16-byte pieces of whole 128-byte row segments (8 rows per instruction: 8 lines, half the
 // instructions), parks them in registers for a pass, writes them to [column][row] planes in LDS at the pass boundary and reads its own columns' rows back:
 // two workgroup barriers per pass for an eighth of the line requests.
-template <bool NT, bool R4, bool STAGED, int P = 8>
+template <bool NT, bool R4, int P = 8>
 __global__ FDC_PLAIN_DS512 __launch_bounds__(512) void k_blk512(const float2 *__restrict__ in, size_t in_stride, float2 *__restrict__ out,
                                                       const float2 *__restrict__ tw256, const float2 *__restrict__ tw512 /* W_512^k, k < 256 */,
                                                       const float2 *__restrict__ twq /* [n1][16] W_N^(16 n1 q) */,
@@ -134,42 +133,32 @@ __global__ FDC_PLAIN_DS512 __launch_bounds__(512) void k_blk512(const float2 *__
     if (first >= nb) return;
 
     constexpr unsigned inbytes = (unsigned)GM::kN * 8u;
-    constexpr unsigned kRow32 = 32u * (unsigned)kN1 * 8u;          // 32 rows further on, bytes (P = 8: 32 KiB)
-    constexpr unsigned kRow8 = 8u * (unsigned)kN1 * 8u;            // 8 rows (staged loads: one instruction further on)
-    // row n2 = 2 (16 a + b) + par of column 16 pass + c4: kN1 columns per row; a adds 32 rows, a pass 16 columns = 128 B
-    const unsigned voff = (unsigned)((2 * b + par) * kN1 + c4) * 8u;
+    constexpr unsigned kRow8 = 8u * (unsigned)kN1 * 8u;            // 8 rows: one load instruction further on
     const __amdgpu_buffer_rsrc_t rcb = make_rsrc(cbt, (unsigned)kN1 * 32u * 8u);
     const unsigned voffc = (unsigned)(c4 * 32 + b + 16 * par) * 8u;
     cf LA[16], LB[16], cbA, cbB;
-    // staged: wave w fetches rows 64 w + 8 i + (lane >> 3), columns 2 (lane & 7), + 1 of the pass (16 bytes); instruction i adds 8 rows = 8 KiB
-    [[maybe_unused]] float2 *stg = reinterpret_cast<float2 *>(fdc_smem_b512 + GM::kOffStage);
-    [[maybe_unused]] const unsigned voffs = (unsigned)((64 * w + (lane >> 3)) * kN1 + 2 * (lane & 7)) * 8u;
-    [[maybe_unused]] float2 *const stw = stg + 2 * (lane & 7) * k5StagePlane + 64 * w + (lane >> 3) + 2 * (lane & 7);   // + 8 i rows; second column: + one plane
-    [[maybe_unused]] const float2 *const strd = stg + c4 * k5StagePlane + 2 * b + par + 2 * w;            // this lane's rows 32 a + 2 b + par of column c4 (pair w: turned by 2 w)
-    [[maybe_unused]] u32x4 PF[8];
-    [[maybe_unused]] auto stage_load = [&](int mb, int pn) __attribute__((always_inline)) {
+    // wave w fetches rows 64 w + 8 i + (lane >> 3), columns 2 (lane & 7), + 1 of the pass (16 bytes); instruction i adds 8 rows = 8 KiB
+    float2 *stg = reinterpret_cast<float2 *>(fdc_smem_b512 + GM::kOffStage);
+    const unsigned voffs = (unsigned)((64 * w + (lane >> 3)) * kN1 + 2 * (lane & 7)) * 8u;
+    float2 *const stw = stg + 2 * (lane & 7) * k5StagePlane + 64 * w + (lane >> 3) + 2 * (lane & 7);   // + 8 i rows; second column: + one plane
+    const float2 *const strd = stg + c4 * k5StagePlane + 2 * b + par + 2 * w;            // this lane's rows 32 a + 2 b + par of column c4 (pair w: turned by 2 w)
+    u32x4 PF[8];
+    auto stage_load = [&](int mb, int pn) __attribute__((always_inline)) {
         const __amdgpu_buffer_rsrc_t rin = make_rsrc(in + (size_t)mb * in_stride + 16 * pn, inbytes);
 #pragma unroll
         for (int i = 0; i < 8; i++) PF[i] = bld4(rin, voffs, (unsigned)i * kRow8);
     };
-    [[maybe_unused]] auto stage_write = [&]() __attribute__((always_inline)) {
+    auto stage_write = [&]() __attribute__((always_inline)) {
 #pragma unroll
         for (int i = 0; i < 8; i++) {
             st2(&stw[8 * i], mk(__uint_as_float(PF[i].x), __uint_as_float(PF[i].y)));
             st2(&stw[k5StagePlane + 8 * i], mk(__uint_as_float(PF[i].z), __uint_as_float(PF[i].w)));
         }
     };
-    if constexpr (STAGED) {
-        stage_load(first, 0);
-        cbA = bld2(rcb, voffc, 0);
-        stage_write();                                           // pass 0 of the first block: visible after the barrier behind the tables
-        stage_load(first, 1);
-    } else {
-        const __amdgpu_buffer_rsrc_t rin = make_rsrc(in + (size_t)first * in_stride, inbytes);
-#pragma unroll
-        for (int a = 0; a < 16; a++) LA[a] = bld2(rin, voff, (unsigned)a * kRow32);
-        cbA = bld2(rcb, voffc, 0);
-    }
+    stage_load(first, 0);
+    cbA = bld2(rcb, voffc, 0);
+    stage_write();                                               // pass 0 of the first block: visible after the barrier behind the tables
+    stage_load(first, 1);
     // ---- tables
     for (int i = tid; i < 256; i += 512) {
         wrow[(i >> 4) * 18 + (i & 15)] = tw256[((i >> 4) * (i & 15)) & 255];
@@ -201,30 +190,16 @@ __global__ FDC_PLAIN_DS512 __launch_bounds__(512) void k_blk512(const float2 *__
         const int mnext = m + grid < nb ? m + grid : m;
         typedef unsigned long long gvec __attribute__((ext_vector_type(P)));
         gvec G[8];
-        auto one_pass = [&](const int ps, cf (&cur)[16], const cf cb, cf (&L)[16], cf &cbn) __attribute__((always_inline)) {
-            if constexpr (STAGED) {
-                // the pass's rows are in the planes (written a pass ago, or by the prologue): take this lane's sixteen, then hand the planes over to
-                // the rows that arrived in the meantime (pass + 1) and request pass + 2
-                __syncthreads();
+        auto one_pass = [&](const int ps, cf (&cur)[16], const cf cb, cf &cbn) __attribute__((always_inline)) {
+            // the pass's rows are in the planes (written a pass ago, or by the prologue): take this lane's sixteen, then hand the planes over to
+            // the rows that arrived in the meantime (pass + 1) and request pass + 2
+            __syncthreads();
 #pragma unroll
-                for (int a = 0; a < 16; a++) cur[a] = ld2(&strd[32 * a]);
-                __syncthreads();
-                stage_write();
-                stage_load(ps < P - 2 ? m : mnext, (ps + 2) & (P - 1));
-                cbn = bld2(rcb, voffc, (unsigned)((ps + 1) & (P - 1)) * 4096u);
-            } else {
-                const int pn = ps < P - 1 ? ps + 1 : 0;
-                const int mb = ps < P - 1 ? m : mnext;
-                const __amdgpu_buffer_rsrc_t rin = make_rsrc(in + (size_t)mb * in_stride + 16 * pn, inbytes);
-                if (hints & 2) {
-#pragma unroll
-                    for (int a = 0; a < 16; a++) L[a] = bld2_nt(rin, voff, (unsigned)a * kRow32);
-                } else {
-#pragma unroll
-                    for (int a = 0; a < 16; a++) L[a] = bld2(rin, voff, (unsigned)a * kRow32);
-                }
-                cbn = bld2(rcb, voffc, (unsigned)pn * 4096u);
-            }
+            for (int a = 0; a < 16; a++) cur[a] = ld2(&strd[32 * a]);
+            __syncthreads();
+            stage_write();
+            stage_load(ps < P - 2 ? m : mnext, (ps + 2) & (P - 1));
+            cbn = bld2(rcb, voffc, (unsigned)((ps + 1) & (P - 1)) * 4096u);
             // ---- the 256-point forward transform of this lane's parity: exactly the old stage 1
             dft16<false>(cur);
             {
@@ -297,8 +272,8 @@ __global__ FDC_PLAIN_DS512 __launch_bounds__(512) void k_blk512(const float2 *__
         };
 #pragma nounroll
         for (int pp = 0; pp < P; pp += 2) {
-            one_pass(pp, LA, cbA, LB, cbB);
-            one_pass(pp + 1, LB, cbB, LA, cbA);
+            one_pass(pp, LA, cbA, cbB);
+            one_pass(pp + 1, LB, cbB, cbA);
         }
         // ---------------- stage 2: FFT-N1 over n1 = 16 pass + c4 of every row t' = rowbase + 2 (b + 16 j) + par ----------------
         // get(j, pass): the value of row group j; rowbase: first output row of the run; njc: its number of 32-row groups (a trip holds kJT of them:
@@ -379,10 +354,6 @@ __global__ FDC_PLAIN_DS512 __launch_bounds__(512) void k_blk512(const float2 *__
     }
 }
 
-#ifndef FDC_512_STAGED
-#define FDC_512_STAGED 1
-#endif
-
 bool poly_block512_supports(int N, int R)
 {
     return (N == 65536 || N == 32768 || N == 16384) && (R == 2 || R == 4);
@@ -391,12 +362,11 @@ bool poly_block512_supports(int N, int R)
 hipError_t init_block512_kernels()
 {
     hipError_t e = hipSuccess;
-#define FDC_SET5(A, B, C, P) \
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_blk512<A, B, C, P>), hipFuncAttributeMaxDynamicSharedMemorySize, C ? B5Geom<P>::kLdsStaged : B5Geom<P>::kLds);
-    FDC_SET5(true, false, false, 8) FDC_SET5(false, false, false, 8) FDC_SET5(true, true, false, 8) FDC_SET5(false, true, false, 8)
-    FDC_SET5(true, false, true, 8) FDC_SET5(false, false, true, 8) FDC_SET5(true, true, true, 8) FDC_SET5(false, true, true, 8)
-    FDC_SET5(true, false, true, 4) FDC_SET5(false, false, true, 4) FDC_SET5(true, true, true, 4) FDC_SET5(false, true, true, 4)
-    FDC_SET5(true, false, true, 2) FDC_SET5(false, false, true, 2) FDC_SET5(true, true, true, 2) FDC_SET5(false, true, true, 2)
+#define FDC_SET5(A, B, P) \
+    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_blk512<A, B, P>), hipFuncAttributeMaxDynamicSharedMemorySize, B5Geom<P>::kLds);
+#define FDC_SET5P(P) FDC_SET5(true, false, P) FDC_SET5(false, false, P) FDC_SET5(true, true, P) FDC_SET5(false, true, P)
+    FDC_SET5P(8) FDC_SET5P(4) FDC_SET5P(2)
+#undef FDC_SET5P
 #undef FDC_SET5
     return e;
 }
@@ -410,22 +380,18 @@ hipError_t launch_poly_block512(const float2 *in, size_t in_stride, float2 *out,
     if (!poly_block512_supports(N, R) || (R == 4 && !scratch)) return hipErrorInvalidValue;
     int grid = ncu > 0 ? ncu : 256;
     if (grid > nb_chunk) grid = nb_chunk;
-    constexpr bool kStaged = FDC_512_STAGED != 0;
-#define FDC_L512(A, B, S, P) \
-    hipExtLaunchKernelGGL((k_blk512<A, B, S, P>), dim3((unsigned)grid), dim3(512), S ? B5Geom<P>::kLdsStaged : B5Geom<P>::kLds, s, ev_start, ev_stop, 0u, in, in_stride, out, \
+#define FDC_L512(A, B, P) \
+    hipExtLaunchKernelGGL((k_blk512<A, B, P>), dim3((unsigned)grid), dim3(512), B5Geom<P>::kLds, s, ev_start, ev_stop, 0u, in, in_stride, out, \
                           tw256, tw512, twq, cbt, shn, slot_off, (long long)mbase * (B ? 384 : 256), (long long)nb_call, out_bytes, nb_chunk, hints, \
                           B ? scratch : (float2 *)nullptr, half ? 1 : 0)
     const bool nt = (hints & 1) != 0;
-    if (N == 65536) {
-        if (R == 4) { if (nt) FDC_L512(true, true, kStaged, 8); else FDC_L512(false, true, kStaged, 8); }
-        else { if (nt) FDC_L512(true, false, kStaged, 8); else FDC_L512(false, false, kStaged, 8); }
-    } else if (N == 32768) {
-        if (R == 4) { if (nt) FDC_L512(true, true, true, 4); else FDC_L512(false, true, true, 4); }
-        else { if (nt) FDC_L512(true, false, true, 4); else FDC_L512(false, false, true, 4); }
-    } else {
-        if (R == 4) { if (nt) FDC_L512(true, true, true, 2); else FDC_L512(false, true, true, 2); }
-        else { if (nt) FDC_L512(true, false, true, 2); else FDC_L512(false, false, true, 2); }
-    }
+#define FDC_L512P(P) \
+    do { \
+        if (R == 4) { if (nt) FDC_L512(true, true, P); else FDC_L512(false, true, P); } \
+        else { if (nt) FDC_L512(true, false, P); else FDC_L512(false, false, P); } \
+    } while (0)
+    if (N == 65536) FDC_L512P(8); else if (N == 32768) FDC_L512P(4); else FDC_L512P(2);
+#undef FDC_L512P
 #undef FDC_L512
     return hipGetLastError();
 }

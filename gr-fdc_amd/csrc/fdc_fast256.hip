@@ -15,11 +15,6 @@
 #include "fdc_devutil.hpp"
 #include <cstdlib>
 
-// k_c256's output stores streamed (nt) like those of k_c512 / k_c1024 (fdc_devutil.hpp st2_out): -2 % on the channel kernels of a mixed plan, -1.3 % on the
-// example plan's, +1.4 % on a full band of 256-bin channels forced onto the spectrum path (profiles/r06/ch_nt_stores_ab.txt); -DFDC_C256_NT=0 builds the plain form
-#ifndef FDC_C256_NT
-#define FDC_C256_NT 1
-#endif
 namespace fdc {
 
 extern __shared__ __attribute__((aligned(16))) unsigned char fdc_smem_fast[];
@@ -192,12 +187,10 @@ __global__ __launch_bounds__(256, 4) void k_c256(const float2 *__restrict__ spec
 #pragma unroll
         for (int q = 0; q < 16; q++) {
             const int tt = b + 16 * q;
+            // streamed (nt) like k_c512 / k_c1024 (fdc_devutil.hpp st2_out): -2 % on the channel kernels of a mixed plan, -1.3 % on the example
+            // plan's, +1.4 % on a full band of 256-bin channels forced onto the spectrum path (profiles/r06/ch_nt_stores_ab.txt)
             if (tt >= skip) {
-#if FDC_C256_NT
                 st2_out(out + ri.dst + tt, v[rev16(q)] * 256.f);
-#else
-                st2(out + ri.dst + tt, v[rev16(q)] * 256.f);
-#endif
             }
         }
     }
@@ -285,10 +278,7 @@ __global__ __launch_bounds__(256, 4) void k_x256(const float2 *__restrict__ spec
 // when items are exactly N - N/R apart) those rows are handed over in registers — row 16a+b of the next block IS row
 // 16(a + 16 - KEEP) + b of this one — and only 16 - KEEP rows per thread are loaded (R = 2: half the input reads;
 // measured 0.144 -> 0.129 ms per 1024 blocks).  TC = 32: 512 threads, 2 workgroups/CU; TC = 16: 256 threads, 4/CU.
-// ABL (diagnostic builds only, FDC_ABLATE env): 0 = real kernel, 1 = memory only (loads -> stores, no math, no LDS),
-// 2 = math + LDS only (one load per thread, data kept live), 3 = loads + math, one store per thread, 4 = one load per thread + math + all
-// stores; results are garbage for ABL != 0.
-template <int TC, int ABL, int KEEP>
+template <int TC, int KEEP>
 __global__ __launch_bounds__(TC * 16, 4) void k_p1(const float2 *__restrict__ in, size_t in_stride,
                                                    float2 *__restrict__ g, const float2 *__restrict__ tw256,
                                                    const float2 *__restrict__ twq, const float2 *__restrict__ cbt,
@@ -332,16 +322,10 @@ __global__ __launch_bounds__(TC * 16, 4) void k_p1(const float2 *__restrict__ in
     // One tile: consume `cur` (block m), prefetch block mn (the next block of the run: overlap handed over in registers;
     // or the first block of this workgroup's next run: all rows loaded; or none, mn < 0) into `nbuf`.
     auto do_tile = [&](cf (&cur)[16], cf (&nbuf)[16], int m, int mn) {
-        // The row loads are inline assembly and the wait for them is stated at the END of the tile, behind this tile's stores
-        // (vm_wait, fdc_devutil.hpp): left to the compiler, the loop header waits with vmcnt(0) — for the eight stores of the tile
-        // before, once per tile (worth 1.2 % at N = 65536, nothing at N = 262144: profiles/r05/NOTES.md section 2).
+        // the rows are needed at the END of the tile, behind this tile's stores (vm_wait, fdc_devutil.hpp)
         if (mn >= 0) {
             const srd_t rin = make_srd(in + (size_t)mn * in_stride, inbytes);
-            if (ABL == 2 || ABL == 4) {
-                nbuf[0] = ald2<false>(rin, voff, 0);
-#pragma unroll
-                for (int a = 1; a < 16; a++) nbuf[a] = nbuf[0] * (float)a;
-            } else if (KEEP > 0 && mn == m + 1) {
+            if (KEEP > 0 && mn == m + 1) {
 #pragma unroll
                 for (int a = 0; a < KEEP; a++) nbuf[a] = cur[a + 16 - KEEP];       // the overlap, already on chip
                 if (hints & 2) {
@@ -359,13 +343,6 @@ __global__ __launch_bounds__(TC * 16, 4) void k_p1(const float2 *__restrict__ in
         // G is stored tile-major, G[m][column tile][t'][TC]: this workgroup's whole output (lout*TC points) is
         // one contiguous run, and stage 2 reads it back in runs of TC rows x TC columns.
         const __amdgpu_buffer_rsrc_t rg = make_rsrc(g + ((size_t)m * (size_t)(N1 / TC) + (c0 / TC)) * (size_t)lout * TC, gtile);
-        if (ABL == 1) {
-#pragma unroll
-            for (int q = 0; q < 16; q++)
-                if (q >= qs) bst2(rg, goff, (unsigned)(q - qs) * gstep, cur[q]);
-            vm_wait<0>(nbuf);
-            return;
-        }
         dft16<false>(cur);
         __syncthreads();                                        // tables ready / previous tile's LDS reads done
         // twiddles first, as one batch: a table read between two tile writes would wait (lgkmcnt is in-order)
@@ -414,24 +391,21 @@ __global__ __launch_bounds__(TC * 16, 4) void k_p1(const float2 *__restrict__ in
         if (hints & 8) {
 #pragma unroll
             for (int q = 0; q < 16; q++)
-                if (q >= qs && ((ABL != 2 && ABL != 3) || q == 15)) bst2_nt(rg, goff, (unsigned)(q - qs) * gstep, u[rev16(q)]);
+                if (q >= qs) bst2_nt(rg, goff, (unsigned)(q - qs) * gstep, u[rev16(q)]);
         } else {
 #pragma unroll
             for (int q = 0; q < 16; q++)
-                if (q >= qs && ((ABL != 2 && ABL != 3) || q == 15)) bst2(rg, goff, (unsigned)(q - qs) * gstep, u[rev16(q)]);
+                if (q >= qs) bst2(rg, goff, (unsigned)(q - qs) * gstep, u[rev16(q)]);
         }
-        // the next block's rows were requested a tile ago: waited for HERE, behind the stores (vmcnt counts in issue order: "at most
-        // the stores of this tile outstanding" = every row load has landed, no store is waited for)
-        if (KEEP > 0 && ABL == 0) vm_wait<16 - KEEP>(nbuf);
-        else if (ABL == 2 || ABL == 3) vm_wait<1>(nbuf);
-        else vm_wait<0>(nbuf);
+        // the next block's rows were requested a tile ago: needed HERE, behind the stores
+        vm_wait(nbuf);
     };
     cf L[16];
     {
         const srd_t rin = make_srd(in + (size_t)(grp * bpg) * in_stride, inbytes);
 #pragma unroll
         for (int a = 0; a < 16; a++) L[a] = ald2<false>(rin, voff, a * rowstep);
-        vm_wait<0>(L);
+        vm_wait(L);
     }
     for (int run = grp; run * bpg < nb; run += ngrp) {
         const int m0 = run * bpg, m1 = m0 + bpg < nb ? m0 + bpg : nb;
@@ -477,7 +451,7 @@ __global__ __launch_bounds__(TR * 16, 4) void k_p2(const float2 *__restrict__ g,
     const unsigned ctstep = (unsigned)lout * TCG * 8u;         // bytes between column tiles of one block
     // TCG = 16: ct = a, column = b.  TCG = 32: ct = a >> 1, column = 16*(a & 1) + b.
     const unsigned voff = (unsigned)(r * TCG + b) * 8u;
-    cf L[16];                                        // loads as inline assembly, waited for behind the stores: see k_p2k
+    cf L[16];                                        // needed behind the stores (vm_wait, fdc_devutil.hpp)
     auto issue = [&](int t) __attribute__((always_inline)) {
         const size_t m = t / tpb;
         const int t0 = (t - (int)m * tpb) * TR;
@@ -493,7 +467,7 @@ __global__ __launch_bounds__(TR * 16, 4) void k_p2(const float2 *__restrict__ g,
         }
     };
     issue(tl);
-    vm_wait<0>(L);
+    vm_wait(L);
     for (;;) {
         cf v[16];
 #pragma unroll
@@ -538,7 +512,7 @@ __global__ __launch_bounds__(TR * 16, 4) void k_p2(const float2 *__restrict__ g,
             for (int q = 0; q < 16; q++) bst2(rout, so[q], 0, v[rev16(q)]);
         }
         if (nxt >= ntiles) break;
-        vm_wait<16>(L);
+        vm_wait(L);
         tl = nxt;
     }
 }
@@ -550,25 +524,8 @@ __global__ __launch_bounds__(TR * 16, 4) void k_p2(const float2 *__restrict__ g,
 // LDS exchange layouts (both conflict-free for b64 accesses, rows on the fast lanes at the store end):
 //   exchange 1: (r, p, b')    at (p*64 + b')*16 + ((r ^ b') & 15)
 //   exchange 2: (r, p, d, s)  at ((p*4 + d)*16 + (s ^ (d & 1)))*16 + r
-// Round 6: 16-BYTE ACCESSES at both ends as a build variant (-DFDC_P2K_WIDE=1; the shipped form is the 8-byte one of rounds 2-5, see below).  The memory pattern alone runs at 6.3-6.6 TB/s
-// with 16 bytes per lane where the 8-byte form of this kernel moved its 537 MB at 5.76 (profiles/r05/NOTES.md section 1), and what kept the wide shape
-// out of k_p1 — lane pairs must trade halves so that a lane ends up with ONE column (loads) / one slot's TWO rows (stores) — costs one
-// instruction per dword here: v_permlane16_swap_b32 (gfx950) trades the odd rows of one register with the even rows of another, so the lane bit
-// that pairs two lanes is made bit 4 of the lane at both ends.
-//   loads : lane (c8, rlo, ah, rmid) of wave (rhi, j) asks for columns 2 c8, 2 c8 + 1 of row r at a = 8 ah + i, i < 8 (sixteen bytes); after eight
-//           swaps per component it holds column col = 2 c8 + ah at all sixteen a: the layer-1 roles with another lane numbering
-//   stores: layer-2/3 roles numbered so that bit 4 of the lane is bit 0 of the row: lanes l and l ^ 16 hold rows r2, r2 ^ 1 of the same sixteen slots;
-//           after the swaps the even row's lane has slots 0-7 of BOTH rows and the odd row's lane slots 8-15: eight 16-byte stores each.
-// The exchanges stay conflict-free under the new lane numberings (worked out against the bank rules as in the comment above: exchange 2's row
-// position is r2 ^ (d & 1) now, so that the two d of a 16-lane store group do not fall on the same 32 banks).
-// MEASURED (profiles/r06/ab_p2k_wide.txt, same box, three alternations, N = 262144): 0.0990 / 0.1001 / 0.1010 ms per 256 blocks against 0.0956 / 0.0980 /
-// 0.1062 for the 8-byte form: nothing.  Halving the instructions does not change what the memory system sees: G's column tiles are 16 columns wide
-// (k_p1's layout) and a tile has 16 rows per slot (LDS: 128 KiB), so both ends stay at 128-byte pieces; the pattern bench's gain came with 256-byte
-// pieces.  The 32 swaps per lane and tile cost nothing either.  Shipped: the 8-byte form (FDC_P2K_WIDE=0); the wide form passes the same parity tests.
-#ifndef FDC_P2K_WIDE
-#define FDC_P2K_WIDE 0
-#endif
-typedef unsigned u32x2p __attribute__((ext_vector_type(2)));
+// Round 6 measured 16-byte accesses at both ends (v_permlane16_swap_b32 trading halves between lane pairs): nothing (profiles/r06/ab_p2k_wide.txt,
+// N = 262144: G's column tiles and a tile's rows per slot keep both ends at 128-byte pieces either way).
 __global__ __launch_bounds__(1024, 1) void k_p2k(const float2 *__restrict__ g, float2 *__restrict__ out,
                                                   const float2 *__restrict__ tw1024,
                                                   const long long *__restrict__ slot_off, long long nrows,
@@ -591,50 +548,26 @@ __global__ __launch_bounds__(1024, 1) void k_p2k(const float2 *__restrict__ g, f
         const long long o = slot_off[tid];
         soff[tid] = o >= 0 ? (unsigned)((o * nb_call + out_base) * 8) : 0xFFFFFFFFu;
     }
-#if FDC_P2K_WIDE
-    const int ah = (tid >> 4) & 1;                                   // which half of a the lane loads; afterwards bit 0 of its column
-    const int col = 2 * (tid & 7) + ah, r = ((tid >> 3) & 1) + 2 * ((tid >> 5) & 1) + 4 * ((tid >> 6) & 3), j = tid >> 8;
-    const int bp = 16 * j + col;
-    const int r2 = 2 * ((tid >> 1) & 7) + ((tid >> 4) & 1), d = (tid & 1) + 2 * ((tid >> 5) & 1), p2 = tid >> 6;
-#else
     const int col = tid & 15, r = (tid >> 4) & 15, j = tid >> 8;     // layer 1: row r, b' = 16j + col
     const int bp = 16 * j + col;
     const int r2 = tid & 15, d = (tid >> 4) & 3, p2 = tid >> 6;      // layer 2: row r2, (p2, d); layer 3: (p2, e = d)
-#endif
     const __amdgpu_buffer_rsrc_t rout = make_rsrc(out, out_bytes);
     const int tpb = lout / TR;                                       // tiles per block
     // G[m][ct][t'][16]: point n1 = 64a + b' sits in column tile ct = 4a + j at column col
     const unsigned astep = 4u * (unsigned)lout * 16u * 8u;
-#if FDC_P2K_WIDE
-    const unsigned voff = (unsigned)((j * lout + r) * 16 + (col & ~1)) * 8u + 8u * (unsigned)ah * astep;
-#else
     const unsigned voff = (unsigned)((j * lout + r) * 16 + col) * 8u;
-#endif
     // LDS addresses with the swizzles folded into a few base pointers (everything else is an immediate offset)
     float2 *const wr1 = tile + bp * 16 + ((r ^ bp) & 15);                          // + p*1024
     const float2 *rd1[4];                                                          // + c*64, base by c & 3
 #pragma unroll
     for (int k = 0; k < 4; k++) rd1[k] = tile + (p2 * 64 + d) * 16 + ((r2 ^ d ^ (4 * k)) & 15);
     float2 *wr2[2];                                                                // s even / odd: + (s>>1)*32
-    constexpr int kPosSw = FDC_P2K_WIDE ? 1 : 0;                                   // wide form: row position r2 ^ (d & 1)
-    wr2[0] = tile + ((p2 * 4 + d) * 16 + (d & 1)) * 16 + (r2 ^ (kPosSw & d));
-    wr2[1] = tile + ((p2 * 4 + d) * 16 + 1 - (d & 1)) * 16 + (r2 ^ (kPosSw & d));
+    wr2[0] = tile + ((p2 * 4 + d) * 16 + (d & 1)) * 16 + r2;
+    wr2[1] = tile + ((p2 * 4 + d) * 16 + 1 - (d & 1)) * 16 + r2;
     const float2 *rd2[2];                                                          // d' even / odd: + (d'*16 + 4f)*16
     rd2[0] = tile + (p2 * 64 + d) * 16 + r2;
-    rd2[1] = tile + (p2 * 64 + (d ^ 1)) * 16 + (r2 ^ kPosSw);
-    // the tile loads are inline assembly and waited for behind the tile's stores (vm_wait, fdc_devutil.hpp): the compiler's own wait at
-    // the loop latch was vmcnt(0) — every wave of the one workgroup a compute unit has sat out the completion of its sixteen stores
-#if FDC_P2K_WIDE
-    u32x4 L4[8];
-    auto issue = [&](int t) __attribute__((always_inline)) {
-        const size_t m = t / tpb;
-        const int t0 = (t - (int)m * tpb) * TR;
-        const __amdgpu_buffer_rsrc_t rg = make_rsrc(g + m * (size_t)lout * 1024 + (size_t)t0 * 16, (unsigned)lout * 1024u * 8u);
-#pragma unroll
-        for (int i = 0; i < 8; i++) L4[i] = bld4(rg, voff, (unsigned)i * astep);
-    };
-    issue(tl);
-#else
+    rd2[1] = tile + (p2 * 64 + (d ^ 1)) * 16 + r2;
+    // the tile's rows are needed behind the tile's stores (vm_wait, fdc_devutil.hpp)
     cf L[16];
     auto issue = [&](int t) __attribute__((always_inline)) {
         const size_t m = t / tpb;
@@ -644,24 +577,11 @@ __global__ __launch_bounds__(1024, 1) void k_p2k(const float2 *__restrict__ g, f
         for (int a = 0; a < 16; a++) L[a] = ald2<false>(rg, voff, (unsigned)a * astep);
     };
     issue(tl);
-    vm_wait<0>(L);
-#endif
+    vm_wait(L);
     for (;;) {
         cf v[16];
-#if FDC_P2K_WIDE
-        // (columns 2 c8, 2 c8 + 1 at a = 8 ah + i) -> (column 2 c8 + ah at a = i and at a = 8 + i): the even row of a pair keeps its first column and
-        // gets it at the other eight a from the odd row, which keeps its second column
-#pragma unroll
-        for (int i = 0; i < 8; i++) {
-            const u32x2p sx = __builtin_amdgcn_permlane16_swap(L4[i].x, L4[i].z, false, false);
-            const u32x2p sy = __builtin_amdgcn_permlane16_swap(L4[i].y, L4[i].w, false, false);
-            v[i] = mk(__uint_as_float(sx.x), __uint_as_float(sy.x));
-            v[8 + i] = mk(__uint_as_float(sx.y), __uint_as_float(sy.y));
-        }
-#else
 #pragma unroll
         for (int a = 0; a < 16; a++) v[a] = L[a];
-#endif
         const int nxt = tl + gridDim.x;
         if (nxt < ntiles) issue(nxt);
         dft16<false>(v);                                            // Y_b'[p] in v[rev16(p)]
@@ -706,28 +626,9 @@ __global__ __launch_bounds__(1024, 1) void k_p2k(const float2 *__restrict__ g, f
 #pragma unroll
         for (int f = 0; f < 4; f++) dft4<false>(v[4 * f], v[4 * f + 1], v[4 * f + 2], v[4 * f + 3]);
         // Always sixteen stores per lane: a slot the plan does not use, or a row beyond the call, gets an offset beyond the descriptor's
-        // extent and is dropped by its range check (no branch per store; the count is what the wait below is stated in)
-#if FDC_P2K_WIDE
-        // rows r2 (even) and r2 + 1 of a slot are 16 contiguous bytes of its stream: the even row's lane takes slots v[0..7] of both rows, the odd
-        // row's lane slots v[8..15]; always eight stores per lane (unused slots / rows beyond the call: beyond the descriptor's extent)
-        const int odd = r2 & 1;
-        const long long rho = (long long)tl * TR + (r2 & ~1);
-        const bool live = rho < nrows;
-        const unsigned rbytes = (unsigned)rho * 8u;
-#pragma unroll
-        for (int i = 0; i < 8; i++) {
-            const int f = i >> 2, u = i & 3;
-            const unsigned off = soff[p2 + 16 * (4 * (f + 2 * odd) + d) + 256 * u];
-            const unsigned o = (off == 0xFFFFFFFFu || !live) ? 0xFFFFFFF0u : off + rbytes;
-            const u32x2p sx = __builtin_amdgcn_permlane16_swap(__float_as_uint(v[i].x), __float_as_uint(v[i + 8].x), false, false);
-            const u32x2p sy = __builtin_amdgcn_permlane16_swap(__float_as_uint(v[i].y), __float_as_uint(v[i + 8].y), false, false);
-            const cf lo = mk(__uint_as_float(sx.x), __uint_as_float(sy.x)), hi = mk(__uint_as_float(sx.y), __uint_as_float(sy.y));
-            if (hints & 1) bst4<true>(rout, o, lo, hi); else bst4<false>(rout, o, lo, hi);
-        }
-        if (nxt >= ntiles) break;
-        tl = nxt;
-#else
+        // extent and is dropped by its range check (no branch per store)
         const long long rho = (long long)tl * TR + r2;
+
         const bool live = rho < nrows;
         const unsigned rbytes = (unsigned)rho * 8u;
         unsigned so[16];
@@ -746,9 +647,8 @@ __global__ __launch_bounds__(1024, 1) void k_p2k(const float2 *__restrict__ g, f
             for (int i = 0; i < 16; i++) bst2(rout, so[i], 0, v[i]);
         }
         if (nxt >= ntiles) break;
-        vm_wait<16>(L);                                              // the next tile has landed; this tile's stores are not waited for
+        vm_wait(L);                                              // the next tile has landed; this tile's stores are not waited for
         tl = nxt;
-#endif
     }
 }
 
@@ -767,13 +667,12 @@ hipError_t init_fast_kernels()
     if (e != hipSuccess) return e;
     e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_b256), hipFuncAttributeMaxDynamicSharedMemorySize, a);
     if (e != hipSuccess) return e;
-#define FDC_SETP1(T, A, K) \
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_p1<T, A, K>), hipFuncAttributeMaxDynamicSharedMemorySize, a); \
+#define FDC_SETP1(T, K) \
+    e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_p1<T, K>), hipFuncAttributeMaxDynamicSharedMemorySize, a); \
     if (e != hipSuccess) return e;
-    FDC_SETP1(32, 0, 0) FDC_SETP1(16, 0, 0) FDC_SETP1(16, 1, 0) FDC_SETP1(16, 2, 0) FDC_SETP1(32, 1, 0) FDC_SETP1(32, 2, 0)
-    FDC_SETP1(16, 3, 8) FDC_SETP1(16, 4, 0)
-    FDC_SETP1(16, 0, 8) FDC_SETP1(16, 0, 4) FDC_SETP1(16, 0, 2) FDC_SETP1(16, 0, 1)
-    FDC_SETP1(32, 0, 8) FDC_SETP1(32, 0, 4) FDC_SETP1(32, 0, 2) FDC_SETP1(32, 0, 1)
+    FDC_SETP1(32, 0) FDC_SETP1(16, 0)
+    FDC_SETP1(16, 8) FDC_SETP1(16, 4) FDC_SETP1(16, 2) FDC_SETP1(16, 1)
+    FDC_SETP1(32, 8) FDC_SETP1(32, 4) FDC_SETP1(32, 2) FDC_SETP1(32, 1)
 #undef FDC_SETP1
     e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_p2<32, 32>), hipFuncAttributeMaxDynamicSharedMemorySize, a);
     if (e != hipSuccess) return e;
@@ -868,22 +767,17 @@ hipError_t launch_poly_stage1(const float2 *in, size_t in_stride, float2 *g, int
     if (groups > runs) groups = runs;
     const unsigned g1 = (unsigned)(groups * ct);
     const size_t lds1 = 256 * TC * 8 + 2304 + TC * 144 + 1024;
-    static int abl = -1, noreuse = 0;
-    if (abl < 0) {
-        const char *t = debug_env("FDC_ABLATE"); abl = t ? atoi(t) : 0;
-        const char *g4 = debug_env("FDC_POLY_NOREUSE"); noreuse = g4 ? atoi(g4) : 0;
-    }
+    static int noreuse = -1;
+    if (noreuse < 0) { const char *g4 = debug_env("FDC_POLY_NOREUSE"); noreuse = g4 ? atoi(g4) : 0; }
     // the overlap of consecutive blocks travels in registers when the items are exactly N - N/R apart
-    const bool reuse = !noreuse && (abl == 0 || abl == 3) && in_stride == (size_t)256 * N1 - (size_t)256 * N1 / R && R <= 16;
-#define FDC_LP1(T, A, K) \
-    hipLaunchKernelGGL((k_p1<T, A, K>), dim3(g1), dim3(T * 16), lds1, s, in, in_stride, g, tw256, twq, cbt, shn, N1, log2ct, \
+    const bool reuse = !noreuse && in_stride == (size_t)256 * N1 - (size_t)256 * N1 / R && R <= 16;
+#define FDC_LP1(T, K) \
+    hipLaunchKernelGGL((k_p1<T, K>), dim3(g1), dim3(T * 16), lds1, s, in, in_stride, g, tw256, twq, cbt, shn, N1, log2ct, \
                        nb_chunk, bpg, skip / 16, lout, nt_hints())
 #define FDC_LP1K(T) \
-    do { if (!reuse) FDC_LP1(T, 0, 0); else if (R == 2) FDC_LP1(T, 0, 8); else if (R == 4) FDC_LP1(T, 0, 4); \
-         else if (R == 8) FDC_LP1(T, 0, 2); else FDC_LP1(T, 0, 1); } while (0)
-    if (TC == 32) { if (abl == 1) FDC_LP1(32, 1, 0); else if (abl == 2) FDC_LP1(32, 2, 0); else FDC_LP1K(32); }
-    else { if (abl == 1) FDC_LP1(16, 1, 0); else if (abl == 2) FDC_LP1(16, 2, 0); else if (abl == 3 && reuse && R == 2) FDC_LP1(16, 3, 8);
-           else if (abl == 4) FDC_LP1(16, 4, 0); else FDC_LP1K(16); }
+    do { if (!reuse) FDC_LP1(T, 0); else if (R == 2) FDC_LP1(T, 8); else if (R == 4) FDC_LP1(T, 4); \
+         else if (R == 8) FDC_LP1(T, 2); else FDC_LP1(T, 1); } while (0)
+    if (TC == 32) FDC_LP1K(32); else FDC_LP1K(16);
 #undef FDC_LP1K
 #undef FDC_LP1
     return hipGetLastError();

@@ -30,16 +30,7 @@ namespace fdc {
 
 extern __shared__ __attribute__((aligned(16))) unsigned char fdc_smem_f4[];
 
-// diagnostics (tools/build_variant.sh -DF4_EXP=bits): 1 = every input load from one cached line, 2 = every window load from one cached line,
-// 4 = no output stores (unless a value the data never takes): what each stream's latency costs the kernel (profiles/r06/NOTES.md section 8);
-// 8 = three of the forward transform's five workgroup barriers left out (WRONG results): what they cost
-#ifndef F4_EXP
-#define F4_EXP 0
-#endif
-// streamed (nt) accesses: bit 0 = output stores, bit 1 = input loads (A/B: profiles/r06/NOTES.md section 8)
-#ifndef F4_NT
-#define F4_NT 1
-#endif
+// output stores streamed (nt), input loads plain (A/B: profiles/r06/NOTES.md section 8)
 namespace {
 constexpr int kF4TilePts = 16 * 272;                         // exchange tile of one block's forward transform; then its spectrum; then rows' exchanges
 // LDS image for T blocks (teams of four waves) per workgroup: [T tiles][W_256^(x y) 16 x 18][W_4096^(x y) 16 x 18][schedule: 4 T waves x 8 slots]
@@ -66,22 +57,14 @@ __device__ __forceinline__ void wave_sync()
 
 __device__ __forceinline__ void out_st(float2 *p, cf v, float)
 {
-#if F4_NT & 1
-    if (!(F4_EXP & 4) || v.x == 1.2345e30f) __builtin_nontemporal_store(v, reinterpret_cast<cf *>(p));
-#else
-    if (!(F4_EXP & 4) || v.x == 1.2345e30f) st2(p, v);
-#endif
+    __builtin_nontemporal_store(v, reinterpret_cast<cf *>(p));
 }
 // integer output (fdc_pipeline_set_output_format): the sample narrowed times s (oq_bits), one dword (sc16) / one 16-bit store (sc8), nt as above
 template <class TO, class TU>
 __device__ __forceinline__ void out_st_oq(TO *p, cf v, float s)
 {
     const TU u = (TU)oq_bits(TO{}, v, s);
-#if F4_NT & 1
-    if (!(F4_EXP & 4) || v.x == 1.2345e30f) __builtin_nontemporal_store(u, reinterpret_cast<TU *>(p));
-#else
-    if (!(F4_EXP & 4) || v.x == 1.2345e30f) *reinterpret_cast<TU *>(p) = u;
-#endif
+    __builtin_nontemporal_store(u, reinterpret_cast<TU *>(p));
 }
 __device__ __forceinline__ void out_st(sc16 *p, cf v, float s) { out_st_oq<sc16, unsigned>(p, v, s); }
 __device__ __forceinline__ void out_st(sc8 *p, cf v, float s) { out_st_oq<sc8, unsigned short>(p, v, s); }
@@ -94,7 +77,7 @@ __device__ __forceinline__ RowAt row_at(const F4Row &ri, int L, int m0, int nb, 
 {
     const int k = ri.valid ? ri.valid - 1 : 0, m = m0 + k;
     const int cnt = (int)(((unsigned)(fbm + m) % (unsigned)R) * (unsigned)ri.shift % (unsigned)R);     // phase counter in closed form (lib/phase_shifting_windowing_vcc_impl.cc:58,83-89)
-    return RowAt{wins + ((F4_EXP & 2) ? 0 : ri.win_off + cnt * L), tiles + k * kF4TilePts + ri.f, nb_call * ri.out_off + ((long long)mbase + m) * ri.lout - (L - ri.lout),
+    return RowAt{wins + (ri.win_off + cnt * L), tiles + k * kF4TilePts + ri.f, nb_call * ri.out_off + ((long long)mbase + m) * ri.lout - (L - ri.lout),
                  ri.valid != 0 && m < nb};
 }
 }  // namespace
@@ -154,8 +137,7 @@ __global__ __launch_bounds__(256 * TEAMS, 4 /* waves per SIMD */) void k_f4096(c
             for (int c = 0; c < 16; c++) raw[c] = m < nb ? iq_bits(in + (size_t)m * in_stride + (tid + 256 * c)) : 0u;
         } else
 #pragma unroll
-        for (int c = 0; c < 16; c++) u[c] = m < nb ? ((F4_NT & 2) ? __builtin_nontemporal_load(reinterpret_cast<const cf *>(in + (size_t)m * in_stride + (tid + 256 * c)))
-                                                                   : ld2(in + ((F4_EXP & 1) ? (size_t)(tid & 15) + 16 * c : (size_t)m * in_stride + (tid + 256 * c)))) : mk(0.f, 0.f);
+        for (int c = 0; c < 16; c++) u[c] = m < nb ? ld2(in + ((size_t)m * in_stride + (tid + 256 * c))) : mk(0.f, 0.f);
         __syncthreads();
         if constexpr (!std::is_same<TI, float2>::value) {
 #pragma unroll
@@ -176,7 +158,6 @@ __global__ __launch_bounds__(256 * TEAMS, 4 /* waves per SIMD */) void k_f4096(c
 #pragma unroll
         for (int b = 0; b < 16; b++) u[b] = ld2(&tile[hi * 272 + b * 16 + lo]);      // thread = (a = lo, k0 = hi)
         dft16<false>(u);                                             // layer 2 over b: k1 in u[rev16(k1)]
-        if constexpr (F4_EXP & 8) __builtin_amdgcn_wave_barrier(); else
         __syncthreads();                                             // every read of exchange 1 is done
         {
             const cf s = ld2(&t4k[lo * 18 + hi]);                    // W_4096^(a k0)
@@ -189,12 +170,10 @@ __global__ __launch_bounds__(256 * TEAMS, 4 /* waves per SIMD */) void k_f4096(c
 #pragma unroll
             for (int k1 = 0; k1 < 16; k1++) st2(&tile[k1 * 257 + hi * 16 + (lo ^ hi)], cmul(u[rev16(k1)], k1 == 0 ? s : cmul(s, w[k1])));
         }
-        if constexpr (F4_EXP & 8) __builtin_amdgcn_wave_barrier(); else
         __syncthreads();
 #pragma unroll
         for (int a = 0; a < 16; a++) u[a] = ld2(&tile[hi * 257 + lo * 16 + (a ^ lo)]);   // thread = (k0 = lo, k1 = hi)
         dft16<false>(u);                                             // layer 3 over a: bin k0 + 16 k1 + 256 k2 in u[rev16(k2)]
-        if constexpr (F4_EXP & 8) __builtin_amdgcn_wave_barrier(); else
         __syncthreads();                                             // every read of exchange 2 is done
         // the shifted spectrum (fftshift: bin k at k + N/2; python/FrequencyDomainChannelizer.py:206 fft_vcc(..., shift = True)), times 1/N
 #pragma unroll
@@ -227,7 +206,7 @@ __global__ __launch_bounds__(256 * TEAMS, 4 /* waves per SIMD */) void k_f4096(c
         {
             cf w[16];
 #pragma unroll
-            for (int a = 0; a < 16; a++) w[a] = ld2(a0.win + ((F4_EXP & 2) ? 0 : 16 * a) + b);
+            for (int a = 0; a < 16; a++) w[a] = ld2(a0.win + 16 * a + b);
 #pragma unroll
             for (int a = 0; a < 16; a++) v[a ^ 8] = cmul(ld2(a0.spec + 16 * a + b), w[a]);      // ifftshift of the slice: i -> i + l/2
         }
@@ -236,7 +215,7 @@ __global__ __launch_bounds__(256 * TEAMS, 4 /* waves per SIMD */) void k_f4096(c
             a1 = row_at(r1, 256, m0, nb, mbase, fbm, R, wins, nb_call, tiles);
             cf w[16];
 #pragma unroll
-            for (int a = 0; a < 16; a++) w[a] = ld2(a1.win + ((F4_EXP & 2) ? 0 : 16 * a) + b);
+            for (int a = 0; a < 16; a++) w[a] = ld2(a1.win + 16 * a + b);
 #pragma unroll
             for (int a = 0; a < 16; a++) v[16 + (a ^ 8)] = cmul(ld2(a1.spec + 16 * a + b), w[a]);
         }
@@ -251,7 +230,7 @@ __global__ __launch_bounds__(256 * TEAMS, 4 /* waves per SIMD */) void k_f4096(c
             a0 = row_at(r0, L, m0, nb, mbase, fbm, R, wins, nb_call, tiles);
             cf w[32];
 #pragma unroll
-            for (int a = 0; a < 32; a++) w[a] = ld2(a0.win + ((F4_EXP & 2) ? 0 : (a << lg)) + b);
+            for (int a = 0; a < 32; a++) w[a] = ld2(a0.win + (a << lg) + b);
 #pragma unroll
             for (int a = 0; a < 32; a++) v[a ^ 16] = cmul(ld2(a0.spec + (a << lg) + b), w[a]);
             dft32<true>(v);                                          // over a: index p in v[pos32(p)]
@@ -265,7 +244,7 @@ __global__ __launch_bounds__(256 * TEAMS, 4 /* waves per SIMD */) void k_f4096(c
         if ((lane >> lg) >= 8) a0.on = false;
         cf w[16];
 #pragma unroll
-        for (int a = 0; a < 16; a++) w[a] = ld2(a0.win + ((F4_EXP & 2) ? 0 : (a << lg)) + b);
+        for (int a = 0; a < 16; a++) w[a] = ld2(a0.win + (a << lg) + b);
 #pragma unroll
         for (int a = 0; a < 16; a++) v[a ^ 8] = cmul(ld2(a0.spec + (a << lg) + b), w[a]);          // ifftshift of the slice: i -> i + l/2 = a -> a ^ 8
         dft16<true>(reinterpret_cast<cf (&)[16]>(v[0]));             // over a: index p in v[rev16(p)]

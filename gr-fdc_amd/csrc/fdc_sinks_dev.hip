@@ -287,10 +287,7 @@ __device__ long long block_exscan(long long v, long long *tot, long long *sh /* 
 // pass of their own, :359-362), position of the channel in the list (its sequence number: the list is ordered by activation).
 constexpr int kDetWaves = 16;
 constexpr int kDetStaged = 8;                        // candidates per block held in LDS (more than that: read from memory)
-#ifndef FDC_DET_SLAB
-#define FDC_DET_SLAB 64
-#endif
-constexpr int kDetSlab = FDC_DET_SLAB;               // blocks per slab (<= 64: lanes = blocks).  Measured on configs[4], payloads in HBM:
+constexpr int kDetSlab = 64;                         // blocks per slab (<= 64: lanes = blocks).  Measured on configs[4], payloads in HBM:
                                                      // 64 -> 1.00 ms per step, 32 -> 1.06, 16 -> 1.18 (shorter slabs split the regions
                                                      // further but pay the per-slab set-up more often)
 __host__ __device__ constexpr size_t det_lds_bytes(int nb, int words)
@@ -397,17 +394,6 @@ __global__ __launch_bounds__(64 * kDetWaves) void k_det_track(DetParams dp, int 
         }
     };
 
-#ifdef FDC_DET_STATS
-    unsigned long long tacc[8] = {}, tlast = __builtin_readcyclecounter();
-    int nregsum = 0;
-    unsigned long long wacc[3] = {};                                 // this wave: region set-up, passes of alive channels, activations
-    int wcnt[3] = {};                                                // regions, passes of alive channels, activations
-#define FDC_WT(i, n) do { const unsigned long long tn = __builtin_readcyclecounter(); wacc[i] += tn - wlast; wlast = tn; wcnt[i] += (n); } while (0)
-#define FDC_DT(i) do { const unsigned long long tn = __builtin_readcyclecounter(); tacc[i] += tn - tlast; tlast = tn; } while (0)
-#else
-#define FDC_WT(i, n) do { } while (0)
-#define FDC_DT(i) do { } while (0)
-#endif
     // the tables of a slab (candidate counts of its blocks, the first `staged` candidates of each) are requested a slab ahead, one entry
     // per thread (64 x staged = 512 <= the workgroup's threads), and only written to LDS here: their latency lies behind the slab before
     auto want_km = [&](int mb) { return (tid < kDetSlab && mb + tid < nb) ? kc[mb + tid] : 0; };
@@ -426,7 +412,6 @@ __global__ __launch_bounds__(64 * kDetWaves) void k_det_track(DetParams dp, int 
         if (tid < 16) COV[tid] = 0;
         if (tid == 0) { cnt[0] = 0; cnt[1] = 0; cnt[5] = 0; }
         __syncthreads();
-        FDC_DT(0);
         {   // the staged candidates: a thread each; what a block has beyond them (rare): a wave per block
             const int q = tid / staged, j = tid % staged;
             if (tid < 64 * staged && j < KM[q]) { const int2 pc = CS[tid]; cover(cell_of(pc.x), cell_of(pc.y)); }
@@ -437,7 +422,6 @@ __global__ __launch_bounds__(64 * kDetWaves) void k_det_track(DetParams dp, int 
         }
         for (int i = tid; i < nal; i += 64 * kDetWaves) cover(cell_of(AL[A_DS + i]), cell_of(AL[A_DE + i]));
         __syncthreads();
-        FDC_DT(1);
         if (wv == 0) {
             // regions = maximal runs of covered cells: lane w looks at word w (ncell <= 1024 = 16 words)
             const unsigned long long c = lane < 16 ? COV[lane] : 0ull;
@@ -461,10 +445,6 @@ __global__ __launch_bounds__(64 * kDetWaves) void k_det_track(DetParams dp, int 
         }
         __syncthreads();
         const int nreg = cnt[0];
-        FDC_DT(2);
-#ifdef FDC_DET_STATS
-        nregsum += nreg;
-#endif
         for (;;) {
             int r = 0;
             if (lane == 0) r = atomicAdd(&cnt[1], 1);
@@ -477,9 +457,6 @@ __global__ __launch_bounds__(64 * kDetWaves) void k_det_track(DetParams dp, int 
             // This wave is the only one that looks at the region's candidates in this slab, and lane = block: what a block's
             // candidates are, which of them are the region's (RM), taken (cl) or have become channels (nm) stays in the lane's
             // registers for the whole region — a channel's pass over the slab is compares and ballots, no memory round trip.
-#ifdef FDC_DET_STATS
-            unsigned long long wlast = __builtin_readcyclecounter();
-#endif
             const int m = m0 + lane;
             const int k = KM[lane];
             int2 cs[staged];
@@ -540,7 +517,6 @@ __global__ __launch_bounds__(64 * kDetWaves) void k_det_track(DetParams dp, int 
                 end_out = F ? m0 + endlane : -1;
                 streak_out = lastv >= f ? lane_val(st, lastv) : inact0;
             };
-            FDC_WT(0, 1);
             // the channels alive at the start of the slab, in list order
             for (int i0 = 0; i0 < nal; i0 += 64) {
                 const int i = i0 + lane;
@@ -552,7 +528,6 @@ __global__ __launch_bounds__(64 * kDetWaves) void k_det_track(DetParams dp, int 
                     int end, streak;
                     scan(ds, de, m0, AL[A_STK + ii], end, streak);
                     settle(AL[A_T + ii], AL[A_KEY + ii], ds, de, end, streak);
-                    FDC_WT(1, 1);
                 }
             }
             // candidates of the region nobody took become channels (:785-841), block after block
@@ -605,7 +580,6 @@ __global__ __launch_bounds__(64 * kDetWaves) void k_det_track(DetParams dp, int 
                         t0++;
                         if (lane == 0) chs[t] = DetCh{cx, cy, ces, ccls, mf, 64 * w + jl, -1, 0};
                         settle(t, nlive0 + mf * g.cand_cap + 64 * w + jl, cx, cy, end, streak);
-                        FDC_WT(2, 1);
                     }
                 }
                 ms = mf + 1;
@@ -614,9 +588,7 @@ __global__ __launch_bounds__(64 * kDetWaves) void k_det_track(DetParams dp, int 
 #pragma unroll
             for (int w = 0; w < WORDS; w++) if (nm[w]) atomicOr(&NM[(size_t)m * words + w], nm[w]);
         }
-        FDC_DT(3);
         __syncthreads();
-        FDC_DT(4);
         // ---- the list of the next slab: who is still alive, in the reference's list order (old ones, then by activation)
         const int nt = cnt[5] < kDetMaxCells ? cnt[5] : kDetMaxCells;
         if (tid < nt) {
@@ -627,7 +599,6 @@ __global__ __launch_bounds__(64 * kDetWaves) void k_det_track(DetParams dp, int 
         }
         nal = nt;
         __syncthreads();
-        FDC_DT(5);
     }
     // the channels that outlive the call: their misses in a row go into the next call's list
     for (int i = tid; i < nal; i += 64 * kDetWaves) chs[AL[A_T + i]].streak = AL[A_STK + i];
@@ -739,7 +710,6 @@ __global__ __launch_bounds__(64 * kDetWaves) void k_det_track(DetParams dp, int 
             }
         }
     };
-    FDC_DT(6);
     for (int t = wv; t < nown; t += kDetWaves) {
         const DetCh h = chs[t];
         DetChanRegs c;
@@ -775,14 +745,6 @@ __global__ __launch_bounds__(64 * kDetWaves) void k_det_track(DetParams dp, int 
     if (tid == 0) {
         sst[sg].nlive = nsv; sst[sg].counter = counter0 + nnew;
         npdu[lst] = cnt[3]; nowner[sg] = nown;
-#ifdef FDC_DET_STATS
-        printf("[det]   wave 0 of seg %d: %d regions set up in %llu kcycles, %d passes of alive channels in %llu, %d activations in %llu\n", sg, wcnt[0],
-               wacc[0] / 1000, wcnt[1], wacc[1] / 1000, wcnt[2], wacc[2] / 1000);
-        FDC_DT(7);
-        printf("[det] seg %d: %d cells, %d live before, %d new, %d survive, %d records, %d regions in all slabs; kcycles wave 0: tables %llu cover %llu regions %llu work %llu wait %llu "
-               "rebuild %llu prefix %llu emit+rest %llu\n", sg, g.ncell, nlive0, nnew, nsv, cnt[3], nregsum, tacc[0] / 1000, tacc[1] / 1000, tacc[2] / 1000,
-               tacc[3] / 1000, tacc[4] / 1000, tacc[5] / 1000, tacc[6] / 1000, tacc[7] / 1000);
-#endif
     }
 }
 
