@@ -417,13 +417,18 @@ void det_emit(fdc_sinks *s, Emit &e, Segment &g, DetChan &c, bool fin, size_t nb
 {
     PduRec r;
     r.key = e.key++;
-    r.meta.kind = 1; r.meta.source = g.ID; r.meta.chan_id = c.ID;
+    // the number the ID string carries (activate()): SegmentDetection's own ID where the bank was given one — as the device engine reports it
+    r.meta.kind = 1; r.meta.chan_id = c.ID;
+    r.meta.source = (s->cfg.det_variant == 1 && s->cfg.det_id >= 0 && s->segs.size() == 1) ? s->cfg.det_id : g.ID;
     r.meta.finalized = fin; r.meta.part = c.part; r.meta.has_part = fin ? (c.part > 0) : 1;
     r.meta.rel_bw = (double)c.extract_width / (double)s->N;
     r.meta.rel_cfreq = (double)(c.extract_start + c.extract_stop) / 2.0 / (double)s->N;
     // the vcm block counts from 1 (…vcm_impl.cc:188), SegmentDetection from 0 (SegmentDetection_impl.cc:118)
     const int64_t bc = e.blockcount - (s->cfg.det_variant == 1 ? 1 : 0);
-    r.meta.blockstart = bc - c.count; r.meta.blockend = bc;
+    // blockcount - count in the counter's own type: the vcm block's is `unsigned int` (…vcm_impl.h:142), so a channel activated in
+    // the very first item (count 2 with the zero history, counter 1) publishes 4294967295, not -1; SegmentDetection's size_t
+    // difference comes out of pmt::from_long(long) as the signed value (SegmentDetection_impl.h:96)
+    r.meta.blockstart = s->cfg.det_variant == 1 ? bc - c.count : (int64_t)(uint32_t)(bc - c.count); r.meta.blockend = bc;
     r.meta.vectorstart = c.extract_start; r.meta.vectorend = c.extract_stop;
     std::snprintf(r.meta.id, sizeof r.meta.id, "%s", c.msg_id.c_str());
     r.blocklen = c.outputsamples;
@@ -1567,7 +1572,9 @@ static int dev_build(fdc_sinks *s, int b)
         m.chan_id = r.chan_id; m.finalized = r.flags & 1; m.part = r.part;
         m.rel_bw = (double)width / (double)s->N;
         m.rel_cfreq = (double)(vstart + vend) / 2.0 / (double)s->N;
-        m.blockstart = m.blockend - r.count; m.vectorstart = vstart; m.vectorend = vend;
+        // the vcm block's counter is `unsigned int`: blockcount - count wraps at 2^32 for a channel activated in the first item (det_emit)
+        m.blockstart = (det && !sd) ? (int64_t)(uint32_t)(m.blockend - r.count) : m.blockend - r.count;
+        m.vectorstart = vstart; m.vectorend = vend;
         m.nsamples = (int64_t)(r.q1 - r.q0) * o.blocklen;
         m.samples = m.nsamples ? base + sizeof(float2) * (size_t)r.off : nullptr;
         if ((time_t)r.act_time != last_t) {                    // create_ID() / get_ID_for_msg(): local time of the activation

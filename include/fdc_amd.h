@@ -384,7 +384,7 @@ enum {
 };
 typedef struct {
     int32_t kind;        /* 0 = PowerActivationChannel, 1 = detected channel of a segment                       */
-    int32_t source;      /* PAC: its ID argument; detection: segment index                                      */
+    int32_t source;      /* PAC: its ID argument; detection: segment index, or det_id where a SegmentDetection bank was given one                                    */
     int32_t chan_id;     /* the running number inside the ID string: PAC finished_channels at activation
                             (…PowActChan.<ID>.<n>), detection: channel counter of the segment (…DETECTED.<seg>.<n>) */
     int32_t finalized, part, has_part;   /* has_part: whether the dict carries "part" (…vcm_impl.cc:419-420)   */

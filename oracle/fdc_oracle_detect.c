@@ -6,8 +6,8 @@
  * Each function cites the lines it follows.  PDUs (pmt::cons(dict, c32vector)) are returned as POD records; the
  * timestamp part of the ID strings (…_impl.cc get_current_time) is not modelled.
  * The inverse transforms use the oracle's double-precision FFT (fdc_oracle.c), rounded to float once, exactly like
- * the throughput chain.  Pinning: the reference holds no tests for these blocks; the only reference outputs available
- * are the PDU metadata recorded in SURVEY.md §8c (tests/golden/sink_known_answers.json).
+ * the throughput chain.  Pinning: the reference's own *_impl.cc files, compiled where they lie into oracle/_ref/libref_sinks.so
+ * (ref_sinks_driver.cpp, ref_standins/), judge this file in tests/test_sinks_reference_cpu.py.
  */
 #include <float.h>
 #include <math.h>
@@ -496,7 +496,11 @@ static void vcm_fill(const fdco_vcm *v, const vcm_seg *g, const vcm_chan *c, fdc
     d->kind = 1; d->source = g->ID; d->chan_id = c->ID;
     d->rel_bw = (double)c->extract_width / (double)v->blocklen;
     d->rel_cfreq = (double)(c->extract_start + c->extract_stop) / 2.0 / (double)v->blocklen;
-    d->blockstart = (long)v->blockcount - c->count; d->blockend = (long)v->blockcount;
+    /* blockcount - c.count in the counter's own type: `unsigned int` in the vcm block (…vcm_impl.h:142; a channel activated in the
+     * first item, count 2 at counter 1, publishes 4294967295), size_t in SegmentDetection (SegmentDetection_impl.h:96), whose
+     * difference pmt::from_long(long) takes as the signed value.  Found by the compiled reference (test_sinks_reference_cpu.py). */
+    d->blockstart = v->variant == 0 ? (long)(unsigned)(v->blockcount - (unsigned)c->count) : (long)v->blockcount - c->count;
+    d->blockend = (long)v->blockcount;
     d->vectorstart = c->extract_start; d->vectorend = c->extract_stop;
 }
 

@@ -1,5 +1,6 @@
 """TEST INFRASTRUCTURE — ctypes face of oracle/libfdc_oracle.so (the CPU restatement) and, when
-built, oracle/_ref/libref_windows.so (the reference's own lib/windows.h).
+built, oracle/_ref/libref_windows.so (the reference's own lib/windows.h) and oracle/_ref/libref_sinks.so (the reference's
+own three sink blocks over the stand-ins of oracle/ref_standins/).
 
 Importable only from tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg.  The product
 package (gr-fdc_amd/) never imports this module.
@@ -13,6 +14,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = os.environ.get("FDC_ORACLE_LIB") or os.path.join(_HERE, "libfdc_oracle.so")    # FDC_ORACLE_LIB: the sanitizer build (oracle/_san)
 _REF = os.path.join(_HERE, "_ref", "libref_windows.so")
+_REF_SINKS = os.path.join(_HERE, "_ref", "libref_sinks.so")
 
 _fp = C.POINTER(C.c_float)
 _ip = C.POINTER(C.c_int)
@@ -21,7 +23,7 @@ _dp = C.POINTER(C.c_double)
 
 def build(force=False):
     """Compile the oracle (and oracle/_ref when /root/reference is present)."""
-    if force or not os.path.exists(_LIB) or (os.path.isdir("/root/reference") and not os.path.exists(_REF)):
+    if force or not os.path.exists(_LIB) or (os.path.isdir("/root/reference") and not (os.path.exists(_REF) and os.path.exists(_REF_SINKS))):
         subprocess.check_call(["make", "-C", _HERE, "-s"])
 
 
@@ -62,6 +64,10 @@ def lib():
 
 def have_ref():
     return os.path.exists(_REF)
+
+
+def have_ref_sinks():
+    return os.path.exists(_REF_SINKS)
 
 
 # ---- bench.py's "reference-equivalent" CPU leg (oracle/ref_equiv.c): the chain with FFTW3f + VOLK found by dlopen()
@@ -340,3 +346,96 @@ class SegmentDetection(ActivityDetectionVcm):
         v = (C.c_int * 5)()
         lib().fdco_vcm_segment_params(self._h, 0, v)
         self.segments = [dict(start=v[0], stop=v[1], width=v[2], dec=v[3], npower=v[4])]
+
+
+# ---- the reference's OWN sink blocks (oracle/_ref/libref_sinks.so: lib/*_impl.cc compiled where they lie, oracle/ref_sinks_driver.cpp) ----
+class _RefPduList(C.Structure):
+    _fields_ = [("pdu", C.POINTER(_Pdu)), ("n", C.c_int), ("cap", C.c_int), ("ids", C.POINTER(C.c_char_p))]
+
+
+_refs = None
+
+
+def _ref_sinks():
+    global _refs
+    if _refs is None:
+        h = C.CDLL(_REF_SINKS)
+        h.ref_sinks_last_error.restype = C.c_char_p
+        h.ref_pac_create.restype = C.c_void_p
+        h.ref_pac_create.argtypes = [C.c_int, C.c_float, C.c_float, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int]
+        h.ref_vcm_create.restype = C.c_void_p
+        h.ref_vcm_create.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_float, C.c_int, C.c_double, C.c_int]
+        h.ref_sd_create.restype = C.c_void_p
+        h.ref_sd_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int,
+                                    C.c_int]
+        h.ref_sinks_destroy.argtypes = [C.c_void_p]
+        h.ref_sinks_work.restype = C.c_int
+        h.ref_sinks_work.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+        h.ref_sinks_drain.restype = C.c_int
+        h.ref_sinks_drain.argtypes = [C.c_void_p, C.POINTER(_RefPduList)]
+        h.ref_sinks_list_clear.argtypes = [C.POINTER(_RefPduList)]
+        _refs = h
+    return _refs
+
+
+class _RefSink:
+    """work(spectrum, per_call=0) -> the PDU dicts of the oracle classes above plus "ident", the reference's ID string as published
+    (wall-clock stamp included).  source / chan_id are read from that string ("<stamp>.PowActChan.<ID>.<n>.fin|.part",
+    "<stamp>.DETECTED.<segment>.<n>"); vectorstart / vectorend are -1 where the dictionary has no such key (PowerActivationChannel).
+    per_call: spectrum items per work() call of the block (0 = all in one call)."""
+
+    def _take(self, handle, blocklen):
+        if not handle:
+            raise ValueError(_ref_sinks().ref_sinks_last_error().decode())
+        self._h, self.N = handle, blocklen
+
+    def work(self, spectrum, per_call=0):
+        spectrum = np.ascontiguousarray(spectrum, dtype=np.complex64)
+        r = _ref_sinks()
+        if r.ref_sinks_work(self._h, spectrum.ctypes.data, spectrum.size // self.N, int(per_call)) < 0:
+            raise RuntimeError(r.ref_sinks_last_error().decode())
+        L = _RefPduList()
+        if r.ref_sinks_drain(self._h, C.byref(L)) < 0:
+            raise RuntimeError(r.ref_sinks_last_error().decode())
+        out = []
+        for i in range(L.n):
+            p = L.pdu[i]
+            ident = L.ids[i].decode()
+            tail = ident[20:].split(".")            # the stamp is "YYYY-mm-dd-HH-MM-SS." (19 characters and a dot)
+            d = dict(kind=p.kind, source=int(tail[1]), chan_id=int(tail[2]), finalized=bool(p.finalized), part=p.part,
+                     has_part=bool(p.has_part), rel_bw=p.rel_bw, rel_cfreq=p.rel_cfreq, blockstart=p.blockstart,
+                     blockend=p.blockend, vectorstart=p.vectorstart, vectorend=p.vectorend, ident=ident)
+            d["samples"] = np.ctypeslib.as_array(p.samples, shape=(2 * p.nsamples,)).copy().view(np.complex64) \
+                if p.nsamples > 0 else np.zeros(0, np.complex64)
+            out.append(d)
+        r.ref_sinks_list_clear(C.byref(L))
+        return out
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            _ref_sinks().ref_sinks_destroy(self._h)
+            self._h = None
+
+
+class RefPowerActivationChannel(_RefSink):
+    """The reference's PowerActivationChannel::make(...), message output on, file output off, verbose 0."""
+
+    def __init__(self, blocklen, cfreq, bw, relinvovl, thresh, maxblocks, deactivation_delay, ID=0):
+        self._take(_ref_sinks().ref_pac_create(blocklen, cfreq, bw, relinvovl, thresh, maxblocks, deactivation_delay, ID), blocklen)
+
+
+class RefActivityDetectionVcm(_RefSink):
+    """The reference's activity_detection_channelizer_vcm::make(...); `threads` selects its threaded paths."""
+
+    def __init__(self, blocklen, segments, thresh, relinvovl, maxblocks, minchandist, deactivation_delay, puffer, threads=False):
+        seg = np.array(segments, dtype=np.float32).reshape(-1, 2)
+        self._take(_ref_sinks().ref_vcm_create(blocklen, len(seg), seg.ctypes.data, thresh, relinvovl, maxblocks, minchandist,
+                                               deactivation_delay, puffer, int(threads)), blocklen)
+
+
+class RefSegmentDetection(_RefSink):
+    """The reference's SegmentDetection::make(...)."""
+
+    def __init__(self, ID, blocklen, relinvovl, seg_start, seg_stop, thresh, minchandist, puffer, maxblocks, delay, threads=False):
+        self._take(_ref_sinks().ref_sd_create(ID, blocklen, relinvovl, seg_start, seg_stop, thresh, minchandist, puffer, maxblocks,
+                                              delay, int(threads)), blocklen)

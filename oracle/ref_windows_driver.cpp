@@ -1,8 +1,7 @@
 // TEST INFRASTRUCTURE. Thin C-ABI driver around the reference's OWN window generator.
 // The reference header is compiled unmodified from where it lies (/root/reference/lib/windows.h,
 // passed with -I by oracle/Makefile); nothing of it is copied into this repository.  It needs only
-// the C++ standard library, so it is the one piece of the path buildable in this image
-// (the *_impl.cc files need GNU Radio / VOLK / pmt headers, which are absent => unbuildable here).
+// the C++ standard library (the sink blocks' *_impl.cc files need stand-ins: ref_sinks_driver.cpp).
 #include "windows.h"
 
 extern "C" void ref_cr_win(int wintype, int blocksize, float passbw, float stopbw, int relinvovl,

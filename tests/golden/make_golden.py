@@ -11,8 +11,9 @@ Fixtures are DATA (inputs + expected outputs):
   chain_numpy.npz      the throughput chain evaluated with numpy.fft in
                        complex128 — an implementation independent of oracle/fdc_oracle.c — on seeded
                        multicarrier input, float32-rounded at the reference's stage boundaries.
-  sink_known_answers.json  PDU metadata the reference's sink blocks produced in the survey session's
-                       validation run, kept as known answers for the detector restatement.
+  sink_known_answers.json  PDU metadata of three cases from the reference's own sink blocks, compiled where they lie into
+                       oracle/_ref/libref_sinks.so (sink_known_answers() below).
+  sink_ref_runs.npz    NOT made here: tests/golden/make_sink_ref_runs.py records the reference's sink blocks on seeded cases.
 """
 import json
 import os
@@ -126,18 +127,41 @@ def make_chain():
     np.savez_compressed(os.path.join(HERE, "chain_numpy.npz"), **d)
 
 
-def make_sink_known_answers():
-    ka = {
-        "source": "SURVEY.md section 8c validation run: reference sink blocks fed a synthetic burst "
-                  "(bins 1600-1799 active in blocks 3-7, N=4096, R=4)",
-        "PowerActivationChannel": dict(rel_bw=0.0625, blockstart=2, blockend=9, nsamples=1344),
-        "SegmentDetection": dict(vectorstart=1442, vectorend=1954, rel_bw=0.125, blockstart=2, blockend=9,
-                                 nsamples=2688),
-        "activity_detection_channelizer_vcm": dict(vectorstart=1442, vectorend=1954, rel_bw=0.125,
-                                                   blockstart=3, blockend=10, nsamples=2688),
+def _known_answer_spectrum():
+    """burst_spectrum(4096, 12, [(1600, 1800, 3, 7, 1.0)], 0) of tests/test_sinks_gpu.py: bins 1600-1799 active in blocks 3-7"""
+    N, nb = 4096, 12
+    rng = np.random.default_rng(0)
+    s = 1e-3 * (rng.standard_normal((nb, N)) + 1j * rng.standard_normal((nb, N)))
+    s[3:8, 1600:1800] += 1.0 * (rng.standard_normal((5, 200)) + 1j * rng.standard_normal((5, 200)))
+    return s.astype(np.complex64)
+
+
+def sink_known_answers():
+    """The three known-answer cases of tests/test_sinks_gpu.py through the reference's OWN sink blocks (oracle/_ref/libref_sinks.so:
+    lib/*_impl.cc compiled where they lie over oracle/ref_standins/, recipe `make -C oracle ref`)."""
+    N, R = 4096, 4
+    spec = _known_answer_spectrum()
+    (p,) = O.RefPowerActivationChannel(N, (1600 + 1800) / 2 / N, 200 / N, R, 6.0, -1, 0, 0).work(spec)
+    (v,) = O.RefActivityDetectionVcm(N, [[0.3, 0.55]], 10.0, R, -1, 0.005, 1, 0.2).work(spec)
+    (d,) = O.RefSegmentDetection(0, N, R, 0.3, 0.55, 10.0, 0.005, 0.2, -1, 1).work(spec)
+
+    def det(m):
+        return dict(vectorstart=int(m["vectorstart"]), vectorend=int(m["vectorend"]), rel_bw=float(m["rel_bw"]),
+                    blockstart=int(m["blockstart"]), blockend=int(m["blockend"]), nsamples=int(m["samples"].size))
+    return {
+        "source": "the reference's own sink blocks, compiled by `make -C oracle ref` into oracle/_ref/libref_sinks.so over the stand-ins of "
+                  "oracle/ref_standins/, fed a synthetic burst (bins 1600-1799 active in blocks 3-7, N=4096, R=4); "
+                  "tests/golden/make_golden.py sink_known_answers()",
+        "PowerActivationChannel": dict(rel_bw=float(p["rel_bw"]), blockstart=int(p["blockstart"]), blockend=int(p["blockend"]),
+                                       nsamples=int(p["samples"].size)),
+        "SegmentDetection": det(d),
+        "activity_detection_channelizer_vcm": det(v),
     }
+
+
+def make_sink_known_answers():
     with open(os.path.join(HERE, "sink_known_answers.json"), "w") as fh:
-        json.dump(ka, fh, indent=1)
+        json.dump(sink_known_answers(), fh, indent=1)
 
 
 if __name__ == "__main__":

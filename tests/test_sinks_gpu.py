@@ -141,8 +141,8 @@ def test_vcm_known_answer_and_face(oracle, golden_dir):
     assert unstamp(d["ID"]) == "DETECTED.0.0" and d["finalized"] is True and "part" not in d
     assert (abs(d["rel_bw"] - ka["rel_bw"]) < 1e-12 and d["blockstart"] == ka["blockstart"] and d["blockend"] == ka["blockend"]
             and data.size == ka["nsamples"])
-    # the survey run's segment geometry is not recorded: the detection grid (dec = 10 bins) may shift the slice
-    assert abs(d["vectorstart"] - ka["vectorstart"]) <= 10 and d["vectorend"] - d["vectorstart"] == 512
+    # the known answer is the compiled reference's own run of this case (tests/golden/make_golden.py): the slice is met exactly
+    assert (d["vectorstart"], d["vectorend"]) == (ka["vectorstart"], ka["vectorend"]) and d["vectorend"] - d["vectorstart"] == 512
     with pytest.raises(ValueError):
         G.activity_detection_channelizer_vcm(N, [[0.5, 0.3]], 10.0, R, -1, True, False, "", False, 0.005, 1, 0.2, 0)
     with pytest.raises(ValueError):
@@ -209,6 +209,7 @@ def test_segment_detection_face_vs_oracle(oracle, golden_dir, N, R, maxblocks, d
     spec2 = burst_spectrum(4096, 12, [(1600, 1800, 3, 7, 1.0)], 0)
     (d, s), = G.SegmentDetection(0, 4096, 4, 0.3, 0.55, 10.0, 0.005, 0.2, -1, 1, True, False, "", False, 0).work(spec2)
     assert (d["blockstart"], d["blockend"], s.size) == (ka["blockstart"], ka["blockend"], ka["nsamples"]) and abs(d["rel_bw"] - ka["rel_bw"]) < 1e-12
+    assert (d["vectorstart"], d["vectorend"]) == (ka["vectorstart"], ka["vectorend"])
 
 
 def test_sinks_wider_than_one_workgroup_transform(oracle):
