@@ -1,6 +1,7 @@
 """TEST INFRASTRUCTURE — ctypes face of oracle/libfdc_oracle.so (the CPU restatement) and, when
 built, oracle/_ref/libref_windows.so (the reference's own lib/windows.h) and oracle/_ref/libref_sinks.so (the reference's
-own three sink blocks over the stand-ins of oracle/ref_standins/).
+own three sink blocks over the stand-ins of oracle/ref_standins/) and oracle/_ref/libref_chain.so (the reference's own three
+throughput-chain blocks over the same stand-ins).
 
 Importable only from tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg.  The product
 package (gr-fdc_amd/) never imports this module.
@@ -15,6 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = os.environ.get("FDC_ORACLE_LIB") or os.path.join(_HERE, "libfdc_oracle.so")    # FDC_ORACLE_LIB: the sanitizer build (oracle/_san)
 _REF = os.path.join(_HERE, "_ref", "libref_windows.so")
 _REF_SINKS = os.path.join(_HERE, "_ref", "libref_sinks.so")
+_REF_CHAIN = os.path.join(_HERE, "_ref", "libref_chain.so")
 
 _fp = C.POINTER(C.c_float)
 _ip = C.POINTER(C.c_int)
@@ -23,7 +25,7 @@ _dp = C.POINTER(C.c_double)
 
 def build(force=False):
     """Compile the oracle (and oracle/_ref when /root/reference is present)."""
-    if force or not os.path.exists(_LIB) or (os.path.isdir("/root/reference") and not (os.path.exists(_REF) and os.path.exists(_REF_SINKS))):
+    if force or not os.path.exists(_LIB) or (os.path.isdir("/root/reference") and not (os.path.exists(_REF) and os.path.exists(_REF_SINKS) and os.path.exists(_REF_CHAIN))):
         subprocess.check_call(["make", "-C", _HERE, "-s"])
 
 
@@ -68,6 +70,10 @@ def have_ref():
 
 def have_ref_sinks():
     return os.path.exists(_REF_SINKS)
+
+
+def have_ref_chain():
+    return os.path.exists(_REF_CHAIN)
 
 
 # ---- bench.py's "reference-equivalent" CPU leg (oracle/ref_equiv.c): the chain with FFTW3f + VOLK found by dlopen()
@@ -439,3 +445,75 @@ class RefSegmentDetection(_RefSink):
     def __init__(self, ID, blocklen, relinvovl, seg_start, seg_stop, thresh, minchandist, puffer, maxblocks, delay, threads=False):
         self._take(_ref_sinks().ref_sd_create(ID, blocklen, relinvovl, seg_start, seg_stop, thresh, minchandist, puffer, maxblocks,
                                               delay, int(threads)), blocklen)
+
+
+# ---- the reference's OWN throughput-chain blocks (oracle/_ref/libref_chain.so: lib/*_impl.cc compiled where they lie, oracle/ref_chain_driver.cpp) ----
+_refc = None
+
+
+def _ref_chain():
+    global _refc
+    if _refc is None:
+        h = C.CDLL(_REF_CHAIN)
+        h.ref_chain_last_error.restype = C.c_char_p
+        h.ref_overlap_save_create.restype = C.c_void_p
+        h.ref_overlap_save_create.argtypes = [C.c_int, C.c_int, C.c_int]
+        h.ref_vector_cut_create.restype = C.c_void_p
+        h.ref_vector_cut_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
+        h.ref_phase_window_create.restype = C.c_void_p
+        h.ref_phase_window_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int]
+        h.ref_chain_destroy.argtypes = [C.c_void_p]
+        h.ref_chain_work.restype = C.c_int
+        h.ref_chain_work.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        _refc = h
+    return _refc
+
+
+class _RefChainBlock:
+    """work(input) -> output: ONE call of the block's own work() over all whole items of `input` (in_bytes per item in, out_bytes per
+    item out); state (overlap history, window counter) is the block's and crosses the calls."""
+
+    def _take(self, handle, in_bytes, out_bytes):
+        if not handle:
+            raise ValueError(_ref_chain().ref_chain_last_error().decode())
+        self._h, self.in_bytes, self.out_bytes = handle, int(in_bytes), int(out_bytes)
+
+    def work(self, inp):
+        inp = np.ascontiguousarray(inp)
+        if inp.nbytes % self.in_bytes:
+            raise ValueError("input is not a whole number of items")
+        n = inp.nbytes // self.in_bytes
+        out = np.empty(n * self.out_bytes, dtype=np.uint8)
+        if n == 0:                                   # the scheduler never calls work() for nothing (overlap_save would read behind `in`)
+            return out.view(inp.dtype)
+        r = _ref_chain()
+        if r.ref_chain_work(self._h, n, inp.ctypes.data, out.ctypes.data) != n:
+            raise RuntimeError(r.ref_chain_last_error().decode())
+        return out.view(inp.dtype) if out.nbytes % inp.dtype.itemsize == 0 else out
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            _ref_chain().ref_chain_destroy(self._h)
+            self._h = None
+
+
+class RefOverlapSave(_RefChainBlock):
+    """The reference's overlap_save::make(itemsize, outputlen, overlaplen)."""
+
+    def __init__(self, itemsize, outputlen, overlaplen):
+        self._take(_ref_chain().ref_overlap_save_create(itemsize, outputlen, overlaplen), itemsize * (outputlen - overlaplen), itemsize * outputlen)
+
+
+class RefVectorCut(_RefChainBlock):
+    """The reference's vector_cut_vxx::make(itemsize, veclen, offset, blocklen)."""
+
+    def __init__(self, itemsize, veclen, offset, blocklen):
+        self._take(_ref_chain().ref_vector_cut_create(itemsize, veclen, offset, blocklen), itemsize * veclen, itemsize * blocklen)
+
+
+class RefPhaseWindow(_RefChainBlock):
+    """The reference's phase_shifting_windowing_vcc::make(blocklen, numphasestates, shifts, passbw, stopbw, windowtype); ValueError with the
+    constructor's own message where it throws std::invalid_argument."""
+
+    def __init__(self, blocklen, numphasestates, shifts, passbw, stopbw, windowtype):
+        self._take(_ref_chain().ref_phase_window_create(blocklen, numphasestates, shifts, passbw, stopbw, windowtype), 8 * blocklen, 8 * blocklen)

@@ -79,7 +79,9 @@ def multicarrier(N, chans, nsamp, seed, noise=0.1):
 
 
 def numpy_chain(N, R, wintype, chans, x):
-    """App. A.1-A.4 with numpy.fft (complex128), float32 at the reference's stage boundaries."""
+    """App. A.1-A.4 with numpy.fft (complex128), float32 at the reference's stage boundaries.  A restatement by reading, kept because it
+    documents the algorithm line by line; the reference's own run (oracle/ref_hier.py, tests/test_hier_reference_cpu.py) now judges the
+    oracle that this function cross-checks, and so this function too."""
     ovl = N // R
     H = N - ovl
     nb = x.size // H
