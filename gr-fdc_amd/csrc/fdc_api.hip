@@ -1260,36 +1260,33 @@ static int launch_bank(fdc_pipeline *p, const fdc_pipeline::Bank &bk, const floa
                        unsigned out_bytes, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1, int fmt = 0, float scale = 1.0f, const void *raw = nullptr,
                        int ofmt = 0, float oscale = 1.0f, void *oq = nullptr)
 {
-    const bool half = bk.r == bk.L / 2;
+    fdc::BlockLaunch b{};
+    b.in = in0; b.in_stride = (size_t)p->H; b.out = o;
+    b.nb_chunk = nb; b.mbase = m0; b.nb_call = nblocks;
+    b.slot_off = bk.d_slot_off; b.out_bytes = out_bytes;
+    b.ncu = p->ncu - p->reserved_cu; b.hints = p->block_hints;
+    b.s = s; b.ev_start = ev0; b.ev_stop = ev1;
+    b.N = p->N; b.R = p->R; b.scratch = p->d_fscr;
+    b.L = bk.L; b.r = bk.r; b.first_block = first_block + m0;
+    b.cbt = bk.d_cbt; b.shn = bk.d_shn; b.tab = bk.d_tab;
+    b.tw256 = p->d_tw256;
+    b.twq = bk.L == 512 ? p->d_twq512 : bk.L == 1024 ? p->d_twq1k : p->d_twq;
+    b.twl = bk.L == 512 ? p->d_tw512 : bk.L == 1024 ? p->d_tw1k : nullptr;
     if (ofmt) {
         if (bk.L != 256) return fail(FDC_ERR_UNSUPPORTED, "integer stores in a %d-bin bank", bk.L);
-        HIPCHK(fdc::launch_poly_block_oq(fmt, scale, fmt ? raw : static_cast<const void *>(in0), (size_t)p->H, ofmt, oscale, oq, nb, m0, nblocks, p->d_tw256,
-                                         p->d_twq, bk.d_cbt, bk.d_shn, bk.d_slot_off, out_bytes, p->ncu - p->reserved_cu, p->block_hints, s, bk.r,
-                                         first_block + m0, ev0, ev1, p->R, p->d_fscr, p->N));
+        HIPCHK(fdc::launch_poly_block_oq(b, fmt, scale, fmt ? raw : static_cast<const void *>(in0), ofmt, oscale, oq));
         return FDC_OK;
     }
     if (fmt) {
         if (bk.L != 256) return fail(FDC_ERR_UNSUPPORTED, "integer loads in a %d-bin bank", bk.L);
-        HIPCHK(fdc::launch_poly_block_iq(fmt, scale, raw, (size_t)p->H, o, nb, m0, nblocks, p->d_tw256, p->d_twq, bk.d_cbt, bk.d_shn, bk.d_slot_off, out_bytes,
-                                         p->ncu - p->reserved_cu, p->block_hints, s, bk.r, first_block + m0, ev0, ev1, p->R, p->d_fscr, p->N));
+        HIPCHK(fdc::launch_poly_block_iq(b, fmt, scale, raw));
         return FDC_OK;
     }
     switch (bk.L) {
-    case 256:
-        HIPCHK(fdc::launch_poly_block(in0, (size_t)p->H, o, nb, m0, nblocks, p->d_tw256, p->d_twq, bk.d_cbt, bk.d_shn, bk.d_slot_off, out_bytes, p->ncu - p->reserved_cu,
-                                      p->block_hints, s, bk.r, first_block + m0, ev0, ev1, p->R, p->d_fscr, p->N));
-        break;
-    case 512:
-        HIPCHK(fdc::launch_poly_block512(in0, (size_t)p->H, o, nb, m0, nblocks, p->d_tw256, p->d_tw512, p->d_twq512, bk.d_cbt, bk.d_shn, bk.d_slot_off,
-                                         out_bytes, p->ncu - p->reserved_cu, p->block_hints, s, ev0, ev1, p->R, p->d_fscr, half, p->N));
-        break;
-    case 1024:
-        HIPCHK(fdc::launch_poly_block1024(in0, (size_t)p->H, o, nb, m0, nblocks, p->d_tw256, p->d_tw1k, p->d_twq1k, bk.d_cbt, bk.d_shn, bk.d_slot_off,
-                                          out_bytes, p->ncu - p->reserved_cu, p->block_hints, s, ev0, ev1, half, p->R, p->d_fscr, p->N));
-        break;
-    default:
-        HIPCHK(fdc::launch_poly_block_narrow(bk.L, in0, (size_t)p->H, o, nb, m0, nblocks, bk.d_tab, bk.d_cbt, bk.d_slot_off, out_bytes, p->ncu - p->reserved_cu,
-                                             p->block_hints, s, ev0, ev1, p->R, p->d_fscr, bk.r, p->N));
+    case 256: HIPCHK(fdc::launch_poly_block(b)); break;
+    case 512: HIPCHK(fdc::launch_poly_block512(b)); break;
+    case 1024: HIPCHK(fdc::launch_poly_block1024(b)); break;
+    default: HIPCHK(fdc::launch_poly_block_narrow(b));
     }
     return FDC_OK;
 }

@@ -1,8 +1,8 @@
 // gfx950 one-block-per-CU form of the uniform-plan path for channels of l = 1024 bins (N = 65536 = 1024 rows x 64 columns, R = 2, every
 // channel on the 1024-bin grid, one window): fdc_block512.hip taken one step further — a column's 1024 rows split into FOUR PHASES
 // n2 = 4 mu + rho, each a 256-point sub-sequence that is exactly a "column" of fdc_block256.hip.  A quad of lanes is the four phases of ONE
-// column; all four run the 256-point transforms of the old stage 1 in lockstep, and the radix-4 layers that join them are two DPP exchanges
-// inside the quad (lane ^ 2, a -j / +j on lane 3, lane ^ 1):
+// column; all four run the 256-point transforms of stage 1 (strip_fft256 / strip_ifft256, fdc_blockcommon.hpp) in lockstep, and the radix-4 layers
+// that join them are two DPP exchanges inside the quad (quad_xor2, a -j / +j on lane 3, quad_xor1):
 //     forward (decimation in time):  A[kap + 256 i] = sum_rho W_4^(i rho) (W_1024^(kap rho) E_rho[kap])          kap = 0 .. 255
 //                                    natural phase order in, lane lam holds i = bit-swapped lam afterwards
 //     product: shape[k2]/N (-1)^n1 W_N^(n1 k2), k2 = kap + 256 i, all of it before the inverse layer (its i part differs between the lanes that
@@ -17,41 +17,16 @@
 // samples of one channel.
 //
 // The arithmetic is that of k_p1g + k_p2g (fdc_kernels.hip) regrouped; parity against the oracle: tests/test_parity_gpu.py.
-#include <hip/hip_ext.h>
-#include <type_traits>
-#include "fdc_kernels.h"
-#include "fdc_radix16.hpp"
-#include "fdc_devutil.hpp"
+#include "fdc_blockcommon.hpp"
 
 namespace fdc {
 
 extern __shared__ __attribute__((aligned(16))) unsigned char fdc_smem_b1k[];
 
-__device__ __forceinline__ unsigned long long pack1k(cf v) { return ((unsigned long long)__float_as_uint(v.y) << 32) | __float_as_uint(v.x); }
-__device__ __forceinline__ cf unpack1k(unsigned long long u) { return mk(__uint_as_float((unsigned)u), __uint_as_float((unsigned)(u >> 32))); }
-#if defined(__HIP_DEVICE_COMPILE__)
-#define FDC_PLAIN_DS1K __attribute__((target("no-load-store-opt")))
-#else
-#define FDC_PLAIN_DS1K
-#endif
-
-__device__ __forceinline__ cf q1k_xor1(cf x)
-{
-    return mk(__int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x.x), 0xB1, 0xF, 0xF, true)),
-              __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x.y), 0xB1, 0xF, 0xF, true)));
-}
-__device__ __forceinline__ cf q1k_xor2(cf x)
-{
-    return mk(__int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x.x), 0x4E, 0xF, 0xF, true)),
-              __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x.y), 0x4E, 0xF, 0xF, true)));
-}
-
 // LDS map (bytes).  The block length is a template parameter (round 5): N = 1024 rows x (8 P) columns, P = 2, 4, 8 passes of 8 columns: N = 16384, 32768,
 // 65536; the channel slots are the columns N1 = 8 P.  Stage 1 depends on P through the row pitch and the table sizes only; G is 8 P registers per lane;
 // stage 2 is a DFT-P over the pass index in registers, one trip through LDS ([1024 / P rows][P klo][8 c3]: P = 8: 128 rows, four trips for the 512 kept
 // rows; P = 2: all 512 in one) and the same DFT-8 over c3; a wave reads (klo = wave mod P, 128-row block = wave div P).
-constexpr int kKScrPts = 1084;                                   // per-wave exchange strip, as in fdc_block256.hip
-constexpr int kKOffX = 8 * kKScrPts * 8;                         // 69376: end of the strips
 // Round 5 (41 % of this kernel's LDS cycles were bank conflicts, profiles/r05/NOTES.md section 5): the four lanes of a quad read the rows (rho, b) /
 // (i, b) of these two tables in ONE instruction, and with rho / i strides of whole multiples of 64 dwords all four fell on the same banks (4-way).
 // T1k: rho stride 296 points (592 dwords = 4 windows of 4 dwords mod 16): the 4 x 4 rows of a 16-byte read's lane group on 16 different windows.
@@ -73,7 +48,7 @@ struct B1kGeom {
     static constexpr int kLd = P * 8 + 2;                         // trip rows: [P klo][8 c3] + 2 (row stride 132 / 68 / 36 dwords: 4 x an odd number: a 16-byte read's
                                                                   // consecutive rows on different 4-dword windows)
     static constexpr int kTrip = kTripRows * kLd * 8;             // P = 8: 67584 (below the strips' end); 4: 69632; 2: 73728
-    static constexpr int kOffCt = kTrip > kKOffX ? kTrip : kKOffX;   // [8 c3][P klo]  W_N1^(c3 klo): behind the strips and the trip buffer
+    static constexpr int kOffCt = kTrip > kStripsEnd ? kTrip : kStripsEnd;   // [8 c3][P klo]  W_N1^(c3 klo): behind the strips and the trip buffer
     static constexpr int kOffWrow = kOffCt + 8 * P * 8;           // [16][18]  W_256^(b p)
     static constexpr int kOffT1k = kOffWrow + 16 * 18 * 8;        // [4 rho][16 b][18]  W_1024^(rho (b + 16 q))
     static constexpr int kOffB = kOffT1k + 4 * kKT1kRho * 8;      // [N1 n1][18]  W_N^(16 n1 q)
@@ -85,14 +60,6 @@ struct B1kGeom {
     static_assert(kLds <= 160 * 1024, "LDS budget");
     static_assert((kLd * 2) % 8 == 4, "trip rows an odd number of 4-dword windows apart");
 };
-template <int P> __device__ __forceinline__ constexpr int b1k_pass_idx(int k) { return P == 8 ? 4 * (k & 1) + (k >> 1) : k; }
-template <int P>
-__device__ __forceinline__ void b1k_pass_dft(cf (&a)[P])
-{
-    if constexpr (P == 8) dft8<false>(a);                          // klo = k0 + 2 k1 in a[4 k0 + k1]
-    else if constexpr (P == 4) dft4<false>(a[0], a[1], a[2], a[3]);
-    else { const cf s0 = a[0] + a[1], d0 = a[0] - a[1]; a[0] = s0; a[1] = d0; }
-}
 
 // The rows reach the lanes through LDS.  One column per wave means a wave's own load instruction would be 64 single samples from 64 rows
 // (64 cache lines); staged, the workgroup's eight waves fetch the pass's 8 columns x 1024 rows in 16-byte pieces of whole 64-byte row segments (wave w:
@@ -102,7 +69,7 @@ __device__ __forceinline__ void b1k_pass_dft(cf (&a)[P])
 // phases stay in the G registers as for R = 2 (output rows 256 ..); the rows 64 <= m < 128 go to 128 KiB of per-workgroup scratch ([pass][q - 4][thread]:
 // the L2 holds it) and come back for a second, 256-row run of stage 2 (output rows 0 .. 255), as in fdc_block512.hip.
 template <bool NT, bool R4, int P = 8>
-__global__ FDC_PLAIN_DS1K __launch_bounds__(512) void k_blk1024(const float2 *__restrict__ in, size_t in_stride, float2 *__restrict__ out,
+__global__ FDC_PLAIN_DS __launch_bounds__(512) void k_blk1024(const float2 *__restrict__ in, size_t in_stride, float2 *__restrict__ out,
                                                       const float2 *__restrict__ tw256, const float2 *__restrict__ tw1024 /* W_1024^k, k < 1024 */,
                                                       const float2 *__restrict__ twq /* [n1][16] W_N^(16 n1 q) */,
                                                       const float2 *__restrict__ cbt /* [n1][64] (-1)^n1 W_N^(n1 (b + 256 i)) at b + 16 i */,
@@ -127,9 +94,7 @@ __global__ FDC_PLAIN_DS1K __launch_bounds__(512) void k_blk1024(const float2 *__
     const int w = tid >> 6, lane = tid & 63, rho = lane & 3, b = lane >> 2;
     const int iq = ((rho & 1) << 1) | (rho >> 1);                         // the quarter i of k2 this lane holds between the two radix-4 layers
 
-    const int grid = gridDim.x, per = grid >> 3;
-    const bool xmap = (grid & 7) == 0;
-    const int first = xmap ? (int)(blockIdx.x & 7) * per + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
+    const int grid = gridDim.x, first = xcd_first_block();
     if (first >= nb) return;
 
     constexpr unsigned inbytes = (unsigned)GM::kN * 8u;
@@ -175,8 +140,8 @@ __global__ FDC_PLAIN_DS1K __launch_bounds__(512) void k_blk1024(const float2 *__
     }
     __syncthreads();
 
-    float2 *const scrw = scr + w * kKScrPts + lane;
-    const float2 *const scrr = scr + w * kKScrPts + rho + 68 * b;
+    float2 *const scrw = scr + w * kStripPts + lane;
+    const float2 *const scrr = scr + w * kStripPts + rho + 68 * b;
     const float2 *const wr = wrow + b * 18;
     const float2 *const t1r = t1k + rho * kKT1kRho + b * 18;
     const float2 *const btw = Bt + w * 18;                                // + pass * 8 rows
@@ -203,24 +168,9 @@ __global__ FDC_PLAIN_DS1K __launch_bounds__(512) void k_blk1024(const float2 *__
             stage_write();
             stage_load(ps < P - 2 ? m : mnext, (ps + 2) & (P - 1));
             cbn = bld2(rcb, voffc, (unsigned)((ps + 1) & (P - 1)) * 4096u);
-            // ---- the 256-point forward transform of this lane's phase: exactly the old stage 1
-            dft16<false>(cur);
-            {
-                cf tw[16];
-#pragma unroll
-                for (int i = 0; i < 8; i++) {
-                    const float4 t = ld4(&wr[2 * i]);
-                    tw[2 * i] = mk(t.x, t.y); tw[2 * i + 1] = mk(t.z, t.w);
-                }
-                st2(&scrw[0], cur[rev16(0)]);
-#pragma unroll
-                for (int p = 1; p < 16; p++) st2(&scrw[68 * p], cmul(cur[rev16(p)], tw[p]));
-            }
-            __builtin_amdgcn_wave_barrier();
+            // ---- the 256-point forward transform of this lane's phase
             cf v[16];
-#pragma unroll
-            for (int bb = 0; bb < 16; bb++) v[bb] = ld2(&scrr[4 * bb]);
-            dft16<false>(v);                                      // E_rho at kap = b + 16 q in v[rev16(q)]
+            strip_fft256(cur, v, wr, scrw, scrr);                 // E_rho at kap = b + 16 q in v[rev16(q)]
             // ---- forward radix-4 layer, product, inverse radix-4 layer: two values at a time, 16-byte table reads
             cf u[16];
             {
@@ -235,40 +185,23 @@ __global__ FDC_PLAIN_DS1K __launch_bounds__(512) void k_blk1024(const float2 *__
                     for (int e = 0; e < 2; e++) {
                         const int q = 2 * g2 + e;
                         cf x = cmul(v[rev16(q)], w1s[e]);                            // E_rho W_1024^(kap rho)
-                        x = q1k_xor2(x) + x * sg2;                                   // lanes 0, 1: x_rho + x_(rho+2); lanes 2, 3: x_(rho-2) - x_rho
+                        x = quad_xor2(x) + x * sg2;                                   // lanes 0, 1: x_rho + x_(rho+2); lanes 2, 3: x_(rho-2) - x_rho
                         x = rot ? mk(x.y, -x.x) : x;                                 // lane 3: -j
-                        x = q1k_xor1(x) + x * sg1;                                   // A[kap + 256 iq]
+                        x = quad_xor1(x) + x * sg1;                                   // A[kap + 256 iq]
                         // shape / N, W_N^(16 n1 q), (-1)^n1 W_N^(n1 (b + 256 iq)) = cb
                         cf y = cmul(cmul(x, bps[e]), cb) * shs[e];
-                        y = q1k_xor1(y) + y * sg1;                                   // lanes (0, 1) hold quarters 0, 2; lanes (2, 3) quarters 1, 3
+                        y = quad_xor1(y) + y * sg1;                                   // lanes (0, 1) hold quarters 0, 2; lanes (2, 3) quarters 1, 3
                         y = rot ? mk(-y.y, y.x) : y;                                 // lane 3: +j
-                        y = q1k_xor2(y) + y * sg2;                                   // sum_i W_4^(-i rho) U[kap + 256 i] in lane rho
+                        y = quad_xor2(y) + y * sg2;                                   // sum_i W_4^(-i rho) U[kap + 256 i] in lane rho
                         u[q] = cmulc(y, w1s[e]) * osg;                               // conj(W_1024^(kap rho)), and (-1)^rho: the ifftshift
                     }
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
             // ---- the 256-point inverse transform of this lane's phase (no q ^ 8: the shift was the sign above)
-            dft16<true>(u);
-            {
-                cf tw[16];
+            strip_ifft256(u, wr, scrw, scrr);                     // g[4 m + rho], m = b + 16 q in u[rev16(q)]; keep q >= 8
 #pragma unroll
-                for (int i = 0; i < 8; i++) {
-                    const float4 t = ld4(&wr[2 * i]);
-                    tw[2 * i] = mk(t.x, t.y); tw[2 * i + 1] = mk(t.z, t.w);
-                }
-#pragma unroll
-                for (int p = 1; p < 16; p++) u[rev16(p)] = cmulc(u[rev16(p)], tw[p]);
-            }
-            __builtin_amdgcn_wave_barrier();
-#pragma unroll
-            for (int p = 0; p < 16; p++) st2(&scrw[68 * p], u[rev16(p)]);
-            __builtin_amdgcn_wave_barrier();
-#pragma unroll
-            for (int bb = 0; bb < 16; bb++) u[bb] = ld2(&scrr[4 * bb]);
-            dft16<true>(u);                                       // g[4 m + rho], m = b + 16 q in u[rev16(q)]; keep q >= 8
-#pragma unroll
-            for (int j = 0; j < 8; j++) G[j][ps] = pack1k(u[rev16(8 + j)]);
+            for (int j = 0; j < 8; j++) G[j][ps] = pack_cf(u[rev16(8 + j)]);
             if constexpr (R4) {                                   // R = 4 keeps q >= 4: m = 64 .. 127 go to the scratch, [pass][q - 4][thread]
 #pragma unroll
                 for (int j = 0; j < 4; j++) bst2(rscr, (unsigned)tid * 8u + (unsigned)j * 4096u, (unsigned)ps * 16384u, u[rev16(4 + j)]);
@@ -314,11 +247,11 @@ __global__ FDC_PLAIN_DS1K __launch_bounds__(512) void k_blk1024(const float2 *__
                     cf a[P];
 #pragma unroll
                     for (int ps = 0; ps < P; ps++) a[ps] = src[jj][ps];
-                    b1k_pass_dft<P>(a);
+                    pass_dft<P>(a);
                     float2 *const g = gw + jj * 64 * kKLd;
                     st2(&g[0], a[0]);
 #pragma unroll
-                    for (int k = 1; k < P; k++) st2(&g[8 * k], cmul(a[b1k_pass_idx<P>(k)], ct[k]));
+                    for (int k = 1; k < P; k++) st2(&g[8 * k], cmul(a[pass_idx<P>(k)], ct[k]));
                 }
                 __builtin_amdgcn_sched_barrier(0);
                 __syncthreads();                                      // the trip is in LDS
@@ -349,7 +282,7 @@ __global__ FDC_PLAIN_DS1K __launch_bounds__(512) void k_blk1024(const float2 *__
                 __builtin_amdgcn_sched_barrier(0);
             }
         };
-        stage2([&](int j, int ps) { return unpack1k(G[j][ps]); }, R4 ? 256 : 0, std::integral_constant<int, 8>{});
+        stage2([&](int j, int ps) { return unpack_cf(G[j][ps]); }, R4 ? 256 : 0, std::integral_constant<int, 8>{});
         if constexpr (R4) {
             // m = 64 .. 127 = output rows 0 .. 255: this lane's own stores, served by the L2
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -367,38 +300,24 @@ bool poly_block1024_supports(int N, int R)
 hipError_t init_block1024_kernels()
 {
     hipError_t e = hipSuccess;
-#define FDC_SET1K(A, C, P) \
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_blk1024<A, C, P>), hipFuncAttributeMaxDynamicSharedMemorySize, B1kGeom<P>::kLds);
-#define FDC_SET1KP(P) FDC_SET1K(true, false, P) FDC_SET1K(false, false, P) FDC_SET1K(true, true, P) FDC_SET1K(false, true, P)
-    FDC_SET1KP(8) FDC_SET1KP(4) FDC_SET1KP(2)
-#undef FDC_SET1KP
-#undef FDC_SET1K
+    for_block_variants(kEvery, kEvery, kEvery, [&](auto NT, auto R4, auto P) {
+        if (e == hipSuccess) e = set_block_lds(reinterpret_cast<const void *>(k_blk1024<NT() != 0, R4() != 0, P()>), B1kGeom<P()>::kLds);
+    });
     return e;
 }
 
-hipError_t launch_poly_block1024(const float2 *in, size_t in_stride, float2 *out, int nb_chunk, int mbase, int nb_call, const float2 *tw256,
-                                 const float2 *tw1024, const float2 *twq, const float2 *cbt, const float *shn, const long long *slot_off,
-                                 unsigned out_bytes, int ncu, int hints, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop, bool half, int R,
-                                 float2 *scratch, int N)
+hipError_t launch_poly_block1024(const BlockLaunch &b)
 {
-    if (nb_chunk <= 0) return hipSuccess;
-    if (!poly_block1024_supports(N, R) || (R == 4 && !scratch)) return hipErrorInvalidValue;
-    int grid = ncu > 0 ? ncu : 256;
-    if (grid > nb_chunk) grid = nb_chunk;
-#define FDC_L1K(A, C, P) \
-    hipExtLaunchKernelGGL((k_blk1024<A, C, P>), dim3((unsigned)grid), dim3(512), B1kGeom<P>::kLds, s, ev_start, ev_stop, 0u, in, in_stride, \
-                          out, tw256, tw1024, twq, cbt, shn, slot_off, (long long)mbase * (C ? 768 : 512), (long long)nb_call, out_bytes, nb_chunk, hints, \
-                          half ? 1 : 0, C ? scratch : (float2 *)nullptr)
-    const bool nt = (hints & 1) != 0;
-#define FDC_L1KP(P) \
-    do { \
-        if (R == 4) { if (nt) FDC_L1K(true, true, P); else FDC_L1K(false, true, P); } \
-        else { if (nt) FDC_L1K(true, false, P); else FDC_L1K(false, false, P); } \
-    } while (0)
-    if (N == 65536) FDC_L1KP(8); else if (N == 32768) FDC_L1KP(4); else FDC_L1KP(2);
-#undef FDC_L1KP
-#undef FDC_L1K
-    return hipGetLastError();
+    if (b.nb_chunk <= 0) return hipSuccess;
+    if (!poly_block1024_supports(b.N, b.R) || (b.R == 4 && !b.scratch) || (b.r != 0 && !b.half())) return hipErrorInvalidValue;
+    hipError_t e = hipErrorInvalidValue;                        // stays if no instantiation matches
+    for_block_variants(b.hints & 1, b.R == 4, b.N / 8192, [&](auto NT, auto R4, auto P) {
+        hipExtLaunchKernelGGL((k_blk1024<NT() != 0, R4() != 0, P()>), dim3((unsigned)b.grid()), dim3(512), B1kGeom<P()>::kLds, b.s, b.ev_start, b.ev_stop, 0u,
+                              b.in, b.in_stride, b.out, b.tw256, b.twl, b.twq, b.cbt, b.shn, b.slot_off, (long long)b.mbase * (R4() ? 768 : 512),
+                              (long long)b.nb_call, b.out_bytes, b.nb_chunk, b.hints, b.half() ? 1 : 0, R4() ? b.scratch : (float2 *)nullptr);
+        e = hipGetLastError();
+    });
+    return e;
 }
 
 }  // namespace fdc

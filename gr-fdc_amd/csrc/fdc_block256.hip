@@ -29,11 +29,7 @@
 //
 // The arithmetic is the uniform-plan commutation of fdc_fast256.hip (same tables, same rounding points), so the
 // result matches k_p1 + k_p2 to the last few ulps; parity against the oracle: tests/test_parity_gpu.py.
-#include <hip/hip_ext.h>
-#include <type_traits>
-#include "fdc_kernels.h"
-#include "fdc_radix16.hpp"
-#include "fdc_devutil.hpp"
+#include "fdc_blockcommon.hpp"
 #include "fdc_iq.hpp"
 
 namespace fdc {
@@ -41,15 +37,6 @@ namespace fdc {
 extern __shared__ __attribute__((aligned(16))) unsigned char fdc_smem_blk[];
 
 typedef unsigned long long u8v __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ unsigned long long pack_cf(cf v) { return ((unsigned long long)__float_as_uint(v.y) << 32) | __float_as_uint(v.x); }
-__device__ __forceinline__ cf unpack_cf(unsigned long long u) { return mk(__uint_as_float((unsigned)u), __uint_as_float((unsigned)(u >> 32))); }
-// The SI load/store optimizer would pair the exchange reads into ds_read2_b64, which moves 128 B/clk where
-// ds_read_b64 moves 256 (MI355X_MICROARCH.md, LDS table): switched off for this kernel (device pass only).
-#if defined(__HIP_DEVICE_COMPILE__)
-#define FDC_PLAIN_DS __attribute__((target("no-load-store-opt")))
-#else
-#define FDC_PLAIN_DS
-#endif
 
 // The block length is a template parameter: N = 256 rows x (32 P) columns with P = 2, 4, 8 passes of 32 columns, i.e. N = 16384,
 // 32768, 65536; the number of channel slots is the number of columns N1 = 32 P.  Stage 1 does not depend on P except through the row
@@ -57,9 +44,7 @@ __device__ __forceinline__ cf unpack_cf(unsigned long long u) { return mk(__uint
 // trip through LDS and the same DFT-32 over c5.  With P < 8 a trip holds all 128 rows of a run (P = 8: 64) and a wave reads
 // (klo = wave mod P, row half = wave div P).
 //
-// LDS map (bytes).  Stage-1 scratch: per wave 68*15 + 64 = 1084 points (element (p; lane) at lane + 68 p).
-constexpr int kBlkScrPts = 1084;
-constexpr int kBlkOffX = 8 * kBlkScrPts * 8;                      // 69376: end of the stage-1 strips
+// LDS map (bytes).  Stage-1 scratch: the eight per-wave exchange strips (fdc_blockcommon.hpp), kStripsEnd bytes.
 template <int P>
 struct BlkGeom {
     static_assert(P == 2 || P == 4 || P == 8, "passes of 32 columns: N = 16384, 32768 or 65536");
@@ -74,7 +59,7 @@ struct BlkGeom {
     // P = 2: 32 P + 2 (4 dwords mod 64: as clean for the reads), which brings the workgroup under half of the LDS: two workgroups per CU
     static constexpr int kLd = P == 2 ? 32 * P + 2 : 32 * P + 6;
     static constexpr int kTripBytes = 16 * kJT * kLd * 8;         // P = 8: 134144
-    static constexpr int kOffCt = kTripBytes > kBlkOffX ? kTripBytes : kBlkOffX;   // stage-2 twiddles [32][P], behind the trip buffer and the strips
+    static constexpr int kOffCt = kTripBytes > kStripsEnd ? kTripBytes : kStripsEnd;   // stage-2 twiddles [32][P], behind the trip buffer and the strips
     static constexpr int kOffWrow = P == 8 ? 136960 : kOffCt + 32 * P * 8;   // tables: above the strips and the trip buffer
     static constexpr int kOffB = kOffWrow + 16 * 18 * 8;
     static constexpr int kOffSA = kOffB + 32 * 18 * 8;
@@ -84,7 +69,7 @@ struct BlkGeom {
     static constexpr int kOffWrowF = kOffSoffOff + kN1 * 4;
     static constexpr int kLdsOff = kOffWrowF + 16 * 18 * 8;       // P = 8: 163584 <= 163840
     static_assert(kLdsOff <= 160 * 1024 && kLds <= 160 * 1024, "LDS budget");
-    static_assert(kOffCt >= kBlkOffX && kOffCt + 32 * P * 8 <= kOffWrow, "stage-2 trip buffer and twiddles below the tables, tables above the strips");
+    static_assert(kOffCt >= kStripsEnd && kOffCt + 32 * P * 8 <= kOffWrow, "stage-2 trip buffer and twiddles below the tables, tables above the strips");
     static_assert((16 * (kJB - 1) * kLd + 32 * (P - 1)) * 8 < 65536, "ds offsets of a base register");
 };
 
@@ -104,20 +89,6 @@ struct BlkGeom {
 // quarters of every inverse transform are kept, G is 192 rows x N1 columns.  The rows t >= 128 stay in the G registers
 // as for R = 2; the rows 64 <= t < 128 take the route of the forward-transform variant: per-workgroup scratch (L2),
 // read back for a third, 64-row run of stage 2.  Off the grid (OFF) the window phase counter runs: a constant j^p per block in cb.
-
-// DFT over the pass index (the register index of G): P points in place; the result X[k] is read through blk_pass_idx<P>(k)
-template <int P> __device__ __forceinline__ constexpr int blk_pass_idx(int k) { return P == 8 ? 4 * (k & 1) + (k >> 1) : k; }
-template <int P>
-__device__ __forceinline__ void blk_pass_dft(cf (&a)[P])
-{
-    if constexpr (P == 8) dft8<false>(a);                          // klo = k0 + 2 k1 in a[4 k0 + k1]
-    else if constexpr (P == 4) {                                   // natural order
-        dft4<false>(a[0], a[1], a[2], a[3]);
-    } else {
-        const cf s0 = a[0] + a[1], d0 = a[0] - a[1];
-        a[0] = s0; a[1] = d0;
-    }
-}
 
 // HALF = true: every channel half a slot higher (f = 256 slot + 128: a bank centred on multiples of 256 bins) WITHOUT the offset machinery.  The block
 // modulated by exp(-2 pi i 128 n / N) = W_N^(128 n1) (-1)^n2: the (-1)^n2 moves every column's spectrum by half its length, which together with the
@@ -168,11 +139,7 @@ __global__ FDC_PLAIN_DS __launch_bounds__(512, (P == 2 && !OFF && !R4 && !FWD) ?
         for (int q = 0; q < 4; q++) mqs[q] = keep[wu * 4 + q];
     }
 
-    // block order: round rho, XCD x = workgroup mod 8 (round-robin dispatch), slot = workgroup / 8:
-    // block = rho*grid + x*(grid/8) + slot, i.e. one XCD works on grid/8 consecutive blocks at a time
-    const int grid = gridDim.x, per = grid >> 3;
-    const bool xmap = (grid & 7) == 0;
-    const int first = xmap ? (int)(blockIdx.x & 7) * per + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
+    const int grid = gridDim.x, first = xcd_first_block();
     if (first >= nb) return;
 
     constexpr unsigned inbytes = (unsigned)GM::kN * kEs;
@@ -224,8 +191,8 @@ __global__ FDC_PLAIN_DS __launch_bounds__(512, (P == 2 && !OFF && !R4 && !FWD) ?
     }
     __syncthreads();
 
-    float2 *const scrw = scr + w * kBlkScrPts + lane;             // exchange write base: element p at + 68 p
-    const float2 *const scrr = scr + w * kBlkScrPts + col + 68 * b;   // exchange read base: element bb at + 4 bb
+    float2 *const scrw = scr + w * kStripPts + lane;             // exchange write base: element p at + 68 p
+    const float2 *const scrr = scr + w * kStripPts + col + 68 * b;   // exchange read base: element bb at + 4 bb
     const float2 *const wr = wrow + b * 18;
     const float2 *const wrf = wrowF + b * 18;
     const float2 *const btr = Bt + c5 * 18;
@@ -303,8 +270,7 @@ __global__ FDC_PLAIN_DS __launch_bounds__(512, (P == 2 && !OFF && !R4 && !FWD) ?
             }
             __builtin_amdgcn_wave_barrier();                      // same wave, in-order LDS queue: no s_barrier
             cf v[16];
-#pragma unroll
-            for (int bb = 0; bb < 16; bb++) v[bb] = ld2(&scrr[4 * bb]);
+            strip_get(v, scrr);
             if constexpr (FWD) {
                 // round-2..5 form: T[k2 = b + 16 q][n1] = A[k2] W_N^(n1 k2) / N.  The half q < 8 stays in the G registers, the half q >= 8 goes to this
                 // workgroup's 256 KiB of scratch ([pass][j][thread]: 512-byte wave stores) and comes back for the second run of stage 2
@@ -343,12 +309,7 @@ __global__ FDC_PLAIN_DS __launch_bounds__(512, (P == 2 && !OFF && !R4 && !FWD) ?
                 u[rev16(0)] = cmul(u[rev16(0)], cb);
 #pragma unroll
                 for (int p = 1; p < 16; p++) u[rev16(p)] = cmul(cmulc(u[rev16(p)], tw[p]), cb);
-                __builtin_amdgcn_wave_barrier();
-#pragma unroll
-                for (int p = 0; p < 16; p++) st2(&scrw[68 * p], u[rev16(p)]);
-                __builtin_amdgcn_wave_barrier();
-#pragma unroll
-                for (int bb = 0; bb < 16; bb++) u[bb] = ld2(&scrr[4 * bb]);
+                strip_trip(u, scrw, scrr);
                 dft16<true>(u);                                       // y[t = b + 16 q] in u[rev16(q)]; keep q >= 8 (R = 2)
 #pragma unroll
                 for (int j = 0; j < 8; j++) FDC_GPUT(j, ps, u[rev16(8 + j)]);
@@ -426,11 +387,11 @@ __global__ FDC_PLAIN_DS __launch_bounds__(512, (P == 2 && !OFF && !R4 && !FWD) ?
                     cf a[P];
 #pragma unroll
                     for (int ps = 0; ps < P; ps++) a[ps] = src[jj][ps];
-                    blk_pass_dft<P>(a);
+                    pass_dft<P>(a);
                     float2 *const gw = (jj < kJB ? gw0 : gw1) + (jj % kJB) * 16 * kLd;
                     st2(&gw[0], a[0]);
 #pragma unroll
-                    for (int k = 1; k < P; k++) st2(&gw[32 * k], cmul(a[blk_pass_idx<P>(k)], ct[k]));
+                    for (int k = 1; k < P; k++) st2(&gw[32 * k], cmul(a[pass_idx<P>(k)], ct[k]));
                 }
                 __builtin_amdgcn_sched_barrier(0);                    // keep the next phase's arithmetic (and its registers) behind
                 __syncthreads();                                      // the trip is in LDS
@@ -638,16 +599,14 @@ hipError_t init_block_kernels()
 bool poly_block_supports(int N) { return N == 16384 || N == 32768 || N == 65536; }
 
 template <class TI, class TO = float2>
-static hipError_t poly_block_in(const TI *in, size_t in_stride, TO *out, int nb_chunk, int mbase, int nb_call,
-                                const float2 *tw256, const float2 *twq, const float2 *cbt, const float *shn,
-                                const long long *slot_off, unsigned out_bytes, int ncu, int hints, hipStream_t s,
-                                int r, long long first_block, hipEvent_t ev_start, hipEvent_t ev_stop, int R,
-                                float2 *scratch, int N, float iq_scale, float oq_scale = 1.0f)
+static hipError_t poly_block_in(const BlockLaunch &b, const TI *in, TO *out, float iq_scale, float oq_scale = 1.0f)
 {
-    if (nb_chunk <= 0) return hipSuccess;
+    if (b.nb_chunk <= 0) return hipSuccess;
+    if (b.L != 256 || b.r < 0 || b.r >= 256) return hipErrorInvalidValue;
     constexpr bool kIq = !std::is_same<TI, float2>::value, kOq = !std::is_same<TO, float2>::value;
+    const bool nt = (b.hints & 1) != 0, r4 = b.R == 4;
     // integer output: the streamed-store forms only (init_block_kernels_oq); the macros below name NT = true for both hints then
-    if (kOq && !(hints & 1)) return hipErrorInvalidValue;
+    if (kOq && !nt) return hipErrorInvalidValue;
     // the kernel's last argument: float2 input and output, no group powers (null); otherwise the scale(s) of the integer side(s) (IqTail)
     auto iq_tail = [](float si, float so) -> typename IqTail<TI, TO>::type {
         if constexpr (!kIq && !kOq) return (void)si, (void)so, (float *)nullptr;
@@ -655,98 +614,66 @@ static hipError_t poly_block_in(const TI *in, size_t in_stride, TO *out, int nb_
         else if constexpr (kIq) return (void)so, si;
         else return (void)si, so;
     };
-    const bool halfslot = (r & 255) == 128;                 // half a slot: the on-grid kernel with its tables moved (HALF), R = 2 and 4
-    if (!poly_block_supports(N) || (R != 2 && R != 4) || (R == 4 && !scratch)) return hipErrorInvalidValue;
-    int grid = ncu > 0 ? ncu : 256;                         // one 512-thread workgroup per CU (LDS: up to 159.5 KiB each)
-    // N = 16384 on the grid at R = 2: 126 registers and 79.75 KiB of LDS per workgroup: two workgroups per CU, one's stage 2 beside the
-    // other's stage 1
-    if (N == 16384 && R == 2 && (!(r & 255) || halfslot)) grid *= 2;
-    if (grid > nb_chunk) grid = nb_chunk;
+    const bool halfslot = b.half();                         // half a slot: the on-grid kernel with its tables moved (HALF), R = 2 and 4
+    if (!poly_block_supports(b.N) || (b.R != 2 && !r4) || (r4 && !b.scratch)) return hipErrorInvalidValue;
+    // one 512-thread workgroup per CU (LDS: up to 159.5 KiB each).  N = 16384 on the grid at R = 2: 126 registers and 79.75 KiB of LDS per
+    // workgroup: two workgroups per CU, one's stage 2 beside the other's stage 1
+    const int grid = b.grid(b.N == 16384 && b.R == 2 && (!b.r || halfslot) ? 2 : 1);
     // output samples are written once and never read back here: streamed (nt) stores, measured 0.186 -> 0.172 ms (hints bit 0)
     // ev_start / ev_stop (timing): the dispatch packet's own begin / end time stamps (hipExtLaunchKernel) — no barrier packet
     // in front of or behind the kernel, unlike hipEventRecord (measured 7-17 us per bracketed launch)
     // R = 4: three quarters of every inverse transform kept: 192 rows per block, 64 of them via the scratch
-#define FDC_LB(P, A, B, R4) \
-    hipExtLaunchKernelGGL((k_blk256<P, A || kOq, B, false, R4, false, TI, TO>), dim3((unsigned)grid), dim3(512), B ? BlkGeom<P>::kLdsOff : BlkGeom<P>::kLds, s, \
-                          ev_start, ev_stop, 0u, in, in_stride, out, tw256, twq, cbt, shn, slot_off, (long long)mbase * (R4 ? 192 : 128), (long long)nb_call, \
-                          out_bytes, nb_chunk, hints, (unsigned long long *)nullptr, r & 255, first_block, R4 ? scratch : (float2 *)nullptr, (const unsigned *)nullptr, \
-                          iq_tail(iq_scale, oq_scale))
-#define FDC_LH(P, A, R4) \
-    hipExtLaunchKernelGGL((k_blk256<P, A || kOq, false, false, R4, true, TI, TO>), dim3((unsigned)grid), dim3(512), BlkGeom<P>::kLds, s, ev_start, \
-                          ev_stop, 0u, in, in_stride, out, tw256, twq, cbt, shn, slot_off, (long long)mbase * (R4 ? 192 : 128), (long long)nb_call, \
-                          out_bytes, nb_chunk, hints, (unsigned long long *)nullptr, 0, first_block, R4 ? scratch : (float2 *)nullptr, (const unsigned *)nullptr, \
-                          iq_tail(iq_scale, oq_scale))
+    // FDC_L(P, NT, OFF, R4, HALF, roff): one instantiation with the launch's arguments
+#define FDC_L(P, A, O, R4, H, roff) \
+    hipExtLaunchKernelGGL((k_blk256<P, A || kOq, O, false, R4, H, TI, TO>), dim3((unsigned)grid), dim3(512), O ? BlkGeom<P>::kLdsOff : BlkGeom<P>::kLds, b.s, \
+                          b.ev_start, b.ev_stop, 0u, in, b.in_stride, out, b.tw256, b.twq, b.cbt, b.shn, b.slot_off, (long long)b.mbase * (R4 ? 192 : 128), \
+                          (long long)b.nb_call, b.out_bytes, b.nb_chunk, b.hints, (unsigned long long *)nullptr, roff, b.first_block, \
+                          R4 ? b.scratch : (float2 *)nullptr, (const unsigned *)nullptr, iq_tail(iq_scale, oq_scale))
+#define FDC_LB(P, A, O, R4) FDC_L(P, A, O, R4, false, b.r)
+#define FDC_LH(P, A, R4) FDC_L(P, A, false, R4, true, 0)
 // (FDC_R4(P): the R = 4 forms exist — not at P = 8 on float input with integer output, kOqR4Narrowed)
 #define FDC_R4(P) if constexpr (P != 8 || !kOqR4Narrowed<TI, TO>::value)
 #define FDC_LP(P) \
     do { \
         if (halfslot) { \
-            if (R == 4) { FDC_R4(P) { if (hints & 1) FDC_LH(P, true, true); else FDC_LH(P, false, true); } else return hipErrorInvalidValue; } \
-            else { if (hints & 1) FDC_LH(P, true, false); else FDC_LH(P, false, false); } \
-        } else if (R == 4 && (r & 255)) { FDC_R4(P) { if (hints & 1) FDC_LB(P, true, true, true); else FDC_LB(P, false, true, true); } else return hipErrorInvalidValue; } \
-        else if (R == 4) { FDC_R4(P) { if (hints & 1) FDC_LB(P, true, false, true); else FDC_LB(P, false, false, true); } else return hipErrorInvalidValue; } \
-        else if (r & 255) { if (hints & 1) FDC_LB(P, true, true, false); else FDC_LB(P, false, true, false); } \
-        else { if (hints & 1) FDC_LB(P, true, false, false); else FDC_LB(P, false, false, false); } \
+            if (r4) { FDC_R4(P) { if (nt) FDC_LH(P, true, true); else FDC_LH(P, false, true); } else return hipErrorInvalidValue; } \
+            else { if (nt) FDC_LH(P, true, false); else FDC_LH(P, false, false); } \
+        } else if (r4 && b.r) { FDC_R4(P) { if (nt) FDC_LB(P, true, true, true); else FDC_LB(P, false, true, true); } else return hipErrorInvalidValue; } \
+        else if (r4) { FDC_R4(P) { if (nt) FDC_LB(P, true, false, true); else FDC_LB(P, false, false, true); } else return hipErrorInvalidValue; } \
+        else if (b.r) { if (nt) FDC_LB(P, true, true, false); else FDC_LB(P, false, true, false); } \
+        else { if (nt) FDC_LB(P, true, false, false); else FDC_LB(P, false, false, false); } \
     } while (0)
-    if (N == 65536) FDC_LP(8); else if (N == 32768) FDC_LP(4); else FDC_LP(2);
+    if (b.N == 65536) FDC_LP(8); else if (b.N == 32768) FDC_LP(4); else FDC_LP(2);
 #undef FDC_LP
 #undef FDC_R4
 #undef FDC_LH
 #undef FDC_LB
+#undef FDC_L
     return hipGetLastError();
 }
 
-hipError_t launch_poly_block(const float2 *in, size_t in_stride, float2 *out, int nb_chunk, int mbase, int nb_call,
-                             const float2 *tw256, const float2 *twq, const float2 *cbt, const float *shn,
-                             const long long *slot_off, unsigned out_bytes, int ncu, int hints, hipStream_t s,
-                             int r, long long first_block, hipEvent_t ev_start, hipEvent_t ev_stop, int R,
-                             float2 *scratch, int N)
-{
-    return poly_block_in(in, in_stride, out, nb_chunk, mbase, nb_call, tw256, twq, cbt, shn, slot_off, out_bytes, ncu, hints, s, r, first_block,
-                         ev_start, ev_stop, R, scratch, N, 1.0f);
-}
+hipError_t launch_poly_block(const BlockLaunch &b) { return poly_block_in(b, b.in, b.out, 1.0f); }
 
-hipError_t launch_poly_block_iq(int fmt, float scale, const void *in, size_t in_stride, float2 *out, int nb_chunk, int mbase, int nb_call,
-                                const float2 *tw256, const float2 *twq, const float2 *cbt, const float *shn,
-                                const long long *slot_off, unsigned out_bytes, int ncu, int hints, hipStream_t s,
-                                int r, long long first_block, hipEvent_t ev_start, hipEvent_t ev_stop, int R, float2 *scratch, int N)
+hipError_t launch_poly_block_iq(const BlockLaunch &b, int fmt, float scale, const void *in)
 {
-    if (fmt == kIqSc16)
-        return poly_block_in(static_cast<const sc16 *>(in), in_stride, out, nb_chunk, mbase, nb_call, tw256, twq, cbt, shn, slot_off, out_bytes, ncu, hints, s,
-                             r, first_block, ev_start, ev_stop, R, scratch, N, scale);
-    if (fmt == kIqSc8)
-        return poly_block_in(static_cast<const sc8 *>(in), in_stride, out, nb_chunk, mbase, nb_call, tw256, twq, cbt, shn, slot_off, out_bytes, ncu, hints, s,
-                             r, first_block, ev_start, ev_stop, R, scratch, N, scale);
+    if (fmt == kIqSc16) return poly_block_in(b, static_cast<const sc16 *>(in), b.out, scale);
+    if (fmt == kIqSc8) return poly_block_in(b, static_cast<const sc8 *>(in), b.out, scale);
     return hipErrorInvalidValue;
 }
 
 template <class TO>
-static hipError_t poly_block_oq_in(int ifmt, float iscale, const void *in, size_t in_stride, TO *out, int nb_chunk, int mbase, int nb_call,
-                                   const float2 *tw256, const float2 *twq, const float2 *cbt, const float *shn, const long long *slot_off,
-                                   unsigned out_bytes, int ncu, int hints, hipStream_t s, int r, long long first_block, hipEvent_t ev_start,
-                                   hipEvent_t ev_stop, int R, float2 *scratch, int N, float oscale)
+static hipError_t poly_block_oq_in(const BlockLaunch &b, int ifmt, float iscale, const void *in, TO *out, float oscale)
 {
-#define FDC_OQ(TI, sc) \
-    return poly_block_in<TI, TO>(static_cast<const TI *>(in), in_stride, out, nb_chunk, mbase, nb_call, tw256, twq, cbt, shn, slot_off, out_bytes, ncu, \
-                                 hints, s, r, first_block, ev_start, ev_stop, R, scratch, N, sc, oscale)
-    if (ifmt == kIqFloat) FDC_OQ(float2, 1.0f);
-    if (ifmt == kIqSc16) FDC_OQ(sc16, iscale);
-    if (ifmt == kIqSc8) FDC_OQ(sc8, iscale);
-#undef FDC_OQ
+    if (ifmt == kIqFloat) return poly_block_in<float2, TO>(b, static_cast<const float2 *>(in), out, 1.0f, oscale);
+    if (ifmt == kIqSc16) return poly_block_in<sc16, TO>(b, static_cast<const sc16 *>(in), out, iscale, oscale);
+    if (ifmt == kIqSc8) return poly_block_in<sc8, TO>(b, static_cast<const sc8 *>(in), out, iscale, oscale);
     return hipErrorInvalidValue;
 }
 
-hipError_t launch_poly_block_oq(int ifmt, float iscale, const void *in, size_t in_stride, int ofmt, float oscale, void *out, int nb_chunk, int mbase,
-                                int nb_call, const float2 *tw256, const float2 *twq, const float2 *cbt, const float *shn,
-                                const long long *slot_off, unsigned out_bytes, int ncu, int hints, hipStream_t s,
-                                int r, long long first_block, hipEvent_t ev_start, hipEvent_t ev_stop, int R, float2 *scratch, int N)
+hipError_t launch_poly_block_oq(const BlockLaunch &b, int ifmt, float iscale, const void *in, int ofmt, float oscale, void *out)
 {
-    if (ofmt == kIqSc16)
-        return poly_block_oq_in(ifmt, iscale, in, in_stride, static_cast<sc16 *>(out), nb_chunk, mbase, nb_call, tw256, twq, cbt, shn, slot_off, out_bytes,
-                                ncu, hints, s, r, first_block, ev_start, ev_stop, R, scratch, N, oscale);
-    if (ofmt == kIqSc8)
-        return poly_block_oq_in(ifmt, iscale, in, in_stride, static_cast<sc8 *>(out), nb_chunk, mbase, nb_call, tw256, twq, cbt, shn, slot_off, out_bytes,
-                                ncu, hints, s, r, first_block, ev_start, ev_stop, R, scratch, N, oscale);
+    if (ofmt == kIqSc16) return poly_block_oq_in(b, ifmt, iscale, in, static_cast<sc16 *>(out), oscale);
+    if (ofmt == kIqSc8) return poly_block_oq_in(b, ifmt, iscale, in, static_cast<sc8 *>(out), oscale);
     return hipErrorInvalidValue;
 }
 

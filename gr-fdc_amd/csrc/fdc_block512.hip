@@ -5,8 +5,8 @@
 // fdc_block256.hip (16 lanes x 16 row registers per column) would need 32 row registers per lane and pass — 64 VGPRs beside the 64 of
 // the prefetch and the 128 of G.  Instead the column's rows n2 = 2 mu + par are two 256-point sub-sequences, each of which is exactly a
 // "column" of the 256 kernel: a QUAD of lanes is (column c, parity 0), (c + 1, 0), (c, 1), (c + 1, 1), both parities run the 256-point
-// transforms of the old stage 1 in lockstep on the same instructions, and the radix-2 layer that joins them is an exchange with lane ^ 2
-// (DPP quad_perm [2, 3, 0, 1]):
+// transforms of stage 1 (strip_fft256 / strip_ifft256, fdc_blockcommon.hpp) in lockstep on the same instructions, and the radix-2 layer that joins them is an exchange with lane ^ 2
+// (quad_xor2: the other parity of the same column):
 //     forward (decimation in time):   A[kap]       = E[kap] + W_512^kap O[kap]          kap = 0 .. 255
 //                                     A[kap + 256] = E[kap] - W_512^kap O[kap]          -> parity-0 lanes hold the lower half of k2, parity-1 the upper
 //     product: shape[k2]/N (-1)^n1 W_N^(n1 k2), k2 = kap + 256 h — all of it BEFORE the inverse layer (its h part differs between the lanes
@@ -20,37 +20,16 @@
 // DFT-16 over c4 in the lane that owns (row, klo); a wave's store is 64 consecutive samples of one channel.
 //
 // The arithmetic is that of k_p1g + k_p2g (fdc_kernels.hip) regrouped; parity against the oracle: tests/test_parity_gpu.py.
-#include <hip/hip_ext.h>
-#include <type_traits>
-#include "fdc_kernels.h"
-#include "fdc_radix16.hpp"
-#include "fdc_devutil.hpp"
+#include "fdc_blockcommon.hpp"
 
 namespace fdc {
 
 extern __shared__ __attribute__((aligned(16))) unsigned char fdc_smem_b512[];
 
-__device__ __forceinline__ unsigned long long pack512(cf v) { return ((unsigned long long)__float_as_uint(v.y) << 32) | __float_as_uint(v.x); }
-__device__ __forceinline__ cf unpack512(unsigned long long u) { return mk(__uint_as_float((unsigned)u), __uint_as_float((unsigned)(u >> 32))); }
-#if defined(__HIP_DEVICE_COMPILE__)
-#define FDC_PLAIN_DS512 __attribute__((target("no-load-store-opt")))
-#else
-#define FDC_PLAIN_DS512
-#endif
-
-// the value of the lane two further on in the quad (lane ^ 2): the other parity of the same column
-__device__ __forceinline__ cf swap_parity(cf x)
-{
-    return mk(__int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x.x), 0x4E, 0xF, 0xF, true)),
-              __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x.y), 0x4E, 0xF, 0xF, true)));
-}
-
 // LDS map (bytes).  The block length is a template parameter (round 5): N = 512 rows x (16 P) columns, P = 2, 4, 8 passes of 16 columns: N = 16384, 32768,
 // 65536; the channel slots are the columns N1 = 16 P.  Stage 1 does not depend on P except through the row pitch and the table sizes; G is 16 P
 // registers per lane; stage 2 is a DFT-P over the pass index in registers, one trip through LDS and the same DFT-16 over c4.  A trip holds 512 / P rows
 // ([rows][P klo][16 c4]; P = 8: 64 rows, four trips for the 256 kept rows; P = 2: all 256 in one) and a wave reads (klo = wave mod P, row block = wave div P).
-constexpr int k5ScrPts = 1084;                                   // per-wave exchange strip, as in fdc_block256.hip
-constexpr int k5OffX = 8 * k5ScrPts * 8;                         // 69376: end of the strips
 // W_512^(b + 16 q) for the parity-1 lanes as [16 b][18] from point k5T512Tab on; the parity-0 lanes' factor is 1: ONE row of ones at point 0, read by all
 // of them (a broadcast).  The table starts 92 dwords behind the ones (= 28 mod 64 + 64): a 16-byte read's lane group then finds the ones and its
 // four b rows on five different 4-dword windows (round 5: two tables [2 par][16][18] put (0, b) and (1, b) on the same banks — 2-way on every read)
@@ -72,7 +51,7 @@ struct B5Geom {
     static constexpr int kJT = 16 / P;                            // 32-row groups (two parities x 16 b) per trip
     static constexpr int kLd = P * 16 + 6;                        // trip rows: [P klo][16 c4] + 6 points (row stride = 12 dwords mod 64 for P = 8, 4, 2: 268, 140, 76)
     static constexpr int kTrip = kTripRows * kLd * 8;             // P = 8: 68608; 4: 71680; 2: 77824
-    static constexpr int kOffCt = kTrip > k5OffX ? kTrip : k5OffX;   // [16 c4][P klo]  W_N1^(c4 klo): behind the strips and the trip buffer
+    static constexpr int kOffCt = kTrip > kStripsEnd ? kTrip : kStripsEnd;   // [16 c4][P klo]  W_N1^(c4 klo): behind the strips and the trip buffer
     static constexpr int kOffWrow = kOffCt + 16 * P * 8;          // [16][18]  W_256^(b p)
     static constexpr int kOffT512 = kOffWrow + 16 * 18 * 8;
     static constexpr int kOffB = kOffT512 + (k5T512Tab + 16 * 18) * 8;   // [P pass][16 c4][16]  W_N^(16 n1 q), n1 = 16 pass + c4 (rows unpadded: a wave reads two of them, broadcast)
@@ -84,15 +63,6 @@ struct B5Geom {
     static_assert(kLds <= 160 * 1024, "LDS budget");
     static_assert((kLd * 2) % 64 == 12, "trip rows 12 dwords apart mod 64: the lane groups of ds_read_b128 on all banks");
 };
-// DFT over the pass index (the register index of G): P points in place; X[k] is read through b5_pass_idx<P>(k)
-template <int P> __device__ __forceinline__ constexpr int b5_pass_idx(int k) { return P == 8 ? 4 * (k & 1) + (k >> 1) : k; }
-template <int P>
-__device__ __forceinline__ void b5_pass_dft(cf (&a)[P])
-{
-    if constexpr (P == 8) dft8<false>(a);                          // klo = k0 + 2 k1 in a[4 k0 + k1]
-    else if constexpr (P == 4) dft4<false>(a[0], a[1], a[2], a[3]);
-    else { const cf s0 = a[0] + a[1], d0 = a[0] - a[1]; a[0] = s0; a[1] = d0; }
-}
 
 // R4 = true: relinvovl = 4 (the reference's default overlap): 384 of the 512 samples of every inverse transform are kept.  The rows m >= 128 of
 // both parities stay in the G registers as for R = 2 (output rows 128 ..); the rows 64 <= m < 128 go to 128 KiB of per-workgroup scratch
@@ -102,7 +72,7 @@ __device__ __forceinline__ void b5_pass_dft(cf (&a)[P])
 // instructions), parks them in registers for a pass, writes them to [column][row] planes in LDS at the pass boundary and reads its own columns' rows back:
 // two workgroup barriers per pass for an eighth of the line requests.
 template <bool NT, bool R4, int P = 8>
-__global__ FDC_PLAIN_DS512 __launch_bounds__(512) void k_blk512(const float2 *__restrict__ in, size_t in_stride, float2 *__restrict__ out,
+__global__ FDC_PLAIN_DS __launch_bounds__(512) void k_blk512(const float2 *__restrict__ in, size_t in_stride, float2 *__restrict__ out,
                                                       const float2 *__restrict__ tw256, const float2 *__restrict__ tw512 /* W_512^k, k < 256 */,
                                                       const float2 *__restrict__ twq /* [n1][16] W_N^(16 n1 q) */,
                                                       const float2 *__restrict__ cbt /* [n1][32] (-1)^n1 W_N^(n1 (b + 256 h)) at b + 16 h */,
@@ -127,9 +97,7 @@ __global__ FDC_PLAIN_DS512 __launch_bounds__(512) void k_blk512(const float2 *__
     // lane = vc + 4 b: vc = creal + 2 par (a quad = two columns x two parities), b = row group of the 256-point sub-transform
     const int w = tid >> 6, lane = tid & 63, vc = lane & 3, creal = vc & 1, par = vc >> 1, b = lane >> 2, c4 = 2 * w + creal;
 
-    const int grid = gridDim.x, per = grid >> 3;
-    const bool xmap = (grid & 7) == 0;
-    const int first = xmap ? (int)(blockIdx.x & 7) * per + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
+    const int grid = gridDim.x, first = xcd_first_block();
     if (first >= nb) return;
 
     constexpr unsigned inbytes = (unsigned)GM::kN * 8u;
@@ -174,8 +142,8 @@ __global__ FDC_PLAIN_DS512 __launch_bounds__(512) void k_blk512(const float2 *__
     for (int i = tid; i < 512; i += 512) Sh[(i >> 8) * k5ShPar + (i & 15) * 16 + ((i >> 4) & 15)] = shn[i];   // i = b + 16 q + 256 h
     __syncthreads();
 
-    float2 *const scrw = scr + w * k5ScrPts + lane;
-    const float2 *const scrr = scr + w * k5ScrPts + vc + 68 * b;
+    float2 *const scrw = scr + w * kStripPts + lane;
+    const float2 *const scrr = scr + w * kStripPts + vc + 68 * b;
     const float2 *const wr = wrow + b * 18;
     const float2 *const t5r = par ? t512 + k5T512Tab + b * 18 : t512;
     const float2 *const btr = Bt + c4 * 16;                              // + pass * 16 rows
@@ -200,24 +168,9 @@ __global__ FDC_PLAIN_DS512 __launch_bounds__(512) void k_blk512(const float2 *__
             stage_write();
             stage_load(ps < P - 2 ? m : mnext, (ps + 2) & (P - 1));
             cbn = bld2(rcb, voffc, (unsigned)((ps + 1) & (P - 1)) * 4096u);
-            // ---- the 256-point forward transform of this lane's parity: exactly the old stage 1
-            dft16<false>(cur);
-            {
-                cf tw[16];
-#pragma unroll
-                for (int i = 0; i < 8; i++) {
-                    const float4 t = ld4(&wr[2 * i]);
-                    tw[2 * i] = mk(t.x, t.y); tw[2 * i + 1] = mk(t.z, t.w);
-                }
-                st2(&scrw[0], cur[rev16(0)]);
-#pragma unroll
-                for (int p = 1; p < 16; p++) st2(&scrw[68 * p], cmul(cur[rev16(p)], tw[p]));
-            }
-            __builtin_amdgcn_wave_barrier();
+            // ---- the 256-point forward transform of this lane's parity
             cf v[16];
-#pragma unroll
-            for (int bb = 0; bb < 16; bb++) v[bb] = ld2(&scrr[4 * bb]);
-            dft16<false>(v);                                      // E (par 0) / O (par 1) at kap = b + 16 q in v[rev16(q)]
+            strip_fft256(cur, v, wr, scrw, scrr);                 // E (par 0) / O (par 1) at kap = b + 16 q in v[rev16(q)]
             // ---- forward radix-2 layer, product, inverse radix-2 layer (the parity-0 lanes' "twiddle" is a table row of ones: no branches).
             // One value at a time, 8-byte table reads: the kernel has no registers for wider ones.
             cf u[16];
@@ -234,37 +187,20 @@ __global__ FDC_PLAIN_DS512 __launch_bounds__(512) void k_blk512(const float2 *__
                     for (int e = 0; e < 4; e++) {
                         const int q = 4 * g4 + e;
                         const cf x = cmul(v[rev16(q)], w5s[e]);                      // par 1: O W_512^kap; par 0: E
-                        const cf a = swap_parity(x) + x * fsgn;                      // par 0: E + O' = A[kap]; par 1: E - O' = A[kap + 256]
+                        const cf a = quad_xor2(x) + x * fsgn;                      // par 0: E + O' = A[kap]; par 1: E - O' = A[kap + 256]
                         // shape / N, W_N^(16 n1 q), (-1)^n1 W_N^(n1 (b + 256 h)) = cb
                         const cf y = cmul(cmul(a, bps[e]), cb) * shs[e];
                         // ifftshift: the h = 1 lane's value is P (index kap), the h = 0 lane's is Q (index kap + 256)
-                        const cf z = y + swap_parity(y) * fsgn;                      // par 0: Q + P; par 1: P - Q
+                        const cf z = y + quad_xor2(y) * fsgn;                      // par 0: Q + P; par 1: P - Q
                         u[q] = cmulc(z, w5s[e]) * hsgn;                              // par 1: conj(W_512^kap)
                     }
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
             // ---- the 256-point inverse transform of this lane's parity (no q ^ 8: the shift was the half swap)
-            dft16<true>(u);
-            {
-                cf tw[16];
+            strip_ifft256(u, wr, scrw, scrr);                     // g[2 m + par], m = b + 16 q in u[rev16(q)]; keep q >= 8
 #pragma unroll
-                for (int i = 0; i < 8; i++) {
-                    const float4 t = ld4(&wr[2 * i]);
-                    tw[2 * i] = mk(t.x, t.y); tw[2 * i + 1] = mk(t.z, t.w);
-                }
-#pragma unroll
-                for (int p = 1; p < 16; p++) u[rev16(p)] = cmulc(u[rev16(p)], tw[p]);
-            }
-            __builtin_amdgcn_wave_barrier();
-#pragma unroll
-            for (int p = 0; p < 16; p++) st2(&scrw[68 * p], u[rev16(p)]);
-            __builtin_amdgcn_wave_barrier();
-#pragma unroll
-            for (int bb = 0; bb < 16; bb++) u[bb] = ld2(&scrr[4 * bb]);
-            dft16<true>(u);                                       // g[2 m + par], m = b + 16 q in u[rev16(q)]; keep q >= 8
-#pragma unroll
-            for (int j = 0; j < 8; j++) G[j][ps] = pack512(u[rev16(8 + j)]);
+            for (int j = 0; j < 8; j++) G[j][ps] = pack_cf(u[rev16(8 + j)]);
             if constexpr (R4) {                                   // R = 4 keeps q >= 4: m = 64 .. 127 go to the scratch, [pass][q - 4][thread]
 #pragma unroll
                 for (int j = 0; j < 4; j++) bst2(rscr, (unsigned)tid * 8u + (unsigned)j * 4096u, (unsigned)ps * 16384u, u[rev16(4 + j)]);
@@ -311,11 +247,11 @@ __global__ FDC_PLAIN_DS512 __launch_bounds__(512) void k_blk512(const float2 *__
                     cf a[P];
 #pragma unroll
                     for (int ps = 0; ps < P; ps++) a[ps] = src[jj][ps];
-                    b5_pass_dft<P>(a);
+                    pass_dft<P>(a);
                     float2 *const g = gw + jj * 32 * k5Ld;
                     st2(&g[0], a[0]);
 #pragma unroll
-                    for (int k = 1; k < P; k++) st2(&g[16 * k], cmul(a[b5_pass_idx<P>(k)], ct[k]));
+                    for (int k = 1; k < P; k++) st2(&g[16 * k], cmul(a[pass_idx<P>(k)], ct[k]));
                 }
                 __builtin_amdgcn_sched_barrier(0);
                 __syncthreads();                                      // the trip is in LDS
@@ -344,7 +280,7 @@ __global__ FDC_PLAIN_DS512 __launch_bounds__(512) void k_blk512(const float2 *__
                 __builtin_amdgcn_sched_barrier(0);
             }
         };
-        stage2([&](int j, int ps) { return unpack512(G[j][ps]); }, R4 ? 128 : 0, std::integral_constant<int, 8>{});
+        stage2([&](int j, int ps) { return unpack_cf(G[j][ps]); }, R4 ? 128 : 0, std::integral_constant<int, 8>{});
         if constexpr (R4) {
             // m = 64 .. 127 = output rows 0 .. 127: this lane's own stores, served by the L2
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -362,38 +298,24 @@ bool poly_block512_supports(int N, int R)
 hipError_t init_block512_kernels()
 {
     hipError_t e = hipSuccess;
-#define FDC_SET5(A, B, P) \
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_blk512<A, B, P>), hipFuncAttributeMaxDynamicSharedMemorySize, B5Geom<P>::kLds);
-#define FDC_SET5P(P) FDC_SET5(true, false, P) FDC_SET5(false, false, P) FDC_SET5(true, true, P) FDC_SET5(false, true, P)
-    FDC_SET5P(8) FDC_SET5P(4) FDC_SET5P(2)
-#undef FDC_SET5P
-#undef FDC_SET5
+    for_block_variants(kEvery, kEvery, kEvery, [&](auto NT, auto R4, auto P) {
+        if (e == hipSuccess) e = set_block_lds(reinterpret_cast<const void *>(k_blk512<NT() != 0, R4() != 0, P()>), B5Geom<P()>::kLds);
+    });
     return e;
 }
 
-hipError_t launch_poly_block512(const float2 *in, size_t in_stride, float2 *out, int nb_chunk, int mbase, int nb_call, const float2 *tw256,
-                                const float2 *tw512, const float2 *twq, const float2 *cbt, const float *shn, const long long *slot_off,
-                                unsigned out_bytes, int ncu, int hints, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop, int R, float2 *scratch,
-                                bool half, int N)
+hipError_t launch_poly_block512(const BlockLaunch &b)
 {
-    if (nb_chunk <= 0) return hipSuccess;
-    if (!poly_block512_supports(N, R) || (R == 4 && !scratch)) return hipErrorInvalidValue;
-    int grid = ncu > 0 ? ncu : 256;
-    if (grid > nb_chunk) grid = nb_chunk;
-#define FDC_L512(A, B, P) \
-    hipExtLaunchKernelGGL((k_blk512<A, B, P>), dim3((unsigned)grid), dim3(512), B5Geom<P>::kLds, s, ev_start, ev_stop, 0u, in, in_stride, out, \
-                          tw256, tw512, twq, cbt, shn, slot_off, (long long)mbase * (B ? 384 : 256), (long long)nb_call, out_bytes, nb_chunk, hints, \
-                          B ? scratch : (float2 *)nullptr, half ? 1 : 0)
-    const bool nt = (hints & 1) != 0;
-#define FDC_L512P(P) \
-    do { \
-        if (R == 4) { if (nt) FDC_L512(true, true, P); else FDC_L512(false, true, P); } \
-        else { if (nt) FDC_L512(true, false, P); else FDC_L512(false, false, P); } \
-    } while (0)
-    if (N == 65536) FDC_L512P(8); else if (N == 32768) FDC_L512P(4); else FDC_L512P(2);
-#undef FDC_L512P
-#undef FDC_L512
-    return hipGetLastError();
+    if (b.nb_chunk <= 0) return hipSuccess;
+    if (!poly_block512_supports(b.N, b.R) || (b.R == 4 && !b.scratch) || (b.r != 0 && !b.half())) return hipErrorInvalidValue;
+    hipError_t e = hipErrorInvalidValue;                        // stays if no instantiation matches
+    for_block_variants(b.hints & 1, b.R == 4, b.N / 8192, [&](auto NT, auto R4, auto P) {
+        hipExtLaunchKernelGGL((k_blk512<NT() != 0, R4() != 0, P()>), dim3((unsigned)b.grid()), dim3(512), B5Geom<P()>::kLds, b.s, b.ev_start, b.ev_stop, 0u,
+                              b.in, b.in_stride, b.out, b.tw256, b.twl, b.twq, b.cbt, b.shn, b.slot_off, (long long)b.mbase * (R4() ? 384 : 256),
+                              (long long)b.nb_call, b.out_bytes, b.nb_chunk, b.hints, R4() ? b.scratch : (float2 *)nullptr, b.half() ? 1 : 0);
+        e = hipGetLastError();
+    });
+    return e;
 }
 
 }  // namespace fdc

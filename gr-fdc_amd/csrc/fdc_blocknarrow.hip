@@ -4,7 +4,7 @@
 //
 // An l-point column in the lane layout of fdc_block256.hip would leave most of the 16 x 16 exchange idle and need S times the passes.
 // Instead virtual column V carries the real columns n1 = S V + e, e < S, as the samples nu = S mu + e of ONE 256-point sequence
-// z[S mu + e] = x[(S V + e) + N1 mu]; the 256-point transforms of the old stage 1 run on z unchanged, and the radix-S layers that separate
+// z[S mu + e] = x[(S V + e) + N1 mu]; the 256-point transforms of stage 1 (strip_fft256 and the strip round trip of fdc_blockcommon.hpp) run on z unchanged, and the radix-S layers that separate
 // and re-join the columns combine the registers q0, q0 + 16/S, ... OF THE SAME LANE (k = b + 16 q  <->  k + l): no exchange, no extra pass.
 //     forward:  Z[kap + l i] = sum_e W_S^(i e) (W_256^(kap e) A_e[kap])           kap < l, i < S
 //               => S W_256^(kap e) A_e[kap] = sum_i W_S^(-i e) Z[kap + l i]         (an inverse DFT-S over the registers)
@@ -20,44 +20,19 @@
 //
 // All constants of stage 1 come from ONE host-built table image (fdc_api.hip: double precision, rounded once).  The arithmetic is that of
 // k_p1g + k_p2g (fdc_kernels.hip) regrouped; parity against the oracle: tests/test_parity_gpu.py.
-#include <hip/hip_ext.h>
 #include <cmath>
-#include <type_traits>
-#include "fdc_kernels.h"
-#include "fdc_radix16.hpp"
-#include "fdc_devutil.hpp"
+#include "fdc_blockcommon.hpp"
 
 namespace fdc {
 
 extern __shared__ __attribute__((aligned(16))) unsigned char fdc_smem_nar[];
 
-__device__ __forceinline__ unsigned long long pack_nar(cf v) { return ((unsigned long long)__float_as_uint(v.y) << 32) | __float_as_uint(v.x); }
-__device__ __forceinline__ cf unpack_nar(unsigned long long u) { return mk(__uint_as_float((unsigned)u), __uint_as_float((unsigned)(u >> 32))); }
-#if defined(__HIP_DEVICE_COMPILE__)
-#define FDC_PLAIN_DSN __attribute__((target("no-load-store-opt")))
-#else
-#define FDC_PLAIN_DSN
-#endif
-
-// the value of lane ^ 1 / lane ^ 2 of the quad
-__device__ __forceinline__ cf quad_xor1(cf x)
-{
-    return mk(__int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x.x), 0xB1, 0xF, 0xF, true)),
-              __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x.y), 0xB1, 0xF, 0xF, true)));
-}
-__device__ __forceinline__ cf quad_xor2(cf x)
-{
-    return mk(__int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x.x), 0x4E, 0xF, 0xF, true)),
-              __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x.y), 0x4E, 0xF, 0xF, true)));
-}
-
-// LDS map (bytes): strips and trip buffer as in fdc_block256.hip; the tables are one image, laid out by the host in the order below.
+// LDS map (bytes): the strips (fdc_blockcommon.hpp) and the trip buffer as in fdc_block256.hip; the tables are one image, laid out by the host in the order below.
 // S = columns per virtual column (2: l = 128, 4: l = 64); QG = 16/S registers q0 per lane carry kap = b + 16 q0 < l.
 // P = passes of 32 virtual columns (round 5): N = 256 rows x 32 P virtual columns = 8192 P (P = 8: 65536; 4: 32768; 2: 16384), N1 = 32 P S slots.
 // Stage 2 is the FFT-32P over V: DFT-P over the pass index in registers, one trip through LDS, DFT-32 over c5.  A trip holds up to 8 / P blocks of 64 rows
 // ([rows][P klo][32 c5]): a wave reads (klo = wave mod P, block = wave div P); a run of fewer blocks than a trip holds (R = 2: 128 kept rows = two blocks;
 // the rows that come back from the scratch at R = 4: one) leaves the other waves without a row for the DFT-32.
-constexpr int kNarScrPts = 1084;
 template <int S, int P = 8>
 struct NarGeom {
     static_assert(S == 2 || S == 4, "two or four columns per virtual column");
@@ -71,8 +46,7 @@ struct NarGeom {
     static constexpr int kLd = 32 * P + 6;                       // stage-2 trip rows: [P klo][32 c5] + 6 (12 dwords mod 64)
     static constexpr int kTripBlocks = (8 / P) < 2 ? (8 / P) : 2;   // 64-row blocks a trip ever holds (a run has two at most)
     static constexpr int kTrip = 64 * kTripBlocks * kLd * 8;     // P = 8: 134144; 4: 137216; 2: 71680
-    static constexpr int kStrips = 8 * kNarScrPts * 8;
-    static constexpr int kOffTab = P == 8 ? 136960 : (kTrip > kStrips ? kTrip : kStrips);
+    static constexpr int kOffTab = P == 8 ? 136960 : (kTrip > kStripsEnd ? kTrip : kStripsEnd);
     // table rows read 16 bytes at a time by the sixteen b rows of a wave: row strides of 20 (S = 2), 12 and 28 (S = 4) dwords put the sixteen
     // reads on sixteen different bank quartets
     static constexpr int kRowQ = kQG + 2;                        // Bt, SA rows: 10 / 6 points
@@ -87,7 +61,7 @@ struct NarGeom {
     static constexpr int kTabPts = kTCt + 32 * P;
     static constexpr int kOffSoff = kOffTab + kTabPts * 8;       // [P klo][S lane][32 register] output offsets (bytes)
     static constexpr int kLds = kOffSoff + kN1 * 4;              // P = 8: S = 2: 161536; S = 4: 163072
-    static_assert(kTrip <= kOffTab && kStrips <= kOffTab && kOffTab % 16 == 0 && kLds <= 160 * 1024, "LDS budget");
+    static_assert(kTrip <= kOffTab && kStripsEnd <= kOffTab && kOffTab % 16 == 0 && kLds <= 160 * 1024, "LDS budget");
     static_assert((kLd * 2) % 64 == 12, "trip rows 12 dwords apart mod 64");
 };
 
@@ -161,15 +135,6 @@ void poly_block_narrow_tables(int L, int N, const float *shn, float2 *img, bool 
     }
 }
 
-template <int P> __device__ __forceinline__ constexpr int nar_pass_idx(int k) { return P == 8 ? 4 * (k & 1) + (k >> 1) : k; }
-template <int P>
-__device__ __forceinline__ void nar_pass_dft(cf (&a)[P])
-{
-    if constexpr (P == 8) dft8<false>(a);                          // klo = k0 + 2 k1 in a[4 k0 + k1]
-    else if constexpr (P == 4) dft4<false>(a[0], a[1], a[2], a[3]);
-    else { const cf s0 = a[0] + a[1], d0 = a[0] - a[1]; a[0] = s0; a[1] = d0; }
-}
-
 // R4 = true: relinvovl = 4 (the reference's default overlap): three quarters of every inverse transform are kept.  The rows t >= 128 of the
 // virtual column stay in the G registers as for R = 2; the rows 64 <= t < 128 go to 128 KiB of per-workgroup scratch ([pass][q - 4][thread]: the
 // L2 holds it) and come back for a second, 64-row run of stage 2 (the first 64/S output rows of the block), as in fdc_block256.hip.
@@ -179,7 +144,7 @@ __device__ __forceinline__ void nar_pass_dft(cf (&a)[P])
 // same lane — times one constant per column: W_N^(r e) conj(W_256^(r e)) (in TD, host) and W_N^(r S V) (in cbt).  The kernel differs in which registers the
 // separation reads.
 template <int S, bool NT, bool R4, bool HALF, int ROT = 0, int P = 8>
-__global__ FDC_PLAIN_DSN __launch_bounds__(512) void k_blknar(const float2 *__restrict__ in, size_t in_stride, float2 *__restrict__ out,
+__global__ FDC_PLAIN_DS __launch_bounds__(512) void k_blknar(const float2 *__restrict__ in, size_t in_stride, float2 *__restrict__ out,
                                                     const float2 *__restrict__ tab /* the table image */,
                                                     const float2 *__restrict__ cbt /* [32 P V][16 b]  W_N^(S V b) */,
                                                     const long long *__restrict__ slot_off /* [32 P S] */, long long out_base, long long nb_call,
@@ -197,9 +162,7 @@ __global__ FDC_PLAIN_DSN __launch_bounds__(512) void k_blknar(const float2 *__re
     // lane = col + 4 b: virtual column c5 = 4 wave + col of the pass, rows nu = 16 a + b of its 256-point sequence
     const int w = tid >> 6, lane = tid & 63, col = lane & 3, b = lane >> 2, c5 = 4 * w + col;
 
-    const int grid = gridDim.x, per = grid >> 3;
-    const bool xmap = (grid & 7) == 0;
-    const int first = xmap ? (int)(blockIdx.x & 7) * per + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
+    const int grid = gridDim.x, first = xcd_first_block();
     if (first >= nb) return;
 
     constexpr unsigned inbytes = (unsigned)GM::kN * 8u;
@@ -226,8 +189,8 @@ __global__ FDC_PLAIN_DSN __launch_bounds__(512) void k_blknar(const float2 *__re
     }
     __syncthreads();
 
-    float2 *const scrw = scr + w * kNarScrPts + lane;
-    const float2 *const scrr = scr + w * kNarScrPts + col + 68 * b;
+    float2 *const scrw = scr + w * kStripPts + lane;
+    const float2 *const scrr = scr + w * kStripPts + col + 68 * b;
     const float2 *const wr = tbl + GM::kTWrow + b * 18;
     const float2 *const btr = tbl + GM::kTB + c5 * GM::kRowQ;
     const float2 *const sab = tbl + GM::kTSA + b * GM::kRowQ;             // + pass * 16 rows
@@ -253,24 +216,9 @@ __global__ FDC_PLAIN_DSN __launch_bounds__(512) void k_blknar(const float2 *__re
                 }
                 cbn = bld2(rcb, voffc, (unsigned)pn * 4096u);
             }
-            // ---- the 256-point forward transform of the virtual column: exactly the old stage 1
-            dft16<false>(cur);
-            {
-                cf tw[16];
-#pragma unroll
-                for (int i = 0; i < 8; i++) {
-                    const float4 t = ld4(&wr[2 * i]);
-                    tw[2 * i] = mk(t.x, t.y); tw[2 * i + 1] = mk(t.z, t.w);
-                }
-                st2(&scrw[0], cur[rev16(0)]);
-#pragma unroll
-                for (int p = 1; p < 16; p++) st2(&scrw[68 * p], cmul(cur[rev16(p)], tw[p]));
-            }
-            __builtin_amdgcn_wave_barrier();
+            // ---- the 256-point forward transform of the virtual column
             cf v[16];
-#pragma unroll
-            for (int bb = 0; bb < 16; bb++) v[bb] = ld2(&scrr[4 * bb]);
-            dft16<false>(v);                                      // Z[k = b + 16 q] in v[rev16(q)]
+            strip_fft256(cur, v, wr, scrw, scrr);                 // Z[k = b + 16 q] in v[rev16(q)]
             // ---- separate the S columns (registers q0 + (16/S) i), product, shift, re-join
             cf u[16];
             {
@@ -310,6 +258,7 @@ __global__ FDC_PLAIN_DSN __launch_bounds__(512) void k_blknar(const float2 *__re
                 }
             }
             // ---- the 256-point inverse transform of the virtual column (no q ^ 8: the shift was inside the l-point parts)
+            // (strip_ifft256 with cb folded into the twiddle step; the row read is written out: through ld_row the compiler orders this kernel otherwise)
             dft16<true>(u);
             {
                 cf tw[16];
@@ -322,15 +271,10 @@ __global__ FDC_PLAIN_DSN __launch_bounds__(512) void k_blknar(const float2 *__re
 #pragma unroll
                 for (int p = 1; p < 16; p++) u[rev16(p)] = cmul(cmulc(u[rev16(p)], tw[p]), cb);
             }
-            __builtin_amdgcn_wave_barrier();
-#pragma unroll
-            for (int p = 0; p < 16; p++) st2(&scrw[68 * p], u[rev16(p)]);
-            __builtin_amdgcn_wave_barrier();
-#pragma unroll
-            for (int bb = 0; bb < 16; bb++) u[bb] = ld2(&scrr[4 * bb]);
+            strip_trip(u, scrw, scrr);
             dft16<true>(u);                                       // y[t = b + 16 q] in u[rev16(q)]; keep q >= 8
 #pragma unroll
-            for (int j = 0; j < 8; j++) G[j][ps] = pack_nar(u[rev16(8 + j)]);
+            for (int j = 0; j < 8; j++) G[j][ps] = pack_cf(u[rev16(8 + j)]);
             if constexpr (R4) {                                   // R = 4 keeps q >= 4: rows 64..127 go to the scratch, [pass][q - 4][thread]
 #pragma unroll
                 for (int j = 0; j < 4; j++) bst2(rscr, (unsigned)tid * 8u + (unsigned)j * 4096u, (unsigned)ps * 16384u, u[rev16(4 + j)]);
@@ -381,11 +325,11 @@ __global__ FDC_PLAIN_DSN __launch_bounds__(512) void k_blknar(const float2 *__re
                     cf a[P];
 #pragma unroll
                     for (int ps = 0; ps < P; ps++) a[ps] = src[jj][ps];
-                    nar_pass_dft<P>(a);
+                    pass_dft<P>(a);
                     float2 *const gw = gwb[jj >> 1] + (jj & 1) * 16 * kNarLd;
                     st2(&gw[0], a[0]);
 #pragma unroll
-                    for (int k = 1; k < P; k++) st2(&gw[32 * k], cmul(a[nar_pass_idx<P>(k)], ct[k]));
+                    for (int k = 1; k < P; k++) st2(&gw[32 * k], cmul(a[pass_idx<P>(k)], ct[k]));
                 }
                 __builtin_amdgcn_sched_barrier(0);
                 __syncthreads();                                      // the trip is in LDS
@@ -440,7 +384,7 @@ __global__ FDC_PLAIN_DSN __launch_bounds__(512) void k_blknar(const float2 *__re
                 __builtin_amdgcn_sched_barrier(0);
             }
         };
-        stage2([&](int j, int ps) { return unpack_nar(G[j][ps]); }, R4 ? 64 / S : 0, std::integral_constant<int, 2>{});
+        stage2([&](int j, int ps) { return unpack_cf(G[j][ps]); }, R4 ? 64 / S : 0, std::integral_constant<int, 2>{});
         if constexpr (R4) {
             // rows 64..127 of the inverse transforms = the first output rows: this lane's own stores, served by the L2
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -451,60 +395,46 @@ __global__ FDC_PLAIN_DSN __launch_bounds__(512) void k_blknar(const float2 *__re
     }
 }
 
+// f(S, NT, R4, HALF, ROT, P) for the instantiation that matches, or for every one (kEvery).  quarter: the bank's offset from the l-bin grid in quarters of
+// a channel: 2 is the HALF form, 1 and 3 move the spectrum of the virtual column by ROT = r / 16 = quarter * 4 / S registers
+template <class F>
+static void for_narrow_variants(int S, int quarter, int nt, int r4, int p, F &&f)
+{
+    for_values<2, 4>(S, [&](auto SS) {
+        for_values<0, 2, 1, 3>(quarter, [&](auto Q) {
+            constexpr bool kHalf = Q() == 2;
+            constexpr int kRot = (Q() & 1) ? Q() * 4 / SS() : 0;
+            for_block_variants(nt, r4, p, [&](auto NT, auto R4, auto P) {
+                f(SS, NT, R4, std::integral_constant<bool, kHalf>{}, std::integral_constant<int, kRot>{}, P);
+            });
+        });
+    });
+}
+
 hipError_t init_block_narrow_kernels()
 {
     hipError_t e = hipSuccess;
-#define FDC_SETN(S, A, B, H, Q, P) \
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_blknar<S, A, B, H, Q, P>), hipFuncAttributeMaxDynamicSharedMemorySize, NarGeom<S, P>::kLds);
-#define FDC_SETNS(S, H, Q, P) FDC_SETN(S, true, false, H, Q, P) FDC_SETN(S, false, false, H, Q, P) FDC_SETN(S, true, true, H, Q, P) FDC_SETN(S, false, true, H, Q, P)
-#define FDC_SETNP(P) \
-    FDC_SETNS(2, false, 0, P) FDC_SETNS(2, true, 0, P) FDC_SETNS(2, false, 2, P) FDC_SETNS(2, false, 6, P) \
-    FDC_SETNS(4, false, 0, P) FDC_SETNS(4, true, 0, P) FDC_SETNS(4, false, 1, P) FDC_SETNS(4, false, 3, P)
-    FDC_SETNP(8) FDC_SETNP(4) FDC_SETNP(2)
-#undef FDC_SETNP
-#undef FDC_SETNS
-#undef FDC_SETN
+    for_narrow_variants(kEvery, kEvery, kEvery, kEvery, kEvery, [&](auto S, auto NT, auto R4, auto H, auto ROT, auto P) {
+        if (e == hipSuccess)
+            e = set_block_lds(reinterpret_cast<const void *>(k_blknar<S(), NT() != 0, R4() != 0, H(), ROT(), P()>), NarGeom<S(), P()>::kLds);
+    });
     return e;
 }
 
-// r: the bank's offset from the l-bin grid: 0, l/4, l/2 (= half), 3l/4
-template <int P>
-static hipError_t launch_narrow_p(int L, const float2 *in, size_t in_stride, float2 *out, int nb_chunk, int mbase, int nb_call, const float2 *tab,
-                                  const float2 *cbt, const long long *slot_off, unsigned out_bytes, int grid, int hints, hipStream_t s,
-                                  hipEvent_t ev_start, hipEvent_t ev_stop, int R, float2 *scratch, int r)
+hipError_t launch_poly_block_narrow(const BlockLaunch &b)
 {
-    const int rows = R == 4 ? 3 * L / 4 : L / 2, quarter = r / (L / 4);
-#define FDC_LNAR(S, A, B, H, Q) \
-    hipExtLaunchKernelGGL((k_blknar<S, A, B, H, Q, P>), dim3((unsigned)grid), dim3(512), NarGeom<S, P>::kLds, s, ev_start, ev_stop, 0u, in, in_stride, out, tab, cbt, \
-                          slot_off, (long long)mbase * rows, (long long)nb_call, out_bytes, nb_chunk, hints, B ? scratch : (float2 *)nullptr)
-#define FDC_LNARH(S, H, Q) \
-    do { \
-        if (R == 4) { if (hints & 1) FDC_LNAR(S, true, true, H, Q); else FDC_LNAR(S, false, true, H, Q); } \
-        else { if (hints & 1) FDC_LNAR(S, true, false, H, Q); else FDC_LNAR(S, false, false, H, Q); } \
-    } while (0)
-    if (L == 128) {
-        if (quarter == 2) FDC_LNARH(2, true, 0); else if (quarter == 1) FDC_LNARH(2, false, 2); else if (quarter == 3) FDC_LNARH(2, false, 6); else FDC_LNARH(2, false, 0);
-    } else {
-        if (quarter == 2) FDC_LNARH(4, true, 0); else if (quarter == 1) FDC_LNARH(4, false, 1); else if (quarter == 3) FDC_LNARH(4, false, 3); else FDC_LNARH(4, false, 0);
-    }
-#undef FDC_LNARH
-#undef FDC_LNAR
-    return hipGetLastError();
-}
-
-hipError_t launch_poly_block_narrow(int L, const float2 *in, size_t in_stride, float2 *out, int nb_chunk, int mbase, int nb_call, const float2 *tab,
-                                    const float2 *cbt, const long long *slot_off, unsigned out_bytes, int ncu, int hints, hipStream_t s,
-                                    hipEvent_t ev_start, hipEvent_t ev_stop, int R, float2 *scratch, int r, int N)
-{
-    if (nb_chunk <= 0) return hipSuccess;
-    if (!poly_block_narrow_supports(N, L, R) || (R == 4 && !scratch) || r < 0 || r >= L || (r % (L / 4))) return hipErrorInvalidValue;
-    int grid = ncu > 0 ? ncu : 256;
-    if (grid > nb_chunk) grid = nb_chunk;
-    switch (N) {
-    case 65536: return launch_narrow_p<8>(L, in, in_stride, out, nb_chunk, mbase, nb_call, tab, cbt, slot_off, out_bytes, grid, hints, s, ev_start, ev_stop, R, scratch, r);
-    case 32768: return launch_narrow_p<4>(L, in, in_stride, out, nb_chunk, mbase, nb_call, tab, cbt, slot_off, out_bytes, grid, hints, s, ev_start, ev_stop, R, scratch, r);
-    default: return launch_narrow_p<2>(L, in, in_stride, out, nb_chunk, mbase, nb_call, tab, cbt, slot_off, out_bytes, grid, hints, s, ev_start, ev_stop, R, scratch, r);
-    }
+    const int L = b.L;
+    if (b.nb_chunk <= 0) return hipSuccess;
+    if (!poly_block_narrow_supports(b.N, L, b.R) || (b.R == 4 && !b.scratch) || b.r < 0 || b.r >= L || (b.r % (L / 4))) return hipErrorInvalidValue;
+    const int rows = b.R == 4 ? 3 * L / 4 : L / 2;
+    hipError_t e = hipErrorInvalidValue;                        // stays if no instantiation matches
+    for_narrow_variants(256 / L, b.r / (L / 4), b.hints & 1, b.R == 4, b.N / 8192, [&](auto S, auto NT, auto R4, auto H, auto ROT, auto P) {
+        hipExtLaunchKernelGGL((k_blknar<S(), NT() != 0, R4() != 0, H(), ROT(), P()>), dim3((unsigned)b.grid()), dim3(512), NarGeom<S(), P()>::kLds, b.s,
+                              b.ev_start, b.ev_stop, 0u, b.in, b.in_stride, b.out, b.tab, b.cbt, b.slot_off, (long long)b.mbase * rows, (long long)b.nb_call,
+                              b.out_bytes, b.nb_chunk, b.hints, R4() ? b.scratch : (float2 *)nullptr);
+        e = hipGetLastError();
+    });
+    return e;
 }
 
 }  // namespace fdc

@@ -134,69 +134,73 @@ hipError_t launch_poly_stage1_generic(const float2 *in, size_t in_stride, float2
                                       const float2 *tw, int ntab, const float2 *t2, hipStream_t s);
 int poly_stage1_generic_tile_columns(int N, int L);
 
-// uniform plan, N = 16384 / 32768 / 65536, R = 2 or 4: the whole path in one kernel, one block per CU, G kept in registers (fdc_block256.hip).
-// hints: 1 = nt output stores, 2 = nt input loads.  ncu: compute units of the device (grid size).
+// ---- uniform plans, N = 16384 / 32768 / 65536, R = 2 or 4: the whole path in one kernel, one block per CU, G kept in registers
+// (fdc_block256.hip, fdc_block512.hip, fdc_block1024.hip, fdc_blocknarrow.hip; their shared core: fdc_blockcommon.hpp).
+// One launch of a bank's block kernel over a launch group: what every launcher below takes.
+struct BlockLaunch {
+    const float2 *in;            // first sample of the launch group's first block
+    size_t in_stride;            // samples from one block to the next
+    float2 *out;
+    int nb_chunk, mbase, nb_call;   // blocks of this launch, index of its first block in the call, blocks of the call
+    const long long *slot_off;   // [N / L]: where each channel slot's samples go (negative: unused)
+    unsigned out_bytes;          // whole output, < 4 GiB
+    int ncu;                     // compute units of the device (grid size)
+    int hints;                   // 1 = nt output stores, 2 = nt input loads
+    hipStream_t s;
+    hipEvent_t ev_start, ev_stop;   // timing: stamped by the dispatch itself (may be null)
+    int N, R;                    // block length; overlap 2 or 4
+    float2 *scratch;             // R = 4: ncu x 32768 points
+    int L, r;                    // channel width; common offset f mod L of the bank's channels (the tables hold it)
+    long long first_block;       // global index of block 0 of this launch (window phase of odd r, L = 256)
+    const float2 *cbt;           // L >= 256: [n1][L / 16] (-1)^n1 W_N^(n1 (b + r + 256 i)); narrow: [V][16] W_N^(S V (b + r))
+    const float *shn;            // [L] shape / N (L >= 256)
+    const float2 *tw256, *twq;   // W_256^k; [n1][16] W_N^(16 n1 q) (L >= 256)
+    const float2 *twl;           // L = 512: W_512^k, k < 256; L = 1024: W_1024^k, k < 1024
+    const float2 *tab;           // L = 128 / 64: the table image of poly_block_narrow_tables()
+
+    bool half() const { return r == L / 2; }                 // the bank half a channel off the grid: the on-grid kernels with their tables moved
+    int grid(int per_cu = 1) const                           // one 512-thread workgroup per CU (or per_cu), never more than there are blocks
+    {
+        const int g = (ncu > 0 ? ncu : 256) * per_cu;
+        return g > nb_chunk ? nb_chunk : g;
+    }
+};
+
+// L = 256 (fdc_block256.hip): any offset r; cbt must hold (-1)^n1 W_N^(n1 (b + r))
 hipError_t init_block_kernels();
-hipError_t launch_poly_block(const float2 *in, size_t in_stride, float2 *out, int nb_chunk, int mbase, int nb_call,
-                             const float2 *tw256, const float2 *twq, const float2 *cbt, const float *shn,
-                             const long long *slot_off, unsigned out_bytes, int ncu, int hints, hipStream_t s,
-                             int r = 0 /* common offset f mod 256 of the channels; cbt must then hold (-1)^n1 W_N^(n1 (b + r)) */,
-                             long long first_block = 0 /* global index of block 0 of this launch (window phase of odd r) */,
-                             hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr /* timing: stamped by the dispatch itself */,
-                             int R = 2 /* 2 or 4 */, float2 *scratch = nullptr /* R = 4: ncu x 32768 points */,
-                             int N = 65536 /* block length: 16384, 32768 or 65536 (poly_block_supports) */);
-// the same on complex integer input (fmt: kIqSc16 / kIqSc8, fdc_iq.hpp; in_stride in samples), widened in the kernel's loads (the channelizer forms)
-hipError_t launch_poly_block_iq(int fmt, float scale, const void *in, size_t in_stride, float2 *out, int nb_chunk, int mbase, int nb_call,
-                                const float2 *tw256, const float2 *twq, const float2 *cbt, const float *shn,
-                                const long long *slot_off, unsigned out_bytes, int ncu, int hints, hipStream_t s,
-                                int r, long long first_block, hipEvent_t ev_start, hipEvent_t ev_stop, int R, float2 *scratch, int N);
-// integer OUTPUT (ofmt: kIqSc16 / kIqSc8 with its scale; out_bytes: the narrow extent), narrowed in the kernel's stores, on input ifmt (kIqFloat: float2,
-// or kIqSc16 / kIqSc8 with iscale); streamed stores only (hints bit 0 set)
-hipError_t launch_poly_block_oq(int ifmt, float iscale, const void *in, size_t in_stride, int ofmt, float oscale, void *out, int nb_chunk, int mbase,
-                                int nb_call, const float2 *tw256, const float2 *twq, const float2 *cbt, const float *shn,
-                                const long long *slot_off, unsigned out_bytes, int ncu, int hints, hipStream_t s,
-                                int r, long long first_block, hipEvent_t ev_start, hipEvent_t ev_stop, int R, float2 *scratch, int N);
+hipError_t launch_poly_block(const BlockLaunch &b);
+// the same on complex integer input (fmt: kIqSc16 / kIqSc8, fdc_iq.hpp; in_stride in samples), widened in the kernel's loads; b.in is not read
+hipError_t launch_poly_block_iq(const BlockLaunch &b, int fmt, float scale, const void *in);
+// integer OUTPUT (ofmt: kIqSc16 / kIqSc8 with its scale; b.out_bytes: the narrow extent), narrowed in the kernel's stores, on input ifmt (kIqFloat: float2,
+// or kIqSc16 / kIqSc8 with iscale); streamed stores only (hints bit 0 set); b.in and b.out are not read
+hipError_t launch_poly_block_oq(const BlockLaunch &b, int ifmt, float iscale, const void *in, int ofmt, float oscale, void *out);
 bool poly_block_supports(int N);
 
-// uniform plan of 512-bin channels on the 512-bin grid, N = 65536, R = 2 or 4: one kernel, one block per CU (fdc_block512.hip): the two
-// parities of a column's 512 rows run the 256-point machinery side by side in the lanes of a quad.
-//   tw512[k] = W_512^k (k < 256); twq[n1][q] = W_N^(16 n1 q) (128 x 16); cbt[n1][b + 16 h] = (-1)^n1 W_N^(n1 (b + 256 h)) (128 x 32);
-//   shn[k2] = shape[k2] / N (512); slot_off[128]
+// L = 512 on the 512-bin grid or half a channel off it (fdc_block512.hip): the two parities of a column's 512 rows run the 256-point machinery side by
+// side in the lanes of a quad.
+//   twl[k] = W_512^k (k < 256); twq[n1][q] = W_N^(16 n1 q) (N/512 x 16); cbt[n1][b + 16 h] = (-1)^n1 W_N^(n1 (b + 256 h)) (N/512 x 32);
+//   shn[k2] = shape[k2] / N (512); half: shn and cbt with their halves swapped, W_N^(256 n1) in cbt
 hipError_t init_block512_kernels();
-hipError_t launch_poly_block512(const float2 *in, size_t in_stride, float2 *out, int nb_chunk, int mbase, int nb_call, const float2 *tw256,
-                                const float2 *tw512, const float2 *twq, const float2 *cbt, const float *shn, const long long *slot_off,
-                                unsigned out_bytes, int ncu, int hints, hipStream_t s, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr,
-                                int R = 2 /* 2 or 4 */, float2 *scratch = nullptr /* R = 4: ncu x 32768 points */,
-                                bool half = false /* the bank at f = 512 slot + 256: shn and cbt with their halves swapped, W_N^(256 n1) in cbt */,
-                                int N = 65536 /* block length: 16384, 32768 or 65536 (poly_block512_supports) */);
+hipError_t launch_poly_block512(const BlockLaunch &b);
 bool poly_block512_supports(int N, int R);
 
-// uniform plan of 1024-bin channels on the 1024-bin grid, N = 65536, R = 2 or 4: one kernel, one block per CU (fdc_block1024.hip): the four phases of a
-// column's 1024 rows run the 256-point machinery side by side in the lanes of a quad.
-//   tw1024[k] = W_1024^k (k < 1024); twq[n1][q] = W_N^(16 n1 q) (64 x 16); cbt[n1][b + 16 i] = (-1)^n1 W_N^(n1 (b + 256 i)) (64 x 64);
-//   shn[k2] = shape[k2] / N (1024); slot_off[64]
+// L = 1024 on the 1024-bin grid or half a channel off it (fdc_block1024.hip): the four phases of a column's 1024 rows run the 256-point machinery side
+// by side in the lanes of a quad.  scratch (R = 4): ncu x 16384 points.
+//   twl[k] = W_1024^k (k < 1024); twq[n1][q] = W_N^(16 n1 q) (N/1024 x 16); cbt[n1][b + 16 i] = (-1)^n1 W_N^(n1 (b + 256 i)) (N/1024 x 64);
+//   shn[k2] = shape[k2] / N (1024); half: the quarters of shn and cbt moved by two, W_N^(512 n1) in cbt
 hipError_t init_block1024_kernels();
-hipError_t launch_poly_block1024(const float2 *in, size_t in_stride, float2 *out, int nb_chunk, int mbase, int nb_call, const float2 *tw256,
-                                 const float2 *tw1024, const float2 *twq, const float2 *cbt, const float *shn, const long long *slot_off,
-                                 unsigned out_bytes, int ncu, int hints, hipStream_t s, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr,
-                                 bool half = false /* the bank at f = 1024 slot + 512: the quarters of shn and cbt moved by two, W_N^(512 n1) in cbt */,
-                                 int R = 2 /* 2 or 4 */, float2 *scratch = nullptr /* R = 4: ncu x 16384 points */,
-                                 int N = 65536 /* block length: 16384, 32768 or 65536 (poly_block1024_supports) */);
+hipError_t launch_poly_block1024(const BlockLaunch &b);
 bool poly_block1024_supports(int N, int R);
 
-// uniform plan of narrow channels (l = 128 or 64 bins on the l-bin grid), N = 16384 / 32768 / 65536, R = 2 or 4: one kernel, one block per CU
-// (fdc_blocknarrow.hip): S = 256/l adjacent columns interleaved into one 256-point virtual column, separated and re-joined in registers.
-//   tab = the table image of poly_block_narrow_tables() (shn[k2] = shape[k2] / N, l values); cbt[V][b] = W_N^(S V b) (N/256 x 16); slot_off[N / l]
+// narrow channels, L = 128 or 64, r = 0, L/4, L/2, 3L/4 (fdc_blocknarrow.hip): S = 256/L adjacent columns interleaved into one 256-point virtual column,
+// separated and re-joined in registers.  scratch (R = 4): ncu x 16384 points.
+//   tab = the table image of poly_block_narrow_tables() (shn[k2] = shape[k2] / N, L values); cbt[V][b] = W_N^(S V b) (N/256 x 16); slot_off[N / L]
 bool poly_block_narrow_supports(int N, int L, int R);
 hipError_t init_block_narrow_kernels();
 int poly_block_narrow_table_points(int L, int N);
 void poly_block_narrow_tables(int L, int N, const float *shn, float2 *img, bool half = false /* the bank at f = l slot + l/2; cbt then W_N^(S V (b + l/2)) */,
                               int r = 0 /* l/4 or 3l/4 (not with half): the bank at f = l slot + r; cbt then W_N^(S V (b + r)) */);
-hipError_t launch_poly_block_narrow(int L, const float2 *in, size_t in_stride, float2 *out, int nb_chunk, int mbase, int nb_call, const float2 *tab,
-                                    const float2 *cbt, const long long *slot_off, unsigned out_bytes, int ncu, int hints, hipStream_t s,
-                                    hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr, int R = 2 /* 2 or 4 */,
-                                    float2 *scratch = nullptr /* R = 4: ncu x 16384 points */,
-                                    int r = 0 /* the bank's offset from the l-bin grid: 0, l/4, l/2, 3l/4 (tables to match) */, int N = 65536);
+hipError_t launch_poly_block_narrow(const BlockLaunch &b);
 
 // forward transform of N-sample blocks (N = 16384 / 32768 / 65536) with the block kernel (both halves of k2 in one launch): shifted, 1/N-scaled spectrum
 hipError_t launch_block_fft(int N, const float2 *in, size_t in_stride, float2 *out, int nitems, const float2 *tw256,
