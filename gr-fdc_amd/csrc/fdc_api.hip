@@ -46,6 +46,7 @@ int fail(int code, const char *fmt, ...)
         hipError_t _e = (expr);                                                                        \
         if (_e != hipSuccess) return fail(FDC_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(_e)); \
     } while (0)
+#define RCCHK(expr) do { const int _rc = (expr); if (_rc != FDC_OK) return _rc; } while (0)   // a callee's status (it has set the error text)
 
 // body of an extern "C" entry: nothing thrown inside crosses the C boundary (fdc_guard.hpp)
 #define FDC_ENTRY(name) return fdc::guarded(name, [&]() -> int {
@@ -180,7 +181,7 @@ struct fdc_pipeline {
     int block_min = kBlockMinBlocks;   // FDC_BLOCK_MIN_BLOCKS (tests: 1 = the block kernels at any size)
     float2 *d_g = nullptr;                       // uniform path (two launches): stage-1 output G, chunk*lout*N/256 samples
     int ncu = 0;                                 // compute units of the handle's device
-    int reserved_cu = 0;                         // fdc_pipeline_reserve_compute_units: left out of the persistent kernels' grids
+    int reserved_cu = 0;                         // what fdc_pipeline_reserve_compute_units stored (nothing else writes it): left out of the persistent kernels' grids
     float2 *d_twq = nullptr;                     // banks of 256-bin channels: W_N^(16 n1 q)
     // N = 65536 spectrum path: forward transform by the block kernel (fdc_block256.hip, FWD), own r = 0 tables
     bool fwd_block = false;
@@ -240,16 +241,7 @@ struct fdc_pipeline {
     hipEvent_t ev_hier = nullptr;   // on the bank's fill stream behind the last call's transform and history copy: the ring may be overwritten
     bool hier_ring_busy = false;
     bool hier_broken = false;    // a pipelined call failed after it had advanced the stream state: the pair of handles cannot go on (see work_sinks_pipelined)
-    bool reserve_user = false;   // fdc_pipeline_reserve_compute_units was called: the pipelined entry leaves the reservation alone
-    // fdc_pipeline_process_device_power: where the power of the spectrum's 16-bin groups goes (the sinks' cells are summed from it): group sums of
-    // the block whose spectrum starts at gpow_spec + k N go to gpow_base + k N / 16.  Set for the duration of one call.
-    float *gpow_base = nullptr;
-    const float2 *gpow_spec = nullptr;
-    // fdc_pipeline_work_waterfall: the row sums of the call's blocks go to wf_rows + (block - wf_first) * 1024 (path 5: the fused kernel's epilogue);
-    // wf_spec: the call writes the internal spectrum the rows are summed from (other paths), without keep_spectrum.  Set for the duration of one call.
-    float *wf_rows = nullptr;
-    int64_t wf_first = 0;
-    bool wf_spec = false;
+    bool reserve_user = false;   // fdc_pipeline_reserve_compute_units was called with n > 0: the pipelined entry takes that reservation, not its own
     std::string wf_route;        // the route of the last waterfall call (fdc_pipeline_describe)
     bool cfg_generic = false;    // FDC_FORCE_GENERIC=1: bypass the size-specialised kernels (A/B testing)
     // timing
@@ -1183,18 +1175,55 @@ static int get_event(fdc_pipeline *p, size_t *idx)
     return FDC_OK;
 }
 
+namespace {
+// One launch group of a call: blocks [m0, m0 + nb) of the call's nblocks; first_block: the stream's index of the call's block 0.  The kernels place
+// the group's samples in the CALL's output by m0 and nblocks.
+struct Span { int nb, m0, nblocks; int64_t first_block; };
+
+// What one call brings to the enqueue path: the entry fills it (device_call), everything below process_device_impl reads it, and the two results come
+// back in it.  Nothing per call is parked on the handle, so no call can leave anything behind for the next.  Plain members: making one allocates nothing.
+struct DeviceCall {
+    // input form.  fmt: 0 = float2 ring; FDC_IQ_SC16 / FDC_IQ_SC8: a ring of complex integers (scale: their factor), and `wide` the float2 buffer of
+    // chunk*H + ovl samples a launch group is widened into where the kernels take float input
+    int fmt = 0; float scale = 1.0f; float2 *wide = nullptr;
+    // output form.  ofmt: 0 = complex float into d_out; FDC_OQ_SC16 / FDC_OQ_SC8 (times oscale): narrow samples into d_out (same offsets).  Kernels that do not
+    // narrow themselves (oq_fused) write float into fout (nblocks*sum_lout samples); k_complex_to_iq narrows it into d_out unless narrow is false (the caller does)
+    int ofmt = 0; float oscale = 1.0f; float2 *fout = nullptr; bool narrow = true;
+    hipStream_t stream = nullptr;        // every launch of the call
+    void *spectrum = nullptr;            // the caller's spectrum buffer for the blocks of this invocation, or none
+    bool own_spectrum = false;           // `spectrum` is the entry's own staging (waterfall): allowed without keep_spectrum
+    // group powers (fdc_pipeline_process_device_power): the 16-bin group sums of the block whose spectrum starts at gpow_origin + k N go to gpow + k N / 16
+    float *gpow = nullptr; const float2 *gpow_origin = nullptr;
+    // waterfall rows (path 5: the fused kernel's epilogue): the row sums of the stream's block b go to rows + (b - rows_first) * 1024
+    float *rows = nullptr; int64_t rows_first = 0;
+    int ncu = 0;                         // compute units the call's persistent kernels may use
+    // results: no launch group had to be widened (each read the integer input in its own loads); the call's kernels narrowed in their own stores
+    bool all_fused = true, ofused = false;
+};
+}  // namespace
+
+static DeviceCall device_call(const fdc_pipeline *p, void *stream, void *d_spectrum, int fmt = 0, float scale = 1.0f)
+{
+    DeviceCall call;
+    call.fmt = fmt; call.scale = scale;
+    call.stream = stream ? static_cast<hipStream_t>(stream) : p->stream;
+    call.spectrum = d_spectrum;
+    call.ncu = p->ncu - p->reserved_cu;
+    return call;
+}
+
 // Channels wider than 4096 bins: all channels of one width and all blocks of the launch group as ONE batch of the task-addressed two-pass
 // inverse transform (fdc_kernels.hip: pass A reads slice * window straight from the spectrum, the ifftshift is its input rotation; pass B
 // writes the kept samples, times l, into the channel streams) — in pieces of up to 32 Mi points of scratch between the passes.
 // gids: the group's channel ids in the device list p->d_groups.
-static int channels_wide(fdc_pipeline *p, const float2 *spec, float2 *d_out, const int32_t *d_gids, int ngroup, int l, int nb,
-                         int mbase, int nb_call, int64_t first_block, hipStream_t s)
+static int channels_wide(fdc_pipeline *p, const float2 *spec, float2 *d_out, const int32_t *d_gids, int ngroup, int l, const Span &span, hipStream_t s)
 {
+    const int nb = span.nb;
     const int per = (int)std::max<long long>(1, std::min<long long>(nb, (long long)p->big_pts / ((long long)ngroup * l)));   // blocks per piece
     const int lout = l - l / p->R;
     for (int m0 = 0; m0 < nb; m0 += per) {
         const int n = std::min(per, nb - m0);
-        HIPCHK(fdc::launch_wide_tasks(p->d_wtasks, p->d_chans, d_gids, ngroup, p->R, n, mbase + m0, nb_call, first_block, s));
+        HIPCHK(fdc::launch_wide_tasks(p->d_wtasks, p->d_chans, d_gids, ngroup, p->R, n, span.m0 + m0, span.nblocks, span.first_block, s));
         HIPCHK(fdc::launch_extract_wide(spec + (size_t)m0 * p->N, p->N, p->d_wtasks, n * ngroup, l, l - lout, p->d_wins, p->d_big, d_out, p->d_tw, p->ntab, s,
                                         (float)l));
     }
@@ -1202,8 +1231,7 @@ static int channels_wide(fdc_pipeline *p, const float2 *spec, float2 *d_out, con
 }
 
 // The channel kernels of one launch group over the plan's channels by width (rem: over the remainder of a split plan only)
-static int run_channel_groups(fdc_pipeline *p, bool rem, const float2 *spec, float2 *d_out, int nb, int m0, int nblocks, int64_t first_block,
-                              hipStream_t s)
+static int run_channel_groups(fdc_pipeline *p, bool rem, const float2 *spec, float2 *d_out, const Span &span, hipStream_t s)
 {
     const auto &groups = rem ? p->rgroups : p->groups;
     const auto &off = rem ? p->rgroup_off : p->group_off;
@@ -1212,30 +1240,30 @@ static int run_channel_groups(fdc_pipeline *p, bool rem, const float2 *spec, flo
     const int32_t *ids = rem ? p->d_rgroups : p->d_groups;
     for (size_t g = 0; g < groups.size(); g++) {
         const int l = groups[g].first, ng = (int)groups[g].second.size();
-        if (l > 4096) {
-            const int rcw = channels_wide(p, spec, d_out, ids + off[g], ng, l, nb, m0, nblocks, first_block, s);
-            if (rcw != FDC_OK) return rcw;
-        } else if (l == 256 && ((256 / p->R) & 1) == 0 && !p->cfg_generic)
-            HIPCHK(fdc::launch_channels256(spec, d_out, p->d_chans, ids + off[g], ng, al[g] != 0, oal[g] != 0, p->N, p->R, nb, m0, nblocks, first_block,
-                                           p->d_wins, p->d_tw256, s));
+        if (l > 4096)
+            RCCHK(channels_wide(p, spec, d_out, ids + off[g], ng, l, span, s));
+        else if (l == 256 && ((256 / p->R) & 1) == 0 && !p->cfg_generic)
+            HIPCHK(fdc::launch_channels256(spec, d_out, p->d_chans, ids + off[g], ng, al[g] != 0, oal[g] != 0, p->N, p->R, span.nb, span.m0, span.nblocks,
+                                           span.first_block, p->d_wins, p->d_tw256, s));
         else if ((l == 512 || l == 1024) && l <= p->N && !p->cfg_generic)
-            HIPCHK(fdc::launch_channels_wide(spec, d_out, p->d_chans, ids + off[g], ng, l, p->N, p->R, nb, m0, nblocks, first_block, p->d_wins, p->d_tw,
-                                             p->ntab, s));
+            HIPCHK(fdc::launch_channels_wide(spec, d_out, p->d_chans, ids + off[g], ng, l, p->N, p->R, span.nb, span.m0, span.nblocks, span.first_block,
+                                             p->d_wins, p->d_tw, p->ntab, s));
         else
-            HIPCHK(fdc::launch_channels(spec, d_out, p->d_chans, ids + off[g], ng, l, p->N, p->R, nb, m0, nblocks, first_block, p->d_wins, p->d_tw,
-                                        p->ntab, s));
+            HIPCHK(fdc::launch_channels(spec, d_out, p->d_chans, ids + off[g], ng, l, p->N, p->R, span.nb, span.m0, span.nblocks, span.first_block, p->d_wins,
+                                        p->d_tw, p->ntab, s));
     }
     return FDC_OK;
 }
 
 // The remainder of a split plan for one launch group: forward transform into the handle's internal (partial) spectrum, channel kernels
 // over the remainder's groups.  ev2 / ev3 (timing): recorded behind the forward transform and behind the channel kernels.
-static int run_remainder(fdc_pipeline *p, const float2 *in0, int m0, int nb, int nblocks, int64_t first_block, float2 *d_out, bool few,
-                         hipStream_t s, hipEvent_t ev2, hipEvent_t ev3)
+static int run_remainder(fdc_pipeline *p, const DeviceCall &call, const float2 *in0, float2 *d_out, const Span &span, hipEvent_t ev2, hipEvent_t ev3)
 {
-    if (p->fwd_block && !few)
+    hipStream_t s = call.stream;
+    const int nb = span.nb;
+    if (p->fwd_block && nb >= p->block_min)
         HIPCHK(fdc::launch_block_fft(p->N, in0, (size_t)p->H, p->d_spec, nb, p->d_tw256, p->d_ftwq, p->d_fcbt, p->d_fshn,
-                                          p->d_fslot, p->d_fscr, p->ncu - p->reserved_cu, p->block_hints, s, nullptr, p->d_keep));
+                                          p->d_fslot, p->d_fscr, call.ncu, p->block_hints, s, nullptr, p->d_keep));
     else if (p->N == 65536)
         HIPCHK(fdc::launch_fft65536(in0, (size_t)p->H, p->d_spec, p->d_tmp, nb, p->N / 2, 1.0f / (float)p->N, p->d_tw256,
                                     p->d_twf, s, nullptr));
@@ -1243,8 +1271,7 @@ static int run_remainder(fdc_pipeline *p, const float2 *in0, int m0, int nb, int
         HIPCHK(fdc::launch_fft(in0, (size_t)p->H, p->d_spec, p->d_tmp, p->N, nb, false, 0, p->N / 2, 1.0f / (float)p->N, p->d_tw, p->ntab,
                                s, nullptr, p->d_twf, p->cfg_generic));
     if (ev2) HIPCHK(hipEventRecord(ev2, s));
-    const int rc = run_channel_groups(p, true, p->d_spec, d_out, nb, m0, nblocks, first_block, s);
-    if (rc != FDC_OK) return rc;
+    RCCHK(run_channel_groups(p, true, p->d_spec, d_out, span, s));
     if (ev3) HIPCHK(hipEventRecord(ev3, s));
     return FDC_OK;
 }
@@ -1253,33 +1280,29 @@ static int run_remainder(fdc_pipeline *p, const float2 *in0, int m0, int nb, int
 enum { kSpanBanks = 0 /* banks | remainder forward | remainder channels */, kSpanTwoLaunch = 1 /* stage 1 | - | stage 2 (+ remainder) */,
        kSpanSpectrumLds = 2 /* forward transform = a + b | channels */, kSpanSpectrum = 3 /* pass A / block forward | pass B | channels */ };
 
-// one launch of the bank's block kernel over the launch group (ev0 / ev1: stamped by the dispatch itself, may be null)
-// fmt != 0: in0 is complex integer input (raw: the launch group's first sample), read by the 256-bin kernel itself
-// ofmt != 0: the 256-bin kernel narrows in its stores into oq (out_bytes: the narrow extent), o is not written
-static int launch_bank(fdc_pipeline *p, const fdc_pipeline::Bank &bk, const float2 *in0, float2 *o, int nb, int m0, int nblocks, int64_t first_block,
-                       unsigned out_bytes, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1, int fmt = 0, float scale = 1.0f, const void *raw = nullptr,
-                       int ofmt = 0, float oscale = 1.0f, void *oq = nullptr)
+// one launch of the bank's block kernel over a launch group.  b: the group's part of the launch (input, output, its blocks, the events the dispatch itself
+// stamps); the handle's and the bank's part is filled in here.  raw: the group's first integer sample where the 256-bin kernel reads the call's integer
+// input itself (null: float samples, b.in); oq: the call's narrow output where it narrows in its stores (b.out_bytes: the narrow extent; null: float, b.out)
+static int launch_bank(fdc_pipeline *p, const DeviceCall &call, const fdc_pipeline::Bank &bk, fdc::BlockLaunch b, const void *raw, void *oq)
 {
-    fdc::BlockLaunch b{};
-    b.in = in0; b.in_stride = (size_t)p->H; b.out = o;
-    b.nb_chunk = nb; b.mbase = m0; b.nb_call = nblocks;
-    b.slot_off = bk.d_slot_off; b.out_bytes = out_bytes;
-    b.ncu = p->ncu - p->reserved_cu; b.hints = p->block_hints;
-    b.s = s; b.ev_start = ev0; b.ev_stop = ev1;
+    b.in_stride = (size_t)p->H;
+    b.slot_off = bk.d_slot_off;
+    b.ncu = call.ncu; b.hints = p->block_hints;
+    b.s = call.stream;
     b.N = p->N; b.R = p->R; b.scratch = p->d_fscr;
-    b.L = bk.L; b.r = bk.r; b.first_block = first_block + m0;
+    b.L = bk.L; b.r = bk.r;
     b.cbt = bk.d_cbt; b.shn = bk.d_shn; b.tab = bk.d_tab;
     b.tw256 = p->d_tw256;
     b.twq = bk.L == 512 ? p->d_twq512 : bk.L == 1024 ? p->d_twq1k : p->d_twq;
     b.twl = bk.L == 512 ? p->d_tw512 : bk.L == 1024 ? p->d_tw1k : nullptr;
-    if (ofmt) {
+    if (oq) {
         if (bk.L != 256) return fail(FDC_ERR_UNSUPPORTED, "integer stores in a %d-bin bank", bk.L);
-        HIPCHK(fdc::launch_poly_block_oq(b, fmt, scale, fmt ? raw : static_cast<const void *>(in0), ofmt, oscale, oq));
+        HIPCHK(fdc::launch_poly_block_oq(b, raw ? call.fmt : 0, call.scale, raw ? raw : static_cast<const void *>(b.in), call.ofmt, call.oscale, oq));
         return FDC_OK;
     }
-    if (fmt) {
+    if (raw) {
         if (bk.L != 256) return fail(FDC_ERR_UNSUPPORTED, "integer loads in a %d-bin bank", bk.L);
-        HIPCHK(fdc::launch_poly_block_iq(b, fmt, scale, raw));
+        HIPCHK(fdc::launch_poly_block_iq(b, call.fmt, call.scale, raw));
         return FDC_OK;
     }
     switch (bk.L) {
@@ -1291,84 +1314,85 @@ static int launch_bank(fdc_pipeline *p, const fdc_pipeline::Bank &bk, const floa
     return FDC_OK;
 }
 
-// whether a launch group of the plan reads integer input in its own loads: path 5 (k_f4096) and the banks of 256-bin channels (k_blk256) without
-// a remainder; every other form reads a float ring the group is widened into first (k_iq_to_complex)
-static bool iq_fused(const fdc_pipeline *p, bool spectrum, bool few)
+// whether the plan's kernels take complex integers themselves, in their loads or their stores: path 5 (k_f4096) and the banks of 256-bin channels
+// (k_blk256) without a remainder — not with a spectrum or waterfall rows to write
+static bool int_kernels(const fdc_pipeline *p, const DeviceCall &call)
 {
-    if (spectrum || p->wf_rows || p->cfg_generic) return false;
+    if (call.spectrum || call.rows || p->cfg_generic) return false;
     if (p->fused) return true;
-    if (!p->poly_ok || !p->poly_block || p->split || (few && two_launch_possible(p))) return false;
+    if (!p->poly_ok || !p->poly_block || p->split) return false;
     for (const auto &b : p->banks) if (b.L != 256) return false;
     return true;
 }
 
-// integer output: whether EVERY launch group of a call of nblocks narrows in its own kernel's stores — path 5 (k_f4096) and the banks of 256-bin channels
-// (k_blk256, streamed stores; not N = 65536 at R = 4 on float input, whose forms would spill: fdc_block256.hip kOqR4Narrowed) without a remainder;
-// otherwise the call writes complex float and k_complex_to_iq narrows it (whole call: one layout).  fmt: the input form.
-static bool oq_fused(const fdc_pipeline *p, int fmt, bool spectrum, int nblocks)
+// integer input: whether a launch group (few: shorter than block_min) reads it in its own loads; every other form reads a float ring the group is
+// widened into first (k_iq_to_complex)
+static bool iq_fused(const fdc_pipeline *p, const DeviceCall &call, bool few)
 {
-    if (spectrum || p->wf_rows || p->cfg_generic) return false;
+    return int_kernels(p, call) && (p->fused || !(few && two_launch_possible(p)));
+}
+
+// integer output: whether EVERY launch group of a call of nblocks narrows in its own kernel's stores (k_blk256: streamed stores; not N = 65536 at R = 4
+// on float input, whose forms would spill: fdc_block256.hip kOqR4Narrowed); otherwise the call writes complex float and k_complex_to_iq narrows it
+// (whole call: one layout)
+static bool oq_fused(const fdc_pipeline *p, const DeviceCall &call, int nblocks)
+{
+    if (!int_kernels(p, call)) return false;
     if (p->fused) return true;
-    if (!p->poly_ok || !p->poly_block || p->split || !(p->block_hints & 1)) return false;
-    if (!fmt && p->N == 65536 && p->R == 4) return false;
-    for (const auto &b : p->banks) if (b.L != 256) return false;
+    if (!(p->block_hints & 1) || (!call.fmt && p->N == 65536 && p->R == 4)) return false;
     for (int m0 = 0; m0 < nblocks; m0 += p->chunk)
         if (std::min(p->chunk, nblocks - m0) < p->block_min && two_launch_possible(p)) return false;
     return true;
 }
 
-// fmt: 0 = float2 ring; FDC_IQ_SC16 / FDC_IQ_SC8: a ring of complex integers (scale: their factor), and `wide` the float2 buffer of chunk*H + ovl
-// samples a launch group is widened into where the kernels take float input.
-// ofmt: 0 = complex float output into d_out; FDC_OQ_SC16 / FDC_OQ_SC8 (times oscale): d_out receives the narrow samples (same offsets).  Where the call's
-// kernels do not narrow themselves (oq_fused) they write complex float into fout (nblocks*sum_lout samples) and k_complex_to_iq narrows it into d_out —
-// unless narrow is false (the caller narrows fout itself: the scatter into registered host buffers).  *ofused: which of the two it was.
-static int process_device_impl(fdc_pipeline *p, int fmt, float scale, const void *d_ring, int64_t first_block, int nblocks,
-                               void *d_out, void *d_spectrum, void *stream, float2 *wide, bool *all_fused,
-                               int ofmt = 0, float oscale = 1.0f, float2 *fout = nullptr, bool narrow = true, bool *ofused_out = nullptr)
+// The enqueue path of every entry: nblocks blocks from d_ring (the stream's block first_block first) to d_out, as `call` says; its results say how
+static int process_device_impl(fdc_pipeline *p, DeviceCall &call, const void *d_ring, int64_t first_block, int nblocks, void *d_out)
 {
-    if (!p) return fail(FDC_ERR_INVALID_ARGUMENT, "null handle");
     if (nblocks < 0 || first_block < 0) return fail(FDC_ERR_INVALID_ARGUMENT, "negative block count/index");
     if (nblocks == 0) return FDC_OK;
     if (!d_ring || (p->C > 0 && !d_out)) return fail(FDC_ERR_INVALID_ARGUMENT, "null device buffer");
-    if (d_spectrum && !p->cfg.keep_spectrum && !p->wf_spec) return fail(FDC_ERR_INVALID_ARGUMENT, "spectrum output needs keep_spectrum");
+    void *const d_spectrum = call.spectrum;
+    if (d_spectrum && !p->cfg.keep_spectrum && !call.own_spectrum) return fail(FDC_ERR_INVALID_ARGUMENT, "spectrum output needs keep_spectrum");
     // one call produces less than 4 GiB (32-bit output offsets; checked for max_blocks at create): a longer call is refused, not sent down
     // a path whose internal spectrum may be partial (a split plan's remainder-only spectrum under the channel kernels of ALL channels)
     if ((int64_t)nblocks * p->sum_lout * 8 > 0xFFFFF000ll)
         return fail(FDC_ERR_INVALID_ARGUMENT, "nblocks %d x %lld output samples per block is more than the 4 GiB one call may produce", nblocks, (long long)p->sum_lout);
     HIPCHK(hipSetDevice(p->cfg.device_id));
-    hipStream_t s = stream ? (hipStream_t)stream : p->stream;
+    hipStream_t s = call.stream;
+    const int fmt = call.fmt, ofmt = call.ofmt;
     const float2 *ring = static_cast<const float2 *>(d_ring);
     const unsigned char *iring = static_cast<const unsigned char *>(d_ring);
     const size_t esz = fdc::iq_bytes(fmt);
-    const bool ofused = ofmt && oq_fused(p, fmt, d_spectrum != nullptr, nblocks);
-    if (ofused_out) *ofused_out = ofused;
-    if (ofmt && !ofused && !fout) return fail(FDC_ERR_INVALID_ARGUMENT, "integer output: no float staging");
-    float2 *o = ofmt && !ofused ? fout : static_cast<float2 *>(d_out);
+    const bool ofused = ofmt && oq_fused(p, call, nblocks);
+    call.ofused = ofused;
+    if (ofmt && !ofused && !call.fout) return fail(FDC_ERR_INVALID_ARGUMENT, "integer output: no float staging");
+    float2 *o = ofmt && !ofused ? call.fout : static_cast<float2 *>(d_out);
     const size_t osz = ofused ? fdc::iq_bytes(ofmt) : sizeof(float2);       // bytes per sample the kernels store
     unsigned char *const ob = ofused ? static_cast<unsigned char *>(d_out) : reinterpret_cast<unsigned char *>(o);
     const bool use_poly = p->poly_ok && !d_spectrum;
     const unsigned out_bytes = (unsigned)((int64_t)nblocks * p->sum_lout * (int64_t)osz);
     for (int m0 = 0; m0 < nblocks; m0 += p->chunk) {
         const int nb = std::min(p->chunk, nblocks - m0);
+        const Span grp{nb, m0, nblocks, first_block};
         float2 *spec = d_spectrum ? static_cast<float2 *>(d_spectrum) + (size_t)m0 * p->N : p->d_spec;
         hipEvent_t ev[3]; hipEvent_t *evp = nullptr; std::array<size_t, 5> span{};
         // events on every timing_stride-th launch group only: a sample of the launches, so that the packets between the
         // kernels (measured 7-17 us per group) do not slow the region they time
         const bool tg = p->timing && (p->timing_seq++ % p->timing_stride) == 0;
         if (tg) {
-            for (int i = 0; i < 4; i++) { int rc = get_event(p, &span[i]); if (rc) return rc; }
+            for (int i = 0; i < 4; i++) RCCHK(get_event(p, &span[i]));
             for (int i = 0; i < 3; i++) ev[i] = p->events[span[i]];
             evp = ev;
         }
         const float2 *in0 = ring + (size_t)m0 * p->H;
         const void *raw0 = iring + (size_t)m0 * p->H * esz;
         const bool few = nb < p->block_min;
-        const bool ifused = fmt && iq_fused(p, d_spectrum != nullptr, few);
+        const bool ifused = fmt && iq_fused(p, call, few);
         if (fmt && !ifused) {
             // this launch group's samples (nb blocks and the history in front of the last one) widened into the float ring the kernels read
-            HIPCHK(fdc::launch_iq_to_complex(fmt, scale, raw0, wide, (size_t)nb * p->H + (size_t)p->ovl, s));
-            in0 = wide;
-            if (all_fused) *all_fused = false;
+            HIPCHK(fdc::launch_iq_to_complex(fmt, call.scale, raw0, call.wide, (size_t)nb * p->H + (size_t)p->ovl, s));
+            in0 = call.wide;
+            call.all_fused = false;
         }
         // overlap-save gather fused into the load (item m at ring + m*H), fftshift + 1/N into the store.
         // A block kernel gives a whole block to one compute unit: a launch group of fewer blocks than the device has compute
@@ -1377,12 +1401,12 @@ static int process_device_impl(fdc_pipeline *p, int fmt, float scale, const void
         if (p->fused && !d_spectrum) {
             // N = 4096: one launch, nothing but the input samples and the output samples crosses the memory interface
             if (tg) HIPCHK(hipEventRecord(p->events[span[0]], s));
-            float *wf = p->wf_rows ? p->wf_rows + (size_t)(first_block - p->wf_first + m0) * fdc::kWfWidth : nullptr;
+            float *wf = call.rows ? call.rows + (size_t)(first_block - call.rows_first + m0) * fdc::kWfWidth : nullptr;
             if (ofused)
-                HIPCHK(fdc::launch_fused4096_oq(ifused ? fmt : 0, scale, ifused ? raw0 : static_cast<const void *>(in0), (size_t)p->H, ofmt, oscale, d_out, nb, p->R,
-                                                m0, nblocks, first_block, p->d_tw, p->ntab, p->d_wins, p->d_f4rows, p->f4_cls, p->f4_teams, s));
+                HIPCHK(fdc::launch_fused4096_oq(ifused ? fmt : 0, call.scale, ifused ? raw0 : static_cast<const void *>(in0), (size_t)p->H, ofmt, call.oscale, d_out, nb,
+                                                p->R, m0, nblocks, first_block, p->d_tw, p->ntab, p->d_wins, p->d_f4rows, p->f4_cls, p->f4_teams, s));
             else if (ifused)
-                HIPCHK(fdc::launch_fused4096_iq(fmt, scale, raw0, (size_t)p->H, o, nb, p->R, m0, nblocks, first_block, p->d_tw, p->ntab, p->d_wins, p->d_f4rows,
+                HIPCHK(fdc::launch_fused4096_iq(fmt, call.scale, raw0, (size_t)p->H, o, nb, p->R, m0, nblocks, first_block, p->d_tw, p->ntab, p->d_wins, p->d_f4rows,
                                                 p->f4_cls, p->f4_teams, s));
             else
                 HIPCHK(fdc::launch_fused4096(in0, (size_t)p->H, o, nb, p->R, m0, nblocks, first_block, p->d_tw, p->ntab, p->d_wins, p->d_f4rows, p->f4_cls, p->f4_teams, s, wf));
@@ -1392,21 +1416,22 @@ static int process_device_impl(fdc_pipeline *p, int fmt, float scale, const void
         if (use_poly && p->poly_block && !(few && two_launch_possible(p))) {
             // one launch per bank: nothing but the input rows and the output samples crosses the memory interface.
             // timing: the first launch's begin and the last one's end are the dispatches' own stamps, no packets around the kernels
+            fdc::BlockLaunch b{};
+            b.in = in0; b.out = o;
+            b.nb_chunk = nb; b.mbase = m0; b.nb_call = nblocks;
+            b.first_block = first_block + m0; b.out_bytes = out_bytes;
             for (size_t k = 0; k < p->banks.size(); k++) {
-                const int rcb = launch_bank(p, p->banks[k], in0, o, nb, m0, nblocks, first_block, out_bytes, s,
-                                            tg && k == 0 ? p->events[span[0]] : nullptr, tg && k + 1 == p->banks.size() ? p->events[span[1]] : nullptr,
-                                            ifused ? fmt : 0, scale, raw0, ofused ? ofmt : 0, oscale, d_out);
-                if (rcb != FDC_OK) return rcb;
+                b.ev_start = tg && k == 0 ? p->events[span[0]] : nullptr;
+                b.ev_stop = tg && k + 1 == p->banks.size() ? p->events[span[1]] : nullptr;
+                RCCHK(launch_bank(p, call, p->banks[k], b, ifused ? raw0 : nullptr, ofused ? d_out : nullptr));
             }
             for (const auto &al : p->bank_alias) {
                 const fdc::ChanDev &dc = p->chans[(size_t)al.first], &sc = p->chans[(size_t)al.second];
                 HIPCHK(hipMemcpyAsync(ob + osz * ((size_t)nblocks * dc.out_off + (size_t)m0 * dc.lout), ob + osz * ((size_t)nblocks * sc.out_off + (size_t)m0 * sc.lout),
                                       osz * (size_t)nb * dc.lout, hipMemcpyDeviceToDevice, s));
             }
-            if (p->split) {
-                const int rcr = run_remainder(p, in0, m0, nb, nblocks, first_block, o, few, s, tg ? p->events[span[2]] : nullptr, tg ? p->events[span[3]] : nullptr);
-                if (rcr != FDC_OK) return rcr;
-            } else if (tg) span[2] = span[3] = span[1];
+            if (p->split) RCCHK(run_remainder(p, call, in0, o, grp, tg ? p->events[span[2]] : nullptr, tg ? p->events[span[3]] : nullptr));
+            else if (tg) span[2] = span[3] = span[1];
             if (tg) { span[4] = kSpanBanks; p->ev_spans.push_back(span); }
             continue;
         }
@@ -1417,18 +1442,15 @@ static int process_device_impl(fdc_pipeline *p, int fmt, float scale, const void
             if (bk.L != 256)
                 HIPCHK(fdc::launch_poly_stage1_generic(in0, (size_t)p->H, p->d_g, p->N, bk.L, p->R, nb, bk.d_shn, p->d_tw, p->ntab, p->d_t2g, s));
             else
-                HIPCHK(fdc::launch_poly_stage1(in0, (size_t)p->H, p->d_g, p->N / 256, p->R, nb, p->d_tw256, p->d_twq, bk.d_cbt, bk.d_shn, p->ncu - p->reserved_cu, s));
+                HIPCHK(fdc::launch_poly_stage1(in0, (size_t)p->H, p->d_g, p->N / 256, p->R, nb, p->d_tw256, p->d_twq, bk.d_cbt, bk.d_shn, call.ncu, s));
             if (tg) { HIPCHK(hipEventRecord(p->events[span[1]], s)); span[2] = span[1]; }   // the end of stage 1 IS the start of stage 2
             if (bk.L != 256)
                 HIPCHK(fdc::launch_poly_stage2_generic(p->d_g, o, p->N / bk.L, p->R, nb, m0, nblocks, bk.d_slot_off, p->d_tw, p->ntab, s, bk.L));
             else if (p->N != 65536 && p->N != 262144)
                 HIPCHK(fdc::launch_poly_stage2_generic(p->d_g, o, p->N / 256, p->R, nb, m0, nblocks, bk.d_slot_off, p->d_tw, p->ntab, s));
             else
-                HIPCHK(fdc::launch_poly_stage2(p->d_g, o, p->N / 256, p->R, nb, m0, nblocks, p->d_tw256, p->d_tw1024, bk.d_slot_off, out_bytes, p->ncu - p->reserved_cu, s));
-            if (p->split) {                                     // (timing: the remainder is counted with stage 2)
-                const int rcr = run_remainder(p, in0, m0, nb, nblocks, first_block, o, few, s, nullptr, nullptr);
-                if (rcr != FDC_OK) return rcr;
-            }
+                HIPCHK(fdc::launch_poly_stage2(p->d_g, o, p->N / 256, p->R, nb, m0, nblocks, p->d_tw256, p->d_tw1024, bk.d_slot_off, out_bytes, call.ncu, s));
+            if (p->split) RCCHK(run_remainder(p, call, in0, o, grp, nullptr, nullptr));   // (timing: the remainder is counted with stage 2)
             if (tg) {
                 HIPCHK(hipEventRecord(p->events[span[3]], s));
                 span[4] = kSpanTwoLaunch;
@@ -1440,10 +1462,10 @@ static int process_device_impl(fdc_pipeline *p, int fmt, float scale, const void
         // spectrum buffer — writes a full spectrum into THAT buffer, d_keep is not applied.)
         // the power of the 16-bin groups of the caller's spectrum (fdc_pipeline_process_device_power): summed by the block kernel while the bins are in
         // its registers; by a pass over the spectrum where another transform ran
-        float *const gp = (p->gpow_base && d_spectrum) ? p->gpow_base + (size_t)(spec - p->gpow_spec) / 16 : nullptr;
+        float *const gp = (call.gpow && d_spectrum) ? call.gpow + (size_t)(spec - call.gpow_origin) / 16 : nullptr;
         if (p->fwd_block && !few)
             HIPCHK(fdc::launch_block_fft(p->N, in0, (size_t)p->H, spec, nb, p->d_tw256, p->d_ftwq, p->d_fcbt,
-                                              p->d_fshn, p->d_fslot, p->d_fscr, p->ncu - p->reserved_cu, p->block_hints, s, evp, d_spectrum ? nullptr : p->d_keep, gp));
+                                              p->d_fshn, p->d_fslot, p->d_fscr, call.ncu, p->block_hints, s, evp, d_spectrum ? nullptr : p->d_keep, gp));
         else {
             if (p->N == 65536 && !p->cfg_generic)
                 HIPCHK(fdc::launch_fft65536(in0, (size_t)p->H, spec, p->d_tmp, nb, p->N / 2,
@@ -1453,35 +1475,37 @@ static int process_device_impl(fdc_pipeline *p, int fmt, float scale, const void
                                        1.0f / (float)p->N, p->d_tw, p->ntab, s, evp, p->d_twf, p->cfg_generic, d_spectrum ? ~0ull : p->keep4096));
             if (gp) HIPCHK(fdc::launch_group_power(spec, p->N, nb, gp, s));
         }
-        { const int rcc = run_channel_groups(p, false, spec, o, nb, m0, nblocks, first_block, s); if (rcc != FDC_OK) return rcc; }
+        RCCHK(run_channel_groups(p, false, spec, o, grp, s));
         if (tg) {
             HIPCHK(hipEventRecord(p->events[span[3]], s));
             span[4] = p->N <= fdc::kMaxLdsFft ? kSpanSpectrumLds : kSpanSpectrum;
             p->ev_spans.push_back(span);
         }
     }
-    if (ofmt && !ofused && narrow && p->C > 0) HIPCHK(fdc::launch_complex_to_iq(ofmt, oscale, fout, d_out, (size_t)nblocks * p->sum_lout, s));
+    if (ofmt && !ofused && call.narrow && p->C > 0) HIPCHK(fdc::launch_complex_to_iq(ofmt, call.oscale, call.fout, d_out, (size_t)nblocks * p->sum_lout, s));
     return FDC_OK;
 }
 
-static const char *iq_name(int fmt) { return fmt == FDC_IQ_SC16 ? "sc16" : "sc8"; }
+// how the last integer-input / integer-output call was served (fdc_pipeline_describe): "<sc16|sc8>: fused", or what it was instead
+static std::string route(int fmt, bool fused, const char *otherwise)
+{
+    return std::string(fmt == FDC_IQ_SC16 ? "sc16" : "sc8") + ": " + (fused ? "fused" : otherwise);
+}
 
 // The device entries with the handle's output format: integer output needs the float staging (p->d_out, max_blocks*sum_lout samples, allocated by
 // fdc_pipeline_set_output_format, never on this enqueue path) where the call's kernels do not narrow themselves
-static int process_device_oq(fdc_pipeline *p, int fmt, float scale, const void *d_ring, int64_t first_block, int nblocks, void *d_out, void *d_spectrum,
-                             void *stream, float2 *wide, bool *all_fused)
+static int process_device_oq(fdc_pipeline *p, DeviceCall &call, const void *d_ring, int64_t first_block, int nblocks, void *d_out)
 {
     const int ofmt = p->out_form;
-    if (!ofmt || nblocks <= 0) return process_device_impl(p, fmt, scale, d_ring, first_block, nblocks, d_out, d_spectrum, stream, wide, all_fused);
-    if (!oq_fused(p, fmt, d_spectrum != nullptr, nblocks)) {
+    if (!ofmt || nblocks <= 0) return process_device_impl(p, call, d_ring, first_block, nblocks, d_out);
+    call.ofmt = ofmt; call.oscale = p->out_scale; call.fout = p->d_out;
+    if (!oq_fused(p, call, nblocks)) {
         if (nblocks > p->cfg.max_blocks)
             return fail(FDC_ERR_INVALID_ARGUMENT, "integer output on this plan: nblocks %d above max_blocks %d", nblocks, p->cfg.max_blocks);
         if (!p->d_out && p->sum_lout > 0) return fail(FDC_ERR_HIP, "integer output: no float staging");
     }
-    bool of = false;
-    const int rc = process_device_impl(p, fmt, scale, d_ring, first_block, nblocks, d_out, d_spectrum, stream, wide, all_fused, ofmt, p->out_scale, p->d_out,
-                                       true, &of);
-    if (rc == FDC_OK) p->oq_route = std::string(iq_name(ofmt)) + (of ? ": fused" : ": narrowed");
+    const int rc = process_device_impl(p, call, d_ring, first_block, nblocks, d_out);
+    if (rc == FDC_OK) p->oq_route = route(ofmt, call.ofused, "narrowed");
     return rc;
 }
 
@@ -1490,7 +1514,8 @@ int fdc_pipeline_process_device(fdc_pipeline *p, const void *d_ring, int64_t fir
 {
     FDC_ENTRY("fdc_pipeline_process_device")
     if (!p) return fail(FDC_ERR_INVALID_ARGUMENT, "null handle");
-    return process_device_oq(p, 0, 1.0f, d_ring, first_block, nblocks, d_out, d_spectrum, stream, nullptr, nullptr);
+    DeviceCall call = device_call(p, stream, d_spectrum);
+    return process_device_oq(p, call, d_ring, first_block, nblocks, d_out);
     FDC_ENTRY_END
 }
 
@@ -1506,20 +1531,20 @@ int fdc_pipeline_process_device_iq(fdc_pipeline *p, int32_t format, float scale,
 {
     FDC_ENTRY("fdc_pipeline_process_device_iq")
     if (!p) return fail(FDC_ERR_INVALID_ARGUMENT, "null handle");
-    int rc = check_iq_form(format, scale);
-    if (rc != FDC_OK) return rc;
+    RCCHK(check_iq_form(format, scale));
     if (reinterpret_cast<uintptr_t>(d_ring) & 3) return fail(FDC_ERR_INVALID_ARGUMENT, "the integer ring must be 4-byte aligned");
+    DeviceCall call = device_call(p, stream, d_spectrum, format, scale);
     if (nblocks > 0 && !p->d_iqw) {
         bool need = false;      // the widened launch group: allocated at the first call that has a form without integer loads
-        for (int m0 = 0; m0 < nblocks && !need; m0 += p->chunk) need = !iq_fused(p, d_spectrum != nullptr, std::min(p->chunk, nblocks - m0) < p->block_min);
+        for (int m0 = 0; m0 < nblocks && !need; m0 += p->chunk) need = !iq_fused(p, call, std::min(p->chunk, nblocks - m0) < p->block_min);
         if (need) {
             HIPCHK(hipSetDevice(p->cfg.device_id));
             HIPCHK(hipMalloc(&p->d_iqw, sizeof(float2) * ((size_t)p->chunk * p->H + (size_t)p->ovl)));
         }
     }
-    bool all = true;
-    rc = process_device_oq(p, format, scale, d_ring, first_block, nblocks, d_out, d_spectrum, stream, p->d_iqw, &all);
-    if (rc == FDC_OK && nblocks > 0) p->iq_route = std::string(iq_name(format)) + (all ? ": fused" : ": widened");
+    call.wide = p->d_iqw;
+    const int rc = process_device_oq(p, call, d_ring, first_block, nblocks, d_out);
+    if (rc == FDC_OK && nblocks > 0) p->iq_route = route(format, call.all_fused, "widened");
     return rc;
     FDC_ENTRY_END
 }
@@ -1531,11 +1556,10 @@ int fdc_pipeline_process_device_power(fdc_pipeline *p, const void *d_ring, int64
     if (!p) return fail(FDC_ERR_INVALID_ARGUMENT, "null handle");
     if (p->out_form) return fail(FDC_ERR_INVALID_ARGUMENT, "fdc_pipeline_process_device_power writes complex float outputs only (the handle's output format is not FC32)");
     if (d_group_power && (!d_spectrum || (p->N & 15))) return fail(FDC_ERR_INVALID_ARGUMENT, "group powers go with a spectrum output of a block length that is a multiple of 16");
-    p->gpow_base = static_cast<float *>(d_group_power);
-    p->gpow_spec = static_cast<const float2 *>(d_spectrum);
-    const int rc = fdc_pipeline_process_device(p, d_ring, first_block, nblocks, d_out, d_spectrum, stream);
-    p->gpow_base = nullptr; p->gpow_spec = nullptr;
-    return rc;
+    DeviceCall call = device_call(p, stream, d_spectrum);
+    call.gpow = static_cast<float *>(d_group_power);
+    call.gpow_origin = static_cast<const float2 *>(d_spectrum);
+    return process_device_impl(p, call, d_ring, first_block, nblocks, d_out);
     FDC_ENTRY_END
 }
 
@@ -1647,7 +1671,7 @@ static int work_io_setup(fdc_pipeline *p)
 }
 
 // The input form of a work call against the form the handle is latched to (the first work call after create / reset latches it): a call in another
-// form is refused before it touches anything.  fmt 0 = float input (scale unused).  check_form only compares; latch_form records the form of a
+// form is refused before it touches anything.  fmt 0 = float input (scale unused).  check_form only compares; begin_work records the form of a
 // call that got past its set-up (a first call that fails there leaves the handle unlatched).
 static int check_form(const fdc_pipeline *p, int fmt, float scale)
 {
@@ -1662,64 +1686,36 @@ static int check_form(const fdc_pipeline *p, int fmt, float scale)
     return fail(FDC_ERR_INVALID_ARGUMENT, "the handle takes %s input since its first work call (reset it to change the input form), not %s",
                 name(p->in_form, p->in_scale).c_str(), name(fmt, scale).c_str());
 }
-static void latch_form(fdc_pipeline *p, int fmt, float scale)
-{
-    if (p->in_form < 0) { p->in_form = fmt; p->in_scale = fmt ? scale : 0.f; }
-}
 
-// Host entry.  The call is cut into sub-batches; sub-batch k's H2D copy (stream s_in), its kernels (p->stream) and
-// its D2H leg (s_out) run beside the neighbouring sub-batches' other legs, so a long call moves at the rate of the
-// slower PCIe direction instead of the sum of all legs.  Caller buffers pinned with fdc_host_register() are DMA'd in
-// place (input: one async copy; outputs: one scatter kernel storing straight into the caller's per-channel buffers).
-// Pageable input is copied by the runtime's pin-on-the-fly path from a feeder thread; pageable outputs come back
-// through two pinned staging slots and a CPU copy on this thread.
-// span: the call is one contiguous span of a longer stream handed over by a dispatcher (fdc_pipeline_work_span): the history comes
-// from `halo` (N/R samples, NULL = zeros) and the block counter from `first_block` instead of from the handle.
-// fmt != 0: `in` and `halo` hold complex integers (FDC_IQ_SC16 / FDC_IQ_SC8, times scale): the ring and its history are kept in that format
-// (d_iq), the integer kernels read it where the plan has them, the handle's float ring takes the widened launch groups otherwise.
-// Integer output (p->out_form): the kernels narrow into d_oq where the plan lets them (oq_fused), else they write d_out and k_complex_to_iq narrows it
-// into d_oq; registered outputs are scattered from either (k_scatter_oq: narrowing from d_out, copying from d_oq), staged ones copied from d_oq.
-static int pipeline_work_impl(fdc_pipeline *p, const void *in, int nblocks, void *const *outs, void *spectrum,
-                              float2 *d_spec_dst, bool span = false, const void *halo = nullptr, int64_t first_block = 0, int fmt = 0, float scale = 1.0f)
+// The host entries' argument checks.  A call of no blocks passes whatever its buffers are: the entry returns 0 before it looks at them.
+static int check_work_args(const fdc_pipeline *p, const void *in, int nblocks, void *const *outs)
 {
-    if (!p) return fail(FDC_ERR_INVALID_ARGUMENT, "null handle");
     if (nblocks < 0) return fail(FDC_ERR_INVALID_ARGUMENT, "negative item count");
-    if (nblocks == 0) return 0;
+    if (nblocks == 0) return FDC_OK;
     if (nblocks > p->cfg.max_blocks) return fail(FDC_ERR_INVALID_ARGUMENT, "nblocks %d above max_blocks %d", nblocks, p->cfg.max_blocks);
     if (!in || (p->C > 0 && !outs)) return fail(FDC_ERR_INVALID_ARGUMENT, "null host buffer");
-    if ((spectrum || (d_spec_dst && !p->wf_spec)) && !p->cfg.keep_spectrum) return fail(FDC_ERR_INVALID_ARGUMENT, "spectrum output needs keep_spectrum");
-    int rc = check_form(p, fmt, scale);
-    if (rc != FDC_OK) return rc;
+    return FDC_OK;
+}
+
+// What a stream entry does first: the input form against the latch, the device, the buffers of the first call (that needs them); then the form is latched
+static int begin_work(fdc_pipeline *p, int fmt, float scale)
+{
+    RCCHK(check_form(p, fmt, scale));
     HIPCHK(hipSetDevice(p->cfg.device_id));
-    if ((rc = work_io_setup(p)) != FDC_OK) return rc;
-    hipStream_t s = p->stream;
-    const size_t nin = (size_t)nblocks * p->H, esz = fdc::iq_bytes(fmt);
-    const int ofmt = p->out_form;
-    const float oscale = p->out_scale;
-    const size_t osz = ofmt ? fdc::iq_bytes(ofmt) : sizeof(float2);       // bytes per output sample the caller receives
-    if (ofmt && !p->d_oq && p->sum_lout > 0) HIPCHK(hipMalloc(&p->d_oq, fdc::kIqRingBytes * (size_t)p->cfg.max_blocks * p->sum_lout));
+    RCCHK(work_io_setup(p));
+    if (p->out_form && !p->d_oq && p->sum_lout > 0) HIPCHK(hipMalloc(&p->d_oq, fdc::kIqRingBytes * (size_t)p->cfg.max_blocks * p->sum_lout));
     if (fmt && !p->d_iq) {
-        // the integer ring: allocated at the first integer call, for the WIDEST format (a reset may latch the handle to another one); its
-        // history starts at zero, as the float ring's
+        // the integer ring, for the WIDEST format (a reset may latch the handle to another one); its history starts at zero, as the float ring's
         HIPCHK(hipMalloc(&p->d_iq, fdc::kIqRingBytes * ((size_t)p->ovl + (size_t)p->cfg.max_blocks * p->H)));
-        HIPCHK(hipMemsetAsync(p->d_iq, 0, fdc::kIqRingBytes * (size_t)p->ovl, s));
+        HIPCHK(hipMemsetAsync(p->d_iq, 0, fdc::kIqRingBytes * (size_t)p->ovl, p->stream));
     }
-    latch_form(p, fmt, scale);
-    // the ring the call's samples go to, as bytes: float2 (d_ring) or the integer format (d_iq)
-    unsigned char *const ringb = fmt ? static_cast<unsigned char *>(p->d_iq) : reinterpret_cast<unsigned char *>(p->d_ring);
-    const unsigned char *hin = static_cast<const unsigned char *>(in);
-    if (span) {
-        // every kernel of the call is enqueued on s behind this copy; the previous call ended with s drained
-        if (halo) HIPCHK(hipMemcpyAsync(ringb, halo, esz * (size_t)p->ovl, hipMemcpyHostToDevice, s));
-        else HIPCHK(hipMemsetAsync(ringb, 0, esz * (size_t)p->ovl, s));
-        p->blockcount = first_block;
-    }
+    if (p->in_form < 0) { p->in_form = fmt; p->in_scale = fmt ? scale : 0.f; }
+    return FDC_OK;
+}
 
-    // spectrum wanted (debug port / sinks): every sub-batch writes its part of one whole-call buffer
-    float2 *d_specfull = d_spec_dst;
-    if (spectrum && !d_specfull && (rc = spec_staging(p, &d_specfull)) != FDC_OK) return rc;
-
-    const bool in_reg = host_registered(in, esz * nin);
+// The scatter table of a call whose outputs (osz bytes per sample) are ALL registered host buffers (else false): the scatter kernels store in place
+static bool fill_scatter_table(fdc_pipeline *p, void *const *outs, int nblocks, size_t osz)
+{
     bool out_reg = p->C > 0;
     for (int c = 0; c < p->C && out_reg; c++) {
         fdc::ScatterEnt &e = p->pin_tab[c];
@@ -1727,18 +1723,73 @@ static int pipeline_work_impl(fdc_pipeline *p, const void *in, int nblocks, void
         if (outs[c] && !host_registered(outs[c], osz * (size_t)nblocks * p->chans[c].lout, reinterpret_cast<void **>(&e.dst)))
             out_reg = false;
     }
-    bool all_fused = true, oq_all = true, oq_sub = false;
-    // dok: the float results of the sub-batch starting at block b0.  Integer output: its narrow results go to the same sample offset of d_oq (oq_sub: the
+    return out_reg;
+}
+
+// The results of a whole call (src: on the device, [channel][nblocks*lout] samples of osz bytes) to the buffers the caller gave, one copy per channel
+static int copy_outputs(const fdc_pipeline *p, void *const *outs, int nblocks, size_t osz, const void *src, hipStream_t s)
+{
+    for (int c = 0; c < p->C; c++)
+        if (outs[c])
+            HIPCHK(hipMemcpyAsync(outs[c], static_cast<const unsigned char *>(src) + osz * (size_t)nblocks * p->chans[c].out_off,
+                                  osz * (size_t)nblocks * p->chans[c].lout, hipMemcpyDeviceToHost, s));
+    return FDC_OK;
+}
+
+// span: the call is one contiguous span of a longer stream handed over by a dispatcher (fdc_pipeline_work_span and friends): the history comes from
+// `halo` (N/R samples, NULL = zeros) and the block counter from `first_block` instead of from the handle
+struct SpanStart { bool span; const void *halo; int64_t first_block; };
+
+// Host entry.  The call is cut into sub-batches; sub-batch k's H2D copy (stream s_in), its kernels (p->stream) and
+// its D2H leg (s_out) run beside the neighbouring sub-batches' other legs, so a long call moves at the rate of the
+// slower PCIe direction instead of the sum of all legs.  Caller buffers pinned with fdc_host_register() are DMA'd in
+// place (input: one async copy; outputs: one scatter kernel storing straight into the caller's per-channel buffers).
+// Pageable input is copied by the runtime's pin-on-the-fly path from a feeder thread; pageable outputs come back
+// through two pinned staging slots and a CPU copy on this thread.
+// call: the entry's (device_call; its spectrum: a device destination of the entry's own, the sinks' buffer or the waterfall's staging).
+// call.fmt != 0: `in` and the halo hold complex integers (FDC_IQ_SC16 / FDC_IQ_SC8, times scale): the ring and its history are kept in that format
+// (d_iq), the integer kernels read it where the plan has them, the handle's float ring takes the widened launch groups otherwise.
+// Integer output (p->out_form): the kernels narrow into d_oq where the plan lets them (oq_fused), else they write d_out and k_complex_to_iq narrows it
+// into d_oq; registered outputs are scattered from either (k_scatter_oq: narrowing from d_out, copying from d_oq), staged ones copied from d_oq.
+static int pipeline_work_impl(fdc_pipeline *p, DeviceCall call, const void *in, int nblocks, void *const *outs, void *spectrum, SpanStart from = {})
+{
+    int rc = check_work_args(p, in, nblocks, outs);
+    if (rc != FDC_OK || nblocks == 0) return rc;
+    if ((spectrum || (call.spectrum && !call.own_spectrum)) && !p->cfg.keep_spectrum) return fail(FDC_ERR_INVALID_ARGUMENT, "spectrum output needs keep_spectrum");
+    const int fmt = call.fmt;
+    RCCHK(begin_work(p, fmt, call.scale));
+    hipStream_t s = p->stream;
+    const size_t nin = (size_t)nblocks * p->H, esz = fdc::iq_bytes(fmt);
+    const int ofmt = p->out_form;
+    const float oscale = p->out_scale;
+    const size_t osz = ofmt ? fdc::iq_bytes(ofmt) : sizeof(float2);       // bytes per output sample the caller receives
+    // the ring the call's samples go to, as bytes: float2 (d_ring) or the integer format (d_iq)
+    unsigned char *const ringb = fmt ? static_cast<unsigned char *>(p->d_iq) : reinterpret_cast<unsigned char *>(p->d_ring);
+    const unsigned char *hin = static_cast<const unsigned char *>(in);
+    if (from.span) {
+        // every kernel of the call is enqueued on s behind this copy; the previous call ended with s drained
+        if (from.halo) HIPCHK(hipMemcpyAsync(ringb, from.halo, esz * (size_t)p->ovl, hipMemcpyHostToDevice, s));
+        else HIPCHK(hipMemsetAsync(ringb, 0, esz * (size_t)p->ovl, s));
+        p->blockcount = from.first_block;
+    }
+
+    // spectrum wanted (debug port / sinks): every sub-batch writes its part of one whole-call buffer
+    float2 *d_specfull = static_cast<float2 *>(call.spectrum);
+    if (spectrum && !d_specfull && (rc = spec_staging(p, &d_specfull)) != FDC_OK) return rc;
+
+    const bool in_reg = host_registered(in, esz * nin);
+    const bool out_reg = fill_scatter_table(p, outs, nblocks, osz);
+    call.wide = fmt ? p->d_ring : nullptr;
+    call.ofmt = ofmt; call.oscale = oscale; call.narrow = !out_reg;
+    bool oq_all = true;
+    // dok: the float results of the sub-batch starting at block b0.  Integer output: its narrow results go to the same sample offset of d_oq (call.ofused: the
     // kernels wrote them there themselves; otherwise dok holds float and is narrowed into d_oq, unless the outputs are registered: k_scatter_oq narrows)
     auto process = [&](size_t b0, int nb, int64_t first, float2 *dok, float2 *dspec) {
-        if (ofmt) {
-            const int rc2 = process_device_impl(p, fmt, scale, ringb + b0 * p->H * esz, first, nb, p->d_oq + osz * b0 * (size_t)p->sum_lout, dspec, s,
-                                                fmt ? p->d_ring : nullptr, &all_fused, ofmt, oscale, dok, !out_reg, &oq_sub);
-            oq_all = oq_all && oq_sub;
-            return rc2;
-        }
-        return fmt ? process_device_impl(p, fmt, scale, ringb + b0 * p->H * esz, first, nb, dok, dspec, s, p->d_ring, &all_fused)
-                   : fdc_pipeline_process_device(p, ringb + b0 * p->H * esz, first, nb, dok, dspec, s);
+        call.spectrum = dspec; call.fout = dok;
+        const int rc2 = process_device_impl(p, call, ringb + b0 * p->H * esz, first, nb,
+                                            ofmt ? static_cast<void *>(p->d_oq + osz * b0 * (size_t)p->sum_lout) : static_cast<void *>(dok));
+        oq_all = oq_all && call.ofused;
+        return rc2;
     };
     // what the caller's buffers receive for the sub-batch at b0: float from d_out, or narrow from d_oq
     auto res = [&](size_t b0) -> const void * {
@@ -1746,23 +1797,25 @@ static int pipeline_work_impl(fdc_pipeline *p, const void *in, int nblocks, void
     };
     auto scatter = [&](size_t b0, int nb, hipStream_t st) -> hipError_t {
         if (!ofmt) return fdc::launch_scatter_out(p->d_out + b0 * (size_t)p->sum_lout, p->d_tab, p->C, nb, (long long)b0, st);
-        return oq_sub ? fdc::launch_scatter_oq(ofmt, res(b0), ofmt, oscale, p->d_tab, p->C, nb, (long long)b0, st)
+        return call.ofused ? fdc::launch_scatter_oq(ofmt, res(b0), ofmt, oscale, p->d_tab, p->C, nb, (long long)b0, st)
                       : fdc::launch_scatter_oq(fdc::kIqFloat, p->d_out + b0 * (size_t)p->sum_lout, ofmt, oscale, p->d_tab, p->C, nb, (long long)b0, st);
     };
     const int sub = p->sub;
     if (!out_reg && p->C > 0 && !p->pin_out[0])
         for (int i = 0; i < 2; i++)
             HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&p->pin_out[i]), sizeof(float2) * (size_t)sub * p->sum_lout, hipHostMallocDefault));
-    // staged outputs: wait for sub-batch j's D2H, then hand its pieces to the caller's per-channel buffers
-    auto drain = [&](int j) -> int {
-        const int b0 = j * sub, nb = std::min(sub, nblocks - b0);
-        HIPCHK(hipEventSynchronize(p->ev_out[j & 1]));
-        const unsigned char *src = reinterpret_cast<const unsigned char *>(p->pin_out[j & 1]);
+    // staged outputs: the pieces of the sub-batch (b0, nb) that has arrived in pin_out[slot] go to the caller's per-channel buffers
+    auto deliver = [&](int slot, int b0, int nb) {
+        const unsigned char *src = reinterpret_cast<const unsigned char *>(p->pin_out[slot]);
         for (int c = 0; c < p->C; c++) {
             if (!outs[c]) continue;
             const size_t lo = (size_t)p->chans[c].lout;
             std::memcpy(static_cast<unsigned char *>(outs[c]) + osz * (size_t)b0 * lo, src + osz * (size_t)nb * p->chans[c].out_off, osz * nb * lo);
         }
+    };
+    auto drain = [&](int j) -> int {                                      // ... behind sub-batch j's D2H
+        HIPCHK(hipEventSynchronize(p->ev_out[j & 1]));
+        deliver(j & 1, j * sub, std::min(sub, nblocks - j * sub));
         return FDC_OK;
     };
     const int K = (nblocks + sub - 1) / sub;
@@ -1778,13 +1831,9 @@ static int pipeline_work_impl(fdc_pipeline *p, const void *in, int nblocks, void
         if (spectrum) HIPCHK(hipMemcpyAsync(spectrum, d_specfull, sizeof(float2) * (size_t)nblocks * p->N, hipMemcpyDeviceToHost, s));
         HIPCHK(hipMemcpyAsync(ringb, ringb + esz * nin, esz * (size_t)p->ovl, hipMemcpyDeviceToDevice, s));
         HIPCHK(hipStreamSynchronize(s));
-        if (fmt) p->iq_route = std::string(iq_name(fmt)) + (all_fused ? ": fused" : ": widened");
-        if (ofmt) p->oq_route = std::string(iq_name(ofmt)) + (oq_all ? ": fused" : ": narrowed");
-        if (p->C > 0 && !out_reg)
-            for (int c = 0; c < p->C; c++)
-                if (outs[c])
-                    std::memcpy(outs[c], reinterpret_cast<const unsigned char *>(p->pin_out[0]) + osz * (size_t)nblocks * p->chans[c].out_off,
-                                osz * (size_t)nblocks * p->chans[c].lout);
+        if (fmt) p->iq_route = route(fmt, call.all_fused, "widened");
+        if (ofmt) p->oq_route = route(ofmt, oq_all, "narrowed");
+        if (p->C > 0 && !out_reg) deliver(0, 0, nblocks);
         p->blockcount += nblocks;
         return nblocks;
     }
@@ -1845,8 +1894,8 @@ static int pipeline_work_impl(fdc_pipeline *p, const void *in, int nblocks, void
     HIPCHK(hipMemcpyAsync(ringb, ringb + esz * nin, esz * (size_t)p->ovl, hipMemcpyDeviceToDevice, s));
     HIPCHK(hipStreamSynchronize(s));
     HIPCHK(hipStreamSynchronize(p->s_out));
-    if (fmt) p->iq_route = std::string(iq_name(fmt)) + (all_fused ? ": fused" : ": widened");
-    if (ofmt) p->oq_route = std::string(iq_name(ofmt)) + (oq_all ? ": fused" : ": narrowed");
+    if (fmt) p->iq_route = route(fmt, call.all_fused, "widened");
+    if (ofmt) p->oq_route = route(ofmt, oq_all, "narrowed");
     p->blockcount += nblocks;
     return nblocks;
 }
@@ -1854,7 +1903,8 @@ static int pipeline_work_impl(fdc_pipeline *p, const void *in, int nblocks, void
 int fdc_pipeline_work(fdc_pipeline *p, const void *in, int nblocks, void *const *outs, void *spectrum)
 {
     FDC_ENTRY("fdc_pipeline_work")
-    return pipeline_work_impl(p, in, nblocks, outs, spectrum, nullptr);
+    if (!p) return fail(FDC_ERR_INVALID_ARGUMENT, "null handle");
+    return pipeline_work_impl(p, device_call(p, nullptr, nullptr), in, nblocks, outs, spectrum);
     FDC_ENTRY_END
 }
 
@@ -1878,18 +1928,12 @@ int fdc_pipeline_work_waterfall(fdc_pipeline *p, fdc_waterfall *w, const void *i
     float *gpow = nullptr;
     if (!fused && (rc = spec_staging(p, &spec)) != FDC_OK) return rc;
     if (groups && (rc = fdc::wf_group_buffer(w, nblocks, &gpow)) != FDC_OK) return rc;
-    {
-        // the per-call fields are cleared however the call leaves (an exception included): a later fdc_pipeline_work must not see them
-        struct Clear {
-            fdc_pipeline *p;
-            ~Clear() { p->wf_rows = nullptr; p->wf_spec = false; p->gpow_base = nullptr; p->gpow_spec = nullptr; }
-        } clear{p};
-        p->wf_rows = fused ? fdc::wf_block_rows(w) : nullptr;
-        p->wf_first = p->blockcount;
-        p->wf_spec = !fused;
-        p->gpow_base = gpow; p->gpow_spec = gpow ? spec : nullptr;
-        rc = pipeline_work_impl(p, in, nblocks, outs, nullptr, spec);
-    }
+    DeviceCall call = device_call(p, nullptr, spec);
+    call.own_spectrum = true;                                   // the staging the rows are summed from: no keep_spectrum needed
+    call.rows = fused ? fdc::wf_block_rows(w) : nullptr;
+    call.rows_first = p->blockcount;
+    call.gpow = gpow; call.gpow_origin = gpow ? spec : nullptr;
+    rc = pipeline_work_impl(p, call, in, nblocks, outs, nullptr);
     if (rc < 0) return rc;
     p->wf_route = fused ? "k_f4096 epilogue (pixels from the spectrum in LDS)"
                 : groups ? "k_wf_from_groups (pixels from the 16-bin group powers of the internal spectrum)"
@@ -1906,27 +1950,20 @@ int fdc_pipeline_work_span(fdc_pipeline *p, const void *halo, const void *in, in
 {
     FDC_ENTRY("fdc_pipeline_work_span")
     if (first_block < 0) return fail(FDC_ERR_INVALID_ARGUMENT, "negative block index");
-    return pipeline_work_impl(p, in, nblocks, outs, spectrum, nullptr, true, halo, first_block);
+    if (!p) return fail(FDC_ERR_INVALID_ARGUMENT, "null handle");
+    return pipeline_work_impl(p, device_call(p, nullptr, nullptr), in, nblocks, outs, spectrum, {true, halo, first_block});
     FDC_ENTRY_END
 }
 
 // Real input: the float items are copied to the device and widened there into the complex ring (imaginary part 0); the
 // rest of the call is the one-stream form of the complex entry.
-static int pipeline_work_real_impl(fdc_pipeline *p, const void *in, int nblocks, void *const *outs, void *spectrum, bool span,
-                                   const void *halo, int64_t first_block)
+static int pipeline_work_real_impl(fdc_pipeline *p, const void *in, int nblocks, void *const *outs, void *spectrum, SpanStart from = {})
 {
     if (!p) return fail(FDC_ERR_INVALID_ARGUMENT, "null handle");
-    if (nblocks < 0) return fail(FDC_ERR_INVALID_ARGUMENT, "negative item count");
-    if (nblocks == 0) return 0;
-    if (nblocks > p->cfg.max_blocks) return fail(FDC_ERR_INVALID_ARGUMENT, "nblocks %d above max_blocks %d", nblocks, p->cfg.max_blocks);
-    if (!in || (p->C > 0 && !outs)) return fail(FDC_ERR_INVALID_ARGUMENT, "null host buffer");
+    int rc = check_work_args(p, in, nblocks, outs);
+    if (rc != FDC_OK || nblocks == 0) return rc;
     if (spectrum && !p->cfg.keep_spectrum) return fail(FDC_ERR_INVALID_ARGUMENT, "spectrum output needs keep_spectrum");
-    int rc = check_form(p, 0, 0.f);
-    if (rc != FDC_OK) return rc;
-    HIPCHK(hipSetDevice(p->cfg.device_id));
-    rc = work_io_setup(p);
-    if (rc != FDC_OK) return rc;
-    latch_form(p, 0, 0.f);
+    RCCHK(begin_work(p, 0, 0.f));
     hipStream_t s = p->stream;
     const size_t nin = (size_t)nblocks * p->H;
     // d_real: [N/R history samples of a span call][max_blocks*H new samples]
@@ -1934,32 +1971,26 @@ static int pipeline_work_real_impl(fdc_pipeline *p, const void *in, int nblocks,
     float2 *d_specfull = nullptr;
     if (spectrum && (rc = spec_staging(p, &d_specfull)) != FDC_OK) return rc;
     HIPCHK(hipMemcpyAsync(p->d_real + p->ovl, in, sizeof(float) * nin, hipMemcpyHostToDevice, s));
-    if (span) {
-        if (halo) HIPCHK(hipMemcpyAsync(p->d_real, halo, sizeof(float) * (size_t)p->ovl, hipMemcpyHostToDevice, s));
+    if (from.span) {
+        if (from.halo) HIPCHK(hipMemcpyAsync(p->d_real, from.halo, sizeof(float) * (size_t)p->ovl, hipMemcpyHostToDevice, s));
         else HIPCHK(hipMemsetAsync(p->d_real, 0, sizeof(float) * (size_t)p->ovl, s));
         HIPCHK(fdc::launch_real_to_complex(p->d_real, p->d_ring, (size_t)p->ovl + nin, s));
-        p->blockcount = first_block;
+        p->blockcount = from.first_block;
     } else {
         HIPCHK(fdc::launch_real_to_complex(p->d_real + p->ovl, p->d_ring + p->ovl, nin, s));
     }
     // integer output (p->out_form): the narrow results in d_oq (the kernels' own stores, or k_complex_to_iq behind them), copied as they are
     const int ofmt = p->out_form;
     const size_t osz = ofmt ? fdc::iq_bytes(ofmt) : sizeof(float2);
-    if (ofmt && !p->d_oq && p->sum_lout > 0) HIPCHK(hipMalloc(&p->d_oq, fdc::kIqRingBytes * (size_t)p->cfg.max_blocks * p->sum_lout));
-    bool of = false;
-    if (ofmt) rc = process_device_impl(p, 0, 1.0f, p->d_ring, p->blockcount, nblocks, p->d_oq, d_specfull, s, nullptr, nullptr, ofmt, p->out_scale, p->d_out,
-                                       true, &of);
-    else rc = fdc_pipeline_process_device(p, p->d_ring, p->blockcount, nblocks, p->d_out, d_specfull, s);
-    if (rc != FDC_OK) return rc;
-    const unsigned char *res = ofmt ? p->d_oq : reinterpret_cast<const unsigned char *>(p->d_out);
-    for (int c = 0; c < p->C; c++)
-        if (outs[c])
-            HIPCHK(hipMemcpyAsync(outs[c], res + osz * (size_t)nblocks * p->chans[c].out_off,
-                                  osz * (size_t)nblocks * p->chans[c].lout, hipMemcpyDeviceToHost, s));
+    void *const res = ofmt ? static_cast<void *>(p->d_oq) : static_cast<void *>(p->d_out);
+    DeviceCall call = device_call(p, nullptr, d_specfull);
+    call.ofmt = ofmt; call.oscale = p->out_scale; call.fout = p->d_out;
+    RCCHK(process_device_impl(p, call, p->d_ring, p->blockcount, nblocks, res));
+    RCCHK(copy_outputs(p, outs, nblocks, osz, res, s));
     if (spectrum) HIPCHK(hipMemcpyAsync(spectrum, d_specfull, sizeof(float2) * (size_t)nblocks * p->N, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(p->d_ring, p->d_ring + nin, sizeof(float2) * (size_t)p->ovl, hipMemcpyDeviceToDevice, s));
     HIPCHK(hipStreamSynchronize(s));
-    if (ofmt) p->oq_route = std::string(iq_name(ofmt)) + (of ? ": fused" : ": narrowed");
+    if (ofmt) p->oq_route = route(ofmt, call.ofused, "narrowed");
     p->blockcount += nblocks;
     return nblocks;
 }
@@ -1967,7 +1998,7 @@ static int pipeline_work_real_impl(fdc_pipeline *p, const void *in, int nblocks,
 int fdc_pipeline_work_real(fdc_pipeline *p, const void *in, int nblocks, void *const *outs, void *spectrum)
 {
     FDC_ENTRY("fdc_pipeline_work_real")
-    return pipeline_work_real_impl(p, in, nblocks, outs, spectrum, false, nullptr, 0);
+    return pipeline_work_real_impl(p, in, nblocks, outs, spectrum);
     FDC_ENTRY_END
 }
 
@@ -1976,7 +2007,7 @@ int fdc_pipeline_work_span_real(fdc_pipeline *p, const void *halo, const void *i
 {
     FDC_ENTRY("fdc_pipeline_work_span_real")
     if (first_block < 0) return fail(FDC_ERR_INVALID_ARGUMENT, "negative block index");
-    return pipeline_work_real_impl(p, in, nblocks, outs, spectrum, true, halo, first_block);
+    return pipeline_work_real_impl(p, in, nblocks, outs, spectrum, {true, halo, first_block});
     FDC_ENTRY_END
 }
 
@@ -1984,9 +2015,8 @@ int fdc_pipeline_work_iq(fdc_pipeline *p, int32_t format, float scale, const voi
 {
     FDC_ENTRY("fdc_pipeline_work_iq")
     if (!p) return fail(FDC_ERR_INVALID_ARGUMENT, "null handle");
-    const int rc = check_iq_form(format, scale);
-    if (rc != FDC_OK) return rc;
-    return pipeline_work_impl(p, in, nblocks, outs, spectrum, nullptr, false, nullptr, 0, format, scale);
+    RCCHK(check_iq_form(format, scale));
+    return pipeline_work_impl(p, device_call(p, nullptr, nullptr, format, scale), in, nblocks, outs, spectrum);
     FDC_ENTRY_END
 }
 
@@ -1995,10 +2025,9 @@ int fdc_pipeline_work_span_iq(fdc_pipeline *p, int32_t format, float scale, cons
 {
     FDC_ENTRY("fdc_pipeline_work_span_iq")
     if (!p) return fail(FDC_ERR_INVALID_ARGUMENT, "null handle");
-    const int rc = check_iq_form(format, scale);
-    if (rc != FDC_OK) return rc;
+    RCCHK(check_iq_form(format, scale));
     if (first_block < 0) return fail(FDC_ERR_INVALID_ARGUMENT, "negative block index");
-    return pipeline_work_impl(p, in, nblocks, outs, spectrum, nullptr, true, halo, first_block, format, scale);
+    return pipeline_work_impl(p, device_call(p, nullptr, nullptr, format, scale), in, nblocks, outs, spectrum, {true, halo, first_block});
     FDC_ENTRY_END
 }
 
@@ -2013,19 +2042,13 @@ int fdc_pipeline_work_span_iq(fdc_pipeline *p, int32_t format, float scale, cons
 // the call has stream outputs: with pinned input the call costs what its input copy costs.
 static int work_sinks_pipelined(fdc_pipeline *p, const void *in, int nblocks, void *const *outs, void *spectrum, fdc_sinks *sinks)
 {
-    if (nblocks < 0) return fail(FDC_ERR_INVALID_ARGUMENT, "negative item count");
-    if (nblocks == 0) return 0;
-    if (nblocks > p->cfg.max_blocks) return fail(FDC_ERR_INVALID_ARGUMENT, "nblocks %d above max_blocks %d", nblocks, p->cfg.max_blocks);
-    if (!in || (p->C > 0 && !outs)) return fail(FDC_ERR_INVALID_ARGUMENT, "null host buffer");
+    int rc = check_work_args(p, in, nblocks, outs);
+    if (rc != FDC_OK || nblocks == 0) return rc;
     if (!p->cfg.keep_spectrum) return fail(FDC_ERR_INVALID_ARGUMENT, "spectrum output needs keep_spectrum");
     if (p->hier_bank && p->hier_bank != sinks && p->hier_filled > 0)
         return fail(FDC_ERR_INVALID_ARGUMENT, "a batch of another bank is still inside this pipeline: fdc_pipeline_flush_sinks() with that bank first");
     if (p->hier_broken) return fail(FDC_ERR_HIP, "an earlier pipelined call failed after it had advanced the stream state: destroy the pipeline and the bank");
-    int rc = check_form(p, 0, 0.f);
-    if (rc != FDC_OK) return rc;
-    HIPCHK(hipSetDevice(p->cfg.device_id));
-    if ((rc = work_io_setup(p)) != FDC_OK) return rc;
-    latch_form(p, 0, 0.f);
+    RCCHK(begin_work(p, 0, 0.f));
     if (!p->ev_hier) {
         HIPCHK(hipEventCreateWithFlags(&p->ev_hier, hipEventDisableTiming));
         HIPCHK(hipStreamSynchronize(p->stream));                  // work_io_setup zeroes the history on the handle's own stream; this entry runs on others
@@ -2034,9 +2057,13 @@ static int work_sinks_pipelined(fdc_pipeline *p, const void *in, int nblocks, vo
     hipStream_t fs = static_cast<hipStream_t>(fdc_sinks_fill_stream(sinks));
     const bool first = p->hier_filled == 0;                       // stream start, or everything was flushed: the bank's current buffer is free
     float2 *dst = static_cast<float2 *>(first ? fdc_sinks_spectrum(sinks) : fdc_sinks_spectrum_ahead(sinks));
+    // the power of the spectrum's 16-bin groups comes out of the forward kernel's epilogue: the bank's cells are summed from it (no pass over the spectrum)
+    float *const gpw = static_cast<float *>(first ? fdc_sinks_group_power(sinks) : fdc_sinks_group_power_ahead(sinks));
+    DeviceCall call = device_call(p, fs, dst);
+    call.gpow = gpw; call.gpow_origin = dst;
     // the persistent block kernels take every compute unit; the decision chains of the batch before run beside them on a few units left free
-    // (long launch groups only: a group of one round is over before a chain would notice)
-    if (!p->reserve_user) p->reserved_cu = std::min(nblocks, p->chunk) >= 2 * p->ncu ? p->ncu / 8 : 0;
+    // (long launch groups only: a group of one round is over before a chain would notice).  The user's own reservation goes first.
+    if (!p->reserve_user) call.ncu = p->ncu - (std::min(nblocks, p->chunk) >= 2 * p->ncu ? p->ncu / 8 : 0);
 
     const size_t nin = (size_t)nblocks * p->H;
     // input: one copy on s_in.  The ring is read by the transform of the call before (fill stream) until ev_hier.
@@ -2044,10 +2071,7 @@ static int work_sinks_pipelined(fdc_pipeline *p, const void *in, int nblocks, vo
     HIPCHK(hipMemcpyAsync(p->d_ring + p->ovl, in, sizeof(float2) * nin, hipMemcpyHostToDevice, p->s_in));
     HIPCHK(hipEventRecord(p->ev_in[0], p->s_in));
     HIPCHK(hipStreamWaitEvent(fs, p->ev_in[0], 0));
-    // the power of the spectrum's 16-bin groups comes out of the forward kernel's epilogue: the bank's cells are summed from it (no pass over the spectrum)
-    float *const gpw = static_cast<float *>(first ? fdc_sinks_group_power(sinks) : fdc_sinks_group_power_ahead(sinks));
-    rc = fdc_pipeline_process_device_power(p, p->d_ring, p->blockcount, nblocks, p->d_out, dst, gpw, fs);
-    if (rc != FDC_OK) return rc;
+    RCCHK(process_device_impl(p, call, p->d_ring, p->blockcount, nblocks, p->d_out));
     // history <- last ovl samples of this call (overlap_save_impl.cc:78)
     HIPCHK(hipMemcpyAsync(p->d_ring, p->d_ring + nin, sizeof(float2) * (size_t)p->ovl, hipMemcpyDeviceToDevice, fs));
     HIPCHK(hipEventRecord(p->ev_hier, fs));
@@ -2056,33 +2080,14 @@ static int work_sinks_pipelined(fdc_pipeline *p, const void *in, int nblocks, vo
     // from here on the call has happened as far as the stream state goes (history, block counter, the bank's buffer): a failure below cannot be
     // retried with the same items nor skipped — the pair is marked broken and every later call says so
     struct Broken { fdc_pipeline *p; bool ok = false; ~Broken() { if (!ok) p->hier_broken = true; } } guard{p};
-    rc = gpw ? fdc_sinks_prepare_from_groups(sinks, nblocks, first ? 0 : 1) : fdc_sinks_prepare(sinks, nblocks, first ? 0 : 1);
-    if (rc != FDC_OK) return rc;
-    bool out_reg = p->C > 0;
-    if (p->C > 0) {
-        for (int c = 0; c < p->C && out_reg; c++) {
-            fdc::ScatterEnt &e = p->pin_tab[c];
-            e.dst = nullptr; e.out_off = p->chans[c].out_off; e.lout = p->chans[c].lout; e.pad = 0;
-            if (outs[c] && !host_registered(outs[c], sizeof(float2) * (size_t)nblocks * p->chans[c].lout, reinterpret_cast<void **>(&e.dst)))
-                out_reg = false;
-        }
-        if (out_reg) HIPCHK(fdc::launch_scatter_out(p->d_out, p->d_tab, p->C, nblocks, 0, fs));
-        else
-            for (int c = 0; c < p->C; c++)
-                if (outs[c])
-                    HIPCHK(hipMemcpyAsync(outs[c], p->d_out + (size_t)nblocks * p->chans[c].out_off,
-                                          sizeof(float2) * (size_t)nblocks * p->chans[c].lout, hipMemcpyDeviceToHost, fs));
-    }
+    RCCHK(gpw ? fdc_sinks_prepare_from_groups(sinks, nblocks, first ? 0 : 1) : fdc_sinks_prepare(sinks, nblocks, first ? 0 : 1));
+    if (fill_scatter_table(p, outs, nblocks, sizeof(float2))) HIPCHK(fdc::launch_scatter_out(p->d_out, p->d_tab, p->C, nblocks, 0, fs));
+    else RCCHK(copy_outputs(p, outs, nblocks, sizeof(float2), p->d_out, fs));
     if (spectrum) HIPCHK(hipMemcpyAsync(spectrum, dst, sizeof(float2) * (size_t)nblocks * p->N, hipMemcpyDeviceToHost, fs));
     const int before = p->hier_filled;
     p->hier_filled = nblocks;
-    if (before > 0) {
-        const int rs = fdc_sinks_submit_device(sinks, before);
-        if (rs < 0) return rs;
-    } else {
-        const int rs = fdc_sinks_submit_device(sinks, 0);          // nothing to submit yet: hands out a batch still in flight, or no PDUs
-        if (rs < 0) return rs;
-    }
+    const int rs = fdc_sinks_submit_device(sinks, before);         // 0: nothing to submit yet, it hands out a batch still in flight, or no PDUs
+    if (rs < 0) return rs;
     HIPCHK(hipEventSynchronize(p->ev_in[0]));
     if (p->C > 0 || spectrum) HIPCHK(hipStreamSynchronize(fs));
     guard.ok = true;
@@ -2103,9 +2108,9 @@ int fdc_pipeline_work_sinks(fdc_pipeline *p, const void *in, int nblocks, void *
     // the spectrum goes straight into the sinks' device buffer (no PCIe round trip), then the sinks run on it; their power cells are summed from
     // the group powers the forward kernel leaves beside the spectrum
     float *const gpw = static_cast<float *>(fdc_sinks_group_power(sinks));
-    p->gpow_base = gpw; p->gpow_spec = static_cast<const float2 *>(fdc_sinks_spectrum(sinks));
-    int rc = pipeline_work_impl(p, in, nblocks, outs, spectrum, static_cast<float2 *>(fdc_sinks_spectrum(sinks)));
-    p->gpow_base = nullptr; p->gpow_spec = nullptr;
+    DeviceCall call = device_call(p, nullptr, fdc_sinks_spectrum(sinks));
+    call.gpow = gpw; call.gpow_origin = static_cast<const float2 *>(call.spectrum);
+    int rc = pipeline_work_impl(p, call, in, nblocks, outs, spectrum);
     if (rc < 0) return rc;
     if (gpw && rc > 0) { const int rp = fdc_sinks_prepare_from_groups(sinks, nblocks, 0); if (rp != FDC_OK) return rp; }
     const int rs = fdc_sinks_work_device(sinks, nblocks);
@@ -2144,10 +2149,8 @@ int fdc_pipeline_work_spectrum(fdc_pipeline *p, const void *in, int nblocks, voi
     // sink branches remain.  The front-end state (overlap history) is untouched; the block counter advances.
     if (!p) return fail(FDC_ERR_INVALID_ARGUMENT, "null handle");
     if (int rcf = check_float_output(p, "fdc_pipeline_work_spectrum")) return rcf;
-    if (nblocks < 0) return fail(FDC_ERR_INVALID_ARGUMENT, "negative item count");
-    if (nblocks == 0) return 0;
-    if (nblocks > p->cfg.max_blocks) return fail(FDC_ERR_INVALID_ARGUMENT, "nblocks %d above max_blocks %d", nblocks, p->cfg.max_blocks);
-    if (!in || (p->C > 0 && !outs)) return fail(FDC_ERR_INVALID_ARGUMENT, "null host buffer");
+    const int rca = check_work_args(p, in, nblocks, outs);
+    if (rca != FDC_OK || nblocks == 0) return rca;
     if (sinks && (fdc_sinks_blocklen(sinks) != p->N || nblocks > fdc_sinks_max_blocks(sinks)))
         return fail(FDC_ERR_INVALID_ARGUMENT, "sinks were created for blocklen %d / %d blocks per call, pipeline call has %d / %d",
                     fdc_sinks_blocklen(sinks), fdc_sinks_max_blocks(sinks), p->N, nblocks);
@@ -2159,13 +2162,13 @@ int fdc_pipeline_work_spectrum(fdc_pipeline *p, const void *in, int nblocks, voi
     const size_t n = (size_t)nblocks * p->N;
     HIPCHK(hipMemcpyAsync(d_full, in, sizeof(float2) * n, hipMemcpyHostToDevice, s));
     HIPCHK(fdc::launch_scale(d_full, d_full, n, 1.0f / (float)p->N, s));
+    // (not run_channel_groups: this loop sends 512- and 1024-bin groups to launch_channels, not launch_channels_wide — merging would change which kernel runs)
     for (size_t g = 0; g < p->groups.size(); g++) {
         const int l = p->groups[g].first;
-        if (l > 4096) {
-            const int rcw = channels_wide(p, d_full, p->d_out, p->d_groups + p->group_off[g], (int)p->groups[g].second.size(), l, nblocks, 0, nblocks,
-                                          p->blockcount, s);
-            if (rcw != FDC_OK) return rcw;
-        } else if (l == 256 && ((256 / p->R) & 1) == 0 && !p->cfg_generic)
+        if (l > 4096)
+            RCCHK(channels_wide(p, d_full, p->d_out, p->d_groups + p->group_off[g], (int)p->groups[g].second.size(), l,
+                                Span{nblocks, 0, nblocks, p->blockcount}, s));
+        else if (l == 256 && ((256 / p->R) & 1) == 0 && !p->cfg_generic)
             HIPCHK(fdc::launch_channels256(d_full, p->d_out, p->d_chans, p->d_groups + p->group_off[g],
                                            (int)p->groups[g].second.size(), p->g_aligned[g] != 0, p->g_out_aligned[g] != 0,
                                            p->N, p->R, nblocks, 0, nblocks, p->blockcount, p->d_wins, p->d_tw256, s));
@@ -2174,11 +2177,7 @@ int fdc_pipeline_work_spectrum(fdc_pipeline *p, const void *in, int nblocks, voi
                                         (int)p->groups[g].second.size(), l, p->N, p->R, nblocks, 0, nblocks, p->blockcount,
                                         p->d_wins, p->d_tw, p->ntab, s));
     }
-    for (int c = 0; c < p->C; c++) {
-        if (!outs[c]) continue;
-        HIPCHK(hipMemcpyAsync(outs[c], p->d_out + (size_t)nblocks * p->chans[c].out_off,
-                              sizeof(float2) * (size_t)nblocks * p->chans[c].lout, hipMemcpyDeviceToHost, s));
-    }
+    RCCHK(copy_outputs(p, outs, nblocks, sizeof(float2), p->d_out, s));
     if (spectrum) HIPCHK(hipMemcpyAsync(spectrum, d_full, sizeof(float2) * n, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     p->blockcount += nblocks;
