@@ -196,6 +196,40 @@ def _oq_format(fmt, scale):
     return OQ_FORMATS[fmt], sc
 
 
+def fine_tuning_increment(nu):
+    """fdc_fine_tuning_increment: the 64-bit phase increment per output sample of a fine-tuning frequency nu (cycles per output sample, |nu| < 0.5):
+    round_half_even(nu * 2**64) mod 2**64.  ValueError for NaN and |nu| >= 0.5.  Host only."""
+    inc = C.c_uint64(0)
+    rc = _lib.lib().fdc_fine_tuning_increment(float(nu), C.byref(inc))
+    if rc == -1:
+        raise ValueError(_lib.lib().fdc_last_error().decode())
+    _lib.check(rc)
+    return int(inc.value)
+
+
+def fine_tuning_nu(blocksize, freq, f, l):
+    """The fine-tuning frequency (cycles per output sample) that puts a carrier at `freq` (INTERNAL units: cycles per input sample, DC at 0.5) at DC of
+    the channel cut at bins [f, f + l) of the blocksize-point spectrum: the carrier's distance from the slice centre in bins — wrapped to the nearest
+    representative modulo blocksize, so that a slice wrapped below zero gets the small residual — over l."""
+    d = float(freq) * blocksize - (f + l / 2.0)
+    d -= blocksize * math.floor(d / blocksize + 0.5)
+    return d / l
+
+
+def _set_fine_tuning(fn, handle, nchan, nu):
+    """Pipeline.set_fine_tuning / PipelineGroup.set_fine_tuning: nu None (off) or one C double per channel"""
+    if nu is None:
+        rc = fn(handle, None, nchan)
+    else:
+        arr = np.ascontiguousarray(nu, dtype=np.float64)
+        if arr.ndim != 1:
+            raise ValueError("fine tuning takes one frequency per channel")
+        rc = fn(handle, arr.ctypes.data_as(C.POINTER(C.c_double)), int(arr.size))
+    if rc == -1:
+        raise ValueError(_lib.lib().fdc_last_error().decode())
+    _lib.check(rc)
+
+
 class _OutputFormat:
     """The channel outputs in the handle's output format (fdc_pipeline_set_output_format): complex64 arrays of nblocks*lout_c samples, or
     int16 / int8 arrays of shape (nblocks*lout_c, 2) (interleaved I/Q: sc16 / sc8)."""
@@ -267,6 +301,14 @@ class Pipeline(_OutputFormat):
         code, sc = _oq_format(fmt, scale)
         _lib.check(_lib.lib().fdc_pipeline_set_output_format(self._h, code, float(sc)))
         self._oq, self._oq_scale = code, sc if code else np.float32(1.0)
+
+    def set_fine_tuning(self, nu):
+        """fdc_pipeline_set_fine_tuning: nu[c] in cycles per OUTPUT sample of channel c, |nu| < 0.5 (an array of C doubles, one per channel), or None /
+        all zeros to switch it off.  While it is on, sample t of channel c's stream (counted from the last reset()) comes out times
+        exp(-2j pi frac(inc_c t / 2**64)), inc_c = fine_tuning_increment(nu[c]): a carrier nu_c above the slice centre lands at DC.  A setting like
+        set_output_format: it applies from the next call and survives reset(); the sink, spectrum-item, group-power and waterfall entries are
+        refused while it is on.  ValueError for a wrong count, NaN or |nu| >= 0.5 (nothing changes)."""
+        _set_fine_tuning(_lib.lib().fdc_pipeline_set_fine_tuning, self._h, len(self.channels), nu)
 
     # -- host path (what sync_block::work() would call)
     def work(self, x, want_spectrum=False, sinks=None, outs=None):
@@ -486,6 +528,10 @@ class PipelineGroup(_OutputFormat):
         _lib.check(_lib.lib().fdc_pipeline_group_set_output_format(self._h, code, float(sc)))
         self._oq, self._oq_scale = code, sc if code else np.float32(1.0)
 
+    def set_fine_tuning(self, nu):
+        """fdc_pipeline_group_set_fine_tuning: Pipeline.set_fine_tuning for every member."""
+        _set_fine_tuning(_lib.lib().fdc_pipeline_group_set_fine_tuning, self._h, len(self.channels), nu)
+
     def _run(self, fn, x, nb, want_spectrum, outs):
         outs = self._check_outs(outs, nb)
         ptrs = (C.c_void_p * max(1, len(outs)))(*[o.ctypes.data for o in outs])
@@ -570,7 +616,7 @@ class FrequencyDomainChannelizer:
                  pow_act_deactivation_delay,
                  pow_act_maxblocks, act_det_maxblocks,
                  debug, device_id=0, max_blocks=64, devices=None, pipelined=False, waterfall=None, iq_input=None, iq_scale=1.0,
-                 iq_output=None, iq_output_scale=1.0):
+                 iq_output=None, iq_output_scale=1.0, fine_tuning=False):
         # pipelined (not an argument of the reference): the sink blocks run beside the front end of the FOLLOWING work() calls, as the
         # thread-per-block scheduler runs them beside the FFT in the reference (fdc_pipeline_work_sinks on a look-ahead bank,
         # include/fdc_amd.h): same PDUs, handed out one or two work() calls later; flush() at the end of the stream
@@ -640,6 +686,26 @@ class FrequencyDomainChannelizer:
                 raise ValueError("iq_output cannot go with a waterfall")
             _oq_format(iq_output, iq_output_scale)
 
+        # fine_tuning (not an argument of the reference): every throughput channel comes out centred on its requested carrier, not on the bin its slice
+        # was rounded, wrapped or clamped to (Pipeline.set_fine_tuning with fine_tuning_nu of each channel, kept in self.fine_nu).  The PDUs of the sink
+        # blocks carry rel_cfreq themselves.
+        self.fine_tuning = bool(fine_tuning)
+        self.fine_nu = None
+        if self.fine_tuning:
+            if self.inpveclen != 1:
+                raise ValueError("fine_tuning needs inpveclen 1: the pre-transformed item entry writes the channels as they are cut")
+            if activity_controlled_channels or activity_detection_segments:
+                raise ValueError("fine_tuning cannot go with activity-controlled channels or detection segments")
+            if waterfall is not None:
+                raise ValueError("fine_tuning cannot go with a waterfall")
+            self.fine_nu = []
+            for (fr, bw) in self.throughput_channels:
+                f, l = get_opt_channelparams(self.blocksize, self.relinvovl, fr, bw)[:2]
+                nu = fine_tuning_nu(self.blocksize, fr, f, l)
+                if not abs(nu) < 0.5:
+                    raise ValueError("fine_tuning: the carrier %r lies outside its slice [%d, %d) (a slice clamped at the band edge)" % (fr, f, f + l))
+                self.fine_nu.append(nu)
+
         if self.verbose:                                        # runtime information, :176-193
             bar = '\n' + '#' * 32 + '\n'
             for ln in (bar, '# gr-FDC Frequency Domain Channelizer Runtime Information', bar,
@@ -689,6 +755,8 @@ class FrequencyDomainChannelizer:
                                      keep_spectrum=self.debug or self.sinks is not None)
         if iq_output is not None:
             self.pipeline.set_output_format(iq_output, iq_output_scale)
+        if self.fine_tuning:
+            self.pipeline.set_fine_tuning(np.asarray(self.fine_nu, dtype=np.float64))
         self.N_throughput_channelizers = len(self.channel_params)
         # waterfall (not an argument of the reference, whose example flowgraph wires the spectrum to complex_to_mag_squared and
         # FDC.WaterfallMsgTagging outside the hier block): a gr_fdc_amd.Waterfall fed from the spectrum on the device; work() then

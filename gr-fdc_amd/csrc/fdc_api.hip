@@ -7,6 +7,7 @@
 #include "fdc_plan_cost.hpp"
 #include "fdc_waterfall.hpp"
 #include "fdc_iq.hpp"
+#include "fdc_fine.hpp"
 
 #include <algorithm>
 #include <array>
@@ -226,6 +227,13 @@ struct fdc_pipeline {
     unsigned char *d_oq = nullptr;   // host entries: the narrow results, max_blocks*sum_lout samples of fdc::kIqRingBytes (the widest format), allocated
                                      // at the first integer-output call
     std::string oq_route;        // how the last integer-output call was served (fdc_pipeline_describe)
+    // fine tuning (fdc_pipeline_set_fine_tuning): a setting like the output format.  fine_on: some increment is not zero; the tables are allocated by the
+    // first call that switches it on and rewritten by every later one: d_fine[c] = (inc_c, where channel c's lout_c step factors start in d_fstep),
+    // d_f4fine the same per row of path 5's schedule (d_f4rows)
+    bool fine_on = false;
+    fdc::FineChan *d_fine = nullptr, *d_f4fine = nullptr;
+    float2 *d_fstep = nullptr;
+    std::string fine_route;      // how the last call with fine tuning was served (fdc_pipeline_describe)
     float2 *d_out = nullptr;     // work(): max_blocks*sum_lout
     int64_t blockcount = 0;      // work(): blocks consumed so far
     // work(): transfers and kernels of consecutive sub-batches overlap (H2D on s_in, kernels on stream, D2H on s_out)
@@ -428,6 +436,7 @@ void fdc_pipeline_destroy(fdc_pipeline *p)
     (void)hipFree(p->d_tw512); (void)hipFree(p->d_twq512); (void)hipFree(p->d_t2g);
     (void)hipFree(p->d_tw1k); (void)hipFree(p->d_twq1k);
     (void)hipFree(p->d_big); (void)hipFree(p->d_wtasks); (void)hipFree(p->d_tmp); (void)hipFree(p->d_spec); (void)hipFree(p->d_ring); (void)hipFree(p->d_out); (void)hipFree(p->d_real); (void)hipFree(p->d_iq); (void)hipFree(p->d_iqw);
+    (void)hipFree(p->d_fine); (void)hipFree(p->d_f4fine); (void)hipFree(p->d_fstep);
     if (p->stream) (void)hipStreamDestroy(p->stream);
     delete p;
 }
@@ -1138,6 +1147,7 @@ int32_t fdc_pipeline_describe(const fdc_pipeline *p, char *buf, int32_t n)
     if (!p->wf_route.empty()) add("; waterfall rows: %s", p->wf_route.c_str());
     if (!p->iq_route.empty()) add("; input %s", p->iq_route.c_str());
     if (!p->oq_route.empty()) add("; output %s", p->oq_route.c_str());
+    if (!p->fine_route.empty()) add("; fine tuning: %s", p->fine_route.c_str());
     std::snprintf(buf, (size_t)n, "%s", t);
     return k;
 }
@@ -1339,6 +1349,7 @@ static bool oq_fused(const fdc_pipeline *p, const DeviceCall &call, int nblocks)
 {
     if (!int_kernels(p, call)) return false;
     if (p->fused) return true;
+    if (p->fine_on) return false;            // the banks' kernels do not turn their samples: float, k_fine_rotate, then narrowed
     if (!(p->block_hints & 1) || (!call.fmt && p->N == 65536 && p->R == 4)) return false;
     for (int m0 = 0; m0 < nblocks; m0 += p->chunk)
         if (std::min(p->chunk, nblocks - m0) < p->block_min && two_launch_possible(p)) return false;
@@ -1371,6 +1382,12 @@ static int process_device_impl(fdc_pipeline *p, DeviceCall &call, const void *d_
     unsigned char *const ob = ofused ? static_cast<unsigned char *>(d_out) : reinterpret_cast<unsigned char *>(o);
     const bool use_poly = p->poly_ok && !d_spectrum;
     const unsigned out_bytes = (unsigned)((int64_t)nblocks * p->sum_lout * (int64_t)osz);
+    // fine tuning: path 5 turns the samples in its own stores; everywhere else k_fine_rotate goes over the launch group's float results behind its channel kernels
+    const bool fine = p->fine_on && p->C > 0, fine_fused = fine && p->fused && !d_spectrum;
+    auto rotate = [&](const Span &g) -> int {
+        if (fine) HIPCHK(fdc::launch_fine_rotate(o, p->d_chans, p->d_fine, p->d_fstep, p->C, g.nb, g.m0, g.nblocks, g.first_block, s));
+        return FDC_OK;
+    };
     for (int m0 = 0; m0 < nblocks; m0 += p->chunk) {
         const int nb = std::min(p->chunk, nblocks - m0);
         const Span grp{nb, m0, nblocks, first_block};
@@ -1402,7 +1419,11 @@ static int process_device_impl(fdc_pipeline *p, DeviceCall &call, const void *d_
             // N = 4096: one launch, nothing but the input samples and the output samples crosses the memory interface
             if (tg) HIPCHK(hipEventRecord(p->events[span[0]], s));
             float *wf = call.rows ? call.rows + (size_t)(first_block - call.rows_first + m0) * fdc::kWfWidth : nullptr;
-            if (ofused)
+            if (fine_fused)
+                HIPCHK(fdc::launch_fused4096_fine(ifused ? fmt : 0, call.scale, ifused ? raw0 : static_cast<const void *>(in0), (size_t)p->H, ofused ? ofmt : 0, call.oscale,
+                                                  ofused ? d_out : static_cast<void *>(o), nb, p->R, m0, nblocks, first_block, p->d_tw, p->ntab, p->d_wins, p->d_f4rows,
+                                                  p->f4_cls, p->f4_teams, p->d_f4fine, p->d_fstep, s));
+            else if (ofused)
                 HIPCHK(fdc::launch_fused4096_oq(ifused ? fmt : 0, call.scale, ifused ? raw0 : static_cast<const void *>(in0), (size_t)p->H, ofmt, call.oscale, d_out, nb,
                                                 p->R, m0, nblocks, first_block, p->d_tw, p->ntab, p->d_wins, p->d_f4rows, p->f4_cls, p->f4_teams, s));
             else if (ifused)
@@ -1433,6 +1454,7 @@ static int process_device_impl(fdc_pipeline *p, DeviceCall &call, const void *d_
             if (p->split) RCCHK(run_remainder(p, call, in0, o, grp, tg ? p->events[span[2]] : nullptr, tg ? p->events[span[3]] : nullptr));
             else if (tg) span[2] = span[3] = span[1];
             if (tg) { span[4] = kSpanBanks; p->ev_spans.push_back(span); }
+            RCCHK(rotate(grp));
             continue;
         }
         if (use_poly) {
@@ -1451,6 +1473,7 @@ static int process_device_impl(fdc_pipeline *p, DeviceCall &call, const void *d_
             else
                 HIPCHK(fdc::launch_poly_stage2(p->d_g, o, p->N / 256, p->R, nb, m0, nblocks, p->d_tw256, p->d_tw1024, bk.d_slot_off, out_bytes, call.ncu, s));
             if (p->split) RCCHK(run_remainder(p, call, in0, o, grp, nullptr, nullptr));   // (timing: the remainder is counted with stage 2)
+            RCCHK(rotate(grp));
             if (tg) {
                 HIPCHK(hipEventRecord(p->events[span[3]], s));
                 span[4] = kSpanTwoLaunch;
@@ -1476,6 +1499,7 @@ static int process_device_impl(fdc_pipeline *p, DeviceCall &call, const void *d_
             if (gp) HIPCHK(fdc::launch_group_power(spec, p->N, nb, gp, s));
         }
         RCCHK(run_channel_groups(p, false, spec, o, grp, s));
+        RCCHK(rotate(grp));
         if (tg) {
             HIPCHK(hipEventRecord(p->events[span[3]], s));
             span[4] = p->N <= fdc::kMaxLdsFft ? kSpanSpectrumLds : kSpanSpectrum;
@@ -1483,6 +1507,7 @@ static int process_device_impl(fdc_pipeline *p, DeviceCall &call, const void *d_
         }
     }
     if (ofmt && !ofused && call.narrow && p->C > 0) HIPCHK(fdc::launch_complex_to_iq(ofmt, call.oscale, call.fout, d_out, (size_t)nblocks * p->sum_lout, s));
+    if (fine) p->fine_route = fine_fused ? "fused" : "rotated";
     return FDC_OK;
 }
 
@@ -1555,6 +1580,7 @@ int fdc_pipeline_process_device_power(fdc_pipeline *p, const void *d_ring, int64
     FDC_ENTRY("fdc_pipeline_process_device_power")
     if (!p) return fail(FDC_ERR_INVALID_ARGUMENT, "null handle");
     if (p->out_form) return fail(FDC_ERR_INVALID_ARGUMENT, "fdc_pipeline_process_device_power writes complex float outputs only (the handle's output format is not FC32)");
+    if (p->fine_on) return fail(FDC_ERR_INVALID_ARGUMENT, "fdc_pipeline_process_device_power writes the channels as they are cut: switch fine tuning off first");
     if (d_group_power && (!d_spectrum || (p->N & 15))) return fail(FDC_ERR_INVALID_ARGUMENT, "group powers go with a spectrum output of a block length that is a multiple of 16");
     DeviceCall call = device_call(p, stream, d_spectrum);
     call.gpow = static_cast<float *>(d_group_power);
@@ -1606,12 +1632,15 @@ void fdc_pipeline_reset(fdc_pipeline *p)
     p->in_scale = 0.f;
     p->iq_route.clear();
     p->oq_route.clear();         // (the output format itself is a setting: it stays)
+    p->fine_route.clear();       // (and so does fine tuning)
 }
 
 // the entries that write complex float only (sinks, spectrum items, group powers, waterfall): refused while the output format is not FC32
-static int check_float_output(const fdc_pipeline *p, const char *entry)
+// (and, but for the flush of a batch that is inside already, while fine tuning is on: they write the channels as they are cut)
+static int check_float_output(const fdc_pipeline *p, const char *entry, bool writes_channels = true)
 {
     if (p && p->out_form) return fail(FDC_ERR_INVALID_ARGUMENT, "%s writes complex float outputs only: set the output format to FDC_OQ_FC32 first", entry);
+    if (p && p->fine_on && writes_channels) return fail(FDC_ERR_INVALID_ARGUMENT, "%s writes the channels as they are cut: switch fine tuning off first (fdc_pipeline_set_fine_tuning(p, NULL, C))", entry);
     return FDC_OK;
 }
 
@@ -1630,6 +1659,57 @@ int fdc_pipeline_set_output_format(fdc_pipeline *p, int32_t format, float scale)
     }
     p->out_form = format;
     p->out_scale = format ? scale : 1.0f;
+    return FDC_OK;
+    FDC_ENTRY_END
+}
+
+int fdc_fine_tuning_increment(double nu, uint64_t *inc)
+{
+    FDC_ENTRY("fdc_fine_tuning_increment")
+    if (!inc) return fail(FDC_ERR_INVALID_ARGUMENT, "null argument");
+    if (!(std::fabs(nu) < 0.5)) return fail(FDC_ERR_INVALID_ARGUMENT, "the fine-tuning frequency must be inside (-0.5, 0.5) cycles per output sample");
+    // nu * 2^64 is exact in double (a power of two), |.| < 2^63; nearbyint rounds half to even in the default rounding mode
+    const double r = std::nearbyint(std::ldexp(nu, 64));
+    *inc = r < 0 ? (uint64_t)0 - (uint64_t)(-r) : (uint64_t)r;
+    return FDC_OK;
+    FDC_ENTRY_END
+}
+
+int fdc_pipeline_set_fine_tuning(fdc_pipeline *p, const double *nu, int n)
+{
+    FDC_ENTRY("fdc_pipeline_set_fine_tuning")
+    if (!p) return fail(FDC_ERR_INVALID_ARGUMENT, "null handle");
+    if (n != p->C) return fail(FDC_ERR_INVALID_ARGUMENT, "fine tuning: %d frequencies for %d channels", n, p->C);
+    if (p->hier_filled > 0)
+        return fail(FDC_ERR_INVALID_ARGUMENT, "a pipelined sinks batch is still inside the handle: fdc_pipeline_flush_sinks until it returns 0 first");
+    std::vector<uint64_t> inc((size_t)p->C, 0);
+    bool on = false;
+    for (int c = 0; nu && c < p->C; c++) {
+        RCCHK(fdc_fine_tuning_increment(nu[c], &inc[(size_t)c]));
+        on = on || inc[(size_t)c] != 0;
+    }
+    if (!on) { p->fine_on = false; p->fine_route.clear(); return FDC_OK; }
+    // the tables: per channel (inc, start of its step factors; even, so that a row of them can be read 16 bytes at a time), per schedule row of path 5
+    // the same, and step_c[j] = exp(-2 pi i frac(inc_c j / 2^64)) designed in double, rounded once
+    std::vector<fdc::FineChan> fc((size_t)p->C), f4(64, fdc::FineChan{0, 0});
+    long long off = 0;
+    for (int c = 0; c < p->C; c++) { fc[(size_t)c] = fdc::FineChan{inc[(size_t)c], off}; off += (p->chans[(size_t)c].lout + 1) & ~1; }
+    std::vector<float2> step((size_t)off, make_float2(1.0f, 0.0f));
+    for (int c = 0; c < p->C; c++)
+        for (int j = 0; j < p->chans[(size_t)c].lout; j++)
+            step[(size_t)(fc[(size_t)c].step_off + j)] = unit(std::ldexp((double)(inc[(size_t)c] * (uint64_t)j), -64));
+    if (p->fused)
+        for (int w = 0; w < 4 * p->f4_teams; w++)
+            for (size_t k = 0; k < p->f4_wave[w].size() && k < 8; k++) f4[(size_t)(8 * w) + k] = fc[(size_t)(p->f4_wave[w][k] >> 1)];
+    HIPCHK(hipSetDevice(p->cfg.device_id));
+    HIPCHK(hipStreamSynchronize(p->stream));          // (no call of the host entries is in flight; a device entry's caller orders its own stream)
+    if (!p->d_fine) HIPCHK(hipMalloc(&p->d_fine, sizeof(fdc::FineChan) * fc.size()));
+    if (!p->d_fstep) HIPCHK(hipMalloc(&p->d_fstep, sizeof(float2) * step.size()));
+    if (p->fused && !p->d_f4fine) HIPCHK(hipMalloc(&p->d_f4fine, sizeof(fdc::FineChan) * f4.size()));
+    HIPCHK(hipMemcpy(p->d_fine, fc.data(), sizeof(fdc::FineChan) * fc.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(p->d_fstep, step.data(), sizeof(float2) * step.size(), hipMemcpyHostToDevice));
+    if (p->fused) HIPCHK(hipMemcpy(p->d_f4fine, f4.data(), sizeof(fdc::FineChan) * f4.size(), hipMemcpyHostToDevice));
+    p->fine_on = true;
     return FDC_OK;
     FDC_ENTRY_END
 }
@@ -2122,7 +2202,7 @@ int fdc_pipeline_flush_sinks(fdc_pipeline *p, fdc_sinks *sinks)
 {
     FDC_ENTRY("fdc_pipeline_flush_sinks")
     if (!p || !sinks) return fail(FDC_ERR_INVALID_ARGUMENT, "null handle");
-    if (int rcf = check_float_output(p, "fdc_pipeline_flush_sinks")) return rcf;
+    if (int rcf = check_float_output(p, "fdc_pipeline_flush_sinks", false)) return rcf;
     if (p->hier_broken) return fail(FDC_ERR_HIP, "an earlier pipelined call failed after it had advanced the stream state: destroy the pipeline and the bank");
     if (p->hier_bank == sinks && p->hier_filled > 0) {
         const int n = p->hier_filled;

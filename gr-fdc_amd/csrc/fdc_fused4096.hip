@@ -25,6 +25,7 @@
 #include "fdc_devutil.hpp"
 #include <type_traits>
 #include "fdc_iq.hpp"
+#include "fdc_fine.hpp"
 
 namespace fdc {
 
@@ -69,6 +70,24 @@ __device__ __forceinline__ void out_st_oq(TO *p, cf v, float s)
 __device__ __forceinline__ void out_st(sc16 *p, cf v, float s) { out_st_oq<sc16, unsigned>(p, v, s); }
 __device__ __forceinline__ void out_st(sc8 *p, cf v, float s) { out_st_oq<sc8, unsigned short>(p, v, s); }
 
+// Fine tuning in the stores (the FINE forms; fdc_fine.hpp): rows[wave][slot] = the increment of the schedule row's channel and where its step factors start,
+// block0 = the stream's index of the launch's block 0
+struct F4Fine { const FineChan *rows; const float2 *step; unsigned long long block0; };
+// what the stores of one row need: its base (once per row) and its step factors, moved so that sample t of the L-point transform reads st[t]
+__device__ __forceinline__ void fine_row(const F4Fine &fa, int slot, const F4Row &ri, int m0, int L, cf &base, const float2 *&st)
+{
+    const FineChan f = fa.rows[slot];
+    base = fine_base(f.inc, fa.block0 + (unsigned long long)(m0 + (ri.valid ? ri.valid - 1 : 0)), (unsigned)ri.lout);
+    st = fa.step + (f.step_off - (L - ri.lout));
+}
+// the value of sample t of a row as it is stored; FINE: turned first
+template <bool FINE>
+__device__ __forceinline__ cf fine_val(cf v, [[maybe_unused]] cf base, [[maybe_unused]] const float2 *st, [[maybe_unused]] int t)
+{
+    if constexpr (FINE) return fine_rotate(v, base, ld2(st + t));
+    else return v;
+}
+
 struct RowAt { const float2 *win; const float2 *spec; long long dst; bool on; };
 // ri.valid: 0 = no row, 1 + k = a row of the workgroup's block k
 // fbm = (first block of the call + first block of the launch) mod R
@@ -91,6 +110,7 @@ __device__ __forceinline__ RowAt row_at(const F4Row &ri, int L, int m0, int nb, 
 // registers the spectrum store leaves; ROWS = false is the kernel without it, instruction for instruction
 // TI: the input sample, float2 or complex integer (sc16 / sc8, fdc_iq.hpp: widened times iq_scale right after its load)
 // TO: the output sample, float2 or complex integer (sc16 / sc8: narrowed times oq_scale in out_st)
+// (the body is fdc_fused4096_body.inc, shared with the FINE forms below)
 template <bool WIDE, int TEAMS, bool ROWS, class TI = float2, class TO = float2>
 __global__ __launch_bounds__(256 * TEAMS, 4 /* waves per SIMD */) void k_f4096(const TI *__restrict__ in, size_t in_stride, TO *__restrict__ out, int nb, int R,
                                                   int mbase, int nb_call, int fbm /* (first block of the call + mbase) mod R */, const float2 *__restrict__ tw,
@@ -98,320 +118,20 @@ __global__ __launch_bounds__(256 * TEAMS, 4 /* waves per SIMD */) void k_f4096(c
                                                   const F4Row *__restrict__ rows, unsigned wcls,
                                                   typename IqTail<TI, TO>::type wf /* integer TI / TO: iq_scale / oq_scale */)
 {
-    static_assert(!ROWS || std::is_same<TO, float2>::value, "integer output: not the waterfall form");
-    [[maybe_unused]] const float iq_scale = iq_tail_scale(wf);
-    [[maybe_unused]] const float oq_scale = oq_tail_scale(wf);
-    float2 *tiles = reinterpret_cast<float2 *>(fdc_smem_f4);
-    float2 *t256 = reinterpret_cast<float2 *>(fdc_smem_f4 + f4_off_t256(TEAMS));
-    float2 *t4k = reinterpret_cast<float2 *>(fdc_smem_f4 + f4_off_t4k(TEAMS));
-    const F4Row *srows = reinterpret_cast<const F4Row *>(fdc_smem_f4 + f4_off_rows(TEAMS));
-    const int team = TEAMS == 1 ? 0 : threadIdx.x >> 8, tid = threadIdx.x & 255, lo = tid & 15, hi = tid >> 4;
-    // neighbouring blocks share R - 1 of R input samples: workgroup ids go round the eight XCDs, so XCD x takes the x-th eighth of the launch
-    // and the shared samples are hits in ITS L2
-    const int ngroups = (nb + TEAMS - 1) / TEAMS, per = (ngroups + 7) >> 3;
-    const int grp = (int)(blockIdx.x & 7) * per + (int)(blockIdx.x >> 3);
-    if (grp >= ngroups) return;
-    const int m0 = TEAMS * grp, m = m0 + team;
-    float2 *tile = tiles + team * kF4TilePts;
-    if (team == 0) {
-        t256[hi * 18 + lo] = tw[((16 * hi * lo) & 4095) * twstride];
-        t4k[hi * 18 + lo] = tw[(hi * lo) * twstride];
-    }
-    if (team == TEAMS - 1) {
-        if (tid < 64 * TEAMS) reinterpret_cast<float4 *>(fdc_smem_f4 + f4_off_rows(TEAMS))[tid] = reinterpret_cast<const float4 *>(rows)[tid];
-        if constexpr (WIDE) {
-            float2 *w1k = reinterpret_cast<float2 *>(fdc_smem_f4 + f4_off_w1k(TEAMS)), *w64 = reinterpret_cast<float2 *>(fdc_smem_f4 + f4_off_w64(TEAMS));
-            for (int i = tid; i < 512; i += 256) w1k[(i >> 5) * 34 + (i & 31)] = tw[((i >> 5) * (i & 31)) * (4 * twstride)];
-            if (tid < 64) w64[(tid >> 5) * 34 + (tid & 31)] = tid < 32 ? make_float2(1.0f, 0.0f) : tw[(tid & 31) * (64 * twstride)];
-        }
-    }
-    // ---- forward transform: n = a + 16 b + 256 c, k = k0 + 16 k1 + 256 k2 (k_fft4096, fdc_chanwide.hip) ---------------------------------
-    cf v[32];
-    {
-        cf (&u)[16] = reinterpret_cast<cf (&)[16]>(v[0]);
-        // integer input: the sixteen raw words first, all in flight together; widened behind the barrier (converted one by one as they
-        // arrive, the compiler waited for each load before issuing the next)
-        [[maybe_unused]] unsigned raw[16];
-        if constexpr (!std::is_same<TI, float2>::value) {
-#pragma unroll
-            for (int c = 0; c < 16; c++) raw[c] = m < nb ? iq_bits(in + (size_t)m * in_stride + (tid + 256 * c)) : 0u;
-        } else
-#pragma unroll
-        for (int c = 0; c < 16; c++) u[c] = m < nb ? ld2(in + ((size_t)m * in_stride + (tid + 256 * c))) : mk(0.f, 0.f);
-        __syncthreads();
-        if constexpr (!std::is_same<TI, float2>::value) {
-#pragma unroll
-            for (int c = 0; c < 16; c++) u[c] = iq_widen_bits(TI{}, raw[c], iq_scale);
-        }
-        dft16<false>(u);                                             // layer 1 over c: k0 in u[rev16(k0)]; thread = (a = lo, b = hi)
-        {
-            cf w[16];
-#pragma unroll
-            for (int i = 0; i < 8; i++) {
-                const float4 t = ld4(&t256[hi * 18 + 2 * i]);
-                w[2 * i] = mk(t.x, t.y); w[2 * i + 1] = mk(t.z, t.w);
-            }
-#pragma unroll
-            for (int k0 = 0; k0 < 16; k0++) st2(&tile[k0 * 272 + tid], k0 == 0 ? u[rev16(0)] : cmul(u[rev16(k0)], w[k0]));
-        }
-        __syncthreads();
-#pragma unroll
-        for (int b = 0; b < 16; b++) u[b] = ld2(&tile[hi * 272 + b * 16 + lo]);      // thread = (a = lo, k0 = hi)
-        dft16<false>(u);                                             // layer 2 over b: k1 in u[rev16(k1)]
-        __syncthreads();                                             // every read of exchange 1 is done
-        {
-            const cf s = ld2(&t4k[lo * 18 + hi]);                    // W_4096^(a k0)
-            cf w[16];
-#pragma unroll
-            for (int i = 0; i < 8; i++) {
-                const float4 t = ld4(&t256[lo * 18 + 2 * i]);        // W_256^(a k1)
-                w[2 * i] = mk(t.x, t.y); w[2 * i + 1] = mk(t.z, t.w);
-            }
-#pragma unroll
-            for (int k1 = 0; k1 < 16; k1++) st2(&tile[k1 * 257 + hi * 16 + (lo ^ hi)], cmul(u[rev16(k1)], k1 == 0 ? s : cmul(s, w[k1])));
-        }
-        __syncthreads();
-#pragma unroll
-        for (int a = 0; a < 16; a++) u[a] = ld2(&tile[hi * 257 + lo * 16 + (a ^ lo)]);   // thread = (k0 = lo, k1 = hi)
-        dft16<false>(u);                                             // layer 3 over a: bin k0 + 16 k1 + 256 k2 in u[rev16(k2)]
-        __syncthreads();                                             // every read of exchange 2 is done
-        // the shifted spectrum (fftshift: bin k at k + N/2; python/FrequencyDomainChannelizer.py:206 fft_vcc(..., shift = True)), times 1/N
-#pragma unroll
-        for (int k2 = 0; k2 < 16; k2++) st2(&tile[tid + 256 * (k2 ^ 8)], u[rev16(k2)] * (1.0f / 4096.0f));
-        if constexpr (ROWS) {
-            // shifted bin tid + 256 (k2 ^ 8) is pixel (tid >> 2) + 64 (k2 ^ 8): the four bins of a pixel are in four adjacent lanes (one DPP quad);
-            // m is uniform over the team, so every lane of the quad takes part
-            if (m < nb) {
-                float *dst = wf + (size_t)m * 1024 + (tid >> 2);
-#pragma unroll
-                for (int k2 = 0; k2 < 16; k2++) {
-                    const cf x = u[rev16(k2)] * (1.0f / 4096.0f);
-                    const float pw = quad_sum(x.x * x.x + x.y * x.y);
-                    if ((tid & 3) == 0) dst[64 * (k2 ^ 8)] = pw;
-                }
-            }
-        }
-    }
-    __syncthreads();
-    // ---- the rows of this wave ---------------------------------------------------------------------------------------------------------
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
-    const unsigned cls = (wcls >> (4 * wave)) & 0xfu;
-    const F4Row *wr = srows + 8 * wave;
-    F4Row r0{}, r1{};
-    RowAt a0{}, a1{};
-    if (cls == 1 || cls == 2) {
-        const int b = lane & 15;
-        r0 = wr[lane >> 4];
-        a0 = row_at(r0, 256, m0, nb, mbase, fbm, R, wins, nb_call, tiles);
-        {
-            cf w[16];
-#pragma unroll
-            for (int a = 0; a < 16; a++) w[a] = ld2(a0.win + 16 * a + b);
-#pragma unroll
-            for (int a = 0; a < 16; a++) v[a ^ 8] = cmul(ld2(a0.spec + 16 * a + b), w[a]);      // ifftshift of the slice: i -> i + l/2
-        }
-        if (cls == 2) {
-            r1 = wr[4 + (lane >> 4)];
-            a1 = row_at(r1, 256, m0, nb, mbase, fbm, R, wins, nb_call, tiles);
-            cf w[16];
-#pragma unroll
-            for (int a = 0; a < 16; a++) w[a] = ld2(a1.win + 16 * a + b);
-#pragma unroll
-            for (int a = 0; a < 16; a++) v[16 + (a ^ 8)] = cmul(ld2(a1.spec + 16 * a + b), w[a]);
-        }
-        dft16<true>(reinterpret_cast<cf (&)[16]>(v[0]));
-        if (cls == 2) dft16<true>(reinterpret_cast<cf (&)[16]>(v[16]));
-    }
-    if constexpr (WIDE) {
-        if (cls == 3 || cls == 4) {
-            const int L = cls == 3 ? 512 : 1024, lg = cls == 3 ? 4 : 5;
-            const int b = lane & ((1 << lg) - 1);
-            r0 = wr[lane >> lg];
-            a0 = row_at(r0, L, m0, nb, mbase, fbm, R, wins, nb_call, tiles);
-            cf w[32];
-#pragma unroll
-            for (int a = 0; a < 32; a++) w[a] = ld2(a0.win + (a << lg) + b);
-#pragma unroll
-            for (int a = 0; a < 32; a++) v[a ^ 16] = cmul(ld2(a0.spec + (a << lg) + b), w[a]);
-            dft32<true>(v);                                          // over a: index p in v[pos32(p)]
-        }
-    }
-    if (cls >= 5) {
-        // l = 128 (8 lanes x 16 points per row), 64 (4 lanes), 32 (2 lanes), 16 (one lane): eight rows on the first 8 * lanes lanes of the wave; slice (a << lg) + b
-        const int lg = 8 - (int)cls, b = lane & ((1 << lg) - 1);
-        r0 = wr[(lane >> lg) & 7];
-        a0 = row_at(r0, 16 << lg, m0, nb, mbase, fbm, R, wins, nb_call, tiles);
-        if ((lane >> lg) >= 8) a0.on = false;
-        cf w[16];
-#pragma unroll
-        for (int a = 0; a < 16; a++) w[a] = ld2(a0.win + (a << lg) + b);
-#pragma unroll
-        for (int a = 0; a < 16; a++) v[a ^ 8] = cmul(ld2(a0.spec + (a << lg) + b), w[a]);          // ifftshift of the slice: i -> i + l/2 = a -> a ^ 8
-        dft16<true>(reinterpret_cast<cf (&)[16]>(v[0]));             // over a: index p in v[rev16(p)]
-    }
-    __syncthreads();                                                 // every slice has been read: the tiles belong to the rows' exchanges
-    if (cls == 1 || cls == 2) {
-        const int b = lane & 15;
-        cf w[16];
-#pragma unroll
-        for (int i = 0; i < 8; i++) {
-            const float4 t = ld4(&t256[b * 18 + 2 * i]);
-            w[2 * i] = mk(t.x, t.y); w[2 * i + 1] = mk(t.z, t.w);
-        }
-        // element (b, p) of a row at p * 16 + (b ^ p): stores of one p and loads of one b are conflict-free (k_c256)
-        float2 *row0 = tiles + r0.xch, *row1 = tiles + r1.xch;
-        if (a0.on) {
-#pragma unroll
-            for (int p = 0; p < 16; p++) st2(&row0[p * 16 + (b ^ p)], cmulc(v[rev16(p)], w[p]));
-        }
-        if (cls == 2 && a1.on) {
-#pragma unroll
-            for (int p = 0; p < 16; p++) st2(&row1[p * 16 + (b ^ p)], cmulc(v[16 + rev16(p)], w[p]));
-        }
-        wave_sync();
-#pragma unroll
-        for (int bb = 0; bb < 16; bb++) v[bb] = ld2(&row0[b * 16 + (bb ^ b)]);
-        if (cls == 2) {
-#pragma unroll
-            for (int bb = 0; bb < 16; bb++) v[16 + bb] = ld2(&row1[b * 16 + (bb ^ b)]);
-        }
-        dft16<true>(reinterpret_cast<cf (&)[16]>(v[0]));
-        if (cls == 2) dft16<true>(reinterpret_cast<cf (&)[16]>(v[16]));
-        // y[t], t = b + 16 q; keep t >= l/R (vector_cut_vxx(l, l - lout, lout)), times l (multiply_const_cc)
-        const int skip = 256 - r0.lout;
-        if (a0.on) {
-#pragma unroll
-            for (int q = 0; q < 16; q++) if (b + 16 * q >= skip) out_st(out + a0.dst + b + 16 * q, v[rev16(q)] * 256.f, oq_scale);
-        }
-        if (cls == 2 && a1.on) {
-#pragma unroll
-            for (int q = 0; q < 16; q++) if (b + 16 * q >= skip) out_st(out + a1.dst + b + 16 * q, v[16 + rev16(q)] * 256.f, oq_scale);
-        }
-    }
-    if constexpr (WIDE) {
-        // the inter-layer twiddles of both wide forms from ONE table: W_1024^(x p) = W_1024^((x & 15) p) W_64^((x >> 4) p), x < 32;
-        // l = 1024: x = b; l = 512: W_512^(b p) = W_1024^(2 b p), x = 2 b
-        if (cls == 3 || cls == 4) {
-            const int lg = cls == 3 ? 4 : 5, b = lane & ((1 << lg) - 1), x = cls == 3 ? 2 * b : b;
-            const float2 *wa = reinterpret_cast<const float2 *>(fdc_smem_f4 + f4_off_w1k(TEAMS)) + (x & 15) * 34;
-            const float2 *wb = reinterpret_cast<const float2 *>(fdc_smem_f4 + f4_off_w64(TEAMS)) + (x >> 4) * 34;
-            float2 *row = tiles + r0.xch;
-            // element (b, p) of a row at p * lanes + (b ^ (p mod lanes)) (k_c1024, k_c512)
-            if (a0.on) {
-#pragma unroll
-                for (int i = 0; i < 16; i++) {
-                    const float4 t = ld4(&wa[2 * i]), c = ld4(&wb[2 * i]);
-                    st2(&row[((2 * i) << lg) + (b ^ ((2 * i) & ((1 << lg) - 1)))], cmulc(v[pos32(2 * i)], cmul(mk(t.x, t.y), mk(c.x, c.y))));
-                    st2(&row[((2 * i + 1) << lg) + (b ^ ((2 * i + 1) & ((1 << lg) - 1)))], cmulc(v[pos32(2 * i + 1)], cmul(mk(t.z, t.w), mk(c.z, c.w))));
-                }
-            }
-            wave_sync();
-            if (cls == 4) {
-#pragma unroll
-                for (int bb = 0; bb < 32; bb++) v[bb] = ld2(&row[b * 32 + (bb ^ b)]);
-                dft32<true>(v);                                      // y[t = b + 32 q] in v[pos32(q)]
-                const int skip = 1024 - r0.lout;
-                if (a0.on) {
-#pragma unroll
-                    for (int q = 0; q < 32; q++) if (b + 32 * q >= skip) out_st(out + a0.dst + b + 32 * q, v[pos32(q)] * 1024.f, oq_scale);
-                }
-            } else {
-                // l = 512 = 32 x 16: DFT-16 over b for p = lane and p = lane + 16; y[t = p + 32 q]
-#pragma unroll
-                for (int bb = 0; bb < 16; bb++) {
-                    v[bb] = ld2(&row[b * 16 + (bb ^ b)]);
-                    v[16 + bb] = ld2(&row[(b + 16) * 16 + (bb ^ b)]);
-                }
-                dft16<true>(reinterpret_cast<cf (&)[16]>(v[0]));
-                dft16<true>(reinterpret_cast<cf (&)[16]>(v[16]));
-                const int skip = 512 - r0.lout;
-                if (a0.on) {
-#pragma unroll
-                    for (int q = 0; q < 16; q++) {
-                        const int t0 = b + 32 * q, t1 = t0 + 16;
-                        if (t0 >= skip) out_st(out + a0.dst + t0, v[rev16(q)] * 512.f, oq_scale);
-                        if (t1 >= skip) out_st(out + a0.dst + t1, v[16 + rev16(q)] * 512.f, oq_scale);
-                    }
-                }
-            }
-        }
-    }
-    if (cls >= 5) {
-        // y[t = p + 16 q] = sum_b W_l^(-b p) W_(l/16)^(-b q) (DFT-16 over a)[p]: twiddle W_l^(b p) = W_256^((256 / l) b p) from the 256 table, an exchange inside the
-        // row — element (b, p) at p * lanes + (b ^ (p mod lanes)) — then every lane runs the DFT-(l/16) over b for its 16 / lanes values of p
-        const int lg = 8 - (int)cls, lanes = 1 << lg, b = lane & (lanes - 1);
-        cf w[16];
-#pragma unroll
-        for (int i = 0; i < 8; i++) {
-            const float4 t = ld4(&t256[(b << (4 - lg)) * 18 + 2 * i]);
-            w[2 * i] = mk(t.x, t.y); w[2 * i + 1] = mk(t.z, t.w);
-        }
-        float2 *row = tiles + r0.xch;
-        if (a0.on) {
-#pragma unroll
-            for (int p = 0; p < 16; p++) st2(&row[(p << lg) + (b ^ (p & (lanes - 1)))], cmulc(v[rev16(p)], w[p]));
-        }
-        wave_sync();
-        if (cls == 5) {
-            // p = b and p = b + 8: two DFT-8 (dft8 leaves X[k0 + 2 k1] in [4 k0 + k1])
-#pragma unroll
-            for (int bb = 0; bb < 8; bb++) {
-                v[bb] = ld2(&row[(b << 3) + (bb ^ b)]);
-                v[8 + bb] = ld2(&row[((b + 8) << 3) + (bb ^ b)]);
-            }
-            dft8<true>(reinterpret_cast<cf (&)[8]>(v[0]));
-            dft8<true>(reinterpret_cast<cf (&)[8]>(v[8]));
-            const int skip = 128 - r0.lout;
-            if (a0.on) {
-#pragma unroll
-                for (int q = 0; q < 8; q++) {
-                    const int t0 = b + 16 * q, t1 = t0 + 8;
-                    if (t0 >= skip) out_st(out + a0.dst + t0, v[4 * (q & 1) + (q >> 1)] * 128.f, oq_scale);
-                    if (t1 >= skip) out_st(out + a0.dst + t1, v[8 + 4 * (q & 1) + (q >> 1)] * 128.f, oq_scale);
-                }
-            }
-        } else if (cls == 7) {
-            // l = 32: p = b + 2 j, j < 8: eight DFT-2; y[t = p + 16 q], q < 2
-#pragma unroll
-            for (int j = 0; j < 8; j++) {
-                const cf e = ld2(&row[((b + 2 * j) << 1) + b]), o = ld2(&row[((b + 2 * j) << 1) + (1 ^ b)]);
-                v[2 * j] = e + o; v[2 * j + 1] = e - o;
-            }
-            const int skip = 32 - r0.lout;
-            if (a0.on) {
-#pragma unroll
-                for (int j = 0; j < 8; j++) {
-#pragma unroll
-                    for (int q = 0; q < 2; q++) if (b + 2 * j + 16 * q >= skip) out_st(out + a0.dst + b + 2 * j + 16 * q, v[2 * j + q] * 32.f, oq_scale);
-                }
-            }
-        } else if (cls == 8) {
-            // l = 16: the DFT-16 over a is the whole transform (the trip through the row's exchange area only puts y[p] into register p)
-#pragma unroll
-            for (int p = 0; p < 16; p++) v[p] = ld2(&row[p]);
-            const int skip = 16 - r0.lout;
-            if (a0.on) {
-#pragma unroll
-                for (int p = 0; p < 16; p++) if (p >= skip) out_st(out + a0.dst + p, v[p] * 16.f, oq_scale);
-            }
-        } else {
-            // p = b + 4 j, j < 4: four DFT-4
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-#pragma unroll
-                for (int bb = 0; bb < 4; bb++) v[4 * j + bb] = ld2(&row[((b + 4 * j) << 2) + (bb ^ b)]);
-                dft4<true>(v[4 * j], v[4 * j + 1], v[4 * j + 2], v[4 * j + 3]);
-            }
-            const int skip = 64 - r0.lout;
-            if (a0.on) {
-#pragma unroll
-                for (int j = 0; j < 4; j++) {
-#pragma unroll
-                    for (int q = 0; q < 4; q++) if (b + 4 * j + 16 * q >= skip) out_st(out + a0.dst + b + 4 * j + 16 * q, v[4 * j + q] * 64.f, oq_scale);
-                }
-            }
-        }
-    }
+    constexpr bool FINE = false;
+    [[maybe_unused]] const F4Fine fa{};
+#include "fdc_fused4096_body.inc"
+}
+
+// FINE: fine tuning (fdc_fine.hpp) in the stores: every sample turned by base * step before it is stored (and before oq_bits for integer TO).  The same
+// arguments and the fine-tuning tables behind them; no waterfall form
+template <bool WIDE, int TEAMS, class TI = float2, class TO = float2>
+__global__ __launch_bounds__(256 * TEAMS, 4 /* waves per SIMD */) void k_f4096_fine(const TI *__restrict__ in, size_t in_stride, TO *__restrict__ out, int nb, int R,
+                                                  int mbase, int nb_call, int fbm, const float2 *__restrict__ tw, int twstride, const float2 *__restrict__ wins,
+                                                  const F4Row *__restrict__ rows, unsigned wcls, typename IqTail<TI, TO>::type wf, const F4Fine fa)
+{
+    constexpr bool FINE = true, ROWS = false;
+#include "fdc_fused4096_body.inc"
 }
 
 template <bool ROWS, class TI = float2, class TO = float2>
@@ -434,9 +154,33 @@ static hipError_t init_fused4096_oq()
     return e != hipSuccess ? e : init_fused4096_forms<false, sc8, TO>();
 }
 
+template <class TI, class TO>
+static hipError_t init_fused4096_fine_forms()
+{
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_f4096_fine<false, 2, TI, TO>), hipFuncAttributeMaxDynamicSharedMemorySize, f4_lds(2));
+    if (e != hipSuccess) return e;
+    e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_f4096_fine<false, 1, TI, TO>), hipFuncAttributeMaxDynamicSharedMemorySize, f4_lds(1));
+    if (e != hipSuccess) return e;
+    e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_f4096_fine<true, 1, TI, TO>), hipFuncAttributeMaxDynamicSharedMemorySize, f4_lds_wide(1));
+    if (e != hipSuccess) return e;
+    return hipFuncSetAttribute(reinterpret_cast<const void *>(k_f4096_fine<true, 2, TI, TO>), hipFuncAttributeMaxDynamicSharedMemorySize, f4_lds_wide(2));
+}
+
+template <class TO>
+static hipError_t init_fused4096_fine_out()
+{
+    hipError_t e = init_fused4096_fine_forms<float2, TO>();
+    if (e == hipSuccess) e = init_fused4096_fine_forms<sc16, TO>();
+    return e != hipSuccess ? e : init_fused4096_fine_forms<sc8, TO>();
+}
+
 hipError_t init_fused4096_kernels()
 {
-    hipError_t e = init_fused4096_forms<false>();
+    hipError_t e = init_fused4096_fine_out<float2>();                 // fine tuning in the stores: every input and output form
+    if (e == hipSuccess) e = init_fused4096_fine_out<sc16>();
+    if (e == hipSuccess) e = init_fused4096_fine_out<sc8>();
+    if (e != hipSuccess) return e;
+    e = init_fused4096_forms<false>();
     if (e == hipSuccess) e = init_fused4096_forms<true>();
     if (e == hipSuccess) e = init_fused4096_forms<false, sc16>();     // integer input: the channel outputs only (no ROWS form)
     if (e == hipSuccess) e = init_fused4096_forms<false, sc8>();
@@ -536,6 +280,49 @@ hipError_t launch_fused4096_oq(int ifmt, float iscale, const void *in, size_t in
     if (ofmt == kIqSc8)
         return fused4096_oq_in(ifmt, iscale, in, in_stride, static_cast<sc8 *>(out), nb_chunk, R, mbase, nb_call, sh, tw, ntab, wins, rows, wcls, teams, s, oscale);
     return hipErrorInvalidValue;
+}
+
+// ---- fine tuning in the kernel's stores (fdc_fine.hpp): every input form (ifmt) and output form (ofmt; kIqFloat: out holds float2) -----------------------
+template <class TI, class TO>
+static void launch_fused4096_fine_form(const F4Shape &sh, int teams, hipStream_t s, const void *in, size_t in_stride, void *out, int nb_chunk, int R, int mbase,
+                                       int nb_call, const float2 *tw, int ntab, const float2 *wins, const F4Row *rows, unsigned wcls,
+                                       typename IqTail<TI, TO>::type wf, const F4Fine &fa)
+{
+    const TI *i = static_cast<const TI *>(in);
+    TO *o = static_cast<TO *>(out);
+    if (sh.wide && teams == 1)
+        hipLaunchKernelGGL((k_f4096_fine<true, 1, TI, TO>), sh.grid, dim3(256), f4_lds_wide(1), s, i, in_stride, o, nb_chunk, R, mbase, nb_call, sh.fbm, tw, ntab / 4096, wins, rows, wcls, wf, fa);
+    else if (sh.wide)
+        hipLaunchKernelGGL((k_f4096_fine<true, 2, TI, TO>), sh.grid, dim3(512), f4_lds_wide(2), s, i, in_stride, o, nb_chunk, R, mbase, nb_call, sh.fbm, tw, ntab / 4096, wins, rows, wcls, wf, fa);
+    else if (teams == 2)
+        hipLaunchKernelGGL((k_f4096_fine<false, 2, TI, TO>), sh.grid, dim3(512), f4_lds(2), s, i, in_stride, o, nb_chunk, R, mbase, nb_call, sh.fbm, tw, ntab / 4096, wins, rows, wcls, wf, fa);
+    else
+        hipLaunchKernelGGL((k_f4096_fine<false, 1, TI, TO>), sh.grid, dim3(256), f4_lds(1), s, i, in_stride, o, nb_chunk, R, mbase, nb_call, sh.fbm, tw, ntab / 4096, wins, rows, wcls, wf, fa);
+}
+
+hipError_t launch_fused4096_fine(int ifmt, float iscale, const void *in, size_t in_stride, int ofmt, float oscale, void *out, int nb_chunk, int R, int mbase,
+                                 int nb_call, int64_t first_block, const float2 *tw, int ntab, const float2 *wins, const F4Row *rows, unsigned wcls, int teams,
+                                 const FineChan *fine_rows, const float2 *fine_step, hipStream_t s)
+{
+    if (nb_chunk <= 0) return hipSuccess;
+    F4Shape sh;
+    const hipError_t e = f4_shape(nb_chunk, R, mbase, first_block, wcls, teams, &sh);
+    if (e != hipSuccess) return e;
+    const F4Fine fa{fine_rows, fine_step, (unsigned long long)(first_block + mbase)};
+    const float2 both = make_float2(iscale, oscale);
+#define FDC_F4FINE(TI, TO, tail) launch_fused4096_fine_form<TI, TO>(sh, teams, s, in, in_stride, out, nb_chunk, R, mbase, nb_call, tw, ntab, wins, rows, wcls, tail, fa)
+    if (ifmt == kIqFloat && ofmt == kIqFloat) FDC_F4FINE(float2, float2, nullptr);
+    else if (ifmt == kIqSc16 && ofmt == kIqFloat) FDC_F4FINE(sc16, float2, iscale);
+    else if (ifmt == kIqSc8 && ofmt == kIqFloat) FDC_F4FINE(sc8, float2, iscale);
+    else if (ifmt == kIqFloat && ofmt == kIqSc16) FDC_F4FINE(float2, sc16, oscale);
+    else if (ifmt == kIqFloat && ofmt == kIqSc8) FDC_F4FINE(float2, sc8, oscale);
+    else if (ifmt == kIqSc16 && ofmt == kIqSc16) FDC_F4FINE(sc16, sc16, both);
+    else if (ifmt == kIqSc16 && ofmt == kIqSc8) FDC_F4FINE(sc16, sc8, both);
+    else if (ifmt == kIqSc8 && ofmt == kIqSc16) FDC_F4FINE(sc8, sc16, both);
+    else if (ifmt == kIqSc8 && ofmt == kIqSc8) FDC_F4FINE(sc8, sc8, both);
+    else return hipErrorInvalidValue;
+#undef FDC_F4FINE
+    return hipGetLastError();
 }
 
 }  // namespace fdc

@@ -351,6 +351,19 @@ void fdc_pipeline_group_reset(fdc_pipeline_group *g)
     g->dead = false;
 }
 
+int fdc_pipeline_group_set_fine_tuning(fdc_pipeline_group *g, const double *nu, int n)
+{
+    FDC_ENTRY("fdc_pipeline_group_set_fine_tuning")
+    if (!g) return fdc::set_error(FDC_ERR_INVALID_ARGUMENT, "null group handle");
+    // every member takes the same arguments: the first refuses what all would refuse, before any has changed
+    for (fdc_pipeline *p : g->mem) {
+        const int rc = fdc_pipeline_set_fine_tuning(p, nu, n);
+        if (rc != FDC_OK) return rc;
+    }
+    return FDC_OK;
+    FDC_ENTRY_END
+}
+
 int fdc_pipeline_group_set_output_format(fdc_pipeline_group *g, int32_t format, float scale)
 {
     FDC_ENTRY("fdc_pipeline_group_set_output_format")

@@ -103,6 +103,13 @@ hipError_t launch_fused4096_oq(int ifmt, float iscale, const void *in, size_t in
                                int nb_call, int64_t first_block, const float2 *tw, int ntab, const float2 *wins, const F4Row *rows, unsigned wcls, int teams,
                                hipStream_t s);
 
+// fine tuning in the kernel's stores (fdc_fine.hpp): any input form (ifmt: kIqFloat = float2 in) and output form (ofmt: kIqFloat = float2 out), no waterfall rows;
+// fine_rows[8 waves][8 slots]: the increment and step-table start of each schedule row's channel, fine_step: the step table
+struct FineChan;
+hipError_t launch_fused4096_fine(int ifmt, float iscale, const void *in, size_t in_stride, int ofmt, float oscale, void *out, int nb_chunk, int R, int mbase,
+                                 int nb_call, int64_t first_block, const float2 *tw, int ntab, const float2 *wins, const F4Row *rows, unsigned wcls, int teams,
+                                 const FineChan *fine_rows, const float2 *fine_step, hipStream_t s);
+
 // uniform plan (all channels l = 256, f = 256*slot, N = 256*N1): stage 1 + stage 2, no spectrum in memory.
 //   twq[n1][q] = W_N^(16*n1*q), cbt[n1][b] = (-1)^n1 W_N^(n1*b)  (16 entries per n1 each), shn[k2] = shape[k2]/N;
 //   slot_off[c] = per-block sample offset of the channel sitting in slot c, or -1;  g: nb_chunk*lout*N1 scratch
@@ -220,6 +227,11 @@ hipError_t launch_real_to_complex(const float *in, float2 *out, size_t n, hipStr
 hipError_t launch_iq_to_complex(int fmt, float scale, const void *in, float2 *out, size_t n, hipStream_t s);
 // complex float -> complex integer samples (fmt: kIqSc16 / kIqSc8), each component saturate(round_half_even(x * scale)) (fdc_iq.hpp oq_bits)
 hipError_t launch_complex_to_iq(int fmt, float scale, const float2 *in, void *out, size_t n, hipStream_t s);
+
+// Fine tuning (fdc_fine.hpp): blocks [mbase, mbase + nb_chunk) of a call's channel-major float outputs turned in place, channel c by
+// exp(-2 pi i frac(fine[c].inc t / 2^64)) at its stream sample t = (first_block + m) lout_c + j; step: the channels' step factors at fine[c].step_off
+hipError_t launch_fine_rotate(float2 *out, const ChanDev *chans, const FineChan *fine, const float2 *step, int nchan, int nb_chunk, int mbase, int nb_call,
+                              int64_t first_block, hipStream_t s);
 
 hipError_t launch_scale(const float2 *in, float2 *out, size_t n, float k, hipStream_t s);
 

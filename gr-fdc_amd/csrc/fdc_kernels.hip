@@ -15,10 +15,13 @@
 //   fft_vcc(l, inv, shift)  python/FrequencyDomainChannelizer.py:228 (ifftshift fused into the LDS index)
 //   cut + *l                python/FrequencyDomainChannelizer.py:229-231
 #include "fdc_kernels.h"
+#include <algorithm>
 #include <cstdlib>
 #include <type_traits>
 #include "fdc_radix16.hpp"
 #include "fdc_iq.hpp"
+#include "fdc_fine.hpp"
+#include "fdc_devutil.hpp"
 
 namespace fdc {
 
@@ -1012,6 +1015,51 @@ hipError_t launch_complex_to_iq(int fmt, float scale, const float2 *in, void *ou
     if (fmt == kIqSc16) hipLaunchKernelGGL(k_complex_to_iq<sc16>, dim3((unsigned)g), dim3(256), 0, s, in, static_cast<sc16 *>(out), n, scale);
     else if (fmt == kIqSc8) hipLaunchKernelGGL(k_complex_to_iq<sc8>, dim3((unsigned)g), dim3(256), 0, s, in, static_cast<sc8 *>(out), n, scale);
     else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+// Fine tuning behind the channel kernels of a launch group (fdc_fine.hpp): blocks [mbase, mbase + nb) of the call's channel-major float outputs, in place.
+// A channel's rows of the group are one contiguous run; a row — one (block, channel): lout samples, one base — goes to a power-of-two set of lanes of
+// a wave, 16 bytes per lane and access where the row allows it (lout even, the run 16-byte aligned; the step table's rows start at even offsets).
+__global__ __launch_bounds__(256) void k_fine_rotate(float2 *out, const ChanDev *__restrict__ chans, const FineChan *__restrict__ fine,
+                                                     const float2 *__restrict__ step, int c0, int nb, int mbase, long long nb_call,
+                                                     unsigned long long first_block)
+{
+    const int c = c0 + (int)blockIdx.y;
+    const unsigned lout = (unsigned)chans[c].lout;
+    const FineChan fc = fine[c];
+    float2 *o = out + nb_call * chans[c].out_off + (long long)mbase * lout;
+    const float2 *st = step + fc.step_off;
+    const bool wide = !(lout & 1) && (reinterpret_cast<uintptr_t>(o) & 15) == 0;
+    const unsigned per = wide ? lout >> 1 : lout;                              // accesses per row
+    unsigned lg = per <= 1 ? 0 : 32 - (unsigned)__clz((int)(per - 1));
+    if (lg > 6) lg = 6;
+    const unsigned lanes = 1u << lg, lane = threadIdx.x & 63, sub = lane & (lanes - 1), rows = 64u >> lg;
+    const unsigned wave = blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = gridDim.x * 4;
+    for (unsigned m = wave * rows + (lane >> lg); m < (unsigned)nb; m += nwaves * rows) {
+        const cf base = fine_base(fc.inc, first_block + (unsigned long long)(mbase + (int)m), lout);
+        float2 *row = o + (size_t)m * lout;
+        if (wide) {
+            for (unsigned i = sub; i < per; i += lanes) {
+                const float4 y = ld4(row + 2 * i), s = ld4(st + 2 * i);
+                st4(row + 2 * i, fine_rotate(mk(y.x, y.y), base, mk(s.x, s.y)), fine_rotate(mk(y.z, y.w), base, mk(s.z, s.w)));
+            }
+        } else {
+            for (unsigned i = sub; i < per; i += lanes) st2(row + i, fine_rotate(ld2(row + i), base, ld2(st + i)));
+        }
+    }
+}
+
+hipError_t launch_fine_rotate(float2 *out, const ChanDev *chans, const FineChan *fine, const float2 *step, int nchan, int nb_chunk, int mbase, int nb_call,
+                              int64_t first_block, hipStream_t s)
+{
+    if (nchan <= 0 || nb_chunk <= 0) return hipSuccess;
+    for (int c0 = 0; c0 < nchan; c0 += 32768) {
+        const int nc = nchan - c0 < 32768 ? nchan - c0 : 32768;
+        const int gx = std::max(1, std::min((nb_chunk + 3) / 4, (2048 + nc - 1) / nc));      // grid-stride over the rows: about eight workgroups per unit
+        hipLaunchKernelGGL(k_fine_rotate, dim3((unsigned)gx, (unsigned)nc), dim3(256), 0, s, out, chans, fine, step, c0, nb_chunk, mbase, (long long)nb_call,
+                           (unsigned long long)first_block);
+    }
     return hipGetLastError();
 }
 

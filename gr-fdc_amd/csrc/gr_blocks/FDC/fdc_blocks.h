@@ -127,6 +127,10 @@ public:
     virtual int output_item_len(int port) const = 0;
     // which kernels the plan was given, in words (fdc_pipeline_describe; the first member of a group)
     virtual std::string kernel_plan() const = 0;
+    // fine tuning (fdc_pipeline_set_fine_tuning, include/fdc_amd.h): nu[c] in cycles per output sample of port c, |nu| < 0.5, one per channel; an empty
+    // vector switches it off.  A setting: it applies from the next work() call and is kept over set_devices() / set_max_items().  Throws
+    // std::invalid_argument for a wrong count, NaN, |nu| >= 0.5, and on a block with sink blocks attached (their entry writes the channels as cut).
+    virtual void set_fine_tuning(const std::vector<double> &nu) = 0;
 
     // The hier block's sink blocks on THIS block's spectrum (python/FrequencyDomainChannelizer.py:237-278 connects one
     // PowerActivationChannel per activity-controlled channel and one SegmentDetection per segment to the normalised spectrum;

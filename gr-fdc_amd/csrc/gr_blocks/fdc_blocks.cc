@@ -222,6 +222,7 @@ class fdc_pipeline_vcc_impl : public fdc_pipeline_vcc, device_state {
     std::vector<fdc_channel> d_ch;
     size_t d_in_item = 0;
     std::vector<int> d_lout;
+    std::vector<double> d_fine;                // fine tuning: one frequency per channel, or empty = off (kept over rebuild())
     std::vector<void *> d_pinned;
     // attach_sinks(): the hier block's sink blocks on this block's device-resident spectrum
     bool d_has_sinks = false;
@@ -259,6 +260,7 @@ class fdc_pipeline_vcc_impl : public fdc_pipeline_vcc, device_state {
         for (size_t i = 0; i < d_ch.size(); i++) d_lout.push_back(fdc_pipeline_channel_lout(p0, (int)i));
         // the scheduler offers whole device batches and sizes this block's and its upstream buffers for two of them
         apply_scheduler_hints(this, sched_batch(), d_max_items, (int)d_ch.size());
+        apply_fine_tuning();
         if (d_has_sinks) {
             fdc_sinks_cfg c{};
             c.device_id = d_devices[0]; c.blocklen = d_blocklen; c.relinvovl = d_relinvovl;
@@ -273,6 +275,15 @@ class fdc_pipeline_vcc_impl : public fdc_pipeline_vcc, device_state {
             c.flags = d_ss.pipelined ? FDC_SINKS_LOOKAHEAD : 0;
             check_create(fdc_sinks_create(&c, &d_s));
         }
+    }
+    void apply_fine_tuning()
+    {
+        if (d_fine.empty() && !d_p && !d_g) return;
+        if (!d_fine.empty() && d_has_sinks) throw std::invalid_argument("fdc_pipeline_vcc: fine tuning cannot go with sink blocks");
+        const double *nu = d_fine.empty() ? nullptr : d_fine.data();
+        const int n = d_fine.empty() ? (int)d_ch.size() : (int)d_fine.size();
+        const int rc = d_g ? fdc_pipeline_group_set_fine_tuning(d_g, nu, n) : fdc_pipeline_set_fine_tuning(d_p, nu, n);
+        if (rc != FDC_OK) throw std::invalid_argument(std::string("fdc_pipeline_vcc: ") + fdc_last_error());
     }
     void drop_sinks()
     {
@@ -311,6 +322,13 @@ public:
             message_port_register_out("msgout");
 #endif
         }
+    }
+    void set_fine_tuning(const std::vector<double> &nu) override
+    {
+        const std::vector<double> before = d_fine;
+        d_fine = nu;
+        try { apply_fine_tuning(); }
+        catch (...) { d_fine = before; throw; }
     }
     int sinks_latency() const override { return d_s && d_p ? fdc_pipeline_sinks_latency(d_p, d_s) : 0; }
     int flush_sinks() override

@@ -187,6 +187,29 @@ enum { FDC_OQ_FC32 = 0,   /* complex float32 (the default) */
        FDC_OQ_SC8  = 2 }; /* = FDC_IQ_SC8 */
 int fdc_pipeline_set_output_format(fdc_pipeline *p, int32_t format, float scale);
 
+/* FINE TUNING: centre each channel on its requested frequency.  A channel's slice is cut at whole bins, so its stream carries the signal at a residual
+ * offset of up to half a bin of N (more for slices wrapped or clamped at a band edge).  With a fine-tuning frequency nu_c for channel c, in cycles per
+ * OUTPUT sample of that channel, |nu_c| < 0.5, sample t of the channel's stream becomes
+ *     y'_c[t] = y_c[t] * exp(-2 pi i phi_c(t)),   phi_c(t) = ((inc_c * t) mod 2^64) / 2^64,   inc_c = round_half_even(nu_c * 2^64) mod 2^64
+ * where y_c[t] is exactly what the entry writes without it and t = (global block index) * lout_c + j is the stream's own sample index (the block index:
+ * the handle's block counter, or first_block of the span and device entries).  The phase is an INTEGER function of t (a 64-bit wrapping product): no
+ * drift, no accumulated rounding, no dependence on how the stream is cut into calls, launch groups or spans.
+ *   fdc_fine_tuning_increment   inc for one nu (host only, no device); NaN and |nu| >= 0.5: FDC_ERR_INVALID_ARGUMENT
+ *   fdc_pipeline_set_fine_tuning   nu[n], n = the channel count (else FDC_ERR_INVALID_ARGUMENT; so is any nu the function above refuses: nothing changes);
+ *                               nu = NULL or all zeros switches it off
+ * A SETTING like fdc_pipeline_set_output_format: it may change between any two calls and applies from the next one; it does not touch the history, the
+ * block counter or the input-form latch, and survives fdc_pipeline_reset; refused while a pipelined sinks batch is inside the handle.  Every table it
+ * needs is allocated (once) and written here, nothing in a work call; the call waits for the handle's own stream first (device entries on another
+ * stream: the caller orders them).  While it is on, the channel outputs of fdc_pipeline_work, _work_span, _work_real, _work_span_real, _work_iq,
+ * _work_span_iq, _process_device, _process_device_iq and the group's work entries are y'; with integer output the turn comes BEFORE the narrowing:
+ * oq(y' * scale).  The debug spectrum is unchanged.  fdc_pipeline_work_sinks, _work_spectrum, _process_device_power and fdc_pipeline_work_waterfall return
+ * FDC_ERR_INVALID_ARGUMENT and change nothing while it is on.  Per sample the device multiplies y * base * step in float32, in this order and without
+ * FMA contraction: base = the phasor of phi_c(block * lout_c), computed once per (block, channel), step = a per-channel table of lout_c phasors designed
+ * in double; |y' - y w| <= 11 * 2^-24 |y| against the exact phasor w.  Path 5 turns the samples in its kernel's own stores
+ * (fdc_pipeline_describe: "fine tuning: fused"), every other plan in one pass over the launch group's results ("fine tuning: rotated"). */
+int fdc_fine_tuning_increment(double nu, uint64_t *inc);
+int fdc_pipeline_set_fine_tuning(fdc_pipeline *p, const double *nu, int n);
+
 /* Optional: pin a host range that will be handed to fdc_pipeline_work() again and again (GNU Radio's circular buffers
  * live as long as the flowgraph: register them in start(), unregister in stop()).  A call whose `in` lies in a
  * registered range is DMA'd from it in place, and when every outs[c] does, the results are stored straight into
@@ -298,6 +321,9 @@ void fdc_pipeline_group_reset(fdc_pipeline_group *g);           /* history <- ze
 /* complex integer output for every member (fdc_pipeline_set_output_format: the same arguments, refusals and setting semantics).  A group call takes
  * the members' own setting and refuses (FDC_ERR_INVALID_ARGUMENT) when members set one by one through fdc_pipeline_group_member disagree. */
 int fdc_pipeline_group_set_output_format(fdc_pipeline_group *g, int32_t format, float scale);
+/* fine tuning for every member (fdc_pipeline_set_fine_tuning: the same arguments, refusals and setting semantics); the spans carry their global block
+ * index, so a group's output is one handle's */
+int fdc_pipeline_group_set_fine_tuning(fdc_pipeline_group *g, const double *nu, int n);
 int32_t fdc_pipeline_group_size(const fdc_pipeline_group *g);
 fdc_pipeline *fdc_pipeline_group_member(fdc_pipeline_group *g, int i);   /* owned by the group (fdc_pipeline_path, sizes, timing) */
 int32_t fdc_pipeline_group_device(const fdc_pipeline_group *g, int i);
