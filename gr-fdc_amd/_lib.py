@@ -58,6 +58,7 @@ class fdc_sinks_cfg(C.Structure):
 FDC_SINKS_HOST_DECISIONS = 1
 FDC_SINKS_DEVICE_PAYLOAD = 2
 FDC_SINKS_LOOKAHEAD = 4
+FDC_OQ_FC32, FDC_OQ_SC16, FDC_OQ_SC8 = 0, 1, 2
 
 
 class fdc_pdu(C.Structure):
@@ -158,6 +159,10 @@ SYMBOLS = {
     "fdc_sinks_submit_device": (C.c_int, [_vp, C.c_int]),
     "fdc_sinks_flush": (C.c_int, [_vp]),
     "fdc_sinks_engine": (C.c_int32, [_vp]),
+    "fdc_sinks_set_payload_format": (C.c_int, [_vp, C.c_int32, C.c_float]),
+    "fdc_sinks_payload_format": (C.c_int, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_float)]),
+    "fdc_sinks_payload_route": (C.c_int32, [_vp]),
+    "fdc_sinks_group_set_payload_format": (C.c_int, [_vp, C.c_int32, C.c_float]),
     "fdc_set_log_callback": (None, [_vp, _vp]),
     "fdc_sinks_pdu_count": (C.c_int, [_vp]),
     "fdc_sinks_pdu": (C.c_int, [_vp, C.c_int, C.POINTER(fdc_pdu)]),

@@ -616,12 +616,16 @@ class FrequencyDomainChannelizer:
                  pow_act_deactivation_delay,
                  pow_act_maxblocks, act_det_maxblocks,
                  debug, device_id=0, max_blocks=64, devices=None, pipelined=False, waterfall=None, iq_input=None, iq_scale=1.0,
-                 iq_output=None, iq_output_scale=1.0, fine_tuning=False):
+                 iq_output=None, iq_output_scale=1.0, fine_tuning=False, *, payload_format=None, payload_scale=1.0):
         # pipelined (not an argument of the reference): the sink blocks run beside the front end of the FOLLOWING work() calls, as the
         # thread-per-block scheduler runs them beside the FFT in the reference (fdc_pipeline_work_sinks on a look-ahead bank,
         # include/fdc_amd.h): same PDUs, handed out one or two work() calls later; flush() at the end of the stream
         self.pipelined = bool(pipelined)
         self.verbose = int(verbose)
+        # payload_format / payload_scale (not arguments of the reference): the PDU payloads of the sink blocks as "sc16" / "sc8", narrowed on the
+        # device (fdc_sinks_set_payload_format); messages then carry int16[n, 2] / int8[n, 2] arrays and the files the narrow bytes
+        from .sinks import _check_face_payload
+        self._payload_code = _check_face_payload(payload_format, self.verbose)
         self.itemsize = inptype
         self.debug = bool(debug)
         if self.itemsize not in (8, 4):
@@ -741,6 +745,8 @@ class FrequencyDomainChannelizer:
                                det_delay=add, puffer=puf, max_blocks=max_blocks, device_id=device_id,
                                det_variant=1,      # the hier block instantiates SegmentDetection (:25, :261-278)
                                verbose=self.verbose, lookahead=self.pipelined and self.inpveclen == 1)
+            if self._payload_code != 0:                         # before the first call, serial and pipelined form alike
+                self.sinks.set_payload_format(payload_format, payload_scale)
         # devices = [ordinals]: the throughput chain of one work() call spread over several GPUs (fdc_pipeline_group); the sink
         # blocks stay on ONE device's spectrum, so a hier block with sinks keeps the single-device handle
         if devices is not None and len(devices) > 1 and self.sinks is None and self.inpveclen == 1:

@@ -13,7 +13,9 @@
 #include "fdc_kernels.h"
 #include "fdc_radix16.hpp"
 #include "fdc_devutil.hpp"
+#include "fdc_iq.hpp"
 #include <cstdlib>
+#include <type_traits>
 
 namespace fdc {
 
@@ -200,10 +202,15 @@ __global__ __launch_bounds__(256, 4) void k_c256(const float2 *__restrict__ spec
 // carriers of that class): slice of spectrum slot `slot` from bin `start`, the task's phase-resolved window, halves swapped,
 // IFFT-256, the first 256/R samples dropped, results at the task's landing offset.  Replaces the generic LDS kernel k_extract<1>
 // for this width (1.9 -> ~4 TB/s).
-__global__ __launch_bounds__(256, 4) void k_x256(const float2 *__restrict__ spec, float2 *__restrict__ out,
-                                                 const ExtractTask *__restrict__ tasks, int ntasks, int N, int skip,
-                                                 const float2 *__restrict__ wins,
-                                                 const float2 *__restrict__ tw256)
+// TO: the sample type of the EMITTED runs (fdc_sinks_set_payload_format).  float2: everything goes to `out`, the kernel the bank always had.  sc16 / sc8:
+// a row whose landing offset lies in the emitted part of the layout, [0, used_a), is narrowed (fdc_iq.hpp oq_bits) into `nout` at the same sample
+// offset — a dword per sample for sc16, 16 bits for sc8 — and a row in the buffered part stays float2 in `out`.  A row is one block of one PDU: the
+// predicate is uniform over its 16 lanes.
+template <class TO>
+__device__ __forceinline__ void x256_rows(const float2 *__restrict__ spec, float2 *__restrict__ out,
+                                          const ExtractTask *__restrict__ tasks, int ntasks, int N, int skip,
+                                          const float2 *__restrict__ wins,
+                                          const float2 *__restrict__ tw256, TO *__restrict__ nout, long long used_a, float scale)
 {
     __shared__ RowInfo rows[16];
     float2 *tile = reinterpret_cast<float2 *>(fdc_smem_fast);
@@ -254,12 +261,43 @@ __global__ __launch_bounds__(256, 4) void k_x256(const float2 *__restrict__ spec
     dft16<true>(v);
     if (ri.valid) {
         // y[t], t = p + 16q; keep t >= w/R; no scaling (PowerActivationChannel_impl.cc:277-281, …vcm_impl.cc:390-394)
+        if constexpr (!std::is_same<TO, float2>::value) {
+            if (ri.dst + skip < used_a) {
+#pragma unroll
+                for (int q = 0; q < 16; q++) {
+                    const int tt = b + 16 * q;
+                    if (tt >= skip) {
+                        const unsigned u = oq_bits(TO{}, v[rev16(q)], scale);
+                        if constexpr (sizeof(TO) == 4) *reinterpret_cast<unsigned *>(nout + ri.dst + tt) = u;
+                        else *reinterpret_cast<unsigned short *>(nout + ri.dst + tt) = (unsigned short)u;
+                    }
+                }
+                return;
+            }
+        }
 #pragma unroll
         for (int q = 0; q < 16; q++) {
             const int tt = b + 16 * q;
             if (tt >= skip) st2(out + ri.dst + tt, v[rev16(q)]);
         }
     }
+}
+
+__global__ __launch_bounds__(256, 4) void k_x256(const float2 *__restrict__ spec, float2 *__restrict__ out,
+                                                 const ExtractTask *__restrict__ tasks, int ntasks, int N, int skip,
+                                                 const float2 *__restrict__ wins,
+                                                 const float2 *__restrict__ tw256)
+{
+    x256_rows<float2>(spec, out, tasks, ntasks, N, skip, wins, tw256, nullptr, 0, 1.0f);
+}
+
+template <class TO>
+__global__ __launch_bounds__(256, 4) void k_x256n(const float2 *__restrict__ spec, float2 *__restrict__ out,
+                                                  const ExtractTask *__restrict__ tasks, int ntasks, int N, int skip,
+                                                  const float2 *__restrict__ wins,
+                                                  const float2 *__restrict__ tw256, TO *__restrict__ nout, long long used_a, float scale)
+{
+    x256_rows<TO>(spec, out, tasks, ntasks, N, skip, wins, tw256, nout, used_a, scale);
 }
 
 // ---- uniform-plan path ("polyphase commutation") ------------------------------------------------------------
@@ -686,7 +724,7 @@ hipError_t init_fast_kernels()
 #define FDC_SETC(k) \
     e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, c); \
     if (e != hipSuccess) return e;
-    FDC_SETC(k_c256) FDC_SETC(k_x256)
+    FDC_SETC(k_c256) FDC_SETC(k_x256) FDC_SETC(k_x256n<sc16>) FDC_SETC(k_x256n<sc8>)
 #undef FDC_SETC
     return hipSuccess;
 }
@@ -727,6 +765,19 @@ hipError_t launch_extract256(const float2 *spec, int N, const ExtractTask *tasks
 {
     if (ntasks <= 0) return hipSuccess;
     hipLaunchKernelGGL(k_x256, dim3((unsigned)((ntasks + 15) / 16)), dim3(256), kCTileBytes + 2304, s, spec, out, tasks, ntasks, N, skip, wins, tw256);
+    return hipGetLastError();
+}
+
+hipError_t launch_extract256_narrow(int fmt, float scale, const float2 *spec, int N, const ExtractTask *tasks, int ntasks, int skip, const float2 *wins,
+                                    float2 *out, void *nout, long long used_a, const float2 *tw256, hipStream_t s)
+{
+    if (ntasks <= 0) return hipSuccess;
+    const dim3 grid((unsigned)((ntasks + 15) / 16));
+    if (fmt == kIqSc16)
+        hipLaunchKernelGGL(k_x256n<sc16>, grid, dim3(256), kCTileBytes + 2304, s, spec, out, tasks, ntasks, N, skip, wins, tw256, static_cast<sc16 *>(nout), used_a, scale);
+    else if (fmt == kIqSc8)
+        hipLaunchKernelGGL(k_x256n<sc8>, grid, dim3(256), kCTileBytes + 2304, s, spec, out, tasks, ntasks, N, skip, wins, tw256, static_cast<sc8 *>(nout), used_a, scale);
+    else return hipErrorInvalidValue;
     return hipGetLastError();
 }
 

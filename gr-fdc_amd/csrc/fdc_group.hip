@@ -619,6 +619,29 @@ int fdc_sinks_group_pdus(const fdc_sinks_group *g, fdc_pdu *out, int cap)
     return n;
 }
 
+int fdc_sinks_group_set_payload_format(fdc_sinks_group *g, int32_t format, float scale)
+{
+    FDC_ENTRY("fdc_sinks_group_set_payload_format")
+    if (!g) return fdc::set_error(FDC_ERR_INVALID_ARGUMENT, "null group handle");
+    if (g->dead) return fdc::set_error(FDC_ERR_HIP, "the group failed in an earlier call and must be destroyed");
+    // all or none: the members that took the setting go back to what they had when a later one refuses
+    std::vector<std::pair<int32_t, float>> was(g->mem.size(), {FDC_OQ_FC32, 1.0f});
+    for (size_t i = 0; i < g->mem.size(); i++) {
+        fdc_sinks *sm = g->mem[i].s;
+        if (!sm) continue;
+        fdc_sinks_payload_format(sm, &was[i].first, &was[i].second);
+        const int rc = fdc_sinks_set_payload_format(sm, format, scale);
+        if (rc != FDC_OK) {
+            const std::string why = fdc_last_error();
+            for (size_t k = 0; k < i; k++) if (g->mem[k].s) (void)fdc_sinks_set_payload_format(g->mem[k].s, was[k].first, was[k].second);
+            return fdc::set_error(rc, "member %d (device %d): %s", (int)i, g->mem[i].dev, why.c_str());
+        }
+    }
+    g->pdus.clear();
+    return FDC_OK;
+    FDC_ENTRY_END
+}
+
 int32_t fdc_sinks_group_size(const fdc_sinks_group *g) { return g ? (int32_t)g->mem.size() : -1; }
 fdc_sinks *fdc_sinks_group_member(fdc_sinks_group *g, int i) { return g && i >= 0 && i < (int)g->mem.size() ? g->mem[(size_t)i].s : nullptr; }
 

@@ -257,6 +257,10 @@ hipError_t launch_extract(const float2 *spec, int N, const ExtractTask *tasks, i
 // width 256 on the register kernel of the l = 256 channels (fdc_fast256.hip); tw256: exp(-2 pi i j/256)
 hipError_t launch_extract256(const float2 *spec, int N, const ExtractTask *tasks, int ntasks, int skip, const float2 *wins, float2 *out,
                              const float2 *tw256, hipStream_t s);
+// ... with the emitted runs narrowed in its own stores (fdc_sinks_set_payload_format, fmt = kIqSc16 / kIqSc8): a task whose out_off lies below used_a
+// lands in nout (samples of the format, same sample offset), every other one in out as complex float
+hipError_t launch_extract256_narrow(int fmt, float scale, const float2 *spec, int N, const ExtractTask *tasks, int ntasks, int skip, const float2 *wins,
+                                    float2 *out, void *nout, long long used_a, const float2 *tw256, hipStream_t s);
 
 // single-block faces
 hipError_t launch_overlap_save(const unsigned char *ring, unsigned char *out, size_t in_item_bytes,

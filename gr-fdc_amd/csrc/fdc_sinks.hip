@@ -15,6 +15,7 @@
 #include "fdc_kernels.h"
 #include "fdc_sinks_dev.h"
 #include "fdc_guard.hpp"
+#include "fdc_iq.hpp"
 
 #include <algorithm>
 #include <cfloat>
@@ -236,6 +237,11 @@ struct fdc_sinks {
     WorkerPool pool;
     std::string det_logfile;                 // verbose == 2: …vcm_impl.cc:94 / SegmentDetection_impl.cc:51
     int host_threads = 0;                    // cfg.threads (host engine), 0 = from the bank's size
+    // fdc_sinks_set_payload_format: what fdc_pdu.samples holds (fdc::IqFormat = FDC_OQ_*), and the route the last finished batch took to it
+    int pay_fmt = fdc::kIqFloat;
+    float pay_scale = 1.0f;
+    int pay_route = 0;
+    bool pay_all256 = false;                 // the bank holds 256-bin PowerActivationChannels and nothing else: every extraction it can ever make is k_x256's
     // ---- device engine (fdc_sinks_dev.hip): decisions, layout and buffered blocks stay on the device
     struct Dev {
         bool on = false;
@@ -256,6 +262,11 @@ struct fdc_sinks {
         fdc::SinkPdu *h_pdus = nullptr;      // pinned: the first kEagerPdus records travel with the summary
         float2 *d_land[2] = {nullptr, nullptr}; size_t cap_land[2] = {0, 0};      // landing buffers (emitted runs, then buffered rests)
         cfl *h_land[2] = {nullptr, nullptr}; size_t cap_hland[2] = {0, 0};        // pinned copies of the emitted runs
+        // sc16 / sc8 payloads: the emitted runs [0, used_a) once more, narrow, at the same SAMPLE offsets (capacities in bytes); the buffered rests
+        // stay float in d_land
+        void *d_nland[2] = {nullptr, nullptr}; size_t cap_nland[2] = {0, 0};
+        void *h_nland[2] = {nullptr, nullptr}; size_t cap_hnland[2] = {0, 0};
+        int fmt_of[2] = {0, 0}, route_of[2] = {0, 0};                             // payload format and route (fdc_sinks_payload_route) of the batch in buffer b
         hipStream_t s_copy = nullptr;
         int carry_width = 0;                 // streams that can hold blocks from the call before: every PowerActivationChannel, or a
                                              // segment's live channels (disjoint detect ranges: at most one per power cell)
@@ -652,9 +663,9 @@ void fdc_sinks_destroy(fdc_sinks *s)
                         (void *)d.d_winoff, (void *)d.d_live, (void *)d.d_live2, (void *)d.d_detch, (void *)d.d_live_off, (void *)d.d_cand, (void *)d.d_pgeom,
                         (void *)d.d_pstate, (void *)d.d_dgeom, (void *)d.d_sst, (void *)d.d_tasks, (void *)d.d_pdus,
                         (void *)d.d_pdus_out, (void *)d.d_owners, (void *)d.d_sorted, (void *)d.d_sum, (void *)d.d_land[0],
-                        (void *)d.d_land[1]})
+                        (void *)d.d_land[1], d.d_nland[0], d.d_nland[1]})
             (void)hipFree(q);
-        for (void *q : {(void *)d.h_sum, (void *)d.h_pdus, (void *)d.h_land[0], (void *)d.h_land[1]}) if (q) (void)hipHostFree(q);
+        for (void *q : {(void *)d.h_sum, (void *)d.h_pdus, (void *)d.h_land[0], (void *)d.h_land[1], d.h_nland[0], d.h_nland[1]}) if (q) (void)hipHostFree(q);
     }
     if (s->stream) (void)hipStreamDestroy(s->stream);
     delete s;
@@ -863,6 +874,8 @@ int fdc_sinks_create(const fdc_sinks_cfg *cfg, fdc_sinks **out)
         }
     }
     raw->host_threads = cfg->threads > 0 ? std::min(cfg->threads, 32) : 0;
+    raw->pay_all256 = raw->segs.empty() && !raw->pacs.empty() &&
+                      std::all_of(raw->pacs.begin(), raw->pacs.end(), [](const Pac &p) { return p.extract_width == 256; });
     if (const char *t = fdc::debug_env("FDC_SINKS_THREADS")) if (atoi(t) >= 1) raw->host_threads = std::min(atoi(t), 32);   // debugging override
     {
         const int rcd = dev_setup(raw);
@@ -1040,8 +1053,9 @@ static int batch_end_swap(fdc_sinks *s, hipEvent_t done)
     return FDC_OK;
 }
 
+// narrow: the fused payload route (every task is of the 256-bin class): the emitted runs [0, used_a) go to it in the bank's payload format
 static int run_extractions(fdc_sinks *s, const fdc::ExtractTask *d_tasks, const size_t *first, const size_t *cnt, float2 *d_out, bool trace,
-                           hipStream_t q0 = nullptr)
+                           hipStream_t q0 = nullptr, void *narrow = nullptr, long long used_a = 0)
 {
     const int N = s->N;
     if (!q0) q0 = s->stream;
@@ -1090,7 +1104,10 @@ static int run_extractions(fdc_sinks *s, const fdc::ExtractTask *d_tasks, const 
         if (trace) std::fprintf(stderr, "[fdc_sinks]     width %d: %zu tasks\n", w, j - i);
         if (multi && w <= 4096 && !(w == 256 && s->d_tw256)) continue;
         if (side && w > 4096) continue;
-        if (w == 256 && s->d_tw256) {
+        if (w == 256 && s->d_tw256 && narrow) {
+            HIPCHK(fdc::launch_extract256_narrow(s->pay_fmt, s->pay_scale, s->d_spec, N, d_tasks + i, (int)(j - i), skip, s->d_wins, d_out, narrow, used_a,
+                                                 s->d_tw256, q0));
+        } else if (w == 256 && s->d_tw256) {
             HIPCHK(fdc::launch_extract256(s->d_spec, N, d_tasks + i, (int)(j - i), skip, s->d_wins, d_out, s->d_tw256, q0));
         } else if (w <= 4096) {
             HIPCHK(fdc::launch_extract(s->d_spec, N, d_tasks + i, (int)(j - i), w, skip, s->d_wins, d_out, s->d_tw, N, q0));
@@ -1459,7 +1476,31 @@ static int dev_launch_extractions(fdc_sinks *s, int nblocks)
         HIPCHK(hipMalloc(reinterpret_cast<void **>(&d.d_land[b]), sizeof(float2) * want));
         d.cap_land[b] = want;
     }
-    if (!devpay && (size_t)sum.used_a > d.cap_hland[b]) {
+    // Payload format (fdc_sinks_set_payload_format).  FUSED: every extraction of the batch is of the 256-bin class, whose kernel has narrow stores — it and
+    // the move of the buffered blocks write the emitted runs narrow themselves, and [0, used_a) of the float buffer is never written: nothing reads it (the
+    // payload comes from the narrow buffer, and what the NEXT batch moves on lies at prev_off = tail_off / live_off = an owner's b_off, k_sink_layout: always
+    // in [b_start, used_total)).  NARROWED: any other mix of classes runs as ever, and one pass narrows [0, used_a) behind the extractions.
+    const int fmt = s->pay_fmt;
+    const size_t sbytes = fdc::iq_bytes(fmt);
+    // A batch without extractions (only buffered blocks go out, or nothing does) takes the route of the bank's own kind: fused for a bank that is
+    // nothing but 256-bin PowerActivationChannels, narrowed for every other one.
+    bool fused = fmt != fdc::kIqFloat && s->d_tw256 != nullptr && (sum.class_cnt[8] > 0 || s->pay_all256);
+    for (int k = 0; k < 32 && fused; k++) if (k != 8 && sum.class_cnt[k]) fused = false;
+    d.fmt_of[b] = fmt; d.route_of[b] = fmt == fdc::kIqFloat ? 0 : fused ? 2 : 1;
+    if (fmt != fdc::kIqFloat && (size_t)sum.used_a * sbytes > d.cap_nland[b]) {
+        const size_t want = std::max<size_t>((size_t)sum.used_a * 3 / 2, (size_t)1 << 16) * sbytes;
+        (void)hipFree(d.d_nland[b]); d.d_nland[b] = nullptr; d.cap_nland[b] = 0;
+        HIPCHK(hipMalloc(&d.d_nland[b], want));
+        d.cap_nland[b] = want;
+    }
+    if (fmt != fdc::kIqFloat && !devpay && (size_t)sum.used_a * sbytes > d.cap_hnland[b]) {
+        const size_t want = std::max<size_t>((size_t)sum.used_a * 3 / 2, (size_t)1 << 16) * sbytes;
+        if (d.h_nland[b]) (void)hipHostFree(d.h_nland[b]);
+        d.h_nland[b] = nullptr; d.cap_hnland[b] = 0;
+        HIPCHK(hipHostMalloc(&d.h_nland[b], want, hipHostMallocDefault));
+        d.cap_hnland[b] = want;
+    }
+    if (fmt == fdc::kIqFloat && !devpay && (size_t)sum.used_a > d.cap_hland[b]) {
         const size_t want = std::max<size_t>((size_t)sum.used_a * 3 / 2, (size_t)1 << 16);
         if (d.h_land[b]) (void)hipHostFree(d.h_land[b]);
         d.h_land[b] = nullptr; d.cap_hland[b] = 0;
@@ -1474,9 +1515,14 @@ static int dev_launch_extractions(fdc_sinks *s, int nblocks)
         // grids from what the layout found, not from the worst case the lists were allocated for
         HIPCHK(fdc::launch_task_scatter(d.nlist, d.d_task_base, d.d_ntask, std::min<long long>(d.max_list, std::max(1, sum.max_list_tasks)), d.d_tasks,
                                         d.d_owners, d.d_sum, d.d_class_fill, d.d_sorted, s->stream));
-    if (d.any && sum.ncarry > 0)
-        HIPCHK(fdc::launch_carry_copy(d.d_owners, std::min(d.carry_width, std::max(1, sum.max_region_owners)), d.d_owner_base, d.d_nowner, npac, nseg,
-                                      d.d_sum, d.d_land[d.cur], d.d_land[b], s->stream));
+    if (d.any && sum.ncarry > 0) {
+        const int nown = std::min(d.carry_width, std::max(1, sum.max_region_owners));
+        if (fused)
+            HIPCHK(fdc::launch_carry_copy_narrow(fmt, s->pay_scale, d.d_owners, nown, d.d_owner_base, d.d_nowner, npac, nseg, d.d_land[d.cur], d.d_land[b],
+                                                 d.d_nland[b], s->stream));
+        else
+            HIPCHK(fdc::launch_carry_copy(d.d_owners, nown, d.d_owner_base, d.d_nowner, npac, nseg, d.d_sum, d.d_land[d.cur], d.d_land[b], s->stream));
+    }
     if (s->s_x) {
         HIPCHK(hipEventRecord(s->ev_tasks, s->stream));
         HIPCHK(hipStreamWaitEvent(qx, s->ev_tasks, 0));
@@ -1496,15 +1542,17 @@ static int dev_launch_extractions(fdc_sinks *s, int nblocks)
     if (sum.ntask) {
         size_t first[32], cnt[32];
         for (int k = 0; k < 32; k++) { first[k] = (size_t)sum.class_base[k]; cnt[k] = (size_t)sum.class_cnt[k]; }
-        const int rce = run_extractions(s, d.d_sorted, first, cnt, d.d_land[b], trace, qx);
+        const int rce = run_extractions(s, d.d_sorted, first, cnt, d.d_land[b], trace, qx, fused ? d.d_nland[b] : nullptr, (long long)sum.used_a);
         if (rce != FDC_OK) return rce;
     }
+    if (fmt != fdc::kIqFloat && !fused) HIPCHK(fdc::launch_complex_to_iq(fmt, s->pay_scale, d.d_land[b], d.d_nland[b], (size_t)sum.used_a, qx));
     { const int rh = batch_end_history(s, nblocks, qx); if (rh != FDC_OK) return rh; }
     HIPCHK(hipEventRecord(d.ev_extract[b], qx));
     { const int rh = batch_end_swap(s, d.ev_extract[b]); if (rh != FDC_OK) return rh; }
     if (!devpay && sum.used_a) {
         HIPCHK(hipStreamWaitEvent(d.s_copy, d.ev_extract[b], 0));
-        HIPCHK(hipMemcpyAsync(d.h_land[b], d.d_land[b], sizeof(float2) * (size_t)sum.used_a, hipMemcpyDeviceToHost, d.s_copy));
+        if (fmt != fdc::kIqFloat) HIPCHK(hipMemcpyAsync(d.h_nland[b], d.d_nland[b], sbytes * (size_t)sum.used_a, hipMemcpyDeviceToHost, d.s_copy));
+        else HIPCHK(hipMemcpyAsync(d.h_land[b], d.d_land[b], sizeof(float2) * (size_t)sum.used_a, hipMemcpyDeviceToHost, d.s_copy));
         HIPCHK(hipEventRecord(d.ev_copied[b], d.s_copy));
     }
     d.cur = b; d.any = true; d.inflight = true; d.pend[b] = true; d.nb_of[b] = nblocks; d.bc0[b] = bc0_this;
@@ -1525,6 +1573,7 @@ static int dev_wait(fdc_sinks *s, int b)
     else HIPCHK(hipEventSynchronize(d.ev_extract[b]));
     d.pend[b] = false;
     d.inflight = d.pend[0] || d.pend[1];
+    s->pay_route = d.route_of[b];
     return d.nb_of[b];
 }
 
@@ -1539,7 +1588,10 @@ static int dev_build(fdc_sinks *s, int b)
     order.resize(recs.size());
     for (size_t i = 0; i < recs.size(); i++) order[i] = {recs[i].key, (uint32_t)i};
     std::sort(order.begin(), order.end());
-    const char *base = devpay ? reinterpret_cast<const char *>(d.d_land[b]) : reinterpret_cast<const char *>(d.h_land[b]);
+    const bool narrow = d.fmt_of[b] != fdc::kIqFloat;       // the narrow landing buffers: same sample offsets, their own sample size
+    const size_t sbytes = fdc::iq_bytes(d.fmt_of[b]);
+    const char *base = devpay ? static_cast<const char *>(narrow ? d.d_nland[b] : (void *)d.d_land[b])
+                              : static_cast<const char *>(narrow ? d.h_nland[b] : (void *)d.h_land[b]);
     s->pdus.resize(recs.size());
     time_t last_t = (time_t)-1;
     char tbuf[40] = "";
@@ -1576,7 +1628,7 @@ static int dev_build(fdc_sinks *s, int b)
         m.blockstart = (det && !sd) ? (int64_t)(uint32_t)(m.blockend - r.count) : m.blockend - r.count;
         m.vectorstart = vstart; m.vectorend = vend;
         m.nsamples = (int64_t)(r.q1 - r.q0) * o.blocklen;
-        m.samples = m.nsamples ? base + sizeof(float2) * (size_t)r.off : nullptr;
+        m.samples = m.nsamples ? base + sbytes * (size_t)r.off : nullptr;
         if ((time_t)r.act_time != last_t) {                    // create_ID() / get_ID_for_msg(): local time of the activation
             last_t = (time_t)r.act_time;
             struct tm tmv;
@@ -1676,6 +1728,37 @@ int fdc_sinks_flush(fdc_sinks *s)
 }
 
 int32_t fdc_sinks_engine(const fdc_sinks *s) { return s ? (s->dev.on ? 1 : 0) : -1; }
+
+int fdc_sinks_set_payload_format(fdc_sinks *s, int32_t format, float scale)
+{
+    FDC_ENTRY("fdc_sinks_set_payload_format")
+    if (!s) return fdc::set_error(FDC_ERR_INVALID_ARGUMENT, "null handle");
+    FDC_DEAD_CHECK(s);
+    if (format != FDC_OQ_FC32 && format != FDC_OQ_SC16 && format != FDC_OQ_SC8)
+        return fdc::set_error(FDC_ERR_INVALID_ARGUMENT, "unknown payload format %d (FDC_OQ_FC32, FDC_OQ_SC16 or FDC_OQ_SC8)", (int)format);
+    if (!(std::isfinite(scale) && scale != 0.0f)) return fdc::set_error(FDC_ERR_INVALID_ARGUMENT, "the payload scale must be finite and not zero");
+    // a batch under way was laid out (and maybe narrowed) for the format it met: flush first.  A pipelined fdc_pipeline_work_sinks that holds batches
+    // of the bank shows here too: its newest batch sits prepared in one of the spectrum buffers, the one before is in flight
+    if (s->dev.inflight || s->dev.eager_n > 0 || s->prepared >= 0 || s->prepared_ahead >= 0)
+        return fdc::set_error(FDC_ERR_INVALID_ARGUMENT, "a batch is submitted, prepared ahead or in flight: flush the bank (fdc_sinks_flush / fdc_pipeline_flush_sinks) first");
+    if (format != FDC_OQ_FC32 && !s->dev.on)
+        return fdc::set_error(FDC_ERR_UNSUPPORTED, "sc16 / sc8 payloads need the device engine: this bank decides on the host (FDC_SINKS_HOST_DECISIONS, verbose, or segments above %d cells)", fdc::kDetMaxCells);
+    s->pay_fmt = format; s->pay_scale = scale;
+    s->pdus.clear();
+    return FDC_OK;
+    FDC_ENTRY_END
+}
+
+int fdc_sinks_payload_format(const fdc_sinks *s, int32_t *format, float *scale)
+{
+    FDC_ENTRY("fdc_sinks_payload_format")
+    if (!s || !format || !scale) return fdc::set_error(FDC_ERR_INVALID_ARGUMENT, "null argument");
+    *format = s->pay_fmt; *scale = s->pay_scale;
+    return FDC_OK;
+    FDC_ENTRY_END
+}
+
+int32_t fdc_sinks_payload_route(const fdc_sinks *s) { return s ? s->pay_route : -1; }
 
 int fdc_sinks_work_device(fdc_sinks *s, int nblocks)
 {

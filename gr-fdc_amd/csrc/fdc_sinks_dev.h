@@ -126,5 +126,8 @@ hipError_t launch_task_scatter(int nlist, const int64_t *task_base, const int32_
 // buffered blocks of the previous call move to their place in this call's landing buffer
 hipError_t launch_carry_copy(const SinkOwner *owners, int nowner_cap, const int64_t *owner_base, const int32_t *nowner, int npac, int nseg,
                              const SinkSummary *sum, const float2 *prev, float2 *cur, hipStream_t s);
+// ... the ones that go out in this call narrowed into ncur (samples of fmt = kIqSc16 / kIqSc8 at the same sample offsets), the rest into cur as float
+hipError_t launch_carry_copy_narrow(int fmt, float scale, const SinkOwner *owners, int nowner_cap, const int64_t *owner_base, const int32_t *nowner,
+                                    int npac, int nseg, const float2 *prev, float2 *cur, void *ncur, hipStream_t s);
 
 }  // namespace fdc

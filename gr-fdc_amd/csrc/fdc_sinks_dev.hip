@@ -13,6 +13,7 @@
 // kernel places the streams in the landing buffer so that every PDU is one contiguous run and only emitted runs cross PCIe.
 #include <climits>
 #include "fdc_sinks_dev.h"
+#include "fdc_iq.hpp"
 #include <cfloat>
 #include <cstdio>
 
@@ -1036,6 +1037,57 @@ hipError_t launch_carry_copy(const SinkOwner *owners, int nowner_max, const int6
     if (nowner_max <= 0 || !prev) return hipSuccess;
     hipLaunchKernelGGL(k_carry_copy, dim3((unsigned)nowner_max, (unsigned)(nseg + 1), kCarrySplit), dim3(256), 0, s, owners, owner_base,
                        nowner, npac, prev, cur);
+    return hipGetLastError();
+}
+
+// The same with the emitted runs narrowed (fdc_sinks_set_payload_format, the fused route): the carried blocks that go out in this call are narrowed
+// (fdc_iq.hpp oq_bits) into the narrow landing buffer at their sample offset, the ones that stay buffered move on as complex float.
+template <class TO>
+__global__ __launch_bounds__(256) void k_carry_copy_narrow(const SinkOwner *__restrict__ owners, const int64_t *__restrict__ owner_base,
+                                                           const int32_t *__restrict__ nowner, int npac, const float2 *__restrict__ prev,
+                                                           float2 *__restrict__ cur, TO *__restrict__ ncur, float scale)
+{
+    const int rg = blockIdx.y, c = blockIdx.x;
+    const int cnt = rg == 0 ? npac : nowner[rg - 1];
+    if (c >= cnt) return;
+    const SinkOwner o = owners[(rg == 0 ? 0 : owner_base[rg - 1]) + c];
+    if (o.carried <= 0) return;
+    const int ne = o.carried < o.emitted ? o.carried : o.emitted;
+    const float2 *src = prev + o.prev_off;
+    TO *da = ncur + o.a_off;
+    float2 *db = cur + o.b_off - (long long)ne * o.len;
+    const long long nA = (long long)ne * o.len, n = (long long)o.carried * o.len;
+    // two samples per lane and trip where everything is even: 16-byte loads, 8-byte (sc16) / 4-byte (sc8) narrow stores
+    if (!((o.len | o.prev_off | o.a_off | o.b_off) & 1)) {
+        const float4 *s4 = reinterpret_cast<const float4 *>(src);
+        float4 *b4 = reinterpret_cast<float4 *>(db);
+        const long long n4 = n >> 1, nA4 = nA >> 1;
+        for (long long i = (long long)blockIdx.z * 256 + threadIdx.x; i < n4; i += 256 * kCarrySplit) {
+            const float4 t = s4[i];
+            if (i < nA4) {
+                const unsigned u0 = oq_bits(TO{}, mk(t.x, t.y), scale), u1 = oq_bits(TO{}, mk(t.z, t.w), scale);
+                if constexpr (sizeof(TO) == 4) *reinterpret_cast<uint2 *>(da + 2 * i) = make_uint2(u0, u1);
+                else *reinterpret_cast<unsigned *>(da + 2 * i) = u0 | (u1 << 16);
+            } else b4[i] = t;
+        }
+    } else {
+        for (long long i = (long long)blockIdx.z * 256 + threadIdx.x; i < n; i += 256 * kCarrySplit) {
+            if (i < nA) da[i] = oq_narrow(TO{}, from2(src[i]), scale);
+            else db[i] = src[i];
+        }
+    }
+}
+
+hipError_t launch_carry_copy_narrow(int fmt, float scale, const SinkOwner *owners, int nowner_max, const int64_t *owner_base, const int32_t *nowner,
+                                    int npac, int nseg, const float2 *prev, float2 *cur, void *ncur, hipStream_t s)
+{
+    if (nowner_max <= 0 || !prev) return hipSuccess;
+    const dim3 grid((unsigned)nowner_max, (unsigned)(nseg + 1), kCarrySplit);
+    if (fmt == kIqSc16)
+        hipLaunchKernelGGL(k_carry_copy_narrow<sc16>, grid, dim3(256), 0, s, owners, owner_base, nowner, npac, prev, cur, static_cast<sc16 *>(ncur), scale);
+    else if (fmt == kIqSc8)
+        hipLaunchKernelGGL(k_carry_copy_narrow<sc8>, grid, dim3(256), 0, s, owners, owner_base, nowner, npac, prev, cur, static_cast<sc8 *>(ncur), scale);
+    else return hipErrorInvalidValue;
     return hipGetLastError();
 }
 

@@ -7,7 +7,8 @@
                                                               — include/FDC/activity_detection_channelizer_vcm.h:49
 
 work(items) takes normalised-spectrum items and returns the PDUs the reference would publish on "msgout" as
-(dict, complex64 array) pairs with the same keys (…vcm_impl.cc:415-430, PowerActivationChannel_impl.cc:222-233).
+(dict, complex64 array) pairs — with payload_format="sc16" / "sc8" (fdc_sinks_set_payload_format: narrowed on the device before they
+leave it) (dict, int16[n, 2] / int8[n, 2] array) pairs — with the same keys (…vcm_impl.cc:415-430, PowerActivationChannel_impl.cc:222-233).
 The ID strings are the reference's, timestamp of the activation included: "<Y-m-d-H-M-S>.PowActChan.<ID>.<n>(.fin|.part)",
 "<Y-m-d-H-M-S>.DETECTED.<seg>.<n>" (PowerActivationChannel_impl.cc:308-312, …vcm_impl.cc:526-530); `verbose` selects the
 reference's log lines (1 = stdout, 2 = its log files in the working directory).
@@ -21,7 +22,41 @@ import numpy as np
 from . import _lib
 
 
+PAYLOAD_FORMATS = {"fc32": _lib.FDC_OQ_FC32, "sc16": _lib.FDC_OQ_SC16, "sc8": _lib.FDC_OQ_SC8}
+_PAYLOAD_NAMES = {v: k for k, v in PAYLOAD_FORMATS.items()}
+# per payload format: bytes per sample, numpy type of one component
+_PAYLOAD_ITEM = {_lib.FDC_OQ_FC32: (8, np.float32), _lib.FDC_OQ_SC16: (4, np.int16), _lib.FDC_OQ_SC8: (2, np.int8)}
+
+
+def payload_format_code(fmt):
+    """"fc32" / "sc16" / "sc8" (or None = "fc32") -> FDC_OQ_*; anything else is a ValueError"""
+    if fmt is None:
+        return _lib.FDC_OQ_FC32
+    if not isinstance(fmt, str) or fmt.lower() not in PAYLOAD_FORMATS:
+        raise ValueError("unknown payload format %r: 'fc32', 'sc16' or 'sc8'" % (fmt,))
+    return PAYLOAD_FORMATS[fmt.lower()]
+
+
+def _payload_array(address, nsamples, code):
+    """nsamples samples of format `code` at a host address, copied: complex64[n], int16[n, 2] or int8[n, 2]"""
+    size, comp = _PAYLOAD_ITEM[code]
+    if nsamples <= 0:
+        return np.zeros(0, np.complex64) if code == _lib.FDC_OQ_FC32 else np.zeros((0, 2), comp)
+    raw = np.frombuffer((C.c_char * (size * nsamples)).from_address(address), dtype=comp).copy()
+    return raw.view(np.complex64) if code == _lib.FDC_OQ_FC32 else raw.reshape(-1, 2)
+
+
+def _check_face_payload(fmt, verbose):
+    """The block faces: the format's code; sc16 / sc8 together with a verbose mode (host engine: float payloads only) is a ValueError"""
+    code = payload_format_code(fmt)
+    if code != _lib.FDC_OQ_FC32 and int(verbose) != 0:
+        raise ValueError("payload_format=%r needs the device engine: verbose modes decide on the host and give complex float payloads only" % (fmt,))
+    return code
+
+
 class Sinks:
+    _payload_code = _lib.FDC_OQ_FC32
+
     def __init__(self, blocklen, relinvovl, pac=(), pac_thresh=6.0, pac_maxblocks=-1, pac_delay=0,
                  segments=(), det_thresh=10.0, det_maxblocks=-1, minchandist=0.005, det_delay=1, puffer=0.2,
                  max_blocks=64, device_id=0, det_variant=0, verbose=0, det_id=-1, host_decisions=False, device_payload=False,
@@ -94,10 +129,34 @@ class Sinks:
         """1 = decisions on the device (default), 0 = on host threads (verbose != 0, host_decisions, very fine segments)"""
         return int(_lib.lib().fdc_sinks_engine(self._h))
 
+    def set_payload_format(self, fmt, scale=1.0):
+        """fdc_sinks_set_payload_format: "fc32" (default), "sc16" or "sc8"; each payload component becomes
+        saturate(round_half_even(float32(y * scale))).  Between batches only (flush first); drops the bank's current PDUs."""
+        code = payload_format_code(fmt)
+        rc = _lib.lib().fdc_sinks_set_payload_format(self._h, code, float(scale))
+        if rc == -1:
+            raise ValueError(_lib.lib().fdc_last_error().decode())
+        _lib.check(rc)
+        self._payload_code = code
+
+    @property
+    def payload_format(self):
+        """(name, scale) as the bank reports it"""
+        f, sc = C.c_int32(), C.c_float()
+        _lib.check(_lib.lib().fdc_sinks_payload_format(self._h, C.byref(f), C.byref(sc)))
+        return _PAYLOAD_NAMES[int(f.value)], float(sc.value)
+
+    @property
+    def payload_route(self):
+        """of the last finished batch: 0 = float, 1 = narrowed by a pass of its own, 2 = fused into the kernels' stores"""
+        return int(_lib.lib().fdc_sinks_payload_route(self._h))
+
     def _collect(self):
         n = _lib.lib().fdc_sinks_pdu_count(self._h)
         if n <= 0:
             return []
+        code = self._payload_code
+        size = _PAYLOAD_ITEM[code][0]
         arr = (_lib.fdc_pdu * n)()
         _lib.check(_lib.lib().fdc_sinks_pdus(self._h, arr, n))
         if self.device_payload and self.engine() == 1:      # payloads stay on the device: (address, sample count) instead of arrays
@@ -108,15 +167,11 @@ class Sinks:
         # payloads that sit one behind the other in the handle's buffer are copied out as ONE array and sliced
         out, i = [], 0
         while i < n:
-            j, base, end = i, arr[i].samples, (arr[i].samples or 0) + 8 * arr[i].nsamples
+            j, base, end = i, arr[i].samples, (arr[i].samples or 0) + size * arr[i].nsamples
             while j + 1 < n and arr[j + 1].samples == end and arr[j + 1].nsamples > 0:
                 j += 1
-                end += 8 * arr[j].nsamples
-            total = (end - (base or 0)) // 8
-            if total > 0:
-                blob = np.frombuffer((C.c_float * (2 * total)).from_address(base), dtype=np.complex64).copy()
-            else:
-                blob = np.zeros(0, np.complex64)
+                end += size * arr[j].nsamples
+            blob = _payload_array(base, (end - (base or 0)) // size, code)
             off = 0
             for k in range(i, j + 1):
                 p = arr[k]
@@ -203,6 +258,31 @@ class SinksGroup(Sinks):
     def engine(self):
         return 1
 
+    def set_payload_format(self, fmt, scale=1.0):
+        """fdc_sinks_group_set_payload_format: every member, or none"""
+        code = payload_format_code(fmt)
+        rc = _lib.lib().fdc_sinks_group_set_payload_format(self._g, code, float(scale))
+        if rc == -1:
+            raise ValueError(_lib.lib().fdc_last_error().decode())
+        _lib.check(rc)
+        self._payload_code = code
+
+    @property
+    def payload_format(self):
+        for i in range(self.size()):
+            m = _lib.lib().fdc_sinks_group_member(self._g, i)
+            if m:
+                f, sc = C.c_int32(), C.c_float()
+                _lib.check(_lib.lib().fdc_sinks_payload_format(m, C.byref(f), C.byref(sc)))
+                return _PAYLOAD_NAMES[int(f.value)], float(sc.value)
+        return "fc32", 1.0
+
+    @property
+    def payload_route(self):
+        """the members' routes of the last call"""
+        ms = [_lib.lib().fdc_sinks_group_member(self._g, i) for i in range(self.size())]
+        return [int(_lib.lib().fdc_sinks_payload_route(m)) for m in ms if m]
+
     def size(self):
         return int(_lib.lib().fdc_sinks_group_size(self._g))
 
@@ -228,8 +308,7 @@ class SinksGroup(Sinks):
         out = []
         for k in range(n):
             p = arr[k]
-            data = np.frombuffer((C.c_float * (2 * p.nsamples)).from_address(p.samples), dtype=np.complex64).copy() if p.nsamples > 0 \
-                else np.zeros(0, np.complex64)
+            data = _payload_array(p.samples, p.nsamples, self._payload_code)
             out.append((dict(id=p.id.decode(), kind=p.kind, source=p.source, chan_id=p.chan_id, finalized=bool(p.finalized), part=p.part,
                              has_part=bool(p.has_part), rel_bw=p.rel_bw, rel_cfreq=p.rel_cfreq, blockstart=p.blockstart,
                              blockend=p.blockend, vectorstart=p.vectorstart, vectorend=p.vectorend), data))
@@ -273,7 +352,7 @@ def _det_pdu(meta, data):
 
 def _write_files(path, pdus, pac):
     """<path>/<ID>.fin and <path>/<ID>.parted.<n>, raw complex64 (…vcm_impl.cc:431-439,488-496;
-    PowerActivationChannel_impl.cc:235-244)."""
+    PowerActivationChannel_impl.cc:235-244); with an integer payload format the narrow samples as they are."""
     for d, data in pdus:
         base = d["ID"]
         if pac:
@@ -287,10 +366,13 @@ def _write_files(path, pdus, pac):
 
 class PowerActivationChannel:
     def __init__(self, blocklen, cfreq, bw, relinvovl, thresh, maxblocks, deactivation_delay, msg, fileoutput, path,
-                 verbose, ID, device_id=0, max_blocks=64):
+                 verbose, ID, device_id=0, max_blocks=64, *, payload_format=None, payload_scale=1.0):
         self.msg, self.fileoutput, self.path = bool(msg), bool(fileoutput), str(path)
+        code = _check_face_payload(payload_format, verbose)
         self.bank = Sinks(blocklen, relinvovl, pac=[(cfreq, bw, ID)], pac_thresh=thresh, pac_maxblocks=maxblocks,
                           pac_delay=deactivation_delay, max_blocks=max_blocks, device_id=device_id, verbose=verbose)
+        if code != _lib.FDC_OQ_FC32:
+            self.bank.set_payload_format(payload_format, payload_scale)
         self.params = self.bank.pac_params(0)
 
     def work(self, spectrum):
@@ -302,14 +384,18 @@ class PowerActivationChannel:
 
 class activity_detection_channelizer_vcm:
     def __init__(self, blocklen, segments, thresh, relinvovl, maxblocks, message, fileoutput, path, threads,
-                 minchandist, channel_deactivation_delay, window_flank_puffer, verbose, device_id=0, max_blocks=64):
+                 minchandist, channel_deactivation_delay, window_flank_puffer, verbose, device_id=0, max_blocks=64, *,
+                 payload_format=None, payload_scale=1.0):
         self.msg, self.fileoutput, self.path = bool(message), bool(fileoutput), str(path)
+        code = _check_face_payload(payload_format, verbose)
         for s in segments:
             if len(s) != 2:
                 raise ValueError("Segment is incorrect. must be of size 2")
         self.bank = Sinks(blocklen, relinvovl, segments=[tuple(s) for s in segments], det_thresh=thresh,
                           det_maxblocks=maxblocks, minchandist=minchandist, det_delay=channel_deactivation_delay,
                           puffer=window_flank_puffer, max_blocks=max_blocks, device_id=device_id, verbose=verbose)
+        if code != _lib.FDC_OQ_FC32:
+            self.bank.set_payload_format(payload_format, payload_scale)
         self.segments = [self.bank.segment_params(i) for i in range(len(segments))]
 
     def work(self, spectrum):
@@ -326,12 +412,15 @@ class SegmentDetection:
 
     def __init__(self, ID, blocklen, relinvovl, seg_start, seg_stop, thresh, minchandist, window_flank_puffer,
                  maxblocks_to_emit, channel_deactivation_delay, messageoutput, fileoutput, path, threads, verbose,
-                 device_id=0, max_blocks=64):
+                 device_id=0, max_blocks=64, *, payload_format=None, payload_scale=1.0):
         self.ID, self.msg, self.fileoutput, self.path = int(ID), bool(messageoutput), bool(fileoutput), str(path)
+        code = _check_face_payload(payload_format, verbose)
         self.bank = Sinks(blocklen, relinvovl, segments=[(seg_start, seg_stop)], det_thresh=thresh,
                           det_maxblocks=maxblocks_to_emit, minchandist=minchandist, det_delay=channel_deactivation_delay,
                           puffer=window_flank_puffer, max_blocks=max_blocks, device_id=device_id, det_variant=1,
                           verbose=verbose, det_id=self.ID)
+        if code != _lib.FDC_OQ_FC32:
+            self.bank.set_payload_format(payload_format, payload_scale)
         self.segment = self.bank.segment_params(0)
 
     def work(self, spectrum):

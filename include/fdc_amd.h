@@ -417,7 +417,8 @@ typedef struct {
     double rel_bw, rel_cfreq;
     int64_t blockstart, blockend, vectorstart, vectorend;   /* vectorstart/end are in the dict for detection only */
     int64_t nsamples;
-    const void *samples; /* complex float32, owned by the handle until its next work call                     */
+    const void *samples; /* nsamples items of the bank's payload format (fdc_sinks_set_payload_format: complex float32 by default,
+                            sc16 or sc8), owned by the handle until its next work call; a device pointer under FDC_SINKS_DEVICE_PAYLOAD */
     char id[72];         /* the message ID the reference builds when the channel is ACTIVATED:
                             "<YYYY-mm-dd-HH-MM-SS>.PowActChan.<ID>.<n>" (PowerActivationChannel_impl.cc:308-312; the dict and
                             the file name append ".fin" / ".part" / ".parted.<k>", :224, :237) and
@@ -492,6 +493,30 @@ int fdc_sinks_work_device(fdc_sinks *s, int nblocks);
 int fdc_sinks_submit_device(fdc_sinks *s, int nblocks);
 int fdc_sinks_flush(fdc_sinks *s);
 int32_t fdc_sinks_engine(const fdc_sinks *s);       /* 0 = host decisions, 1 = device decisions */
+/* PAYLOAD FORMAT: fdc_pdu.samples as sc16 / sc8, narrowed on the device before they leave it (the payload copy over PCIe is what bounds a bank
+ * whose PDUs land in host memory: sc16 halves its bytes, sc8 quarters them).  A setting of the bank like fdc_pipeline_set_output_format, and its rule:
+ *   format   FDC_OQ_FC32 (default), FDC_OQ_SC16 (int16 I, int16 Q interleaved: 4 bytes per sample) or FDC_OQ_SC8 (int8: 2 bytes)
+ *   scale    float32; zero or not finite: FDC_ERR_INVALID_ARGUMENT (negative is allowed)
+ * Each component of each payload sample y (exactly what the bank emits in FC32) becomes saturate(round_half_even(float32(y * scale))), the product
+ * rounded once and kept out of FMA contraction; NaN -> 0, +-Inf -> the limits.  fdc_pdu keeps its layout: nsamples stays a sample count, samples
+ * points at nsamples items of the format (host memory, or device memory under FDC_SINKS_DEVICE_PAYLOAD).
+ * The setting does not touch the channel state machines, the buffered blocks or the block counter: blocks buffered in live channels across batches
+ * stay complex float on the device and are narrowed when their PDU goes out, so a PDU collected over several batches (and over a change of the
+ * format) has the bits of the narrowed float PDU.
+ * Refused with FDC_ERR_INVALID_ARGUMENT, nothing changed: a null handle, an unknown format, a bad scale; a batch submitted, prepared (ahead) or in
+ * flight (fdc_sinks_flush first); a pipelined fdc_pipeline_work_sinks that still holds batches of the bank (fdc_pipeline_flush_sinks first).
+ * Refused with FDC_ERR_UNSUPPORTED: any format but FC32 on a bank that runs the HOST engine (FDC_SINKS_HOST_DECISIONS, verbose != 0, segments of more
+ * than 1024 cells): it assembles payloads on the host from float landing runs; narrowing there is out of scope.
+ * A successful call drops the bank's current PDUs (fdc_sinks_pdu_count == 0): every PDU a caller can see is in the format the bank reports.
+ * Two routes, chosen per batch (fdc_sinks_payload_route: of the last finished batch; 0 = float, 1 = narrowed, 2 = fused):
+ *   fused      every extraction of the batch is of the 256-bin class (a bank of 256-bin PowerActivationChannels): the extraction kernel and the move of
+ *              the buffered blocks store the emitted runs narrow themselves; the float landing buffer holds the buffered rests only
+ *              (a batch without extractions: fused on a bank that holds nothing but 256-bin PowerActivationChannels, narrowed on any other)
+ *   narrowed   any mix of width classes: the batch runs as in FC32, then one pass narrows the emitted runs in front of the payload copy
+ * The narrow landing buffers (device, and pinned host unless FDC_SINKS_DEVICE_PAYLOAD) grow by the rule of the float ones; nothing else is allocated. */
+int fdc_sinks_set_payload_format(fdc_sinks *s, int32_t format, float scale);
+int fdc_sinks_payload_format(const fdc_sinks *s, int32_t *format, float *scale);   /* both out-pointers are required */
+int32_t fdc_sinks_payload_route(const fdc_sinks *s);                               /* -1 for a null handle */
 /* Look-ahead (banks created with FDC_SINKS_LOOKAHEAD; round 5).  The decision kernels of a batch are chains — one wave per
  * PowerActivationChannel, one workgroup per detection segment (lib/activity_detection_channelizer_vcm_impl.cc:741-841 is sequential over
  * blocks and channels) — that leave the device idle, and the host has to see their summary before it can size the extraction launches.
@@ -570,6 +595,8 @@ int32_t fdc_sinks_group_size(const fdc_sinks_group *g);
 fdc_sinks *fdc_sinks_group_member(fdc_sinks_group *g, int i);                        /* owned by the group; NULL for a member without work */
 /* member i: its device, the band [lo, hi) of bins it copies, how many PowerActivationChannels and segments it holds */
 int fdc_sinks_group_member_info(const fdc_sinks_group *g, int i, int32_t *device, int32_t *lo, int32_t *hi, int32_t *npac, int32_t *nseg);
+/* fdc_sinks_set_payload_format on every member (all or none: a member on the host engine refuses sc16 / sc8 for the whole group); drops the group's PDUs */
+int fdc_sinks_group_set_payload_format(fdc_sinks_group *g, int32_t format, float scale);
 
 /* ------------------------------------------------------------------------------------------------
  * Single-block faces (same arithmetic as the fused pipeline, one reference block each).
