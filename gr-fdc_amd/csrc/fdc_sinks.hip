@@ -2,50 +2,34 @@
 // activity_detection_channelizer_vcm, sharing one device-resident spectrum (the hier block feeds all of them from the
 // same normalize_input output, python/FrequencyDomainChannelizer.py:301-312).
 //
-// Split of work: the data-parallel parts run on the GPU for a whole batch of blocks —
-// per-(block, cell) power sums (k_cell_power) and the window * half-swap * IFFT * discard extractions (k_extract,
-// grouped by width) — while the per-block decision logic, which is inherently sequential over blocks and tiny
-// (a few hundred floats per block), runs on the host between the two GPU phases:
-//     GPU power cells -> D2H -> host state machines (one pass over the batch, emits an extraction task list and PDU
-//     records that reference tasks) -> GPU extractions -> D2H -> payload assembly.
-// Behaviour follows lib/PowerActivationChannel_impl.cc and lib/activity_detection_channelizer_vcm_impl.cc; line
-// references are given at each decision.  The `threads` flag of the reference is accepted and ignored (GPU batching
-// replaces the per-channel std::thread fan-out).
-#include "../../include/fdc_amd.h"
-#include "fdc_kernels.h"
-#include "fdc_sinks_dev.h"
+// The data-parallel parts run on the GPU for a whole batch of blocks in every bank: per-(block, cell)
+// power sums (k_cell_power) and the window * half-swap * IFFT * discard extractions (k_extract, grouped by width).  The
+// per-block decisions between them — the work() loops of the reference blocks — have two engines:
+//   * the DEVICE engine (fdc_sinks_dev.hip; its host side is here: dev_setup, dev_enqueue, dev_launch_extractions, dev_build,
+//     dev_wait): the loops run as kernels, task lists, layout and buffered blocks stay on the device, batches go two deep
+//     (fdc_sinks_submit_device / fdc_sinks_flush), payloads may stay in device memory or leave as sc16 / sc8.  The default.
+//   * the HOST engine (fdc_sinks_host.hip): power cells to the host, state machines on host threads, extractions, payloads
+//     assembled on the host; one synchronous batch per call.  The fall-back: a bank gets it with FDC_SINKS_HOST_DECISIONS,
+//     with verbose != 0 (the reference's logs are written where the decisions fall), with a segment above kDetMaxCells cells
+//     or tables beyond the device engine's budget (dev_setup decides; fdc_sinks_engine() reports).
+// This file holds construction and destruction, every extern "C" entry, and what both engines share: the two ends of a batch
+// (batch_begin, batch_end_history, batch_end_swap), the extraction launches (run_extractions) and the reference's logs.  The
+// handle and its records are in fdc_sinks_state.hpp.  Behaviour follows lib/PowerActivationChannel_impl.cc and
+// lib/activity_detection_channelizer_vcm_impl.cc; line references are given at each decision.  The `threads` flag of the
+// reference sizes the host engine's worker pool and nothing else (GPU batching replaces the per-channel std::thread fan-out).
+#include "fdc_sinks_state.hpp"
 #include "fdc_guard.hpp"
-#include "fdc_iq.hpp"
 
 #include <algorithm>
 #include <cfloat>
-#include <chrono>
 #include <cmath>
-#include <complex>
-#include <condition_variable>
-#include <functional>
-#include <mutex>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
-#include <deque>
-#include <memory>
-#include <string>
-#include <thread>
-#include <vector>
 
 extern "C" const char *fdc_last_error(void);
-namespace fdc { int set_error(int code, const char *fmt, ...); int pick_device(int device_id); const char *debug_env(const char *name); }
 
-namespace {
-
-using cfl = std::complex<float>;
-
-#define HIPCHK(expr)                                                                                              \
-    do {                                                                                                          \
-        hipError_t _e = (expr);                                                                                   \
-        if (_e != hipSuccess) return fdc::set_error(FDC_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(_e)); \
-    } while (0)
+using namespace fdc::sinks;
 
 // body of an extern "C" entry: nothing thrown inside crosses the C boundary (fdc_guard.hpp)
 #define FDC_ENTRY(name) return fdc::guarded(name, [&]() -> int {
@@ -58,237 +42,24 @@ using cfl = std::complex<float>;
             return fdc::set_error(FDC_ERR_HIP, "the bank failed in an earlier call and must be destroyed (%s)", (s)->poison_why.c_str()); \
     } while (0)
 
-int pow2ceil(int k) { return (int)std::pow(2.0, std::ceil(std::log2((double)k))); }
-bool ispow2i(int k) { return k > 0 && (k & (k - 1)) == 0; }
-
-// A buffered output block of a channel: either still on the device as the result of a task of the current call, or a
-// host copy carried over from an earlier call.
-struct BlockRef {
-    int64_t task = -1;
-    std::vector<cfl> owned;
-};
-
-struct PduRec {
-    int64_t key = 0;                // emission order inside a call: block, then PowerActivationChannels in order, then detections
-    fdc_pdu meta{};
-    std::vector<BlockRef> blocks;
-    int blocklen = 0;               // samples per block
-    std::vector<cfl> payload;
-};
-
-struct Pac {
-    int ID = 0, extract_start = 0, extract_stop = 0, extract_width = 0, output_len = 0, ovl_offset = 0;
-    int measure_start = 0, measure_stop = 0, deltaphase = 0, win_off = 0, cell = 0;
-    bool active = false;
-    float lastpower = FLT_MAX;
-    int count = 0, phase = 0, part = 0, finished = 0, id_at_activation = 0;
-    std::string msg_id;                  // create_ID() at activation, :308-312
-    std::vector<BlockRef> blocks;        // handed to the PDU as a whole when it is emitted
-};
-
-struct DetChan {
-    int ID, detect_start, detect_stop, extract_start, extract_stop, extract_width, wclass, ovlskip, outputsamples;
-    int count, phase, phaseincrement, inactive, part;
-    std::string msg_id;                  // get_ID_for_msg() at activation, …vcm_impl.cc:526-530
-    std::deque<BlockRef> data;
-};
-
-struct Segment {
-    int ID = 0, start = 0, stop = 0, width = 0, ncell = 0, cell0 = 0, counter = 0;
-    std::deque<DetChan> chans;
-};
-
-
-// What a worker thread collects while it runs its range of PowerActivationChannels over a batch.  Kept from call to call:
-// the lists keep their capacity (no page faults on fresh heap memory in every call).
-struct WorkerLists {
-    std::vector<fdc::ExtractTask> tasks;
-    std::vector<int> w, skip;
-    int64_t used = 0;
-    std::vector<PduRec> pdus;
-    void clear() { tasks.clear(); w.clear(); skip.clear(); used = 0; pdus.clear(); }
-};
-
-// Fork-join pool of the handle (threads are made once; a batch costs two condition-variable round trips instead of a
-// thread creation per worker).
-class WorkerPool {
-public:
-    ~WorkerPool() { stop(); }
-    // false: a job threw (std::bad_alloc from a growing list, normally): the batch is lost, the process is not
-    bool run(int n, const std::function<void(int)> &fn)
-    {
-        if ((int)th_.size() < n) grow(n);
-        {
-            std::lock_guard<std::mutex> g(m_);
-            job_ = &fn; njob_ = n; pending_ = n; gen_++; failed_ = false;
-        }
-        cv_.notify_all();
-        std::unique_lock<std::mutex> lk(m_);
-        done_.wait(lk, [&] { return pending_ == 0; });
-        job_ = nullptr;
-        return !failed_;
-    }
-    void stop()
-    {
-        {
-            std::lock_guard<std::mutex> g(m_);
-            quit_ = true;
-        }
-        cv_.notify_all();
-        for (auto &t : th_) t.join();
-        th_.clear();
-    }
-private:
-    void grow(int n)
-    {
-        for (int i = (int)th_.size(); i < n; i++)
-            th_.emplace_back([this, i] {
-                uint64_t seen = 0;
-                for (;;) {
-                    const std::function<void(int)> *fn = nullptr;
-                    {
-                        std::unique_lock<std::mutex> lk(m_);
-                        cv_.wait(lk, [&] { return quit_ || (gen_ != seen && i < njob_); });
-                        if (quit_) return;
-                        seen = gen_; fn = job_;
-                    }
-                    bool ok = true;
-                    try { (*fn)(i); } catch (...) { ok = false; }     // nothing may unwind out of a worker thread
-                    {
-                        std::lock_guard<std::mutex> g(m_);
-                        if (!ok) failed_ = true;
-                        pending_--;
-                    }
-                    done_.notify_one();
-                }
-            });
-    }
-    std::vector<std::thread> th_;
-    std::mutex m_;
-    std::condition_variable cv_, done_;
-    const std::function<void(int)> *job_ = nullptr;
-    int njob_ = 0, pending_ = 0;
-    uint64_t gen_ = 0;
-    bool quit_ = false, failed_ = false;
-};
-
-}  // namespace
-
-struct fdc_sinks {
-    fdc_sinks_cfg cfg{};
-    int N = 0, R = 0, dec = 1;
-    float pac_thr = 0.f, det_thr = 0.f;
-    std::vector<Pac> pacs;
-    std::vector<Segment> segs;
-    std::vector<int> det_win_off;            // per width class
-    std::vector<fdc::PowerCell> cells;
-    int64_t blockcount = 1;                  // both reference blocks start counting at 1 (hist is block 0)
-    // A work / submit / flush call that fails after it has begun to advance the bank's state (block counter, channel state on the
-    // device, buffered blocks, the two-deep pipeline) cannot be undone or repeated: the handle is dead from then on and every
-    // later call says so (include/fdc_amd.h, "Failure").
-    bool poisoned = false;
-    std::string poison_why;
-    hipStream_t stream = nullptr;
-    float2 *d_spec = nullptr;                // (max_blocks + 1) * N: slot 0 = history block.  The buffer the NEXT batch is read from
-    float2 *d_wins = nullptr, *d_tw = nullptr, *d_tw256 = nullptr;    // window pool, exp(-2 pi i k/N), exp(-2 pi i j/256)
-    fdc::PowerCell *d_cells = nullptr;
-    float *d_power = nullptr;                // power cells of the batch in d_spec
-    // FDC_SINKS_LOOKAHEAD: a second spectrum / power buffer and a stream of its own for their producer, so that the forward transform
-    // (and the power cells) of batch n + 1 run on the device beside the decision kernels of batch n — one wave per channel or a
-    // workgroup per segment: latency-bound kernels that leave the machine idle (fdc_sinks_spectrum_ahead, fdc_sinks_prepare_ahead).
-    // d_spec / d_power always name the buffers of the batch the next submit reads; the pair swaps when a batch's extractions are enqueued.
-    float2 *d_spec_ahead = nullptr;
-    float *d_power_ahead = nullptr;
-    // Two, not three: with two, the forward transform of batch n + 2 waits for the extractions of batch n to release their buffer, and a batch's whole
-    // chain (transform, cells, decisions, the host's look at the summary, task placement, extractions: 0.65 ms at configs[2]) runs two deep: 0.34 ms per
-    // step for 0.29 ms of fill-stream work (profiles/r06/timeline_cfg3_shipped.txt).  With a third buffer (round 6, measured and removed) the transform
-    // does run beside the extractions — and both slow down: they are the two bandwidth-heavy kernels of the step (configs[2] 0.340 -> 0.335 ms, forward
-    // kernel 0.25 -> 0.28; configs[4] 0.49 -> 0.53, forward kernel 0.40 beside k_det_track and the extractions; profiles/r06/sched_three_buffers.txt).
-    // The step is the memory system's, not the schedule's.
-    // round 6: the power of every 16-bin group of the spectra in d_spec (slot 1 on) / d_spec_ahead, written by the producer's forward kernel
-    // (fdc_pipeline_process_device_power) beside the spectrum: fdc_sinks_prepare_from_groups sums the cells from it instead of reading the spectrum back
-    float *d_gpow = nullptr, *d_gpow_ahead = nullptr;
-    hipStream_t s_fill = nullptr;
-    hipEvent_t ev_fill = nullptr;
-    // ... and two side streams: the width classes above 4096 points are two small launches each (a few hundred transforms); side by side
-    // they fill the device, one after the other they do not (configs[4]: 3 x (42 + 20) us).  Only with the flag: with the payload copy to the
-    // host running, more streams than hardware queues put a class behind the copy (profiles/r03/NOTES.md).
-    hipStream_t s_side[2] = {nullptr, nullptr};
-    hipEvent_t ev_fork = nullptr, ev_join[2] = {nullptr, nullptr};
-    // ... and the extraction kernels of a batch on a stream of their own (s_x), so that the NEXT batch's decision chain — enqueued on the bank's
-    // stream by the next submit — starts beside them instead of behind them (two deep as before: that submit hands out this batch's PDUs).
-    // Placement of the tasks and the buffered blocks' move stay on the bank's stream (they read what the next chain overwrites).
-    hipStream_t s_x = nullptr;
-    hipEvent_t ev_tasks = nullptr;
-    hipEvent_t ev_ready = nullptr, ev_ready_ahead = nullptr;   // recorded on s_fill behind the power cells of the batch in d_spec / d_spec_ahead (fdc_sinks_prepare)
-    int prepared = -1, prepared_ahead = -1;  // blocks whose power cells are already (being) computed in d_power / d_power_ahead on s_fill; -1 = none
-    fdc::ExtractTask *d_tasks = nullptr; size_t cap_tasks = 0;
-    float2 *d_ext = nullptr; size_t cap_ext = 0;
-    float2 *d_wide = nullptr; size_t wide_cap = 0;  // scratch of extractions wider than 4096 points (between the two passes): wide_cap points
-    std::vector<fdc::ExtractTask> sorted;          // tasks grouped by width class
-    cfl *h_ext = nullptr; size_t cap_hext = 0;      // pinned landing buffer of the extractions
-    std::vector<float> h_power;
-    std::vector<PduRec> pdus;
-    // per-call scratch
-    std::vector<fdc::ExtractTask> tasks;
-    std::vector<int> task_w, task_skip;
-    int64_t ext_used = 0;
-    std::vector<std::unique_ptr<WorkerLists>> wl;    // one per worker thread (separate heap objects: no shared cache lines)
-    WorkerPool pool;
-    std::string det_logfile;                 // verbose == 2: …vcm_impl.cc:94 / SegmentDetection_impl.cc:51
-    int host_threads = 0;                    // cfg.threads (host engine), 0 = from the bank's size
-    // fdc_sinks_set_payload_format: what fdc_pdu.samples holds (fdc::IqFormat = FDC_OQ_*), and the route the last finished batch took to it
-    int pay_fmt = fdc::kIqFloat;
-    float pay_scale = 1.0f;
-    int pay_route = 0;
-    bool pay_all256 = false;                 // the bank holds 256-bin PowerActivationChannels and nothing else: every extraction it can ever make is k_x256's
-    // ---- device engine (fdc_sinks_dev.hip): decisions, layout and buffered blocks stay on the device
-    struct Dev {
-        bool on = false;
-        int nlist = 0, npw = 0;
-        long long max_list = 0;              // longest task list (grid of the scatter kernel)
-        std::vector<int64_t> task_base, pdu_base, owner_base, cand_base;
-        int64_t *d_task_base = nullptr, *d_pdu_base = nullptr, *d_owner_base = nullptr, *d_cand_base = nullptr;
-        int32_t *d_ntask = nullptr, *d_npdu = nullptr, *d_nowner = nullptr, *d_error = nullptr, *d_class_fill = nullptr;
-        int32_t *d_ncand = nullptr, *d_winoff = nullptr, *d_live = nullptr, *d_live2 = nullptr;
-        fdc::DetCh *d_detch = nullptr;        // tracker scratch: one life record per entry of the owner table
-        int64_t *d_live_off = nullptr;
-        int2 *d_cand = nullptr;
-        fdc::PacGeom *d_pgeom = nullptr; fdc::PacState *d_pstate = nullptr;
-        fdc::DetGeom *d_dgeom = nullptr; fdc::DetSegState *d_sst = nullptr;
-        fdc::SinkTask *d_tasks = nullptr; fdc::SinkPdu *d_pdus = nullptr, *d_pdus_out = nullptr; fdc::SinkOwner *d_owners = nullptr;
-        fdc::ExtractTask *d_sorted = nullptr;
-        fdc::SinkSummary *d_sum = nullptr, *h_sum = nullptr;
-        fdc::SinkPdu *h_pdus = nullptr;      // pinned: the first kEagerPdus records travel with the summary
-        float2 *d_land[2] = {nullptr, nullptr}; size_t cap_land[2] = {0, 0};      // landing buffers (emitted runs, then buffered rests)
-        cfl *h_land[2] = {nullptr, nullptr}; size_t cap_hland[2] = {0, 0};        // pinned copies of the emitted runs
-        // sc16 / sc8 payloads: the emitted runs [0, used_a) once more, narrow, at the same SAMPLE offsets (capacities in bytes); the buffered rests
-        // stay float in d_land
-        void *d_nland[2] = {nullptr, nullptr}; size_t cap_nland[2] = {0, 0};
-        void *h_nland[2] = {nullptr, nullptr}; size_t cap_hnland[2] = {0, 0};
-        int fmt_of[2] = {0, 0}, route_of[2] = {0, 0};                             // payload format and route (fdc_sinks_payload_route) of the batch in buffer b
-        hipStream_t s_copy = nullptr;
-        int carry_width = 0;                 // streams that can hold blocks from the call before: every PowerActivationChannel, or a
-                                             // segment's live channels (disjoint detect ranges: at most one per power cell)
-        hipEvent_t ev_decide = nullptr, ev_extract[2] = {nullptr, nullptr}, ev_copied[2] = {nullptr, nullptr};
-        std::vector<fdc::SinkPdu> recs[2];
-        std::vector<std::pair<int64_t, uint32_t>> order;     // emission order of a batch's records (scratch of dev_build)
-        fdc::SinkSummary sum[2];
-        int64_t bc0[2] = {0, 0};              // block counter at the start of the batch in landing buffer b
-        int nb_of[2] = {0, 0};
-        bool pend[2] = {false, false};        // batch in landing buffer b is enqueued and not yet handed out
-        int cur = 1;                          // landing buffer of the newest batch
-        bool inflight = false;                // some batch is pending
-        bool any = false;                     // a batch has run: d_land[cur] holds buffered blocks
-        int eager_n = 0;                      // look-ahead: the decision chain of the NEXT batch (prepared, this many blocks) is already enqueued
-    } dev;
-};
-
 namespace {
+
+bool ispow2i(int k) { return k > 0 && (k & (k - 1)) == 0; }
 
 std::mutex g_log_mu;
 fdc_log_fn g_log_fn = nullptr;
 void *g_log_user = nullptr;
+
+void start_logfile(const std::string &file)      // constructors: the file is truncated to one empty line
+{
+    FILE *f = std::fopen(file.c_str(), "w");
+    if (!f) std::fprintf(stderr, "Logfile not writable: %s\n", file.c_str());
+    else { std::fputc('\n', f); std::fclose(f); }
+}
+
+}  // namespace
+
+namespace fdc { namespace sinks {
 
 // get_current_time(), …vcm_impl.cc:56-69 / PowerActivationChannel_impl.cc:435-447 (the reference formats into char p[40]
 // with a stated size of 80; 19 characters are written)
@@ -324,215 +95,134 @@ void sink_log(const fdc_sinks *s, const std::string &file, const std::string &li
         else { std::fputs(line.c_str(), f); std::fputc('\n', f); std::fclose(f); }
     }
 }
-std::string pac_logfile(const Pac &p) { return "gr-FDC.PowActChan." + std::to_string(p.ID) + ".log"; }
-void start_logfile(const std::string &file)      // constructors: the file is truncated to one empty line
+
+// ---- FDC_SINKS_LOOKAHEAD (see the struct): what a batch does at its two ends
+// start of a batch: whatever its producer enqueued on the fill stream (forward transform, power cells) comes first
+int batch_begin(fdc_sinks *s, int nblocks, bool *have_power)
 {
-    FILE *f = std::fopen(file.c_str(), "w");
-    if (!f) std::fprintf(stderr, "Logfile not writable: %s\n", file.c_str());
-    else { std::fputc('\n', f); std::fclose(f); }
+    *have_power = false;
+    if (!s->s_fill) {
+        // one-buffer bank: fdc_sinks_prepare_from_groups has (enqueued, on this stream) the cells of exactly this batch
+        *have_power = s->prepared == nblocks;
+        s->prepared = -1;
+        return FDC_OK;
+    }
+    if (s->prepared == nblocks) {
+        // fdc_sinks_prepare marked the point of the fill stream where this batch is complete: what the producer has enqueued there SINCE
+        // (the next batch's transform) is not waited for — it is what runs beside this batch's decisions
+        HIPCHK(hipStreamWaitEvent(s->stream, s->ev_ready, 0));
+        *have_power = true;
+    } else {
+        HIPCHK(hipEventRecord(s->ev_fill, s->s_fill));          // no mark: everything enqueued on the fill stream so far
+        HIPCHK(hipStreamWaitEvent(s->stream, s->ev_fill, 0));
+    }
+    s->prepared = -1;
+    return FDC_OK;
+}
+// end of a batch (enqueued behind its last reader): history <- its last block (save_hist, PowerActivationChannel_impl.cc:173;
+// …vcm_impl.cc:571) — slot 0 of the buffer the NEXT batch is read from, which with look-ahead is the other one ...
+int batch_end_history(fdc_sinks *s, int nblocks, hipStream_t q)
+{
+    const size_t N = (size_t)s->N;
+    float2 *const next = s->d_spec_ahead ? s->d_spec_ahead : s->d_spec;
+    HIPCHK(hipMemcpyAsync(next, s->d_spec + (size_t)nblocks * N, sizeof(float2) * N, hipMemcpyDeviceToDevice, q));
+    return FDC_OK;
+}
+// ... then the buffers swap, and the fill stream may overwrite this batch's buffer once `done` (an event on the bank's stream behind the
+// history copy; null: everything enqueued on it so far) has passed
+int batch_end_swap(fdc_sinks *s, hipEvent_t done)
+{
+    if (!s->s_fill) return FDC_OK;
+    if (done) HIPCHK(hipStreamWaitEvent(s->s_fill, done, 0));
+    else { HIPCHK(hipEventRecord(s->ev_fill, s->stream)); HIPCHK(hipStreamWaitEvent(s->s_fill, s->ev_fill, 0)); }
+    std::swap(s->d_spec, s->d_spec_ahead);
+    std::swap(s->d_power, s->d_power_ahead);
+    std::swap(s->d_gpow, s->d_gpow_ahead);
+    std::swap(s->ev_ready, s->ev_ready_ahead);
+    s->prepared = s->prepared_ahead; s->prepared_ahead = -1;
+    return FDC_OK;
 }
 
-// Where the decisions of one batch are collected: the handle's own lists, or the private lists of a worker thread that
-// runs a range of PowerActivationChannels on its own (they do not interact; the lists are merged afterwards).
-struct Emit {
-    std::vector<fdc::ExtractTask> *tasks;
-    std::vector<int> *task_w, *task_skip;
-    int64_t *ext_used;
-    std::vector<PduRec> *pdus;
-    int64_t blockcount;             // the block counter while the current block is processed
-    int64_t key;                    // order key of a PDU emitted now
-};
-
-int64_t add_task(Emit &e, int slot, int start, int w, int skip, int win_off)
+// Extractions of one call, one launch (or one gather / batched transform / scatter sequence) per width class.
+// tasks: grouped by class, class k (width 2^k) = [first[k], first[k] + cnt[k])
+// narrow: the fused payload route (every task is of the 256-bin class): the emitted runs [0, used_a) go to it in the bank's payload format
+int run_extractions(fdc_sinks *s, const fdc::ExtractTask *d_tasks, const size_t *first, const size_t *cnt, float2 *d_out, bool trace,
+                    hipStream_t q0, void *narrow, long long used_a)
 {
-    fdc::ExtractTask t{};
-    t.slot = slot; t.start = start; t.win_off = win_off; t.out_off = *e.ext_used;
-    *e.ext_used += w - skip;
-    e.tasks->push_back(t);
-    e.task_w->push_back(w); e.task_skip->push_back(skip);
-    return (int64_t)e.tasks->size() - 1;
-}
-
-// ---------------------------------------------------------------- PowerActivationChannel
-void pac_process(const fdc_sinks *s, Emit &e, Pac &p, int slot)            // process_channel, …_impl.cc:260-284
-{
-    BlockRef b;
-    b.task = add_task(e, slot, p.extract_start, p.extract_width, p.ovl_offset, p.win_off + p.phase * p.extract_width);
-    p.blocks.push_back(std::move(b));
-    p.count++;
-    p.phase = (p.phase + p.deltaphase) % s->R;
-}
-
-void pac_emit(const fdc_sinks *s, Emit &e, Pac &p, bool fin)               // emit_data, :212-258
-{
-    PduRec r;
-    r.key = e.key;
-    r.meta.kind = 0; r.meta.source = p.ID; r.meta.chan_id = p.id_at_activation;
-    r.meta.finalized = fin; r.meta.part = p.part; r.meta.has_part = 1;
-    r.meta.rel_cfreq = (double)(p.extract_start + p.extract_stop) / 2.0 / (double)s->N;
-    r.meta.rel_bw = (double)p.extract_width / (double)s->N;
-    r.meta.blockstart = e.blockcount - p.count; r.meta.blockend = e.blockcount;
-    r.meta.vectorstart = p.extract_start; r.meta.vectorend = p.extract_stop;
-    std::snprintf(r.meta.id, sizeof r.meta.id, "%s", p.msg_id.c_str());
-    r.blocklen = p.output_len;
-    r.blocks = std::move(p.blocks);                                        // the whole list changes hands: no per-block move
-    p.blocks.clear();
-    p.blocks.reserve(r.blocks.size() + 2);
-    if (s->cfg.verbose)                                                    // :246-253
-        sink_log(s, pac_logfile(p), p.msg_id + (fin ? std::string(".fin") : ".parted." + std::to_string(p.part)) + ": start=" +
-                 std::to_string(p.extract_start) + ", stop=" + std::to_string(p.extract_stop) + ", blockstart=" +
-                 std::to_string((long long)r.meta.blockstart) + ", blockend=" + std::to_string((long long)r.meta.blockend));
-    e.pdus->push_back(std::move(r));
-    p.part++;
-}
-
-void pac_step(const fdc_sinks *s, Emit &e, Pac &p, float pwr, int slot)    // one item of work(), :146-170
-{
-    if (pwr == 0.0f) pwr = FLT_MIN;                                        // :293-294
-    bool changed = false;
-    if (!p.active && pwr / p.lastpower >= s->pac_thr) changed = true;      // :296-302
-    else if (p.active && p.lastpower / pwr >= s->pac_thr) changed = true;
-    p.lastpower = pwr;
-    if (changed) {
-        if (!p.active) {                                                   // activate(), :198-210
-            p.part = 0; p.count = 0; p.active = true; p.phase = 0; p.blocks.clear();
-            p.id_at_activation = p.finished;
-            p.msg_id = current_time_string() + ".PowActChan." + std::to_string(p.ID) + "." + std::to_string(p.finished);
-            pac_process(s, e, p, slot - 1);                                // previous block (slot 0 = saved history)
-            pac_process(s, e, p, slot);
+    const int N = s->N;
+    if (!q0) q0 = s->stream;
+    // the classes that fit one workgroup's transform at 16 points per lane (w <= 4096; 256 has a kernel of its own) are independent and
+    // each fills a part of the device only: two or more of them go out as ONE launch
+    int mw[32], nm = 0;
+    size_t mfirst[32], mcnt[32];
+    for (int k = 0; k < 32; k++) {
+        const int w = 1 << k;
+        if (cnt[k] && w <= 4096 && !(w == 256 && s->d_tw256)) { mw[nm] = w; mfirst[nm] = first[k]; mcnt[nm] = cnt[k]; nm++; }
+    }
+    const bool multi = nm >= 2 && nm <= fdc::kMaxExtractClasses;
+    // side streams (look-ahead banks): two or three classes above 4096 points, each in one piece of its own slice of the scratch
+    int nwide = 0, wk[3] = {0, 0, 0};
+    size_t wneed = 0;
+    bool side = s->s_side[0] != nullptr;
+    for (int k = 13; k < 32 && side; k++)
+        if (cnt[k]) {
+            if (nwide == 3 || cnt[k] * ((size_t)1 << k) > ((size_t)64 << 20)) { side = false; break; }
+            wk[nwide++] = k; wneed += cnt[k] * ((size_t)1 << k);
+        }
+    side = side && nwide >= 2;
+    if (side) {
+        HIPCHK(s->d_wide.reserve(wneed, wneed + wneed / 2));
+        HIPCHK(hipEventRecord(s->ev_fork, q0));
+        size_t off = 0;
+        for (int c = 0; c < nwide; c++) {
+            const int k = wk[c], w = 1 << k;
+            hipStream_t q = c == 0 ? q0 : s->s_side[c - 1];
+            if (c) HIPCHK(hipStreamWaitEvent(q, s->ev_fork, 0));
+            if (c == 0 && multi)        // the classes up to 4096 points go first on the bank's own stream, the widest class behind them
+                HIPCHK(fdc::launch_extract_multi(s->d_spec, N, d_tasks, mw, mfirst, mcnt, nm, s->R, s->d_wins, d_out, s->d_tw, N, q0));
+            HIPCHK(fdc::launch_extract_wide(s->d_spec, N, d_tasks + first[k], (int)cnt[k], w, w / s->R, s->d_wins, s->d_wide + off, d_out, s->d_tw, N, q));
+            off += cnt[k] * (size_t)w;
+            if (c) HIPCHK(hipEventRecord(s->ev_join[c - 1], q));
+        }
+    } else if (multi) HIPCHK(fdc::launch_extract_multi(s->d_spec, N, d_tasks, mw, mfirst, mcnt, nm, s->R, s->d_wins, d_out, s->d_tw, N, q0));
+    for (int k = 0; k < 32; k++) {
+        if (!cnt[k]) continue;
+        const int w = 1 << k, skip = w / s->R;
+        const size_t i = first[k], j = first[k] + cnt[k];
+        if (trace) std::fprintf(stderr, "[fdc_sinks]     width %d: %zu tasks\n", w, j - i);
+        if (multi && w <= 4096 && !(w == 256 && s->d_tw256)) continue;
+        if (side && w > 4096) continue;
+        if (w == 256 && s->d_tw256 && narrow) {
+            HIPCHK(fdc::launch_extract256_narrow(s->pay_fmt, s->pay_scale, s->d_spec, N, d_tasks + i, (int)(j - i), skip, s->d_wins, d_out, narrow, used_a,
+                                                 s->d_tw256, q0));
+        } else if (w == 256 && s->d_tw256) {
+            HIPCHK(fdc::launch_extract256(s->d_spec, N, d_tasks + i, (int)(j - i), skip, s->d_wins, d_out, s->d_tw256, q0));
+        } else if (w <= 4096) {
+            HIPCHK(fdc::launch_extract(s->d_spec, N, d_tasks + i, (int)(j - i), w, skip, s->d_wins, d_out, s->d_tw, N, q0));
         } else {
-            pac_process(s, e, p, slot);
-            p.active = false;                                              // deactivate(), :189-196
-            pac_emit(s, e, p, true);
-            p.finished++;
-        }
-    } else if (p.active) {
-        pac_process(s, e, p, slot);
-        const int mb = s->cfg.pac_maxblocks;
-        if (mb == 0 || (mb > 0 && p.count % mb == 0)) pac_emit(s, e, p, false);
-    }
-}
-
-// ---------------------------------------------------------------- activity_detection_channelizer_vcm
-void det_process(fdc_sinks *s, Emit &e, DetChan &c, int slot)        // process_channel, …vcm_impl.cc:373-397
-{
-    BlockRef b;
-    b.task = add_task(e, slot, c.extract_start, c.extract_width, c.ovlskip,
-                      s->det_win_off[c.wclass] + c.phase * c.extract_width);
-    c.data.push_back(std::move(b));
-    c.count++;
-    c.phase = (c.phase + c.phaseincrement) % s->R;
-}
-
-void det_emit(fdc_sinks *s, Emit &e, Segment &g, DetChan &c, bool fin, size_t nblk)   // :406-452 / :454-510
-{
-    PduRec r;
-    r.key = e.key++;
-    // the number the ID string carries (activate()): SegmentDetection's own ID where the bank was given one — as the device engine reports it
-    r.meta.kind = 1; r.meta.chan_id = c.ID;
-    r.meta.source = (s->cfg.det_variant == 1 && s->cfg.det_id >= 0 && s->segs.size() == 1) ? s->cfg.det_id : g.ID;
-    r.meta.finalized = fin; r.meta.part = c.part; r.meta.has_part = fin ? (c.part > 0) : 1;
-    r.meta.rel_bw = (double)c.extract_width / (double)s->N;
-    r.meta.rel_cfreq = (double)(c.extract_start + c.extract_stop) / 2.0 / (double)s->N;
-    // the vcm block counts from 1 (…vcm_impl.cc:188), SegmentDetection from 0 (SegmentDetection_impl.cc:118)
-    const int64_t bc = e.blockcount - (s->cfg.det_variant == 1 ? 1 : 0);
-    // blockcount - count in the counter's own type: the vcm block's is `unsigned int` (…vcm_impl.h:142), so a channel activated in
-    // the very first item (count 2 with the zero history, counter 1) publishes 4294967295, not -1; SegmentDetection's size_t
-    // difference comes out of pmt::from_long(long) as the signed value (SegmentDetection_impl.h:96)
-    r.meta.blockstart = s->cfg.det_variant == 1 ? bc - c.count : (int64_t)(uint32_t)(bc - c.count); r.meta.blockend = bc;
-    r.meta.vectorstart = c.extract_start; r.meta.vectorend = c.extract_stop;
-    std::snprintf(r.meta.id, sizeof r.meta.id, "%s", c.msg_id.c_str());
-    r.blocklen = c.outputsamples;
-    for (size_t i = 0; i < nblk; i++) { r.blocks.push_back(std::move(c.data.front())); c.data.pop_front(); }
-    if (s->cfg.verbose)                                                        // …vcm_impl.cc:441-450, :498-508
-        sink_log(s, s->det_logfile, c.msg_id + (fin ? std::string(".fin: ") : ".parted." + std::to_string(c.part) + ": ") + "start=" +
-                 std::to_string(c.extract_start) + ", stop=" + std::to_string(c.extract_stop) + ", blockstart=" +
-                 std::to_string((long long)r.meta.blockstart) + ", blockend=" + std::to_string((long long)r.meta.blockend));
-    e.pdus->push_back(std::move(r));
-}
-
-void seg_detect(fdc_sinks *s, Segment &g, const float *P)   // detect_channels, :617-628
-{
-    const int n = g.ncell, dec = s->dec;
-    // get_active_channels, :694-739
-    struct Edge { float r; int pos; };
-    std::vector<Edge> rise;
-    std::vector<int> fall;
-    const float inv = 1.0f / s->det_thr;
-    const bool sd = s->cfg.det_variant == 1;
-    for (int i = 1; i < n; i++) {
-        // vcm guards a zero denominator (:703-706); SegmentDetection divides as is (volk_32f_x2_divide_32f, :206)
-        const float pd = (!sd && P[i - 1] == 0.0f) ? P[i] / FLT_MIN : P[i] / P[i - 1];
-        if (pd > s->det_thr) rise.push_back({pd, (i - 1) * dec + g.start});
-        else if (sd) { if (pd < inv) fall.push_back(i * dec + g.start); }        // if / else if (:209-210)
-        if (!sd && pd < inv) fall.push_back(i * dec + g.start);                  // two independent ifs (:708-709)
-    }
-    std::stable_sort(rise.begin(), rise.end(), [](const Edge &a, const Edge &b) { return a.r > b.r; });   // :713
-    std::vector<std::pair<int, int>> cand;
-    for (const Edge &e : rise) {
-        int ne = -1;
-        for (int f : fall) if (f > e.pos) { ne = f; break; }                   // get_next_int, :678-692
-        if (ne <= e.pos) continue;
-        bool clash = false;
-        for (auto &a : cand) if (e.pos < a.second && ne >= a.first) { clash = true; break; }   // :727-734
-        if (!clash) cand.emplace_back(e.pos, ne);
-    }
-    // match_active_channels, :741-783
-    if (cand.empty()) {
-        for (auto &c : g.chans) c.inactive += 1;
-        return;
-    }
-    for (auto &c : g.chans) {
-        bool idle = true;
-        for (size_t i = 0; i < cand.size();) {
-            if (cand[i].first < c.detect_stop && cand[i].second >= c.detect_start) {
-                c.inactive = 0; idle = false;
-                cand.erase(cand.begin() + i);
-            } else i++;
-        }
-        if (idle) c.inactive += 1;
-    }
-    for (auto &pc : cand) {                                                    // activate, :785-841
-        const int dw = pc.second - pc.first, mid = pc.first + dw / 2;
-        const int ew = pow2ceil((int)std::ceil((double)dw * (1.0 + 2.0 * s->cfg.window_flank_puffer)));
-        if (ew > s->N) continue;                                               // logged and skipped in the reference
-        if (s->det_win_off[(size_t)std::lround(std::log2((double)ew))] < 0) continue;   // no window table for this width (see create)
-        int es = mid - ew / 2, ee = mid + ew / 2;
-        if (es < 0) { es = 0; ee = ew; }
-        if (ee > s->N) { ee = s->N; es = s->N - ew; }
-        DetChan c{};
-        c.ID = g.counter++;
-        c.detect_start = pc.first; c.detect_stop = pc.second; c.extract_start = es; c.extract_stop = ee;
-        c.extract_width = ew; c.wclass = (int)std::log2((double)ew);
-        c.ovlskip = ew / s->R; c.outputsamples = ew - c.ovlskip;
-        c.count = 0; c.phase = 0; c.phaseincrement = es % s->R; c.inactive = -1; c.part = 0;
-        const int segname = (s->cfg.det_variant == 1 && s->cfg.det_id >= 0 && s->segs.size() == 1) ? s->cfg.det_id : g.ID;
-        c.msg_id = current_time_string() + ".DETECTED." + std::to_string(segname) + "." + std::to_string(c.ID);
-        g.chans.push_back(std::move(c));
-    }
-}
-
-void seg_extract(fdc_sinks *s, Emit &e, Segment &g, int slot)        // extract_channels_in_segments_singlethread, :306-337
-{
-    const int mb = s->cfg.det_maxblocks, delay = s->cfg.det_deactivation_delay;
-    for (auto &c : g.chans) {
-        if (c.inactive < 0) { det_process(s, e, c, slot - 1); det_process(s, e, c, slot); c.inactive = 0; }   // :399-403
-        else if (c.inactive > delay) det_emit(s, e, g, c, true, c.data.size());
-        else det_process(s, e, c, slot);
-        if (s->cfg.det_variant == 0 && mb >= 0 && (int)c.data.size() >= mb) {  // :317-318, :454-470
-            const size_t ntx = mb == 0 ? c.data.size() : (size_t)mb;
-            if (ntx > 0) { det_emit(s, e, g, c, false, ntx); c.part++; }
-        }
-    }
-    if (s->cfg.det_variant == 1 && mb >= 0)                                     // SegmentDetection: separate pass, :359-362
-        for (auto &c : g.chans)
-            if ((int)c.data.size() >= mb) {
-                const size_t ntx = mb == 0 ? c.data.size() : (size_t)mb;
-                if (ntx > 0) { det_emit(s, e, g, c, false, ntx); c.part++; }
+            // above 4096 points (a carrier, or a run of merged carriers, over 1/16 of a 65536-bin band): the two-pass inverse transform,
+            // the whole class in batches of up to 64 Mi points — pass A reads slice * window straight from the spectrum (the half swap is
+            // its input rotation), pass B writes [skip, w) to the landing offsets.  The scratch between the passes follows the demand
+            // (batch x w points, grown geometrically), not the 64 Mi ceiling.  (One workgroup per 8192-point transform — 32 points per
+            // lane, two workgroups per compute unit — was slower than the two passes: 98 us for the 536 extractions of a configs[4] step;
+            // that class and the two above it took 271 us with a gathered copy and a scatter around the transform, 212 us this way.)
+            const size_t per = std::min(std::max<size_t>(1, ((size_t)64 << 20) / (size_t)w), j - i);
+            const size_t wcap = s->d_wide.capacity();
+            HIPCHK(s->d_wide.reserve(per * (size_t)w, std::min(std::max(per * (size_t)w, wcap * 2), std::max<size_t>((size_t)64 << 20, (size_t)w))));
+            const size_t fit = std::max<size_t>(1, s->d_wide.capacity() / (size_t)w);
+            for (size_t k0 = i; k0 < j; k0 += fit) {
+                const int n = (int)std::min(fit, j - k0);
+                HIPCHK(fdc::launch_extract_wide(s->d_spec, N, d_tasks + k0, n, w, skip, s->d_wins, s->d_wide, d_out, s->d_tw, N, q0));
             }
-    for (size_t i = 0; i < g.chans.size();)                                     // clear_inactive_channels, :512-524
-        if (g.chans[i].inactive > delay) g.chans.erase(g.chans.begin() + i); else i++;
+        }
+    }
+    if (side) for (int c = 1; c < nwide; c++) HIPCHK(hipStreamWaitEvent(q0, s->ev_join[c - 1], 0));    // the bank's stream goes on behind every class
+    return FDC_OK;
 }
+
+}}  // namespace fdc::sinks
+
+namespace {
 
 // ---------------------------------------------------------------- device engine: set-up
 // Which engine a bank gets, and the device-side tables and lists of the device engine.  Every list is allocated for its
@@ -579,16 +269,15 @@ int dev_setup(fdc_sinks *s)
     const int64_t bytes = ntask * (int64_t)(sizeof(fdc::SinkTask) + sizeof(fdc::ExtractTask)) + npdu * 2 * (int64_t)sizeof(fdc::SinkPdu) +
                           nown * (int64_t)sizeof(fdc::SinkOwner) + ncand * (int64_t)sizeof(int2);
     if (bytes > (2ll << 30)) return FDC_OK;
-#define DALLOC(ptr, n) HIPCHK(hipMalloc(reinterpret_cast<void **>(&(ptr)), std::max<size_t>(16, sizeof(*(ptr)) * (size_t)(n))))
-#define DUP(ptr, vec) do { DALLOC(ptr, (vec).size()); HIPCHK(hipMemcpy(ptr, (vec).data(), sizeof(*(ptr)) * (vec).size(), hipMemcpyHostToDevice)); } while (0)
+#define DALLOC(buf, n) HIPCHK((buf).alloc((size_t)(n)))
+#define DUP(buf, vec) HIPCHK((buf).upload(vec))
     DUP(d.d_task_base, d.task_base); DUP(d.d_pdu_base, d.pdu_base); DUP(d.d_owner_base, d.owner_base); DUP(d.d_cand_base, d.cand_base);
     DALLOC(d.d_ntask, d.nlist); DALLOC(d.d_npdu, d.nlist); DALLOC(d.d_nowner, nseg + 1); DALLOC(d.d_error, 1); DALLOC(d.d_class_fill, 32);
     HIPCHK(hipMemset(d.d_error, 0, sizeof(int32_t)));
     HIPCHK(hipMemset(d.d_nowner, 0, sizeof(int32_t) * (size_t)(nseg + 1)));
     DALLOC(d.d_tasks, ntask); DALLOC(d.d_sorted, ntask); DALLOC(d.d_pdus, npdu); DALLOC(d.d_pdus_out, std::max<int64_t>(npdu, kEagerPdus)); DALLOC(d.d_owners, nown);
     DALLOC(d.d_sum, 1);
-    HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&d.h_sum), sizeof(fdc::SinkSummary), hipHostMallocDefault));
-    HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&d.h_pdus), sizeof(fdc::SinkPdu) * kEagerPdus, hipHostMallocDefault));
+    DALLOC(d.h_sum, 1); DALLOC(d.h_pdus, kEagerPdus);
     if (npac) {
         std::vector<fdc::PacGeom> pg((size_t)npac);
         std::vector<fdc::PacState> ps((size_t)npac);
@@ -650,25 +339,13 @@ void fdc_sinks_destroy(fdc_sinks *s)
     if (s->s_fill) { (void)hipStreamSynchronize(s->s_fill); (void)hipStreamDestroy(s->s_fill); }
     for (hipStream_t q : {s->s_side[0], s->s_side[1], s->s_x}) if (q) { (void)hipStreamSynchronize(q); (void)hipStreamDestroy(q); }
     for (hipEvent_t e : {s->ev_fill, s->ev_ready, s->ev_ready_ahead, s->ev_fork, s->ev_join[0], s->ev_join[1], s->ev_tasks}) if (e) (void)hipEventDestroy(e);
-    (void)hipFree(s->d_spec_ahead); (void)hipFree(s->d_power_ahead); (void)hipFree(s->d_gpow); (void)hipFree(s->d_gpow_ahead);
-    (void)hipFree(s->d_spec); (void)hipFree(s->d_wins); (void)hipFree(s->d_tw); (void)hipFree(s->d_tw256); (void)hipFree(s->d_cells);
-    (void)hipFree(s->d_power); (void)hipFree(s->d_tasks); (void)hipFree(s->d_ext); (void)hipFree(s->d_wide);
-    if (s->h_ext) (void)hipHostFree(s->h_ext);
     {
         auto &d = s->dev;
         if (d.s_copy) { (void)hipStreamSynchronize(d.s_copy); (void)hipStreamDestroy(d.s_copy); }
         for (hipEvent_t e : {d.ev_decide, d.ev_extract[0], d.ev_extract[1], d.ev_copied[0], d.ev_copied[1]}) if (e) (void)hipEventDestroy(e);
-        for (void *q : {(void *)d.d_task_base, (void *)d.d_pdu_base, (void *)d.d_owner_base, (void *)d.d_cand_base, (void *)d.d_ntask,
-                        (void *)d.d_npdu, (void *)d.d_nowner, (void *)d.d_error, (void *)d.d_class_fill, (void *)d.d_ncand,
-                        (void *)d.d_winoff, (void *)d.d_live, (void *)d.d_live2, (void *)d.d_detch, (void *)d.d_live_off, (void *)d.d_cand, (void *)d.d_pgeom,
-                        (void *)d.d_pstate, (void *)d.d_dgeom, (void *)d.d_sst, (void *)d.d_tasks, (void *)d.d_pdus,
-                        (void *)d.d_pdus_out, (void *)d.d_owners, (void *)d.d_sorted, (void *)d.d_sum, (void *)d.d_land[0],
-                        (void *)d.d_land[1], d.d_nland[0], d.d_nland[1]})
-            (void)hipFree(q);
-        for (void *q : {(void *)d.h_sum, (void *)d.h_pdus, (void *)d.h_land[0], (void *)d.h_land[1], d.h_nland[0], d.h_nland[1]}) if (q) (void)hipHostFree(q);
     }
     if (s->stream) (void)hipStreamDestroy(s->stream);
-    delete s;
+    delete s;                                                  // the buffers go with it (fdc_buffers.hpp)
 }
 
 int fdc_sinks_create(const fdc_sinks_cfg *cfg, fdc_sinks **out)
@@ -820,10 +497,10 @@ int fdc_sinks_create(const fdc_sinks_cfg *cfg, fdc_sinks **out)
     HIPCHK(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
     fdc_sinks *raw = s.release();
 #define CHKF(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { int _r = fdc::set_error(_e == hipErrorOutOfMemory ? FDC_ERR_NOMEM : FDC_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(_e)); fdc_sinks_destroy(raw); return _r; } } while (0)
-    CHKF(hipMalloc(&raw->d_spec, sizeof(float2) * ((size_t)cfg->max_blocks + 1) * N));
+    CHKF(raw->d_spec.alloc(((size_t)cfg->max_blocks + 1) * N));
     CHKF(hipMemset(raw->d_spec, 0, sizeof(float2) * (size_t)N));            // zero history block (…cc:89 / :111)
     if (!pool.empty()) {
-        CHKF(hipMalloc(&raw->d_wins, sizeof(float2) * pool.size()));
+        CHKF(raw->d_wins.alloc(pool.size()));
         CHKF(hipMemcpy(raw->d_wins, pool.data(), sizeof(float2) * pool.size(), hipMemcpyHostToDevice));
     }
     {
@@ -832,25 +509,25 @@ int fdc_sinks_create(const fdc_sinks_cfg *cfg, fdc_sinks **out)
             const double a = -2.0 * M_PI * (double)k / (double)N;
             tw[k] = make_float2((float)std::cos(a), (float)std::sin(a));
         }
-        CHKF(hipMalloc(&raw->d_tw, sizeof(float2) * (size_t)N));
+        CHKF(raw->d_tw.alloc((size_t)N));
         CHKF(hipMemcpy(raw->d_tw, tw.data(), sizeof(float2) * (size_t)N, hipMemcpyHostToDevice));
         if (N >= 256) {                                                        // width-256 extractions run on the register kernel
             std::vector<float2> t256(256);
             for (int j = 0; j < 256; j++) t256[(size_t)j] = tw[(size_t)j * (size_t)(N / 256)];
-            CHKF(hipMalloc(&raw->d_tw256, sizeof(float2) * 256));
+            CHKF(raw->d_tw256.alloc(256));
             CHKF(hipMemcpy(raw->d_tw256, t256.data(), sizeof(float2) * 256, hipMemcpyHostToDevice));
         }
     }
     if (!raw->cells.empty()) {
-        CHKF(hipMalloc(&raw->d_cells, sizeof(fdc::PowerCell) * raw->cells.size()));
+        CHKF(raw->d_cells.alloc(raw->cells.size()));
         CHKF(hipMemcpy(raw->d_cells, raw->cells.data(), sizeof(fdc::PowerCell) * raw->cells.size(), hipMemcpyHostToDevice));
-        CHKF(hipMalloc(&raw->d_power, sizeof(float) * raw->cells.size() * (size_t)cfg->max_blocks));
+        CHKF(raw->d_power.alloc(raw->cells.size() * (size_t)cfg->max_blocks));
     }
-    if (!raw->cells.empty() && N >= 16) CHKF(hipMalloc(&raw->d_gpow, sizeof(float) * (size_t)cfg->max_blocks * (size_t)(N / 16)));
+    if (!raw->cells.empty() && N >= 16) CHKF(raw->d_gpow.alloc((size_t)cfg->max_blocks * (size_t)(N / 16)));
     if (cfg->flags & FDC_SINKS_LOOKAHEAD) {
-        if (raw->d_gpow) CHKF(hipMalloc(&raw->d_gpow_ahead, sizeof(float) * (size_t)cfg->max_blocks * (size_t)(N / 16)));
-        CHKF(hipMalloc(&raw->d_spec_ahead, sizeof(float2) * ((size_t)cfg->max_blocks + 1) * N));
-        if (!raw->cells.empty()) CHKF(hipMalloc(&raw->d_power_ahead, sizeof(float) * raw->cells.size() * (size_t)cfg->max_blocks));
+        if (raw->d_gpow) CHKF(raw->d_gpow_ahead.alloc((size_t)cfg->max_blocks * (size_t)(N / 16)));
+        CHKF(raw->d_spec_ahead.alloc(((size_t)cfg->max_blocks + 1) * N));
+        if (!raw->cells.empty()) CHKF(raw->d_power_ahead.alloc(raw->cells.size() * (size_t)cfg->max_blocks));
         CHKF(hipStreamCreateWithFlags(&raw->s_fill, hipStreamNonBlocking));
         CHKF(hipEventCreateWithFlags(&raw->ev_fill, hipEventDisableTiming));
         CHKF(hipEventCreateWithFlags(&raw->ev_ready, hipEventDisableTiming));
@@ -1004,401 +681,6 @@ int fdc_sinks_segment_params(const fdc_sinks *s, int i, int32_t *v)
     FDC_ENTRY_END
 }
 
-// Extractions of one call, one launch (or one gather / batched transform / scatter sequence) per width class.
-// tasks: grouped by class, class k (width 2^k) = [first[k], first[k] + cnt[k])
-// ---- FDC_SINKS_LOOKAHEAD (see the struct): what a batch does at its two ends
-// start of a batch: whatever its producer enqueued on the fill stream (forward transform, power cells) comes first
-static int batch_begin(fdc_sinks *s, int nblocks, bool *have_power)
-{
-    *have_power = false;
-    if (!s->s_fill) {
-        // one-buffer bank: fdc_sinks_prepare_from_groups has (enqueued, on this stream) the cells of exactly this batch
-        *have_power = s->prepared == nblocks;
-        s->prepared = -1;
-        return FDC_OK;
-    }
-    if (s->prepared == nblocks) {
-        // fdc_sinks_prepare marked the point of the fill stream where this batch is complete: what the producer has enqueued there SINCE
-        // (the next batch's transform) is not waited for — it is what runs beside this batch's decisions
-        HIPCHK(hipStreamWaitEvent(s->stream, s->ev_ready, 0));
-        *have_power = true;
-    } else {
-        HIPCHK(hipEventRecord(s->ev_fill, s->s_fill));          // no mark: everything enqueued on the fill stream so far
-        HIPCHK(hipStreamWaitEvent(s->stream, s->ev_fill, 0));
-    }
-    s->prepared = -1;
-    return FDC_OK;
-}
-// end of a batch (enqueued behind its last reader): history <- its last block (save_hist, PowerActivationChannel_impl.cc:173;
-// …vcm_impl.cc:571) — slot 0 of the buffer the NEXT batch is read from, which with look-ahead is the other one ...
-static int batch_end_history(fdc_sinks *s, int nblocks, hipStream_t q)
-{
-    const size_t N = (size_t)s->N;
-    float2 *const next = s->d_spec_ahead ? s->d_spec_ahead : s->d_spec;
-    HIPCHK(hipMemcpyAsync(next, s->d_spec + (size_t)nblocks * N, sizeof(float2) * N, hipMemcpyDeviceToDevice, q));
-    return FDC_OK;
-}
-// ... then the buffers swap, and the fill stream may overwrite this batch's buffer once `done` (an event on the bank's stream behind the
-// history copy; null: everything enqueued on it so far) has passed
-static int batch_end_swap(fdc_sinks *s, hipEvent_t done)
-{
-    if (!s->s_fill) return FDC_OK;
-    if (done) HIPCHK(hipStreamWaitEvent(s->s_fill, done, 0));
-    else { HIPCHK(hipEventRecord(s->ev_fill, s->stream)); HIPCHK(hipStreamWaitEvent(s->s_fill, s->ev_fill, 0)); }
-    std::swap(s->d_spec, s->d_spec_ahead);
-    std::swap(s->d_power, s->d_power_ahead);
-    std::swap(s->d_gpow, s->d_gpow_ahead);
-    std::swap(s->ev_ready, s->ev_ready_ahead);
-    s->prepared = s->prepared_ahead; s->prepared_ahead = -1;
-    return FDC_OK;
-}
-
-// narrow: the fused payload route (every task is of the 256-bin class): the emitted runs [0, used_a) go to it in the bank's payload format
-static int run_extractions(fdc_sinks *s, const fdc::ExtractTask *d_tasks, const size_t *first, const size_t *cnt, float2 *d_out, bool trace,
-                           hipStream_t q0 = nullptr, void *narrow = nullptr, long long used_a = 0)
-{
-    const int N = s->N;
-    if (!q0) q0 = s->stream;
-    // the classes that fit one workgroup's transform at 16 points per lane (w <= 4096; 256 has a kernel of its own) are independent and
-    // each fills a part of the device only: two or more of them go out as ONE launch
-    int mw[32], nm = 0;
-    size_t mfirst[32], mcnt[32];
-    for (int k = 0; k < 32; k++) {
-        const int w = 1 << k;
-        if (cnt[k] && w <= 4096 && !(w == 256 && s->d_tw256)) { mw[nm] = w; mfirst[nm] = first[k]; mcnt[nm] = cnt[k]; nm++; }
-    }
-    const bool multi = nm >= 2 && nm <= fdc::kMaxExtractClasses;
-    // side streams (look-ahead banks): two or three classes above 4096 points, each in one piece of its own slice of the scratch
-    int nwide = 0, wk[3] = {0, 0, 0};
-    size_t wneed = 0;
-    bool side = s->s_side[0] != nullptr;
-    for (int k = 13; k < 32 && side; k++)
-        if (cnt[k]) {
-            if (nwide == 3 || cnt[k] * ((size_t)1 << k) > ((size_t)64 << 20)) { side = false; break; }
-            wk[nwide++] = k; wneed += cnt[k] * ((size_t)1 << k);
-        }
-    side = side && nwide >= 2;
-    if (side) {
-        if (s->wide_cap < wneed) {
-            (void)hipFree(s->d_wide); s->d_wide = nullptr; s->wide_cap = 0;
-            HIPCHK(hipMalloc(&s->d_wide, sizeof(float2) * (wneed + wneed / 2)));
-            s->wide_cap = wneed + wneed / 2;
-        }
-        HIPCHK(hipEventRecord(s->ev_fork, q0));
-        size_t off = 0;
-        for (int c = 0; c < nwide; c++) {
-            const int k = wk[c], w = 1 << k;
-            hipStream_t q = c == 0 ? q0 : s->s_side[c - 1];
-            if (c) HIPCHK(hipStreamWaitEvent(q, s->ev_fork, 0));
-            if (c == 0 && multi)        // the classes up to 4096 points go first on the bank's own stream, the widest class behind them
-                HIPCHK(fdc::launch_extract_multi(s->d_spec, N, d_tasks, mw, mfirst, mcnt, nm, s->R, s->d_wins, d_out, s->d_tw, N, q0));
-            HIPCHK(fdc::launch_extract_wide(s->d_spec, N, d_tasks + first[k], (int)cnt[k], w, w / s->R, s->d_wins, s->d_wide + off, d_out, s->d_tw, N, q));
-            off += cnt[k] * (size_t)w;
-            if (c) HIPCHK(hipEventRecord(s->ev_join[c - 1], q));
-        }
-    } else if (multi) HIPCHK(fdc::launch_extract_multi(s->d_spec, N, d_tasks, mw, mfirst, mcnt, nm, s->R, s->d_wins, d_out, s->d_tw, N, q0));
-    for (int k = 0; k < 32; k++) {
-        if (!cnt[k]) continue;
-        const int w = 1 << k, skip = w / s->R;
-        const size_t i = first[k], j = first[k] + cnt[k];
-        if (trace) std::fprintf(stderr, "[fdc_sinks]     width %d: %zu tasks\n", w, j - i);
-        if (multi && w <= 4096 && !(w == 256 && s->d_tw256)) continue;
-        if (side && w > 4096) continue;
-        if (w == 256 && s->d_tw256 && narrow) {
-            HIPCHK(fdc::launch_extract256_narrow(s->pay_fmt, s->pay_scale, s->d_spec, N, d_tasks + i, (int)(j - i), skip, s->d_wins, d_out, narrow, used_a,
-                                                 s->d_tw256, q0));
-        } else if (w == 256 && s->d_tw256) {
-            HIPCHK(fdc::launch_extract256(s->d_spec, N, d_tasks + i, (int)(j - i), skip, s->d_wins, d_out, s->d_tw256, q0));
-        } else if (w <= 4096) {
-            HIPCHK(fdc::launch_extract(s->d_spec, N, d_tasks + i, (int)(j - i), w, skip, s->d_wins, d_out, s->d_tw, N, q0));
-        } else {
-            // above 4096 points (a carrier, or a run of merged carriers, over 1/16 of a 65536-bin band): the two-pass inverse transform,
-            // the whole class in batches of up to 64 Mi points — pass A reads slice * window straight from the spectrum (the half swap is
-            // its input rotation), pass B writes [skip, w) to the landing offsets.  The scratch between the passes follows the demand
-            // (batch x w points, grown geometrically), not the 64 Mi ceiling.  (One workgroup per 8192-point transform — 32 points per
-            // lane, two workgroups per compute unit — was slower than the two passes: 98 us for the 536 extractions of a configs[4] step;
-            // that class and the two above it took 271 us with a gathered copy and a scatter around the transform, 212 us this way.)
-            const size_t per = std::min(std::max<size_t>(1, ((size_t)64 << 20) / (size_t)w), j - i);
-            if (s->wide_cap < per * (size_t)w) {
-                const size_t want = std::min(std::max(per * (size_t)w, s->wide_cap * 2), std::max<size_t>((size_t)64 << 20, (size_t)w));
-                (void)hipFree(s->d_wide); s->d_wide = nullptr; s->wide_cap = 0;
-                HIPCHK(hipMalloc(&s->d_wide, sizeof(float2) * want));
-                s->wide_cap = want;
-            }
-            const size_t fit = std::max<size_t>(1, s->wide_cap / (size_t)w);
-            for (size_t k0 = i; k0 < j; k0 += fit) {
-                const int n = (int)std::min(fit, j - k0);
-                HIPCHK(fdc::launch_extract_wide(s->d_spec, N, d_tasks + k0, n, w, skip, s->d_wins, s->d_wide, d_out, s->d_tw, N, q0));
-            }
-        }
-    }
-    if (side) for (int c = 1; c < nwide; c++) HIPCHK(hipStreamWaitEvent(q0, s->ev_join[c - 1], 0));    // the bank's stream goes on behind every class
-    return FDC_OK;
-}
-
-static int host_work_device(fdc_sinks *s, int nblocks)
-{
-    static const bool trace = fdc::debug_env("FDC_SINKS_TRACE") != nullptr;      // phase times on stderr (diagnostics)
-    auto now = [] { return std::chrono::steady_clock::now(); };
-    auto t0 = now();
-    auto lap = [&](const char *what) {
-        if (!trace) return;
-        const auto t1 = now();
-        std::fprintf(stderr, "[fdc_sinks] %-22s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(t1 - t0).count());
-        t0 = t1;
-    };
-    s->pdus.clear();
-    lap("previous PDUs released");
-    bool pool_ok = true;
-    const int N = s->N, ncells = (int)s->cells.size();
-    // phase 1: power of every cell of every block
-    bool have_power = false;
-    { const int rb = batch_begin(s, nblocks, &have_power); if (rb != FDC_OK) return rb; }
-    if (ncells) {
-        if (!have_power) HIPCHK(fdc::launch_cell_power(s->d_spec + N, N, s->d_cells, ncells, nblocks, s->d_power, s->stream));
-        s->h_power.resize((size_t)ncells * nblocks);
-        HIPCHK(hipMemcpyAsync(s->h_power.data(), s->d_power, sizeof(float) * s->h_power.size(), hipMemcpyDeviceToHost, s->stream));
-        HIPCHK(hipStreamSynchronize(s->stream));
-    }
-    lap("cell power + D2H");
-    // phase 2: decisions (work() loops of both reference blocks).  Every block: the PowerActivationChannels in order, then the
-    // detection segments.  PowerActivationChannel instances do not interact, so a large bank is cut into ranges that worker
-    // threads run over the whole batch on their own; the PDUs carry an order key (block, then instance) and are put back
-    // into the order the sequential loop emits them in.
-    s->tasks.clear(); s->task_w.clear(); s->task_skip.clear(); s->ext_used = 0;
-    const int64_t bc0 = s->blockcount;
-    const int npac = (int)s->pacs.size();
-    int nthr = 1;
-    if (npac >= 32 && (int64_t)npac * nblocks >= 16384 && s->cfg.verbose == 0) {
-        const unsigned hc = std::thread::hardware_concurrency();
-        nthr = (int)std::min<unsigned>(8, std::max<unsigned>(1, hc / 2));
-        if (s->host_threads > 0) nthr = s->host_threads;
-        nthr = std::min(nthr, npac / 8);
-    }
-    auto run_pacs = [&](int a, int b, Emit e) {
-        for (int m = 0; m < nblocks; m++) {
-            const float *P = s->h_power.data() + (size_t)m * ncells;
-            e.blockcount = bc0 + m;
-            for (int i = a; i < b; i++) {
-                e.key = ((int64_t)m << 24) | i;
-                pac_step(s, e, s->pacs[(size_t)i], P[s->pacs[(size_t)i].cell], m + 1);
-            }
-        }
-    };
-    // the workers' form: one channel at a time over the whole batch (its state stays in registers, its tasks are appended in
-    // one run); the PDUs find their place through the order key, the tasks through the landing layout
-    auto run_pacs_by_channel = [&](int a, int b, Emit e) {
-        const float *P0 = s->h_power.data();
-        for (int i = a; i < b; i++) {
-            Pac &p = s->pacs[(size_t)i];
-            const float *P = P0 + p.cell;
-            for (int m = 0; m < nblocks; m++) {
-                e.blockcount = bc0 + m;
-                e.key = ((int64_t)m << 24) | i;
-                pac_step(s, e, p, P[(size_t)m * ncells], m + 1);
-            }
-        }
-    };
-    Emit em{&s->tasks, &s->task_w, &s->task_skip, &s->ext_used, &s->pdus, bc0, 0};
-    if (nthr > 1) {
-        while ((int)s->wl.size() < nthr) s->wl.emplace_back(new WorkerLists());
-        std::vector<int> lo((size_t)nthr + 1);
-        for (int t = 0; t <= nthr; t++) lo[(size_t)t] = (int)((int64_t)npac * t / nthr);
-        std::vector<double> tms((size_t)nthr, 0.0);
-        pool_ok = s->pool.run(nthr, [&](int t) {
-            const auto a0 = now();
-            WorkerLists &L = *s->wl[(size_t)t];
-            L.clear();
-            run_pacs_by_channel(lo[(size_t)t], lo[(size_t)t + 1], Emit{&L.tasks, &L.w, &L.skip, &L.used, &L.pdus, bc0, 0});
-            tms[(size_t)t] = std::chrono::duration<double, std::milli>(now() - a0).count();
-        });
-        if (trace) { std::fprintf(stderr, "[fdc_sinks]     worker ms:"); for (double v : tms) std::fprintf(stderr, " %.3f", v); std::fprintf(stderr, "\n"); }
-        lap("  PAC state machines (threads)");
-        // merge: task indices of a worker move up by the number of tasks in front of them (live channels and PDUs alike);
-        // every worker moves its own lists into place
-        std::vector<int64_t> base((size_t)nthr + 1, (int64_t)s->tasks.size());
-        for (int t = 0; t < nthr; t++) {
-            base[(size_t)t + 1] = base[(size_t)t] + (int64_t)s->wl[(size_t)t]->tasks.size();
-            s->ext_used += s->wl[(size_t)t]->used;
-        }
-        s->tasks.resize((size_t)base[(size_t)nthr]); s->task_w.resize((size_t)base[(size_t)nthr]); s->task_skip.resize((size_t)base[(size_t)nthr]);
-        pool_ok = s->pool.run(nthr, [&](int t) {
-            WorkerLists &L = *s->wl[(size_t)t];
-            const int64_t b0 = base[(size_t)t];
-            std::copy(L.tasks.begin(), L.tasks.end(), s->tasks.begin() + b0);
-            std::copy(L.w.begin(), L.w.end(), s->task_w.begin() + b0);
-            std::copy(L.skip.begin(), L.skip.end(), s->task_skip.begin() + b0);
-            if (b0) {
-                for (auto &r : L.pdus) for (auto &bk : r.blocks) if (bk.task >= 0) bk.task += b0;
-                for (int i = lo[(size_t)t]; i < lo[(size_t)t + 1]; i++)
-                    for (auto &bk : s->pacs[(size_t)i].blocks) if (bk.task >= 0) bk.task += b0;
-            }
-        });
-        for (int t = 0; t < nthr; t++)
-            for (auto &r : s->wl[(size_t)t]->pdus) s->pdus.push_back(std::move(r));
-    } else if (npac) {
-        run_pacs(0, npac, em);
-    }
-    lap("  PAC total incl. merge");
-    const int nseg = (int)s->segs.size();
-    const int nthr_s = (nseg >= 2 && (int64_t)nseg * nblocks >= 256 && s->cfg.verbose == 0) ? std::min(nseg, 8) : 1;
-    if (nthr_s > 1) {
-        // The segments of a detection block do not interact either (…vcm_impl.cc:558-562 loops over them per item): a worker
-        // takes whole segments through the batch; the order key (block, then segment, then emission) restores the reference's order.
-        while ((int)s->wl.size() < nthr_s) s->wl.emplace_back(new WorkerLists());
-        pool_ok = s->pool.run(nthr_s, [&](int t) {
-            WorkerLists &L = *s->wl[(size_t)t];
-            L.clear();
-            Emit e{&L.tasks, &L.w, &L.skip, &L.used, &L.pdus, bc0, 0};
-            for (int gi = t; gi < nseg; gi += nthr_s) {
-                Segment &g = s->segs[(size_t)gi];
-                for (int m = 0; m < nblocks; m++) {
-                    e.blockcount = bc0 + m;
-                    e.key = ((int64_t)m << 24) | (1 << 23) | ((int64_t)gi << 12);
-                    seg_detect(s, g, s->h_power.data() + (size_t)m * ncells + g.cell0);
-                    seg_extract(s, e, g, m + 1);
-                }
-            }
-        });
-        std::vector<int64_t> base((size_t)nthr_s + 1, (int64_t)s->tasks.size());
-        for (int t = 0; t < nthr_s; t++) {
-            base[(size_t)t + 1] = base[(size_t)t] + (int64_t)s->wl[(size_t)t]->tasks.size();
-            s->ext_used += s->wl[(size_t)t]->used;
-        }
-        s->tasks.resize((size_t)base[(size_t)nthr_s]); s->task_w.resize((size_t)base[(size_t)nthr_s]); s->task_skip.resize((size_t)base[(size_t)nthr_s]);
-        pool_ok = s->pool.run(nthr_s, [&](int t) {
-            WorkerLists &L = *s->wl[(size_t)t];
-            const int64_t b0 = base[(size_t)t];
-            std::copy(L.tasks.begin(), L.tasks.end(), s->tasks.begin() + b0);
-            std::copy(L.w.begin(), L.w.end(), s->task_w.begin() + b0);
-            std::copy(L.skip.begin(), L.skip.end(), s->task_skip.begin() + b0);
-            if (b0) {
-                for (auto &r : L.pdus) for (auto &bk : r.blocks) if (bk.task >= 0) bk.task += b0;
-                for (int gi = t; gi < nseg; gi += nthr_s)
-                    for (auto &c : s->segs[(size_t)gi].chans) for (auto &bk : c.data) if (bk.task >= 0) bk.task += b0;
-            }
-        });
-        for (int t = 0; t < nthr_s; t++)
-            for (auto &r : s->wl[(size_t)t]->pdus) s->pdus.push_back(std::move(r));
-    } else if (nseg)
-        for (int m = 0; m < nblocks; m++) {
-            const float *P = s->h_power.data() + (size_t)m * ncells;
-            em.blockcount = bc0 + m;
-            em.key = ((int64_t)m << 24) | (1 << 23);
-            for (auto &g : s->segs) seg_detect(s, g, P + g.cell0);                  // …vcm_impl.cc:558
-            for (auto &g : s->segs) seg_extract(s, em, g, m + 1);                   // :562
-        }
-    s->blockcount = bc0 + nblocks;
-    if (!pool_ok) return fdc::set_error(FDC_ERR_NOMEM, "a decision worker failed (out of memory?): the batch is lost");
-    if ((npac && (nthr > 1 || nseg)) || nthr_s > 1)
-        std::stable_sort(s->pdus.begin(), s->pdus.end(), [](const PduRec &a, const PduRec &b) { return a.key < b.key; });
-    lap("decisions (host)");
-    // Landing layout: the blocks of every PDU emitted in this call sit one behind the other (PDU order, block order),
-    // so a PDU whose blocks all come from this call needs no assembly — its payload IS a run of the landing buffer;
-    // blocks that stay buffered in live channels follow.
-    {
-        std::vector<int64_t> noff(s->tasks.size(), -1);
-        int64_t pos = 0;
-        for (auto &r : s->pdus)
-            for (auto &b : r.blocks)
-                if (b.task >= 0) { noff[(size_t)b.task] = pos; pos += r.blocklen; }
-        for (size_t i = 0; i < s->tasks.size(); i++)
-            if (noff[i] < 0) { noff[i] = pos; pos += s->task_w[i] - s->task_skip[i]; }
-        for (size_t i = 0; i < s->tasks.size(); i++) s->tasks[i].out_off = noff[i];
-    }
-    // phase 3: extractions, one launch per width class
-    const size_t nt = s->tasks.size();
-    if (nt) {
-        // tasks grouped by width: a counting sort over the (at most 25) power-of-two classes, order inside a class kept;
-        // nothing to do when every task has the same width (a PowerActivationChannel bank of equal channels)
-        size_t cnt[32] = {0}, first[32];
-        for (size_t i = 0; i < nt; i++) cnt[31 - __builtin_clz((unsigned)s->task_w[i])]++;
-        size_t acc = 0;
-        int nclasses = 0;
-        for (int k = 0; k < 32; k++) { first[k] = acc; acc += cnt[k]; nclasses += cnt[k] != 0; }
-        const fdc::ExtractTask *upload = s->tasks.data();
-        if (nclasses > 1) {
-            s->sorted.resize(nt);
-            size_t pos[32];
-            std::copy(first, first + 32, pos);
-            for (size_t i = 0; i < nt; i++) s->sorted[pos[31 - __builtin_clz((unsigned)s->task_w[i])]++] = s->tasks[i];
-            upload = s->sorted.data();
-        }
-        if (nt > s->cap_tasks) {
-            (void)hipFree(s->d_tasks); s->d_tasks = nullptr; s->cap_tasks = 0;
-            HIPCHK(hipMalloc(&s->d_tasks, sizeof(fdc::ExtractTask) * nt * 2));
-            s->cap_tasks = nt * 2;
-        }
-        if ((size_t)s->ext_used > s->cap_hext) {
-            if (s->h_ext) (void)hipHostFree(s->h_ext);
-            s->h_ext = nullptr; s->cap_hext = 0;
-            HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&s->h_ext), sizeof(cfl) * (size_t)s->ext_used * 2, hipHostMallocDefault));
-            s->cap_hext = (size_t)s->ext_used * 2;
-        }
-        if ((size_t)s->ext_used > s->cap_ext) {
-            (void)hipFree(s->d_ext); s->d_ext = nullptr; s->cap_ext = 0;
-            HIPCHK(hipMalloc(&s->d_ext, sizeof(float2) * (size_t)s->ext_used * 2));
-            s->cap_ext = (size_t)s->ext_used * 2;
-        }
-        lap("  task grouping + buffers");
-        HIPCHK(hipMemcpyAsync(s->d_tasks, upload, sizeof(fdc::ExtractTask) * nt, hipMemcpyHostToDevice, s->stream));
-        {
-            const int rce = run_extractions(s, s->d_tasks, first, cnt, s->d_ext, trace);
-            if (rce != FDC_OK) return rce;
-        }
-        if (trace) { HIPCHK(hipStreamSynchronize(s->stream)); lap("  task upload + extraction kernels"); }
-        HIPCHK(hipMemcpyAsync(s->h_ext, s->d_ext, sizeof(float2) * (size_t)s->ext_used, hipMemcpyDeviceToHost, s->stream));
-    }
-    // history <- last block of this call (save_hist, PowerActivationChannel_impl.cc:173; …vcm_impl.cc:571)
-    { const int rh = batch_end_history(s, nblocks, s->stream); if (rh != FDC_OK) return rh; }
-    HIPCHK(hipStreamSynchronize(s->stream));
-    { const int rh = batch_end_swap(s, nullptr); if (rh != FDC_OK) return rh; }
-    lap("extractions + D2H");
-    // phase 4: payloads; blocks still buffered in live channels become host copies
-    auto resolve = [&](BlockRef &b, int len) {
-        if (b.task >= 0) {
-            const cfl *src = s->h_ext + s->tasks[(size_t)b.task].out_off;
-            b.owned.assign(src, src + len);
-            b.task = -1;
-        }
-    };
-    auto finish_pdu = [&](PduRec &r) {
-        bool all_here = !r.blocks.empty();
-        for (auto &b : r.blocks) if (b.task < 0) { all_here = false; break; }
-        if (all_here) {                     // contiguous in the landing buffer by construction (layout above)
-            r.meta.nsamples = (int64_t)r.blocks.size() * r.blocklen;
-            r.meta.samples = s->h_ext + s->tasks[(size_t)r.blocks.front().task].out_off;
-        } else {                            // some blocks were kept from an earlier call: assemble
-            r.payload.reserve(r.blocks.size() * (size_t)r.blocklen);
-            for (auto &b : r.blocks) {
-                const cfl *src = b.task >= 0 ? s->h_ext + s->tasks[(size_t)b.task].out_off : b.owned.data();
-                r.payload.insert(r.payload.end(), src, src + r.blocklen);
-            }
-            r.meta.nsamples = (int64_t)r.payload.size();
-            r.meta.samples = r.payload.data();
-        }
-        r.blocks.clear();
-    };
-    // PDUs and live channels are independent of each other: a large bank is finished by the worker threads
-    const int npdu = (int)s->pdus.size();
-    const int nasm = std::max(nthr, nthr_s);
-    if (nasm > 1 && (npdu >= 64 || npac >= 64)) {
-        pool_ok = s->pool.run(nasm, [&](int t) {
-            for (int i = (int)((int64_t)npdu * t / nasm), e = (int)((int64_t)npdu * (t + 1) / nasm); i < e; i++) finish_pdu(s->pdus[(size_t)i]);
-            for (int i = (int)((int64_t)npac * t / nasm), e = (int)((int64_t)npac * (t + 1) / nasm); i < e; i++)
-                for (auto &b : s->pacs[(size_t)i].blocks) resolve(b, s->pacs[(size_t)i].output_len);
-        });
-    } else {
-        for (auto &r : s->pdus) finish_pdu(r);
-        for (auto &p : s->pacs) for (auto &b : p.blocks) resolve(b, p.output_len);
-    }
-    for (auto &g : s->segs) for (auto &c : g.chans) for (auto &b : c.data) resolve(b, c.outputsamples);
-    if (!pool_ok) return fdc::set_error(FDC_ERR_NOMEM, "a payload worker failed (out of memory?): the batch is lost");
-    lap("payload assembly");
-    if (trace) std::fprintf(stderr, "[fdc_sinks] %zu tasks, %lld samples extracted, %zu PDUs\n", nt, (long long)s->ext_used, s->pdus.size());
-    return nblocks;
-}
-
 // ---------------------------------------------------------------- device engine: a call
 // dev_enqueue(): power cells, decision kernels, layout — nothing here waits for the device.  dev_launch_extractions(): needs
 // the summary of the layout kernel (buffer sizes, tasks per width class) on the host, then enqueues the rest: placement of the
@@ -1460,7 +742,7 @@ static int dev_launch_extractions(fdc_sinks *s, int nblocks)
         return fdc::set_error(FDC_ERR_UNSUPPORTED, "detection: more than %d live channels in one segment", fdc::kDetMaxCells);
     }
     d.sum[b] = sum;
-    d.recs[b].assign(d.h_pdus, d.h_pdus + std::min(sum.npdu, kEagerPdus));
+    d.recs[b].assign(d.h_pdus.get(), d.h_pdus.get() + std::min(sum.npdu, kEagerPdus));
     if (sum.npdu > kEagerPdus) {
         d.recs[b].resize((size_t)sum.npdu);
         HIPCHK(hipMemcpyAsync(d.recs[b].data() + kEagerPdus, d.d_pdus_out + kEagerPdus, sizeof(fdc::SinkPdu) * (size_t)(sum.npdu - kEagerPdus),
@@ -1470,12 +752,9 @@ static int dev_launch_extractions(fdc_sinks *s, int nblocks)
     const bool devpay = (s->cfg.flags & FDC_SINKS_DEVICE_PAYLOAD) != 0;
     // the buffer last held call k-2: its copy to the host was waited for when that call was completed, its buffered blocks were
     // moved on by call k-1 (enqueued; hipFree waits for the device)
-    if ((size_t)sum.used_total > d.cap_land[b]) {
-        const size_t want = std::max<size_t>((size_t)sum.used_total * 3 / 2, (size_t)1 << 16);
-        (void)hipFree(d.d_land[b]); d.d_land[b] = nullptr; d.cap_land[b] = 0;
-        HIPCHK(hipMalloc(reinterpret_cast<void **>(&d.d_land[b]), sizeof(float2) * want));
-        d.cap_land[b] = want;
-    }
+    // grown to 3/2 of the demand, at least 64 Ki samples
+    auto roomy = [](size_t n) { return std::max<size_t>(n * 3 / 2, (size_t)1 << 16); };
+    HIPCHK(d.d_land[b].reserve((size_t)sum.used_total, roomy((size_t)sum.used_total)));
     // Payload format (fdc_sinks_set_payload_format).  FUSED: every extraction of the batch is of the 256-bin class, whose kernel has narrow stores — it and
     // the move of the buffered blocks write the emitted runs narrow themselves, and [0, used_a) of the float buffer is never written: nothing reads it (the
     // payload comes from the narrow buffer, and what the NEXT batch moves on lies at prev_off = tail_off / live_off = an owner's b_off, k_sink_layout: always
@@ -1487,26 +766,10 @@ static int dev_launch_extractions(fdc_sinks *s, int nblocks)
     bool fused = fmt != fdc::kIqFloat && s->d_tw256 != nullptr && (sum.class_cnt[8] > 0 || s->pay_all256);
     for (int k = 0; k < 32 && fused; k++) if (k != 8 && sum.class_cnt[k]) fused = false;
     d.fmt_of[b] = fmt; d.route_of[b] = fmt == fdc::kIqFloat ? 0 : fused ? 2 : 1;
-    if (fmt != fdc::kIqFloat && (size_t)sum.used_a * sbytes > d.cap_nland[b]) {
-        const size_t want = std::max<size_t>((size_t)sum.used_a * 3 / 2, (size_t)1 << 16) * sbytes;
-        (void)hipFree(d.d_nland[b]); d.d_nland[b] = nullptr; d.cap_nland[b] = 0;
-        HIPCHK(hipMalloc(&d.d_nland[b], want));
-        d.cap_nland[b] = want;
-    }
-    if (fmt != fdc::kIqFloat && !devpay && (size_t)sum.used_a * sbytes > d.cap_hnland[b]) {
-        const size_t want = std::max<size_t>((size_t)sum.used_a * 3 / 2, (size_t)1 << 16) * sbytes;
-        if (d.h_nland[b]) (void)hipHostFree(d.h_nland[b]);
-        d.h_nland[b] = nullptr; d.cap_hnland[b] = 0;
-        HIPCHK(hipHostMalloc(&d.h_nland[b], want, hipHostMallocDefault));
-        d.cap_hnland[b] = want;
-    }
-    if (fmt == fdc::kIqFloat && !devpay && (size_t)sum.used_a > d.cap_hland[b]) {
-        const size_t want = std::max<size_t>((size_t)sum.used_a * 3 / 2, (size_t)1 << 16);
-        if (d.h_land[b]) (void)hipHostFree(d.h_land[b]);
-        d.h_land[b] = nullptr; d.cap_hland[b] = 0;
-        HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&d.h_land[b]), sizeof(cfl) * want, hipHostMallocDefault));
-        d.cap_hland[b] = want;
-    }
+    const size_t used_a = (size_t)sum.used_a;
+    if (fmt != fdc::kIqFloat) HIPCHK(d.d_nland[b].reserve(used_a * sbytes, roomy(used_a) * sbytes));
+    if (fmt != fdc::kIqFloat && !devpay) HIPCHK(d.h_nland[b].reserve(used_a * sbytes, roomy(used_a) * sbytes));
+    if (fmt == fdc::kIqFloat && !devpay) HIPCHK(d.h_land[b].reserve(used_a, roomy(used_a)));
     // look-ahead banks: the extractions run on their own stream.  The batch before's may still be at work there: its landing buffer (the
     // buffered blocks move on from it) and the sorted task list (about to be rewritten) are its to read until it is done
     hipStream_t qx = s->s_x ? s->s_x : s->stream;
@@ -1542,7 +805,7 @@ static int dev_launch_extractions(fdc_sinks *s, int nblocks)
     if (sum.ntask) {
         size_t first[32], cnt[32];
         for (int k = 0; k < 32; k++) { first[k] = (size_t)sum.class_base[k]; cnt[k] = (size_t)sum.class_cnt[k]; }
-        const int rce = run_extractions(s, d.d_sorted, first, cnt, d.d_land[b], trace, qx, fused ? d.d_nland[b] : nullptr, (long long)sum.used_a);
+        const int rce = run_extractions(s, d.d_sorted, first, cnt, d.d_land[b], trace, qx, fused ? d.d_nland[b].get() : nullptr, (long long)sum.used_a);
         if (rce != FDC_OK) return rce;
     }
     if (fmt != fdc::kIqFloat && !fused) HIPCHK(fdc::launch_complex_to_iq(fmt, s->pay_scale, d.d_land[b], d.d_nland[b], (size_t)sum.used_a, qx));
@@ -1590,8 +853,9 @@ static int dev_build(fdc_sinks *s, int b)
     std::sort(order.begin(), order.end());
     const bool narrow = d.fmt_of[b] != fdc::kIqFloat;       // the narrow landing buffers: same sample offsets, their own sample size
     const size_t sbytes = fdc::iq_bytes(d.fmt_of[b]);
-    const char *base = devpay ? static_cast<const char *>(narrow ? d.d_nland[b] : (void *)d.d_land[b])
-                              : static_cast<const char *>(narrow ? d.h_nland[b] : (void *)d.h_land[b]);
+    const void *const land = devpay ? (narrow ? (void *)d.d_nland[b].get() : (void *)d.d_land[b].get())
+                                    : (narrow ? (void *)d.h_nland[b].get() : (void *)d.h_land[b].get());
+    const char *base = static_cast<const char *>(land);
     s->pdus.resize(recs.size());
     time_t last_t = (time_t)-1;
     char tbuf[40] = "";
@@ -1603,7 +867,7 @@ static int dev_build(fdc_sinks *s, int b)
         fdc_pdu &m = o.meta;
         m = fdc_pdu{};
         const bool det = (r.flags >> 16) & 1;
-        const int64_t blk = r.key >> 40;                       // block index inside the batch
+        const int64_t blk = r.key >> fdc::kKeyShiftDev;        // block index inside the batch
         int width, vstart, vend;
         if (!det) {
             const Pac &p = s->pacs[(size_t)r.owner];
@@ -1612,7 +876,7 @@ static int dev_build(fdc_sinks *s, int b)
             m.kind = 0; m.source = p.ID; m.has_part = 1;
             m.blockend = d.bc0[b] + blk;                       // blockcount while the item is processed (:226-227)
         } else {
-            const int sgi = (int)((r.key >> 28) & 0x7FF);
+            const int sgi = (int)((r.key >> fdc::kKeySegShiftDev) & 0x7FF);
             width = 1 << ((r.flags >> 8) & 0xFF); vstart = r.vstart; vend = vstart + width;
             m.kind = 1;
             m.source = (sd && s->cfg.det_id >= 0 && s->segs.size() == 1) ? s->cfg.det_id : s->segs[(size_t)sgi].ID;
@@ -1654,6 +918,19 @@ static int dev_build(fdc_sinks *s, int b)
     return d.nb_of[b];
 }
 
+// What every batch entry checks first: the handle, that it is alive, the batch size (`what` names the argument in the message), and
+// where `flags` ask for it that no submitted batch is in flight and that no batch prepared ahead has its decisions enqueued.
+enum { kNotInFlight = 1, kNotEager = 2 };
+static int batch_entry_check(const fdc_sinks *s, const char *what, int n, int flags)
+{
+    if (!s) return fdc::set_error(FDC_ERR_INVALID_ARGUMENT, "null handle");
+    FDC_DEAD_CHECK(s);
+    if (n < 0 || n > s->cfg.max_blocks) return fdc::set_error(FDC_ERR_INVALID_ARGUMENT, "%s %d outside [0, max_blocks]", what, n);
+    if ((flags & kNotInFlight) && s->dev.on && s->dev.inflight) return fdc::set_error(FDC_ERR_INVALID_ARGUMENT, "a submitted batch is in flight: fdc_sinks_flush() first");
+    if ((flags & kNotEager) && s->dev.eager_n > 0) return fdc::set_error(FDC_ERR_INVALID_ARGUMENT, "a batch prepared ahead has its decisions enqueued: submit it before feeding the bank from the host");
+    return FDC_OK;
+}
+
 // rc < 0 from a step that may have advanced the bank's state: the handle is dead (see fdc_sinks::poisoned)
 static int poison(fdc_sinks *s, int rc)
 {
@@ -1673,9 +950,7 @@ static int dev_complete(fdc_sinks *s, int b)
 int fdc_sinks_submit_device(fdc_sinks *s, int nblocks)
 {
     FDC_ENTRY("fdc_sinks_submit_device")
-    if (!s) return fdc::set_error(FDC_ERR_INVALID_ARGUMENT, "null handle");
-    FDC_DEAD_CHECK(s);
-    if (nblocks < 0 || nblocks > s->cfg.max_blocks) return fdc::set_error(FDC_ERR_INVALID_ARGUMENT, "nblocks %d outside [0, max_blocks]", nblocks);
+    { const int rc0 = batch_entry_check(s, "nblocks", nblocks, 0); if (rc0 != FDC_OK) return rc0; }
     if (!s->dev.on) {                                          // host engine: the batch is done when the call returns
         if (nblocks == 0) { s->pdus.clear(); return 0; }
         HIPCHK(hipSetDevice(s->cfg.device_id));
@@ -1763,10 +1038,7 @@ int32_t fdc_sinks_payload_route(const fdc_sinks *s) { return s ? s->pay_route : 
 int fdc_sinks_work_device(fdc_sinks *s, int nblocks)
 {
     FDC_ENTRY("fdc_sinks_work_device")
-    if (!s) return fdc::set_error(FDC_ERR_INVALID_ARGUMENT, "null handle");
-    FDC_DEAD_CHECK(s);
-    if (nblocks < 0 || nblocks > s->cfg.max_blocks) return fdc::set_error(FDC_ERR_INVALID_ARGUMENT, "nblocks %d outside [0, max_blocks]", nblocks);
-    if (s->dev.on && s->dev.inflight) return fdc::set_error(FDC_ERR_INVALID_ARGUMENT, "a submitted batch is in flight: fdc_sinks_flush() first");
+    { const int rc0 = batch_entry_check(s, "nblocks", nblocks, kNotInFlight); if (rc0 != FDC_OK) return rc0; }
     if (nblocks == 0) { s->pdus.clear(); return 0; }
     HIPCHK(hipSetDevice(s->cfg.device_id));
     if (!s->dev.on) return poison(s, host_work_device(s, nblocks));
@@ -1780,11 +1052,7 @@ int fdc_sinks_work_device(fdc_sinks *s, int nblocks)
 int fdc_sinks_work(fdc_sinks *s, const void *spectrum, int nitems)
 {
     FDC_ENTRY("fdc_sinks_work")
-    if (!s) return fdc::set_error(FDC_ERR_INVALID_ARGUMENT, "null handle");
-    FDC_DEAD_CHECK(s);
-    if (nitems < 0 || nitems > s->cfg.max_blocks) return fdc::set_error(FDC_ERR_INVALID_ARGUMENT, "nitems %d outside [0, max_blocks]", nitems);
-    if (s->dev.on && s->dev.inflight) return fdc::set_error(FDC_ERR_INVALID_ARGUMENT, "a submitted batch is in flight: fdc_sinks_flush() first");
-    if (s->dev.eager_n > 0) return fdc::set_error(FDC_ERR_INVALID_ARGUMENT, "a batch prepared ahead has its decisions enqueued: submit it before feeding the bank from the host");
+    { const int rc0 = batch_entry_check(s, "nitems", nitems, kNotInFlight | kNotEager); if (rc0 != FDC_OK) return rc0; }
     if (nitems == 0) { s->pdus.clear(); return 0; }
     if (!spectrum) return fdc::set_error(FDC_ERR_INVALID_ARGUMENT, "null buffer");
     HIPCHK(hipSetDevice(s->cfg.device_id));
@@ -1819,11 +1087,7 @@ int fdc_sinks_read_band(const fdc_sinks *s, int32_t *lo, int32_t *hi)
 int fdc_sinks_work_band(fdc_sinks *s, const void *spectrum, int nitems, int32_t bin_lo, int32_t bin_hi)
 {
     FDC_ENTRY("fdc_sinks_work_band")
-    if (!s) return fdc::set_error(FDC_ERR_INVALID_ARGUMENT, "null handle");
-    FDC_DEAD_CHECK(s);
-    if (nitems < 0 || nitems > s->cfg.max_blocks) return fdc::set_error(FDC_ERR_INVALID_ARGUMENT, "nitems %d outside [0, max_blocks]", nitems);
-    if (s->dev.on && s->dev.inflight) return fdc::set_error(FDC_ERR_INVALID_ARGUMENT, "a submitted batch is in flight: fdc_sinks_flush() first");
-    if (s->dev.eager_n > 0) return fdc::set_error(FDC_ERR_INVALID_ARGUMENT, "a batch prepared ahead has its decisions enqueued: submit it before feeding the bank from the host");
+    { const int rc0 = batch_entry_check(s, "nitems", nitems, kNotInFlight | kNotEager); if (rc0 != FDC_OK) return rc0; }
     if (bin_lo < 0 || bin_hi > s->N || bin_lo > bin_hi) return fdc::set_error(FDC_ERR_INVALID_ARGUMENT, "band [%d, %d) outside the block", bin_lo, bin_hi);
     int32_t need_lo = 0, need_hi = 0;
     fdc_sinks_read_band(s, &need_lo, &need_hi);
@@ -1846,8 +1110,7 @@ int fdc_sinks_pdu_emit_items(const fdc_sinks *s, int32_t *item, int cap)
 {
     if (!s) return fdc::set_error(FDC_ERR_INVALID_ARGUMENT, "null handle");
     const int n = (int)s->pdus.size();
-    // the order key of a PDU starts with the index of the item that emitted it: bits 24.. on the host engine, 40.. on the device engine
-    const int sh = s->dev.on ? 40 : 24;
+    const int sh = item_shift(s);                              // the order key of a PDU starts with the index of the item that emitted it
     for (int i = 0; i < n && i < cap; i++) item[i] = (int32_t)(s->pdus[(size_t)i].key >> sh);
     return n;
 }
@@ -1857,13 +1120,12 @@ int fdc_sinks_pdu_emit_order(const fdc_sinks *s, int32_t *item, int32_t *pac, in
     FDC_ENTRY("fdc_sinks_pdu_emit_order")
     if (!s) return fdc::set_error(FDC_ERR_INVALID_ARGUMENT, "null handle");
     const int n = (int)s->pdus.size();
-    // the order key: item index in the high bits (above), and for a PowerActivationChannel its index in this bank's list in the low ones
-    // (host engine: bits 0..22, device engine: 0..38; detections carry bit 23 / 39 and their own sub-order)
-    const int sh = s->dev.on ? 40 : 24;
+    // the order key: item index in the high bits (above), and for a PowerActivationChannel its index in this bank's list below the detection bit
+    const int sh = item_shift(s);
     for (int i = 0; i < n && i < cap; i++) {
         const PduRec &r = s->pdus[(size_t)i];
         if (item) item[i] = (int32_t)(r.key >> sh);
-        if (pac) pac[i] = r.meta.kind == 0 ? (int32_t)(r.key & ((1ll << (sh - 1)) - 1)) : -1;
+        if (pac) pac[i] = r.meta.kind == 0 ? (int32_t)(r.key & (fdc::key_det_bit(sh) - 1)) : -1;
     }
     return n;
     FDC_ENTRY_END

@@ -29,6 +29,18 @@ struct SinkOwner {
 // Extraction decided by a state machine: block `q` of stream `owner`
 struct SinkTask { int32_t owner, q, slot, start, win_off, cls; };
 
+// Order key of a PDU: the emission order inside a call, as the reference's sequential loops emit (block, then the
+// PowerActivationChannels in order, then the detections).  One layout at two widths — the host engine builds the narrow one
+// (fdc_sinks_host.hip), the decision kernels the wide one (fdc_sinks_dev.hip writes its numbers out: k_pac_decide, k_det_track):
+//     item (block index inside the call) << shift
+//   | PowerActivationChannel: its index in the bank's list, below the detection bit
+//   | detection: 1 << (shift - 1) | segment << seg shift | sub-order inside the segment (host: a running count of emissions;
+//                device: pass << 27 | 2 * channel sequence + (partial ? 1 : 0))
+constexpr int kKeyShiftHost = 24, kKeyShiftDev = 40;            // the item index starts here
+constexpr int kKeySegShiftHost = 12, kKeySegShiftDev = 28;      // detections: the segment's index (11 bits)
+constexpr int64_t key_det_bit(int item_shift) { return (int64_t)1 << (item_shift - 1); }
+constexpr int64_t kKeyDetBitHost = key_det_bit(kKeyShiftHost), kKeyDetBitDev = key_det_bit(kKeyShiftDev);
+
 // Emission record: blocks [q0, q1) of stream `owner`.  Kept small (the state machines write one per emission): what the
 // host can work out itself — the dictionary's block numbers from the block index in `key` and `count`, the geometry of a
 // PowerActivationChannel from `owner` — is not in it.

@@ -226,9 +226,11 @@ def test_cfg5_full_size_activity_detection(oracle):
 
 
 def test_combined_bank_both_threaded_phases_two_calls(oracle):
-    """One bank with 64 PowerActivationChannels AND two detection segments, fed in two calls of 256 blocks: both decision
-    phases run on the worker threads (PowerActivationChannels by channel, segments by segment), their lists are merged twice
-    per call, PDUs that span the call boundary carry blocks over, and the emission order is restored from the order keys.
+    """One bank with 64 PowerActivationChannels AND two detection segments, fed in two calls of 256 blocks: PDUs that span
+    the call boundary carry blocks over, and the emission order is restored from the order keys.  The bank is built without
+    host_decisions and its segments have 161 cells each, so it runs the DEVICE engine (engine() == 1): both decision phases
+    are kernels here, and despite its name the test does not reach the host engine's worker threads — those are covered by
+    tests/test_sinks_engines_gpu.py::test_host_engine_worker_threads_equal_sequential_and_device_engine.
     Every PDU against the oracle; the order inside a call: block-major, PowerActivationChannels before detections."""
     N, R, nb = 65536, 2, 512
     C = 64

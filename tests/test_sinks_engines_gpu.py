@@ -148,3 +148,47 @@ def test_randomised_banks_device_engine_equals_host_engine():
     spec.loader.exec_module(mod)
     ndev, npdu = mod.main(30, 7)
     assert ndev >= 20 and npdu > 1000
+
+
+def test_host_engine_worker_threads_equal_sequential_and_device_engine():
+    """The host engine's worker threads (the two threaded decision phases and the merge of the workers' lists), which the
+    comparisons above are too small to reach.  70 PowerActivationChannels and two detection segments, 600 blocks in calls of
+    256, 256 and 88: 70 x 256 >= 16384 puts the PowerActivationChannels of the first two calls on worker threads, 2 x 256 >= 256
+    the segments; the third call runs the sequential loops against the state the threaded calls left behind.  Three banks on the
+    same input: host engine with four workers, host engine with threads=1 (PowerActivationChannels sequential; the segment
+    phase still takes two workers, its rule ignores `threads`), and the device engine.  All three share the power-cell and
+    extraction kernels, so everything is equal exactly.  PDUs of both kinds must hold blocks from the call before the one that
+    emits them: those blocks sit in live channels when the workers' lists are merged, which is what the merge's shift of the
+    live owners' task indices is for — for a PowerActivationChannel in a worker behind the first one (channels 17 and up of 70
+    with four workers), whose base is not zero."""
+    N, R, nb, cuts = 2048, 2, 600, (256, 512)
+    plan, carriers = [], []
+    for c in range(70):
+        cf = (c + 0.5) / 72 + 0.005
+        bw = (0.004, 0.008, 0.002)[c % 3]
+        plan.append((cf, bw, 100 + c))
+        carriers.append((int(round((cf - bw / 2) * N)), int(round((cf + bw / 2) * N))))
+    for c in (6, 12, 21, 27, 42, 48, 57, 63):             # four more in each segment, in gaps between the channels above
+        mid = int(round(((c + 1.0) / 72 + 0.005) * N))
+        carriers.append((mid - 4, mid + 4))
+    spec = onoff_spectrum(N, nb, carriers, 31)
+    kw = dict(pac=plan, pac_thresh=6.0, pac_maxblocks=3, segments=[(0.05, 0.45), (0.55, 0.95)], det_thresh=10.0, det_maxblocks=3,
+              minchandist=0.005, det_delay=1, puffer=0.2, max_blocks=256)
+    thr4 = G.Sinks(N, R, host_decisions=True, threads=4, **kw)
+    thr1 = G.Sinks(N, R, host_decisions=True, threads=1, **kw)
+    dev = G.Sinks(N, R, **kw)
+    assert thr4.engine() == 0 and thr1.engine() == 0 and dev.engine() == 1
+    a, b, c = run_calls(thr4, spec, cuts), run_calls(thr1, spec, cuts), run_calls(dev, spec, cuts)
+    assert len(a) > 500
+    crossing = {0: 0, 1: 0}
+    for m, d in a:
+        width = int(m["vectorend"]) - int(m["vectorstart"])
+        nblk = d.size // (width - width // R)
+        # the first call ends with block counter 256, the second with 512; the PDU's blocks end at blockend (one earlier for a
+        # finished detection): emitted behind the cut, and its oldest block is from in front of it
+        if any(m["blockstart"] < cut < m["blockend"] and m["blockend"] - nblk < cut for cut in cuts):
+            if m["kind"] == 1 or m["source"] >= 100 + 17:
+                crossing[int(m["kind"])] += 1
+    assert crossing[0] >= 1 and crossing[1] >= 1, crossing
+    same(a, b, "host engine, 4 workers against threads=1")
+    same(a, c, "host engine, 4 workers against the device engine")
