@@ -23,6 +23,10 @@ struct PinMem {
     static hipError_t get(void **p, size_t bytes) { return hipHostMalloc(p, bytes, hipHostMallocDefault); }
     static void put(void *p) { (void)hipHostFree(p); }
 };
+struct MappedMem {                       // pinned AND mapped into the device's address space (hipHostGetDevicePointer): kernels read it in place
+    static hipError_t get(void **p, size_t bytes) { return hipHostMalloc(p, bytes, hipHostMallocMapped); }
+    static void put(void *p) { (void)hipHostFree(p); }
+};
 
 template <typename T, typename Mem>
 class Buf {
@@ -59,5 +63,7 @@ struct DevBuf : Buf<T, DevMem> {
 };
 template <typename T>
 using PinBuf = Buf<T, PinMem>;
+template <typename T>
+using MappedBuf = Buf<T, MappedMem>;
 
 }  // namespace fdc

@@ -1,0 +1,397 @@
+// The enqueue path of the pipeline handle: what one call brings (DeviceCall), its launch groups and their kernels (process_device_impl), and the
+// device entries fdc_pipeline_process_device*.
+#include "fdc_pipeline.hpp"
+
+namespace fdc { namespace pipe {
+
+static int get_event(fdc_pipeline *p, size_t *idx)
+{
+    if (p->ev_used == p->events.size()) {
+        hipEvent_t e;
+        HIPCHK(hipEventCreate(&e));
+        p->events.push_back(e);
+    }
+    *idx = p->ev_used++;
+    return FDC_OK;
+}
+
+DeviceCall device_call(const fdc_pipeline *p, void *stream, void *d_spectrum, int fmt, float scale)
+{
+    DeviceCall call;
+    call.fmt = fmt; call.scale = scale;
+    call.stream = stream ? static_cast<hipStream_t>(stream) : p->stream;
+    call.spectrum = d_spectrum;
+    call.ncu = p->ncu - p->reserved_cu;
+    return call;
+}
+
+// Channels wider than 4096 bins: all channels of one width and all blocks of the launch group as ONE batch of the task-addressed two-pass
+// inverse transform (fdc_kernels.hip: pass A reads slice * window straight from the spectrum, the ifftshift is its input rotation; pass B
+// writes the kept samples, times l, into the channel streams) — in pieces of up to 32 Mi points of scratch between the passes.
+// gids: the group's channel ids in the device list p->d_groups.
+int channels_wide(fdc_pipeline *p, const float2 *spec, float2 *d_out, const int32_t *d_gids, int ngroup, int l, const Span &span, hipStream_t s)
+{
+    const int nb = span.nb;
+    const int per = (int)std::max<long long>(1, std::min<long long>(nb, (long long)p->big_pts / ((long long)ngroup * l)));   // blocks per piece
+    const int lout = l - l / p->R;
+    for (int m0 = 0; m0 < nb; m0 += per) {
+        const int n = std::min(per, nb - m0);
+        HIPCHK(fdc::launch_wide_tasks(p->d_wtasks, p->d_chans, d_gids, ngroup, p->R, n, span.m0 + m0, span.nblocks, span.first_block, s));
+        HIPCHK(fdc::launch_extract_wide(spec + (size_t)m0 * p->N, p->N, p->d_wtasks, n * ngroup, l, l - lout, p->d_wins, p->d_big, d_out, p->d_tw, p->ntab, s,
+                                        (float)l));
+    }
+    return FDC_OK;
+}
+
+// The channel kernels of one launch group over the plan's channels by width (rem: over the remainder of a split plan only)
+static int run_channel_groups(fdc_pipeline *p, bool rem, const float2 *spec, float2 *d_out, const Span &span, hipStream_t s)
+{
+    const auto &groups = rem ? p->rgroups : p->groups;
+    const auto &off = rem ? p->rgroup_off : p->group_off;
+    const auto &al = rem ? p->rg_aligned : p->g_aligned;
+    const auto &oal = rem ? p->rg_out_aligned : p->g_out_aligned;
+    const int32_t *ids = rem ? p->d_rgroups : p->d_groups;
+    for (size_t g = 0; g < groups.size(); g++) {
+        const int l = groups[g].first, ng = (int)groups[g].second.size();
+        if (l > 4096)
+            RCCHK(channels_wide(p, spec, d_out, ids + off[g], ng, l, span, s));
+        else if (l == 256 && ((256 / p->R) & 1) == 0 && !p->cfg_generic)
+            HIPCHK(fdc::launch_channels256(spec, d_out, p->d_chans, ids + off[g], ng, al[g] != 0, oal[g] != 0, p->N, p->R, span.nb, span.m0, span.nblocks,
+                                           span.first_block, p->d_wins, p->d_tw256, s));
+        else if ((l == 512 || l == 1024) && l <= p->N && !p->cfg_generic)
+            HIPCHK(fdc::launch_channels_wide(spec, d_out, p->d_chans, ids + off[g], ng, l, p->N, p->R, span.nb, span.m0, span.nblocks, span.first_block,
+                                             p->d_wins, p->d_tw, p->ntab, s));
+        else
+            HIPCHK(fdc::launch_channels(spec, d_out, p->d_chans, ids + off[g], ng, l, p->N, p->R, span.nb, span.m0, span.nblocks, span.first_block, p->d_wins,
+                                        p->d_tw, p->ntab, s));
+    }
+    return FDC_OK;
+}
+
+// The remainder of a split plan for one launch group: forward transform into the handle's internal (partial) spectrum, channel kernels
+// over the remainder's groups.  ev2 / ev3 (timing): recorded behind the forward transform and behind the channel kernels.
+static int run_remainder(fdc_pipeline *p, const DeviceCall &call, const float2 *in0, float2 *d_out, const Span &span, hipEvent_t ev2, hipEvent_t ev3)
+{
+    hipStream_t s = call.stream;
+    const int nb = span.nb;
+    if (p->fwd_block && nb >= p->block_min)
+        HIPCHK(fdc::launch_block_fft(p->N, in0, (size_t)p->H, p->d_spec, nb, p->d_tw256, p->d_ftwq, p->d_fcbt, p->d_fshn,
+                                          p->d_fslot, p->d_fscr, call.ncu, p->block_hints, s, nullptr, p->d_keep));
+    else if (p->N == 65536)
+        HIPCHK(fdc::launch_fft65536(in0, (size_t)p->H, p->d_spec, p->d_tmp, nb, p->N / 2, 1.0f / (float)p->N, p->d_tw256,
+                                    p->d_twf, s, nullptr));
+    else
+        HIPCHK(fdc::launch_fft(in0, (size_t)p->H, p->d_spec, p->d_tmp, p->N, nb, false, 0, p->N / 2, 1.0f / (float)p->N, p->d_tw, p->ntab,
+                               s, nullptr, p->d_twf, p->cfg_generic));
+    if (ev2) HIPCHK(hipEventRecord(ev2, s));
+    RCCHK(run_channel_groups(p, true, p->d_spec, d_out, span, s));
+    if (ev3) HIPCHK(hipEventRecord(ev3, s));
+    return FDC_OK;
+}
+
+// one launch of the bank's block kernel over a launch group.  b: the group's part of the launch (input, output, its blocks, the events the dispatch itself
+// stamps); the handle's and the bank's part is filled in here.  raw: the group's first integer sample where the 256-bin kernel reads the call's integer
+// input itself (null: float samples, b.in); oq: the call's narrow output where it narrows in its stores (b.out_bytes: the narrow extent; null: float, b.out)
+static int launch_bank(fdc_pipeline *p, const DeviceCall &call, const fdc_pipeline::Bank &bk, fdc::BlockLaunch b, const void *raw, void *oq)
+{
+    b.in_stride = (size_t)p->H;
+    b.slot_off = bk.d_slot_off;
+    b.ncu = call.ncu; b.hints = p->block_hints;
+    b.s = call.stream;
+    b.N = p->N; b.R = p->R; b.scratch = p->d_fscr;
+    b.L = bk.L; b.r = bk.r;
+    b.cbt = bk.d_cbt; b.shn = bk.d_shn; b.tab = bk.d_tab;
+    b.tw256 = p->d_tw256;
+    b.twq = bk.L == 512 ? p->d_twq512 : bk.L == 1024 ? p->d_twq1k : p->d_twq;
+    b.twl = bk.L == 512 ? p->d_tw512 : bk.L == 1024 ? p->d_tw1k : nullptr;
+    if (oq) {
+        if (bk.L != 256) return set_error(FDC_ERR_UNSUPPORTED, "integer stores in a %d-bin bank", bk.L);
+        HIPCHK(fdc::launch_poly_block_oq(b, raw ? call.fmt : 0, call.scale, raw ? raw : static_cast<const void *>(b.in), call.ofmt, call.oscale, oq));
+        return FDC_OK;
+    }
+    if (raw) {
+        if (bk.L != 256) return set_error(FDC_ERR_UNSUPPORTED, "integer loads in a %d-bin bank", bk.L);
+        HIPCHK(fdc::launch_poly_block_iq(b, call.fmt, call.scale, raw));
+        return FDC_OK;
+    }
+    switch (bk.L) {
+    case 256: HIPCHK(fdc::launch_poly_block(b)); break;
+    case 512: HIPCHK(fdc::launch_poly_block512(b)); break;
+    case 1024: HIPCHK(fdc::launch_poly_block1024(b)); break;
+    default: HIPCHK(fdc::launch_poly_block_narrow(b));
+    }
+    return FDC_OK;
+}
+
+// whether the plan's kernels take complex integers themselves, in their loads or their stores: path 5 (k_f4096) and the banks of 256-bin channels
+// (k_blk256) without a remainder — not with a spectrum or waterfall rows to write
+static bool int_kernels(const fdc_pipeline *p, const DeviceCall &call)
+{
+    if (call.spectrum || call.rows || p->cfg_generic) return false;
+    if (p->fused) return true;
+    if (!p->poly_ok || !p->poly_block || p->split) return false;
+    for (const auto &b : p->banks) if (b.L != 256) return false;
+    return true;
+}
+
+// integer input: whether a launch group (few: shorter than block_min) reads it in its own loads; every other form reads a float ring the group is
+// widened into first (k_iq_to_complex)
+static bool iq_fused(const fdc_pipeline *p, const DeviceCall &call, bool few)
+{
+    return int_kernels(p, call) && (p->fused || !(few && two_launch_possible(p)));
+}
+
+// integer output: whether EVERY launch group of a call of nblocks narrows in its own kernel's stores (k_blk256: streamed stores; not N = 65536 at R = 4
+// on float input, whose forms would spill: fdc_block256.hip kOqR4Narrowed); otherwise the call writes complex float and k_complex_to_iq narrows it
+// (whole call: one layout)
+static bool oq_fused(const fdc_pipeline *p, const DeviceCall &call, int nblocks)
+{
+    if (!int_kernels(p, call)) return false;
+    if (p->fused) return true;
+    if (p->fine_on) return false;            // the banks' kernels do not turn their samples: float, k_fine_rotate, then narrowed
+    if (!(p->block_hints & 1) || (!call.fmt && p->N == 65536 && p->R == 4)) return false;
+    for (int m0 = 0; m0 < nblocks; m0 += p->chunk)
+        if (std::min(p->chunk, nblocks - m0) < p->block_min && two_launch_possible(p)) return false;
+    return true;
+}
+
+// The enqueue path of every entry: nblocks blocks from d_ring (the stream's block first_block first) to d_out, as `call` says; its results say how
+int process_device_impl(fdc_pipeline *p, DeviceCall &call, const void *d_ring, int64_t first_block, int nblocks, void *d_out)
+{
+    if (nblocks < 0 || first_block < 0) return set_error(FDC_ERR_INVALID_ARGUMENT, "negative block count/index");
+    if (nblocks == 0) return FDC_OK;
+    if (!d_ring || (p->C > 0 && !d_out)) return set_error(FDC_ERR_INVALID_ARGUMENT, "null device buffer");
+    void *const d_spectrum = call.spectrum;
+    if (d_spectrum && !p->cfg.keep_spectrum && !call.own_spectrum) return set_error(FDC_ERR_INVALID_ARGUMENT, "spectrum output needs keep_spectrum");
+    // one call produces less than 4 GiB (32-bit output offsets; checked for max_blocks at create): a longer call is refused, not sent down
+    // a path whose internal spectrum may be partial (a split plan's remainder-only spectrum under the channel kernels of ALL channels)
+    if ((int64_t)nblocks * p->sum_lout * 8 > 0xFFFFF000ll)
+        return set_error(FDC_ERR_INVALID_ARGUMENT, "nblocks %d x %lld output samples per block is more than the 4 GiB one call may produce", nblocks, (long long)p->sum_lout);
+    HIPCHK(hipSetDevice(p->cfg.device_id));
+    hipStream_t s = call.stream;
+    const int fmt = call.fmt, ofmt = call.ofmt;
+    const float2 *ring = static_cast<const float2 *>(d_ring);
+    const unsigned char *iring = static_cast<const unsigned char *>(d_ring);
+    const size_t esz = fdc::iq_bytes(fmt);
+    const bool ofused = ofmt && oq_fused(p, call, nblocks);
+    call.ofused = ofused;
+    if (ofmt && !ofused && !call.fout) return set_error(FDC_ERR_INVALID_ARGUMENT, "integer output: no float staging");
+    float2 *o = ofmt && !ofused ? call.fout : static_cast<float2 *>(d_out);
+    const size_t osz = ofused ? fdc::iq_bytes(ofmt) : sizeof(float2);       // bytes per sample the kernels store
+    unsigned char *const ob = ofused ? static_cast<unsigned char *>(d_out) : reinterpret_cast<unsigned char *>(o);
+    const bool use_poly = p->poly_ok && !d_spectrum;
+    const unsigned out_bytes = (unsigned)((int64_t)nblocks * p->sum_lout * (int64_t)osz);
+    // fine tuning: path 5 turns the samples in its own stores; everywhere else k_fine_rotate goes over the launch group's float results behind its channel kernels
+    const bool fine = p->fine_on && p->C > 0, fine_fused = fine && p->fused && !d_spectrum;
+    auto rotate = [&](const Span &g) -> int {
+        if (fine) HIPCHK(fdc::launch_fine_rotate(o, p->d_chans, p->d_fine, p->d_fstep, p->C, g.nb, g.m0, g.nblocks, g.first_block, s));
+        return FDC_OK;
+    };
+    for (int m0 = 0; m0 < nblocks; m0 += p->chunk) {
+        const int nb = std::min(p->chunk, nblocks - m0);
+        const Span grp{nb, m0, nblocks, first_block};
+        float2 *spec = d_spectrum ? static_cast<float2 *>(d_spectrum) + (size_t)m0 * p->N : p->d_spec;
+        hipEvent_t ev[3]; hipEvent_t *evp = nullptr; std::array<size_t, 5> span{};
+        // events on every timing_stride-th launch group only: a sample of the launches, so that the packets between the
+        // kernels (measured 7-17 us per group) do not slow the region they time
+        const bool tg = p->timing && (p->timing_seq++ % p->timing_stride) == 0;
+        if (tg) {
+            for (int i = 0; i < 4; i++) RCCHK(get_event(p, &span[i]));
+            for (int i = 0; i < 3; i++) ev[i] = p->events[span[i]];
+            evp = ev;
+        }
+        const float2 *in0 = ring + (size_t)m0 * p->H;
+        const void *raw0 = iring + (size_t)m0 * p->H * esz;
+        const bool few = nb < p->block_min;
+        const bool ifused = fmt && iq_fused(p, call, few);
+        if (fmt && !ifused) {
+            // this launch group's samples (nb blocks and the history in front of the last one) widened into the float ring the kernels read
+            HIPCHK(fdc::launch_iq_to_complex(fmt, call.scale, raw0, call.wide, (size_t)nb * p->H + (size_t)p->ovl, s));
+            in0 = call.wide;
+            call.all_fused = false;
+        }
+        // overlap-save gather fused into the load (item m at ring + m*H), fftshift + 1/N into the store.
+        // A block kernel gives a whole block to one compute unit: a launch group of fewer blocks than the device has compute
+        // units leaves the rest idle (one block takes ~42 us there, however few there are).  Short calls — a scheduler handing
+        // over a few items — take the two-launch form where the plan has one (ONE bank on its grid), which spreads every block over the device.
+        if (p->fused && !d_spectrum) {
+            // N = 4096: one launch, nothing but the input samples and the output samples crosses the memory interface
+            if (tg) HIPCHK(hipEventRecord(p->events[span[0]], s));
+            float *wf = call.rows ? call.rows + (size_t)(first_block - call.rows_first + m0) * fdc::kWfWidth : nullptr;
+            if (fine_fused)
+                HIPCHK(fdc::launch_fused4096_fine(ifused ? fmt : 0, call.scale, ifused ? raw0 : static_cast<const void *>(in0), (size_t)p->H, ofused ? ofmt : 0, call.oscale,
+                                                  ofused ? d_out : static_cast<void *>(o), nb, p->R, m0, nblocks, first_block, p->d_tw, p->ntab, p->d_wins, p->d_f4rows,
+                                                  p->f4_cls, p->f4_teams, p->d_f4fine, p->d_fstep, s));
+            else if (ofused)
+                HIPCHK(fdc::launch_fused4096_oq(ifused ? fmt : 0, call.scale, ifused ? raw0 : static_cast<const void *>(in0), (size_t)p->H, ofmt, call.oscale, d_out, nb,
+                                                p->R, m0, nblocks, first_block, p->d_tw, p->ntab, p->d_wins, p->d_f4rows, p->f4_cls, p->f4_teams, s));
+            else if (ifused)
+                HIPCHK(fdc::launch_fused4096_iq(fmt, call.scale, raw0, (size_t)p->H, o, nb, p->R, m0, nblocks, first_block, p->d_tw, p->ntab, p->d_wins, p->d_f4rows,
+                                                p->f4_cls, p->f4_teams, s));
+            else
+                HIPCHK(fdc::launch_fused4096(in0, (size_t)p->H, o, nb, p->R, m0, nblocks, first_block, p->d_tw, p->ntab, p->d_wins, p->d_f4rows, p->f4_cls, p->f4_teams, s, wf));
+            if (tg) { HIPCHK(hipEventRecord(p->events[span[1]], s)); span[2] = span[3] = span[1]; span[4] = kSpanBanks; p->ev_spans.push_back(span); }
+            continue;
+        }
+        if (use_poly && p->poly_block && !(few && two_launch_possible(p))) {
+            // one launch per bank: nothing but the input rows and the output samples crosses the memory interface.
+            // timing: the first launch's begin and the last one's end are the dispatches' own stamps, no packets around the kernels
+            fdc::BlockLaunch b{};
+            b.in = in0; b.out = o;
+            b.nb_chunk = nb; b.mbase = m0; b.nb_call = nblocks;
+            b.first_block = first_block + m0; b.out_bytes = out_bytes;
+            for (size_t k = 0; k < p->banks.size(); k++) {
+                b.ev_start = tg && k == 0 ? p->events[span[0]] : nullptr;
+                b.ev_stop = tg && k + 1 == p->banks.size() ? p->events[span[1]] : nullptr;
+                RCCHK(launch_bank(p, call, p->banks[k], b, ifused ? raw0 : nullptr, ofused ? d_out : nullptr));
+            }
+            for (const auto &al : p->bank_alias) {
+                const fdc::ChanDev &dc = p->chans[(size_t)al.first], &sc = p->chans[(size_t)al.second];
+                HIPCHK(hipMemcpyAsync(ob + osz * ((size_t)nblocks * dc.out_off + (size_t)m0 * dc.lout), ob + osz * ((size_t)nblocks * sc.out_off + (size_t)m0 * sc.lout),
+                                      osz * (size_t)nb * dc.lout, hipMemcpyDeviceToDevice, s));
+            }
+            if (p->split) RCCHK(run_remainder(p, call, in0, o, grp, tg ? p->events[span[2]] : nullptr, tg ? p->events[span[3]] : nullptr));
+            else if (tg) span[2] = span[3] = span[1];
+            if (tg) { span[4] = kSpanBanks; p->ev_spans.push_back(span); }
+            RCCHK(rotate(grp));
+            continue;
+        }
+        if (use_poly) {
+            // ONE bank on its grid: window + IFFT commuted in front of pass B; only G (lout * N / l per block) between the two launches
+            const fdc_pipeline::Bank &bk = p->banks[0];
+            if (tg) HIPCHK(hipEventRecord(p->events[span[0]], s));
+            if (bk.L != 256)
+                HIPCHK(fdc::launch_poly_stage1_generic(in0, (size_t)p->H, p->d_g, p->N, bk.L, p->R, nb, bk.d_shn, p->d_tw, p->ntab, p->d_t2g, s));
+            else
+                HIPCHK(fdc::launch_poly_stage1(in0, (size_t)p->H, p->d_g, p->N / 256, p->R, nb, p->d_tw256, p->d_twq, bk.d_cbt, bk.d_shn, call.ncu, s));
+            if (tg) { HIPCHK(hipEventRecord(p->events[span[1]], s)); span[2] = span[1]; }   // the end of stage 1 IS the start of stage 2
+            if (bk.L != 256)
+                HIPCHK(fdc::launch_poly_stage2_generic(p->d_g, o, p->N / bk.L, p->R, nb, m0, nblocks, bk.d_slot_off, p->d_tw, p->ntab, s, bk.L));
+            else if (p->N != 65536 && p->N != 262144)
+                HIPCHK(fdc::launch_poly_stage2_generic(p->d_g, o, p->N / 256, p->R, nb, m0, nblocks, bk.d_slot_off, p->d_tw, p->ntab, s));
+            else
+                HIPCHK(fdc::launch_poly_stage2(p->d_g, o, p->N / 256, p->R, nb, m0, nblocks, p->d_tw256, p->d_tw1024, bk.d_slot_off, out_bytes, call.ncu, s));
+            if (p->split) RCCHK(run_remainder(p, call, in0, o, grp, nullptr, nullptr));   // (timing: the remainder is counted with stage 2)
+            RCCHK(rotate(grp));
+            if (tg) {
+                HIPCHK(hipEventRecord(p->events[span[3]], s));
+                span[4] = kSpanTwoLaunch;
+                p->ev_spans.push_back(span);
+            }
+            continue;
+        }
+        // a spectrum in memory.  (A split plan's internal spectrum holds its remainder's bins only: whoever gets here with one — a caller's
+        // spectrum buffer — writes a full spectrum into THAT buffer, d_keep is not applied.)
+        // the power of the 16-bin groups of the caller's spectrum (fdc_pipeline_process_device_power): summed by the block kernel while the bins are in
+        // its registers; by a pass over the spectrum where another transform ran
+        float *const gp = (call.gpow && d_spectrum) ? call.gpow + (size_t)(spec - call.gpow_origin) / 16 : nullptr;
+        if (p->fwd_block && !few)
+            HIPCHK(fdc::launch_block_fft(p->N, in0, (size_t)p->H, spec, nb, p->d_tw256, p->d_ftwq, p->d_fcbt,
+                                              p->d_fshn, p->d_fslot, p->d_fscr, call.ncu, p->block_hints, s, evp, d_spectrum ? nullptr : p->d_keep, gp));
+        else {
+            if (p->N == 65536 && !p->cfg_generic)
+                HIPCHK(fdc::launch_fft65536(in0, (size_t)p->H, spec, p->d_tmp, nb, p->N / 2,
+                                            1.0f / (float)p->N, p->d_tw256, p->d_twf, s, evp));
+            else
+                HIPCHK(fdc::launch_fft(in0, (size_t)p->H, spec, p->d_tmp, p->N, nb, false, 0, p->N / 2,
+                                       1.0f / (float)p->N, p->d_tw, p->ntab, s, evp, p->d_twf, p->cfg_generic, d_spectrum ? ~0ull : p->keep4096));
+            if (gp) HIPCHK(fdc::launch_group_power(spec, p->N, nb, gp, s));
+        }
+        RCCHK(run_channel_groups(p, false, spec, o, grp, s));
+        RCCHK(rotate(grp));
+        if (tg) {
+            HIPCHK(hipEventRecord(p->events[span[3]], s));
+            span[4] = p->N <= fdc::kMaxLdsFft ? kSpanSpectrumLds : kSpanSpectrum;
+            p->ev_spans.push_back(span);
+        }
+    }
+    if (ofmt && !ofused && call.narrow && p->C > 0) HIPCHK(fdc::launch_complex_to_iq(ofmt, call.oscale, call.fout, d_out, (size_t)nblocks * p->sum_lout, s));
+    if (fine) p->fine_route = fine_fused ? "fused" : "rotated";
+    return FDC_OK;
+}
+
+// how the last integer-input / integer-output call was served (fdc_pipeline_describe): "<sc16|sc8>: fused", or what it was instead
+std::string route(int fmt, bool fused, const char *otherwise)
+{
+    return std::string(fmt == FDC_IQ_SC16 ? "sc16" : "sc8") + ": " + (fused ? "fused" : otherwise);
+}
+
+// The device entries with the handle's output format: integer output needs the float staging (p->d_out, max_blocks*sum_lout samples, allocated by
+// fdc_pipeline_set_output_format, never on this enqueue path) where the call's kernels do not narrow themselves
+static int process_device_oq(fdc_pipeline *p, DeviceCall &call, const void *d_ring, int64_t first_block, int nblocks, void *d_out)
+{
+    const int ofmt = p->out_form;
+    if (!ofmt || nblocks <= 0) return process_device_impl(p, call, d_ring, first_block, nblocks, d_out);
+    call.ofmt = ofmt; call.oscale = p->out_scale; call.fout = p->d_out;
+    if (!oq_fused(p, call, nblocks)) {
+        if (nblocks > p->cfg.max_blocks)
+            return set_error(FDC_ERR_INVALID_ARGUMENT, "integer output on this plan: nblocks %d above max_blocks %d", nblocks, p->cfg.max_blocks);
+        if (!p->d_out && p->sum_lout > 0) return set_error(FDC_ERR_HIP, "integer output: no float staging");
+    }
+    const int rc = process_device_impl(p, call, d_ring, first_block, nblocks, d_out);
+    if (rc == FDC_OK) p->oq_route = route(ofmt, call.ofused, "narrowed");
+    return rc;
+}
+
+int check_iq_form(int32_t format, float scale)
+{
+    if (format != FDC_IQ_SC16 && format != FDC_IQ_SC8) return set_error(FDC_ERR_INVALID_ARGUMENT, "unknown complex integer format %d", (int)format);
+    if (!std::isfinite(scale) || scale == 0.0f) return set_error(FDC_ERR_INVALID_ARGUMENT, "the scale must be finite and not zero");
+    return FDC_OK;
+}
+
+} }  // namespace fdc::pipe
+
+using namespace fdc::pipe;
+
+extern "C" {
+
+int fdc_pipeline_process_device(fdc_pipeline *p, const void *d_ring, int64_t first_block, int nblocks,
+                                void *d_out, void *d_spectrum, void *stream)
+{
+    FDC_ENTRY("fdc_pipeline_process_device")
+    if (!p) return set_error(FDC_ERR_INVALID_ARGUMENT, "null handle");
+    DeviceCall call = device_call(p, stream, d_spectrum);
+    return process_device_oq(p, call, d_ring, first_block, nblocks, d_out);
+    FDC_ENTRY_END
+}
+
+int fdc_pipeline_process_device_iq(fdc_pipeline *p, int32_t format, float scale, const void *d_ring, int64_t first_block, int nblocks,
+                                   void *d_out, void *d_spectrum, void *stream)
+{
+    FDC_ENTRY("fdc_pipeline_process_device_iq")
+    if (!p) return set_error(FDC_ERR_INVALID_ARGUMENT, "null handle");
+    RCCHK(check_iq_form(format, scale));
+    if (reinterpret_cast<uintptr_t>(d_ring) & 3) return set_error(FDC_ERR_INVALID_ARGUMENT, "the integer ring must be 4-byte aligned");
+    DeviceCall call = device_call(p, stream, d_spectrum, format, scale);
+    if (nblocks > 0 && !p->d_iqw) {
+        bool need = false;      // the widened launch group: allocated at the first call that has a form without integer loads
+        for (int m0 = 0; m0 < nblocks && !need; m0 += p->chunk) need = !iq_fused(p, call, std::min(p->chunk, nblocks - m0) < p->block_min);
+        if (need) {
+            HIPCHK(hipSetDevice(p->cfg.device_id));
+            HIPCHK(p->d_iqw.alloc((size_t)p->chunk * p->H + (size_t)p->ovl));
+        }
+    }
+    call.wide = p->d_iqw;
+    const int rc = process_device_oq(p, call, d_ring, first_block, nblocks, d_out);
+    if (rc == FDC_OK && nblocks > 0) p->iq_route = route(format, call.all_fused, "widened");
+    return rc;
+    FDC_ENTRY_END
+}
+
+int fdc_pipeline_process_device_power(fdc_pipeline *p, const void *d_ring, int64_t first_block, int nblocks, void *d_out, void *d_spectrum,
+                                      void *d_group_power, void *stream)
+{
+    FDC_ENTRY("fdc_pipeline_process_device_power")
+    if (!p) return set_error(FDC_ERR_INVALID_ARGUMENT, "null handle");
+    if (p->out_form) return set_error(FDC_ERR_INVALID_ARGUMENT, "fdc_pipeline_process_device_power writes complex float outputs only (the handle's output format is not FC32)");
+    if (p->fine_on) return set_error(FDC_ERR_INVALID_ARGUMENT, "fdc_pipeline_process_device_power writes the channels as they are cut: switch fine tuning off first");
+    if (d_group_power && (!d_spectrum || (p->N & 15))) return set_error(FDC_ERR_INVALID_ARGUMENT, "group powers go with a spectrum output of a block length that is a multiple of 16");
+    DeviceCall call = device_call(p, stream, d_spectrum);
+    call.gpow = static_cast<float *>(d_group_power);
+    call.gpow_origin = static_cast<const float2 *>(d_spectrum);
+    return process_device_impl(p, call, d_ring, first_block, nblocks, d_out);
+    FDC_ENTRY_END
+}
+
+}  // extern "C"

@@ -284,6 +284,7 @@ extern "C" {
 
 int fdc_waterfall_check(const fdc_waterfall_cfg *cfg, fdc_waterfall_cfg *normalized)
 {
+    FDC_ENTRY("fdc_waterfall_check")
     if (!cfg) return fdc::set_error(FDC_ERR_INVALID_ARGUMENT, "null configuration");
     if (!blocklen_ok(cfg->blocklen))
         return fdc::set_error(FDC_ERR_INVALID_ARGUMENT, "blocklen %d: a waterfall row needs a multiple of 1024 or a divisor of 1024", cfg->blocklen);
@@ -293,16 +294,19 @@ int fdc_waterfall_check(const fdc_waterfall_cfg *cfg, fdc_waterfall_cfg *normali
         if (normalized->blockdecimation <= 0) normalized->blockdecimation = 1;
     }
     return FDC_OK;
+    FDC_ENTRY_END
 }
 
 int fdc_waterfall_color_table(int32_t scheme, uint8_t *rgb, uint8_t *frame)
 {
+    FDC_ENTRY("fdc_waterfall_color_table")
     if (!rgb && !frame) return fdc::set_error(FDC_ERR_INVALID_ARGUMENT, "null buffers");
     uint8_t t[3 * W], fr[3];
     color_table(scheme, t, fr);
     if (rgb) std::memcpy(rgb, t, sizeof t);
     if (frame) std::memcpy(frame, fr, sizeof fr);
     return FDC_OK;
+    FDC_ENTRY_END
 }
 
 int fdc_waterfall_edges(int32_t loginput, double minvaldb, double maxvaldb, double *edges)

@@ -1,5 +1,5 @@
 """GPU tests (-m gpu): a call leaves nothing behind on the handle.  What an entry brings with it — waterfall rows, the spectrum staging it may write
-without keep_spectrum, group powers — lives for that call only (csrc/fdc_api.hip, DeviceCall): the next call through ANOTHER entry on the same
+without keep_spectrum, group powers — lives for that call only (csrc/fdc_pipeline.hpp, DeviceCall): the next call through ANOTHER entry on the same
 handle computes what a fresh handle computes, is refused what a fresh handle is refused, and takes the kernels a fresh handle takes."""
 import ctypes as C
 

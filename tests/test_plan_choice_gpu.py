@@ -1,4 +1,4 @@
-"""GPU tests (-m gpu) of the plan selector (csrc/fdc_api.hip: classify_plan; constants: csrc/fdc_plan_cost.hpp).
+"""GPU tests (-m gpu) of the plan selector (csrc/fdc_plan.hip: classify_plan; constants: csrc/fdc_plan_cost.hpp).
 
 (a) banks of DIFFERENT widths in one plan: the reference derives l per channel
     (python/FrequencyDomainChannelizer.py:323-327) and its own example is mixed (examples/FDC_example.grc); a plan that is a

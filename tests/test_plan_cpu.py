@@ -1,4 +1,4 @@
-"""CPU tests (-m "not gpu") of the plan selector (csrc/fdc_api.hip: classify_plan; csrc/fdc_plan_cost.hpp) through fdc_pipeline_plan_preview,
+"""CPU tests (-m "not gpu") of the plan selector (csrc/fdc_plan.hip: classify_plan; csrc/fdc_plan_cost.hpp) through fdc_pipeline_plan_preview,
 which runs fdc_pipeline_create's validation and classification without a device: which channels become banks (one block-kernel launch each),
 copies, or the remainder / the spectrum path.  The GPU side of the same question — is the choice the FASTEST form — is
 tests/test_plan_choice_gpu.py; here: the structure of every plan the selector makes is valid, whatever it is fed."""
