@@ -260,8 +260,24 @@ class _OutputFormat:
         return outs
 
 
+def _levels(fn, handle, nchan, last_nb, nblocks):
+    """The (power, peak) pairs of the last work call as float32[nblocks, C, 2] (fdc_pipeline_levels / fdc_pipeline_group_levels)."""
+    if nblocks is None:
+        if last_nb is None:
+            raise ValueError("levels(): no work call yet")
+        nblocks = last_nb
+    nblocks = int(nblocks)
+    if nblocks < 0:
+        raise ValueError("levels(): negative block count")
+    out = np.empty((nblocks, nchan, 2), dtype=np.float32)
+    _lib.check(fn(handle, out.ctypes.data_as(C.POINTER(C.c_float)), nblocks))
+    return out
+
+
 class Pipeline(_OutputFormat):
     """fdc_pipeline handle: channels = [(f, l, passbw, stopbw), ...]."""
+    _last_nb = None        # block count of the last work call that had blocks (levels())
+    _call_nb = 0           # ... and of the last work call
 
     def __init__(self, blocklen, relinvovl, channels, windowtype=WINDOWTYPES.HANN, max_blocks=64,
                  device_id=0, chunk_blocks=0, keep_spectrum=False, flags=None, min_block_launch=None, host_sub_blocks=None):
@@ -310,6 +326,27 @@ class Pipeline(_OutputFormat):
         refused while it is on.  ValueError for a wrong count, NaN or |nu| >= 0.5 (nothing changes)."""
         _set_fine_tuning(_lib.lib().fdc_pipeline_set_fine_tuning, self._h, len(self.channels), nu)
 
+    def set_levels(self, on=True):
+        """fdc_pipeline_set_levels: with levels on, every call also sums, on the device, power = sum(re^2 + im^2) and peak = max(|re|, |im|) of each
+        (block, channel) row of the complex64 samples it writes — after fine tuning, before the sc16 / sc8 narrowing, so peak * |scale| >= 32767.5
+        (127.5) says a row saturated.  A setting like set_output_format: it applies from the next call and survives reset(); the sink,
+        spectrum-item, group-power and waterfall entries are refused while it is on."""
+        _lib.check(_lib.lib().fdc_pipeline_set_levels(self._h, int(bool(on))))
+
+    def levels(self, nblocks=None):
+        """fdc_pipeline_levels: float32[nblocks of the last call, C, 2], [m, c] = (power, peak) of block m of channel c.  nblocks: the last call's
+        block count where it did not go through this object's work methods (process_device, work_raw)."""
+        return _levels(_lib.lib().fdc_pipeline_levels, self._h, len(self.channels), self._last_nb, nblocks)
+
+    def levels_device(self):
+        """fdc_pipeline_levels_device: the device address of the levels ([block][C] float2), None while levels are off."""
+        return _lib.lib().fdc_pipeline_levels_device(self._h)
+
+    def _ran(self, nb):
+        self._call_nb = int(nb)
+        if nb > 0:
+            self._last_nb = int(nb)
+
     # -- host path (what sync_block::work() would call)
     def work(self, x, want_spectrum=False, sinks=None, outs=None):
         """sinks: a gr_fdc_amd.Sinks bank fed from the device-resident spectrum of this call (needs keep_spectrum).
@@ -328,6 +365,7 @@ class Pipeline(_OutputFormat):
         else:
             _lib.check(_lib.lib().fdc_pipeline_work(self._h, x.ctypes.data, nb, ptrs,
                                                    spec.ctypes.data if spec is not None else None))
+        self._ran(nb)
         return (outs, spec) if want_spectrum else outs
 
     def work_waterfall(self, x, waterfall):
@@ -371,6 +409,7 @@ class Pipeline(_OutputFormat):
         spec = np.empty(nb * self.N, dtype=np.complex64) if want_spectrum else None
         _lib.check(_lib.lib().fdc_pipeline_work_real(self._h, x.ctypes.data, nb, ptrs,
                                                     spec.ctypes.data if spec is not None else None))
+        self._ran(nb)
         return (outs, spec) if want_spectrum else outs
 
     def work_iq(self, x, scale=1.0, want_spectrum=False, outs=None):
@@ -385,6 +424,7 @@ class Pipeline(_OutputFormat):
         spec = np.empty(nb * self.N, dtype=np.complex64) if want_spectrum else None
         _lib.check(_lib.lib().fdc_pipeline_work_iq(self._h, fmt, float(sc), x.ctypes.data, nb, ptrs,
                                                   spec.ctypes.data if spec is not None else None))
+        self._ran(nb)
         return (outs, spec) if want_spectrum else outs
 
     def work_span_iq(self, halo, x, first_block, scale=1.0, want_spectrum=False):
@@ -402,12 +442,15 @@ class Pipeline(_OutputFormat):
         spec = np.empty(nb * self.N, dtype=np.complex64) if want_spectrum else None
         _lib.check(_lib.lib().fdc_pipeline_work_span_iq(self._h, fmt, float(sc), hp, x.ctypes.data, int(first_block), nb, ptrs,
                                                        spec.ctypes.data if spec is not None else None))
+        self._ran(nb)
         return (outs, spec) if want_spectrum else outs
 
     def work_raw(self, in_ptr, nblocks, out_ptrs):
         """fdc_pipeline_work on raw addresses (out_ptrs: ctypes array of c_void_p, one per channel) — for callers that
         keep their buffers and want no per-call Python work, e.g. timing the C entry itself."""
-        return _lib.check(_lib.lib().fdc_pipeline_work(self._h, in_ptr, int(nblocks), out_ptrs, None))
+        rc = _lib.check(_lib.lib().fdc_pipeline_work(self._h, in_ptr, int(nblocks), out_ptrs, None))
+        self._ran(int(nblocks))
+        return rc
 
     def work_spectrum(self, spec_items, want_spectrum=False, sinks=None):
         """Items that are already transformed (unnormalised, fftshifted): hier block with inpveclen > 1."""
@@ -436,6 +479,7 @@ class Pipeline(_OutputFormat):
         else:
             _lib.check(_lib.lib().fdc_pipeline_process_device(self._h, d_ring, int(first_block), int(nblocks), d_out,
                                                              d_spectrum, stream))
+            self._ran(int(nblocks))
 
     def process_device_iq(self, fmt, scale, d_ring, first_block, nblocks, d_out, d_spectrum=None, stream=None):
         """fdc_pipeline_process_device_iq: a device ring of complex integers (fmt: "sc16" / "sc8" or IQ_SC16 / IQ_SC8; d_ring 4-byte aligned).
@@ -445,6 +489,7 @@ class Pipeline(_OutputFormat):
             raise ValueError("fmt is 'sc16' or 'sc8'")
         _lib.check(_lib.lib().fdc_pipeline_process_device_iq(self._h, fmt, float(np.float32(scale)), d_ring, int(first_block), int(nblocks),
                                                             d_out, d_spectrum, stream))
+        self._ran(int(nblocks))
 
     def synchronize(self):
         _lib.check(_lib.lib().fdc_pipeline_synchronize(self._h))
@@ -532,11 +577,25 @@ class PipelineGroup(_OutputFormat):
         """fdc_pipeline_group_set_fine_tuning: Pipeline.set_fine_tuning for every member."""
         _set_fine_tuning(_lib.lib().fdc_pipeline_group_set_fine_tuning, self._h, len(self.channels), nu)
 
+    _last_nb = None        # block count of the last work call that had blocks (levels())
+    _call_nb = 0           # ... and of the last work call
+
+    def set_levels(self, on=True):
+        """fdc_pipeline_group_set_levels: Pipeline.set_levels for every member."""
+        _lib.check(_lib.lib().fdc_pipeline_group_set_levels(self._h, int(bool(on))))
+
+    def levels(self, nblocks=None):
+        """fdc_pipeline_group_levels: Pipeline.levels of the last group call, the members' spans put together in block order."""
+        return _levels(_lib.lib().fdc_pipeline_group_levels, self._h, len(self.channels), self._last_nb, nblocks)
+
     def _run(self, fn, x, nb, want_spectrum, outs):
         outs = self._check_outs(outs, nb)
         ptrs = (C.c_void_p * max(1, len(outs)))(*[o.ctypes.data for o in outs])
         spec = np.empty(nb * self.N, dtype=np.complex64) if want_spectrum else None
         _lib.check(fn(self._h, x.ctypes.data, nb, ptrs, spec.ctypes.data if spec is not None else None))
+        self._call_nb = int(nb)
+        if nb > 0:
+            self._last_nb = int(nb)
         return (outs, spec) if want_spectrum else outs
 
     def work(self, x, want_spectrum=False, outs=None):
@@ -559,7 +618,10 @@ class PipelineGroup(_OutputFormat):
                          want_spectrum, outs)
 
     def work_raw(self, in_ptr, nblocks, out_ptrs):
-        return _lib.check(_lib.lib().fdc_pipeline_group_work(self._h, in_ptr, int(nblocks), out_ptrs, None))
+        rc = _lib.check(_lib.lib().fdc_pipeline_group_work(self._h, in_ptr, int(nblocks), out_ptrs, None))
+        if int(nblocks) > 0:
+            self._last_nb = int(nblocks)
+        return rc
 
     def reset(self):
         _lib.lib().fdc_pipeline_group_reset(self._h)
@@ -616,7 +678,7 @@ class FrequencyDomainChannelizer:
                  pow_act_deactivation_delay,
                  pow_act_maxblocks, act_det_maxblocks,
                  debug, device_id=0, max_blocks=64, devices=None, pipelined=False, waterfall=None, iq_input=None, iq_scale=1.0,
-                 iq_output=None, iq_output_scale=1.0, fine_tuning=False, *, payload_format=None, payload_scale=1.0):
+                 iq_output=None, iq_output_scale=1.0, fine_tuning=False, *, payload_format=None, payload_scale=1.0, levels=False):
         # pipelined (not an argument of the reference): the sink blocks run beside the front end of the FOLLOWING work() calls, as the
         # thread-per-block scheduler runs them beside the FFT in the reference (fdc_pipeline_work_sinks on a look-ahead bank,
         # include/fdc_amd.h): same PDUs, handed out one or two work() calls later; flush() at the end of the stream
@@ -710,6 +772,18 @@ class FrequencyDomainChannelizer:
                     raise ValueError("fine_tuning: the carrier %r lies outside its slice [%d, %d) (a slice clamped at the band edge)" % (fr, f, f + l))
                 self.fine_nu.append(nu)
 
+        # levels (not an argument of the reference): after every work() self.levels is float32[items, throughput channels, 2], (power, peak) of every
+        # block of every port as the device summed them (Pipeline.set_levels): of the float samples, after fine tuning and before iq_output narrows them
+        self.levels_on = bool(levels)
+        self.levels = None
+        if self.levels_on:
+            if self.inpveclen != 1:
+                raise ValueError("levels needs inpveclen 1: the pre-transformed item entry gives no channel levels")
+            if activity_controlled_channels or activity_detection_segments:
+                raise ValueError("levels cannot go with activity-controlled channels or detection segments")
+            if waterfall is not None:
+                raise ValueError("levels cannot go with a waterfall")
+
         if self.verbose:                                        # runtime information, :176-193
             bar = '\n' + '#' * 32 + '\n'
             for ln in (bar, '# gr-FDC Frequency Domain Channelizer Runtime Information', bar,
@@ -763,6 +837,8 @@ class FrequencyDomainChannelizer:
             self.pipeline.set_output_format(iq_output, iq_output_scale)
         if self.fine_tuning:
             self.pipeline.set_fine_tuning(np.asarray(self.fine_nu, dtype=np.float64))
+        if self.levels_on:
+            self.pipeline.set_levels(True)
         self.N_throughput_channelizers = len(self.channel_params)
         # waterfall (not an argument of the reference, whose example flowgraph wires the spectrum to complex_to_mag_squared and
         # FDC.WaterfallMsgTagging outside the hier block): a gr_fdc_amd.Waterfall fed from the spectrum on the device; work() then
@@ -836,6 +912,9 @@ class FrequencyDomainChannelizer:
         self.messages = []
         if self.sinks is not None:
             self._publish()
+        if self.levels_on:
+            # (a call without items leaves the handle's previous result in place: this call's array is empty)
+            self.levels = self.pipeline.levels() if self.pipeline._call_nb > 0 else np.empty((0, len(self.channel_params), 2), dtype=np.float32)
         if self.debug:
             outs, spec = res
             return [spec] + outs

@@ -408,6 +408,7 @@ int32_t fdc_pipeline_describe(const fdc_pipeline *p, char *buf, int32_t n)
     if (!p->iq_route.empty()) add("; input %s", p->iq_route.c_str());
     if (!p->oq_route.empty()) add("; output %s", p->oq_route.c_str());
     if (!p->fine_route.empty()) add("; fine tuning: %s", p->fine_route.c_str());
+    if (!p->levels_route.empty()) add("; levels: %s", p->levels_route.c_str());
     std::snprintf(buf, (size_t)n, "%s", t);
     return k;
 }
@@ -478,6 +479,7 @@ void fdc_pipeline_reset(fdc_pipeline *p)
     p->iq_route.clear();
     p->oq_route.clear();         // (the output format itself is a setting: it stays)
     p->fine_route.clear();       // (and so does fine tuning)
+    p->levels_route.clear();     // (and so do the channel levels)
 }
 
 int fdc_pipeline_set_output_format(fdc_pipeline *p, int32_t format, float scale)
@@ -549,5 +551,50 @@ int fdc_pipeline_set_fine_tuning(fdc_pipeline *p, const double *nu, int n)
     return FDC_OK;
     FDC_ENTRY_END
 }
+
+int fdc_pipeline_set_levels(fdc_pipeline *p, int32_t on)
+{
+    FDC_ENTRY("fdc_pipeline_set_levels")
+    if (!p) return set_error(FDC_ERR_INVALID_ARGUMENT, "null handle");
+    if (p->hier_filled > 0)
+        return set_error(FDC_ERR_INVALID_ARGUMENT, "a pipelined sinks batch is still inside the handle: fdc_pipeline_flush_sinks until it returns 0 first");
+    HIPCHK(hipSetDevice(p->cfg.device_id));
+    HIPCHK(hipStreamSynchronize(p->stream));          // (no call of the host entries is in flight; a device entry's caller orders its own stream)
+    if (!on) { p->levels_on = false; p->levels_route.clear(); return FDC_OK; }
+    // everything the feature needs, once: one (power, peak) pair per block of the longest call and channel, on the device and pinned on the host
+    const size_t n = (size_t)p->cfg.max_blocks * (size_t)p->C;
+    if (n > 0 && !p->d_levels) HIPCHK(p->d_levels.alloc(n));
+    if (n > 0 && !p->pin_levels) HIPCHK(p->pin_levels.alloc(n));
+    if (!p->levels_on) p->lev_blocks = -1;            // switched on: no call has levels yet
+    p->levels_on = true;
+    const char *sep = fdc::debug_env("FDC_LEVELS_SEPARATE");
+    p->levels_separate = sep && atoi(sep) > 0;
+    return FDC_OK;
+    FDC_ENTRY_END
+}
+
+int fdc_pipeline_levels(fdc_pipeline *p, float *dst, int nblocks)
+{
+    FDC_ENTRY("fdc_pipeline_levels")
+    if (!p) return set_error(FDC_ERR_INVALID_ARGUMENT, "null handle");
+    if (!p->levels_on) return set_error(FDC_ERR_INVALID_ARGUMENT, "channel levels are off (fdc_pipeline_set_levels)");
+    if (p->lev_blocks < 0) return set_error(FDC_ERR_INVALID_ARGUMENT, "no work call has run since the channel levels were switched on");
+    if (nblocks != p->lev_blocks) return set_error(FDC_ERR_INVALID_ARGUMENT, "the last work call had %d blocks, not %d", p->lev_blocks, nblocks);
+    const size_t n = (size_t)nblocks * (size_t)p->C;
+    if (n == 0) return FDC_OK;
+    if (!dst) return set_error(FDC_ERR_INVALID_ARGUMENT, "null argument");
+    if (!p->lev_host) {
+        // a device entry's levels: read behind everything enqueued so far on the stream it ran on
+        HIPCHK(hipSetDevice(p->cfg.device_id));
+        HIPCHK(hipMemcpyAsync(p->pin_levels.get(), p->d_levels.get(), sizeof(float2) * n, hipMemcpyDeviceToHost, p->lev_stream));
+        HIPCHK(hipStreamSynchronize(p->lev_stream));
+        p->lev_host = true;
+    }
+    std::memcpy(dst, p->pin_levels.get(), sizeof(float2) * n);
+    return FDC_OK;
+    FDC_ENTRY_END
+}
+
+void *fdc_pipeline_levels_device(fdc_pipeline *p) { return p && p->levels_on ? static_cast<void *>(p->d_levels.get()) : nullptr; }
 
 }  // extern "C"

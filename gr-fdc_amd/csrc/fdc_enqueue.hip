@@ -146,6 +146,7 @@ static bool iq_fused(const fdc_pipeline *p, const DeviceCall &call, bool few)
 // (whole call: one layout)
 static bool oq_fused(const fdc_pipeline *p, const DeviceCall &call, int nblocks)
 {
+    if (call.levels) return false;           // the levels are of the float samples: float, the levels pass, then narrowed (every path, path 5 included)
     if (!int_kernels(p, call)) return false;
     if (p->fused) return true;
     if (p->fine_on) return false;            // the banks' kernels do not turn their samples: float, k_fine_rotate, then narrowed
@@ -183,9 +184,17 @@ int process_device_impl(fdc_pipeline *p, DeviceCall &call, const void *d_ring, i
     const unsigned out_bytes = (unsigned)((int64_t)nblocks * p->sum_lout * (int64_t)osz);
     // fine tuning: path 5 turns the samples in its own stores; everywhere else k_fine_rotate goes over the launch group's float results behind its channel kernels
     const bool fine = p->fine_on && p->C > 0, fine_fused = fine && p->fused && !d_spectrum;
-    auto rotate = [&](const Span &g) -> int {
-        if (fine) HIPCHK(fdc::launch_fine_rotate(o, p->d_chans, p->d_fine, p->d_fstep, p->C, g.nb, g.m0, g.nblocks, g.first_block, s));
+    // channel levels: one pass over the launch group's float results (k_chan_levels), behind the rotation — or inside it: with both settings on,
+    // off path 5, k_fine_rotate reduces the turned samples it holds and no second trip over the output is made
+    float2 *const lev = p->C > 0 ? call.levels : nullptr;
+    const bool lev_merged = lev && fine && !fine_fused && !p->levels_separate;
+    auto levels = [&](const Span &g) -> int {
+        if (lev) HIPCHK(fdc::launch_chan_levels(o, p->d_chans, lev, p->C, g.nb, g.m0, g.nblocks, s));
         return FDC_OK;
+    };
+    auto rotate = [&](const Span &g) -> int {
+        if (fine) HIPCHK(fdc::launch_fine_rotate(o, p->d_chans, p->d_fine, p->d_fstep, p->C, g.nb, g.m0, g.nblocks, g.first_block, s, lev_merged ? lev : nullptr));
+        return lev_merged ? FDC_OK : levels(g);
     };
     for (int m0 = 0; m0 < nblocks; m0 += p->chunk) {
         const int nb = std::min(p->chunk, nblocks - m0);
@@ -231,6 +240,7 @@ int process_device_impl(fdc_pipeline *p, DeviceCall &call, const void *d_ring, i
             else
                 HIPCHK(fdc::launch_fused4096(in0, (size_t)p->H, o, nb, p->R, m0, nblocks, first_block, p->d_tw, p->ntab, p->d_wins, p->d_f4rows, p->f4_cls, p->f4_teams, s, wf));
             if (tg) { HIPCHK(hipEventRecord(p->events[span[1]], s)); span[2] = span[3] = span[1]; span[4] = kSpanBanks; p->ev_spans.push_back(span); }
+            RCCHK(levels(grp));
             continue;
         }
         if (use_poly && p->poly_block && !(few && two_launch_possible(p))) {
@@ -307,7 +317,13 @@ int process_device_impl(fdc_pipeline *p, DeviceCall &call, const void *d_ring, i
     }
     if (ofmt && !ofused && call.narrow && p->C > 0) HIPCHK(fdc::launch_complex_to_iq(ofmt, call.oscale, call.fout, d_out, (size_t)nblocks * p->sum_lout, s));
     if (fine) p->fine_route = fine_fused ? "fused" : "rotated";
+    if (lev) p->levels_route = lev_merged ? "with the rotation" : "pass";
     return FDC_OK;
+}
+
+void levels_written(fdc_pipeline *p, int nblocks, hipStream_t stream, bool host)
+{
+    p->lev_blocks = nblocks; p->lev_stream = stream; p->lev_host = host;
 }
 
 // how the last integer-input / integer-output call was served (fdc_pipeline_describe): "<sc16|sc8>: fused", or what it was instead
@@ -318,18 +334,27 @@ std::string route(int fmt, bool fused, const char *otherwise)
 
 // The device entries with the handle's output format: integer output needs the float staging (p->d_out, max_blocks*sum_lout samples, allocated by
 // fdc_pipeline_set_output_format, never on this enqueue path) where the call's kernels do not narrow themselves
+// Channel levels (p->levels_on): the call's levels go to the handle's buffer ([max_blocks][C], allocated by fdc_pipeline_set_levels), so such a call
+// needs nblocks <= max_blocks too; nothing is enqueued otherwise
 static int process_device_oq(fdc_pipeline *p, DeviceCall &call, const void *d_ring, int64_t first_block, int nblocks, void *d_out)
 {
     const int ofmt = p->out_form;
-    if (!ofmt || nblocks <= 0) return process_device_impl(p, call, d_ring, first_block, nblocks, d_out);
-    call.ofmt = ofmt; call.oscale = p->out_scale; call.fout = p->d_out;
-    if (!oq_fused(p, call, nblocks)) {
-        if (nblocks > p->cfg.max_blocks)
-            return set_error(FDC_ERR_INVALID_ARGUMENT, "integer output on this plan: nblocks %d above max_blocks %d", nblocks, p->cfg.max_blocks);
-        if (!p->d_out && p->sum_lout > 0) return set_error(FDC_ERR_HIP, "integer output: no float staging");
+    const bool lev = p->levels_on && nblocks > 0;
+    if (lev) {
+        if (nblocks > p->cfg.max_blocks) return set_error(FDC_ERR_INVALID_ARGUMENT, "channel levels: nblocks %d above max_blocks %d", nblocks, p->cfg.max_blocks);
+        call.levels = p->d_levels;
+    }
+    if (ofmt && nblocks > 0) {
+        call.ofmt = ofmt; call.oscale = p->out_scale; call.fout = p->d_out;
+        if (!oq_fused(p, call, nblocks)) {
+            if (nblocks > p->cfg.max_blocks)
+                return set_error(FDC_ERR_INVALID_ARGUMENT, "integer output on this plan: nblocks %d above max_blocks %d", nblocks, p->cfg.max_blocks);
+            if (!p->d_out && p->sum_lout > 0) return set_error(FDC_ERR_HIP, "integer output: no float staging");
+        }
     }
     const int rc = process_device_impl(p, call, d_ring, first_block, nblocks, d_out);
-    if (rc == FDC_OK) p->oq_route = route(ofmt, call.ofused, "narrowed");
+    if (rc == FDC_OK && ofmt && nblocks > 0) p->oq_route = route(ofmt, call.ofused, "narrowed");
+    if (rc == FDC_OK && lev) levels_written(p, nblocks, call.stream, false);
     return rc;
 }
 
@@ -386,6 +411,7 @@ int fdc_pipeline_process_device_power(fdc_pipeline *p, const void *d_ring, int64
     if (!p) return set_error(FDC_ERR_INVALID_ARGUMENT, "null handle");
     if (p->out_form) return set_error(FDC_ERR_INVALID_ARGUMENT, "fdc_pipeline_process_device_power writes complex float outputs only (the handle's output format is not FC32)");
     if (p->fine_on) return set_error(FDC_ERR_INVALID_ARGUMENT, "fdc_pipeline_process_device_power writes the channels as they are cut: switch fine tuning off first");
+    if (p->levels_on) return set_error(FDC_ERR_INVALID_ARGUMENT, "fdc_pipeline_process_device_power gives no channel levels: switch them off first (fdc_pipeline_set_levels(p, 0))");
     if (d_group_power && (!d_spectrum || (p->N & 15))) return set_error(FDC_ERR_INVALID_ARGUMENT, "group powers go with a spectrum output of a block length that is a multiple of 16");
     DeviceCall call = device_call(p, stream, d_spectrum);
     call.gpow = static_cast<float *>(d_group_power);

@@ -1018,47 +1018,224 @@ hipError_t launch_complex_to_iq(int fmt, float scale, const float2 *in, void *ou
     return hipGetLastError();
 }
 
+// Channel levels (fdc_pipeline_set_levels): power = sum of re^2 + im^2 and peak = max of |re|, |im| (fmax: a NaN component is passed over) of one row —
+// the lout samples of one (block, channel).  ONE ORDER PER SUM: the bits of a row's power depend on lout and the row's samples only.  The row goes to
+// 2^lev_log2_lanes(lout) lanes of one wave, by lout alone; lane `sub` takes the sample PAIRS sub, sub + lanes, ... in index order, of a pair the even
+// sample first; a term is (re re + im im), each product and each sum rounded on its own (no FMA contraction, as fine_mul and oq_bits); the lanes are
+// joined by an xor butterfly from distance 1 upwards.  Both access widths of both kernels (k_chan_levels, k_fine_rotate<true>) keep exactly this, so
+// neither the row's alignment nor how the stream was cut, nor which kernel summed it, shows in the result.  No atomics, no LDS.
+struct LevAcc { float sum, peak; };
+
+__device__ __forceinline__ unsigned lev_log2_lanes(unsigned lout)
+{
+    const unsigned npair = (lout + 1) >> 1;
+    const unsigned lg = npair <= 1 ? 0 : 32 - (unsigned)__clz((int)(npair - 1));
+    return lg > 6 ? 6 : lg;
+}
+
+// a lane starts from (0, NaN): a lane without samples adds +0 and its NaN is passed over by fmax; a row of NaN only keeps NaN (np.fmax.reduce)
+__device__ __forceinline__ LevAcc lev_zero() { return LevAcc{0.0f, __builtin_nanf("")}; }
+
+__device__ __forceinline__ void lev_add(LevAcc &a, cf y)
+{
+#pragma clang fp contract(off)
+    const float p = y.x * y.x, q = y.y * y.y;
+    const float t = p + q;
+    a.sum = a.sum + t;
+    a.peak = fmaxf(a.peak, fmaxf(fabsf(y.x), fabsf(y.y)));
+}
+
+// the row's 2^lg lanes joined: every lane of the row ends with the row's values (float addition commutes, so with the same bits)
+__device__ __forceinline__ void lev_join(LevAcc &a, unsigned lg)
+{
+    for (unsigned d = 1; d < (1u << lg); d <<= 1) {
+        a.sum = a.sum + __shfl_xor(a.sum, (int)d, 64);
+        a.peak = fmaxf(a.peak, __shfl_xor(a.peak, (int)d, 64));
+    }
+}
+
 // Fine tuning behind the channel kernels of a launch group (fdc_fine.hpp): blocks [mbase, mbase + nb) of the call's channel-major float outputs, in place.
 // A channel's rows of the group are one contiguous run; a row — one (block, channel): lout samples, one base — goes to a power-of-two set of lanes of
 // a wave, 16 bytes per lane and access where the row allows it (lout even, the run 16-byte aligned; the step table's rows start at even offsets).
+// LEVELS (fine tuning and channel levels both on): the turned samples are reduced while the lane holds them and one lane of the row stores
+// levels[(mbase + m) * nchan + c]; the lanes take sample pairs in both access widths (the levels' one order, above).  LEVELS = false is the kernel as it was.
+// (LV: the two arguments only the LEVELS form has — float2 *levels, int nchan — so that k_fine_rotate<false> keeps the parent's argument block too)
+template <bool LEVELS, class... LV>
 __global__ __launch_bounds__(256) void k_fine_rotate(float2 *out, const ChanDev *__restrict__ chans, const FineChan *__restrict__ fine,
                                                      const float2 *__restrict__ step, int c0, int nb, int mbase, long long nb_call,
-                                                     unsigned long long first_block)
+                                                     unsigned long long first_block, LV... lv)
 {
+    static_assert(sizeof...(LV) == (LEVELS ? 2 : 0), "k_fine_rotate<true, float2 *, int> or k_fine_rotate<false>");
     const int c = c0 + (int)blockIdx.y;
     const unsigned lout = (unsigned)chans[c].lout;
     const FineChan fc = fine[c];
     float2 *o = out + nb_call * chans[c].out_off + (long long)mbase * lout;
     const float2 *st = step + fc.step_off;
     const bool wide = !(lout & 1) && (reinterpret_cast<uintptr_t>(o) & 15) == 0;
-    const unsigned per = wide ? lout >> 1 : lout;                              // accesses per row
-    unsigned lg = per <= 1 ? 0 : 32 - (unsigned)__clz((int)(per - 1));
-    if (lg > 6) lg = 6;
-    const unsigned lanes = 1u << lg, lane = threadIdx.x & 63, sub = lane & (lanes - 1), rows = 64u >> lg;
-    const unsigned wave = blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = gridDim.x * 4;
-    for (unsigned m = wave * rows + (lane >> lg); m < (unsigned)nb; m += nwaves * rows) {
-        const cf base = fine_base(fc.inc, first_block + (unsigned long long)(mbase + (int)m), lout);
-        float2 *row = o + (size_t)m * lout;
-        if (wide) {
-            for (unsigned i = sub; i < per; i += lanes) {
-                const float4 y = ld4(row + 2 * i), s = ld4(st + 2 * i);
-                st4(row + 2 * i, fine_rotate(mk(y.x, y.y), base, mk(s.x, s.y)), fine_rotate(mk(y.z, y.w), base, mk(s.z, s.w)));
+    if constexpr (LEVELS) {
+        struct Dst { float2 *levels; int nchan; };
+        const Dst dst{lv...};
+        float2 *const levels = dst.levels;
+        const int nchan = dst.nchan;
+        const unsigned npair = (lout + 1) >> 1, lg = lev_log2_lanes(lout);
+        const unsigned lanes = 1u << lg, lane = threadIdx.x & 63, sub = lane & (lanes - 1), rows = 64u >> lg;
+        const unsigned wave = blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = gridDim.x * 4;
+        // (whole waves leave together: the trip count depends on the wave alone, so every lane of a row is there for the butterfly)
+        for (unsigned m0 = wave * rows; m0 < (unsigned)nb; m0 += nwaves * rows) {
+            const unsigned m = m0 + (lane >> lg);
+            const bool live = m < (unsigned)nb;
+            LevAcc acc = lev_zero();
+            if (live) {
+                const cf base = fine_base(fc.inc, first_block + (unsigned long long)(mbase + (int)m), lout);
+                float2 *row = o + (size_t)m * lout;
+                if (wide) {
+                    for (unsigned i = sub; i < npair; i += lanes) {
+                        const float4 y = ld4(row + 2 * i), s = ld4(st + 2 * i);
+                        const cf a = fine_rotate(mk(y.x, y.y), base, mk(s.x, s.y)), b = fine_rotate(mk(y.z, y.w), base, mk(s.z, s.w));
+                        st4(row + 2 * i, a, b);
+                        lev_add(acc, a); lev_add(acc, b);
+                    }
+                } else {
+                    for (unsigned i = sub; i < npair; i += lanes) {
+                        const cf a = fine_rotate(ld2(row + 2 * i), base, ld2(st + 2 * i));
+                        st2(row + 2 * i, a);
+                        lev_add(acc, a);
+                        if (2 * i + 1 < lout) {
+                            const cf b = fine_rotate(ld2(row + 2 * i + 1), base, ld2(st + 2 * i + 1));
+                            st2(row + 2 * i + 1, b);
+                            lev_add(acc, b);
+                        }
+                    }
+                }
             }
-        } else {
-            for (unsigned i = sub; i < per; i += lanes) st2(row + i, fine_rotate(ld2(row + i), base, ld2(st + i)));
+            lev_join(acc, lg);
+            if (live && sub == 0) levels[(size_t)(mbase + (int)m) * (size_t)nchan + (size_t)c] = make_float2(acc.sum, acc.peak);
+        }
+    } else {
+        const unsigned per = wide ? lout >> 1 : lout;                              // accesses per row
+        unsigned lg = per <= 1 ? 0 : 32 - (unsigned)__clz((int)(per - 1));
+        if (lg > 6) lg = 6;
+        const unsigned lanes = 1u << lg, lane = threadIdx.x & 63, sub = lane & (lanes - 1), rows = 64u >> lg;
+        const unsigned wave = blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = gridDim.x * 4;
+        for (unsigned m = wave * rows + (lane >> lg); m < (unsigned)nb; m += nwaves * rows) {
+            const cf base = fine_base(fc.inc, first_block + (unsigned long long)(mbase + (int)m), lout);
+            float2 *row = o + (size_t)m * lout;
+            if (wide) {
+                for (unsigned i = sub; i < per; i += lanes) {
+                    const float4 y = ld4(row + 2 * i), s = ld4(st + 2 * i);
+                    st4(row + 2 * i, fine_rotate(mk(y.x, y.y), base, mk(s.x, s.y)), fine_rotate(mk(y.z, y.w), base, mk(s.z, s.w)));
+                }
+            } else {
+                for (unsigned i = sub; i < per; i += lanes) st2(row + i, fine_rotate(ld2(row + i), base, ld2(st + i)));
+            }
         }
     }
 }
 
+// levels: null = fine tuning alone; else the levels of the call's block 0 ([block][nchan] float2): the turned samples are reduced in the same pass
 hipError_t launch_fine_rotate(float2 *out, const ChanDev *chans, const FineChan *fine, const float2 *step, int nchan, int nb_chunk, int mbase, int nb_call,
-                              int64_t first_block, hipStream_t s)
+                              int64_t first_block, hipStream_t s, float2 *levels)
 {
     if (nchan <= 0 || nb_chunk <= 0) return hipSuccess;
     for (int c0 = 0; c0 < nchan; c0 += 32768) {
         const int nc = nchan - c0 < 32768 ? nchan - c0 : 32768;
         const int gx = std::max(1, std::min((nb_chunk + 3) / 4, (2048 + nc - 1) / nc));      // grid-stride over the rows: about eight workgroups per unit
-        hipLaunchKernelGGL(k_fine_rotate, dim3((unsigned)gx, (unsigned)nc), dim3(256), 0, s, out, chans, fine, step, c0, nb_chunk, mbase, (long long)nb_call,
-                           (unsigned long long)first_block);
+        if (levels)
+            hipLaunchKernelGGL((k_fine_rotate<true, float2 *, int>), dim3((unsigned)gx, (unsigned)nc), dim3(256), 0, s, out, chans, fine, step, c0, nb_chunk, mbase,
+                               (long long)nb_call, (unsigned long long)first_block, levels, nchan);
+        else
+            hipLaunchKernelGGL(k_fine_rotate<false>, dim3((unsigned)gx, (unsigned)nc), dim3(256), 0, s, out, chans, fine, step, c0, nb_chunk, mbase,
+                               (long long)nb_call, (unsigned long long)first_block);
+    }
+    return hipGetLastError();
+}
+
+// Channel levels of a launch group: blocks [mbase, mbase + nb) of the call's channel-major float outputs, read once; one float2 (power, peak) per
+// (block, channel) goes to levels[(mbase + m) * nchan + c] and nothing else is written.  k_fine_rotate's shape: grid y = channel, a row on a
+// power-of-two set of lanes of one wave (by lout: the levels' one order, above), 16 bytes per lane where the run is 16-byte aligned and lout even, two
+// 8-byte loads otherwise, a grid-stride loop over the blocks.  A trip issues all its loads — four pairs per lane: four rows where a row is one pair per
+// lane, four steps along a longer row — before the first is used.
+// (no branch around a load: a lane without a pair of its own loads one that exists — the row's last pair, the group's last row — and leaves it out of
+// its sums, so that the four loads of a trip are in flight together and not each behind its own wait)
+template <bool WIDE>
+__device__ __forceinline__ void lev_load(const float2 *row, unsigned i, unsigned lout, cf &a, cf &b)
+{
+    if (WIDE) {
+        const float4 y = ld4(row + 2 * i);
+        a = mk(y.x, y.y); b = mk(y.z, y.w);
+    } else {
+        a = ld2(row + 2 * i);
+        b = ld2(row + (2 * i + 1 < lout ? 2 * i + 1 : lout - 1));
+    }
+}
+
+template <bool WIDE>
+__device__ __forceinline__ void chan_levels_rows(const float2 *o, float2 *__restrict__ levels, unsigned lout, unsigned nb, int mbase, int nchan, int c)
+{
+    const unsigned npair = (lout + 1) >> 1, lg = lev_log2_lanes(lout);
+    const unsigned lanes = 1u << lg, lane = threadIdx.x & 63, sub = lane & (lanes - 1), rows = 64u >> lg;
+    const unsigned wave = blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = gridDim.x * 4;
+    if (npair <= lanes) {
+        // a row is at most one pair per lane: four rows per trip, a grid stride apart
+        const bool has = sub < npair, two = 2 * sub + 1 < lout;
+        const unsigned i = has ? sub : npair - 1;
+        for (unsigned m0 = wave * rows; m0 < nb; m0 += 4 * nwaves * rows) {
+            cf a[4], b[4];
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                const unsigned m = m0 + (unsigned)u * nwaves * rows + (lane >> lg);
+                lev_load<WIDE>(o + (size_t)(m < nb ? m : nb - 1) * lout, i, lout, a[u], b[u]);
+            }
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                const unsigned m = m0 + (unsigned)u * nwaves * rows + (lane >> lg);
+                LevAcc acc = lev_zero();
+                if (has) { lev_add(acc, a[u]); if (two) lev_add(acc, b[u]); }
+                lev_join(acc, lg);
+                if (m < nb && sub == 0) levels[(size_t)(mbase + (int)m) * (size_t)nchan + (size_t)c] = make_float2(acc.sum, acc.peak);
+            }
+        }
+    } else {
+        // a long row (more than 64 pairs) takes the whole wave: four steps of the row per trip, in index order
+        for (unsigned m = wave; m < nb; m += nwaves) {
+            const float2 *row = o + (size_t)m * lout;
+            LevAcc acc = lev_zero();
+            for (unsigned i0 = sub; i0 < npair; i0 += 4 * lanes) {
+                cf a[4], b[4];
+#pragma unroll
+                for (int u = 0; u < 4; u++) {
+                    const unsigned i = i0 + (unsigned)u * lanes;
+                    lev_load<WIDE>(row, i < npair ? i : npair - 1, lout, a[u], b[u]);
+                }
+#pragma unroll
+                for (int u = 0; u < 4; u++) {
+                    const unsigned i = i0 + (unsigned)u * lanes;
+                    if (i < npair) { lev_add(acc, a[u]); if (2 * i + 1 < lout) lev_add(acc, b[u]); }
+                }
+            }
+            lev_join(acc, lg);
+            if (sub == 0) levels[(size_t)(mbase + (int)m) * (size_t)nchan + (size_t)c] = make_float2(acc.sum, acc.peak);
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_chan_levels(const float2 *__restrict__ out, const ChanDev *__restrict__ chans, float2 *__restrict__ levels, int c0,
+                                                     int nchan, int nb, int mbase, long long nb_call)
+{
+    const int c = c0 + (int)blockIdx.y;
+    const unsigned lout = (unsigned)chans[c].lout;
+    const float2 *o = out + nb_call * chans[c].out_off + (long long)mbase * lout;
+    if (!(lout & 1) && (reinterpret_cast<uintptr_t>(o) & 15) == 0) chan_levels_rows<true>(o, levels, lout, (unsigned)nb, mbase, nchan, c);
+    else chan_levels_rows<false>(o, levels, lout, (unsigned)nb, mbase, nchan, c);
+}
+
+hipError_t launch_chan_levels(const float2 *out, const ChanDev *chans, float2 *levels, int nchan, int nb_chunk, int mbase, int nb_call, hipStream_t s)
+{
+    if (nchan <= 0 || nb_chunk <= 0) return hipSuccess;
+    for (int c0 = 0; c0 < nchan; c0 += 32768) {
+        const int nc = nchan - c0 < 32768 ? nchan - c0 : 32768;
+        const int gx = std::max(1, std::min((nb_chunk + 3) / 4, (2048 + nc - 1) / nc));      // grid-stride over the rows: about eight workgroups per unit
+        hipLaunchKernelGGL(k_chan_levels, dim3((unsigned)gx, (unsigned)nc), dim3(256), 0, s, out, chans, levels, c0, nchan, nb_chunk, mbase, (long long)nb_call);
     }
     return hipGetLastError();
 }

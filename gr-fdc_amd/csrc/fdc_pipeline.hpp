@@ -163,6 +163,17 @@ struct fdc_pipeline {
     fdc::DevBuf<fdc::FineChan> d_fine, d_f4fine;
     fdc::DevBuf<float2> d_fstep;
     std::string fine_route;      // how the last call with fine tuning was served (fdc_pipeline_describe)
+    // channel levels (fdc_pipeline_set_levels): a setting like the two above.  d_levels: [max_blocks][C] (power, peak) of the last call, row = block of the
+    // call; pin_levels its pinned twin, which a host entry fills in front of its synchronise (lev_host) and fdc_pipeline_levels fills after a device entry,
+    // behind a synchronise of the stream that one ran on (lev_stream).  Both are allocated by the first call that switches the setting on.
+    bool levels_on = false;
+    bool levels_separate = false;   // FDC_LEVELS_SEPARATE=1 (debug environment): rotation and levels as two passes where one merged pass would run (A/B testing)
+    fdc::DevBuf<float2> d_levels;
+    fdc::PinBuf<float2> pin_levels;
+    int lev_blocks = -1;         // block count of the last successful work call with levels on (-1: none yet)
+    bool lev_host = false;
+    hipStream_t lev_stream = nullptr;
+    std::string levels_route;    // how the last call with levels was served (fdc_pipeline_describe)
     fdc::DevBuf<float2> d_out;   // work(): max_blocks*sum_lout (out_staging)
     int64_t blockcount = 0;      // work(): blocks consumed so far
     // work(): transfers and kernels of consecutive sub-batches overlap (H2D on s_in, kernels on stream, D2H on s_out)
@@ -213,6 +224,9 @@ struct DeviceCall {
     float *gpow = nullptr; const float2 *gpow_origin = nullptr;
     // waterfall rows (path 5: the fused kernel's epilogue): the row sums of the stream's block b go to rows + (b - rows_first) * 1024
     float *rows = nullptr; int64_t rows_first = 0;
+    // channel levels (fdc_pipeline_set_levels): where (power, peak) of the call's block 0, channel 0 go, [block][C]; null = none.  With them the kernels
+    // write float whatever the output format (the levels are of the float samples; the narrowing comes behind)
+    float2 *levels = nullptr;
     int ncu = 0;                         // compute units the call's persistent kernels may use
     // results: no launch group had to be widened (each read the integer input in its own loads); the call's kernels narrowed in their own stores
     bool all_fused = true, ofused = false;
@@ -256,6 +270,7 @@ DeviceCall device_call(const fdc_pipeline *p, void *stream, void *d_spectrum, in
 int process_device_impl(fdc_pipeline *p, DeviceCall &call, const void *d_ring, int64_t first_block, int nblocks, void *d_out);
 int channels_wide(fdc_pipeline *p, const float2 *spec, float2 *d_out, const int32_t *d_gids, int ngroup, int l, const Span &span, hipStream_t s);
 int check_iq_form(int32_t format, float scale);
+void levels_written(fdc_pipeline *p, int nblocks, hipStream_t stream, bool host);   // a call with levels on succeeded: what fdc_pipeline_levels hands out
 std::string route(int fmt, bool fused, const char *otherwise);   // "<sc16|sc8>: fused", or what the call was instead (fdc_pipeline_describe)
 
 } }  // namespace fdc::pipe

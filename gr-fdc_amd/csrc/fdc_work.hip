@@ -10,11 +10,22 @@ using namespace fdc::pipe;
 extern "C" {
 
 // the entries that write complex float only (sinks, spectrum items, group powers, waterfall): refused while the output format is not FC32
-// (and, but for the flush of a batch that is inside already, while fine tuning is on: they write the channels as they are cut)
+// (and, but for the flush of a batch that is inside already, while fine tuning is on: they write the channels as they are cut; and while channel
+// levels are on: they give none)
 static int check_float_output(const fdc_pipeline *p, const char *entry, bool writes_channels = true)
 {
     if (p && p->out_form) return set_error(FDC_ERR_INVALID_ARGUMENT, "%s writes complex float outputs only: set the output format to FDC_OQ_FC32 first", entry);
     if (p && p->fine_on && writes_channels) return set_error(FDC_ERR_INVALID_ARGUMENT, "%s writes the channels as they are cut: switch fine tuning off first (fdc_pipeline_set_fine_tuning(p, NULL, C))", entry);
+    if (p && p->levels_on && writes_channels) return set_error(FDC_ERR_INVALID_ARGUMENT, "%s gives no channel levels: switch them off first (fdc_pipeline_set_levels(p, 0))", entry);
+    return FDC_OK;
+}
+
+// Channel levels of a host entry's call: one copy of its nblocks*C (power, peak) pairs to the pinned twin, enqueued in front of the call's synchronise,
+// so that fdc_pipeline_levels is a memcpy
+static int levels_home(fdc_pipeline *p, int nblocks, hipStream_t s)
+{
+    if (p->levels_on && p->C > 0)
+        HIPCHK(hipMemcpyAsync(p->pin_levels.get(), p->d_levels.get(), sizeof(float2) * (size_t)nblocks * p->C, hipMemcpyDeviceToHost, s));
     return FDC_OK;
 }
 
@@ -168,8 +179,10 @@ static int pipeline_work_impl(fdc_pipeline *p, DeviceCall call, const void *in, 
     bool oq_all = true;
     // dok: the float results of the sub-batch starting at block b0.  Integer output: its narrow results go to the same sample offset of d_oq (call.ofused: the
     // kernels wrote them there themselves; otherwise dok holds float and is narrowed into d_oq, unless the outputs are registered: k_scatter_oq narrows)
+    // (channel levels: a sub-batch is a call of its own to the enqueue path, so each hands in where ITS block 0 goes)
     auto process = [&](size_t b0, int nb, int64_t first, float2 *dok, float2 *dspec) {
         call.spectrum = dspec; call.fout = dok;
+        call.levels = p->levels_on && p->C > 0 ? p->d_levels + b0 * (size_t)p->C : nullptr;
         const int rc2 = process_device_impl(p, call, ringb + b0 * p->H * esz, first, nb,
                                             ofmt ? static_cast<void *>(p->d_oq + osz * b0 * (size_t)p->sum_lout) : static_cast<void *>(dok));
         oq_all = oq_all && call.ofused;
@@ -214,7 +227,9 @@ static int pipeline_work_impl(fdc_pipeline *p, DeviceCall call, const void *in, 
         }
         if (spectrum) HIPCHK(hipMemcpyAsync(spectrum, d_specfull, sizeof(float2) * (size_t)nblocks * p->N, hipMemcpyDeviceToHost, s));
         HIPCHK(hipMemcpyAsync(ringb, ringb + esz * nin, esz * (size_t)p->ovl, hipMemcpyDeviceToDevice, s));
+        RCCHK(levels_home(p, nblocks, s));
         HIPCHK(hipStreamSynchronize(s));
+        if (p->levels_on) levels_written(p, nblocks, s, true);
         if (fmt) p->iq_route = route(fmt, call.all_fused, "widened");
         if (ofmt) p->oq_route = route(ofmt, oq_all, "narrowed");
         if (p->C > 0 && !out_reg) deliver(0, 0, nblocks);
@@ -276,8 +291,10 @@ static int pipeline_work_impl(fdc_pipeline *p, DeviceCall call, const void *in, 
     if (spectrum) HIPCHK(hipMemcpyAsync(spectrum, d_specfull, sizeof(float2) * (size_t)nblocks * p->N, hipMemcpyDeviceToHost, s));
     // history <- last ovl samples of this call (overlap_save_impl.cc:78); src and dst never overlap (H >= ovl)
     HIPCHK(hipMemcpyAsync(ringb, ringb + esz * nin, esz * (size_t)p->ovl, hipMemcpyDeviceToDevice, s));
+    RCCHK(levels_home(p, nblocks, s));
     HIPCHK(hipStreamSynchronize(s));
     HIPCHK(hipStreamSynchronize(p->s_out));
+    if (p->levels_on) levels_written(p, nblocks, s, true);
     if (fmt) p->iq_route = route(fmt, call.all_fused, "widened");
     if (ofmt) p->oq_route = route(ofmt, oq_all, "narrowed");
     p->blockcount += nblocks;
@@ -369,11 +386,14 @@ static int pipeline_work_real_impl(fdc_pipeline *p, const void *in, int nblocks,
     void *const res = ofmt ? static_cast<void *>(p->d_oq) : static_cast<void *>(p->d_out);
     DeviceCall call = device_call(p, nullptr, d_specfull);
     call.ofmt = ofmt; call.oscale = p->out_scale; call.fout = p->d_out;
+    call.levels = p->levels_on && p->C > 0 ? p->d_levels.get() : nullptr;
     RCCHK(process_device_impl(p, call, p->d_ring, p->blockcount, nblocks, res));
     RCCHK(copy_outputs(p, outs, nblocks, osz, res, s));
     if (spectrum) HIPCHK(hipMemcpyAsync(spectrum, d_specfull, sizeof(float2) * (size_t)nblocks * p->N, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(p->d_ring, p->d_ring + nin, sizeof(float2) * (size_t)p->ovl, hipMemcpyDeviceToDevice, s));
+    RCCHK(levels_home(p, nblocks, s));
     HIPCHK(hipStreamSynchronize(s));
+    if (p->levels_on) levels_written(p, nblocks, s, true);
     if (ofmt) p->oq_route = route(ofmt, call.ofused, "narrowed");
     p->blockcount += nblocks;
     return nblocks;

@@ -210,6 +210,39 @@ int fdc_pipeline_set_output_format(fdc_pipeline *p, int32_t format, float scale)
 int fdc_fine_tuning_increment(double nu, uint64_t *inc);
 int fdc_pipeline_set_fine_tuning(fdc_pipeline *p, const double *nu, int n);
 
+/* CHANNEL LEVELS: per-block power and peak of every channel, summed on the device (meters, squelch, occupancy, an AGC that sets the next call's output
+ * scale — without pulling the float streams over the link).  With levels on, every (block m of the call, channel c) gets two float32 values from the
+ * lout_c samples the call produces for it:
+ *     power[m][c] = sum_j (re_j^2 + im_j^2)        peak[m][c] = max_j max(|re_j|, |im_j|)   (fmax: a NaN component is passed over)
+ * of the complex float32 samples y' the entry writes, or would write before narrowing: AFTER fine tuning, BEFORE the sc16 / sc8 narrowing.  So
+ * peak * |scale| >= 32767.5 (sc16) or >= 127.5 (sc8) means some component of that row saturated in the narrowing.  Layout: levels[m][c] = (power, peak),
+ * float[nblocks][C][2], c the plan's channel index (a channel that is a copy of another channel's slice has its own entry).  Rows with samples that are
+ * not finite give what IEEE arithmetic and fmax give; nothing traps and no other row is disturbed.  The bits of power[m][c] depend on lout_c and the
+ * row's sample values only (one lane assignment and one summation tree per lout, no FMA contraction, no atomics): not on the row's address, not on how
+ * the stream is cut into calls, sub-batches, launch groups or spans, not on which kernel summed it.  |power - P| <= (lout_c + 8) 2^-24 P against the exact
+ * sum of squares P of the float32 samples; peak is exact.
+ *   fdc_pipeline_set_levels      on != 0 / 0.  A SETTING like fdc_pipeline_set_output_format and fdc_pipeline_set_fine_tuning: it may change between any
+ *                                two calls and applies from the next one; it does not touch the history, the block counter or the input-form latch, and
+ *                                survives fdc_pipeline_reset; refused while a pipelined sinks batch is inside the handle; it waits for the handle's own
+ *                                stream first.  The first call that switches it on allocates everything the feature needs, once (max_blocks*C pairs on
+ *                                the device and pinned on the host); nothing in a work call, nothing inside a device entry.  With C = 0, on is accepted
+ *                                and every result is empty.
+ *   fdc_pipeline_levels          the levels of the last successful work call (host or device entry; a device entry's are read after a synchronise of
+ *                                the stream it ran on): dst receives nblocks*C*2 floats.  nblocks must be that call's block count, otherwise
+ *                                FDC_ERR_INVALID_ARGUMENT; the same while levels are off and before any call.  A call of 0 blocks leaves the previous
+ *                                result in place.
+ *   fdc_pipeline_levels_device   the device buffer ([block of the call][C] float2), NULL while off: for callers of fdc_pipeline_process_device /
+ *                                _process_device_iq, who read it ordered on their own stream.  While levels are on, a device call needs
+ *                                nblocks <= max_blocks (the rule of a narrowed device call): above it FDC_ERR_INVALID_ARGUMENT, nothing enqueued.
+ * While levels are on, fdc_pipeline_work_sinks, _work_spectrum, _process_device_power and fdc_pipeline_work_waterfall return FDC_ERR_INVALID_ARGUMENT and
+ * change nothing (fdc_pipeline_flush_sinks still flushes a batch that is inside), and every plan writes complex float first: with integer output the
+ * samples are narrowed behind the levels ("output sc16: narrowed"; "fused" again once levels are off).  One pass over the launch group's results reads
+ * them once (fdc_pipeline_describe: "levels: pass"); with fine tuning on, off path 5, the rotation's pass reduces the turned samples it holds and no
+ * second trip is made ("levels: with the rotation"). */
+int fdc_pipeline_set_levels(fdc_pipeline *p, int32_t on);
+int fdc_pipeline_levels(fdc_pipeline *p, float *dst, int nblocks);
+void *fdc_pipeline_levels_device(fdc_pipeline *p);
+
 /* Optional: pin a host range that will be handed to fdc_pipeline_work() again and again (GNU Radio's circular buffers
  * live as long as the flowgraph: register them in start(), unregister in stop()).  A call whose `in` lies in a
  * registered range is DMA'd from it in place, and when every outs[c] does, the results are stored straight into
@@ -324,6 +357,11 @@ int fdc_pipeline_group_set_output_format(fdc_pipeline_group *g, int32_t format, 
 /* fine tuning for every member (fdc_pipeline_set_fine_tuning: the same arguments, refusals and setting semantics); the spans carry their global block
  * index, so a group's output is one handle's */
 int fdc_pipeline_group_set_fine_tuning(fdc_pipeline_group *g, const double *nu, int n);
+/* channel levels for every member (fdc_pipeline_set_levels: the same argument, refusals and setting semantics), and the levels of the last group call:
+ * the members' spans (fdc_pipeline_group_last_spans) put together in block order, nblocks*C*2 floats with the bits one handle gives for the same call;
+ * nblocks must be that call's block count (FDC_ERR_INVALID_ARGUMENT otherwise, while levels are off and before any call) */
+int fdc_pipeline_group_set_levels(fdc_pipeline_group *g, int32_t on);
+int fdc_pipeline_group_levels(fdc_pipeline_group *g, float *dst, int nblocks);
 int32_t fdc_pipeline_group_size(const fdc_pipeline_group *g);
 fdc_pipeline *fdc_pipeline_group_member(fdc_pipeline_group *g, int i);   /* owned by the group (fdc_pipeline_path, sizes, timing) */
 int32_t fdc_pipeline_group_device(const fdc_pipeline_group *g, int i);
