@@ -27,8 +27,10 @@
 // XCD take CONSECUTIVE blocks in the same round, so the shared half is fetched from memory once and served to the
 // neighbour from that XCD's L2.
 //
-// The arithmetic is the uniform-plan commutation of fdc_fast256.hip (same tables, same rounding points), so the
-// result matches k_p1 + k_p2 to the last few ulps; parity against the oracle: tests/test_parity_gpu.py.
+// The arithmetic is the uniform-plan commutation of fdc_fast256.hip with the same number of multiplications per value.  At N = 16384 the
+// tables and rounding points are the same too; at N = 32768 and 65536 stage 1 factors its tables otherwise (k_blk256, kSplit), so the
+// result matches k_p1 + k_p2 to a few ulps either way; parity against the oracle: tests/test_parity_gpu.py,
+// tests/test_block256_stage1_tables_gpu.py.
 #include "fdc_blockcommon.hpp"
 #include "fdc_iq.hpp"
 
@@ -61,13 +63,18 @@ struct BlkGeom {
     static constexpr int kTripBytes = 16 * kJT * kLd * 8;         // P = 8: 134144
     static constexpr int kOffCt = kTripBytes > kStripsEnd ? kTripBytes : kStripsEnd;   // stage-2 twiddles [32][P], behind the trip buffer and the strips
     static constexpr int kOffWrow = P == 8 ? 136960 : kOffCt + 32 * P * 8;   // tables: above the strips and the trip buffer
-    static constexpr int kOffB = kOffWrow + 16 * 18 * 8;
-    static constexpr int kOffSA = kOffB + 32 * 18 * 8;
-    static constexpr int kOffSoff = kOffSA + 16 * P * 18 * 8;
-    static constexpr int kLds = kOffSoff + kN1 * 4;               // P = 8: 163328 <= 163840
-    static constexpr int kOffSoffOff = kOffSA + 16 * P * 16 * 8;  // offset plans: unpadded SA rows, then soff, then wrowF
-    static constexpr int kOffWrowF = kOffSoffOff + kN1 * 4;
-    static constexpr int kLdsOff = kOffWrowF + 16 * 18 * 8;       // P = 8: 163584 <= 163840
+    // The stage-1 tables behind wrow.  kSplit (P > 2): the lane table LT (64 rows of 18), the wave rows UR ([kN1 / 4][16]) and the rows of CB
+    // ([P + 8][16]) — cb comes from LDS.  P = 2: Bt (32 rows of 18) and SA (16 P rows of 18), cb from memory: the on-grid form there runs two workgroups per CU on
+    // 81664 of 81920 bytes and has no room for the two wave tables.
+    static constexpr bool kSplit = P > 2;
+    static constexpr int kOffLT = kOffWrow + 16 * 18 * 8;
+    static constexpr int kOffUR = kOffLT + 64 * 18 * 8;
+    static constexpr int kOffB = kOffLT, kOffSA = kOffB + 32 * 18 * 8;
+    static constexpr int kOffSoff = kSplit ? kOffUR + kN1 * 4 * 8 : kOffSA + 16 * P * 18 * 8;
+    static constexpr int kOffCbl = kOffSoff + kN1 * 4;
+    static constexpr int kLds = kOffCbl + (kSplit ? (P + 8) * 16 * 8 : 0);   // P = 8: 159744; P = 2: 81664
+    static constexpr int kOffWrowF = kLds;                        // offset plans: the forward twiddle rows behind everything else
+    static constexpr int kLdsOff = kOffWrowF + 16 * 18 * 8;       // P = 8: 162048
     static_assert(kLdsOff <= 160 * 1024 && kLds <= 160 * 1024, "LDS budget");
     static_assert(kOffCt >= kStripsEnd && kOffCt + 32 * P * 8 <= kOffWrow, "stage-2 trip buffer and twiddles below the tables, tables above the strips");
     static_assert((16 * (kJB - 1) * kLd + 32 * (P - 1)) * 8 < 65536, "ds offsets of a base register");
@@ -119,12 +126,20 @@ __global__ FDC_PLAIN_DS __launch_bounds__(512, (P == 2 && !OFF && !R4 && !FWD) ?
     static_assert(!HALF || (!OFF && !FWD), "the half-slot form is a variant of the on-grid channelizer");
     constexpr int kN1 = GM::kN1, kLd = GM::kLd, kJT = GM::kJT, kJB = GM::kJB;
     float2 *scr = reinterpret_cast<float2 *>(fdc_smem_blk);                     // stage 1: 8 wave scratches; stage 2: the trip buffer
-    float2 *wrow = reinterpret_cast<float2 *>(fdc_smem_blk + GM::kOffWrow);     // [b][p] = W256^(b p), rows of 18
-    float2 *Bt = reinterpret_cast<float2 *>(fdc_smem_blk + GM::kOffB);             // [c5][q] = W_N^(16 c5 q)
-    float2 *SA = reinterpret_cast<float2 *>(fdc_smem_blk + GM::kOffSA);           // [pass][b][q] = shape[b+16q]/N * W_N^(512 pass q)
-    // offset plans need a second twiddle table: the SA rows give up their padding (2-way conflicts on 8 reads per pass)
-    constexpr int kSaLd = OFF ? 16 : 18;
-    unsigned *soff = reinterpret_cast<unsigned *>(fdc_smem_blk + (OFF ? GM::kOffSoffOff : GM::kOffSoff));
+    float2 *wrow = reinterpret_cast<float2 *>(fdc_smem_blk + GM::kOffWrow);     // [b][p - 1 mod 16] = W256^(b p), rows of 18 (ld_row_sh)
+    // The inter-pass twiddle times the window, W_N^(16 q (32 pass + c5)) shape[b + 16 q] / N, c5 = 4 wave + col, in two factors.
+    // kSplit: LT[lane = col + 4 b][q] = W_N^(16 q col) shape[b + 16 q] / N cbt[col][b] depends on the lane and on nothing else;
+    // UR[8 pass + wave][q] = W_N^(16 q (32 pass + 4 wave)) is the same for every lane of a wave (a broadcast read).  cbt[n1 = 32 pass + c5][b] =
+    // (-1)^n1 W_N^(n1 (b + r)) factors the same way: cbt[col][b] is in LT, CB[pass][b] = cbt[32 pass][b] and CB[P + wave][b] =
+    // cbt[4 wave][b] are read once per pass (the second is a constant of the lane, but there is no register to keep it in).
+    // P = 2: Bt[c5][q] = W_N^(16 c5 q) and SA[pass][b][q] = shape[b + 16 q] / N W_N^(512 pass q); cbt[n1][b] comes from memory a pass ahead.
+    constexpr bool kSplit = GM::kSplit;
+    float2 *LT = reinterpret_cast<float2 *>(fdc_smem_blk + GM::kOffLT);
+    float2 *UR = reinterpret_cast<float2 *>(fdc_smem_blk + GM::kOffUR);
+    float2 *CBL = reinterpret_cast<float2 *>(fdc_smem_blk + GM::kOffCbl);
+    float2 *Bt = reinterpret_cast<float2 *>(fdc_smem_blk + GM::kOffB);
+    float2 *SA = reinterpret_cast<float2 *>(fdc_smem_blk + GM::kOffSA);
+    unsigned *soff = reinterpret_cast<unsigned *>(fdc_smem_blk + GM::kOffSoff);
     float2 *ctab = reinterpret_cast<float2 *>(fdc_smem_blk + GM::kOffCt);       // [c5][klo] = W_N1^(c5 klo): stage 2, after the DFT-P
     const int tid = threadIdx.x;
     // stage-1 roles
@@ -152,10 +167,11 @@ __global__ FDC_PLAIN_DS __launch_bounds__(512, (P == 2 && !OFF && !R4 && !FWD) ?
         else return mk(__uint_as_float((unsigned)__builtin_amdgcn_raw_buffer_load_b16(r, voff, soff, kAux)), 0.f);
     };
     // the first block's rows are requested before the tables are built: their latency hides behind the table set-up
-    const __amdgpu_buffer_rsrc_t rcb = make_rsrc(cbt, (unsigned)kN1 * 16u * 8u);      // cbt[n1][b], n1 = 32 pass + c5
-    const unsigned voffc = (unsigned)(c5 * 16 + b) * 8u;
+    // P = 2 only (kSplit reads cb from LDS): cbt[n1][b], n1 = 32 pass + c5, from memory, requested a pass ahead into cbA / cbB
+    [[maybe_unused]] const __amdgpu_buffer_rsrc_t rcb = make_rsrc(cbt, (unsigned)kN1 * 16u * 8u);
+    [[maybe_unused]] const unsigned voffc = (unsigned)(c5 * 16 + b) * 8u;
     // two row sets: a pass computes on one while the rows of the next pass arrive in the other (no register copies between passes)
-    cf LA[16], LB[16], cbA, cbB;
+    cf LA[16], LB[16], cbA = mk(1.f, 0.f), cbB = cbA;           // (kSplit: cbA / cbB stay what they are here and are never read)
     {
         const __amdgpu_buffer_rsrc_t rin = make_rsrc(in + (size_t)first * in_stride, inbytes);
 #pragma unroll
@@ -163,7 +179,7 @@ __global__ FDC_PLAIN_DS __launch_bounds__(512, (P == 2 && !OFF && !R4 && !FWD) ?
             if constexpr (kIq) LA[a] = ld_in(rin, (unsigned)a * kRowGrp, std::integral_constant<int, 0>{});
             else LA[a] = bld2(rin, voff, (unsigned)a * kRowGrp);
         }
-        cbA = bld2(rcb, voffc, 0);
+        if constexpr (!kSplit) cbA = bld2(rcb, voffc, 0);
     }
     // ---- tables (once per workgroup; the workgroup is persistent)
     // Offset plans (every channel at f = 256*slot + r, OFF): the block is modulated by exp(-2 pi i r n / N), n = n1 + N1 (16a + b),
@@ -173,21 +189,36 @@ __global__ FDC_PLAIN_DS __launch_bounds__(512, (P == 2 && !OFF && !R4 && !FWD) ?
     float2 *wrowF = OFF ? reinterpret_cast<float2 *>(fdc_smem_blk + GM::kOffWrowF) : wrow;
     const int r16 = roff & 15;
     for (int i = tid; i < 256; i += 512) {
-        wrow[(i >> 4) * 18 + (i & 15)] = tw256[((i >> 4) * (i & 15)) & 255];
+        // entry p of a row sits at index p - 1, entry 0 behind entry 15: the used entries are whole 16-byte pairs (ld_row_sh)
+        const int ip = (i >> 4) * 18 + (((i & 15) - 1) & 15);
+        wrow[ip] = tw256[((i >> 4) * (i & 15)) & 255];
         if (OFF)     // entry [b][p]: the twiddle of register Z[p], whose true index is pt = (p - r) mod 16: W_256^(b (pt + r))
-            wrowF[(i >> 4) * 18 + (i & 15)] = tw256[((i >> 4) * ((((i & 15) - r16) & 15) + roff)) & 255];
+            wrowF[ip] = tw256[((i >> 4) * ((((i & 15) - r16) & 15) + roff)) & 255];
     }
     for (int i = tid; i < kN1; i += 512) {
         const long long o = slot_off[i];                  // slot i = klo + P khi, khi = k0 + 2 k1, is entry [klo][16 k0 + rev16(k1)]
         soff[(i % P) * 32 + ((i / P) & 1) * 16 + rev16((i / P) >> 1)] = o >= 0 ? (unsigned)((o * nb_call + out_base) * kOs) : 0xFFFFFFFFu;
     }
     for (int i = tid; i < 32 * P; i += 512) ctab[i] = tw256[((i / P) * (i % P) * (8 / P)) & 255];     // [c5][klo] = W_N1^(c5 klo)
-    Bt[(tid >> 4) * 18 + (tid & 15)] = twq[HALF ? tid ^ 8 : tid];   // c5 = tid >> 4 < 32, q = tid & 15 (HALF: the entry of q ^ 8)
-    for (int i = tid; i < 256 * P; i += 512) {
-        const int ps = i >> 8, bb = (i >> 4) & 15, q = i & 15, qt = HALF ? q ^ 8 : q;
-        const float2 t = twq[(size_t)(32 * ps) * 16 + qt];                       // W_N^(16 * 32 ps * q)
-        const float s = shn[bb + 16 * qt];
-        SA[(ps * 16 + bb) * kSaLd + q] = make_float2(t.x * s, t.y * s);
+    if constexpr (kSplit) {
+        for (int i = tid; i < 1024; i += 512) {
+            const int ln = i >> 4, q = i & 15, qt = HALF ? q ^ 8 : q;            // HALF: the entries of q ^ 8
+            const float2 t = twq[(ln & 3) * 16 + qt];                            // W_N^(16 col q)
+            const float s = shn[(ln >> 2) + 16 * qt];
+            const float2 e = make_float2(t.x * s, t.y * s), c = cbt[(ln & 3) * 16 + (ln >> 2)];
+            LT[ln * 18 + q] = make_float2(e.x * c.x - e.y * c.y, e.x * c.y + e.y * c.x);
+        }
+        for (int i = tid; i < kN1 * 4; i += 512) UR[i] = twq[(i >> 4) * 64 + (HALF ? (i & 15) ^ 8 : i & 15)];   // row 4 (i >> 4) of twq
+        if (tid < (P + 8) * 16)                                                  // rows 32 pass, then rows 4 wave of cbt
+            CBL[tid] = cbt[(tid < P * 16 ? (tid >> 4) * 512 : ((tid >> 4) - P) * 64) + (tid & 15)];
+    } else {
+        Bt[(tid >> 4) * 18 + (tid & 15)] = twq[HALF ? tid ^ 8 : tid];            // c5 = tid >> 4 < 32, q = tid & 15 (HALF: the entry of q ^ 8)
+        for (int i = tid; i < 256 * P; i += 512) {
+            const int ps = i >> 8, bb = (i >> 4) & 15, q = i & 15, qt = HALF ? q ^ 8 : q;
+            const float2 t = twq[(size_t)(32 * ps) * 16 + qt];                   // W_N^(16 * 32 ps * q)
+            const float s = shn[bb + 16 * qt];
+            SA[(ps * 16 + bb) * 18 + q] = make_float2(t.x * s, t.y * s);
+        }
     }
     __syncthreads();
 
@@ -195,7 +226,10 @@ __global__ FDC_PLAIN_DS __launch_bounds__(512, (P == 2 && !OFF && !R4 && !FWD) ?
     const float2 *const scrr = scr + w * kStripPts + col + 68 * b;   // exchange read base: element bb at + 4 bb
     const float2 *const wr = wrow + b * 18;
     const float2 *const wrf = wrowF + b * 18;
-    const float2 *const btr = Bt + c5 * 18;
+    // the two table rows of a pass: kSplit: UR row 8 pass + wave and the lane's LT row; P = 2: Bt row c5 and SA row 16 pass + b
+    const float2 *const tr0 = kSplit ? UR + w * 16 : Bt + c5 * 18;  // kSplit: + 128 pass
+    const float2 *const tr1 = kSplit ? LT + lane * 18 : SA + b * 18;   // P = 2: + 288 pass
+    const float2 *const cblr = CBL + b;                             // + 16 pass, + 16 (P + wave)
     const __amdgpu_buffer_rsrc_t rout = make_rsrc(out, out_bytes);
     // FWD / R4: this workgroup's scratch, [pass][j][thread]
     constexpr bool kScr = FWD || R4;
@@ -227,7 +261,8 @@ __global__ FDC_PLAIN_DS __launch_bounds__(512, (P == 2 && !OFF && !R4 && !FWD) ?
         // pass (of this block, or pass 0 of this workgroup's next block; after the last block: the same rows again, unused)
         // are requested first, unconditionally (a conditional request costs a second set of register copies).
         auto one_pass = [&](const int ps, cf (&cur)[16], const cf cbc, cf (&L)[16], cf &cbn) __attribute__((always_inline)) {
-            const cf cb = (OFF && R4) ? cmul(cbc, phs) : OFF ? cbc * sgn : cbc;
+            const cf cbl = kSplit ? cmul(ld2(&cblr[16 * ps]), ld2(&cblr[16 * (P + w)])) : cbc;
+            const cf cb = (OFF && R4) ? cmul(cbl, phs) : OFF ? cbl * sgn : cbl;
             const int pn = ps < P - 1 ? ps + 1 : 0;
             const int mb = ps < P - 1 ? m : mnext;
             // the pass offset (32 columns) sits in the descriptor's base: every pass uses the same per-lane offset and the
@@ -248,19 +283,16 @@ __global__ FDC_PLAIN_DS __launch_bounds__(512, (P == 2 && !OFF && !R4 && !FWD) ?
 #pragma unroll
                 for (int a = 0; a < 16; a++) L[a] = bld2(rin, voff, (unsigned)a * kRowGrp);
             }
-            cbn = bld2(rcb, voffc, (unsigned)pn * 4096u);
+            if constexpr (!kSplit) cbn = bld2(rcb, voffc, (unsigned)pn * 4096u);
+            const float2 *const r0 = tr0 + (kSplit ? 128 * ps : 0), *const r1 = tr1 + (kSplit ? 0 : 288 * ps);
             if constexpr (kIq) {
 #pragma unroll
                 for (int a = 0; a < 16; a++) cur[a] = iq_widen_bits(TI{}, __float_as_uint(cur[a].x), iq_scale);
             }
             dft16<false>(cur);                                    // in place, over a: index p in cur[rev16(p)]
             cf tw[16];
-#pragma unroll
-            for (int i = 0; i < 8; i++) {
-                const float4 t = ld4(&wrf[2 * i]);
-                tw[2 * i] = mk(t.x, t.y); tw[2 * i + 1] = mk(t.z, t.w);
-            }
-            if (OFF) {
+            ld_row_sh<OFF>(tw, wrf);
+            if constexpr (OFF) {
 #pragma unroll
                 for (int p = 0; p < 16; p++) st2(&scrw[68 * ((p - r16) & 15)], cmul(cur[rev16(p)], tw[p]));
             } else {
@@ -275,10 +307,9 @@ __global__ FDC_PLAIN_DS __launch_bounds__(512, (P == 2 && !OFF && !R4 && !FWD) ?
                 // round-2..5 form: T[k2 = b + 16 q][n1] = A[k2] W_N^(n1 k2) / N.  The half q < 8 stays in the G registers, the half q >= 8 goes to this
                 // workgroup's 256 KiB of scratch ([pass][j][thread]: 512-byte wave stores) and comes back for the second run of stage 2
                 dft16<false>(v);
-                const float2 *sar = SA + (ps * 16 + b) * kSaLd;
 #pragma unroll
                 for (int i = 0; i < 8; i++) {
-                    const float4 t0 = ld4(&btr[2 * i]), t1 = ld4(&sar[2 * i]);
+                    const float4 t0 = ld4(&r0[2 * i]), t1 = ld4(&r1[2 * i]);
                     const cf y0 = cmul(cmul(cmul(v[rev16(2 * i)], mk(t0.x, t0.y)), mk(t1.x, t1.y)), cb);
                     const cf y1 = cmul(cmul(cmul(v[rev16(2 * i + 1)], mk(t0.z, t0.w)), mk(t1.z, t1.w)), cb);
                     if (i < 4) { FDC_GPUT(2 * i, ps, y0); FDC_GPUT(2 * i + 1, ps, y1); }
@@ -291,21 +322,16 @@ __global__ FDC_PLAIN_DS __launch_bounds__(512, (P == 2 && !OFF && !R4 && !FWD) ?
                 dft16<false>(v);                                  // A[k2 = b + 16 q] in v[rev16(q)]
                 cf u[16];
                 {
-                    const float2 *sar = SA + (ps * 16 + b) * kSaLd;
 #pragma unroll
                     for (int i = 0; i < 8; i++) {
-                        const float4 t0 = ld4(&btr[2 * i]), t1 = ld4(&sar[2 * i]);
+                        const float4 t0 = ld4(&r0[2 * i]), t1 = ld4(&r1[2 * i]);
                         // window * inter-pass twiddle, placed at the ifftshifted position (k2 ^ 128 <=> q ^ 8)
                         u[HALF ? 2 * i : (2 * i) ^ 8] = cmul(cmul(v[rev16(2 * i)], mk(t0.x, t0.y)), mk(t1.x, t1.y));
                         u[HALF ? 2 * i + 1 : (2 * i + 1) ^ 8] = cmul(cmul(v[rev16(2 * i + 1)], mk(t0.z, t0.w)), mk(t1.z, t1.w));
                     }
                 }
                 dft16<true>(u);
-#pragma unroll
-                for (int i = 0; i < 8; i++) {
-                    const float4 t = ld4(&wr[2 * i]);
-                    tw[2 * i] = mk(t.x, t.y); tw[2 * i + 1] = mk(t.z, t.w);
-                }
+                ld_row_sh<false>(tw, wr);
                 u[rev16(0)] = cmul(u[rev16(0)], cb);
 #pragma unroll
                 for (int p = 1; p < 16; p++) u[rev16(p)] = cmul(cmulc(u[rev16(p)], tw[p]), cb);

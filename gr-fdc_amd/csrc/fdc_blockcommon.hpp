@@ -66,6 +66,25 @@ __device__ __forceinline__ void ld_row(cf (&t)[n], const float2 *row)
     }
 }
 
+// The same row stored one element down (k_blk256): entry p at index p - 1, p = 1 ... 15.  Entry 0 is W^0 = 1 and never multiplied; with the row
+// stored from entry 0 the compiler drops that element and pairs the rest as (1, 2), (3, 4), ..., which are only 8-byte aligned: seven ds_read2_b64
+// (128 B/clk) and a lone ds_read_b64 where the shifted row takes seven ds_read_b128 (256 B/clk) and the same lone read.  WRAP: the row has a
+// live entry 0 (the forward row of the offset plans), kept at index 15: eight 16-byte reads, the last one (15, 0).  t[0] is not written otherwise.
+template <bool WRAP>
+__device__ __forceinline__ void ld_row_sh(cf (&t)[16], const float2 *row)
+{
+#pragma unroll
+    for (int i = 0; i < 7; i++) {
+        const float4 q = ld4(&row[2 * i]);
+        t[2 * i + 1] = mk(q.x, q.y); t[2 * i + 2] = mk(q.z, q.w);
+    }
+    if constexpr (WRAP) {
+        const float4 q = ld4(&row[14]);
+        t[15] = mk(q.x, q.y); t[0] = mk(q.z, q.w);
+    } else
+        t[15] = ld2(&row[14]);
+}
+
 // The per-wave exchange strip of stage 1: 68*15 + 64 = 1084 points, element (p; lane) at lane + 68 p.  A lane = col + 4 b writes its sixteen
 // values from scrw = strip + lane and reads the sixteen of (col, row 16 b + bb) from scrr = strip + col + 68 b.  Both 16 x 16 exchanges of
 // the FFT-256 / IFFT-256 pair stay inside the wave (in-order LDS queue: a wave barrier, no s_barrier).
