@@ -12,7 +12,7 @@
 //       n2 = 16a + b of its column.  Both 16 x 16 exchanges of the FFT-256 / IFFT-256 pair stay inside the wave
 //       (a private 8.5 KiB LDS scratch, in-order LDS queue, no s_barrier), so the eight waves drift apart and one
 //       wave's LDS phases overlap the other waves' DFT-16 arithmetic.  The next pass's rows are loaded into
-//       registers before the current pass is computed.  The 8 kept outputs t = b + 16q, q >= 8, of every pass go
+//       registers a pass ahead: at the top of the pass, or (SPREAD) four at a time between its phases.  The 8 kept outputs t = b + 16q, q >= 8, of every pass go
 //       into the G registers (indexed by the pass: s_set_gpr_idx).
 //   stage 2, 2 chunks of 64 rows t': the FFT-256 over n1 = 32 pass + c5 starts with a DFT-8 over the pass index, which
 //       is the register index of G (no exchange), then W_256^(c5 klo), then ONE trip through LDS ([row][klo][c5]) to the
@@ -47,6 +47,12 @@ typedef unsigned long long u8v __attribute__((ext_vector_type(8)));
 // (klo = wave mod P, row half = wave div P).
 //
 // LDS map (bytes).  Stage-1 scratch: the eight per-wave exchange strips (fdc_blockcommon.hpp), kStripsEnd bytes.
+// Which forms of k_blk256 have a spread instantiation (SPREAD: the next pass's row loads in four groups over the pass, one_pass): the channelizer on
+// the grid and half a slot up.  Not the forms whose registers the placement costs
+// (scratch, a spill): offset plans, the forward transform, and at P = 8 the forms at R = 4 or with integer output.
+template <int P, bool OFF, bool FWD, bool R4, class TO>
+constexpr bool kBlkSpread = !OFF && !FWD && !(P == 8 && (R4 || !std::is_same<TO, float2>::value));
+
 template <int P>
 struct BlkGeom {
     static_assert(P == 2 || P == 4 || P == 8, "passes of 32 columns: N = 16384, 32768 or 65536");
@@ -105,7 +111,9 @@ struct BlkGeom {
 // TI: the input sample, float2 or complex integer (sc16 / sc8: fdc_iq.hpp); integer rows are loaded as they are (4 / 2 bytes a sample) and
 // widened in registers at the top of the pass that transforms them, times iq_scale.  TO: the output sample, float2 or complex integer (sc16 / sc8:
 // narrowed in the store, times oq_scale, oq_bits): one dword / one 16-bit store per sample at the same per-wave offsets, scaled to the narrow element
-template <int P, bool NT, bool OFF, bool FWD, bool R4 = false, bool HALF = false, class TI = float2, class TO = float2>
+// SPREAD: the row loads of the next pass are issued in groups between the phases of a pass (ld_rows) instead of all sixteen at its top; plain loads
+// only: a launch with streamed input loads (hints bit 1, a diagnostic) takes the form without it
+template <int P, bool NT, bool OFF, bool FWD, bool R4 = false, bool HALF = false, class TI = float2, class TO = float2, bool SPREAD = false>
 __global__ FDC_PLAIN_DS __launch_bounds__(512, (P == 2 && !OFF && !R4 && !FWD) ? 4 : 2) void k_blk256(const TI *__restrict__ in, size_t in_stride, TO *__restrict__ out,
                                                 const float2 *__restrict__ tw256, const float2 *__restrict__ twq,
                                                 const float2 *__restrict__ cbt, const float *__restrict__ shn,
@@ -117,6 +125,7 @@ __global__ FDC_PLAIN_DS __launch_bounds__(512, (P == 2 && !OFF && !R4 && !FWD) ?
 {
     typedef BlkGeom<P> GM;
     constexpr bool kIq = !std::is_same<TI, float2>::value, kOq = !std::is_same<TO, float2>::value;
+    static_assert(!SPREAD || kBlkSpread<P, OFF, FWD, R4, TO>, "no spread form of this one");
     static_assert(!kIq || !FWD, "integer input: the channelizer forms (the forward transform takes widened input)");
     static_assert(!kOq || !FWD, "integer output: the channelizer forms");
     constexpr unsigned kEs = (unsigned)sizeof(TI);                              // bytes per input sample
@@ -268,28 +277,49 @@ __global__ FDC_PLAIN_DS __launch_bounds__(512, (P == 2 && !OFF && !R4 && !FWD) ?
             // the pass offset (32 columns) sits in the descriptor's base: every pass uses the same per-lane offset and the
             // same 16 scalar row offsets
             const __amdgpu_buffer_rsrc_t rin = make_rsrc(in + (size_t)mb * in_stride + 32 * pn, inbytes);
-            if constexpr (kIq) {
-                if (hints & 2) {
+            // (the forms with a spread twin are launched with hints bit 1 set only; their plain arm stays so that every SPREAD = false form is
+            // the code it was: without the branch the pass loop is scheduled and allocated otherwise, profiles/spread_loads/NOTES.md)
+            if constexpr (!SPREAD) {
+                if constexpr (kIq) {
+                    if (hints & 2) {
 #pragma unroll
-                    for (int a = 0; a < 16; a++) L[a] = ld_in(rin, (unsigned)a * kRowGrp, std::integral_constant<int, 2>{});
+                        for (int a = 0; a < 16; a++) L[a] = ld_in(rin, (unsigned)a * kRowGrp, std::integral_constant<int, 2>{});
+                    } else {
+#pragma unroll
+                        for (int a = 0; a < 16; a++) L[a] = ld_in(rin, (unsigned)a * kRowGrp, std::integral_constant<int, 0>{});
+                    }
+                } else if (hints & 2) {
+#pragma unroll
+                    for (int a = 0; a < 16; a++) L[a] = bld2_nt(rin, voff, (unsigned)a * kRowGrp);
                 } else {
 #pragma unroll
-                    for (int a = 0; a < 16; a++) L[a] = ld_in(rin, (unsigned)a * kRowGrp, std::integral_constant<int, 0>{});
+                    for (int a = 0; a < 16; a++) L[a] = bld2(rin, voff, (unsigned)a * kRowGrp);
                 }
-            } else if (hints & 2) {
-#pragma unroll
-                for (int a = 0; a < 16; a++) L[a] = bld2_nt(rin, voff, (unsigned)a * kRowGrp);
-            } else {
-#pragma unroll
-                for (int a = 0; a < 16; a++) L[a] = bld2(rin, voff, (unsigned)a * kRowGrp);
+                if constexpr (!kSplit) cbn = bld2(rcb, voffc, (unsigned)pn * 4096u);
             }
-            if constexpr (!kSplit) cbn = bld2(rcb, voffc, (unsigned)pn * 4096u);
+            // SPREAD: rows 4 g ... 4 g + 3 (and cbn at P = 2 with the last of them), behind the first dft16 (14 % of a pass), the middle dft16
+            // (39 %), the first inverse dft16 (65 %) and the second exchange (84 %): profiles/spread_loads/NOTES.md.  L is dead from the previous
+            // pass's first exchange write on, and this pass's rows are consumed by its first dft16: the waits at the top of a pass cover the
+            // previous pass's loads only.  A full scheduling fence in front of a group holds it in its place.
+            auto ld_rows = [&](auto group) __attribute__((always_inline)) {
+                constexpr int g = decltype(group)::value;
+                if constexpr (SPREAD) {
+                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int a = 4 * g; a < 4 * g + 4; a++) {
+                        if constexpr (kIq) L[a] = ld_in(rin, (unsigned)a * kRowGrp, std::integral_constant<int, 0>{});
+                        else L[a] = bld2(rin, voff, (unsigned)a * kRowGrp);
+                    }
+                    if constexpr (!kSplit && g == 3) cbn = bld2(rcb, voffc, (unsigned)pn * 4096u);
+                }
+            };
             const float2 *const r0 = tr0 + (kSplit ? 128 * ps : 0), *const r1 = tr1 + (kSplit ? 0 : 288 * ps);
             if constexpr (kIq) {
 #pragma unroll
                 for (int a = 0; a < 16; a++) cur[a] = iq_widen_bits(TI{}, __float_as_uint(cur[a].x), iq_scale);
             }
             dft16<false>(cur);                                    // in place, over a: index p in cur[rev16(p)]
+            ld_rows(std::integral_constant<int, 0>{});
             cf tw[16];
             ld_row_sh<OFF>(tw, wrf);
             if constexpr (OFF) {
@@ -320,6 +350,7 @@ __global__ FDC_PLAIN_DS __launch_bounds__(512, (P == 2 && !OFF && !R4 && !FWD) ?
                 }
             } else {
                 dft16<false>(v);                                  // A[k2 = b + 16 q] in v[rev16(q)]
+                ld_rows(std::integral_constant<int, 1>{});
                 cf u[16];
                 {
 #pragma unroll
@@ -331,14 +362,19 @@ __global__ FDC_PLAIN_DS __launch_bounds__(512, (P == 2 && !OFF && !R4 && !FWD) ?
                     }
                 }
                 dft16<true>(u);
+                ld_rows(std::integral_constant<int, 2>{});
                 ld_row_sh<false>(tw, wr);
                 u[rev16(0)] = cmul(u[rev16(0)], cb);
 #pragma unroll
                 for (int p = 1; p < 16; p++) u[rev16(p)] = cmul(cmulc(u[rev16(p)], tw[p]), cb);
                 strip_trip(u, scrw, scrr);
+                ld_rows(std::integral_constant<int, 3>{});
                 dft16<true>(u);                                       // y[t = b + 16 q] in u[rev16(q)]; keep q >= 8 (R = 2)
+                // (without the branch that used to open a pass, two passes are one scheduling region: fenced, the G moves stay one s_set_gpr_idx pair)
+                if constexpr (SPREAD) __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int j = 0; j < 8; j++) FDC_GPUT(j, ps, u[rev16(8 + j)]);
+                if constexpr (SPREAD) __builtin_amdgcn_sched_barrier(0);
                 if constexpr (R4) {                                   // R = 4 keeps q >= 4: rows 64..127 go to the scratch, [pass][q - 4][thread]
 #pragma unroll
                     for (int j = 0; j < 4; j++) bst2(rscr, (unsigned)tid * 8u + (unsigned)j * 4096u, (unsigned)ps * 16384u, u[rev16(4 + j)]);
@@ -535,17 +571,27 @@ __global__ FDC_PLAIN_DS __launch_bounds__(512, (P == 2 && !OFF && !R4 && !FWD) ?
     }
 }
 
+// the LDS size of one form, and of its spread twin if it has one
+template <int P, bool A, bool O, bool F, bool R4, bool H, class TI, class TO>
+static hipError_t set_block_form(int bytes)
+{
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_blk256<P, A, O, F, R4, H, TI, TO, false>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if constexpr (kBlkSpread<P, O, F, R4, TO>)
+        if (e == hipSuccess)
+            e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_blk256<P, A, O, F, R4, H, TI, TO, true>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    return e;
+}
+
 // the channelizer forms of one input type (TI != float2: the integer-input instantiations, fdc_pipeline_work_iq)
 template <class TI>
 static hipError_t init_block_kernels_in()
 {
     hipError_t e;
 #define FDC_SETB(P, A, B, R4) \
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_blk256<P, A, B, false, R4, false, TI>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                            B ? BlkGeom<P>::kLdsOff : BlkGeom<P>::kLds); \
+    e = set_block_form<P, A, B, false, R4, false, TI, float2>(B ? BlkGeom<P>::kLdsOff : BlkGeom<P>::kLds); \
     if (e != hipSuccess) return e;
 #define FDC_SETH(P, A, R4) \
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_blk256<P, A, false, false, R4, true, TI>), hipFuncAttributeMaxDynamicSharedMemorySize, BlkGeom<P>::kLds); \
+    e = set_block_form<P, A, false, false, R4, true, TI, float2>(BlkGeom<P>::kLds); \
     if (e != hipSuccess) return e;
 #define FDC_SETP(P) \
     FDC_SETB(P, true, false, false) FDC_SETB(P, false, false, false) FDC_SETB(P, true, true, false) FDC_SETB(P, false, true, false) \
@@ -571,11 +617,10 @@ static hipError_t init_block_kernels_oq()
 {
     hipError_t e;
 #define FDC_SETB(P, B, R4) \
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_blk256<P, true, B, false, R4, false, TI, TO>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                            B ? BlkGeom<P>::kLdsOff : BlkGeom<P>::kLds); \
+    e = set_block_form<P, true, B, false, R4, false, TI, TO>(B ? BlkGeom<P>::kLdsOff : BlkGeom<P>::kLds); \
     if (e != hipSuccess) return e;
 #define FDC_SETH(P, R4) \
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_blk256<P, true, false, false, R4, true, TI, TO>), hipFuncAttributeMaxDynamicSharedMemorySize, BlkGeom<P>::kLds); \
+    e = set_block_form<P, true, false, false, R4, true, TI, TO>(BlkGeom<P>::kLds); \
     if (e != hipSuccess) return e;
 #define FDC_SETP(P) \
     FDC_SETB(P, false, false) FDC_SETB(P, true, false) FDC_SETB(P, false, true) FDC_SETB(P, true, true) FDC_SETH(P, false) FDC_SETH(P, true)
@@ -585,6 +630,32 @@ static hipError_t init_block_kernels_oq()
 #undef FDC_SETP
 #undef FDC_SETH
 #undef FDC_SETB
+    return hipSuccess;
+}
+
+// the float forms: the channelizer, the forward transform, the half-slot channelizer
+static hipError_t init_block_kernels_float()
+{
+    hipError_t e;
+#define FDC_SETB(P, A, B, F, R4) \
+    e = set_block_form<P, A, B, F, R4, false, float2, float2>(B ? BlkGeom<P>::kLdsOff : BlkGeom<P>::kLds); \
+    if (e != hipSuccess) return e;
+#define FDC_SETP(P) \
+    FDC_SETB(P, true, false, false, false) FDC_SETB(P, false, false, false, false) FDC_SETB(P, true, true, false, false) \
+    FDC_SETB(P, false, true, false, false) FDC_SETB(P, true, false, false, true) FDC_SETB(P, false, false, false, true) \
+    FDC_SETB(P, true, true, false, true) FDC_SETB(P, false, true, false, true)
+    FDC_SETP(2) FDC_SETP(4) FDC_SETP(8)
+    FDC_SETB(8, true, false, true, false) FDC_SETB(8, false, false, true, false) FDC_SETB(4, true, false, true, false) FDC_SETB(4, false, false, true, false)
+    FDC_SETB(2, true, false, true, false) FDC_SETB(2, false, false, true, false)
+#undef FDC_SETP
+#undef FDC_SETB
+#define FDC_SETH(P, A, R4) \
+    e = set_block_form<P, A, false, false, R4, true, float2, float2>(BlkGeom<P>::kLds); \
+    if (e != hipSuccess) return e;
+#define FDC_SETHP(P) FDC_SETH(P, true, false) FDC_SETH(P, false, false) FDC_SETH(P, true, true) FDC_SETH(P, false, true)
+    FDC_SETHP(2) FDC_SETHP(4) FDC_SETHP(8)
+#undef FDC_SETHP
+#undef FDC_SETH
     return hipSuccess;
 }
 
@@ -599,27 +670,7 @@ hipError_t init_block_kernels()
     if ((e = init_block_kernels_oq<sc16, sc8>()) != hipSuccess) return e;
     if ((e = init_block_kernels_oq<sc8, sc16>()) != hipSuccess) return e;
     if ((e = init_block_kernels_oq<sc8, sc8>()) != hipSuccess) return e;
-#define FDC_SETB(P, A, B, F, R4) \
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_blk256<P, A, B, F, R4>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                            B ? BlkGeom<P>::kLdsOff : BlkGeom<P>::kLds); \
-    if (e != hipSuccess) return e;
-#define FDC_SETP(P) \
-    FDC_SETB(P, true, false, false, false) FDC_SETB(P, false, false, false, false) FDC_SETB(P, true, true, false, false) \
-    FDC_SETB(P, false, true, false, false) FDC_SETB(P, true, false, false, true) FDC_SETB(P, false, false, false, true) \
-    FDC_SETB(P, true, true, false, true) FDC_SETB(P, false, true, false, true)
-    FDC_SETP(2) FDC_SETP(4) FDC_SETP(8)
-    FDC_SETB(8, true, false, true, false) FDC_SETB(8, false, false, true, false) FDC_SETB(4, true, false, true, false) FDC_SETB(4, false, false, true, false)
-    FDC_SETB(2, true, false, true, false) FDC_SETB(2, false, false, true, false)
-#undef FDC_SETP
-#undef FDC_SETB
-#define FDC_SETH(P, A, R4) \
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_blk256<P, A, false, false, R4, true>), hipFuncAttributeMaxDynamicSharedMemorySize, BlkGeom<P>::kLds); \
-    if (e != hipSuccess) return e;
-#define FDC_SETHP(P) FDC_SETH(P, true, false) FDC_SETH(P, false, false) FDC_SETH(P, true, true) FDC_SETH(P, false, true)
-    FDC_SETHP(2) FDC_SETHP(4) FDC_SETHP(8)
-#undef FDC_SETHP
-#undef FDC_SETH
-    return hipSuccess;
+    return init_block_kernels_float();
 }
 
 bool poly_block_supports(int N) { return N == 16384 || N == 32768 || N == 65536; }
@@ -649,9 +700,9 @@ static hipError_t poly_block_in(const BlockLaunch &b, const TI *in, TO *out, flo
     // ev_start / ev_stop (timing): the dispatch packet's own begin / end time stamps (hipExtLaunchKernel) — no barrier packet
     // in front of or behind the kernel, unlike hipEventRecord (measured 7-17 us per bracketed launch)
     // R = 4: three quarters of every inverse transform kept: 192 rows per block, 64 of them via the scratch
-    // FDC_L(P, NT, OFF, R4, HALF, roff): one instantiation with the launch's arguments
+    // FDC_L(P, NT, OFF, R4, HALF, roff): one instantiation with the launch's arguments, in its spread form if it has one and SP says so
 #define FDC_L(P, A, O, R4, H, roff) \
-    hipExtLaunchKernelGGL((k_blk256<P, A || kOq, O, false, R4, H, TI, TO>), dim3((unsigned)grid), dim3(512), O ? BlkGeom<P>::kLdsOff : BlkGeom<P>::kLds, b.s, \
+    hipExtLaunchKernelGGL((k_blk256<P, A || kOq, O, false, R4, H, TI, TO, (SP && kBlkSpread<P, O, false, R4, TO>)>), dim3((unsigned)grid), dim3(512), O ? BlkGeom<P>::kLdsOff : BlkGeom<P>::kLds, b.s, \
                           b.ev_start, b.ev_stop, 0u, in, b.in_stride, out, b.tw256, b.twq, b.cbt, b.shn, b.slot_off, (long long)b.mbase * (R4 ? 192 : 128), \
                           (long long)b.nb_call, b.out_bytes, b.nb_chunk, b.hints, (unsigned long long *)nullptr, roff, b.first_block, \
                           R4 ? b.scratch : (float2 *)nullptr, (const unsigned *)nullptr, iq_tail(iq_scale, oq_scale))
@@ -669,7 +720,14 @@ static hipError_t poly_block_in(const BlockLaunch &b, const TI *in, TO *out, flo
         else if (b.r) { if (nt) FDC_LB(P, true, true, false); else FDC_LB(P, false, true, false); } \
         else { if (nt) FDC_LB(P, true, false, false); else FDC_LB(P, false, false, false); } \
     } while (0)
-    if (b.N == 65536) FDC_LP(8); else if (b.N == 32768) FDC_LP(4); else FDC_LP(2);
+    // streamed input loads (hints bit 1, a diagnostic): the forms with all sixteen row loads at the top of a pass
+    auto launch = [&](auto sp) -> hipError_t {
+        constexpr bool SP = decltype(sp)::value;
+        if (b.N == 65536) FDC_LP(8); else if (b.N == 32768) FDC_LP(4); else FDC_LP(2);
+        return hipSuccess;
+    };
+    const hipError_t e = (b.hints & 2) ? launch(std::false_type{}) : launch(std::true_type{});
+    if (e != hipSuccess) return e;
 #undef FDC_LP
 #undef FDC_R4
 #undef FDC_LH
