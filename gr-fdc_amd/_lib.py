@@ -105,6 +105,9 @@ SYMBOLS = {
     "fdc_pipeline_levels_device": (_vp, [_vp]),
     "fdc_pipeline_group_set_levels": (C.c_int, [_vp, C.c_int32]),
     "fdc_pipeline_group_levels": (C.c_int, [_vp, C.POINTER(C.c_float), C.c_int]),
+    "fdc_pipeline_set_gains": (C.c_int, [_vp, C.POINTER(C.c_float), C.c_int]),
+    "fdc_pipeline_gains": (C.c_int, [_vp, C.POINTER(C.c_float), C.c_int]),
+    "fdc_pipeline_group_set_gains": (C.c_int, [_vp, C.POINTER(C.c_float), C.c_int]),
     "fdc_pipeline_group_create": (C.c_int, [C.POINTER(fdc_pipeline_cfg), C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(_vp)]),
     "fdc_pipeline_group_destroy": (None, [_vp]),
     "fdc_pipeline_group_work": (C.c_int, [_vp, _vp, C.c_int, C.POINTER(_vp), _vp]),

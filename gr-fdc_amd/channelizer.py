@@ -230,6 +230,27 @@ def _set_fine_tuning(fn, handle, nchan, nu):
     _lib.check(rc)
 
 
+def _check_gains(nchan, g):
+    """Pipeline.set_gains / PipelineGroup.set_gains: g None (off) or one finite value per channel; float32[C] or None.  Raises before any library call."""
+    if g is None:
+        return None
+    with np.errstate(over="ignore"):            # (a value beyond float32 becomes infinite and is refused below)
+        arr = np.ascontiguousarray(g, dtype=np.float32)
+    if arr.ndim != 1 or arr.size != nchan:
+        raise ValueError("gains takes one value per channel (%d)" % nchan)
+    if not np.isfinite(arr).all():
+        raise ValueError("gains must be finite (channel %d is not)" % int(np.flatnonzero(~np.isfinite(arr))[0]))
+    return arr
+
+
+def _set_gains(fn, handle, nchan, g):
+    arr = _check_gains(nchan, g)
+    rc = fn(handle, None if arr is None else arr.ctypes.data_as(C.POINTER(C.c_float)), nchan)
+    if rc == -1:
+        raise ValueError(_lib.lib().fdc_last_error().decode())
+    _lib.check(rc)
+
+
 class _OutputFormat:
     """The channel outputs in the handle's output format (fdc_pipeline_set_output_format): complex64 arrays of nblocks*lout_c samples, or
     int16 / int8 arrays of shape (nblocks*lout_c, 2) (interleaved I/Q: sc16 / sc8)."""
@@ -337,6 +358,20 @@ class Pipeline(_OutputFormat):
         """fdc_pipeline_levels: float32[nblocks of the last call, C, 2], [m, c] = (power, peak) of block m of channel c.  nblocks: the last call's
         block count where it did not go through this object's work methods (process_device, work_raw)."""
         return _levels(_lib.lib().fdc_pipeline_levels, self._h, len(self.channels), self._last_nb, nblocks)
+
+    def set_gains(self, g):
+        """fdc_pipeline_set_gains: g[c] (converted to float32, any finite value: zero mutes, negative inverts) multiplies every sample of channel c's
+        stream on the device, each component rounded once: (y.view(float32) * g).view(complex64) of what the call writes with gains off.  Order: cut,
+        fine tuning, gain, levels, sc16 / sc8 narrowing — the levels are those of the gained samples, integer output is oq(gained * scale).  None, or
+        all ones, switches it off.  A setting like set_output_format: it applies from the next call and survives reset(); the sink, spectrum-item,
+        group-power and waterfall entries are refused while it is on.  ValueError for a wrong count, NaN or Inf (nothing changes)."""
+        _set_gains(_lib.lib().fdc_pipeline_set_gains, self._h, len(self.channels), g)
+
+    def gains(self):
+        """fdc_pipeline_gains: the gains in force, float32[C] (ones while off)."""
+        out = np.empty(len(self.channels), dtype=np.float32)
+        _lib.check(_lib.lib().fdc_pipeline_gains(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), int(out.size)))
+        return out
 
     def levels_device(self):
         """fdc_pipeline_levels_device: the device address of the levels ([block][C] float2), None while levels are off."""
@@ -584,6 +619,10 @@ class PipelineGroup(_OutputFormat):
         """fdc_pipeline_group_set_levels: Pipeline.set_levels for every member."""
         _lib.check(_lib.lib().fdc_pipeline_group_set_levels(self._h, int(bool(on))))
 
+    def set_gains(self, g):
+        """fdc_pipeline_group_set_gains: Pipeline.set_gains for every member."""
+        _set_gains(_lib.lib().fdc_pipeline_group_set_gains, self._h, len(self.channels), g)
+
     def levels(self, nblocks=None):
         """fdc_pipeline_group_levels: Pipeline.levels of the last group call, the members' spans put together in block order."""
         return _levels(_lib.lib().fdc_pipeline_group_levels, self._h, len(self.channels), self._last_nb, nblocks)
@@ -678,7 +717,7 @@ class FrequencyDomainChannelizer:
                  pow_act_deactivation_delay,
                  pow_act_maxblocks, act_det_maxblocks,
                  debug, device_id=0, max_blocks=64, devices=None, pipelined=False, waterfall=None, iq_input=None, iq_scale=1.0,
-                 iq_output=None, iq_output_scale=1.0, fine_tuning=False, *, payload_format=None, payload_scale=1.0, levels=False):
+                 iq_output=None, iq_output_scale=1.0, fine_tuning=False, *, payload_format=None, payload_scale=1.0, levels=False, gains=None):
         # pipelined (not an argument of the reference): the sink blocks run beside the front end of the FOLLOWING work() calls, as the
         # thread-per-block scheduler runs them beside the FFT in the reference (fdc_pipeline_work_sinks on a look-ahead bank,
         # include/fdc_amd.h): same PDUs, handed out one or two work() calls later; flush() at the end of the stream
@@ -784,6 +823,19 @@ class FrequencyDomainChannelizer:
             if waterfall is not None:
                 raise ValueError("levels cannot go with a waterfall")
 
+        # gains (not an argument of the reference): one output gain per throughput channel, applied on the device behind fine tuning and in front of the
+        # levels and of iq_output's narrowing (Pipeline.set_gains); set_gains() changes them between work() calls (an AGC fed from self.levels)
+        self.gains = None if gains is None else _check_gains(len(self.throughput_channels), gains)
+        self._gains_refusal = None
+        if self.inpveclen != 1:
+            self._gains_refusal = "gains needs inpveclen 1: the pre-transformed item entry writes the channels as they are cut"
+        elif activity_controlled_channels or activity_detection_segments:
+            self._gains_refusal = "gains cannot go with activity-controlled channels or detection segments"
+        elif waterfall is not None:
+            self._gains_refusal = "gains cannot go with a waterfall"
+        if self.gains is not None and self._gains_refusal:
+            raise ValueError(self._gains_refusal)
+
         if self.verbose:                                        # runtime information, :176-193
             bar = '\n' + '#' * 32 + '\n'
             for ln in (bar, '# gr-FDC Frequency Domain Channelizer Runtime Information', bar,
@@ -839,6 +891,8 @@ class FrequencyDomainChannelizer:
             self.pipeline.set_fine_tuning(np.asarray(self.fine_nu, dtype=np.float64))
         if self.levels_on:
             self.pipeline.set_levels(True)
+        if self.gains is not None:
+            self.pipeline.set_gains(self.gains)
         self.N_throughput_channelizers = len(self.channel_params)
         # waterfall (not an argument of the reference, whose example flowgraph wires the spectrum to complex_to_mag_squared and
         # FDC.WaterfallMsgTagging outside the hier block): a gr_fdc_amd.Waterfall fed from the spectrum on the device; work() then
@@ -931,6 +985,14 @@ class FrequencyDomainChannelizer:
             _write_files(self.outputpath, det, False)
         if self.msgoutput:
             self.messages += pac + det
+
+    def set_gains(self, g):
+        """New gains (one per throughput channel, or None: off) from the next work() call on: Pipeline.set_gains, with the constructor's refusals."""
+        arr = _check_gains(len(self.throughput_channels), g)
+        if arr is not None and self._gains_refusal:
+            raise ValueError(self._gains_refusal)
+        self.pipeline.set_gains(arr)
+        self.gains = arr
 
     def flush(self):
         """End of the stream (what the block's stop() does): the pipelined form still holds the PDUs of the last one or two work()

@@ -409,6 +409,7 @@ int32_t fdc_pipeline_describe(const fdc_pipeline *p, char *buf, int32_t n)
     if (!p->oq_route.empty()) add("; output %s", p->oq_route.c_str());
     if (!p->fine_route.empty()) add("; fine tuning: %s", p->fine_route.c_str());
     if (!p->levels_route.empty()) add("; levels: %s", p->levels_route.c_str());
+    if (!p->gains_route.empty()) add("; gains: %s", p->gains_route.c_str());
     std::snprintf(buf, (size_t)n, "%s", t);
     return k;
 }
@@ -480,6 +481,7 @@ void fdc_pipeline_reset(fdc_pipeline *p)
     p->oq_route.clear();         // (the output format itself is a setting: it stays)
     p->fine_route.clear();       // (and so does fine tuning)
     p->levels_route.clear();     // (and so do the channel levels)
+    p->gains_route.clear();      // (and the channel gains)
 }
 
 int fdc_pipeline_set_output_format(fdc_pipeline *p, int32_t format, float scale)
@@ -591,6 +593,42 @@ int fdc_pipeline_levels(fdc_pipeline *p, float *dst, int nblocks)
         p->lev_host = true;
     }
     std::memcpy(dst, p->pin_levels.get(), sizeof(float2) * n);
+    return FDC_OK;
+    FDC_ENTRY_END
+}
+
+int fdc_pipeline_set_gains(fdc_pipeline *p, const float *gain, int n)
+{
+    FDC_ENTRY("fdc_pipeline_set_gains")
+    if (!p) return set_error(FDC_ERR_INVALID_ARGUMENT, "null handle");
+    if (n != p->C) return set_error(FDC_ERR_INVALID_ARGUMENT, "channel gains: %d gains for %d channels", n, p->C);
+    if (p->hier_filled > 0)
+        return set_error(FDC_ERR_INVALID_ARGUMENT, "a pipelined sinks batch is still inside the handle: fdc_pipeline_flush_sinks until it returns 0 first");
+    bool on = false;
+    for (int c = 0; gain && c < p->C; c++) {
+        if (!std::isfinite(gain[c])) return set_error(FDC_ERR_INVALID_ARGUMENT, "channel gains: the gain of channel %d is not finite", c);
+        on = on || gain[c] != 1.0f;
+    }
+    if (!on) { p->gains_on = false; p->gains.clear(); p->gains_route.clear(); return FDC_OK; }
+    HIPCHK(hipSetDevice(p->cfg.device_id));
+    HIPCHK(hipStreamSynchronize(p->stream));          // (no call of the host entries is in flight; a device entry's caller orders its own stream)
+    if (!p->d_gain) HIPCHK(p->d_gain.alloc((size_t)p->C));       // once: an AGC that sets new gains before every call allocates nothing
+    HIPCHK(hipMemcpy(p->d_gain, gain, sizeof(float) * (size_t)p->C, hipMemcpyHostToDevice));
+    if (p->gains.size() != (size_t)p->C) p->gains.resize((size_t)p->C);
+    std::memcpy(p->gains.data(), gain, sizeof(float) * (size_t)p->C);
+    p->gains_on = true;
+    return FDC_OK;
+    FDC_ENTRY_END
+}
+
+int fdc_pipeline_gains(const fdc_pipeline *p, float *dst, int n)
+{
+    FDC_ENTRY("fdc_pipeline_gains")
+    if (!p) return set_error(FDC_ERR_INVALID_ARGUMENT, "null handle");
+    if (n != p->C) return set_error(FDC_ERR_INVALID_ARGUMENT, "channel gains: room for %d gains of %d channels", n, p->C);
+    if (n == 0) return FDC_OK;
+    if (!dst) return set_error(FDC_ERR_INVALID_ARGUMENT, "null argument");
+    for (int c = 0; c < n; c++) dst[c] = p->gains_on ? p->gains[(size_t)c] : 1.0f;
     return FDC_OK;
     FDC_ENTRY_END
 }

@@ -22,6 +22,7 @@ DeviceCall device_call(const fdc_pipeline *p, void *stream, void *d_spectrum, in
     call.stream = stream ? static_cast<hipStream_t>(stream) : p->stream;
     call.spectrum = d_spectrum;
     call.ncu = p->ncu - p->reserved_cu;
+    call.gain = p->gains_on && p->C > 0 ? p->d_gain.get() : nullptr;
     return call;
 }
 
@@ -147,6 +148,7 @@ static bool iq_fused(const fdc_pipeline *p, const DeviceCall &call, bool few)
 static bool oq_fused(const fdc_pipeline *p, const DeviceCall &call, int nblocks)
 {
     if (call.levels) return false;           // the levels are of the float samples: float, the levels pass, then narrowed (every path, path 5 included)
+    if (call.gain) return false;             // the gain multiplies the float samples: float, the gain pass, then narrowed (every path, path 5 included)
     if (!int_kernels(p, call)) return false;
     if (p->fused) return true;
     if (p->fine_on) return false;            // the banks' kernels do not turn their samples: float, k_fine_rotate, then narrowed
@@ -188,12 +190,22 @@ int process_device_impl(fdc_pipeline *p, DeviceCall &call, const void *d_ring, i
     // off path 5, k_fine_rotate reduces the turned samples it holds and no second trip over the output is made
     float2 *const lev = p->C > 0 ? call.levels : nullptr;
     const bool lev_merged = lev && fine && !fine_fused && !p->levels_separate;
+    // channel gains: behind the rotation and in front of the levels and the narrowing.  Where k_fine_rotate runs it multiplies the turned sample it holds
+    // (gain_rot); where none runs k_chan_gain goes over the launch group's float results once, sums the levels of the gained samples too (k_chan_levels is
+    // then not launched) and, where this path narrows an integer output itself, stores the narrow samples (gain_narrow: no call-wide k_complex_to_iq)
+    const float *const gain = p->C > 0 ? call.gain : nullptr;
+    const bool gain_rot = gain && fine && !fine_fused;
+    const bool gain_narrow = gain && !gain_rot && ofmt && !ofused && call.narrow;
     auto levels = [&](const Span &g) -> int {
-        if (lev) HIPCHK(fdc::launch_chan_levels(o, p->d_chans, lev, p->C, g.nb, g.m0, g.nblocks, s));
+        if (gain && !gain_rot)
+            HIPCHK(fdc::launch_chan_gain(o, p->d_chans, gain, lev, gain_narrow ? ofmt : 0, call.oscale, gain_narrow ? d_out : nullptr, p->C, g.nb, g.m0, g.nblocks, s));
+        else if (lev) HIPCHK(fdc::launch_chan_levels(o, p->d_chans, lev, p->C, g.nb, g.m0, g.nblocks, s));
         return FDC_OK;
     };
     auto rotate = [&](const Span &g) -> int {
-        if (fine) HIPCHK(fdc::launch_fine_rotate(o, p->d_chans, p->d_fine, p->d_fstep, p->C, g.nb, g.m0, g.nblocks, g.first_block, s, lev_merged ? lev : nullptr));
+        if (fine)
+            HIPCHK(fdc::launch_fine_rotate(o, p->d_chans, p->d_fine, p->d_fstep, p->C, g.nb, g.m0, g.nblocks, g.first_block, s, lev_merged ? lev : nullptr,
+                                           gain_rot ? gain : nullptr));
         return lev_merged ? FDC_OK : levels(g);
     };
     for (int m0 = 0; m0 < nblocks; m0 += p->chunk) {
@@ -315,9 +327,10 @@ int process_device_impl(fdc_pipeline *p, DeviceCall &call, const void *d_ring, i
             p->ev_spans.push_back(span);
         }
     }
-    if (ofmt && !ofused && call.narrow && p->C > 0) HIPCHK(fdc::launch_complex_to_iq(ofmt, call.oscale, call.fout, d_out, (size_t)nblocks * p->sum_lout, s));
+    if (ofmt && !ofused && call.narrow && !gain_narrow && p->C > 0) HIPCHK(fdc::launch_complex_to_iq(ofmt, call.oscale, call.fout, d_out, (size_t)nblocks * p->sum_lout, s));
     if (fine) p->fine_route = fine_fused ? "fused" : "rotated";
-    if (lev) p->levels_route = lev_merged ? "with the rotation" : "pass";
+    if (lev) p->levels_route = lev_merged ? "with the rotation" : gain && !gain_rot ? "with the gains" : "pass";
+    if (gain) p->gains_route = gain_rot ? "with the rotation" : gain_narrow ? "with the narrowing" : "pass";
     return FDC_OK;
 }
 
@@ -412,6 +425,7 @@ int fdc_pipeline_process_device_power(fdc_pipeline *p, const void *d_ring, int64
     if (p->out_form) return set_error(FDC_ERR_INVALID_ARGUMENT, "fdc_pipeline_process_device_power writes complex float outputs only (the handle's output format is not FC32)");
     if (p->fine_on) return set_error(FDC_ERR_INVALID_ARGUMENT, "fdc_pipeline_process_device_power writes the channels as they are cut: switch fine tuning off first");
     if (p->levels_on) return set_error(FDC_ERR_INVALID_ARGUMENT, "fdc_pipeline_process_device_power gives no channel levels: switch them off first (fdc_pipeline_set_levels(p, 0))");
+    if (p->gains_on) return set_error(FDC_ERR_INVALID_ARGUMENT, "fdc_pipeline_process_device_power writes the channels as they are cut: switch the channel gains off first (fdc_pipeline_set_gains(p, NULL, C))");
     if (d_group_power && (!d_spectrum || (p->N & 15))) return set_error(FDC_ERR_INVALID_ARGUMENT, "group powers go with a spectrum output of a block length that is a multiple of 16");
     DeviceCall call = device_call(p, stream, d_spectrum);
     call.gpow = static_cast<float *>(d_group_power);

@@ -390,6 +390,19 @@ int fdc_pipeline_group_set_levels(fdc_pipeline_group *g, int32_t on)
     FDC_ENTRY_END
 }
 
+int fdc_pipeline_group_set_gains(fdc_pipeline_group *g, const float *gain, int n)
+{
+    FDC_ENTRY("fdc_pipeline_group_set_gains")
+    if (!g) return fdc::set_error(FDC_ERR_INVALID_ARGUMENT, "null group handle");
+    // every member takes the same arguments: the first refuses what all would refuse, before any has changed
+    for (fdc_pipeline *p : g->mem) {
+        const int rc = fdc_pipeline_set_gains(p, gain, n);
+        if (rc != FDC_OK) return rc;
+    }
+    return FDC_OK;
+    FDC_ENTRY_END
+}
+
 // the levels of the last group call: the members' spans (what fdc_pipeline_group_last_spans reports) put together in block order
 int fdc_pipeline_group_levels(fdc_pipeline_group *g, float *dst, int nblocks)
 {

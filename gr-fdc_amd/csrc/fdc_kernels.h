@@ -232,11 +232,17 @@ hipError_t launch_complex_to_iq(int fmt, float scale, const float2 *in, void *ou
 // exp(-2 pi i frac(fine[c].inc t / 2^64)) at its stream sample t = (first_block + m) lout_c + j; step: the channels' step factors at fine[c].step_off
 // levels (fine tuning AND channel levels on): the pass also reduces the turned samples it holds and stores their levels as launch_chan_levels would
 hipError_t launch_fine_rotate(float2 *out, const ChanDev *chans, const FineChan *fine, const float2 *step, int nchan, int nb_chunk, int mbase, int nb_call,
-                              int64_t first_block, hipStream_t s, float2 *levels = nullptr);
+                              int64_t first_block, hipStream_t s, float2 *levels = nullptr, const float *gain = nullptr);
 
 // Channel levels (fdc_pipeline_set_levels): blocks [mbase, mbase + nb_chunk) of a call's channel-major float outputs read once; levels[(mbase + m) * nchan + c] =
 // (sum of re^2 + im^2, max of |re| and |im|) over the lout_c samples of block m of channel c.  One summation order per lout (fdc_kernels.hip)
 hipError_t launch_chan_levels(const float2 *out, const ChanDev *chans, float2 *levels, int nchan, int nb_chunk, int mbase, int nb_call, hipStream_t s);
+
+// Channel gains (fdc_pipeline_set_gains) where no rotation pass runs: blocks [mbase, mbase + nb_chunk) of a call's channel-major float results times
+// gain[c], every component rounded once.  fmt 0: in place; kIqSc16 / kIqSc8: `out` is read only and oq_narrow(product, scale) goes to the same sample
+// offset of the narrow output `nar`.  levels (null: none): the gained samples' levels as launch_chan_levels would sum them, in the same pass
+hipError_t launch_chan_gain(float2 *out, const ChanDev *chans, const float *gain, float2 *levels, int fmt, float scale, void *nar, int nchan, int nb_chunk,
+                            int mbase, int nb_call, hipStream_t s);
 
 hipError_t launch_scale(const float2 *in, float2 *out, size_t n, float k, hipStream_t s);
 

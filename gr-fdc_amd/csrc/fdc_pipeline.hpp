@@ -174,6 +174,12 @@ struct fdc_pipeline {
     bool lev_host = false;
     hipStream_t lev_stream = nullptr;
     std::string levels_route;    // how the last call with levels was served (fdc_pipeline_describe)
+    // channel gains (fdc_pipeline_set_gains): a setting like the three above.  gains_on: some gain is not exactly 1; gains: the C gains in force (empty
+    // while off: all ones); d_gain their device table, allocated by the first call that switches the setting on and rewritten by every later one
+    bool gains_on = false;
+    std::vector<float> gains;
+    fdc::DevBuf<float> d_gain;
+    std::string gains_route;     // how the last call with gains was served (fdc_pipeline_describe)
     fdc::DevBuf<float2> d_out;   // work(): max_blocks*sum_lout (out_staging)
     int64_t blockcount = 0;      // work(): blocks consumed so far
     // work(): transfers and kernels of consecutive sub-batches overlap (H2D on s_in, kernels on stream, D2H on s_out)
@@ -227,6 +233,9 @@ struct DeviceCall {
     // channel levels (fdc_pipeline_set_levels): where (power, peak) of the call's block 0, channel 0 go, [block][C]; null = none.  With them the kernels
     // write float whatever the output format (the levels are of the float samples; the narrowing comes behind)
     float2 *levels = nullptr;
+    // channel gains (fdc_pipeline_set_gains): the handle's device table of C gains, null = off (device_call).  With them the kernels write float whatever
+    // the output format, as with levels: float, (rotation,) gain, (levels,) narrowing
+    const float *gain = nullptr;
     int ncu = 0;                         // compute units the call's persistent kernels may use
     // results: no launch group had to be widened (each read the integer input in its own loads); the call's kernels narrowed in their own stores
     bool all_fused = true, ofused = false;

@@ -11,12 +11,13 @@ extern "C" {
 
 // the entries that write complex float only (sinks, spectrum items, group powers, waterfall): refused while the output format is not FC32
 // (and, but for the flush of a batch that is inside already, while fine tuning is on: they write the channels as they are cut; and while channel
-// levels are on: they give none)
+// levels are on: they give none; and while channel gains are on: they write the channels as they are cut)
 static int check_float_output(const fdc_pipeline *p, const char *entry, bool writes_channels = true)
 {
     if (p && p->out_form) return set_error(FDC_ERR_INVALID_ARGUMENT, "%s writes complex float outputs only: set the output format to FDC_OQ_FC32 first", entry);
     if (p && p->fine_on && writes_channels) return set_error(FDC_ERR_INVALID_ARGUMENT, "%s writes the channels as they are cut: switch fine tuning off first (fdc_pipeline_set_fine_tuning(p, NULL, C))", entry);
     if (p && p->levels_on && writes_channels) return set_error(FDC_ERR_INVALID_ARGUMENT, "%s gives no channel levels: switch them off first (fdc_pipeline_set_levels(p, 0))", entry);
+    if (p && p->gains_on && writes_channels) return set_error(FDC_ERR_INVALID_ARGUMENT, "%s writes the channels as they are cut: switch the channel gains off first (fdc_pipeline_set_gains(p, NULL, C))", entry);
     return FDC_OK;
 }
 

@@ -210,8 +210,8 @@ int fdc_pipeline_set_output_format(fdc_pipeline *p, int32_t format, float scale)
 int fdc_fine_tuning_increment(double nu, uint64_t *inc);
 int fdc_pipeline_set_fine_tuning(fdc_pipeline *p, const double *nu, int n);
 
-/* CHANNEL LEVELS: per-block power and peak of every channel, summed on the device (meters, squelch, occupancy, an AGC that sets the next call's output
- * scale — without pulling the float streams over the link).  With levels on, every (block m of the call, channel c) gets two float32 values from the
+/* CHANNEL LEVELS: per-block power and peak of every channel, summed on the device (meters, squelch, occupancy, an AGC that sets the next call's channel
+ * gains, CHANNEL GAINS below — without pulling the float streams over the link).  With levels on, every (block m of the call, channel c) gets two float32 values from the
  * lout_c samples the call produces for it:
  *     power[m][c] = sum_j (re_j^2 + im_j^2)        peak[m][c] = max_j max(|re_j|, |im_j|)   (fmax: a NaN component is passed over)
  * of the complex float32 samples y' the entry writes, or would write before narrowing: AFTER fine tuning, BEFORE the sc16 / sc8 narrowing.  So
@@ -242,6 +242,36 @@ int fdc_pipeline_set_fine_tuning(fdc_pipeline *p, const double *nu, int n);
 int fdc_pipeline_set_levels(fdc_pipeline *p, int32_t on);
 int fdc_pipeline_levels(fdc_pipeline *p, float *dst, int nblocks);
 void *fdc_pipeline_levels_device(fdc_pipeline *p);
+
+/* CHANNEL GAINS: a per-channel output gain, applied on the device.  fdc_pipeline_set_output_format has ONE scale for every channel of the plan; the
+ * channels of a real band differ by tens of dB, so with one scale the strong ones clip or the weak ones keep two or three bits of an sc8 / sc16 sample.
+ * With a gain g_c (float32) for channel c, every sample of that channel's stream becomes
+ *     y''_c[t] = ( f32(re(y'_c[t]) * g_c), f32(im(y'_c[t]) * g_c) )
+ * where y' is exactly what the entry writes with gains off (after fine tuning when that is on).  Each product is rounded once in float32 and kept out of
+ * FMA contraction with whatever produced y' (the rule of the integer input's scale and of fine tuning); float32 subnormals are kept, so the statement
+ * holds for every finite value: in numpy, (y.view(np.float32) * np.float32(g)).view(np.complex64), bit for bit on every route.
+ * Order of the settings, fixed: cut -> fine tuning -> GAIN -> levels -> sc16 / sc8 narrowing.  The levels are those of y'' (a caller who wants the
+ * pre-gain power divides by g^2), so the clip rule peak * |scale| >= 32767.5 / 127.5 stays true; integer output is oq(y'' * scale): two roundings, the
+ * gain's and then the narrowing's, which is observably not oq(y' * (g * scale)).  The debug spectrum is unchanged.
+ *   fdc_pipeline_set_gains   gain[n], n = the channel count (else FDC_ERR_INVALID_ARGUMENT; n = 0 with no channels is accepted).  Any finite float32: zero
+ *                            mutes, negative inverts.  NaN or +-Inf in any entry: FDC_ERR_INVALID_ARGUMENT, nothing changes.  gain = NULL, or every
+ *                            entry exactly 1.0f, switches the setting off.
+ *   fdc_pipeline_gains       copies the n = C gains in force to dst: C ones while off.
+ * A SETTING like fdc_pipeline_set_output_format, _set_fine_tuning and _set_levels: it may change between any two calls and applies from the next one; it
+ * does not touch the history, the block counter or the input-form latch, and survives fdc_pipeline_reset; refused while a pipelined sinks batch is inside
+ * the handle; it waits for the handle's own stream before the device table is rewritten (device entries on another stream: the caller orders them).  The
+ * first call that switches gains on allocates a device table of C floats, once; later calls — an AGC that sets new gains before every work call —
+ * allocate nothing and copy C floats; nothing is allocated in a work call or a device entry.  A device call needs nblocks <= max_blocks only where it
+ * already does (levels on, or a narrowed integer route): gains add no rule of their own.
+ * While gains are on, fdc_pipeline_work_sinks, _work_spectrum, _process_device_power and fdc_pipeline_work_waterfall return FDC_ERR_INVALID_ARGUMENT and
+ * change nothing (fdc_pipeline_flush_sinks still flushes), and every plan writes complex float first: with integer output the samples are narrowed behind
+ * the gain ("output sc16: narrowed"; "fused" again once gains are off).  fdc_pipeline_describe names the route of the last call: where the rotation's
+ * pass runs (fine tuning on, off path 5 or with a spectrum output) it multiplies the turned sample it holds ("gains: with the rotation"); otherwise one
+ * pass over the launch group's float results multiplies them in place ("gains: pass") or, where the call narrows an integer output on the device
+ * itself (the device entries, staged host outputs), reads them once and stores the narrow samples ("gains: with the narrowing").  With levels on the
+ * same pass sums them ("levels: with the rotation" / "levels: with the gains"): no further trip over the output. */
+int fdc_pipeline_set_gains(fdc_pipeline *p, const float *gain, int n);
+int fdc_pipeline_gains(const fdc_pipeline *p, float *dst, int n);
 
 /* Optional: pin a host range that will be handed to fdc_pipeline_work() again and again (GNU Radio's circular buffers
  * live as long as the flowgraph: register them in start(), unregister in stop()).  A call whose `in` lies in a
@@ -362,6 +392,8 @@ int fdc_pipeline_group_set_fine_tuning(fdc_pipeline_group *g, const double *nu, 
  * nblocks must be that call's block count (FDC_ERR_INVALID_ARGUMENT otherwise, while levels are off and before any call) */
 int fdc_pipeline_group_set_levels(fdc_pipeline_group *g, int32_t on);
 int fdc_pipeline_group_levels(fdc_pipeline_group *g, float *dst, int nblocks);
+/* channel gains for every member (fdc_pipeline_set_gains: the same arguments, refusals and setting semantics) */
+int fdc_pipeline_group_set_gains(fdc_pipeline_group *g, const float *gain, int n);
 int32_t fdc_pipeline_group_size(const fdc_pipeline_group *g);
 fdc_pipeline *fdc_pipeline_group_member(fdc_pipeline_group *g, int i);   /* owned by the group (fdc_pipeline_path, sizes, timing) */
 int32_t fdc_pipeline_group_device(const fdc_pipeline_group *g, int i);
