@@ -307,6 +307,7 @@ int process_device_impl(fdc_pipeline *p, DeviceCall &call, const void *d_ring, i
         // the power of the 16-bin groups of the caller's spectrum (fdc_pipeline_process_device_power): summed by the block kernel while the bins are in
         // its registers; by a pass over the spectrum where another transform ran
         float *const gp = (call.gpow && d_spectrum) ? call.gpow + (size_t)(spec - call.gpow_origin) / 16 : nullptr;
+        if (gp) p->gpow_src |= (p->fwd_block && !few) ? 1 : 2;
         if (p->fwd_block && !few)
             HIPCHK(fdc::launch_block_fft(p->N, in0, (size_t)p->H, spec, nb, p->d_tw256, p->d_ftwq, p->d_fcbt,
                                               p->d_fshn, p->d_fslot, p->d_fscr, call.ncu, p->block_hints, s, evp, d_spectrum ? nullptr : p->d_keep, gp));

@@ -198,6 +198,7 @@ struct fdc_pipeline {
     bool hier_broken = false;    // a pipelined call failed after it had advanced the stream state: the pair of handles cannot go on (see work_sinks_pipelined)
     bool reserve_user = false;   // fdc_pipeline_reserve_compute_units was called with n > 0: the pipelined entry takes that reservation, not its own
     std::string wf_route;        // the route of the last waterfall call (fdc_pipeline_describe)
+    int gpow_src = 0;            // who summed the 16-bin group powers of the last waterfall call: bit 0 the block kernel's epilogue, bit 1 k_group_power
     bool cfg_generic = false;    // FDC_FORCE_GENERIC=1: bypass the size-specialised kernels (A/B testing)
     // timing
     bool timing = false;

@@ -335,11 +335,17 @@ int fdc_pipeline_work_waterfall(fdc_pipeline *p, fdc_waterfall *w, const void *i
     call.rows = fused ? fdc::wf_block_rows(w) : nullptr;
     call.rows_first = p->blockcount;
     call.gpow = gpow; call.gpow_origin = gpow ? spec : nullptr;
+    p->gpow_src = 0;
     rc = pipeline_work_impl(p, call, in, nblocks, outs, nullptr);
     if (rc < 0) return rc;
     p->wf_route = fused ? "k_f4096 epilogue (pixels from the spectrum in LDS)"
                 : groups ? "k_wf_from_groups (pixels from the 16-bin group powers of the internal spectrum)"
                          : "k_wf_from_spectrum (pixels from the bins of the internal spectrum)";
+    // which transform of the call's launch groups summed the group powers (a call may mix them: a short last launch group takes the two-pass transform)
+    if (groups)
+        p->wf_route += p->gpow_src == 1 ? ", group powers: block kernel epilogue"
+                     : p->gpow_src == 2 ? ", group powers: k_group_power behind the two-pass transform"
+                                        : ", group powers: block kernel epilogue and k_group_power";
     if (groups) HIPCHK(fdc::wf_rows_from_groups(w, gpow, nblocks, p->stream));
     else if (!fused) HIPCHK(fdc::wf_rows_from_spectrum(w, spec, nblocks, p->stream));
     rc = fdc::wf_finish(w, nblocks, p->stream, rows, index, rgb, nrows);

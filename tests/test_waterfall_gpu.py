@@ -144,8 +144,10 @@ def test_waterfall_entry_refuses_mismatches_and_small_caps():
 @pytest.mark.parametrize("nb", [8, 100])
 def test_group_sum_route_at_65536(oracle, name, chans, flags, path, nb):
     """Plans off path 5 take the spectrum path for a waterfall call, whatever their path without rows (fdc_pipeline_path() names the plan's
-    path; a call with rows runs the spectrum path, as a call with a debug spectrum does): nb = 100 takes the block forward kernel, whose
-    epilogue sums the 16-bin groups; nb = 8, below the block kernels' minimum, the two-pass transform and a pass over the spectrum."""
+    path; a call with rows runs the spectrum path, as a call with a debug spectrum does).  Both block counts take the block forward kernel, whose
+    epilogue sums the 16-bin groups: the suite runs with the block kernels' minimum at one block (conftest.py, FDC_BLOCK_MIN_BLOCKS), so nb = 8
+    is not below it.  The two-pass transform with a pass over the spectrum (k_group_power) behind it is run by
+    test_waterfall_routes_gpu.py::test_group_sum_route_at_every_r, which takes the minimum back to its default or forbids the block kernels."""
     N, R, D = 65536, 2, 3
     H = N - N // R
     x = noise(nb * H, 5 + nb)
