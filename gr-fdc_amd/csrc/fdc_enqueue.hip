@@ -142,20 +142,84 @@ static bool iq_fused(const fdc_pipeline *p, const DeviceCall &call, bool few)
     return int_kernels(p, call) && (p->fused || !(few && two_launch_possible(p)));
 }
 
+// Path 5 (k_f4096, one launch per group) serves the call: the plan has it and no spectrum is asked for
+static bool path5(const fdc_pipeline *p, const DeviceCall &call) { return p->fused && !call.spectrum; }
+
+// THE RULE of the passes behind a plan's kernels (fdc_postpass.hip), on which oq_fused and PostPass both rest: they go over the kernels' complex
+// float results in the order rotation -> gain -> levels -> narrowing.  Path 5 turns its samples in its own stores; every other kernel leaves
+// fine tuning to the rotation pass.  The levels are of the float samples the caller gets (turned and gained), and the gain multiplies float samples.
+// So a call with a rotation pass, gains or levels has its kernels store float, and narrows behind the last of them.
+static bool rotation_pass(const fdc_pipeline *p, const DeviceCall &call) { return p->fine_on && !path5(p, call); }
+static bool float_passes(const fdc_pipeline *p, const DeviceCall &call) { return rotation_pass(p, call) || call.gain || call.levels; }
+
 // integer output: whether EVERY launch group of a call of nblocks narrows in its own kernel's stores (k_blk256: streamed stores; not N = 65536 at R = 4
 // on float input, whose forms would spill: fdc_block256.hip kOqR4Narrowed); otherwise the call writes complex float and k_complex_to_iq narrows it
 // (whole call: one layout)
 static bool oq_fused(const fdc_pipeline *p, const DeviceCall &call, int nblocks)
 {
-    if (call.levels) return false;           // the levels are of the float samples: float, the levels pass, then narrowed (every path, path 5 included)
-    if (call.gain) return false;             // the gain multiplies the float samples: float, the gain pass, then narrowed (every path, path 5 included)
+    if (float_passes(p, call)) return false;  // THE RULE: float, the passes, then narrowed (every path, path 5 included)
     if (!int_kernels(p, call)) return false;
     if (p->fused) return true;
-    if (p->fine_on) return false;            // the banks' kernels do not turn their samples: float, k_fine_rotate, then narrowed
     if (!(p->block_hints & 1) || (!call.fmt && p->N == 65536 && p->R == 4)) return false;
     for (int m0 = 0; m0 < nblocks; m0 += p->chunk)
         if (std::min(p->chunk, nblocks - m0) < p->block_min && two_launch_possible(p)) return false;
     return true;
+}
+
+// What one call runs behind its kernels: per launch group (run_post_passes), then once over the call (run_post_tail).  Filled once per call
+// (post_pass) from THE RULE: a pass carries what stands behind it in that order where it can, so that a group's samples are gone over once.
+struct PostPass {
+    bool fine_fused = false;    // fine tuning on, and path 5 turns the samples in its own stores: no rotation pass
+    bool rotate = false;        // k_fine_rotate behind the group's kernels: fine tuning on, off path 5 ...
+    bool rot_gain = false;      //   ... which multiplies the turned samples by the gains
+    bool rot_levels = false;    //   ... and reduces them to the levels (not under FDC_LEVELS_SEPARATE)
+    bool gain_pass = false;     // k_chan_gain: gains on and no rotation pass; it sums the levels too, where they are on ...
+    bool gain_narrows = false;  //   ... and stores the narrow samples, where the call narrows behind its kernels
+    bool levels_pass = false;   // k_chan_levels: levels on and neither pass above carries them
+    bool narrow_tail = false;   // the call-wide k_complex_to_iq from the float staging
+    const float *gain = nullptr;
+    float2 *levels = nullptr;
+};
+
+static PostPass post_pass(const fdc_pipeline *p, const DeviceCall &call, bool ofused)
+{
+    PostPass pp;
+    if (p->C <= 0) return pp;
+    const bool narrow = call.ofmt && !ofused && call.narrow;
+    pp.gain = call.gain; pp.levels = call.levels;
+    pp.fine_fused = p->fine_on && path5(p, call);
+    pp.rotate = rotation_pass(p, call);
+    pp.rot_gain = pp.rotate && pp.gain;
+    pp.rot_levels = pp.rotate && pp.levels && !p->levels_separate;
+    pp.gain_pass = pp.gain && !pp.rotate;
+    pp.gain_narrows = pp.gain_pass && narrow;
+    pp.levels_pass = pp.levels && !pp.rot_levels && !pp.gain_pass;
+    pp.narrow_tail = narrow && !pp.gain_narrows;
+    return pp;
+}
+
+// behind the kernels of launch group g, whose float results are in o (d_out: the call's output, narrow where the gain pass narrows)
+static int run_post_passes(const fdc_pipeline *p, const DeviceCall &call, const PostPass &pp, const Span &g, float2 *o, void *d_out)
+{
+    hipStream_t s = call.stream;
+    if (pp.rotate)
+        HIPCHK(fdc::launch_fine_rotate(o, p->d_chans, p->d_fine, p->d_fstep, p->C, g.nb, g.m0, g.nblocks, g.first_block, s, pp.rot_levels ? pp.levels : nullptr,
+                                       pp.rot_gain ? pp.gain : nullptr));
+    if (pp.gain_pass)
+        HIPCHK(fdc::launch_chan_gain(o, p->d_chans, pp.gain, pp.levels, pp.gain_narrows ? call.ofmt : 0, call.oscale, pp.gain_narrows ? d_out : nullptr, p->C, g.nb,
+                                     g.m0, g.nblocks, s));
+    if (pp.levels_pass) HIPCHK(fdc::launch_chan_levels(o, p->d_chans, pp.levels, p->C, g.nb, g.m0, g.nblocks, s));
+    return FDC_OK;
+}
+
+// behind the last launch group: the call-wide narrowing, and how the call was served (fdc_pipeline_describe)
+static int run_post_tail(fdc_pipeline *p, const DeviceCall &call, const PostPass &pp, int nblocks, void *d_out)
+{
+    if (pp.narrow_tail) HIPCHK(fdc::launch_complex_to_iq(call.ofmt, call.oscale, call.fout, d_out, (size_t)nblocks * p->sum_lout, call.stream));
+    if (pp.fine_fused || pp.rotate) p->fine_route = pp.fine_fused ? "fused" : "rotated";
+    if (pp.levels) p->levels_route = pp.rot_levels ? "with the rotation" : pp.gain_pass ? "with the gains" : "pass";
+    if (pp.gain) p->gains_route = pp.rot_gain ? "with the rotation" : pp.gain_narrows ? "with the narrowing" : "pass";
+    return FDC_OK;
 }
 
 // The enqueue path of every entry: nblocks blocks from d_ring (the stream's block first_block first) to d_out, as `call` says; its results say how
@@ -184,30 +248,7 @@ int process_device_impl(fdc_pipeline *p, DeviceCall &call, const void *d_ring, i
     unsigned char *const ob = ofused ? static_cast<unsigned char *>(d_out) : reinterpret_cast<unsigned char *>(o);
     const bool use_poly = p->poly_ok && !d_spectrum;
     const unsigned out_bytes = (unsigned)((int64_t)nblocks * p->sum_lout * (int64_t)osz);
-    // fine tuning: path 5 turns the samples in its own stores; everywhere else k_fine_rotate goes over the launch group's float results behind its channel kernels
-    const bool fine = p->fine_on && p->C > 0, fine_fused = fine && p->fused && !d_spectrum;
-    // channel levels: one pass over the launch group's float results (k_chan_levels), behind the rotation — or inside it: with both settings on,
-    // off path 5, k_fine_rotate reduces the turned samples it holds and no second trip over the output is made
-    float2 *const lev = p->C > 0 ? call.levels : nullptr;
-    const bool lev_merged = lev && fine && !fine_fused && !p->levels_separate;
-    // channel gains: behind the rotation and in front of the levels and the narrowing.  Where k_fine_rotate runs it multiplies the turned sample it holds
-    // (gain_rot); where none runs k_chan_gain goes over the launch group's float results once, sums the levels of the gained samples too (k_chan_levels is
-    // then not launched) and, where this path narrows an integer output itself, stores the narrow samples (gain_narrow: no call-wide k_complex_to_iq)
-    const float *const gain = p->C > 0 ? call.gain : nullptr;
-    const bool gain_rot = gain && fine && !fine_fused;
-    const bool gain_narrow = gain && !gain_rot && ofmt && !ofused && call.narrow;
-    auto levels = [&](const Span &g) -> int {
-        if (gain && !gain_rot)
-            HIPCHK(fdc::launch_chan_gain(o, p->d_chans, gain, lev, gain_narrow ? ofmt : 0, call.oscale, gain_narrow ? d_out : nullptr, p->C, g.nb, g.m0, g.nblocks, s));
-        else if (lev) HIPCHK(fdc::launch_chan_levels(o, p->d_chans, lev, p->C, g.nb, g.m0, g.nblocks, s));
-        return FDC_OK;
-    };
-    auto rotate = [&](const Span &g) -> int {
-        if (fine)
-            HIPCHK(fdc::launch_fine_rotate(o, p->d_chans, p->d_fine, p->d_fstep, p->C, g.nb, g.m0, g.nblocks, g.first_block, s, lev_merged ? lev : nullptr,
-                                           gain_rot ? gain : nullptr));
-        return lev_merged ? FDC_OK : levels(g);
-    };
+    const PostPass pp = post_pass(p, call, ofused);      // what runs behind the kernels of every launch group and behind the call: decided here, once
     for (int m0 = 0; m0 < nblocks; m0 += p->chunk) {
         const int nb = std::min(p->chunk, nblocks - m0);
         const Span grp{nb, m0, nblocks, first_block};
@@ -239,7 +280,7 @@ int process_device_impl(fdc_pipeline *p, DeviceCall &call, const void *d_ring, i
             // N = 4096: one launch, nothing but the input samples and the output samples crosses the memory interface
             if (tg) HIPCHK(hipEventRecord(p->events[span[0]], s));
             float *wf = call.rows ? call.rows + (size_t)(first_block - call.rows_first + m0) * fdc::kWfWidth : nullptr;
-            if (fine_fused)
+            if (pp.fine_fused)
                 HIPCHK(fdc::launch_fused4096_fine(ifused ? fmt : 0, call.scale, ifused ? raw0 : static_cast<const void *>(in0), (size_t)p->H, ofused ? ofmt : 0, call.oscale,
                                                   ofused ? d_out : static_cast<void *>(o), nb, p->R, m0, nblocks, first_block, p->d_tw, p->ntab, p->d_wins, p->d_f4rows,
                                                   p->f4_cls, p->f4_teams, p->d_f4fine, p->d_fstep, s));
@@ -252,7 +293,7 @@ int process_device_impl(fdc_pipeline *p, DeviceCall &call, const void *d_ring, i
             else
                 HIPCHK(fdc::launch_fused4096(in0, (size_t)p->H, o, nb, p->R, m0, nblocks, first_block, p->d_tw, p->ntab, p->d_wins, p->d_f4rows, p->f4_cls, p->f4_teams, s, wf));
             if (tg) { HIPCHK(hipEventRecord(p->events[span[1]], s)); span[2] = span[3] = span[1]; span[4] = kSpanBanks; p->ev_spans.push_back(span); }
-            RCCHK(levels(grp));
+            RCCHK(run_post_passes(p, call, pp, grp, o, d_out));
             continue;
         }
         if (use_poly && p->poly_block && !(few && two_launch_possible(p))) {
@@ -275,7 +316,7 @@ int process_device_impl(fdc_pipeline *p, DeviceCall &call, const void *d_ring, i
             if (p->split) RCCHK(run_remainder(p, call, in0, o, grp, tg ? p->events[span[2]] : nullptr, tg ? p->events[span[3]] : nullptr));
             else if (tg) span[2] = span[3] = span[1];
             if (tg) { span[4] = kSpanBanks; p->ev_spans.push_back(span); }
-            RCCHK(rotate(grp));
+            RCCHK(run_post_passes(p, call, pp, grp, o, d_out));
             continue;
         }
         if (use_poly) {
@@ -294,7 +335,7 @@ int process_device_impl(fdc_pipeline *p, DeviceCall &call, const void *d_ring, i
             else
                 HIPCHK(fdc::launch_poly_stage2(p->d_g, o, p->N / 256, p->R, nb, m0, nblocks, p->d_tw256, p->d_tw1024, bk.d_slot_off, out_bytes, call.ncu, s));
             if (p->split) RCCHK(run_remainder(p, call, in0, o, grp, nullptr, nullptr));   // (timing: the remainder is counted with stage 2)
-            RCCHK(rotate(grp));
+            RCCHK(run_post_passes(p, call, pp, grp, o, d_out));
             if (tg) {
                 HIPCHK(hipEventRecord(p->events[span[3]], s));
                 span[4] = kSpanTwoLaunch;
@@ -321,17 +362,14 @@ int process_device_impl(fdc_pipeline *p, DeviceCall &call, const void *d_ring, i
             if (gp) HIPCHK(fdc::launch_group_power(spec, p->N, nb, gp, s));
         }
         RCCHK(run_channel_groups(p, false, spec, o, grp, s));
-        RCCHK(rotate(grp));
+        RCCHK(run_post_passes(p, call, pp, grp, o, d_out));
         if (tg) {
             HIPCHK(hipEventRecord(p->events[span[3]], s));
             span[4] = p->N <= fdc::kMaxLdsFft ? kSpanSpectrumLds : kSpanSpectrum;
             p->ev_spans.push_back(span);
         }
     }
-    if (ofmt && !ofused && call.narrow && !gain_narrow && p->C > 0) HIPCHK(fdc::launch_complex_to_iq(ofmt, call.oscale, call.fout, d_out, (size_t)nblocks * p->sum_lout, s));
-    if (fine) p->fine_route = fine_fused ? "fused" : "rotated";
-    if (lev) p->levels_route = lev_merged ? "with the rotation" : gain && !gain_rot ? "with the gains" : "pass";
-    if (gain) p->gains_route = gain_rot ? "with the rotation" : gain_narrow ? "with the narrowing" : "pass";
+    RCCHK(run_post_tail(p, call, pp, nblocks, d_out));
     return FDC_OK;
 }
 

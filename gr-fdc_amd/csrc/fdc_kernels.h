@@ -225,6 +225,9 @@ hipError_t launch_group_power(const float2 *spec, int N, int nblocks, float *gpo
 hipError_t launch_real_to_complex(const float *in, float2 *out, size_t n, hipStream_t s);
 // complex integer samples (fmt: kIqSc16 / kIqSc8, fdc_iq.hpp) -> complex float, (I * scale, Q * scale)
 hipError_t launch_iq_to_complex(int fmt, float scale, const void *in, float2 *out, size_t n, hipStream_t s);
+
+// The passes behind a plan's kernels (fdc_postpass.hip), over the channel-major float results of a launch group; which of them a call runs, and in
+// which order: fdc_enqueue.hip, PostPass
 // complex float -> complex integer samples (fmt: kIqSc16 / kIqSc8), each component saturate(round_half_even(x * scale)) (fdc_iq.hpp oq_bits)
 hipError_t launch_complex_to_iq(int fmt, float scale, const float2 *in, void *out, size_t n, hipStream_t s);
 
@@ -235,7 +238,7 @@ hipError_t launch_fine_rotate(float2 *out, const ChanDev *chans, const FineChan 
                               int64_t first_block, hipStream_t s, float2 *levels = nullptr, const float *gain = nullptr);
 
 // Channel levels (fdc_pipeline_set_levels): blocks [mbase, mbase + nb_chunk) of a call's channel-major float outputs read once; levels[(mbase + m) * nchan + c] =
-// (sum of re^2 + im^2, max of |re| and |im|) over the lout_c samples of block m of channel c.  One summation order per lout (fdc_kernels.hip)
+// (sum of re^2 + im^2, max of |re| and |im|) over the lout_c samples of block m of channel c.  One summation order per lout (fdc_postpass.hip)
 hipError_t launch_chan_levels(const float2 *out, const ChanDev *chans, float2 *levels, int nchan, int nb_chunk, int mbase, int nb_call, hipStream_t s);
 
 // Channel gains (fdc_pipeline_set_gains) where no rotation pass runs: blocks [mbase, mbase + nb_chunk) of a call's channel-major float results times

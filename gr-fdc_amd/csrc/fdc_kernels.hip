@@ -20,7 +20,6 @@
 #include <type_traits>
 #include "fdc_radix16.hpp"
 #include "fdc_iq.hpp"
-#include "fdc_fine.hpp"
 #include "fdc_devutil.hpp"
 
 namespace fdc {
@@ -998,414 +997,6 @@ hipError_t launch_iq_to_complex(int fmt, float scale, const void *in, float2 *ou
     if (fmt == kIqSc16) hipLaunchKernelGGL(k_iq_to_complex<sc16>, dim3((unsigned)g), dim3(256), 0, s, static_cast<const sc16 *>(in), out, n, scale);
     else if (fmt == kIqSc8) hipLaunchKernelGGL(k_iq_to_complex<sc8>, dim3((unsigned)g), dim3(256), 0, s, static_cast<const sc8 *>(in), out, n, scale);
     else return hipErrorInvalidValue;
-    return hipGetLastError();
-}
-
-// complex float -> complex integer samples, times scale (fdc_iq.hpp oq_narrow): the narrowing back end of the plans without integer stores of their own
-template <class TO>
-__global__ __launch_bounds__(256) void k_complex_to_iq(const float2 *__restrict__ in, TO *__restrict__ out, size_t n, float scale)
-{
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) out[i] = oq_narrow(TO{}, from2(in[i]), scale);
-}
-
-hipError_t launch_complex_to_iq(int fmt, float scale, const float2 *in, void *out, size_t n, hipStream_t s)
-{
-    if (!n) return hipSuccess;
-    size_t g = (n + 255) / 256; if (g > 8192) g = 8192;
-    if (fmt == kIqSc16) hipLaunchKernelGGL(k_complex_to_iq<sc16>, dim3((unsigned)g), dim3(256), 0, s, in, static_cast<sc16 *>(out), n, scale);
-    else if (fmt == kIqSc8) hipLaunchKernelGGL(k_complex_to_iq<sc8>, dim3((unsigned)g), dim3(256), 0, s, in, static_cast<sc8 *>(out), n, scale);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
-}
-
-// Channel levels (fdc_pipeline_set_levels): power = sum of re^2 + im^2 and peak = max of |re|, |im| (fmax: a NaN component is passed over) of one row —
-// the lout samples of one (block, channel).  ONE ORDER PER SUM: the bits of a row's power depend on lout and the row's samples only.  The row goes to
-// 2^lev_log2_lanes(lout) lanes of one wave, by lout alone; lane `sub` takes the sample PAIRS sub, sub + lanes, ... in index order, of a pair the even
-// sample first; a term is (re re + im im), each product and each sum rounded on its own (no FMA contraction, as fine_mul and oq_bits); the lanes are
-// joined by an xor butterfly from distance 1 upwards.  Both access widths of both kernels (k_chan_levels, k_fine_rotate<true>) keep exactly this, so
-// neither the row's alignment nor how the stream was cut, nor which kernel summed it, shows in the result.  No atomics, no LDS.
-struct LevAcc { float sum, peak; };
-
-__device__ __forceinline__ unsigned lev_log2_lanes(unsigned lout)
-{
-    const unsigned npair = (lout + 1) >> 1;
-    const unsigned lg = npair <= 1 ? 0 : 32 - (unsigned)__clz((int)(npair - 1));
-    return lg > 6 ? 6 : lg;
-}
-
-// a lane starts from (0, NaN): a lane without samples adds +0 and its NaN is passed over by fmax; a row of NaN only keeps NaN (np.fmax.reduce)
-__device__ __forceinline__ LevAcc lev_zero() { return LevAcc{0.0f, __builtin_nanf("")}; }
-
-__device__ __forceinline__ void lev_add(LevAcc &a, cf y)
-{
-#pragma clang fp contract(off)
-    const float p = y.x * y.x, q = y.y * y.y;
-    const float t = p + q;
-    a.sum = a.sum + t;
-    a.peak = fmaxf(a.peak, fmaxf(fabsf(y.x), fabsf(y.y)));
-}
-
-// the row's 2^lg lanes joined: every lane of the row ends with the row's values (float addition commutes, so with the same bits)
-__device__ __forceinline__ void lev_join(LevAcc &a, unsigned lg)
-{
-    for (unsigned d = 1; d < (1u << lg); d <<= 1) {
-        a.sum = a.sum + __shfl_xor(a.sum, (int)d, 64);
-        a.peak = fmaxf(a.peak, __shfl_xor(a.peak, (int)d, 64));
-    }
-}
-
-// Fine tuning behind the channel kernels of a launch group (fdc_fine.hpp): blocks [mbase, mbase + nb) of the call's channel-major float outputs, in place.
-// A channel's rows of the group are one contiguous run; a row — one (block, channel): lout samples, one base — goes to a power-of-two set of lanes of
-// a wave, 16 bytes per lane and access where the row allows it (lout even, the run 16-byte aligned; the step table's rows start at even offsets).
-// LEVELS (fine tuning and channel levels both on): the turned samples are reduced while the lane holds them and one lane of the row stores
-// levels[(mbase + m) * nchan + c]; the lanes take sample pairs in both access widths (the levels' one order, above).  LEVELS = false is the kernel as it was.
-// (LV: the two arguments only the LEVELS form has — float2 *levels, int nchan — so that k_fine_rotate<false> keeps the parent's argument block too)
-// GAIN (fine tuning and channel gains both on, fdc_pipeline_set_gains): one more argument at the end of LV, const float *gain — the turned sample times
-// gain[c] (gain_mul: rounded once, on its own), and it is the gained sample that is stored and reduced: k_fine_rotate<false, const float *> and
-// k_fine_rotate<true, float2 *, int, const float *>.  The two forms without it keep their argument blocks and their instructions.
-__device__ __forceinline__ cf gain_mul(cf y, float g) { return mk(iq_mul(y.x, g), iq_mul(y.y, g)); }
-__device__ __forceinline__ const float *fine_gain_arg() { return nullptr; }
-__device__ __forceinline__ const float *fine_gain_arg(const float *g) { return g; }
-__device__ __forceinline__ const float *fine_gain_arg(float2 *, int) { return nullptr; }
-__device__ __forceinline__ const float *fine_gain_arg(float2 *, int, const float *g) { return g; }
-
-template <bool LEVELS, class... LV>
-__global__ __launch_bounds__(256) void k_fine_rotate(float2 *out, const ChanDev *__restrict__ chans, const FineChan *__restrict__ fine,
-                                                     const float2 *__restrict__ step, int c0, int nb, int mbase, long long nb_call,
-                                                     unsigned long long first_block, LV... lv)
-{
-    constexpr bool GAIN = sizeof...(LV) == (LEVELS ? 3 : 1);
-    static_assert(GAIN || sizeof...(LV) == (LEVELS ? 2 : 0), "k_fine_rotate<true, float2 *, int[, const float *]> or k_fine_rotate<false[, const float *]>");
-    const int c = c0 + (int)blockIdx.y;
-    const unsigned lout = (unsigned)chans[c].lout;
-    const FineChan fc = fine[c];
-    float g = 1.0f;
-    if constexpr (GAIN) g = fine_gain_arg(lv...)[c];
-    float2 *o = out + nb_call * chans[c].out_off + (long long)mbase * lout;
-    const float2 *st = step + fc.step_off;
-    const bool wide = !(lout & 1) && (reinterpret_cast<uintptr_t>(o) & 15) == 0;
-    if constexpr (LEVELS) {
-        struct Dst { float2 *levels; int nchan; const float *gain = nullptr; };
-        const Dst dst{lv...};
-        float2 *const levels = dst.levels;
-        const int nchan = dst.nchan;
-        const unsigned npair = (lout + 1) >> 1, lg = lev_log2_lanes(lout);
-        const unsigned lanes = 1u << lg, lane = threadIdx.x & 63, sub = lane & (lanes - 1), rows = 64u >> lg;
-        const unsigned wave = blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = gridDim.x * 4;
-        // (whole waves leave together: the trip count depends on the wave alone, so every lane of a row is there for the butterfly)
-        for (unsigned m0 = wave * rows; m0 < (unsigned)nb; m0 += nwaves * rows) {
-            const unsigned m = m0 + (lane >> lg);
-            const bool live = m < (unsigned)nb;
-            LevAcc acc = lev_zero();
-            if (live) {
-                const cf base = fine_base(fc.inc, first_block + (unsigned long long)(mbase + (int)m), lout);
-                float2 *row = o + (size_t)m * lout;
-                if (wide) {
-                    for (unsigned i = sub; i < npair; i += lanes) {
-                        const float4 y = ld4(row + 2 * i), s = ld4(st + 2 * i);
-                        cf a = fine_rotate(mk(y.x, y.y), base, mk(s.x, s.y)), b = fine_rotate(mk(y.z, y.w), base, mk(s.z, s.w));
-                        if constexpr (GAIN) { a = gain_mul(a, g); b = gain_mul(b, g); }
-                        st4(row + 2 * i, a, b);
-                        lev_add(acc, a); lev_add(acc, b);
-                    }
-                } else {
-                    for (unsigned i = sub; i < npair; i += lanes) {
-                        cf a = fine_rotate(ld2(row + 2 * i), base, ld2(st + 2 * i));
-                        if constexpr (GAIN) a = gain_mul(a, g);
-                        st2(row + 2 * i, a);
-                        lev_add(acc, a);
-                        if (2 * i + 1 < lout) {
-                            cf b = fine_rotate(ld2(row + 2 * i + 1), base, ld2(st + 2 * i + 1));
-                            if constexpr (GAIN) b = gain_mul(b, g);
-                            st2(row + 2 * i + 1, b);
-                            lev_add(acc, b);
-                        }
-                    }
-                }
-            }
-            lev_join(acc, lg);
-            if (live && sub == 0) levels[(size_t)(mbase + (int)m) * (size_t)nchan + (size_t)c] = make_float2(acc.sum, acc.peak);
-        }
-    } else {
-        const unsigned per = wide ? lout >> 1 : lout;                              // accesses per row
-        unsigned lg = per <= 1 ? 0 : 32 - (unsigned)__clz((int)(per - 1));
-        if (lg > 6) lg = 6;
-        const unsigned lanes = 1u << lg, lane = threadIdx.x & 63, sub = lane & (lanes - 1), rows = 64u >> lg;
-        const unsigned wave = blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = gridDim.x * 4;
-        for (unsigned m = wave * rows + (lane >> lg); m < (unsigned)nb; m += nwaves * rows) {
-            const cf base = fine_base(fc.inc, first_block + (unsigned long long)(mbase + (int)m), lout);
-            float2 *row = o + (size_t)m * lout;
-            if (wide) {
-                for (unsigned i = sub; i < per; i += lanes) {
-                    const float4 y = ld4(row + 2 * i), s = ld4(st + 2 * i);
-                    if constexpr (GAIN)
-                        st4(row + 2 * i, gain_mul(fine_rotate(mk(y.x, y.y), base, mk(s.x, s.y)), g), gain_mul(fine_rotate(mk(y.z, y.w), base, mk(s.z, s.w)), g));
-                    else
-                        st4(row + 2 * i, fine_rotate(mk(y.x, y.y), base, mk(s.x, s.y)), fine_rotate(mk(y.z, y.w), base, mk(s.z, s.w)));
-                }
-            } else {
-                for (unsigned i = sub; i < per; i += lanes) {
-                    if constexpr (GAIN) st2(row + i, gain_mul(fine_rotate(ld2(row + i), base, ld2(st + i)), g));
-                    else st2(row + i, fine_rotate(ld2(row + i), base, ld2(st + i)));
-                }
-            }
-        }
-    }
-}
-
-// levels: null = fine tuning alone; else the levels of the call's block 0 ([block][nchan] float2): the turned samples are reduced in the same pass
-// gain: null = none; else the nchan channel gains: the turned samples are multiplied in the same pass, in front of the reduction
-hipError_t launch_fine_rotate(float2 *out, const ChanDev *chans, const FineChan *fine, const float2 *step, int nchan, int nb_chunk, int mbase, int nb_call,
-                              int64_t first_block, hipStream_t s, float2 *levels, const float *gain)
-{
-    if (nchan <= 0 || nb_chunk <= 0) return hipSuccess;
-    for (int c0 = 0; c0 < nchan; c0 += 32768) {
-        const int nc = nchan - c0 < 32768 ? nchan - c0 : 32768;
-        const int gx = std::max(1, std::min((nb_chunk + 3) / 4, (2048 + nc - 1) / nc));      // grid-stride over the rows: about eight workgroups per unit
-        if (gain && levels)
-            hipLaunchKernelGGL((k_fine_rotate<true, float2 *, int, const float *>), dim3((unsigned)gx, (unsigned)nc), dim3(256), 0, s, out, chans, fine, step, c0,
-                               nb_chunk, mbase, (long long)nb_call, (unsigned long long)first_block, levels, nchan, gain);
-        else if (gain)
-            hipLaunchKernelGGL((k_fine_rotate<false, const float *>), dim3((unsigned)gx, (unsigned)nc), dim3(256), 0, s, out, chans, fine, step, c0, nb_chunk, mbase,
-                               (long long)nb_call, (unsigned long long)first_block, gain);
-        else if (levels)
-            hipLaunchKernelGGL((k_fine_rotate<true, float2 *, int>), dim3((unsigned)gx, (unsigned)nc), dim3(256), 0, s, out, chans, fine, step, c0, nb_chunk, mbase,
-                               (long long)nb_call, (unsigned long long)first_block, levels, nchan);
-        else
-            hipLaunchKernelGGL(k_fine_rotate<false>, dim3((unsigned)gx, (unsigned)nc), dim3(256), 0, s, out, chans, fine, step, c0, nb_chunk, mbase,
-                               (long long)nb_call, (unsigned long long)first_block);
-    }
-    return hipGetLastError();
-}
-
-// Channel levels of a launch group: blocks [mbase, mbase + nb) of the call's channel-major float outputs, read once; one float2 (power, peak) per
-// (block, channel) goes to levels[(mbase + m) * nchan + c] and nothing else is written.  k_fine_rotate's shape: grid y = channel, a row on a
-// power-of-two set of lanes of one wave (by lout: the levels' one order, above), 16 bytes per lane where the run is 16-byte aligned and lout even, two
-// 8-byte loads otherwise, a grid-stride loop over the blocks.  A trip issues all its loads — four pairs per lane: four rows where a row is one pair per
-// lane, four steps along a longer row — before the first is used.
-// (no branch around a load: a lane without a pair of its own loads one that exists — the row's last pair, the group's last row — and leaves it out of
-// its sums, so that the four loads of a trip are in flight together and not each behind its own wait)
-template <bool WIDE>
-__device__ __forceinline__ void lev_load(const float2 *row, unsigned i, unsigned lout, cf &a, cf &b)
-{
-    if (WIDE) {
-        const float4 y = ld4(row + 2 * i);
-        a = mk(y.x, y.y); b = mk(y.z, y.w);
-    } else {
-        a = ld2(row + 2 * i);
-        b = ld2(row + (2 * i + 1 < lout ? 2 * i + 1 : lout - 1));
-    }
-}
-
-template <bool WIDE>
-__device__ __forceinline__ void chan_levels_rows(const float2 *o, float2 *__restrict__ levels, unsigned lout, unsigned nb, int mbase, int nchan, int c)
-{
-    const unsigned npair = (lout + 1) >> 1, lg = lev_log2_lanes(lout);
-    const unsigned lanes = 1u << lg, lane = threadIdx.x & 63, sub = lane & (lanes - 1), rows = 64u >> lg;
-    const unsigned wave = blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = gridDim.x * 4;
-    if (npair <= lanes) {
-        // a row is at most one pair per lane: four rows per trip, a grid stride apart
-        const bool has = sub < npair, two = 2 * sub + 1 < lout;
-        const unsigned i = has ? sub : npair - 1;
-        for (unsigned m0 = wave * rows; m0 < nb; m0 += 4 * nwaves * rows) {
-            cf a[4], b[4];
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-                const unsigned m = m0 + (unsigned)u * nwaves * rows + (lane >> lg);
-                lev_load<WIDE>(o + (size_t)(m < nb ? m : nb - 1) * lout, i, lout, a[u], b[u]);
-            }
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-                const unsigned m = m0 + (unsigned)u * nwaves * rows + (lane >> lg);
-                LevAcc acc = lev_zero();
-                if (has) { lev_add(acc, a[u]); if (two) lev_add(acc, b[u]); }
-                lev_join(acc, lg);
-                if (m < nb && sub == 0) levels[(size_t)(mbase + (int)m) * (size_t)nchan + (size_t)c] = make_float2(acc.sum, acc.peak);
-            }
-        }
-    } else {
-        // a long row (more than 64 pairs) takes the whole wave: four steps of the row per trip, in index order
-        for (unsigned m = wave; m < nb; m += nwaves) {
-            const float2 *row = o + (size_t)m * lout;
-            LevAcc acc = lev_zero();
-            for (unsigned i0 = sub; i0 < npair; i0 += 4 * lanes) {
-                cf a[4], b[4];
-#pragma unroll
-                for (int u = 0; u < 4; u++) {
-                    const unsigned i = i0 + (unsigned)u * lanes;
-                    lev_load<WIDE>(row, i < npair ? i : npair - 1, lout, a[u], b[u]);
-                }
-#pragma unroll
-                for (int u = 0; u < 4; u++) {
-                    const unsigned i = i0 + (unsigned)u * lanes;
-                    if (i < npair) { lev_add(acc, a[u]); if (2 * i + 1 < lout) lev_add(acc, b[u]); }
-                }
-            }
-            lev_join(acc, lg);
-            if (sub == 0) levels[(size_t)(mbase + (int)m) * (size_t)nchan + (size_t)c] = make_float2(acc.sum, acc.peak);
-        }
-    }
-}
-
-__global__ __launch_bounds__(256) void k_chan_levels(const float2 *__restrict__ out, const ChanDev *__restrict__ chans, float2 *__restrict__ levels, int c0,
-                                                     int nchan, int nb, int mbase, long long nb_call)
-{
-    const int c = c0 + (int)blockIdx.y;
-    const unsigned lout = (unsigned)chans[c].lout;
-    const float2 *o = out + nb_call * chans[c].out_off + (long long)mbase * lout;
-    if (!(lout & 1) && (reinterpret_cast<uintptr_t>(o) & 15) == 0) chan_levels_rows<true>(o, levels, lout, (unsigned)nb, mbase, nchan, c);
-    else chan_levels_rows<false>(o, levels, lout, (unsigned)nb, mbase, nchan, c);
-}
-
-hipError_t launch_chan_levels(const float2 *out, const ChanDev *chans, float2 *levels, int nchan, int nb_chunk, int mbase, int nb_call, hipStream_t s)
-{
-    if (nchan <= 0 || nb_chunk <= 0) return hipSuccess;
-    for (int c0 = 0; c0 < nchan; c0 += 32768) {
-        const int nc = nchan - c0 < 32768 ? nchan - c0 : 32768;
-        const int gx = std::max(1, std::min((nb_chunk + 3) / 4, (2048 + nc - 1) / nc));      // grid-stride over the rows: about eight workgroups per unit
-        hipLaunchKernelGGL(k_chan_levels, dim3((unsigned)gx, (unsigned)nc), dim3(256), 0, s, out, chans, levels, c0, nchan, nb_chunk, mbase, (long long)nb_call);
-    }
-    return hipGetLastError();
-}
-
-// Channel gains of a launch group where no rotation pass runs (fdc_pipeline_set_gains): blocks [mbase, mbase + nb) of the call's channel-major float
-// results times gain[c], each component rounded once (gain_mul).  k_chan_levels' shape, trip for trip: grid y = channel, a row on 2^lev_log2_lanes(lout)
-// lanes of one wave, 16-byte accesses where lout is even and the run 16-byte aligned, 8-byte ones otherwise, a grid-stride loop over the blocks, the four
-// loads of a trip issued before the first use.  TO = float2: the product goes back where it was read (in place).  TO = sc16 / sc8: the float staging is
-// read only and oq_narrow(TO, product, scale) goes to the same sample offset of the call's narrow output `nar` — two samples per store where the row is
-// read 16 bytes at a time and the narrow run is aligned for it (pair), one otherwise.  LEVELS: the gained samples are reduced in the levels' one order
-// (pairs in index order, the even sample first, the butterfly from distance 1), so k_chan_levels is not launched behind this kernel.
-// (a lane without a pair of its own loads one that exists, as in chan_levels_rows, and neither stores nor sums it)
-__device__ __forceinline__ void gain_store(float2 *row, sc16 *, unsigned i, unsigned lout, bool wide, bool, cf a, cf b, float)
-{
-    if (wide) st4(row + 2 * i, a, b);
-    else { st2(row + 2 * i, a); if (2 * i + 1 < lout) st2(row + 2 * i + 1, b); }
-}
-
-template <class TO>
-__device__ __forceinline__ void gain_store(const float2 *, TO *nrow, unsigned i, unsigned lout, bool, bool pair, cf a, cf b, float scale)
-{
-    if (pair) {
-        if constexpr (std::is_same<TO, sc16>::value) *reinterpret_cast<uint2 *>(nrow + 2 * i) = make_uint2(oq_bits(TO{}, a, scale), oq_bits(TO{}, b, scale));
-        else *reinterpret_cast<unsigned *>(nrow + 2 * i) = oq_bits(TO{}, a, scale) | (oq_bits(TO{}, b, scale) << 16);
-    } else {
-        nrow[2 * i] = oq_narrow(TO{}, a, scale);
-        if (2 * i + 1 < lout) nrow[2 * i + 1] = oq_narrow(TO{}, b, scale);
-    }
-}
-
-template <bool WIDE, bool LEVELS, class TO>
-__device__ __forceinline__ void chan_gain_rows(typename std::conditional<std::is_same<TO, float2>::value, float2, const float2>::type *o,
-                                               typename std::conditional<std::is_same<TO, float2>::value, sc16, TO>::type *nar, bool pair, float g, float scale,
-                                               float2 *__restrict__ levels, unsigned lout, unsigned nb, int mbase, int nchan, int c)
-{
-    const unsigned npair = (lout + 1) >> 1, lg = lev_log2_lanes(lout);
-    const unsigned lanes = 1u << lg, lane = threadIdx.x & 63, sub = lane & (lanes - 1), rows = 64u >> lg;
-    const unsigned wave = blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = gridDim.x * 4;
-    if (npair <= lanes) {
-        // a row is at most one pair per lane: four rows per trip, a grid stride apart
-        const bool has = sub < npair, two = 2 * sub + 1 < lout;
-        const unsigned i = has ? sub : npair - 1;
-        for (unsigned m0 = wave * rows; m0 < nb; m0 += 4 * nwaves * rows) {
-            cf a[4], b[4];
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-                const unsigned m = m0 + (unsigned)u * nwaves * rows + (lane >> lg);
-                lev_load<WIDE>(o + (size_t)(m < nb ? m : nb - 1) * lout, i, lout, a[u], b[u]);
-            }
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-                const unsigned m = m0 + (unsigned)u * nwaves * rows + (lane >> lg);
-                const cf ga = gain_mul(a[u], g), gb = gain_mul(b[u], g);
-                if (has && m < nb) gain_store(o + (size_t)m * lout, nar + (size_t)m * lout, i, lout, WIDE, pair, ga, gb, scale);
-                if constexpr (LEVELS) {
-                    LevAcc acc = lev_zero();
-                    if (has) { lev_add(acc, ga); if (two) lev_add(acc, gb); }
-                    lev_join(acc, lg);
-                    if (m < nb && sub == 0) levels[(size_t)(mbase + (int)m) * (size_t)nchan + (size_t)c] = make_float2(acc.sum, acc.peak);
-                }
-            }
-        }
-    } else {
-        // a long row (more than 64 pairs) takes the whole wave: four steps of the row per trip, in index order
-        for (unsigned m = wave; m < nb; m += nwaves) {
-            auto *row = o + (size_t)m * lout;
-            auto *nrow = nar + (size_t)m * lout;
-            LevAcc acc = lev_zero();
-            for (unsigned i0 = sub; i0 < npair; i0 += 4 * lanes) {
-                cf a[4], b[4];
-#pragma unroll
-                for (int u = 0; u < 4; u++) {
-                    const unsigned i = i0 + (unsigned)u * lanes;
-                    lev_load<WIDE>(row, i < npair ? i : npair - 1, lout, a[u], b[u]);
-                }
-#pragma unroll
-                for (int u = 0; u < 4; u++) {
-                    const unsigned i = i0 + (unsigned)u * lanes;
-                    if (i < npair) {
-                        const cf ga = gain_mul(a[u], g), gb = gain_mul(b[u], g);
-                        gain_store(row, nrow, i, lout, WIDE, pair, ga, gb, scale);
-                        if constexpr (LEVELS) { lev_add(acc, ga); if (2 * i + 1 < lout) lev_add(acc, gb); }
-                    }
-                }
-            }
-            if constexpr (LEVELS) {
-                lev_join(acc, lg);
-                if (sub == 0) levels[(size_t)(mbase + (int)m) * (size_t)nchan + (size_t)c] = make_float2(acc.sum, acc.peak);
-            }
-        }
-    }
-}
-
-// (out: read and written for TO = float2, read only otherwise; nar, scale: the narrow forms' output and its factor; levels, nchan: the LEVELS forms')
-template <bool LEVELS, class TO = float2>
-__global__ __launch_bounds__(256) void k_chan_gain(float2 *out, const ChanDev *__restrict__ chans, const float *__restrict__ gain, TO *nar, float scale,
-                                                   float2 *__restrict__ levels, int c0, int nchan, int nb, int mbase, long long nb_call)
-{
-    constexpr bool NARROW = !std::is_same<TO, float2>::value;
-    const int c = c0 + (int)blockIdx.y;
-    const unsigned lout = (unsigned)chans[c].lout;
-    const long long run = nb_call * chans[c].out_off + (long long)mbase * lout;      // the channel's run of this launch group, in samples of either output
-    float2 *o = out + run;
-    const float g = gain[c];
-    const bool wide = !(lout & 1) && (reinterpret_cast<uintptr_t>(o) & 15) == 0;
-    if constexpr (NARROW) {
-        TO *n = nar + run;
-        const bool pair = wide && (reinterpret_cast<uintptr_t>(n) & (2 * sizeof(TO) - 1)) == 0;
-        if (wide) chan_gain_rows<true, LEVELS, TO>(o, n, pair, g, scale, levels, lout, (unsigned)nb, mbase, nchan, c);
-        else chan_gain_rows<false, LEVELS, TO>(o, n, false, g, scale, levels, lout, (unsigned)nb, mbase, nchan, c);
-    } else {
-        if (wide) chan_gain_rows<true, LEVELS, float2>(o, nullptr, false, g, scale, levels, lout, (unsigned)nb, mbase, nchan, c);
-        else chan_gain_rows<false, LEVELS, float2>(o, nullptr, false, g, scale, levels, lout, (unsigned)nb, mbase, nchan, c);
-    }
-}
-
-template <bool LEVELS, class TO>
-static void chan_gain_launch(dim3 grid, hipStream_t s, float2 *out, const ChanDev *chans, const float *gain, void *nar, float scale, float2 *levels, int c0,
-                             int nchan, int nb, int mbase, int nb_call)
-{
-    hipLaunchKernelGGL((k_chan_gain<LEVELS, TO>), grid, dim3(256), 0, s, out, chans, gain, static_cast<TO *>(nar), scale, levels, c0, nchan, nb, mbase,
-                       (long long)nb_call);
-}
-
-// fmt 0: in place on `out`; kIqSc16 / kIqSc8: `out` read, oq_narrow(product, scale) to `nar`.  levels: null = none
-hipError_t launch_chan_gain(float2 *out, const ChanDev *chans, const float *gain, float2 *levels, int fmt, float scale, void *nar, int nchan, int nb_chunk,
-                            int mbase, int nb_call, hipStream_t s)
-{
-    if (nchan <= 0 || nb_chunk <= 0) return hipSuccess;
-    if (fmt != kIqFloat && fmt != kIqSc16 && fmt != kIqSc8) return hipErrorInvalidValue;
-    if (fmt != kIqFloat && !nar) return hipErrorInvalidValue;
-    for (int c0 = 0; c0 < nchan; c0 += 32768) {
-        const int nc = nchan - c0 < 32768 ? nchan - c0 : 32768;
-        const int gx = std::max(1, std::min((nb_chunk + 3) / 4, (2048 + nc - 1) / nc));      // grid-stride over the rows: about eight workgroups per unit
-        const dim3 grid((unsigned)gx, (unsigned)nc);
-#define FDC_GAIN(LV) \
-        (fmt == kIqSc16 ? chan_gain_launch<LV, sc16>(grid, s, out, chans, gain, nar, scale, levels, c0, nchan, nb_chunk, mbase, nb_call) \
-         : fmt == kIqSc8 ? chan_gain_launch<LV, sc8>(grid, s, out, chans, gain, nar, scale, levels, c0, nchan, nb_chunk, mbase, nb_call) \
-                         : chan_gain_launch<LV, float2>(grid, s, out, chans, gain, nullptr, scale, levels, c0, nchan, nb_chunk, mbase, nb_call))
-        if (levels) FDC_GAIN(true); else FDC_GAIN(false);
-#undef FDC_GAIN
-    }
     return hipGetLastError();
 }
 

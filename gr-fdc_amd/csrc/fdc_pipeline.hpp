@@ -232,10 +232,10 @@ struct DeviceCall {
     // waterfall rows (path 5: the fused kernel's epilogue): the row sums of the stream's block b go to rows + (b - rows_first) * 1024
     float *rows = nullptr; int64_t rows_first = 0;
     // channel levels (fdc_pipeline_set_levels): where (power, peak) of the call's block 0, channel 0 go, [block][C]; null = none.  With them the kernels
-    // write float whatever the output format (the levels are of the float samples; the narrowing comes behind)
+    // write float whatever the output format (the order of the passes: fdc_enqueue.hip, float_passes)
     float2 *levels = nullptr;
     // channel gains (fdc_pipeline_set_gains): the handle's device table of C gains, null = off (device_call).  With them the kernels write float whatever
-    // the output format, as with levels: float, (rotation,) gain, (levels,) narrowing
+    // the output format, as with levels
     const float *gain = nullptr;
     int ncu = 0;                         // compute units the call's persistent kernels may use
     // results: no launch group had to be widened (each read the integer input in its own loads); the call's kernels narrowed in their own stores

@@ -1,0 +1,361 @@
+// gfx950 (MI355X, CDNA4) kernels of the frequency-domain channelizer — the passes that run BEHIND a plan's kernels, over the channel-major float
+// results of a launch group: the rotation of fine tuning (k_fine_rotate), the channel gains (k_chan_gain), the channel levels (k_chan_levels) and the
+// narrowing to complex integers (k_complex_to_iq).  Which of them a call runs, and in which order, is decided once per call: PostPass, fdc_enqueue.hip.
+//
+// One shape for the three per-channel kernels: grid y = channel, a row — the lout samples of one (block, channel) — on a power-of-two set of lanes of one
+// wave, 16 bytes per lane and access where the row allows it (lout even, the channel's run 16-byte aligned), 8 bytes otherwise, a grid-stride loop over
+// the blocks (channel_grids).  k_chan_levels and k_chan_gain are one loop, walk_rows, with an operation each; it keeps four loads in flight per lane.
+// k_fine_rotate keeps its own, one-deep loop: moving it onto walk_rows changes how many loads it keeps in flight, which is a speed change to be measured
+// on its own.
+#include "fdc_kernels.h"
+#include <algorithm>
+#include <type_traits>
+#include "fdc_iq.hpp"
+#include "fdc_fine.hpp"
+#include "fdc_devutil.hpp"
+
+namespace fdc {
+
+// grid x * 4 waves stride over the rows of a channel (about eight workgroups per unit); grid y = channel, in pieces of 32768 channels.
+// launch(grid, c0) enqueues one piece
+template <class F>
+static hipError_t channel_grids(int nchan, int nb_chunk, F launch)
+{
+    if (nchan <= 0 || nb_chunk <= 0) return hipSuccess;
+    for (int c0 = 0; c0 < nchan; c0 += 32768) {
+        const int nc = nchan - c0 < 32768 ? nchan - c0 : 32768;
+        const int gx = std::max(1, std::min((nb_chunk + 3) / 4, (2048 + nc - 1) / nc));
+        launch(dim3((unsigned)gx, (unsigned)nc), c0);
+    }
+    return hipGetLastError();
+}
+
+// a run-time bool as a compile-time one: f(std::true_type) or f(std::false_type)
+template <class F>
+static void with_bool(bool b, F f)
+{
+    if (b) f(std::true_type{}); else f(std::false_type{});
+}
+
+// complex float -> complex integer samples, times scale (fdc_iq.hpp oq_narrow): the narrowing back end of the plans without integer stores of their own
+template <class TO>
+__global__ __launch_bounds__(256) void k_complex_to_iq(const float2 *__restrict__ in, TO *__restrict__ out, size_t n, float scale)
+{
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) out[i] = oq_narrow(TO{}, from2(in[i]), scale);
+}
+
+hipError_t launch_complex_to_iq(int fmt, float scale, const float2 *in, void *out, size_t n, hipStream_t s)
+{
+    if (!n) return hipSuccess;
+    size_t g = (n + 255) / 256; if (g > 8192) g = 8192;
+    if (fmt == kIqSc16) hipLaunchKernelGGL(k_complex_to_iq<sc16>, dim3((unsigned)g), dim3(256), 0, s, in, static_cast<sc16 *>(out), n, scale);
+    else if (fmt == kIqSc8) hipLaunchKernelGGL(k_complex_to_iq<sc8>, dim3((unsigned)g), dim3(256), 0, s, in, static_cast<sc8 *>(out), n, scale);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+// Channel levels (fdc_pipeline_set_levels): power = sum of re^2 + im^2 and peak = max of |re|, |im| (fmax: a NaN component is passed over) of one row.
+// ONE ORDER PER SUM: the bits of a row's power depend on lout and the row's samples only.  The row goes to 2^lev_log2_lanes(lout) lanes of one wave, by
+// lout alone; lane `sub` takes the sample PAIRS sub, sub + lanes, ... in index order, of a pair the even sample first; a term is (re re + im im), each
+// product and each sum rounded on its own (no FMA contraction, as fine_mul and oq_bits); the lanes are joined by an xor butterfly from distance 1
+// upwards.  Both access widths of every kernel that sums (walk_rows, k_fine_rotate<true>) keep exactly this, so neither the row's alignment nor how the
+// stream was cut, nor which kernel summed it, shows in the result.  No atomics, no LDS.
+struct LevAcc { float sum, peak; };
+
+// the lanes of a row of `per` accesses: log2 of the next power of two, a wave at the most
+__device__ __forceinline__ unsigned row_log2_lanes(unsigned per)
+{
+    const unsigned lg = per <= 1 ? 0 : 32 - (unsigned)__clz((int)(per - 1));
+    return lg > 6 ? 6 : lg;
+}
+__device__ __forceinline__ unsigned lev_log2_lanes(unsigned lout) { return row_log2_lanes((lout + 1) >> 1); }
+
+// a lane starts from (0, NaN): a lane without samples adds +0 and its NaN is passed over by fmax; a row of NaN only keeps NaN (np.fmax.reduce)
+__device__ __forceinline__ LevAcc lev_zero() { return LevAcc{0.0f, __builtin_nanf("")}; }
+
+__device__ __forceinline__ void lev_add(LevAcc &a, cf y)
+{
+#pragma clang fp contract(off)
+    const float p = y.x * y.x, q = y.y * y.y;
+    const float t = p + q;
+    a.sum = a.sum + t;
+    a.peak = fmaxf(a.peak, fmaxf(fabsf(y.x), fabsf(y.y)));
+}
+
+// the row's 2^lg lanes joined: every lane of the row ends with the row's values (float addition commutes, so with the same bits)
+__device__ __forceinline__ void lev_join(LevAcc &a, unsigned lg)
+{
+    for (unsigned d = 1; d < (1u << lg); d <<= 1) {
+        a.sum = a.sum + __shfl_xor(a.sum, (int)d, 64);
+        a.peak = fmaxf(a.peak, __shfl_xor(a.peak, (int)d, 64));
+    }
+}
+
+// where the levels of channel c go: row m of the launch group is block mbase + m of the call
+struct LevDst {
+    float2 *levels; int mbase, nchan, c;
+    __device__ __forceinline__ void store(unsigned m, LevAcc acc) const
+    {
+        levels[(size_t)(mbase + (int)m) * (size_t)nchan + (size_t)c] = make_float2(acc.sum, acc.peak);
+    }
+};
+
+// the channel gain (fdc_pipeline_set_gains): each component times gain[c], rounded once, on its own
+__device__ __forceinline__ cf gain_mul(cf y, float g) { return mk(iq_mul(y.x, g), iq_mul(y.y, g)); }
+
+// Fine tuning behind the channel kernels of a launch group (fdc_fine.hpp): blocks [mbase, mbase + nb) of the call's channel-major float outputs, in
+// place; a channel's rows of the group are one contiguous run, a row has one base (the step table's rows start at even offsets, so a 16-byte row
+// reads 16-byte steps).  GAIN: the turned sample times gain[c] (gain_mul), and it is the gained sample that is stored and reduced.  LEVELS: the
+// samples are reduced while the lane holds them and one lane of the row stores the row's levels; the lanes then take sample pairs in both access
+// widths (the levels' one order).  Without LEVELS an 8-byte row spreads its samples over the lanes instead: contiguous 8-byte accesses.
+// gain, levels and nchan are null / 0 where the form does not use them.
+template <bool LEVELS, bool GAIN>
+__global__ __launch_bounds__(256) void k_fine_rotate(float2 *out, const ChanDev *__restrict__ chans, const FineChan *__restrict__ fine,
+                                                     const float2 *__restrict__ step, const float *__restrict__ gain, float2 *levels, int c0, int nchan,
+                                                     int nb, int mbase, long long nb_call, unsigned long long first_block)
+{
+    const int c = c0 + (int)blockIdx.y;
+    const unsigned lout = (unsigned)chans[c].lout;
+    const FineChan fc = fine[c];
+    float g = 1.0f;
+    if constexpr (GAIN) g = gain[c];
+    float2 *o = out + nb_call * chans[c].out_off + (long long)mbase * lout;
+    const float2 *st = step + fc.step_off;
+    const bool wide = !(lout & 1) && (reinterpret_cast<uintptr_t>(o) & 15) == 0;
+    const unsigned per = LEVELS || wide ? (lout + 1) >> 1 : lout;                  // accesses per row: pairs, or the samples of an 8-byte row without levels
+    const unsigned lg = row_log2_lanes(per);
+    const unsigned lanes = 1u << lg, lane = threadIdx.x & 63, sub = lane & (lanes - 1), rows = 64u >> lg;
+    const unsigned wave = blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = gridDim.x * 4;
+    const LevDst dst{levels, mbase, nchan, c};
+    // (whole waves leave together: the trip count depends on the wave alone, so every lane of a row is there for the butterfly)
+    for (unsigned m0 = wave * rows; m0 < (unsigned)nb; m0 += nwaves * rows) {
+        const unsigned m = m0 + (lane >> lg);
+        const bool live = m < (unsigned)nb;
+        LevAcc acc = lev_zero();
+        if (live) {
+            const cf base = fine_base(fc.inc, first_block + (unsigned long long)(mbase + (int)m), lout);
+            float2 *row = o + (size_t)m * lout;
+            if (wide) {
+                for (unsigned i = sub; i < per; i += lanes) {
+                    const float4 y = ld4(row + 2 * i), s = ld4(st + 2 * i);
+                    cf a = fine_rotate(mk(y.x, y.y), base, mk(s.x, s.y)), b = fine_rotate(mk(y.z, y.w), base, mk(s.z, s.w));
+                    if constexpr (GAIN) { a = gain_mul(a, g); b = gain_mul(b, g); }
+                    st4(row + 2 * i, a, b);
+                    if constexpr (LEVELS) { lev_add(acc, a); lev_add(acc, b); }
+                }
+            } else {
+                // LEVELS: i counts pairs, whose odd sample the last one of an odd row lacks; else i counts samples
+                constexpr unsigned k = LEVELS ? 2 : 1;
+                for (unsigned i = sub; i < per; i += lanes) {
+#pragma unroll
+                    for (unsigned j = k * i; j < k * i + k; j++) {
+                        if (j < lout) {
+                            cf a = fine_rotate(ld2(row + j), base, ld2(st + j));
+                            if constexpr (GAIN) a = gain_mul(a, g);
+                            st2(row + j, a);
+                            if constexpr (LEVELS) lev_add(acc, a);
+                        }
+                    }
+                }
+            }
+        }
+        if constexpr (LEVELS) {
+            lev_join(acc, lg);
+            if (live && sub == 0) dst.store(m, acc);
+        }
+    }
+}
+
+// levels: null = fine tuning alone; else the levels of the call's block 0 ([block][nchan] float2): the turned samples are reduced in the same pass
+// gain: null = none; else the nchan channel gains: the turned samples are multiplied in the same pass, in front of the reduction
+hipError_t launch_fine_rotate(float2 *out, const ChanDev *chans, const FineChan *fine, const float2 *step, int nchan, int nb_chunk, int mbase, int nb_call,
+                              int64_t first_block, hipStream_t s, float2 *levels, const float *gain)
+{
+    return channel_grids(nchan, nb_chunk, [&](dim3 grid, int c0) {
+        with_bool(levels != nullptr, [&](auto lv) {
+            with_bool(gain != nullptr, [&](auto gn) {
+                hipLaunchKernelGGL((k_fine_rotate<decltype(lv)::value, decltype(gn)::value>), grid, dim3(256), 0, s, out, chans, fine, step, gain, levels, c0,
+                                   nchan, nb_chunk, mbase, (long long)nb_call, (unsigned long long)first_block);
+            });
+        });
+    });
+}
+
+// The row walker of k_chan_levels and k_chan_gain: the rows [0, nb) of one channel's run `o`, each row on 2^lev_log2_lanes(lout) lanes, the lanes taking
+// sample pairs (the levels' one order, above); WIDE: one 16-byte load per pair, else two 8-byte loads.  A trip issues all its loads — four pairs per
+// lane: four rows where a row is one pair per lane, four steps along a longer row — before the first is used.
+// (no branch around a load: a lane without a pair of its own loads one that exists — the row's last pair, the group's last row — and leaves it out, so
+// that the four loads of a trip are in flight together and not each behind its own wait)
+// The walker owns which lane holds which pair of which row; what happens to a held pair is the operation's:
+//   op.transform(a, b)         the pair's two samples, changed in place (any lane, any pair: no side effect)
+//   op.store(m, i, a, b)       pair i of row m, the lane's own: b is a sample of the row where 2 i + 1 < lout
+//   Op::kLevels, op.dst        whether the transformed samples are reduced, and where the row's levels go
+template <bool WIDE>
+__device__ __forceinline__ void row_load(const float2 *row, unsigned i, unsigned lout, cf &a, cf &b)
+{
+    if (WIDE) {
+        const float4 y = ld4(row + 2 * i);
+        a = mk(y.x, y.y); b = mk(y.z, y.w);
+    } else {
+        a = ld2(row + 2 * i);
+        b = ld2(row + (2 * i + 1 < lout ? 2 * i + 1 : lout - 1));
+    }
+}
+
+template <bool WIDE, class Op>
+__device__ __forceinline__ void walk_rows(const float2 *o, unsigned lout, unsigned nb, const Op &op)
+{
+    const unsigned npair = (lout + 1) >> 1, lg = lev_log2_lanes(lout);
+    const unsigned lanes = 1u << lg, lane = threadIdx.x & 63, sub = lane & (lanes - 1), rows = 64u >> lg;
+    const unsigned wave = blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = gridDim.x * 4;
+    if (npair <= lanes) {
+        // a row is at most one pair per lane: four rows per trip, a grid stride apart
+        const bool has = sub < npair, two = 2 * sub + 1 < lout;
+        const unsigned i = has ? sub : npair - 1;
+        for (unsigned m0 = wave * rows; m0 < nb; m0 += 4 * nwaves * rows) {
+            cf a[4], b[4];
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                const unsigned m = m0 + (unsigned)u * nwaves * rows + (lane >> lg);
+                row_load<WIDE>(o + (size_t)(m < nb ? m : nb - 1) * lout, i, lout, a[u], b[u]);
+            }
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                const unsigned m = m0 + (unsigned)u * nwaves * rows + (lane >> lg);
+                op.transform(a[u], b[u]);
+                if (has && m < nb) op.store(m, i, a[u], b[u]);
+                if constexpr (Op::kLevels) {
+                    LevAcc acc = lev_zero();
+                    if (has) { lev_add(acc, a[u]); if (two) lev_add(acc, b[u]); }
+                    lev_join(acc, lg);
+                    if (m < nb && sub == 0) op.dst.store(m, acc);
+                }
+            }
+        }
+    } else {
+        // a long row (more than 64 pairs) takes the whole wave: four steps of the row per trip, in index order
+        for (unsigned m = wave; m < nb; m += nwaves) {
+            const float2 *row = o + (size_t)m * lout;
+            LevAcc acc = lev_zero();
+            for (unsigned i0 = sub; i0 < npair; i0 += 4 * lanes) {
+                cf a[4], b[4];
+#pragma unroll
+                for (int u = 0; u < 4; u++) {
+                    const unsigned i = i0 + (unsigned)u * lanes;
+                    row_load<WIDE>(row, i < npair ? i : npair - 1, lout, a[u], b[u]);
+                }
+#pragma unroll
+                for (int u = 0; u < 4; u++) {
+                    const unsigned i = i0 + (unsigned)u * lanes;
+                    if (i < npair) {
+                        op.transform(a[u], b[u]);
+                        op.store(m, i, a[u], b[u]);
+                        if constexpr (Op::kLevels) { lev_add(acc, a[u]); if (2 * i + 1 < lout) lev_add(acc, b[u]); }
+                    }
+                }
+            }
+            if constexpr (Op::kLevels) {
+                lev_join(acc, lg);
+                if (sub == 0) op.dst.store(m, acc);
+            }
+        }
+    }
+}
+
+// Channel levels of a launch group: blocks [mbase, mbase + nb) of the call's channel-major float outputs, read once; one float2 (power, peak) per
+// (block, channel) goes to levels[(mbase + m) * nchan + c] and nothing else is written: the walker with "accumulate only"
+struct LevelsOp {
+    static constexpr bool kLevels = true;
+    LevDst dst;
+    __device__ __forceinline__ void transform(cf &, cf &) const {}
+    __device__ __forceinline__ void store(unsigned, unsigned, cf, cf) const {}
+};
+
+__global__ __launch_bounds__(256) void k_chan_levels(const float2 *__restrict__ out, const ChanDev *__restrict__ chans, float2 *__restrict__ levels, int c0,
+                                                     int nchan, int nb, int mbase, long long nb_call)
+{
+    const int c = c0 + (int)blockIdx.y;
+    const unsigned lout = (unsigned)chans[c].lout;
+    const float2 *o = out + nb_call * chans[c].out_off + (long long)mbase * lout;
+    const LevelsOp op{{levels, mbase, nchan, c}};
+    if (!(lout & 1) && (reinterpret_cast<uintptr_t>(o) & 15) == 0) walk_rows<true>(o, lout, (unsigned)nb, op);
+    else walk_rows<false>(o, lout, (unsigned)nb, op);
+}
+
+hipError_t launch_chan_levels(const float2 *out, const ChanDev *chans, float2 *levels, int nchan, int nb_chunk, int mbase, int nb_call, hipStream_t s)
+{
+    return channel_grids(nchan, nb_chunk, [&](dim3 grid, int c0) {
+        hipLaunchKernelGGL(k_chan_levels, grid, dim3(256), 0, s, out, chans, levels, c0, nchan, nb_chunk, mbase, (long long)nb_call);
+    });
+}
+
+// Channel gains of a launch group where no rotation pass runs (fdc_pipeline_set_gains): blocks [mbase, mbase + nb) of the call's channel-major float
+// results times gain[c] (gain_mul): the walker with "gain, store, accumulate if LEVELS".  TO = float2: the product goes back where it was read (in
+// place).  TO = sc16 / sc8: the float staging is read only and oq_narrow(TO, product, scale) goes to the same sample offset of the call's narrow output
+// `nar` — two samples per store where the row is read 16 bytes at a time and the narrow run is aligned for it (pair), one otherwise.  LEVELS: the gained
+// samples are reduced in the levels' one order, so k_chan_levels is not launched behind this kernel.
+template <bool WIDE, bool LEVELS, class TO>
+struct GainOp {
+    static constexpr bool kLevels = LEVELS;
+    float2 *o; TO *nar; unsigned lout; bool pair; float g, scale;      // o, nar: the channel's run in the float results and in the narrow output
+    LevDst dst;
+    __device__ __forceinline__ void transform(cf &a, cf &b) const { a = gain_mul(a, g); b = gain_mul(b, g); }
+    __device__ __forceinline__ void store(unsigned m, unsigned i, cf a, cf b) const
+    {
+        if constexpr (std::is_same<TO, float2>::value) {
+            float2 *row = o + (size_t)m * lout;
+            if (WIDE) st4(row + 2 * i, a, b);
+            else { st2(row + 2 * i, a); if (2 * i + 1 < lout) st2(row + 2 * i + 1, b); }
+        } else {
+            TO *nrow = nar + (size_t)m * lout;
+            if (pair) {
+                if constexpr (std::is_same<TO, sc16>::value) *reinterpret_cast<uint2 *>(nrow + 2 * i) = make_uint2(oq_bits(TO{}, a, scale), oq_bits(TO{}, b, scale));
+                else *reinterpret_cast<unsigned *>(nrow + 2 * i) = oq_bits(TO{}, a, scale) | (oq_bits(TO{}, b, scale) << 16);
+            } else {
+                nrow[2 * i] = oq_narrow(TO{}, a, scale);
+                if (2 * i + 1 < lout) nrow[2 * i + 1] = oq_narrow(TO{}, b, scale);
+            }
+        }
+    }
+};
+
+// (out: read and written for TO = float2, read only otherwise; nar, scale: the narrow forms' output and its factor; levels, nchan: the LEVELS forms')
+template <bool LEVELS, class TO = float2>
+__global__ __launch_bounds__(256) void k_chan_gain(float2 *out, const ChanDev *__restrict__ chans, const float *__restrict__ gain, TO *nar, float scale,
+                                                   float2 *__restrict__ levels, int c0, int nchan, int nb, int mbase, long long nb_call)
+{
+    const int c = c0 + (int)blockIdx.y;
+    const unsigned lout = (unsigned)chans[c].lout;
+    const long long run = nb_call * chans[c].out_off + (long long)mbase * lout;      // the channel's run of this launch group, in samples of either output
+    float2 *o = out + run;
+    TO *n = std::is_same<TO, float2>::value ? nullptr : nar + run;
+    const bool wide = !(lout & 1) && (reinterpret_cast<uintptr_t>(o) & 15) == 0;
+    const bool pair = wide && (reinterpret_cast<uintptr_t>(n) & (2 * sizeof(TO) - 1)) == 0;
+    const LevDst dst{levels, mbase, nchan, c};
+    if (wide) walk_rows<true>(o, lout, (unsigned)nb, GainOp<true, LEVELS, TO>{o, n, lout, pair, gain[c], scale, dst});
+    else walk_rows<false>(o, lout, (unsigned)nb, GainOp<false, LEVELS, TO>{o, n, lout, false, gain[c], scale, dst});
+}
+
+// fmt 0: in place on `out`; kIqSc16 / kIqSc8: `out` read, oq_narrow(product, scale) to `nar`.  levels: null = none
+hipError_t launch_chan_gain(float2 *out, const ChanDev *chans, const float *gain, float2 *levels, int fmt, float scale, void *nar, int nchan, int nb_chunk,
+                            int mbase, int nb_call, hipStream_t s)
+{
+    if (nchan <= 0 || nb_chunk <= 0) return hipSuccess;
+    if (fmt != kIqFloat && fmt != kIqSc16 && fmt != kIqSc8) return hipErrorInvalidValue;
+    if (fmt != kIqFloat && !nar) return hipErrorInvalidValue;
+    return channel_grids(nchan, nb_chunk, [&](dim3 grid, int c0) {
+        with_bool(levels != nullptr, [&](auto lv) {
+            auto to = [&](auto *n) {
+                hipLaunchKernelGGL((k_chan_gain<decltype(lv)::value, std::remove_pointer_t<decltype(n)>>), grid, dim3(256), 0, s, out, chans, gain, n, scale, levels,
+                                   c0, nchan, nb_chunk, mbase, (long long)nb_call);
+            };
+            switch (fmt) {
+            case kIqSc16: to(static_cast<sc16 *>(nar)); break;
+            case kIqSc8: to(static_cast<sc8 *>(nar)); break;
+            default: to(static_cast<float2 *>(nullptr));
+            }
+        });
+    });
+}
+
+}  // namespace fdc

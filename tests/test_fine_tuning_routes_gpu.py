@@ -1,7 +1,7 @@
 """GPU tests (-m gpu) of fine tuning on every route, channel width, overlap and call form (tests/test_fine_tuning_gpu.py covers the setting itself).
 
 Two pieces of device code turn the samples: the FINE forms of the one-launch kernel on path 5 (k_f4096_fine, csrc/fdc_fused4096_body.inc: every row class has
-its own fine_row call and store indices), and k_fine_rotate behind the channel kernels of every other plan (csrc/fdc_kernels.hip, launched per launch group by
+its own fine_row call and store indices), and k_fine_rotate behind the channel kernels of every other plan (csrc/fdc_postpass.hip, launched per launch group by
 process_device_impl).  Each case here is an index, an offset or a dispatch decision of one of them.
 
 The model and its bound are test_fine_tuning_gpu.py's (holds(), phasors(); DESIGN.md "Fine tuning"): the float64 phasor of the 64-bit wrapping phase applied

@@ -1,7 +1,7 @@
 """GPU tests (-m gpu) of the channel gains on every plan, inside the device code that applies them, and together with the other settings
 (tests/test_gains_gpu.py covers the setting itself and the call forms; its helpers are used here).
 
-Three routes apply a gain (csrc/fdc_kernels.hip; chosen per call and launched per launch group by process_device_impl): k_fine_rotate's GAIN forms where
+Three routes apply a gain (csrc/fdc_postpass.hip; chosen per call and launched per launch group by process_device_impl): k_fine_rotate's GAIN forms where
 the rotation's pass runs ("gains: with the rotation"), k_chan_gain in place on the float results ("gains: pass"), and k_chan_gain's sc16 / sc8 forms,
 which read the float staging and store the narrow samples ("gains: with the narrowing").  Each case here is an index, an offset or a dispatch decision of
 one of them.  Every comparison is in bytes against gained() / narrowed(gained()) of the same handle's gains-off float outputs; levels against the model

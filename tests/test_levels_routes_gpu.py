@@ -2,7 +2,7 @@
 (tests/test_levels_gpu.py covers the setting itself and the call forms; its helpers and the model of tests/test_levels_cpu.py are used here).
 
 Two pieces of device code sum levels: k_chan_levels, one pass over a launch group's float results behind the channel kernels of every plan (path 5
-included), and k_fine_rotate<true>, the rotation's pass when fine tuning is on too, off path 5 (csrc/fdc_kernels.hip; launched per launch group by
+included), and k_fine_rotate<true>, the rotation's pass when fine tuning is on too, off path 5 (csrc/fdc_postpass.hip; launched per launch group by
 process_device_impl).  Each case here is an index, an offset or a dispatch decision of one of them.  Every comparison is against the model applied to the
 float32 outputs of the same call: the bound for power, bit-equality for peak; the outputs are byte-equal to the same handle's with levels off."""
 import functools

@@ -1,12 +1,16 @@
 #!/usr/bin/env python3
-"""Do the one-block-per-CU kernels of two commits compile to the same code?
+"""Do the kernels of two commits compile to the same code?
 
-    tools/compare_block_isa.py [BASE [NEW]]      BASE: a commit (default HEAD); NEW: a commit, or the working tree when left out
+    tools/compare_block_isa.py [--files A,B,...] [--new-files C,D,...] [BASE [NEW]]
+        BASE: a commit (default HEAD); NEW: a commit, or the working tree when left out
+        --files: the .hip files of gr-fdc_amd/csrc to compile, without the suffix (default: the four one-block-per-CU kernel files);
+        --new-files: those of the NEW side where they differ — a kernel that moved between files is matched by its symbol
 
-Compiles gr-fdc_amd/csrc/fdc_block{256,512,1024,narrow}.hip of both sides for the device only (the Makefile's flags plus
---cuda-device-only -S) and compares every kernel by symbol: the instructions of its body, and its resource usage (the .amdhsa_* block, the
-.set lines of its register counts, its entry in the amdhsa.kernels metadata).  The order of the kernels in the file and the numbers in local
-labels follow the order of instantiation, which is not code: both are normalised away.  Needs hipcc, no GPU.  Exit status 1 on a difference."""
+Compiles the files of both sides for the device only (the Makefile's flags plus --cuda-device-only -S) and compares every kernel by symbol:
+the instructions of its body, and its resource usage (the .amdhsa_* block, the .set lines of its register counts, its entry in the
+amdhsa.kernels metadata).  The order of the kernels in a file and the numbers in local labels follow the order of instantiation, which is
+not code: both are normalised away.  Needs hipcc, no GPU.  Exit status 1 on a difference."""
+import argparse
 import os
 import re
 import subprocess
@@ -21,7 +25,7 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=" + os.environ.get("ARCH"
          "--cuda-device-only", "-S"]
 
 
-def compile_side(rev, tmp):
+def compile_side(rev, files, tmp):
     """{file: assembly text} of one side; rev None = the working tree"""
     src = os.path.join(ROOT, CSRC)
     if rev is not None:
@@ -34,7 +38,7 @@ def compile_side(rev, tmp):
         src = os.path.join(top, CSRC)
     out = {}
     procs = []
-    for f in FILES:
+    for f in files:
         s = os.path.join(tmp, "%s_%s.s" % (f, (rev or "worktree").replace("/", "_")))
         procs.append((f, s, subprocess.Popen([HIPCC] + FLAGS + [f + ".hip", "-o", s], cwd=src, stderr=subprocess.PIPE, text=True)))
     for f, s, p in procs:
@@ -90,28 +94,42 @@ def kernels(text):
     return {k: (body[k], res.get(k)) for k in body}
 
 
+def pooled(side):
+    """{symbol: (instructions, resource usage, file)} over all files of one side"""
+    return {k: v + (f,) for f, text in side.items() for k, v in kernels(text).items()}
+
+
 def main():
-    base = sys.argv[1] if len(sys.argv) > 1 else "HEAD"
-    new = sys.argv[2] if len(sys.argv) > 2 else None
-    bad = False
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--files", default=",".join(FILES))
+    ap.add_argument("--new-files")
+    ap.add_argument("base", nargs="?", default="HEAD")
+    ap.add_argument("new", nargs="?")
+    a = ap.parse_args()
+    fa = a.files.split(",")
+    fb = (a.new_files or a.files).split(",")
     with tempfile.TemporaryDirectory() as tmp:
-        a, b = compile_side(base, tmp), compile_side(new, tmp)
-    print("%s %s --cuda-device-only -S; %s vs %s" % (os.path.basename(HIPCC), " ".join(FLAGS[:-2]), base, new or "the working tree"))
-    for f in FILES:
-        ka, kb = kernels(a[f]), kernels(b[f])
-        gone, added = sorted(set(ka) - set(kb)), sorted(set(kb) - set(ka))
-        both = sorted(set(ka) & set(kb))
+        ka, kb = pooled(compile_side(a.base, fa, tmp)), pooled(compile_side(a.new, fb, tmp))
+    print("%s %s --cuda-device-only -S; %s (%s) vs %s (%s)" % (os.path.basename(HIPCC), " ".join(FLAGS[:-2]), a.base, " ".join(fa),
+                                                             a.new or "the working tree", " ".join(fb)))
+    bad = False
+    for f in fa:
+        mine = sorted(k for k in ka if ka[k][2] == f)
+        both = [k for k in mine if k in kb]
         nres = sum(ka[k][1] == kb[k][1] for k in both)
         nins = sum(ka[k][0] == kb[k][0] for k in both)
-        print("%s: %d instantiations; %d with identical resource usage, %d with identical instructions" % (f, len(ka), nres, nins))
-        for k in gone:
-            print("  no longer instantiated: " + k)
-        for k in added:
-            print("  new instantiation: " + k)
-        for k in both:
-            if ka[k] != kb[k]:
+        print("%s: %d instantiations; %d with identical resource usage, %d with identical instructions" % (f, len(mine), nres, nins))
+        for k in mine:
+            if k not in kb:
+                print("  no longer instantiated: " + k)
+            elif ka[k][:2] != kb[k][:2]:
                 print("  differs: " + k)
-        bad = bad or gone or added or nres != len(ka) or nins != len(ka)
+            elif kb[k][2] != f:
+                print("  identical, now in %s: %s" % (kb[k][2], k))
+        bad = bad or nres != len(mine) or nins != len(mine)
+    for k in sorted(set(kb) - set(ka)):
+        print("  new instantiation (%s): %s" % (kb[k][2], k))
+        bad = True
     return 1 if bad else 0
 
 
