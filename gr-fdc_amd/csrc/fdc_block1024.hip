@@ -309,11 +309,11 @@ hipError_t init_block1024_kernels()
 hipError_t launch_poly_block1024(const BlockLaunch &b)
 {
     if (b.nb_chunk <= 0) return hipSuccess;
-    if (!poly_block1024_supports(b.N, b.R) || (b.R == 4 && !b.scratch) || (b.r != 0 && !b.half())) return hipErrorInvalidValue;
+    if (!poly_block1024_supports(b.N, b.R) || (b.R == 4 && !b.scratch) || (b.r != 0 && !b.half()) || b.ifmt || b.ofmt) return hipErrorInvalidValue;
     hipError_t e = hipErrorInvalidValue;                        // stays if no instantiation matches
     for_block_variants(b.hints & 1, b.R == 4, b.N / 8192, [&](auto NT, auto R4, auto P) {
         hipExtLaunchKernelGGL((k_blk1024<NT() != 0, R4() != 0, P()>), dim3((unsigned)b.grid()), dim3(512), B1kGeom<P()>::kLds, b.s, b.ev_start, b.ev_stop, 0u,
-                              b.in, b.in_stride, b.out, b.tw256, b.twl, b.twq, b.cbt, b.shn, b.slot_off, (long long)b.mbase * (R4() ? 768 : 512),
+                              b.fin(), b.in_stride, b.fout(), b.tw256, b.twl, b.twq, b.cbt, b.shn, b.slot_off, (long long)b.mbase * (R4() ? 768 : 512),
                               (long long)b.nb_call, b.out_bytes, b.nb_chunk, b.hints, b.half() ? 1 : 0, R4() ? b.scratch : (float2 *)nullptr);
         e = hipGetLastError();
     });

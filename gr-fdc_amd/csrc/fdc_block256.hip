@@ -571,128 +571,59 @@ __global__ FDC_PLAIN_DS __launch_bounds__(512, (P == 2 && !OFF && !R4 && !FWD) ?
     }
 }
 
-// the LDS size of one form, and of its spread twin if it has one
-template <int P, bool A, bool O, bool F, bool R4, bool H, class TI, class TO>
-static hipError_t set_block_form(int bytes)
+// Which forms of k_blk256 exist, stated ONCE.  Integer output: streamed (nt) stores only — a handle with FDC_PIPE_PLAIN_STORES narrows behind the float form
+// instead (half the instantiations) — and at P = 8 no R = 4 form on float input: the narrowing costs the 256-register kernel 2-3 spilled registers, so those
+// plans narrow behind the float form too (fdc_enqueue.hip oq_fused).  The half-slot form is a variant of the on-grid channelizer; the forward transform is
+// float2 to float2, on the grid, nothing else; a spread twin where kBlkSpread says so.
+template <int P, bool NT, bool OFF, bool FWD, bool R4, bool HALF, class TI, class TO, bool SPREAD>
+constexpr bool blk256_form()
 {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_blk256<P, A, O, F, R4, H, TI, TO, false>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if constexpr (kBlkSpread<P, O, F, R4, TO>)
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_blk256<P, A, O, F, R4, H, TI, TO, true>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    return e;
+    constexpr bool kIq = !std::is_same<TI, float2>::value, kOq = !std::is_same<TO, float2>::value;
+    constexpr bool kOqR4Narrowed = P == 8 && R4 && !kIq && kOq;
+    return (!kOq || NT) && !kOqR4Narrowed && !(HALF && OFF) && (!FWD || !(kIq || kOq || OFF || R4 || HALF)) && (!SPREAD || kBlkSpread<P, OFF, FWD, R4, TO>);
 }
 
-// the channelizer forms of one input type (TI != float2: the integer-input instantiations, fdc_pipeline_work_iq)
-template <class TI>
-static hipError_t init_block_kernels_in()
+// f(kernel, LDS bytes, TI{}, TO{}) for the forms that match (fdc_forms.hpp; kEvery: every value of that argument).  spread = 1: the spread twin of a form
+// that has one, the form itself otherwise; 0: the form with all sixteen row loads at the top of a pass
+template <class F>
+static void for_blk256_forms(int p, int nt, int off, int fwd, int r4, int half, int ifmt, int ofmt, int spread, F &&f)
 {
-    hipError_t e;
-#define FDC_SETB(P, A, B, R4) \
-    e = set_block_form<P, A, B, false, R4, false, TI, float2>(B ? BlkGeom<P>::kLdsOff : BlkGeom<P>::kLds); \
-    if (e != hipSuccess) return e;
-#define FDC_SETH(P, A, R4) \
-    e = set_block_form<P, A, false, false, R4, true, TI, float2>(BlkGeom<P>::kLds); \
-    if (e != hipSuccess) return e;
-#define FDC_SETP(P) \
-    FDC_SETB(P, true, false, false) FDC_SETB(P, false, false, false) FDC_SETB(P, true, true, false) FDC_SETB(P, false, true, false) \
-    FDC_SETB(P, true, false, true) FDC_SETB(P, false, false, true) FDC_SETB(P, true, true, true) FDC_SETB(P, false, true, true) \
-    FDC_SETH(P, true, false) FDC_SETH(P, false, false) FDC_SETH(P, true, true) FDC_SETH(P, false, true)
-    FDC_SETP(2) FDC_SETP(4) FDC_SETP(8)
-#undef FDC_SETP
-#undef FDC_SETH
-#undef FDC_SETB
-    return hipSuccess;
-}
-
-// P = 8, R = 4 (N = 65536, three quarters of every inverse transform kept) on float input with integer output: the narrowing costs the 256-register
-// kernel 2-3 spilled registers, so these plans narrow behind the float form instead (fdc_api.hip oq_fused)
-template <class TI, class TO> struct kOqR4Narrowed {
-    static constexpr bool value = std::is_same<TI, float2>::value && !std::is_same<TO, float2>::value;
-};
-
-// the channelizer forms with integer output (TO = sc16 / sc8, fdc_pipeline_set_output_format) for one input type: streamed (nt) stores only — a
-// handle with FDC_PIPE_PLAIN_STORES narrows behind the float form instead (half the instantiations)
-template <class TI, class TO>
-static hipError_t init_block_kernels_oq()
-{
-    hipError_t e;
-#define FDC_SETB(P, B, R4) \
-    e = set_block_form<P, true, B, false, R4, false, TI, TO>(B ? BlkGeom<P>::kLdsOff : BlkGeom<P>::kLds); \
-    if (e != hipSuccess) return e;
-#define FDC_SETH(P, R4) \
-    e = set_block_form<P, true, false, false, R4, true, TI, TO>(BlkGeom<P>::kLds); \
-    if (e != hipSuccess) return e;
-#define FDC_SETP(P) \
-    FDC_SETB(P, false, false) FDC_SETB(P, true, false) FDC_SETB(P, false, true) FDC_SETB(P, true, true) FDC_SETH(P, false) FDC_SETH(P, true)
-    FDC_SETP(2) FDC_SETP(4)
-    FDC_SETB(8, false, false) FDC_SETB(8, true, false) FDC_SETH(8, false)
-    if constexpr (!kOqR4Narrowed<TI, TO>::value) { FDC_SETB(8, false, true) FDC_SETB(8, true, true) FDC_SETH(8, true) }
-#undef FDC_SETP
-#undef FDC_SETH
-#undef FDC_SETB
-    return hipSuccess;
-}
-
-// the float forms: the channelizer, the forward transform, the half-slot channelizer
-static hipError_t init_block_kernels_float()
-{
-    hipError_t e;
-#define FDC_SETB(P, A, B, F, R4) \
-    e = set_block_form<P, A, B, F, R4, false, float2, float2>(B ? BlkGeom<P>::kLdsOff : BlkGeom<P>::kLds); \
-    if (e != hipSuccess) return e;
-#define FDC_SETP(P) \
-    FDC_SETB(P, true, false, false, false) FDC_SETB(P, false, false, false, false) FDC_SETB(P, true, true, false, false) \
-    FDC_SETB(P, false, true, false, false) FDC_SETB(P, true, false, false, true) FDC_SETB(P, false, false, false, true) \
-    FDC_SETB(P, true, true, false, true) FDC_SETB(P, false, true, false, true)
-    FDC_SETP(2) FDC_SETP(4) FDC_SETP(8)
-    FDC_SETB(8, true, false, true, false) FDC_SETB(8, false, false, true, false) FDC_SETB(4, true, false, true, false) FDC_SETB(4, false, false, true, false)
-    FDC_SETB(2, true, false, true, false) FDC_SETB(2, false, false, true, false)
-#undef FDC_SETP
-#undef FDC_SETB
-#define FDC_SETH(P, A, R4) \
-    e = set_block_form<P, A, false, false, R4, true, float2, float2>(BlkGeom<P>::kLds); \
-    if (e != hipSuccess) return e;
-#define FDC_SETHP(P) FDC_SETH(P, true, false) FDC_SETH(P, false, false) FDC_SETH(P, true, true) FDC_SETH(P, false, true)
-    FDC_SETHP(2) FDC_SETHP(4) FDC_SETHP(8)
-#undef FDC_SETHP
-#undef FDC_SETH
-    return hipSuccess;
+    auto form = [&](auto P, auto NT, auto OFF, auto FWD, auto R4, auto HALF, auto ti, auto to) {
+        using TI = decltype(ti);
+        using TO = decltype(to);
+        constexpr bool kNt = NT() != 0, kOff = OFF() != 0, kFwd = FWD() != 0, kR4 = R4() != 0, kHalf = HALF() != 0;
+        constexpr int kLds = kOff ? BlkGeom<P()>::kLdsOff : BlkGeom<P()>::kLds;
+        if constexpr (blk256_form<P(), kNt, kOff, kFwd, kR4, kHalf, TI, TO, false>()) {
+            constexpr bool kTwin = blk256_form<P(), kNt, kOff, kFwd, kR4, kHalf, TI, TO, true>();
+            if (spread != 1 || !kTwin) f(k_blk256<P(), kNt, kOff, kFwd, kR4, kHalf, TI, TO, false>, kLds, ti, to);
+            if constexpr (kTwin)
+                if (spread != 0) f(k_blk256<P(), kNt, kOff, kFwd, kR4, kHalf, TI, TO, true>, kLds, ti, to);
+        }
+    };
+    for_values<2, 4, 8>(p, [&](auto P) { for_values<1, 0>(nt, [&](auto NT) { for_values<0, 1>(off, [&](auto OFF) { for_values<0, 1>(fwd, [&](auto FWD) {
+        for_values<0, 1>(r4, [&](auto R4) { for_values<0, 1>(half, [&](auto HALF) {
+            for_samples(ifmt, [&](auto ti) { for_samples(ofmt, [&](auto to) { form(P, NT, OFF, FWD, R4, HALF, ti, to); }); });
+        }); });
+    }); }); }); });
 }
 
 hipError_t init_block_kernels()
 {
-    hipError_t e = init_block_kernels_in<sc16>();
-    if (e != hipSuccess) return e;
-    if ((e = init_block_kernels_in<sc8>()) != hipSuccess) return e;
-    if ((e = init_block_kernels_oq<float2, sc16>()) != hipSuccess) return e;
-    if ((e = init_block_kernels_oq<float2, sc8>()) != hipSuccess) return e;
-    if ((e = init_block_kernels_oq<sc16, sc16>()) != hipSuccess) return e;
-    if ((e = init_block_kernels_oq<sc16, sc8>()) != hipSuccess) return e;
-    if ((e = init_block_kernels_oq<sc8, sc16>()) != hipSuccess) return e;
-    if ((e = init_block_kernels_oq<sc8, sc8>()) != hipSuccess) return e;
-    return init_block_kernels_float();
+    hipError_t e = hipSuccess;
+    for_blk256_forms(kEvery, kEvery, kEvery, kEvery, kEvery, kEvery, kEvery, kEvery, kEvery, [&](auto k, int lds, auto, auto) {
+        if (e == hipSuccess) e = set_block_lds(reinterpret_cast<const void *>(k), lds);
+    });
+    return e;
 }
 
 bool poly_block_supports(int N) { return N == 16384 || N == 32768 || N == 65536; }
 
-template <class TI, class TO = float2>
-static hipError_t poly_block_in(const BlockLaunch &b, const TI *in, TO *out, float iq_scale, float oq_scale = 1.0f)
+hipError_t launch_poly_block(const BlockLaunch &b)
 {
     if (b.nb_chunk <= 0) return hipSuccess;
-    if (b.L != 256 || b.r < 0 || b.r >= 256) return hipErrorInvalidValue;
-    constexpr bool kIq = !std::is_same<TI, float2>::value, kOq = !std::is_same<TO, float2>::value;
-    const bool nt = (b.hints & 1) != 0, r4 = b.R == 4;
-    // integer output: the streamed-store forms only (init_block_kernels_oq); the macros below name NT = true for both hints then
-    if (kOq && !nt) return hipErrorInvalidValue;
-    // the kernel's last argument: float2 input and output, no group powers (null); otherwise the scale(s) of the integer side(s) (IqTail)
-    auto iq_tail = [](float si, float so) -> typename IqTail<TI, TO>::type {
-        if constexpr (!kIq && !kOq) return (void)si, (void)so, (float *)nullptr;
-        else if constexpr (kIq && kOq) return make_float2(si, so);
-        else if constexpr (kIq) return (void)so, si;
-        else return (void)si, so;
-    };
-    const bool halfslot = b.half();                         // half a slot: the on-grid kernel with its tables moved (HALF), R = 2 and 4
-    if (!poly_block_supports(b.N) || (b.R != 2 && !r4) || (r4 && !b.scratch)) return hipErrorInvalidValue;
+    const bool r4 = b.R == 4, halfslot = b.half();         // half a slot: the on-grid kernel with its tables moved (HALF), R = 2 and 4
+    if (b.L != 256 || b.r < 0 || b.r >= 256 || !poly_block_supports(b.N) || (b.R != 2 && !r4) || (r4 && !b.scratch)) return hipErrorInvalidValue;
+    if (b.ifmt == kEvery || b.ofmt == kEvery) return hipErrorInvalidValue;      // a launch names one form
     // one 512-thread workgroup per CU (LDS: up to 159.5 KiB each).  N = 16384 on the grid at R = 2: 126 registers and 79.75 KiB of LDS per
     // workgroup: two workgroups per CU, one's stage 2 beside the other's stage 1
     const int grid = b.grid(b.N == 16384 && b.R == 2 && (!b.r || halfslot) ? 2 : 1);
@@ -700,65 +631,18 @@ static hipError_t poly_block_in(const BlockLaunch &b, const TI *in, TO *out, flo
     // ev_start / ev_stop (timing): the dispatch packet's own begin / end time stamps (hipExtLaunchKernel) — no barrier packet
     // in front of or behind the kernel, unlike hipEventRecord (measured 7-17 us per bracketed launch)
     // R = 4: three quarters of every inverse transform kept: 192 rows per block, 64 of them via the scratch
-    // FDC_L(P, NT, OFF, R4, HALF, roff): one instantiation with the launch's arguments, in its spread form if it has one and SP says so
-#define FDC_L(P, A, O, R4, H, roff) \
-    hipExtLaunchKernelGGL((k_blk256<P, A || kOq, O, false, R4, H, TI, TO, (SP && kBlkSpread<P, O, false, R4, TO>)>), dim3((unsigned)grid), dim3(512), O ? BlkGeom<P>::kLdsOff : BlkGeom<P>::kLds, b.s, \
-                          b.ev_start, b.ev_stop, 0u, in, b.in_stride, out, b.tw256, b.twq, b.cbt, b.shn, b.slot_off, (long long)b.mbase * (R4 ? 192 : 128), \
-                          (long long)b.nb_call, b.out_bytes, b.nb_chunk, b.hints, (unsigned long long *)nullptr, roff, b.first_block, \
-                          R4 ? b.scratch : (float2 *)nullptr, (const unsigned *)nullptr, iq_tail(iq_scale, oq_scale))
-#define FDC_LB(P, A, O, R4) FDC_L(P, A, O, R4, false, b.r)
-#define FDC_LH(P, A, R4) FDC_L(P, A, false, R4, true, 0)
-// (FDC_R4(P): the R = 4 forms exist — not at P = 8 on float input with integer output, kOqR4Narrowed)
-#define FDC_R4(P) if constexpr (P != 8 || !kOqR4Narrowed<TI, TO>::value)
-#define FDC_LP(P) \
-    do { \
-        if (halfslot) { \
-            if (r4) { FDC_R4(P) { if (nt) FDC_LH(P, true, true); else FDC_LH(P, false, true); } else return hipErrorInvalidValue; } \
-            else { if (nt) FDC_LH(P, true, false); else FDC_LH(P, false, false); } \
-        } else if (r4 && b.r) { FDC_R4(P) { if (nt) FDC_LB(P, true, true, true); else FDC_LB(P, false, true, true); } else return hipErrorInvalidValue; } \
-        else if (r4) { FDC_R4(P) { if (nt) FDC_LB(P, true, false, true); else FDC_LB(P, false, false, true); } else return hipErrorInvalidValue; } \
-        else if (b.r) { if (nt) FDC_LB(P, true, true, false); else FDC_LB(P, false, true, false); } \
-        else { if (nt) FDC_LB(P, true, false, false); else FDC_LB(P, false, false, false); } \
-    } while (0)
     // streamed input loads (hints bit 1, a diagnostic): the forms with all sixteen row loads at the top of a pass
-    auto launch = [&](auto sp) -> hipError_t {
-        constexpr bool SP = decltype(sp)::value;
-        if (b.N == 65536) FDC_LP(8); else if (b.N == 32768) FDC_LP(4); else FDC_LP(2);
-        return hipSuccess;
-    };
-    const hipError_t e = (b.hints & 2) ? launch(std::false_type{}) : launch(std::true_type{});
-    if (e != hipSuccess) return e;
-#undef FDC_LP
-#undef FDC_R4
-#undef FDC_LH
-#undef FDC_LB
-#undef FDC_L
-    return hipGetLastError();
-}
-
-hipError_t launch_poly_block(const BlockLaunch &b) { return poly_block_in(b, b.in, b.out, 1.0f); }
-
-hipError_t launch_poly_block_iq(const BlockLaunch &b, int fmt, float scale, const void *in)
-{
-    if (fmt == kIqSc16) return poly_block_in(b, static_cast<const sc16 *>(in), b.out, scale);
-    if (fmt == kIqSc8) return poly_block_in(b, static_cast<const sc8 *>(in), b.out, scale);
-    return hipErrorInvalidValue;
-}
-
-template <class TO>
-static hipError_t poly_block_oq_in(const BlockLaunch &b, int ifmt, float iscale, const void *in, TO *out, float oscale)
-{
-    if (ifmt == kIqFloat) return poly_block_in<float2, TO>(b, static_cast<const float2 *>(in), out, 1.0f, oscale);
-    if (ifmt == kIqSc16) return poly_block_in<sc16, TO>(b, static_cast<const sc16 *>(in), out, iscale, oscale);
-    if (ifmt == kIqSc8) return poly_block_in<sc8, TO>(b, static_cast<const sc8 *>(in), out, iscale, oscale);
-    return hipErrorInvalidValue;
-}
-
-hipError_t launch_poly_block_oq(const BlockLaunch &b, int ifmt, float iscale, const void *in, int ofmt, float oscale, void *out)
-{
-    if (ofmt == kIqSc16) return poly_block_oq_in(b, ifmt, iscale, in, static_cast<sc16 *>(out), oscale);
-    if (ofmt == kIqSc8) return poly_block_oq_in(b, ifmt, iscale, in, static_cast<sc8 *>(out), oscale);
-    return hipErrorInvalidValue;
+    hipError_t e = hipErrorInvalidValue;                        // stays if no form matches
+    for_blk256_forms(b.N / 8192, b.hints & 1, !halfslot && b.r, 0, r4, halfslot, b.ifmt, b.ofmt, !(b.hints & 2), [&](auto k, int lds, auto ti, auto to) {
+        using TI = decltype(ti);
+        using TO = decltype(to);
+        hipExtLaunchKernelGGL(k, dim3((unsigned)grid), dim3(512), lds, b.s, b.ev_start, b.ev_stop, 0u, static_cast<const TI *>(b.in), b.in_stride,
+                              static_cast<TO *>(b.out), b.tw256, b.twq, b.cbt, b.shn, b.slot_off, (long long)b.mbase * (r4 ? 192 : 128), (long long)b.nb_call,
+                              b.out_bytes, b.nb_chunk, b.hints, (unsigned long long *)nullptr, halfslot ? 0 : b.r, b.first_block,
+                              r4 ? b.scratch : (float2 *)nullptr, (const unsigned *)nullptr, iq_tail<TI, TO>(nullptr, b.iscale, b.oscale));
+        e = hipGetLastError();
+    });
+    return e;
 }
 
 // Forward transform of nitems blocks of 65536 samples (item m at in + m*in_stride) into the shifted, 1/N-scaled spectrum
@@ -777,16 +661,16 @@ hipError_t launch_block_fft(int N, const float2 *in, size_t in_stride, float2 *o
         int grid = ncu > 0 ? ncu : 256;
         if (grid > nb) grid = nb;
         hipEvent_t e0 = ev && m0 == 0 ? ev[0] : nullptr, e2 = ev && m0 + nb >= nitems ? ev[1] : nullptr;
-#define FDC_LF(P, A) \
-        hipExtLaunchKernelGGL((k_blk256<P, A, false, true>), dim3((unsigned)grid), dim3(512), BlkGeom<P>::kLds, s, e0, e2, 0u, in + (size_t)m0 * in_stride, \
-                              in_stride, out + (size_t)m0 * (size_t)N, tw256, twq, cbt0, shn1, slot_off, 0ll, 1ll, \
-                              (unsigned)((size_t)nb * (size_t)N * 8), nb, hints, (unsigned long long *)nullptr, 0, 0ll, scratch, keep, \
-                              gpow ? gpow + (size_t)m0 * (size_t)(N / 16) : (float *)nullptr)
-        const bool nt = (hints & 1) != 0;
-        if (N == 65536) { if (nt) FDC_LF(8, true); else FDC_LF(8, false); }
-        else if (N == 32768) { if (nt) FDC_LF(4, true); else FDC_LF(4, false); }
-        else { if (nt) FDC_LF(2, true); else FDC_LF(2, false); }
-#undef FDC_LF
+        hipError_t e = hipErrorInvalidValue;
+        for_blk256_forms(N / 8192, hints & 1, 0, 1, 0, 0, kIqFloat, kIqFloat, 0, [&](auto k, int lds, auto ti, auto to) {
+            if constexpr (std::is_same<decltype(ti), float2>::value && std::is_same<decltype(to), float2>::value) {
+                hipExtLaunchKernelGGL(k, dim3((unsigned)grid), dim3(512), lds, s, e0, e2, 0u, in + (size_t)m0 * in_stride, in_stride, out + (size_t)m0 * (size_t)N,
+                                      tw256, twq, cbt0, shn1, slot_off, 0ll, 1ll, (unsigned)((size_t)nb * (size_t)N * 8), nb, hints,
+                                      (unsigned long long *)nullptr, 0, 0ll, scratch, keep, gpow ? gpow + (size_t)m0 * (size_t)(N / 16) : (float *)nullptr);
+                e = hipGetLastError();
+            }
+        });
+        if (e != hipSuccess) return e;
     }
     if (ev) { hipError_t e = hipEventRecord(ev[2], s); if (e != hipSuccess) return e; }
     return hipGetLastError();

@@ -8,6 +8,7 @@
 #include "fdc_kernels.h"
 #include "fdc_radix16.hpp"
 #include "fdc_devutil.hpp"
+#include "fdc_forms.hpp"
 
 namespace fdc {
 
@@ -133,15 +134,7 @@ __device__ __forceinline__ void strip_ifft256(cf (&u)[16], const float2 *wr, flo
     strip_trip(u, scrw, scrr);
     dft16<true>(u);
 }
-// ---- host: which instantiation a launch takes
-// f(std::integral_constant<int, V>{}) for the V that equals v, or for every V (v = kEvery): a kernel file writes "set the LDS attribute of every
-// instantiation" and "launch the one that matches" over the same list of template arguments
-constexpr int kEvery = -1;
-template <int... Vs, class F>
-inline void for_values(int v, F &&f)
-{
-    ((v == kEvery || v == Vs ? f(std::integral_constant<int, Vs>{}) : void()), ...);
-}
+// ---- host: which instantiation a launch takes (fdc_forms.hpp)
 // the (NT, R4, P) forms of a channelizer kernel: streamed stores (hints bit 0), R = 4, P = N / 8192 passes
 template <class F>
 inline void for_block_variants(int nt, int r4, int p, F &&f)
@@ -149,10 +142,6 @@ inline void for_block_variants(int nt, int r4, int p, F &&f)
     for_values<8, 4, 2>(p, [&](auto P) {
         for_values<0, 1>(r4, [&](auto R4) { for_values<1, 0>(nt, [&](auto NT) { f(NT, R4, P); }); });
     });
-}
-inline hipError_t set_block_lds(const void *kernel, int bytes)
-{
-    return hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
 }
 
 }  // namespace fdc

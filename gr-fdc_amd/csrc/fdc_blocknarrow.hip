@@ -18,7 +18,7 @@
 //     Y[k + 256 i] = sum_e W_S^(i e) (W_{256 S}^(k e) F_e[k]),   k = klo + 8 khi
 // A wave's store is 64/S consecutive samples of each of S slots (S = 2: two 256-byte runs; S = 4: four 128-byte runs).
 //
-// All constants of stage 1 come from ONE host-built table image (fdc_api.hip: double precision, rounded once).  The arithmetic is that of
+// All constants of stage 1 come from ONE host-built table image (poly_block_narrow_tables: double precision, rounded once).  The arithmetic is that of
 // k_p1g + k_p2g (fdc_kernels.hip) regrouped; parity against the oracle: tests/test_parity_gpu.py.
 #include <cmath>
 #include "fdc_blockcommon.hpp"
@@ -80,7 +80,7 @@ int poly_block_narrow_table_points(int L, int N)
 // half: the bank sits half a channel higher (f = l slot + l/2: channels centred on multiples of l).  That is the on-grid plan of the block
 // modulated by exp(-2 pi i (l/2) n / N) = W_N^((l/2) n1) (-1)^n2: the (-1)^n2 moves every column's spectrum by l/2 bins, which together with the
 // ifftshift of the inverse is the identity — the data stays in its registers and only the tables move (entries of kap ^ l/2), the separation's
-// and the re-join's twiddles cancel, and the per-column constant W_N^((l/2) n1) goes into TD (its e part) and cbt (its V part, fdc_api.hip).
+// and the re-join's twiddles cancel, and the per-column constant W_N^((l/2) n1) goes into TD (its e part) and cbt (its V part, fdc_plan.hip).
 template <int S, int P>
 static void narrow_tables(const float *shn, float2 *img, bool half, int r)
 {
@@ -425,12 +425,12 @@ hipError_t launch_poly_block_narrow(const BlockLaunch &b)
 {
     const int L = b.L;
     if (b.nb_chunk <= 0) return hipSuccess;
-    if (!poly_block_narrow_supports(b.N, L, b.R) || (b.R == 4 && !b.scratch) || b.r < 0 || b.r >= L || (b.r % (L / 4))) return hipErrorInvalidValue;
+    if (!poly_block_narrow_supports(b.N, L, b.R) || (b.R == 4 && !b.scratch) || b.r < 0 || b.r >= L || (b.r % (L / 4)) || b.ifmt || b.ofmt) return hipErrorInvalidValue;
     const int rows = b.R == 4 ? 3 * L / 4 : L / 2;
     hipError_t e = hipErrorInvalidValue;                        // stays if no instantiation matches
     for_narrow_variants(256 / L, b.r / (L / 4), b.hints & 1, b.R == 4, b.N / 8192, [&](auto S, auto NT, auto R4, auto H, auto ROT, auto P) {
         hipExtLaunchKernelGGL((k_blknar<S(), NT() != 0, R4() != 0, H(), ROT(), P()>), dim3((unsigned)b.grid()), dim3(512), NarGeom<S(), P()>::kLds, b.s,
-                              b.ev_start, b.ev_stop, 0u, b.in, b.in_stride, b.out, b.tab, b.cbt, b.slot_off, (long long)b.mbase * rows, (long long)b.nb_call,
+                              b.ev_start, b.ev_stop, 0u, b.fin(), b.in_stride, b.fout(), b.tab, b.cbt, b.slot_off, (long long)b.mbase * rows, (long long)b.nb_call,
                               b.out_bytes, b.nb_chunk, b.hints, R4() ? b.scratch : (float2 *)nullptr);
         e = hipGetLastError();
     });

@@ -90,12 +90,12 @@ static int run_remainder(fdc_pipeline *p, const DeviceCall &call, const float2 *
     return FDC_OK;
 }
 
-// one launch of the bank's block kernel over a launch group.  b: the group's part of the launch (input, output, its blocks, the events the dispatch itself
-// stamps); the handle's and the bank's part is filled in here.  raw: the group's first integer sample where the 256-bin kernel reads the call's integer
-// input itself (null: float samples, b.in); oq: the call's narrow output where it narrows in its stores (b.out_bytes: the narrow extent; null: float, b.out)
-static int launch_bank(fdc_pipeline *p, const DeviceCall &call, const fdc_pipeline::Bank &bk, fdc::BlockLaunch b, const void *raw, void *oq)
+// one launch of the bank's block kernel over a launch group.  b: the group's part of the launch (its samples and their formats, its blocks, the events the
+// dispatch itself stamps); the handle's and the bank's part is filled in here.  Integer samples: the 256-bin kernel only
+static int launch_bank(fdc_pipeline *p, const DeviceCall &call, const fdc_pipeline::Bank &bk, fdc::BlockLaunch b)
 {
     b.in_stride = (size_t)p->H;
+    b.iscale = call.scale; b.oscale = call.oscale;
     b.slot_off = bk.d_slot_off;
     b.ncu = call.ncu; b.hints = p->block_hints;
     b.s = call.stream;
@@ -105,16 +105,7 @@ static int launch_bank(fdc_pipeline *p, const DeviceCall &call, const fdc_pipeli
     b.tw256 = p->d_tw256;
     b.twq = bk.L == 512 ? p->d_twq512 : bk.L == 1024 ? p->d_twq1k : p->d_twq;
     b.twl = bk.L == 512 ? p->d_tw512 : bk.L == 1024 ? p->d_tw1k : nullptr;
-    if (oq) {
-        if (bk.L != 256) return set_error(FDC_ERR_UNSUPPORTED, "integer stores in a %d-bin bank", bk.L);
-        HIPCHK(fdc::launch_poly_block_oq(b, raw ? call.fmt : 0, call.scale, raw ? raw : static_cast<const void *>(b.in), call.ofmt, call.oscale, oq));
-        return FDC_OK;
-    }
-    if (raw) {
-        if (bk.L != 256) return set_error(FDC_ERR_UNSUPPORTED, "integer loads in a %d-bin bank", bk.L);
-        HIPCHK(fdc::launch_poly_block_iq(b, call.fmt, call.scale, raw));
-        return FDC_OK;
-    }
+    if (bk.L != 256 && (b.ifmt || b.ofmt)) return set_error(FDC_ERR_UNSUPPORTED, "integer %s in a %d-bin bank", b.ofmt ? "stores" : "loads", bk.L);
     switch (bk.L) {
     case 256: HIPCHK(fdc::launch_poly_block(b)); break;
     case 512: HIPCHK(fdc::launch_poly_block512(b)); break;
@@ -249,6 +240,17 @@ int process_device_impl(fdc_pipeline *p, DeviceCall &call, const void *d_ring, i
     const bool use_poly = p->poly_ok && !d_spectrum;
     const unsigned out_bytes = (unsigned)((int64_t)nblocks * p->sum_lout * (int64_t)osz);
     const PostPass pp = post_pass(p, call, ofused);      // what runs behind the kernels of every launch group and behind the call: decided here, once
+    // path 5: the call's part of every group's launch (the group's: its input, its blocks and its waterfall rows)
+    fdc::F4Launch f4{};
+    if (p->fused && !d_spectrum) {
+        f4.iscale = call.scale; f4.in_stride = (size_t)p->H;
+        f4.out = ofused ? d_out : o; f4.ofmt = ofused ? ofmt : 0; f4.oscale = call.oscale;
+        f4.R = p->R; f4.nb_call = nblocks; f4.first_block = first_block;
+        f4.tw = p->d_tw; f4.ntab = p->ntab; f4.wins = p->d_wins;
+        f4.rows = p->d_f4rows; f4.wcls = p->f4_cls; f4.teams = p->f4_teams;
+        if (pp.fine_fused) { f4.fine_rows = p->d_f4fine; f4.fine_step = p->d_fstep; }
+        f4.s = s;
+    }
     for (int m0 = 0; m0 < nblocks; m0 += p->chunk) {
         const int nb = std::min(p->chunk, nblocks - m0);
         const Span grp{nb, m0, nblocks, first_block};
@@ -280,18 +282,9 @@ int process_device_impl(fdc_pipeline *p, DeviceCall &call, const void *d_ring, i
             // N = 4096: one launch, nothing but the input samples and the output samples crosses the memory interface
             if (tg) HIPCHK(hipEventRecord(p->events[span[0]], s));
             float *wf = call.rows ? call.rows + (size_t)(first_block - call.rows_first + m0) * fdc::kWfWidth : nullptr;
-            if (pp.fine_fused)
-                HIPCHK(fdc::launch_fused4096_fine(ifused ? fmt : 0, call.scale, ifused ? raw0 : static_cast<const void *>(in0), (size_t)p->H, ofused ? ofmt : 0, call.oscale,
-                                                  ofused ? d_out : static_cast<void *>(o), nb, p->R, m0, nblocks, first_block, p->d_tw, p->ntab, p->d_wins, p->d_f4rows,
-                                                  p->f4_cls, p->f4_teams, p->d_f4fine, p->d_fstep, s));
-            else if (ofused)
-                HIPCHK(fdc::launch_fused4096_oq(ifused ? fmt : 0, call.scale, ifused ? raw0 : static_cast<const void *>(in0), (size_t)p->H, ofmt, call.oscale, d_out, nb,
-                                                p->R, m0, nblocks, first_block, p->d_tw, p->ntab, p->d_wins, p->d_f4rows, p->f4_cls, p->f4_teams, s));
-            else if (ifused)
-                HIPCHK(fdc::launch_fused4096_iq(fmt, call.scale, raw0, (size_t)p->H, o, nb, p->R, m0, nblocks, first_block, p->d_tw, p->ntab, p->d_wins, p->d_f4rows,
-                                                p->f4_cls, p->f4_teams, s));
-            else
-                HIPCHK(fdc::launch_fused4096(in0, (size_t)p->H, o, nb, p->R, m0, nblocks, first_block, p->d_tw, p->ntab, p->d_wins, p->d_f4rows, p->f4_cls, p->f4_teams, s, wf));
+            f4.in = ifused ? raw0 : in0; f4.ifmt = ifused ? fmt : 0;
+            f4.nb_chunk = nb; f4.mbase = m0; f4.wf = wf;
+            HIPCHK(fdc::launch_fused4096(f4));
             if (tg) { HIPCHK(hipEventRecord(p->events[span[1]], s)); span[2] = span[3] = span[1]; span[4] = kSpanBanks; p->ev_spans.push_back(span); }
             RCCHK(run_post_passes(p, call, pp, grp, o, d_out));
             continue;
@@ -300,13 +293,14 @@ int process_device_impl(fdc_pipeline *p, DeviceCall &call, const void *d_ring, i
             // one launch per bank: nothing but the input rows and the output samples crosses the memory interface.
             // timing: the first launch's begin and the last one's end are the dispatches' own stamps, no packets around the kernels
             fdc::BlockLaunch b{};
-            b.in = in0; b.out = o;
+            b.in = ifused ? raw0 : in0; b.ifmt = ifused ? fmt : 0;
+            b.out = ofused ? d_out : o; b.ofmt = ofused ? ofmt : 0;
             b.nb_chunk = nb; b.mbase = m0; b.nb_call = nblocks;
             b.first_block = first_block + m0; b.out_bytes = out_bytes;
             for (size_t k = 0; k < p->banks.size(); k++) {
                 b.ev_start = tg && k == 0 ? p->events[span[0]] : nullptr;
                 b.ev_stop = tg && k + 1 == p->banks.size() ? p->events[span[1]] : nullptr;
-                RCCHK(launch_bank(p, call, p->banks[k], b, ifused ? raw0 : nullptr, ofused ? d_out : nullptr));
+                RCCHK(launch_bank(p, call, p->banks[k], b));
             }
             for (const auto &al : p->bank_alias) {
                 const fdc::ChanDev &dc = p->chans[(size_t)al.first], &sc = p->chans[(size_t)al.second];

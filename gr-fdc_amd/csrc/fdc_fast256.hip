@@ -773,12 +773,13 @@ hipError_t launch_extract256_narrow(int fmt, float scale, const float2 *spec, in
 {
     if (ntasks <= 0) return hipSuccess;
     const dim3 grid((unsigned)((ntasks + 15) / 16));
-    if (fmt == kIqSc16)
-        hipLaunchKernelGGL(k_x256n<sc16>, grid, dim3(256), kCTileBytes + 2304, s, spec, out, tasks, ntasks, N, skip, wins, tw256, static_cast<sc16 *>(nout), used_a, scale);
-    else if (fmt == kIqSc8)
-        hipLaunchKernelGGL(k_x256n<sc8>, grid, dim3(256), kCTileBytes + 2304, s, spec, out, tasks, ntasks, N, skip, wins, tw256, static_cast<sc8 *>(nout), used_a, scale);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
+    hipError_t e = hipErrorInvalidValue;                        // stays if fmt is no integer format
+    for_int_samples(fmt, [&](auto t) {
+        hipLaunchKernelGGL(k_x256n<decltype(t)>, grid, dim3(256), kCTileBytes + 2304, s, spec, out, tasks, ntasks, N, skip, wins, tw256, static_cast<decltype(t) *>(nout),
+                           used_a, scale);
+        e = hipGetLastError();
+    });
+    return e;
 }
 
 // FDC_NT bits (A/B testing): 1 = stage-2 output stores nt, 2 = stage-1 input loads nt, 4 = stage-2 G loads nt, 8 = stage-1 G stores nt

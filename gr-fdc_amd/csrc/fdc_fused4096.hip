@@ -7,7 +7,7 @@
 //
 //   a workgroup takes T blocks, T teams of four waves: each team transforms one block (4096 points = 32 KiB, the same three DFT-16 layers as
 //   k_fft4096, fdc_chanwide.hip) and stores the shifted, 1/N-scaled spectrum to LDS over its exchange tile (32 KiB); every one of the 4 T
-//   WAVES then owns rows — (block of the workgroup, channel) — of ONE channel width: the plan's schedule, made by the host (fdc_api.hip,
+//   WAVES then owns rows — (block of the workgroup, channel) — of ONE channel width: the plan's schedule, made by the host (fdc_plan.hip,
 //   plan_fused4096).  T = 2 (512 threads, two workgroups on a unit) for plans with wide rows: a wave's instructions cost the same for one
 //   row as for a full wave of them, and the reference's example plan fills its 1024- and 512-bin waves only with the rows of two blocks;
 //   T = 1 (256 threads, FOUR workgroups on a unit: four barrier domains instead of two, 11 - 12 % faster) where no row is wide.
@@ -134,195 +134,63 @@ __global__ __launch_bounds__(256 * TEAMS, 4 /* waves per SIMD */) void k_f4096_f
 #include "fdc_fused4096_body.inc"
 }
 
-template <bool ROWS, class TI = float2, class TO = float2>
-static hipError_t init_fused4096_forms()
+// The forms of the kernel, stated ONCE (fdc_forms.hpp): (WIDE, TEAMS) of either kernel on every input and output sample type; FINE takes
+// k_f4096_fine, which has no waterfall form; ROWS on float input and float output only.  f(kernel, TEAMS, LDS bytes, TI{}, TO{}, FINE) for the forms
+// that match (kEvery: every value of that argument)
+template <class F>
+static void for_f4_forms(int wide, int teams, int rows, int fine, int ifmt, int ofmt, F &&f)
 {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_f4096<false, 2, ROWS, TI, TO>), hipFuncAttributeMaxDynamicSharedMemorySize, f4_lds(2));
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_f4096<false, 1, ROWS, TI, TO>), hipFuncAttributeMaxDynamicSharedMemorySize, f4_lds(1));
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_f4096<true, 1, ROWS, TI, TO>), hipFuncAttributeMaxDynamicSharedMemorySize, f4_lds_wide(1));
-    if (e != hipSuccess) return e;
-    return hipFuncSetAttribute(reinterpret_cast<const void *>(k_f4096<true, 2, ROWS, TI, TO>), hipFuncAttributeMaxDynamicSharedMemorySize, f4_lds_wide(2));
-}
-
-template <class TO>
-static hipError_t init_fused4096_oq()
-{
-    hipError_t e = init_fused4096_forms<false, float2, TO>();
-    if (e == hipSuccess) e = init_fused4096_forms<false, sc16, TO>();
-    return e != hipSuccess ? e : init_fused4096_forms<false, sc8, TO>();
-}
-
-template <class TI, class TO>
-static hipError_t init_fused4096_fine_forms()
-{
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_f4096_fine<false, 2, TI, TO>), hipFuncAttributeMaxDynamicSharedMemorySize, f4_lds(2));
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_f4096_fine<false, 1, TI, TO>), hipFuncAttributeMaxDynamicSharedMemorySize, f4_lds(1));
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_f4096_fine<true, 1, TI, TO>), hipFuncAttributeMaxDynamicSharedMemorySize, f4_lds_wide(1));
-    if (e != hipSuccess) return e;
-    return hipFuncSetAttribute(reinterpret_cast<const void *>(k_f4096_fine<true, 2, TI, TO>), hipFuncAttributeMaxDynamicSharedMemorySize, f4_lds_wide(2));
-}
-
-template <class TO>
-static hipError_t init_fused4096_fine_out()
-{
-    hipError_t e = init_fused4096_fine_forms<float2, TO>();
-    if (e == hipSuccess) e = init_fused4096_fine_forms<sc16, TO>();
-    return e != hipSuccess ? e : init_fused4096_fine_forms<sc8, TO>();
+    auto form = [&](auto W, auto T, auto ROWS, auto FINE, auto ti, auto to) {
+        using TI = decltype(ti);
+        using TO = decltype(to);
+        constexpr bool kWide = W() != 0, kFloat = std::is_same<TI, float2>::value && std::is_same<TO, float2>::value;
+        constexpr int kLds = kWide ? f4_lds_wide(T()) : f4_lds(T());
+        if constexpr (FINE() && !ROWS()) f(k_f4096_fine<kWide, T(), TI, TO>, T, kLds, ti, to, FINE);
+        else if constexpr (!FINE() && (!ROWS() || kFloat)) f(k_f4096<kWide, T(), ROWS() != 0, TI, TO>, T, kLds, ti, to, FINE);
+    };
+    for_values<0, 1>(wide, [&](auto W) { for_values<1, 2>(teams, [&](auto T) { for_values<0, 1>(rows, [&](auto ROWS) { for_values<0, 1>(fine, [&](auto FINE) {
+        for_samples(ifmt, [&](auto ti) { for_samples(ofmt, [&](auto to) { form(W, T, ROWS, FINE, ti, to); }); });
+    }); }); }); });
 }
 
 hipError_t init_fused4096_kernels()
 {
-    hipError_t e = init_fused4096_fine_out<float2>();                 // fine tuning in the stores: every input and output form
-    if (e == hipSuccess) e = init_fused4096_fine_out<sc16>();
-    if (e == hipSuccess) e = init_fused4096_fine_out<sc8>();
-    if (e != hipSuccess) return e;
-    e = init_fused4096_forms<false>();
-    if (e == hipSuccess) e = init_fused4096_forms<true>();
-    if (e == hipSuccess) e = init_fused4096_forms<false, sc16>();     // integer input: the channel outputs only (no ROWS form)
-    if (e == hipSuccess) e = init_fused4096_forms<false, sc8>();
-    if (e == hipSuccess) e = init_fused4096_oq<sc16>();               // integer output, every input form (no ROWS form)
-    return e != hipSuccess ? e : init_fused4096_oq<sc8>();
+    hipError_t e = hipSuccess;
+    for_f4_forms(kEvery, kEvery, kEvery, kEvery, kEvery, kEvery, [&](auto k, auto, int lds, auto, auto, auto) {
+        if (e == hipSuccess) e = set_block_lds(reinterpret_cast<const void *>(k), lds);
+    });
+    return e;
 }
 
 int fused4096_tile_points() { return kF4TilePts; }
 
-template <bool ROWS, class TI = float2, class TO = float2>
-static void launch_fused4096_form(dim3 grid, bool wide, int teams, hipStream_t s, const TI *in, size_t in_stride, TO *out, int nb_chunk, int R,
-                                  int mbase, int nb_call, int fbm, const float2 *tw, int ntab, const float2 *wins, const F4Row *rows, unsigned wcls,
-                                  typename IqTail<TI, TO>::type wf /* integer TI / TO: the scale(s) */)
+hipError_t launch_fused4096(const F4Launch &a)
 {
-    if (wide && teams == 1)
-        hipLaunchKernelGGL((k_f4096<true, 1, ROWS, TI, TO>), grid, dim3(256), f4_lds_wide(1), s, in, in_stride, out, nb_chunk, R, mbase, nb_call, fbm, tw, ntab / 4096, wins, rows, wcls, wf);
-    else if (wide)
-        hipLaunchKernelGGL((k_f4096<true, 2, ROWS, TI, TO>), grid, dim3(512), f4_lds_wide(2), s, in, in_stride, out, nb_chunk, R, mbase, nb_call, fbm, tw, ntab / 4096, wins, rows, wcls, wf);
-    else if (teams == 2)
-        hipLaunchKernelGGL((k_f4096<false, 2, ROWS, TI, TO>), grid, dim3(512), f4_lds(2), s, in, in_stride, out, nb_chunk, R, mbase, nb_call, fbm, tw, ntab / 4096, wins, rows, wcls, wf);
-    else
-        hipLaunchKernelGGL((k_f4096<false, 1, ROWS, TI, TO>), grid, dim3(256), f4_lds(1), s, in, in_stride, out, nb_chunk, R, mbase, nb_call, fbm, tw, ntab / 4096, wins, rows, wcls, wf);
-}
-
-// The launch shape both entries share: whether a wave holds wide rows (l = 512 / 1024: the WIDE form), the grid (one workgroup per `teams`
-// blocks, a multiple of the eight XCDs) and fbm = (first block of the call + first block of the launch) mod R
-struct F4Shape { dim3 grid; bool wide; int fbm; };
-static hipError_t f4_shape(int nb_chunk, int R, int mbase, int64_t first_block, unsigned wcls, int teams, F4Shape *sh)
-{
-    if (teams != 2 && teams != 1) return hipErrorInvalidValue;
+    if (a.nb_chunk <= 0) return hipSuccess;
+    if (a.teams == kEvery || a.ifmt == kEvery || a.ofmt == kEvery) return hipErrorInvalidValue;      // a launch names one form
+    // whether a wave holds wide rows (l = 512 / 1024: the WIDE form)
     bool wide = false;
-    for (int w = 0; w < 8; w++) wide = wide || ((wcls >> (4 * w)) & 0xfu) == 3 || ((wcls >> (4 * w)) & 0xfu) == 4;
-    const int ngroups = (nb_chunk + teams - 1) / teams;
-    *sh = F4Shape{dim3((unsigned)(8 * ((ngroups + 7) / 8))), wide, (int)((first_block + mbase) % R)};
-    return hipSuccess;
-}
-
-// teams: blocks per workgroup the schedule was made for (1: rows[4 waves][8]; 2: rows[8 waves][8])
-// wf: NULL, or nb_chunk x 1024 floats: the waterfall row sums of the chunk's blocks (the ROWS form of the kernel)
-hipError_t launch_fused4096(const float2 *in, size_t in_stride, float2 *out, int nb_chunk, int R, int mbase, int nb_call, int64_t first_block,
-                            const float2 *tw, int ntab, const float2 *wins, const F4Row *rows, unsigned wcls, int teams, hipStream_t s, float *wf)
-{
-    if (nb_chunk <= 0) return hipSuccess;
-    F4Shape sh;
-    const hipError_t e = f4_shape(nb_chunk, R, mbase, first_block, wcls, teams, &sh);
-    if (e != hipSuccess) return e;
-    if (wf) launch_fused4096_form<true>(sh.grid, sh.wide, teams, s, in, in_stride, out, nb_chunk, R, mbase, nb_call, sh.fbm, tw, ntab, wins, rows, wcls, wf);
-    else launch_fused4096_form<false>(sh.grid, sh.wide, teams, s, in, in_stride, out, nb_chunk, R, mbase, nb_call, sh.fbm, tw, ntab, wins, rows, wcls, nullptr);
-    return hipGetLastError();
-}
-
-hipError_t launch_fused4096_iq(int fmt, float scale, const void *in, size_t in_stride, float2 *out, int nb_chunk, int R, int mbase, int nb_call,
-                               int64_t first_block, const float2 *tw, int ntab, const float2 *wins, const F4Row *rows, unsigned wcls, int teams, hipStream_t s)
-{
-    if (nb_chunk <= 0) return hipSuccess;
-    if (fmt != kIqSc16 && fmt != kIqSc8) return hipErrorInvalidValue;
-    F4Shape sh;
-    const hipError_t e = f4_shape(nb_chunk, R, mbase, first_block, wcls, teams, &sh);
-    if (e != hipSuccess) return e;
-    if (fmt == kIqSc16)
-        launch_fused4096_form<false>(sh.grid, sh.wide, teams, s, static_cast<const sc16 *>(in), in_stride, out, nb_chunk, R, mbase, nb_call, sh.fbm, tw, ntab,
-                                     wins, rows, wcls, scale);
-    else
-        launch_fused4096_form<false>(sh.grid, sh.wide, teams, s, static_cast<const sc8 *>(in), in_stride, out, nb_chunk, R, mbase, nb_call, sh.fbm, tw, ntab,
-                                     wins, rows, wcls, scale);
-    return hipGetLastError();
-}
-
-template <class TO>
-static hipError_t fused4096_oq_in(int ifmt, float iscale, const void *in, size_t in_stride, TO *out, int nb_chunk, int R, int mbase, int nb_call,
-                                  const F4Shape &sh, const float2 *tw, int ntab, const float2 *wins, const F4Row *rows, unsigned wcls, int teams,
-                                  hipStream_t s, float oscale)
-{
-    if (ifmt == kIqFloat)
-        launch_fused4096_form<false>(sh.grid, sh.wide, teams, s, static_cast<const float2 *>(in), in_stride, out, nb_chunk, R, mbase, nb_call, sh.fbm, tw,
-                                     ntab, wins, rows, wcls, oscale);
-    else if (ifmt == kIqSc16)
-        launch_fused4096_form<false>(sh.grid, sh.wide, teams, s, static_cast<const sc16 *>(in), in_stride, out, nb_chunk, R, mbase, nb_call, sh.fbm, tw,
-                                     ntab, wins, rows, wcls, make_float2(iscale, oscale));
-    else if (ifmt == kIqSc8)
-        launch_fused4096_form<false>(sh.grid, sh.wide, teams, s, static_cast<const sc8 *>(in), in_stride, out, nb_chunk, R, mbase, nb_call, sh.fbm, tw,
-                                     ntab, wins, rows, wcls, make_float2(iscale, oscale));
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
-}
-
-hipError_t launch_fused4096_oq(int ifmt, float iscale, const void *in, size_t in_stride, int ofmt, float oscale, void *out, int nb_chunk, int R, int mbase,
-                               int nb_call, int64_t first_block, const float2 *tw, int ntab, const float2 *wins, const F4Row *rows, unsigned wcls, int teams,
-                               hipStream_t s)
-{
-    if (nb_chunk <= 0) return hipSuccess;
-    F4Shape sh;
-    const hipError_t e = f4_shape(nb_chunk, R, mbase, first_block, wcls, teams, &sh);
-    if (e != hipSuccess) return e;
-    if (ofmt == kIqSc16)
-        return fused4096_oq_in(ifmt, iscale, in, in_stride, static_cast<sc16 *>(out), nb_chunk, R, mbase, nb_call, sh, tw, ntab, wins, rows, wcls, teams, s, oscale);
-    if (ofmt == kIqSc8)
-        return fused4096_oq_in(ifmt, iscale, in, in_stride, static_cast<sc8 *>(out), nb_chunk, R, mbase, nb_call, sh, tw, ntab, wins, rows, wcls, teams, s, oscale);
-    return hipErrorInvalidValue;
-}
-
-// ---- fine tuning in the kernel's stores (fdc_fine.hpp): every input form (ifmt) and output form (ofmt; kIqFloat: out holds float2) -----------------------
-template <class TI, class TO>
-static void launch_fused4096_fine_form(const F4Shape &sh, int teams, hipStream_t s, const void *in, size_t in_stride, void *out, int nb_chunk, int R, int mbase,
-                                       int nb_call, const float2 *tw, int ntab, const float2 *wins, const F4Row *rows, unsigned wcls,
-                                       typename IqTail<TI, TO>::type wf, const F4Fine &fa)
-{
-    const TI *i = static_cast<const TI *>(in);
-    TO *o = static_cast<TO *>(out);
-    if (sh.wide && teams == 1)
-        hipLaunchKernelGGL((k_f4096_fine<true, 1, TI, TO>), sh.grid, dim3(256), f4_lds_wide(1), s, i, in_stride, o, nb_chunk, R, mbase, nb_call, sh.fbm, tw, ntab / 4096, wins, rows, wcls, wf, fa);
-    else if (sh.wide)
-        hipLaunchKernelGGL((k_f4096_fine<true, 2, TI, TO>), sh.grid, dim3(512), f4_lds_wide(2), s, i, in_stride, o, nb_chunk, R, mbase, nb_call, sh.fbm, tw, ntab / 4096, wins, rows, wcls, wf, fa);
-    else if (teams == 2)
-        hipLaunchKernelGGL((k_f4096_fine<false, 2, TI, TO>), sh.grid, dim3(512), f4_lds(2), s, i, in_stride, o, nb_chunk, R, mbase, nb_call, sh.fbm, tw, ntab / 4096, wins, rows, wcls, wf, fa);
-    else
-        hipLaunchKernelGGL((k_f4096_fine<false, 1, TI, TO>), sh.grid, dim3(256), f4_lds(1), s, i, in_stride, o, nb_chunk, R, mbase, nb_call, sh.fbm, tw, ntab / 4096, wins, rows, wcls, wf, fa);
-}
-
-hipError_t launch_fused4096_fine(int ifmt, float iscale, const void *in, size_t in_stride, int ofmt, float oscale, void *out, int nb_chunk, int R, int mbase,
-                                 int nb_call, int64_t first_block, const float2 *tw, int ntab, const float2 *wins, const F4Row *rows, unsigned wcls, int teams,
-                                 const FineChan *fine_rows, const float2 *fine_step, hipStream_t s)
-{
-    if (nb_chunk <= 0) return hipSuccess;
-    F4Shape sh;
-    const hipError_t e = f4_shape(nb_chunk, R, mbase, first_block, wcls, teams, &sh);
-    if (e != hipSuccess) return e;
-    const F4Fine fa{fine_rows, fine_step, (unsigned long long)(first_block + mbase)};
-    const float2 both = make_float2(iscale, oscale);
-#define FDC_F4FINE(TI, TO, tail) launch_fused4096_fine_form<TI, TO>(sh, teams, s, in, in_stride, out, nb_chunk, R, mbase, nb_call, tw, ntab, wins, rows, wcls, tail, fa)
-    if (ifmt == kIqFloat && ofmt == kIqFloat) FDC_F4FINE(float2, float2, nullptr);
-    else if (ifmt == kIqSc16 && ofmt == kIqFloat) FDC_F4FINE(sc16, float2, iscale);
-    else if (ifmt == kIqSc8 && ofmt == kIqFloat) FDC_F4FINE(sc8, float2, iscale);
-    else if (ifmt == kIqFloat && ofmt == kIqSc16) FDC_F4FINE(float2, sc16, oscale);
-    else if (ifmt == kIqFloat && ofmt == kIqSc8) FDC_F4FINE(float2, sc8, oscale);
-    else if (ifmt == kIqSc16 && ofmt == kIqSc16) FDC_F4FINE(sc16, sc16, both);
-    else if (ifmt == kIqSc16 && ofmt == kIqSc8) FDC_F4FINE(sc16, sc8, both);
-    else if (ifmt == kIqSc8 && ofmt == kIqSc16) FDC_F4FINE(sc8, sc16, both);
-    else if (ifmt == kIqSc8 && ofmt == kIqSc8) FDC_F4FINE(sc8, sc8, both);
-    else return hipErrorInvalidValue;
-#undef FDC_F4FINE
-    return hipGetLastError();
+    for (int w = 0; w < 8; w++) wide = wide || ((a.wcls >> (4 * w)) & 0xfu) == 3 || ((a.wcls >> (4 * w)) & 0xfu) == 4;
+    const int fbm = (int)((a.first_block + a.mbase) % a.R);
+    const F4Fine fa{a.fine_rows, a.fine_step, (unsigned long long)(a.first_block + a.mbase)};
+    hipError_t e = hipErrorInvalidValue;                        // stays if no form matches
+    for_f4_forms(wide, a.teams, a.wf != nullptr, a.fine_rows != nullptr, a.ifmt, a.ofmt, [&](auto k, auto T, int lds, auto ti, auto to, auto FINE) {
+        using TI = decltype(ti);
+        using TO = decltype(to);
+        // one workgroup per T blocks, a multiple of the eight XCDs
+        const dim3 grid((unsigned)(8 * (((a.nb_chunk + T() - 1) / T() + 7) / 8)));
+        const TI *in = static_cast<const TI *>(a.in);
+        TO *out = static_cast<TO *>(a.out);
+        const typename IqTail<TI, TO>::type tail = iq_tail<TI, TO>(a.wf, a.iscale, a.oscale);
+        if constexpr (FINE())
+            hipLaunchKernelGGL(k, grid, dim3(256 * T()), lds, a.s, in, a.in_stride, out, a.nb_chunk, a.R, a.mbase, a.nb_call, fbm, a.tw, a.ntab / 4096, a.wins, a.rows,
+                               a.wcls, tail, fa);
+        else
+            hipLaunchKernelGGL(k, grid, dim3(256 * T()), lds, a.s, in, a.in_stride, out, a.nb_chunk, a.R, a.mbase, a.nb_call, fbm, a.tw, a.ntab / 4096, a.wins, a.rows,
+                               a.wcls, tail);
+        e = hipGetLastError();
+    });
+    return e;
 }
 
 }  // namespace fdc

@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "fdc_radix16.hpp"
+#include "fdc_forms.hpp"
 
 namespace fdc {
 
@@ -37,6 +38,29 @@ __device__ __forceinline__ float iq_tail_scale(const float *) { return 1.0f; }
 __device__ __forceinline__ float oq_tail_scale(float s) { return s; }
 __device__ __forceinline__ float oq_tail_scale(float2 s) { return s.y; }
 __device__ __forceinline__ float oq_tail_scale(const float *) { return 1.0f; }
+// host: that argument of one launch — ptr (may be null) for the float2 forms, the scale(s) of the integer side(s) otherwise
+template <class TI, class TO>
+inline typename IqTail<TI, TO>::type iq_tail(float *ptr, float iscale, float oscale)
+{
+    constexpr bool kIq = !std::is_same<TI, float2>::value, kOq = !std::is_same<TO, float2>::value;
+    if constexpr (kIq && kOq) return make_float2(iscale, oscale);
+    else if constexpr (kIq) return iscale;
+    else if constexpr (kOq) return oscale;
+    else return ptr;
+}
+
+// host: which sample type a launch takes (fdc_forms.hpp): f(float2{}), f(sc16{}) or f(sc8{}) for the type of format fmt, or for every one (fmt = kEvery);
+// for_int_samples: the kernels without a float2 form
+template <int FMT> struct IqSample { typedef float2 type; };
+template <> struct IqSample<kIqSc16> { typedef sc16 type; };
+template <> struct IqSample<kIqSc8> { typedef sc8 type; };
+template <int... FMTS, class F>
+inline void for_sample_formats(int fmt, F &&f)
+{
+    for_values<FMTS...>(fmt, [&](auto V) { f(typename IqSample<decltype(V)::value>::type{}); });
+}
+template <class F> inline void for_samples(int fmt, F &&f) { for_sample_formats<kIqFloat, kIqSc16, kIqSc8>(fmt, f); }
+template <class F> inline void for_int_samples(int fmt, F &&f) { for_sample_formats<kIqSc16, kIqSc8>(fmt, f); }
 
 // one sample's raw bits (a dword / a 16-bit load), widened later by iq_widen_bits
 __device__ __forceinline__ unsigned iq_bits(const sc16 *p) { return *reinterpret_cast<const unsigned *>(p); }

@@ -1,4 +1,4 @@
-// Internal launcher interface between the C-ABI (fdc_api.hip) and the gfx950 kernels.
+// Internal launcher interface between the host side of the library (the C-ABI entries, fdc_plan.hip, fdc_enqueue.hip) and the gfx950 kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -83,7 +83,7 @@ hipError_t launch_fft4096(const float2 *in, size_t in_stride, float2 *out, int n
                           unsigned long long keep = ~0ull /* 64-bin groups of the output some reader wants */);
 
 // N = 4096 in one launch (fdc_fused4096.hip): forward transform + every channel's slice / window / inverse transform, the spectrum stays in LDS.
-// A 512-thread workgroup takes a pair of blocks.  The schedule is the host's (fdc_api.hip plan_fused4096): rows[8 waves][8 slots], four bits per
+// A 512-thread workgroup takes a pair of blocks.  The schedule is the host's (fdc_plan.hip plan_fused4096): rows[8 waves][8 slots], four bits per
 // wave in wcls (0 = no rows, 1 = l = 256 slots 0..3, 2 = l = 256 slots 0..7, 3 = l = 512 slots 0..3, 4 = l = 1024 slots 0..1, 5 / 6 / 7 / 8 = l = 128 / 64 / 32 / 16
 // slots 0..7); valid = 0: no row,
 // 1 + k: a row of the pair's block k; xch = the row's exchange area in the two tiles (points), rows disjoint, all inside 2 fused4096_tile_points().
@@ -91,24 +91,26 @@ hipError_t launch_fft4096(const float2 *in, size_t in_stride, float2 *out, int n
 struct F4Row { int32_t f, win_off, shift, xch, lout, valid; long long out_off; };
 hipError_t init_fused4096_kernels();
 int fused4096_tile_points();
-hipError_t launch_fused4096(const float2 *in, size_t in_stride, float2 *out, int nb_chunk, int R, int mbase, int nb_call, int64_t first_block,
-                            const float2 *tw, int ntab, const float2 *wins, const F4Row *rows, unsigned wcls, int teams /* blocks per workgroup: 1 (rows[4][8], no wide rows) or 2 (rows[8][8]) */, hipStream_t s,
-                            float *wf = nullptr /* nb_chunk x 1024 waterfall row sums (fdc_waterfall.hip), or NULL */);
-// the same on complex integer input (fmt: kIqSc16 / kIqSc8, fdc_iq.hpp; item m at in + m*in_stride samples), widened in the kernel's loads
-hipError_t launch_fused4096_iq(int fmt, float scale, const void *in, size_t in_stride, float2 *out, int nb_chunk, int R, int mbase, int nb_call,
-                               int64_t first_block, const float2 *tw, int ntab, const float2 *wins, const F4Row *rows, unsigned wcls, int teams, hipStream_t s);
-// integer OUTPUT (ofmt: kIqSc16 / kIqSc8 with its scale, fdc_iq.hpp oq_bits; out: the same sample offsets, narrow elements), narrowed in the kernel's
-// stores; input ifmt: kIqFloat (in: float2) or kIqSc16 / kIqSc8 with iscale
-hipError_t launch_fused4096_oq(int ifmt, float iscale, const void *in, size_t in_stride, int ofmt, float oscale, void *out, int nb_chunk, int R, int mbase,
-                               int nb_call, int64_t first_block, const float2 *tw, int ntab, const float2 *wins, const F4Row *rows, unsigned wcls, int teams,
-                               hipStream_t s);
-
-// fine tuning in the kernel's stores (fdc_fine.hpp): any input form (ifmt: kIqFloat = float2 in) and output form (ofmt: kIqFloat = float2 out), no waterfall rows;
-// fine_rows[8 waves][8 slots]: the increment and step-table start of each schedule row's channel, fine_step: the step table
+// One launch over a launch group.  Which form of the kernel it takes (fdc_fused4096.hip, for_f4_forms) follows from the formats, wf, fine_rows, teams and
+// wcls; hipErrorInvalidValue where there is none: an unknown format, wf together with integer samples or fine tuning, teams other than 1 or 2
 struct FineChan;
-hipError_t launch_fused4096_fine(int ifmt, float iscale, const void *in, size_t in_stride, int ofmt, float oscale, void *out, int nb_chunk, int R, int mbase,
-                                 int nb_call, int64_t first_block, const float2 *tw, int ntab, const float2 *wins, const F4Row *rows, unsigned wcls, int teams,
-                                 const FineChan *fine_rows, const float2 *fine_step, hipStream_t s);
+struct F4Launch {
+    const void *in;              // first sample of the launch group's first block; item m at in + m * in_stride samples
+    int ifmt; float iscale;      // kIqFloat (fdc_iq.hpp): in holds float2; kIqSc16 / kIqSc8: integer samples, widened times iscale in the kernel's loads
+    size_t in_stride;
+    void *out;                   // float2, or with ofmt = kIqSc16 / kIqSc8 the same sample offsets in narrow elements, narrowed times oscale in the stores (oq_bits)
+    int ofmt; float oscale;
+    int nb_chunk, R, mbase, nb_call;   // blocks of this launch, overlap, index of its first block in the call, blocks of the call
+    int64_t first_block;         // the stream's index of the call's block 0
+    const float2 *tw; int ntab;  // exp(-2 pi i k / ntab), ntab a multiple of 4096
+    const float2 *wins;
+    const F4Row *rows; unsigned wcls; int teams;   // the schedule; teams = blocks per workgroup: 1 (rows[4][8], no wide rows) or 2 (rows[8][8])
+    float *wf;                   // null, or nb_chunk x 1024 waterfall row sums (fdc_waterfall.hip): the ROWS form
+    const FineChan *fine_rows;   // null, or fine tuning in the stores (fdc_fine.hpp): [8 waves][8 slots] the increment and step-table start of each schedule
+    const float2 *fine_step;     //   row's channel, and the step table: the FINE forms
+    hipStream_t s;
+};
+hipError_t launch_fused4096(const F4Launch &a);
 
 // uniform plan (all channels l = 256, f = 256*slot, N = 256*N1): stage 1 + stage 2, no spectrum in memory.
 //   twq[n1][q] = W_N^(16*n1*q), cbt[n1][b] = (-1)^n1 W_N^(n1*b)  (16 entries per n1 each), shn[k2] = shape[k2]/N;
@@ -145,9 +147,13 @@ int poly_stage1_generic_tile_columns(int N, int L);
 // (fdc_block256.hip, fdc_block512.hip, fdc_block1024.hip, fdc_blocknarrow.hip; their shared core: fdc_blockcommon.hpp).
 // One launch of a bank's block kernel over a launch group: what every launcher below takes.
 struct BlockLaunch {
-    const float2 *in;            // first sample of the launch group's first block
+    // the samples: complex float (kIqFloat, fdc_iq.hpp), or for L = 256 complex integers (kIqSc16 / kIqSc8) that the kernel widens times iscale in its loads
+    // and narrows times oscale in its stores (out_bytes: the narrow extent; streamed stores only, hints bit 0).  The other widths take float only
+    const void *in;              // first sample of the launch group's first block
+    int ifmt; float iscale;
     size_t in_stride;            // samples from one block to the next
-    float2 *out;
+    void *out;
+    int ofmt; float oscale;
     int nb_chunk, mbase, nb_call;   // blocks of this launch, index of its first block in the call, blocks of the call
     const long long *slot_off;   // [N / L]: where each channel slot's samples go (negative: unused)
     unsigned out_bytes;          // whole output, < 4 GiB
@@ -165,6 +171,8 @@ struct BlockLaunch {
     const float2 *twl;           // L = 512: W_512^k, k < 256; L = 1024: W_1024^k, k < 1024
     const float2 *tab;           // L = 128 / 64: the table image of poly_block_narrow_tables()
 
+    const float2 *fin() const { return static_cast<const float2 *>(in); }   // float samples, as the kernels without integer forms take them
+    float2 *fout() const { return static_cast<float2 *>(out); }
     bool half() const { return r == L / 2; }                 // the bank half a channel off the grid: the on-grid kernels with their tables moved
     int grid(int per_cu = 1) const                           // one 512-thread workgroup per CU (or per_cu), never more than there are blocks
     {
@@ -173,14 +181,10 @@ struct BlockLaunch {
     }
 };
 
-// L = 256 (fdc_block256.hip): any offset r; cbt must hold (-1)^n1 W_N^(n1 (b + r))
+// L = 256 (fdc_block256.hip): any offset r; cbt must hold (-1)^n1 W_N^(n1 (b + r)).  Which form of the kernel a launch takes: for_blk256_forms there;
+// hipErrorInvalidValue where there is none
 hipError_t init_block_kernels();
 hipError_t launch_poly_block(const BlockLaunch &b);
-// the same on complex integer input (fmt: kIqSc16 / kIqSc8, fdc_iq.hpp; in_stride in samples), widened in the kernel's loads; b.in is not read
-hipError_t launch_poly_block_iq(const BlockLaunch &b, int fmt, float scale, const void *in);
-// integer OUTPUT (ofmt: kIqSc16 / kIqSc8 with its scale; b.out_bytes: the narrow extent), narrowed in the kernel's stores, on input ifmt (kIqFloat: float2,
-// or kIqSc16 / kIqSc8 with iscale); streamed stores only (hints bit 0 set); b.in and b.out are not read
-hipError_t launch_poly_block_oq(const BlockLaunch &b, int ifmt, float iscale, const void *in, int ofmt, float oscale, void *out);
 bool poly_block_supports(int N);
 
 // L = 512 on the 512-bin grid or half a channel off it (fdc_block512.hip): the two parities of a column's 512 rows run the 256-point machinery side by
@@ -215,7 +219,7 @@ hipError_t launch_block_fft(int N, const float2 *in, size_t in_stride, float2 *o
                             const long long *slot_off /* [N / 256]: 256 c */, float2 *scratch /* ncu x 32768 points */,
                             int ncu, int hints, hipStream_t s,
                             hipEvent_t *ev /* null or 3: start, end, end */,
-                            const unsigned *keep = nullptr /* [N / 8192][4] words: 64-bin stores some channel reads (fdc_api.hip), or all */,
+                            const unsigned *keep = nullptr /* [N / 8192][4] words: 64-bin stores some channel reads (fdc_plan.hip), or all */,
                             float *gpow = nullptr /* nitems x N / 16 floats: the power of every 16-bin group of the spectrum, summed in the epilogue */);
 // the sinks' power cells from those group sums + the bins of the groups a cell cuts; the group sums of a spectrum in memory (launch groups the block kernel did not transform)
 hipError_t launch_cell_power_groups(const float2 *spec, const float *gpow, int N, const PowerCell *cells, int ncells, int nblocks, float *out, hipStream_t s);

@@ -994,10 +994,12 @@ hipError_t launch_iq_to_complex(int fmt, float scale, const void *in, float2 *ou
 {
     if (!n) return hipSuccess;
     size_t g = (n + 255) / 256; if (g > 8192) g = 8192;
-    if (fmt == kIqSc16) hipLaunchKernelGGL(k_iq_to_complex<sc16>, dim3((unsigned)g), dim3(256), 0, s, static_cast<const sc16 *>(in), out, n, scale);
-    else if (fmt == kIqSc8) hipLaunchKernelGGL(k_iq_to_complex<sc8>, dim3((unsigned)g), dim3(256), 0, s, static_cast<const sc8 *>(in), out, n, scale);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
+    hipError_t e = hipErrorInvalidValue;                        // stays if fmt is no integer format
+    for_int_samples(fmt, [&](auto t) {
+        hipLaunchKernelGGL(k_iq_to_complex<decltype(t)>, dim3((unsigned)g), dim3(256), 0, s, static_cast<const decltype(t) *>(in), out, n, scale);
+        e = hipGetLastError();
+    });
+    return e;
 }
 
 // registered outputs with integer output: k_scatter_out's layout; TS = float2 narrows on the way (the caller's mapped buffer receives the narrow bytes
@@ -1033,9 +1035,9 @@ hipError_t launch_scatter_oq(int src_fmt, const void *src, int ofmt, float scale
 {
     if (nchan <= 0 || nb <= 0) return hipSuccess;
     if (src_fmt != kIqFloat && src_fmt != ofmt) return hipErrorInvalidValue;
-    if (ofmt == kIqSc16) return scatter_oq_to<sc16>(src_fmt, src, scale, tab, nchan, nb, row0, s);
-    if (ofmt == kIqSc8) return scatter_oq_to<sc8>(src_fmt, src, scale, tab, nchan, nb, row0, s);
-    return hipErrorInvalidValue;
+    hipError_t e = hipErrorInvalidValue;
+    for_int_samples(ofmt, [&](auto t) { e = scatter_oq_to<decltype(t)>(src_fmt, src, scale, tab, nchan, nb, row0, s); });
+    return e;
 }
 
 hipError_t launch_scale(const float2 *in, float2 *out, size_t n, float k, hipStream_t s)

@@ -48,10 +48,12 @@ hipError_t launch_complex_to_iq(int fmt, float scale, const float2 *in, void *ou
 {
     if (!n) return hipSuccess;
     size_t g = (n + 255) / 256; if (g > 8192) g = 8192;
-    if (fmt == kIqSc16) hipLaunchKernelGGL(k_complex_to_iq<sc16>, dim3((unsigned)g), dim3(256), 0, s, in, static_cast<sc16 *>(out), n, scale);
-    else if (fmt == kIqSc8) hipLaunchKernelGGL(k_complex_to_iq<sc8>, dim3((unsigned)g), dim3(256), 0, s, in, static_cast<sc8 *>(out), n, scale);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
+    hipError_t e = hipErrorInvalidValue;                        // stays if fmt is no integer format
+    for_int_samples(fmt, [&](auto t) {
+        hipLaunchKernelGGL(k_complex_to_iq<decltype(t)>, dim3((unsigned)g), dim3(256), 0, s, in, static_cast<decltype(t) *>(out), n, scale);
+        e = hipGetLastError();
+    });
+    return e;
 }
 
 // Channel levels (fdc_pipeline_set_levels): power = sum of re^2 + im^2 and peak = max of |re|, |im| (fmax: a NaN component is passed over) of one row.
@@ -345,15 +347,11 @@ hipError_t launch_chan_gain(float2 *out, const ChanDev *chans, const float *gain
     if (fmt != kIqFloat && !nar) return hipErrorInvalidValue;
     return channel_grids(nchan, nb_chunk, [&](dim3 grid, int c0) {
         with_bool(levels != nullptr, [&](auto lv) {
-            auto to = [&](auto *n) {
-                hipLaunchKernelGGL((k_chan_gain<decltype(lv)::value, std::remove_pointer_t<decltype(n)>>), grid, dim3(256), 0, s, out, chans, gain, n, scale, levels,
-                                   c0, nchan, nb_chunk, mbase, (long long)nb_call);
-            };
-            switch (fmt) {
-            case kIqSc16: to(static_cast<sc16 *>(nar)); break;
-            case kIqSc8: to(static_cast<sc8 *>(nar)); break;
-            default: to(static_cast<float2 *>(nullptr));
-            }
+            for_samples(fmt, [&](auto t) {                      // float2: in place, no narrow output
+                constexpr bool kNarrow = !std::is_same<decltype(t), float2>::value;
+                hipLaunchKernelGGL((k_chan_gain<decltype(lv)::value, decltype(t)>), grid, dim3(256), 0, s, out, chans, gain,
+                                   static_cast<decltype(t) *>(kNarrow ? nar : nullptr), scale, levels, c0, nchan, nb_chunk, mbase, (long long)nb_call);
+            });
         });
     });
 }

@@ -1083,12 +1083,12 @@ hipError_t launch_carry_copy_narrow(int fmt, float scale, const SinkOwner *owner
 {
     if (nowner_max <= 0 || !prev) return hipSuccess;
     const dim3 grid((unsigned)nowner_max, (unsigned)(nseg + 1), kCarrySplit);
-    if (fmt == kIqSc16)
-        hipLaunchKernelGGL(k_carry_copy_narrow<sc16>, grid, dim3(256), 0, s, owners, owner_base, nowner, npac, prev, cur, static_cast<sc16 *>(ncur), scale);
-    else if (fmt == kIqSc8)
-        hipLaunchKernelGGL(k_carry_copy_narrow<sc8>, grid, dim3(256), 0, s, owners, owner_base, nowner, npac, prev, cur, static_cast<sc8 *>(ncur), scale);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
+    hipError_t e = hipErrorInvalidValue;                        // stays if fmt is no integer format
+    for_int_samples(fmt, [&](auto t) {
+        hipLaunchKernelGGL(k_carry_copy_narrow<decltype(t)>, grid, dim3(256), 0, s, owners, owner_base, nowner, npac, prev, cur, static_cast<decltype(t) *>(ncur), scale);
+        e = hipGetLastError();
+    });
+    return e;
 }
 
 hipError_t init_sink_kernels()

@@ -3,7 +3,7 @@
 
     tools/compare_block_isa.py [--files A,B,...] [--new-files C,D,...] [BASE [NEW]]
         BASE: a commit (default HEAD); NEW: a commit, or the working tree when left out
-        --files: the .hip files of gr-fdc_amd/csrc to compile, without the suffix (default: the four one-block-per-CU kernel files);
+        --files: the .hip files of gr-fdc_amd/csrc to compile, without the suffix (default: the four one-block-per-CU kernel files and fdc_fused4096);
         --new-files: those of the NEW side where they differ — a kernel that moved between files is matched by its symbol
 
 Compiles the files of both sides for the device only (the Makefile's flags plus --cuda-device-only -S) and compares every kernel by symbol:
@@ -19,17 +19,18 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = "gr-fdc_amd/csrc"
-FILES = ["fdc_block256", "fdc_block512", "fdc_block1024", "fdc_blocknarrow"]
+FILES = ["fdc_block256", "fdc_block512", "fdc_block1024", "fdc_blocknarrow", "fdc_fused4096"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=" + os.environ.get("ARCH", "gfx950"), "-Wall", "-Wno-unused-result",
          "--cuda-device-only", "-S"]
 
 
 def compile_side(rev, files, tmp):
-    """{file: assembly text} of one side; rev None = the working tree"""
+    """{file: assembly text} of one side, compiled in tmp (a directory of this side's own: BASE and NEW may be the same commit); rev None = the working tree"""
     src = os.path.join(ROOT, CSRC)
+    os.makedirs(tmp)
     if rev is not None:
-        top = os.path.join(tmp, "src_" + rev.replace("/", "_"))
+        top = os.path.join(tmp, "src")
         os.makedirs(top)
         tar = subprocess.Popen(["git", "-C", ROOT, "archive", rev, CSRC, "include"], stdout=subprocess.PIPE)
         subprocess.check_call(["tar", "-x", "-C", top], stdin=tar.stdout)
@@ -39,7 +40,7 @@ def compile_side(rev, files, tmp):
     out = {}
     procs = []
     for f in files:
-        s = os.path.join(tmp, "%s_%s.s" % (f, (rev or "worktree").replace("/", "_")))
+        s = os.path.join(tmp, f + ".s")
         procs.append((f, s, subprocess.Popen([HIPCC] + FLAGS + [f + ".hip", "-o", s], cwd=src, stderr=subprocess.PIPE, text=True)))
     for f, s, p in procs:
         err = p.communicate()[1]
@@ -109,7 +110,7 @@ def main():
     fa = a.files.split(",")
     fb = (a.new_files or a.files).split(",")
     with tempfile.TemporaryDirectory() as tmp:
-        ka, kb = pooled(compile_side(a.base, fa, tmp)), pooled(compile_side(a.new, fb, tmp))
+        ka, kb = pooled(compile_side(a.base, fa, os.path.join(tmp, "base"))), pooled(compile_side(a.new, fb, os.path.join(tmp, "new")))
     print("%s %s --cuda-device-only -S; %s (%s) vs %s (%s)" % (os.path.basename(HIPCC), " ".join(FLAGS[:-2]), a.base, " ".join(fa),
                                                              a.new or "the working tree", " ".join(fb)))
     bad = False
