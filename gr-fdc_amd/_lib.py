@@ -105,6 +105,11 @@ SYMBOLS = {
     "fdc_pipeline_levels_device": (_vp, [_vp]),
     "fdc_pipeline_group_set_levels": (C.c_int, [_vp, C.c_int32]),
     "fdc_pipeline_group_levels": (C.c_int, [_vp, C.POINTER(C.c_float), C.c_int]),
+    "fdc_pipeline_set_lag1": (C.c_int, [_vp, C.c_int32]),
+    "fdc_pipeline_lag1": (C.c_int, [_vp, C.POINTER(C.c_float), C.c_int]),
+    "fdc_pipeline_lag1_device": (_vp, [_vp]),
+    "fdc_pipeline_group_set_lag1": (C.c_int, [_vp, C.c_int32]),
+    "fdc_pipeline_group_lag1": (C.c_int, [_vp, C.POINTER(C.c_float), C.c_int]),
     "fdc_pipeline_set_gains": (C.c_int, [_vp, C.POINTER(C.c_float), C.c_int]),
     "fdc_pipeline_gains": (C.c_int, [_vp, C.POINTER(C.c_float), C.c_int]),
     "fdc_pipeline_group_set_gains": (C.c_int, [_vp, C.POINTER(C.c_float), C.c_int]),

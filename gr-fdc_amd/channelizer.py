@@ -295,6 +295,26 @@ def _levels(fn, handle, nchan, last_nb, nblocks):
     return out
 
 
+def _lag1(fn, handle, nchan, last_nb, nblocks):
+    """The lag-1 correlation of the last work call as complex64[nblocks, C] (fdc_pipeline_lag1 / fdc_pipeline_group_lag1)."""
+    if nblocks is None:
+        if last_nb is None:
+            raise ValueError("lag1(): no work call yet")
+        nblocks = last_nb
+    nblocks = int(nblocks)
+    if nblocks < 0:
+        raise ValueError("lag1(): negative block count")
+    out = np.empty((nblocks, nchan), dtype=np.complex64)
+    _lib.check(fn(handle, out.ctypes.data_as(C.POINTER(C.c_float)), nblocks))
+    return out
+
+
+def lag1_frequency(s):
+    """The mean frequency a lag-1 correlation S (Pipeline.lag1, any shape) stands for: angle(S) / (2 pi) as float64, in cycles per output sample —
+    the unit of set_fine_tuning, so adding it to the nu in force cancels the residual.  S = 0 gives 0."""
+    return np.angle(np.asarray(s, dtype=np.complex128)) / (2.0 * np.pi)
+
+
 class Pipeline(_OutputFormat):
     """fdc_pipeline handle: channels = [(f, l, passbw, stopbw), ...]."""
     _last_nb = None        # block count of the last work call that had blocks (levels())
@@ -376,6 +396,23 @@ class Pipeline(_OutputFormat):
     def levels_device(self):
         """fdc_pipeline_levels_device: the device address of the levels ([block][C] float2), None while levels are off."""
         return _lib.lib().fdc_pipeline_levels_device(self._h)
+
+    def set_lag1(self, on=True):
+        """fdc_pipeline_set_lag1: with it on, every call also sums, on the device, S = sum_j y[j] conj(y[j - 1]) over the samples of each (block,
+        channel) row of the complex64 samples it writes — after fine tuning and the gain, before the sc16 / sc8 narrowing; the product across the
+        block boundary is not taken.  lag1_frequency(S) is the row's mean frequency in the unit of set_fine_tuning (the measurement of an AFC).  A
+        setting like set_levels: it applies from the next call and survives reset(); the sink, spectrum-item, group-power and waterfall entries are
+        refused while it is on."""
+        _lib.check(_lib.lib().fdc_pipeline_set_lag1(self._h, int(bool(on))))
+
+    def lag1(self, nblocks=None):
+        """fdc_pipeline_lag1: complex64[nblocks of the last call, C], [m, c] = S of block m of channel c.  nblocks: the last call's block count
+        where it did not go through this object's work methods (process_device, work_raw)."""
+        return _lag1(_lib.lib().fdc_pipeline_lag1, self._h, len(self.channels), self._last_nb, nblocks)
+
+    def lag1_device(self):
+        """fdc_pipeline_lag1_device: the device address of the lag-1 correlation ([block][C] float2), None while it is off."""
+        return _lib.lib().fdc_pipeline_lag1_device(self._h)
 
     def _ran(self, nb):
         self._call_nb = int(nb)
@@ -627,6 +664,14 @@ class PipelineGroup(_OutputFormat):
         """fdc_pipeline_group_levels: Pipeline.levels of the last group call, the members' spans put together in block order."""
         return _levels(_lib.lib().fdc_pipeline_group_levels, self._h, len(self.channels), self._last_nb, nblocks)
 
+    def set_lag1(self, on=True):
+        """fdc_pipeline_group_set_lag1: Pipeline.set_lag1 for every member."""
+        _lib.check(_lib.lib().fdc_pipeline_group_set_lag1(self._h, int(bool(on))))
+
+    def lag1(self, nblocks=None):
+        """fdc_pipeline_group_lag1: Pipeline.lag1 of the last group call, the members' spans put together in block order."""
+        return _lag1(_lib.lib().fdc_pipeline_group_lag1, self._h, len(self.channels), self._last_nb, nblocks)
+
     def _run(self, fn, x, nb, want_spectrum, outs):
         outs = self._check_outs(outs, nb)
         ptrs = (C.c_void_p * max(1, len(outs)))(*[o.ctypes.data for o in outs])
@@ -717,7 +762,7 @@ class FrequencyDomainChannelizer:
                  pow_act_deactivation_delay,
                  pow_act_maxblocks, act_det_maxblocks,
                  debug, device_id=0, max_blocks=64, devices=None, pipelined=False, waterfall=None, iq_input=None, iq_scale=1.0,
-                 iq_output=None, iq_output_scale=1.0, fine_tuning=False, *, payload_format=None, payload_scale=1.0, levels=False, gains=None):
+                 iq_output=None, iq_output_scale=1.0, fine_tuning=False, *, payload_format=None, payload_scale=1.0, levels=False, gains=None, lag1=False):
         # pipelined (not an argument of the reference): the sink blocks run beside the front end of the FOLLOWING work() calls, as the
         # thread-per-block scheduler runs them beside the FFT in the reference (fdc_pipeline_work_sinks on a look-ahead bank,
         # include/fdc_amd.h): same PDUs, handed out one or two work() calls later; flush() at the end of the stream
@@ -823,6 +868,18 @@ class FrequencyDomainChannelizer:
             if waterfall is not None:
                 raise ValueError("levels cannot go with a waterfall")
 
+        # lag1 (not an argument of the reference): after every work() self.lag1 is complex64[items, throughput channels], the lag-1 correlation of every
+        # block of every port as the device summed it (Pipeline.set_lag1): of the float samples, after fine tuning and the gain, before iq_output narrows
+        self.lag1_on = bool(lag1)
+        self.lag1 = None
+        if self.lag1_on:
+            if self.inpveclen != 1:
+                raise ValueError("lag1 needs inpveclen 1: the pre-transformed item entry gives no channel lag-1 correlation")
+            if activity_controlled_channels or activity_detection_segments:
+                raise ValueError("lag1 cannot go with activity-controlled channels or detection segments")
+            if waterfall is not None:
+                raise ValueError("lag1 cannot go with a waterfall")
+
         # gains (not an argument of the reference): one output gain per throughput channel, applied on the device behind fine tuning and in front of the
         # levels and of iq_output's narrowing (Pipeline.set_gains); set_gains() changes them between work() calls (an AGC fed from self.levels)
         self.gains = None if gains is None else _check_gains(len(self.throughput_channels), gains)
@@ -893,6 +950,8 @@ class FrequencyDomainChannelizer:
             self.pipeline.set_levels(True)
         if self.gains is not None:
             self.pipeline.set_gains(self.gains)
+        if self.lag1_on:
+            self.pipeline.set_lag1(True)
         self.N_throughput_channelizers = len(self.channel_params)
         # waterfall (not an argument of the reference, whose example flowgraph wires the spectrum to complex_to_mag_squared and
         # FDC.WaterfallMsgTagging outside the hier block): a gr_fdc_amd.Waterfall fed from the spectrum on the device; work() then
@@ -969,6 +1028,8 @@ class FrequencyDomainChannelizer:
         if self.levels_on:
             # (a call without items leaves the handle's previous result in place: this call's array is empty)
             self.levels = self.pipeline.levels() if self.pipeline._call_nb > 0 else np.empty((0, len(self.channel_params), 2), dtype=np.float32)
+        if self.lag1_on:
+            self.lag1 = self.pipeline.lag1() if self.pipeline._call_nb > 0 else np.empty((0, len(self.channel_params)), dtype=np.complex64)
         if self.debug:
             outs, spec = res
             return [spec] + outs

@@ -410,6 +410,7 @@ int32_t fdc_pipeline_describe(const fdc_pipeline *p, char *buf, int32_t n)
     if (!p->fine_route.empty()) add("; fine tuning: %s", p->fine_route.c_str());
     if (!p->levels_route.empty()) add("; levels: %s", p->levels_route.c_str());
     if (!p->gains_route.empty()) add("; gains: %s", p->gains_route.c_str());
+    if (!p->lag1_route.empty()) add("; lag1: %s", p->lag1_route.c_str());
     std::snprintf(buf, (size_t)n, "%s", t);
     return k;
 }
@@ -482,6 +483,7 @@ void fdc_pipeline_reset(fdc_pipeline *p)
     p->fine_route.clear();       // (and so does fine tuning)
     p->levels_route.clear();     // (and so do the channel levels)
     p->gains_route.clear();      // (and the channel gains)
+    p->lag1_route.clear();       // (and the channel lag-1 correlation)
 }
 
 int fdc_pipeline_set_output_format(fdc_pipeline *p, int32_t format, float scale)
@@ -597,6 +599,48 @@ int fdc_pipeline_levels(fdc_pipeline *p, float *dst, int nblocks)
     FDC_ENTRY_END
 }
 
+// the channel lag-1 correlation: the levels' setting and reader, word for word, on a buffer pair of its own
+int fdc_pipeline_set_lag1(fdc_pipeline *p, int32_t on)
+{
+    FDC_ENTRY("fdc_pipeline_set_lag1")
+    if (!p) return set_error(FDC_ERR_INVALID_ARGUMENT, "null handle");
+    if (p->hier_filled > 0)
+        return set_error(FDC_ERR_INVALID_ARGUMENT, "a pipelined sinks batch is still inside the handle: fdc_pipeline_flush_sinks until it returns 0 first");
+    HIPCHK(hipSetDevice(p->cfg.device_id));
+    HIPCHK(hipStreamSynchronize(p->stream));          // (no call of the host entries is in flight; a device entry's caller orders its own stream)
+    if (!on) { p->lag1_on = false; p->lag1_route.clear(); return FDC_OK; }
+    // everything the feature needs, once: one complex sum per block of the longest call and channel, on the device and pinned on the host
+    const size_t n = (size_t)p->cfg.max_blocks * (size_t)p->C;
+    if (n > 0 && !p->d_lag1) HIPCHK(p->d_lag1.alloc(n));
+    if (n > 0 && !p->pin_lag1) HIPCHK(p->pin_lag1.alloc(n));
+    if (!p->lag1_on) p->lag_blocks = -1;              // switched on: no call has a result yet
+    p->lag1_on = true;
+    return FDC_OK;
+    FDC_ENTRY_END
+}
+
+int fdc_pipeline_lag1(fdc_pipeline *p, float *dst, int nblocks)
+{
+    FDC_ENTRY("fdc_pipeline_lag1")
+    if (!p) return set_error(FDC_ERR_INVALID_ARGUMENT, "null handle");
+    if (!p->lag1_on) return set_error(FDC_ERR_INVALID_ARGUMENT, "the channel lag-1 correlation is off (fdc_pipeline_set_lag1)");
+    if (p->lag_blocks < 0) return set_error(FDC_ERR_INVALID_ARGUMENT, "no work call has run since the channel lag-1 correlation was switched on");
+    if (nblocks != p->lag_blocks) return set_error(FDC_ERR_INVALID_ARGUMENT, "the last work call had %d blocks, not %d", p->lag_blocks, nblocks);
+    const size_t n = (size_t)nblocks * (size_t)p->C;
+    if (n == 0) return FDC_OK;
+    if (!dst) return set_error(FDC_ERR_INVALID_ARGUMENT, "null argument");
+    if (!p->lag_host) {
+        // a device entry's result: read behind everything enqueued so far on the stream it ran on
+        HIPCHK(hipSetDevice(p->cfg.device_id));
+        HIPCHK(hipMemcpyAsync(p->pin_lag1.get(), p->d_lag1.get(), sizeof(float2) * n, hipMemcpyDeviceToHost, p->lag_stream));
+        HIPCHK(hipStreamSynchronize(p->lag_stream));
+        p->lag_host = true;
+    }
+    std::memcpy(dst, p->pin_lag1.get(), sizeof(float2) * n);
+    return FDC_OK;
+    FDC_ENTRY_END
+}
+
 int fdc_pipeline_set_gains(fdc_pipeline *p, const float *gain, int n)
 {
     FDC_ENTRY("fdc_pipeline_set_gains")
@@ -632,6 +676,8 @@ int fdc_pipeline_gains(const fdc_pipeline *p, float *dst, int n)
     return FDC_OK;
     FDC_ENTRY_END
 }
+
+void *fdc_pipeline_lag1_device(fdc_pipeline *p) { return p && p->lag1_on ? static_cast<void *>(p->d_lag1.get()) : nullptr; }
 
 void *fdc_pipeline_levels_device(fdc_pipeline *p) { return p && p->levels_on ? static_cast<void *>(p->d_levels.get()) : nullptr; }
 

@@ -137,11 +137,12 @@ static bool iq_fused(const fdc_pipeline *p, const DeviceCall &call, bool few)
 static bool path5(const fdc_pipeline *p, const DeviceCall &call) { return p->fused && !call.spectrum; }
 
 // THE RULE of the passes behind a plan's kernels (fdc_postpass.hip), on which oq_fused and PostPass both rest: they go over the kernels' complex
-// float results in the order rotation -> gain -> levels -> narrowing.  Path 5 turns its samples in its own stores; every other kernel leaves
+// float results in the order rotation -> gain -> levels, lag-1 -> narrowing.  Path 5 turns its samples in its own stores; every other kernel leaves
 // fine tuning to the rotation pass.  The levels are of the float samples the caller gets (turned and gained), and the gain multiplies float samples.
-// So a call with a rotation pass, gains or levels has its kernels store float, and narrows behind the last of them.
+// The lag-1 correlation is of the same samples as the levels.
+// So a call with a rotation pass, gains, levels or lag-1 has its kernels store float, and narrows behind the last of them.
 static bool rotation_pass(const fdc_pipeline *p, const DeviceCall &call) { return p->fine_on && !path5(p, call); }
-static bool float_passes(const fdc_pipeline *p, const DeviceCall &call) { return rotation_pass(p, call) || call.gain || call.levels; }
+static bool float_passes(const fdc_pipeline *p, const DeviceCall &call) { return rotation_pass(p, call) || call.gain || call.levels || call.lag1; }
 
 // integer output: whether EVERY launch group of a call of nblocks narrows in its own kernel's stores (k_blk256: streamed stores; not N = 65536 at R = 4
 // on float input, whose forms would spill: fdc_block256.hip kOqR4Narrowed); otherwise the call writes complex float and k_complex_to_iq narrows it
@@ -170,6 +171,7 @@ struct PostPass {
     bool narrow_tail = false;   // the call-wide k_complex_to_iq from the float staging
     const float *gain = nullptr;
     float2 *levels = nullptr;
+    float2 *lag1 = nullptr;     // k_chan_lag1, always a pass of its own over the group's final float results: lag-1 on
 };
 
 static PostPass post_pass(const fdc_pipeline *p, const DeviceCall &call, bool ofused)
@@ -177,7 +179,7 @@ static PostPass post_pass(const fdc_pipeline *p, const DeviceCall &call, bool of
     PostPass pp;
     if (p->C <= 0) return pp;
     const bool narrow = call.ofmt && !ofused && call.narrow;
-    pp.gain = call.gain; pp.levels = call.levels;
+    pp.gain = call.gain; pp.levels = call.levels; pp.lag1 = call.lag1;
     pp.fine_fused = p->fine_on && path5(p, call);
     pp.rotate = rotation_pass(p, call);
     pp.rot_gain = pp.rotate && pp.gain;
@@ -200,6 +202,8 @@ static int run_post_passes(const fdc_pipeline *p, const DeviceCall &call, const 
         HIPCHK(fdc::launch_chan_gain(o, p->d_chans, pp.gain, pp.levels, pp.gain_narrows ? call.ofmt : 0, call.oscale, pp.gain_narrows ? d_out : nullptr, p->C, g.nb,
                                      g.m0, g.nblocks, s));
     if (pp.levels_pass) HIPCHK(fdc::launch_chan_levels(o, p->d_chans, pp.levels, p->C, g.nb, g.m0, g.nblocks, s));
+    // (the narrowing gain pass has left o as it was cut: the lag-1 pass multiplies what it reads, which gives the bits of the gained samples)
+    if (pp.lag1) HIPCHK(fdc::launch_chan_lag1(o, p->d_chans, pp.gain_narrows ? pp.gain : nullptr, pp.lag1, p->C, g.nb, g.m0, g.nblocks, s));
     return FDC_OK;
 }
 
@@ -209,6 +213,7 @@ static int run_post_tail(fdc_pipeline *p, const DeviceCall &call, const PostPass
     if (pp.narrow_tail) HIPCHK(fdc::launch_complex_to_iq(call.ofmt, call.oscale, call.fout, d_out, (size_t)nblocks * p->sum_lout, call.stream));
     if (pp.fine_fused || pp.rotate) p->fine_route = pp.fine_fused ? "fused" : "rotated";
     if (pp.levels) p->levels_route = pp.rot_levels ? "with the rotation" : pp.gain_pass ? "with the gains" : "pass";
+    if (pp.lag1) p->lag1_route = "pass";
     if (pp.gain) p->gains_route = pp.rot_gain ? "with the rotation" : pp.gain_narrows ? "with the narrowing" : "pass";
     return FDC_OK;
 }
@@ -372,6 +377,11 @@ void levels_written(fdc_pipeline *p, int nblocks, hipStream_t stream, bool host)
     p->lev_blocks = nblocks; p->lev_stream = stream; p->lev_host = host;
 }
 
+void lag1_written(fdc_pipeline *p, int nblocks, hipStream_t stream, bool host)
+{
+    p->lag_blocks = nblocks; p->lag_stream = stream; p->lag_host = host;
+}
+
 // how the last integer-input / integer-output call was served (fdc_pipeline_describe): "<sc16|sc8>: fused", or what it was instead
 std::string route(int fmt, bool fused, const char *otherwise)
 {
@@ -381,7 +391,7 @@ std::string route(int fmt, bool fused, const char *otherwise)
 // The device entries with the handle's output format: integer output needs the float staging (p->d_out, max_blocks*sum_lout samples, allocated by
 // fdc_pipeline_set_output_format, never on this enqueue path) where the call's kernels do not narrow themselves
 // Channel levels (p->levels_on): the call's levels go to the handle's buffer ([max_blocks][C], allocated by fdc_pipeline_set_levels), so such a call
-// needs nblocks <= max_blocks too; nothing is enqueued otherwise
+// needs nblocks <= max_blocks too; nothing is enqueued otherwise.  The channel lag-1 correlation (p->lag1_on, d_lag1) likewise
 static int process_device_oq(fdc_pipeline *p, DeviceCall &call, const void *d_ring, int64_t first_block, int nblocks, void *d_out)
 {
     const int ofmt = p->out_form;
@@ -389,6 +399,11 @@ static int process_device_oq(fdc_pipeline *p, DeviceCall &call, const void *d_ri
     if (lev) {
         if (nblocks > p->cfg.max_blocks) return set_error(FDC_ERR_INVALID_ARGUMENT, "channel levels: nblocks %d above max_blocks %d", nblocks, p->cfg.max_blocks);
         call.levels = p->d_levels;
+    }
+    const bool lag = p->lag1_on && nblocks > 0;
+    if (lag) {
+        if (nblocks > p->cfg.max_blocks) return set_error(FDC_ERR_INVALID_ARGUMENT, "channel lag-1 correlation: nblocks %d above max_blocks %d", nblocks, p->cfg.max_blocks);
+        call.lag1 = p->d_lag1;
     }
     if (ofmt && nblocks > 0) {
         call.ofmt = ofmt; call.oscale = p->out_scale; call.fout = p->d_out;
@@ -401,6 +416,7 @@ static int process_device_oq(fdc_pipeline *p, DeviceCall &call, const void *d_ri
     const int rc = process_device_impl(p, call, d_ring, first_block, nblocks, d_out);
     if (rc == FDC_OK && ofmt && nblocks > 0) p->oq_route = route(ofmt, call.ofused, "narrowed");
     if (rc == FDC_OK && lev) levels_written(p, nblocks, call.stream, false);
+    if (rc == FDC_OK && lag) lag1_written(p, nblocks, call.stream, false);
     return rc;
 }
 
@@ -458,6 +474,7 @@ int fdc_pipeline_process_device_power(fdc_pipeline *p, const void *d_ring, int64
     if (p->out_form) return set_error(FDC_ERR_INVALID_ARGUMENT, "fdc_pipeline_process_device_power writes complex float outputs only (the handle's output format is not FC32)");
     if (p->fine_on) return set_error(FDC_ERR_INVALID_ARGUMENT, "fdc_pipeline_process_device_power writes the channels as they are cut: switch fine tuning off first");
     if (p->levels_on) return set_error(FDC_ERR_INVALID_ARGUMENT, "fdc_pipeline_process_device_power gives no channel levels: switch them off first (fdc_pipeline_set_levels(p, 0))");
+    if (p->lag1_on) return set_error(FDC_ERR_INVALID_ARGUMENT, "fdc_pipeline_process_device_power gives no channel lag-1 correlation: switch it off first (fdc_pipeline_set_lag1(p, 0))");
     if (p->gains_on) return set_error(FDC_ERR_INVALID_ARGUMENT, "fdc_pipeline_process_device_power writes the channels as they are cut: switch the channel gains off first (fdc_pipeline_set_gains(p, NULL, C))");
     if (d_group_power && (!d_spectrum || (p->N & 15))) return set_error(FDC_ERR_INVALID_ARGUMENT, "group powers go with a spectrum output of a block length that is a multiple of 16");
     DeviceCall call = device_call(p, stream, d_spectrum);

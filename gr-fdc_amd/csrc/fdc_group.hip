@@ -423,6 +423,39 @@ int fdc_pipeline_group_levels(fdc_pipeline_group *g, float *dst, int nblocks)
     FDC_ENTRY_END
 }
 
+int fdc_pipeline_group_set_lag1(fdc_pipeline_group *g, int32_t on)
+{
+    FDC_ENTRY("fdc_pipeline_group_set_lag1")
+    if (!g) return fdc::set_error(FDC_ERR_INVALID_ARGUMENT, "null group handle");
+    // every member takes the same argument: the first refuses what all would refuse, before any has changed
+    for (fdc_pipeline *p : g->mem) {
+        const int rc = fdc_pipeline_set_lag1(p, on);
+        if (rc != FDC_OK) return rc;
+    }
+    return FDC_OK;
+    FDC_ENTRY_END
+}
+
+// the lag-1 correlation of the last group call: the members' spans put together in block order, as the levels
+int fdc_pipeline_group_lag1(fdc_pipeline_group *g, float *dst, int nblocks)
+{
+    FDC_ENTRY("fdc_pipeline_group_lag1")
+    if (!g) return fdc::set_error(FDC_ERR_INVALID_ARGUMENT, "null group handle");
+    int total = 0;
+    for (int32_t n : g->last_n) total += n;
+    if (g->last_n.empty() || total == 0) return fdc::set_error(FDC_ERR_INVALID_ARGUMENT, "no group call has run yet");
+    if (nblocks != total) return fdc::set_error(FDC_ERR_INVALID_ARGUMENT, "the last group call had %d blocks, not %d", total, nblocks);
+    if (!dst && g->C > 0) return fdc::set_error(FDC_ERR_INVALID_ARGUMENT, "null argument");
+    const int64_t first = g->last_first[0];
+    for (size_t i = 0; i < g->mem.size(); i++) {
+        if (g->last_n[i] == 0) continue;
+        const int rc = fdc_pipeline_lag1(g->mem[i], dst + (size_t)(g->last_first[i] - first) * (size_t)g->C * 2, g->last_n[i]);
+        if (rc != FDC_OK) return rc;
+    }
+    return FDC_OK;
+    FDC_ENTRY_END
+}
+
 int32_t fdc_pipeline_group_size(const fdc_pipeline_group *g) { return g ? (int32_t)g->mem.size() : -1; }
 fdc_pipeline *fdc_pipeline_group_member(fdc_pipeline_group *g, int i)
 {

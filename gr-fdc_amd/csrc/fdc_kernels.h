@@ -251,6 +251,12 @@ hipError_t launch_chan_levels(const float2 *out, const ChanDev *chans, float2 *l
 hipError_t launch_chan_gain(float2 *out, const ChanDev *chans, const float *gain, float2 *levels, int fmt, float scale, void *nar, int nchan, int nb_chunk,
                             int mbase, int nb_call, hipStream_t s);
 
+// Channel lag-1 correlation (fdc_pipeline_set_lag1): blocks [mbase, mbase + nb_chunk) of a call's channel-major float results read once;
+// lag1[(mbase + m) * nchan + c] = sum over j >= 1 of y[j] conj(y[j - 1]) over the lout_c samples of block m of channel c.  One summation order per lout
+// (fdc_postpass.hip).  gain (null: none): the samples times gain[c] first, where the gain pass in front has left the float results as they were cut
+hipError_t launch_chan_lag1(const float2 *out, const ChanDev *chans, const float *gain, float2 *lag1, int nchan, int nb_chunk, int mbase, int nb_call,
+                            hipStream_t s);
+
 hipError_t launch_scale(const float2 *in, float2 *out, size_t n, float k, hipStream_t s);
 
 // sinks

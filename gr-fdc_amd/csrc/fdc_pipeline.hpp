@@ -174,6 +174,15 @@ struct fdc_pipeline {
     bool lev_host = false;
     hipStream_t lev_stream = nullptr;
     std::string levels_route;    // how the last call with levels was served (fdc_pipeline_describe)
+    // channel lag-1 correlation (fdc_pipeline_set_lag1): a setting, with the levels' state.  d_lag1: [max_blocks][C] (Re S, Im S) of the last call; pin_lag1
+    // its pinned twin (lag_host, lag_stream as lev_host, lev_stream).  Both are allocated by the first call that switches the setting on.
+    bool lag1_on = false;
+    fdc::DevBuf<float2> d_lag1;
+    fdc::PinBuf<float2> pin_lag1;
+    int lag_blocks = -1;         // block count of the last successful work call with lag-1 on (-1: none yet)
+    bool lag_host = false;
+    hipStream_t lag_stream = nullptr;
+    std::string lag1_route;      // how the last call with lag-1 was served (fdc_pipeline_describe)
     // channel gains (fdc_pipeline_set_gains): a setting like the three above.  gains_on: some gain is not exactly 1; gains: the C gains in force (empty
     // while off: all ones); d_gain their device table, allocated by the first call that switches the setting on and rewritten by every later one
     bool gains_on = false;
@@ -234,6 +243,9 @@ struct DeviceCall {
     // channel levels (fdc_pipeline_set_levels): where (power, peak) of the call's block 0, channel 0 go, [block][C]; null = none.  With them the kernels
     // write float whatever the output format (the order of the passes: fdc_enqueue.hip, float_passes)
     float2 *levels = nullptr;
+    // channel lag-1 correlation (fdc_pipeline_set_lag1): where (Re S, Im S) of the call's block 0, channel 0 go, [block][C]; null = none.  As with levels
+    // the kernels write float whatever the output format
+    float2 *lag1 = nullptr;
     // channel gains (fdc_pipeline_set_gains): the handle's device table of C gains, null = off (device_call).  With them the kernels write float whatever
     // the output format, as with levels
     const float *gain = nullptr;
@@ -281,6 +293,7 @@ int process_device_impl(fdc_pipeline *p, DeviceCall &call, const void *d_ring, i
 int channels_wide(fdc_pipeline *p, const float2 *spec, float2 *d_out, const int32_t *d_gids, int ngroup, int l, const Span &span, hipStream_t s);
 int check_iq_form(int32_t format, float scale);
 void levels_written(fdc_pipeline *p, int nblocks, hipStream_t stream, bool host);   // a call with levels on succeeded: what fdc_pipeline_levels hands out
+void lag1_written(fdc_pipeline *p, int nblocks, hipStream_t stream, bool host);     // the same of the lag-1 correlation (fdc_pipeline_lag1)
 std::string route(int fmt, bool fused, const char *otherwise);   // "<sc16|sc8>: fused", or what the call was instead (fdc_pipeline_describe)
 
 } }  // namespace fdc::pipe

@@ -1,10 +1,12 @@
 // gfx950 (MI355X, CDNA4) kernels of the frequency-domain channelizer — the passes that run BEHIND a plan's kernels, over the channel-major float
-// results of a launch group: the rotation of fine tuning (k_fine_rotate), the channel gains (k_chan_gain), the channel levels (k_chan_levels) and the
-// narrowing to complex integers (k_complex_to_iq).  Which of them a call runs, and in which order, is decided once per call: PostPass, fdc_enqueue.hip.
+// results of a launch group: the rotation of fine tuning (k_fine_rotate), the channel gains (k_chan_gain), the channel levels (k_chan_levels), the
+// channel lag-1 correlation (k_chan_lag1) and the narrowing to complex integers (k_complex_to_iq).  Which of them a call runs, and in which order, is
+// decided once per call: PostPass, fdc_enqueue.hip.
 //
-// One shape for the three per-channel kernels: grid y = channel, a row — the lout samples of one (block, channel) — on a power-of-two set of lanes of one
+// One shape for the four per-channel kernels: grid y = channel, a row — the lout samples of one (block, channel) — on a power-of-two set of lanes of one
 // wave, 16 bytes per lane and access where the row allows it (lout even, the channel's run 16-byte aligned), 8 bytes otherwise, a grid-stride loop over
 // the blocks (channel_grids).  k_chan_levels and k_chan_gain are one loop, walk_rows, with an operation each; it keeps four loads in flight per lane.
+// k_chan_lag1 has the same loop written out (lag1_rows): it also needs the sample in front of each pair, which another lane holds.
 // k_fine_rotate keeps its own, one-deep loop: moving it onto walk_rows changes how many loads it keeps in flight, which is a speed change to be measured
 // on its own.
 #include "fdc_kernels.h"
@@ -288,6 +290,138 @@ hipError_t launch_chan_levels(const float2 *out, const ChanDev *chans, float2 *l
 {
     return channel_grids(nchan, nb_chunk, [&](dim3 grid, int c0) {
         hipLaunchKernelGGL(k_chan_levels, grid, dim3(256), 0, s, out, chans, levels, c0, nchan, nb_chunk, mbase, (long long)nb_call);
+    });
+}
+
+// Channel lag-1 correlation (fdc_pipeline_set_lag1): S = sum over j = 1 .. lout - 1 of y[j] conj(y[j - 1]) of one row, the row's own samples only.
+// ONE ORDER PER SUM, the levels': the row on 2^lev_log2_lanes(lout) lanes, lane `sub` the pairs sub, sub + lanes, ... in index order; the lane that owns
+// pair i adds y[2i] conj(y[2i - 1]) where i >= 1, then y[2i + 1] conj(y[2i]) where 2i + 1 < lout; a term a conj(b) is (a.x b.x + a.y b.y, a.y b.x -
+// a.x b.y), every product and sum rounded on its own, Re and Im summed apart from +0; the lanes joined by the xor butterfly from distance 1 upwards.
+struct LagAcc { float re, im; };
+
+__device__ __forceinline__ void lag_add(LagAcc &s, cf a, cf b)
+{
+#pragma clang fp contract(off)
+    const float p = a.x * b.x, q = a.y * b.y;
+    const float t = p + q;
+    s.re = s.re + t;
+    const float u = a.y * b.x, v = a.x * b.y;
+    const float w = u - v;
+    s.im = s.im + w;
+}
+
+__device__ __forceinline__ void lag_join(LagAcc &s, unsigned lg)
+{
+    for (unsigned d = 1; d < (1u << lg); d <<= 1) {
+        s.re = s.re + __shfl_xor(s.re, (int)d, 64);
+        s.im = s.im + __shfl_xor(s.im, (int)d, 64);
+    }
+}
+
+// the value of the lane below (lane 0: its own), and of lane 63; both are run by the whole wave
+__device__ __forceinline__ cf lane_below(cf v) { return mk(__shfl_up(v.x, 1, 64), __shfl_up(v.y, 1, 64)); }
+__device__ __forceinline__ cf lane_63(cf v)
+{
+    return mk(__int_as_float(__builtin_amdgcn_readlane(__float_as_int(v.x), 63)), __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v.y), 63)));
+}
+
+// The rows [0, nb) of one channel's run `o`, in the shape of walk_rows: four pairs per lane and trip, all loaded before the first is used, a lane
+// without a pair of its own loading one that exists and leaving it out.  The sample in front of pair i, y[2i - 1], is the odd sample of pair i - 1:
+// the lane below holds it (lane_below), or, for lane 0 of a row that takes the whole wave, lane 63 at the step before (lane_63: a register of this
+// trip, or `carry` from the trip before).  Every loop here has a trip count that depends on the wave alone and the moves across lanes stand outside
+// every per-lane condition, so the whole wave runs them.  A lane that loaded a substitute is never below a lane with a first term: the pair below
+// pair i < npair is pair i - 1, a pair of the row with both its samples; and lane sub = 0 of a row of fewer than 64 lanes takes no first term, so
+// what lane_below hands it from the neighbouring row is not used.
+// g (GAINED: the narrowing gain pass runs in front and leaves the float results as they were cut): the samples times g first (gain_mul), which
+// are the bits the in-place gain pass would have left.
+template <bool WIDE, bool GAINED>
+__device__ __forceinline__ void lag1_rows(const float2 *o, unsigned lout, unsigned nb, float g, float2 *lag1, int mbase, int nchan, int c)
+{
+    const unsigned npair = (lout + 1) >> 1, lg = lev_log2_lanes(lout);
+    const unsigned lanes = 1u << lg, lane = threadIdx.x & 63, sub = lane & (lanes - 1), rows = 64u >> lg;
+    const unsigned wave = blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = gridDim.x * 4;
+    float2 *dst = lag1 + (size_t)mbase * (size_t)nchan + (size_t)c;
+    if (npair <= lanes) {
+        // a row is at most one pair per lane: four rows per trip, a grid stride apart
+        const bool has = sub < npair, first = has && sub >= 1, two = 2 * sub + 1 < lout;
+        const unsigned i = has ? sub : npair - 1;
+        for (unsigned m0 = wave * rows; m0 < nb; m0 += 4 * nwaves * rows) {
+            cf a[4], b[4];
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                const unsigned m = m0 + (unsigned)u * nwaves * rows + (lane >> lg);
+                row_load<WIDE>(o + (size_t)(m < nb ? m : nb - 1) * lout, i, lout, a[u], b[u]);
+            }
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                const unsigned m = m0 + (unsigned)u * nwaves * rows + (lane >> lg);
+                if (GAINED) { a[u] = gain_mul(a[u], g); b[u] = gain_mul(b[u], g); }
+                const cf z = lane_below(b[u]);
+                LagAcc acc{0.0f, 0.0f};
+                if (first) lag_add(acc, a[u], z);
+                if (has && two) lag_add(acc, b[u], a[u]);
+                lag_join(acc, lg);
+                if (m < nb && sub == 0) dst[(size_t)m * (size_t)nchan] = make_float2(acc.re, acc.im);
+            }
+        }
+    } else {
+        // a long row (more than 64 pairs) takes the whole wave: four steps of the row per trip, in index order
+        for (unsigned m = wave; m < nb; m += nwaves) {
+            const float2 *row = o + (size_t)m * lout;
+            LagAcc acc{0.0f, 0.0f};
+            cf carry = mk(0.0f, 0.0f);                          // the odd sample of the lane's last pair of the trip before
+            for (unsigned i0 = 0; i0 < npair; i0 += 4 * 64) {
+                cf a[4], b[4];
+#pragma unroll
+                for (int u = 0; u < 4; u++) {
+                    const unsigned i = i0 + (unsigned)u * 64 + lane;
+                    row_load<WIDE>(row, i < npair ? i : npair - 1, lout, a[u], b[u]);
+                }
+#pragma unroll
+                for (int u = 0; u < 4; u++) {
+                    const unsigned i = i0 + (unsigned)u * 64 + lane;
+                    if (i0 + (unsigned)u * 64 >= npair) break;          // (the same for the whole wave) no lane has a pair at this step or behind it
+                    if (GAINED) { a[u] = gain_mul(a[u], g); b[u] = gain_mul(b[u], g); }
+                    const cf below = lane_below(b[u]), wrap = lane_63(u ? b[u - 1] : carry);
+                    const cf z = lane ? below : wrap;
+                    if (i < npair) {
+                        if (i >= 1) lag_add(acc, a[u], z);
+                        if (2 * i + 1 < lout) lag_add(acc, b[u], a[u]);
+                    }
+                }
+                carry = b[3];
+            }
+            lag_join(acc, lg);
+            if (lane == 0) dst[(size_t)m * (size_t)nchan] = make_float2(acc.re, acc.im);
+        }
+    }
+}
+
+// Channel lag-1 correlation of a launch group: blocks [mbase, mbase + nb) of the call's channel-major float results, read once; one float2 (Re S, Im S)
+// per (block, channel) goes to lag1[(mbase + m) * nchan + c] and nothing else is written.  gain: null, or the channel gains the samples are to be
+// multiplied by first
+__global__ __launch_bounds__(256) void k_chan_lag1(const float2 *__restrict__ out, const ChanDev *__restrict__ chans, const float *__restrict__ gain,
+                                                   float2 *__restrict__ lag1, int c0, int nchan, int nb, int mbase, long long nb_call)
+{
+    const int c = c0 + (int)blockIdx.y;
+    const unsigned lout = (unsigned)chans[c].lout;
+    const float2 *o = out + nb_call * chans[c].out_off + (long long)mbase * lout;
+    const bool wide = !(lout & 1) && (reinterpret_cast<uintptr_t>(o) & 15) == 0;
+    if (gain) {
+        const float g = gain[c];
+        if (wide) lag1_rows<true, true>(o, lout, (unsigned)nb, g, lag1, mbase, nchan, c);
+        else lag1_rows<false, true>(o, lout, (unsigned)nb, g, lag1, mbase, nchan, c);
+    } else {
+        if (wide) lag1_rows<true, false>(o, lout, (unsigned)nb, 1.0f, lag1, mbase, nchan, c);
+        else lag1_rows<false, false>(o, lout, (unsigned)nb, 1.0f, lag1, mbase, nchan, c);
+    }
+}
+
+hipError_t launch_chan_lag1(const float2 *out, const ChanDev *chans, const float *gain, float2 *lag1, int nchan, int nb_chunk, int mbase, int nb_call,
+                            hipStream_t s)
+{
+    return channel_grids(nchan, nb_chunk, [&](dim3 grid, int c0) {
+        hipLaunchKernelGGL(k_chan_lag1, grid, dim3(256), 0, s, out, chans, gain, lag1, c0, nchan, nb_chunk, mbase, (long long)nb_call);
     });
 }
 

@@ -11,22 +11,25 @@ extern "C" {
 
 // the entries that write complex float only (sinks, spectrum items, group powers, waterfall): refused while the output format is not FC32
 // (and, but for the flush of a batch that is inside already, while fine tuning is on: they write the channels as they are cut; and while channel
-// levels are on: they give none; and while channel gains are on: they write the channels as they are cut)
+// levels or the lag-1 correlation are on: they give none; and while channel gains are on: they write the channels as they are cut)
 static int check_float_output(const fdc_pipeline *p, const char *entry, bool writes_channels = true)
 {
     if (p && p->out_form) return set_error(FDC_ERR_INVALID_ARGUMENT, "%s writes complex float outputs only: set the output format to FDC_OQ_FC32 first", entry);
     if (p && p->fine_on && writes_channels) return set_error(FDC_ERR_INVALID_ARGUMENT, "%s writes the channels as they are cut: switch fine tuning off first (fdc_pipeline_set_fine_tuning(p, NULL, C))", entry);
     if (p && p->levels_on && writes_channels) return set_error(FDC_ERR_INVALID_ARGUMENT, "%s gives no channel levels: switch them off first (fdc_pipeline_set_levels(p, 0))", entry);
+    if (p && p->lag1_on && writes_channels) return set_error(FDC_ERR_INVALID_ARGUMENT, "%s gives no channel lag-1 correlation: switch it off first (fdc_pipeline_set_lag1(p, 0))", entry);
     if (p && p->gains_on && writes_channels) return set_error(FDC_ERR_INVALID_ARGUMENT, "%s writes the channels as they are cut: switch the channel gains off first (fdc_pipeline_set_gains(p, NULL, C))", entry);
     return FDC_OK;
 }
 
 // Channel levels of a host entry's call: one copy of its nblocks*C (power, peak) pairs to the pinned twin, enqueued in front of the call's synchronise,
-// so that fdc_pipeline_levels is a memcpy
+// so that fdc_pipeline_levels is a memcpy; and the same of its lag-1 correlation (fdc_pipeline_lag1)
 static int levels_home(fdc_pipeline *p, int nblocks, hipStream_t s)
 {
     if (p->levels_on && p->C > 0)
         HIPCHK(hipMemcpyAsync(p->pin_levels.get(), p->d_levels.get(), sizeof(float2) * (size_t)nblocks * p->C, hipMemcpyDeviceToHost, s));
+    if (p->lag1_on && p->C > 0)
+        HIPCHK(hipMemcpyAsync(p->pin_lag1.get(), p->d_lag1.get(), sizeof(float2) * (size_t)nblocks * p->C, hipMemcpyDeviceToHost, s));
     return FDC_OK;
 }
 
@@ -184,6 +187,7 @@ static int pipeline_work_impl(fdc_pipeline *p, DeviceCall call, const void *in, 
     auto process = [&](size_t b0, int nb, int64_t first, float2 *dok, float2 *dspec) {
         call.spectrum = dspec; call.fout = dok;
         call.levels = p->levels_on && p->C > 0 ? p->d_levels + b0 * (size_t)p->C : nullptr;
+        call.lag1 = p->lag1_on && p->C > 0 ? p->d_lag1 + b0 * (size_t)p->C : nullptr;
         const int rc2 = process_device_impl(p, call, ringb + b0 * p->H * esz, first, nb,
                                             ofmt ? static_cast<void *>(p->d_oq + osz * b0 * (size_t)p->sum_lout) : static_cast<void *>(dok));
         oq_all = oq_all && call.ofused;
@@ -231,6 +235,7 @@ static int pipeline_work_impl(fdc_pipeline *p, DeviceCall call, const void *in, 
         RCCHK(levels_home(p, nblocks, s));
         HIPCHK(hipStreamSynchronize(s));
         if (p->levels_on) levels_written(p, nblocks, s, true);
+    if (p->lag1_on) lag1_written(p, nblocks, s, true);
         if (fmt) p->iq_route = route(fmt, call.all_fused, "widened");
         if (ofmt) p->oq_route = route(ofmt, oq_all, "narrowed");
         if (p->C > 0 && !out_reg) deliver(0, 0, nblocks);
@@ -296,6 +301,7 @@ static int pipeline_work_impl(fdc_pipeline *p, DeviceCall call, const void *in, 
     HIPCHK(hipStreamSynchronize(s));
     HIPCHK(hipStreamSynchronize(p->s_out));
     if (p->levels_on) levels_written(p, nblocks, s, true);
+    if (p->lag1_on) lag1_written(p, nblocks, s, true);
     if (fmt) p->iq_route = route(fmt, call.all_fused, "widened");
     if (ofmt) p->oq_route = route(ofmt, oq_all, "narrowed");
     p->blockcount += nblocks;
@@ -394,6 +400,7 @@ static int pipeline_work_real_impl(fdc_pipeline *p, const void *in, int nblocks,
     DeviceCall call = device_call(p, nullptr, d_specfull);
     call.ofmt = ofmt; call.oscale = p->out_scale; call.fout = p->d_out;
     call.levels = p->levels_on && p->C > 0 ? p->d_levels.get() : nullptr;
+    call.lag1 = p->lag1_on && p->C > 0 ? p->d_lag1.get() : nullptr;
     RCCHK(process_device_impl(p, call, p->d_ring, p->blockcount, nblocks, res));
     RCCHK(copy_outputs(p, outs, nblocks, osz, res, s));
     if (spectrum) HIPCHK(hipMemcpyAsync(spectrum, d_specfull, sizeof(float2) * (size_t)nblocks * p->N, hipMemcpyDeviceToHost, s));
@@ -401,6 +408,7 @@ static int pipeline_work_real_impl(fdc_pipeline *p, const void *in, int nblocks,
     RCCHK(levels_home(p, nblocks, s));
     HIPCHK(hipStreamSynchronize(s));
     if (p->levels_on) levels_written(p, nblocks, s, true);
+    if (p->lag1_on) lag1_written(p, nblocks, s, true);
     if (ofmt) p->oq_route = route(ofmt, call.ofused, "narrowed");
     p->blockcount += nblocks;
     return nblocks;

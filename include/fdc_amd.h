@@ -273,6 +273,40 @@ void *fdc_pipeline_levels_device(fdc_pipeline *p);
 int fdc_pipeline_set_gains(fdc_pipeline *p, const float *gain, int n);
 int fdc_pipeline_gains(const fdc_pipeline *p, float *dst, int n);
 
+/* CHANNEL LAG-1 CORRELATION: a per-block frequency estimate of every channel, summed on the device — the measurement of an AFC, as the levels are the
+ * measurement of an AGC: fine tuning takes nu_c in cycles per output sample, and this says what nu_c should be.  With the setting on, every (block m of
+ * the call, channel c) gets one complex float32 value from the lout_c samples the call produces for it:
+ *     S[m][c] = sum_{j = 1 .. lout_c - 1}  y[j] conj(y[j - 1])
+ * of the complex float32 samples y the entry writes, or would write before narrowing: AFTER fine tuning and the channel gain, BEFORE the sc16 / sc8
+ * narrowing (cut -> fine tuning -> gain -> levels, lag-1 -> narrowing), so a loop sees the residual left by the fine tuning in force.  arg(S) / (2 pi)
+ * is the row's mean frequency in cycles per output sample, the unit of fdc_pipeline_set_fine_tuning: added to the nu in force it cancels the residual;
+ * |S| against the row's power (CHANNEL LEVELS) says how far to trust it.  Only the row's own samples: the product across the block boundary is not
+ * taken, so the value needs no state and no sample of another call, span or launch group, and every cut of a stream gives the same values.
+ * Layout: lag1[m][c] = (Re S, Im S), float[nblocks][C][2], c the plan's channel index (a channel that is a copy of another channel's slice has its
+ * own entry); lout_c = 1 gives (+0, +0).  Rows with samples that are not finite give what IEEE arithmetic gives; no other row is disturbed.  The bits
+ * of S[m][c] depend on lout_c and the row's sample values only (the levels' lane assignment and summation tree, each product and sum rounded on its
+ * own, no atomics).  Each component is within (lout_c + 8) 2^-24 M of the exact sum over the float32 samples, M = sum_j |y[j]| |y[j - 1]| (relative
+ * to M, not to |S|: the terms may cancel).
+ *   fdc_pipeline_set_lag1        on != 0 / 0.  A SETTING with the semantics of fdc_pipeline_set_levels, word for word: it may change between any two
+ *                                calls and applies from the next one; it does not touch the history, the block counter or the input-form latch, and
+ *                                survives fdc_pipeline_reset; refused while a pipelined sinks batch is inside the handle; it waits for the handle's own
+ *                                stream first.  The first call that switches it on allocates max_blocks*C float2 on the device and pinned on the
+ *                                host, once; nothing in a work call, nothing inside a device entry.  With C = 0, on is accepted and every result
+ *                                is empty.
+ *   fdc_pipeline_lag1            the values of the last successful work call (host or device entry; a device entry's are read after a synchronise of
+ *                                the stream it ran on): dst receives nblocks*C*2 floats.  nblocks must be that call's block count, otherwise
+ *                                FDC_ERR_INVALID_ARGUMENT; the same while the setting is off and before any call.  A call of 0 blocks leaves the
+ *                                previous result in place.
+ *   fdc_pipeline_lag1_device     the device buffer ([block of the call][C] float2), NULL while off.  While the setting is on, a device call needs
+ *                                nblocks <= max_blocks: above it FDC_ERR_INVALID_ARGUMENT, nothing enqueued.
+ * While the setting is on, fdc_pipeline_work_sinks, _work_spectrum, _process_device_power and fdc_pipeline_work_waterfall return
+ * FDC_ERR_INVALID_ARGUMENT and change nothing (fdc_pipeline_flush_sinks still flushes), and every plan writes complex float first: with integer output
+ * the samples are narrowed behind the pass ("output sc16: narrowed"; "fused" again once it is off).  It is always one pass of its own over the launch
+ * group's final float results, which reads them once (fdc_pipeline_describe: "lag1: pass"). */
+int fdc_pipeline_set_lag1(fdc_pipeline *p, int32_t on);
+int fdc_pipeline_lag1(fdc_pipeline *p, float *dst, int nblocks);
+void *fdc_pipeline_lag1_device(fdc_pipeline *p);
+
 /* Optional: pin a host range that will be handed to fdc_pipeline_work() again and again (GNU Radio's circular buffers
  * live as long as the flowgraph: register them in start(), unregister in stop()).  A call whose `in` lies in a
  * registered range is DMA'd from it in place, and when every outs[c] does, the results are stored straight into
@@ -392,6 +426,9 @@ int fdc_pipeline_group_set_fine_tuning(fdc_pipeline_group *g, const double *nu, 
  * nblocks must be that call's block count (FDC_ERR_INVALID_ARGUMENT otherwise, while levels are off and before any call) */
 int fdc_pipeline_group_set_levels(fdc_pipeline_group *g, int32_t on);
 int fdc_pipeline_group_levels(fdc_pipeline_group *g, float *dst, int nblocks);
+/* the channel lag-1 correlation for every member (fdc_pipeline_set_lag1), and that of the last group call, put together as the levels are */
+int fdc_pipeline_group_set_lag1(fdc_pipeline_group *g, int32_t on);
+int fdc_pipeline_group_lag1(fdc_pipeline_group *g, float *dst, int nblocks);
 /* channel gains for every member (fdc_pipeline_set_gains: the same arguments, refusals and setting semantics) */
 int fdc_pipeline_group_set_gains(fdc_pipeline_group *g, const float *gain, int n);
 int32_t fdc_pipeline_group_size(const fdc_pipeline_group *g);
