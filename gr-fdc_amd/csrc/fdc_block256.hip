@@ -28,9 +28,10 @@
 // neighbour from that XCD's L2.
 //
 // The arithmetic is the uniform-plan commutation of fdc_fast256.hip with the same number of multiplications per value.  At N = 16384 the
-// tables and rounding points are the same too; at N = 32768 and 65536 stage 1 factors its tables otherwise (k_blk256, kSplit), so the
-// result matches k_p1 + k_p2 to a few ulps either way; parity against the oracle: tests/test_parity_gpu.py,
-// tests/test_block256_stage1_tables_gpu.py.
+// tables and rounding points are the same too; at N = 32768 and 65536 stage 1 factors its tables otherwise (k_blk256, kSplit), and at N = 65536 the
+// channelizer on the grid and half a slot up takes the wave's part of them from memory through the scalar path and cb as one table entry
+// (kBlkSrow, SROW), so the result matches k_p1 + k_p2 to a few ulps either way; parity against the oracle: tests/test_parity_gpu.py,
+// tests/test_block256_stage1_tables_gpu.py, tests/test_block256_scalar_row_gpu.py.
 #include "fdc_blockcommon.hpp"
 #include "fdc_iq.hpp"
 
@@ -39,6 +40,20 @@ namespace fdc {
 extern __shared__ __attribute__((aligned(16))) unsigned char fdc_smem_blk[];
 
 typedef unsigned long long u8v __attribute__((ext_vector_type(8)));
+
+// SROW (k_blk256): four table entries at a wave-uniform address in the constant address space, i.e. one s_load_dwordx8 (two adjacent ones: the
+// compiler makes them one s_load_dwordx16), and the complex multiplication that takes such an entry from its scalar register pair (cmul,
+// fdc_radix16.hpp, with b in SGPRs)
+typedef unsigned int u32x8 __attribute__((ext_vector_type(8)));
+typedef __attribute__((address_space(4))) u32x8 srow_piece;
+__device__ __forceinline__ cf cmul_s(cf a, cf b)
+{
+    cf r;
+    asm("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[0,1]\n\t"
+        "v_pk_fma_f32 %0, %1, %2, %0 op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[0,1,0]"
+        : "=&v"(r) : "v"(a), "s"(b));
+    return r;
+}
 
 // The block length is a template parameter: N = 256 rows x (32 P) columns with P = 2, 4, 8 passes of 32 columns, i.e. N = 16384,
 // 32768, 65536; the number of channel slots is the number of columns N1 = 32 P.  Stage 1 does not depend on P except through the row
@@ -53,9 +68,20 @@ typedef unsigned long long u8v __attribute__((ext_vector_type(8)));
 template <int P, bool OFF, bool FWD, bool R4, class TO>
 constexpr bool kBlkSpread = !OFF && !FWD && !(P == 8 && (R4 || !std::is_same<TO, float2>::value));
 
-template <int P>
+// Which forms of k_blk256 take the wave's twiddle row through the scalar path (SROW, one_pass) instead of the LDS table UR, and cb as one entry of a
+// table of N1 / 4 rows in UR's place: at P = 8 the channelizer on the grid and half a slot up at R = 2, whatever the sample formats.  The forms that must
+// give the same values go together: both spread twins of a form (tests/test_block256_load_placement_gpu.py), and the integer-output forms with the float
+// form whose narrowed output theirs must equal byte for byte (tests/test_iq_output_gpu.py) — cb is one table entry here and a float product of two
+// there.  Not P = 2 (no UR there); not P = 4, where it is worth nothing measurable and costs the spread forms 14 - 26 spilled SGPRs; offset plans,
+// R = 4 and the forward transform have not been built this way (they stand at 94 - 106 of 106 SGPRs and 250 - 256 VGPRs as they are, and the scheme
+// takes 7 - 16 SGPRs more): profiles/srow/NOTES.md.
+template <int P, bool OFF, bool FWD, bool R4>
+constexpr bool kBlkSrow = P == 8 && !OFF && !FWD && !R4;
+
+template <int P, bool SROW = false>
 struct BlkGeom {
     static_assert(P == 2 || P == 4 || P == 8, "passes of 32 columns: N = 16384, 32768 or 65536");
+    static_assert(!SROW || P > 2, "the scalar wave row replaces UR, which P = 2 does not have");
     static constexpr int kN1 = 32 * P;                            // columns = channel slots
     static constexpr int kN = 256 * kN1;
     static constexpr int kJT = P == 8 ? 4 : 8;                    // 16-row groups per stage-2 trip (64 or 128 rows)
@@ -70,20 +96,23 @@ struct BlkGeom {
     static constexpr int kOffCt = kTripBytes > kStripsEnd ? kTripBytes : kStripsEnd;   // stage-2 twiddles [32][P], behind the trip buffer and the strips
     static constexpr int kOffWrow = P == 8 ? 136960 : kOffCt + 32 * P * 8;   // tables: above the strips and the trip buffer
     // The stage-1 tables behind wrow.  kSplit (P > 2): the lane table LT (64 rows of 18), the wave rows UR ([kN1 / 4][16]) and the rows of CB
-    // ([P + 8][16]) — cb comes from LDS.  P = 2: Bt (32 rows of 18) and SA (16 P rows of 18), cb from memory: the on-grid form there runs two workgroups per CU on
+    // ([P + 8][16]) — cb comes from LDS.  SROW: no UR (the wave row comes from memory through the scalar path) and CB whole, [kN1 / 4][16], in its place.
+    // P = 2: Bt (32 rows of 18) and SA (16 P rows of 18), cb from memory: the on-grid form there runs two workgroups per CU on
     // 81664 of 81920 bytes and has no room for the two wave tables.
     static constexpr bool kSplit = P > 2;
     static constexpr int kOffLT = kOffWrow + 16 * 18 * 8;
     static constexpr int kOffUR = kOffLT + 64 * 18 * 8;
     static constexpr int kOffB = kOffLT, kOffSA = kOffB + 32 * 18 * 8;
-    static constexpr int kOffSoff = kSplit ? kOffUR + kN1 * 4 * 8 : kOffSA + 16 * P * 18 * 8;
+    static constexpr int kOffSoff = kSplit ? kOffUR + (SROW ? 0 : kN1 * 4 * 8) : kOffSA + 16 * P * 18 * 8;
     static constexpr int kOffCbl = kOffSoff + kN1 * 4;
-    static constexpr int kLds = kOffCbl + (kSplit ? (P + 8) * 16 * 8 : 0);   // P = 8: 159744; P = 2: 81664
+    static constexpr int kCblRows = SROW ? kN1 / 4 : P + 8;
+    static constexpr int kLds = kOffCbl + (kSplit ? kCblRows * 16 * 8 : 0);   // P = 8: 159744 (SROW: 157696); P = 2: 81664
     static constexpr int kOffWrowF = kLds;                        // offset plans: the forward twiddle rows behind everything else
     static constexpr int kLdsOff = kOffWrowF + 16 * 18 * 8;       // P = 8: 162048
     static_assert(kLdsOff <= 160 * 1024 && kLds <= 160 * 1024, "LDS budget");
     static_assert(kOffCt >= kStripsEnd && kOffCt + 32 * P * 8 <= kOffWrow, "stage-2 trip buffer and twiddles below the tables, tables above the strips");
     static_assert((16 * (kJB - 1) * kLd + 32 * (P - 1)) * 8 < 65536, "ds offsets of a base register");
+    static_assert(!SROW || kCblRows * 16 * 8 == kN1 * 4 * 8, "the whole cb table takes what UR had: the total shrinks by the two-factor table");
 };
 
 // FWD = false: the channelizer (above).  FWD = true: the same machinery as a plain forward transform of the block (no window,
@@ -123,7 +152,8 @@ __global__ FDC_PLAIN_DS __launch_bounds__(512, (P == 2 && !OFF && !R4 && !FWD) ?
                                                 float2 *__restrict__ fwd_scratch, const unsigned *__restrict__ keep,
                                                 typename IqTail<TI, TO>::type gpow /* integer TI / TO: iq_scale / oq_scale */)
 {
-    typedef BlkGeom<P> GM;
+    constexpr bool kSrow = kBlkSrow<P, OFF, FWD, R4>;
+    typedef BlkGeom<P, kSrow> GM;
     constexpr bool kIq = !std::is_same<TI, float2>::value, kOq = !std::is_same<TO, float2>::value;
     static_assert(!SPREAD || kBlkSpread<P, OFF, FWD, R4, TO>, "no spread form of this one");
     static_assert(!kIq || !FWD, "integer input: the channelizer forms (the forward transform takes widened input)");
@@ -141,6 +171,9 @@ __global__ FDC_PLAIN_DS __launch_bounds__(512, (P == 2 && !OFF && !R4 && !FWD) ?
     // UR[8 pass + wave][q] = W_N^(16 q (32 pass + 4 wave)) is the same for every lane of a wave (a broadcast read).  cbt[n1 = 32 pass + c5][b] =
     // (-1)^n1 W_N^(n1 (b + r)) factors the same way: cbt[col][b] is in LT, CB[pass][b] = cbt[32 pass][b] and CB[P + wave][b] =
     // cbt[4 wave][b] are read once per pass (the second is a constant of the lane, but there is no register to keep it in).
+    // SROW: the row UR[8 pass + wave] is row 32 pass + 4 wave of twq as it lies in memory (HALF: its two halves swapped), the same for the whole wave:
+    // read from there in four pieces of four entries through the scalar path, each entry the scalar operand of one multiplication; no UR in LDS, and in
+    // its place CB[8 pass + wave][b] = cbt[32 pass + 4 wave][b] whole: one read per pass, no product.
     // P = 2: Bt[c5][q] = W_N^(16 c5 q) and SA[pass][b][q] = shape[b + 16 q] / N W_N^(512 pass q); cbt[n1][b] comes from memory a pass ahead.
     constexpr bool kSplit = GM::kSplit;
     float2 *LT = reinterpret_cast<float2 *>(fdc_smem_blk + GM::kOffLT);
@@ -217,9 +250,13 @@ __global__ FDC_PLAIN_DS __launch_bounds__(512, (P == 2 && !OFF && !R4 && !FWD) ?
             const float2 e = make_float2(t.x * s, t.y * s), c = cbt[(ln & 3) * 16 + (ln >> 2)];
             LT[ln * 18 + q] = make_float2(e.x * c.x - e.y * c.y, e.x * c.y + e.y * c.x);
         }
-        for (int i = tid; i < kN1 * 4; i += 512) UR[i] = twq[(i >> 4) * 64 + (HALF ? (i & 15) ^ 8 : i & 15)];   // row 4 (i >> 4) of twq
-        if (tid < (P + 8) * 16)                                                  // rows 32 pass, then rows 4 wave of cbt
-            CBL[tid] = cbt[(tid < P * 16 ? (tid >> 4) * 512 : ((tid >> 4) - P) * 64) + (tid & 15)];
+        if constexpr (kSrow) {
+            for (int i = tid; i < kN1 * 4; i += 512) CBL[i] = cbt[(i >> 4) * 64 + (i & 15)];   // row 4 (i >> 4) of cbt
+        } else {
+            for (int i = tid; i < kN1 * 4; i += 512) UR[i] = twq[(i >> 4) * 64 + (HALF ? (i & 15) ^ 8 : i & 15)];   // row 4 (i >> 4) of twq
+            if (tid < (P + 8) * 16)                                                  // rows 32 pass, then rows 4 wave of cbt
+                CBL[tid] = cbt[(tid < P * 16 ? (tid >> 4) * 512 : ((tid >> 4) - P) * 64) + (tid & 15)];
+        }
     } else {
         Bt[(tid >> 4) * 18 + (tid & 15)] = twq[HALF ? tid ^ 8 : tid];            // c5 = tid >> 4 < 32, q = tid & 15 (HALF: the entry of q ^ 8)
         for (int i = tid; i < 256 * P; i += 512) {
@@ -238,7 +275,9 @@ __global__ FDC_PLAIN_DS __launch_bounds__(512, (P == 2 && !OFF && !R4 && !FWD) ?
     // the two table rows of a pass: kSplit: UR row 8 pass + wave and the lane's LT row; P = 2: Bt row c5 and SA row 16 pass + b
     const float2 *const tr0 = kSplit ? UR + w * 16 : Bt + c5 * 18;  // kSplit: + 128 pass
     const float2 *const tr1 = kSplit ? LT + lane * 18 : SA + b * 18;   // P = 2: + 288 pass
-    const float2 *const cblr = CBL + b;                             // + 16 pass, + 16 (P + wave)
+    const float2 *const cblr = CBL + b + (kSrow ? 16 * w : 0);      // + 16 pass, + 16 (P + wave); SROW: + 128 pass
+    // SROW: row 4 wave of twq as pieces of four entries, at an address the whole wave shares (scalar loads); + 128 pass, + piece
+    [[maybe_unused]] const srow_piece *const srow = (const srow_piece *)(unsigned long long)(twq + (kSrow ? 64 * __builtin_amdgcn_readfirstlane(w) : 0));
     const __amdgpu_buffer_rsrc_t rout = make_rsrc(out, out_bytes);
     // FWD / R4: this workgroup's scratch, [pass][j][thread]
     constexpr bool kScr = FWD || R4;
@@ -270,7 +309,7 @@ __global__ FDC_PLAIN_DS __launch_bounds__(512, (P == 2 && !OFF && !R4 && !FWD) ?
         // pass (of this block, or pass 0 of this workgroup's next block; after the last block: the same rows again, unused)
         // are requested first, unconditionally (a conditional request costs a second set of register copies).
         auto one_pass = [&](const int ps, cf (&cur)[16], const cf cbc, cf (&L)[16], cf &cbn) __attribute__((always_inline)) {
-            const cf cbl = kSplit ? cmul(ld2(&cblr[16 * ps]), ld2(&cblr[16 * (P + w)])) : cbc;
+            const cf cbl = kSrow ? ld2(&cblr[128 * ps]) : kSplit ? cmul(ld2(&cblr[16 * ps]), ld2(&cblr[16 * (P + w)])) : cbc;
             const cf cb = (OFF && R4) ? cmul(cbl, phs) : OFF ? cbl * sgn : cbl;
             const int pn = ps < P - 1 ? ps + 1 : 0;
             const int mb = ps < P - 1 ? m : mnext;
@@ -318,8 +357,19 @@ __global__ FDC_PLAIN_DS __launch_bounds__(512, (P == 2 && !OFF && !R4 && !FWD) ?
 #pragma unroll
                 for (int a = 0; a < 16; a++) cur[a] = iq_widen_bits(TI{}, __float_as_uint(cur[a].x), iq_scale);
             }
+            // SROW: piece k = entries 4 k ... 4 k + 3 of the wave's row (HALF: of the row with its halves swapped).  Two pieces are requested here, behind
+            // the first dft16, the other two into the same registers once the first two are used up: sixteen row SGPRs at most.  A scalar load shares
+            // its counter with LDS and returns out of order, so every LDS wait behind a request waits for the pieces too: a request is placed where
+            // LDS reads that have to be waited for anyway follow it (here: the forward twiddle row).  A fence in front of a request keeps it from moving
+            // up, and from joining the pieces before it (32 row SGPRs live: spills, profiles/stage1_tables/NOTES.md).
+            [[maybe_unused]] auto ld_piece = [&](int k) __attribute__((always_inline)) -> u32x8 {
+                __builtin_amdgcn_sched_barrier(0);
+                return srow[128 * ps + (HALF ? k ^ 2 : k)];
+            };
+            [[maybe_unused]] u32x8 pc[2];
             dft16<false>(cur);                                    // in place, over a: index p in cur[rev16(p)]
             ld_rows(std::integral_constant<int, 0>{});
+            if constexpr (kSrow) { pc[0] = ld_piece(0); pc[1] = ld_piece(1); }
             cf tw[16];
             ld_row_sh<OFF>(tw, wrf);
             if constexpr (OFF) {
@@ -352,7 +402,28 @@ __global__ FDC_PLAIN_DS __launch_bounds__(512, (P == 2 && !OFF && !R4 && !FWD) ?
                 dft16<false>(v);                                  // A[k2 = b + 16 q] in v[rev16(q)]
                 ld_rows(std::integral_constant<int, 1>{});
                 cf u[16];
-                {
+                if constexpr (kSrow) {
+                    // A half of the row at a time: its eight multiplications by the row entry (the scalar operand; no LDS), then, for the first half,
+                    // the request of the other two pieces into the registers just used, then its eight multiplications by the lane-table entry.  The
+                    // waits for the lane table's reads are the first behind the request and cover it: the pieces arrive while those reads do.
+#pragma unroll
+                    for (int h = 0; h < 2; h++) {
+                        cf t[8];
+#pragma unroll
+                        for (int j = 0; j < 8; j++) {
+                            const u32x8 pj = pc[j >> 2];
+                            t[j] = cmul_s(v[rev16(8 * h + j)], mk(__uint_as_float(pj[2 * (j & 3)]), __uint_as_float(pj[2 * (j & 3) + 1])));
+                        }
+                        if (h == 0) { pc[0] = ld_piece(2); pc[1] = ld_piece(3); }
+#pragma unroll
+                        for (int i = 0; i < 4; i++) {
+                            const float4 t1 = ld4(&r1[8 * h + 2 * i]);
+                            // window * inter-pass twiddle, placed at the ifftshifted position (k2 ^ 128 <=> q ^ 8)
+                            u[HALF ? 8 * h + 2 * i : (8 * h + 2 * i) ^ 8] = cmul(t[2 * i], mk(t1.x, t1.y));
+                            u[HALF ? 8 * h + 2 * i + 1 : (8 * h + 2 * i + 1) ^ 8] = cmul(t[2 * i + 1], mk(t1.z, t1.w));
+                        }
+                    }
+                } else {
 #pragma unroll
                     for (int i = 0; i < 8; i++) {
                         const float4 t0 = ld4(&r0[2 * i]), t1 = ld4(&r1[2 * i]);
@@ -592,7 +663,8 @@ static void for_blk256_forms(int p, int nt, int off, int fwd, int r4, int half, 
         using TI = decltype(ti);
         using TO = decltype(to);
         constexpr bool kNt = NT() != 0, kOff = OFF() != 0, kFwd = FWD() != 0, kR4 = R4() != 0, kHalf = HALF() != 0;
-        constexpr int kLds = kOff ? BlkGeom<P()>::kLdsOff : BlkGeom<P()>::kLds;
+        constexpr bool kSrow = kBlkSrow<P(), kOff, kFwd, kR4>;      // (never an offset plan)
+        constexpr int kLds = kOff ? BlkGeom<P()>::kLdsOff : BlkGeom<P(), kSrow>::kLds;
         if constexpr (blk256_form<P(), kNt, kOff, kFwd, kR4, kHalf, TI, TO, false>()) {
             constexpr bool kTwin = blk256_form<P(), kNt, kOff, kFwd, kR4, kHalf, TI, TO, true>();
             if (spread != 1 || !kTwin) f(k_blk256<P(), kNt, kOff, kFwd, kR4, kHalf, TI, TO, false>, kLds, ti, to);
