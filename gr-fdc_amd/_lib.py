@@ -110,6 +110,9 @@ SYMBOLS = {
     "fdc_pipeline_lag1_device": (_vp, [_vp]),
     "fdc_pipeline_group_set_lag1": (C.c_int, [_vp, C.c_int32]),
     "fdc_pipeline_group_lag1": (C.c_int, [_vp, C.POINTER(C.c_float), C.c_int]),
+    "fdc_pipeline_set_demod": (C.c_int, [_vp, C.c_int32, C.c_float]),
+    "fdc_pipeline_demod": (C.c_int, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_float)]),
+    "fdc_pipeline_demod_device": (C.c_int, [_vp, C.c_int32, C.c_float, _vp, _vp, _vp, _vp, C.c_int, _vp]),
     "fdc_pipeline_set_gains": (C.c_int, [_vp, C.POINTER(C.c_float), C.c_int]),
     "fdc_pipeline_gains": (C.c_int, [_vp, C.POINTER(C.c_float), C.c_int]),
     "fdc_pipeline_group_set_gains": (C.c_int, [_vp, C.POINTER(C.c_float), C.c_int]),

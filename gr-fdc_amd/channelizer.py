@@ -251,17 +251,37 @@ def _set_gains(fn, handle, nchan, g):
     _lib.check(rc)
 
 
+DEMOD_FM, DEMOD_MAG = 1, 2        # FDC_DEMOD_FM, FDC_DEMOD_MAG (include/fdc_amd.h)
+
+
+def _demod_mode(mode, gain):
+    """Pipeline.set_demod: (FDC_DEMOD_* code, float32 gain).  Raises before any library call."""
+    if mode is None:
+        return 0, np.float32(1.0)
+    if not isinstance(mode, str) or mode.lower() not in ("fm", "mag"):
+        raise ValueError("demod is None, 'fm' or 'mag'")
+    with np.errstate(over="ignore"):
+        g = np.float32(gain)
+    if not np.isfinite(g) or g == 0:
+        raise ValueError("the demodulation gain must be finite and not zero")
+    return (DEMOD_FM if mode.lower() == "fm" else DEMOD_MAG), g
+
+
 class _OutputFormat:
     """The channel outputs in the handle's output format (fdc_pipeline_set_output_format): complex64 arrays of nblocks*lout_c samples, or
-    int16 / int8 arrays of shape (nblocks*lout_c, 2) (interleaved I/Q: sc16 / sc8)."""
+    int16 / int8 arrays of shape (nblocks*lout_c, 2) (interleaved I/Q: sc16 / sc8); float32 arrays of nblocks*lout_c samples while the channel
+    demodulation is on (Pipeline.set_demod, which excludes integer output)."""
     _oq = OQ_FC32
     _oq_scale = np.float32(1.0)
+    _demod = 0
 
     def output_format(self):
         """(format name, scale): ("fc32", 1.0), ("sc16", s) or ("sc8", s)."""
         return ({OQ_FC32: "fc32", IQ_SC16: "sc16", IQ_SC8: "sc8"}[self._oq], float(self._oq_scale))
 
     def _new_outs(self, nb):
+        if getattr(self, "_demod", 0):              # (getattr: the allocators are also called on stand-in objects that carry lout and _oq only)
+            return [np.empty(nb * lo, dtype=np.float32) for lo in self.lout]
         if self._oq == OQ_FC32:
             return [np.empty(nb * lo, dtype=np.complex64) for lo in self.lout]
         return [np.empty((nb * lo, 2), dtype=_OQ_DTYPES[self._oq]) for lo in self.lout]
@@ -271,10 +291,13 @@ class _OutputFormat:
             return self._new_outs(nb)
         if len(outs) != len(self.lout):
             raise ValueError("outs needs one array per channel")
-        dt = np.complex64 if self._oq == OQ_FC32 else _OQ_DTYPES[self._oq]
-        per = 1 if self._oq == OQ_FC32 else 2
+        demod = bool(getattr(self, "_demod", 0))
+        dt = np.float32 if demod else np.complex64 if self._oq == OQ_FC32 else _OQ_DTYPES[self._oq]
+        per = 1 if demod or self._oq == OQ_FC32 else 2
         for o, lo in zip(outs, self.lout):
             if not isinstance(o, np.ndarray) or o.dtype != dt or not o.flags.c_contiguous or o.size != per * nb * lo:
+                if demod:
+                    raise ValueError("outs[c] must be contiguous float32 with nblocks*lout_c samples (the channel demodulation is on)")
                 if self._oq == OQ_FC32:
                     raise ValueError("outs[c] must be contiguous complex64 with nblocks*lout_c samples")
                 raise ValueError("outs[c] must be contiguous %s with nblocks*lout_c interleaved I/Q samples (the output format)" % np.dtype(dt).name)
@@ -413,6 +436,35 @@ class Pipeline(_OutputFormat):
     def lag1_device(self):
         """fdc_pipeline_lag1_device: the device address of the lag-1 correlation ([block][C] float2), None while it is off."""
         return _lib.lib().fdc_pipeline_lag1_device(self._h)
+
+    def set_demod(self, mode, gain=1.0):
+        """fdc_pipeline_set_demod: mode None (off), "fm" or "mag"; gain (converted to float32) finite and not zero.  While it is on, work*, work_span*
+        and work_iq* return float32 arrays of nblocks*lout_c samples, one per channel, and process_device* take device buffers of 4-byte samples:
+        "fm": gain * atan2 of y[t] conj(y[t - 1]) (the FM discriminator; gain = 1 / (2 pi) gives cycles per output sample, the unit of
+        set_fine_tuning and lag1_frequency), "mag": gain * |y[t]| (bit for bit numpy's float32 statement), y the complex64 sample the call writes
+        with it off, after fine tuning and the gain.  FM's sample in front of a call's first is the last one of the call before where the call goes on
+        at the next block, zero at a stream start (after create, reset(), a switch of mode, a device or span call elsewhere in the stream).  A setting
+        like set_output_format: it applies from the next call and survives reset(); it excludes sc16 / sc8 output, and the sink, spectrum-item,
+        group-power and waterfall entries are refused while it is on.  ValueError for an unknown mode or a gain that is zero or not finite, FdcError
+        where the library refuses (integer output set, a pipelined sinks batch inside); nothing changes then."""
+        code, g = _demod_mode(mode, gain)
+        _lib.check(_lib.lib().fdc_pipeline_set_demod(self._h, code, float(g)))
+        self._demod = code
+
+    def demod_device(self, mode, gain, d_in, d_out, nblocks, d_carry_in=None, d_carry_out=None, stream=None):
+        """fdc_pipeline_demod_device: the demodulating pass alone on device buffers of the caller (d_in: complex64 in process_device's layout, d_out:
+        float32 at the same element offsets; "fm": d_carry_in, C complex64 or None, is read and d_carry_out, C complex64, written).  The handle's
+        own setting, carry and stream position are not touched."""
+        code, g = _demod_mode(mode, gain)
+        if code == 0:
+            raise ValueError("demod_device takes 'fm' or 'mag'")
+        _lib.check(_lib.lib().fdc_pipeline_demod_device(self._h, code, float(g), d_in, d_out, d_carry_in, d_carry_out, int(nblocks), stream))
+
+    def demod(self):
+        """fdc_pipeline_demod: (mode, gain) in force: (None, 1.0), ("fm", g) or ("mag", g)."""
+        mode, gain = C.c_int32(0), C.c_float(0)
+        _lib.check(_lib.lib().fdc_pipeline_demod(self._h, C.byref(mode), C.byref(gain)))
+        return ({0: None, DEMOD_FM: "fm", DEMOD_MAG: "mag"}[mode.value], float(gain.value))
 
     def _ran(self, nb):
         self._call_nb = int(nb)
@@ -762,7 +814,8 @@ class FrequencyDomainChannelizer:
                  pow_act_deactivation_delay,
                  pow_act_maxblocks, act_det_maxblocks,
                  debug, device_id=0, max_blocks=64, devices=None, pipelined=False, waterfall=None, iq_input=None, iq_scale=1.0,
-                 iq_output=None, iq_output_scale=1.0, fine_tuning=False, *, payload_format=None, payload_scale=1.0, levels=False, gains=None, lag1=False):
+                 iq_output=None, iq_output_scale=1.0, fine_tuning=False, *, payload_format=None, payload_scale=1.0, levels=False, gains=None, lag1=False,
+                 demod=None, demod_gain=1.0):
         # pipelined (not an argument of the reference): the sink blocks run beside the front end of the FOLLOWING work() calls, as the
         # thread-per-block scheduler runs them beside the FFT in the reference (fdc_pipeline_work_sinks on a look-ahead bank,
         # include/fdc_amd.h): same PDUs, handed out one or two work() calls later; flush() at the end of the stream
@@ -880,6 +933,23 @@ class FrequencyDomainChannelizer:
             if waterfall is not None:
                 raise ValueError("lag1 cannot go with a waterfall")
 
+        # demod / demod_gain (not arguments of the reference): "fm" / "mag" — the channel ports come back as float32 arrays, the FM discriminator's output
+        # (gain * angle of y[t] conj(y[t - 1]): quadrature_demod_cf behind every port) or the envelope (complex_to_mag), computed on the device behind
+        # fine tuning and the gains (Pipeline.set_demod); levels and lag1 stay those of the complex samples.  The refusals of lag1, and iq_output
+        self.demod, self.demod_gain = demod, float(demod_gain)
+        if demod is not None:
+            _demod_mode(demod, demod_gain)
+            if self.inpveclen != 1:
+                raise ValueError("demod needs inpveclen 1: the pre-transformed item entry writes complex outputs only")
+            if activity_controlled_channels or activity_detection_segments:
+                raise ValueError("demod cannot go with activity-controlled channels or detection segments")
+            if waterfall is not None:
+                raise ValueError("demod cannot go with a waterfall")
+            if iq_output is not None:
+                raise ValueError("demod cannot go with iq_output: the demodulated ports are float32")
+            if devices is not None and len(devices) > 1:
+                raise ValueError("demod needs one device: the group entries do not serve the channel demodulation")
+
         # gains (not an argument of the reference): one output gain per throughput channel, applied on the device behind fine tuning and in front of the
         # levels and of iq_output's narrowing (Pipeline.set_gains); set_gains() changes them between work() calls (an AGC fed from self.levels)
         self.gains = None if gains is None else _check_gains(len(self.throughput_channels), gains)
@@ -952,6 +1022,8 @@ class FrequencyDomainChannelizer:
             self.pipeline.set_gains(self.gains)
         if self.lag1_on:
             self.pipeline.set_lag1(True)
+        if self.demod is not None:
+            self.pipeline.set_demod(self.demod, self.demod_gain)
         self.N_throughput_channelizers = len(self.channel_params)
         # waterfall (not an argument of the reference, whose example flowgraph wires the spectrum to complex_to_mag_squared and
         # FDC.WaterfallMsgTagging outside the hier block): a gr_fdc_amd.Waterfall fed from the spectrum on the device; work() then

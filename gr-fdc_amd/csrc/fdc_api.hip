@@ -411,6 +411,7 @@ int32_t fdc_pipeline_describe(const fdc_pipeline *p, char *buf, int32_t n)
     if (!p->levels_route.empty()) add("; levels: %s", p->levels_route.c_str());
     if (!p->gains_route.empty()) add("; gains: %s", p->gains_route.c_str());
     if (!p->lag1_route.empty()) add("; lag1: %s", p->lag1_route.c_str());
+    if (!p->demod_route.empty()) add("; demod: %s", p->demod_route.c_str());
     std::snprintf(buf, (size_t)n, "%s", t);
     return k;
 }
@@ -484,6 +485,8 @@ void fdc_pipeline_reset(fdc_pipeline *p)
     p->levels_route.clear();     // (and so do the channel levels)
     p->gains_route.clear();      // (and the channel gains)
     p->lag1_route.clear();       // (and the channel lag-1 correlation)
+    p->demod_route.clear();      // (and the channel demodulation, whose stream starts anew: no carry in front of the next call)
+    p->demod_next = -1;
 }
 
 int fdc_pipeline_set_output_format(fdc_pipeline *p, int32_t format, float scale)
@@ -494,6 +497,8 @@ int fdc_pipeline_set_output_format(fdc_pipeline *p, int32_t format, float scale)
     if (!std::isfinite(scale) || scale == 0.0f) return set_error(FDC_ERR_INVALID_ARGUMENT, "the output scale must be finite and not zero");
     if (p->hier_filled > 0)
         return set_error(FDC_ERR_INVALID_ARGUMENT, "a pipelined sinks batch is still inside the handle: fdc_pipeline_flush_sinks until it returns 0 first");
+    if (format && p->demod_mode)
+        return set_error(FDC_ERR_INVALID_ARGUMENT, "the channel demodulation writes real float32 samples: switch it off first (fdc_pipeline_set_demod(p, FDC_DEMOD_OFF, 1))");
     if (format && !p->d_out) {
         // the float staging of the plans whose kernels do not narrow themselves: allocated here, once, so that no device entry allocates while it enqueues
         HIPCHK(hipSetDevice(p->cfg.device_id));
@@ -637,6 +642,64 @@ int fdc_pipeline_lag1(fdc_pipeline *p, float *dst, int nblocks)
         p->lag_host = true;
     }
     std::memcpy(dst, p->pin_lag1.get(), sizeof(float2) * n);
+    return FDC_OK;
+    FDC_ENTRY_END
+}
+
+// the channel demodulation: a setting like the ones above; FM's stream state (the carry) starts anew whenever the mode changes
+int fdc_pipeline_set_demod(fdc_pipeline *p, int32_t mode, float gain)
+{
+    FDC_ENTRY("fdc_pipeline_set_demod")
+    if (!p) return set_error(FDC_ERR_INVALID_ARGUMENT, "null handle");
+    if (mode != FDC_DEMOD_OFF && mode != FDC_DEMOD_FM && mode != FDC_DEMOD_MAG) return set_error(FDC_ERR_INVALID_ARGUMENT, "unknown demodulation mode %d", (int)mode);
+    if (mode && (!std::isfinite(gain) || gain == 0.0f)) return set_error(FDC_ERR_INVALID_ARGUMENT, "the demodulation gain must be finite and not zero");
+    if (p->hier_filled > 0)
+        return set_error(FDC_ERR_INVALID_ARGUMENT, "a pipelined sinks batch is still inside the handle: fdc_pipeline_flush_sinks until it returns 0 first");
+    if (mode && p->out_form)
+        return set_error(FDC_ERR_INVALID_ARGUMENT, "the channel demodulation writes real float32 samples: set the output format to FDC_OQ_FC32 first");
+    HIPCHK(hipSetDevice(p->cfg.device_id));
+    HIPCHK(hipStreamSynchronize(p->stream));          // (no call of the host entries is in flight; a device entry's caller orders its own stream)
+    if (!mode) { p->demod_mode = 0; p->demod_gain = 1.0f; p->demod_next = -1; p->demod_route.clear(); return FDC_OK; }
+    // everything the feature needs, once: the float staging the kernels write (integer output's) and the two carry buffers
+    RCCHK(out_staging(p));
+    for (int i = 0; i < 2; i++)
+        if (p->C > 0 && !p->d_carry[i]) HIPCHK(p->d_carry[i].alloc((size_t)p->C));
+    if (mode != p->demod_mode) p->demod_next = -1;    // switched on, or another mode: no sample in front of the next call (a new gain alone keeps it)
+    p->demod_mode = mode;
+    p->demod_gain = gain;
+    return FDC_OK;
+    FDC_ENTRY_END
+}
+
+int fdc_pipeline_demod(const fdc_pipeline *p, int32_t *mode, float *gain)
+{
+    FDC_ENTRY("fdc_pipeline_demod")
+    if (!p) return set_error(FDC_ERR_INVALID_ARGUMENT, "null handle");
+    if (mode) *mode = p->demod_mode;
+    if (gain) *gain = p->demod_gain;
+    return FDC_OK;
+    FDC_ENTRY_END
+}
+
+// the demodulating pass alone, on the caller's device buffers: the handle gives its channel table and nothing of its state is read or written
+int fdc_pipeline_demod_device(const fdc_pipeline *p, int32_t mode, float gain, const void *d_in, void *d_out, const void *d_carry_in, void *d_carry_out,
+                              int nblocks, void *stream)
+{
+    FDC_ENTRY("fdc_pipeline_demod_device")
+    if (!p) return set_error(FDC_ERR_INVALID_ARGUMENT, "null handle");
+    if (mode != FDC_DEMOD_FM && mode != FDC_DEMOD_MAG) return set_error(FDC_ERR_INVALID_ARGUMENT, "unknown demodulation mode %d", (int)mode);
+    if (!std::isfinite(gain) || gain == 0.0f) return set_error(FDC_ERR_INVALID_ARGUMENT, "the demodulation gain must be finite and not zero");
+    if (nblocks < 0) return set_error(FDC_ERR_INVALID_ARGUMENT, "negative block count");
+    if (nblocks == 0 || p->C <= 0) return FDC_OK;
+    if ((int64_t)nblocks * p->sum_lout * 8 > 0xFFFFF000ll)
+        return set_error(FDC_ERR_INVALID_ARGUMENT, "nblocks %d x %lld output samples per block is more than the 4 GiB one call may produce", nblocks, (long long)p->sum_lout);
+    if (!d_in || !d_out || (mode == FDC_DEMOD_FM && !d_carry_out)) return set_error(FDC_ERR_INVALID_ARGUMENT, "null device buffer");
+    if (mode == FDC_DEMOD_FM && d_carry_in == d_carry_out) return set_error(FDC_ERR_INVALID_ARGUMENT, "the carry is read from one buffer and written to another");
+    HIPCHK(hipSetDevice(p->cfg.device_id));
+    const bool fm = mode == FDC_DEMOD_FM;
+    HIPCHK(fdc::launch_chan_demod(mode, gain, static_cast<const float2 *>(d_in), static_cast<float *>(d_out), p->d_chans,
+                                  fm ? static_cast<const float2 *>(d_carry_in) : nullptr, fm ? static_cast<float2 *>(d_carry_out) : nullptr, p->C, nblocks,
+                                  (long long)p->sum_lout, stream ? static_cast<hipStream_t>(stream) : p->stream));
     return FDC_OK;
     FDC_ENTRY_END
 }

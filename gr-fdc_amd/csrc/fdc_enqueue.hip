@@ -137,7 +137,7 @@ static bool iq_fused(const fdc_pipeline *p, const DeviceCall &call, bool few)
 static bool path5(const fdc_pipeline *p, const DeviceCall &call) { return p->fused && !call.spectrum; }
 
 // THE RULE of the passes behind a plan's kernels (fdc_postpass.hip), on which oq_fused and PostPass both rest: they go over the kernels' complex
-// float results in the order rotation -> gain -> levels, lag-1 -> narrowing.  Path 5 turns its samples in its own stores; every other kernel leaves
+// float results in the order rotation -> gain -> levels, lag-1 -> narrowing or demodulation.  Path 5 turns its samples in its own stores; every other kernel leaves
 // fine tuning to the rotation pass.  The levels are of the float samples the caller gets (turned and gained), and the gain multiplies float samples.
 // The lag-1 correlation is of the same samples as the levels.
 // So a call with a rotation pass, gains, levels or lag-1 has its kernels store float, and narrows behind the last of them.
@@ -150,6 +150,7 @@ static bool float_passes(const fdc_pipeline *p, const DeviceCall &call) { return
 static bool oq_fused(const fdc_pipeline *p, const DeviceCall &call, int nblocks)
 {
     if (float_passes(p, call)) return false;  // THE RULE: float, the passes, then narrowed (every path, path 5 included)
+    if (oq_demod(call.ofmt)) return false;    // demodulation: never in a kernel's own stores
     if (!int_kernels(p, call)) return false;
     if (p->fused) return true;
     if (!(p->block_hints & 1) || (!call.fmt && p->N == 65536 && p->R == 4)) return false;
@@ -172,13 +173,16 @@ struct PostPass {
     const float *gain = nullptr;
     float2 *levels = nullptr;
     float2 *lag1 = nullptr;     // k_chan_lag1, always a pass of its own over the group's final float results: lag-1 on
+    int demod = 0;              // the call-wide k_chan_demod from the float staging, in the place of the narrowing: FDC_DEMOD_FM / _MAG
+    bool demod_cont = false;    //   ... FM: the call continues the stream of the last demodulating call, whose carry stands in front of its first sample
 };
 
 static PostPass post_pass(const fdc_pipeline *p, const DeviceCall &call, bool ofused)
 {
     PostPass pp;
     if (p->C <= 0) return pp;
-    const bool narrow = call.ofmt && !ofused && call.narrow;
+    pp.demod = oq_demod(call.ofmt) ? call.ofmt - kOqDemod : 0;
+    const bool narrow = call.ofmt && !pp.demod && !ofused && call.narrow;
     pp.gain = call.gain; pp.levels = call.levels; pp.lag1 = call.lag1;
     pp.fine_fused = p->fine_on && path5(p, call);
     pp.rotate = rotation_pass(p, call);
@@ -208,8 +212,17 @@ static int run_post_passes(const fdc_pipeline *p, const DeviceCall &call, const 
 }
 
 // behind the last launch group: the call-wide narrowing, and how the call was served (fdc_pipeline_describe)
-static int run_post_tail(fdc_pipeline *p, const DeviceCall &call, const PostPass &pp, int nblocks, void *d_out)
+static int run_post_tail(fdc_pipeline *p, const DeviceCall &call, const PostPass &pp, int64_t first_block, int nblocks, void *d_out)
 {
+    if (pp.demod) {
+        // FM reads one carry buffer and writes the other; behind the enqueue the written one is the handle's, for the call that goes on at the next block
+        const bool fm = pp.demod == FDC_DEMOD_FM;
+        HIPCHK(fdc::launch_chan_demod(pp.demod, call.oscale, call.fout, static_cast<float *>(d_out), p->d_chans,
+                                      fm && pp.demod_cont ? p->d_carry[p->carry_cur].get() : nullptr, fm ? p->d_carry[p->carry_cur ^ 1].get() : nullptr,
+                                      p->C, nblocks, (long long)p->sum_lout, call.stream));
+        if (fm) { p->carry_cur ^= 1; p->demod_next = first_block + nblocks; }
+        p->demod_route = fm ? "fm" : "mag";
+    }
     if (pp.narrow_tail) HIPCHK(fdc::launch_complex_to_iq(call.ofmt, call.oscale, call.fout, d_out, (size_t)nblocks * p->sum_lout, call.stream));
     if (pp.fine_fused || pp.rotate) p->fine_route = pp.fine_fused ? "fused" : "rotated";
     if (pp.levels) p->levels_route = pp.rot_levels ? "with the rotation" : pp.gain_pass ? "with the gains" : "pass";
@@ -244,7 +257,13 @@ int process_device_impl(fdc_pipeline *p, DeviceCall &call, const void *d_ring, i
     unsigned char *const ob = ofused ? static_cast<unsigned char *>(d_out) : reinterpret_cast<unsigned char *>(o);
     const bool use_poly = p->poly_ok && !d_spectrum;
     const unsigned out_bytes = (unsigned)((int64_t)nblocks * p->sum_lout * (int64_t)osz);
-    const PostPass pp = post_pass(p, call, ofused);      // what runs behind the kernels of every launch group and behind the call: decided here, once
+    PostPass pp = post_pass(p, call, ofused);            // what runs behind the kernels of every launch group and behind the call: decided here, once
+    if (pp.demod == FDC_DEMOD_FM) {
+        // the carry is the sample in front of this call's first only where the call goes on at the block after the last demodulating call's last;
+        // a call that fails from here on leaves nothing to continue
+        pp.demod_cont = p->demod_next == first_block;
+        p->demod_next = -1;
+    }
     // path 5: the call's part of every group's launch (the group's: its input, its blocks and its waterfall rows)
     fdc::F4Launch f4{};
     if (p->fused && !d_spectrum) {
@@ -368,7 +387,7 @@ int process_device_impl(fdc_pipeline *p, DeviceCall &call, const void *d_ring, i
             p->ev_spans.push_back(span);
         }
     }
-    RCCHK(run_post_tail(p, call, pp, nblocks, d_out));
+    RCCHK(run_post_tail(p, call, pp, first_block, nblocks, d_out));
     return FDC_OK;
 }
 
@@ -392,9 +411,15 @@ std::string route(int fmt, bool fused, const char *otherwise)
 // fdc_pipeline_set_output_format, never on this enqueue path) where the call's kernels do not narrow themselves
 // Channel levels (p->levels_on): the call's levels go to the handle's buffer ([max_blocks][C], allocated by fdc_pipeline_set_levels), so such a call
 // needs nblocks <= max_blocks too; nothing is enqueued otherwise.  The channel lag-1 correlation (p->lag1_on, d_lag1) likewise
+// Channel demodulation (p->demod_mode): the call's real output comes from the float staging too, so nblocks <= max_blocks as well
 static int process_device_oq(fdc_pipeline *p, DeviceCall &call, const void *d_ring, int64_t first_block, int nblocks, void *d_out)
 {
     const int ofmt = p->out_form;
+    if (p->demod_mode && nblocks > 0 && p->C > 0) {
+        if (nblocks > p->cfg.max_blocks) return set_error(FDC_ERR_INVALID_ARGUMENT, "channel demodulation: nblocks %d above max_blocks %d", nblocks, p->cfg.max_blocks);
+        if (!p->d_out && p->sum_lout > 0) return set_error(FDC_ERR_HIP, "channel demodulation: no float staging");
+        call.ofmt = out_code(p); call.oscale = p->demod_gain; call.fout = p->d_out;
+    }
     const bool lev = p->levels_on && nblocks > 0;
     if (lev) {
         if (nblocks > p->cfg.max_blocks) return set_error(FDC_ERR_INVALID_ARGUMENT, "channel levels: nblocks %d above max_blocks %d", nblocks, p->cfg.max_blocks);
@@ -475,6 +500,7 @@ int fdc_pipeline_process_device_power(fdc_pipeline *p, const void *d_ring, int64
     if (p->fine_on) return set_error(FDC_ERR_INVALID_ARGUMENT, "fdc_pipeline_process_device_power writes the channels as they are cut: switch fine tuning off first");
     if (p->levels_on) return set_error(FDC_ERR_INVALID_ARGUMENT, "fdc_pipeline_process_device_power gives no channel levels: switch them off first (fdc_pipeline_set_levels(p, 0))");
     if (p->lag1_on) return set_error(FDC_ERR_INVALID_ARGUMENT, "fdc_pipeline_process_device_power gives no channel lag-1 correlation: switch it off first (fdc_pipeline_set_lag1(p, 0))");
+    if (p->demod_mode) return set_error(FDC_ERR_INVALID_ARGUMENT, "fdc_pipeline_process_device_power writes complex float outputs only: switch the channel demodulation off first (fdc_pipeline_set_demod(p, FDC_DEMOD_OFF, 1))");
     if (p->gains_on) return set_error(FDC_ERR_INVALID_ARGUMENT, "fdc_pipeline_process_device_power writes the channels as they are cut: switch the channel gains off first (fdc_pipeline_set_gains(p, NULL, C))");
     if (d_group_power && (!d_spectrum || (p->N & 15))) return set_error(FDC_ERR_INVALID_ARGUMENT, "group powers go with a spectrum output of a block length that is a multiple of 16");
     DeviceCall call = device_call(p, stream, d_spectrum);

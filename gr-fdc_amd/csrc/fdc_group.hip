@@ -195,6 +195,13 @@ int group_work(fdc_pipeline_group *g, const void *in, int nblocks, void *const *
             return fdc::set_error(FDC_ERR_INVALID_ARGUMENT, "the group's members have different output formats (set it with fdc_pipeline_group_set_output_format)");
     }
     const size_t osz = ofmt ? fdc::iq_bytes(ofmt) : 2 * sizeof(float);
+    // the channel demodulation has no group form: its 4-byte samples would misplace the spans, and the first sample of a span has no predecessor on
+    // its member's device
+    for (fdc_pipeline *pm : g->mem) {
+        int32_t dm = FDC_DEMOD_OFF;
+        if (fdc_pipeline_demod(pm, &dm, nullptr) != FDC_OK || dm != FDC_DEMOD_OFF)
+            return fdc::set_error(FDC_ERR_INVALID_ARGUMENT, "a member has the channel demodulation on, which the group entries do not serve: switch it off first (fdc_pipeline_set_demod(member, FDC_DEMOD_OFF, 1))");
+    }
     if (fmt && (fmt != FDC_IQ_SC16 && fmt != FDC_IQ_SC8)) return fdc::set_error(FDC_ERR_INVALID_ARGUMENT, "unknown complex integer format %d", fmt);
     if (fmt && (!std::isfinite(scale) || scale == 0.0f)) return fdc::set_error(FDC_ERR_INVALID_ARGUMENT, "the scale must be finite and not zero");
     if (g->in_form >= 0 && (g->in_form != fmt || (fmt && std::memcmp(&g->in_scale, &scale, sizeof(float)) != 0)))

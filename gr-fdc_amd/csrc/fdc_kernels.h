@@ -257,6 +257,14 @@ hipError_t launch_chan_gain(float2 *out, const ChanDev *chans, const float *gain
 hipError_t launch_chan_lag1(const float2 *out, const ChanDev *chans, const float *gain, float2 *lag1, int nchan, int nb_chunk, int mbase, int nb_call,
                             hipStream_t s);
 
+// Channel demodulation (fdc_pipeline_set_demod): the whole call's channel-major float results `in` (nb_call blocks) read once, one real float32 per
+// sample to the same element offset of `out`.  mode: kDemodFm / kDemodMag = FDC_DEMOD_FM / FDC_DEMOD_MAG.  FM: carry_in[c] is the sample in front of
+// channel c's first (null: none, the stream starts anew) and carry_out[c] receives its last; two different buffers of nchan float2.  MAG uses neither.
+// sum_lout: the plan's output samples per block (sizes the grid)
+enum { kDemodFm = 1, kDemodMag = 2 };
+hipError_t launch_chan_demod(int mode, float gain, const float2 *in, float *out, const ChanDev *chans, const float2 *carry_in, float2 *carry_out, int nchan,
+                             int nb_call, long long sum_lout, hipStream_t s);
+
 hipError_t launch_scale(const float2 *in, float2 *out, size_t n, float k, hipStream_t s);
 
 // sinks

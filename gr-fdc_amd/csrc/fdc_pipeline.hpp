@@ -189,6 +189,16 @@ struct fdc_pipeline {
     std::vector<float> gains;
     fdc::DevBuf<float> d_gain;
     std::string gains_route;     // how the last call with gains was served (fdc_pipeline_describe)
+    // channel demodulation (fdc_pipeline_set_demod): a setting like the ones above.  demod_mode: FDC_DEMOD_OFF / _FM / _MAG, demod_gain its factor.
+    // d_carry: FM's stream state, the last complex float sample of every channel of the last demodulating call, two buffers of C: a call reads
+    // d_carry[carry_cur] where it continues the stream (its first_block is demod_next; -1: the stream starts anew) and its kernel writes the other one;
+    // the enqueue path swaps behind a successful enqueue.  Both, and the float staging d_out, are allocated by the first call that switches it on.
+    int demod_mode = 0;
+    float demod_gain = 1.f;
+    fdc::DevBuf<float2> d_carry[2];
+    int carry_cur = 0;
+    int64_t demod_next = -1;
+    std::string demod_route;     // which demodulation the last call with the setting on ran (fdc_pipeline_describe)
     fdc::DevBuf<float2> d_out;   // work(): max_blocks*sum_lout (out_staging)
     int64_t blockcount = 0;      // work(): blocks consumed so far
     // work(): transfers and kernels of consecutive sub-batches overlap (H2D on s_in, kernels on stream, D2H on s_out)
@@ -232,6 +242,8 @@ struct DeviceCall {
     int fmt = 0; float scale = 1.0f; float2 *wide = nullptr;
     // output form.  ofmt: 0 = complex float into d_out; FDC_OQ_SC16 / FDC_OQ_SC8 (times oscale): narrow samples into d_out (same offsets).  Kernels that do not
     // narrow themselves (oq_fused) write float into fout (nblocks*sum_lout samples); k_complex_to_iq narrows it into d_out unless narrow is false (the caller does)
+    // Channel demodulation (fdc_pipeline_set_demod) rides ofmt as two private codes of 4 bytes per sample, kOqDemod + FDC_DEMOD_FM / _MAG, with its gain in
+    // oscale: never fused (the kernels write float into fout) and never left to the caller (narrow stays true): k_chan_demod is the call's tail
     int ofmt = 0; float oscale = 1.0f; float2 *fout = nullptr; bool narrow = true;
     hipStream_t stream = nullptr;        // every launch of the call
     void *spectrum = nullptr;            // the caller's spectrum buffer for the blocks of this invocation, or none
@@ -257,6 +269,14 @@ struct DeviceCall {
 // which form a timed launch group ran (ev_spans[.][4]): how the three intervals between its four events map to ms[0..2]
 enum { kSpanBanks = 0 /* banks | remainder forward | remainder channels */, kSpanTwoLaunch = 1 /* stage 1 | - | stage 2 (+ remainder) */,
        kSpanSpectrumLds = 2 /* forward transform = a + b | channels */, kSpanSpectrum = 3 /* pass A / block forward | pass B | channels */ };
+
+// the private output codes of channel demodulation (DeviceCall::ofmt), and the bytes per sample of any output code
+constexpr int kOqDemod = 16;
+inline bool oq_demod(int ofmt) { return ofmt > kOqDemod; }
+inline size_t oq_bytes(int ofmt) { return oq_demod(ofmt) ? sizeof(float) : fdc::iq_bytes(ofmt); }
+// the output code of the handle's next call: demodulation while it is on (it excludes integer output; a plan without channels has nothing to
+// demodulate), else the output format
+inline int out_code(const fdc_pipeline *p) { return p->demod_mode && p->C > 0 ? kOqDemod + p->demod_mode : p->out_form; }
 
 inline bool ispow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
 

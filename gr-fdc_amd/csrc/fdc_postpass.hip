@@ -1,6 +1,7 @@
 // gfx950 (MI355X, CDNA4) kernels of the frequency-domain channelizer — the passes that run BEHIND a plan's kernels, over the channel-major float
 // results of a launch group: the rotation of fine tuning (k_fine_rotate), the channel gains (k_chan_gain), the channel levels (k_chan_levels), the
-// channel lag-1 correlation (k_chan_lag1) and the narrowing to complex integers (k_complex_to_iq).  Which of them a call runs, and in which order, is
+// channel lag-1 correlation (k_chan_lag1) and the narrowing to complex integers (k_complex_to_iq) — and, over a whole call's float results in the
+// place of the narrowing, the channel demodulation (k_chan_demod, at the end of this file).  Which of them a call runs, and in which order, is
 // decided once per call: PostPass, fdc_enqueue.hip.
 //
 // One shape for the four per-channel kernels: grid y = channel, a row — the lout samples of one (block, channel) — on a power-of-two set of lanes of one
@@ -487,6 +488,117 @@ hipError_t launch_chan_gain(float2 *out, const ChanDev *chans, const float *gain
                                    static_cast<decltype(t) *>(kNarrow ? nar : nullptr), scale, levels, c0, nchan, nb_chunk, mbase, (long long)nb_call);
             });
         });
+    });
+}
+
+// Channel demodulation (fdc_pipeline_set_demod): one real float32 sample per complex float32 sample of a call's channel-major float results, 8 bytes
+// read and 4 written per sample.  FM: d[t] = gain * atan2f(Im P, Re P), P = y[t] conj(y[t - 1]) with lag_add's products (every product and sum
+// rounded on its own); where both components of P compare equal to zero d[t] = +0 (a silent channel, a stream start: no +-pi from signed zeros).
+// MAG: d[t] = gain * sqrt(re re + im im), the products, the sum and the correctly rounded root each rounded on their own.
+template <int MODE>
+__device__ __forceinline__ float demod_one(cf a, cf b, float gain)
+{
+#pragma clang fp contract(off)
+    if constexpr (MODE == kDemodFm) {
+        const float p = a.x * b.x, q = a.y * b.y;
+        const float re = p + q;
+        const float u = a.y * b.x, v = a.x * b.y;
+        const float im = u - v;
+        const float d = gain * atan2f(im, re);
+        return re == 0.0f && im == 0.0f ? 0.0f : d;
+    } else {
+        const float p = a.x * a.x, q = a.y * a.y;
+        const float s = p + q;
+        // (sqrtf is the correctly rounded root: hipcc's default, and the Makefile has no fast-math flag.  __fsqrt_rn is the native, 1 ulp instruction in
+        // this HIP unless OCML_BASIC_ROUNDED_OPERATIONS is defined)
+        return gain * sqrtf(s);
+    }
+}
+
+// One channel's run of the call: T = nblocks * lout consecutive samples y -> d (a channel's stream is contiguous across the blocks of a call, so the
+// sample in front of y[t] is y[t - 1] whatever the block).  A wave takes 256 consecutive samples per trip, a lane four of them: two 16-byte loads and
+// one 16-byte store (WIDE: both runs 16-byte aligned; the run's last lane may hold fewer than four), else four 8-byte loads and up to four 4-byte
+// stores; the arithmetic is the same, so both give the same bits.  All loads of a trip are issued before the first is used; a lane past the run's
+// end loads its last sample and stores nothing.  FM: the sample in front of a lane's first comes from the lane below (lane_below, run by the whole
+// wave: the trip count depends on the wave alone and the move stands outside every per-lane condition, as in lag1_rows); lane 0 loads it, 8 bytes
+// more: the element in front of the wave's 256, or at t = 0 the carry (cin; null: the stream starts anew, zero).  The lane that holds y[T - 1]
+// writes it to cout, the carry of the next call: another buffer than cin, so no workgroup reads what another writes.
+template <int MODE, bool WIDE>
+__device__ __forceinline__ void demod_run(const float2 *y, float *d, unsigned T, float gain, const float2 *cin, float2 *cout)
+{
+    const unsigned lane = threadIdx.x & 63;
+    const unsigned wave = blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = gridDim.x * 4;
+    for (unsigned base = wave * 256; base < T; base += nwaves * 256) {
+        const unsigned t = base + 4 * lane;
+        const bool full = t + 4 <= T;
+        cf v[4];
+        if (WIDE && full) {
+            const float4 lo = ld4(y + t), hi = ld4(y + t + 2);
+            v[0] = mk(lo.x, lo.y); v[1] = mk(lo.z, lo.w); v[2] = mk(hi.x, hi.y); v[3] = mk(hi.z, hi.w);
+        } else {
+#pragma unroll
+            for (unsigned j = 0; j < 4; j++) v[j] = ld2(y + (t + j < T ? t + j : T - 1));
+        }
+        float r[4];
+        if constexpr (MODE == kDemodFm) {
+            cf front = mk(0.0f, 0.0f);
+            if (lane == 0) {
+                if (base) front = ld2(y + base - 1);
+                else if (cin) front = ld2(cin);
+            }
+            const cf below = lane_below(v[3]);
+            const cf prev = lane ? below : front;
+            r[0] = demod_one<MODE>(v[0], prev, gain);
+#pragma unroll
+            for (unsigned j = 1; j < 4; j++) r[j] = demod_one<MODE>(v[j], v[j - 1], gain);
+#pragma unroll
+            for (unsigned j = 0; j < 4; j++)
+                if (t + j + 1 == T) st2(cout, v[j]);
+        } else {
+#pragma unroll
+            for (unsigned j = 0; j < 4; j++) r[j] = demod_one<MODE>(v[j], v[j], gain);
+        }
+        if (WIDE && full) {
+            *reinterpret_cast<float4 *>(d + t) = make_float4(r[0], r[1], r[2], r[3]);
+        } else {
+#pragma unroll
+            for (unsigned j = 0; j < 4; j++)
+                if (t + j < T) d[t + j] = r[j];
+        }
+    }
+}
+
+// in: the call's float results ([channel][nb_call * lout] float2 at nb_call * out_off); out: its real output, the same element offsets.  carry_in
+// (null: no sample in front) and carry_out: [nchan] float2, FM only
+template <int MODE>
+__global__ __launch_bounds__(256) void k_chan_demod(const float2 *__restrict__ in, float *__restrict__ out, const ChanDev *__restrict__ chans,
+                                                    const float2 *__restrict__ carry_in, float2 *__restrict__ carry_out, float gain, int c0,
+                                                    long long nb_call)
+{
+    const int c = c0 + (int)blockIdx.y;
+    const long long run = nb_call * chans[c].out_off;
+    const unsigned T = (unsigned)(nb_call * chans[c].lout);
+    const float2 *y = in + run;
+    float *d = out + run;
+    const float2 *cin = carry_in ? carry_in + c : nullptr;
+    float2 *cout = MODE == kDemodFm ? carry_out + c : nullptr;
+    if (((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(d)) & 15) == 0) demod_run<MODE, true>(y, d, T, gain, cin, cout);
+    else demod_run<MODE, false>(y, d, T, gain, cin, cout);
+}
+
+// mode kDemodFm / kDemodMag; sum_lout: the plan's output samples per block (the grid: a wave per 256 samples of a run of mean length)
+hipError_t launch_chan_demod(int mode, float gain, const float2 *in, float *out, const ChanDev *chans, const float2 *carry_in, float2 *carry_out, int nchan,
+                             int nb_call, long long sum_lout, hipStream_t s)
+{
+    if (nchan <= 0 || nb_call <= 0) return hipSuccess;
+    if (mode != kDemodFm && mode != kDemodMag) return hipErrorInvalidValue;
+    if (mode == kDemodFm && !carry_out) return hipErrorInvalidValue;
+    const long long trips = ((long long)nb_call * sum_lout / nchan + 255) / 256;
+    return channel_grids(nchan, (int)std::max<long long>(1, std::min<long long>(trips, 1 << 20)), [&](dim3 grid, int c0) {
+        if (mode == kDemodFm)
+            hipLaunchKernelGGL(k_chan_demod<kDemodFm>, grid, dim3(256), 0, s, in, out, chans, carry_in, carry_out, gain, c0, (long long)nb_call);
+        else
+            hipLaunchKernelGGL(k_chan_demod<kDemodMag>, grid, dim3(256), 0, s, in, out, chans, carry_in, carry_out, gain, c0, (long long)nb_call);
     });
 }
 

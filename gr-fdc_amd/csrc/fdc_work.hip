@@ -11,7 +11,8 @@ extern "C" {
 
 // the entries that write complex float only (sinks, spectrum items, group powers, waterfall): refused while the output format is not FC32
 // (and, but for the flush of a batch that is inside already, while fine tuning is on: they write the channels as they are cut; and while channel
-// levels or the lag-1 correlation are on: they give none; and while channel gains are on: they write the channels as they are cut)
+// levels or the lag-1 correlation are on: they give none; and while channel gains are on: they write the channels as they are cut; and while the
+// channel demodulation is on: their channel outputs are complex float)
 static int check_float_output(const fdc_pipeline *p, const char *entry, bool writes_channels = true)
 {
     if (p && p->out_form) return set_error(FDC_ERR_INVALID_ARGUMENT, "%s writes complex float outputs only: set the output format to FDC_OQ_FC32 first", entry);
@@ -19,6 +20,7 @@ static int check_float_output(const fdc_pipeline *p, const char *entry, bool wri
     if (p && p->levels_on && writes_channels) return set_error(FDC_ERR_INVALID_ARGUMENT, "%s gives no channel levels: switch them off first (fdc_pipeline_set_levels(p, 0))", entry);
     if (p && p->lag1_on && writes_channels) return set_error(FDC_ERR_INVALID_ARGUMENT, "%s gives no channel lag-1 correlation: switch it off first (fdc_pipeline_set_lag1(p, 0))", entry);
     if (p && p->gains_on && writes_channels) return set_error(FDC_ERR_INVALID_ARGUMENT, "%s writes the channels as they are cut: switch the channel gains off first (fdc_pipeline_set_gains(p, NULL, C))", entry);
+    if (p && p->demod_mode && writes_channels) return set_error(FDC_ERR_INVALID_ARGUMENT, "%s writes complex float outputs only: switch the channel demodulation off first (fdc_pipeline_set_demod(p, FDC_DEMOD_OFF, 1))", entry);
     return FDC_OK;
 }
 
@@ -102,7 +104,7 @@ static int begin_work(fdc_pipeline *p, int fmt, float scale)
     RCCHK(check_form(p, fmt, scale));
     HIPCHK(hipSetDevice(p->cfg.device_id));
     RCCHK(work_io_setup(p));
-    if (p->out_form && !p->d_oq && p->sum_lout > 0) HIPCHK(p->d_oq.alloc(fdc::kIqRingBytes * (size_t)p->cfg.max_blocks * p->sum_lout));
+    if (out_code(p) && !p->d_oq && p->sum_lout > 0) HIPCHK(p->d_oq.alloc(fdc::kIqRingBytes * (size_t)p->cfg.max_blocks * p->sum_lout));
     if (fmt && !p->d_iq) {
         // the integer ring, for the WIDEST format (a reset may latch the handle to another one); its history starts at zero, as the float ring's
         HIPCHK(p->d_iq.alloc(fdc::kIqRingBytes * ((size_t)p->ovl + (size_t)p->cfg.max_blocks * p->H)));
@@ -150,6 +152,8 @@ struct SpanStart { bool span; const void *halo; int64_t first_block; };
 // (d_iq), the integer kernels read it where the plan has them, the handle's float ring takes the widened launch groups otherwise.
 // Integer output (p->out_form): the kernels narrow into d_oq where the plan lets them (oq_fused), else they write d_out and k_complex_to_iq narrows it
 // into d_oq; registered outputs are scattered from either (k_scatter_oq: narrowing from d_out, copying from d_oq), staged ones copied from d_oq.
+// Channel demodulation (p->demod_mode; it excludes integer output) goes the same way with its 4-byte real samples: the kernels write d_out, k_chan_demod
+// writes d_oq behind every sub-batch, registered outputs are scattered from d_oq by the copy form (a real float32 is the size of an sc16 sample).
 static int pipeline_work_impl(fdc_pipeline *p, DeviceCall call, const void *in, int nblocks, void *const *outs, void *spectrum, SpanStart from = {})
 {
     int rc = check_work_args(p, in, nblocks, outs);
@@ -159,9 +163,10 @@ static int pipeline_work_impl(fdc_pipeline *p, DeviceCall call, const void *in, 
     RCCHK(begin_work(p, fmt, call.scale));
     hipStream_t s = p->stream;
     const size_t nin = (size_t)nblocks * p->H, esz = fdc::iq_bytes(fmt);
-    const int ofmt = p->out_form;
-    const float oscale = p->out_scale;
-    const size_t osz = ofmt ? fdc::iq_bytes(ofmt) : sizeof(float2);       // bytes per output sample the caller receives
+    const int ofmt = out_code(p);
+    const bool demod = oq_demod(ofmt);
+    const float oscale = demod ? p->demod_gain : p->out_scale;
+    const size_t osz = ofmt ? oq_bytes(ofmt) : sizeof(float2);            // bytes per output sample the caller receives
     // the ring the call's samples go to, as bytes: float2 (d_ring) or the integer format (d_iq)
     unsigned char *const ringb = fmt ? static_cast<unsigned char *>(p->d_iq) : reinterpret_cast<unsigned char *>(p->d_ring.get());
     const unsigned char *hin = static_cast<const unsigned char *>(in);
@@ -179,7 +184,7 @@ static int pipeline_work_impl(fdc_pipeline *p, DeviceCall call, const void *in, 
     const bool in_reg = host_registered(in, esz * nin);
     const bool out_reg = fill_scatter_table(p, outs, nblocks, osz);
     call.wide = fmt ? p->d_ring : nullptr;
-    call.ofmt = ofmt; call.oscale = oscale; call.narrow = !out_reg;
+    call.ofmt = ofmt; call.oscale = oscale; call.narrow = !out_reg || demod;
     bool oq_all = true;
     // dok: the float results of the sub-batch starting at block b0.  Integer output: its narrow results go to the same sample offset of d_oq (call.ofused: the
     // kernels wrote them there themselves; otherwise dok holds float and is narrowed into d_oq, unless the outputs are registered: k_scatter_oq narrows)
@@ -199,6 +204,7 @@ static int pipeline_work_impl(fdc_pipeline *p, DeviceCall call, const void *in, 
     };
     auto scatter = [&](size_t b0, int nb, hipStream_t st) -> hipError_t {
         if (!ofmt) return fdc::launch_scatter_out(p->d_out + b0 * (size_t)p->sum_lout, p->d_tab, p->C, nb, (long long)b0, st);
+        if (demod) return fdc::launch_scatter_oq(fdc::kIqSc16, res(b0), fdc::kIqSc16, 1.0f, p->d_tab, p->C, nb, (long long)b0, st);   // 4-byte elements, copied
         return call.ofused ? fdc::launch_scatter_oq(ofmt, res(b0), ofmt, oscale, p->d_tab, p->C, nb, (long long)b0, st)
                       : fdc::launch_scatter_oq(fdc::kIqFloat, p->d_out + b0 * (size_t)p->sum_lout, ofmt, oscale, p->d_tab, p->C, nb, (long long)b0, st);
     };
@@ -237,7 +243,7 @@ static int pipeline_work_impl(fdc_pipeline *p, DeviceCall call, const void *in, 
         if (p->levels_on) levels_written(p, nblocks, s, true);
     if (p->lag1_on) lag1_written(p, nblocks, s, true);
         if (fmt) p->iq_route = route(fmt, call.all_fused, "widened");
-        if (ofmt) p->oq_route = route(ofmt, oq_all, "narrowed");
+        if (p->out_form) p->oq_route = route(ofmt, oq_all, "narrowed");
         if (p->C > 0 && !out_reg) deliver(0, 0, nblocks);
         p->blockcount += nblocks;
         return nblocks;
@@ -303,7 +309,7 @@ static int pipeline_work_impl(fdc_pipeline *p, DeviceCall call, const void *in, 
     if (p->levels_on) levels_written(p, nblocks, s, true);
     if (p->lag1_on) lag1_written(p, nblocks, s, true);
     if (fmt) p->iq_route = route(fmt, call.all_fused, "widened");
-    if (ofmt) p->oq_route = route(ofmt, oq_all, "narrowed");
+    if (p->out_form) p->oq_route = route(ofmt, oq_all, "narrowed");
     p->blockcount += nblocks;
     return nblocks;
 }
@@ -393,12 +399,13 @@ static int pipeline_work_real_impl(fdc_pipeline *p, const void *in, int nblocks,
     } else {
         HIPCHK(fdc::launch_real_to_complex(p->d_real + p->ovl, p->d_ring + p->ovl, nin, s));
     }
-    // integer output (p->out_form): the narrow results in d_oq (the kernels' own stores, or k_complex_to_iq behind them), copied as they are
-    const int ofmt = p->out_form;
-    const size_t osz = ofmt ? fdc::iq_bytes(ofmt) : sizeof(float2);
+    // integer output (p->out_form): the narrow results in d_oq (the kernels' own stores, or k_complex_to_iq behind them), copied as they are;
+    // channel demodulation (p->demod_mode): the real results in d_oq likewise
+    const int ofmt = out_code(p);
+    const size_t osz = ofmt ? oq_bytes(ofmt) : sizeof(float2);
     void *const res = ofmt ? static_cast<void *>(p->d_oq) : static_cast<void *>(p->d_out);
     DeviceCall call = device_call(p, nullptr, d_specfull);
-    call.ofmt = ofmt; call.oscale = p->out_scale; call.fout = p->d_out;
+    call.ofmt = ofmt; call.oscale = oq_demod(ofmt) ? p->demod_gain : p->out_scale; call.fout = p->d_out;
     call.levels = p->levels_on && p->C > 0 ? p->d_levels.get() : nullptr;
     call.lag1 = p->lag1_on && p->C > 0 ? p->d_lag1.get() : nullptr;
     RCCHK(process_device_impl(p, call, p->d_ring, p->blockcount, nblocks, res));
@@ -409,7 +416,7 @@ static int pipeline_work_real_impl(fdc_pipeline *p, const void *in, int nblocks,
     HIPCHK(hipStreamSynchronize(s));
     if (p->levels_on) levels_written(p, nblocks, s, true);
     if (p->lag1_on) lag1_written(p, nblocks, s, true);
-    if (ofmt) p->oq_route = route(ofmt, call.ofused, "narrowed");
+    if (p->out_form) p->oq_route = route(ofmt, call.ofused, "narrowed");
     p->blockcount += nblocks;
     return nblocks;
 }

@@ -307,6 +307,54 @@ int fdc_pipeline_set_lag1(fdc_pipeline *p, int32_t on);
 int fdc_pipeline_lag1(fdc_pipeline *p, float *dst, int nblocks);
 void *fdc_pipeline_lag1_device(fdc_pipeline *p);
 
+/* CHANNEL DEMODULATION: the FM discriminator (GNU Radio's quadrature_demod_cf) or the envelope (complex_to_mag) of every channel, on the device, as the
+ * last pass over the float results: cut -> fine tuning -> gain -> levels, lag-1 -> demodulation, in the place the sc16 / sc8 narrowing has.  While the
+ * setting is on, every channel's output stream is REAL float32, 4 bytes per sample: the same number of samples in the same channel-major layout
+ * (device entries: channel c's nblocks*lout_c elements start at ELEMENT offset nblocks*out_off_c of d_out; host entries: outs[c] is
+ * float[nblocks*lout_c]).  With y[t] the complex float32 sample the entry would write with the setting off (after fine tuning and the channel gain;
+ * levels and lag-1 stay those of y):
+ *   FDC_DEMOD_FM    P = y[t] conj(y[t-1]) = (a.x b.x + a.y b.y, a.y b.x - a.x b.y) with a = y[t], b = y[t-1], every product and sum rounded on its own
+ *                   (lag-1's term); d[t] = float32(gain * atan2f(Im P, Re P)).  Where both components of P compare equal to zero d[t] = +0.0f: a silent
+ *                   channel and a stream start give zeros, not +-pi from signed zeros.  NaN propagates.  gain = 1 / (2 pi) gives cycles per output
+ *                   sample, the unit of fdc_pipeline_set_fine_tuning and of arg(S) / (2 pi) of the lag-1 correlation.
+ *                   |d[t] - gain theta| <= |gain| (5 + 13 |theta|) 2^-24 modulo 2 pi |gain|, theta the exact angle of the exact product of the float32
+ *                   samples, where |y[t]| |y[t-1]| >= 2^-60.
+ *   FDC_DEMOD_MAG   d[t] = float32(gain * sqrt(float32(float32(re re) + float32(im im)))), the square root correctly rounded: numpy states it bit
+ *                   for bit in float32.  It needs no state and uses none.
+ * THE SAMPLE IN FRONT (FM): inside a call y[t-1] is the element before y[t] in the channel's run (a channel's stream is contiguous across the blocks of
+ * a call).  In front of a call's first sample stands the handle's CARRY, the last y of each channel of the previous call, held on the device: it is used
+ * when the call CONTINUES the stream, that is when its first_block is the block after the last block of the previous successful demodulating call;
+ * for fdc_pipeline_work and its kin that is always so between resets, and the sub-batches a host entry cuts its call into are linked the same way.
+ * Otherwise the stream starts anew, y[-1] = 0 and d[0] = +0: a device or span entry elsewhere in the stream, the first call after create or
+ * fdc_pipeline_reset, after switching from OFF, after a change of mode, after a call that failed once it had begun to enqueue (a call that is REFUSED
+ * for its arguments or the handle's settings enqueues nothing and leaves the carry as it was: the next call may still continue the stream).  A change of gain alone keeps the carry.  The bits of d
+ * depend on the stream's samples and the setting only: not on how the stream is cut into calls, sub-batches, launch groups or chunks, nor on the route.
+ *   fdc_pipeline_set_demod   mode FDC_DEMOD_OFF / _FM / _MAG; gain finite and not zero (ignored with OFF); anything else FDC_ERR_INVALID_ARGUMENT and
+ *                            the previous setting stays in force.  A SETTING like the ones above: it applies from the next call, does not touch the
+ *                            history, the block counter or the input-form latch, and survives fdc_pipeline_reset (the carry does not); refused while a
+ *                            pipelined sinks batch is inside the handle; it waits for the handle's own stream first.  The first call that switches it
+ *                            on allocates two carry buffers of C float2 and the float staging of integer output (max_blocks*sum_lout samples), once;
+ *                            the host entries' 4-byte staging is allocated at their first such call; nothing in the steady state, nothing inside a
+ *                            device entry.  While it is on a device call needs nblocks <= max_blocks.
+ *   fdc_pipeline_demod       the setting in force (either pointer may be NULL).
+ * EXCLUSIVE with integer output: set_demod(FM / MAG) is refused while the output format is not FDC_OQ_FC32, and fdc_pipeline_set_output_format(sc16 /
+ * sc8) while the demodulation is on.  While it is on, fdc_pipeline_work_sinks, _work_spectrum, _process_device_power and fdc_pipeline_work_waterfall
+ * return FDC_ERR_INVALID_ARGUMENT and change nothing, and so do the group's work entries when a member has it on (there is no group setter: 4-byte
+ * samples would misplace the spans, and a span's first sample has no predecessor on its device).  fdc_pipeline_describe: "demod: fm" / "demod: mag"
+ * after a call that ran it. */
+enum { FDC_DEMOD_OFF = 0, FDC_DEMOD_FM = 1, FDC_DEMOD_MAG = 2 };
+int fdc_pipeline_set_demod(fdc_pipeline *p, int32_t mode, float gain);
+int fdc_pipeline_demod(const fdc_pipeline *p, int32_t *mode, float *gain);
+/* The demodulating pass alone, for complex channel streams that are on the device already (and the entry the footprint tests reach the kernel by):
+ * d_in holds one call's complex float32 results in the layout fdc_pipeline_process_device writes (nblocks blocks, channel c at element offset
+ * nblocks*out_off_c), d_out receives the real float32 samples at the same element offsets.  FM: d_carry_in (C float2, NULL: nothing stands in front,
+ * the stream starts anew) is read, d_carry_out (C float2, another buffer, not NULL) receives the last complex sample of every channel; MAG ignores
+ * both.  Exactly 4*nblocks*sum_lout bytes of d_out and, in FM, C float2 of d_carry_out are written, enqueued on `stream` (NULL: the handle's).  The
+ * handle gives its channel table only: its setting, its own carry and its stream position are neither read nor changed, whatever its setting is.
+ * mode other than FM / MAG, a gain that is zero or not finite, nblocks < 0, a NULL buffer: FDC_ERR_INVALID_ARGUMENT, nothing enqueued. */
+int fdc_pipeline_demod_device(const fdc_pipeline *p, int32_t mode, float gain, const void *d_in, void *d_out, const void *d_carry_in, void *d_carry_out,
+                              int nblocks, void *stream);
+
 /* Optional: pin a host range that will be handed to fdc_pipeline_work() again and again (GNU Radio's circular buffers
  * live as long as the flowgraph: register them in start(), unregister in stop()).  A call whose `in` lies in a
  * registered range is DMA'd from it in place, and when every outs[c] does, the results are stored straight into
