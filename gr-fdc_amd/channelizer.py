@@ -338,6 +338,25 @@ def lag1_frequency(s):
     return np.angle(np.asarray(s, dtype=np.complex128)) / (2.0 * np.pi)
 
 
+AUDIO_MAX_DECIM, AUDIO_MAX_TAPS = 64, 256
+
+
+def lowpass_taps(decim, ntaps, cutoff=None):
+    """A low-pass for decimating a demodulated port (Pipeline.set_demod) by `decim`, 1 .. 64, on the host today (GNU Radio's fir_filter_fff): a
+    Hamming-windowed sinc of ntaps taps, 1 .. 256, with its cutoff (the -6 dB point) at `cutoff` cycles per input sample (default 0.5 / decim, the
+    output rate's Nyquist frequency), designed in float64, normalised to unit DC gain and returned as float32."""
+    if isinstance(decim, bool) or not isinstance(decim, (int, np.integer)) or not 1 <= int(decim) <= AUDIO_MAX_DECIM:
+        raise ValueError("the audio decimation is an integer in 1 .. %d" % AUDIO_MAX_DECIM)
+    if isinstance(ntaps, bool) or not isinstance(ntaps, (int, np.integer)) or not 1 <= int(ntaps) <= AUDIO_MAX_TAPS:
+        raise ValueError("ntaps is an integer in 1 .. %d" % AUDIO_MAX_TAPS)
+    fc = 0.5 / int(decim) if cutoff is None else float(cutoff)
+    if not 0.0 < fc <= 0.5:
+        raise ValueError("the cutoff is in (0, 0.5] cycles per sample")
+    n = np.arange(int(ntaps), dtype=np.float64) - (int(ntaps) - 1) / 2.0
+    h = 2.0 * fc * np.sinc(2.0 * fc * n) * np.hamming(int(ntaps))
+    return (h / h.sum()).astype(np.float32)
+
+
 class Pipeline(_OutputFormat):
     """fdc_pipeline handle: channels = [(f, l, passbw, stopbw), ...]."""
     _last_nb = None        # block count of the last work call that had blocks (levels())
