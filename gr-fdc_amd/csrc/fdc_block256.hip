@@ -12,7 +12,8 @@
 //       n2 = 16a + b of its column.  Both 16 x 16 exchanges of the FFT-256 / IFFT-256 pair stay inside the wave
 //       (a private 8.5 KiB LDS scratch, in-order LDS queue, no s_barrier), so the eight waves drift apart and one
 //       wave's LDS phases overlap the other waves' DFT-16 arithmetic.  The next pass's rows are loaded into
-//       registers a pass ahead: at the top of the pass, or (SPREAD) four at a time between its phases.  The 8 kept outputs t = b + 16q, q >= 8, of every pass go
+//       registers a pass ahead: at the top of the pass into a second row set, or (SPREAD) four at a time between its phases — at P >= 4 into the
+//       registers the pass computes on, dead by then, with the lane's twiddle row in the second set's place (kBlkOneSet).  The 8 kept outputs t = b + 16q, q >= 8, of every pass go
 //       into the G registers (indexed by the pass: s_set_gpr_idx).
 //   stage 2, 2 chunks of 64 rows t': the FFT-256 over n1 = 32 pass + c5 starts with a DFT-8 over the pass index, which
 //       is the register index of G (no exchange), then W_256^(c5 klo), then ONE trip through LDS ([row][klo][c5]) to the
@@ -77,6 +78,15 @@ constexpr bool kBlkSpread = !OFF && !FWD && !(P == 8 && (R4 || !std::is_same<TO,
 // takes 7 - 16 SGPRs more): profiles/srow/NOTES.md.
 template <int P, bool OFF, bool FWD, bool R4>
 constexpr bool kBlkSrow = P == 8 && !OFF && !FWD && !R4;
+
+// Which forms of k_blk256 run stage 1 on ONE row set, with the lane's twiddle row W_256^(b p) held in registers for the length of a block's stage 1
+// (one_pass, the pass loop): the spread forms at P >= 4.  A spread pass is done with its rows at its first exchange write (22 % of the pass); with the
+// first group of the next pass's loads behind that write instead of behind the first dft16, all sixteen land in the registers they are used from, and the
+// second set's 32 registers hold the row that every pass otherwise reads from LDS twice (forward, and conjugated for the inverse).  The spread forms are
+// never offset plans: one row serves both uses.  Not P = 2: two workgroups per CU there, 128 registers each, and the row does not fit beside G and the
+// rows (128 VGPRs with 10 of them spilled to 44 bytes of scratch, against 126 and none): profiles/one_row_set/NOTES.md.
+template <int P, bool SPREAD>
+constexpr bool kBlkOneSet = SPREAD && P >= 4;
 
 template <int P, bool SROW = false>
 struct BlkGeom {
@@ -153,6 +163,7 @@ __global__ FDC_PLAIN_DS __launch_bounds__(512, (P == 2 && !OFF && !R4 && !FWD) ?
                                                 typename IqTail<TI, TO>::type gpow /* integer TI / TO: iq_scale / oq_scale */)
 {
     constexpr bool kSrow = kBlkSrow<P, OFF, FWD, R4>;
+    constexpr bool kOne = kBlkOneSet<P, SPREAD>;
     typedef BlkGeom<P, kSrow> GM;
     constexpr bool kIq = !std::is_same<TI, float2>::value, kOq = !std::is_same<TO, float2>::value;
     static_assert(!SPREAD || kBlkSpread<P, OFF, FWD, R4, TO>, "no spread form of this one");
@@ -212,8 +223,9 @@ __global__ FDC_PLAIN_DS __launch_bounds__(512, (P == 2 && !OFF && !R4 && !FWD) ?
     // P = 2 only (kSplit reads cb from LDS): cbt[n1][b], n1 = 32 pass + c5, from memory, requested a pass ahead into cbA / cbB
     [[maybe_unused]] const __amdgpu_buffer_rsrc_t rcb = make_rsrc(cbt, (unsigned)kN1 * 16u * 8u);
     [[maybe_unused]] const unsigned voffc = (unsigned)(c5 * 16 + b) * 8u;
-    // two row sets: a pass computes on one while the rows of the next pass arrive in the other (no register copies between passes)
-    cf LA[16], LB[16], cbA = mk(1.f, 0.f), cbB = cbA;           // (kSplit: cbA / cbB stay what they are here and are never read)
+    // two row sets: a pass computes on one while the rows of the next pass arrive in the other (no register copies between passes); kBlkOneSet: LA
+    // alone (LB / cbB are never touched there; declared inside the block loop they change the code of the P = 2 forms)
+    [[maybe_unused]] cf LA[16], LB[16], cbA = mk(1.f, 0.f), cbB = cbA;   // (kSplit: cbA / cbB stay what they are here and are never read)
     {
         const __amdgpu_buffer_rsrc_t rin = make_rsrc(in + (size_t)first * in_stride, inbytes);
 #pragma unroll
@@ -305,6 +317,9 @@ __global__ FDC_PLAIN_DS __launch_bounds__(512, (P == 2 && !OFF && !R4 && !FWD) ?
 #define FDC_GGET(j, ps) unpack_cf(G[j][ps])
 #define FDC_GPUT(j, ps, val) G[j][ps] = pack_cf(val)
         // ---------------- stage 1 ----------------
+        // kBlkOneSet: the lane's twiddle row W_256^(b p), p = 1 ... 15, for every pass of this block
+        [[maybe_unused]] cf twk[16];
+        if constexpr (kOne) ld_row_sh<false>(twk, wr);
         // One pass per trip.  The 16 rows of this lane's column were requested a whole pass ago into L; the rows of the next
         // pass (of this block, or pass 0 of this workgroup's next block; after the last block: the same rows again, unused)
         // are requested first, unconditionally (a conditional request costs a second set of register copies).
@@ -340,6 +355,8 @@ __global__ FDC_PLAIN_DS __launch_bounds__(512, (P == 2 && !OFF && !R4 && !FWD) ?
             // (39 %), the first inverse dft16 (65 %) and the second exchange (84 %): profiles/spread_loads/NOTES.md.  L is dead from the previous
             // pass's first exchange write on, and this pass's rows are consumed by its first dft16: the waits at the top of a pass cover the
             // previous pass's loads only.  A full scheduling fence in front of a group holds it in its place.
+            // kBlkOneSet: L is cur itself, whose rows are dead from this pass's first exchange write on: the first group goes behind that write
+            // (22 %), the others are where they were.
             auto ld_rows = [&](auto group) __attribute__((always_inline)) {
                 constexpr int g = decltype(group)::value;
                 if constexpr (SPREAD) {
@@ -368,10 +385,16 @@ __global__ FDC_PLAIN_DS __launch_bounds__(512, (P == 2 && !OFF && !R4 && !FWD) ?
             };
             [[maybe_unused]] u32x8 pc[2];
             dft16<false>(cur);                                    // in place, over a: index p in cur[rev16(p)]
-            ld_rows(std::integral_constant<int, 0>{});
+            if constexpr (!kOne) ld_rows(std::integral_constant<int, 0>{});
             if constexpr (kSrow) { pc[0] = ld_piece(0); pc[1] = ld_piece(1); }
+            // kBlkOneSet: the twiddle row is the block's (twk, registers), for this use and for the inverse's below; no LDS read here, and the pieces
+            // just requested are waited for with the exchange read
             cf tw[16];
-            ld_row_sh<OFF>(tw, wrf);
+            if constexpr (kOne) {
+#pragma unroll
+                for (int p = 1; p < 16; p++) tw[p] = twk[p];
+            } else
+                ld_row_sh<OFF>(tw, wrf);
             if constexpr (OFF) {
 #pragma unroll
                 for (int p = 0; p < 16; p++) st2(&scrw[68 * ((p - r16) & 15)], cmul(cur[rev16(p)], tw[p]));
@@ -380,6 +403,7 @@ __global__ FDC_PLAIN_DS __launch_bounds__(512, (P == 2 && !OFF && !R4 && !FWD) ?
 #pragma unroll
                 for (int p = 1; p < 16; p++) st2(&scrw[68 * p], cmul(cur[rev16(p)], tw[p]));
             }
+            if constexpr (kOne) ld_rows(std::integral_constant<int, 0>{});   // cur is dead: the next pass's rows 0 ... 3 into it
             __builtin_amdgcn_wave_barrier();                      // same wave, in-order LDS queue: no s_barrier
             cf v[16];
             strip_get(v, scrr);
@@ -434,7 +458,7 @@ __global__ FDC_PLAIN_DS __launch_bounds__(512, (P == 2 && !OFF && !R4 && !FWD) ?
                 }
                 dft16<true>(u);
                 ld_rows(std::integral_constant<int, 2>{});
-                ld_row_sh<false>(tw, wr);
+                if constexpr (!kOne) ld_row_sh<false>(tw, wr);
                 u[rev16(0)] = cmul(u[rev16(0)], cb);
 #pragma unroll
                 for (int p = 1; p < 16; p++) u[rev16(p)] = cmul(cmulc(u[rev16(p)], tw[p]), cb);
@@ -454,6 +478,8 @@ __global__ FDC_PLAIN_DS __launch_bounds__(512, (P == 2 && !OFF && !R4 && !FWD) ?
         };
         // two passes per trip: the row sets swap roles (the pass count is even for every P).  The offset-plan variant at P = 8 has no
         // registers for the second set's live range (32 bytes of scratch): it copies the rows at the top of a pass as before.
+        // kBlkOneSet: every pass computes on LA and loads the next pass's rows into it; the second set's registers hold the twiddle row, read here
+        // once per block (not once per workgroup: stage 2 needs the registers — G 128, the prefetched rows 32, its 32 points 64)
         if constexpr (OFF && P == 8) {
 #pragma nounroll
             for (int ps = 0; ps < P; ps++) {
@@ -461,6 +487,12 @@ __global__ FDC_PLAIN_DS __launch_bounds__(512, (P == 2 && !OFF && !R4 && !FWD) ?
 #pragma unroll
                 for (int a = 0; a < 16; a++) cur[a] = LA[a];
                 one_pass(ps, cur, cbA, LA, cbA);
+            }
+        } else if constexpr (kOne) {
+#pragma nounroll
+            for (int pp = 0; pp < P; pp += 2) {
+                one_pass(pp, LA, cbA, LA, cbA);
+                one_pass(pp + 1, LA, cbA, LA, cbA);
             }
         } else {
 #pragma nounroll
