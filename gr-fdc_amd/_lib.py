@@ -113,7 +113,14 @@ SYMBOLS = {
     "fdc_pipeline_set_demod": (C.c_int, [_vp, C.c_int32, C.c_float]),
     "fdc_pipeline_demod": (C.c_int, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_float)]),
     "fdc_pipeline_demod_device": (C.c_int, [_vp, C.c_int32, C.c_float, _vp, _vp, _vp, _vp, C.c_int, _vp]),
-    "fdc_pipeline_set_gains": (C.c_int, [_vp, C.POINTER(C.c_float), C.c_int]),
+    "fdc_pipeline_set_audio": (C.c_int, [_vp, C.c_int32, C.POINTER(C.c_float), C.c_int32, C.c_int32, C.c_float]),
+    "fdc_pipeline_audio_setting": (C.c_int, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_float),
+                                             C.POINTER(C.c_float)]),
+    "fdc_pipeline_audio_row": (C.c_int64, [_vp]),
+    "fdc_pipeline_audio": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int]),
+    "fdc_pipeline_audio_device": (_vp, [_vp]),
+    "fdc_pipeline_audio_pass_device": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, _vp]),
+    "fdc_pipeline_set_gains": (C.c_int,[_vp, C.POINTER(C.c_float), C.c_int]),
     "fdc_pipeline_gains": (C.c_int, [_vp, C.POINTER(C.c_float), C.c_int]),
     "fdc_pipeline_group_set_gains": (C.c_int, [_vp, C.POINTER(C.c_float), C.c_int]),
     "fdc_pipeline_group_create": (C.c_int, [C.POINTER(fdc_pipeline_cfg), C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(_vp)]),

@@ -341,8 +341,49 @@ def lag1_frequency(s):
 AUDIO_MAX_DECIM, AUDIO_MAX_TAPS = 64, 256
 
 
+AUDIO_F32, AUDIO_S16 = 0, 1       # FDC_AUDIO_F32, FDC_AUDIO_S16 (include/fdc_amd.h)
+_AUDIO_FORMATS = {"f32": AUDIO_F32, "s16": AUDIO_S16}
+_AUDIO_DTYPES = {AUDIO_F32: np.float32, AUDIO_S16: np.int16}
+
+
+def _audio_args(decim, taps, fmt, scale):
+    """Pipeline.set_audio: (decim, float32 taps, FDC_AUDIO_* code, float32 scale), (0, None, 0, 1) for decim None.  Raises before any library call."""
+    if decim is None:
+        return 0, None, AUDIO_F32, np.float32(1.0)
+    if isinstance(decim, bool) or not isinstance(decim, (int, np.integer)) or not 1 <= int(decim) <= AUDIO_MAX_DECIM:
+        raise ValueError("the audio decimation is an integer in 1 .. %d (None: off)" % AUDIO_MAX_DECIM)
+    if taps is None:
+        raise ValueError("the audio needs its taps (lowpass_taps)")
+    with np.errstate(over="ignore"):
+        h = np.ascontiguousarray(taps, dtype=np.float32).reshape(-1)
+    if not 1 <= h.size <= AUDIO_MAX_TAPS:
+        raise ValueError("the audio filter has 1 .. %d taps" % AUDIO_MAX_TAPS)
+    if not np.isfinite(h).all():
+        raise ValueError("the audio taps must be finite (tap %d is not)" % int(np.flatnonzero(~np.isfinite(h))[0]))
+    if not isinstance(fmt, str) or fmt.lower() not in _AUDIO_FORMATS:
+        raise ValueError("the audio format is 'f32' or 's16'")
+    code = _AUDIO_FORMATS[fmt.lower()]
+    with np.errstate(over="ignore"):
+        sc = np.float32(scale)
+    if code == AUDIO_S16 and (not np.isfinite(sc) or sc == 0):
+        raise ValueError("the audio scale must be finite and not zero")
+    return int(decim), h, code, sc if code == AUDIO_S16 else np.float32(1.0)
+
+
+def audio_channels(mat, lout, decim):
+    """The [nb, A] block-major audio matrix of a call (Pipeline.audio) as one array per channel: channel c owns the lout_c / decim columns from
+    sum(lout_i / decim, i < c) on, and its stream is those columns of all rows, row after row."""
+    mat = np.asarray(mat)
+    per = [int(lo) // int(decim) for lo in lout]
+    if mat.ndim != 2 or mat.shape[1] != sum(per):
+        raise ValueError("the audio matrix has %d columns, one per audio sample of a block of every channel" % sum(per))
+    at = np.concatenate([[0], np.cumsum(per)]).astype(np.int64)
+    return [np.ascontiguousarray(mat[:, at[c]:at[c + 1]]).reshape(-1) for c in range(len(per))]
+
+
 def lowpass_taps(decim, ntaps, cutoff=None):
-    """A low-pass for decimating a demodulated port (Pipeline.set_demod) by `decim`, 1 .. 64, on the host today (GNU Radio's fir_filter_fff): a
+    """A low-pass for decimating a demodulated port (Pipeline.set_demod) by `decim`, 1 .. 64: the taps of Pipeline.set_audio, which runs the filter on
+    the device behind the demodulation (GNU Radio's fir_filter_fff). A
     Hamming-windowed sinc of ntaps taps, 1 .. 256, with its cutoff (the -6 dB point) at `cutoff` cycles per input sample (default 0.5 / decim, the
     output rate's Nyquist frequency), designed in float64, normalised to unit DC gain and returned as float32."""
     if isinstance(decim, bool) or not isinstance(decim, (int, np.integer)) or not 1 <= int(decim) <= AUDIO_MAX_DECIM:
@@ -485,6 +526,81 @@ class Pipeline(_OutputFormat):
         _lib.check(_lib.lib().fdc_pipeline_demod(self._h, C.byref(mode), C.byref(gain)))
         return ({0: None, DEMOD_FM: "fm", DEMOD_MAG: "mag"}[mode.value], float(gain.value))
 
+    _audio = 0             # the decimation set_audio switched on (0: off): the early refusal of outs= only; sizes are asked of the library at every call
+
+    def set_audio(self, decim, taps=None, fmt="f32", scale=1.0):
+        """fdc_pipeline_set_audio: decim None switches it off; else decim 1 .. 64 that divides every lout_c, taps (converted to float32; 1 .. 256,
+        finite; lowpass_taps), fmt "f32" or "s16", scale (s16 only) finite and not zero.  It needs the demodulation (set_demod) and runs behind it, on
+        the device: a[n] = sum over k of taps[k] d[n decim - k] in float32, k ascending from +0, every product and sum rounded on its own; "s16":
+        saturate(rint(a * scale)) as int16 (NaN -> 0).  While it is on, work*, work_span* and work_iq* return one AUDIO array per channel, nblocks *
+        lout_c / decim samples of float32 or int16, and take no outs=; process_device* write the demodulated ports as before and the audio is fetched
+        with audio() or read at audio_device().  The K - 1 demodulated samples in front of a call's first are the tail of the call before where the
+        call goes on at the next block, zeros at a stream start (after create, reset(), a new decim or taps, a switch of demodulation mode, a device
+        or span call elsewhere in the stream); a new fmt, scale or demodulation gain keeps them.  A setting like set_demod: it applies from the next
+        call and survives reset().  ValueError for arguments out of range (nothing reaches the library), FdcError where the library refuses
+        (demodulation off, decim does not divide a channel's lout, a pipelined sinks batch inside); nothing changes then."""
+        d, h, code, sc = _audio_args(decim, taps, fmt, scale)
+        _lib.check(_lib.lib().fdc_pipeline_set_audio(self._h, d, None if h is None else h.ctypes.data_as(C.POINTER(C.c_float)), 0 if h is None else int(h.size),
+                                                     code, float(sc)))
+        self._audio = d
+
+    def audio_setting(self):
+        """fdc_pipeline_audio_setting: None while off, else (decim, float32 taps, "f32" / "s16", scale): what the library has in force now."""
+        d, k, f, sc = C.c_int32(0), C.c_int32(0), C.c_int32(0), C.c_float(0)
+        taps = np.zeros(AUDIO_MAX_TAPS, dtype=np.float32)
+        _lib.check(_lib.lib().fdc_pipeline_audio_setting(self._h, C.byref(d), C.byref(k), C.byref(f), C.byref(sc), taps.ctypes.data_as(C.POINTER(C.c_float))))
+        if d.value == 0:
+            return None
+        return int(d.value), taps[:k.value].copy(), {AUDIO_F32: "f32", AUDIO_S16: "s16"}[f.value], float(sc.value)
+
+    def audio(self, nblocks=None):
+        """fdc_pipeline_audio: the audio of the last call, [nblocks, A] float32 or int16, A = sum of lout_c / decim: row m is block m of the call, channel
+        c its columns from sum(lout_i / decim, i < c) on (audio_channels slices it).  nblocks: the last call's block count where it did not go
+        through this object's work methods (process_device, work_raw).  The array is sized from what the library says its setting is now, and the
+        library is told that size."""
+        if nblocks is None:
+            if self._last_nb is None:
+                raise ValueError("audio(): no work call yet")
+            nblocks = self._last_nb
+        nblocks = int(nblocks)
+        if nblocks < 0:
+            raise ValueError("audio(): negative block count")
+        setting = self.audio_setting()
+        if setting is None:
+            raise ValueError("audio(): the channel audio is off (set_audio)")
+        out = np.empty((nblocks, int(_lib.lib().fdc_pipeline_audio_row(self._h))), dtype=_AUDIO_DTYPES[_AUDIO_FORMATS[setting[2]]])
+        if out.size:
+            _lib.check(_lib.lib().fdc_pipeline_audio(self._h, out.ctypes.data, out.nbytes, nblocks))
+        return out
+
+    def audio_device(self):
+        """fdc_pipeline_audio_device: the device address of the audio ([block of the last call][A] float32 / int16), None while it is off."""
+        return _lib.lib().fdc_pipeline_audio_device(self._h)
+
+    def audio_pass_device(self, d_in, d_out, nblocks, d_hist_in=None, d_hist_out=None, stream=None):
+        """fdc_pipeline_audio_pass_device: the audio pass alone on device buffers of the caller, with the setting in force (d_in: float32 in
+        process_device's layout, d_out: nblocks * A elements, d_hist_in: C (K - 1) float32 or None, d_hist_out: another such buffer, None only where
+        K = 1).  The handle's own history and stream position are not touched."""
+        _lib.check(_lib.lib().fdc_pipeline_audio_pass_device(self._h, d_in, d_out, d_hist_in, d_hist_out, int(nblocks), stream))
+
+    def _host_outs(self, outs, nb):
+        """(outs, ptrs) of a host call.  While the channel audio is on — asked of the library at this call — the entries write no port: (None, None),
+        and outs= is refused."""
+        if outs is not None and getattr(self, "_audio", 0):
+            raise ValueError("outs= cannot go with the channel audio: the call returns the audio arrays (set_audio)")
+        if getattr(self, "_h", None) and self.audio_setting() is not None:
+            if outs is not None:
+                raise ValueError("outs= cannot go with the channel audio: the call returns the audio arrays (set_audio)")
+            return None, None
+        outs = self._check_outs(outs, nb)
+        return outs, (C.c_void_p * max(1, len(outs)))(*[o.ctypes.data for o in outs])
+
+    def _host_results(self, outs, nb):
+        """what a host call returns: its outs, or (the audio on: _host_outs gave None) one audio array per channel, sliced from the matrix"""
+        if outs is not None:
+            return outs
+        return audio_channels(self.audio(nb), self.lout, self.audio_setting()[0])
+
     def _ran(self, nb):
         self._call_nb = int(nb)
         if nb > 0:
@@ -499,8 +615,7 @@ class Pipeline(_OutputFormat):
         if x.size % self.H:
             raise ValueError("input must be a whole number of (N - N/R)-sample items")
         nb = x.size // self.H
-        outs = self._check_outs(outs, nb)
-        ptrs = (C.c_void_p * max(1, len(outs)))(*[o.ctypes.data for o in outs])
+        outs, ptrs = self._host_outs(outs, nb)
         spec = np.empty(nb * self.N, dtype=np.complex64) if want_spectrum else None
         if sinks is not None:
             _lib.check(_lib.lib().fdc_pipeline_work_sinks(self._h, x.ctypes.data, nb, ptrs,
@@ -509,6 +624,7 @@ class Pipeline(_OutputFormat):
             _lib.check(_lib.lib().fdc_pipeline_work(self._h, x.ctypes.data, nb, ptrs,
                                                    spec.ctypes.data if spec is not None else None))
         self._ran(nb)
+        outs = self._host_results(outs, nb)
         return (outs, spec) if want_spectrum else outs
 
     def work_waterfall(self, x, waterfall):
@@ -547,12 +663,12 @@ class Pipeline(_OutputFormat):
         if x.size % self.H:
             raise ValueError("input must be a whole number of (N - N/R)-sample items")
         nb = x.size // self.H
-        outs = self._new_outs(nb)
-        ptrs = (C.c_void_p * max(1, len(outs)))(*[o.ctypes.data for o in outs])
+        outs, ptrs = self._host_outs(None, nb)
         spec = np.empty(nb * self.N, dtype=np.complex64) if want_spectrum else None
         _lib.check(_lib.lib().fdc_pipeline_work_real(self._h, x.ctypes.data, nb, ptrs,
                                                     spec.ctypes.data if spec is not None else None))
         self._ran(nb)
+        outs = self._host_results(outs, nb)
         return (outs, spec) if want_spectrum else outs
 
     def work_iq(self, x, scale=1.0, want_spectrum=False, outs=None):
@@ -562,12 +678,12 @@ class Pipeline(_OutputFormat):
         latches the handle's input form (float, or this format and scale): a call in another form raises FdcError.  outs: as work()."""
         x, fmt, n, sc = _iq_input(x, scale, self.H)
         nb = n // self.H
-        outs = self._check_outs(outs, nb)
-        ptrs = (C.c_void_p * max(1, len(outs)))(*[o.ctypes.data for o in outs])
+        outs, ptrs = self._host_outs(outs, nb)
         spec = np.empty(nb * self.N, dtype=np.complex64) if want_spectrum else None
         _lib.check(_lib.lib().fdc_pipeline_work_iq(self._h, fmt, float(sc), x.ctypes.data, nb, ptrs,
                                                   spec.ctypes.data if spec is not None else None))
         self._ran(nb)
+        outs = self._host_results(outs, nb)
         return (outs, spec) if want_spectrum else outs
 
     def work_span_iq(self, halo, x, first_block, scale=1.0, want_spectrum=False):
@@ -580,12 +696,12 @@ class Pipeline(_OutputFormat):
                 raise ValueError("halo: N/R samples of the input's format")
             hp = halo.ctypes.data
         nb = n // self.H
-        outs = self._new_outs(nb)
-        ptrs = (C.c_void_p * max(1, len(outs)))(*[o.ctypes.data for o in outs])
+        outs, ptrs = self._host_outs(None, nb)
         spec = np.empty(nb * self.N, dtype=np.complex64) if want_spectrum else None
         _lib.check(_lib.lib().fdc_pipeline_work_span_iq(self._h, fmt, float(sc), hp, x.ctypes.data, int(first_block), nb, ptrs,
                                                        spec.ctypes.data if spec is not None else None))
         self._ran(nb)
+        outs = self._host_results(outs, nb)
         return (outs, spec) if want_spectrum else outs
 
     def work_raw(self, in_ptr, nblocks, out_ptrs):
@@ -834,7 +950,7 @@ class FrequencyDomainChannelizer:
                  pow_act_maxblocks, act_det_maxblocks,
                  debug, device_id=0, max_blocks=64, devices=None, pipelined=False, waterfall=None, iq_input=None, iq_scale=1.0,
                  iq_output=None, iq_output_scale=1.0, fine_tuning=False, *, payload_format=None, payload_scale=1.0, levels=False, gains=None, lag1=False,
-                 demod=None, demod_gain=1.0):
+                 demod=None, demod_gain=1.0, audio_decim=None, audio_taps=None, audio_format="f32", audio_scale=1.0):
         # pipelined (not an argument of the reference): the sink blocks run beside the front end of the FOLLOWING work() calls, as the
         # thread-per-block scheduler runs them beside the FFT in the reference (fdc_pipeline_work_sinks on a look-ahead bank,
         # include/fdc_amd.h): same PDUs, handed out one or two work() calls later; flush() at the end of the stream
@@ -969,6 +1085,19 @@ class FrequencyDomainChannelizer:
             if devices is not None and len(devices) > 1:
                 raise ValueError("demod needs one device: the group entries do not serve the channel demodulation")
 
+        # audio_decim / audio_taps / audio_format / audio_scale (not arguments of the reference): the decimating low-pass behind every demodulated port
+        # (fir_filter_fff with decimation audio_decim), on the device (Pipeline.set_audio): the ports come back at the audio rate, lout_c / audio_decim
+        # samples per block, as float32 or ("s16") int16.  It needs demod and its taps (lowpass_taps), and carries the refusals of demod
+        self.audio_decim, self.audio_taps, self.audio_format, self.audio_scale = audio_decim, audio_taps, audio_format, float(audio_scale)
+        if audio_decim is not None:
+            if demod is None:
+                raise ValueError("audio_decim needs demod: the audio filter runs behind the channel demodulation")
+            if audio_taps is None:
+                raise ValueError("audio_decim needs audio_taps (lowpass_taps)")
+            _audio_args(audio_decim, audio_taps, audio_format, audio_scale)
+        elif audio_taps is not None:
+            raise ValueError("audio_taps needs audio_decim")
+
         # gains (not an argument of the reference): one output gain per throughput channel, applied on the device behind fine tuning and in front of the
         # levels and of iq_output's narrowing (Pipeline.set_gains); set_gains() changes them between work() calls (an AGC fed from self.levels)
         self.gains = None if gains is None else _check_gains(len(self.throughput_channels), gains)
@@ -1043,6 +1172,8 @@ class FrequencyDomainChannelizer:
             self.pipeline.set_lag1(True)
         if self.demod is not None:
             self.pipeline.set_demod(self.demod, self.demod_gain)
+        if self.audio_decim is not None:
+            self.pipeline.set_audio(self.audio_decim, self.audio_taps, self.audio_format, self.audio_scale)
         self.N_throughput_channelizers = len(self.channel_params)
         # waterfall (not an argument of the reference, whose example flowgraph wires the spectrum to complex_to_mag_squared and
         # FDC.WaterfallMsgTagging outside the hier block): a gr_fdc_amd.Waterfall fed from the spectrum on the device; work() then

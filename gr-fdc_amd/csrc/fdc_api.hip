@@ -412,6 +412,7 @@ int32_t fdc_pipeline_describe(const fdc_pipeline *p, char *buf, int32_t n)
     if (!p->gains_route.empty()) add("; gains: %s", p->gains_route.c_str());
     if (!p->lag1_route.empty()) add("; lag1: %s", p->lag1_route.c_str());
     if (!p->demod_route.empty()) add("; demod: %s", p->demod_route.c_str());
+    if (!p->audio_route.empty()) add("; audio: %s", p->audio_route.c_str());
     std::snprintf(buf, (size_t)n, "%s", t);
     return k;
 }
@@ -487,6 +488,8 @@ void fdc_pipeline_reset(fdc_pipeline *p)
     p->lag1_route.clear();       // (and the channel lag-1 correlation)
     p->demod_route.clear();      // (and the channel demodulation, whose stream starts anew: no carry in front of the next call)
     p->demod_next = -1;
+    p->audio_route.clear();      // (and the channel audio, whose history does not survive either)
+    p->audio_next = -1;
 }
 
 int fdc_pipeline_set_output_format(fdc_pipeline *p, int32_t format, float scale)
@@ -657,6 +660,8 @@ int fdc_pipeline_set_demod(fdc_pipeline *p, int32_t mode, float gain)
         return set_error(FDC_ERR_INVALID_ARGUMENT, "a pipelined sinks batch is still inside the handle: fdc_pipeline_flush_sinks until it returns 0 first");
     if (mode && p->out_form)
         return set_error(FDC_ERR_INVALID_ARGUMENT, "the channel demodulation writes real float32 samples: set the output format to FDC_OQ_FC32 first");
+    if (!mode && p->audio_decim)
+        return set_error(FDC_ERR_INVALID_ARGUMENT, "the channel audio filters the demodulated samples: switch the audio off first (fdc_pipeline_set_audio(p, 0, NULL, 0, 0, 1))");
     HIPCHK(hipSetDevice(p->cfg.device_id));
     HIPCHK(hipStreamSynchronize(p->stream));          // (no call of the host entries is in flight; a device entry's caller orders its own stream)
     if (!mode) { p->demod_mode = 0; p->demod_gain = 1.0f; p->demod_next = -1; p->demod_route.clear(); return FDC_OK; }
@@ -664,7 +669,8 @@ int fdc_pipeline_set_demod(fdc_pipeline *p, int32_t mode, float gain)
     RCCHK(out_staging(p));
     for (int i = 0; i < 2; i++)
         if (p->C > 0 && !p->d_carry[i]) HIPCHK(p->d_carry[i].alloc((size_t)p->C));
-    if (mode != p->demod_mode) p->demod_next = -1;    // switched on, or another mode: no sample in front of the next call (a new gain alone keeps it)
+    if (mode != p->demod_mode) p->demod_next = p->audio_next = -1;    // switched on, or another mode: no sample in front of the next call, no history in
+                                                                      // front of its audio (a new gain alone keeps both)
     p->demod_mode = mode;
     p->demod_gain = gain;
     return FDC_OK;
@@ -700,6 +706,125 @@ int fdc_pipeline_demod_device(const fdc_pipeline *p, int32_t mode, float gain, c
     HIPCHK(fdc::launch_chan_demod(mode, gain, static_cast<const float2 *>(d_in), static_cast<float *>(d_out), p->d_chans,
                                   fm ? static_cast<const float2 *>(d_carry_in) : nullptr, fm ? static_cast<float2 *>(d_carry_out) : nullptr, p->C, nblocks,
                                   (long long)p->sum_lout, stream ? static_cast<hipStream_t>(stream) : p->stream));
+    return FDC_OK;
+    FDC_ENTRY_END
+}
+
+// the channel audio: a setting that needs the demodulation; everything it needs is allocated here, once per size, and the stream state (the history)
+// starts anew whenever the filter changes
+int fdc_pipeline_set_audio(fdc_pipeline *p, int32_t decim, const float *taps, int32_t ntaps, int32_t format, float scale)
+{
+    FDC_ENTRY("fdc_pipeline_set_audio")
+    if (!p) return set_error(FDC_ERR_INVALID_ARGUMENT, "null handle");
+    if (decim) {
+        if (decim < 1 || decim > 64) return set_error(FDC_ERR_INVALID_ARGUMENT, "the audio decimation %d is not in 1 .. 64", (int)decim);
+        if (ntaps < 1 || ntaps > 256 || !taps) return set_error(FDC_ERR_INVALID_ARGUMENT, "the audio filter has 1 .. 256 taps");
+        for (int k = 0; k < ntaps; k++)
+            if (!std::isfinite(taps[k])) return set_error(FDC_ERR_INVALID_ARGUMENT, "audio tap %d is not finite", k);
+        if (format != FDC_AUDIO_F32 && format != FDC_AUDIO_S16) return set_error(FDC_ERR_INVALID_ARGUMENT, "unknown audio format %d", (int)format);
+        if (format == FDC_AUDIO_S16 && (!std::isfinite(scale) || scale == 0.0f)) return set_error(FDC_ERR_INVALID_ARGUMENT, "the audio scale must be finite and not zero");
+    }
+    if (p->hier_filled > 0)
+        return set_error(FDC_ERR_INVALID_ARGUMENT, "a pipelined sinks batch is still inside the handle: fdc_pipeline_flush_sinks until it returns 0 first");
+    if (decim && !p->demod_mode)
+        return set_error(FDC_ERR_INVALID_ARGUMENT, "the channel audio filters the demodulated samples: switch the channel demodulation on first (fdc_pipeline_set_demod)");
+    for (int c = 0; decim && c < p->C; c++)
+        if (p->chans[(size_t)c].lout % decim)
+            return set_error(FDC_ERR_INVALID_ARGUMENT, "the audio decimation %d does not divide the %d output samples per block of channel %d", (int)decim,
+                             (int)p->chans[(size_t)c].lout, c);
+    HIPCHK(hipSetDevice(p->cfg.device_id));
+    HIPCHK(hipStreamSynchronize(p->stream));          // (no call of the host entries is in flight; a device entry's caller orders its own stream)
+    if (!decim) {
+        p->audio_decim = 0; p->audio_format = FDC_AUDIO_F32; p->audio_scale = 1.0f; p->audio_taps.clear(); p->audio_row = 0;
+        p->audio_next = -1; p->aud_blocks = -1; p->audio_route.clear();
+        return FDC_OK;
+    }
+    // the audio's own prefix sums, in channel order (not out_off, which copies of a channel may share)
+    std::vector<long long> aoff((size_t)std::max(p->C, 1), 0);
+    long long row = 0;
+    for (int c = 0; c < p->C; c++) { aoff[(size_t)c] = row; row += p->chans[(size_t)c].lout / decim; }
+    // everything the feature needs, once per size: the taps and the columns, the two histories, the rows of the longest call (4 bytes per element: the
+    // wider format) and their pinned twin
+    const size_t nh = (size_t)p->C * (size_t)(ntaps - 1), na = sizeof(float) * (size_t)p->cfg.max_blocks * (size_t)row;
+    if (!p->d_ataps) HIPCHK(p->d_ataps.alloc(256));
+    if (p->C > 0 && !p->d_aoff) HIPCHK(p->d_aoff.alloc((size_t)p->C));
+    for (int i = 0; i < 2; i++)
+        if (nh > p->d_ahist[i].capacity()) HIPCHK(p->d_ahist[i].reserve(nh, nh));
+    if (na > p->d_audio.capacity()) HIPCHK(p->d_audio.reserve(na, na));
+    if (na > p->pin_audio.capacity()) HIPCHK(p->pin_audio.reserve(na, na));
+    HIPCHK(hipMemcpy(p->d_ataps, taps, sizeof(float) * (size_t)ntaps, hipMemcpyHostToDevice));
+    if (p->C > 0) HIPCHK(hipMemcpy(p->d_aoff, aoff.data(), sizeof(long long) * (size_t)p->C, hipMemcpyHostToDevice));
+    // a new decimation or other taps: another filter, whose stream starts anew; a new format or scale alone keeps the history.  The rows of the last call
+    // are in the format and the width of the setting they were made with: a new format or decimation leaves none to fetch
+    const bool same = p->audio_decim == decim && p->audio_taps.size() == (size_t)ntaps && std::memcmp(p->audio_taps.data(), taps, sizeof(float) * (size_t)ntaps) == 0;
+    if (!same) p->audio_next = -1;
+    if (p->audio_decim != decim || p->audio_format != format) p->aud_blocks = -1;
+    p->audio_decim = decim; p->audio_format = format; p->audio_scale = format == FDC_AUDIO_S16 ? scale : 1.0f;
+    p->audio_taps.assign(taps, taps + ntaps);
+    p->audio_row = row;
+    return FDC_OK;
+    FDC_ENTRY_END
+}
+
+int fdc_pipeline_audio_setting(const fdc_pipeline *p, int32_t *decim, int32_t *ntaps, int32_t *format, float *scale, float *taps)
+{
+    FDC_ENTRY("fdc_pipeline_audio_setting")
+    if (!p) return set_error(FDC_ERR_INVALID_ARGUMENT, "null handle");
+    if (decim) *decim = p->audio_decim;
+    if (ntaps) *ntaps = (int32_t)p->audio_taps.size();
+    if (format) *format = p->audio_format;
+    if (scale) *scale = p->audio_scale;
+    if (taps) std::copy(p->audio_taps.begin(), p->audio_taps.end(), taps);
+    return FDC_OK;
+    FDC_ENTRY_END
+}
+
+int64_t fdc_pipeline_audio_row(const fdc_pipeline *p) { return p && p->audio_decim ? p->audio_row : 0; }
+
+// the audio rows of the last call: never more than the caller says its buffer holds
+int fdc_pipeline_audio(fdc_pipeline *p, void *dst, size_t capacity_bytes, int nblocks)
+{
+    FDC_ENTRY("fdc_pipeline_audio")
+    if (!p) return set_error(FDC_ERR_INVALID_ARGUMENT, "null handle");
+    if (!p->audio_decim) return set_error(FDC_ERR_INVALID_ARGUMENT, "the channel audio is off (fdc_pipeline_set_audio)");
+    if (p->aud_blocks < 0) return set_error(FDC_ERR_INVALID_ARGUMENT, "no work call has run since the channel audio was switched on or its format or decimation changed");
+    if (nblocks != p->aud_blocks) return set_error(FDC_ERR_INVALID_ARGUMENT, "the last work call had %d blocks, not %d", p->aud_blocks, nblocks);
+    const size_t n = fdc::pipe::audio_bytes(p) * (size_t)nblocks * (size_t)p->audio_row;
+    if (n == 0) return FDC_OK;
+    if (capacity_bytes < n) return set_error(FDC_ERR_INVALID_ARGUMENT, "the audio of %d blocks takes %zu bytes, the buffer holds %zu", nblocks, n, capacity_bytes);
+    if (!dst) return set_error(FDC_ERR_INVALID_ARGUMENT, "null argument");
+    if (!p->aud_host) {
+        // a device entry's rows: read behind everything enqueued so far on the stream it ran on
+        HIPCHK(hipSetDevice(p->cfg.device_id));
+        HIPCHK(hipMemcpyAsync(p->pin_audio.get(), p->d_audio.get(), n, hipMemcpyDeviceToHost, p->aud_stream));
+        HIPCHK(hipStreamSynchronize(p->aud_stream));
+        p->aud_host = true;
+    }
+    std::memcpy(dst, p->pin_audio.get(), n);
+    return FDC_OK;
+    FDC_ENTRY_END
+}
+
+void *fdc_pipeline_audio_device(fdc_pipeline *p) { return p && p->audio_decim ? static_cast<void *>(p->d_audio.get()) : nullptr; }
+
+// the audio pass alone, on the caller's device buffers: the handle gives its channel table and the audio setting, nothing of its stream state
+int fdc_pipeline_audio_pass_device(const fdc_pipeline *p, const void *d_in, void *d_out, const void *d_hist_in, void *d_hist_out, int nblocks, void *stream)
+{
+    FDC_ENTRY("fdc_pipeline_audio_pass_device")
+    if (!p) return set_error(FDC_ERR_INVALID_ARGUMENT, "null handle");
+    if (!p->audio_decim) return set_error(FDC_ERR_INVALID_ARGUMENT, "the channel audio is off (fdc_pipeline_set_audio)");
+    if (nblocks < 0) return set_error(FDC_ERR_INVALID_ARGUMENT, "negative block count");
+    if (nblocks == 0 || p->C <= 0) return FDC_OK;
+    if ((int64_t)nblocks * p->sum_lout * 8 > 0xFFFFF000ll)
+        return set_error(FDC_ERR_INVALID_ARGUMENT, "nblocks %d x %lld output samples per block is more than the 4 GiB one call may produce", nblocks, (long long)p->sum_lout);
+    const int K = (int)p->audio_taps.size();
+    if (!d_in || !d_out || (K > 1 && !d_hist_out)) return set_error(FDC_ERR_INVALID_ARGUMENT, "null device buffer");
+    if (K > 1 && d_hist_in == d_hist_out) return set_error(FDC_ERR_INVALID_ARGUMENT, "the history is read from one buffer and written to another");
+    HIPCHK(hipSetDevice(p->cfg.device_id));
+    HIPCHK(fdc::launch_chan_audio(p->audio_format, p->audio_decim, K, p->audio_scale, p->d_ataps, p->d_aoff, (long long)p->audio_row,
+                                  static_cast<const float *>(d_in), d_out, p->d_chans, K > 1 ? static_cast<const float *>(d_hist_in) : nullptr,
+                                  K > 1 ? static_cast<float *>(d_hist_out) : nullptr, p->C, nblocks, (long long)p->sum_lout,
+                                  stream ? static_cast<hipStream_t>(stream) : p->stream));
     return FDC_OK;
     FDC_ENTRY_END
 }

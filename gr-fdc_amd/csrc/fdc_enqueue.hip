@@ -175,6 +175,8 @@ struct PostPass {
     float2 *lag1 = nullptr;     // k_chan_lag1, always a pass of its own over the group's final float results: lag-1 on
     int demod = 0;              // the call-wide k_chan_demod from the float staging, in the place of the narrowing: FDC_DEMOD_FM / _MAG
     bool demod_cont = false;    //   ... FM: the call continues the stream of the last demodulating call, whose carry stands in front of its first sample
+    void *audio = nullptr;      // the call-wide k_chan_audio behind it, over the demodulated samples: the audio on (where row 0 of the call's audio goes)
+    bool audio_cont = false;    //   ... the call continues the audio stream: the handle's history stands in front of its first sample
 };
 
 static PostPass post_pass(const fdc_pipeline *p, const DeviceCall &call, bool ofused)
@@ -192,6 +194,7 @@ static PostPass post_pass(const fdc_pipeline *p, const DeviceCall &call, bool of
     pp.gain_narrows = pp.gain_pass && narrow;
     pp.levels_pass = pp.levels && !pp.rot_levels && !pp.gain_pass;
     pp.narrow_tail = narrow && !pp.gain_narrows;
+    pp.audio = pp.demod ? call.audio : nullptr;
     return pp;
 }
 
@@ -222,6 +225,16 @@ static int run_post_tail(fdc_pipeline *p, const DeviceCall &call, const PostPass
                                       p->C, nblocks, (long long)p->sum_lout, call.stream));
         if (fm) { p->carry_cur ^= 1; p->demod_next = first_block + nblocks; }
         p->demod_route = fm ? "fm" : "mag";
+    }
+    if (pp.audio) {
+        // the demodulated samples are where the demodulation has just written them; the history is read from one buffer and written to the other,
+        // which is the handle's behind the enqueue, for the call that goes on at the next block
+        const int K = (int)p->audio_taps.size();
+        HIPCHK(fdc::launch_chan_audio(p->audio_format, p->audio_decim, K, p->audio_scale, p->d_ataps, p->d_aoff, (long long)p->audio_row,
+                                      static_cast<const float *>(d_out), pp.audio, p->d_chans, pp.audio_cont && K > 1 ? p->d_ahist[p->ahist_cur].get() : nullptr,
+                                      K > 1 ? p->d_ahist[p->ahist_cur ^ 1].get() : nullptr, p->C, nblocks, (long long)p->sum_lout, call.stream));
+        p->ahist_cur ^= 1; p->audio_next = first_block + nblocks;
+        p->audio_route = "pass";
     }
     if (pp.narrow_tail) HIPCHK(fdc::launch_complex_to_iq(call.ofmt, call.oscale, call.fout, d_out, (size_t)nblocks * p->sum_lout, call.stream));
     if (pp.fine_fused || pp.rotate) p->fine_route = pp.fine_fused ? "fused" : "rotated";
@@ -263,6 +276,11 @@ int process_device_impl(fdc_pipeline *p, DeviceCall &call, const void *d_ring, i
         // a call that fails from here on leaves nothing to continue
         pp.demod_cont = p->demod_next == first_block;
         p->demod_next = -1;
+    }
+    if (pp.audio) {
+        // the same rule for the audio's history, in both modes
+        pp.audio_cont = p->audio_next == first_block;
+        p->audio_next = -1;
     }
     // path 5: the call's part of every group's launch (the group's: its input, its blocks and its waterfall rows)
     fdc::F4Launch f4{};
@@ -401,6 +419,11 @@ void lag1_written(fdc_pipeline *p, int nblocks, hipStream_t stream, bool host)
     p->lag_blocks = nblocks; p->lag_stream = stream; p->lag_host = host;
 }
 
+void audio_written(fdc_pipeline *p, int nblocks, hipStream_t stream, bool host)
+{
+    p->aud_blocks = nblocks; p->aud_stream = stream; p->aud_host = host;
+}
+
 // how the last integer-input / integer-output call was served (fdc_pipeline_describe): "<sc16|sc8>: fused", or what it was instead
 std::string route(int fmt, bool fused, const char *otherwise)
 {
@@ -411,7 +434,8 @@ std::string route(int fmt, bool fused, const char *otherwise)
 // fdc_pipeline_set_output_format, never on this enqueue path) where the call's kernels do not narrow themselves
 // Channel levels (p->levels_on): the call's levels go to the handle's buffer ([max_blocks][C], allocated by fdc_pipeline_set_levels), so such a call
 // needs nblocks <= max_blocks too; nothing is enqueued otherwise.  The channel lag-1 correlation (p->lag1_on, d_lag1) likewise
-// Channel demodulation (p->demod_mode): the call's real output comes from the float staging too, so nblocks <= max_blocks as well
+// Channel demodulation (p->demod_mode): the call's real output comes from the float staging too, so nblocks <= max_blocks as well; the channel
+// audio behind it (p->audio_decim) goes to the handle's d_audio while d_out receives the demodulated samples as ever
 static int process_device_oq(fdc_pipeline *p, DeviceCall &call, const void *d_ring, int64_t first_block, int nblocks, void *d_out)
 {
     const int ofmt = p->out_form;
@@ -419,6 +443,7 @@ static int process_device_oq(fdc_pipeline *p, DeviceCall &call, const void *d_ri
         if (nblocks > p->cfg.max_blocks) return set_error(FDC_ERR_INVALID_ARGUMENT, "channel demodulation: nblocks %d above max_blocks %d", nblocks, p->cfg.max_blocks);
         if (!p->d_out && p->sum_lout > 0) return set_error(FDC_ERR_HIP, "channel demodulation: no float staging");
         call.ofmt = out_code(p); call.oscale = p->demod_gain; call.fout = p->d_out;
+        call.audio = audio_rows(p, 0);          // (the audio goes to the handle's buffer, [max_blocks][A]: the check above covers it)
     }
     const bool lev = p->levels_on && nblocks > 0;
     if (lev) {
@@ -442,6 +467,7 @@ static int process_device_oq(fdc_pipeline *p, DeviceCall &call, const void *d_ri
     if (rc == FDC_OK && ofmt && nblocks > 0) p->oq_route = route(ofmt, call.ofused, "narrowed");
     if (rc == FDC_OK && lev) levels_written(p, nblocks, call.stream, false);
     if (rc == FDC_OK && lag) lag1_written(p, nblocks, call.stream, false);
+    if (rc == FDC_OK && call.audio) audio_written(p, nblocks, call.stream, false);
     return rc;
 }
 

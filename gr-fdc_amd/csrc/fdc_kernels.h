@@ -265,6 +265,16 @@ enum { kDemodFm = 1, kDemodMag = 2 };
 hipError_t launch_chan_demod(int mode, float gain, const float2 *in, float *out, const ChanDev *chans, const float2 *carry_in, float2 *carry_out, int nchan,
                              int nb_call, long long sum_lout, hipStream_t s);
 
+// Channel audio (fdc_pipeline_set_audio): the decimating FIR over the whole call's demodulated samples `in` (launch_chan_demod's out), a[n] = sum over
+// k ascending of taps[k] d[n decim - k] from +0, every product and sum rounded on its own.  format: kAudioF32 / kAudioS16 = FDC_AUDIO_F32 / _S16 (S16:
+// oq_round(a, scale)).  out: row 0 of the call's block-major matrix [nb_call][row] of float / int16; channel c owns the lout_c / decim columns from
+// aoff[c] on.  hist_in ([nchan][ntaps - 1] float; null: zeros) stands in front of every channel's first sample, hist_out (another buffer; null only
+// where ntaps = 1) receives the last ntaps - 1 values of (what stood in front, the call's samples).  decim divides every lout_c
+enum { kAudioF32 = 0, kAudioS16 = 1 };
+hipError_t launch_chan_audio(int format, int decim, int ntaps, float scale, const float *taps, const long long *aoff, long long row, const float *in,
+                             void *out, const ChanDev *chans, const float *hist_in, float *hist_out, int nchan, int nb_call, long long sum_lout,
+                             hipStream_t s);
+
 hipError_t launch_scale(const float2 *in, float2 *out, size_t n, float k, hipStream_t s);
 
 // sinks

@@ -199,6 +199,26 @@ struct fdc_pipeline {
     int carry_cur = 0;
     int64_t demod_next = -1;
     std::string demod_route;     // which demodulation the last call with the setting on ran (fdc_pipeline_describe)
+    // channel audio (fdc_pipeline_set_audio): a setting that needs the demodulation.  audio_decim: 0 = off; audio_taps: the K taps in force, d_ataps their
+    // device copy; audio_row: A, the audio samples per block of all channels, d_aoff[c] channel c's first column.  d_ahist: the stream state, the K - 1
+    // demodulated samples in front of the next call's first of every channel, two buffers of C (K - 1): a call reads d_ahist[ahist_cur] where it continues
+    // the stream (its first_block is audio_next; -1: the stream starts anew) and its kernel writes the other one; the enqueue path swaps behind a
+    // successful enqueue (FM's carry likewise).  d_audio: [max_blocks][A] elements of the last call (4 bytes each: the wider format), pin_audio its pinned
+    // twin (aud_host, aud_stream as lev_host, lev_stream).  All of it is allocated by fdc_pipeline_set_audio, never on the enqueue path.
+    int audio_decim = 0, audio_format = 0;
+    float audio_scale = 1.f;
+    std::vector<float> audio_taps;
+    int64_t audio_row = 0;
+    fdc::DevBuf<float> d_ataps, d_ahist[2];
+    fdc::DevBuf<long long> d_aoff;
+    int ahist_cur = 0;
+    int64_t audio_next = -1;
+    fdc::DevBuf<unsigned char> d_audio;
+    fdc::PinBuf<unsigned char> pin_audio;
+    int aud_blocks = -1;         // block count of the last successful work call with the audio on (-1: none yet)
+    bool aud_host = false;
+    hipStream_t aud_stream = nullptr;
+    std::string audio_route;     // the last call with the setting on ran the audio pass (fdc_pipeline_describe)
     fdc::DevBuf<float2> d_out;   // work(): max_blocks*sum_lout (out_staging)
     int64_t blockcount = 0;      // work(): blocks consumed so far
     // work(): transfers and kernels of consecutive sub-batches overlap (H2D on s_in, kernels on stream, D2H on s_out)
@@ -261,6 +281,9 @@ struct DeviceCall {
     // channel gains (fdc_pipeline_set_gains): the handle's device table of C gains, null = off (device_call).  With them the kernels write float whatever
     // the output format, as with levels
     const float *gain = nullptr;
+    // channel audio (fdc_pipeline_set_audio): where row 0 of the call's audio goes, [block][A] elements of the setting's format; null = none.  It
+    // goes with a demodulating output code only
+    void *audio = nullptr;
     int ncu = 0;                         // compute units the call's persistent kernels may use
     // results: no launch group had to be widened (each read the integer input in its own loads); the call's kernels narrowed in their own stores
     bool all_fused = true, ofused = false;
@@ -277,6 +300,12 @@ inline size_t oq_bytes(int ofmt) { return oq_demod(ofmt) ? sizeof(float) : fdc::
 // the output code of the handle's next call: demodulation while it is on (it excludes integer output; a plan without channels has nothing to
 // demodulate), else the output format
 inline int out_code(const fdc_pipeline *p) { return p->demod_mode && p->C > 0 ? kOqDemod + p->demod_mode : p->out_form; }
+
+// channel audio: whether the handle's next call runs the pass, and the bytes of one audio element
+inline bool audio_on(const fdc_pipeline *p) { return p->audio_decim > 0 && p->demod_mode && p->C > 0; }
+inline size_t audio_bytes(const fdc_pipeline *p) { return p->audio_format == FDC_AUDIO_S16 ? sizeof(int16_t) : sizeof(float); }
+// ... and where the rows from block b0 of a host call on go in the handle's buffer
+inline void *audio_rows(const fdc_pipeline *p, size_t b0) { return audio_on(p) ? p->d_audio.get() + audio_bytes(p) * b0 * (size_t)p->audio_row : nullptr; }
 
 inline bool ispow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
 
@@ -314,6 +343,7 @@ int channels_wide(fdc_pipeline *p, const float2 *spec, float2 *d_out, const int3
 int check_iq_form(int32_t format, float scale);
 void levels_written(fdc_pipeline *p, int nblocks, hipStream_t stream, bool host);   // a call with levels on succeeded: what fdc_pipeline_levels hands out
 void lag1_written(fdc_pipeline *p, int nblocks, hipStream_t stream, bool host);     // the same of the lag-1 correlation (fdc_pipeline_lag1)
+void audio_written(fdc_pipeline *p, int nblocks, hipStream_t stream, bool host);    // ... and of the channel audio (fdc_pipeline_audio)
 std::string route(int fmt, bool fused, const char *otherwise);   // "<sc16|sc8>: fused", or what the call was instead (fdc_pipeline_describe)
 
 } }  // namespace fdc::pipe

@@ -1,8 +1,8 @@
 // gfx950 (MI355X, CDNA4) kernels of the frequency-domain channelizer — the passes that run BEHIND a plan's kernels, over the channel-major float
 // results of a launch group: the rotation of fine tuning (k_fine_rotate), the channel gains (k_chan_gain), the channel levels (k_chan_levels), the
 // channel lag-1 correlation (k_chan_lag1) and the narrowing to complex integers (k_complex_to_iq) — and, over a whole call's float results in the
-// place of the narrowing, the channel demodulation (k_chan_demod, at the end of this file).  Which of them a call runs, and in which order, is
-// decided once per call: PostPass, fdc_enqueue.hip.
+// place of the narrowing, the channel demodulation (k_chan_demod) and behind it the channel audio (k_chan_audio, at the end of this file).  Which of
+// them a call runs, and in which order, is decided once per call: PostPass, fdc_enqueue.hip.
 //
 // One shape for the four per-channel kernels: grid y = channel, a row — the lout samples of one (block, channel) — on a power-of-two set of lanes of one
 // wave, 16 bytes per lane and access where the row allows it (lout even, the channel's run 16-byte aligned), 8 bytes otherwise, a grid-stride loop over
@@ -599,6 +599,160 @@ hipError_t launch_chan_demod(int mode, float gain, const float2 *in, float *out,
             hipLaunchKernelGGL(k_chan_demod<kDemodFm>, grid, dim3(256), 0, s, in, out, chans, carry_in, carry_out, gain, c0, (long long)nb_call);
         else
             hipLaunchKernelGGL(k_chan_demod<kDemodMag>, grid, dim3(256), 0, s, in, out, chans, carry_in, carry_out, gain, c0, (long long)nb_call);
+    });
+}
+
+// Channel audio (fdc_pipeline_set_audio): the decimating FIR behind the demodulation, a[n] = sum over k = 0 .. K - 1 of h[k] d[n D - k] over one
+// channel's run d of the call (T = nblocks * lout real samples, contiguous across the blocks; in front of d[0] stand the K - 1 values of the history,
+// or zeros).  THE ORDER IS THE DEFINITION: k ascending from acc = +0, every product and every sum rounded on its own (audio_mac).
+// A workgroup takes a TILE of consecutive outputs: the tile's samples — the K - 1 in front of its first output's and D per output — are staged
+// in LDS DE-INTERLEAVED BY PHASE: tile sample i at plane i mod D, index i / D.  Output j of the tile reads, for tap k, tile sample j D + (K - 1 - k):
+// plane (K - 1 - k) mod D and index j + (K - 1 - k) / D, so the lanes of a wave — consecutive j — read consecutive words of one plane, whatever D
+// is (staged in sample order they would read words D apart: a D-way bank conflict).  The plane pitch is ceil(64 / D) modulo 64, so that the 64
+// consecutive samples a wave stages fall into different banks where D divides 64.  The tap of a step is the same for the whole workgroup: a scalar
+// load.  The staging loops' trip counts depend on the workgroup alone, the computing loop's on the wave alone; the barriers stand outside both and
+// outside every per-lane condition.
+// The outputs go to the block-major audio matrix: output n of the run is column aoff + n mod (lout / D) of row n / (lout / D).  The workgroup of
+// the run's first tile also writes the new history, the last K - 1 values of (what stood in front, d), to ANOTHER buffer than the one read.
+constexpr unsigned kAudioLdsWords = 10240;        // 40 KiB: four workgroups per compute unit
+
+struct AudioTile { unsigned pitch, front, outs; };   // plane pitch in words; ceil((K - 1) / D), the planes' words in front of output 0; outputs per tile
+
+__host__ __device__ inline AudioTile audio_tile(unsigned D, unsigned K)
+{
+    AudioTile t;
+    const unsigned w = ((64 + D - 1) / D) & 63;
+    t.pitch = kAudioLdsWords / D;
+    t.pitch -= (t.pitch - w) & 63;                  // pitch = w modulo 64; D * pitch <= kAudioLdsWords; pitch >= 97 (D <= 64)
+    t.front = (K - 1 + D - 1) / D;                  // <= 255 at D = 1, where pitch is 10240; <= 8 where pitch is below 160
+    t.outs = t.pitch - t.front;                     // the tile's last sample, outs D + K - 2, has index outs + front - 1 < pitch
+    if (t.outs >= 256) t.outs &= ~255u;             // whole trips of a wave's 256 outputs where the tile holds that many
+    return t;
+}
+
+__device__ __forceinline__ float audio_mac(float acc, float h, float z)
+{
+#pragma clang fp contract(off)
+    const float p = h * z;
+    return acc + p;
+}
+
+__device__ __forceinline__ void audio_store(float *out, long long at, float a, float) { out[at] = a; }
+__device__ __forceinline__ void audio_store(short *out, long long at, float a, float scale) { out[at] = (short)oq_round(a, scale, -32768, 32767); }
+
+// sample t of (history, run): t in [-(K - 1), T)
+__device__ __forceinline__ float audio_sample(const float *d, const float *hin, int K, long long t)
+{
+    return t >= 0 ? d[t] : hin ? hin[K - 1 + t] : 0.0f;
+}
+
+// in: the call's demodulated samples ([channel][nb_call * lout] float at nb_call * out_off); out: row 0 of the call's audio ([nb_call][A] TO);
+// hist_in (null: zeros) and hist_out (null where K = 1): [nchan][K - 1] float
+template <class TO>
+__global__ __launch_bounds__(256) void k_chan_audio(const float *__restrict__ in, TO *__restrict__ out, const ChanDev *__restrict__ chans,
+                                                    const long long *__restrict__ aoff, const float *__restrict__ taps,
+                                                    const float *__restrict__ hist_in, float *__restrict__ hist_out, int D, int K, float scale,
+                                                    long long A, int c0, long long nb_call)
+{
+    __shared__ float tile[kAudioLdsWords];
+    const int c = c0 + (int)blockIdx.y;
+    const unsigned lout = (unsigned)chans[c].lout, tid = threadIdx.x;
+    const unsigned npb = lout / (unsigned)D;                        // outputs per block
+    const unsigned nout = (unsigned)nb_call * npb;
+    const long long T = nb_call * (long long)lout;
+    const float *d = in + nb_call * chans[c].out_off;
+    const float *hin = hist_in ? hist_in + (size_t)c * (size_t)(K - 1) : nullptr;
+    TO *o = out + aoff[c];
+    const AudioTile g = audio_tile((unsigned)D, (unsigned)K);
+    const unsigned magic = (unsigned)(0x100000000ull / (unsigned)D) + 1u;      // i / D = umulhi(i, magic) for i < 2^16, D >= 2
+    // where tile sample i lies in LDS: plane i mod D, index i / D
+    const auto lds_at = [&](unsigned i) {
+        const unsigned q = D == 1 ? i : __umulhi(i, magic);
+        return (i - q * (unsigned)D) * g.pitch + q;
+    };
+    for (unsigned o0 = blockIdx.x * g.outs; o0 < nout; o0 += gridDim.x * g.outs) {
+        const unsigned nt = nout - o0 < g.outs ? nout - o0 : g.outs;            // outputs of this tile
+        const long long t0 = (long long)o0 * D - (K - 1);
+        // stage.  The samples in front of the run (the first tile's K - 1) come from the history.  Those of the run are loaded 16 bytes at a time
+        // between the 16-byte boundaries inside them, four such loads in flight per lane (a lane past the last quad loads that one again and stores
+        // nothing); the up to three samples in front of the first boundary and behind the last are loaded one by one
+        const long long tb = t0 < 0 ? 0 : t0;
+        if (t0 < 0 && tid < (unsigned)(K - 1)) tile[lds_at(tid)] = hin ? hin[tid] : 0.0f;                 // (tile sample i is t = i - (K - 1))
+        // element e of da is sample tb - lo + e of the run, da 16-byte aligned: the tile's are [lo, hi), and e is tile sample e + first
+        const unsigned lo = (unsigned)((reinterpret_cast<uintptr_t>(d + tb) >> 2) & 3), hi = lo + (unsigned)((long long)(o0 + nt) * D - tb);
+        const unsigned first = (unsigned)(tb - t0) - lo;
+        const unsigned up = (lo + 3) & ~3u, down = hi & ~3u;
+        const unsigned lo4 = up < hi ? up : hi, hi4 = down > lo4 ? down : lo4;      // the quads are [lo4, hi4): lo <= lo4 <= hi4 <= hi
+        const float *da = d + tb - lo;
+        if (tid < lo4 - lo) tile[lds_at(lo + tid + first)] = da[lo + tid];
+        if (tid < hi - hi4) tile[lds_at(hi4 + tid + first)] = da[hi4 + tid];
+        for (unsigned q0 = lo4 >> 2, qe = hi4 >> 2; q0 < qe; q0 += 1024) {
+            float4 v[4];
+#pragma unroll
+            for (unsigned u = 0; u < 4; u++) {
+                const unsigned q = q0 + u * 256 + tid;
+                v[u] = *reinterpret_cast<const float4 *>(da + 4 * (q < qe ? q : qe - 1));
+            }
+#pragma unroll
+            for (unsigned u = 0; u < 4; u++) {
+                const unsigned q = q0 + u * 256 + tid, i = 4 * q + first;
+                if (q < qe) {
+                    tile[lds_at(i)] = v[u].x; tile[lds_at(i + 1)] = v[u].y; tile[lds_at(i + 2)] = v[u].z; tile[lds_at(i + 3)] = v[u].w;
+                }
+            }
+        }
+        __syncthreads();
+        // compute.  A wave takes 256 consecutive outputs of the tile per trip, a lane four of them, 64 apart: the trip count depends on the wave alone
+        for (unsigned j0 = (tid >> 6) * 256; j0 < nt; j0 += 1024) {
+            unsigned j[4]; float acc[4];
+#pragma unroll
+            for (unsigned u = 0; u < 4; u++) {
+                const unsigned jj = j0 + u * 64 + (tid & 63);
+                j[u] = jj < nt ? jj : nt - 1;                                   // (a lane without an output computes the tile's last and leaves it out)
+                acc[u] = 0.0f;
+            }
+            // tap k reads tile sample j D + (K - 1 - k): the plane and the index in front go down with k
+            unsigned r = (unsigned)(K - 1) % (unsigned)D, at = r * g.pitch + (unsigned)(K - 1) / (unsigned)D;
+            // (four taps a trip, which is what the scalar registers hold without a spill: their scalar loads and LDS reads are in flight together, not each behind its own wait)
+#pragma unroll 4
+            for (int k = 0; k < K; k++) {
+                const float h = taps[k];
+#pragma unroll
+                for (unsigned u = 0; u < 4; u++) acc[u] = audio_mac(acc[u], h, tile[at + j[u]]);
+                if (r) { r--; at -= g.pitch; } else { r = (unsigned)D - 1; at += r * g.pitch - 1; }
+            }
+#pragma unroll
+            for (unsigned u = 0; u < 4; u++) {
+                const unsigned jj = j0 + u * 64 + (tid & 63);
+                if (jj < nt) {
+                    const unsigned n = o0 + jj, m = n / npb;
+                    audio_store(o, (long long)m * A + (long long)(n - m * npb), acc[u], scale);
+                }
+            }
+        }
+        __syncthreads();                                                        // the tile is read: the next trip may overwrite it
+    }
+    if (blockIdx.x == 0 && tid < (unsigned)(K - 1))
+        hist_out[(size_t)c * (size_t)(K - 1) + tid] = audio_sample(d, hin, K, T - (K - 1) + (long long)tid);
+}
+
+hipError_t launch_chan_audio(int format, int decim, int ntaps, float scale, const float *taps, const long long *aoff, long long row, const float *in,
+                             void *out, const ChanDev *chans, const float *hist_in, float *hist_out, int nchan, int nb_call, long long sum_lout,
+                             hipStream_t s)
+{
+    if (nchan <= 0 || nb_call <= 0) return hipSuccess;
+    if (format != kAudioF32 && format != kAudioS16) return hipErrorInvalidValue;
+    if (decim < 1 || decim > 64 || ntaps < 1 || ntaps > 256 || !taps || !aoff || !in || !out) return hipErrorInvalidValue;
+    if (ntaps > 1 && (!hist_out || hist_in == hist_out)) return hipErrorInvalidValue;
+    // the grid: a workgroup per tile of a run of mean length (channel_grids takes it in units of four)
+    const long long tiles = ((long long)nb_call * sum_lout / nchan / decim) / audio_tile((unsigned)decim, (unsigned)ntaps).outs + 1;
+    return channel_grids(nchan, (int)std::min<long long>(4 * tiles, 1 << 20), [&](dim3 grid, int c0) {
+        if (format == kAudioS16)
+            hipLaunchKernelGGL(k_chan_audio<short>, grid, dim3(256), 0, s, in, static_cast<short *>(out), chans, aoff, taps, hist_in, hist_out, decim, ntaps,
+                               scale, row, c0, (long long)nb_call);
+        else
+            hipLaunchKernelGGL(k_chan_audio<float>, grid, dim3(256), 0, s, in, static_cast<float *>(out), chans, aoff, taps, hist_in, hist_out, decim, ntaps,
+                               scale, row, c0, (long long)nb_call);
     });
 }
 

@@ -32,6 +32,9 @@ static int levels_home(fdc_pipeline *p, int nblocks, hipStream_t s)
         HIPCHK(hipMemcpyAsync(p->pin_levels.get(), p->d_levels.get(), sizeof(float2) * (size_t)nblocks * p->C, hipMemcpyDeviceToHost, s));
     if (p->lag1_on && p->C > 0)
         HIPCHK(hipMemcpyAsync(p->pin_lag1.get(), p->d_lag1.get(), sizeof(float2) * (size_t)nblocks * p->C, hipMemcpyDeviceToHost, s));
+    // ... and of its audio rows, which are all the call hands to the host while the channel audio is on (fdc_pipeline_audio)
+    if (audio_on(p))
+        HIPCHK(hipMemcpyAsync(p->pin_audio.get(), p->d_audio.get(), audio_bytes(p) * (size_t)nblocks * (size_t)p->audio_row, hipMemcpyDeviceToHost, s));
     return FDC_OK;
 }
 
@@ -94,7 +97,7 @@ static int check_work_args(const fdc_pipeline *p, const void *in, int nblocks, v
     if (nblocks < 0) return set_error(FDC_ERR_INVALID_ARGUMENT, "negative item count");
     if (nblocks == 0) return FDC_OK;
     if (nblocks > p->cfg.max_blocks) return set_error(FDC_ERR_INVALID_ARGUMENT, "nblocks %d above max_blocks %d", nblocks, p->cfg.max_blocks);
-    if (!in || (p->C > 0 && !outs)) return set_error(FDC_ERR_INVALID_ARGUMENT, "null host buffer");
+    if (!in || (p->C > 0 && !outs && !audio_on(p))) return set_error(FDC_ERR_INVALID_ARGUMENT, "null host buffer");   // (audio on: outs is not looked at)
     return FDC_OK;
 }
 
@@ -181,8 +184,10 @@ static int pipeline_work_impl(fdc_pipeline *p, DeviceCall call, const void *in, 
     float2 *d_specfull = static_cast<float2 *>(call.spectrum);
     if (spectrum && !d_specfull && (rc = spec_staging(p, &d_specfull)) != FDC_OK) return rc;
 
+    // channel audio on: the call hands the host its audio rows and nothing else: outs is not looked at, no port is copied or scattered
+    const bool audio = audio_on(p), ports = p->C > 0 && !audio;
     const bool in_reg = host_registered(in, esz * nin);
-    const bool out_reg = fill_scatter_table(p, outs, nblocks, osz);
+    const bool out_reg = ports && fill_scatter_table(p, outs, nblocks, osz);
     call.wide = fmt ? p->d_ring : nullptr;
     call.ofmt = ofmt; call.oscale = oscale; call.narrow = !out_reg || demod;
     bool oq_all = true;
@@ -193,6 +198,7 @@ static int pipeline_work_impl(fdc_pipeline *p, DeviceCall call, const void *in, 
         call.spectrum = dspec; call.fout = dok;
         call.levels = p->levels_on && p->C > 0 ? p->d_levels + b0 * (size_t)p->C : nullptr;
         call.lag1 = p->lag1_on && p->C > 0 ? p->d_lag1 + b0 * (size_t)p->C : nullptr;
+        call.audio = audio_rows(p, b0);
         const int rc2 = process_device_impl(p, call, ringb + b0 * p->H * esz, first, nb,
                                             ofmt ? static_cast<void *>(p->d_oq + osz * b0 * (size_t)p->sum_lout) : static_cast<void *>(dok));
         oq_all = oq_all && call.ofused;
@@ -209,7 +215,7 @@ static int pipeline_work_impl(fdc_pipeline *p, DeviceCall call, const void *in, 
                       : fdc::launch_scatter_oq(fdc::kIqFloat, p->d_out + b0 * (size_t)p->sum_lout, ofmt, oscale, p->d_tab, p->C, nb, (long long)b0, st);
     };
     const int sub = p->sub;
-    if (!out_reg && p->C > 0 && !p->pin_out[0])
+    if (!out_reg && ports && !p->pin_out[0])
         for (int i = 0; i < 2; i++)
             HIPCHK(p->pin_out[i].alloc((size_t)sub * p->sum_lout));
     // staged outputs: the pieces of the sub-batch (b0, nb) that has arrived in pin_out[slot] go to the caller's per-channel buffers
@@ -232,7 +238,7 @@ static int pipeline_work_impl(fdc_pipeline *p, DeviceCall call, const void *in, 
         HIPCHK(hipMemcpyAsync(ringb + esz * p->ovl, hin, esz * nin, hipMemcpyHostToDevice, s));
         rc = process(0, nblocks, p->blockcount, p->d_out, d_specfull);
         if (rc != FDC_OK) return rc;
-        if (p->C > 0) {
+        if (ports) {
             if (out_reg) HIPCHK(scatter(0, nblocks, s));
             else HIPCHK(hipMemcpyAsync(p->pin_out[0], res(0), osz * (size_t)nblocks * p->sum_lout, hipMemcpyDeviceToHost, s));
         }
@@ -242,9 +248,10 @@ static int pipeline_work_impl(fdc_pipeline *p, DeviceCall call, const void *in, 
         HIPCHK(hipStreamSynchronize(s));
         if (p->levels_on) levels_written(p, nblocks, s, true);
     if (p->lag1_on) lag1_written(p, nblocks, s, true);
+        if (audio) audio_written(p, nblocks, s, true);
         if (fmt) p->iq_route = route(fmt, call.all_fused, "widened");
         if (p->out_form) p->oq_route = route(ofmt, oq_all, "narrowed");
-        if (p->C > 0 && !out_reg) deliver(0, 0, nblocks);
+        if (ports && !out_reg) deliver(0, 0, nblocks);
         p->blockcount += nblocks;
         return nblocks;
     }
@@ -288,7 +295,7 @@ static int pipeline_work_impl(fdc_pipeline *p, DeviceCall call, const void *in, 
         float2 *dok = p->d_out + (size_t)b0 * p->sum_lout;                    // [channel][nb*lout] of this sub-batch
         rc = process((size_t)b0, nb, p->blockcount + b0, dok, d_specfull ? d_specfull + (size_t)b0 * p->N : nullptr);
         if (rc != FDC_OK) return rc;
-        if (p->C == 0) continue;
+        if (!ports) continue;
         HIPCHK(hipEventRecord(p->ev_k[slot], s));
         HIPCHK(hipStreamWaitEvent(p->s_out, p->ev_k[slot], 0));
         if (out_reg) {
@@ -299,7 +306,7 @@ static int pipeline_work_impl(fdc_pipeline *p, DeviceCall call, const void *in, 
             if (k >= 1 && (rc = drain(k - 1)) != FDC_OK) return rc;
         }
     }
-    if (!out_reg && p->C > 0 && (rc = drain(K - 1)) != FDC_OK) return rc;
+    if (!out_reg && ports && (rc = drain(K - 1)) != FDC_OK) return rc;
     if (spectrum) HIPCHK(hipMemcpyAsync(spectrum, d_specfull, sizeof(float2) * (size_t)nblocks * p->N, hipMemcpyDeviceToHost, s));
     // history <- last ovl samples of this call (overlap_save_impl.cc:78); src and dst never overlap (H >= ovl)
     HIPCHK(hipMemcpyAsync(ringb, ringb + esz * nin, esz * (size_t)p->ovl, hipMemcpyDeviceToDevice, s));
@@ -308,6 +315,7 @@ static int pipeline_work_impl(fdc_pipeline *p, DeviceCall call, const void *in, 
     HIPCHK(hipStreamSynchronize(p->s_out));
     if (p->levels_on) levels_written(p, nblocks, s, true);
     if (p->lag1_on) lag1_written(p, nblocks, s, true);
+    if (audio) audio_written(p, nblocks, s, true);
     if (fmt) p->iq_route = route(fmt, call.all_fused, "widened");
     if (p->out_form) p->oq_route = route(ofmt, oq_all, "narrowed");
     p->blockcount += nblocks;
@@ -408,14 +416,16 @@ static int pipeline_work_real_impl(fdc_pipeline *p, const void *in, int nblocks,
     call.ofmt = ofmt; call.oscale = oq_demod(ofmt) ? p->demod_gain : p->out_scale; call.fout = p->d_out;
     call.levels = p->levels_on && p->C > 0 ? p->d_levels.get() : nullptr;
     call.lag1 = p->lag1_on && p->C > 0 ? p->d_lag1.get() : nullptr;
+    call.audio = audio_rows(p, 0);
     RCCHK(process_device_impl(p, call, p->d_ring, p->blockcount, nblocks, res));
-    RCCHK(copy_outputs(p, outs, nblocks, osz, res, s));
+    if (!call.audio) RCCHK(copy_outputs(p, outs, nblocks, osz, res, s));     // (audio on: the rows go home with the levels, outs is not looked at)
     if (spectrum) HIPCHK(hipMemcpyAsync(spectrum, d_specfull, sizeof(float2) * (size_t)nblocks * p->N, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(p->d_ring, p->d_ring + nin, sizeof(float2) * (size_t)p->ovl, hipMemcpyDeviceToDevice, s));
     RCCHK(levels_home(p, nblocks, s));
     HIPCHK(hipStreamSynchronize(s));
     if (p->levels_on) levels_written(p, nblocks, s, true);
     if (p->lag1_on) lag1_written(p, nblocks, s, true);
+    if (call.audio) audio_written(p, nblocks, s, true);
     if (p->out_form) p->oq_route = route(ofmt, call.ofused, "narrowed");
     p->blockcount += nblocks;
     return nblocks;

@@ -355,6 +355,55 @@ int fdc_pipeline_demod(const fdc_pipeline *p, int32_t *mode, float *gain);
 int fdc_pipeline_demod_device(const fdc_pipeline *p, int32_t mode, float gain, const void *d_in, void *d_out, const void *d_carry_in, void *d_carry_out,
                               int nblocks, void *stream);
 
+/* CHANNEL AUDIO: a decimating FIR (GNU Radio's fir_filter_fff with decimation D) behind the channel demodulation, on the device, so that the ports
+ * leave the card at the audio rate.  With d_c[t] the real float32 stream the demodulation gives for channel c, D the decimation and h[0 .. K-1] the
+ * float32 taps:
+ *     a_c[n] = sum over k = 0 .. K-1 of h[k] d_c[n D - k]
+ * in float32, k ascending from acc = +0, every product and every sum rounded on its own (no fused multiply-add); NaN and +-Inf follow IEEE.
+ * FDC_AUDIO_S16: q = saturate(round_half_even(float32(a scale))), NaN -> 0, +-Inf -> the limits (the rule of sc16 output).
+ * THE HISTORY: in front of a call's first sample stand K - 1 values of d, held per channel on the device.  They are used when the call CONTINUES
+ * the stream, that is when its first_block is the block after the last one of the previous successful call with the audio on (the handle keeps this
+ * position for the audio, in both demodulation modes); otherwise zeros stand there: after create or fdc_pipeline_reset, after switching the audio
+ * on or changing the decimation or the taps, after a change of demodulation mode, after a call that failed once it had begun to enqueue, at a device
+ * or span call elsewhere in the stream.  A new format, audio scale or demodulation gain alone keeps the history, and a call that is REFUSED leaves it
+ * as it was.  After a call the history is the tail of (what stood in front, the call's d): calls of fewer than K - 1 samples are covered.  The
+ * bits of the audio depend on the stream's samples and the settings only, not on how the stream is cut.
+ * THE LAYOUT: D divides every lout_c, so every block gives lout_c / D audio samples of channel c however the stream is cut.  The audio of a call is a
+ * BLOCK-MAJOR matrix [nblocks][A] of float32 or int16, A = sum over c of lout_c / D; in a row channel c owns the lout_c / D columns from
+ * aoff_c = sum over i < c of lout_i / D on (the audio's own prefix sums in channel order); row m belongs to block first_block + m.  Channel c's
+ * stream is column block c of all rows, row after row.
+ * THE AUDIO IS A RESULT HELD BY THE HANDLE, like the levels: it is never written to a buffer whose size only the caller knows.
+ *   fdc_pipeline_set_audio      decim 0 switches it off (the other arguments are ignored).  Otherwise decim 1 .. 64, ntaps 1 .. 256 finite taps, format
+ *                               FDC_AUDIO_F32 / _S16, scale finite and not zero (ignored for F32).  FDC_ERR_INVALID_ARGUMENT, the previous setting staying
+ *                               in force: any of these out of range; while the demodulation is off; where decim does not divide some lout_c (the message
+ *                               names the channel); while a pipelined sinks batch is inside the handle.  fdc_pipeline_set_demod(FDC_DEMOD_OFF) is
+ *                               refused while the audio is on.  A SETTING: it applies from the next call and survives fdc_pipeline_reset (the history
+ *                               does not); it waits for the handle's own stream first.  It allocates everything the feature needs, once per size: the taps
+ *                               on the device, two history buffers of C (K - 1) floats, the rows of max_blocks blocks and their pinned twin; nothing in
+ *                               the steady state of any entry.  A plan without channels accepts it.
+ *   fdc_pipeline_audio_setting  the setting in force (decim 0: off); any pointer may be NULL; taps receives ntaps floats (room for 256).
+ *   fdc_pipeline_audio_row      A, 0 while off.
+ *   fdc_pipeline_audio          the first nblocks rows of the last call, nblocks being that call's block count (as fdc_pipeline_levels), to dst:
+ *                               nblocks * A elements.  capacity_bytes below that: FDC_ERR_INVALID_ARGUMENT, nothing written.  After a host entry it
+ *                               is a memcpy; after a device entry it waits for the stream that one ran on.
+ *   fdc_pipeline_audio_device   the device buffer ([block of the last call][A]), NULL while off.
+ * WHILE IT IS ON, the host stream entries (fdc_pipeline_work, _work_real, _work_iq and the span forms) run the demodulation and the audio pass and
+ * hand the host the audio alone: they write NOTHING to outs, which may be NULL, and copy no port.  The device entries write the demodulated float
+ * ports to d_out as ever (4 * nblocks * sum_lout bytes) and the audio to the handle's buffer.  fdc_pipeline_describe: "audio: pass" after a call
+ * that ran it. */
+enum { FDC_AUDIO_F32 = 0, FDC_AUDIO_S16 = 1 };
+int fdc_pipeline_set_audio(fdc_pipeline *p, int32_t decim, const float *taps, int32_t ntaps, int32_t format, float scale);
+int fdc_pipeline_audio_setting(const fdc_pipeline *p, int32_t *decim, int32_t *ntaps, int32_t *format, float *scale, float *taps);
+int64_t fdc_pipeline_audio_row(const fdc_pipeline *p);
+int fdc_pipeline_audio(fdc_pipeline *p, void *dst, size_t capacity_bytes, int nblocks);
+void *fdc_pipeline_audio_device(fdc_pipeline *p);
+/* The audio pass alone, on device buffers of the caller (and the entry the footprint tests reach the kernel by), with the handle's channel table and
+ * audio setting (which must be on) and nothing of its stream state: d_in real float32 in fdc_pipeline_process_device's layout (channel c at element
+ * offset nblocks*out_off_c), d_out exactly nblocks * A elements, d_hist_in C (K - 1) floats or NULL (zeros), d_hist_out another buffer that receives
+ * exactly C (K - 1) floats (NULL only where K = 1).  Enqueued on `stream` (NULL: the handle's). */
+int fdc_pipeline_audio_pass_device(const fdc_pipeline *p, const void *d_in, void *d_out, const void *d_hist_in, void *d_hist_out, int nblocks,
+                                   void *stream);
+
 /* Optional: pin a host range that will be handed to fdc_pipeline_work() again and again (GNU Radio's circular buffers
  * live as long as the flowgraph: register them in start(), unregister in stop()).  A call whose `in` lies in a
  * registered range is DMA'd from it in place, and when every outs[c] does, the results are stored straight into
