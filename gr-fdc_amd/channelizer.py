@@ -251,6 +251,41 @@ def _set_gains(fn, handle, nchan, g):
     _lib.check(rc)
 
 
+SQUELCH_MAX_HANG = 65535
+
+
+def _squelch_args(nchan, open_thr, close_thr, hang):
+    """Pipeline.set_squelch: (float32 open[C], float32 close[C], hang), (None, None, 0) for open_thr None.  A scalar broadcasts to the channels; close_thr
+    None is open_thr.  Raises before any library call."""
+    if open_thr is None:
+        return None, None, 0
+    with np.errstate(over="ignore"):            # (a value beyond float32 becomes infinite and is refused below)
+        o = np.asarray(open_thr, dtype=np.float32)
+        c = o if close_thr is None else np.asarray(close_thr, dtype=np.float32)
+    if o.ndim > 1 or c.ndim > 1 or (o.ndim == 1 and o.size != nchan) or (c.ndim == 1 and c.size != nchan):
+        raise ValueError("the squelch thresholds are one value per channel (%d) or a scalar" % nchan)
+    o, c = np.ascontiguousarray(np.broadcast_to(o, (nchan,))), np.ascontiguousarray(np.broadcast_to(c, (nchan,)))
+    if not (np.isfinite(o).all() and np.isfinite(c).all()) or (o < 0).any() or (c < 0).any():
+        raise ValueError("the squelch thresholds must be finite and not negative")
+    if (c > o).any():
+        raise ValueError("a close threshold is above its open threshold (channel %d)" % int(np.flatnonzero(c > o)[0]))
+    if isinstance(hang, bool) or not isinstance(hang, (int, np.integer)) or not 0 <= int(hang) <= SQUELCH_MAX_HANG:
+        raise ValueError("the squelch hang count is an integer in 0 .. %d blocks" % SQUELCH_MAX_HANG)
+    return o, c, int(hang)
+
+
+def squelch_thresholds(lout, open_db, close_db=None):
+    """Thresholds for Pipeline.set_squelch from dB of MEAN power per sample (0 dB: a mean |y|^2 of 1, in front of the channel gain): the levels' power
+    is the sum over a row of re^2 + im^2, so the threshold of channel c is lout_c * 10^(dB / 10).  open_db / close_db: a scalar or one value per
+    channel; close_db None: the open thresholds.  Returns (open, close), float32[C] each."""
+    lo = np.asarray(lout, dtype=np.float64).reshape(-1)
+    o = np.broadcast_to(np.asarray(open_db, dtype=np.float64), lo.shape)
+    c = o if close_db is None else np.broadcast_to(np.asarray(close_db, dtype=np.float64), lo.shape)
+    if (c > o).any():
+        raise ValueError("a close level is above its open level")
+    return (lo * 10.0 ** (o / 10.0)).astype(np.float32), (lo * 10.0 ** (c / 10.0)).astype(np.float32)
+
+
 DEMOD_FM, DEMOD_MAG = 1, 2        # FDC_DEMOD_FM, FDC_DEMOD_MAG (include/fdc_amd.h)
 
 
@@ -582,6 +617,61 @@ class Pipeline(_OutputFormat):
         process_device's layout, d_out: nblocks * A elements, d_hist_in: C (K - 1) float32 or None, d_hist_out: another such buffer, None only where
         K = 1).  The handle's own history and stream position are not touched."""
         _lib.check(_lib.lib().fdc_pipeline_audio_pass_device(self._h, d_in, d_out, d_hist_in, d_hist_out, int(nblocks), stream))
+
+    def set_squelch(self, open_thr, close_thr=None, hang=0):
+        """fdc_pipeline_set_squelch: open_thr None switches it off; else thresholds in the levels' unit (the sum over a row of re^2 + im^2 in front of
+        the channel gain; squelch_thresholds converts from dB of mean power), one per channel or a scalar for all, close_thr (default: open_thr) not
+        above open_thr, both finite and >= 0, and hang 0 .. 65535 blocks.  It needs the levels (set_levels) and decides on them, on the device: a
+        channel opens at a block whose power reaches open_thr, stays open while it reaches close_thr, and closes at the (hang + 1)-th consecutive
+        block below (tests/squelch_model.py).  squelch() gives the mask of the last call; with the audio on (set_audio) the audio of closed blocks is
+        zero and is not filtered.  The state of every channel is kept on the device from call to call and starts closed after create, reset(),
+        switching it on, or a device or span call elsewhere in the stream; new thresholds or a new hang keep which channels are open.  A setting: it
+        applies from the next call and survives reset().  ValueError for arguments out of range (nothing reaches the library), FdcError where the
+        library refuses (levels off, a pipelined sinks batch inside); nothing changes then."""
+        o, c, h = _squelch_args(len(self.channels), open_thr, close_thr, hang)
+        if o is not None and o.size == 0:         # (a plan without channels: pointers that are not NULL, which means off)
+            o = c = np.zeros(1, np.float32)
+        fp = C.POINTER(C.c_float)
+        _lib.check(_lib.lib().fdc_pipeline_set_squelch(self._h, None if o is None else o.ctypes.data_as(fp), None if c is None else c.ctypes.data_as(fp),
+                                                       len(self.channels), h))
+
+    def squelch_setting(self):
+        """fdc_pipeline_squelch_setting: None while off, else (float32 open[C], float32 close[C], hang): what the library has in force now."""
+        hang = C.c_int32(0)
+        _lib.check(_lib.lib().fdc_pipeline_squelch_setting(self._h, None, None, C.byref(hang)))
+        if hang.value < 0:
+            return None
+        o, c = np.zeros(max(1, len(self.channels)), np.float32), np.zeros(max(1, len(self.channels)), np.float32)
+        fp = C.POINTER(C.c_float)
+        _lib.check(_lib.lib().fdc_pipeline_squelch_setting(self._h, o.ctypes.data_as(fp), c.ctypes.data_as(fp), None))
+        return o[:len(self.channels)], c[:len(self.channels)], int(hang.value)
+
+    def squelch(self, nblocks=None):
+        """fdc_pipeline_squelch: the mask of the last call, uint8 [nblocks, C]: 1 where the channel is open at that block.  nblocks: the last call's
+        block count where it did not go through this object's work methods (process_device, work_raw)."""
+        if nblocks is None:
+            if self._last_nb is None:
+                raise ValueError("squelch(): no work call yet")
+            nblocks = self._last_nb
+        nblocks = int(nblocks)
+        if nblocks < 0:
+            raise ValueError("squelch(): negative block count")
+        if self.squelch_setting() is None:
+            raise ValueError("squelch(): the channel squelch is off (set_squelch)")
+        out = np.empty((nblocks, len(self.channels)), dtype=np.uint8)
+        if out.size:
+            _lib.check(_lib.lib().fdc_pipeline_squelch(self._h, out.ctypes.data, out.nbytes, nblocks))
+        return out
+
+    def squelch_device(self):
+        """fdc_pipeline_squelch_device: the device address of the mask ([block of the last call][C] bytes), None while it is off."""
+        return _lib.lib().fdc_pipeline_squelch_device(self._h)
+
+    def squelch_pass_device(self, d_levels, d_mask, nblocks, d_state_in=None, d_state_out=None, stream=None):
+        """fdc_pipeline_squelch_pass_device: the decision alone on device buffers of the caller, with the setting and the gains in force (d_levels:
+        [nblocks][C] float32 pairs, d_mask: nblocks * C bytes, d_state_in: C int32 pairs (open, h) or None, d_state_out: another such buffer).  The
+        handle's own state and stream position are not touched."""
+        _lib.check(_lib.lib().fdc_pipeline_squelch_pass_device(self._h, d_levels, d_mask, d_state_in, d_state_out, int(nblocks), stream))
 
     def _host_outs(self, outs, nb):
         """(outs, ptrs) of a host call.  While the channel audio is on — asked of the library at this call — the entries write no port: (None, None),
@@ -950,7 +1040,8 @@ class FrequencyDomainChannelizer:
                  pow_act_maxblocks, act_det_maxblocks,
                  debug, device_id=0, max_blocks=64, devices=None, pipelined=False, waterfall=None, iq_input=None, iq_scale=1.0,
                  iq_output=None, iq_output_scale=1.0, fine_tuning=False, *, payload_format=None, payload_scale=1.0, levels=False, gains=None, lag1=False,
-                 demod=None, demod_gain=1.0, audio_decim=None, audio_taps=None, audio_format="f32", audio_scale=1.0):
+                 demod=None, demod_gain=1.0, audio_decim=None, audio_taps=None, audio_format="f32", audio_scale=1.0, squelch_db=None, squelch_close_db=None,
+                 squelch_hang=0):
         # pipelined (not an argument of the reference): the sink blocks run beside the front end of the FOLLOWING work() calls, as the
         # thread-per-block scheduler runs them beside the FFT in the reference (fdc_pipeline_work_sinks on a look-ahead bank,
         # include/fdc_amd.h): same PDUs, handed out one or two work() calls later; flush() at the end of the stream
@@ -1098,6 +1189,22 @@ class FrequencyDomainChannelizer:
         elif audio_taps is not None:
             raise ValueError("audio_taps needs audio_decim")
 
+        # squelch_db / squelch_close_db / squelch_hang (not arguments of the reference): a carrier-operated squelch per throughput channel, decided on the
+        # device from the levels (Pipeline.set_squelch): the channel opens at a block whose mean power in front of the gain reaches squelch_db (dB; a scalar
+        # or one value per channel), stays open while it reaches squelch_close_db (default: squelch_db) and closes after squelch_hang + 1 blocks below.
+        # After every work() self.squelch is uint8[items, throughput channels]; with audio_decim the audio of closed blocks is zero.  It needs levels
+        self.squelch_db, self.squelch_close_db, self.squelch_hang = squelch_db, squelch_close_db, squelch_hang
+        self.squelch = None
+        if squelch_db is not None:
+            if not self.levels_on:
+                raise ValueError("squelch_db needs levels=True: the squelch decides on the channel levels")
+            if devices is not None and len(devices) > 1:
+                raise ValueError("squelch_db needs one device: the group entries do not serve the channel squelch")
+            # (the thresholds take the channels' lout, which the handle knows: the checks that do not are made here)
+            _squelch_args(len(self.throughput_channels), *squelch_thresholds(np.ones(len(self.throughput_channels)), squelch_db, squelch_close_db), squelch_hang)
+        elif squelch_close_db is not None or squelch_hang:
+            raise ValueError("squelch_close_db and squelch_hang need squelch_db")
+
         # gains (not an argument of the reference): one output gain per throughput channel, applied on the device behind fine tuning and in front of the
         # levels and of iq_output's narrowing (Pipeline.set_gains); set_gains() changes them between work() calls (an AGC fed from self.levels)
         self.gains = None if gains is None else _check_gains(len(self.throughput_channels), gains)
@@ -1174,6 +1281,8 @@ class FrequencyDomainChannelizer:
             self.pipeline.set_demod(self.demod, self.demod_gain)
         if self.audio_decim is not None:
             self.pipeline.set_audio(self.audio_decim, self.audio_taps, self.audio_format, self.audio_scale)
+        if self.squelch_db is not None:
+            self.set_squelch(self.squelch_db, self.squelch_close_db, self.squelch_hang)
         self.N_throughput_channelizers = len(self.channel_params)
         # waterfall (not an argument of the reference, whose example flowgraph wires the spectrum to complex_to_mag_squared and
         # FDC.WaterfallMsgTagging outside the hier block): a gr_fdc_amd.Waterfall fed from the spectrum on the device; work() then
@@ -1252,6 +1361,8 @@ class FrequencyDomainChannelizer:
             self.levels = self.pipeline.levels() if self.pipeline._call_nb > 0 else np.empty((0, len(self.channel_params), 2), dtype=np.float32)
         if self.lag1_on:
             self.lag1 = self.pipeline.lag1() if self.pipeline._call_nb > 0 else np.empty((0, len(self.channel_params)), dtype=np.complex64)
+        if self.squelch_db is not None:
+            self.squelch = self.pipeline.squelch() if self.pipeline._call_nb > 0 else np.empty((0, len(self.channel_params)), dtype=np.uint8)
         if self.debug:
             outs, spec = res
             return [spec] + outs
@@ -1276,6 +1387,17 @@ class FrequencyDomainChannelizer:
             raise ValueError(self._gains_refusal)
         self.pipeline.set_gains(arr)
         self.gains = arr
+
+    def set_squelch(self, open_db, close_db=None, hang=0):
+        """New squelch levels (dB of mean power in front of the gain: a scalar or one per throughput channel; None: off) and hang count from the next
+        work() call on: Pipeline.set_squelch over squelch_thresholds; which channels are open is kept.  It needs levels=True and one device."""
+        if open_db is None:
+            self.pipeline.set_squelch(None)
+        else:
+            if not self.levels_on or not isinstance(self.pipeline, Pipeline):
+                raise ValueError("the squelch needs levels=True and one device")
+            self.pipeline.set_squelch(*squelch_thresholds(self.pipeline.lout, open_db, close_db), hang=hang)
+        self.squelch_db, self.squelch_close_db, self.squelch_hang = open_db, close_db, hang
 
     def flush(self):
         """End of the stream (what the block's stop() does): the pipelined form still holds the PDUs of the last one or two work()

@@ -413,6 +413,7 @@ int32_t fdc_pipeline_describe(const fdc_pipeline *p, char *buf, int32_t n)
     if (!p->lag1_route.empty()) add("; lag1: %s", p->lag1_route.c_str());
     if (!p->demod_route.empty()) add("; demod: %s", p->demod_route.c_str());
     if (!p->audio_route.empty()) add("; audio: %s", p->audio_route.c_str());
+    if (!p->squelch_route.empty()) add("; squelch: %s", p->squelch_route.c_str());
     std::snprintf(buf, (size_t)n, "%s", t);
     return k;
 }
@@ -490,6 +491,8 @@ void fdc_pipeline_reset(fdc_pipeline *p)
     p->demod_next = -1;
     p->audio_route.clear();      // (and the channel audio, whose history does not survive either)
     p->audio_next = -1;
+    p->squelch_route.clear();    // (and the channel squelch: every channel starts closed again)
+    p->squelch_next = -1;
 }
 
 int fdc_pipeline_set_output_format(fdc_pipeline *p, int32_t format, float scale)
@@ -570,6 +573,8 @@ int fdc_pipeline_set_levels(fdc_pipeline *p, int32_t on)
     if (!p) return set_error(FDC_ERR_INVALID_ARGUMENT, "null handle");
     if (p->hier_filled > 0)
         return set_error(FDC_ERR_INVALID_ARGUMENT, "a pipelined sinks batch is still inside the handle: fdc_pipeline_flush_sinks until it returns 0 first");
+    if (!on && p->squelch_on)
+        return set_error(FDC_ERR_INVALID_ARGUMENT, "the channel squelch decides on the levels: switch the squelch off first (fdc_pipeline_set_squelch(p, NULL, NULL, C, 0))");
     HIPCHK(hipSetDevice(p->cfg.device_id));
     HIPCHK(hipStreamSynchronize(p->stream));          // (no call of the host entries is in flight; a device entry's caller orders its own stream)
     if (!on) { p->levels_on = false; p->levels_route.clear(); return FDC_OK; }
@@ -807,7 +812,8 @@ int fdc_pipeline_audio(fdc_pipeline *p, void *dst, size_t capacity_bytes, int nb
 
 void *fdc_pipeline_audio_device(fdc_pipeline *p) { return p && p->audio_decim ? static_cast<void *>(p->d_audio.get()) : nullptr; }
 
-// the audio pass alone, on the caller's device buffers: the handle gives its channel table and the audio setting, nothing of its stream state
+// the audio pass alone, on the caller's device buffers: the handle gives its channel table and the audio setting, nothing of its stream state (but,
+// while the squelch is on, the mask of its last work call, which gates the pass)
 int fdc_pipeline_audio_pass_device(const fdc_pipeline *p, const void *d_in, void *d_out, const void *d_hist_in, void *d_hist_out, int nblocks, void *stream)
 {
     FDC_ENTRY("fdc_pipeline_audio_pass_device")
@@ -820,11 +826,122 @@ int fdc_pipeline_audio_pass_device(const fdc_pipeline *p, const void *d_in, void
     const int K = (int)p->audio_taps.size();
     if (!d_in || !d_out || (K > 1 && !d_hist_out)) return set_error(FDC_ERR_INVALID_ARGUMENT, "null device buffer");
     if (K > 1 && d_hist_in == d_hist_out) return set_error(FDC_ERR_INVALID_ARGUMENT, "the history is read from one buffer and written to another");
+    // the squelch on: the gated form, over the handle's mask of the last call (fdc_pipeline_squelch_device), which must have this call's rows
+    const unsigned char *gate = squelch_rows(p, 0);
+    if (gate && p->sq_blocks != nblocks)
+        return set_error(FDC_ERR_INVALID_ARGUMENT, "the channel squelch is on: the gated audio pass reads the mask of the last call, which had %d blocks, not %d",
+                         p->sq_blocks, nblocks);
     HIPCHK(hipSetDevice(p->cfg.device_id));
     HIPCHK(fdc::launch_chan_audio(p->audio_format, p->audio_decim, K, p->audio_scale, p->d_ataps, p->d_aoff, (long long)p->audio_row,
                                   static_cast<const float *>(d_in), d_out, p->d_chans, K > 1 ? static_cast<const float *>(d_hist_in) : nullptr,
                                   K > 1 ? static_cast<float *>(d_hist_out) : nullptr, p->C, nblocks, (long long)p->sum_lout,
-                                  stream ? static_cast<hipStream_t>(stream) : p->stream));
+                                  stream ? static_cast<hipStream_t>(stream) : p->stream, gate));
+    return FDC_OK;
+    FDC_ENTRY_END
+}
+
+// the channel squelch: a setting that needs the levels; everything it needs is allocated here, once, and new thresholds or a new hang count keep the
+// stream state (which channels are open)
+int fdc_pipeline_set_squelch(fdc_pipeline *p, const float *open_thr, const float *close_thr, int n, int32_t hang)
+{
+    FDC_ENTRY("fdc_pipeline_set_squelch")
+    if (!p) return set_error(FDC_ERR_INVALID_ARGUMENT, "null handle");
+    if (n != p->C) return set_error(FDC_ERR_INVALID_ARGUMENT, "channel squelch: %d thresholds for %d channels", n, p->C);
+    if (open_thr) {
+        if (!close_thr) return set_error(FDC_ERR_INVALID_ARGUMENT, "channel squelch: no close thresholds");
+        if (hang < 0 || hang > 65535) return set_error(FDC_ERR_INVALID_ARGUMENT, "channel squelch: the hang count %d is not in 0 .. 65535", (int)hang);
+        for (int c = 0; c < p->C; c++) {
+            if (!std::isfinite(open_thr[c]) || !std::isfinite(close_thr[c]) || open_thr[c] < 0.0f || close_thr[c] < 0.0f)
+                return set_error(FDC_ERR_INVALID_ARGUMENT, "channel squelch: the thresholds of channel %d are not finite and >= 0", c);
+            if (close_thr[c] > open_thr[c])
+                return set_error(FDC_ERR_INVALID_ARGUMENT, "channel squelch: the close threshold of channel %d is above its open threshold", c);
+        }
+    }
+    if (p->hier_filled > 0)
+        return set_error(FDC_ERR_INVALID_ARGUMENT, "a pipelined sinks batch is still inside the handle: fdc_pipeline_flush_sinks until it returns 0 first");
+    if (open_thr && !p->levels_on)
+        return set_error(FDC_ERR_INVALID_ARGUMENT, "the channel squelch decides on the levels: switch the channel levels on first (fdc_pipeline_set_levels(p, 1))");
+    HIPCHK(hipSetDevice(p->cfg.device_id));
+    HIPCHK(hipStreamSynchronize(p->stream));          // (no call of the host entries is in flight; a device entry's caller orders its own stream)
+    if (!open_thr) {
+        p->squelch_on = false; p->sq_open.clear(); p->sq_close.clear(); p->sq_hang = 0;
+        p->squelch_next = -1; p->sq_blocks = -1; p->squelch_route.clear();
+        return FDC_OK;
+    }
+    // everything the feature needs, once: the two threshold tables, the two states, the mask of the longest call and its pinned twin
+    const size_t nc = (size_t)p->C, nm = (size_t)p->cfg.max_blocks * nc;
+    for (int i = 0; i < 2; i++) {
+        if (nc > 0 && !p->d_sqthr[i]) HIPCHK(p->d_sqthr[i].alloc(nc));
+        if (nc > 0 && !p->d_sqstate[i]) HIPCHK(p->d_sqstate[i].alloc(2 * nc));
+    }
+    if (nm > 0 && !p->d_mask) HIPCHK(p->d_mask.alloc(nm));
+    if (nm > 0 && !p->pin_mask) HIPCHK(p->pin_mask.alloc(nm));
+    if (nc > 0) {
+        HIPCHK(hipMemcpy(p->d_sqthr[0], open_thr, sizeof(float) * nc, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(p->d_sqthr[1], close_thr, sizeof(float) * nc, hipMemcpyHostToDevice));
+    }
+    if (p->sq_open.size() != nc) { p->sq_open.resize(nc); p->sq_close.resize(nc); }
+    std::copy(open_thr, open_thr + nc, p->sq_open.begin());
+    std::copy(close_thr, close_thr + nc, p->sq_close.begin());
+    p->sq_hang = hang;
+    if (!p->squelch_on) { p->squelch_next = -1; p->sq_blocks = -1; }      // switched on: every channel starts closed, no call has a mask yet
+    p->squelch_on = true;
+    return FDC_OK;
+    FDC_ENTRY_END
+}
+
+int fdc_pipeline_squelch_setting(const fdc_pipeline *p, float *open_thr, float *close_thr, int32_t *hang)
+{
+    FDC_ENTRY("fdc_pipeline_squelch_setting")
+    if (!p) return set_error(FDC_ERR_INVALID_ARGUMENT, "null handle");
+    if (hang) *hang = p->squelch_on ? p->sq_hang : -1;
+    if (open_thr) std::copy(p->sq_open.begin(), p->sq_open.end(), open_thr);
+    if (close_thr) std::copy(p->sq_close.begin(), p->sq_close.end(), close_thr);
+    return FDC_OK;
+    FDC_ENTRY_END
+}
+
+// the mask of the last call: never more than the caller says its buffer holds
+int fdc_pipeline_squelch(fdc_pipeline *p, uint8_t *dst, size_t capacity_bytes, int nblocks)
+{
+    FDC_ENTRY("fdc_pipeline_squelch")
+    if (!p) return set_error(FDC_ERR_INVALID_ARGUMENT, "null handle");
+    if (!p->squelch_on) return set_error(FDC_ERR_INVALID_ARGUMENT, "the channel squelch is off (fdc_pipeline_set_squelch)");
+    if (p->sq_blocks < 0) return set_error(FDC_ERR_INVALID_ARGUMENT, "no work call has run since the channel squelch was switched on");
+    if (nblocks != p->sq_blocks) return set_error(FDC_ERR_INVALID_ARGUMENT, "the last work call had %d blocks, not %d", p->sq_blocks, nblocks);
+    const size_t n = (size_t)nblocks * (size_t)p->C;
+    if (n == 0) return FDC_OK;
+    if (capacity_bytes < n) return set_error(FDC_ERR_INVALID_ARGUMENT, "the mask of %d blocks takes %zu bytes, the buffer holds %zu", nblocks, n, capacity_bytes);
+    if (!dst) return set_error(FDC_ERR_INVALID_ARGUMENT, "null argument");
+    if (!p->sq_host) {
+        // a device entry's mask: read behind everything enqueued so far on the stream it ran on
+        HIPCHK(hipSetDevice(p->cfg.device_id));
+        HIPCHK(hipMemcpyAsync(p->pin_mask.get(), p->d_mask.get(), n, hipMemcpyDeviceToHost, p->sq_stream));
+        HIPCHK(hipStreamSynchronize(p->sq_stream));
+        p->sq_host = true;
+    }
+    std::memcpy(dst, p->pin_mask.get(), n);
+    return FDC_OK;
+    FDC_ENTRY_END
+}
+
+void *fdc_pipeline_squelch_device(fdc_pipeline *p) { return p && p->squelch_on ? static_cast<void *>(p->d_mask.get()) : nullptr; }
+
+// the decision alone, on the caller's device buffers: the handle gives its setting, its gains and its channel count, nothing of its stream state
+int fdc_pipeline_squelch_pass_device(const fdc_pipeline *p, const void *d_levels, void *d_mask, const void *d_state_in, void *d_state_out, int nblocks,
+                                     void *stream)
+{
+    FDC_ENTRY("fdc_pipeline_squelch_pass_device")
+    if (!p) return set_error(FDC_ERR_INVALID_ARGUMENT, "null handle");
+    if (!p->squelch_on) return set_error(FDC_ERR_INVALID_ARGUMENT, "the channel squelch is off (fdc_pipeline_set_squelch)");
+    if (nblocks < 0) return set_error(FDC_ERR_INVALID_ARGUMENT, "negative block count");
+    if (nblocks == 0 || p->C <= 0) return FDC_OK;
+    if (!d_levels || !d_mask || !d_state_out) return set_error(FDC_ERR_INVALID_ARGUMENT, "null device buffer");
+    if (d_state_in == d_state_out) return set_error(FDC_ERR_INVALID_ARGUMENT, "the state is read from one buffer and written to another");
+    HIPCHK(hipSetDevice(p->cfg.device_id));
+    HIPCHK(fdc::launch_chan_squelch(static_cast<const float2 *>(d_levels), p->gains_on ? p->d_gain.get() : nullptr, p->d_sqthr[0], p->d_sqthr[1], p->sq_hang,
+                                    static_cast<const int *>(d_state_in), static_cast<int *>(d_state_out), static_cast<unsigned char *>(d_mask), p->C, nblocks,
+                                    stream ? static_cast<hipStream_t>(stream) : p->stream));
     return FDC_OK;
     FDC_ENTRY_END
 }

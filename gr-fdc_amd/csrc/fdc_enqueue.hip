@@ -177,6 +177,8 @@ struct PostPass {
     bool demod_cont = false;    //   ... FM: the call continues the stream of the last demodulating call, whose carry stands in front of its first sample
     void *audio = nullptr;      // the call-wide k_chan_audio behind it, over the demodulated samples: the audio on (where row 0 of the call's audio goes)
     bool audio_cont = false;    //   ... the call continues the audio stream: the handle's history stands in front of its first sample
+    unsigned char *squelch = nullptr;   // the call-wide k_chan_squelch over the call's levels, in front of the audio (which it gates): the squelch on
+    bool squelch_cont = false;  //   ... the call continues the squelch's stream: the handle's state stands in front of its first block
 };
 
 static PostPass post_pass(const fdc_pipeline *p, const DeviceCall &call, bool ofused)
@@ -195,6 +197,7 @@ static PostPass post_pass(const fdc_pipeline *p, const DeviceCall &call, bool of
     pp.levels_pass = pp.levels && !pp.rot_levels && !pp.gain_pass;
     pp.narrow_tail = narrow && !pp.gain_narrows;
     pp.audio = pp.demod ? call.audio : nullptr;
+    pp.squelch = pp.levels ? call.squelch : nullptr;
     return pp;
 }
 
@@ -217,6 +220,15 @@ static int run_post_passes(const fdc_pipeline *p, const DeviceCall &call, const 
 // behind the last launch group: the call-wide narrowing, and how the call was served (fdc_pipeline_describe)
 static int run_post_tail(fdc_pipeline *p, const DeviceCall &call, const PostPass &pp, int64_t first_block, int nblocks, void *d_out)
 {
+    if (pp.squelch) {
+        // the last launch group's levels are enqueued: the decision over all the call's rows.  The state is read from one buffer and written to the other,
+        // which is the handle's behind the enqueue, for the call that goes on at the next block
+        HIPCHK(fdc::launch_chan_squelch(pp.levels, pp.gain, p->d_sqthr[0], p->d_sqthr[1], p->sq_hang,
+                                        pp.squelch_cont ? p->d_sqstate[p->sqstate_cur].get() : nullptr, p->d_sqstate[p->sqstate_cur ^ 1].get(), pp.squelch, p->C,
+                                        nblocks, call.stream));
+        p->sqstate_cur ^= 1; p->squelch_next = first_block + nblocks;
+        p->squelch_route = "pass";
+    }
     if (pp.demod) {
         // FM reads one carry buffer and writes the other; behind the enqueue the written one is the handle's, for the call that goes on at the next block
         const bool fm = pp.demod == FDC_DEMOD_FM;
@@ -232,9 +244,9 @@ static int run_post_tail(fdc_pipeline *p, const DeviceCall &call, const PostPass
         const int K = (int)p->audio_taps.size();
         HIPCHK(fdc::launch_chan_audio(p->audio_format, p->audio_decim, K, p->audio_scale, p->d_ataps, p->d_aoff, (long long)p->audio_row,
                                       static_cast<const float *>(d_out), pp.audio, p->d_chans, pp.audio_cont && K > 1 ? p->d_ahist[p->ahist_cur].get() : nullptr,
-                                      K > 1 ? p->d_ahist[p->ahist_cur ^ 1].get() : nullptr, p->C, nblocks, (long long)p->sum_lout, call.stream));
+                                      K > 1 ? p->d_ahist[p->ahist_cur ^ 1].get() : nullptr, p->C, nblocks, (long long)p->sum_lout, call.stream, pp.squelch));
         p->ahist_cur ^= 1; p->audio_next = first_block + nblocks;
-        p->audio_route = "pass";
+        p->audio_route = pp.squelch ? "pass, gated" : "pass";
     }
     if (pp.narrow_tail) HIPCHK(fdc::launch_complex_to_iq(call.ofmt, call.oscale, call.fout, d_out, (size_t)nblocks * p->sum_lout, call.stream));
     if (pp.fine_fused || pp.rotate) p->fine_route = pp.fine_fused ? "fused" : "rotated";
@@ -281,6 +293,11 @@ int process_device_impl(fdc_pipeline *p, DeviceCall &call, const void *d_ring, i
         // the same rule for the audio's history, in both modes
         pp.audio_cont = p->audio_next == first_block;
         p->audio_next = -1;
+    }
+    if (pp.squelch) {
+        // ... and for the squelch's state
+        pp.squelch_cont = p->squelch_next == first_block;
+        p->squelch_next = -1;
     }
     // path 5: the call's part of every group's launch (the group's: its input, its blocks and its waterfall rows)
     fdc::F4Launch f4{};
@@ -424,6 +441,11 @@ void audio_written(fdc_pipeline *p, int nblocks, hipStream_t stream, bool host)
     p->aud_blocks = nblocks; p->aud_stream = stream; p->aud_host = host;
 }
 
+void squelch_written(fdc_pipeline *p, int nblocks, hipStream_t stream, bool host)
+{
+    p->sq_blocks = nblocks; p->sq_stream = stream; p->sq_host = host;
+}
+
 // how the last integer-input / integer-output call was served (fdc_pipeline_describe): "<sc16|sc8>: fused", or what it was instead
 std::string route(int fmt, bool fused, const char *otherwise)
 {
@@ -449,6 +471,7 @@ static int process_device_oq(fdc_pipeline *p, DeviceCall &call, const void *d_ri
     if (lev) {
         if (nblocks > p->cfg.max_blocks) return set_error(FDC_ERR_INVALID_ARGUMENT, "channel levels: nblocks %d above max_blocks %d", nblocks, p->cfg.max_blocks);
         call.levels = p->d_levels;
+        call.squelch = squelch_rows(p, 0);      // (the mask goes to the handle's buffer, [max_blocks][C]: the check above covers it)
     }
     const bool lag = p->lag1_on && nblocks > 0;
     if (lag) {
@@ -468,6 +491,7 @@ static int process_device_oq(fdc_pipeline *p, DeviceCall &call, const void *d_ri
     if (rc == FDC_OK && lev) levels_written(p, nblocks, call.stream, false);
     if (rc == FDC_OK && lag) lag1_written(p, nblocks, call.stream, false);
     if (rc == FDC_OK && call.audio) audio_written(p, nblocks, call.stream, false);
+    if (rc == FDC_OK && call.squelch) squelch_written(p, nblocks, call.stream, false);
     return rc;
 }
 

@@ -270,10 +270,19 @@ hipError_t launch_chan_demod(int mode, float gain, const float2 *in, float *out,
 // oq_round(a, scale)).  out: row 0 of the call's block-major matrix [nb_call][row] of float / int16; channel c owns the lout_c / decim columns from
 // aoff[c] on.  hist_in ([nchan][ntaps - 1] float; null: zeros) stands in front of every channel's first sample, hist_out (another buffer; null only
 // where ntaps = 1) receives the last ntaps - 1 values of (what stood in front, the call's samples).  decim divides every lout_c
+// gate (null: none): row 0 of the call's squelch mask ([nb_call][nchan] bytes, launch_chan_squelch): the gated forms, which store zero bits for the
+// outputs of a closed (block, channel), skip the work of closed tiles and leave the history what the ungated pass leaves
 enum { kAudioF32 = 0, kAudioS16 = 1 };
 hipError_t launch_chan_audio(int format, int decim, int ntaps, float scale, const float *taps, const long long *aoff, long long row, const float *in,
                              void *out, const ChanDev *chans, const float *hist_in, float *hist_out, int nchan, int nb_call, long long sum_lout,
-                             hipStream_t s);
+                             hipStream_t s, const unsigned char *gate = nullptr);
+
+// Channel squelch (fdc_pipeline_set_squelch): the decision over the call's rows of the levels ([nb_call][nchan] (power, peak), launch_chan_levels and
+// its kin), one byte per (block, channel) to mask ([nb_call][nchan]): open at a block whose power reaches g2 thr_open[c], held while it reaches
+// g2 thr_close[c], closed after hang + 1 consecutive blocks below (g2 = gain[c]^2 rounded once; gain null: 1).  state_in ([nchan][2] int: open, h;
+// null: all closed) stands in front of the call, state_out (another buffer) receives the state behind its last block.  hang 0 .. 65535
+hipError_t launch_chan_squelch(const float2 *levels, const float *gain, const float *thr_open, const float *thr_close, int hang, const int *state_in,
+                               int *state_out, unsigned char *mask, int nchan, int nb_call, hipStream_t s);
 
 hipError_t launch_scale(const float2 *in, float2 *out, size_t n, float k, hipStream_t s);
 

@@ -219,6 +219,24 @@ struct fdc_pipeline {
     bool aud_host = false;
     hipStream_t aud_stream = nullptr;
     std::string audio_route;     // the last call with the setting on ran the audio pass (fdc_pipeline_describe)
+    // channel squelch (fdc_pipeline_set_squelch): a setting that needs the levels.  sq_open / sq_close: the C thresholds in force, d_sqthr[0] / [1] their
+    // device tables; sq_hang the hang count.  d_sqstate: the stream state, (open, h) of every channel behind the last call, two buffers of C int pairs: a
+    // call reads d_sqstate[sqstate_cur] where it continues the stream (its first_block is squelch_next; -1: every channel starts closed) and its kernel
+    // writes the other one; the enqueue path swaps behind a successful enqueue (the audio history likewise).  d_mask: [max_blocks][C] bytes of the last
+    // call, pin_mask its pinned twin (sq_host, sq_stream as lev_host, lev_stream).  All of it is allocated by fdc_pipeline_set_squelch.
+    bool squelch_on = false;
+    std::vector<float> sq_open, sq_close;
+    int sq_hang = 0;
+    fdc::DevBuf<float> d_sqthr[2];
+    fdc::DevBuf<int> d_sqstate[2];
+    int sqstate_cur = 0;
+    int64_t squelch_next = -1;
+    fdc::DevBuf<unsigned char> d_mask;
+    fdc::PinBuf<unsigned char> pin_mask;
+    int sq_blocks = -1;          // block count of the last successful work call with the squelch on (-1: none yet)
+    bool sq_host = false;
+    hipStream_t sq_stream = nullptr;
+    std::string squelch_route;   // the last call with the setting on ran the squelch pass (fdc_pipeline_describe)
     fdc::DevBuf<float2> d_out;   // work(): max_blocks*sum_lout (out_staging)
     int64_t blockcount = 0;      // work(): blocks consumed so far
     // work(): transfers and kernels of consecutive sub-batches overlap (H2D on s_in, kernels on stream, D2H on s_out)
@@ -284,7 +302,9 @@ struct DeviceCall {
     // channel audio (fdc_pipeline_set_audio): where row 0 of the call's audio goes, [block][A] elements of the setting's format; null = none.  It
     // goes with a demodulating output code only
     void *audio = nullptr;
-    int ncu = 0;                         // compute units the call's persistent kernels may use
+    // channel squelch (fdc_pipeline_set_squelch): where the mask byte of the call's block 0, channel 0 goes, [block][C]; null = none.  It goes with levels
+    unsigned char *squelch = nullptr;
+    int ncu = 0;                        // compute units the call's persistent kernels may use
     // results: no launch group had to be widened (each read the integer input in its own loads); the call's kernels narrowed in their own stores
     bool all_fused = true, ofused = false;
 };
@@ -306,6 +326,12 @@ inline bool audio_on(const fdc_pipeline *p) { return p->audio_decim > 0 && p->de
 inline size_t audio_bytes(const fdc_pipeline *p) { return p->audio_format == FDC_AUDIO_S16 ? sizeof(int16_t) : sizeof(float); }
 // ... and where the rows from block b0 of a host call on go in the handle's buffer
 inline void *audio_rows(const fdc_pipeline *p, size_t b0) { return audio_on(p) ? p->d_audio.get() + audio_bytes(p) * b0 * (size_t)p->audio_row : nullptr; }
+
+// channel squelch: where the mask rows from block b0 of a host call on go in the handle's buffer (null: the call runs no squelch pass)
+inline unsigned char *squelch_rows(const fdc_pipeline *p, size_t b0)
+{
+    return p->squelch_on && p->levels_on && p->C > 0 ? p->d_mask.get() + b0 * (size_t)p->C : nullptr;
+}
 
 inline bool ispow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
 
@@ -344,6 +370,7 @@ int check_iq_form(int32_t format, float scale);
 void levels_written(fdc_pipeline *p, int nblocks, hipStream_t stream, bool host);   // a call with levels on succeeded: what fdc_pipeline_levels hands out
 void lag1_written(fdc_pipeline *p, int nblocks, hipStream_t stream, bool host);     // the same of the lag-1 correlation (fdc_pipeline_lag1)
 void audio_written(fdc_pipeline *p, int nblocks, hipStream_t stream, bool host);    // ... and of the channel audio (fdc_pipeline_audio)
+void squelch_written(fdc_pipeline *p, int nblocks, hipStream_t stream, bool host);  // ... and of the channel squelch (fdc_pipeline_squelch)
 std::string route(int fmt, bool fused, const char *otherwise);   // "<sc16|sc8>: fused", or what the call was instead (fdc_pipeline_describe)
 
 } }  // namespace fdc::pipe

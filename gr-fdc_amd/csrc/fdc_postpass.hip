@@ -1,8 +1,9 @@
 // gfx950 (MI355X, CDNA4) kernels of the frequency-domain channelizer — the passes that run BEHIND a plan's kernels, over the channel-major float
 // results of a launch group: the rotation of fine tuning (k_fine_rotate), the channel gains (k_chan_gain), the channel levels (k_chan_levels), the
 // channel lag-1 correlation (k_chan_lag1) and the narrowing to complex integers (k_complex_to_iq) — and, over a whole call's float results in the
-// place of the narrowing, the channel demodulation (k_chan_demod) and behind it the channel audio (k_chan_audio, at the end of this file).  Which of
-// them a call runs, and in which order, is decided once per call: PostPass, fdc_enqueue.hip.
+// place of the narrowing, the channel demodulation (k_chan_demod) and behind it the channel audio (k_chan_audio, at the end of this file), which the
+// channel squelch (k_chan_squelch, over the call's levels) gates.  Which of them a call runs, and in which order, is decided once per call: PostPass,
+// fdc_enqueue.hip.
 //
 // One shape for the four per-channel kernels: grid y = channel, a row — the lout samples of one (block, channel) — on a power-of-two set of lanes of one
 // wave, 16 bytes per lane and access where the row allows it (lout even, the channel's run 16-byte aligned), 8 bytes otherwise, a grid-stride loop over
@@ -602,6 +603,160 @@ hipError_t launch_chan_demod(int mode, float gain, const float2 *in, float *out,
     });
 }
 
+// Channel squelch (fdc_pipeline_set_squelch): per channel a state machine over the blocks of the stream — open at a block whose power reaches the
+// open threshold, held while it reaches the close threshold, closed after hang + 1 consecutive blocks below it — in the PARALLEL form
+// tests/squelch_model.py proves equal to the sequential rule.  With strong = (p >= To) and low = neither p >= To nor p >= Tc, block m is open iff a
+// strong block lies at or before m and no run of hang + 1 consecutive low blocks has ended behind that strong block and at or before m.  Three
+// inclusive max-scans over the block index give that: s = the last strong block, nl = the last block that is not low (m - nl is the length of the run
+// of low blocks that ends at m), e = the last block at which that length reached hang + 1; open = s > e.  A carried open state (1, h) stands for
+// a strong block at index -1 - (hang - h) with hang - h low blocks behind it; a closed one for none (kSqNeg).  The scans are on integers, so
+// the order in which they are joined does not show in the result.
+// One workgroup per channel.  A trip covers 256 * kSqPer consecutive blocks, a lane kSqPer consecutive ones: the lane walks its own blocks, the lanes
+// of a wave are joined by __shfl_up, the four waves through LDS, the trips by a carry every lane holds.  The trip count depends on nb alone and both
+// barriers of a trip stand outside every per-lane condition (the rule of lag1_rows); the LDS slots alternate with the trip, so no third barrier guards
+// them.  The powers of the next trip are loaded before this trip's scans.  The thread that decides block nb - 1 writes the new state, to ANOTHER
+// buffer than the one read.
+// kSqPer = 16 (4096 blocks a trip).  On a call of four channels and 16384 blocks (four workgroups) it takes about 0.025 ms, 0.86 of k_chan_levels
+// (profiles/squelch/README.md), and WHAT BOUNDS IT THERE HAS NOT BEEN MEASURED.  Known: 8 blocks a lane, twice the trips, took the same time within
+// the spread, so the trip count alone is not it.  A hypothesis from the code: within one load or store instruction every lane touches another
+// cache line (rows of C (power, peak) pairs, a lane's rows 16 apart), so a compute unit issues 64 line requests per instruction, although a lane's
+// later loads reuse its lines and the four workgroups read the same ones; latency and launch overhead of four workgroups may weigh as much.
+// Staging a trip's rows through LDS with the lanes on consecutive rows, and a wave per channel for short calls, are not built.  At 32 blocks a
+// lane the kernel spilled scalar registers.
+constexpr int kSqNeg = -(1 << 30);
+constexpr unsigned kSqPer = 16;
+
+// inclusive max-scan over the lanes of a wave (run by the whole wave)
+__device__ __forceinline__ int wave_max_scan(int v)
+{
+    const int lane = (int)(threadIdx.x & 63);
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const int u = __shfl_up(v, (unsigned)d, 64);
+        v = lane >= d && u > v ? u : v;
+    }
+    return v;
+}
+
+// the value in front of this thread's: carry, the waves below (tot: their totals) and the lanes below (inc: the wave's inclusive scan)
+__device__ __forceinline__ int scan_front(int inc, int carry, const int *tot, int &total)
+{
+    const int w = (int)(threadIdx.x >> 6), up = __shfl_up(inc, 1u, 64);
+    int below = carry;
+    total = carry;
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+        const int t = tot[u];
+        if (u < w && t > below) below = t;
+        if (t > total) total = t;
+    }
+    return (threadIdx.x & 63) && up > below ? up : below;
+}
+
+// levels: row 0 of the call ([nb][nchan] (power, peak)); mask: row 0 of the call's mask ([nb][nchan] bytes); gain: null = all ones;
+// state_in: null = every channel (0, 0); state_out: [nchan][2] int (open, h)
+__global__ __launch_bounds__(256) void k_chan_squelch(const float2 *__restrict__ levels, const float *__restrict__ gain, const float *__restrict__ thr_open,
+                                                      const float *__restrict__ thr_close, const int *__restrict__ state_in, int *__restrict__ state_out,
+                                                      unsigned char *__restrict__ mask, int hang, int nchan, int nb)
+{
+    __shared__ int tot[2][3][4];
+    const int c = (int)blockIdx.x;
+    const unsigned tid = threadIdx.x, w = tid >> 6;
+    float To, Tc;
+    {
+#pragma clang fp contract(off)
+        const float g = gain ? gain[c] : 1.0f;
+        const float g2 = g * g;
+        To = g2 * thr_open[c];
+        Tc = g2 * thr_close[c];
+    }
+    int cs = kSqNeg, cn = -1, ce = kSqNeg;                  // the carries in front of the trip: last strong, last not low, last run end
+    if (state_in) {
+        const int so = state_in[2 * c], sh = state_in[2 * c + 1];
+        if (so != 0) {
+            const int h = sh < 0 ? 0 : sh > hang ? hang : sh;
+            cs = cn = -1 - (hang - h);
+        }
+    }
+    const float2 *lv = levels + c;
+    unsigned char *mrow = mask + c;
+    const unsigned per_trip = 256 * kSqPer;
+    float p[kSqPer], pn[kSqPer];
+#pragma unroll
+    for (unsigned v = 0; v < kSqPer; v++) {
+        const unsigned m = tid * kSqPer + v;
+        pn[v] = lv[(size_t)(m < (unsigned)nb ? m : (unsigned)nb - 1) * (size_t)nchan].x;
+    }
+    for (unsigned m0 = 0, par = 0; m0 < (unsigned)nb; m0 += per_trip, par ^= 1) {
+        const unsigned mb = m0 + tid * kSqPer;
+#pragma unroll
+        for (unsigned v = 0; v < kSqPer; v++) p[v] = pn[v];
+        if (m0 + per_trip < (unsigned)nb) {                 // (the same for the whole workgroup)
+#pragma unroll
+            for (unsigned v = 0; v < kSqPer; v++) {
+                const unsigned m = mb + per_trip + v;
+                pn[v] = lv[(size_t)(m < (unsigned)nb ? m : (unsigned)nb - 1) * (size_t)nchan].x;
+            }
+        }
+        // the lane's own blocks: their classes, its last strong and last not-low block
+        unsigned strong = 0, low = 0;
+        int ls = kSqNeg, ln = kSqNeg;
+#pragma unroll
+        for (unsigned v = 0; v < kSqPer; v++) {
+            if (mb + v < (unsigned)nb) {
+                const bool s = p[v] >= To, l = !s && !(p[v] >= Tc);
+                strong |= (unsigned)s << v; low |= (unsigned)l << v;
+                if (s) ls = (int)(mb + v);
+                if (!l) ln = (int)(mb + v);
+            }
+        }
+        const int is = wave_max_scan(ls), in = wave_max_scan(ln);
+        if ((tid & 63) == 63) { tot[par][0][w] = is; tot[par][1][w] = in; }
+        __syncthreads();
+        int ts, tn, te;
+        const int fs = scan_front(is, cs, tot[par][0], ts), fn = scan_front(in, cn, tot[par][1], tn);
+        // where a run of low blocks reached hang + 1 among the lane's own
+        int n = fn, le = kSqNeg;
+#pragma unroll
+        for (unsigned v = 0; v < kSqPer; v++) {
+            if (mb + v < (unsigned)nb) {
+                if (!((low >> v) & 1)) n = (int)(mb + v);
+                if ((int)(mb + v) - n >= hang + 1) le = (int)(mb + v);
+            }
+        }
+        const int ie = wave_max_scan(le);
+        if ((tid & 63) == 63) tot[par][2][w] = ie;
+        __syncthreads();
+        const int fe = scan_front(ie, ce, tot[par][2], te);
+        // the decisions of the lane's own blocks
+        int s = fs, e = fe;
+        n = fn;
+#pragma unroll
+        for (unsigned v = 0; v < kSqPer; v++) {
+            const int m = (int)(mb + v);
+            if (m < nb) {
+                if ((strong >> v) & 1) s = m;
+                if (!((low >> v) & 1)) n = m;
+                if (m - n >= hang + 1) e = m;
+                const int open = s > e;
+                mrow[(size_t)m * (size_t)nchan] = (unsigned char)open;
+                if (m == nb - 1) { state_out[2 * c] = open; state_out[2 * c + 1] = open ? hang - (m - n) : 0; }
+            }
+        }
+        cs = ts; cn = tn; ce = te;
+    }
+}
+
+hipError_t launch_chan_squelch(const float2 *levels, const float *gain, const float *thr_open, const float *thr_close, int hang, const int *state_in,
+                               int *state_out, unsigned char *mask, int nchan, int nb_call, hipStream_t s)
+{
+    if (nchan <= 0 || nb_call <= 0) return hipSuccess;
+    if (!levels || !thr_open || !thr_close || !state_out || !mask || state_in == state_out || hang < 0 || hang > 65535) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_chan_squelch, dim3((unsigned)nchan), dim3(256), 0, s, levels, gain, thr_open, thr_close, state_in, state_out, mask, hang,
+                       nchan, nb_call);
+    return hipGetLastError();
+}
+
 // Channel audio (fdc_pipeline_set_audio): the decimating FIR behind the demodulation, a[n] = sum over k = 0 .. K - 1 of h[k] d[n D - k] over one
 // channel's run d of the call (T = nblocks * lout real samples, contiguous across the blocks; in front of d[0] stand the K - 1 values of the history,
 // or zeros).  THE ORDER IS THE DEFINITION: k ascending from acc = +0, every product and every sum rounded on its own (audio_mac).
@@ -646,16 +801,39 @@ __device__ __forceinline__ float audio_sample(const float *d, const float *hin, 
     return t >= 0 ? d[t] : hin ? hin[K - 1 + t] : 0.0f;
 }
 
+// THE GATED FORMS (GATE; the channel squelch on, fdc_pipeline_set_squelch): an output of a closed (block, channel) is stored as zero bits, the
+// footprint is the ungated pass's, and the history runs on over the ungated samples.  What they save is the work: a tile none of whose rows is open
+// stages nothing and runs no tap loop (every wave looks at the same rows of the mask and joins its lanes by a ballot, so the condition is the same
+// for the whole workgroup, and both barriers stand outside it); a wave whose trip of 256 outputs lies in closed rows skips the tap loop; otherwise
+// the store selects per output.  The ungated forms take no gate arguments and are the code they were.
+__device__ __forceinline__ const unsigned char *gate_mask(const unsigned char *m, int) { return m; }
+__device__ __forceinline__ unsigned gate_pitch(const unsigned char *, int nchan) { return (unsigned)nchan; }
+
+// whether any of the rows [r0, r1] of one channel's mask column is open: the same answer in every lane of the wave
+__device__ __forceinline__ bool gate_any_open(const unsigned char *col, unsigned pitch, unsigned r0, unsigned r1)
+{
+    bool open = false;
+    for (unsigned r = r0; r <= r1; r += 64) {               // (the trip count is the wave's)
+        const unsigned rr = r + (threadIdx.x & 63);
+        open = open || (rr <= r1 && col[(size_t)rr * pitch] != 0);
+    }
+    return __builtin_amdgcn_ballot_w64(open) != 0;
+}
+
 // in: the call's demodulated samples ([channel][nb_call * lout] float at nb_call * out_off); out: row 0 of the call's audio ([nb_call][A] TO);
-// hist_in (null: zeros) and hist_out (null where K = 1): [nchan][K - 1] float
-template <class TO>
+// hist_in (null: zeros) and hist_out (null where K = 1): [nchan][K - 1] float; gate (GATE only): row 0 of the call's mask ([nb_call][nchan] bytes), nchan
+template <class TO, bool GATE, class... Gate>
 __global__ __launch_bounds__(256) void k_chan_audio(const float *__restrict__ in, TO *__restrict__ out, const ChanDev *__restrict__ chans,
                                                     const long long *__restrict__ aoff, const float *__restrict__ taps,
                                                     const float *__restrict__ hist_in, float *__restrict__ hist_out, int D, int K, float scale,
-                                                    long long A, int c0, long long nb_call)
+                                                    long long A, int c0, long long nb_call, Gate... gate)
 {
+    static_assert(GATE == (sizeof...(Gate) == 2), "the gated forms take (mask, nchan)");
     __shared__ float tile[kAudioLdsWords];
     const int c = c0 + (int)blockIdx.y;
+    const unsigned char *gcol = nullptr;                            // GATE: the channel's column of the mask and the pitch of its rows
+    unsigned gpitch = 0;
+    if constexpr (GATE) { gcol = gate_mask(gate...) + c; gpitch = gate_pitch(gate...); }
     const unsigned lout = (unsigned)chans[c].lout, tid = threadIdx.x;
     const unsigned npb = lout / (unsigned)D;                        // outputs per block
     const unsigned nout = (unsigned)nb_call * npb;
@@ -673,13 +851,17 @@ __global__ __launch_bounds__(256) void k_chan_audio(const float *__restrict__ in
     for (unsigned o0 = blockIdx.x * g.outs; o0 < nout; o0 += gridDim.x * g.outs) {
         const unsigned nt = nout - o0 < g.outs ? nout - o0 : g.outs;            // outputs of this tile
         const long long t0 = (long long)o0 * D - (K - 1);
+        // GATE: a tile without an open row stages nothing (its samples count as none: no lane below has anything to load), and its waves run no tap
+        // loop and store zeros.  The same for the whole workgroup, and both barriers stand outside the condition
+        bool tile_open = true;
+        if constexpr (GATE) tile_open = gate_any_open(gcol, gpitch, o0 / npb, (o0 + nt - 1) / npb);
         // stage.  The samples in front of the run (the first tile's K - 1) come from the history.  Those of the run are loaded 16 bytes at a time
         // between the 16-byte boundaries inside them, four such loads in flight per lane (a lane past the last quad loads that one again and stores
         // nothing); the up to three samples in front of the first boundary and behind the last are loaded one by one
         const long long tb = t0 < 0 ? 0 : t0;
-        if (t0 < 0 && tid < (unsigned)(K - 1)) tile[lds_at(tid)] = hin ? hin[tid] : 0.0f;                 // (tile sample i is t = i - (K - 1))
+        if (tile_open && t0 < 0 && tid < (unsigned)(K - 1)) tile[lds_at(tid)] = hin ? hin[tid] : 0.0f;                 // (tile sample i is t = i - (K - 1))
         // element e of da is sample tb - lo + e of the run, da 16-byte aligned: the tile's are [lo, hi), and e is tile sample e + first
-        const unsigned lo = (unsigned)((reinterpret_cast<uintptr_t>(d + tb) >> 2) & 3), hi = lo + (unsigned)((long long)(o0 + nt) * D - tb);
+        const unsigned lo = (unsigned)((reinterpret_cast<uintptr_t>(d + tb) >> 2) & 3), hi = lo + (tile_open ? (unsigned)((long long)(o0 + nt) * D - tb) : 0u);
         const unsigned first = (unsigned)(tb - t0) - lo;
         const unsigned up = (lo + 3) & ~3u, down = hi & ~3u;
         const unsigned lo4 = up < hi ? up : hi, hi4 = down > lo4 ? down : lo4;      // the quads are [lo4, hi4): lo <= lo4 <= hi4 <= hi
@@ -711,11 +893,14 @@ __global__ __launch_bounds__(256) void k_chan_audio(const float *__restrict__ in
                 j[u] = jj < nt ? jj : nt - 1;                                   // (a lane without an output computes the tile's last and leaves it out)
                 acc[u] = 0.0f;
             }
+            // GATE: a trip that lies wholly in closed rows runs no tap loop (the same for the whole wave)
+            bool taps_run = true;
+            if constexpr (GATE) taps_run = tile_open && gate_any_open(gcol, gpitch, (o0 + j0) / npb, (o0 + (j0 + 256 < nt ? j0 + 256 : nt) - 1) / npb);
             // tap k reads tile sample j D + (K - 1 - k): the plane and the index in front go down with k
             unsigned r = (unsigned)(K - 1) % (unsigned)D, at = r * g.pitch + (unsigned)(K - 1) / (unsigned)D;
             // (four taps a trip, which is what the scalar registers hold without a spill: their scalar loads and LDS reads are in flight together, not each behind its own wait)
 #pragma unroll 4
-            for (int k = 0; k < K; k++) {
+            for (int k = 0; k < (taps_run ? K : 0); k++) {
                 const float h = taps[k];
 #pragma unroll
                 for (unsigned u = 0; u < 4; u++) acc[u] = audio_mac(acc[u], h, tile[at + j[u]]);
@@ -726,7 +911,9 @@ __global__ __launch_bounds__(256) void k_chan_audio(const float *__restrict__ in
                 const unsigned jj = j0 + u * 64 + (tid & 63);
                 if (jj < nt) {
                     const unsigned n = o0 + jj, m = n / npb;
-                    audio_store(o, (long long)m * A + (long long)(n - m * npb), acc[u], scale);
+                    const long long at_out = (long long)m * A + (long long)(n - m * npb);
+                    if (GATE && !gcol[(size_t)m * gpitch]) o[at_out] = TO(0);
+                    else audio_store(o, at_out, acc[u], scale);
                 }
             }
         }
@@ -738,7 +925,7 @@ __global__ __launch_bounds__(256) void k_chan_audio(const float *__restrict__ in
 
 hipError_t launch_chan_audio(int format, int decim, int ntaps, float scale, const float *taps, const long long *aoff, long long row, const float *in,
                              void *out, const ChanDev *chans, const float *hist_in, float *hist_out, int nchan, int nb_call, long long sum_lout,
-                             hipStream_t s)
+                             hipStream_t s, const unsigned char *gate)
 {
     if (nchan <= 0 || nb_call <= 0) return hipSuccess;
     if (format != kAudioF32 && format != kAudioS16) return hipErrorInvalidValue;
@@ -747,12 +934,19 @@ hipError_t launch_chan_audio(int format, int decim, int ntaps, float scale, cons
     // the grid: a workgroup per tile of a run of mean length (channel_grids takes it in units of four)
     const long long tiles = ((long long)nb_call * sum_lout / nchan / decim) / audio_tile((unsigned)decim, (unsigned)ntaps).outs + 1;
     return channel_grids(nchan, (int)std::min<long long>(4 * tiles, 1 << 20), [&](dim3 grid, int c0) {
-        if (format == kAudioS16)
-            hipLaunchKernelGGL(k_chan_audio<short>, grid, dim3(256), 0, s, in, static_cast<short *>(out), chans, aoff, taps, hist_in, hist_out, decim, ntaps,
-                               scale, row, c0, (long long)nb_call);
+        if (gate) {
+            if (format == kAudioS16)
+                hipLaunchKernelGGL((k_chan_audio<short, true, const unsigned char *, int>), grid, dim3(256), 0, s, in, static_cast<short *>(out), chans, aoff,
+                                   taps, hist_in, hist_out, decim, ntaps, scale, row, c0, (long long)nb_call, gate, nchan);
+            else
+                hipLaunchKernelGGL((k_chan_audio<float, true, const unsigned char *, int>), grid, dim3(256), 0, s, in, static_cast<float *>(out), chans, aoff,
+                                   taps, hist_in, hist_out, decim, ntaps, scale, row, c0, (long long)nb_call, gate, nchan);
+        } else if (format == kAudioS16)
+            hipLaunchKernelGGL((k_chan_audio<short, false>), grid, dim3(256), 0, s, in, static_cast<short *>(out), chans, aoff, taps, hist_in, hist_out, decim,
+                               ntaps, scale, row, c0, (long long)nb_call);
         else
-            hipLaunchKernelGGL(k_chan_audio<float>, grid, dim3(256), 0, s, in, static_cast<float *>(out), chans, aoff, taps, hist_in, hist_out, decim, ntaps,
-                               scale, row, c0, (long long)nb_call);
+            hipLaunchKernelGGL((k_chan_audio<float, false>), grid, dim3(256), 0, s, in, static_cast<float *>(out), chans, aoff, taps, hist_in, hist_out, decim,
+                               ntaps, scale, row, c0, (long long)nb_call);
     });
 }
 

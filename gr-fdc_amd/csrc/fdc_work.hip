@@ -32,6 +32,9 @@ static int levels_home(fdc_pipeline *p, int nblocks, hipStream_t s)
         HIPCHK(hipMemcpyAsync(p->pin_levels.get(), p->d_levels.get(), sizeof(float2) * (size_t)nblocks * p->C, hipMemcpyDeviceToHost, s));
     if (p->lag1_on && p->C > 0)
         HIPCHK(hipMemcpyAsync(p->pin_lag1.get(), p->d_lag1.get(), sizeof(float2) * (size_t)nblocks * p->C, hipMemcpyDeviceToHost, s));
+    // ... and of its squelch mask (fdc_pipeline_squelch)
+    if (squelch_rows(p, 0))
+        HIPCHK(hipMemcpyAsync(p->pin_mask.get(), p->d_mask.get(), (size_t)nblocks * p->C, hipMemcpyDeviceToHost, s));
     // ... and of its audio rows, which are all the call hands to the host while the channel audio is on (fdc_pipeline_audio)
     if (audio_on(p))
         HIPCHK(hipMemcpyAsync(p->pin_audio.get(), p->d_audio.get(), audio_bytes(p) * (size_t)nblocks * (size_t)p->audio_row, hipMemcpyDeviceToHost, s));
@@ -199,6 +202,7 @@ static int pipeline_work_impl(fdc_pipeline *p, DeviceCall call, const void *in, 
         call.levels = p->levels_on && p->C > 0 ? p->d_levels + b0 * (size_t)p->C : nullptr;
         call.lag1 = p->lag1_on && p->C > 0 ? p->d_lag1 + b0 * (size_t)p->C : nullptr;
         call.audio = audio_rows(p, b0);
+        call.squelch = squelch_rows(p, b0);
         const int rc2 = process_device_impl(p, call, ringb + b0 * p->H * esz, first, nb,
                                             ofmt ? static_cast<void *>(p->d_oq + osz * b0 * (size_t)p->sum_lout) : static_cast<void *>(dok));
         oq_all = oq_all && call.ofused;
@@ -249,6 +253,7 @@ static int pipeline_work_impl(fdc_pipeline *p, DeviceCall call, const void *in, 
         if (p->levels_on) levels_written(p, nblocks, s, true);
     if (p->lag1_on) lag1_written(p, nblocks, s, true);
         if (audio) audio_written(p, nblocks, s, true);
+        if (squelch_rows(p, 0)) squelch_written(p, nblocks, s, true);
         if (fmt) p->iq_route = route(fmt, call.all_fused, "widened");
         if (p->out_form) p->oq_route = route(ofmt, oq_all, "narrowed");
         if (ports && !out_reg) deliver(0, 0, nblocks);
@@ -316,6 +321,7 @@ static int pipeline_work_impl(fdc_pipeline *p, DeviceCall call, const void *in, 
     if (p->levels_on) levels_written(p, nblocks, s, true);
     if (p->lag1_on) lag1_written(p, nblocks, s, true);
     if (audio) audio_written(p, nblocks, s, true);
+    if (squelch_rows(p, 0)) squelch_written(p, nblocks, s, true);
     if (fmt) p->iq_route = route(fmt, call.all_fused, "widened");
     if (p->out_form) p->oq_route = route(ofmt, oq_all, "narrowed");
     p->blockcount += nblocks;
@@ -417,6 +423,7 @@ static int pipeline_work_real_impl(fdc_pipeline *p, const void *in, int nblocks,
     call.levels = p->levels_on && p->C > 0 ? p->d_levels.get() : nullptr;
     call.lag1 = p->lag1_on && p->C > 0 ? p->d_lag1.get() : nullptr;
     call.audio = audio_rows(p, 0);
+    call.squelch = squelch_rows(p, 0);
     RCCHK(process_device_impl(p, call, p->d_ring, p->blockcount, nblocks, res));
     if (!call.audio) RCCHK(copy_outputs(p, outs, nblocks, osz, res, s));     // (audio on: the rows go home with the levels, outs is not looked at)
     if (spectrum) HIPCHK(hipMemcpyAsync(spectrum, d_specfull, sizeof(float2) * (size_t)nblocks * p->N, hipMemcpyDeviceToHost, s));
@@ -426,6 +433,7 @@ static int pipeline_work_real_impl(fdc_pipeline *p, const void *in, int nblocks,
     if (p->levels_on) levels_written(p, nblocks, s, true);
     if (p->lag1_on) lag1_written(p, nblocks, s, true);
     if (call.audio) audio_written(p, nblocks, s, true);
+    if (call.squelch) squelch_written(p, nblocks, s, true);
     if (p->out_form) p->oq_route = route(ofmt, call.ofused, "narrowed");
     p->blockcount += nblocks;
     return nblocks;

@@ -401,8 +401,57 @@ void *fdc_pipeline_audio_device(fdc_pipeline *p);
  * audio setting (which must be on) and nothing of its stream state: d_in real float32 in fdc_pipeline_process_device's layout (channel c at element
  * offset nblocks*out_off_c), d_out exactly nblocks * A elements, d_hist_in C (K - 1) floats or NULL (zeros), d_hist_out another buffer that receives
  * exactly C (K - 1) floats (NULL only where K = 1).  Enqueued on `stream` (NULL: the handle's). */
+/* While the channel squelch is on (below) this entry does read one thing of the handle's: it runs the GATED form over the mask of the last successful
+ * work call (fdc_pipeline_squelch_device), and is refused unless nblocks is that call's block count; the bytes written are the same. */
 int fdc_pipeline_audio_pass_device(const fdc_pipeline *p, const void *d_in, void *d_out, const void *d_hist_in, void *d_hist_out, int nblocks,
                                    void *stream);
+
+/* CHANNEL SQUELCH: per channel a carrier-operated squelch on the block powers the levels give, decided on the device, with hysteresis and a hang time;
+ * with the channel audio on it gates the audio.  The setting: per-channel float32 thresholds open_c >= close_c >= 0, finite, and one hang count of
+ * blocks, 0 .. 65535.  The state of a channel is (open in {0, 1}, h in [0, hang]) and starts as (0, 0).  For block m of the stream, in order:
+ *     p  = the float32 power the levels hold for (m, c) (after fine tuning and the gain)
+ *     g2 = float32(g_c g_c), g_c the channel gain in force (1 while the gains are off);  To = float32(g2 open_c), Tc = float32(g2 close_c)
+ *     if p >= To: open = 1, h = hang;   else if open and p >= Tc: h = hang;   else if open: h > 0 ? h -= 1 : open = 0
+ *     mask[m][c] = open
+ * Every comparison is an IEEE float32 >=, so a NaN power or a NaN threshold product is below.  The thresholds therefore refer to the power IN FRONT of
+ * the gain: an AGC that levels every channel does not defeat them.  Their unit is the levels' own: the sum over the row of re^2 + im^2, which is the
+ * mean power times lout_c.  tests/squelch_model.py states the rule in numpy, and the mask is that model's byte for byte.
+ * A GAIN OF 0 makes both products +0, which every power that is not NaN reaches (the gained samples are zeros, their power +0): a channel muted
+ * with gain 0 has mask = 1, whatever its thresholds.  Mute with the squelch's thresholds, not with the gain, where the mask matters.
+ * THE STATE lives on the device, one int32 pair per channel.  It is used when a call CONTINUES the stream, that is when its first_block is the block
+ * after the last one of the previous successful call with the squelch on (the handle keeps this position for the squelch); otherwise every channel
+ * starts at (0, 0): after create or fdc_pipeline_reset, after switching the squelch on, after a call that failed once it had begun to enqueue, at a
+ * device or span call elsewhere in the stream.  New thresholds or a new hang count while it is on keep `open`; h is read as min(h, the hang count
+ * in force), and is 0 while the channel is closed.  A call that is REFUSED leaves everything as it was.  The bits of the mask depend on the
+ * stream's powers and the settings only, not on how the stream is cut into calls, sub-batches or launch groups, nor on the plan's route.
+ *   fdc_pipeline_set_squelch          open_thr NULL switches it off.  FDC_ERR_INVALID_ARGUMENT, the previous setting staying in force: n != C; a threshold
+ *                                     that is not finite or negative; close > open; hang out of range; while the levels are off; while a pipelined sinks
+ *                                     batch is inside the handle.  fdc_pipeline_set_levels(p, 0) is refused while the squelch is on.  A SETTING: it
+ *                                     applies from the next call and survives fdc_pipeline_reset (the state does not); it waits for the handle's own
+ *                                     stream first.  It allocates everything the feature needs, once: two threshold tables, two state buffers, max_blocks
+ *                                     C mask bytes and their pinned twin; nothing in the steady state of any entry.  A plan without channels accepts it.
+ *   fdc_pipeline_squelch_setting      the setting in force; any pointer may be NULL; the thresholds receive C floats each, hang -1 while it is off.
+ *   fdc_pipeline_squelch              mask[nblocks][C] of the last call, one byte (0 / 1) per block and channel, nblocks being that call's block count
+ *                                     (as fdc_pipeline_levels).  capacity_bytes below nblocks C: FDC_ERR_INVALID_ARGUMENT, nothing written.  After a
+ *                                     host entry it is a memcpy from the pinned twin, copied home with the levels; after a device entry it waits
+ *                                     for the stream that one ran on.
+ *   fdc_pipeline_squelch_device       the device mask ([block of the last call][C] bytes), NULL while off.
+ * WITH THE CHANNEL AUDIO ON (fdc_pipeline_set_audio) the audio pass is GATED: an audio sample of a closed (block, channel) is stored as +0.0f
+ * (FDC_AUDIO_F32) or 0 (FDC_AUDIO_S16), the filter's history runs on over the ungated demodulated stream, so a channel that opens has the bits it
+ * would have had without a squelch, and the pass writes exactly the bytes of the ungated pass; closed tiles are not filtered.  The demodulated ports
+ * themselves are NOT gated: the device entries write d_out as without the squelch, and with the audio off the squelch gives the mask only.
+ * While it is on the entries that refuse under the levels refuse as they do; there is no group setter.  fdc_pipeline_describe: "squelch: pass" after a
+ * call that ran it, and "audio: pass, gated". */
+int fdc_pipeline_set_squelch(fdc_pipeline *p, const float *open_thr, const float *close_thr, int n, int32_t hang);
+int fdc_pipeline_squelch_setting(const fdc_pipeline *p, float *open_thr, float *close_thr, int32_t *hang);
+int fdc_pipeline_squelch(fdc_pipeline *p, uint8_t *dst, size_t capacity_bytes, int nblocks);
+void *fdc_pipeline_squelch_device(fdc_pipeline *p);
+/* The decision alone, on device buffers of the caller (and the entry the tests reach the kernel by with hand-made powers), with the handle's setting
+ * (which must be on), gains and channel count and nothing of its stream state: d_levels [nblocks][C] float32 pairs (power, peak) as
+ * fdc_pipeline_levels_device holds them, d_mask exactly nblocks C bytes, d_state_in C int32 pairs (open, h) or NULL ((0, 0)), d_state_out another
+ * buffer that receives exactly C int32 pairs.  Enqueued on `stream` (NULL: the handle's). */
+int fdc_pipeline_squelch_pass_device(const fdc_pipeline *p, const void *d_levels, void *d_mask, const void *d_state_in, void *d_state_out, int nblocks,
+                                     void *stream);
 
 /* Optional: pin a host range that will be handed to fdc_pipeline_work() again and again (GNU Radio's circular buffers
  * live as long as the flowgraph: register them in start(), unregister in stop()).  A call whose `in` lies in a
