@@ -125,6 +125,10 @@ SYMBOLS = {
     "fdc_pipeline_squelch": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int]),
     "fdc_pipeline_squelch_device": (_vp, [_vp]),
     "fdc_pipeline_squelch_pass_device": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, _vp]),
+    "fdc_pipeline_set_audio_packing": (C.c_int, [_vp, C.c_int]),
+    "fdc_pipeline_audio_packing": (C.c_int, [_vp]),
+    "fdc_pipeline_audio_packed": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int, C.POINTER(C.c_int64)]),
+    "fdc_pipeline_audio_pack_offsets_device": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, _vp]),
     "fdc_pipeline_set_gains": (C.c_int,[_vp, C.POINTER(C.c_float), C.c_int]),
     "fdc_pipeline_gains": (C.c_int, [_vp, C.POINTER(C.c_float), C.c_int]),
     "fdc_pipeline_group_set_gains": (C.c_int, [_vp, C.POINTER(C.c_float), C.c_int]),

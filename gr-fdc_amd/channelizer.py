@@ -416,6 +416,44 @@ def audio_channels(mat, lout, decim):
     return [np.ascontiguousarray(mat[:, at[c]:at[c + 1]]).reshape(-1) for c in range(len(per))]
 
 
+def _pack_npb(mask, npb):
+    """(uint8 mask [nblocks, C], int64 npb [C]) of the packed-audio helpers, checked"""
+    mask = np.asarray(mask)
+    if mask.ndim != 2:
+        raise ValueError("the squelch mask is [nblocks, C]")
+    per = np.asarray(npb, dtype=np.int64).reshape(-1)
+    if per.size != mask.shape[1] or (per < 0).any():
+        raise ValueError("npb is one count of audio samples per block for each of the mask's %d channels" % mask.shape[1])
+    return mask != 0, per
+
+
+def audio_pack_offsets(mask, npb):
+    """Where every (block, channel) cell of a call lies in its packed audio (Pipeline.set_audio_packing): mask is the call's squelch mask [nblocks, C],
+    npb[c] = lout_c / decim the audio samples of one block of channel c.  A cell weighs mask[m, c] * npb[c]; the cells are ordered row-major (block
+    outer, channel inner); off[m, c] is the sum of the weights in front of (m, c), for a closed cell where it would go.  Returns (off int64
+    [nblocks, C], count): count is the sum of all weights, the length of the packed array."""
+    open_, per = _pack_npb(mask, npb)
+    w = (open_ * per[None, :]).reshape(-1)
+    end = np.cumsum(w, dtype=np.int64)
+    return (end - w).reshape(open_.shape), int(end[-1]) if end.size else 0
+
+
+def unpack_audio(packed, mask, npb):
+    """The packed audio of a call (Pipeline.audio_packed) as one 1-D array per channel: the channel's open blocks in order, mask[:, c].sum() * npb[c]
+    samples.  mask: the call's squelch mask [nblocks, C] (Pipeline.squelch), npb[c] = lout_c / decim."""
+    packed = np.asarray(packed).reshape(-1)
+    open_, per = _pack_npb(mask, npb)
+    off, count = audio_pack_offsets(open_, per)
+    if packed.size != count:
+        raise ValueError("the packed audio has %d samples, the mask's open cells hold %d" % (packed.size, count))
+    out = []
+    for c in range(per.size):
+        rows = np.flatnonzero(open_[:, c])
+        idx = off[rows, c][:, None] + np.arange(per[c], dtype=np.int64)[None, :]
+        out.append(packed[idx.reshape(-1)])
+    return out
+
+
 def lowpass_taps(decim, ntaps, cutoff=None):
     """A low-pass for decimating a demodulated port (Pipeline.set_demod) by `decim`, 1 .. 64: the taps of Pipeline.set_audio, which runs the filter on
     the device behind the demodulation (GNU Radio's fir_filter_fff). A
@@ -600,6 +638,8 @@ class Pipeline(_OutputFormat):
         nblocks = int(nblocks)
         if nblocks < 0:
             raise ValueError("audio(): negative block count")
+        if getattr(self, "_packing", False):
+            raise ValueError("audio(): the audio packing is on, there is no matrix: audio_packed() (set_audio_packing)")
         setting = self.audio_setting()
         if setting is None:
             raise ValueError("audio(): the channel audio is off (set_audio)")
@@ -617,6 +657,53 @@ class Pipeline(_OutputFormat):
         process_device's layout, d_out: nblocks * A elements, d_hist_in: C (K - 1) float32 or None, d_hist_out: another such buffer, None only where
         K = 1).  The handle's own history and stream position are not touched."""
         _lib.check(_lib.lib().fdc_pipeline_audio_pass_device(self._h, d_in, d_out, d_hist_in, d_hist_out, int(nblocks), stream))
+
+    def set_audio_packing(self, on):
+        """fdc_pipeline_set_audio_packing: with the channel audio (set_audio) and the squelch (set_squelch) on, only the audio of open (block, channel)
+        cells leaves the device: audio_packed() gives them one behind the other, block-major (tests/audio_pack_model.py), squelch() the mask that says
+        whose they are, and the work methods return one array per channel with its open blocks (unpack_audio).  audio() raises while it is on.  A
+        setting: it applies from the next call and survives reset(); the packing carries no state from call to call.  FdcError where the library
+        refuses (audio or squelch off, a pipelined sinks batch inside); nothing changes then.  At full occupancy it costs a second synchronise per
+        host call and saves nothing: leave it off on a band whose channels are mostly open."""
+        if not isinstance(on, (bool, np.bool_, int, np.integer)):
+            raise ValueError("set_audio_packing(on): on is a bool")
+        _lib.check(_lib.lib().fdc_pipeline_set_audio_packing(self._h, 1 if on else 0))
+        self._packing = bool(on)
+
+    def audio_packing(self):
+        """fdc_pipeline_audio_packing: whether the library has the packing on now."""
+        return _lib.lib().fdc_pipeline_audio_packing(self._h) == 1
+
+    def audio_packed(self, nblocks=None):
+        """fdc_pipeline_audio_packed: the packed audio of the last call, a 1-D array of `count` float32 or int16 (the audio setting's format): the
+        samples of the open (block, channel) cells in block-major order (unpack_audio slices it by squelch()).  nblocks: the last call's block count
+        where it did not go through this object's work methods.  The library is asked for the count first and told the array's size."""
+        if nblocks is None:
+            if self._last_nb is None:
+                raise ValueError("audio_packed(): no work call yet")
+            nblocks = self._last_nb
+        nblocks = int(nblocks)
+        if nblocks < 0:
+            raise ValueError("audio_packed(): negative block count")
+        if not getattr(self, "_packing", False):
+            raise ValueError("audio_packed(): the audio packing is off (set_audio_packing)")
+        setting = self.audio_setting()
+        if setting is None:
+            raise ValueError("audio_packed(): the channel audio is off (set_audio)")
+        if nblocks == 0 or not self.channels:          # (nothing was packed: the library keeps no call of no blocks)
+            return np.empty(0, dtype=_AUDIO_DTYPES[_AUDIO_FORMATS[setting[2]]])
+        count = C.c_int64(0)
+        _lib.check(_lib.lib().fdc_pipeline_audio_packed(self._h, None, 0, nblocks, C.byref(count)))
+        out = np.empty(int(count.value), dtype=_AUDIO_DTYPES[_AUDIO_FORMATS[setting[2]]])
+        if out.size:
+            _lib.check(_lib.lib().fdc_pipeline_audio_packed(self._h, out.ctypes.data, out.nbytes, nblocks, C.byref(count)))
+        return out
+
+    def audio_pack_offsets_device(self, d_mask, d_off, d_total_out, nblocks, d_base_in=None, stream=None):
+        """fdc_pipeline_audio_pack_offsets_device: the packed audio's offsets alone on device buffers of the caller, with the handle's channel table and
+        the audio's decimation (d_mask: nblocks * C bytes, d_off: nblocks * C uint32, d_total_out: one int64, d_base_in: one int64 added to every
+        offset and the total, or None).  Nothing of the handle's state is read or written."""
+        _lib.check(_lib.lib().fdc_pipeline_audio_pack_offsets_device(self._h, d_mask, d_base_in, d_off, d_total_out, int(nblocks), stream))
 
     def set_squelch(self, open_thr, close_thr=None, hang=0):
         """fdc_pipeline_set_squelch: open_thr None switches it off; else thresholds in the levels' unit (the sum over a row of re^2 + im^2 in front of
@@ -689,7 +776,14 @@ class Pipeline(_OutputFormat):
         """what a host call returns: its outs, or (the audio on: _host_outs gave None) one audio array per channel, sliced from the matrix"""
         if outs is not None:
             return outs
-        return audio_channels(self.audio(nb), self.lout, self.audio_setting()[0])
+        decim = self.audio_setting()[0]
+        if getattr(self, "_packing", False):
+            # the packing on: one array per channel with its open blocks of this call; which they are: squelch()
+            per = [int(lo) // decim for lo in self.lout]
+            if nb <= 0:
+                return unpack_audio(np.empty(0, _AUDIO_DTYPES[_AUDIO_FORMATS[self.audio_setting()[2]]]), np.zeros((0, len(per)), np.uint8), per)
+            return unpack_audio(self.audio_packed(nb), self.squelch(nb), per)
+        return audio_channels(self.audio(nb), self.lout, decim)
 
     def _ran(self, nb):
         self._call_nb = int(nb)
@@ -1041,7 +1135,7 @@ class FrequencyDomainChannelizer:
                  debug, device_id=0, max_blocks=64, devices=None, pipelined=False, waterfall=None, iq_input=None, iq_scale=1.0,
                  iq_output=None, iq_output_scale=1.0, fine_tuning=False, *, payload_format=None, payload_scale=1.0, levels=False, gains=None, lag1=False,
                  demod=None, demod_gain=1.0, audio_decim=None, audio_taps=None, audio_format="f32", audio_scale=1.0, squelch_db=None, squelch_close_db=None,
-                 squelch_hang=0):
+                 squelch_hang=0, audio_packed=False):
         # pipelined (not an argument of the reference): the sink blocks run beside the front end of the FOLLOWING work() calls, as the
         # thread-per-block scheduler runs them beside the FFT in the reference (fdc_pipeline_work_sinks on a look-ahead bank,
         # include/fdc_amd.h): same PDUs, handed out one or two work() calls later; flush() at the end of the stream
@@ -1205,6 +1299,14 @@ class FrequencyDomainChannelizer:
         elif squelch_close_db is not None or squelch_hang:
             raise ValueError("squelch_close_db and squelch_hang need squelch_db")
 
+        # audio_packed (not an argument of the reference): with audio_decim and squelch_db, only the audio of open (item, channel) cells leaves the
+        # device (Pipeline.set_audio_packing): work() returns per channel the audio of its open items of the call, self.squelch says which they are
+        if not isinstance(audio_packed, (bool, np.bool_)):
+            raise ValueError("audio_packed is a bool")
+        self.audio_packed = bool(audio_packed)
+        if self.audio_packed and (audio_decim is None or squelch_db is None):
+            raise ValueError("audio_packed needs audio_decim and squelch_db: it packs the channel audio by the squelch's mask")
+
         # gains (not an argument of the reference): one output gain per throughput channel, applied on the device behind fine tuning and in front of the
         # levels and of iq_output's narrowing (Pipeline.set_gains); set_gains() changes them between work() calls (an AGC fed from self.levels)
         self.gains = None if gains is None else _check_gains(len(self.throughput_channels), gains)
@@ -1283,6 +1385,8 @@ class FrequencyDomainChannelizer:
             self.pipeline.set_audio(self.audio_decim, self.audio_taps, self.audio_format, self.audio_scale)
         if self.squelch_db is not None:
             self.set_squelch(self.squelch_db, self.squelch_close_db, self.squelch_hang)
+        if self.audio_packed:
+            self.pipeline.set_audio_packing(True)
         self.N_throughput_channelizers = len(self.channel_params)
         # waterfall (not an argument of the reference, whose example flowgraph wires the spectrum to complex_to_mag_squared and
         # FDC.WaterfallMsgTagging outside the hier block): a gr_fdc_amd.Waterfall fed from the spectrum on the device; work() then

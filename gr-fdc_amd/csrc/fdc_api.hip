@@ -733,10 +733,19 @@ int fdc_pipeline_set_audio(fdc_pipeline *p, int32_t decim, const float *taps, in
         return set_error(FDC_ERR_INVALID_ARGUMENT, "a pipelined sinks batch is still inside the handle: fdc_pipeline_flush_sinks until it returns 0 first");
     if (decim && !p->demod_mode)
         return set_error(FDC_ERR_INVALID_ARGUMENT, "the channel audio filters the demodulated samples: switch the channel demodulation on first (fdc_pipeline_set_demod)");
+    if (!decim && p->pack_on)
+        return set_error(FDC_ERR_INVALID_ARGUMENT, "the audio packing packs the channel audio: switch the packing off first (fdc_pipeline_set_audio_packing(p, 0))");
     for (int c = 0; decim && c < p->C; c++)
         if (p->chans[(size_t)c].lout % decim)
             return set_error(FDC_ERR_INVALID_ARGUMENT, "the audio decimation %d does not divide the %d output samples per block of channel %d", (int)decim,
                              (int)p->chans[(size_t)c].lout, c);
+    if (decim && p->pack_on) {
+        // (the packed offsets are 32-bit words: the bound fdc_pipeline_set_audio_packing checked, for the new decimation)
+        unsigned long long a = 0;
+        for (int c = 0; c < p->C; c++) a += (unsigned long long)(p->chans[(size_t)c].lout / decim);
+        if ((unsigned long long)p->cfg.max_blocks * a >= (1ull << 32))
+            return set_error(FDC_ERR_INVALID_ARGUMENT, "the audio packing is on: max_blocks x the audio samples per block must stay below 2^32");
+    }
     HIPCHK(hipSetDevice(p->cfg.device_id));
     HIPCHK(hipStreamSynchronize(p->stream));          // (no call of the host entries is in flight; a device entry's caller orders its own stream)
     if (!decim) {
@@ -792,6 +801,7 @@ int fdc_pipeline_audio(fdc_pipeline *p, void *dst, size_t capacity_bytes, int nb
     FDC_ENTRY("fdc_pipeline_audio")
     if (!p) return set_error(FDC_ERR_INVALID_ARGUMENT, "null handle");
     if (!p->audio_decim) return set_error(FDC_ERR_INVALID_ARGUMENT, "the channel audio is off (fdc_pipeline_set_audio)");
+    if (p->pack_on) return set_error(FDC_ERR_INVALID_ARGUMENT, "the audio packing is on: there is no matrix, fetch the packed audio (fdc_pipeline_audio_packed)");
     if (p->aud_blocks < 0) return set_error(FDC_ERR_INVALID_ARGUMENT, "no work call has run since the channel audio was switched on or its format or decimation changed");
     if (nblocks != p->aud_blocks) return set_error(FDC_ERR_INVALID_ARGUMENT, "the last work call had %d blocks, not %d", p->aud_blocks, nblocks);
     const size_t n = fdc::pipe::audio_bytes(p) * (size_t)nblocks * (size_t)p->audio_row;
@@ -831,11 +841,96 @@ int fdc_pipeline_audio_pass_device(const fdc_pipeline *p, const void *d_in, void
     if (gate && p->sq_blocks != nblocks)
         return set_error(FDC_ERR_INVALID_ARGUMENT, "the channel squelch is on: the gated audio pass reads the mask of the last call, which had %d blocks, not %d",
                          p->sq_blocks, nblocks);
+    // the packing on: the packed form, over the offsets of that same call (which count the elements it writes at the front of d_out)
+    const unsigned *pack = gate ? pack_rows(p, 0) : nullptr;
+    if (pack && p->aud_blocks != nblocks)
+        return set_error(FDC_ERR_INVALID_ARGUMENT, "the audio packing is on: the packed audio pass reads the offsets of the last call, and no call of %d blocks "
+                         "has run since the packing was switched on or the audio's format or decimation changed", nblocks);
     HIPCHK(hipSetDevice(p->cfg.device_id));
     HIPCHK(fdc::launch_chan_audio(p->audio_format, p->audio_decim, K, p->audio_scale, p->d_ataps, p->d_aoff, (long long)p->audio_row,
                                   static_cast<const float *>(d_in), d_out, p->d_chans, K > 1 ? static_cast<const float *>(d_hist_in) : nullptr,
                                   K > 1 ? static_cast<float *>(d_hist_out) : nullptr, p->C, nblocks, (long long)p->sum_lout,
-                                  stream ? static_cast<hipStream_t>(stream) : p->stream, gate));
+                                  stream ? static_cast<hipStream_t>(stream) : p->stream, gate, pack));
+    return FDC_OK;
+    FDC_ENTRY_END
+}
+
+// the audio packing: a setting that needs the audio and the squelch; everything it needs is allocated here, once
+int fdc_pipeline_set_audio_packing(fdc_pipeline *p, int on)
+{
+    FDC_ENTRY("fdc_pipeline_set_audio_packing")
+    if (!p) return set_error(FDC_ERR_INVALID_ARGUMENT, "null handle");
+    if (p->hier_filled > 0)
+        return set_error(FDC_ERR_INVALID_ARGUMENT, "a pipelined sinks batch is still inside the handle: fdc_pipeline_flush_sinks until it returns 0 first");
+    if (on && (!p->audio_decim || !p->squelch_on))
+        return set_error(FDC_ERR_INVALID_ARGUMENT, "the audio packing packs the channel audio by the squelch's mask: switch both on first (fdc_pipeline_set_audio, fdc_pipeline_set_squelch)");
+    if (on && (unsigned long long)p->cfg.max_blocks * (unsigned long long)p->audio_row >= (1ull << 32))
+        return set_error(FDC_ERR_INVALID_ARGUMENT, "the audio packing keeps 32-bit offsets: max_blocks %d x %lld audio samples per block is not below 2^32",
+                         p->cfg.max_blocks, (long long)p->audio_row);
+    HIPCHK(hipSetDevice(p->cfg.device_id));
+    HIPCHK(hipStreamSynchronize(p->stream));          // (no call of the host entries is in flight; a device entry's caller orders its own stream)
+    if (on) {
+        // everything the feature needs, once: the offsets of the longest call, the running total and its pinned twin
+        const size_t nm = (size_t)p->cfg.max_blocks * (size_t)p->C;
+        if (nm > 0 && !p->d_packoff) HIPCHK(p->d_packoff.alloc(nm));
+        if (!p->d_packtotal) HIPCHK(p->d_packtotal.alloc(1));
+        if (!p->pin_packtotal) HIPCHK(p->pin_packtotal.alloc(1));
+    }
+    // the audio of the last call is in the form of the setting it was made with: a switch leaves none to fetch
+    if (p->pack_on != (on != 0)) { p->aud_blocks = -1; p->pack_count = 0; }
+    p->pack_on = on != 0;
+    return FDC_OK;
+    FDC_ENTRY_END
+}
+
+int fdc_pipeline_audio_packing(const fdc_pipeline *p) { return p ? (p->pack_on ? 1 : 0) : -1; }
+
+// the packed audio of the last call: its count always, its elements where the caller's buffer holds them
+int fdc_pipeline_audio_packed(fdc_pipeline *p, void *dst, size_t capacity_bytes, int nblocks, int64_t *count)
+{
+    FDC_ENTRY("fdc_pipeline_audio_packed")
+    if (!p) return set_error(FDC_ERR_INVALID_ARGUMENT, "null handle");
+    if (!count) return set_error(FDC_ERR_INVALID_ARGUMENT, "null argument");
+    if (!p->pack_on) return set_error(FDC_ERR_INVALID_ARGUMENT, "the audio packing is off (fdc_pipeline_set_audio_packing)");
+    if (p->aud_blocks < 0) return set_error(FDC_ERR_INVALID_ARGUMENT, "no work call has run since the audio packing was switched on or the audio's format or decimation changed");
+    if (nblocks != p->aud_blocks) return set_error(FDC_ERR_INVALID_ARGUMENT, "the last work call had %d blocks, not %d", p->aud_blocks, nblocks);
+    const size_t esz = fdc::pipe::audio_bytes(p);
+    if (!p->aud_host && packing_on(p) && nblocks > 0) {
+        // a device entry's: the total first, then that many elements, both behind everything enqueued so far on the stream it ran on
+        HIPCHK(hipSetDevice(p->cfg.device_id));
+        HIPCHK(hipMemcpyAsync(p->pin_packtotal.get(), p->d_packtotal.get(), sizeof(long long), hipMemcpyDeviceToHost, p->aud_stream));
+        HIPCHK(hipStreamSynchronize(p->aud_stream));
+        p->pack_count = (int64_t)p->pin_packtotal[0];
+        if (p->pack_count > 0) {
+            HIPCHK(hipMemcpyAsync(p->pin_audio.get(), p->d_audio.get(), esz * (size_t)p->pack_count, hipMemcpyDeviceToHost, p->aud_stream));
+            HIPCHK(hipStreamSynchronize(p->aud_stream));
+        }
+        p->aud_host = true;
+    }
+    const int64_t n = packing_on(p) && nblocks > 0 ? p->pack_count : 0;
+    *count = n;
+    if (!dst || n == 0) return FDC_OK;
+    if (capacity_bytes < esz * (size_t)n)
+        return set_error(FDC_ERR_INVALID_ARGUMENT, "the packed audio takes %zu bytes, the buffer holds %zu", esz * (size_t)n, capacity_bytes);
+    std::memcpy(dst, p->pin_audio.get(), esz * (size_t)n);
+    return FDC_OK;
+    FDC_ENTRY_END
+}
+
+// the offsets alone, on the caller's device buffers: the handle gives its channel table and the audio's decimation, nothing of its state
+int fdc_pipeline_audio_pack_offsets_device(const fdc_pipeline *p, const void *d_mask, const void *d_base_in, void *d_off, void *d_total_out, int nblocks,
+                                           void *stream)
+{
+    FDC_ENTRY("fdc_pipeline_audio_pack_offsets_device")
+    if (!p) return set_error(FDC_ERR_INVALID_ARGUMENT, "null handle");
+    if (!p->audio_decim) return set_error(FDC_ERR_INVALID_ARGUMENT, "the channel audio is off (fdc_pipeline_set_audio): its decimation makes the cells' sizes");
+    if (nblocks < 0) return set_error(FDC_ERR_INVALID_ARGUMENT, "negative block count");
+    if (nblocks == 0 || p->C <= 0) return FDC_OK;
+    if (!d_mask || !d_off || !d_total_out) return set_error(FDC_ERR_INVALID_ARGUMENT, "null device buffer");
+    HIPCHK(hipSetDevice(p->cfg.device_id));
+    HIPCHK(fdc::launch_audio_pack_offsets(static_cast<const unsigned char *>(d_mask), p->d_chans, p->audio_decim, static_cast<const long long *>(d_base_in),
+                                          static_cast<unsigned *>(d_off), static_cast<long long *>(d_total_out), p->C, nblocks,
+                                          stream ? static_cast<hipStream_t>(stream) : p->stream));
     return FDC_OK;
     FDC_ENTRY_END
 }
@@ -859,6 +954,8 @@ int fdc_pipeline_set_squelch(fdc_pipeline *p, const float *open_thr, const float
     }
     if (p->hier_filled > 0)
         return set_error(FDC_ERR_INVALID_ARGUMENT, "a pipelined sinks batch is still inside the handle: fdc_pipeline_flush_sinks until it returns 0 first");
+    if (!open_thr && p->pack_on)
+        return set_error(FDC_ERR_INVALID_ARGUMENT, "the audio packing packs by the squelch's mask: switch the packing off first (fdc_pipeline_set_audio_packing(p, 0))");
     if (open_thr && !p->levels_on)
         return set_error(FDC_ERR_INVALID_ARGUMENT, "the channel squelch decides on the levels: switch the channel levels on first (fdc_pipeline_set_levels(p, 1))");
     HIPCHK(hipSetDevice(p->cfg.device_id));

@@ -179,6 +179,7 @@ struct PostPass {
     bool audio_cont = false;    //   ... the call continues the audio stream: the handle's history stands in front of its first sample
     unsigned char *squelch = nullptr;   // the call-wide k_chan_squelch over the call's levels, in front of the audio (which it gates): the squelch on
     bool squelch_cont = false;  //   ... the call continues the squelch's stream: the handle's state stands in front of its first block
+    unsigned *pack_off = nullptr;   // the offsets of the call's cells in the packed audio, behind the squelch and in front of the audio (which then packs): packing on
 };
 
 static PostPass post_pass(const fdc_pipeline *p, const DeviceCall &call, bool ofused)
@@ -198,6 +199,7 @@ static PostPass post_pass(const fdc_pipeline *p, const DeviceCall &call, bool of
     pp.narrow_tail = narrow && !pp.gain_narrows;
     pp.audio = pp.demod ? call.audio : nullptr;
     pp.squelch = pp.levels ? call.squelch : nullptr;
+    pp.pack_off = pp.audio && pp.squelch ? call.pack_off : nullptr;
     return pp;
 }
 
@@ -229,6 +231,10 @@ static int run_post_tail(fdc_pipeline *p, const DeviceCall &call, const PostPass
         p->sqstate_cur ^= 1; p->squelch_next = first_block + nblocks;
         p->squelch_route = "pass";
     }
+    if (pp.pack_off)
+        // ... and of the mask the offsets of the call's cells: from the running total on where the call appends to a host call's packed buffer
+        HIPCHK(fdc::launch_audio_pack_offsets(pp.squelch, p->d_chans, p->audio_decim, call.pack_append ? p->d_packtotal.get() : nullptr, pp.pack_off,
+                                              p->d_packtotal, p->C, nblocks, call.stream));
     if (pp.demod) {
         // FM reads one carry buffer and writes the other; behind the enqueue the written one is the handle's, for the call that goes on at the next block
         const bool fm = pp.demod == FDC_DEMOD_FM;
@@ -244,9 +250,10 @@ static int run_post_tail(fdc_pipeline *p, const DeviceCall &call, const PostPass
         const int K = (int)p->audio_taps.size();
         HIPCHK(fdc::launch_chan_audio(p->audio_format, p->audio_decim, K, p->audio_scale, p->d_ataps, p->d_aoff, (long long)p->audio_row,
                                       static_cast<const float *>(d_out), pp.audio, p->d_chans, pp.audio_cont && K > 1 ? p->d_ahist[p->ahist_cur].get() : nullptr,
-                                      K > 1 ? p->d_ahist[p->ahist_cur ^ 1].get() : nullptr, p->C, nblocks, (long long)p->sum_lout, call.stream, pp.squelch));
+                                      K > 1 ? p->d_ahist[p->ahist_cur ^ 1].get() : nullptr, p->C, nblocks, (long long)p->sum_lout, call.stream, pp.squelch,
+                                      pp.pack_off));
         p->ahist_cur ^= 1; p->audio_next = first_block + nblocks;
-        p->audio_route = pp.squelch ? "pass, gated" : "pass";
+        p->audio_route = pp.pack_off ? "pass, gated, packed" : pp.squelch ? "pass, gated" : "pass";
     }
     if (pp.narrow_tail) HIPCHK(fdc::launch_complex_to_iq(call.ofmt, call.oscale, call.fout, d_out, (size_t)nblocks * p->sum_lout, call.stream));
     if (pp.fine_fused || pp.rotate) p->fine_route = pp.fine_fused ? "fused" : "rotated";
@@ -473,6 +480,7 @@ static int process_device_oq(fdc_pipeline *p, DeviceCall &call, const void *d_ri
         call.levels = p->d_levels;
         call.squelch = squelch_rows(p, 0);      // (the mask goes to the handle's buffer, [max_blocks][C]: the check above covers it)
     }
+    if (call.audio && call.squelch && packing_on(p)) { call.audio = p->d_audio.get(); call.pack_off = pack_rows(p, 0); call.pack_append = false; }
     const bool lag = p->lag1_on && nblocks > 0;
     if (lag) {
         if (nblocks > p->cfg.max_blocks) return set_error(FDC_ERR_INVALID_ARGUMENT, "channel lag-1 correlation: nblocks %d above max_blocks %d", nblocks, p->cfg.max_blocks);

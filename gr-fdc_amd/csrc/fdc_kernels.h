@@ -275,7 +275,16 @@ hipError_t launch_chan_demod(int mode, float gain, const float2 *in, float *out,
 enum { kAudioF32 = 0, kAudioS16 = 1 };
 hipError_t launch_chan_audio(int format, int decim, int ntaps, float scale, const float *taps, const long long *aoff, long long row, const float *in,
                              void *out, const ChanDev *chans, const float *hist_in, float *hist_out, int nchan, int nb_call, long long sum_lout,
-                             hipStream_t s, const unsigned char *gate = nullptr);
+                             hipStream_t s, const unsigned char *gate = nullptr, const unsigned *pack_off = nullptr);
+// pack_off (null: none; it needs gate): row 0 of the call's offsets ([nb_call][nchan] words, launch_audio_pack_offsets over the same mask): the packed
+// forms, which store the outputs of an open (block, channel) at out[pack_off[block][channel] + i] and those of a closed one nowhere; out is then element
+// 0 of the packed buffer, and exactly the elements the offsets count are written
+
+// Packed audio (fdc_pipeline_set_audio_packing): the offsets of the call's cells in the packed buffer.  mask: row 0 of the call's mask ([nb_call][nchan]
+// bytes); off ([nb_call][nchan] words) receives *base_in (null: 0) + the audio samples (lout_c / decim each) of all open cells in front of (block,
+// channel), block-major; total (one word, which may be base_in's) receives *base_in + those of all open cells.  Three launches on s
+hipError_t launch_audio_pack_offsets(const unsigned char *mask, const ChanDev *chans, int decim, const long long *base_in, unsigned *off, long long *total,
+                                     int nchan, int nb_call, hipStream_t s);
 
 // Channel squelch (fdc_pipeline_set_squelch): the decision over the call's rows of the levels ([nb_call][nchan] (power, peak), launch_chan_levels and
 // its kin), one byte per (block, channel) to mask ([nb_call][nchan]): open at a block whose power reaches g2 thr_open[c], held while it reaches

@@ -237,6 +237,15 @@ struct fdc_pipeline {
     bool sq_host = false;
     hipStream_t sq_stream = nullptr;
     std::string squelch_route;   // the last call with the setting on ran the squelch pass (fdc_pipeline_describe)
+    // packed audio (fdc_pipeline_set_audio_packing): a setting that needs the audio and the squelch.  d_packoff: the offsets of the last call's cells,
+    // [max_blocks][C] words; d_packtotal: the running total of the call on the device (zeroed in front of a host call, read as the base and written
+    // back by each of its sub-batches), pin_packtotal its pinned twin; pack_count: the elements of the last call's packed audio once they are known on
+    // the host (aud_host).  The packed elements live in d_audio / pin_audio.  All of it is allocated by fdc_pipeline_set_audio_packing.
+    bool pack_on = false;
+    fdc::DevBuf<unsigned> d_packoff;
+    fdc::DevBuf<long long> d_packtotal;
+    fdc::PinBuf<long long> pin_packtotal;
+    int64_t pack_count = 0;
     fdc::DevBuf<float2> d_out;   // work(): max_blocks*sum_lout (out_staging)
     int64_t blockcount = 0;      // work(): blocks consumed so far
     // work(): transfers and kernels of consecutive sub-batches overlap (H2D on s_in, kernels on stream, D2H on s_out)
@@ -304,6 +313,11 @@ struct DeviceCall {
     void *audio = nullptr;
     // channel squelch (fdc_pipeline_set_squelch): where the mask byte of the call's block 0, channel 0 goes, [block][C]; null = none.  It goes with levels
     unsigned char *squelch = nullptr;
+    // packed audio (fdc_pipeline_set_audio_packing): where the offsets of the call's block 0 go, [block][C] words; null = none.  It goes with audio and
+    // squelch; `audio` is then element 0 of the packed buffer whichever block the call starts at, the offsets start at the handle's running total where
+    // pack_append says so (a sub-batch behind the first of a host call) and at 0 otherwise, and the total goes to the handle's device word
+    unsigned *pack_off = nullptr;
+    bool pack_append = false;
     int ncu = 0;                        // compute units the call's persistent kernels may use
     // results: no launch group had to be widened (each read the integer input in its own loads); the call's kernels narrowed in their own stores
     bool all_fused = true, ofused = false;
@@ -332,6 +346,10 @@ inline unsigned char *squelch_rows(const fdc_pipeline *p, size_t b0)
 {
     return p->squelch_on && p->levels_on && p->C > 0 ? p->d_mask.get() + b0 * (size_t)p->C : nullptr;
 }
+
+// packed audio: whether the handle's next call packs its audio, and where the offsets rows from block b0 of a host call on go (null: it does not)
+inline bool packing_on(const fdc_pipeline *p) { return p->pack_on && audio_on(p) && squelch_rows(p, 0); }
+inline unsigned *pack_rows(const fdc_pipeline *p, size_t b0) { return packing_on(p) ? p->d_packoff.get() + b0 * (size_t)p->C : nullptr; }
 
 inline bool ispow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
 

@@ -2,8 +2,8 @@
 // results of a launch group: the rotation of fine tuning (k_fine_rotate), the channel gains (k_chan_gain), the channel levels (k_chan_levels), the
 // channel lag-1 correlation (k_chan_lag1) and the narrowing to complex integers (k_complex_to_iq) — and, over a whole call's float results in the
 // place of the narrowing, the channel demodulation (k_chan_demod) and behind it the channel audio (k_chan_audio, at the end of this file), which the
-// channel squelch (k_chan_squelch, over the call's levels) gates.  Which of them a call runs, and in which order, is decided once per call: PostPass,
-// fdc_enqueue.hip.
+// channel squelch (k_chan_squelch, over the call's levels) gates and, with the audio packing on, the offsets (k_pack_rows, k_pack_scan, over the
+// call's mask) place.  Which of them a call runs, and in which order, is decided once per call: PostPass, fdc_enqueue.hip.
 //
 // One shape for the four per-channel kernels: grid y = channel, a row — the lout samples of one (block, channel) — on a power-of-two set of lanes of one
 // wave, 16 bytes per lane and access where the row allows it (lout even, the channel's run 16-byte aligned), 8 bytes otherwise, a grid-stride loop over
@@ -757,6 +757,113 @@ hipError_t launch_chan_squelch(const float2 *levels, const float *gain, const fl
     return hipGetLastError();
 }
 
+// Packed audio (fdc_pipeline_set_audio_packing): where every (block, channel) of the call goes in the packed buffer.  The weight of a cell is
+// mask[m][c] * npb_c (npb_c = lout_c / D, the cell's audio samples), the cells are ordered block-major, off[m][c] is base + the sum of the weights of
+// all cells in front of (m, c) (closed cells too: where they would go) and total is base + the sum over all.  Integers only, so the order of
+// the sums does not show.  Three launches, none of which waits for another workgroup:
+//   k_pack_rows<L, false>  the sum of every row, parked in the row's own first word off[m][0] (no scratch: the footprint is the table's);
+//   k_pack_scan            ONE workgroup turns the nb row sums into the rows' bases, in place: a trip covers 256 * kPackPer = 1024 consecutive rows,
+//                          a lane kPackPer = 4 consecutive ones, the lanes of a wave are joined by __shfl_up, the four waves through LDS, the trips
+//                          by a carry every lane holds (k_chan_squelch's scheme).  The trip count depends on nb alone, the one barrier of a trip
+//                          stands outside every per-lane condition, and the LDS slots alternate with the trip, so no second barrier guards them.
+//                          It reads base_in (null: 0) in front of its first barrier and writes total behind its last, so both may be one word;
+//   k_pack_rows<L, true>   every row again: its base (off[m][0]) plus the exclusive scan along the row, into off[m][c].
+// The lane mapping of k_pack_rows goes by the channel count: up to kPackSerial channels a lane takes a row and walks it (L = 1; four channels are
+// four bytes of mask), above that a wave takes a row, 64 channels a trip, joined by __shfl_up with a carry (L = 64).  No barrier in either.
+constexpr unsigned kPackPer = 4;
+constexpr int kPackSerial = 8;
+
+template <class T>
+__device__ __forceinline__ T wave_sum_scan(T v)                   // inclusive, run by the whole wave
+{
+    const unsigned lane = threadIdx.x & 63;
+#pragma unroll
+    for (unsigned d = 1; d < 64; d <<= 1) {
+        const T u = __shfl_up(v, d, 64);
+        if (lane >= d) v += u;
+    }
+    return v;
+}
+
+template <int L, bool WRITE>
+__global__ __launch_bounds__(256) void k_pack_rows(const unsigned char *__restrict__ mask, const ChanDev *__restrict__ chans, unsigned *off, int D,
+                                                   int nchan, int nb)
+{
+    static_assert(L == 1 || L == 64, "a lane or a wave per row");
+    const unsigned rows = 256 / L;                                  // rows a workgroup takes per trip
+    for (unsigned m = blockIdx.x * rows + threadIdx.x / L; m < (unsigned)nb; m += gridDim.x * rows) {      // (L = 64: the same for the whole wave)
+        const unsigned char *mr = mask + (size_t)m * (size_t)nchan;
+        unsigned *orow = off + (size_t)m * (size_t)nchan;
+        unsigned run = WRITE ? orow[0] : 0u;                        // the row's base (WRITE stores the same value back as cell 0's offset)
+        if constexpr (L == 1) {
+            for (int c = 0; c < nchan; c++) {
+                const unsigned w = mr[c] ? (unsigned)chans[c].lout / (unsigned)D : 0u;
+                if (WRITE) orow[c] = run;
+                run += w;
+            }
+        } else {
+            const unsigned lane = threadIdx.x & 63;
+            for (int c0 = 0; c0 < nchan; c0 += 64) {                // (the trip count is the wave's)
+                const int c = c0 + (int)lane;
+                const unsigned w = c < nchan && mr[c] ? (unsigned)chans[c].lout / (unsigned)D : 0u;
+                const unsigned inc = wave_sum_scan(w);
+                if (WRITE && c < nchan) orow[c] = run + inc - w;
+                run += __shfl(inc, 63, 64);
+            }
+        }
+        if (!WRITE && (L == 1 || (threadIdx.x & 63) == 0)) orow[0] = run;
+    }
+}
+
+// off: row m's sum at off[m * pitch] in, row m's base out; base_in (null: 0) and total may be the same word
+__global__ __launch_bounds__(256) void k_pack_scan(unsigned *off, int pitch, int nb, const long long *base_in, long long *total)
+{
+    __shared__ unsigned long long tot[2][4];
+    const unsigned tid = threadIdx.x, wv = tid >> 6;
+    unsigned long long carry = base_in ? (unsigned long long)*base_in : 0ull;
+    for (unsigned m0 = 0, par = 0; m0 < (unsigned)nb; m0 += 256 * kPackPer, par ^= 1) {
+        const unsigned mb = m0 + tid * kPackPer;
+        unsigned w[kPackPer];
+        unsigned long long s = 0;
+#pragma unroll
+        for (unsigned v = 0; v < kPackPer; v++) {
+            w[v] = mb + v < (unsigned)nb ? off[(size_t)(mb + v) * (size_t)pitch] : 0u;
+            s += w[v];
+        }
+        const unsigned long long inc = wave_sum_scan(s);
+        if ((tid & 63) == 63) tot[par][wv] = inc;
+        __syncthreads();
+        unsigned long long run = carry + inc - s;
+#pragma unroll
+        for (unsigned u = 0; u < 4; u++) {
+            const unsigned long long t = tot[par][u];
+            if (u < wv) run += t;
+            carry += t;
+        }
+#pragma unroll
+        for (unsigned v = 0; v < kPackPer; v++) {
+            if (mb + v < (unsigned)nb) off[(size_t)(mb + v) * (size_t)pitch] = (unsigned)run;
+            run += w[v];
+        }
+    }
+    if (tid == 0) *total = (long long)carry;
+}
+
+hipError_t launch_audio_pack_offsets(const unsigned char *mask, const ChanDev *chans, int decim, const long long *base_in, unsigned *off, long long *total,
+                                     int nchan, int nb_call, hipStream_t s)
+{
+    if (nchan <= 0 || nb_call <= 0) return hipSuccess;
+    if (!mask || !chans || !off || !total || decim < 1) return hipErrorInvalidValue;
+    const bool serial = nchan <= kPackSerial;
+    const unsigned rows = serial ? 256u : 4u, grid = std::min<unsigned>(((unsigned)nb_call + rows - 1) / rows, 1u << 16);
+    if (serial) hipLaunchKernelGGL((k_pack_rows<1, false>), dim3(grid), dim3(256), 0, s, mask, chans, off, decim, nchan, nb_call);
+    else hipLaunchKernelGGL((k_pack_rows<64, false>), dim3(grid), dim3(256), 0, s, mask, chans, off, decim, nchan, nb_call);
+    hipLaunchKernelGGL(k_pack_scan, dim3(1), dim3(256), 0, s, off, nchan, nb_call, base_in, total);
+    if (serial) hipLaunchKernelGGL((k_pack_rows<1, true>), dim3(grid), dim3(256), 0, s, mask, chans, off, decim, nchan, nb_call);
+    else hipLaunchKernelGGL((k_pack_rows<64, true>), dim3(grid), dim3(256), 0, s, mask, chans, off, decim, nchan, nb_call);
+    return hipGetLastError();
+}
+
 // Channel audio (fdc_pipeline_set_audio): the decimating FIR behind the demodulation, a[n] = sum over k = 0 .. K - 1 of h[k] d[n D - k] over one
 // channel's run d of the call (T = nblocks * lout real samples, contiguous across the blocks; in front of d[0] stand the K - 1 values of the history,
 // or zeros).  THE ORDER IS THE DEFINITION: k ascending from acc = +0, every product and every sum rounded on its own (audio_mac).
@@ -820,15 +927,27 @@ __device__ __forceinline__ bool gate_any_open(const unsigned char *col, unsigned
     return __builtin_amdgcn_ballot_w64(open) != 0;
 }
 
+// THE PACKED FORMS (GATE with four gate arguments: mask, nchan, offsets, their pitch; fdc_pipeline_set_audio_packing): the outputs of an open
+// (block, channel) go to out[off[block][channel] + i], i counting within the block, and a closed output is not stored at all: nothing is stored as
+// zero anywhere.  off is what launch_audio_pack_offsets made of the same mask, so the open cells lie one behind the other in block-major order and
+// the pass writes exactly `total` elements.  The lanes of a wave hold consecutive outputs, which within a row are consecutive elements of the packed
+// buffer as they are of the matrix.  Skipping and the history are the gated forms'.
+__device__ __forceinline__ const unsigned char *gate_mask(const unsigned char *m, int, const unsigned *, int) { return m; }
+__device__ __forceinline__ unsigned gate_pitch(const unsigned char *, int nchan, const unsigned *, int) { return (unsigned)nchan; }
+__device__ __forceinline__ const unsigned *pack_table(const unsigned char *, int, const unsigned *off, int) { return off; }
+__device__ __forceinline__ unsigned pack_pitch(const unsigned char *, int, const unsigned *, int pitch) { return (unsigned)pitch; }
+
 // in: the call's demodulated samples ([channel][nb_call * lout] float at nb_call * out_off); out: row 0 of the call's audio ([nb_call][A] TO);
-// hist_in (null: zeros) and hist_out (null where K = 1): [nchan][K - 1] float; gate (GATE only): row 0 of the call's mask ([nb_call][nchan] bytes), nchan
+// hist_in (null: zeros) and hist_out (null where K = 1): [nchan][K - 1] float; gate (GATE only): row 0 of the call's mask ([nb_call][nchan] bytes), nchan;
+// and, the packed forms only, row 0 of the call's offsets ([nb_call][pitch] words) and pitch: out is then element 0 of the packed buffer
 template <class TO, bool GATE, class... Gate>
 __global__ __launch_bounds__(256) void k_chan_audio(const float *__restrict__ in, TO *__restrict__ out, const ChanDev *__restrict__ chans,
                                                     const long long *__restrict__ aoff, const float *__restrict__ taps,
                                                     const float *__restrict__ hist_in, float *__restrict__ hist_out, int D, int K, float scale,
                                                     long long A, int c0, long long nb_call, Gate... gate)
 {
-    static_assert(GATE == (sizeof...(Gate) == 2), "the gated forms take (mask, nchan)");
+    static_assert(GATE == (sizeof...(Gate) == 2 || sizeof...(Gate) == 4), "the gated forms take (mask, nchan), the packed ones (mask, nchan, offsets, pitch)");
+    constexpr bool PACK = sizeof...(Gate) == 4;
     __shared__ float tile[kAudioLdsWords];
     const int c = c0 + (int)blockIdx.y;
     const unsigned char *gcol = nullptr;                            // GATE: the channel's column of the mask and the pitch of its rows
@@ -840,7 +959,8 @@ __global__ __launch_bounds__(256) void k_chan_audio(const float *__restrict__ in
     const long long T = nb_call * (long long)lout;
     const float *d = in + nb_call * chans[c].out_off;
     const float *hin = hist_in ? hist_in + (size_t)c * (size_t)(K - 1) : nullptr;
-    TO *o = out + aoff[c];
+    TO *o = out;
+    if constexpr (!PACK) o += aoff[c];                              // (PACK: out is element 0 of the packed buffer, the offsets place the cell)
     const AudioTile g = audio_tile((unsigned)D, (unsigned)K);
     const unsigned magic = (unsigned)(0x100000000ull / (unsigned)D) + 1u;      // i / D = umulhi(i, magic) for i < 2^16, D >= 2
     // where tile sample i lies in LDS: plane i mod D, index i / D
@@ -848,6 +968,11 @@ __global__ __launch_bounds__(256) void k_chan_audio(const float *__restrict__ in
         const unsigned q = D == 1 ? i : __umulhi(i, magic);
         return (i - q * (unsigned)D) * g.pitch + q;
     };
+    // (PACK: the new history first, so that its buffer is not held in scalar registers, of which this form needs three more, across the tiles; it
+    // depends on the input alone)
+    if constexpr (PACK)
+        if (blockIdx.x == 0 && tid < (unsigned)(K - 1))
+            hist_out[(size_t)c * (size_t)(K - 1) + tid] = audio_sample(d, hin, K, T - (K - 1) + (long long)tid);
     for (unsigned o0 = blockIdx.x * g.outs; o0 < nout; o0 += gridDim.x * g.outs) {
         const unsigned nt = nout - o0 < g.outs ? nout - o0 : g.outs;            // outputs of this tile
         const long long t0 = (long long)o0 * D - (K - 1);
@@ -911,30 +1036,47 @@ __global__ __launch_bounds__(256) void k_chan_audio(const float *__restrict__ in
                 const unsigned jj = j0 + u * 64 + (tid & 63);
                 if (jj < nt) {
                     const unsigned n = o0 + jj, m = n / npb;
-                    const long long at_out = (long long)m * A + (long long)(n - m * npb);
-                    if (GATE && !gcol[(size_t)m * gpitch]) o[at_out] = TO(0);
-                    else audio_store(o, at_out, acc[u], scale);
+                    if constexpr (PACK) {
+                        // (the table and its pitch are read from the arguments here, not held in scalar registers across the tap loop)
+                        if (gcol[(size_t)m * gpitch])
+                            audio_store(o, (long long)pack_table(gate...)[m * pack_pitch(gate...) + (unsigned)c] + (long long)(n - m * npb), acc[u], scale);
+                    } else {
+                        const long long at_out = (long long)m * A + (long long)(n - m * npb);
+                        if (GATE && !gcol[(size_t)m * gpitch]) o[at_out] = TO(0);
+                        else audio_store(o, at_out, acc[u], scale);
+                    }
                 }
             }
         }
         __syncthreads();                                                        // the tile is read: the next trip may overwrite it
     }
-    if (blockIdx.x == 0 && tid < (unsigned)(K - 1))
-        hist_out[(size_t)c * (size_t)(K - 1) + tid] = audio_sample(d, hin, K, T - (K - 1) + (long long)tid);
+    if constexpr (!PACK)
+        if (blockIdx.x == 0 && tid < (unsigned)(K - 1))
+            hist_out[(size_t)c * (size_t)(K - 1) + tid] = audio_sample(d, hin, K, T - (K - 1) + (long long)tid);
 }
 
 hipError_t launch_chan_audio(int format, int decim, int ntaps, float scale, const float *taps, const long long *aoff, long long row, const float *in,
                              void *out, const ChanDev *chans, const float *hist_in, float *hist_out, int nchan, int nb_call, long long sum_lout,
-                             hipStream_t s, const unsigned char *gate)
+                             hipStream_t s, const unsigned char *gate, const unsigned *pack_off)
 {
     if (nchan <= 0 || nb_call <= 0) return hipSuccess;
     if (format != kAudioF32 && format != kAudioS16) return hipErrorInvalidValue;
+    if (pack_off && !gate) return hipErrorInvalidValue;
     if (decim < 1 || decim > 64 || ntaps < 1 || ntaps > 256 || !taps || !aoff || !in || !out) return hipErrorInvalidValue;
     if (ntaps > 1 && (!hist_out || hist_in == hist_out)) return hipErrorInvalidValue;
     // the grid: a workgroup per tile of a run of mean length (channel_grids takes it in units of four)
     const long long tiles = ((long long)nb_call * sum_lout / nchan / decim) / audio_tile((unsigned)decim, (unsigned)ntaps).outs + 1;
     return channel_grids(nchan, (int)std::min<long long>(4 * tiles, 1 << 20), [&](dim3 grid, int c0) {
-        if (gate) {
+        if (pack_off) {
+            if (format == kAudioS16)
+                hipLaunchKernelGGL((k_chan_audio<short, true, const unsigned char *, int, const unsigned *, int>), grid, dim3(256), 0, s, in,
+                                   static_cast<short *>(out), chans, aoff, taps, hist_in, hist_out, decim, ntaps, scale, row, c0, (long long)nb_call, gate,
+                                   nchan, pack_off, nchan);
+            else
+                hipLaunchKernelGGL((k_chan_audio<float, true, const unsigned char *, int, const unsigned *, int>), grid, dim3(256), 0, s, in,
+                                   static_cast<float *>(out), chans, aoff, taps, hist_in, hist_out, decim, ntaps, scale, row, c0, (long long)nb_call, gate,
+                                   nchan, pack_off, nchan);
+        } else if (gate) {
             if (format == kAudioS16)
                 hipLaunchKernelGGL((k_chan_audio<short, true, const unsigned char *, int>), grid, dim3(256), 0, s, in, static_cast<short *>(out), chans, aoff,
                                    taps, hist_in, hist_out, decim, ntaps, scale, row, c0, (long long)nb_call, gate, nchan);

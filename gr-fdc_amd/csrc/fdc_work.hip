@@ -35,9 +35,24 @@ static int levels_home(fdc_pipeline *p, int nblocks, hipStream_t s)
     // ... and of its squelch mask (fdc_pipeline_squelch)
     if (squelch_rows(p, 0))
         HIPCHK(hipMemcpyAsync(p->pin_mask.get(), p->d_mask.get(), (size_t)nblocks * p->C, hipMemcpyDeviceToHost, s));
-    // ... and of its audio rows, which are all the call hands to the host while the channel audio is on (fdc_pipeline_audio)
-    if (audio_on(p))
+    // ... and of its audio rows, which are all the call hands to the host while the channel audio is on (fdc_pipeline_audio); packed audio: only the
+    // 8 bytes of its total, the elements follow once the host knows how many they are (packed_home)
+    if (packing_on(p))
+        HIPCHK(hipMemcpyAsync(p->pin_packtotal.get(), p->d_packtotal.get(), sizeof(long long), hipMemcpyDeviceToHost, s));
+    else if (audio_on(p))
         HIPCHK(hipMemcpyAsync(p->pin_audio.get(), p->d_audio.get(), audio_bytes(p) * (size_t)nblocks * (size_t)p->audio_row, hipMemcpyDeviceToHost, s));
+    return FDC_OK;
+}
+
+// Packed audio of a host entry's call, behind the call's synchronise (the total is home): exactly `count` elements to the pinned twin and one more
+// synchronise, neither where no cell was open
+static int packed_home(fdc_pipeline *p, hipStream_t s)
+{
+    if (!packing_on(p)) return FDC_OK;
+    p->pack_count = (int64_t)p->pin_packtotal[0];
+    if (p->pack_count <= 0) return FDC_OK;
+    HIPCHK(hipMemcpyAsync(p->pin_audio.get(), p->d_audio.get(), audio_bytes(p) * (size_t)p->pack_count, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
     return FDC_OK;
 }
 
@@ -189,6 +204,9 @@ static int pipeline_work_impl(fdc_pipeline *p, DeviceCall call, const void *in, 
 
     // channel audio on: the call hands the host its audio rows and nothing else: outs is not looked at, no port is copied or scattered
     const bool audio = audio_on(p), ports = p->C > 0 && !audio;
+    // packed audio: the sub-batches append to one packed buffer, each from the running total on, which starts the call at 0
+    const bool pack = packing_on(p);
+    if (pack) HIPCHK(hipMemsetAsync(p->d_packtotal.get(), 0, sizeof(long long), s));
     const bool in_reg = host_registered(in, esz * nin);
     const bool out_reg = ports && fill_scatter_table(p, outs, nblocks, osz);
     call.wide = fmt ? p->d_ring : nullptr;
@@ -203,6 +221,7 @@ static int pipeline_work_impl(fdc_pipeline *p, DeviceCall call, const void *in, 
         call.lag1 = p->lag1_on && p->C > 0 ? p->d_lag1 + b0 * (size_t)p->C : nullptr;
         call.audio = audio_rows(p, b0);
         call.squelch = squelch_rows(p, b0);
+        if (pack) { call.audio = p->d_audio.get(); call.pack_off = pack_rows(p, b0); call.pack_append = true; }
         const int rc2 = process_device_impl(p, call, ringb + b0 * p->H * esz, first, nb,
                                             ofmt ? static_cast<void *>(p->d_oq + osz * b0 * (size_t)p->sum_lout) : static_cast<void *>(dok));
         oq_all = oq_all && call.ofused;
@@ -250,6 +269,7 @@ static int pipeline_work_impl(fdc_pipeline *p, DeviceCall call, const void *in, 
         HIPCHK(hipMemcpyAsync(ringb, ringb + esz * nin, esz * (size_t)p->ovl, hipMemcpyDeviceToDevice, s));
         RCCHK(levels_home(p, nblocks, s));
         HIPCHK(hipStreamSynchronize(s));
+        RCCHK(packed_home(p, s));
         if (p->levels_on) levels_written(p, nblocks, s, true);
     if (p->lag1_on) lag1_written(p, nblocks, s, true);
         if (audio) audio_written(p, nblocks, s, true);
@@ -318,6 +338,7 @@ static int pipeline_work_impl(fdc_pipeline *p, DeviceCall call, const void *in, 
     RCCHK(levels_home(p, nblocks, s));
     HIPCHK(hipStreamSynchronize(s));
     HIPCHK(hipStreamSynchronize(p->s_out));
+    RCCHK(packed_home(p, s));
     if (p->levels_on) levels_written(p, nblocks, s, true);
     if (p->lag1_on) lag1_written(p, nblocks, s, true);
     if (audio) audio_written(p, nblocks, s, true);
@@ -424,12 +445,14 @@ static int pipeline_work_real_impl(fdc_pipeline *p, const void *in, int nblocks,
     call.lag1 = p->lag1_on && p->C > 0 ? p->d_lag1.get() : nullptr;
     call.audio = audio_rows(p, 0);
     call.squelch = squelch_rows(p, 0);
+    if (packing_on(p)) { call.audio = p->d_audio.get(); call.pack_off = pack_rows(p, 0); call.pack_append = false; }
     RCCHK(process_device_impl(p, call, p->d_ring, p->blockcount, nblocks, res));
     if (!call.audio) RCCHK(copy_outputs(p, outs, nblocks, osz, res, s));     // (audio on: the rows go home with the levels, outs is not looked at)
     if (spectrum) HIPCHK(hipMemcpyAsync(spectrum, d_specfull, sizeof(float2) * (size_t)nblocks * p->N, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(p->d_ring, p->d_ring + nin, sizeof(float2) * (size_t)p->ovl, hipMemcpyDeviceToDevice, s));
     RCCHK(levels_home(p, nblocks, s));
     HIPCHK(hipStreamSynchronize(s));
+    RCCHK(packed_home(p, s));
     if (p->levels_on) levels_written(p, nblocks, s, true);
     if (p->lag1_on) lag1_written(p, nblocks, s, true);
     if (call.audio) audio_written(p, nblocks, s, true);

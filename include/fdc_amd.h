@@ -453,6 +453,50 @@ void *fdc_pipeline_squelch_device(fdc_pipeline *p);
 int fdc_pipeline_squelch_pass_device(const fdc_pipeline *p, const void *d_levels, void *d_mask, const void *d_state_in, void *d_state_out, int nblocks,
                                      void *stream);
 
+/* PACKED AUDIO: with the channel audio and the channel squelch on, only the audio of open (block, channel) cells leaves the device, one cell behind
+ * the other, instead of the [nblocks][A] matrix with its zeros.  With D the audio's decimation and npb_c = lout_c / D:
+ *     a CELL is (m, c), block m of the call and channel c, of weight w(m, c) = mask[m][c] npb_c;  cells are ordered ROW-MAJOR, m outer, c inner;
+ *     off(m, c) = the sum of w over all cells in front of (m, c) (for a closed cell: where it would go);  count = the sum of w over all cells;
+ *     packed[off(m, c) + i] = audio[m][aoff_c + i]  for every OPEN cell and 0 <= i < npb_c,
+ * audio being the matrix the audio pass gives without packing (gated or not: the same bits on open cells), in the audio setting's own format.  The
+ * filter's history runs on over the ungated stream as ever.  The offsets start at 0 in EVERY call: the packing has no stream state.  Two consequences:
+ * with every cell open the packed bytes are the matrix's bytes; and the packed buffers of the calls of a stream, concatenated, are the packed buffer
+ * of the stream in one call, however it is cut (which is why the order is block-major).  tests/audio_pack_model.py states this in numpy, and the
+ * packed bytes, the count and the mask are that model's byte for byte.  NOT BUILT: a channel-major order; packing of the demodulated ports.
+ *   fdc_pipeline_set_audio_packing  on != 0 switches it on.  FDC_ERR_INVALID_ARGUMENT, the previous setting staying in force: unless both the channel audio
+ *                                   and the squelch are on; where max_blocks * A >= 2^32 (the offsets are 32-bit words); while a pipelined sinks batch
+ *                                   is inside the handle.  While it is on, fdc_pipeline_set_audio(decim 0) and fdc_pipeline_set_squelch(NULL ...) are
+ *                                   refused (switch the packing off first), and so is a new decimation that breaks the 2^32 bound; a new audio format,
+ *                                   decimation or taps is allowed otherwise and, as a switch of the packing itself, leaves nothing to fetch until the
+ *                                   next call.  A SETTING: it applies from the next call and survives fdc_pipeline_reset; it waits for the handle's own
+ *                                   stream first.  It allocates everything the feature needs, once: the offsets uint32[max_blocks][C], one int64
+ *                                   running total on the device and its pinned twin; nothing in the steady state of any entry.  The packed elements
+ *                                   live in the audio's own buffers (count <= nblocks * A).  A plan without channels accepts it.
+ *   fdc_pipeline_audio_packing      1 while on, 0 while off, -1 for a NULL handle.
+ *   fdc_pipeline_audio_packed       the packed audio of the last call, nblocks being that call's block count (as fdc_pipeline_audio).  *count receives
+ *                                   the number of ELEMENTS whenever the call is valid (right handle state, right nblocks, count not NULL).  dst NULL: a
+ *                                   query for the count.  capacity_bytes below count elements: FDC_ERR_INVALID_ARGUMENT, nothing written to dst, *count
+ *                                   set all the same, so the caller can size its buffer.  After a host entry it is a memcpy from the pinned twin; after
+ *                                   a device entry it waits for the stream that one ran on, fetches the count and then count elements.
+ * WHILE IT IS ON: fdc_pipeline_audio (the matrix) is refused.  fdc_pipeline_audio_device is the packed buffer, of which only the first count elements
+ * are specified.  The host stream entries bring the mask and the 8-byte count home with the levels, and after the call's synchronise copy exactly count
+ * elements and synchronise once more (neither where count is 0): no entry copies more than count audio elements over the link.  AT FULL OCCUPANCY that
+ * second synchronise is pure cost: leave the packing off on a band whose channels are mostly open.  The sub-batches of a long host call append to one
+ * packed buffer through the running total on the device.  The device entries write the demodulated ports to d_out as ever, the packed audio to
+ * the handle's buffer and the count to the device word.  fdc_pipeline_audio_pass_device runs the PACKED form over the handle's mask and offsets of the
+ * last successful call (refused unless nblocks is that call's block count) and writes exactly count elements at the front of d_out, plus the history
+ * as before.  fdc_pipeline_describe: "audio: pass, gated, packed" after a call that ran it.  With the setting off every entry launches exactly the
+ * kernels it launches without this feature. */
+int fdc_pipeline_set_audio_packing(fdc_pipeline *p, int on);
+int fdc_pipeline_audio_packing(const fdc_pipeline *p);
+int fdc_pipeline_audio_packed(fdc_pipeline *p, void *dst, size_t capacity_bytes, int nblocks, int64_t *count);
+/* The offsets alone, on device buffers of the caller (and the entry the tests reach the kernels by with hand-made masks), with the handle's channel
+ * table and the audio's decimation (the audio must be on) and nothing of its state: d_mask [nblocks][C] bytes, d_base_in one int64 added to every
+ * offset and to the total (NULL: 0), d_off exactly nblocks C uint32 words (an offset is kept modulo 2^32), d_total_out one int64, which may be d_base_in's
+ * word.  Three launches, none of which waits on another workgroup.  Enqueued on `stream` (NULL: the handle's). */
+int fdc_pipeline_audio_pack_offsets_device(const fdc_pipeline *p, const void *d_mask, const void *d_base_in, void *d_off, void *d_total_out, int nblocks,
+                                           void *stream);
+
 /* Optional: pin a host range that will be handed to fdc_pipeline_work() again and again (GNU Radio's circular buffers
  * live as long as the flowgraph: register them in start(), unregister in stop()).  A call whose `in` lies in a
  * registered range is DMA'd from it in place, and when every outs[c] does, the results are stored straight into
