@@ -471,6 +471,73 @@ def lowpass_taps(decim, ntaps, cutoff=None):
     return (h / h.sum()).astype(np.float32)
 
 
+TONES_MAX, TONES_MAX_FRAME, TONE_TABLE = 64, 4096, 1024       # include/fdc_amd.h: tones per channel, blocks per frame, entries of the reference table
+
+
+def _tones_args(nchan, inc, group, frame_blocks):
+    """Pipeline.set_tones: (uint32 inc[C, T], S, W), (None, 0, 0) for inc None.  A 1-D inc is one row for all channels.  Raises before any library call."""
+    if inc is None:
+        return None, 0, 0
+    a = np.asarray(inc)
+    if a.dtype.kind not in "iu" or a.ndim not in (1, 2):
+        raise ValueError("the tone increments are unsigned 32-bit integers, [T] for all channels or [C, T] (tone_increments)")
+    if a.size and (a.min() < 0 or a.max() > 0xFFFFFFFF):
+        raise ValueError("a tone increment is outside 0 .. 2^32 - 1")
+    if a.ndim == 1:
+        a = np.broadcast_to(a[None, :], (nchan, a.size))
+    if a.shape[0] != nchan:
+        raise ValueError("the tone increments have %d rows for %d channels" % (a.shape[0], nchan))
+    if not 1 <= a.shape[1] <= TONES_MAX:
+        raise ValueError("there are 1 .. %d tones per channel" % TONES_MAX)
+    for name, v, hi in (("group length", group, None), ("frame length", frame_blocks, TONES_MAX_FRAME)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) < 1 or (hi is not None and int(v) > hi):
+            raise ValueError("the tone %s is an integer of at least 1%s" % (name, "" if hi is None else " and at most %d" % hi))
+    return np.ascontiguousarray(a, dtype=np.uint32), int(group), int(frame_blocks)
+
+
+def tone_table():
+    """fdc_tone_table: the 1024 float32 (cos, sin)(2 pi k / 1024) pairs of the tones' reference as the library holds them, [1024, 2]."""
+    tab = np.empty((TONE_TABLE, 2), dtype=np.float32)
+    _lib.check(_lib.lib().fdc_tone_table(tab.ctypes.data_as(C.POINTER(C.c_float))))
+    return tab
+
+
+def ctcss_tones():
+    """The 50 standard CTCSS frequencies in Hz, 67.0 .. 254.1, ascending (float64)."""
+    return np.array([67.0, 69.3, 71.9, 74.4, 77.0, 79.7, 82.5, 85.4, 88.5, 91.5, 94.8, 97.4, 100.0, 103.5, 107.2, 110.9, 114.8, 118.8, 123.0, 127.3,
+                     131.8, 136.5, 141.3, 146.2, 151.4, 156.7, 159.8, 162.2, 165.5, 167.9, 171.3, 173.8, 177.3, 179.9, 183.5, 186.2, 189.9, 192.8, 196.6,
+                     199.5, 203.5, 206.5, 210.7, 218.1, 225.7, 229.1, 233.6, 241.8, 250.3, 254.1])
+
+
+def tone_increments(freqs_hz, chan_rate_hz, group):
+    """Phase increments for Pipeline.set_tones: round(2^32 f S / r) mod 2^32 as uint32, f in Hz (any shape; negative frequencies wrap), r the channel's
+    sample rate in Hz (a scalar, or one value per row of a [C, T] freqs_hz) and S the group length.  |f S / r| must stay at or below 0.5: above it the
+    tone aliases at the group rate."""
+    f = np.asarray(freqs_hz, dtype=np.float64)
+    r = np.asarray(chan_rate_hz, dtype=np.float64)
+    if r.ndim == 1 and f.ndim == 2:
+        r = r[:, None]
+    if isinstance(group, bool) or not isinstance(group, (int, np.integer)) or int(group) < 1:
+        raise ValueError("the tone group length is an integer of at least 1")
+    if not np.isfinite(f).all() or not np.isfinite(r).all() or (r <= 0).any():
+        raise ValueError("the frequencies must be finite and the channel rate positive")
+    turns = f * int(group) / r
+    if (np.abs(turns) > 0.5).any():
+        raise ValueError("a tone lies beyond half the group rate (|f S / r| > 0.5)")
+    return (np.rint(turns * 4294967296.0).astype(np.int64) & 0xFFFFFFFF).astype(np.uint32)
+
+
+def tone_amplitude(Z, frame_samples, freqs_hz, chan_rate_hz, group):
+    """The amplitude of a tone at freqs_hz in the demodulated stream from its frame rows Z (Pipeline.tones; the last axis is the tone): |Z| divided by
+    frame_samples / 2 (frame_samples = W lout_c, the samples of a frame) and by the boxcar's droop sin(pi f S / r) / (S sin(pi f / r))."""
+    f = np.asarray(freqs_hz, dtype=np.float64)
+    r = float(chan_rate_hz)
+    x = np.pi * f / r
+    small = np.abs(np.sin(x)) < 1e-12
+    droop = np.where(small, 1.0, np.sin(x * int(group)) / (int(group) * np.where(small, 1.0, np.sin(x))))
+    return np.abs(np.asarray(Z)) / (float(frame_samples) / 2.0) / np.abs(droop)
+
+
 class Pipeline(_OutputFormat):
     """fdc_pipeline handle: channels = [(f, l, passbw, stopbw), ...]."""
     _last_nb = None        # block count of the last work call that had blocks (levels())
@@ -759,6 +826,61 @@ class Pipeline(_OutputFormat):
         [nblocks][C] float32 pairs, d_mask: nblocks * C bytes, d_state_in: C int32 pairs (open, h) or None, d_state_out: another such buffer).  The
         handle's own state and stream position are not touched."""
         _lib.check(_lib.lib().fdc_pipeline_squelch_pass_device(self._h, d_levels, d_mask, d_state_in, d_state_out, int(nblocks), stream))
+
+    def set_tones(self, inc, group=16, frame_blocks=32):
+        """fdc_pipeline_set_tones: inc None switches it off; else uint32 phase increments [C, T] (or [T] for all channels; tone_increments), T 1 .. 64,
+        a group length that divides every lout_c and a frame length of 1 .. 4096 blocks.  It needs the demodulation (set_demod) and runs behind it, on
+        the device: per channel and tone a correlator over the sums of `group` consecutive demodulated samples, integrated over frame_blocks blocks
+        (tests/tones_model.py); tones() gives the frame rows the last call completed.  The open frame is kept on the device from call to call and
+        starts anew after create, reset(), a new setting, a switch of demodulation mode, or a device or span call elsewhere in the stream; a new
+        demodulation gain keeps it.  A setting: it applies from the next call and survives reset().  ValueError for arguments out of range (nothing
+        reaches the library), FdcError where the library refuses (demodulation off, group does not divide a channel's lout, a pipelined sinks
+        batch inside); nothing changes then."""
+        a, s, w = _tones_args(len(self.channels), inc, group, frame_blocks)
+        if a is not None and a.size == 0:         # (a plan without channels: a pointer that is not NULL, which means off)
+            a = np.zeros((1, a.shape[1]), np.uint32)
+        _lib.check(_lib.lib().fdc_pipeline_set_tones(self._h, None if a is None else a.ctypes.data_as(C.POINTER(C.c_uint32)), len(self.channels),
+                                                     0 if a is None else int(a.shape[1]), s, w))
+
+    def tones_setting(self):
+        """fdc_pipeline_tones_setting: None while off, else (uint32 inc[C, T], group, frame_blocks): what the library has in force now."""
+        t, s, w = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        _lib.check(_lib.lib().fdc_pipeline_tones_setting(self._h, C.byref(t), C.byref(s), C.byref(w), None))
+        if t.value == 0:
+            return None
+        inc = np.zeros((max(1, len(self.channels)), t.value), dtype=np.uint32)
+        _lib.check(_lib.lib().fdc_pipeline_tones_setting(self._h, None, None, None, inc.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return inc[:len(self.channels)], int(s.value), int(w.value)
+
+    def tones(self, nblocks=None):
+        """fdc_pipeline_tones: the frame rows the last call completed, complex64 [nf, C, T] (nf may be 0: the call ended inside a frame).  nblocks: the
+        last call's block count where it did not go through this object's work methods (process_device, work_raw)."""
+        if nblocks is None:
+            if self._last_nb is None:
+                raise ValueError("tones(): no work call yet")
+            nblocks = self._last_nb
+        nblocks = int(nblocks)
+        if nblocks < 0:
+            raise ValueError("tones(): negative block count")
+        setting = self.tones_setting()
+        if setting is None:
+            raise ValueError("tones(): the channel tones are off (set_tones)")
+        inc, _, w = setting
+        out = np.empty(((nblocks + w - 1) // w, len(self.channels), inc.shape[1]), dtype=np.complex64)     # (the most a call of nblocks can complete)
+        nf = C.c_int32(0)
+        if nblocks:
+            _lib.check(_lib.lib().fdc_pipeline_tones(self._h, out.ctypes.data, out.nbytes, nblocks, C.byref(nf)))
+        return out[:nf.value].copy()
+
+    def tones_device(self):
+        """fdc_pipeline_tones_device: the device address of the frame rows ([frame of the last call][C][T] float32 pairs), None while it is off."""
+        return _lib.lib().fdc_pipeline_tones_device(self._h)
+
+    def tones_pass_device(self, d_in, d_frames, nblocks, first_block=0, fill=0, d_carry_in=None, d_carry_out=None, stream=None):
+        """fdc_pipeline_tones_pass_device: the tones pass alone on device buffers of the caller, with the setting in force (d_in: float32 in
+        process_device's layout, blocks first_block .. of a stream with `fill` blocks already in the open frame; d_frames: ((fill + nblocks) // W) C T
+        float32 pairs; d_carry_in: C T pairs or None, d_carry_out: another such buffer).  The handle's own state and stream position are not touched."""
+        _lib.check(_lib.lib().fdc_pipeline_tones_pass_device(self._h, d_in, d_frames, d_carry_in, d_carry_out, int(first_block), int(fill), int(nblocks), stream))
 
     def _host_outs(self, outs, nb):
         """(outs, ptrs) of a host call.  While the channel audio is on — asked of the library at this call — the entries write no port: (None, None),
@@ -1135,7 +1257,7 @@ class FrequencyDomainChannelizer:
                  debug, device_id=0, max_blocks=64, devices=None, pipelined=False, waterfall=None, iq_input=None, iq_scale=1.0,
                  iq_output=None, iq_output_scale=1.0, fine_tuning=False, *, payload_format=None, payload_scale=1.0, levels=False, gains=None, lag1=False,
                  demod=None, demod_gain=1.0, audio_decim=None, audio_taps=None, audio_format="f32", audio_scale=1.0, squelch_db=None, squelch_close_db=None,
-                 squelch_hang=0, audio_packed=False):
+                 squelch_hang=0, audio_packed=False, tones=None, tone_group=16, tone_frame=32):
         # pipelined (not an argument of the reference): the sink blocks run beside the front end of the FOLLOWING work() calls, as the
         # thread-per-block scheduler runs them beside the FFT in the reference (fdc_pipeline_work_sinks on a look-ahead bank,
         # include/fdc_amd.h): same PDUs, handed out one or two work() calls later; flush() at the end of the stream
@@ -1307,6 +1429,17 @@ class FrequencyDomainChannelizer:
         if self.audio_packed and (audio_decim is None or squelch_db is None):
             raise ValueError("audio_packed needs audio_decim and squelch_db: it packs the channel audio by the squelch's mask")
 
+        # tones / tone_group / tone_frame (not arguments of the reference): a tone bank per throughput channel behind the demodulation, on the device
+        # (Pipeline.set_tones): tones are the uint32 phase increments, [T] for all channels or [C, T] (tone_increments), tone_group the samples summed in
+        # front of the correlators, tone_frame the items per frame.  After every work() self.tones is complex64 [frames the call completed, throughput
+        # channels, T]; a call that ends inside a frame completes none, and the frame goes on in the next call.  It needs demod
+        self.tone_inc, self.tone_group, self.tone_frame = tones, tone_group, tone_frame
+        self.tones = None
+        if tones is not None:
+            if demod is None:
+                raise ValueError("tones needs demod: the tone bank runs behind the channel demodulation")
+            self.tone_inc = _tones_args(len(self.throughput_channels), tones, tone_group, tone_frame)[0]
+
         # gains (not an argument of the reference): one output gain per throughput channel, applied on the device behind fine tuning and in front of the
         # levels and of iq_output's narrowing (Pipeline.set_gains); set_gains() changes them between work() calls (an AGC fed from self.levels)
         self.gains = None if gains is None else _check_gains(len(self.throughput_channels), gains)
@@ -1387,6 +1520,8 @@ class FrequencyDomainChannelizer:
             self.set_squelch(self.squelch_db, self.squelch_close_db, self.squelch_hang)
         if self.audio_packed:
             self.pipeline.set_audio_packing(True)
+        if self.tone_inc is not None:
+            self.pipeline.set_tones(self.tone_inc, self.tone_group, self.tone_frame)
         self.N_throughput_channelizers = len(self.channel_params)
         # waterfall (not an argument of the reference, whose example flowgraph wires the spectrum to complex_to_mag_squared and
         # FDC.WaterfallMsgTagging outside the hier block): a gr_fdc_amd.Waterfall fed from the spectrum on the device; work() then
@@ -1467,6 +1602,9 @@ class FrequencyDomainChannelizer:
             self.lag1 = self.pipeline.lag1() if self.pipeline._call_nb > 0 else np.empty((0, len(self.channel_params)), dtype=np.complex64)
         if self.squelch_db is not None:
             self.squelch = self.pipeline.squelch() if self.pipeline._call_nb > 0 else np.empty((0, len(self.channel_params)), dtype=np.uint8)
+        if self.tone_inc is not None:
+            self.tones = (self.pipeline.tones() if self.pipeline._call_nb > 0
+                          else np.empty((0, len(self.channel_params), self.tone_inc.shape[1]), dtype=np.complex64))
         if self.debug:
             outs, spec = res
             return [spec] + outs
@@ -1502,6 +1640,19 @@ class FrequencyDomainChannelizer:
                 raise ValueError("the squelch needs levels=True and one device")
             self.pipeline.set_squelch(*squelch_thresholds(self.pipeline.lout, open_db, close_db), hang=hang)
         self.squelch_db, self.squelch_close_db, self.squelch_hang = open_db, close_db, hang
+
+    def set_tones(self, inc, group=16, frame=32):
+        """A new tone bank (uint32 increments [T] or [throughput channels, T]; None: off), group length and frame length in items from the next work()
+        call on: Pipeline.set_tones; the open frame starts anew.  It needs demod and one device."""
+        if inc is None:
+            self.pipeline.set_tones(None)
+            self.tone_inc, self.tones = None, None
+            return
+        if self.demod is None or not isinstance(self.pipeline, Pipeline):
+            raise ValueError("the tones need demod and one device")
+        a = _tones_args(len(self.throughput_channels), inc, group, frame)[0]
+        self.pipeline.set_tones(a, group, frame)
+        self.tone_inc, self.tone_group, self.tone_frame = a, group, frame
 
     def flush(self):
         """End of the stream (what the block's stop() does): the pipelined form still holds the PDUs of the last one or two work()

@@ -414,6 +414,7 @@ int32_t fdc_pipeline_describe(const fdc_pipeline *p, char *buf, int32_t n)
     if (!p->demod_route.empty()) add("; demod: %s", p->demod_route.c_str());
     if (!p->audio_route.empty()) add("; audio: %s", p->audio_route.c_str());
     if (!p->squelch_route.empty()) add("; squelch: %s", p->squelch_route.c_str());
+    if (!p->tones_route.empty()) add("; tones: %s", p->tones_route.c_str());
     std::snprintf(buf, (size_t)n, "%s", t);
     return k;
 }
@@ -493,6 +494,9 @@ void fdc_pipeline_reset(fdc_pipeline *p)
     p->audio_next = -1;
     p->squelch_route.clear();    // (and the channel squelch: every channel starts closed again)
     p->squelch_next = -1;
+    p->tones_route.clear();      // (and the channel tones: no frame is open)
+    p->tones_next = -1;
+    p->tones_fill = 0;
 }
 
 int fdc_pipeline_set_output_format(fdc_pipeline *p, int32_t format, float scale)
@@ -667,6 +671,8 @@ int fdc_pipeline_set_demod(fdc_pipeline *p, int32_t mode, float gain)
         return set_error(FDC_ERR_INVALID_ARGUMENT, "the channel demodulation writes real float32 samples: set the output format to FDC_OQ_FC32 first");
     if (!mode && p->audio_decim)
         return set_error(FDC_ERR_INVALID_ARGUMENT, "the channel audio filters the demodulated samples: switch the audio off first (fdc_pipeline_set_audio(p, 0, NULL, 0, 0, 1))");
+    if (!mode && p->tones_T)
+        return set_error(FDC_ERR_INVALID_ARGUMENT, "the channel tones correlate the demodulated samples: switch the tones off first (fdc_pipeline_set_tones(p, NULL, C, 0, 0, 0))");
     HIPCHK(hipSetDevice(p->cfg.device_id));
     HIPCHK(hipStreamSynchronize(p->stream));          // (no call of the host entries is in flight; a device entry's caller orders its own stream)
     if (!mode) { p->demod_mode = 0; p->demod_gain = 1.0f; p->demod_next = -1; p->demod_route.clear(); return FDC_OK; }
@@ -674,8 +680,8 @@ int fdc_pipeline_set_demod(fdc_pipeline *p, int32_t mode, float gain)
     RCCHK(out_staging(p));
     for (int i = 0; i < 2; i++)
         if (p->C > 0 && !p->d_carry[i]) HIPCHK(p->d_carry[i].alloc((size_t)p->C));
-    if (mode != p->demod_mode) p->demod_next = p->audio_next = -1;    // switched on, or another mode: no sample in front of the next call, no history in
-                                                                      // front of its audio (a new gain alone keeps both)
+    if (mode != p->demod_mode) p->demod_next = p->audio_next = p->tones_next = -1;    // switched on, or another mode: no sample in front of the next call, no
+                                                                      // history in front of its audio, no open tone frame (a new gain alone keeps them)
     p->demod_mode = mode;
     p->demod_gain = gain;
     return FDC_OK;
@@ -1039,6 +1045,133 @@ int fdc_pipeline_squelch_pass_device(const fdc_pipeline *p, const void *d_levels
     HIPCHK(fdc::launch_chan_squelch(static_cast<const float2 *>(d_levels), p->gains_on ? p->d_gain.get() : nullptr, p->d_sqthr[0], p->d_sqthr[1], p->sq_hang,
                                     static_cast<const int *>(d_state_in), static_cast<int *>(d_state_out), static_cast<unsigned char *>(d_mask), p->C, nblocks,
                                     stream ? static_cast<hipStream_t>(stream) : p->stream));
+    return FDC_OK;
+    FDC_ENTRY_END
+}
+
+// the channel tones: a setting that needs the demodulation; everything it needs is allocated here, once per size, and the stream state (the open
+// frame) starts anew whenever any part of the setting changes
+int fdc_pipeline_set_tones(fdc_pipeline *p, const uint32_t *inc, int nchan, int ntones, int32_t group, int32_t frame_blocks)
+{
+    FDC_ENTRY("fdc_pipeline_set_tones")
+    if (!p) return set_error(FDC_ERR_INVALID_ARGUMENT, "null handle");
+    if (nchan != p->C) return set_error(FDC_ERR_INVALID_ARGUMENT, "channel tones: increments for %d channels of %d", nchan, p->C);
+    if (inc) {
+        if (ntones < 1 || ntones > 64) return set_error(FDC_ERR_INVALID_ARGUMENT, "channel tones: %d tones per channel are not in 1 .. 64", ntones);
+        if (group < 1) return set_error(FDC_ERR_INVALID_ARGUMENT, "channel tones: the group length %d is not positive", (int)group);
+        if (frame_blocks < 1 || frame_blocks > 4096) return set_error(FDC_ERR_INVALID_ARGUMENT, "channel tones: the frame length %d is not in 1 .. 4096 blocks", (int)frame_blocks);
+    }
+    if (p->hier_filled > 0)
+        return set_error(FDC_ERR_INVALID_ARGUMENT, "a pipelined sinks batch is still inside the handle: fdc_pipeline_flush_sinks until it returns 0 first");
+    if (inc && !p->demod_mode)
+        return set_error(FDC_ERR_INVALID_ARGUMENT, "the channel tones correlate the demodulated samples: switch the channel demodulation on first (fdc_pipeline_set_demod)");
+    for (int c = 0; inc && c < p->C; c++)
+        if (p->chans[(size_t)c].lout % group)
+            return set_error(FDC_ERR_INVALID_ARGUMENT, "the tone group length %d does not divide the %d output samples per block of channel %d", (int)group,
+                             (int)p->chans[(size_t)c].lout, c);
+    // the frame rows of the longest call, from the deepest fill on
+    const size_t nct = inc ? (size_t)p->C * (size_t)ntones : 0;
+    const size_t nrows = inc ? ((size_t)p->cfg.max_blocks + (size_t)frame_blocks - 1) / (size_t)frame_blocks : 0;
+    if (nrows * nct * sizeof(float2) > ((size_t)1 << 31))
+        return set_error(FDC_ERR_INVALID_ARGUMENT, "channel tones: %zu frame rows of %zu tones take more than 2^31 bytes", nrows, nct);
+    HIPCHK(hipSetDevice(p->cfg.device_id));
+    HIPCHK(hipStreamSynchronize(p->stream));          // (no call of the host entries is in flight; a device entry's caller orders its own stream)
+    if (!inc) {
+        p->tones_T = p->tones_S = p->tones_W = 0; p->tones_inc.clear();
+        p->tones_next = -1; p->tones_fill = 0; p->tn_blocks = -1; p->tn_frames = 0; p->tones_route.clear();
+        return FDC_OK;
+    }
+    // everything the feature needs, once per size: the table, the increments, the two carries, the rows and their pinned twin
+    if (!p->d_ttab) {
+        std::vector<float2> tab((size_t)fdc::kToneTable);
+        fdc::tone_table(tab.data());
+        HIPCHK(p->d_ttab.upload(tab));
+    }
+    if (nct > p->d_tinc.capacity()) HIPCHK(p->d_tinc.reserve(nct, nct));
+    for (int i = 0; i < 2; i++)
+        if (nct > p->d_tcarry[i].capacity()) HIPCHK(p->d_tcarry[i].reserve(nct, nct));
+    if (nrows * nct > p->d_tones.capacity()) HIPCHK(p->d_tones.reserve(nrows * nct, nrows * nct));
+    if (nrows * nct > p->pin_tones.capacity()) HIPCHK(p->pin_tones.reserve(nrows * nct, nrows * nct));
+    if (nct > 0) HIPCHK(hipMemcpy(p->d_tinc, inc, sizeof(uint32_t) * nct, hipMemcpyHostToDevice));
+    const bool same = p->tones_T == ntones && p->tones_S == group && p->tones_W == frame_blocks && p->tones_inc.size() == nct &&
+                      (nct == 0 || std::memcmp(p->tones_inc.data(), inc, sizeof(uint32_t) * nct) == 0);
+    if (!same) { p->tones_next = -1; p->tones_fill = 0; p->tn_blocks = -1; p->tn_frames = 0; }      // another bank: its stream starts anew, no call has rows yet
+    p->tones_T = ntones; p->tones_S = group; p->tones_W = frame_blocks;
+    p->tones_inc.assign(inc, inc + nct);
+    return FDC_OK;
+    FDC_ENTRY_END
+}
+
+int fdc_pipeline_tones_setting(const fdc_pipeline *p, int32_t *ntones, int32_t *group, int32_t *frame_blocks, uint32_t *inc)
+{
+    FDC_ENTRY("fdc_pipeline_tones_setting")
+    if (!p) return set_error(FDC_ERR_INVALID_ARGUMENT, "null handle");
+    if (ntones) *ntones = p->tones_T;
+    if (group) *group = p->tones_S;
+    if (frame_blocks) *frame_blocks = p->tones_W;
+    if (inc) std::copy(p->tones_inc.begin(), p->tones_inc.end(), inc);
+    return FDC_OK;
+    FDC_ENTRY_END
+}
+
+// the frame rows the last call completed: never more than the caller says its buffer holds
+int fdc_pipeline_tones(fdc_pipeline *p, void *dst, size_t capacity_bytes, int nblocks, int32_t *nframes)
+{
+    FDC_ENTRY("fdc_pipeline_tones")
+    if (!p) return set_error(FDC_ERR_INVALID_ARGUMENT, "null handle");
+    if (!p->tones_T) return set_error(FDC_ERR_INVALID_ARGUMENT, "the channel tones are off (fdc_pipeline_set_tones)");
+    if (p->tn_blocks < 0) return set_error(FDC_ERR_INVALID_ARGUMENT, "no work call has run since the channel tones were switched on or their setting changed");
+    if (nblocks != p->tn_blocks) return set_error(FDC_ERR_INVALID_ARGUMENT, "the last work call had %d blocks, not %d", p->tn_blocks, nblocks);
+    const size_t n = sizeof(float2) * (size_t)p->tn_frames * tones_row(p);
+    if (capacity_bytes < n)
+        return set_error(FDC_ERR_INVALID_ARGUMENT, "the %d tone frames of the last call take %zu bytes, the buffer holds %zu", p->tn_frames, n, capacity_bytes);
+    if (nframes) *nframes = p->tn_frames;
+    if (n == 0) return FDC_OK;
+    if (!dst) return set_error(FDC_ERR_INVALID_ARGUMENT, "null argument");
+    if (!p->tn_host) {
+        // a device entry's rows: read behind everything enqueued so far on the stream it ran on
+        HIPCHK(hipSetDevice(p->cfg.device_id));
+        HIPCHK(hipMemcpyAsync(p->pin_tones.get(), p->d_tones.get(), n, hipMemcpyDeviceToHost, p->tn_stream));
+        HIPCHK(hipStreamSynchronize(p->tn_stream));
+        p->tn_host = true;
+    }
+    std::memcpy(dst, p->pin_tones.get(), n);
+    return FDC_OK;
+    FDC_ENTRY_END
+}
+
+void *fdc_pipeline_tones_device(fdc_pipeline *p) { return p && p->tones_T ? static_cast<void *>(p->d_tones.get()) : nullptr; }
+
+// the tones pass alone, on the caller's device buffers: the handle gives its channel table and the tones' setting, nothing of its stream state
+int fdc_pipeline_tones_pass_device(const fdc_pipeline *p, const void *d_in, void *d_frames, const void *d_carry_in, void *d_carry_out, int64_t first_block,
+                                   int32_t fill, int nblocks, void *stream)
+{
+    FDC_ENTRY("fdc_pipeline_tones_pass_device")
+    if (!p) return set_error(FDC_ERR_INVALID_ARGUMENT, "null handle");
+    if (!p->tones_T) return set_error(FDC_ERR_INVALID_ARGUMENT, "the channel tones are off (fdc_pipeline_set_tones)");
+    if (nblocks < 0 || first_block < 0) return set_error(FDC_ERR_INVALID_ARGUMENT, "negative block count/index");
+    if (fill < 0 || fill >= p->tones_W) return set_error(FDC_ERR_INVALID_ARGUMENT, "the fill %d is not in 0 .. %d, the frame length - 1", (int)fill, p->tones_W - 1);
+    if (nblocks == 0 || p->C <= 0) return FDC_OK;
+    if ((int64_t)nblocks * p->sum_lout * 8 > 0xFFFFF000ll)
+        return set_error(FDC_ERR_INVALID_ARGUMENT, "nblocks %d x %lld output samples per block is more than the 4 GiB one call may produce", nblocks, (long long)p->sum_lout);
+    const bool rows = (fill + nblocks) / p->tones_W > 0;
+    if (!d_in || !d_carry_out || (rows && !d_frames)) return set_error(FDC_ERR_INVALID_ARGUMENT, "null device buffer");
+    if (d_carry_in == d_carry_out) return set_error(FDC_ERR_INVALID_ARGUMENT, "the carry is read from one buffer and written to another");
+    HIPCHK(hipSetDevice(p->cfg.device_id));
+    HIPCHK(fdc::launch_chan_tones(static_cast<const float *>(d_in), p->d_chans, p->d_tinc, p->d_ttab, static_cast<const float2 *>(d_carry_in),
+                                  static_cast<float2 *>(d_carry_out), static_cast<float2 *>(d_frames), p->C, p->tones_T, p->tones_S, p->tones_W, fill,
+                                  (long long)first_block, nblocks, stream ? static_cast<hipStream_t>(stream) : p->stream));
+    return FDC_OK;
+    FDC_ENTRY_END
+}
+
+int fdc_tone_table(float *dst)
+{
+    FDC_ENTRY("fdc_tone_table")
+    if (!dst) return set_error(FDC_ERR_INVALID_ARGUMENT, "null argument");
+    std::vector<float2> tab((size_t)fdc::kToneTable);
+    fdc::tone_table(tab.data());
+    std::memcpy(dst, tab.data(), sizeof(float2) * tab.size());
     return FDC_OK;
     FDC_ENTRY_END
 }

@@ -180,6 +180,10 @@ struct PostPass {
     unsigned char *squelch = nullptr;   // the call-wide k_chan_squelch over the call's levels, in front of the audio (which it gates): the squelch on
     bool squelch_cont = false;  //   ... the call continues the squelch's stream: the handle's state stands in front of its first block
     unsigned *pack_off = nullptr;   // the offsets of the call's cells in the packed audio, behind the squelch and in front of the audio (which then packs): packing on
+    float2 *tones = nullptr;    // the call-wide k_chan_tones behind the demodulation, beside the audio and independent of it: the tones on (where the call's
+                                // first completed frame row goes)
+    bool tones_cont = false;    //   ... the call continues the tones' stream: the handle's accumulators stand in front of its first block ...
+    int tones_fill = 0;         //   ... which is block tones_fill of the open frame (0 where the stream starts anew)
 };
 
 static PostPass post_pass(const fdc_pipeline *p, const DeviceCall &call, bool ofused)
@@ -200,6 +204,7 @@ static PostPass post_pass(const fdc_pipeline *p, const DeviceCall &call, bool of
     pp.audio = pp.demod ? call.audio : nullptr;
     pp.squelch = pp.levels ? call.squelch : nullptr;
     pp.pack_off = pp.audio && pp.squelch ? call.pack_off : nullptr;
+    pp.tones = pp.demod ? call.tones : nullptr;
     return pp;
 }
 
@@ -255,6 +260,15 @@ static int run_post_tail(fdc_pipeline *p, const DeviceCall &call, const PostPass
         p->ahist_cur ^= 1; p->audio_next = first_block + nblocks;
         p->audio_route = pp.pack_off ? "pass, gated, packed" : pp.squelch ? "pass, gated" : "pass";
     }
+    if (pp.tones) {
+        // the tone bank over the same demodulated samples, ungated: the open frame's accumulators are read from one buffer and written to the other, which
+        // is the handle's behind the enqueue, with the blocks now inside the open frame, for the call that goes on at the next block
+        HIPCHK(fdc::launch_chan_tones(static_cast<const float *>(d_out), p->d_chans, p->d_tinc, p->d_ttab, pp.tones_cont ? p->d_tcarry[p->tcarry_cur].get() : nullptr,
+                                      p->d_tcarry[p->tcarry_cur ^ 1].get(), pp.tones, p->C, p->tones_T, p->tones_S, p->tones_W, pp.tones_fill, (long long)first_block,
+                                      nblocks, call.stream));
+        p->tcarry_cur ^= 1; p->tones_next = first_block + nblocks; p->tones_fill = (pp.tones_fill + nblocks) % p->tones_W;
+        p->tones_route = "pass";
+    }
     if (pp.narrow_tail) HIPCHK(fdc::launch_complex_to_iq(call.ofmt, call.oscale, call.fout, d_out, (size_t)nblocks * p->sum_lout, call.stream));
     if (pp.fine_fused || pp.rotate) p->fine_route = pp.fine_fused ? "fused" : "rotated";
     if (pp.levels) p->levels_route = pp.rot_levels ? "with the rotation" : pp.gain_pass ? "with the gains" : "pass";
@@ -305,6 +319,13 @@ int process_device_impl(fdc_pipeline *p, DeviceCall &call, const void *d_ring, i
         // ... and for the squelch's state
         pp.squelch_cont = p->squelch_next == first_block;
         p->squelch_next = -1;
+    }
+    call.tones_frames = 0;
+    if (pp.tones) {
+        // ... and for the tones' open frame: its accumulators and how many blocks are inside it
+        pp.tones_cont = p->tones_next == first_block;
+        pp.tones_fill = pp.tones_cont ? p->tones_fill : 0;
+        p->tones_next = -1;
     }
     // path 5: the call's part of every group's launch (the group's: its input, its blocks and its waterfall rows)
     fdc::F4Launch f4{};
@@ -430,6 +451,7 @@ int process_device_impl(fdc_pipeline *p, DeviceCall &call, const void *d_ring, i
         }
     }
     RCCHK(run_post_tail(p, call, pp, first_block, nblocks, d_out));
+    if (pp.tones) call.tones_frames = (pp.tones_fill + nblocks) / p->tones_W;      // (counts the host has: nothing is read back to learn it)
     return FDC_OK;
 }
 
@@ -453,6 +475,11 @@ void squelch_written(fdc_pipeline *p, int nblocks, hipStream_t stream, bool host
     p->sq_blocks = nblocks; p->sq_stream = stream; p->sq_host = host;
 }
 
+void tones_written(fdc_pipeline *p, int nblocks, int nframes, hipStream_t stream, bool host)
+{
+    p->tn_blocks = nblocks; p->tn_frames = nframes; p->tn_stream = stream; p->tn_host = host;
+}
+
 // how the last integer-input / integer-output call was served (fdc_pipeline_describe): "<sc16|sc8>: fused", or what it was instead
 std::string route(int fmt, bool fused, const char *otherwise)
 {
@@ -473,6 +500,7 @@ static int process_device_oq(fdc_pipeline *p, DeviceCall &call, const void *d_ri
         if (!p->d_out && p->sum_lout > 0) return set_error(FDC_ERR_HIP, "channel demodulation: no float staging");
         call.ofmt = out_code(p); call.oscale = p->demod_gain; call.fout = p->d_out;
         call.audio = audio_rows(p, 0);          // (the audio goes to the handle's buffer, [max_blocks][A]: the check above covers it)
+        call.tones = tones_rows(p, 0);          // (and the frame rows to the handle's, [(max_blocks + W - 1) div W][C][T]: likewise)
     }
     const bool lev = p->levels_on && nblocks > 0;
     if (lev) {
@@ -500,6 +528,7 @@ static int process_device_oq(fdc_pipeline *p, DeviceCall &call, const void *d_ri
     if (rc == FDC_OK && lag) lag1_written(p, nblocks, call.stream, false);
     if (rc == FDC_OK && call.audio) audio_written(p, nblocks, call.stream, false);
     if (rc == FDC_OK && call.squelch) squelch_written(p, nblocks, call.stream, false);
+    if (rc == FDC_OK && call.tones) tones_written(p, nblocks, call.tones_frames, call.stream, false);
     return rc;
 }
 

@@ -293,6 +293,17 @@ hipError_t launch_audio_pack_offsets(const unsigned char *mask, const ChanDev *c
 hipError_t launch_chan_squelch(const float2 *levels, const float *gain, const float *thr_open, const float *thr_close, int hang, const int *state_in,
                                int *state_out, unsigned char *mask, int nchan, int nb_call, hipStream_t s);
 
+// Channel tones (fdc_pipeline_set_tones; fdc_tones.hip): the tone bank over the whole call's demodulated samples `in` (launch_chan_demod's out).  inc:
+// [nchan][ntones] phase increments per group of `group` samples (which divides every lout_c); tab: tone_table's kToneTable pairs on the device.  The
+// call is blocks [first_block, first_block + nb_call) of the stream, `fill` blocks (0 .. frame_blocks - 1) of which stand in the open frame in front of
+// it with their accumulators in carry_in ([nchan][ntones] float2; null: zeros; read only where fill > 0).  frames receives the (fill + nb_call) div
+// frame_blocks rows the call completes, [frame][nchan][ntones] float2 (null where it completes none), carry_out (another buffer) all nchan * ntones
+// accumulators of the frame left open, zeros where none is.  tests/tones_model.py is the arithmetic
+constexpr int kToneTable = 1024;
+void tone_table(float2 *dst);       // host: (cos, sin)(2 pi k / kToneTable), designed in double, rounded once, the axis entries exact
+hipError_t launch_chan_tones(const float *in, const ChanDev *chans, const unsigned *inc, const float2 *tab, const float2 *carry_in, float2 *carry_out,
+                             float2 *frames, int nchan, int ntones, int group, int frame_blocks, int fill, long long first_block, int nb_call, hipStream_t s);
+
 hipError_t launch_scale(const float2 *in, float2 *out, size_t n, float k, hipStream_t s);
 
 // sinks

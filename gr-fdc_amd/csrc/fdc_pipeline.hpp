@@ -246,6 +246,27 @@ struct fdc_pipeline {
     fdc::DevBuf<long long> d_packtotal;
     fdc::PinBuf<long long> pin_packtotal;
     int64_t pack_count = 0;
+    // channel tones (fdc_pipeline_set_tones): a setting that needs the demodulation.  tones_T: 0 = off, else the tones per channel; tones_S the group
+    // length, tones_W the frame length in blocks; tones_inc the C T increments in force, d_tinc their device copy, d_ttab the reference table.  The stream
+    // state: tones_fill, the blocks already inside the open frame, and d_tcarry, the open frame's accumulators, two buffers of C T: a call reads
+    // d_tcarry[tcarry_cur] where it continues the stream (its first_block is tones_next; -1: the stream starts anew, fill 0) and its kernel writes the
+    // other one; the enqueue path swaps behind a successful enqueue (the audio history likewise).  d_tones: the frame rows the last call completed,
+    // [(max_blocks + W - 1) div W][C][T], pin_tones its pinned twin (tn_host, tn_stream as lev_host, lev_stream; tn_frames: how many rows).  All of it is
+    // allocated by fdc_pipeline_set_tones, once per size.
+    int tones_T = 0, tones_S = 0, tones_W = 0;
+    std::vector<uint32_t> tones_inc;
+    fdc::DevBuf<unsigned> d_tinc;
+    fdc::DevBuf<float2> d_ttab, d_tcarry[2];
+    int tcarry_cur = 0;
+    int64_t tones_next = -1;
+    int tones_fill = 0;
+    fdc::DevBuf<float2> d_tones;
+    fdc::PinBuf<float2> pin_tones;
+    int tn_blocks = -1;          // block count of the last successful work call with the tones on (-1: none yet)
+    int tn_frames = 0;           // ... and the frames it completed
+    bool tn_host = false;
+    hipStream_t tn_stream = nullptr;
+    std::string tones_route;     // the last call with the setting on ran the tones pass (fdc_pipeline_describe)
     fdc::DevBuf<float2> d_out;   // work(): max_blocks*sum_lout (out_staging)
     int64_t blockcount = 0;      // work(): blocks consumed so far
     // work(): transfers and kernels of consecutive sub-batches overlap (H2D on s_in, kernels on stream, D2H on s_out)
@@ -318,9 +339,14 @@ struct DeviceCall {
     // pack_append says so (a sub-batch behind the first of a host call) and at 0 otherwise, and the total goes to the handle's device word
     unsigned *pack_off = nullptr;
     bool pack_append = false;
+    // channel tones (fdc_pipeline_set_tones): where the first frame row the call completes goes, [frame][C][T]; null = none.  It goes with a demodulating
+    // output code only.  A sub-batch of a host call hands in the row behind the frames the host call has completed so far (tones_frames, below)
+    float2 *tones = nullptr;
     int ncu = 0;                        // compute units the call's persistent kernels may use
-    // results: no launch group had to be widened (each read the integer input in its own loads); the call's kernels narrowed in their own stores
+    // results: no launch group had to be widened (each read the integer input in its own loads); the call's kernels narrowed in their own stores;
+    // the frame rows the tones pass of the call completed
     bool all_fused = true, ofused = false;
+    int tones_frames = 0;
 };
 
 // which form a timed launch group ran (ev_spans[.][4]): how the three intervals between its four events map to ms[0..2]
@@ -350,6 +376,12 @@ inline unsigned char *squelch_rows(const fdc_pipeline *p, size_t b0)
 // packed audio: whether the handle's next call packs its audio, and where the offsets rows from block b0 of a host call on go (null: it does not)
 inline bool packing_on(const fdc_pipeline *p) { return p->pack_on && audio_on(p) && squelch_rows(p, 0); }
 inline unsigned *pack_rows(const fdc_pipeline *p, size_t b0) { return packing_on(p) ? p->d_packoff.get() + b0 * (size_t)p->C : nullptr; }
+
+// channel tones: whether the handle's next call runs the pass, the elements of one frame row, and where the row behind `done` completed frames of a
+// host call goes in the handle's buffer (null: the call runs no tones pass)
+inline bool tones_on(const fdc_pipeline *p) { return p->tones_T > 0 && p->demod_mode && p->C > 0; }
+inline size_t tones_row(const fdc_pipeline *p) { return (size_t)p->C * (size_t)p->tones_T; }
+inline float2 *tones_rows(const fdc_pipeline *p, size_t done) { return tones_on(p) ? p->d_tones.get() + done * tones_row(p) : nullptr; }
 
 inline bool ispow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
 
@@ -389,6 +421,7 @@ void levels_written(fdc_pipeline *p, int nblocks, hipStream_t stream, bool host)
 void lag1_written(fdc_pipeline *p, int nblocks, hipStream_t stream, bool host);     // the same of the lag-1 correlation (fdc_pipeline_lag1)
 void audio_written(fdc_pipeline *p, int nblocks, hipStream_t stream, bool host);    // ... and of the channel audio (fdc_pipeline_audio)
 void squelch_written(fdc_pipeline *p, int nblocks, hipStream_t stream, bool host);  // ... and of the channel squelch (fdc_pipeline_squelch)
+void tones_written(fdc_pipeline *p, int nblocks, int nframes, hipStream_t stream, bool host);   // ... and of the channel tones (fdc_pipeline_tones)
 std::string route(int fmt, bool fused, const char *otherwise);   // "<sc16|sc8>: fused", or what the call was instead (fdc_pipeline_describe)
 
 } }  // namespace fdc::pipe

@@ -26,8 +26,11 @@ static int check_float_output(const fdc_pipeline *p, const char *entry, bool wri
 
 // Channel levels of a host entry's call: one copy of its nblocks*C (power, peak) pairs to the pinned twin, enqueued in front of the call's synchronise,
 // so that fdc_pipeline_levels is a memcpy; and the same of its lag-1 correlation (fdc_pipeline_lag1)
-static int levels_home(fdc_pipeline *p, int nblocks, hipStream_t s)
+static int levels_home(fdc_pipeline *p, int nblocks, hipStream_t s, int tones_frames = 0)
 {
+    // the frame rows the call's tones pass completed (fdc_pipeline_tones), by the same rule: no copy where it completed none
+    if (tones_on(p) && tones_frames > 0)
+        HIPCHK(hipMemcpyAsync(p->pin_tones.get(), p->d_tones.get(), sizeof(float2) * (size_t)tones_frames * tones_row(p), hipMemcpyDeviceToHost, s));
     if (p->levels_on && p->C > 0)
         HIPCHK(hipMemcpyAsync(p->pin_levels.get(), p->d_levels.get(), sizeof(float2) * (size_t)nblocks * p->C, hipMemcpyDeviceToHost, s));
     if (p->lag1_on && p->C > 0)
@@ -212,6 +215,7 @@ static int pipeline_work_impl(fdc_pipeline *p, DeviceCall call, const void *in, 
     call.wide = fmt ? p->d_ring : nullptr;
     call.ofmt = ofmt; call.oscale = oscale; call.narrow = !out_reg || demod;
     bool oq_all = true;
+    int tframes = 0;              // channel tones: the frame rows the call's sub-batches have completed so far; the next one's rows append behind them
     // dok: the float results of the sub-batch starting at block b0.  Integer output: its narrow results go to the same sample offset of d_oq (call.ofused: the
     // kernels wrote them there themselves; otherwise dok holds float and is narrowed into d_oq, unless the outputs are registered: k_scatter_oq narrows)
     // (channel levels: a sub-batch is a call of its own to the enqueue path, so each hands in where ITS block 0 goes)
@@ -222,9 +226,11 @@ static int pipeline_work_impl(fdc_pipeline *p, DeviceCall call, const void *in, 
         call.audio = audio_rows(p, b0);
         call.squelch = squelch_rows(p, b0);
         if (pack) { call.audio = p->d_audio.get(); call.pack_off = pack_rows(p, b0); call.pack_append = true; }
+        call.tones = tones_rows(p, (size_t)tframes);
         const int rc2 = process_device_impl(p, call, ringb + b0 * p->H * esz, first, nb,
                                             ofmt ? static_cast<void *>(p->d_oq + osz * b0 * (size_t)p->sum_lout) : static_cast<void *>(dok));
         oq_all = oq_all && call.ofused;
+        if (rc2 == FDC_OK) tframes += call.tones_frames;
         return rc2;
     };
     // what the caller's buffers receive for the sub-batch at b0: float from d_out, or narrow from d_oq
@@ -267,13 +273,14 @@ static int pipeline_work_impl(fdc_pipeline *p, DeviceCall call, const void *in, 
         }
         if (spectrum) HIPCHK(hipMemcpyAsync(spectrum, d_specfull, sizeof(float2) * (size_t)nblocks * p->N, hipMemcpyDeviceToHost, s));
         HIPCHK(hipMemcpyAsync(ringb, ringb + esz * nin, esz * (size_t)p->ovl, hipMemcpyDeviceToDevice, s));
-        RCCHK(levels_home(p, nblocks, s));
+        RCCHK(levels_home(p, nblocks, s, tframes));
         HIPCHK(hipStreamSynchronize(s));
         RCCHK(packed_home(p, s));
         if (p->levels_on) levels_written(p, nblocks, s, true);
     if (p->lag1_on) lag1_written(p, nblocks, s, true);
         if (audio) audio_written(p, nblocks, s, true);
         if (squelch_rows(p, 0)) squelch_written(p, nblocks, s, true);
+        if (tones_on(p)) tones_written(p, nblocks, tframes, s, true);
         if (fmt) p->iq_route = route(fmt, call.all_fused, "widened");
         if (p->out_form) p->oq_route = route(ofmt, oq_all, "narrowed");
         if (ports && !out_reg) deliver(0, 0, nblocks);
@@ -335,7 +342,7 @@ static int pipeline_work_impl(fdc_pipeline *p, DeviceCall call, const void *in, 
     if (spectrum) HIPCHK(hipMemcpyAsync(spectrum, d_specfull, sizeof(float2) * (size_t)nblocks * p->N, hipMemcpyDeviceToHost, s));
     // history <- last ovl samples of this call (overlap_save_impl.cc:78); src and dst never overlap (H >= ovl)
     HIPCHK(hipMemcpyAsync(ringb, ringb + esz * nin, esz * (size_t)p->ovl, hipMemcpyDeviceToDevice, s));
-    RCCHK(levels_home(p, nblocks, s));
+    RCCHK(levels_home(p, nblocks, s, tframes));
     HIPCHK(hipStreamSynchronize(s));
     HIPCHK(hipStreamSynchronize(p->s_out));
     RCCHK(packed_home(p, s));
@@ -343,6 +350,7 @@ static int pipeline_work_impl(fdc_pipeline *p, DeviceCall call, const void *in, 
     if (p->lag1_on) lag1_written(p, nblocks, s, true);
     if (audio) audio_written(p, nblocks, s, true);
     if (squelch_rows(p, 0)) squelch_written(p, nblocks, s, true);
+    if (tones_on(p)) tones_written(p, nblocks, tframes, s, true);
     if (fmt) p->iq_route = route(fmt, call.all_fused, "widened");
     if (p->out_form) p->oq_route = route(ofmt, oq_all, "narrowed");
     p->blockcount += nblocks;
@@ -446,17 +454,19 @@ static int pipeline_work_real_impl(fdc_pipeline *p, const void *in, int nblocks,
     call.audio = audio_rows(p, 0);
     call.squelch = squelch_rows(p, 0);
     if (packing_on(p)) { call.audio = p->d_audio.get(); call.pack_off = pack_rows(p, 0); call.pack_append = false; }
+    call.tones = tones_rows(p, 0);
     RCCHK(process_device_impl(p, call, p->d_ring, p->blockcount, nblocks, res));
     if (!call.audio) RCCHK(copy_outputs(p, outs, nblocks, osz, res, s));     // (audio on: the rows go home with the levels, outs is not looked at)
     if (spectrum) HIPCHK(hipMemcpyAsync(spectrum, d_specfull, sizeof(float2) * (size_t)nblocks * p->N, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(p->d_ring, p->d_ring + nin, sizeof(float2) * (size_t)p->ovl, hipMemcpyDeviceToDevice, s));
-    RCCHK(levels_home(p, nblocks, s));
+    RCCHK(levels_home(p, nblocks, s, call.tones_frames));
     HIPCHK(hipStreamSynchronize(s));
     RCCHK(packed_home(p, s));
     if (p->levels_on) levels_written(p, nblocks, s, true);
     if (p->lag1_on) lag1_written(p, nblocks, s, true);
     if (call.audio) audio_written(p, nblocks, s, true);
     if (call.squelch) squelch_written(p, nblocks, s, true);
+    if (call.tones) tones_written(p, nblocks, call.tones_frames, s, true);
     if (p->out_form) p->oq_route = route(ofmt, call.ofused, "narrowed");
     p->blockcount += nblocks;
     return nblocks;

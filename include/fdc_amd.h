@@ -497,6 +497,59 @@ int fdc_pipeline_audio_packed(fdc_pipeline *p, void *dst, size_t capacity_bytes,
 int fdc_pipeline_audio_pack_offsets_device(const fdc_pipeline *p, const void *d_mask, const void *d_base_in, void *d_off, void *d_total_out, int nblocks,
                                            void *stream);
 
+/* CHANNEL TONES: per channel a bank of T narrow correlators (a tone squelch's measurement: CTCSS, pilot and paging tones) over the demodulated samples,
+ * integrated over frames of W blocks, on the device.  The setting: T tones per channel, 1 .. 64; a table inc[C][T] of uint32 phase increments; a group
+ * length S >= 1 that divides every lout_c; a frame length W of 1 .. 4096 blocks.  With d the real float32 stream k_chan_demod writes for channel c (the
+ * demodulation gain included), G = lout_c / S and b the stream's block index:
+ *     u(b, q)  = d[b lout_c + q S + i] summed over i = 0 .. S - 1, ascending, in float32 from +0, every sum rounded on its own       (a boxcar by S)
+ *     g        = b G + q (64 bits);  k = ((inc[c][t] g) mod 2^32) >> 22;  (cs, sn) = table[k]
+ *     re = re + float32(u cs);  im = im - float32(u sn)       per group, g ascending, every product and sum rounded on its own, from (+0, +0)
+ * table: 1024 float32 pairs (cos, sin)(2 pi k / 1024), designed in double and rounded once, entries 0 / 256 / 512 / 768 exactly (1, 0), (0, 1), (-1, 0),
+ * (0, -1) (fdc_tone_table writes them; host only, no handle).  The accumulator of (c, t) runs on over the W blocks of a frame; at the frame's last group
+ * it is the frame's row Z[f][c][t] (re, im) and starts again at (+0, +0).  The phase is an integer function of the stream's own group index: no drift,
+ * and nothing depends on how the stream is cut.  tests/tones_model.py states this in numpy, and the rows are that model's byte for byte.
+ * For a tone of amplitude a at frequency f in d, at channel rate r: |Z| ~ a (W lout_c / 2) droop(f), droop(f) = sin(pi f S / r) / (S sin(pi f / r)); an
+ * increment is round(2^32 f S / r).  The tones are NOT gated by the squelch, and the decision on top of them (thresholds, a tone squelch) is the host's.
+ * THE STATE: the handle keeps a block position for the tones, the blocks already inside the open frame (fill, a host integer) and the open frame's
+ * accumulators, float2[C][T], on the device.  A call CONTINUES the stream when its first_block is the block after the last one of the previous
+ * successful call with the tones on; otherwise fill = 0 and the accumulators are zero: after create or fdc_pipeline_reset, after switching the tones on
+ * or changing any part of the setting, after a change of demodulation mode, after a call that failed once it had begun to enqueue, at a device or span
+ * call elsewhere in the stream.  A new demodulation gain alone keeps the state.  A call that is REFUSED leaves everything as it was.  A call of nb
+ * blocks completes nf = (fill + nb) div W frames and leaves fill = (fill + nb) mod W: frames are counted from the tone stream's start (the phase uses
+ * the stream's block index all the same), and nf may be 0.  The rows of the calls of a stream, one behind the other, are the rows of the stream in
+ * one call, byte for byte, however it is cut into calls, sub-batches or launch groups.
+ *   fdc_pipeline_set_tones          inc NULL switches it off.  FDC_ERR_INVALID_ARGUMENT, the previous setting staying in force: nchan != C; ntones not in
+ *                                   1 .. 64, group < 1, frame_blocks not in 1 .. 4096; group does not divide some lout_c (the message names the channel);
+ *                                   while the demodulation is off; while a pipelined sinks batch is inside the handle; where the rows of the longest
+ *                                   call would exceed 2^31 bytes.  fdc_pipeline_set_demod(FDC_DEMOD_OFF) is refused while the tones are on.  A SETTING:
+ *                                   it applies from the next call and survives fdc_pipeline_reset (the state does not); it waits for the handle's own
+ *                                   stream first.  It allocates everything the feature needs, once per size: the table, the increments, two carry
+ *                                   buffers of C T, ((max_blocks + W - 1) div W) C T rows and their pinned twin; nothing in the steady state of any
+ *                                   entry.  A plan without channels accepts it.
+ *   fdc_pipeline_tones_setting      the setting in force; any pointer may be NULL; ntones is 0 while off; inc receives C T words.
+ *   fdc_pipeline_tones              the rows the last call completed, [nf][C][T] float32 pairs, nblocks being that call's block count (as
+ *                                   fdc_pipeline_levels); *nframes receives nf.  capacity_bytes below nf C T 8: FDC_ERR_INVALID_ARGUMENT, nothing
+ *                                   written.  After a host entry it is a memcpy from the pinned twin, copied home with the levels (no copy where
+ *                                   nf = 0); after a device entry it waits for the stream that one ran on.
+ *   fdc_pipeline_tones_device       the device rows, NULL while off.
+ * Whether the ports themselves go to the host is unchanged: with the channel audio off the host entries write the demodulated ports to outs, with it
+ * on they do not; the device entries write d_out as ever.  The tones pass is one more launch behind k_chan_demod, independent of the audio, the squelch
+ * and the packing.  fdc_pipeline_describe: "tones: pass" after a call that ran it.  With the setting off every entry launches exactly the kernels it
+ * launches without this feature.  There is no group setter. */
+int fdc_pipeline_set_tones(fdc_pipeline *p, const uint32_t *inc, int nchan, int ntones, int32_t group, int32_t frame_blocks);
+int fdc_pipeline_tones_setting(const fdc_pipeline *p, int32_t *ntones, int32_t *group, int32_t *frame_blocks, uint32_t *inc);
+int fdc_pipeline_tones(fdc_pipeline *p, void *dst, size_t capacity_bytes, int nblocks, int32_t *nframes);
+void *fdc_pipeline_tones_device(fdc_pipeline *p);
+/* The pass alone, on device buffers of the caller (and the entry the tests reach the kernel by with hand-made samples), with the handle's channel table
+ * and the tones' setting (which must be on) and nothing of its stream state: d_in real float32 in fdc_pipeline_process_device's layout (channel c at
+ * element offset nblocks*out_off_c), blocks [first_block, first_block + nblocks) of a stream with `fill` blocks (0 .. W - 1) already in the open frame;
+ * d_carry_in C T float32 pairs or NULL (zeros; read only where fill > 0), d_carry_out another buffer that receives exactly C T pairs (zeros where the
+ * call leaves no frame open), d_frames exactly ((fill + nblocks) div W) C T pairs (NULL where that is 0).  Enqueued on `stream` (NULL: the handle's). */
+int fdc_pipeline_tones_pass_device(const fdc_pipeline *p, const void *d_in, void *d_frames, const void *d_carry_in, void *d_carry_out, int64_t first_block,
+                                   int32_t fill, int nblocks, void *stream);
+/* The 1024 (cos, sin) pairs of the tones' reference, 2048 floats.  Host only, no handle. */
+int fdc_tone_table(float *dst);
+
 /* Optional: pin a host range that will be handed to fdc_pipeline_work() again and again (GNU Radio's circular buffers
  * live as long as the flowgraph: register them in start(), unregister in stop()).  A call whose `in` lies in a
  * registered range is DMA'd from it in place, and when every outs[c] does, the results are stored straight into
