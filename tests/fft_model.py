@@ -5,6 +5,8 @@
   fft32_model_steps    the same with the roundings a radix-16 / two-pass transform legitimately takes and a radix-2 one does not (see there)
   channel_stage64  one channel of the channel stage (slice, window row, ifftshift, inverse transform, discard, times l) in complex128
   channel_stage32  the same with complex64 products and one of the float32 models
+  chain64, chain32 the whole chain (block, forward transform, shift and 1/N, channel stage) in complex128 / with complex64 intermediates and any
+                   pair of the float32 models; stream_blocks, chain_noise_stream, chain_impulse_stream, chain_tone_stream: its inputs, as streams
   noise, impulse_positions, wide_impulse_positions, impulses, tone      the inputs
   model_error, transform_model_error, channel_model_error, ratios       the criterion: error against the reference, held to a multiple of E_model
 
@@ -178,7 +180,9 @@ def channel_stage64(spec, N, R, chan, window_rows, first_block=0):
     """One channel of the channel stage on the spectrum items `spec` ((nb, N), what the channel kernels read: 1/N applied), in complex128:
     slice [f, f + l), times window row ((first_block + m) mod R * f) mod R, ifftshift, unnormalised inverse transform of length l, the first l // R
     samples discarded, times l (the composition tests/test_oracle.py::test_chain_blockwise_equals_composed_blocks spells out).
-    chan = (f, l); window_rows: the (R, l) table of the ORACLE (tests/golden/windows_ref.npz pins it).  Returns (nb, l - l // R)."""
+    chan = (f, l); window_rows: the (R, l) table of the ORACLE (tests/golden/windows_ref.npz pins it).  Returns (nb, l - l // R).
+    f may be an array of C offsets that agree mod R (one window table, one row per block: a uniform bank): one transform call for all of them,
+    (nb, C, l - l // R)."""
     return _channel_stage(spec, N, R, chan, window_rows, first_block, np.complex128)
 
 
@@ -196,14 +200,121 @@ def channel_model_error(spec, N, R, chan, window_rows, first_block, ref):
 
 def _channel_stage(spec, N, R, chan, window_rows, first_block, dtype, transform=None):
     f, l = chan
+    fs = np.atleast_1d(np.asarray(f, dtype=np.int64))
+    assert (fs % R == fs[0] % R).all() and fs.min() >= 0 and fs.max() + l <= N
     spec = np.asarray(spec).reshape(-1, N)
     nb = spec.shape[0]
     win = np.asarray(window_rows).reshape(R, l)
-    rows = np.array([window_row_index(first_block + m, R, f) for m in range(nb)])
-    y = spec[:, f:f + l].astype(dtype) * win[rows].astype(dtype)
+    rows = np.array([window_row_index(first_block + m, R, int(fs[0])) for m in range(nb)])
+    y = spec[:, fs[:, None] + np.arange(l)[None, :]].astype(dtype) * win[rows].astype(dtype)[:, None, :]
     y = np.fft.ifftshift(y, axes=-1)
     y = transform(y, inverse=True) if dtype == np.complex64 else dft64(y, inverse=True)
-    return y[:, l // R:] * dtype(l)
+    y = y[..., l // R:] * dtype(l)
+    return y[:, 0] if np.ndim(f) == 0 else y
+
+
+# ---------------------------------------------------------------- the whole chain: block -> forward N -> shift, 1/N -> channel stage
+# What the one-launch block kernels (k_blk256 / 512 / 1024, k_blknar, k_f4096) and the two-launch forms compute without a spectrum in memory: the
+# yardstick is the same two transforms in a row.  E of a (block, channel) row: the largest error over the FOUR (forward model, inverse model)
+# combinations of FLOAT32_MODELS.  There are NO factors for it yet: independent correct float32 chains (scipy.fft on complex64, the oracle's compiled
+# float32 chain) are up to 6.1 x (rms) and 8.7 x (per sample) off this E on rows where the models are nearly exact and the other chain is one ulp off
+# (profiles/accuracy/README.md, profiles/accuracy/chain_factors.py) — twice that is no float32-grade bound.
+CHAIN_COMBINATIONS = tuple((fwd, inv) for fwd in FLOAT32_MODELS for inv in FLOAT32_MODELS)
+
+
+def stream_blocks(stream, N, R):
+    """The blocks overlap-save cuts from a stream with N/R zeros in front of it: block m = samples [m H - N/R, m H + H), H = N - N/R.  (nb, N)."""
+    ovl = N // R
+    H = N - ovl
+    s = np.asarray(stream)
+    nb = s.size // H
+    ring = np.concatenate([np.zeros(ovl, dtype=s.dtype), s[:nb * H]])
+    return ring[H * np.arange(nb)[:, None] + np.arange(N)[None, :]]
+
+
+def forward64(blocks, N):
+    """fftshift(fft(block)) / N in complex128 — never rounded to complex64"""
+    y = np.fft.fft(np.asarray(blocks).astype(np.complex128).reshape(-1, N), axis=-1)
+    return np.fft.fftshift(y, axes=-1) / N
+
+
+def forward32(blocks, N, fwd):
+    """the same with one of FLOAT32_MODELS (or any complex64 transform of that signature), rounded to complex64 after the exact 1/N"""
+    y = np.asarray(fwd(np.asarray(blocks).astype(np.complex64).reshape(-1, N)))
+    assert y.dtype == np.complex64
+    return np.fft.fftshift(y, axes=-1) * np.float32(1.0 / N)
+
+
+def chain64(blocks, N, R, chan, window_rows, first_block=0, spec=None):
+    """The chain in complex128.  spec: forward64(blocks, N) when the caller already has it (many channel groups on one input)."""
+    return channel_stage64(forward64(blocks, N) if spec is None else spec, N, R, chan, window_rows, first_block)
+
+
+def chain32(blocks, N, R, chan, window_rows, first_block=0, fwd=fft32_model, inv=fft32_model, spec=None):
+    """The chain with complex64 intermediates: fwd and inv each one of FLOAT32_MODELS.  spec: forward32(blocks, N, fwd) when the caller has it."""
+    return channel_stage32(forward32(blocks, N, fwd) if spec is None else spec, N, R, chan, window_rows, first_block, transform=inv)
+
+
+def chain_model_error(blocks, N, R, chan, window_rows, first_block, ref, specs=None):
+    """E of every row: the largest (rms, max) error, relative to max|ref| (model_error), over the four combinations.  specs: {fwd: forward32(...)}."""
+    e_rms = e_max = None
+    for fwd, inv in CHAIN_COMBINATIONS:
+        y = chain32(blocks, N, R, chan, window_rows, first_block, fwd, inv, None if specs is None else specs[fwd])
+        a, b = model_error(y, ref)
+        e_rms, e_max = (a, b) if e_rms is None else (np.maximum(e_rms, a), np.maximum(e_max, b))
+    return e_rms, e_max
+
+
+def chain_noise_stream(N, R, seed):
+    """R + 1 blocks of noise: every window row occurs"""
+    return noise((R + 1) * (N - N // R), seed)
+
+
+def chain_impulse_stream(N, R):
+    """One unit impulse per block: block m + 1 holds one at impulse_positions(N)[m] (block 0 begins with the N/R zeros in front of the stream and
+    cannot hold the positions below N/R: it only sees block 1's impulse, N - N/R later — as every block sees a neighbour's impulse when that lies
+    in the samples the two share; the reference has them all).  len(impulse_positions(N)) + 1 blocks."""
+    ovl = N // R
+    H = N - ovl
+    pos = impulse_positions(N)
+    s = np.zeros((len(pos) + 1) * H, dtype=np.complex64)
+    for m, p in enumerate(pos):
+        s[(m + 1) * H + p - ovl] = 1.0
+    return s
+
+
+def chain_tone_stream(N, R, cut, j):
+    """R + 1 blocks of a sum of exact-bin tones, one inside every channel's slice: channel c = cut[c] = (f, l) takes bin
+    f + slice_positions(l)[(c + j) % len] of the shifted spectrum.  Every block behind block 0 (which begins with zeros) transforms to one impulse
+    per slice, every channel row to one window value times a pure exponential.  Summed in float64 (one period by an inverse transform of the
+    impulses), rounded once."""
+    H = N - N // R
+    X = np.zeros(N, dtype=np.complex128)
+    for c, (f, l) in enumerate(cut):
+        pos = slice_positions(l)
+        X[f + pos[(c + j) % len(pos)]] = 1.0
+    period = np.fft.ifft(np.fft.ifftshift(X)) * N
+    return period[np.arange((R + 1) * H) % N].astype(np.complex64)
+
+
+def chain_tone_calls(cut):
+    """How many calls j of chain_tone_stream it takes until every slice position has met every residue of c mod 16 that the plan has, per width"""
+    need = set((l, i, c % 16) for c, (f, l) in enumerate(cut) for i in range(len(slice_positions(l))))
+    j = 0
+    while need:
+        need -= set((l, (c + j) % len(slice_positions(l)), c % 16) for c, (f, l) in enumerate(cut))
+        j += 1
+    return j
+
+
+def quantise(stream, bits=16):
+    """(integers (n, 2), scale): the stream on the finest power-of-two grid that keeps its peak inside `bits`-bit integers; the samples a kernel then
+    works on are integers * scale, exact in float32"""
+    s = np.asarray(stream)
+    top = max(float(np.abs(s.real).max()), float(np.abs(s.imag).max()), 1e-30)
+    k = int(np.floor(np.log2((2 ** (bits - 1) - 1) / top)))
+    q = np.stack([np.rint(s.real * 2.0 ** k), np.rint(s.imag * 2.0 ** k)], axis=-1).astype(np.int16 if bits == 16 else np.int8)
+    return q, 2.0 ** -k
 
 
 # ---------------------------------------------------------------- inputs

@@ -13,7 +13,8 @@ r4 on float samples at both lengths, sc16 input at N = 65536 and four integer fo
 
 One case against the oracle: N = 65536 on the grid, three blocks through ONE workgroup (all compute units but one reserved), every sample of every
 channel at the 1e-5 of the other block-kernel tests: the workgroup's second and third block run on a twk read again for each, on rows fetched across
-stage 2."""
+stage 2.  (1e-5 on noise sees a stale or misplaced row, not one slightly wrong table entry — tests/test_fft_model_cpu.py; the byte equality above
+carries the arithmetic of the two-set form over, and tests/test_block_accuracy_gpu.py says what is held to float32-grade error.)"""
 import ctypes as C
 
 import numpy as np

@@ -7,8 +7,10 @@ N = 16384 on the grid and half a slot up at R = 2 launches two workgroups per co
 Either way whatever a pass fetches ahead wraps into a workgroup's next block, and the blocks behind the wrap are among the checked ones.  Checked against
 the oracle with the tolerance of tests/test_parity_gpu.py (relative L2 <= 1e-5 and max-abs / max <= 1e-5): blocks 0 and 1, the two on either side
 of every multiple of the compute-unit count (the grid is one or two workgroups per compute unit), and the last; all channels at N = 16384, every
-16th and the last above.  Every output sample depends on all passes, all eight waves and all four column roles of its block: a wrong table entry
-anywhere shows.
+16th and the last above.  Every output sample depends on all passes, all eight waves and all four column roles of its block: a wrong row, a wrong
+index or a wrong fold shows.  A single table entry that is slightly off (1e-5 rad) does NOT show at 1e-5 on noise (tests/test_fft_model_cpu.py);
+tests/test_block_accuracy_gpu.py holds the forward form of this kernel, which shares these tables, to float32-grade error on impulses, and says what
+is still missing for the channelizing forms.
 
 sc16 in and out: the float output on sc16 input against the oracle (on the widened samples), and the sc16 output byte for byte against the output
 contract (tests/test_iq_output_gpu.py: saturate(rint(y * scale))) applied to that float output."""

@@ -154,3 +154,124 @@ def test_seeded_defect_passes_the_old_criterion_and_fails_the_new(n):
         print("n=%d defect %s: noise L2 %.3g max %.3g; impulses: worst item %.1f x its per-sample bound, %.1f x its L2 bound" % (
             n, defect, l2.max(), mx.max(), worst, r_l2.max() / M.L2_FACTOR))
         assert worst >= 10, (defect, worst)                                                 # the new one: fails, by 10 x at least
+
+
+# ================================================================ the chain: block -> forward N -> shift, 1/N -> channel stage
+# The yardstick of an end-to-end criterion for the kernels that never write a spectrum (fft_model.chain64 / chain32 over the plans and inputs of
+# tests/block_accuracy_cases.py).  What is established here: it is the oracle's chain; a wrong inverse-table entry and a wrong early forward entry
+# that pass 1e-5 on noise end to end stand far above E on the tone and impulse rows.  What could not be established: factors for a per-row bound
+# (block_accuracy_cases.chain_K, profiles/accuracy/README.md).
+import functools                           # noqa: E402
+
+import block_accuracy_cases as BC          # noqa: E402
+
+
+def test_chain_is_the_oracles_chain(oracle):
+    """stream_blocks + chain64 against the oracle's own chain (its double-precision transforms, rounded to float between the blocks) on a stream with
+    a first_block, channel by channel and as one bank call; the four chain32 combinations at float32 grade."""
+    N, R, wt, first = 1024, 4, 2, 7
+    H = N - N // R
+    chans = [(64 * c + 33, 64, 0.6, 0.85) for c in range(15)]
+    x = M.noise(6 * H, 9)
+    outs, _ = oracle.channelizer(N, R, wt, chans, x, first_block=first)
+    win = oracle.window(wt, 64, np.float32(0.6), np.float32(0.85), R)
+    blocks = M.stream_blocks(x, N, R)
+    assert blocks.shape == (6, N) and not blocks[0, :N // R].any() and (blocks[1, :N // R] == x[H - N // R:H]).all()
+    fs = np.array([f for (f, _, _, _) in chans])
+    bank = M.chain64(blocks, N, R, (fs, 64), win, first)
+    assert bank.shape == (6, 15, 48)
+    for c, (f, l, _, _) in enumerate(chans):
+        one = M.chain64(blocks, N, R, (f, l), win, first)
+        assert np.array_equal(one, bank[:, c])
+        l2, mx = M.relative_errors(outs[c].reshape(6, 48), one)
+        assert l2.max() <= 2e-7 and mx.max() <= 4e-7
+    for fwd, inv in M.CHAIN_COMBINATIONS:
+        y = M.chain32(blocks, N, R, (fs, 64), win, first, fwd, inv)
+        assert y.dtype == np.complex64 and y.shape == bank.shape
+        l2, mx = M.relative_errors(y, bank)
+        assert l2.max() <= 4e-7 and mx.max() <= 8e-7
+    e = M.chain_model_error(blocks, N, R, (fs, 64), win, first, bank)
+    assert e[0].shape == e[1].shape == (6, 15) and (e[1] >= e[0]).all() and e[1].max() <= 8e-7
+    assert M.relative_errors(M.chain64(blocks, N, R, (fs, 64), win, first + 1), bank)[0].min() > 1e-2          # the window row matters
+
+
+def test_chain_streams():
+    """the impulse stream puts block m + 1's impulse at impulse_positions(N)[m]; a tone stream's blocks behind the first transform to one impulse per
+    slice; every slice position meets every residue of c mod 16 within chain_tone_calls calls; quantise is exact on its own grid"""
+    N, R = 4096, 4
+    pos = M.impulse_positions(N)
+    blocks = M.stream_blocks(M.chain_impulse_stream(N, R), N, R)
+    assert blocks.shape[0] == len(pos) + 1
+    for m, p in enumerate(pos):
+        assert blocks[m + 1, p] == 1.0
+        assert np.count_nonzero(blocks[m + 1]) <= 3                      # its own, and a neighbour's on either side when that lies in the overlap
+    cut = [(256 * c + 37, 256) for c in range(15)]
+    calls = M.chain_tone_calls(cut)
+    seen = set()
+    for j in range(calls):
+        spec = M.forward64(M.stream_blocks(M.chain_tone_stream(N, R, cut, j), N, R), N)
+        for c, (f, l) in enumerate(cut):
+            k = M.slice_positions(l)[(c + j) % len(M.slice_positions(l))]
+            s = np.abs(spec[1:, f:f + l])
+            assert np.allclose(s[:, k], 1.0, rtol=0, atol=1e-5)
+            s[:, k] = 0
+            assert s.max() <= 1e-5
+            seen.add((k, c % 16))
+    assert seen == set((k, c % 16) for k in M.slice_positions(256) for c in range(15))
+    q, scale = M.quantise(M.noise(1000, 3))
+    assert q.dtype == np.int16 and np.abs(q).max() > 8192
+    again, scale2 = M.quantise((q[:, 0] + 1j * q[:, 1]) * scale)
+    assert scale2 == scale and np.array_equal(again, q)
+
+
+def _worst_over_E(ref_, runs, fwd, inv):
+    """per input kind: (largest relative L2, largest max / max: the suite's present figures; largest rms error / E_rms and largest per-sample error /
+    E_max over the rows more than one ulp off) of the chain with the transforms (fwd, inv)"""
+    out = {}
+    for run in runs:
+        for idx, ref, e, ys in ref_.rows(run, extra=[(fwd, inv)]):
+            l2, mx = M.relative_errors(ys[(fwd, inv)], ref)
+            r_l2, r_max = BC.k_ratios(ys[(fwd, inv)], ref, e)
+            w = out.setdefault(run.kind, [0.0] * 4)
+            out[run.kind] = [max(a, float(b.max())) for a, b in zip(w, (l2, mx, r_l2, r_max))]
+    return out
+
+
+def _fmt(w):
+    return "; ".join("%s: L2 %.2g max %.2g, rms %.1f x E, per sample %.1f x E" % ((k,) + tuple(v)) for k, v in w.items())
+
+
+@pytest.mark.parametrize("which", ["k_blk256 N=65536", "k_f4096 full band"])
+def test_seeded_defect_in_the_chain(oracle, which):
+    """One twiddle entry rotated, in the forward or in the inverse model, end to end over a plan of the block-kernel tests (all channels, every input).
+    Inverse entries (any stage) at 1e-5 rad: noise stays under the suite's 1e-5; the tone rows — one window value times the bare inverse tables —
+    stand at least 16 x above E per sample, twice the largest factor a float32-grade criterion could have (8).
+    Forward entries: only those of the EARLY stages show, the ones that reach many bins of one slice — (stage 1, index 1) at 3e-6 rad passes 1e-5 on
+    noise and is at least 16 x E on an impulse row; an entry of a late stage reaches one bin in 2**stage, at most one per slice, and its 1e-5 arrives in
+    the channel's output divided by about l: it stays within a few E (printed, not asserted: a limit of ANY end-to-end criterion)."""
+    case = {"k_blk256 N=65536": BC.blk256_cases()[8], "k_f4096 full band": BC.fused_cases()[8]}[which]
+    lgN, lgl = case.N.bit_length() - 1, case.chans[0][1].bit_length() - 1
+    ref_ = BC.Reference(case, oracle)
+    runs = list(ref_.runs())
+    for stage, index in ((lgl - 1, 1), (lgl - 1, (1 << lgl) // 4 + 3), (lgl // 2, 1), (1, 1), (lgl - 2, 5)):
+        w = _worst_over_E(ref_, runs, M.fft32_model, functools.partial(M.fft32_model, defect=(stage, index, 1e-5)))
+        print("%s inverse defect %s 1e-5: %s" % (case.id, (stage, index), _fmt(w)))
+        assert w["noise"][0] <= 1e-5 and w["noise"][1] <= 1e-5, (stage, index, w)
+        assert w["tones"][3] >= 16, (stage, index, w)
+    w = _worst_over_E(ref_, runs, functools.partial(M.fft32_model, defect=(1, 1, 3e-6)), M.fft32_model)
+    print("%s forward defect (1, 1) 3e-6: %s" % (case.id, _fmt(w)))
+    assert w["noise"][0] <= 1e-5 and w["noise"][1] <= 1e-5, w
+    assert w["impulses"][3] >= 16, w
+    for stage, index in ((lgN - 1, 1), (lgN // 2, 1)):
+        w = _worst_over_E(ref_, runs, functools.partial(M.fft32_model, defect=(stage, index, 1e-5)), M.fft32_model)
+        print("%s forward defect %s 1e-5 (late stage: diluted by l): %s" % (case.id, (stage, index), _fmt(w)))
+        assert w["noise"][0] <= 1e-5 and w["noise"][1] <= 1e-5, w
+
+
+def test_chain_K_measurement_runs(oracle):
+    """block_accuracy_cases.chain_K (what profiles/accuracy/chain_factors.py prints for every case) on one small plan: it names a row for both figures.
+    The figures themselves are a record, not a bound: see profiles/accuracy/README.md for why no factor follows from them."""
+    pytest.importorskip("scipy.fft")
+    k_rms, row_rms, k_max, row_max = BC.chain_K(BC.fused_cases()[0], oracle)
+    print("CHAIN_K K_rms=%.3f (%s) K_max=%.3f (%s)" % (k_rms, row_rms, k_max, row_max))
+    assert np.isfinite([k_rms, k_max]).all() and k_rms > 0 and k_max > 0 and "block" in row_rms and "block" in row_max
