@@ -135,6 +135,13 @@ SYMBOLS = {
     "fdc_pipeline_tones_device": (_vp, [_vp]),
     "fdc_pipeline_tones_pass_device": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int64, C.c_int32, C.c_int, _vp]),
     "fdc_tone_table": (C.c_int, [C.POINTER(C.c_float)]),
+    "fdc_pipeline_set_tone_squelch": (C.c_int, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int,
+                                                C.c_int32, C.c_int32]),
+    "fdc_pipeline_tone_squelch_setting": (C.c_int, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                                    C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "fdc_pipeline_tone_squelch": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int, C.POINTER(C.c_int32)]),
+    "fdc_pipeline_tone_squelch_device": (_vp, [_vp]),
+    "fdc_pipeline_tone_squelch_pass_device": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int32, C.c_int, _vp]),
     "fdc_pipeline_set_gains": (C.c_int,[_vp, C.POINTER(C.c_float), C.c_int]),
     "fdc_pipeline_gains": (C.c_int, [_vp, C.POINTER(C.c_float), C.c_int]),
     "fdc_pipeline_group_set_gains": (C.c_int, [_vp, C.POINTER(C.c_float), C.c_int]),

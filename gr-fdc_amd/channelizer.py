@@ -538,6 +538,54 @@ def tone_amplitude(Z, frame_samples, freqs_hz, chan_rate_hz, group):
     return np.abs(np.asarray(Z)) / (float(frame_samples) / 2.0) / np.abs(droop)
 
 
+TONE_SQUELCH_MAX_GUARD, TONE_SQUELCH_MAX_HANG = 63, 65535     # include/fdc_amd.h: the guard in tones, the hang count in frames
+
+
+def tone_squelch_thresholds(amplitude, lout, W, S, f, rate):
+    """Thresholds for Pipeline.set_tone_squelch from the AMPLITUDE of the tone in the demodulated stream: the |Z|^2 a tone of that amplitude at f Hz
+    gives over a frame of W blocks of lout samples at `rate` Hz with groups of S, that is (amplitude W lout / 2 droop(f))^2 with the droop
+    tone_amplitude divides by.  amplitude, lout and f broadcast against each other (one value per channel, or a scalar).  Returns float32."""
+    a, lo, fr = np.broadcast_arrays(np.asarray(amplitude, np.float64), np.asarray(lout, np.float64), np.asarray(f, np.float64))
+    if not (np.isfinite(a).all() and np.isfinite(fr).all()) or (a < 0).any() or float(rate) <= 0:
+        raise ValueError("the amplitude must be finite and not negative, the frequency finite and the rate positive")
+    x = np.pi * fr / float(rate)
+    small = np.abs(np.sin(x)) < 1e-12
+    droop = np.where(small, 1.0, np.sin(x * int(S)) / (int(S) * np.where(small, 1.0, np.sin(x))))
+    return ((a * (float(W) * lo / 2.0) * np.abs(droop)) ** 2).astype(np.float32)
+
+
+def _tone_squelch_args(nchan, tone, open_thr, close_thr, ratio, guard, hang):
+    """Pipeline.set_tone_squelch: (int32 tone[C], float32 open[C], float32 close[C], float32 ratio[C], guard, hang), all None / 0 for tone None.  A scalar
+    broadcasts to the channels; close_thr None is open_thr.  Raises before any library call (a tone index at or above the tones' T is the library's
+    to refuse)."""
+    if tone is None:
+        return None, None, None, None, 0, 0
+    t = np.asarray(tone)
+    if t.dtype.kind not in "iu" or t.ndim > 1 or (t.ndim == 1 and t.size != nchan):
+        raise ValueError("the selected tones are integers, one per channel (%d) or a scalar: -1 (not tone-gated) or a tone index" % nchan)
+    if t.size and (t.min() < -1 or t.max() >= TONES_MAX):
+        raise ValueError("a selected tone is outside -1 .. %d" % (TONES_MAX - 1))
+    if open_thr is None:
+        raise ValueError("the tone squelch needs open thresholds")
+    with np.errstate(over="ignore"):            # (a value beyond float32 becomes infinite and is refused below)
+        o = np.asarray(open_thr, dtype=np.float32)
+        c = o if close_thr is None else np.asarray(close_thr, dtype=np.float32)
+        r = np.asarray(ratio, dtype=np.float32)
+    for v in (o, c, r):
+        if v.ndim > 1 or (v.ndim == 1 and v.size != nchan):
+            raise ValueError("the tone squelch's thresholds and ratios are one value per channel (%d) or a scalar" % nchan)
+    t = np.ascontiguousarray(np.broadcast_to(t, (nchan,)), dtype=np.int32)
+    o, c, r = (np.ascontiguousarray(np.broadcast_to(v, (nchan,))) for v in (o, c, r))
+    if not (np.isfinite(o).all() and np.isfinite(c).all() and np.isfinite(r).all()) or (o < 0).any() or (c < 0).any() or (r < 0).any():
+        raise ValueError("the tone squelch's thresholds and ratios must be finite and not negative")
+    if (c > o).any():
+        raise ValueError("a close threshold is above its open threshold (channel %d)" % int(np.flatnonzero(c > o)[0]))
+    for name, v, hi in (("guard", guard, TONE_SQUELCH_MAX_GUARD), ("hang count", hang, TONE_SQUELCH_MAX_HANG)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) <= hi:
+            raise ValueError("the tone squelch's %s is an integer in 0 .. %d" % (name, hi))
+    return t, o, c, r, int(guard), int(hang)
+
+
 class Pipeline(_OutputFormat):
     """fdc_pipeline handle: channels = [(f, l, passbw, stopbw), ...]."""
     _last_nb = None        # block count of the last work call that had blocks (levels())
@@ -881,6 +929,70 @@ class Pipeline(_OutputFormat):
         process_device's layout, blocks first_block .. of a stream with `fill` blocks already in the open frame; d_frames: ((fill + nblocks) // W) C T
         float32 pairs; d_carry_in: C T pairs or None, d_carry_out: another such buffer).  The handle's own state and stream position are not touched."""
         _lib.check(_lib.lib().fdc_pipeline_tones_pass_device(self._h, d_in, d_frames, d_carry_in, d_carry_out, int(first_block), int(fill), int(nblocks), stream))
+
+    def set_tone_squelch(self, tone, open_thr=None, close_thr=None, ratio=0.0, guard=0, hang=0):
+        """fdc_pipeline_set_tone_squelch: tone None switches it off; else per channel (or a scalar for all) the index of the selected tone among the
+        tones' T (-1: the channel is not tone-gated), thresholds on |Z|^2 of that tone's frame rows (tone_squelch_thresholds converts from an
+        amplitude), close_thr (default: open_thr) not above open_thr, and a ratio the selected tone must keep over the strongest tone more than
+        `guard` places away; hang 0 .. 65535 FRAMES.  It needs the tones (set_tones) and the squelch (set_squelch) and decides on the device, per
+        completed frame, by the squelch's own state machine (tests/tone_squelch_model.py); the decision of the frame BEFORE gates the carrier mask, so
+        squelch(), the gated audio and the packed audio see carrier AND tone.  tone_squelch() gives the decisions of the frames the last call
+        completed.  The state goes on exactly where the tones' stream does; a new setting restarts it.  A setting: it applies from the next call and
+        survives reset().  ValueError for arguments out of range (nothing reaches the library), FdcError where the library refuses (tones or squelch
+        off, a tone index at or above T, a pipelined sinks batch inside); nothing changes then."""
+        t, o, c, r, g, h = _tone_squelch_args(len(self.channels), tone, open_thr, close_thr, ratio, guard, hang)
+        if t is not None and t.size == 0:         # (a plan without channels: pointers that are not NULL, which means off)
+            t, o = np.zeros(1, np.int32), np.zeros(1, np.float32)
+            c = r = o
+        fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
+        if t is None:
+            _lib.check(_lib.lib().fdc_pipeline_set_tone_squelch(self._h, None, None, None, None, len(self.channels), 0, 0))
+        else:
+            _lib.check(_lib.lib().fdc_pipeline_set_tone_squelch(self._h, t.ctypes.data_as(ip), o.ctypes.data_as(fp), c.ctypes.data_as(fp), r.ctypes.data_as(fp),
+                                                                len(self.channels), g, h))
+
+    def tone_squelch_setting(self):
+        """fdc_pipeline_tone_squelch_setting: None while off, else (int32 tone[C], float32 open[C], float32 close[C], float32 ratio[C], guard, hang):
+        what the library has in force now."""
+        g, h = C.c_int32(0), C.c_int32(0)
+        _lib.check(_lib.lib().fdc_pipeline_tone_squelch_setting(self._h, None, None, None, None, C.byref(g), C.byref(h)))
+        if h.value < 0:
+            return None
+        n = len(self.channels)
+        t, o, c, r = np.zeros(max(1, n), np.int32), np.zeros(max(1, n), np.float32), np.zeros(max(1, n), np.float32), np.zeros(max(1, n), np.float32)
+        fp = C.POINTER(C.c_float)
+        _lib.check(_lib.lib().fdc_pipeline_tone_squelch_setting(self._h, t.ctypes.data_as(C.POINTER(C.c_int32)), o.ctypes.data_as(fp), c.ctypes.data_as(fp),
+                                                                r.ctypes.data_as(fp), None, None))
+        return t[:n], o[:n], c[:n], r[:n], int(g.value), int(h.value)
+
+    def tone_squelch(self, nblocks=None):
+        """fdc_pipeline_tone_squelch: the decisions of the frames the last call completed, uint8 [nf, C]: 1 where the channel's tone squelch is open
+        behind that frame (nf may be 0).  nblocks: the last call's block count where it did not go through this object's work methods."""
+        if nblocks is None:
+            if self._last_nb is None:
+                raise ValueError("tone_squelch(): no work call yet")
+            nblocks = self._last_nb
+        nblocks = int(nblocks)
+        if nblocks < 0:
+            raise ValueError("tone_squelch(): negative block count")
+        if self.tone_squelch_setting() is None:
+            raise ValueError("tone_squelch(): the tone squelch is off (set_tone_squelch)")
+        w = self.tones_setting()[2]
+        out = np.empty(((nblocks + w - 1) // w, len(self.channels)), dtype=np.uint8)       # (the most a call of nblocks can complete)
+        nf = C.c_int32(0)
+        if nblocks:
+            _lib.check(_lib.lib().fdc_pipeline_tone_squelch(self._h, out.ctypes.data, out.nbytes, nblocks, C.byref(nf)))
+        return out[:nf.value].copy()
+
+    def tone_squelch_device(self):
+        """fdc_pipeline_tone_squelch_device: the device address of the decisions ([frame of the last call][C] bytes), None while it is off."""
+        return _lib.lib().fdc_pipeline_tone_squelch_device(self._h)
+
+    def tone_squelch_pass_device(self, d_frames, d_dec, nblocks, fill=0, d_state_in=None, d_state_out=None, d_mask=None, stream=None):
+        """fdc_pipeline_tone_squelch_pass_device: the decision and the gate alone on device buffers of the caller, with the setting in force (d_frames:
+        ((fill + nblocks) // W) C T float32 pairs, d_dec: that many times C bytes, d_state_in: C int32 pairs (open, h) or None, d_state_out: another such
+        buffer, d_mask: nblocks C bytes ANDed in place, or None for the decision alone).  The handle's own state is not touched."""
+        _lib.check(_lib.lib().fdc_pipeline_tone_squelch_pass_device(self._h, d_frames, d_dec, d_state_in, d_state_out, d_mask, int(fill), int(nblocks), stream))
 
     def _host_outs(self, outs, nb):
         """(outs, ptrs) of a host call.  While the channel audio is on — asked of the library at this call — the entries write no port: (None, None),
@@ -1257,7 +1369,8 @@ class FrequencyDomainChannelizer:
                  debug, device_id=0, max_blocks=64, devices=None, pipelined=False, waterfall=None, iq_input=None, iq_scale=1.0,
                  iq_output=None, iq_output_scale=1.0, fine_tuning=False, *, payload_format=None, payload_scale=1.0, levels=False, gains=None, lag1=False,
                  demod=None, demod_gain=1.0, audio_decim=None, audio_taps=None, audio_format="f32", audio_scale=1.0, squelch_db=None, squelch_close_db=None,
-                 squelch_hang=0, audio_packed=False, tones=None, tone_group=16, tone_frame=32):
+                 squelch_hang=0, audio_packed=False, tones=None, tone_group=16, tone_frame=32, tone_squelch=None, tone_open=None,
+                 tone_close=None, tone_ratio=0.0, tone_guard=0, tone_hang=0):
         # pipelined (not an argument of the reference): the sink blocks run beside the front end of the FOLLOWING work() calls, as the
         # thread-per-block scheduler runs them beside the FFT in the reference (fdc_pipeline_work_sinks on a look-ahead bank,
         # include/fdc_amd.h): same PDUs, handed out one or two work() calls later; flush() at the end of the stream
@@ -1440,6 +1553,22 @@ class FrequencyDomainChannelizer:
                 raise ValueError("tones needs demod: the tone bank runs behind the channel demodulation")
             self.tone_inc = _tones_args(len(self.throughput_channels), tones, tone_group, tone_frame)[0]
 
+        # tone_squelch / tone_open / tone_close / tone_ratio / tone_guard / tone_hang (not arguments of the reference): a tone squelch per throughput
+        # channel, decided on the device from the tones' frame rows (Pipeline.set_tone_squelch): tone_squelch is the index of the selected tone per
+        # channel (or one for all; -1: not tone-gated), tone_open / tone_close thresholds on |Z|^2 (tone_squelch_thresholds), tone_ratio what the tone
+        # must keep over the strongest tone more than tone_guard places away, tone_hang the hang count in frames.  self.squelch is then carrier AND
+        # tone, and after every work() self.tone_squelch_dec is uint8 [frames the call completed, throughput channels].  It needs tones and squelch_db
+        self.tone_squelch = None
+        self.tone_squelch_dec = None
+        if tone_squelch is not None:
+            if tones is None or squelch_db is None:
+                raise ValueError("tone_squelch needs tones and squelch_db: it decides on the tones' frame rows and gates the squelch's mask")
+            self.tone_squelch = _tone_squelch_args(len(self.throughput_channels), tone_squelch, tone_open, tone_close, tone_ratio, tone_guard, tone_hang)
+            if self.tone_squelch[0].size and int(self.tone_squelch[0].max()) >= self.tone_inc.shape[1]:
+                raise ValueError("tone_squelch selects tone %d of %d" % (int(self.tone_squelch[0].max()), self.tone_inc.shape[1]))
+        elif tone_open is not None or tone_close is not None or tone_ratio or tone_guard or tone_hang:
+            raise ValueError("tone_open, tone_close, tone_ratio, tone_guard and tone_hang need tone_squelch")
+
         # gains (not an argument of the reference): one output gain per throughput channel, applied on the device behind fine tuning and in front of the
         # levels and of iq_output's narrowing (Pipeline.set_gains); set_gains() changes them between work() calls (an AGC fed from self.levels)
         self.gains = None if gains is None else _check_gains(len(self.throughput_channels), gains)
@@ -1522,6 +1651,8 @@ class FrequencyDomainChannelizer:
             self.pipeline.set_audio_packing(True)
         if self.tone_inc is not None:
             self.pipeline.set_tones(self.tone_inc, self.tone_group, self.tone_frame)
+        if self.tone_squelch is not None:
+            self.pipeline.set_tone_squelch(*self.tone_squelch)
         self.N_throughput_channelizers = len(self.channel_params)
         # waterfall (not an argument of the reference, whose example flowgraph wires the spectrum to complex_to_mag_squared and
         # FDC.WaterfallMsgTagging outside the hier block): a gr_fdc_amd.Waterfall fed from the spectrum on the device; work() then
@@ -1605,6 +1736,9 @@ class FrequencyDomainChannelizer:
         if self.tone_inc is not None:
             self.tones = (self.pipeline.tones() if self.pipeline._call_nb > 0
                           else np.empty((0, len(self.channel_params), self.tone_inc.shape[1]), dtype=np.complex64))
+        if self.tone_squelch is not None:
+            self.tone_squelch_dec = (self.pipeline.tone_squelch() if self.pipeline._call_nb > 0
+                                     else np.empty((0, len(self.channel_params)), dtype=np.uint8))
         if self.debug:
             outs, spec = res
             return [spec] + outs

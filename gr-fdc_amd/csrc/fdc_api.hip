@@ -415,6 +415,7 @@ int32_t fdc_pipeline_describe(const fdc_pipeline *p, char *buf, int32_t n)
     if (!p->audio_route.empty()) add("; audio: %s", p->audio_route.c_str());
     if (!p->squelch_route.empty()) add("; squelch: %s", p->squelch_route.c_str());
     if (!p->tones_route.empty()) add("; tones: %s", p->tones_route.c_str());
+    if (!p->tsq_route.empty()) add("; tone squelch: %s", p->tsq_route.c_str());
     std::snprintf(buf, (size_t)n, "%s", t);
     return k;
 }
@@ -497,6 +498,8 @@ void fdc_pipeline_reset(fdc_pipeline *p)
     p->tones_route.clear();      // (and the channel tones: no frame is open)
     p->tones_next = -1;
     p->tones_fill = 0;
+    p->tsq_route.clear();        // (and the tone squelch, which goes on where the tones do: every channel starts closed again)
+    p->tsq_valid = false;
 }
 
 int fdc_pipeline_set_output_format(fdc_pipeline *p, int32_t format, float scale)
@@ -960,6 +963,8 @@ int fdc_pipeline_set_squelch(fdc_pipeline *p, const float *open_thr, const float
     }
     if (p->hier_filled > 0)
         return set_error(FDC_ERR_INVALID_ARGUMENT, "a pipelined sinks batch is still inside the handle: fdc_pipeline_flush_sinks until it returns 0 first");
+    if (!open_thr && p->tsq_on)
+        return set_error(FDC_ERR_INVALID_ARGUMENT, "the tone squelch gates the squelch's mask: switch the tone squelch off first (fdc_pipeline_set_tone_squelch(p, NULL, ...))");
     if (!open_thr && p->pack_on)
         return set_error(FDC_ERR_INVALID_ARGUMENT, "the audio packing packs by the squelch's mask: switch the packing off first (fdc_pipeline_set_audio_packing(p, 0))");
     if (open_thr && !p->levels_on)
@@ -1063,6 +1068,9 @@ int fdc_pipeline_set_tones(fdc_pipeline *p, const uint32_t *inc, int nchan, int 
     }
     if (p->hier_filled > 0)
         return set_error(FDC_ERR_INVALID_ARGUMENT, "a pipelined sinks batch is still inside the handle: fdc_pipeline_flush_sinks until it returns 0 first");
+    if (p->tsq_on && (!inc || ntones != p->tones_T || group != p->tones_S || frame_blocks != p->tones_W))
+        return set_error(FDC_ERR_INVALID_ARGUMENT, "the tone squelch decides on the frame rows of %d tones, groups of %d and frames of %d blocks: switch the tone "
+                         "squelch off first (fdc_pipeline_set_tone_squelch(p, NULL, ...))", p->tones_T, p->tones_S, p->tones_W);
     if (inc && !p->demod_mode)
         return set_error(FDC_ERR_INVALID_ARGUMENT, "the channel tones correlate the demodulated samples: switch the channel demodulation on first (fdc_pipeline_set_demod)");
     for (int c = 0; inc && c < p->C; c++)
@@ -1161,6 +1169,132 @@ int fdc_pipeline_tones_pass_device(const fdc_pipeline *p, const void *d_in, void
     HIPCHK(fdc::launch_chan_tones(static_cast<const float *>(d_in), p->d_chans, p->d_tinc, p->d_ttab, static_cast<const float2 *>(d_carry_in),
                                   static_cast<float2 *>(d_carry_out), static_cast<float2 *>(d_frames), p->C, p->tones_T, p->tones_S, p->tones_W, fill,
                                   (long long)first_block, nblocks, stream ? static_cast<hipStream_t>(stream) : p->stream));
+    return FDC_OK;
+    FDC_ENTRY_END
+}
+
+// the tone squelch: a setting that needs the tones and the squelch; everything it needs is allocated here, once, and every new setting restarts its
+// state (not the tones' frames)
+int fdc_pipeline_set_tone_squelch(fdc_pipeline *p, const int32_t *tone, const float *open_thr, const float *close_thr, const float *ratio, int n,
+                                  int32_t guard, int32_t hang_frames)
+{
+    FDC_ENTRY("fdc_pipeline_set_tone_squelch")
+    if (!p) return set_error(FDC_ERR_INVALID_ARGUMENT, "null handle");
+    if (n != p->C) return set_error(FDC_ERR_INVALID_ARGUMENT, "tone squelch: a setting for %d channels of %d", n, p->C);
+    if (p->hier_filled > 0)
+        return set_error(FDC_ERR_INVALID_ARGUMENT, "a pipelined sinks batch is still inside the handle: fdc_pipeline_flush_sinks until it returns 0 first");
+    if (tone) {
+        if (!open_thr || !close_thr || !ratio) return set_error(FDC_ERR_INVALID_ARGUMENT, "tone squelch: no thresholds or ratios");
+        if (!p->tones_T) return set_error(FDC_ERR_INVALID_ARGUMENT, "the tone squelch decides on the tones' frame rows: switch the channel tones on first (fdc_pipeline_set_tones)");
+        if (!p->squelch_on) return set_error(FDC_ERR_INVALID_ARGUMENT, "the tone squelch gates the squelch's mask: switch the channel squelch on first (fdc_pipeline_set_squelch)");
+        if (guard < 0 || guard > 63) return set_error(FDC_ERR_INVALID_ARGUMENT, "tone squelch: the guard %d is not in 0 .. 63", (int)guard);
+        if (hang_frames < 0 || hang_frames > 65535) return set_error(FDC_ERR_INVALID_ARGUMENT, "tone squelch: the hang count %d is not in 0 .. 65535 frames", (int)hang_frames);
+        for (int c = 0; c < p->C; c++) {
+            if (tone[c] < -1 || tone[c] >= p->tones_T)
+                return set_error(FDC_ERR_INVALID_ARGUMENT, "tone squelch: the tone %d of channel %d is not in -1 .. %d", (int)tone[c], c, p->tones_T - 1);
+            if (!std::isfinite(open_thr[c]) || !std::isfinite(close_thr[c]) || !std::isfinite(ratio[c]) || open_thr[c] < 0.0f || close_thr[c] < 0.0f || ratio[c] < 0.0f)
+                return set_error(FDC_ERR_INVALID_ARGUMENT, "tone squelch: the thresholds and the ratio of channel %d are not finite and >= 0", c);
+            if (close_thr[c] > open_thr[c])
+                return set_error(FDC_ERR_INVALID_ARGUMENT, "tone squelch: the close threshold of channel %d is above its open threshold", c);
+        }
+    }
+    HIPCHK(hipSetDevice(p->cfg.device_id));
+    HIPCHK(hipStreamSynchronize(p->stream));          // (no call of the host entries is in flight; a device entry's caller orders its own stream)
+    if (!tone) {
+        p->tsq_on = false; p->tsq_tone.clear(); p->tsq_open.clear(); p->tsq_close.clear(); p->tsq_ratio.clear(); p->tsq_guard = p->tsq_hang = 0;
+        p->tsq_valid = false; p->tsq_blocks = -1; p->tsq_frames = 0; p->tsq_route.clear();
+        return FDC_OK;
+    }
+    // everything the feature needs, once: the tone indices, three tables of thresholds, the two states, the decisions of the longest call from the
+    // deepest fill on and their pinned twin
+    const size_t nc = (size_t)p->C;
+    const size_t nd = (((size_t)p->tones_W - 1 + (size_t)p->cfg.max_blocks) / (size_t)p->tones_W) * nc;
+    if (nc > 0 && !p->d_tsqtone) HIPCHK(p->d_tsqtone.alloc(nc));
+    for (int i = 0; i < 3; i++)
+        if (nc > 0 && !p->d_tsqthr[i]) HIPCHK(p->d_tsqthr[i].alloc(nc));
+    for (int i = 0; i < 2; i++)
+        if (nc > 0 && !p->d_tsqstate[i]) HIPCHK(p->d_tsqstate[i].alloc(2 * nc));
+    if (nd > p->d_tdec.capacity()) HIPCHK(p->d_tdec.reserve(nd, nd));
+    if (nd > p->pin_tdec.capacity()) HIPCHK(p->pin_tdec.reserve(nd, nd));
+    if (nc > 0) {
+        HIPCHK(hipMemcpy(p->d_tsqtone, tone, sizeof(int32_t) * nc, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(p->d_tsqthr[0], open_thr, sizeof(float) * nc, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(p->d_tsqthr[1], close_thr, sizeof(float) * nc, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(p->d_tsqthr[2], ratio, sizeof(float) * nc, hipMemcpyHostToDevice));
+    }
+    p->tsq_tone.assign(tone, tone + nc);
+    p->tsq_open.assign(open_thr, open_thr + nc);
+    p->tsq_close.assign(close_thr, close_thr + nc);
+    p->tsq_ratio.assign(ratio, ratio + nc);
+    p->tsq_guard = guard; p->tsq_hang = hang_frames;
+    p->tsq_valid = false; p->tsq_blocks = -1; p->tsq_frames = 0;      // a new setting: every channel starts closed, no call has decisions yet
+    p->tsq_on = true;
+    return FDC_OK;
+    FDC_ENTRY_END
+}
+
+int fdc_pipeline_tone_squelch_setting(const fdc_pipeline *p, int32_t *tone, float *open_thr, float *close_thr, float *ratio, int32_t *guard,
+                                      int32_t *hang_frames)
+{
+    FDC_ENTRY("fdc_pipeline_tone_squelch_setting")
+    if (!p) return set_error(FDC_ERR_INVALID_ARGUMENT, "null handle");
+    if (guard) *guard = p->tsq_on ? p->tsq_guard : -1;
+    if (hang_frames) *hang_frames = p->tsq_on ? p->tsq_hang : -1;
+    if (tone) std::copy(p->tsq_tone.begin(), p->tsq_tone.end(), tone);
+    if (open_thr) std::copy(p->tsq_open.begin(), p->tsq_open.end(), open_thr);
+    if (close_thr) std::copy(p->tsq_close.begin(), p->tsq_close.end(), close_thr);
+    if (ratio) std::copy(p->tsq_ratio.begin(), p->tsq_ratio.end(), ratio);
+    return FDC_OK;
+    FDC_ENTRY_END
+}
+
+// the decisions of the frames the last call completed: never more than the caller says its buffer holds
+int fdc_pipeline_tone_squelch(fdc_pipeline *p, uint8_t *dst, size_t capacity_bytes, int nblocks, int32_t *nframes)
+{
+    FDC_ENTRY("fdc_pipeline_tone_squelch")
+    if (!p) return set_error(FDC_ERR_INVALID_ARGUMENT, "null handle");
+    if (!p->tsq_on) return set_error(FDC_ERR_INVALID_ARGUMENT, "the tone squelch is off (fdc_pipeline_set_tone_squelch)");
+    if (p->tsq_blocks < 0) return set_error(FDC_ERR_INVALID_ARGUMENT, "no work call has run since the tone squelch was switched on or its setting changed");
+    if (nblocks != p->tsq_blocks) return set_error(FDC_ERR_INVALID_ARGUMENT, "the last work call had %d blocks, not %d", p->tsq_blocks, nblocks);
+    const size_t n = (size_t)p->tsq_frames * (size_t)p->C;
+    if (capacity_bytes < n)
+        return set_error(FDC_ERR_INVALID_ARGUMENT, "the decisions of the %d frames of the last call take %zu bytes, the buffer holds %zu", p->tsq_frames, n, capacity_bytes);
+    if (nframes) *nframes = p->tsq_frames;
+    if (n == 0) return FDC_OK;
+    if (!dst) return set_error(FDC_ERR_INVALID_ARGUMENT, "null argument");
+    if (!p->tsq_host) {
+        // a device entry's decisions: read behind everything enqueued so far on the stream it ran on
+        HIPCHK(hipSetDevice(p->cfg.device_id));
+        HIPCHK(hipMemcpyAsync(p->pin_tdec.get(), p->d_tdec.get(), n, hipMemcpyDeviceToHost, p->tsq_stream));
+        HIPCHK(hipStreamSynchronize(p->tsq_stream));
+        p->tsq_host = true;
+    }
+    std::memcpy(dst, p->pin_tdec.get(), n);
+    return FDC_OK;
+    FDC_ENTRY_END
+}
+
+void *fdc_pipeline_tone_squelch_device(fdc_pipeline *p) { return p && p->tsq_on ? static_cast<void *>(p->d_tdec.get()) : nullptr; }
+
+// the decision and the gate alone, on the caller's device buffers: the handle gives its setting, the tones' T and W and its channel count, nothing of
+// its stream state
+int fdc_pipeline_tone_squelch_pass_device(const fdc_pipeline *p, const void *d_frames, void *d_dec, const void *d_state_in, void *d_state_out, void *d_mask,
+                                          int32_t fill, int nblocks, void *stream)
+{
+    FDC_ENTRY("fdc_pipeline_tone_squelch_pass_device")
+    if (!p) return set_error(FDC_ERR_INVALID_ARGUMENT, "null handle");
+    if (!p->tsq_on) return set_error(FDC_ERR_INVALID_ARGUMENT, "the tone squelch is off (fdc_pipeline_set_tone_squelch)");
+    if (nblocks < 0) return set_error(FDC_ERR_INVALID_ARGUMENT, "negative block count");
+    if (fill < 0 || fill >= p->tones_W) return set_error(FDC_ERR_INVALID_ARGUMENT, "the fill %d is not in 0 .. %d, the frame length - 1", (int)fill, p->tones_W - 1);
+    if (nblocks == 0 || p->C <= 0) return FDC_OK;
+    const bool rows = ((int64_t)fill + nblocks) / p->tones_W > 0;
+    if (!d_state_out || (rows && (!d_frames || !d_dec))) return set_error(FDC_ERR_INVALID_ARGUMENT, "null device buffer");
+    if (d_state_in == d_state_out) return set_error(FDC_ERR_INVALID_ARGUMENT, "the state is read from one buffer and written to another");
+    HIPCHK(hipSetDevice(p->cfg.device_id));
+    HIPCHK(fdc::launch_tone_squelch(static_cast<const float2 *>(d_frames), p->d_tsqtone, p->d_tsqthr[0], p->d_tsqthr[1], p->d_tsqthr[2], p->tsq_guard, p->tsq_hang,
+                                    static_cast<const int *>(d_state_in), static_cast<int *>(d_state_out), static_cast<unsigned char *>(d_dec),
+                                    static_cast<unsigned char *>(d_mask), p->C, p->tones_T, p->tones_W, fill, nblocks,
+                                    stream ? static_cast<hipStream_t>(stream) : p->stream));
     return FDC_OK;
     FDC_ENTRY_END
 }

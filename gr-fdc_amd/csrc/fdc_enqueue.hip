@@ -184,6 +184,9 @@ struct PostPass {
                                 // first completed frame row goes)
     bool tones_cont = false;    //   ... the call continues the tones' stream: the handle's accumulators stand in front of its first block ...
     int tones_fill = 0;         //   ... which is block tones_fill of the open frame (0 where the stream starts anew)
+    unsigned char *tone_dec = nullptr;  // the call-wide k_tone_decide and k_tone_gate behind the tones and in front of the offsets and the audio: the tone squelch
+                                // on (where the decisions of the call's first completed frame go).  It changes the order of the tail (run_post_tail)
+    bool tsq_cont = false;      //   ... the call continues the tones' stream and the handle's tone-squelch state is valid
 };
 
 static PostPass post_pass(const fdc_pipeline *p, const DeviceCall &call, bool ofused)
@@ -205,6 +208,7 @@ static PostPass post_pass(const fdc_pipeline *p, const DeviceCall &call, bool of
     pp.squelch = pp.levels ? call.squelch : nullptr;
     pp.pack_off = pp.audio && pp.squelch ? call.pack_off : nullptr;
     pp.tones = pp.demod ? call.tones : nullptr;
+    pp.tone_dec = pp.tones && pp.squelch ? call.tone_dec : nullptr;
     return pp;
 }
 
@@ -236,10 +240,25 @@ static int run_post_tail(fdc_pipeline *p, const DeviceCall &call, const PostPass
         p->sqstate_cur ^= 1; p->squelch_next = first_block + nblocks;
         p->squelch_route = "pass";
     }
-    if (pp.pack_off)
-        // ... and of the mask the offsets of the call's cells: from the running total on where the call appends to a host call's packed buffer
+    // ... and of the mask the offsets of the call's cells: from the running total on where the call appends to a host call's packed buffer
+    auto pack_offsets = [&]() -> int {
         HIPCHK(fdc::launch_audio_pack_offsets(pp.squelch, p->d_chans, p->audio_decim, call.pack_append ? p->d_packtotal.get() : nullptr, pp.pack_off,
                                               p->d_packtotal, p->C, nblocks, call.stream));
+        return FDC_OK;
+    };
+    // the tone bank over the demodulated samples, ungated: the open frame's accumulators are read from one buffer and written to the other, which
+    // is the handle's behind the enqueue, with the blocks now inside the open frame, for the call that goes on at the next block
+    auto tones = [&]() -> int {
+        HIPCHK(fdc::launch_chan_tones(static_cast<const float *>(d_out), p->d_chans, p->d_tinc, p->d_ttab, pp.tones_cont ? p->d_tcarry[p->tcarry_cur].get() : nullptr,
+                                      p->d_tcarry[p->tcarry_cur ^ 1].get(), pp.tones, p->C, p->tones_T, p->tones_S, p->tones_W, pp.tones_fill, (long long)first_block,
+                                      nblocks, call.stream));
+        p->tcarry_cur ^= 1; p->tones_next = first_block + nblocks; p->tones_fill = (pp.tones_fill + nblocks) % p->tones_W;
+        p->tones_route = "pass";
+        return FDC_OK;
+    };
+    // WITHOUT the tone squelch the order is squelch, offsets, demodulation, audio, tones.  WITH it the offsets and the audio must see the combined mask,
+    // which needs the call's frame rows: squelch, demodulation, tones, the decision and the gate, offsets, audio
+    if (pp.pack_off && !pp.tone_dec) RCCHK(pack_offsets());
     if (pp.demod) {
         // FM reads one carry buffer and writes the other; behind the enqueue the written one is the handle's, for the call that goes on at the next block
         const bool fm = pp.demod == FDC_DEMOD_FM;
@@ -248,6 +267,17 @@ static int run_post_tail(fdc_pipeline *p, const DeviceCall &call, const PostPass
                                       p->C, nblocks, (long long)p->sum_lout, call.stream));
         if (fm) { p->carry_cur ^= 1; p->demod_next = first_block + nblocks; }
         p->demod_route = fm ? "fm" : "mag";
+    }
+    if (pp.tone_dec) {
+        RCCHK(tones());
+        // the decision over the frame rows the tones have just completed, and the carrier mask combined with the decision in force at each block.  The state
+        // is read from one buffer (by both kernels) and written to the other, which is the handle's behind the enqueue
+        HIPCHK(fdc::launch_tone_squelch(pp.tones, p->d_tsqtone, p->d_tsqthr[0], p->d_tsqthr[1], p->d_tsqthr[2], p->tsq_guard, p->tsq_hang,
+                                        pp.tsq_cont ? p->d_tsqstate[p->tsqstate_cur].get() : nullptr, p->d_tsqstate[p->tsqstate_cur ^ 1].get(), pp.tone_dec,
+                                        pp.squelch, p->C, p->tones_T, p->tones_W, pp.tones_fill, nblocks, call.stream));
+        p->tsqstate_cur ^= 1; p->tsq_valid = true;
+        p->tsq_route = "pass";
+        if (pp.pack_off) RCCHK(pack_offsets());
     }
     if (pp.audio) {
         // the demodulated samples are where the demodulation has just written them; the history is read from one buffer and written to the other,
@@ -260,15 +290,7 @@ static int run_post_tail(fdc_pipeline *p, const DeviceCall &call, const PostPass
         p->ahist_cur ^= 1; p->audio_next = first_block + nblocks;
         p->audio_route = pp.pack_off ? "pass, gated, packed" : pp.squelch ? "pass, gated" : "pass";
     }
-    if (pp.tones) {
-        // the tone bank over the same demodulated samples, ungated: the open frame's accumulators are read from one buffer and written to the other, which
-        // is the handle's behind the enqueue, with the blocks now inside the open frame, for the call that goes on at the next block
-        HIPCHK(fdc::launch_chan_tones(static_cast<const float *>(d_out), p->d_chans, p->d_tinc, p->d_ttab, pp.tones_cont ? p->d_tcarry[p->tcarry_cur].get() : nullptr,
-                                      p->d_tcarry[p->tcarry_cur ^ 1].get(), pp.tones, p->C, p->tones_T, p->tones_S, p->tones_W, pp.tones_fill, (long long)first_block,
-                                      nblocks, call.stream));
-        p->tcarry_cur ^= 1; p->tones_next = first_block + nblocks; p->tones_fill = (pp.tones_fill + nblocks) % p->tones_W;
-        p->tones_route = "pass";
-    }
+    if (pp.tones && !pp.tone_dec) RCCHK(tones());
     if (pp.narrow_tail) HIPCHK(fdc::launch_complex_to_iq(call.ofmt, call.oscale, call.fout, d_out, (size_t)nblocks * p->sum_lout, call.stream));
     if (pp.fine_fused || pp.rotate) p->fine_route = pp.fine_fused ? "fused" : "rotated";
     if (pp.levels) p->levels_route = pp.rot_levels ? "with the rotation" : pp.gain_pass ? "with the gains" : "pass";
@@ -326,6 +348,11 @@ int process_device_impl(fdc_pipeline *p, DeviceCall &call, const void *d_ring, i
         pp.tones_cont = p->tones_next == first_block;
         pp.tones_fill = pp.tones_cont ? p->tones_fill : 0;
         p->tones_next = -1;
+    }
+    if (pp.tone_dec) {
+        // ... and the tone squelch goes on exactly where the tones do, unless its setting is new
+        pp.tsq_cont = pp.tones_cont && p->tsq_valid;
+        p->tsq_valid = false;
     }
     // path 5: the call's part of every group's launch (the group's: its input, its blocks and its waterfall rows)
     fdc::F4Launch f4{};
@@ -480,6 +507,11 @@ void tones_written(fdc_pipeline *p, int nblocks, int nframes, hipStream_t stream
     p->tn_blocks = nblocks; p->tn_frames = nframes; p->tn_stream = stream; p->tn_host = host;
 }
 
+void tone_squelch_written(fdc_pipeline *p, int nblocks, int nframes, hipStream_t stream, bool host)
+{
+    p->tsq_blocks = nblocks; p->tsq_frames = nframes; p->tsq_stream = stream; p->tsq_host = host;
+}
+
 // how the last integer-input / integer-output call was served (fdc_pipeline_describe): "<sc16|sc8>: fused", or what it was instead
 std::string route(int fmt, bool fused, const char *otherwise)
 {
@@ -509,6 +541,7 @@ static int process_device_oq(fdc_pipeline *p, DeviceCall &call, const void *d_ri
         call.squelch = squelch_rows(p, 0);      // (the mask goes to the handle's buffer, [max_blocks][C]: the check above covers it)
     }
     if (call.audio && call.squelch && packing_on(p)) { call.audio = p->d_audio.get(); call.pack_off = pack_rows(p, 0); call.pack_append = false; }
+    if (call.tones && call.squelch) call.tone_dec = tone_dec_rows(p, 0);   // (the decisions go to the handle's buffer, a byte per frame row of the tones')
     const bool lag = p->lag1_on && nblocks > 0;
     if (lag) {
         if (nblocks > p->cfg.max_blocks) return set_error(FDC_ERR_INVALID_ARGUMENT, "channel lag-1 correlation: nblocks %d above max_blocks %d", nblocks, p->cfg.max_blocks);
@@ -529,6 +562,7 @@ static int process_device_oq(fdc_pipeline *p, DeviceCall &call, const void *d_ri
     if (rc == FDC_OK && call.audio) audio_written(p, nblocks, call.stream, false);
     if (rc == FDC_OK && call.squelch) squelch_written(p, nblocks, call.stream, false);
     if (rc == FDC_OK && call.tones) tones_written(p, nblocks, call.tones_frames, call.stream, false);
+    if (rc == FDC_OK && call.tone_dec) tone_squelch_written(p, nblocks, call.tones_frames, call.stream, false);
     return rc;
 }
 

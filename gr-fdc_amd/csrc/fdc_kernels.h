@@ -304,6 +304,16 @@ void tone_table(float2 *dst);       // host: (cos, sin)(2 pi k / kToneTable), de
 hipError_t launch_chan_tones(const float *in, const ChanDev *chans, const unsigned *inc, const float2 *tab, const float2 *carry_in, float2 *carry_out,
                              float2 *frames, int nchan, int ntones, int group, int frame_blocks, int fill, long long first_block, int nb_call, hipStream_t s);
 
+// Tone squelch (fdc_pipeline_set_tone_squelch; fdc_tonesquelch.hip): the decision over the (fill + nb_call) div frame_blocks frame rows the call's tones
+// pass completed (`frames`, launch_chan_tones' own; null where it completed none), one byte per (frame, channel) to dec ([frame][nchan]); then, unless
+// mask is null, the call's carrier mask ([nb_call][nchan], launch_chan_squelch's) ANDed in place with the decision in force at each block: state_in's
+// open for the blocks of the frame that was open in front of the call, dec of the frame before otherwise.  tone: [nchan], -1 = the channel is not
+// tone-gated; thr_open / thr_close / ratio: [nchan].  state_in ([nchan][2] int: open, h; null: all closed), state_out (another buffer) as the squelch's,
+// h counting frames.  tests/tone_squelch_model.py is the rule
+hipError_t launch_tone_squelch(const float2 *frames, const int *tone, const float *thr_open, const float *thr_close, const float *ratio, int guard, int hang,
+                               const int *state_in, int *state_out, unsigned char *dec, unsigned char *mask, int nchan, int ntones, int frame_blocks,
+                               int fill, int nb_call, hipStream_t s);
+
 hipError_t launch_scale(const float2 *in, float2 *out, size_t n, float k, hipStream_t s);
 
 // sinks

@@ -267,6 +267,29 @@ struct fdc_pipeline {
     bool tn_host = false;
     hipStream_t tn_stream = nullptr;
     std::string tones_route;     // the last call with the setting on ran the tones pass (fdc_pipeline_describe)
+    // tone squelch (fdc_pipeline_set_tone_squelch): a setting that needs the tones and the squelch.  tsq_tone: the C tone indices in force (-1: the channel
+    // is not tone-gated), tsq_open / tsq_close / tsq_ratio the C thresholds and ratios, tsq_guard and tsq_hang (frames) for all channels; d_tsqtone and
+    // d_tsqthr[0 .. 2] their device tables.  d_tsqstate: the stream state, (open, h) of every channel behind the last completed frame, two buffers of C
+    // int pairs: a call reads d_tsqstate[tsqstate_cur] where it continues the TONES' stream and the state is valid (tsq_valid: a call with the setting in
+    // force has written it) and its kernel writes the other one; the enqueue path swaps behind a successful enqueue.  d_tdec: the decisions of the frames
+    // the last call completed, [(max_blocks + W - 1) div W][C] bytes, pin_tdec its pinned twin (tsq_host, tsq_stream as lev_host, lev_stream; tsq_frames:
+    // how many rows).  All of it is allocated by fdc_pipeline_set_tone_squelch.
+    bool tsq_on = false;
+    std::vector<int32_t> tsq_tone;
+    std::vector<float> tsq_open, tsq_close, tsq_ratio;
+    int tsq_guard = 0, tsq_hang = 0;
+    fdc::DevBuf<int> d_tsqtone;
+    fdc::DevBuf<float> d_tsqthr[3];
+    fdc::DevBuf<int> d_tsqstate[2];
+    int tsqstate_cur = 0;
+    bool tsq_valid = false;
+    fdc::DevBuf<unsigned char> d_tdec;
+    fdc::PinBuf<unsigned char> pin_tdec;
+    int tsq_blocks = -1;         // block count of the last successful work call with the tone squelch on (-1: none yet)
+    int tsq_frames = 0;          // ... and the frames it decided
+    bool tsq_host = false;
+    hipStream_t tsq_stream = nullptr;
+    std::string tsq_route;       // the last call with the setting on ran the tone squelch (fdc_pipeline_describe)
     fdc::DevBuf<float2> d_out;   // work(): max_blocks*sum_lout (out_staging)
     int64_t blockcount = 0;      // work(): blocks consumed so far
     // work(): transfers and kernels of consecutive sub-batches overlap (H2D on s_in, kernels on stream, D2H on s_out)
@@ -342,7 +365,10 @@ struct DeviceCall {
     // channel tones (fdc_pipeline_set_tones): where the first frame row the call completes goes, [frame][C][T]; null = none.  It goes with a demodulating
     // output code only.  A sub-batch of a host call hands in the row behind the frames the host call has completed so far (tones_frames, below)
     float2 *tones = nullptr;
-    int ncu = 0;                        // compute units the call's persistent kernels may use
+    // tone squelch (fdc_pipeline_set_tone_squelch): where the decisions of the first frame the call completes go, [frame][C] bytes; null = none.  It goes
+    // with tones and squelch; a sub-batch of a host call hands in the row behind the frames the host call has completed so far, as for the tones
+    unsigned char *tone_dec = nullptr;
+    int ncu = 0;                       // compute units the call's persistent kernels may use
     // results: no launch group had to be widened (each read the integer input in its own loads); the call's kernels narrowed in their own stores;
     // the frame rows the tones pass of the call completed
     bool all_fused = true, ofused = false;
@@ -383,6 +409,12 @@ inline bool tones_on(const fdc_pipeline *p) { return p->tones_T > 0 && p->demod_
 inline size_t tones_row(const fdc_pipeline *p) { return (size_t)p->C * (size_t)p->tones_T; }
 inline float2 *tones_rows(const fdc_pipeline *p, size_t done) { return tones_on(p) ? p->d_tones.get() + done * tones_row(p) : nullptr; }
 
+// tone squelch: where the decisions behind `done` completed frames of a host call go in the handle's buffer (null: the call runs no tone squelch)
+inline unsigned char *tone_dec_rows(const fdc_pipeline *p, size_t done)
+{
+    return p->tsq_on && tones_on(p) && squelch_rows(p, 0) ? p->d_tdec.get() + done * (size_t)p->C : nullptr;
+}
+
 inline bool ispow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
 
 inline float2 unit(double turns)              // exp(-2 pi i turns), designed in double, rounded once
@@ -422,6 +454,7 @@ void lag1_written(fdc_pipeline *p, int nblocks, hipStream_t stream, bool host); 
 void audio_written(fdc_pipeline *p, int nblocks, hipStream_t stream, bool host);    // ... and of the channel audio (fdc_pipeline_audio)
 void squelch_written(fdc_pipeline *p, int nblocks, hipStream_t stream, bool host);  // ... and of the channel squelch (fdc_pipeline_squelch)
 void tones_written(fdc_pipeline *p, int nblocks, int nframes, hipStream_t stream, bool host);   // ... and of the channel tones (fdc_pipeline_tones)
+void tone_squelch_written(fdc_pipeline *p, int nblocks, int nframes, hipStream_t stream, bool host);   // ... and of the tone squelch (fdc_pipeline_tone_squelch)
 std::string route(int fmt, bool fused, const char *otherwise);   // "<sc16|sc8>: fused", or what the call was instead (fdc_pipeline_describe)
 
 } }  // namespace fdc::pipe

@@ -31,6 +31,9 @@ static int levels_home(fdc_pipeline *p, int nblocks, hipStream_t s, int tones_fr
     // the frame rows the call's tones pass completed (fdc_pipeline_tones), by the same rule: no copy where it completed none
     if (tones_on(p) && tones_frames > 0)
         HIPCHK(hipMemcpyAsync(p->pin_tones.get(), p->d_tones.get(), sizeof(float2) * (size_t)tones_frames * tones_row(p), hipMemcpyDeviceToHost, s));
+    // ... and the tone squelch's decisions of those frames (fdc_pipeline_tone_squelch), likewise
+    if (tone_dec_rows(p, 0) && tones_frames > 0)
+        HIPCHK(hipMemcpyAsync(p->pin_tdec.get(), p->d_tdec.get(), (size_t)tones_frames * (size_t)p->C, hipMemcpyDeviceToHost, s));
     if (p->levels_on && p->C > 0)
         HIPCHK(hipMemcpyAsync(p->pin_levels.get(), p->d_levels.get(), sizeof(float2) * (size_t)nblocks * p->C, hipMemcpyDeviceToHost, s));
     if (p->lag1_on && p->C > 0)
@@ -227,6 +230,7 @@ static int pipeline_work_impl(fdc_pipeline *p, DeviceCall call, const void *in, 
         call.squelch = squelch_rows(p, b0);
         if (pack) { call.audio = p->d_audio.get(); call.pack_off = pack_rows(p, b0); call.pack_append = true; }
         call.tones = tones_rows(p, (size_t)tframes);
+        call.tone_dec = tone_dec_rows(p, (size_t)tframes);
         const int rc2 = process_device_impl(p, call, ringb + b0 * p->H * esz, first, nb,
                                             ofmt ? static_cast<void *>(p->d_oq + osz * b0 * (size_t)p->sum_lout) : static_cast<void *>(dok));
         oq_all = oq_all && call.ofused;
@@ -281,6 +285,7 @@ static int pipeline_work_impl(fdc_pipeline *p, DeviceCall call, const void *in, 
         if (audio) audio_written(p, nblocks, s, true);
         if (squelch_rows(p, 0)) squelch_written(p, nblocks, s, true);
         if (tones_on(p)) tones_written(p, nblocks, tframes, s, true);
+        if (tone_dec_rows(p, 0)) tone_squelch_written(p, nblocks, tframes, s, true);
         if (fmt) p->iq_route = route(fmt, call.all_fused, "widened");
         if (p->out_form) p->oq_route = route(ofmt, oq_all, "narrowed");
         if (ports && !out_reg) deliver(0, 0, nblocks);
@@ -351,6 +356,7 @@ static int pipeline_work_impl(fdc_pipeline *p, DeviceCall call, const void *in, 
     if (audio) audio_written(p, nblocks, s, true);
     if (squelch_rows(p, 0)) squelch_written(p, nblocks, s, true);
     if (tones_on(p)) tones_written(p, nblocks, tframes, s, true);
+    if (tone_dec_rows(p, 0)) tone_squelch_written(p, nblocks, tframes, s, true);
     if (fmt) p->iq_route = route(fmt, call.all_fused, "widened");
     if (p->out_form) p->oq_route = route(ofmt, oq_all, "narrowed");
     p->blockcount += nblocks;
@@ -455,6 +461,7 @@ static int pipeline_work_real_impl(fdc_pipeline *p, const void *in, int nblocks,
     call.squelch = squelch_rows(p, 0);
     if (packing_on(p)) { call.audio = p->d_audio.get(); call.pack_off = pack_rows(p, 0); call.pack_append = false; }
     call.tones = tones_rows(p, 0);
+    call.tone_dec = tone_dec_rows(p, 0);
     RCCHK(process_device_impl(p, call, p->d_ring, p->blockcount, nblocks, res));
     if (!call.audio) RCCHK(copy_outputs(p, outs, nblocks, osz, res, s));     // (audio on: the rows go home with the levels, outs is not looked at)
     if (spectrum) HIPCHK(hipMemcpyAsync(spectrum, d_specfull, sizeof(float2) * (size_t)nblocks * p->N, hipMemcpyDeviceToHost, s));
@@ -467,6 +474,7 @@ static int pipeline_work_real_impl(fdc_pipeline *p, const void *in, int nblocks,
     if (call.audio) audio_written(p, nblocks, s, true);
     if (call.squelch) squelch_written(p, nblocks, s, true);
     if (call.tones) tones_written(p, nblocks, call.tones_frames, s, true);
+    if (call.tone_dec) tone_squelch_written(p, nblocks, call.tones_frames, s, true);
     if (p->out_form) p->oq_route = route(ofmt, call.ofused, "narrowed");
     p->blockcount += nblocks;
     return nblocks;

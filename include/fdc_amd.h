@@ -509,7 +509,7 @@ int fdc_pipeline_audio_pack_offsets_device(const fdc_pipeline *p, const void *d_
  * it is the frame's row Z[f][c][t] (re, im) and starts again at (+0, +0).  The phase is an integer function of the stream's own group index: no drift,
  * and nothing depends on how the stream is cut.  tests/tones_model.py states this in numpy, and the rows are that model's byte for byte.
  * For a tone of amplitude a at frequency f in d, at channel rate r: |Z| ~ a (W lout_c / 2) droop(f), droop(f) = sin(pi f S / r) / (S sin(pi f / r)); an
- * increment is round(2^32 f S / r).  The tones are NOT gated by the squelch, and the decision on top of them (thresholds, a tone squelch) is the host's.
+ * increment is round(2^32 f S / r).  The tones are NOT gated by the squelch; the decision on top of them is the host's, or the device's (TONE SQUELCH).
  * THE STATE: the handle keeps a block position for the tones, the blocks already inside the open frame (fill, a host integer) and the open frame's
  * accumulators, float2[C][T], on the device.  A call CONTINUES the stream when its first_block is the block after the last one of the previous
  * successful call with the tones on; otherwise fill = 0 and the accumulators are zero: after create or fdc_pipeline_reset, after switching the tones on
@@ -549,6 +549,58 @@ int fdc_pipeline_tones_pass_device(const fdc_pipeline *p, const void *d_in, void
                                    int32_t fill, int nblocks, void *stream);
 /* The 1024 (cos, sin) pairs of the tones' reference, 2048 floats.  Host only, no handle. */
 int fdc_tone_table(float *dst);
+
+/* TONE SQUELCH: thresholds on the frame rows of the channel tones decide, per channel and frame, whether the selected tone is there, and the decision
+ * gates the carrier squelch's mask, all on the device: the audio and the packed audio of a channel whose carrier is up but whose tone is another
+ * user's never leave the card.  It needs the channel tones (T, S, W) and the channel squelch.  The setting: per channel a tone index tone_c (-1: the
+ * channel is not tone-gated, else 0 .. T - 1), float32 thresholds open_c >= close_c >= 0 and a float32 ratio_c >= 0, all finite; for all channels a
+ * guard of 0 .. 63 tones and a hang count of 0 .. 65535 FRAMES.  Of the row Z[f][c][0 .. T - 1] of a completed frame, with sel = tone_c:
+ *     e_t = float32(float32(re re) + float32(im im));   e = e_sel
+ *     o   = the largest e_t over the t with |t - sel| > guard, from +0 by "e_t > o ? e_t : o" (a NaN is never taken; +0 where no such t is left)
+ *     R   = float32(ratio_c o);   strong = e >= open_c and e >= R;   hold = e >= close_c and e >= R;   low = neither
+ * every comparison an IEEE float32 >=, so a NaN is below.  Over the frames runs the channel squelch's own state machine with frames in the place of
+ * blocks, from (open, h) = (0, 0): strong -> (1, hang); open and not low -> h = hang; open and low -> h - 1, closing at 0; dec[f][c] = open behind
+ * frame f.  The unit of the thresholds is |Z|^2 (fdc_pipeline_set_tones gives |Z| for a tone of a given amplitude).
+ * THE GATE IS CAUSAL.  Block m of a call stands in frame j = (fill + m) div W counted from the call's first frame, fill being the tones' own.  The
+ * decision in force for it is the carried state's `open` for j = 0 and dec[j - 1][c] otherwise, and mask[m][c] = carrier mask[m][c] AND in force.  The
+ * latency is one frame by construction, which is what makes the bytes independent of how the stream is cut; a caller who wants less picks a smaller W
+ * and a hang.  A channel with tone -1 keeps its carrier mask, has dec = 1, and its state is written as (0, 0).  tests/tone_squelch_model.py states all
+ * of this in numpy, and dec and the mask are that model's byte for byte.
+ * THE STATE lives on the device, one int32 pair per channel.  The tone squelch continues exactly where the tones continue their stream (see CHANNEL
+ * TONES); otherwise it restarts at (0, 0) with fill 0, so the first frame of a fresh stream is closed.  A new tone-squelch setting restarts the state
+ * only, not the tones' frames.  A call that is REFUSED leaves everything as it was.
+ *   fdc_pipeline_set_tone_squelch     tone NULL switches it off.  FDC_ERR_INVALID_ARGUMENT, the previous setting staying in force: n != C; a tone outside
+ *                                     -1 .. T - 1; a threshold or ratio that is not finite or negative; close > open; guard or hang out of range; while
+ *                                     the tones or the channel squelch are off; while a pipelined sinks batch is inside the handle.  While it is on,
+ *                                     fdc_pipeline_set_tones is refused where it would switch the tones off or change T, S or W (new increments alone
+ *                                     are allowed and restart both streams), and so is fdc_pipeline_set_squelch(NULL ...).  A SETTING: it applies from
+ *                                     the next call and survives fdc_pipeline_reset (the state does not); it waits for the handle's own stream first.
+ *                                     It allocates everything the feature needs, once: four tables of C, two state buffers, ((W - 1 + max_blocks) div W)
+ *                                     C decision bytes and their pinned twin; nothing in the steady state of any entry.  A plan without channels accepts it.
+ *   fdc_pipeline_tone_squelch_setting the setting in force; any pointer may be NULL; the arrays receive C elements each, guard and hang -1 while it is off.
+ *   fdc_pipeline_tone_squelch         dec[nf][C] of the frames the last call completed, one byte (0 / 1) each, nblocks being that call's block count
+ *                                     (as fdc_pipeline_tones); *nframes receives nf.  capacity_bytes below nf C: FDC_ERR_INVALID_ARGUMENT, nothing written.
+ *                                     After a host entry it is a memcpy from the pinned twin, copied home with the levels (no copy where nf = 0); after
+ *                                     a device entry it waits for the stream that one ran on.
+ *   fdc_pipeline_tone_squelch_device  the device decisions, NULL while off.
+ * WHILE IT IS ON fdc_pipeline_squelch and fdc_pipeline_squelch_device give the COMBINED mask (carrier AND tone), which is the mask that gates the audio
+ * and feeds the pack offsets; the carrier squelch's own state is untouched by the gate.  A call's tail then runs k_chan_squelch, k_chan_demod,
+ * k_chan_tones, k_tone_decide, k_tone_gate, the pack offsets and k_chan_audio in this order; the sub-batches of a long host call append their decisions
+ * as the tones append their rows.  fdc_pipeline_describe: "tone squelch: pass" after a call that ran it.  With the setting off every entry launches
+ * exactly the kernels it launches without this feature, in the same order.  There is no group setter. */
+int fdc_pipeline_set_tone_squelch(fdc_pipeline *p, const int32_t *tone, const float *open_thr, const float *close_thr, const float *ratio, int n,
+                                  int32_t guard, int32_t hang_frames);
+int fdc_pipeline_tone_squelch_setting(const fdc_pipeline *p, int32_t *tone, float *open_thr, float *close_thr, float *ratio, int32_t *guard,
+                                      int32_t *hang_frames);
+int fdc_pipeline_tone_squelch(fdc_pipeline *p, uint8_t *dst, size_t capacity_bytes, int nblocks, int32_t *nframes);
+void *fdc_pipeline_tone_squelch_device(fdc_pipeline *p);
+/* The decision and the gate alone, on device buffers of the caller (and the entry the tests reach the kernels by with hand-made rows), with the handle's
+ * setting (which must be on), the tones' T and W and the channel count, and nothing of its stream state: d_frames ((fill + nblocks) div W) C T float32
+ * pairs, d_dec exactly that many times C bytes (both may be NULL where that is 0), d_state_in C int32 pairs (open, h) or NULL ((0, 0)), d_state_out
+ * another buffer that receives exactly C int32 pairs (the state as read where the call completes no frame), d_mask exactly nblocks C bytes, ANDed in
+ * place, or NULL: the decision alone.  fill: 0 .. W - 1.  Enqueued on `stream` (NULL: the handle's). */
+int fdc_pipeline_tone_squelch_pass_device(const fdc_pipeline *p, const void *d_frames, void *d_dec, const void *d_state_in, void *d_state_out, void *d_mask,
+                                          int32_t fill, int nblocks, void *stream);
 
 /* Optional: pin a host range that will be handed to fdc_pipeline_work() again and again (GNU Radio's circular buffers
  * live as long as the flowgraph: register them in start(), unregister in stop()).  A call whose `in` lies in a
