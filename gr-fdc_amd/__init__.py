@@ -7,7 +7,7 @@ runs in hand-written gfx950 HIP kernels (gr-fdc_amd/csrc); nothing here computes
 from ._lib import FdcError, lib, LIB_PATH                                   # noqa: F401
 from .blocks import overlap_save, vector_cut_vxx, phase_shifting_windowing_vcc, fft_vcc, window_table  # noqa: F401
 from .channelizer import (FrequencyDomainChannelizer, Pipeline, PipelineGroup, IQ_SC16, IQ_SC8, OQ_FC32, plan_preview, FREQMODE, VERBOSEMODE, WINDOWTYPES,   # noqa: F401
-                          nextpow2, get_opt_channelparams, freq_converters, register_host, unregister_host, defaults, fine_tuning_increment, fine_tuning_nu, lag1_frequency, lowpass_taps, audio_channels, AUDIO_F32, AUDIO_S16, squelch_thresholds,
+                          nextpow2, get_opt_channelparams, freq_converters, register_host, unregister_host, defaults, fine_tuning_increment, fine_tuning_nu, lag1_frequency, lowpass_taps, audio_channels, AUDIO_F32, AUDIO_S16, audio_block_counts, audio_resampled_channels, resampler_taps, audio_resample_ratio, squelch_thresholds,
                           audio_pack_offsets, unpack_audio, tone_table, ctcss_tones, tone_increments, tone_amplitude,
                           tone_squelch_thresholds)
 from ._lib import (FDC_PIPE_FORCE_GENERIC, FDC_PIPE_NO_POLY, FDC_PIPE_NO_BLOCK, FDC_PIPE_PLAIN_STORES, FDC_PIPE_NT_LOADS,   # noqa: F401

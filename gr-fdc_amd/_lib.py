@@ -120,6 +120,12 @@ SYMBOLS = {
     "fdc_pipeline_audio": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int]),
     "fdc_pipeline_audio_device": (_vp, [_vp]),
     "fdc_pipeline_audio_pass_device": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, _vp]),
+    "fdc_pipeline_set_audio_resampler": (C.c_int, [_vp, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.c_int32, C.c_int32, C.c_float]),
+    "fdc_pipeline_audio_resampler_setting": (C.c_int, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                                       C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int32]),
+    "fdc_pipeline_audio_first_block": (C.c_int64, [_vp]),
+    "fdc_audio_resampler_counts": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.POINTER(C.c_int32)]),
+    "fdc_pipeline_audio_resampler_pass_device": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int64, C.c_int, _vp, _vp]),
     "fdc_pipeline_set_squelch": (C.c_int, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.c_int32]),
     "fdc_pipeline_squelch_setting": (C.c_int, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int32)]),
     "fdc_pipeline_squelch": (C.c_int, [_vp, _vp, C.c_size_t, C.c_int]),

@@ -471,6 +471,113 @@ def lowpass_taps(decim, ntaps, cutoff=None):
     return (h / h.sum()).astype(np.float32)
 
 
+RESAMPLER_MAX_UP, RESAMPLER_MAX_DOWN, RESAMPLER_MAX_PHASE_TAPS = 64, 128, 256       # include/fdc_amd.h (fdc_pipeline_set_audio_resampler)
+
+
+def _is_int(v):
+    return not isinstance(v, bool) and isinstance(v, (int, np.integer))
+
+
+def _resampler_ratio(up, down):
+    """(up, down) of the audio resampler as ints, checked: 1 .. 64 over 1 .. 128, reduced"""
+    if not _is_int(up) or not 1 <= int(up) <= RESAMPLER_MAX_UP:
+        raise ValueError("the resampler's interpolation is an integer in 1 .. %d (None: off)" % RESAMPLER_MAX_UP)
+    if not _is_int(down) or not 1 <= int(down) <= RESAMPLER_MAX_DOWN:
+        raise ValueError("the resampler's decimation is an integer in 1 .. %d" % RESAMPLER_MAX_DOWN)
+    g = math.gcd(int(up), int(down))
+    if g != 1:
+        raise ValueError("the ratio %d / %d is not reduced, which would leave tap phases unused: give %d / %d" % (up, down, int(up) // g, int(down) // g))
+    return int(up), int(down)
+
+
+def _resampler_args(up, down, taps, fmt, scale):
+    """Pipeline.set_audio_resampler: (up, down, float32 taps, FDC_AUDIO_* code, float32 scale), (0, 0, None, 0, 1) for up None.  Raises before any
+    library call."""
+    if up is None:
+        return 0, 0, None, AUDIO_F32, np.float32(1.0)
+    up, down = _resampler_ratio(up, down)
+    if taps is None:
+        raise ValueError("the resampler needs its taps (resampler_taps)")
+    with np.errstate(over="ignore"):
+        h = np.ascontiguousarray(taps, dtype=np.float32).reshape(-1)
+    if h.size < 1 or -(-h.size // up) > RESAMPLER_MAX_PHASE_TAPS:
+        raise ValueError("the resampler's filter has 1 .. %d taps per phase: 1 .. %d taps at up = %d" % (RESAMPLER_MAX_PHASE_TAPS, RESAMPLER_MAX_PHASE_TAPS * up, up))
+    if not np.isfinite(h).all():
+        raise ValueError("the resampler's taps must be finite (tap %d is not)" % int(np.flatnonzero(~np.isfinite(h))[0]))
+    if not isinstance(fmt, str) or fmt.lower() not in _AUDIO_FORMATS:
+        raise ValueError("the audio format is 'f32' or 's16'")
+    code = _AUDIO_FORMATS[fmt.lower()]
+    with np.errstate(over="ignore"):
+        sc = np.float32(scale)
+    if code == AUDIO_S16 and (not np.isfinite(sc) or sc == 0):
+        raise ValueError("the audio scale must be finite and not zero")
+    return up, down, h, code, sc if code == AUDIO_S16 else np.float32(1.0)
+
+
+def audio_block_counts(lout, up, down, first_block, nblocks):
+    """How many resampled outputs each of the blocks first_block .. first_block + nblocks - 1 of a channel of lout samples per block owns (int64
+    [nblocks]): block m owns the outputs ceil(m lout up / down) .. ceil((m + 1) lout up / down) - 1, W or W - 1 of them with W = ceil(lout up / down).
+    A function of the ABSOLUTE block index alone, in exact integers (the library's fdc_audio_resampler_counts)."""
+    up, down = _resampler_ratio(up, down)
+    if not _is_int(lout) or int(lout) < 1:
+        raise ValueError("lout is a positive integer")
+    if not _is_int(first_block) or int(first_block) < 0 or not _is_int(nblocks) or int(nblocks) < 0:
+        raise ValueError("first_block and nblocks are integers >= 0")
+    step = int(lout) * up
+    edge = [-((-(int(first_block) + i) * step) // down) for i in range(int(nblocks) + 1)]
+    return np.array([edge[i + 1] - edge[i] for i in range(int(nblocks))], dtype=np.int64)
+
+
+def audio_resampled_channels(mat, lout, up, down, first_block):
+    """The [nb, A] block-major matrix of a resampled call (Pipeline.audio with set_audio_resampler on) as one array per channel holding the VALID samples
+    only: channel c owns the W_c = ceil(lout_c up / down) columns from sum(W_i, i < c) on, row m holds the audio_block_counts(lout_c, ..)[m] outputs
+    of block first_block + m and, where that is W_c - 1, one pad behind them, which is dropped here."""
+    mat = np.asarray(mat)
+    up, down = _resampler_ratio(up, down)
+    per = [-(-int(lo) * up // down) for lo in lout]
+    if mat.ndim != 2 or mat.shape[1] != sum(per):
+        raise ValueError("the audio matrix has %d columns, ceil(lout_c up / down) for every channel" % sum(per))
+    at = np.concatenate([[0], np.cumsum(per)]).astype(np.int64)
+    out = []
+    for c, lo in enumerate(lout):
+        cnt = audio_block_counts(int(lo), up, down, first_block, mat.shape[0])
+        cell = mat[:, at[c]:at[c + 1]]
+        out.append(np.ascontiguousarray(cell[np.arange(per[c])[None, :] < cnt[:, None]]).reshape(-1))
+    return out
+
+
+def resampler_taps(up, down, taps_per_phase=16, cutoff=None):
+    """A prototype low-pass for Pipeline.set_audio_resampler(up, down, ...): a Hamming-windowed sinc of up * taps_per_phase taps with its cutoff (the
+    -6 dB point) at `cutoff` cycles per UPSAMPLED sample (default 0.5 / max(up, down): the narrower of the input's and the output's Nyquist
+    frequency), designed in float64, its sum normalised to `up` (unit gain through the interpolation) and returned as float32."""
+    up, down = _resampler_ratio(up, down)
+    if not _is_int(taps_per_phase) or not 1 <= int(taps_per_phase) <= RESAMPLER_MAX_PHASE_TAPS:
+        raise ValueError("taps_per_phase is an integer in 1 .. %d" % RESAMPLER_MAX_PHASE_TAPS)
+    fc = 0.5 / max(up, down) if cutoff is None else float(cutoff)
+    if not 0.0 < fc <= 0.5:
+        raise ValueError("the cutoff is in (0, 0.5] cycles per upsampled sample")
+    ntaps = up * int(taps_per_phase)
+    n = np.arange(ntaps, dtype=np.float64) - (ntaps - 1) / 2.0
+    h = 2.0 * fc * np.sinc(2.0 * fc * n) * np.hamming(ntaps)
+    return (h * (up / h.sum())).astype(np.float32)
+
+
+def audio_resample_ratio(rate_in, rate_out):
+    """The exact reduced (up, down) with rate_out = rate_in * up / down, for rates given as integers, fractions.Fraction or floats that are exact
+    ratios (25e3, 48000.0); ValueError where up does not fit 1 .. 64 or down 1 .. 128."""
+    from fractions import Fraction
+    try:
+        fin, fout = Fraction(rate_in), Fraction(rate_out)
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError("the rates are finite numbers")
+    if fin <= 0 or fout <= 0:
+        raise ValueError("the rates are positive")
+    r = fout / fin
+    if not 1 <= r.numerator <= RESAMPLER_MAX_UP or not 1 <= r.denominator <= RESAMPLER_MAX_DOWN:
+        raise ValueError("%s -> %s is the ratio %d / %d, beyond %d / %d" % (rate_in, rate_out, r.numerator, r.denominator, RESAMPLER_MAX_UP, RESAMPLER_MAX_DOWN))
+    return int(r.numerator), int(r.denominator)
+
+
 TONES_MAX, TONES_MAX_FRAME, TONE_TABLE = 64, 4096, 1024       # include/fdc_amd.h: tones per channel, blocks per frame, entries of the reference table
 
 
@@ -732,6 +839,49 @@ class Pipeline(_OutputFormat):
                                                      code, float(sc)))
         self._audio = d
 
+    def set_audio_resampler(self, up, down=None, taps=None, fmt="f32", scale=1.0):
+        """fdc_pipeline_set_audio_resampler: up None switches it off; else the reduced ratio up 1 .. 64 over down 1 .. 128, taps (converted to float32;
+        finite, at most 256 per phase: resampler_taps), fmt and scale as set_audio.  The second form of the channel audio, which replaces the decimating
+        one (and set_audio(decim) replaces it): a[n] = sum over k of taps[k up + (n down mod up)] d[(n down div up) - k] with n and the sample index
+        counted from the stream's block 0, in set_audio's arithmetic (tests/resample_model.py).  While it is on, work*, work_span* and work_iq* return
+        one array per channel with the VALID samples of the call (audio_block_counts says how many each block gives) and take no outs=; audio() gives
+        the padded matrix [nblocks, sum of ceil(lout_c up / down)] (audio_resampled_channels slices it).  The history is set_audio's, of
+        ceil(ntaps / up) - 1 samples per channel; a new ratio or other taps restart the stream.  ValueError for arguments out of range (nothing
+        reaches the library), FdcError where the library refuses (demodulation off, the audio packing on, a pipelined sinks batch inside)."""
+        u, d, h, code, sc = _resampler_args(up, down, taps, fmt, scale)
+        _lib.check(_lib.lib().fdc_pipeline_set_audio_resampler(self._h, u, d, None if h is None else h.ctypes.data_as(C.POINTER(C.c_float)),
+                                                               0 if h is None else int(h.size), code, float(sc)))
+        self._audio = u if u else (0 if self.audio_setting() is None else self._audio)
+
+    def audio_resampler_setting(self):
+        """fdc_pipeline_audio_resampler_setting: None while off, else (up, down, float32 taps, "f32" / "s16", scale): what the library has in force now."""
+        u, d, k, f, sc = C.c_int32(0), C.c_int32(0), C.c_int32(0), C.c_int32(0), C.c_float(0)
+        lib = _lib.lib()
+        _lib.check(lib.fdc_pipeline_audio_resampler_setting(self._h, C.byref(u), C.byref(d), C.byref(k), C.byref(f), C.byref(sc), None, 0))
+        if u.value == 0:
+            return None
+        taps = np.zeros(k.value, dtype=np.float32)
+        _lib.check(lib.fdc_pipeline_audio_resampler_setting(self._h, None, None, None, None, None, taps.ctypes.data_as(C.POINTER(C.c_float)), int(taps.size)))
+        return int(u.value), int(d.value), taps, {AUDIO_F32: "f32", AUDIO_S16: "s16"}[f.value], float(sc.value)
+
+    def audio_first_block(self):
+        """fdc_pipeline_audio_first_block: the absolute index of row 0 of the audio the handle holds, -1 where there is none."""
+        return int(_lib.lib().fdc_pipeline_audio_first_block(self._h))
+
+    def audio_resampler_pass_device(self, d_in, d_out, first_block, nblocks, d_hist_in=None, d_hist_out=None, d_mask=None, stream=None):
+        """fdc_pipeline_audio_resampler_pass_device: the resampling pass alone on device buffers of the caller, with the setting in force (d_in: float32
+        in process_device's layout, d_out: nblocks * A elements, d_hist_in: C (Kp - 1) float32 or None, d_hist_out: another such buffer, None only
+        where Kp = 1, d_mask: nblocks * C bytes or None).  The handle's own history and stream position are not touched."""
+        _lib.check(_lib.lib().fdc_pipeline_audio_resampler_pass_device(self._h, d_in, d_out, d_hist_in, d_hist_out, int(first_block), int(nblocks), d_mask, stream))
+
+    def _audio_form(self):
+        """the audio form in force, asked of the library: None, ("decim", decim, fmt) or ("resampled", up, down, fmt)"""
+        s = self.audio_setting()
+        if s is not None:
+            return ("decim", s[0], s[2])
+        r = self.audio_resampler_setting()
+        return None if r is None else ("resampled", r[0], r[1], r[3])
+
     def audio_setting(self):
         """fdc_pipeline_audio_setting: None while off, else (decim, float32 taps, "f32" / "s16", scale): what the library has in force now."""
         d, k, f, sc = C.c_int32(0), C.c_int32(0), C.c_int32(0), C.c_float(0)
@@ -755,10 +905,10 @@ class Pipeline(_OutputFormat):
             raise ValueError("audio(): negative block count")
         if getattr(self, "_packing", False):
             raise ValueError("audio(): the audio packing is on, there is no matrix: audio_packed() (set_audio_packing)")
-        setting = self.audio_setting()
-        if setting is None:
-            raise ValueError("audio(): the channel audio is off (set_audio)")
-        out = np.empty((nblocks, int(_lib.lib().fdc_pipeline_audio_row(self._h))), dtype=_AUDIO_DTYPES[_AUDIO_FORMATS[setting[2]]])
+        form = self._audio_form()
+        if form is None:
+            raise ValueError("audio(): the channel audio is off (set_audio, set_audio_resampler)")
+        out = np.empty((nblocks, int(_lib.lib().fdc_pipeline_audio_row(self._h))), dtype=_AUDIO_DTYPES[_AUDIO_FORMATS[form[-1]]])
         if out.size:
             _lib.check(_lib.lib().fdc_pipeline_audio(self._h, out.ctypes.data, out.nbytes, nblocks))
         return out
@@ -999,7 +1149,7 @@ class Pipeline(_OutputFormat):
         and outs= is refused."""
         if outs is not None and getattr(self, "_audio", 0):
             raise ValueError("outs= cannot go with the channel audio: the call returns the audio arrays (set_audio)")
-        if getattr(self, "_h", None) and self.audio_setting() is not None:
+        if getattr(self, "_h", None) and self._audio_form() is not None:
             if outs is not None:
                 raise ValueError("outs= cannot go with the channel audio: the call returns the audio arrays (set_audio)")
             return None, None
@@ -1010,7 +1160,12 @@ class Pipeline(_OutputFormat):
         """what a host call returns: its outs, or (the audio on: _host_outs gave None) one audio array per channel, sliced from the matrix"""
         if outs is not None:
             return outs
-        decim = self.audio_setting()[0]
+        form = self._audio_form()
+        if form[0] == "resampled":
+            # the valid samples only: the rows are cut by the counts at the call's first block, as the library reports it
+            first = self.audio_first_block()
+            return audio_resampled_channels(self.audio(nb), self.lout, form[1], form[2], max(first, 0))
+        decim = form[1]
         if getattr(self, "_packing", False):
             # the packing on: one array per channel with its open blocks of this call; which they are: squelch()
             per = [int(lo) // decim for lo in self.lout]
@@ -1369,7 +1524,7 @@ class FrequencyDomainChannelizer:
                  debug, device_id=0, max_blocks=64, devices=None, pipelined=False, waterfall=None, iq_input=None, iq_scale=1.0,
                  iq_output=None, iq_output_scale=1.0, fine_tuning=False, *, payload_format=None, payload_scale=1.0, levels=False, gains=None, lag1=False,
                  demod=None, demod_gain=1.0, audio_decim=None, audio_taps=None, audio_format="f32", audio_scale=1.0, squelch_db=None, squelch_close_db=None,
-                 squelch_hang=0, audio_packed=False, tones=None, tone_group=16, tone_frame=32, tone_squelch=None, tone_open=None,
+                 squelch_hang=0, audio_packed=False, audio_up=None, audio_down=None, tones=None, tone_group=16, tone_frame=32, tone_squelch=None, tone_open=None,
                  tone_close=None, tone_ratio=0.0, tone_guard=0, tone_hang=0):
         # pipelined (not an argument of the reference): the sink blocks run beside the front end of the FOLLOWING work() calls, as the
         # thread-per-block scheduler runs them beside the FFT in the reference (fdc_pipeline_work_sinks on a look-ahead bank,
@@ -1515,8 +1670,22 @@ class FrequencyDomainChannelizer:
             if audio_taps is None:
                 raise ValueError("audio_decim needs audio_taps (lowpass_taps)")
             _audio_args(audio_decim, audio_taps, audio_format, audio_scale)
-        elif audio_taps is not None:
-            raise ValueError("audio_taps needs audio_decim")
+        # audio_up / audio_down (not arguments of the reference): the rational resampler in the decimating low-pass's place (Pipeline.set_audio_resampler):
+        # the ports come back at the channel rate times audio_up / audio_down, the valid samples of every call.  audio_taps: the prototype taps
+        # (default: resampler_taps(audio_up, audio_down)); audio_format and audio_scale as above
+        self.audio_up, self.audio_down = audio_up, audio_down
+        if audio_up is not None or audio_down is not None:
+            if audio_decim is not None:
+                raise ValueError("audio_decim and audio_up / audio_down are the two forms of the channel audio: give one of them")
+            if audio_up is None or audio_down is None:
+                raise ValueError("audio_up and audio_down go together")
+            if demod is None:
+                raise ValueError("audio_up / audio_down need demod: the resampler runs behind the channel demodulation")
+            if audio_taps is None:
+                self.audio_taps = resampler_taps(audio_up, audio_down)
+            _resampler_args(audio_up, audio_down, self.audio_taps, audio_format, audio_scale)
+        elif audio_decim is None and audio_taps is not None:
+            raise ValueError("audio_taps needs audio_decim or audio_up / audio_down")
 
         # squelch_db / squelch_close_db / squelch_hang (not arguments of the reference): a carrier-operated squelch per throughput channel, decided on the
         # device from the levels (Pipeline.set_squelch): the channel opens at a block whose mean power in front of the gain reaches squelch_db (dB; a scalar
@@ -1645,6 +1814,8 @@ class FrequencyDomainChannelizer:
             self.pipeline.set_demod(self.demod, self.demod_gain)
         if self.audio_decim is not None:
             self.pipeline.set_audio(self.audio_decim, self.audio_taps, self.audio_format, self.audio_scale)
+        if self.audio_up is not None:
+            self.pipeline.set_audio_resampler(self.audio_up, self.audio_down, self.audio_taps, self.audio_format, self.audio_scale)
         if self.squelch_db is not None:
             self.set_squelch(self.squelch_db, self.squelch_close_db, self.squelch_hang)
         if self.audio_packed:

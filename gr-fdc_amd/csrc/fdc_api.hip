@@ -672,6 +672,8 @@ int fdc_pipeline_set_demod(fdc_pipeline *p, int32_t mode, float gain)
         return set_error(FDC_ERR_INVALID_ARGUMENT, "a pipelined sinks batch is still inside the handle: fdc_pipeline_flush_sinks until it returns 0 first");
     if (mode && p->out_form)
         return set_error(FDC_ERR_INVALID_ARGUMENT, "the channel demodulation writes real float32 samples: set the output format to FDC_OQ_FC32 first");
+    if (!mode && p->rs_up)
+        return set_error(FDC_ERR_INVALID_ARGUMENT, "the audio resampler filters the demodulated samples: switch it off first (fdc_pipeline_set_audio_resampler(p, 0, 0, NULL, 0, 0, 1))");
     if (!mode && p->audio_decim)
         return set_error(FDC_ERR_INVALID_ARGUMENT, "the channel audio filters the demodulated samples: switch the audio off first (fdc_pipeline_set_audio(p, 0, NULL, 0, 0, 1))");
     if (!mode && p->tones_T)
@@ -759,6 +761,7 @@ int fdc_pipeline_set_audio(fdc_pipeline *p, int32_t decim, const float *taps, in
     HIPCHK(hipStreamSynchronize(p->stream));          // (no call of the host entries is in flight; a device entry's caller orders its own stream)
     if (!decim) {
         p->audio_decim = 0; p->audio_format = FDC_AUDIO_F32; p->audio_scale = 1.0f; p->audio_taps.clear(); p->audio_row = 0;
+        p->rs_up = p->rs_down = p->rs_kp = 0; p->rs_taps.clear();       // (whichever form was on)
         p->audio_next = -1; p->aud_blocks = -1; p->audio_route.clear();
         return FDC_OK;
     }
@@ -782,6 +785,7 @@ int fdc_pipeline_set_audio(fdc_pipeline *p, int32_t decim, const float *taps, in
     const bool same = p->audio_decim == decim && p->audio_taps.size() == (size_t)ntaps && std::memcmp(p->audio_taps.data(), taps, sizeof(float) * (size_t)ntaps) == 0;
     if (!same) p->audio_next = -1;
     if (p->audio_decim != decim || p->audio_format != format) p->aud_blocks = -1;
+    p->rs_up = p->rs_down = p->rs_kp = 0; p->rs_taps.clear();           // the two forms replace each other (audio_decim was 0 beside it: all of the above)
     p->audio_decim = decim; p->audio_format = format; p->audio_scale = format == FDC_AUDIO_S16 ? scale : 1.0f;
     p->audio_taps.assign(taps, taps + ntaps);
     p->audio_row = row;
@@ -802,14 +806,14 @@ int fdc_pipeline_audio_setting(const fdc_pipeline *p, int32_t *decim, int32_t *n
     FDC_ENTRY_END
 }
 
-int64_t fdc_pipeline_audio_row(const fdc_pipeline *p) { return p && p->audio_decim ? p->audio_row : 0; }
+int64_t fdc_pipeline_audio_row(const fdc_pipeline *p) { return p && fdc::pipe::audio_set(p) ? p->audio_row : 0; }
 
 // the audio rows of the last call: never more than the caller says its buffer holds
 int fdc_pipeline_audio(fdc_pipeline *p, void *dst, size_t capacity_bytes, int nblocks)
 {
     FDC_ENTRY("fdc_pipeline_audio")
     if (!p) return set_error(FDC_ERR_INVALID_ARGUMENT, "null handle");
-    if (!p->audio_decim) return set_error(FDC_ERR_INVALID_ARGUMENT, "the channel audio is off (fdc_pipeline_set_audio)");
+    if (!fdc::pipe::audio_set(p)) return set_error(FDC_ERR_INVALID_ARGUMENT, "the channel audio is off (fdc_pipeline_set_audio, fdc_pipeline_set_audio_resampler)");
     if (p->pack_on) return set_error(FDC_ERR_INVALID_ARGUMENT, "the audio packing is on: there is no matrix, fetch the packed audio (fdc_pipeline_audio_packed)");
     if (p->aud_blocks < 0) return set_error(FDC_ERR_INVALID_ARGUMENT, "no work call has run since the channel audio was switched on or its format or decimation changed");
     if (nblocks != p->aud_blocks) return set_error(FDC_ERR_INVALID_ARGUMENT, "the last work call had %d blocks, not %d", p->aud_blocks, nblocks);
@@ -829,7 +833,7 @@ int fdc_pipeline_audio(fdc_pipeline *p, void *dst, size_t capacity_bytes, int nb
     FDC_ENTRY_END
 }
 
-void *fdc_pipeline_audio_device(fdc_pipeline *p) { return p && p->audio_decim ? static_cast<void *>(p->d_audio.get()) : nullptr; }
+void *fdc_pipeline_audio_device(fdc_pipeline *p) { return p && fdc::pipe::audio_set(p) ? static_cast<void *>(p->d_audio.get()) : nullptr; }
 
 // the audio pass alone, on the caller's device buffers: the handle gives its channel table and the audio setting, nothing of its stream state (but,
 // while the squelch is on, the mask of its last work call, which gates the pass)
@@ -837,6 +841,7 @@ int fdc_pipeline_audio_pass_device(const fdc_pipeline *p, const void *d_in, void
 {
     FDC_ENTRY("fdc_pipeline_audio_pass_device")
     if (!p) return set_error(FDC_ERR_INVALID_ARGUMENT, "null handle");
+    if (p->rs_up) return set_error(FDC_ERR_INVALID_ARGUMENT, "the audio resampler is on: its pass alone is fdc_pipeline_audio_resampler_pass_device");
     if (!p->audio_decim) return set_error(FDC_ERR_INVALID_ARGUMENT, "the channel audio is off (fdc_pipeline_set_audio)");
     if (nblocks < 0) return set_error(FDC_ERR_INVALID_ARGUMENT, "negative block count");
     if (nblocks == 0 || p->C <= 0) return FDC_OK;
@@ -864,6 +869,147 @@ int fdc_pipeline_audio_pass_device(const fdc_pipeline *p, const void *d_in, void
     FDC_ENTRY_END
 }
 
+// how many outputs of a resampled stream stand in front of block m of a channel of lout samples per block: ceil(m lout up / down)
+static int64_t resampler_first_output(int64_t m, int32_t lout, int32_t up, int32_t down)
+{
+    return (int64_t)(((__int128)m * lout * up + (down - 1)) / down);
+}
+
+// the outputs block first_block + i owns, i = 0 .. nblocks - 1: a function of the absolute block index alone (128-bit products: first_block may be 2^40
+// and more)
+int fdc_audio_resampler_counts(int32_t lout, int32_t up, int32_t down, int64_t first_block, int32_t nblocks, int32_t *counts)
+{
+    FDC_ENTRY("fdc_audio_resampler_counts")
+    if (lout < 1 || up < 1 || up > 64 || down < 1 || down > 128) return set_error(FDC_ERR_INVALID_ARGUMENT, "resampler counts: lout >= 1, up 1 .. 64, down 1 .. 128");
+    if (first_block < 0 || nblocks < 0) return set_error(FDC_ERR_INVALID_ARGUMENT, "negative block count/index");
+    if (nblocks > 0 && !counts) return set_error(FDC_ERR_INVALID_ARGUMENT, "null argument");
+    if (first_block > INT64_MAX - nblocks) return set_error(FDC_ERR_INVALID_ARGUMENT, "resampler counts: the block index does not fit 64 bits");
+    if (((__int128)(first_block + nblocks) * lout * up + (down - 1)) / down > (__int128)INT64_MAX)
+        return set_error(FDC_ERR_INVALID_ARGUMENT, "resampler counts: the output index does not fit 64 bits");
+    int64_t lo = resampler_first_output(first_block, lout, up, down);
+    for (int32_t i = 0; i < nblocks; i++) {
+        const int64_t hi = resampler_first_output(first_block + i + 1, lout, up, down);
+        counts[i] = (int32_t)(hi - lo);
+        lo = hi;
+    }
+    return FDC_OK;
+    FDC_ENTRY_END
+}
+
+static int gcd_int(int a, int b) { while (b) { const int t = a % b; a = b; b = t; } return a; }
+
+// the audio resampler: the other form of the channel audio; everything it needs is allocated here, once per size, and the stream state (the history)
+// starts anew whenever the filter changes
+int fdc_pipeline_set_audio_resampler(fdc_pipeline *p, int32_t up, int32_t down, const float *taps, int32_t ntaps, int32_t format, float scale)
+{
+    FDC_ENTRY("fdc_pipeline_set_audio_resampler")
+    if (!p) return set_error(FDC_ERR_INVALID_ARGUMENT, "null handle");
+    int kp = 0;
+    if (up) {
+        if (up < 1 || up > 64) return set_error(FDC_ERR_INVALID_ARGUMENT, "the resampler's interpolation %d is not in 1 .. 64", (int)up);
+        if (down < 1 || down > 128) return set_error(FDC_ERR_INVALID_ARGUMENT, "the resampler's decimation %d is not in 1 .. 128", (int)down);
+        const int g = gcd_int(up, down);
+        if (g != 1)
+            return set_error(FDC_ERR_INVALID_ARGUMENT, "the ratio %d / %d is not reduced, which would leave tap phases unused: give %d / %d", (int)up, (int)down,
+                             (int)up / g, (int)down / g);
+        if (ntaps < 1 || !taps) return set_error(FDC_ERR_INVALID_ARGUMENT, "the resampler's filter has at least 1 tap");
+        kp = (int)(((int64_t)ntaps + up - 1) / up);
+        if (kp > 256) return set_error(FDC_ERR_INVALID_ARGUMENT, "the resampler's filter has %d taps per phase (ceil(%d / %d)), more than 256", kp, (int)ntaps, (int)up);
+        for (int k = 0; k < ntaps; k++)
+            if (!std::isfinite(taps[k])) return set_error(FDC_ERR_INVALID_ARGUMENT, "resampler tap %d is not finite", k);
+        if (format != FDC_AUDIO_F32 && format != FDC_AUDIO_S16) return set_error(FDC_ERR_INVALID_ARGUMENT, "unknown audio format %d", (int)format);
+        if (format == FDC_AUDIO_S16 && (!std::isfinite(scale) || scale == 0.0f)) return set_error(FDC_ERR_INVALID_ARGUMENT, "the audio scale must be finite and not zero");
+    }
+    if (p->hier_filled > 0)
+        return set_error(FDC_ERR_INVALID_ARGUMENT, "a pipelined sinks batch is still inside the handle: fdc_pipeline_flush_sinks until it returns 0 first");
+    if (up && !p->demod_mode)
+        return set_error(FDC_ERR_INVALID_ARGUMENT, "the audio resampler filters the demodulated samples: switch the channel demodulation on first (fdc_pipeline_set_demod)");
+    if (up && p->pack_on)
+        return set_error(FDC_ERR_INVALID_ARGUMENT, "the audio packing packs the decimating form's cells: switch the packing off first (fdc_pipeline_set_audio_packing(p, 0))");
+    for (int c = 0; up && c < p->C; c++)
+        if ((int64_t)p->chans[(size_t)c].lout * up >= (1ll << 31))
+            return set_error(FDC_ERR_INVALID_ARGUMENT, "the %d output samples per block of channel %d times the interpolation %d reach 2^31", (int)p->chans[(size_t)c].lout, c, (int)up);
+    HIPCHK(hipSetDevice(p->cfg.device_id));
+    HIPCHK(hipStreamSynchronize(p->stream));          // (no call of the host entries is in flight; a device entry's caller orders its own stream)
+    if (!up) {
+        if (p->rs_up) {
+            p->rs_up = p->rs_down = p->rs_kp = 0; p->rs_taps.clear(); p->audio_format = FDC_AUDIO_F32; p->audio_scale = 1.0f; p->audio_row = 0;
+            p->audio_next = -1; p->aud_blocks = -1; p->audio_route.clear();
+        }
+        return FDC_OK;
+    }
+    // the columns: W_c = ceil(lout_c up / down) per channel, in channel order
+    std::vector<long long> aoff((size_t)std::max(p->C, 1), 0);
+    long long row = 0;
+    for (int c = 0; c < p->C; c++) { aoff[(size_t)c] = row; row += ((long long)p->chans[(size_t)c].lout * up + down - 1) / down; }
+    // the taps as the kernel reads them: phase-major, [up][kp], +0 behind the last
+    std::vector<float> pm((size_t)up * (size_t)kp, 0.0f);
+    for (int i = 0; i < ntaps; i++) pm[(size_t)(i % up) * (size_t)kp + (size_t)(i / up)] = taps[i];
+    // everything the feature needs, once per size: the table and the columns, the two histories, the rows of the longest call (4 bytes per element: the
+    // wider format) and their pinned twin
+    const size_t nh = (size_t)p->C * (size_t)(kp - 1), na = sizeof(float) * (size_t)p->cfg.max_blocks * (size_t)row;
+    if (pm.size() > p->d_rstaps.capacity()) HIPCHK(p->d_rstaps.reserve(pm.size(), pm.size()));
+    if (p->C > 0 && !p->d_aoff) HIPCHK(p->d_aoff.alloc((size_t)p->C));
+    for (int i = 0; i < 2; i++)
+        if (nh > p->d_ahist[i].capacity()) HIPCHK(p->d_ahist[i].reserve(nh, nh));
+    if (na > p->d_audio.capacity()) HIPCHK(p->d_audio.reserve(na, na));
+    if (na > p->pin_audio.capacity()) HIPCHK(p->pin_audio.reserve(na, na));
+    HIPCHK(hipMemcpy(p->d_rstaps, pm.data(), sizeof(float) * pm.size(), hipMemcpyHostToDevice));
+    if (p->C > 0) HIPCHK(hipMemcpy(p->d_aoff, aoff.data(), sizeof(long long) * (size_t)p->C, hipMemcpyHostToDevice));
+    // a new ratio or other taps: another filter, whose stream starts anew; a new format or scale alone keeps the history.  The rows of the last call
+    // are in the format and the width of the setting they were made with: a new ratio or format (or the other form before) leaves none to fetch
+    const bool ratio = p->rs_up == up && p->rs_down == down;
+    const bool same = ratio && p->rs_taps.size() == (size_t)ntaps && std::memcmp(p->rs_taps.data(), taps, sizeof(float) * (size_t)ntaps) == 0;
+    if (!same) p->audio_next = -1;
+    if (!ratio || p->audio_format != format) p->aud_blocks = -1;
+    p->audio_decim = 0; p->audio_taps.clear();          // the two forms replace each other
+    p->rs_up = up; p->rs_down = down; p->rs_kp = kp; p->rs_taps.assign(taps, taps + ntaps);
+    p->audio_format = format; p->audio_scale = format == FDC_AUDIO_S16 ? scale : 1.0f;
+    p->audio_row = row;
+    return FDC_OK;
+    FDC_ENTRY_END
+}
+
+int fdc_pipeline_audio_resampler_setting(const fdc_pipeline *p, int32_t *up, int32_t *down, int32_t *ntaps, int32_t *format, float *scale, float *taps,
+                                         int32_t taps_capacity)
+{
+    FDC_ENTRY("fdc_pipeline_audio_resampler_setting")
+    if (!p) return set_error(FDC_ERR_INVALID_ARGUMENT, "null handle");
+    if (up) *up = p->rs_up;
+    if (down) *down = p->rs_down;
+    if (ntaps) *ntaps = (int32_t)p->rs_taps.size();
+    if (format) *format = p->rs_up ? p->audio_format : FDC_AUDIO_F32;
+    if (scale) *scale = p->rs_up ? p->audio_scale : 1.0f;
+    if (taps && taps_capacity >= 0 && (size_t)taps_capacity >= p->rs_taps.size()) std::copy(p->rs_taps.begin(), p->rs_taps.end(), taps);
+    return FDC_OK;
+    FDC_ENTRY_END
+}
+
+int64_t fdc_pipeline_audio_first_block(const fdc_pipeline *p) { return p && fdc::pipe::audio_set(p) && p->aud_blocks >= 0 ? p->aud_first : -1; }
+
+// the resampling pass alone, on the caller's device buffers: the handle gives its channel table and the resampler's setting, nothing of its stream state
+int fdc_pipeline_audio_resampler_pass_device(const fdc_pipeline *p, const void *d_in, void *d_out, const void *d_hist_in, void *d_hist_out,
+                                             int64_t first_block, int nblocks, const void *d_mask, void *stream)
+{
+    FDC_ENTRY("fdc_pipeline_audio_resampler_pass_device")
+    if (!p) return set_error(FDC_ERR_INVALID_ARGUMENT, "null handle");
+    if (!p->rs_up) return set_error(FDC_ERR_INVALID_ARGUMENT, "the audio resampler is off (fdc_pipeline_set_audio_resampler)");
+    if (nblocks < 0 || first_block < 0) return set_error(FDC_ERR_INVALID_ARGUMENT, "negative block count/index");
+    if (nblocks == 0 || p->C <= 0) return FDC_OK;
+    if ((int64_t)nblocks * p->sum_lout * 8 > 0xFFFFF000ll)
+        return set_error(FDC_ERR_INVALID_ARGUMENT, "nblocks %d x %lld output samples per block is more than the 4 GiB one call may produce", nblocks, (long long)p->sum_lout);
+    const int K = p->rs_kp;
+    if (!d_in || !d_out || (K > 1 && !d_hist_out)) return set_error(FDC_ERR_INVALID_ARGUMENT, "null device buffer");
+    if (K > 1 && d_hist_in == d_hist_out) return set_error(FDC_ERR_INVALID_ARGUMENT, "the history is read from one buffer and written to another");
+    HIPCHK(hipSetDevice(p->cfg.device_id));
+    HIPCHK(fdc::launch_chan_resample(p->audio_format, p->rs_up, p->rs_down, K, p->audio_scale, p->d_rstaps, p->d_aoff, (long long)p->audio_row,
+                                     static_cast<const float *>(d_in), d_out, p->d_chans, K > 1 ? static_cast<const float *>(d_hist_in) : nullptr,
+                                     K > 1 ? static_cast<float *>(d_hist_out) : nullptr, p->C, nblocks, (long long)p->sum_lout, (long long)first_block,
+                                     stream ? static_cast<hipStream_t>(stream) : p->stream, static_cast<const unsigned char *>(d_mask)));
+    return FDC_OK;
+    FDC_ENTRY_END
+}
+
 // the audio packing: a setting that needs the audio and the squelch; everything it needs is allocated here, once
 int fdc_pipeline_set_audio_packing(fdc_pipeline *p, int on)
 {
@@ -871,6 +1017,8 @@ int fdc_pipeline_set_audio_packing(fdc_pipeline *p, int on)
     if (!p) return set_error(FDC_ERR_INVALID_ARGUMENT, "null handle");
     if (p->hier_filled > 0)
         return set_error(FDC_ERR_INVALID_ARGUMENT, "a pipelined sinks batch is still inside the handle: fdc_pipeline_flush_sinks until it returns 0 first");
+    if (on && p->rs_up)
+        return set_error(FDC_ERR_INVALID_ARGUMENT, "the audio resampler is on: its cells vary in length and are not packed; use the decimating form (fdc_pipeline_set_audio)");
     if (on && (!p->audio_decim || !p->squelch_on))
         return set_error(FDC_ERR_INVALID_ARGUMENT, "the audio packing packs the channel audio by the squelch's mask: switch both on first (fdc_pipeline_set_audio, fdc_pipeline_set_squelch)");
     if (on && (unsigned long long)p->cfg.max_blocks * (unsigned long long)p->audio_row >= (1ull << 32))

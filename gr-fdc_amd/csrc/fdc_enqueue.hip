@@ -282,13 +282,20 @@ static int run_post_tail(fdc_pipeline *p, const DeviceCall &call, const PostPass
     if (pp.audio) {
         // the demodulated samples are where the demodulation has just written them; the history is read from one buffer and written to the other,
         // which is the handle's behind the enqueue, for the call that goes on at the next block
-        const int K = (int)p->audio_taps.size();
-        HIPCHK(fdc::launch_chan_audio(p->audio_format, p->audio_decim, K, p->audio_scale, p->d_ataps, p->d_aoff, (long long)p->audio_row,
-                                      static_cast<const float *>(d_out), pp.audio, p->d_chans, pp.audio_cont && K > 1 ? p->d_ahist[p->ahist_cur].get() : nullptr,
-                                      K > 1 ? p->d_ahist[p->ahist_cur ^ 1].get() : nullptr, p->C, nblocks, (long long)p->sum_lout, call.stream, pp.squelch,
-                                      pp.pack_off));
+        // (the resampler in the decimating FIR's place: the same history, of Kp - 1 samples, and the call's first block, which sets its phase and counts)
+        const int K = p->rs_up ? p->rs_kp : (int)p->audio_taps.size();
+        if (p->rs_up)
+            HIPCHK(fdc::launch_chan_resample(p->audio_format, p->rs_up, p->rs_down, K, p->audio_scale, p->d_rstaps, p->d_aoff, (long long)p->audio_row,
+                                             static_cast<const float *>(d_out), pp.audio, p->d_chans,
+                                             pp.audio_cont && K > 1 ? p->d_ahist[p->ahist_cur].get() : nullptr, K > 1 ? p->d_ahist[p->ahist_cur ^ 1].get() : nullptr,
+                                             p->C, nblocks, (long long)p->sum_lout, (long long)first_block, call.stream, pp.squelch));
+        else
+            HIPCHK(fdc::launch_chan_audio(p->audio_format, p->audio_decim, K, p->audio_scale, p->d_ataps, p->d_aoff, (long long)p->audio_row,
+                                          static_cast<const float *>(d_out), pp.audio, p->d_chans,
+                                          pp.audio_cont && K > 1 ? p->d_ahist[p->ahist_cur].get() : nullptr, K > 1 ? p->d_ahist[p->ahist_cur ^ 1].get() : nullptr,
+                                          p->C, nblocks, (long long)p->sum_lout, call.stream, pp.squelch, pp.pack_off));
         p->ahist_cur ^= 1; p->audio_next = first_block + nblocks;
-        p->audio_route = pp.pack_off ? "pass, gated, packed" : pp.squelch ? "pass, gated" : "pass";
+        p->audio_route = p->rs_up ? (pp.squelch ? "resampled, gated" : "resampled") : pp.pack_off ? "pass, gated, packed" : pp.squelch ? "pass, gated" : "pass";
     }
     if (pp.tones && !pp.tone_dec) RCCHK(tones());
     if (pp.narrow_tail) HIPCHK(fdc::launch_complex_to_iq(call.ofmt, call.oscale, call.fout, d_out, (size_t)nblocks * p->sum_lout, call.stream));
@@ -492,9 +499,9 @@ void lag1_written(fdc_pipeline *p, int nblocks, hipStream_t stream, bool host)
     p->lag_blocks = nblocks; p->lag_stream = stream; p->lag_host = host;
 }
 
-void audio_written(fdc_pipeline *p, int nblocks, hipStream_t stream, bool host)
+void audio_written(fdc_pipeline *p, int64_t first_block, int nblocks, hipStream_t stream, bool host)
 {
-    p->aud_blocks = nblocks; p->aud_stream = stream; p->aud_host = host;
+    p->aud_first = first_block; p->aud_blocks = nblocks; p->aud_stream = stream; p->aud_host = host;
 }
 
 void squelch_written(fdc_pipeline *p, int nblocks, hipStream_t stream, bool host)
@@ -559,7 +566,7 @@ static int process_device_oq(fdc_pipeline *p, DeviceCall &call, const void *d_ri
     if (rc == FDC_OK && ofmt && nblocks > 0) p->oq_route = route(ofmt, call.ofused, "narrowed");
     if (rc == FDC_OK && lev) levels_written(p, nblocks, call.stream, false);
     if (rc == FDC_OK && lag) lag1_written(p, nblocks, call.stream, false);
-    if (rc == FDC_OK && call.audio) audio_written(p, nblocks, call.stream, false);
+    if (rc == FDC_OK && call.audio) audio_written(p, first_block, nblocks, call.stream, false);
     if (rc == FDC_OK && call.squelch) squelch_written(p, nblocks, call.stream, false);
     if (rc == FDC_OK && call.tones) tones_written(p, nblocks, call.tones_frames, call.stream, false);
     if (rc == FDC_OK && call.tone_dec) tone_squelch_written(p, nblocks, call.tones_frames, call.stream, false);

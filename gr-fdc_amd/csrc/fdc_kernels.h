@@ -280,6 +280,16 @@ hipError_t launch_chan_audio(int format, int decim, int ntaps, float scale, cons
 // forms, which store the outputs of an open (block, channel) at out[pack_off[block][channel] + i] and those of a closed one nowhere; out is then element
 // 0 of the packed buffer, and exactly the elements the offsets count are written
 
+// Audio resampler (fdc_pipeline_set_audio_resampler): the polyphase FIR with interpolation `up` and decimation `down` over the same samples, a[n] = sum
+// over k = 0 .. kp - 1 of h[k up + (n down mod up)] d[(n down div up) - k] with n and the sample index counted from the stream's block 0 (the call
+// starts at block first_block), in launch_chan_audio's arithmetic.  taps_pm: the taps phase-major, [up][kp] (taps_pm[ph kp + k] = h[k up + ph], +0
+// behind the last).  out: row 0 of the call's block-major matrix [nb_call][row]; channel c owns the ceil(lout_c up / down) columns from aoff[c] on, a
+// cell holds the outputs whose newest sample lies in its block, and one zero behind them where it owns a column less.  The histories are [nchan][kp - 1]
+// float, as launch_chan_audio's; gate likewise (the gated forms).  Every element of the matrix is written, and nothing else
+hipError_t launch_chan_resample(int format, int up, int down, int kp, float scale, const float *taps_pm, const long long *aoff, long long row,
+                                const float *in, void *out, const ChanDev *chans, const float *hist_in, float *hist_out, int nchan, int nb_call,
+                                long long sum_lout, long long first_block, hipStream_t s, const unsigned char *gate = nullptr);
+
 // Packed audio (fdc_pipeline_set_audio_packing): the offsets of the call's cells in the packed buffer.  mask: row 0 of the call's mask ([nb_call][nchan]
 // bytes); off ([nb_call][nchan] words) receives *base_in (null: 0) + the audio samples (lout_c / decim each) of all open cells in front of (block,
 // channel), block-major; total (one word, which may be base_in's) receives *base_in + those of all open cells.  Three launches on s

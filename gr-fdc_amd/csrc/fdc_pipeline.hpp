@@ -219,6 +219,14 @@ struct fdc_pipeline {
     bool aud_host = false;
     hipStream_t aud_stream = nullptr;
     std::string audio_route;     // the last call with the setting on ran the audio pass (fdc_pipeline_describe)
+    int64_t aud_first = -1;      // the absolute index of row 0 of that call's audio (fdc_pipeline_audio_first_block)
+    // audio resampler (fdc_pipeline_set_audio_resampler): the other form of the channel audio, which replaces the decimating one and shares its format,
+    // scale, columns (audio_row, d_aoff: W_c = ceil(lout_c up / down) per channel), histories (Kp - 1 per channel), audio_next, rows and their
+    // bookkeeping.  rs_up: 0 = off; rs_taps: the prototype taps in force, rs_kp = ceil(ntaps / up) taps per phase, d_rstaps the table the kernel reads,
+    // phase-major [up][Kp].  All of it is allocated by the setter, once per size.
+    int rs_up = 0, rs_down = 0, rs_kp = 0;
+    std::vector<float> rs_taps;
+    fdc::DevBuf<float> d_rstaps;
     // channel squelch (fdc_pipeline_set_squelch): a setting that needs the levels.  sq_open / sq_close: the C thresholds in force, d_sqthr[0] / [1] their
     // device tables; sq_hang the hang count.  d_sqstate: the stream state, (open, h) of every channel behind the last call, two buffers of C int pairs: a
     // call reads d_sqstate[sqstate_cur] where it continues the stream (its first_block is squelch_next; -1: every channel starts closed) and its kernel
@@ -388,7 +396,8 @@ inline size_t oq_bytes(int ofmt) { return oq_demod(ofmt) ? sizeof(float) : fdc::
 inline int out_code(const fdc_pipeline *p) { return p->demod_mode && p->C > 0 ? kOqDemod + p->demod_mode : p->out_form; }
 
 // channel audio: whether the handle's next call runs the pass, and the bytes of one audio element
-inline bool audio_on(const fdc_pipeline *p) { return p->audio_decim > 0 && p->demod_mode && p->C > 0; }
+inline bool audio_set(const fdc_pipeline *p) { return p->audio_decim > 0 || p->rs_up > 0; }     // either form of the audio is switched on
+inline bool audio_on(const fdc_pipeline *p) { return audio_set(p) && p->demod_mode && p->C > 0; }
 inline size_t audio_bytes(const fdc_pipeline *p) { return p->audio_format == FDC_AUDIO_S16 ? sizeof(int16_t) : sizeof(float); }
 // ... and where the rows from block b0 of a host call on go in the handle's buffer
 inline void *audio_rows(const fdc_pipeline *p, size_t b0) { return audio_on(p) ? p->d_audio.get() + audio_bytes(p) * b0 * (size_t)p->audio_row : nullptr; }
@@ -451,7 +460,7 @@ int channels_wide(fdc_pipeline *p, const float2 *spec, float2 *d_out, const int3
 int check_iq_form(int32_t format, float scale);
 void levels_written(fdc_pipeline *p, int nblocks, hipStream_t stream, bool host);   // a call with levels on succeeded: what fdc_pipeline_levels hands out
 void lag1_written(fdc_pipeline *p, int nblocks, hipStream_t stream, bool host);     // the same of the lag-1 correlation (fdc_pipeline_lag1)
-void audio_written(fdc_pipeline *p, int nblocks, hipStream_t stream, bool host);    // ... and of the channel audio (fdc_pipeline_audio)
+void audio_written(fdc_pipeline *p, int64_t first_block, int nblocks, hipStream_t stream, bool host);    // ... and of the channel audio (fdc_pipeline_audio)
 void squelch_written(fdc_pipeline *p, int nblocks, hipStream_t stream, bool host);  // ... and of the channel squelch (fdc_pipeline_squelch)
 void tones_written(fdc_pipeline *p, int nblocks, int nframes, hipStream_t stream, bool host);   // ... and of the channel tones (fdc_pipeline_tones)
 void tone_squelch_written(fdc_pipeline *p, int nblocks, int nframes, hipStream_t stream, bool host);   // ... and of the tone squelch (fdc_pipeline_tone_squelch)

@@ -282,7 +282,7 @@ static int pipeline_work_impl(fdc_pipeline *p, DeviceCall call, const void *in, 
         RCCHK(packed_home(p, s));
         if (p->levels_on) levels_written(p, nblocks, s, true);
     if (p->lag1_on) lag1_written(p, nblocks, s, true);
-        if (audio) audio_written(p, nblocks, s, true);
+        if (audio) audio_written(p, p->blockcount, nblocks, s, true);
         if (squelch_rows(p, 0)) squelch_written(p, nblocks, s, true);
         if (tones_on(p)) tones_written(p, nblocks, tframes, s, true);
         if (tone_dec_rows(p, 0)) tone_squelch_written(p, nblocks, tframes, s, true);
@@ -353,7 +353,7 @@ static int pipeline_work_impl(fdc_pipeline *p, DeviceCall call, const void *in, 
     RCCHK(packed_home(p, s));
     if (p->levels_on) levels_written(p, nblocks, s, true);
     if (p->lag1_on) lag1_written(p, nblocks, s, true);
-    if (audio) audio_written(p, nblocks, s, true);
+    if (audio) audio_written(p, p->blockcount, nblocks, s, true);
     if (squelch_rows(p, 0)) squelch_written(p, nblocks, s, true);
     if (tones_on(p)) tones_written(p, nblocks, tframes, s, true);
     if (tone_dec_rows(p, 0)) tone_squelch_written(p, nblocks, tframes, s, true);
@@ -471,7 +471,7 @@ static int pipeline_work_real_impl(fdc_pipeline *p, const void *in, int nblocks,
     RCCHK(packed_home(p, s));
     if (p->levels_on) levels_written(p, nblocks, s, true);
     if (p->lag1_on) lag1_written(p, nblocks, s, true);
-    if (call.audio) audio_written(p, nblocks, s, true);
+    if (call.audio) audio_written(p, p->blockcount, nblocks, s, true);
     if (call.squelch) squelch_written(p, nblocks, s, true);
     if (call.tones) tones_written(p, nblocks, call.tones_frames, s, true);
     if (call.tone_dec) tone_squelch_written(p, nblocks, call.tones_frames, s, true);

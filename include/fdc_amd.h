@@ -406,6 +406,54 @@ void *fdc_pipeline_audio_device(fdc_pipeline *p);
 int fdc_pipeline_audio_pass_device(const fdc_pipeline *p, const void *d_in, void *d_out, const void *d_hist_in, void *d_hist_out, int nblocks,
                                    void *stream);
 
+/* AUDIO RESAMPLER: the second form of the channel audio, a polyphase FIR with interpolation L = up and decimation M = down behind the demodulator,
+ * which takes the channel rate fs l / N to a chosen audio rate (25 kHz to 8 kHz: 8 / 25; to 48 kHz: 48 / 25).  The two forms replace each other.
+ * tests/resample_model.py is the definition.  With d_c[t] the float32 stream the demodulation gives for channel c, t the ABSOLUTE sample index (sample 0
+ * is the first of block 0, block m holds samples m lout_c .. (m + 1) lout_c - 1), h[0 .. ntaps-1] the prototype taps, Kp = ceil(ntaps / L) and h
+ * padded with +0 to L Kp entries, output n of the stream (n = 0, 1, ...; it stands at input time n M / L) is
+ *
+ *     a_c[n] = sum over k = 0 .. Kp-1 of h[k L + (n M mod L)] d_c[floor(n M / L) - k]
+ *
+ * in float32, k ascending from acc = +0, every product and every sum rounded on its own (fdc_pipeline_set_audio's rule; the padded zero taps are part
+ * of the sum): upsample by L, filter with h, keep every M-th sample, started at sample 0.  With L = 1 it is fdc_pipeline_set_audio's sum with D = M.
+ * FDC_AUDIO_S16 narrows as there.
+ * THE LAYOUT: output n belongs to block floor(floor(n M / L) / lout_c).  Block m owns the outputs ceil(m lout_c L / M) .. ceil((m + 1) lout_c L / M) - 1:
+ * cnt_c(m) of them, which is W_c or W_c - 1 with W_c = ceil(lout_c L / M) and depends on the ABSOLUTE block index alone (fdc_audio_resampler_counts).
+ * The audio of a call is the block-major matrix [nblocks][A] with A = sum of the W_c; channel c owns the W_c columns from aoff_c = sum over i < c of
+ * W_i on; cell (m, c) holds its cnt_c outputs in order, and where cnt_c = W_c - 1 one pad element of zero bits follows.  The pass writes every element.
+ * THE HISTORY is fdc_pipeline_set_audio's with K = Kp: Kp - 1 values of d per channel stand in front of a call that continues the stream, zeros
+ * otherwise; phase and counts come from the absolute index of the call's first block either way, so the calls of a continuing stream concatenate to
+ * the stream's bits however it is cut.  THE GATE is the decimating form's: with the channel squelch on (with or without the tone squelch) every element
+ * of a closed (block, channel) cell is zero bits and the history runs on over the ungated stream.
+ *   fdc_pipeline_set_audio_resampler  up 0 switches it off.  Otherwise up 1 .. 64, down 1 .. 128, gcd(up, down) = 1 (a ratio that is not reduced
+ *                               would leave tap phases unused), ntaps >= 1 finite taps with ceil(ntaps / up) <= 256; format and scale as
+ *                               fdc_pipeline_set_audio.  FDC_ERR_INVALID_ARGUMENT, the previous setting staying in force: those, while the
+ *                               demodulation is off, while a pipelined sinks batch is inside the handle, while the audio packing is on, and where
+ *                               lout_c up reaches 2^31.  A successful call switches the decimating form off, and a successful
+ *                               fdc_pipeline_set_audio(decim > 0) switches this one off; fdc_pipeline_set_audio(decim 0) switches off whichever is
+ *                               on.  While it is on fdc_pipeline_set_audio_packing(1), fdc_pipeline_set_demod(OFF) and
+ *                               fdc_pipeline_audio_pass_device are refused and fdc_pipeline_audio_setting reports decim 0.  A SETTING: it survives
+ *                               fdc_pipeline_reset, allocates everything once per size and nothing on any entry.  A new ratio or other taps restart
+ *                               the stream; a new format or scale alone keeps the history; a new ratio or format leaves no rows to fetch.
+ *                               All offsets into the matrix are 64-bit: max_blocks A is bounded by memory only.
+ *   fdc_pipeline_audio_resampler_setting  the setting in force (up 0: off); any pointer may be NULL; taps receives ntaps floats only where
+ *                               taps_capacity >= ntaps.
+ *   fdc_pipeline_audio_first_block  the absolute index of row 0 of the audio the handle holds (either form), -1 where there is none.
+ *   fdc_audio_resampler_counts  cnt(first_block + i) for i = 0 .. nblocks-1, of a channel of lout samples per block: a pure host function.
+ * fdc_pipeline_audio_row (A), fdc_pipeline_audio and fdc_pipeline_audio_device serve the matrix above.  fdc_pipeline_describe: "audio: resampled"
+ * or "audio: resampled, gated" after a call that ran it.  With the setting off every entry launches exactly what it launched before. */
+int fdc_pipeline_set_audio_resampler(fdc_pipeline *p, int32_t up, int32_t down, const float *taps, int32_t ntaps, int32_t format, float scale);
+int fdc_pipeline_audio_resampler_setting(const fdc_pipeline *p, int32_t *up, int32_t *down, int32_t *ntaps, int32_t *format, float *scale, float *taps,
+                                         int32_t taps_capacity);
+int64_t fdc_pipeline_audio_first_block(const fdc_pipeline *p);
+int fdc_audio_resampler_counts(int32_t lout, int32_t up, int32_t down, int64_t first_block, int32_t nblocks, int32_t *counts);
+/* The resampling pass alone, on device buffers of the caller, with the handle's channel table and resampler setting (which must be on) and nothing
+ * of its stream state: d_in as fdc_pipeline_audio_pass_device's, d_out exactly nblocks * A elements, the histories exactly C (Kp - 1) floats
+ * (d_hist_in NULL: zeros; d_hist_out NULL only where Kp = 1), first_block the absolute index of the call's first block, d_mask NULL or [nblocks][C]
+ * bytes of the caller's (the gated form).  Enqueued on `stream` (NULL: the handle's). */
+int fdc_pipeline_audio_resampler_pass_device(const fdc_pipeline *p, const void *d_in, void *d_out, const void *d_hist_in, void *d_hist_out,
+                                             int64_t first_block, int nblocks, const void *d_mask, void *stream);
+
 /* CHANNEL SQUELCH: per channel a carrier-operated squelch on the block powers the levels give, decided on the device, with hysteresis and a hang time;
  * with the channel audio on it gates the audio.  The setting: per-channel float32 thresholds open_c >= close_c >= 0, finite, and one hang count of
  * blocks, 0 .. 65535.  The state of a channel is (open in {0, 1}, h in [0, hang]) and starts as (0, 0).  For block m of the stream, in order:
